@@ -88,7 +88,14 @@ def parse():
     p.add_argument('--prewarm', type=int, default=PREWARM_STEPS, help='untimed world steps before --warmup (fixed: every box times the same world steps)')
     p.add_argument('--step-events-in-timed-region', action='store_true', help='record the per-step HIP events inside the timed region (rounds 1-3 did; default: in a second, untimed pass of K steps)')
     p.add_argument('--no-extras', action='store_true', help='skip the side measurements (sync=True, reference-default slot count)')
-    return p.parse_args()
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write what the last timed step handed its caller to DIR/<name>.npy (see sample_outputs); single-GPU path only')
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error('--steps must be at least 1')
+    if args.dump_outputs and (args.gpus > 1 or args.force_dist or args.replicas > 0):
+        p.error('--dump-outputs covers the single-GPU step (not --gpus > 1, --force-dist or --replicas)')
+    return args
 
 
 def contract_bytes(C, K, bf=4):
@@ -376,6 +383,40 @@ def other_cpu_baselines(seed):
     return out
 
 
+DUMP_CELLS, DUMP_SLOTS = 1 << 20, 1 << 19      # sample sizes of --dump-outputs: 12 + 16 + 6 MiB at most
+
+
+def dump_index(n, k, device):
+    """min(n, k) of the positions 0..n-1, ascending: all of them when n <= k, else a sample drawn with numpy's
+    default_rng(0) — the same positions in every run with the same n."""
+    import numpy as np
+    import torch
+    idx = np.arange(n) if n <= k else np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+    return torch.from_numpy(idx).to(device)
+
+
+def sample_outputs(env, action):
+    """What a caller of `obs, result, ... = env.step(agent.forward(obs))` holds after the step, read on the device and
+    downloaded as a fixed sample (dump_index) before anything else runs on the world:
+      medium (3, cells) float32  — channels agents / env_food / chem1 of the (W, H) planes at flat cells x·H + y
+      agents (4, slots) float64  — x, y (exact: Q0.32), alive, agent_food of the sampled slots, slot order
+      action (3, slots) float32  — dx, dy, deposit1 of the same slots (re-derived here if the step kept it in registers)
+    main() adds result (2,) float64 — the step's reward and num_agents."""
+    import torch
+    cells = dump_index(env.medium.W * env.medium.H, DUMP_CELLS, env.device)
+    slots = dump_index(env.agents.N, DUMP_SLOTS, env.device)
+    return {'medium': torch.stack([env.medium.sel(c).reshape(-1)[cells].float() for c in env.medium.channels]).cpu().numpy(),
+            'agents': torch.stack([env.agents.sel(c)[slots].double() for c in env.agents.channels]).cpu().numpy(),
+            'action': torch.stack([action.sel(c)[slots].float() for c in action.channels]).cpu().numpy()}
+
+
+def dump_outputs(out_dir, arrays):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f'{name}.npy'), a)
+
+
 def bench_replicas(args, device, agent_kw):
     """`--replicas R`: R worlds of --size stepped by one launch pair per step (die_forward_env_step_batch), against the
     same R worlds stepped one Env at a time.  Not the contract metric: its own line, value = replica-steps per second."""
@@ -524,12 +565,16 @@ def main():
         if inline:
             ev[0].record()
         for i in range(args.steps):
-            obs, res, *_ = env.step(agent.forward(obs))
+            action = agent.forward(obs)
+            obs, res, *_ = env.step(action)
             if inline:
                 ev[i + 1].record()
         torch.cuda.synchronize()
         barrier()
         dt = time.perf_counter() - t0
+        # (the last step's action is held only until here: an action still referenced when the next step starts is filled in first)
+        outputs = sample_outputs(env, action) if args.dump_outputs else None
+        del action
         if not inline:
             # the per-step distribution (step_ms) from a SECOND pass of K steps, outside the timed region: an event after every
             # step is a marker packet between the step's last kernel and the next step's first one — it costs the loop ≈ 2 % that a
@@ -542,11 +587,15 @@ def main():
             torch.cuda.synchronize()
             res = last
         per_step = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps))
-        return dt, res, per_step, n_pre
+        return dt, res, per_step, n_pre, outputs
 
-    dt, res, per_step, n_pre = timed_run(env, agent)
+    dt, res, per_step, n_pre, outputs = timed_run(env, agent)
     last_reward, last_alive = env.read_result(res)
     env.check()                # (the tile-binned step's sticky error word: a loop that reads nothing back has to ask)
+    if outputs is not None:
+        import numpy as np
+        outputs['result'] = np.array([last_reward, last_alive], dtype=np.float64)
+        dump_outputs(args.dump_outputs, outputs)
     K = env.agents.N
     if dist_on:
         t = torch.tensor([dt], dtype=torch.float64, device=device)

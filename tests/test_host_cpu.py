@@ -176,3 +176,38 @@ def test_step_bound_of_a_gradient_agent_with_momentum(built_lib):
         b = B(i, ns)
         assert b >= n_max and (1 - i) + i * b + ns * n_max <= b * (1 + 1e-6)
     assert math.isinf(B(1.0, 0.0)) and math.isinf(B(1.5, 0.1))
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_exact(tmp_path):
+    """bench.py --dump-outputs: the sampled arrays are the caller's arrays (slot order, exact Q0.32 coordinates) at positions
+    that depend on the array sizes alone, so two builds' dumps compare output for output."""
+    import types
+    import torch
+    import bench
+    from die_amd.device_array import DeviceAction, DeviceAgents, DeviceMedium
+    g = torch.Generator().manual_seed(3)
+    for W, H, N in ((24, 40, 300), (1100, 1000, 600000)):        # all of it / a sample of both the cells and the slots
+        m = DeviceMedium((W, H), 'cpu')
+        m.food.uniform_(generator=g)
+        m.chem.normal_(generator=g)
+        a = DeviceAgents(N, 'cpu')
+        a.x.random_(generator=g)
+        a.y.random_(generator=g)
+        a.alive.fill_(1)
+        a.agent_food.uniform_(generator=g)
+        a.slot = torch.randperm(N, generator=g).to(torch.int32)
+        act = DeviceAction(N, 'cpu', a.slot)
+        act.data.normal_(generator=g)
+        env = types.SimpleNamespace(medium=m, agents=a, device=torch.device('cpu'))
+        out = bench.sample_outputs(env, act)
+        cells = bench.dump_index(W * H, bench.DUMP_CELLS, 'cpu').numpy()
+        slots = bench.dump_index(N, bench.DUMP_SLOTS, 'cpu').numpy()
+        assert len(cells) == min(W * H, bench.DUMP_CELLS) and len(slots) == min(N, bench.DUMP_SLOTS)
+        assert np.array_equal(cells, bench.dump_index(W * H, bench.DUMP_CELLS, 'cpu').numpy())
+        assert out['medium'].dtype == np.float32 and out['action'].dtype == np.float32 and out['agents'].dtype == np.float64
+        assert np.array_equal(out['medium'], m.to_numpy().reshape(3, -1)[:, cells])
+        assert np.array_equal(out['agents'], a.to_numpy()[:, slots])
+        assert np.array_equal(out['action'], act.to_numpy()[:, slots])
+        bench.dump_outputs(str(tmp_path / f'd{W}'), out)
+        assert np.array_equal(np.load(tmp_path / f'd{W}' / 'agents.npy'), out['agents'])
+    assert sum(v.nbytes for v in out.values()) <= 64 << 20
