@@ -606,17 +606,25 @@ def applied(action):
     return a
 
 
-def _binned_steps_against_the_oracle(die, medium, agents, dyn, tile, agent_kind, kw, n_steps, f16=False, form='two launches', seed=3):
+def _binned_steps_against_the_oracle(die, medium, agents, dyn, tile, agent_kind, kw, n_steps, f16=False, form='two launches', seed=3,
+                                     dir0=None, prev_grad=None, k1_threads=0, calls=0, callback=None):
     """`n_steps` × `env.step(agent.forward(obs))` on the tile-binned path, every step teacher-forced against the oracle:
     the oracle starts each step from the device's state (downloaded), computes ITS forward — compared with the action the
     device read back —, then steps with the device's action (so that a decision that sits on a float threshold cannot
     cascade) and its new state is compared with the device's: coordinates / cells / ownership / alive bit-exact, fields,
-    agent_food, reward within 1e-5 relative (fp16 fields: within their 11-bit significand)."""
+    agent_food, reward within 1e-5 relative (fp16 fields: within their 11-bit significand).
+
+    `dir0` / `prev_grad`: the initial heading (and GradientAgent momentum) instead of the oracle agent's; `k1_threads`: the agent
+    kernel's workgroup size (die_pic.k1_threads, 0: the library's); `calls`: the agents' step counter at the first step (the
+    Philox draws and the order table's rebuilds follow it); `callback(step, env, agent, when)`: called with when = 'before' and
+    'after' around every device step (tests/test_gpu_crowds.py reads the device's bookkeeping there)."""
     N = agents.shape[1]
     W, H = medium.shape[1:]
     env = die.Env.from_numpy(medium, agents, dyn, sort_every=0, field_dtype=torch.float16 if f16 else torch.float32)
     env._pic_tile = tile
     env._pic_fused = form != 'three launches'
+    if k1_threads:
+        env._pic_k1_threads = k1_threads
     rd = ref_dyn(dyn)
     for f in ('rate_feed', 'rate_decay_chem', 'diffuse_sigma'):       # the C struct carries them as f32
         setattr(rd, f, float(np.float32(getattr(rd, f))))
@@ -624,12 +632,15 @@ def _binned_steps_against_the_oracle(die, medium, agents, dyn, tile, agent_kind,
         dev, ref = die.PhysarumAgent(max_agents=N, seed=seed, **kw), R.RefPhysarumAgent(N, seed=seed, **kw)
     else:
         dev, ref = die.GradientAgent(max_agents=N, seed=seed, **kw), R.RefGradientAgent(N, seed=seed, **kw)
-    dir0 = f32(ref._direction_rads)
+    dir0 = f32(ref._direction_rads if dir0 is None else dir0)
     momentum = kw.get('inertia', 0) != 0
-    dev.set_state(dir0, prev_grad=f32(ref._prev_grad) if momentum else None)
+    dev.set_state(dir0, prev_grad=f32(ref._prev_grad if prev_grad is None else prev_grad) if momentum else None)
+    dev._calls = ref._calls = calls
     frtol, fatol = (1e-3, 1e-4) if f16 else (RTOL, 1e-7)
     obs = env._get_current_obs
     for step in range(n_steps):
+        if callback is not None:
+            callback(step, env, dev, 'before')
         m0, a0, d0 = env.medium.to_numpy(), env.agents.to_numpy(), dev.direction_rads_numpy()
         ref._direction_rads = d0.copy()
         if momentum:
@@ -643,6 +654,10 @@ def _binned_steps_against_the_oracle(die, medium, agents, dyn, tile, agent_kind,
             assert bad_pg.mean() < 2e-3, f'step {step}: _prev_grad differs for {bad_pg.sum()} of {N} slots'
         assert env._pic is not None and env._pic.held is not None and env._pic.held[0] is env.agents.x, 'the tile-binned step did not run'
         assert env._pic.two_launch(env, dev) == (form != 'three launches')
+        if k1_threads:
+            assert env._pic.k1_threads == k1_threads
+        if callback is not None:
+            callback(step, env, dev, 'after')
         got_action = action.to_numpy()
         # atol: sin/cos of a heading at a zero crossing carry the f32 angle rounding (~2e-7 rad) x scale
         bad = ~np.isclose(got_action, want_action, rtol=max(RTOL, frtol), atol=1e-6 * abs(kw['scale']) + (1e-3 if f16 else 0)).all(axis=0)
@@ -792,7 +807,7 @@ def test_configs2_full_size_teacher_forced_step_vs_oracle(die):
 @pytest.mark.parametrize('form', ['two launches', 'three launches'])
 def test_tile_binned_step_with_a_crowd_crossing_one_border(die, form):
     """Several thousand agents stand in a strip two cells wide along one tile border, all heading across it: more arrivals
-    into one tile than the agent kernel's arrival list holds per round (PIC_LIST_CAP = 1024: it must take a second round,
+    into one tile than the agent kernel's arrival list holds per round (PIC_LIST_CAP = 512: it must take more rounds,
     never overflow — the fault of a round-2 experiment build with a shorter list), and more border agents than a rim list
     of the two-launch form holds (the field kernel must fall back to scanning the segments).  Bit for bit the classic step."""
     W, H, tile = 192, 192, (6, 6)
