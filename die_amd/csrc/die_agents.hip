@@ -54,9 +54,7 @@ static int agent_grid(int64_t N) {
 
 static int fwd_grid(int64_t N) {
     int64_t g = (N + DIE_BLOCK - 1) / DIE_BLOCK;
-#ifndef DIE_FWD_GRID_CAP
 #define DIE_FWD_GRID_CAP (256 * 16)
-#endif
     const int64_t cap = DIE_FWD_GRID_CAP;
     return (int)(g < cap ? (g > 0 ? g : 1) : cap);
 }

@@ -14,16 +14,12 @@
 // "Last writer wins" of the fancy-index assignment at :211 is an atomicMax on the slot id.
 #include "die_forward.h"
 
-#ifndef DIE_MAX_PARTIALS
 #define DIE_MAX_PARTIALS 8192
-#endif
 // workgroup size of the per-agent step kernels (claim pass, dead-slot pass).  Swept on MI355X at 2.5 M agents, step time in
 // µs: 192: 211.5, 256: 206.6, 320: 199.9, 384: 203.4, 448: 204.5, 512: 202.8, 640: 208.0, 768: 201.8 — 5 waves per
 // workgroup it is (one agent per thread under the 8192-workgroup cap, and 20 instead of 24 waves per CU: the kernel
 // is bound by L1 misses in flight, fewer waves thrash the L1 less).
-#ifndef DIE_STEP_BLOCK
 #define DIE_STEP_BLOCK 320
-#endif
 
 struct StepArgs {
     die_geo g;
@@ -340,13 +336,9 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_diffuse(DiffuseArgs a) {
 // winner's deposit before filtering (core/env.py:211) and, for the cells it owns, performs the
 // feeding update food −= rate·food on occupied cells (:222-228): the per-cell scatter of the step
 // becomes two coalesced streams.
-#ifndef DIF_ROWS
 #define DIF_ROWS 16     // rows per wave: 16 → ≈17 waves per CU at 4096² (32: 87 µs, 16: 75 µs, 8: 86 µs for the fused sweep)
-#endif
 #define DIF_WCOLS 248          // output columns per wave
-#ifndef DIF_BLOCK
 #define DIF_BLOCK 128          // waves are independent (no LDS, no barrier): small workgroups balance better
-#endif
 
 struct RowsArgs {
     const void* src;
@@ -665,9 +657,7 @@ extern "C" int die_diffuse_decay_mode(const void* src, void* dst, int32_t W, int
 // ---- step driver ----------------------------------------------------------------------
 static int step_grid(int64_t N) {
     int64_t g = (N + DIE_STEP_BLOCK - 1) / DIE_STEP_BLOCK;
-#ifndef DIE_STEP_GRID_CAP
 #define DIE_STEP_GRID_CAP 8192
-#endif
     const int64_t cap = DIE_STEP_GRID_CAP;   // ≤ DIE_MAX_PARTIALS partial sums for k_reduce (8192 measured 3 % faster than 2048)
     return (int)(g < cap ? (g > 0 ? g : 1) : cap);
 }

@@ -22,7 +22,7 @@
 //   K2        k_pic_resolve, one workgroup per tile over the same kind of set in the new layout: 64-bit LDS atomicMax of
 //             (slot + 1) << 32 | deposit bits per cell, then the tile of the deposit plane is written with coalesced
 //             16-byte stores: the winner's deposit, or DIE_DEP_EMPTY, and the food of the occupied cells is reduced
-//             (food −= rate·food, core/env.py:222-228; PIC_K2_FEED).  An extra workgroup turns (s, inc) into the segment
+//             (food −= rate·food, core/env.py:222-228).  An extra workgroup turns (s, inc) into the segment
 //             sizes and offsets of the next step (exclusive scan over the tiles).
 //   sweep     k_diffuse_rows<T, R, 2, true> (die_env.hip): deposit + gaussian + decay, reading 4 bytes per cell of deposit
 //             plane instead of 8 bytes of claims (and no food at all when K2 has done the feeding); an extra workgroup
@@ -34,110 +34,49 @@
 #include "die_forward.h"
 #include <stdlib.h>
 
-// (PIC_K2_FEED, PIC_K1_BLOCK, PIC_K2_BLOCK, PIC_STAGE_FOOD, PIC_K1_MINW: knobs of the A/B builds of scratch/build_variant.sh;
-// the values below are the measured best: LABBOOK.md, rounds 2–5)
-#ifndef PIC_K2_FEED
-#define PIC_K2_FEED 1
-#endif
-// A/B knobs (scratch/build_variant.sh).  PIC_NT: which streams of the two step kernels are non-temporal accesses (`nt`:
-// the line is first in line for eviction from L2) — one bit per stream, see the pic_ld / pic_st call sites:
-//   0 agent kernel: the six agent streams it reads      1 … the agent_food / heading streams it writes
-//   2 … x, y, slot, deposit, rim lists it writes         3 field kernel: agent streams and rim lists it reads
-//   4 field kernel: food tile read   5 agent kernel: food tile read   6 field kernel: chem store   7 agent kernel: chem window
-//   8 field kernel: chem window      9 field kernel: food store
-// PIC_PRIO = s_setprio around the phases that issue the long loads.
-#ifndef PIC_NT
-#define PIC_NT 0      // (3 buys the field kernel 2.5 µs at 4096² fp32 and costs the agent kernel 3–5 % at 8192² and with fp16 planes: LABBOOK.md, round 3)
-#endif
 typedef uint32_t pic_u4v __attribute__((ext_vector_type(4)));
 typedef uint32_t pic_u2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ constexpr bool pic_nt(int bit) { return bit >= 0 && ((PIC_NT >> bit) & 1); }
-template <int BIT, class V> __device__ __forceinline__ V pic_ld(const V* a) {
-    if constexpr (pic_nt(BIT)) return __builtin_nontemporal_load(a); else return *a;
-}
-template <int BIT, class V> __device__ __forceinline__ void pic_st(V* a, V v) {
-    if constexpr (pic_nt(BIT)) __builtin_nontemporal_store(v, a); else *a = v;
-}
-template <int BIT> __device__ __forceinline__ uint4 pic_ld4(const void* a) {
-    if constexpr (pic_nt(BIT)) { const pic_u4v t = __builtin_nontemporal_load((const pic_u4v*)a); return make_uint4(t.x, t.y, t.z, t.w); }
-    else return *(const uint4*)a;
-}
-template <int BIT> __device__ __forceinline__ void pic_st4(void* a, uint4 v) {
-    if constexpr (pic_nt(BIT)) { pic_u4v t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w; __builtin_nontemporal_store(t, (pic_u4v*)a); }
-    else *(uint4*)a = v;
-}
-template <int BIT> __device__ __forceinline__ uint2 pic_ld2(const void* a) {
-    if constexpr (pic_nt(BIT)) { const pic_u2v t = __builtin_nontemporal_load((const pic_u2v*)a); return make_uint2(t.x, t.y); }
-    else return *(const uint2*)a;
-}
-template <int BIT> __device__ __forceinline__ void pic_st2(void* a, uint2 v) {
-    if constexpr (pic_nt(BIT)) { pic_u2v t; t.x = v.x; t.y = v.y; __builtin_nontemporal_store(t, (pic_u2v*)a); }
-    else *(uint2*)a = v;
-}
 // st_sel: the store's cache policy chosen at run time (wave-uniform flag): non-temporal when the step's state does not fit the
-// 256 MiB Infinity Cache anyway (KbArgs.nt_out)
+// 256 MiB Infinity Cache anyway (KbArgs.nt_out).  Every other access is a plain one: non-temporal agent streams, rim lists and
+// windows, chosen stream by stream at compile time, won at one size and lost at another (LABBOOK.md, rounds 3 and 4).
 template <typename T> struct Vec4;
 template <> struct Vec4<float> {
-    template <int BIT = -1> static __device__ __forceinline__ void ld(const float* p, float v[4]) {
-        const uint4 t = pic_ld4<BIT>(p);
+    static __device__ __forceinline__ void ld(const float* p, float v[4]) {
+        const uint4 t = *(const uint4*)p;
         v[0] = __uint_as_float(t.x); v[1] = __uint_as_float(t.y); v[2] = __uint_as_float(t.z); v[3] = __uint_as_float(t.w);
     }
-    template <int BIT = -1> static __device__ __forceinline__ void st(float* p, const float v[4]) {
-        pic_st4<BIT>(p, make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])));
+    static __device__ __forceinline__ void st(float* p, const float v[4]) {
+        *(uint4*)p = make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
     }
-    template <int BIT = -1> static __device__ __forceinline__ void st_sel(bool nt, float* p, const float v[4]) {
-        if (pic_nt(BIT) || !nt) { st<BIT>(p, v); return; }
+    static __device__ __forceinline__ void st_sel(bool nt, float* p, const float v[4]) {
+        if (!nt) { st(p, v); return; }
         pic_u4v t; t.x = __float_as_uint(v[0]); t.y = __float_as_uint(v[1]); t.z = __float_as_uint(v[2]); t.w = __float_as_uint(v[3]);
         __builtin_nontemporal_store(t, (pic_u4v*)p);
     }
 };
 template <> struct Vec4<__half> {
-    template <int BIT = -1> static __device__ __forceinline__ void ld(const __half* p, float v[4]) {
-        const uint2 t = pic_ld2<BIT>(p);
+    static __device__ __forceinline__ void ld(const __half* p, float v[4]) {
+        const uint2 t = *(const uint2*)p;
         const __half2 a = *(const __half2*)&t.x, b = *(const __half2*)&t.y;
         v[0] = __low2float(a); v[1] = __high2float(a); v[2] = __low2float(b); v[3] = __high2float(b);
     }
-    template <int BIT = -1> static __device__ __forceinline__ void st(__half* p, const float v[4]) {
+    static __device__ __forceinline__ void st(__half* p, const float v[4]) {
         const __half2 a = __halves2half2(die_f2h(v[0]), die_f2h(v[1])), b = __halves2half2(die_f2h(v[2]), die_f2h(v[3]));
         uint2 t; t.x = *(const uint32_t*)&a; t.y = *(const uint32_t*)&b;
-        pic_st2<BIT>(p, t);
+        *(uint2*)p = t;
     }
-    template <int BIT = -1> static __device__ __forceinline__ void st_sel(bool nt, __half* p, const float v[4]) {
-        if (pic_nt(BIT) || !nt) { st<BIT>(p, v); return; }
+    static __device__ __forceinline__ void st_sel(bool nt, __half* p, const float v[4]) {
+        if (!nt) { st(p, v); return; }
         const __half2 a = __halves2half2(die_f2h(v[0]), die_f2h(v[1])), b = __halves2half2(die_f2h(v[2]), die_f2h(v[3]));
         pic_u2v t; t.x = *(const uint32_t*)&a; t.y = *(const uint32_t*)&b;
         __builtin_nontemporal_store(t, (pic_u2v*)p);
     }
 };
 
-// PIC_PRIO_K1 / PIC_PRIO_KB: s_setprio levels, one hex digit per point of the kernel (agent kernel: start, agent streams
-// issued, chunk loop, after the chunk loop; field kernel: start, window loads issued, x pass, unused)
-// PIC_KARG: the agent kernel reads its array pointers from the kernel-argument segment where it uses them (scalar loads)
-// instead of carrying all 26 of them — most of them spilled to vector lanes — through its chunk loop
-#ifndef PIC_KARG
-#define PIC_KARG 1
-#endif
-#ifndef PIC_PRIO_K1
-#define PIC_PRIO_K1 0x3003      // (the waves of a starting workgroup issue their loads ahead of the resident workgroups' chunk loops: 83.5 → 81.4 µs;
-#endif                          //  raising the chunk loop, or the waves that take a second chunk: worse — LABBOOK.md, rounds 3 and 6)
-#ifndef PIC_PRIO_KB
-#define PIC_PRIO_KB 0x0000
-#endif
-#define PIC_SETPRIO(word, i) do { if ((i) == 0 ? (((word) >> 12) & 3) != 0 : ((((word) >> (12 - 4 * (i))) & 3) != (((word) >> (16 - 4 * (i))) & 3))) \
-                                      __builtin_amdgcn_s_setprio(((word) >> (12 - 4 * (i))) & 3); } while (0)
-#ifndef PIC_R6
-#define PIC_R6 1                // A/B: 0 = round 5's prologue and epilogue of the agent kernel (divisions and gridDim in the prologue, priority raised behind it, the tile's last words from wave 0 alone)
-#endif
-#ifndef PIC_K1_BLOCK
+// (block sizes and the like below: the measured best — LABBOOK.md, rounds 2–6)
 #define PIC_K1_BLOCK 512       // ≈ 614 agents stand on a 64×64 tile at ratio 0.15: one or two trips of the loop
-#endif
-#ifndef PIC_K2_BLOCK
 #define PIC_K2_BLOCK 512
-#endif
 #define PIC_MAX_MARGIN 24      // probe reach (cells) up to which K1 stages the chem tile in LDS
-#ifndef PIC_STAGE_FOOD
-#define PIC_STAGE_FOOD 1
-#endif
 
 struct PicLayout {
     uint32_t *x, *y;
@@ -193,38 +132,27 @@ struct PicArgs {
 // Workgroups are handed to the 8 XCDs round robin (linear workgroup id modulo 8), and every XCD has its own L2.  With the plain
 // (blockIdx.y, blockIdx.x) = (tx, ty) mapping the tiles that share cache lines — the margins of their staged windows: a row of a
 // window starts 16–48 bytes before a 256-byte boundary and so touches a 128-byte line of each neighbour along y, the margin rows are
-// the neighbours' along x — always sit in DIFFERENT L2s, and every shared line is fetched from memory twice.  PIC_XCD_MAP:
-//   2 (default): a band of columns per XCD — XCD j takes the tiles with ty in [j·nty/8, (j + 1)·nty/8), walked row of tiles by row of
-//      tiles: neighbours along y meet in one L2 at the same time, neighbours along x nty/8 workgroups later, and at any time the 8 XCDs
-//      read the same rows of the planes at different columns (4096² fp32: agent kernel FETCH_SIZE −26 %, 79.8 → 77.6 µs)
-//   1: one contiguous eighth of the tiles per XCD, in memory order — fewer fetches too (−21 %) but SLOWER (82.1 vs 77.4 µs): the 8 XCDs
-//      then walk addresses that differ by exact multiples of an eighth of every array, i.e. the same memory channels at the same time
-//   0: plain
-#ifndef PIC_XCD_MAP
-#define PIC_XCD_MAP 2
-#endif
-template <bool REVERSE = false>
-__device__ __forceinline__ void pic_xcd_tile(int& tx, int& ty, int ntx, uint32_t row0, uint32_t wb_mul, uint32_t nty_) {      // ntx: rows of tiles; row0: grid rows ahead of the tiles' (the field kernel's extra row); wb_mul: PicArgs.xcd_wb_mul; nty_ = gridDim.x = tiles per row (from the arguments: gridDim is a dependent load through the dispatch packet)
-#if PIC_XCD_MAP == 1
-    if (((gridDim.x * (uint32_t)ntx) & 7u) == 0) {
-        const uint32_t L = (blockIdx.y - row0) * gridDim.x + blockIdx.x, G8 = (gridDim.x * (uint32_t)ntx) >> 3;
-        const uint32_t nl = (L & 7u) * G8 + (L >> 3);
-        tx = (int)(nl / gridDim.x); ty = (int)(nl - (uint32_t)tx * gridDim.x);
-    }
-#elif PIC_XCD_MAP == 2
-    // (gridDim.x = tiles per row.  Bands of wb = floor(nty / 8) columns; the nty mod 8 columns left over — a decomposed rank's planes:
-    // 68 tiles per row — come last, in the plain order)
-    const uint32_t nty = PIC_R6 ? nty_ : gridDim.x, wb = nty >> 3, banded = (wb << 3) * (uint32_t)ntx;
+// the neighbours' along x — always sit in DIFFERENT L2s, and every shared line is fetched from memory twice.  Hence a band of columns
+// per XCD: XCD j takes the tiles with ty in [j·nty/8, (j + 1)·nty/8), walked row of tiles by row of tiles: neighbours along y meet in
+// one L2 at the same time, neighbours along x nty/8 workgroups later, and at any time the 8 XCDs read the same rows of the planes at
+// different columns (4096² fp32: agent kernel FETCH_SIZE −26 %, 79.8 → 77.6 µs).  One contiguous eighth of the tiles per XCD, in
+// memory order, fetched less too (−21 %) but was SLOWER (82.1 vs 77.4 µs): the 8 XCDs then walk addresses that differ by exact
+// multiples of an eighth of every array, i.e. the same memory channels at the same time.  (Walking the field kernel's bands from
+// their far end, so that an XCD's L2 might still hold the agent kernel's last tiles, gave the same counters.)
+// ntx: rows of tiles; row0: grid rows ahead of the tiles' (the field kernel's extra row); wb_mul: PicArgs.xcd_wb_mul; nty = gridDim.x
+// = tiles per row, taken from the arguments (gridDim is a dependent load through the dispatch packet).  Bands of wb = floor(nty / 8)
+// columns; the nty mod 8 columns left over — a decomposed rank's planes: 68 tiles per row — come last, in the plain order.
+__device__ __forceinline__ void pic_xcd_tile(int& tx, int& ty, int ntx, uint32_t row0, uint32_t wb_mul, uint32_t nty) {
+    const uint32_t wb = nty >> 3, banded = (wb << 3) * (uint32_t)ntx;
     const uint32_t L = (blockIdx.y - row0) * nty + blockIdx.x;
     if (wb == 0) return;
     if (L < banded) {
-        const uint32_t k = REVERSE ? wb * (uint32_t)ntx - 1u - (L >> 3) : L >> 3;      // (REVERSE: the band walked from its far end — A/B only)
-        tx = (int)(PIC_R6 && wb_mul ? __umulhi(k, wb_mul) : k / wb); ty = (int)((L & 7u) * wb + (k - (uint32_t)tx * wb));
+        const uint32_t k = L >> 3;
+        tx = (int)(wb_mul ? __umulhi(k, wb_mul) : k / wb); ty = (int)((L & 7u) * wb + (k - (uint32_t)tx * wb));
     } else {
         const uint32_t r = L - banded, rem = nty - (wb << 3);
         tx = (int)(r / rem); ty = (int)((wb << 3) + (r - (uint32_t)tx * rem));
     }
-#endif
 }
 
 // tile of linear workgroup L under an order table; false: no tile (a grid rounded up to whole rows, or — never, unless the table is
@@ -318,52 +246,16 @@ __device__ __forceinline__ void pic_ranges_finish(const PicMeta& mt, uint32_t* b
     PA_BARRIER();
 }
 
-// copy a rows × (vpr·V)-element block of a plane into LDS with 16-byte accesses.  A thread keeps ONE column vector
-// (lane group of 2^cs ≥ vpr lanes per row; surplus lanes copy the last column again) and walks down the rows in steps
-// of blockDim >> cs: per vector one add, two clamps, a multiply-add and the address — the first cut, with a division for
-// the row and tests around every load, spent a quarter of the kernel's instructions here.  Rows / columns outside the
-// world are never read by anybody (probes clamp at the world's edge): their loads are clamped into the plane, no branch.
-// WRAP: rows / columns beyond the plane are their periodic images (the food under an agent that has just walked across the
+// copy a rows × (vpr·V)-element block of a plane into LDS with 16-byte accesses.  Lane groups of EXACTLY `vpr` threads per row
+// (row r0 = thread / vpr by a multiply-shift the host has verified, blockDim / vpr rows per pass; the last blockDim % vpr threads
+// idle); a thread keeps ONE column vector and walks down the rows: per vector one add, the row's wrap or clamp, a multiply-add, the
+// address.  (The first cut, with a division for the row and tests around every load, spent a quarter of the kernel's instructions
+// here; power-of-two lane groups left the lanes beyond `vpr` idle — 10 of 32 for the 88-cell chem rows, 14 of 32 for the food rows —,
+// with exact groups the chem tile ± 12 cells takes 4 vectors per thread instead of 6 and the food tile with its margin 3.)  Rows /
+// columns outside the world are never read by anybody (probes clamp at the world's edge): their loads are clamped into the plane, no
+// branch.  WRAP: rows / columns beyond the plane are their periodic images (the food under an agent that has just walked across the
 // world's seam; H is a multiple of the vector width, so a column vector never straddles the seam).
-template <typename T, int NTB = -1, bool WRAP = false>
-struct PicStage {
-    const T* plane;
-    int gx0, gy0, vpr, rows, W, H, cs;
-    __device__ __forceinline__ uint4 load(int row, int gyc) const {
-        int gx = gx0 + min(row, rows - 1);
-        if (WRAP) { gx += gx < 0 ? W : 0; gx -= gx >= W ? W : 0; }
-        else gx = min(max(gx, 0), W - 1);
-        return pic_ld4<NTB>(plane + (__mul24(gx, H) + gyc));
-    }
-    __device__ __forceinline__ int column() const { return min((int)threadIdx.x & ((1 << cs) - 1), vpr - 1); }
-    __device__ __forceinline__ int col_cell(int cv) const {
-        int gy = gy0 + cv * (16 / (int)sizeof(T));
-        if (WRAP) { gy += gy < 0 ? H : 0; gy -= gy >= H ? H : 0; return gy; }
-        return min(max(gy, 0), H - 16 / (int)sizeof(T));
-    }
-    // the first NB rows of every thread: requested at the very top of the kernel (issue), written to LDS once the
-    // per-tile words and the agent streams have been requested too (commit) …
-    template <int NB> __device__ __forceinline__ void issue(uint4 (&v)[NB]) const {
-        const int gyc = col_cell(column()), r0 = (int)threadIdx.x >> cs, RP = (int)blockDim.x >> cs;
-#pragma unroll
-        for (int q = 0; q < NB; ++q) v[q] = load(r0 + q * RP, gyc);
-    }
-    template <int NB> __device__ __forceinline__ void commit(T* dst, const uint4 (&v)[NB]) const {
-        const int cv = column(), r0 = (int)threadIdx.x >> cs, RP = (int)blockDim.x >> cs;
-#pragma unroll
-        for (int q = 0; q < NB; ++q) ((uint4*)dst)[__mul24(min(r0 + q * RP, rows - 1), vpr) + cv] = v[q];
-        // … and whatever a larger tile / a smaller workgroup leaves over
-        const int gyc = col_cell(cv);
-        for (int row = r0 + NB * RP; row < rows; row += RP) ((uint4*)dst)[__mul24(row, vpr) + cv] = load(row, gyc);
-    }
-};
-
-// The same copy with lane groups of EXACTLY `vpr` threads per row (row r0 = thread / vpr by a multiply-shift the host has
-// verified, blockDim / vpr rows per pass; the last blockDim % vpr threads idle): the power-of-two groups above leave the lanes
-// beyond `vpr` idle — 10 of 32 for the 88-cell chem rows, 14 of 32 for the food rows — so the chem tile ± 12 cells takes 4
-// vectors per thread instead of 6 and the food tile with its margin 3.  A thread keeps its column; per vector: one add, the
-// row's wrap or clamp, a multiply-add, the address.
-template <typename T, int NTB, bool WRAP>
+template <typename T, bool WRAP>
 struct PicStageRows {
     const T* plane;
     int gx0, gy0, vpr, rows, W, H;
@@ -373,7 +265,7 @@ struct PicStageRows {
         int gx = gx0 + min(row, rows - 1);
         if (WRAP) { gx += gx < 0 ? W : 0; gx -= gx >= W ? W : 0; }
         else gx = min(max(gx, 0), W - 1);
-        return pic_ld4<NTB>(plane + (__mul24(gx, H) + gy));
+        return *(const uint4*)(plane + (__mul24(gx, H) + gy));
     }
     __device__ __forceinline__ void where(int& r0, int& cv, int& gy) const {
         r0 = (int)(((uint32_t)threadIdx.x * mg) >> 20);
@@ -403,78 +295,33 @@ struct PicStageRows {
 };
 
 #define PIC_RIM_CAP_MAX 224      // entries of a tile's rim list (k_pic_resolve_diffuse reads the codes of 9 lists with one word per thread)
-#ifndef PIC_LIST_CAP
 #define PIC_LIST_CAP 512        // arrivals of one tile compacted per round (≈ 80 arrive in the benchmark world)
-#endif
 // (The first round appends up to one candidate per thread: a list shorter than the workgroup is written past its end.  A
 // round-2 experiment build with a shorter list faulted that way — most probably the `n1` run of gpurun_out/sw3_n1.err,
 // DESIGN.md §9 — hence the assertion; tests/test_gpu_parity.py::test_tile_binned_step_with_a_crowd_crossing_one_border
 // drives the rounds below beyond the first on the shipped kernel.)
 static_assert(PIC_LIST_CAP >= PIC_K1_BLOCK, "the first round of candidates is one per thread");
 
-// Diagnostic build only (-DPIC_STAMPS; scratch/pic_stamps.py): s_memtime at the phase boundaries of K1, written by lane 0
-// of wave 0 behind the error word (the caller allocates 2 + 40·tiles words: 16 64-bit stamps per tile, [0, 8) the agent
-// kernel's, [8, 16) the field kernel's; then 4 more per tile, below).  No stamp executes in the shipped kernel.
-#if defined(PIC_STAMPS) && !defined(PIC_STAMPS_AGENTS_ONLY)
-#ifdef PIC_STAMPS_RT            // s_memrealtime: ONE 100 MHz clock for the whole GPU (s_memtime's counters are per XCD and not comparable)
-#define PIC_CLOCK "s_memrealtime"
-#else
-#define PIC_CLOCK "s_memtime"
-#endif
-#define PIC_NOW(t_) asm volatile(PIC_CLOCK " %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory")
-#define PIC_STAMP(k) do { if (threadIdx.x == 0) { unsigned long long t_; PIC_NOW(t_); \
-                          ((unsigned long long*)(p.error + 2))[(size_t)tile * 16 + (k)] = t_; } } while (0)
-// round 6: where a workgroup ran and when it ENTERED the kernel — 4 more 64-bit words per tile behind the 16 stamps (the caller
-// allocates 2 + 40·tiles words): [0] agent kernel: XCC_ID << 32 | HW_ID, [1] its entry time, [2] / [3] the field kernel's.
-// (kernel-entry time is taken before the tile is known: PIC_ENTRY_DECL at the top, PIC_ENTRY_STORE once `tile` exists)
-#define PIC_ENTRY_DECL unsigned long long t_entry_ = 0; if (threadIdx.x == 0) PIC_NOW(t_entry_)
-#define PIC_ENTRY_STORE(which) do { if (threadIdx.x == 0) { uint32_t hw_, xcc_; \
-                                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_)); asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_)); \
-                                unsigned long long* e_ = (unsigned long long*)(p.error + 2) + (size_t)p.ntx * p.nty * 16 + (size_t)tile * 4 + 2 * (which); \
-                                e_[0] = ((unsigned long long)xcc_ << 32) | hw_; e_[1] = t_entry_; } } while (0)
-#else
-#define PIC_STAMP(k) do { } while (0)
-#define PIC_ENTRY_DECL do { } while (0)
-#define PIC_ENTRY_STORE(which) do { } while (0)
-#endif
-
-#ifndef PIC_K1_MINW
-#define PIC_K1_MINW 6
-#endif
-#ifndef PIC_STATIC_CHUNKS
-#define PIC_STATIC_CHUNKS 0     // 1: wave w takes chunks w, w + waves, … instead of drawing them from an LDS counter
-#endif
 // element `idx` of a 4-byte-per-agent array: a 32-bit byte offset on the array's (scalar) base — the host refuses worlds of
 // 2^30 agents —, so every stream of an agent shares ONE offset register instead of a 64-bit address of its own
-#ifndef PIC_NT_OUT
-#define PIC_NT_OUT (-1)         // field kernel's plane stores non-temporal: −1 by the state's size (die_pic_forward_env_step), 0 never, 1 always
-#endif
-#ifndef PIC_K1_NT_LD
-#define PIC_K1_NT_LD 0          // agent kernel: its six agent streams (own segment: read once) loaded non-temporally (A/B)
-#endif
-#define PIC_LDN(base, type, idx) (PIC_K1_NT_LD ? __builtin_nontemporal_load(&PIC_AT(base, type, idx)) : PIC_AT(base, type, idx))
-#ifndef PIC_FOOD_COLS
-#define PIC_FOOD_COLS 0         // 1: the agent kernel's food block has a margin of columns too (the round-4 first cut: every new cell from LDS)
-#endif
-#ifndef PIC_TB
-#define PIC_TB true             // the agent kernel reads a PhysarumAgent's random turn bit from the step's table (false: one Philox block per agent whose turn is random)
-#endif
 #define PIC_AT(base, type, idx) (*(type*)((char*)(base) + (size_t)(uint32_t)((uint32_t)(idx) << 2)))
 // (Two persistent forms of this kernel — a tile queue with the next tile's agents prefetched, and one 16-wave workgroup per CU with
 // LDS-DMA loader waves — were built, bit-equal, and measured slower in round 4 (96 / 101 µs against 75–81): LABBOOK.md,
 // scratch/refuted_r04/.)
-template <typename T, int KIND, bool STAGE, bool ACT, bool RIM, bool TILED, bool MOM = false>
-// (waves per SIMD the compiler must leave room for: with fp16 planes the staged windows are 25 KB per workgroup, FOUR workgroups fit a
+// Waves per SIMD the compiler must leave room for: with fp16 planes the staged windows are 25 KB per workgroup, FOUR workgroups fit a
 // CU's LDS and the registers have to fit 8 waves per SIMD too — 78 scalar registers + 29 spilled instead of 106 + 17; with fp32
-// planes, 49 KB, only three fit whatever the registers)
-#ifndef PIC_K1_MINW_F16
+// planes, 49 KB, only three fit whatever the registers.
+#define PIC_K1_MINW 6
 #define PIC_K1_MINW_F16 8
-#endif
+// Wave priority (s_setprio): a starting workgroup's waves run at priority 3 until its tile loads, per-tile words and first agent
+// streams are out — they then issue their loads ahead of the resident workgroups' chunk loops: 83.5 → 81.4 µs —, at 0 through the
+// chunk loop, and at 3 again for the epilogue; raising the chunk loop, or the waves that take a second chunk, was worse
+// (LABBOOK.md, rounds 3 and 6).
+template <typename T, int KIND, bool STAGE, bool ACT, bool RIM, bool TILED, bool MOM = false>
 __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : PIC_K1_MINW)) void k_pic_forward_move(FwdArgs f, PicArgs p) {
-    PIC_ENTRY_DECL;
     // (a starting workgroup's FIRST instructions already run at raised priority: its ≈ 300 instructions of prologue otherwise queue
     // behind the resident workgroups' chunk loops — round 6, profiles/r06_cu_timeline_4096.txt)
-    if (PIC_R6 && ((PIC_PRIO_K1 >> 12) & 3) != 0) __builtin_amdgcn_s_setprio((PIC_PRIO_K1 >> 12) & 3);
+    __builtin_amdgcn_s_setprio(3);
     // (Requesting every argument the prologue needs with the FIRST scalar loads changed nothing, 75.1 against 74.6–75.3 µs: the compiler
     // re-loads them where it uses them.  LABBOOK.md, round 6.)
     // what die_pic_forward_env_step has checked on the host, spelled out for the compiler: the momentum / noise / graph
@@ -486,7 +333,6 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
     if (!MOM) { f.inertia = 0.f; f.noise_scale = 0.f; }
     f.normalized = 1;
     f.g = p.g;                            // one copy of the geometry
-#if PIC_KARG
     // The array pointers are needed at a few places each — the streams once per chunk, the epilogue's once per tile.  Kept in
     // scalar registers from the kernel's entry they (106 registers + 70 spilled to vector lanes, every use a v_readlane and a
     // hazard nop: vector-issue slots of a kernel that is half vector issue) cost more than re-reading them from the
@@ -496,9 +342,6 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
     static_assert(alignof(FwdArgs) == 8 && alignof(PicArgs) == 8 && sizeof(FwdArgs) % 8 == 0, "kernel-argument layout of k_pic_forward_move");
     const volatile KArgs __attribute__((address_space(4)))* ka = (const volatile KArgs __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
 #define PIC_KP(field, type) ((type)ka->p.field)
-#else
-#define PIC_KP(field, type) (p.field)
-#endif
     extern __shared__ __align__(16) unsigned char pic_smem[];     // STAGE: chem of the tile ± margin, then food of the tile ± its margin
     __shared__ uint32_t s_base[9], s_pre[10];                     // ranges of the current tile
     __shared__ unsigned long long s_cnt;                           // stayers | leavers << 21 | rim entries << 42: one LDS atomic per wave and chunk
@@ -549,22 +392,20 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
         pX = 0; pY = 0; pS = 0; pHh = 0; pHl = 0; pA = 0.f;
         if (pidx < own) {
             const uint32_t j = base0 + pidx;
-            pX = PIC_LDN(p.in.x, const uint32_t, j); pY = PIC_LDN(p.in.y, const uint32_t, j); pS = PIC_LDN(p.in.slot, const uint32_t, j);
-            pHh = PIC_LDN(p.in.hhi, const uint32_t, j); pHl = PIC_LDN(p.in.hlo, const uint32_t, j);
-            pA = PIC_LDN(p.in.agent_food, const float, j);
+            pX = PIC_AT(p.in.x, const uint32_t, j); pY = PIC_AT(p.in.y, const uint32_t, j); pS = PIC_AT(p.in.slot, const uint32_t, j);
+            pHh = PIC_AT(p.in.hhi, const uint32_t, j); pHl = PIC_AT(p.in.hlo, const uint32_t, j);
+            pA = PIC_AT(p.in.agent_food, const float, j);
         }
     };
     const int x0 = tx << p.xs, y0 = ty << p.ys;
-    PIC_ENTRY_STORE(0);
-    PIC_STAMP(0);
-    PIC_SETPRIO(PIC_PRIO_K1, 0);
+    __builtin_amdgcn_s_setprio(3);        // (already 3 since the entry; the loads below go out at 3, the chunk loop runs at 0)
     // 1st round trip: the per-tile words (small arrays, L2-resident).  Requested FIRST: vector loads return in order, so a
-    // word requested behind the tile loads would only arrive after all of them (stamps: 6 600 cycles for this phase).
+    // word requested behind the tile loads would only arrive after all of them (timestamps: 6 600 cycles for this phase).
     const PicMeta mt = pic_meta_load(p.in, tx, ty, p.ntx, p.nty);
     // the tiles to stage depend on nothing but the tile index: their loads go out next and overlap both round trips
-    const PicStageRows<T, 7, false> st_c = {(const T*)f.chem, x0 - P, y0 - P, pitch / SV, rows, p.g.W, p.g.H, p.mg_c, PIC_R6 ? p.rp_c : (int)blockDim.x / (pitch / SV)};
-    const PicStageRows<T, 5, true> st_f = {food, x0 - FR, y0 - FC, fpitch / SV, frows, p.g.W, p.g.H, p.mg_f, PIC_R6 ? p.rp_f : (int)blockDim.x / (fpitch / SV)};
-    uint4 sc[4], sf[3];                   // 64×64 tile, 512 threads: chem ± 12 cells = 88 × 22 vectors, food ± (3, 4) = 70 × 18
+    const PicStageRows<T, false> st_c = {(const T*)f.chem, x0 - P, y0 - P, pitch / SV, rows, p.g.W, p.g.H, p.mg_c, p.rp_c};
+    const PicStageRows<T, true> st_f = {food, x0 - FR, y0 - FC, fpitch / SV, frows, p.g.W, p.g.H, p.mg_f, p.rp_f};
+    uint4 sc[4], sf[3];                   // 64×64 tile, 512 threads: chem ± 12 cells = 88 × 22 vectors, food ± 3 rows = 70 × 16
     if (STAGE) {
         st_c.issue(sc);
         st_f.issue(sf);
@@ -574,9 +415,8 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
     // leavers that stand on it are stale copies of agents that came with the message)
     pic_ranges_finish(mt, s_base, s_pre, TILED && p.halo_fresh && p.g.own_x1 > 0 && (x0 < p.g.own_x0 || x0 >= p.g.own_x1 || y0 < p.g.own_y0 || y0 >= p.g.own_y1));
     prefetch_agents();
-    PIC_STAMP(1);
     const uint32_t own = s_pre[1], ncand = s_pre[9] - own, base0 = s_base[0];
-    PIC_SETPRIO(PIC_PRIO_K1, 1);
+    __builtin_amdgcn_s_setprio(0);
     FwdTileMem<T, TILED> tm;
     tm.g = p.g;
     T* s_food = nullptr;
@@ -588,7 +428,6 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
         tm.food = s_food; tm.fx0 = x0 - FR; tm.fy0 = y0 - FC; tm.fpitch = fpitch;
         tm.chem = s_chem; tm.cx0 = x0 - P; tm.cy0 = y0 - P; tm.pitch = pitch;
     }
-    PIC_STAMP(2);
     long long gsum = 0;
     uint32_t nowned = 0;
     // Rounds: the tile's own stayers plus (at most PIC_LIST_CAP per round) the neighbours' leavers that landed here,
@@ -616,22 +455,16 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
             if (hit) s_list[at + (uint32_t)__popcll(m & below)] = j;
         }
         PA_BARRIER();                                           // publishes the staged tiles and the list
-        PIC_STAMP(3);
-        PIC_SETPRIO(PIC_PRIO_K1, 2);
         const uint32_t n_own = cb == 0 ? own : 0u, count = n_own + s_nlist;
         bool first = cb == 0;
-        uint32_t cprev = 0;
         for (;;) {                         // a wave's first chunk is fixed (its streams are already here), then it takes
             uint32_t c = 0;                // chunks of 64 items from the counter until none are left
             if (first) {
                 c = (uint32_t)(wave * DIE_WAVE);
-            } else if (PIC_STATIC_CHUNKS) {
-                c = cprev + (uint32_t)(nwaves * DIE_WAVE);
             } else {
                 if (lane == 0) c = atomicAdd(&s_next, (uint32_t)DIE_WAVE);
                 c = __shfl(c, 0, DIE_WAVE);
             }
-            cprev = c;
             if (c >= count) break;
             const uint32_t idx = c + lane;
             const bool act = idx < count;
@@ -651,13 +484,13 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
                     const uint32_t *ix_ = PIC_KP(in.x, const uint32_t*), *iy_ = PIC_KP(in.y, const uint32_t*), *is_ = PIC_KP(in.slot, const uint32_t*);
                     const uint32_t *ihh_ = PIC_KP(in.hhi, const uint32_t*), *ihl_ = PIC_KP(in.hlo, const uint32_t*);
                     const float* ia_ = PIC_KP(in.agent_food, const float*);
-                    X = PIC_LDN(ix_, const uint32_t, j); Y = PIC_LDN(iy_, const uint32_t, j); sid = PIC_LDN(is_, const uint32_t, j);
-                    hh = PIC_LDN(ihh_, const uint32_t, j); hl = PIC_LDN(ihl_, const uint32_t, j);
-                    af = PIC_LDN(ia_, const float, j);
+                    X = PIC_AT(ix_, const uint32_t, j); Y = PIC_AT(iy_, const uint32_t, j); sid = PIC_AT(is_, const uint32_t, j);
+                    hh = PIC_AT(ihh_, const uint32_t, j); hl = PIC_AT(ihl_, const uint32_t, j);
+                    af = PIC_AT(ia_, const float, j);
                 }
                 hd = __hiloint2double((int)hh, (int)hl);
-                const FwdOut o = STAGE ? die_forward_agent_mem<T, KIND, false, FwdTileMem<T, TILED>, PIC_TB, false>(f, tm, X, Y, hd, sid, (int64_t)j)
-                                       : die_forward_agent_mem<T, KIND, false, FwdGlobalMem<T, false>, PIC_TB, false>(f, FwdGlobalMem<T, false>(f), X, Y, hd, sid, (int64_t)j);
+                const FwdOut o = STAGE ? die_forward_agent_mem<T, KIND, false, FwdTileMem<T, TILED>, true, false>(f, tm, X, Y, hd, sid, (int64_t)j)
+                                       : die_forward_agent_mem<T, KIND, false, FwdGlobalMem<T, false>, true, false>(f, FwdGlobalMem<T, false>(f), X, Y, hd, sid, (int64_t)j);
                 if (MOM) { pux = o.ux; puy = o.uy; }
                 if (ACT && p.adx) { PIC_AT(p.adx, float, j) = o.dx; PIC_AT(p.ady, float, j) = o.dy; PIC_AT(p.adep, float, j) = o.dep; }   // ACT = false: the caller passed no action arrays
                 // _agent_move (core/env.py:163-172)
@@ -684,7 +517,7 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
                     rx += rx < -FR ? p.g.W : 0; rx -= rx >= TX + FR ? p.g.W : 0;
                     ry += ry < -FC ? p.g.H : 0; ry -= ry >= TY + FC ? p.g.H : 0;
                     rx = min(max(rx + FR, 0), frows - 1);                              // (a longer jump is an error, flagged below: never out of the block)
-                    // the block has a margin of ROWS only by default (fm_c = 0): a row of the plane starts on a 256-byte boundary of
+                    // the block has a margin of ROWS only (fm_c = 0): a row of the plane starts on a 256-byte boundary of
                     // the tile, so whole rows cost no partial cache lines, while ± 4 columns made every row touch two more 128-byte
                     // lines (70 rows × 4 lines instead of 64 × 2: + 65 MB of fetches per step at 4096²).  The few agents that leave
                     // the tile's columns (≈ 1 % per step at the benchmark's step length) read their cell from global memory
@@ -733,7 +566,7 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
                 const uint32_t at = br + (uint32_t)__popcll(m_rim & below);
                 if (at < (uint32_t)p.rim_cap) {
                     s_rimc[at] = (uint8_t)code;
-                    pic_st4<2>(&PIC_KP(rim, uint4*)[(size_t)tile * p.rim_cap + at], make_uint4(X, Y, sid, __float_as_uint(dep)));
+                    PIC_KP(rim, uint4*)[(size_t)tile * p.rim_cap + at] = make_uint4(X, Y, sid, __float_as_uint(dep));
                 }
             }
             if (act) {
@@ -742,17 +575,13 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
                     uint32_t *ox_ = PIC_KP(out.x, uint32_t*), *oy_ = PIC_KP(out.y, uint32_t*), *os_ = PIC_KP(out.slot, uint32_t*);
                     uint32_t *ohh_ = PIC_KP(out.hhi, uint32_t*), *ohl_ = PIC_KP(out.hlo, uint32_t*);
                     float *oa_ = PIC_KP(out.agent_food, float*), *od_ = PIC_KP(dep, float*);
-#ifndef PIC_K1_NT_ST
-#define PIC_K1_NT_ST 0          // bit 0: x, y, slot, deposit (the field kernel reads them next); bit 1: agent_food, heading — non-temporal stores (A/B)
-#endif
-#define PIC_ST(bit, base, type, idx, val) do { if ((PIC_K1_NT_ST >> (bit)) & 1) __builtin_nontemporal_store((type)(val), &PIC_AT(base, type, idx)); else PIC_AT(base, type, idx) = (val); } while (0)
-                    PIC_ST(0, ox_, uint32_t, q, X);                // (x, y, slot, deposit are read again by the field kernel)
-                    PIC_ST(0, oy_, uint32_t, q, Y);
-                    PIC_ST(1, oa_, float, q, af);
-                    PIC_ST(0, os_, uint32_t, q, sid);
-                    PIC_ST(1, ohh_, uint32_t, q, (uint32_t)__double2hiint(hd));
-                    PIC_ST(1, ohl_, uint32_t, q, (uint32_t)__double2loint(hd));
-                    PIC_ST(0, od_, float, q, dep);
+                    PIC_AT(ox_, uint32_t, q) = X;                  // (x, y, slot, deposit are read again by the field kernel)
+                    PIC_AT(oy_, uint32_t, q) = Y;
+                    PIC_AT(oa_, float, q) = af;
+                    PIC_AT(os_, uint32_t, q) = sid;
+                    PIC_AT(ohh_, uint32_t, q) = (uint32_t)__double2hiint(hd);
+                    PIC_AT(ohl_, uint32_t, q) = (uint32_t)__double2loint(hd);
+                    PIC_AT(od_, float, q) = dep;
                     if (MOM && p.opgx) { PIC_AT(p.opgx, float, q) = pux; PIC_AT(p.opgy, float, q) = puy; }
                 } else {
                     atomicOr(PIC_KP(error, uint32_t*), 1u);
@@ -766,8 +595,7 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
             PA_BARRIER();
         }
     }
-    PIC_STAMP(4);
-    PIC_SETPRIO(PIC_PRIO_K1, 3);
+    __builtin_amdgcn_s_setprio(3);
     gsum = die_wave_sum(gsum);
     if (lane == 0) s_gain[threadIdx.x / DIE_WAVE] = gsum;
     if (TILED) {
@@ -778,13 +606,12 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
     // pointers they go to are requested ahead of the barrier.  (Round 6: all of it in wave 0, one dependent scalar load after the other,
     // kept a workgroup's slot 0.64 µs beyond its last barrier — profiles/r06_cu_timeline_4096.txt; the slot is not refilled before the
     // last wave has ended.)
-    const int w_inc = PIC_R6 && nwaves > 1 ? 1 : 0, w_rim = PIC_R6 && nwaves > 2 ? 2 : 0;
+    const int w_inc = nwaves > 1 ? 1 : 0, w_rim = nwaves > 2 ? 2 : 0;
     uint32_t* e_inc = nullptr; uint8_t* e_rimc = nullptr; uint32_t* e_rimn = nullptr; long long* e_gain = nullptr;
     if (wave == w_inc) e_inc = PIC_KP(out.inc, uint32_t*);
     if (RIM && wave == w_rim) { e_rimc = PIC_KP(rim_code, uint8_t*); e_rimn = PIC_KP(rim_cnt, uint32_t*); }
     if (wave == 0) e_gain = PIC_KP(part_gain, long long*);
     PA_BARRIER();
-    PIC_STAMP(5);
     if (wave == w_inc && lane < 9 && s_inc[lane]) {
         const int ddx = lane / 3 - 1, ddy = lane % 3 - 1;
         atomicAdd(&e_inc[pic_wrap(tx + ddx, p.ntx) * p.nty + pic_wrap(ty + ddy, p.nty)], s_inc[lane]);
@@ -792,8 +619,11 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
     if (RIM && wave == w_rim) {
         // (a segment too long for the 24-bit positions counts as an overflowing list: the reader scans it)
         const uint32_t nr = on >= (1u << 21) ? (uint32_t)p.rim_cap + 1u : (uint32_t)(s_cnt >> 42) & 0x1FFFFFu;
-        for (uint32_t i = (uint32_t)lane; i < (min(nr, (uint32_t)p.rim_cap) + 3u) / 4u; i += DIE_WAVE)
-            pic_st<2>(&((uint32_t*)e_rimc)[((size_t)tile * p.rim_cap) / 4 + i], ((const uint32_t*)s_rimc)[i]);
+        // (the address first, then the LDS read: the other order leaves the compiler other registers — the same work)
+        for (uint32_t i = (uint32_t)lane; i < (min(nr, (uint32_t)p.rim_cap) + 3u) / 4u; i += DIE_WAVE) {
+            uint32_t* const w = &((uint32_t*)e_rimc)[((size_t)tile * p.rim_cap) / 4 + i];
+            *w = ((const uint32_t*)s_rimc)[i];
+        }
         if (lane == 0) e_rimn[tile] = nr;
     }
     if (wave == 0) {
@@ -808,12 +638,6 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
             if (nfront + nback != on || on >= (1u << 21)) atomicOr(p.error, 1u);
         }
     }
-    PIC_STAMP(7);
-#if defined(PIC_STAMPS) && !defined(PIC_STAMPS_AGENTS_ONLY)
-    // (diagnostic: when have wave 0's own stores — the epilogue's, issued a moment ago — been acknowledged?)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    PIC_STAMP(6);
-#endif
 }
 
 // ---- dead slots on the tile-binned path (the reference's default layout: max_agents = W·H slots, core/data_init.py:143-144) ----------
@@ -899,7 +723,7 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_turn_bits(uint32_t* table, int64_
 // K2.  blockIdx.x == number of tiles: the scan workgroup (sizes and offsets of the layout the NEXT step writes:
 // n = s + inc of the layout just written, exclusive scan; its arrival counters are cleared for that step).
 // FEED: the tile's half of _agent_feed (core/env.py:222-228), food −= rate·food on the occupied cells, is done here — K2 is
-// bound by latency and has memory bandwidth to spare, the field sweep is bound by bandwidth (PIC_K2_FEED, measured below).
+// bound by latency and has memory bandwidth to spare, the field sweep is bound by bandwidth.
 template <typename T, int XS, int YS, bool FEED>
 __global__ __launch_bounds__(PIC_K2_BLOCK) void k_pic_resolve(PicArgs p, float* dep_plane) {
     constexpr int TX = 1 << XS, TY = 1 << YS;
@@ -1045,12 +869,9 @@ template <int XS, int YS> struct KbShape {
 
 // (The four barriers below as LDS-only barriers — s_waitcnt lgkmcnt(0) + s_barrier, no wait for the food stores' acknowledgements —
 // measured in round 5: 58.4–59.6 against 58.6–60.2 µs, nothing.)
-#ifndef PIC_KB_MINW
-#define PIC_KB_MINW 8           // 4 workgroups of 512 threads per CU (A/B: scratch/build_variant.sh)
-#endif
+#define PIC_KB_MINW 8           // 4 workgroups of 512 threads per CU
 template <typename T, int XS, int YS, int R, bool TILED>
 __global__ __launch_bounds__((KbShape<XS, YS>::BLOCK), PIC_KB_MINW) void k_pic_resolve_diffuse(PicArgs p, KbArgs a) {
-    PIC_ENTRY_DECL;
     constexpr int TX = 1 << XS, TY = 1 << YS, BLOCK = KbShape<XS, YS>::BLOCK;
     constexpr int A = 16 / (int)sizeof(T);                 // cells per 16-byte vector
     constexpr int WR = TX + 2 * R, WC = TY + 2 * R;        // the window
@@ -1138,19 +959,12 @@ __global__ __launch_bounds__((KbShape<XS, YS>::BLOCK), PIC_KB_MINW) void k_pic_r
         return;
     }
     int tx = (int)(blockIdx.y - row0), ty = blockIdx.x;
-#ifndef PIC_XCD_MAP_KB
-#define PIC_XCD_MAP_KB 1        // 2: bands walked from their far end (does an XCD's L2 keep the agent kernel's last tiles across the kernel boundary? no: same counters)
-#endif
     bool by_table = false;
     if (p.order && !pic_order_tile(p, (blockIdx.y - row0) * (uint32_t)p.nty + blockIdx.x, tx, ty, by_table)) return;
-    if (!by_table && PIC_XCD_MAP_KB && p.sub_mode == 0) pic_xcd_tile<PIC_XCD_MAP_KB == 2>(tx, ty, p.ntx, row0, p.xcd_wb_mul, (uint32_t)p.nty);
+    if (!by_table && p.sub_mode == 0) pic_xcd_tile(tx, ty, p.ntx, row0, p.xcd_wb_mul, (uint32_t)p.nty);
     if (!pic_sub_tile(p, tx, ty)) return;
     const int x0 = tx << XS, y0 = ty << YS;
     const int W = p.g.W, H = p.g.H;
-    [[maybe_unused]] const int tile = tx * p.nty + ty;
-    PIC_ENTRY_STORE(1);
-    PIC_STAMP(8);
-    PIC_SETPRIO(PIC_PRIO_KB, 0);
     const T* chem = (const T*)a.chem;
     T* food = (T*)p.food;
     // 1. everything that depends on the tile index only goes out first: the per-tile words, the rim lists, the chem window,
@@ -1168,13 +982,13 @@ __global__ __launch_bounds__((KbShape<XS, YS>::BLOCK), PIC_KB_MINW) void k_pic_r
     // exists is known once the counts are here)
     static_assert(NE == 4 && CAPR % 4 == 0 && 9 * CAPR <= 4 * BLOCK, "one word of codes per thread");
     const int rl = 4 * (int)threadIdx.x / CAPR, ri = 4 * (int)threadIdx.x - rl * CAPR;
-    const uint32_t rcodes = rl < 9 ? pic_ld<3>(&((const uint32_t*)a.rim_code)[((size_t)ring_tile(rl) * CAPR + ri) / 4]) : 0u;
+    const uint32_t rcodes = rl < 9 ? ((const uint32_t*)a.rim_code)[((size_t)ring_tile(rl) * CAPR + ri) / 4] : 0u;
     constexpr int NCV = (WR * NV + BLOCK - 1) / BLOCK;
     static_assert(NCV <= 3, "three window vectors per thread at most");       // (named registers: as an array they went to scratch)
     auto window_load = [&](int q) {
         const int i = min((int)threadIdx.x + q * BLOCK, WR * NV - 1);       // (surplus threads load the last vector again: no branch)
         const int r = i / NV, v = i - r * NV;
-        return pic_ld4<8>(chem + ((int64_t)pic_wrap(x0 - R + r, W) * H + pic_wrap(y0 - A + v * A, H)));
+        return *(const uint4*)(chem + ((int64_t)pic_wrap(x0 - R + r, W) * H + pic_wrap(y0 - A + v * A, H)));
     };
     // (Round 5, both measured and dropped: the tile's own stayers requested right here, from scalar-loaded segment words — a barrier
     // and an LDS hand-over earlier than the claims pass: 59.5–60.0 against 57.9–58.6 µs; the four barriers below as LDS-only barriers,
@@ -1182,7 +996,6 @@ __global__ __launch_bounds__((KbShape<XS, YS>::BLOCK), PIC_KB_MINW) void k_pic_r
     uint4 cv0 = window_load(0), cv1 = cv0, cv2 = cv0;
     if constexpr (NCV > 1) cv1 = window_load(1);
     if constexpr (NCV > 2) cv2 = window_load(2);
-    PIC_SETPRIO(PIC_PRIO_KB, 1);
     for (int i = threadIdx.x; i < WR * WC / 4; i += BLOCK) ((uint4*)s_claim)[i] = make_uint4(0u, 0u, 0u, 0u);
     static_assert((WR * WC) % 4 == 0, "16-byte zeroing");
     if (threadIdx.x < 9) {
@@ -1201,7 +1014,6 @@ __global__ __launch_bounds__((KbShape<XS, YS>::BLOCK), PIC_KB_MINW) void k_pic_r
         s_lut[t] = here ? (unsigned char)((ux + 1) * 3 + uy + 1) : (unsigned char)0xFF;
     }
     __syncthreads();
-    PIC_STAMP(9);
     // the chem window into LDS (as float): requested first, so it is here when the per-tile words are — its registers are
     // free for the agents' data
     auto window_commit = [&](int q, const uint4 u) {
@@ -1243,9 +1055,7 @@ __global__ __launch_bounds__((KbShape<XS, YS>::BLOCK), PIC_KB_MINW) void k_pic_r
     // (Crowded tiles — 3 000 agents and more on a tile once the trails have formed, rim lists long overflowed — lived 60 µs here and WERE the
     // field kernel's duration at world step 3 000: one agent per thread and trip, coordinates → cell → slot → deposit one dependent round
     // trip after the other.  PIC_KB_U agents per thread and trip, all their loads requested before the first is used: round 6.)
-#ifndef PIC_KB_U
 #define PIC_KB_U 4
-#endif
     auto scan_segment = [&](int l, bool apply) {
         const uint32_t lo = l == 0 ? own0 + nown : s_off[l], hi = s_off[l] + s_n[l];
         for (uint32_t j0 = lo + threadIdx.x; j0 < hi; j0 += PIC_KB_U * BLOCK) {
@@ -1291,10 +1101,10 @@ __global__ __launch_bounds__((KbShape<XS, YS>::BLOCK), PIC_KB_MINW) void k_pic_r
             if (u < 2) {
                 if (threadIdx.x + u * BLOCK < nown) {
                     const uint32_t j = own0 + threadIdx.x + u * BLOCK;
-                    X[u] = pic_ld<3>(&p.out.x[j]); Y[u] = pic_ld<3>(&p.out.y[j]); cs[u] = pic_ld<3>(&p.out.slot[j]) + 1u; cd[u] = __float_as_uint(pic_ld<3>(&p.dep[j])); cw[u] = 0u;
+                    X[u] = p.out.x[j]; Y[u] = p.out.y[j]; cs[u] = p.out.slot[j] + 1u; cd[u] = __float_as_uint(p.dep[j]); cw[u] = 0u;
                 }
             } else if (rj[u - 2] != 0xFFFFFFFFu) {
-                const uint4 q = pic_ld4<3>(&rrec[rj[u - 2]]);
+                const uint4 q = rrec[rj[u - 2]];
                 X[u] = q.x; Y[u] = q.y; cs[u] = q.z + 1u; cd[u] = q.w; cw[u] = 0u;
             }
         }
@@ -1303,7 +1113,7 @@ __global__ __launch_bounds__((KbShape<XS, YS>::BLOCK), PIC_KB_MINW) void k_pic_r
 #pragma unroll
             for (int q = 0; q < FG; ++q) {
                 const int i = ((int)threadIdx.x + q * BLOCK) * 4;
-                if (i < TX * TY) { const int row = i / TY, col = i - row * TY; Vec4<T>::template ld<4>(food + (int64_t)(x0 + row) * H + y0 + col, fd[q]); }
+                if (i < TX * TY) { const int row = i / TY, col = i - row * TY; Vec4<T>::ld(food + (int64_t)(x0 + row) * H + y0 + col, fd[q]); }
             }
         }
 #pragma unroll
@@ -1329,9 +1139,7 @@ __global__ __launch_bounds__((KbShape<XS, YS>::BLOCK), PIC_KB_MINW) void k_pic_r
         }
     }
     if (over) for (int l = 0; l < 9; ++l) if (over >> l & 1u) scan_segment(l, false);
-    PIC_STAMP(10);
     __syncthreads();
-    PIC_STAMP(11);
     // 4. deposits of the winners; feeding of the tile's occupied cells
     auto deposit = [&](uint32_t widx, uint32_t s1, uint32_t db) {
         if (widx == 0xFFFFFFFFu || s_claim[widx & 0xFFFFu] != s1) return;
@@ -1368,13 +1176,11 @@ __global__ __launch_bounds__((KbShape<XS, YS>::BLOCK), PIC_KB_MINW) void k_pic_r
             if (occ[0] || occ[1] || occ[2] || occ[3]) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) if (occ[q]) fd[g][q] = fd[g][q] - p.rate_feed * fd[g][q];
-                Vec4<T>::template st_sel<9>(a.nt_out != 0, food + (int64_t)(x0 + row) * H + y0 + col, fd[g]);
+                Vec4<T>::st_sel(a.nt_out != 0, food + (int64_t)(x0 + row) * H + y0 + col, fd[g]);
             }
         }
     }
     __syncthreads();
-    PIC_STAMP(12);
-    PIC_SETPRIO(PIC_PRIO_KB, 2);
     // 5. x pass (axis 0): column c of the window, RB output rows per item, the 2R + 1 rows of the stencil in registers
     constexpr int RB = TX >= 64 ? 16 : 8;
     for (int item = threadIdx.x; item < WC * (TX / RB); item += BLOCK) {
@@ -1395,7 +1201,6 @@ __global__ __launch_bounds__((KbShape<XS, YS>::BLOCK), PIC_KB_MINW) void k_pic_r
         }
     }
     __syncthreads();
-    PIC_STAMP(13);
     // 6. y pass (axis 1), decay, 16-byte (fp16: 8-byte) stores of the tile's cells
     T* dst = (T*)a.chem_next;
     constexpr int LO = A - R, LA = LO & ~3, NX = (LO - LA + 4 + 2 * R + 3) / 4;    // aligned float4 reads around the 4 cells
@@ -1416,9 +1221,8 @@ __global__ __launch_bounds__((KbShape<XS, YS>::BLOCK), PIC_KB_MINW) void k_pic_r
             for (int k = 0; k < R; ++k) t += (xf[cc - R + k] + xf[cc + R - k]) * a.w[k];
             o[j] = t * a.keep;
         }
-        Vec4<T>::template st_sel<6>(a.nt_out != 0, dst + (int64_t)(x0 + row) * H + y0 + 4 * cg, o);
+        Vec4<T>::st_sel(a.nt_out != 0, dst + (int64_t)(x0 + row) * H + y0 + 4 * cg, o);
     }
-    PIC_STAMP(14);
 }
 
 // ---- order table (die_pic.order): which workgroup of a launch takes which tile --------------------------------------
@@ -1427,9 +1231,7 @@ __global__ __launch_bounds__((KbShape<XS, YS>::BLOCK), PIC_KB_MINW) void k_pic_r
 // counting sort over 8 classes) — the crowded tiles, and with them the tiles whose rim lists overflow in the field kernel, start
 // first; neighbouring tiles of one class still run side by side in one L2.  n = populations of the layout the coming step reads.
 #define PIC_ORDER_BLOCK 512
-#ifndef PIC_ORDER_PERIOD
 #define PIC_ORDER_PERIOD 32     // steps between two rebuilds of the table (an agent walks 3/4 of a tile meanwhile; 8 / 16 / 32: the same rates, the rebuild is 4.8 µs + a kernel boundary)
-#endif
 // Only the LAST PIC_ORDER_SPAN tiles of a band are sorted; the tiles ahead of them keep the band order.  What matters is that no crowded
 // tile sits in a launch's last rounds — a crowded tile in the middle of a launch delays nobody —, and tiles that are neighbours in space
 // should stay neighbours in time (they share the margins of their windows in one L2): with their bands of 2 048 / 8 192 tiles sorted as
@@ -1448,16 +1250,9 @@ __global__ __launch_bounds__(PIC_ORDER_BLOCK) void k_pic_order(const uint32_t* n
         for (int q = lo; q < hi; ++q) order[(size_t)j * blen + q] = (uint16_t)tile_at(q);
         return;
     }
-#ifndef PIC_ORDER_MIN_CROWDED
-#define PIC_ORDER_MIN_CROWDED 96 // tiles of four and more rounds, per 4 096 tiles of the eight bands' last spans TOGETHER, from which every band's span is sorted (A/B: 0 = always)
-#endif
-#ifndef PIC_ORDER_RMIN
-#define PIC_ORDER_RMIN 0        // A/B: tiles of at most this many rounds count as one class (band order among them) …
-#endif
-#ifndef PIC_ORDER_RMAX
-#define PIC_ORDER_RMAX 7        // … and so do tiles of at least this many
-#endif
-    auto cls = [&](int t) { const uint32_t r = ((n[t] + 63u) / 64u + 7u) / 8u; return 7 - (int)min(max(r, (uint32_t)PIC_ORDER_RMIN), (uint32_t)PIC_ORDER_RMAX); };      // 0: the most crowded
+#define PIC_ORDER_MIN_CROWDED 96 // tiles of four and more rounds, per 4 096 tiles of the eight bands' last spans TOGETHER, from which every band's span is sorted
+    // (tiles of seven and more rounds are one class; coarser classes lost the agent kernel's gain: LABBOOK.md, round 6)
+    auto cls = [&](int t) { const uint32_t r = ((n[t] + 63u) / 64u + 7u) / 8u; return 7 - (int)min(r, 7u); };      // 0: the most crowded
     uint32_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int q = lo; q < hi; ++q) {
         const int k = cls(tile_at(q));
@@ -1849,8 +1644,8 @@ extern "C" int die_pic_forward_env_step(const die_medium* m, const die_pic* p, i
     // the food block: the tile ± the cells an agent can walk onto in one step (floor(reach) + 1 by the move, one more across the
     // world's seam), columns in whole vectors
     k.fm_r = stage ? (int)floorf(reach) + 2 : 0;
-    // (columns: PIC_FOOD_COLS = 1 only)
-    k.fm_c = PIC_FOOD_COLS ? (k.fm_r + V - 1) / V * V : 0;
+    // (rows only: a row of the plane starts on a 256-byte boundary of the tile, see k_pic_forward_move's feeding)
+    k.fm_c = 0;
     const int vpr_c = (TY + 2 * k.margin) / V, vpr_f = (TY + 2 * k.fm_c) / V;     // 16-byte vectors per staged row
     k.mg_c = ((1u << 20) + (uint32_t)vpr_c - 1u) / (uint32_t)vpr_c;
     k.mg_f = ((1u << 20) + (uint32_t)vpr_f - 1u) / (uint32_t)vpr_f;
@@ -1890,7 +1685,7 @@ extern "C" int die_pic_forward_env_step(const die_medium* m, const die_pic* p, i
         return DIE_ERR_UNSUPPORTED;
     }
     k.rim = (uint4*)p->rim; k.rim_code = p->rim_code; k.rim_cnt = p->rim_cnt; k.rim_cap = (int)die_pic_rim_cap(p->tile_xs, p->tile_ys); k.rim_r = R;
-    const bool feed_in_k2 = PIC_K2_FEED && !d->food_infinite;
+    const bool feed_in_k2 = !d->food_infinite;
     int block = p->k1_threads > 0 ? p->k1_threads : (TX * TY >= 4096 ? 512 : 256);
     DIE_REQUIRE(block % DIE_WAVE == 0 && block >= DIE_WAVE && block <= PIC_K1_BLOCK, "die_pic_forward_env_step: k1_threads %d", block);
     k.rp_c = stage ? block / vpr_c : 1; k.rp_f = stage ? block / vpr_f : 1;
@@ -1929,11 +1724,8 @@ extern "C" int die_pic_forward_env_step(const die_medium* m, const die_pic* p, i
 #undef DIE_PIC_K1
     }
     // dead slots (two-launch form): the cells the alive agents stand on now, then the slots that never lived
-#ifndef PIC_DEAD_BLOCKS_CAP
-#define PIC_DEAD_BLOCKS_CAP 0          // workgroups of k_pic_dead: 0 = one slot per thread, else at most this many (grid-stride)
-#endif
-    const int64_t dead_want = dead ? (p->N - p->n_alive + DIE_BLOCK - 1) / DIE_BLOCK : 0;
-    const int64_t dead_launch = PIC_DEAD_BLOCKS_CAP > 0 && dead_want > PIC_DEAD_BLOCKS_CAP ? PIC_DEAD_BLOCKS_CAP : dead_want;
+    // (workgroups of k_pic_dead: one slot per thread)
+    const int64_t dead_launch = dead ? (p->N - p->n_alive + DIE_BLOCK - 1) / DIE_BLOCK : 0;
     const int dead_blocks = (int)(dead_launch < NT ? dead_launch : NT);       // reward partials the field kernel sums behind the tiles'
     if (dead) {
         DIE_REQUIRE(two, "die_pic_forward_env_step: dead slots exist in the two-launch form only");
@@ -1976,10 +1768,8 @@ extern "C" int die_pic_forward_env_step(const die_medium* m, const die_pic* p, i
             // agent arrays beyond the 256 MiB Infinity Cache (4096² fp32: 342 MB, 8192²) non-temporal stores make the step 3.5 % / 2 %
             // faster — the lines would be evicted before the next kernel reads them anyway and only displace the windows' shared
             // lines from L2 —, below it (4096² fp16: 241 MB, 2048²) they cost 1–3 %: the next kernel finds them in the cache
-            {
-                const double state = 3.0 * (double)m->W * m->H * esz + 2.0 * 28.0 * (double)p->N;
-                a.nt_out = PIC_NT_OUT < 0 ? (state > 256.0 * 1024 * 1024 ? 1 : 0) : PIC_NT_OUT;
-            }
+            const double state = 3.0 * (double)m->W * m->H * esz + 2.0 * 28.0 * (double)p->N;
+            a.nt_out = state > 256.0 * 1024 * 1024 ? 1 : 0;
             a.turn_bits = physarum && !g->turn_sign && k.nty > 2 ? p->turn_bits : nullptr;
             a.turn_words = turn_words; a.turn_seed = g->seed; a.turn_step = g->step + 1u;
             if (tiled) {

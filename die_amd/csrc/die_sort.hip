@@ -14,12 +14,8 @@
 #include "die_common.h"
 
 #define DIE_SORT_MAX_EXTRA 4
-#ifndef DIE_SORT_XSHIFT
 #define DIE_SORT_XSHIFT 4      // bucket = 2^XSHIFT rows × 2^YSHIFT columns (16×32: best of the shapes tried)
-#endif
-#ifndef DIE_SORT_YSHIFT
 #define DIE_SORT_YSHIFT 5
-#endif
 
 __device__ __forceinline__ uint32_t sort_key(const die_geo& g, uint32_t X, uint32_t Y, int nby) {
     int ix = die_cell((int64_t)X, g.gW) - g.ox, iy = die_cell((int64_t)Y, g.gH) - g.oy;
@@ -40,9 +36,7 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_sort_hist(die_geo g, int64_t N, c
 
 // exclusive scan of the bucket counts by ONE workgroup: cursor[b] = first position of bucket b.  A thread owns `per`
 // consecutive buckets (per % 4 == 0: 16-byte loads, all of them in flight before the first use).
-#ifndef SORT_SCAN_MAX_PER
 #define SORT_SCAN_MAX_PER 64
-#endif
 __global__ __launch_bounds__(1024) void k_sort_scan(const uint32_t* hist, uint32_t* cursor, int nb, int per) {
     __shared__ uint32_t s[1024];
     const int lo = threadIdx.x * per;
@@ -154,9 +148,7 @@ extern "C" int die_agents_sort(const die_medium* m, const die_agents* in, const 
     char* w = (char*)ws;
     hipStream_t s = (hipStream_t)stream;
     int64_t g = (N + DIE_BLOCK - 1) / DIE_BLOCK;
-#ifndef DIE_SORT_GRID_CAP
 #define DIE_SORT_GRID_CAP 4096
-#endif
     const int grid = (int)(g < DIE_SORT_GRID_CAP ? g : DIE_SORT_GRID_CAP);
     const int nby = (m->H >> DIE_SORT_YSHIFT) + 1;
     for (int i = 0; i < n_extra; ++i)

@@ -86,7 +86,7 @@ class PicState:
         self.n_alive = int(getattr(env, '_pic_n_alive', 0) or 0)
         self.occ = torch.zeros(W * H, dtype=torch.uint8, device=dev) if 0 < self.n_alive < N else None
         self.part = torch.zeros(2 * self.NT, dtype=torch.int64, device=dev)       # reward partials | owned agents (decomposed tiles)
-        self.error = torch.zeros(2 + 40 * self.NT, dtype=torch.int32, device=dev)      # [0]: error word; the rest: diagnostic builds (-DPIC_STAMPS)
+        self.error = torch.zeros(1, dtype=torch.int32, device=dev)       # the step's sticky error word (die_pic.error)
         i32 = lambda: torch.empty(N, dtype=torch.int32, device=dev)
         self.spare = [i32(), i32(), torch.empty(N, dtype=torch.float32, device=dev), i32(), i32()]     # x, y, agent_food, heading hi / lo
         self.spare_pg = None         # GradientAgent with inertia: the (2, N) _prev_grad array of the layout that is not current (die_pic.prev_grad)
