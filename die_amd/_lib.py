@@ -18,7 +18,7 @@ DIE_COST_LINEAR, DIE_COST_ZERO = 0, 1
 DIE_AGENT_GRADIENT, DIE_AGENT_PHYSARUM = 0, 1
 OWNER_EPOCH_SHIFT, OWNER_EPOCH_MAX, OWNER_SLOT_MASK = 27, 31, 0x07FFFFFF
 DIFFUSE_MODES = {'wrap': 0, 'nearest': 1, 'reflect': 2, 'mirror': 3, 'constant': 4}
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 
 class Medium(C.Structure):
@@ -95,6 +95,20 @@ class Batch(C.Structure):
                 ('seed_stride', C.c_uint64), ('n', C.c_int64 * 64)]
 
 
+NCA_MAX_LAYERS = 8
+
+
+class NcaLayer(C.Structure):         # die_nca_layer
+    _fields_ = [('k', C.c_int32), ('cin', C.c_int32), ('cout', C.c_int32), ('reserved', C.c_int32), ('weights', C.c_void_p),
+                ('weight_stride', C.c_int64)]
+
+
+class NcaBatch(C.Structure):         # die_nca_batch
+    _fields_ = [('n_layers', C.c_int32), ('padding_mode', C.c_int32), ('with_agent_channel', C.c_int32), ('sense_epoch', C.c_int32),
+                ('layers', C.POINTER(NcaLayer)), ('coef', C.c_float * 3), ('reserved', C.c_int32), ('scratch', C.c_void_p),
+                ('scratch_bytes', C.c_int64)]
+
+
 class Rect(C.Structure):
     _fields_ = [('plane', C.c_void_p), ('pitch', C.c_int32), ('r0', C.c_int32), ('r1', C.c_int32), ('c0', C.c_int32),
                 ('c1', C.c_int32), ('elem_bytes', C.c_int32), ('buf_offset', C.c_int64)]
@@ -121,6 +135,9 @@ _SIGNATURES = {
     'die_batch_workspace_bytes': (C.c_int64, [C.c_int32]),
     'die_forward_env_step_batch': (C.c_int, [_P(Medium), _P(Agents), _P(GradientAgent), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
                                              C.c_void_p, C.c_int64, C.c_void_p]),
+    'die_nca_batch_scratch_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    'die_nca_env_step_batch': (C.c_int, [_P(Medium), _P(Agents), _P(NcaBatch), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
+                                         C.c_void_p, C.c_int64, C.c_void_p]),
     'die_forward_move_claim_tile': (C.c_int, [_P(Medium), _P(Agents), _P(GradientAgent), _P(Action), _P(Dynamics), C.c_void_p,
                                               C.c_int64, C.c_void_p]),
     'die_env_step_finish': (C.c_int, [_P(Medium), _P(Agents), _P(Action), _P(Dynamics), C.c_void_p, C.c_void_p, C.c_int64,

@@ -4,18 +4,25 @@ costs more in launches and host calls than in kernel time, and R
 
 Replica r is exactly the stand-alone `Env(field_size, dynamics, seed=seed + r, max_agents='alive')` driven by
 `PhysarumAgent(max_agents=K_r, seed=agent_seed + r, ...)`: same initial state, same Philox streams, same kernels'
-arithmetic — bit for bit (tests/test_gpu_parity.py::test_batched_replicas_equal_stand_alone_runs)."""
+arithmetic — bit for bit (tests/test_gpu_parity.py::test_batched_replicas_equal_stand_alone_runs).
+
+`BatchedNeuralAutomataAgent` is a population of NeuralAutomataAgent candidates, one per replica (the evaluation half of
+examples/learning_agents.py): replica r is `Env(field_size, dynamics, seed=seeds[r], max_agents='alive')` driven by a
+NeuralAutomataAgent holding row r of the (R, P) parameter matrix — L + 2 launches per step for the whole population
+(`die_nca_env_step_batch`), bit for bit the stand-alone runs (tests/test_gpu_nca_batch.py)."""
 import ctypes as C
 import math
-from typing import Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
+from torch.nn.utils import parameters_to_vector, vector_to_parameters
 
 from . import _lib
+from .agent.evo import NeuralAutomataAgent
 from .agent.gradient import join64, split64
 from .device_array import Q32, _ptr, stream_ptr
-from .env import BoundaryCondition, Dynamics, Env, linear_action_cost
+from .env import BoundaryCondition, Dynamics, Env, _identity_food_flow, linear_action_cost
 
 
 class BatchedEnv:
@@ -26,23 +33,28 @@ class BatchedEnv:
         each replica takes — the tile-binned step (no claim plane, no re-sort), which the one-launch-pair form does not
         have.  Each replica is then a stand-alone `Env` stepped on its OWN HIP stream (the latency-bound agent kernel of one
         replica overlaps the bandwidth-bound field kernel of another); `step` fans out and joins the streams.
-    Either way replica r is the stand-alone run of seed + r, bit for bit."""
+    Either way replica r is the stand-alone run of seeds[r] (default seed + r), bit for bit.  `seeds=[s] * R` starts every
+    replica from the same world (how a population of candidates is compared)."""
 
     def __init__(self, field_size: Tuple[int, int], dynamics: Optional[Dynamics] = None, *, replicas: int, seed: int = 0,
-                 field_dtype: torch.dtype = torch.float32, device=None, per_replica: Optional[bool] = None):
+                 field_dtype: torch.dtype = torch.float32, device=None, per_replica: Optional[bool] = None,
+                 seeds: Optional[Sequence[int]] = None):
         if not 1 <= replicas <= 64:
             raise ValueError('1..64 replicas')
+        if seeds is not None and len(seeds) != replicas:
+            raise ValueError(f'{len(seeds)} seeds for {replicas} replicas')
         self.dynamics = dynamics or Dynamics()
         d = self.dynamics
         if d.agents_die or d.apply_sense_mask or d.diffuse_mode != 'wrap' or not isinstance(d.boundary, BoundaryCondition):
             raise NotImplementedError('batched replicas: wrap diffusion, no agents_die, no sense mask')
         self.R, self.seed = int(replicas), int(seed)
+        self.seeds = [self.seed + r for r in range(self.R)] if seeds is None else [int(q) for q in seeds]
         self.W, self.H = int(field_size[0]), int(field_size[1])
         self.device = torch.device(device if device is not None else f'cuda:{torch.cuda.current_device()}')
         self.dtype = field_dtype
         self.per_replica = (self.W * self.H >= Env.PIC_MIN_CELLS) if per_replica is None else bool(per_replica)
         if self.per_replica:
-            self.envs = [Env(field_size, d, seed=self.seed + r, max_agents='alive', field_dtype=field_dtype, device=self.device,
+            self.envs = [Env(field_size, d, seed=self.seeds[r], max_agents='alive', field_dtype=field_dtype, device=self.device,
                              sync=False) for r in range(self.R)]
             self.n = [e.agents.N for e in self.envs]
             self.Nmax = max(self.n)
@@ -50,13 +62,13 @@ class BatchedEnv:
             self._obs = [e._get_current_obs for e in self.envs]
             self._steps = 0
             return
-        # every replica starts as the stand-alone Env with seed + r would; its state is copied into slice r
-        envs = [Env(field_size, d, seed=self.seed + r, max_agents='alive', field_dtype=field_dtype, device=self.device, sort_every=0,
+        # every replica starts as the stand-alone Env with seeds[r] would; its state is copied into slice r
+        envs = [Env(field_size, d, seed=self.seeds[r], max_agents='alive', field_dtype=field_dtype, device=self.device, sort_every=0,
                     pic=False) for r in range(self.R)]
         self.n = [e.agents.N for e in envs]
         for r, e in enumerate(envs):
             if not e._all_alive:            # (only a world seeded with no agent at all: 'alive' keeps one dead placeholder slot)
-                raise NotImplementedError(f'batched replicas: replica {r} (seed {self.seed + r}) has no alive agent; dead slots are '
+                raise NotImplementedError(f'batched replicas: replica {r} (seed {self.seeds[r]}) has no alive agent; dead slots are '
                                           'not modelled by the batched step')
         self.Nmax = max(self.n)
         R, W, H, Nm, dev = self.R, self.W, self.H, self.Nmax, self.device
@@ -98,9 +110,13 @@ class BatchedEnv:
             for e in self.envs:
                 e.check()
 
-    def step(self, agent: 'BatchedPhysarumAgent', results: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """One step of every replica: `agent.forward` + `Env.step` fused, two launches for the whole batch.  Returns the
-        (R, 2) float64 tensor of die_step_result words (device; `read_results` decodes)."""
+    def step(self, agent: Union['BatchedPhysarumAgent', 'BatchedNeuralAutomataAgent'],
+             results: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One step of every replica: `agent.forward` + `Env.step` fused, two launches for the whole batch (L + 2 for a
+        BatchedNeuralAutomataAgent of L layers).  Returns the (R, 2) float64 tensor of die_step_result words (device;
+        `read_results` decodes)."""
+        if isinstance(agent, BatchedNeuralAutomataAgent):
+            return self._step_nca(agent, results)
         if results is None:
             results = torch.empty((self.R, 2), dtype=torch.float64, device=self.device)
         if self.per_replica:
@@ -129,7 +145,39 @@ class BatchedEnv:
         self._steps += 1
         return results
 
-    def run(self, agent: 'BatchedPhysarumAgent', n_steps: int) -> torch.Tensor:
+    def _step_nca(self, agent: 'BatchedNeuralAutomataAgent', results: Optional[torch.Tensor]) -> torch.Tensor:
+        agent._check_step(self)                     # every refusal before anything is launched
+        if results is None:
+            results = torch.empty((self.R, 2), dtype=torch.float64, device=self.device)
+        if self.per_replica:
+            cur = torch.cuda.current_stream(self.device)
+            start = cur.record_event()
+            for r, (e, st) in enumerate(zip(self.envs, self.streams)):
+                st.wait_event(start)
+                with torch.cuda.stream(st):
+                    self._obs[r], res, *_ = e.step(agent._replica_agent(r).forward(self._obs[r]))
+                    results[r].copy_(res)
+                cur.wait_stream(st)
+            agent._calls += 1
+            self._steps += 1
+            return results
+        # the sensing reads the claim plane at the current epoch, the claims are made at the next one; at the wrap the
+        # library clears the claim planes between the two (Env.step runs forward before its next_epoch the same way)
+        sense_epoch = self.epoch
+        self.epoch = sense_epoch % _lib.OWNER_EPOCH_MAX + 1
+        m, a, dyn, b = self._structs()
+        nca = agent._struct(sense_epoch)
+        rc = _lib.lib.die_nca_env_step_batch(C.byref(m), C.byref(a), C.byref(nca), None, C.byref(dyn), C.byref(b), _ptr(results),
+                                             _ptr(self._ws), self._ws.numel(), stream_ptr(self.device))
+        if rc != _lib.DIE_OK:
+            self.epoch = sense_epoch                # refused before any launch: nothing changed
+            _lib.check(rc, 'die_nca_env_step_batch')
+        agent._calls += 1
+        self.chem, self.chem_next = self.chem_next, self.chem
+        self._steps += 1
+        return results
+
+    def run(self, agent: Union['BatchedPhysarumAgent', 'BatchedNeuralAutomataAgent'], n_steps: int) -> torch.Tensor:
         out = torch.empty((n_steps, self.R, 2), dtype=torch.float64, device=self.device)
         for i in range(n_steps):
             self.step(agent, out[i])
@@ -193,3 +241,130 @@ class BatchedPhysarumAgent:
             return self.agents[r].direction_rads_numpy()
         k = self.env.n[r]
         return join64(self._hd_hi[r, :k].contiguous(), self._hd_lo[r, :k].contiguous()).cpu().numpy()
+
+
+def _architecture(agent: NeuralAutomataAgent) -> dict:
+    """What every candidate of a population shares: the stack's shape, its boundary, the observed channels, the action scale."""
+    layers = agent.model.conv_layers()
+    return dict(kernel_sizes=tuple(int(k.kernel_size[0]) for k in layers), boundary=tuple(k.padding_mode for k in layers),
+                with_agent_channel=len(agent.obs_channels) == 3, scale=agent.action_coefs[0], deposit=agent.action_coefs[2],
+                shapes=tuple(tuple(k.weight.shape) for k in layers))
+
+
+class BatchedNeuralAutomataAgent:
+    """A population of R NeuralAutomataAgent candidates of one architecture, candidate r stepping replica r of a BatchedEnv.
+    The weights are ONE (R, P) float32 device tensor `parameters`: row r is `parameters_to_vector(model.parameters())` of
+    candidate r — the layout evolution strategies hand around.  In-place writes to `parameters` are seen by the next step."""
+
+    def __init__(self, env: BatchedEnv, template: NeuralAutomataAgent, parameters=None):
+        if not isinstance(template, NeuralAutomataAgent):
+            raise TypeError('template: a NeuralAutomataAgent')
+        self.env, self.template, self.R = env, template, env.R
+        self._arch = _architecture(template)
+        layers = template.model.conv_layers()
+        for k in layers:
+            if k.padding_mode not in _lib.PAD_MODES:
+                raise NotImplementedError(f"boundary={k.padding_mode!r}: one of {sorted(_lib.PAD_MODES)}")
+        if len(set(self._arch['boundary'])) != 1 or len(layers) > _lib.NCA_MAX_LAYERS:
+            raise NotImplementedError(f'one boundary for every layer, at most {_lib.NCA_MAX_LAYERS} layers')
+        self._layers = []                           # (k, cin, cout, offset in a row)
+        off = 0
+        for k in layers:
+            cout, cin, kk, _ = k.weight.shape
+            self._layers.append((int(kk), int(cin), int(cout), off))
+            off += k.weight.numel()
+        self.P = off
+        if parameters is None:
+            parameters = parameters_to_vector(template.model.parameters()).detach().reshape(1, -1).expand(self.R, -1)
+        self.parameters = torch.empty((self.R, self.P), dtype=torch.float32, device=env.device)
+        self.set_parameters(parameters)
+        self._calls = 0
+        self._c = None                              # (parameters' address, NcaLayer array, NcaBatch) of the last step
+        if env.per_replica:
+            self.agents = [self.unpack(template, self.parameters[r]) for r in range(self.R)]
+            return
+        self._scratch = torch.empty(int(_lib.lib.die_nca_batch_scratch_bytes(env.W, env.H, self.R, len(layers))) // 4,
+                                    dtype=torch.float32, device=env.device)
+
+    @classmethod
+    def from_agents(cls, env: BatchedEnv, agents: Sequence[NeuralAutomataAgent]) -> 'BatchedNeuralAutomataAgent':
+        """Candidate r = agents[r]; every agent must share agents[0]'s architecture."""
+        if len(agents) != env.R:
+            raise ValueError(f'{len(agents)} agents for {env.R} replicas')
+        want = _architecture(agents[0])
+        for r, ag in enumerate(agents):
+            if _architecture(ag) != want:
+                raise ValueError(f'agent {r}: architecture {_architecture(ag)} differs from agent 0\'s {want}')
+        return cls(env, agents[0], cls.pack(agents))
+
+    # ------------------------------------------------------------------ parameters
+    @staticmethod
+    def pack(agents: Sequence[NeuralAutomataAgent]) -> torch.Tensor:
+        """(R, P) float32: row r = parameters_to_vector of agents[r]'s model (on that model's device)."""
+        return torch.stack([parameters_to_vector(ag.model.parameters()).detach().to(torch.float32) for ag in agents])
+
+    @staticmethod
+    def unpack(template: NeuralAutomataAgent, row: torch.Tensor) -> NeuralAutomataAgent:
+        """A stand-alone agent of the template's constructor arguments whose weights are `row` (copied)."""
+        args = dict(template.init_params)
+        args.update(args.pop('model_kwargs', {}))
+        with torch.random.fork_rng(devices=[]):     # (the throw-away initial weights leave the caller's RNG alone)
+            ag = NeuralAutomataAgent(**args)
+        ag.model.train(template.model.training)
+        ref = next(ag.model.parameters())
+        vector_to_parameters(row.detach().to(device=ref.device, dtype=ref.dtype).clone(), ag.model.parameters())
+        return ag
+
+    def set_parameters(self, parameters) -> None:
+        """Copy an (R, P) matrix of candidate rows in."""
+        t = torch.as_tensor(parameters)
+        if tuple(t.shape) != (self.R, self.P):
+            raise ValueError(f'parameters of shape {tuple(t.shape)}: ({self.R}, {self.P}) expected (R replicas x P weights)')
+        self.parameters.copy_(t.detach())
+
+    def candidate(self, r: int) -> NeuralAutomataAgent:
+        """Candidate r as a stand-alone NeuralAutomataAgent (on the host: `save()` the winner)."""
+        return self.unpack(self.template, self.parameters[r].cpu())
+
+    def _replica_agent(self, r: int) -> NeuralAutomataAgent:
+        ag = self.agents[r]                         # row r is reloaded every step: in-place writes are seen
+        vector_to_parameters(self.parameters[r].detach(), ag.model.parameters())
+        return ag
+
+    # ------------------------------------------------------------------ step
+    def _check_step(self, env: BatchedEnv):
+        if env is not self.env:
+            raise ValueError('this population was built for another BatchedEnv')
+        p = self.parameters
+        if tuple(p.shape) != (self.R, self.P) or p.dtype != torch.float32 or p.device != env.device or not p.is_contiguous():
+            raise ValueError(f'parameters must stay a contiguous ({self.R}, {self.P}) float32 tensor on {env.device}')
+        model = self.template.model
+        if model.agent_dropout.p > 0 and model.training:
+            raise NotImplementedError('p_agent_dropout > 0 in training mode: its mask is a host-RNG torch op, not batched '
+                                      '(call model.eval(), or step the candidates one at a time)')
+        if env.dynamics.op_food_flow is not _identity_food_flow:
+            raise NotImplementedError('a food-flow operator is not batched: step the candidates one at a time')
+
+    def _struct(self, sense_epoch: int) -> _lib.NcaBatch:
+        base = self.parameters.data_ptr()
+        if self._c is None or self._c[0] != base:
+            layers = (_lib.NcaLayer * len(self._layers))(*[_lib.NcaLayer(k, cin, cout, 0, base + 4 * off, self.P)
+                                                            for k, cin, cout, off in self._layers])
+            nca = _lib.NcaBatch(len(self._layers), _lib.PAD_MODES[self._arch['boundary'][0]], int(self._arch['with_agent_channel']), 0,
+                                layers, (C.c_float * 3)(*self.template.action_coefs), 0, _ptr(self._scratch),
+                                self._scratch.numel() * 4)
+            self._c = (base, layers, nca)
+        nca = self._c[2]
+        nca.sense_epoch = sense_epoch
+        return nca
+
+    def render(self, r: int) -> np.ndarray:
+        """Replica r's last sense planes with the channel axis last: the stand-alone agent's `render()[0]`."""
+        if self.env.per_replica:
+            torch.cuda.synchronize(self.env.device)
+            return self.agents[r].render()[0]
+        if self._calls == 0:
+            return np.ones((2, 2, 3))
+        L, W, H = len(self._layers), self.env.W, self.env.H
+        sets = self._scratch.view(-1, self.R, 4, W, H)
+        return torch.moveaxis(sets[(L - 1) % sets.shape[0], r, :3], 0, -1).cpu().numpy()

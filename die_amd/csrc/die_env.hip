@@ -7,6 +7,8 @@
 //                  _agent_lifecycle (:245-261) when agents_die; alive count
 //   k_reduce       fixed-order sum of the per-block partials → die_step_result (deterministic)
 //   k_diffuse      _medium_diffuse_decay (:136-145): separable gaussian, periodic, × (1 − decay)
+//   k_nca_move_claim_batch  a NeuralAutomataAgent population (die_nca_env_step_batch): every agent reads its action out of
+//                  its candidate's last conv planes (die_gather_scale's product, in registers), then k_move_claim's work
 //
 // Why two agent passes: every slot on a cell must read the food value from BEFORE the step's
 // consumption (co-located agents each get the full amount, :224-225), so all reads of `food`
@@ -184,6 +186,43 @@ __global__ __launch_bounds__(DIE_STEP_BLOCK) void k_forward_move_claim_batch(Fwd
     a.part_alive = a.part_gain + 2 * DIE_MAX_PARTIALS;
     forward_move_claim_body<T, KIND, false>(f, a);
     if (blockIdx.x == 0 && threadIdx.x == 0) a.part_alive[0] = a.N;  // every slot is alive: the sweep's reduction reads the count here
+}
+
+// NeuralAutomataAgent population (die_nca_env_step_batch): replica r's agents read their action out of the last layer's
+// planes of candidate r — die_gather_scale's product, kept in registers — then k_forward_move_claim_batch's step half.
+struct NcaReadArgs {
+    const float* sense;            // replica 0's (dx, dy, deposit) planes, `cells` apart; replica r's `rep` further
+    int64_t cells, rep;
+    float coef[3];
+    float* act[3];                 // replica 0's action arrays (agent_stride apart), or NULL
+};
+
+template <typename T>
+__global__ __launch_bounds__(DIE_STEP_BLOCK) void k_nca_move_claim_batch(NcaReadArgs q, StepArgs a, BatchArgs b) {
+    const int r = blockIdx.y;
+    const int64_t pc = b.cells * r, pa = b.agents * r;
+    a.owner += pc; a.food = (T*)a.food + pc; a.chem = (T*)a.chem + pc;
+    a.x += pa; a.y += pa; a.alive += pa; a.agent_food += pa;
+    a.N = b.n[r];
+    a.part_gain += (int64_t)DIE_MAX_PARTIALS * 3 * r;
+    a.part_alive = a.part_gain + 2 * DIE_MAX_PARTIALS;
+    const float* s0 = q.sense + q.rep * r;
+    const float* s1 = s0 + q.cells;
+    const float* s2 = s1 + q.cells;
+    long long gsum = 0;
+    long long cnt = 0;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < a.N; n += stride) {
+        const uint32_t X = a.x[n], Y = a.y[n];
+        const int64_t c = die_local(a.g, die_cell((int64_t)X, a.g.gW), die_cell((int64_t)Y, a.g.gH));
+        const float dx = s0[c] * q.coef[0];
+        const float dy = s1[c] * q.coef[1];
+        const float dep = s2[c] * q.coef[2];
+        if (q.act[0]) { q.act[0][pa + n] = dx; q.act[1][pa + n] = dy; q.act[2][pa + n] = dep; }
+        gsum += die_fix(move_claim_one<T, false>(a, n, X, Y, dx, dy, dep, (uint32_t)n, cnt));
+    }
+    block_sum_store(gsum, cnt, a.part_gain, a.part_alive);
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.part_alive[0] = a.N;  // every slot is alive (as k_forward_move_claim_batch)
 }
 
 template <typename T>
@@ -997,6 +1036,54 @@ extern "C" int64_t die_batch_workspace_bytes(int32_t replicas) {
     return replicas >= 1 && replicas <= DIE_MAX_REPLICAS ? (int64_t)replicas * WS_PARTS : -1;
 }
 
+// the step half's arguments of every replica (die_forward_env_step_batch, die_nca_env_step_batch), checked before any launch
+static int batch_step_args(StepArgs& k, BatchArgs& ba, int64_t& nmax, const die_medium* m, const die_agents* a, const die_action* act,
+                           const die_dynamics* d, const die_batch* b, void* ws, const char* who) {
+    // fill_args checks the per-replica workspace of the single-world step; here only the partial arrays are used
+    DIE_REQUIRE(m->epoch >= 1 && m->epoch <= DIE_OWNER_EPOCH_MAX && m->owner && a->alive && a->agent_food, "%s: bad medium / agents", who);
+    if (d->boundary != DIE_BOUNDARY_WRAP && d->boundary != DIE_BOUNDARY_LIMIT) {
+        die_set_error("%s: boundary %d is not representable in Q0.32", who, d->boundary);
+        return DIE_ERR_UNSUPPORTED;
+    }
+    DIE_REQUIRE(d->cost == DIE_COST_LINEAR || d->cost == DIE_COST_ZERO, "%s: bad cost operator %d", who, d->cost);
+    k = StepArgs{};
+    k.g = die_geo_of(m); k.epoch = m->epoch; k.N = a->N; k.do_move = 1; k.do_claim = 1; k.tile_w = k.tile_h = k.tiles_y = 1;
+    k.owner = (unsigned long long*)m->owner; k.food = m->food; k.chem = m->chem;
+    k.x = a->x; k.y = a->y; k.slot = a->slot; k.alive = a->alive; k.agent_food = a->agent_food;
+    k.dx = act ? act->dx : nullptr; k.dy = act ? act->dy : nullptr; k.dep = act ? act->deposit : nullptr;
+    k.rate_feed = d->rate_feed; k.w_dep = d->cost_w_deposit; k.w_dist = d->cost_w_dist;
+    k.boundary = d->boundary; k.cost = d->cost; k.food_infinite = d->food_infinite;
+    k.part_gain = (long long*)ws;
+    ba.cells = b->plane_stride; ba.agents = b->agent_stride; ba.seed_stride = b->seed_stride;
+    nmax = 0;
+    for (int r = 0; r < DIE_MAX_REPLICAS; ++r) {
+        ba.n[r] = r < b->replicas ? b->n[r] : 0;
+        DIE_REQUIRE(r >= b->replicas || (b->n[r] >= 1 && b->n[r] <= b->agent_stride), "%s: replica %d has %lld agents", who, r, (long long)b->n[r]);
+        if (ba.n[r] > nmax) nmax = ba.n[r];
+    }
+    return DIE_OK;
+}
+
+// the field sweep of every replica in one launch (gridDim.z), each with its own reduction workgroup over the n_part partials
+static int batch_sweep(const die_medium* m, const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws, int n_part,
+                       hipStream_t s, const char* who) {
+    const int R = (int)(4.0 * (double)d->diffuse_sigma + 0.5);
+    RowsArgs ra;
+    double wd[2 * DIF_MAXR + 1];
+    gaussian_taps(d->diffuse_sigma, wd);
+    ra.src = m->chem; ra.dst = m->chem_next; ra.claim = (const unsigned long long*)m->owner; ra.dep = nullptr; ra.food = m->food;
+    ra.W = m->W; ra.H = m->H; ra.epoch = m->epoch; ra.food_infinite = d->food_infinite; ra.halo = 0; ra.rep_cells = b->plane_stride;
+    ra.wrapx = ra.wrapy = 1;
+    ra.part_gain = (const long long*)ws; ra.part_alive = (const long long*)ws + 2 * DIE_MAX_PARTIALS; ra.n_part = n_part;
+    ra.result = results; ra.alive_const = 0;
+    ra.keep = (float)(1.0 - (double)d->rate_decay_chem); ra.rate_feed = d->rate_feed;
+    for (int q = 0; q <= 2 * R; ++q) ra.w[q] = (float)wd[q];
+    const int rc = m->dtype == DIE_F32 ? launch_rows<float, 1, true>(ra, R, s, b->replicas) : launch_rows<__half, 1, true>(ra, R, s, b->replicas);
+    if (rc != DIE_OK) return rc;
+    DIE_CHECK_LAUNCH(who);
+    return DIE_OK;
+}
+
 extern "C" int die_forward_env_step_batch(const die_medium* m, const die_agents* a, die_gradient_agent* g, const die_action* act,
                                           const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws,
                                           int64_t ws_bytes, void* stream) {
@@ -1015,29 +1102,11 @@ extern "C" int die_forward_env_step_batch(const die_medium* m, const die_agents*
     FwdArgs f;
     int rc = die_fill_fwd_args(f, m, a, g, act, who);
     if (rc != DIE_OK) return rc;
-    // fill_args checks the per-replica workspace of the single-world step; here only the partial arrays are used
-    DIE_REQUIRE(m->epoch >= 1 && m->epoch <= DIE_OWNER_EPOCH_MAX && m->owner && a->alive && a->agent_food, "%s: bad medium / agents", who);
-    if (d->boundary != DIE_BOUNDARY_WRAP && d->boundary != DIE_BOUNDARY_LIMIT) {
-        die_set_error("%s: boundary %d is not representable in Q0.32", who, d->boundary);
-        return DIE_ERR_UNSUPPORTED;
-    }
-    DIE_REQUIRE(d->cost == DIE_COST_LINEAR || d->cost == DIE_COST_ZERO, "%s: bad cost operator %d", who, d->cost);
-    StepArgs k = {};
-    k.g = die_geo_of(m); k.epoch = m->epoch; k.N = a->N; k.do_move = 1; k.do_claim = 1; k.tile_w = k.tile_h = k.tiles_y = 1;
-    k.owner = (unsigned long long*)m->owner; k.food = m->food; k.chem = m->chem;
-    k.x = a->x; k.y = a->y; k.slot = a->slot; k.alive = a->alive; k.agent_food = a->agent_food;
-    k.dx = act ? act->dx : nullptr; k.dy = act ? act->dy : nullptr; k.dep = act ? act->deposit : nullptr;
-    k.rate_feed = d->rate_feed; k.w_dep = d->cost_w_deposit; k.w_dist = d->cost_w_dist;
-    k.boundary = d->boundary; k.cost = d->cost; k.food_infinite = d->food_infinite;
-    k.part_gain = (long long*)ws;
+    StepArgs k;
     BatchArgs ba;
-    ba.cells = b->plane_stride; ba.agents = b->agent_stride; ba.seed_stride = b->seed_stride;
-    int64_t nmax = 0;
-    for (int r = 0; r < DIE_MAX_REPLICAS; ++r) {
-        ba.n[r] = r < b->replicas ? b->n[r] : 0;
-        DIE_REQUIRE(r >= b->replicas || (b->n[r] >= 1 && b->n[r] <= b->agent_stride), "%s: replica %d has %lld agents", who, r, (long long)b->n[r]);
-        if (ba.n[r] > nmax) nmax = ba.n[r];
-    }
+    int64_t nmax;
+    rc = batch_step_args(k, ba, nmax, m, a, act, d, b, ws, who);
+    if (rc != DIE_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(step_grid(nmax), b->replicas);
     if (m->dtype == DIE_F32) {
@@ -1050,22 +1119,59 @@ extern "C" int die_forward_env_step_batch(const die_medium* m, const die_agents*
         else k_forward_move_claim_batch<__half, DIE_AGENT_PHYSARUM><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba);
     }
     DIE_CHECK_LAUNCH(who);
-    // the field sweep of every replica in one launch (gridDim.z), each with its own reduction workgroup
-    const int R = (int)(4.0 * (double)d->diffuse_sigma + 0.5);
-    RowsArgs ra;
-    double wd[2 * DIF_MAXR + 1];
-    gaussian_taps(d->diffuse_sigma, wd);
-    ra.src = m->chem; ra.dst = m->chem_next; ra.claim = (const unsigned long long*)m->owner; ra.dep = nullptr; ra.food = m->food;
-    ra.W = m->W; ra.H = m->H; ra.epoch = m->epoch; ra.food_infinite = d->food_infinite; ra.halo = 0; ra.rep_cells = b->plane_stride;
-    ra.wrapx = ra.wrapy = 1;
-    ra.part_gain = (const long long*)ws; ra.part_alive = (const long long*)ws + 2 * DIE_MAX_PARTIALS; ra.n_part = (int)grid.x;
-    ra.result = results; ra.alive_const = 0;
-    ra.keep = (float)(1.0 - (double)d->rate_decay_chem); ra.rate_feed = d->rate_feed;
-    for (int q = 0; q <= 2 * R; ++q) ra.w[q] = (float)wd[q];
-    rc = m->dtype == DIE_F32 ? launch_rows<float, 1, true>(ra, R, s, b->replicas) : launch_rows<__half, 1, true>(ra, R, s, b->replicas);
+    return batch_sweep(m, d, b, results, ws, (int)grid.x, s, who);
+}
+
+int die_nca_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who);       // die_nca.hip
+int die_nca_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
+                        void* stream);
+
+extern "C" int die_nca_env_step_batch(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
+                                      const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws,
+                                      int64_t ws_bytes, void* stream) {
+    const char* who = "die_nca_env_step_batch";
+    DIE_REQUIRE(m && a && nca && d && b && results && ws, "%s: null argument", who);
+    DIE_REQUIRE(b->replicas >= 1 && b->replicas <= DIE_MAX_REPLICAS, "%s: 1..%d replicas", who, DIE_MAX_REPLICAS);
+    DIE_REQUIRE(ws_bytes >= die_batch_workspace_bytes(b->replicas), "%s: workspace too small", who);
+    DIE_REQUIRE(m->gW <= 0 && !m->sense_mask && !d->has_dead_slots && !d->agents_die && !d->staged && !a->slot,
+                "%s: periodic single-tile replicas with every slot alive, in slot order (no agents_die, no sense mask)", who);
+    DIE_REQUIRE(m->food && m->chem && m->chem_next && m->chem_next != m->chem, "%s: null plane, or chem_next not a second plane", who);
+    DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad field dtype %d", who, m->dtype);
+    DIE_REQUIRE(a->x && a->y, "%s: null agent arrays", who);
+    DIE_REQUIRE(b->plane_stride >= (int64_t)m->W * m->H && b->agent_stride >= a->N, "%s: strides smaller than a replica", who);
+    if (!fused_step_applies(m, d)) {
+        die_set_error("%s: only for periodic planes with H %% 4 == 0 and gaussian radius 1..4", who);
+        return DIE_ERR_UNSUPPORTED;
+    }
+    int rc = die_nca_batch_check(nca, m->W, m->H, b->replicas, who);
     if (rc != DIE_OK) return rc;
+    DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX && m->epoch == nca->sense_epoch % DIE_OWNER_EPOCH_MAX + 1,
+                "%s: claims at epoch %d cannot follow sensing at epoch %d", who, m->epoch, nca->sense_epoch);
+    DIE_REQUIRE(!act || (act->dx && act->dy && act->deposit), "%s: bad action arrays", who);
+    StepArgs k;
+    BatchArgs ba;
+    int64_t nmax;
+    rc = batch_step_args(k, ba, nmax, m, a, act, d, b, ws, who);
+    if (rc != DIE_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    NcaReadArgs q;
+    rc = die_nca_sense_batch(m, b, nca, &q.sense, &q.rep, stream);            // reads the claim plane at sense_epoch …
+    if (rc != DIE_OK) return rc;
+    if (nca->sense_epoch == DIE_OWNER_EPOCH_MAX) {                    // … which is cleared before the tag 1 claims
+        const int64_t words = (int64_t)(b->replicas - 1) * b->plane_stride + (int64_t)m->W * m->H;
+        if (hipMemsetAsync(m->owner, 0, (size_t)words * sizeof(unsigned long long), s) != hipSuccess) {
+            die_set_error("%s: clearing the claim planes failed", who);
+            return DIE_ERR_HIP;
+        }
+    }
+    q.cells = (int64_t)m->W * m->H;
+    for (int c = 0; c < 3; ++c) q.coef[c] = nca->coef[c];
+    q.act[0] = act ? act->dx : nullptr; q.act[1] = act ? act->dy : nullptr; q.act[2] = act ? act->deposit : nullptr;
+    dim3 grid(step_grid(nmax), b->replicas);
+    if (m->dtype == DIE_F32) k_nca_move_claim_batch<float><<<grid, DIE_STEP_BLOCK, 0, s>>>(q, k, ba);
+    else k_nca_move_claim_batch<__half><<<grid, DIE_STEP_BLOCK, 0, s>>>(q, k, ba);
     DIE_CHECK_LAUNCH(who);
-    return DIE_OK;
+    return batch_sweep(m, d, b, results, ws, (int)grid.x, s, who);
 }
 
 static int deposit_feed_diffuse(const die_medium* m, const die_dynamics* d, int halo, bool tile, void* stream,

@@ -9,6 +9,9 @@
 //                     stores).  The first layer reads the medium's own planes: fp32 / fp16 fields, and the 'agents'
 //                     channel straight from the claim plane (occupied ⇔ epoch tag).  The last layer applies tanh.
 //   k_gather_scale    action[c, n] = plane[c][cell(x_n), cell(y_n)] · coef[c] for EVERY slot (only_alive = False).
+//   die_nca_env_step_batch (a population of candidates on batched replicas) runs k_conv_circular<K, true>: the same body
+//                     with the replica in blockIdx.z (its planes, weights and outputs one stride further each); the read-out
+//                     and the step half are k_nca_move_claim_batch in die_env.hip.
 //
 // Roofline: HBM.  A 3→3 channel 3×3 layer is 81 MAC per cell against 24 bytes per cell (3 planes in, 3 out): 6.75 flop
 // per byte, far below the ≈ 20 flop/byte at which fp32 vector math (157 TFLOP/s) meets 8 TB/s — no MFMA: the matrix
@@ -27,6 +30,7 @@ struct ConvArgs {
     const float* w;              // [cout][cin][k][k]
     int W, H, cin, cout, k, epoch, apply_tanh;
     int pad;                     // die_pad_mode: how cells beyond the field are read ('same' padding of torch's Conv2d)
+    int64_t rep_in, rep_w, rep_out;  // batch (gridDim.z = replicas): elements from replica r's planes / weights to r + 1's
 };
 
 // index of the cell that stands in for coordinate v of an axis of n cells, or −1 for "reads as zero" (torch.nn.functional.pad:
@@ -48,15 +52,19 @@ __device__ __forceinline__ float nca_load(const void* p, int kind, int64_t i, in
     return die_claim_occupied(((const unsigned long long*)p)[i], epoch) ? 1.f : 0.f;
 }
 
-template <int K>
+// BATCH: replica blockIdx.z of die_nca_env_step_batch — its input planes, weights and output planes lie blockIdx.z strides
+// on; everything else (tile, LDS, summation order, tanh) is this one body.
+template <int K, bool BATCH = false>
 __global__ __launch_bounds__(DIE_BLOCK) void k_conv_circular(ConvArgs a) {
     constexpr int R = K / 2, LX = NCA_TX + 2 * R, LY = NCA_TY + 2 * R + 1;     // odd pitch: conflict-free column walks
     extern __shared__ __align__(16) float nca_smem[];
     float* s_in = nca_smem;                                  // [cin][LX][LY]
     float* s_w = nca_smem + a.cin * LX * LY;                 // [cout][cin][K][K]
     const int x0 = blockIdx.y * NCA_TX, y0 = blockIdx.x * NCA_TY;
+    const int64_t rep = BATCH ? (int64_t)blockIdx.z : 0;
+    const float* w = a.w + rep * a.rep_w;
     const int nw = a.cout * a.cin * K * K;
-    for (int i = threadIdx.x; i < nw; i += DIE_BLOCK) s_w[i] = a.w[i];
+    for (int i = threadIdx.x; i < nw; i += DIE_BLOCK) s_w[i] = w[i];
     constexpr int LYV = NCA_TY + 2 * R;
     for (int c = 0; c < a.cin; ++c) {
         for (int i = threadIdx.x; i < LX * LYV; i += DIE_BLOCK) {
@@ -64,7 +72,7 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_circular(ConvArgs a) {
             // (rows / columns past the last tile's outputs wrap like a circular field whatever the mode: never used)
             const int vx = x0 - R + li, vy = y0 - R + lj;
             const int gx = nca_pad_index(vx < a.W + R ? vx : vx % a.W, a.W, a.pad), gy = nca_pad_index(vy < a.H + R ? vy : vy % a.H, a.H, a.pad);
-            s_in[(c * LX + li) * LY + lj] = (gx < 0 || gy < 0) ? 0.f : nca_load(a.in[c], a.kind[c], (int64_t)gx * a.H + gy, a.epoch);
+            s_in[(c * LX + li) * LY + lj] = (gx < 0 || gy < 0) ? 0.f : nca_load(a.in[c], a.kind[c], rep * a.rep_in + (int64_t)gx * a.H + gy, a.epoch);
         }
     }
     __syncthreads();
@@ -101,13 +109,26 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_circular(ConvArgs a) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = tanhf(v[q]);
             }
-            float* dst = a.out[o] + (int64_t)gx * a.H + gy;
+            float* dst = a.out[o] + rep * a.rep_out + (int64_t)gx * a.H + gy;
             if (gy + 3 < a.H && (a.H & 3) == 0) *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
             else {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) if (gy + q < a.H) dst[q] = v[q];
             }
         }
+    }
+}
+
+template <bool BATCH>
+static void launch_conv(const ConvArgs& a, int replicas, hipStream_t s) {
+    const int R = a.k / 2;
+    const size_t lds = ((size_t)a.cin * (NCA_TX + 2 * R) * (NCA_TY + 2 * R + 1) + (size_t)a.cout * a.cin * a.k * a.k) * sizeof(float);
+    dim3 grid((a.H + NCA_TY - 1) / NCA_TY, (a.W + NCA_TX - 1) / NCA_TX, replicas);
+    switch (a.k) {
+        case 1: k_conv_circular<1, BATCH><<<grid, DIE_BLOCK, lds, s>>>(a); break;
+        case 3: k_conv_circular<3, BATCH><<<grid, DIE_BLOCK, lds, s>>>(a); break;
+        case 5: k_conv_circular<5, BATCH><<<grid, DIE_BLOCK, lds, s>>>(a); break;
+        default: k_conv_circular<7, BATCH><<<grid, DIE_BLOCK, lds, s>>>(a); break;
     }
 }
 
@@ -141,16 +162,8 @@ extern "C" int die_conv2d(int32_t W, int32_t H, int32_t cin, const die_conv_plan
         for (int q = 0; q < cout && c < cin; ++q) DIE_REQUIRE((const void*)out[q] != in[c].data, "die_conv2d_circular: in-place convolution");
     }
     a.w = weights; a.W = W; a.H = H; a.cin = cin; a.cout = cout; a.k = k; a.epoch = epoch; a.apply_tanh = apply_tanh; a.pad = padding_mode;
-    const int R = k / 2;
-    const size_t lds = ((size_t)cin * (NCA_TX + 2 * R) * (NCA_TY + 2 * R + 1) + (size_t)cout * cin * k * k) * sizeof(float);
-    dim3 grid((H + NCA_TY - 1) / NCA_TY, (W + NCA_TX - 1) / NCA_TX);
-    hipStream_t s = (hipStream_t)stream;
-    switch (k) {
-        case 1: k_conv_circular<1><<<grid, DIE_BLOCK, lds, s>>>(a); break;
-        case 3: k_conv_circular<3><<<grid, DIE_BLOCK, lds, s>>>(a); break;
-        case 5: k_conv_circular<5><<<grid, DIE_BLOCK, lds, s>>>(a); break;
-        default: k_conv_circular<7><<<grid, DIE_BLOCK, lds, s>>>(a); break;
-    }
+    a.rep_in = a.rep_w = a.rep_out = 0;
+    launch_conv<false>(a, 1, (hipStream_t)stream);
     DIE_CHECK_LAUNCH("die_conv2d_circular");
     return DIE_OK;
 }
@@ -184,5 +197,71 @@ extern "C" int die_gather_scale(const die_medium* m, const die_agents* ag, const
     int64_t g = (ag->N + DIE_BLOCK - 1) / DIE_BLOCK;
     k_gather_scale<<<(int)(g < 8192 ? g : 8192), DIE_BLOCK, 0, (hipStream_t)stream>>>(a);
     DIE_CHECK_LAUNCH("die_gather_scale");
+    return DIE_OK;
+}
+
+// ---- die_nca_env_step_batch's sensing (the step itself: die_env.hip) --------------------------------------------------
+// Scratch: [set][replica][NCA_MAXC][W][H] fp32, set = layer % 2 (one set for a single layer); the last layer's planes stay
+// there until the next step (BatchedNeuralAutomataAgent.render).
+static int64_t nca_scratch_sets(int32_t n_layers) { return n_layers >= 2 ? 2 : 1; }
+
+extern "C" int64_t die_nca_batch_scratch_bytes(int32_t W, int32_t H, int32_t replicas, int32_t n_layers) {
+    if (W < 1 || H < 1 || replicas < 1 || replicas > DIE_MAX_REPLICAS || n_layers < 1 || n_layers > DIE_NCA_MAX_LAYERS) return -1;
+    return nca_scratch_sets(n_layers) * replicas * NCA_MAXC * (int64_t)W * H * (int64_t)sizeof(float);
+}
+
+// every argument of the stack, before anything is launched
+int die_nca_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who) {
+    DIE_REQUIRE(nca && nca->layers && nca->scratch, "%s: null stack, layer list or scratch", who);
+    DIE_REQUIRE(nca->n_layers >= 1 && nca->n_layers <= DIE_NCA_MAX_LAYERS, "%s: 1..%d layers (got %d)", who, DIE_NCA_MAX_LAYERS, nca->n_layers);
+    DIE_REQUIRE(nca->padding_mode >= DIE_PAD_CIRCULAR && nca->padding_mode <= DIE_PAD_REPLICATE, "%s: bad padding mode %d", who, nca->padding_mode);
+    DIE_REQUIRE(nca->with_agent_channel == 0 || nca->with_agent_channel == 1, "%s: with_agent_channel is 0 or 1", who);
+    const int64_t need = die_nca_batch_scratch_bytes(W, H, replicas, nca->n_layers);
+    DIE_REQUIRE(need > 0 && nca->scratch_bytes >= need, "%s: scratch too small (%lld < %lld)", who, (long long)nca->scratch_bytes, (long long)need);
+    int cin = 2 + nca->with_agent_channel;
+    for (int l = 0; l < nca->n_layers; ++l) {
+        const die_nca_layer& L = nca->layers[l];
+        if (!(L.k == 1 || L.k == 3 || L.k == 5 || L.k == 7)) {
+            die_set_error("%s: layer %d: kernel size %d (odd sizes up to %d)", who, l, L.k, NCA_MAXK);
+            return DIE_ERR_ARG;
+        }
+        DIE_REQUIRE(L.cin == cin && L.cout >= 1 && L.cout <= NCA_MAXC, "%s: layer %d: %d -> %d channels (input has %d, at most %d out)", who,
+                    l, L.cin, L.cout, cin, NCA_MAXC);
+        DIE_REQUIRE(L.weights && L.weight_stride >= (int64_t)L.cout * L.cin * L.k * L.k, "%s: layer %d: null weights or stride below a "
+                    "replica's block", who, l);
+        DIE_REQUIRE(nca->padding_mode != DIE_PAD_REFLECT || (L.k / 2 < W && L.k / 2 < H), "%s: layer %d: 'reflect' padding of %d cells "
+                    "needs a field larger than that (%dx%d)", who, l, L.k / 2, W, H);
+        cin = L.cout;
+    }
+    DIE_REQUIRE(cin == 3, "%s: the last layer gives %d planes (dx, dy, deposit: 3)", who, cin);
+    return DIE_OK;
+}
+
+// the stack for every replica, one launch per layer; *sense = the last layer's planes of replica 0, replica r's *rep further
+int die_nca_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
+                        void* stream) {
+    const int64_t cells = (int64_t)m->W * m->H, rep_scratch = NCA_MAXC * cells;
+    const int fkind = m->dtype == DIE_F32 ? DIE_PLANE_F32 : DIE_PLANE_F16;
+    ConvArgs a = {};
+    int c = 0;
+    if (nca->with_agent_channel) { a.in[c] = m->owner; a.kind[c++] = DIE_PLANE_AGENTS; }
+    a.in[c] = m->food; a.kind[c++] = fkind;
+    a.in[c] = m->chem; a.kind[c++] = fkind;
+    a.rep_in = b->plane_stride;
+    a.W = m->W; a.H = m->H; a.epoch = nca->sense_epoch; a.pad = nca->padding_mode;
+    float* out = nullptr;
+    for (int l = 0; l < nca->n_layers; ++l) {
+        const die_nca_layer& L = nca->layers[l];
+        out = nca->scratch + (l % nca_scratch_sets(nca->n_layers)) * b->replicas * rep_scratch;
+        for (int o = 0; o < NCA_MAXC; ++o) a.out[o] = o < L.cout ? out + o * cells : nullptr;
+        a.w = L.weights; a.rep_w = L.weight_stride; a.rep_out = rep_scratch;
+        a.cin = L.cin; a.cout = L.cout; a.k = L.k; a.apply_tanh = l == nca->n_layers - 1;
+        launch_conv<true>(a, b->replicas, (hipStream_t)stream);
+        DIE_CHECK_LAUNCH("die_nca_env_step_batch(conv)");
+        for (int o = 0; o < NCA_MAXC; ++o) { a.in[o] = a.out[o]; a.kind[o] = DIE_PLANE_F32; }
+        a.rep_in = rep_scratch;
+    }
+    *sense = out;
+    *rep = rep_scratch;
     return DIE_OK;
 }

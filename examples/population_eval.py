@@ -1,0 +1,121 @@
+"""The evaluation half of the reference's examples/learning_agents.py (`run_epoch`, lines 20-38) for a whole population at
+once: R NeuralAutomataAgent candidates, each scored by the sum of its rewards over `epoch_iters` steps of its own world,
+all R worlds stepped together by die_amd.batch (L + 2 launches per step for an L-layer model).
+
+    python examples/population_eval.py [--replicas 10] [--size 96] [--iters 50] [--generations 0] [--compare]
+
+--generations G runs a plain Gaussian evolution strategy (antithetic samples, normalised fitness) on the mean parameter
+vector — the training loop itself (evotorch's PGPE, MLflow) stays out of scope.  --compare times the same population one
+candidate at a time through `Env` + `NeuralAutomataAgent` (what a direct port of run_epoch does), checks that both give the
+same fitness, and prints candidate-steps/s for both.
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+from torch.nn.utils import parameters_to_vector
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from die_amd import Dynamics, Env, NeuralAutomataAgent                  # noqa: E402
+from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent        # noqa: E402
+
+AGENT_KW = dict(kernel_sizes=[3, 3], scale=0.01, deposit=2.0)           # learning_agents.py
+DYNAMICS_KW = dict(food_infinite=True, rate_decay_chem=0.025, diffuse_sigma=.8)
+
+
+def make_population(size, template, rows, seed):
+    R = rows.shape[0]
+    benv = BatchedEnv((size, size), Dynamics(**DYNAMICS_KW), replicas=R, seeds=[seed] * R)   # every world starts alike
+    return benv, BatchedNeuralAutomataAgent(benv, template, rows)
+
+
+def evaluate_population(benv, pop, iters):
+    """Fitness of every candidate: the sum of its world's rewards over `iters` steps (run_epoch for all of them)."""
+    rewards, _ = BatchedEnv.read_results(benv.run(pop, iters))
+    return [sum(rewards[:, r].tolist()) for r in range(benv.R)]        # (summed in step order, like run_epoch)
+
+
+def run_epoch(env, agent, iters):
+    """run_epoch of the reference, one candidate."""
+    obs, epoch_reward = env._get_current_obs, 0.
+    for _ in range(iters):
+        obs, reward, _, _, _ = env.step(agent.forward(obs))
+        epoch_reward += reward
+    return epoch_reward
+
+
+def one_at_a_time_worlds(size, R, seed):
+    return [Env((size, size), Dynamics(**DYNAMICS_KW), seed=seed, max_agents='alive') for _ in range(R)]
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument('--replicas', type=int, default=10)
+    p.add_argument('--size', type=int, default=96)
+    p.add_argument('--iters', type=int, default=50, help='epoch_iters: steps per evaluation')
+    p.add_argument('--generations', type=int, default=0)
+    p.add_argument('--sigma', type=float, default=0.1)
+    p.add_argument('--lr', type=float, default=0.05)
+    p.add_argument('--seed', type=int, default=0)
+    p.add_argument('--compare', action='store_true')
+    args = p.parse_args()
+    R = args.replicas
+    torch.manual_seed(args.seed)
+    template = NeuralAutomataAgent(**AGENT_KW)
+    cands = []
+    for _ in range(R):
+        template.model.init_weights()
+        cands.append(parameters_to_vector(template.model.parameters()).detach().clone())
+    rows = torch.stack(cands)
+    print(f'{R} candidates of {rows.shape[1]} parameters, {args.size}x{args.size}, {args.iters} steps each', flush=True)
+
+    benv, pop = make_population(args.size, template, rows, args.seed)
+    fitness = evaluate_population(benv, pop, args.iters)
+    for r, f in enumerate(fitness):
+        print(f'candidate {r:2d}: fitness {f:.6f}')
+    best = max(range(R), key=lambda r: fitness[r])
+    print(f'best: candidate {best} ({fitness[best]:.6f}); pop.candidate({best}).save(...) keeps it', flush=True)
+
+    if args.compare:
+        # only the stepping is timed (the worlds are built before); warm-up of both paths first
+        dev = torch.device('cuda')
+        agents = [pop.candidate(r).to(dev) for r in range(R)]
+        evaluate_population(*make_population(args.size, template, rows, args.seed), 2)
+        run_epoch(one_at_a_time_worlds(args.size, 1, args.seed)[0], agents[0], 2)
+        benv, pop = make_population(args.size, template, rows, args.seed)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        batched = evaluate_population(benv, pop, args.iters)
+        t_batch = time.perf_counter() - t0
+        worlds = one_at_a_time_worlds(args.size, R, args.seed)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        alone = [run_epoch(env, ag, args.iters) for env, ag in zip(worlds, agents)]
+        torch.cuda.synchronize()
+        t_alone = time.perf_counter() - t0
+        cs = R * args.iters
+        print(f'batched:       {cs / t_batch:12.0f} candidate-steps/s  ({t_batch * 1e3:.2f} ms)')
+        print(f'one at a time: {cs / t_alone:12.0f} candidate-steps/s  ({t_alone * 1e3:.2f} ms)')
+        print(f'speed-up: {t_alone / t_batch:.2f}x   same fitness: {batched == alone}', flush=True)
+        if batched != alone:
+            sys.exit('the batched fitness differs from the one-at-a-time fitness')
+
+    if args.generations and R < 2:
+        sys.exit('--generations needs at least 2 replicas (antithetic pairs)')
+    mean = rows.mean(dim=0)
+    for g in range(args.generations):
+        half = torch.randn((R // 2, mean.numel()))
+        noise = torch.cat([half, -half])                                    # antithetic pairs
+        samples = mean + args.sigma * noise
+        fit = evaluate_population(*make_population(args.size, template, samples, args.seed + 1 + g), args.iters)
+        f = torch.tensor(fit, dtype=torch.float32)
+        f = (f - f.mean()) / (f.std() + 1e-8)
+        mean = mean + args.lr / (noise.shape[0] * args.sigma) * (noise.T @ f)
+        print(f'generation {g}: mean fitness {sum(fit) / len(fit):.6f}  best {max(fit):.6f}', flush=True)
+
+
+if __name__ == '__main__':
+    main()

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define DIE_ABI_VERSION 23
+#define DIE_ABI_VERSION 24
 
 typedef enum die_status {
     DIE_OK = 0,
@@ -586,6 +586,41 @@ int die_conv2d(int32_t W, int32_t H, int32_t cin, const die_conv_plane* in, int3
  * action[c, n] = planes[c][cell(x_n), cell(y_n)] * coefs[c], c = dx, dy, deposit1. */
 int die_gather_scale(const die_medium* m, const die_agents* a, const float* const* planes, const float* coefs,
                      const die_action* out, void* stream);
+
+/* ---- A population of NeuralAutomataAgents on batched replicas (die_amd/batch.py BatchedNeuralAutomataAgent) ----------
+ * Replica r of a die_batch (same layout, same restrictions as die_forward_env_step_batch) is stepped by candidate r's
+ * ConvolutionModel: one launch per layer (k_conv_circular with the replica in blockIdx.z: same tile, same summation order,
+ * same tanh as die_conv2d), then one launch that reads every agent's action out of its replica's last planes
+ * (die_gather_scale's product) and moves / claims / feeds it, then die_forward_env_step_batch's field sweep.  Replica r
+ * computes exactly what die_conv2d per layer + die_gather_scale + die_env_step compute for that world alone.
+ *   Epochs: the first layer reads the claim plane at `sense_epoch` (the epoch before this step's), the claims are made at
+ * m->epoch, which must be sense_epoch + 1, or 1 after DIE_OWNER_EPOCH_MAX — then the claim planes of every replica are
+ * cleared between the sensing and the claims (what Env.step's next_epoch does).
+ *   Scratch: [set][replica][4][W][H] fp32 planes, set = layer % 2 (one set for a one-layer stack); the last layer's
+ * (dx, dy, deposit) planes of replica r stay in set (n_layers − 1) % 2 until the next call.  `act` may be NULL. */
+#define DIE_NCA_MAX_LAYERS 8
+typedef struct die_nca_layer {
+    int32_t k;                   /* odd, 1..7 */
+    int32_t cin, cout;           /* 1..4; layer 0 reads 2 + with_agent_channel planes, the last gives 3 */
+    int32_t reserved;
+    const float* weights;        /* device fp32: replica r's (cout, cin, k, k) block starts at weights + r * weight_stride */
+    int64_t weight_stride;       /* elements, >= cout * cin * k * k (e.g. the row length of an (R, P) parameter matrix) */
+} die_nca_layer;
+typedef struct die_nca_batch {
+    int32_t n_layers;            /* 1..DIE_NCA_MAX_LAYERS */
+    int32_t padding_mode;        /* die_pad_mode of every layer */
+    int32_t with_agent_channel;  /* 1: layer 0 reads (agents, food, chem); 0: (food, chem) */
+    int32_t sense_epoch;
+    const die_nca_layer* layers;
+    float coef[3];               /* action = plane * coef: scale, scale, deposit */
+    int32_t reserved;
+    float* scratch;
+    int64_t scratch_bytes;
+} die_nca_batch;
+int64_t die_nca_batch_scratch_bytes(int32_t W, int32_t H, int32_t replicas, int32_t n_layers);
+int die_nca_env_step_batch(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
+                           const die_dynamics* d, const die_batch* b, die_step_result* results, void* workspace,
+                           int64_t workspace_bytes, void* stream);
 
 /* ---- message packing for decomposed worlds (die_amd/dist.py; no reference counterpart) ----------
  * A block [r0, r1) x [c0, c1) of a row-major plane (pitch in elements, 2/4/8-byte elements) copied
