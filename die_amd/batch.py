@@ -9,8 +9,14 @@ arithmetic — bit for bit (tests/test_gpu_parity.py::test_batched_replicas_equa
 `BatchedNeuralAutomataAgent` is a population of NeuralAutomataAgent candidates, one per replica (the evaluation half of
 examples/learning_agents.py): replica r is `Env(field_size, dynamics, seed=seeds[r], max_agents='alive')` driven by a
 NeuralAutomataAgent holding row r of the (R, P) parameter matrix — L + 2 launches per step for the whole population
-(`die_nca_env_step_batch`), bit for bit the stand-alone runs (tests/test_gpu_nca_batch.py)."""
+(`die_nca_env_step_batch`), bit for bit the stand-alone runs (tests/test_gpu_nca_batch.py).
+
+A device food-flow operator (`WaveSequence` / `PerlinNoiseSequence.get_flow_operator`) runs on every replica: replica r is then
+the stand-alone run with a fresh operator over the same sequence whose counter starts where the batch's stood at the first
+batched step — every replica sees the same t, and the batch's operator advances once per batched step.  One more launch
+per step (`die_food_flow_batch`) in the small-world regime (tests/test_gpu_flow_batch.py)."""
 import ctypes as C
+import dataclasses
 import math
 from typing import List, Optional, Sequence, Tuple, Union
 
@@ -21,6 +27,7 @@ from torch.nn.utils import parameters_to_vector, vector_to_parameters
 from . import _lib
 from .agent.evo import NeuralAutomataAgent
 from .agent.gradient import join64, split64
+from .data_init import DeviceFoodFlow, device_flow_kind
 from .device_array import Q32, _ptr, stream_ptr
 from .env import BoundaryCondition, Dynamics, Env, _identity_food_flow, linear_action_cost
 
@@ -54,8 +61,9 @@ class BatchedEnv:
         self.dtype = field_dtype
         self.per_replica = (self.W * self.H >= Env.PIC_MIN_CELLS) if per_replica is None else bool(per_replica)
         if self.per_replica:
-            self.envs = [Env(field_size, d, seed=self.seeds[r], max_agents='alive', field_dtype=field_dtype, device=self.device,
-                             sync=False) for r in range(self.R)]
+            # every replica Env gets its own Dynamics: its flow operator is its own (step keeps the counters in line)
+            self.envs = [Env(field_size, dataclasses.replace(d), seed=self.seeds[r], max_agents='alive', field_dtype=field_dtype,
+                             device=self.device, sync=False) for r in range(self.R)]
             self.n = [e.agents.N for e in self.envs]
             self.Nmax = max(self.n)
             self.streams = [torch.cuda.Stream(device=self.device) for _ in range(self.R)]
@@ -117,20 +125,11 @@ class BatchedEnv:
         `read_results` decodes)."""
         if isinstance(agent, BatchedNeuralAutomataAgent):
             return self._step_nca(agent, results)
+        flow = self._flow_kind()                    # refused before anything is launched
         if results is None:
             results = torch.empty((self.R, 2), dtype=torch.float64, device=self.device)
         if self.per_replica:
-            cur = torch.cuda.current_stream(self.device)
-            start = cur.record_event()
-            for r, (e, st) in enumerate(zip(self.envs, self.streams)):
-                st.wait_event(start)
-                with torch.cuda.stream(st):
-                    self._obs[r], res, *_ = e.step(agent.agents[r].forward(self._obs[r]))
-                    results[r].copy_(res)
-                cur.wait_stream(st)
-            agent._calls += 1
-            self._steps += 1
-            return results
+            return self._step_per_replica(agent, lambda r: agent.agents[r], flow, results)
         self.epoch += 1
         if self.epoch > _lib.OWNER_EPOCH_MAX:
             self.owner.zero_()
@@ -142,25 +141,17 @@ class BatchedEnv:
                    'die_forward_env_step_batch')
         agent._calls += 1
         self.chem, self.chem_next = self.chem_next, self.chem
+        self._food_flow(flow, m, b)
         self._steps += 1
         return results
 
     def _step_nca(self, agent: 'BatchedNeuralAutomataAgent', results: Optional[torch.Tensor]) -> torch.Tensor:
         agent._check_step(self)                     # every refusal before anything is launched
+        flow = self._flow_kind()
         if results is None:
             results = torch.empty((self.R, 2), dtype=torch.float64, device=self.device)
         if self.per_replica:
-            cur = torch.cuda.current_stream(self.device)
-            start = cur.record_event()
-            for r, (e, st) in enumerate(zip(self.envs, self.streams)):
-                st.wait_event(start)
-                with torch.cuda.stream(st):
-                    self._obs[r], res, *_ = e.step(agent._replica_agent(r).forward(self._obs[r]))
-                    results[r].copy_(res)
-                cur.wait_stream(st)
-            agent._calls += 1
-            self._steps += 1
-            return results
+            return self._step_per_replica(agent, agent._replica_agent, flow, results)
         # the sensing reads the claim plane at the current epoch, the claims are made at the next one; at the wrap the
         # library clears the claim planes between the two (Env.step runs forward before its next_epoch the same way)
         sense_epoch = self.epoch
@@ -174,6 +165,51 @@ class BatchedEnv:
             _lib.check(rc, 'die_nca_env_step_batch')
         agent._calls += 1
         self.chem, self.chem_next = self.chem_next, self.chem
+        self._food_flow(flow, m, b)
+        self._steps += 1
+        return results
+
+    def _flow_kind(self) -> Optional[int]:
+        """The batched flow of `dynamics.op_food_flow` (DIE_FLOW_WAVE / DIE_FLOW_PERLIN; None for the identity).  Any other
+        operator is refused: a host operator would cost a round trip per replica and step."""
+        op = self.dynamics.op_food_flow
+        if op is _identity_food_flow:
+            return None
+        kind = device_flow_kind(op)
+        if kind is None:
+            raise NotImplementedError(f'batched replicas: food-flow operator {op!r} is not batched — only the device operators of '
+                                      'WaveSequence / PerlinNoiseSequence (get_flow_operator) are; step the replicas one at a time')
+        return kind
+
+    def _food_flow(self, flow: Optional[int], m: _lib.Medium, b: _lib.Batch):
+        """Env._food_flow of every replica: one launch, after the step (the next sensing reads the flowed food)."""
+        if flow is None:
+            return
+        op = self.dynamics.op_food_flow
+        seq = op.seq
+        octaves, seed = (seq._octaves, seq._seed & 0xFFFFFFFFFFFFFFFF) if flow == _lib.DIE_FLOW_PERLIN else (0, 0)
+        _lib.check(_lib.lib.die_food_flow_batch(C.byref(m), C.byref(b), flow, op.next_t(), op.scale, op.decay, octaves, seed,
+                                                stream_ptr(self.device)), 'die_food_flow_batch')
+
+    def _step_per_replica(self, agent, replica_agent, flow: Optional[int], results: torch.Tensor) -> torch.Tensor:
+        """Large worlds: replica r is its own Env stepped by `replica_agent(r)` on its own stream.  With a flow, each Env gets
+        an operator of its own over the batch's sequence, at the batch's counter: all apply the same t, each on its stream."""
+        op = self.dynamics.op_food_flow
+        for e in self.envs:
+            e.dynamics.op_food_flow = op if flow is None else DeviceFoodFlow(op.seq, op.scale, op.decay)
+            if flow is not None:
+                e.dynamics.op_food_flow._k = op._k
+        cur = torch.cuda.current_stream(self.device)
+        start = cur.record_event()
+        for r, (e, st) in enumerate(zip(self.envs, self.streams)):
+            st.wait_event(start)
+            with torch.cuda.stream(st):
+                self._obs[r], res, *_ = e.step(replica_agent(r).forward(self._obs[r]))
+                results[r].copy_(res)
+            cur.wait_stream(st)
+        if flow is not None:
+            op.next_t()
+        agent._calls += 1
         self._steps += 1
         return results
 
@@ -342,8 +378,6 @@ class BatchedNeuralAutomataAgent:
         if model.agent_dropout.p > 0 and model.training:
             raise NotImplementedError('p_agent_dropout > 0 in training mode: its mask is a host-RNG torch op, not batched '
                                       '(call model.eval(), or step the candidates one at a time)')
-        if env.dynamics.op_food_flow is not _identity_food_flow:
-            raise NotImplementedError('a food-flow operator is not batched: step the candidates one at a time')
 
     def _struct(self, sense_epoch: int) -> _lib.NcaBatch:
         base = self.parameters.data_ptr()

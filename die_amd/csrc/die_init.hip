@@ -309,6 +309,83 @@ extern "C" int die_food_flow_perlin(const die_medium* m, double t, int32_t octav
     return DIE_OK;
 }
 
+// ---- food flow on the replicas of a die_batch ----------------------------------------------------------------------
+// The field z(x, y, t) is the same for every replica (same world, same t, same seed); only the food planes differ.  One
+// thread per cell evaluates z once and updates that cell in every plane, issuing a chunk's loads before its first store.
+// (One cell per thread, not a 4-cell vector: at 96² that is 36 workgroups instead of 9 to share the float64 field; the
+// planes themselves are small.)
+// A replica's plane is a whole world: gW = W, gH = H, no offsets.  The expressions restate those of k_food_flow_wave /
+// k_food_flow_perlin token for token (the library contracts a·b + c only inside one expression, so equal expressions
+// round alike); they are not shared with those kernels because hoisting them into a helper changed the old kernels' code.
+// (gi, gj): the cell's index along the first (W) and the second (H) axis.
+__device__ __forceinline__ double flow_wave_z(int gi, int gj, int gW, int gH, double t) {
+    const double pi = 3.141592653589793;
+    const double x = ((double)gj * (1.0 / (double)(gH - 1)) - 0.5) * 2.0;      // x along H, y along W, as k_food_flow_wave
+    const double y = ((double)gi * (1.0 / (double)(gW - 1)) - 0.5) * 2.0;
+    const double r = sqrt(x * x + y * y);
+    const double rwave = r + cos(pi * x) + sin(0.4 * pi * y);
+    const double z_waves = cos(1.0 * pi * (rwave + t));
+    const double z_islands = sin(pi * x * 3.0 + t) + cos(pi * y * 3.0 + t);
+    return (1.0 - 0.25) * z_waves + 0.25 * z_islands;
+}
+
+// (flatten: die_perlin3 is inlined here; called, as the one-plane kernel calls it, it costs 32 B of scratch per lane)
+__device__ __forceinline__ __attribute__((flatten)) double flow_perlin_z(int gi, int gj, int gW, int gH, double t, double octaves, uint64_t seed) {
+    const double x = (double)gi / (double)(gW - 1), y = (double)gj / (double)(gH - 1);      // x along W, as k_food_flow_perlin
+    return rint(die_perlin3(seed, x * octaves, y * octaves, t * octaves) * 1000.0) / 1000.0;
+}
+
+// Loads in flight per thread.  Replicas past the last one of a chunk re-load the last plane (in bounds) and store nothing.
+#define FLOW_BATCH_CHUNK 16
+
+template <typename T, int KIND>
+__global__ __launch_bounds__(DIE_BLOCK) void k_food_flow_batch(T* food, int W, int H, int R, int64_t plane_stride, double t, double scale,
+                                                               double keep, double octaves, uint64_t seed) {
+    const int64_t total = (int64_t)W * H;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const int gi = (int)(i / H), gj = (int)(i - (int64_t)gi * H);
+        const double z = KIND == DIE_FLOW_WAVE ? flow_wave_z(gi, gj, W, H, t) : flow_perlin_z(gi, gj, W, H, t, octaves, seed);
+        for (int r0 = 0; r0 < R; r0 += FLOW_BATCH_CHUNK) {
+            float v[FLOW_BATCH_CHUNK];
+#pragma unroll
+            for (int q = 0; q < FLOW_BATCH_CHUNK; ++q) v[q] = die_ld(food + (int64_t)min(r0 + q, R - 1) * plane_stride, i);
+#pragma unroll
+            for (int q = 0; q < FLOW_BATCH_CHUNK; ++q)
+                if (r0 + q < R) die_st(food + (int64_t)(r0 + q) * plane_stride, i, (float)(scale * z + keep * (double)v[q]));
+        }
+    }
+}
+
+template <typename T>
+static void launch_food_flow_batch(int32_t kind, T* food, int W, int H, int R, int64_t plane_stride, double t, double scale, double keep,
+                                   double octaves, uint64_t seed, hipStream_t s) {
+    const int grid = init_grid((int64_t)W * H);
+    if (kind == DIE_FLOW_WAVE) k_food_flow_batch<T, DIE_FLOW_WAVE><<<grid, DIE_BLOCK, 0, s>>>(food, W, H, R, plane_stride, t, scale, keep, octaves, seed);
+    else k_food_flow_batch<T, DIE_FLOW_PERLIN><<<grid, DIE_BLOCK, 0, s>>>(food, W, H, R, plane_stride, t, scale, keep, octaves, seed);
+}
+
+extern "C" int die_food_flow_batch(const die_medium* m, const die_batch* b, int32_t kind, double t, double scale, double decay,
+                                   int32_t octaves, uint64_t seed, void* stream) {
+    const char* who = "die_food_flow_batch";
+    DIE_REQUIRE(m && b && m->food, "%s: null argument", who);
+    DIE_REQUIRE(b->replicas >= 1 && b->replicas <= DIE_MAX_REPLICAS, "%s: %d replicas, 1..%d expected", who, b->replicas, DIE_MAX_REPLICAS);
+    DIE_REQUIRE(kind == DIE_FLOW_WAVE || kind == DIE_FLOW_PERLIN, "%s: unknown flow kind %d", who, kind);
+    DIE_REQUIRE(kind != DIE_FLOW_PERLIN || octaves >= 1, "%s: octaves %d", who, octaves);
+    DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad field dtype %d", who, m->dtype);
+    DIE_REQUIRE(m->gW <= 0, "%s: a replica's plane is a whole world, not a tile", who);
+    DIE_REQUIRE(m->W >= 2 && m->H >= 2, "%s: the world must be at least 2x2, not %dx%d", who, m->W, m->H);
+    // (the kernel does not need it, but no batched step exists for such planes: the step entries refuse them too)
+    DIE_REQUIRE(m->H % 4 == 0, "%s: H %% 4 != 0 (H = %d): not a batched layout", who, m->H);
+    DIE_REQUIRE(b->plane_stride >= (int64_t)m->W * m->H, "%s: plane_stride %lld smaller than a replica's %dx%d plane", who,
+                (long long)b->plane_stride, m->W, m->H);
+    const hipStream_t s = (hipStream_t)stream;
+    if (m->dtype == DIE_F32) launch_food_flow_batch(kind, (float*)m->food, m->W, m->H, b->replicas, b->plane_stride, t, scale, 1.0 - decay, (double)octaves, seed, s);
+    else launch_food_flow_batch(kind, (__half*)m->food, m->W, m->H, b->replicas, b->plane_stride, t, scale, 1.0 - decay, (double)octaves, seed, s);
+    DIE_CHECK_LAUNCH(who);
+    return DIE_OK;
+}
+
 // ---- DataInitializer builder steps on plain fp32 arrays (core/data_init.py:171-253) --------------------------------
 // with_const (:214-216), with_noise / get_random (:168-169,218-220), with_agents (:222-226), with_food_perlin / with_chem
 // (:228-236) fill one channel; build / build_agents (:238-253) multiply by the static mask and hand the channels over.

@@ -150,6 +150,21 @@ class PerlinNoiseSequence(FieldSequence):
                                                  self._seed & 0xFFFFFFFFFFFFFFFF, stream_ptr(medium.device)), 'die_food_flow_perlin')
 
 
+def device_flow_kind(op) -> Optional[int]:
+    """`_lib.DIE_FLOW_WAVE` / `DIE_FLOW_PERLIN` when `op` is the DeviceFoodFlow of a WaveSequence / PerlinNoiseSequence whose
+    `_flow` is the library's own (the field the batched entry die_food_flow_batch evaluates); None for any other operator — a
+    Python callable, the host operator of a `__getitem__`-only FieldSequence, a subclass with a `_flow` of its own."""
+    if not isinstance(op, DeviceFoodFlow):
+        return None
+    f = getattr(op.seq, '_flow', None)
+    f = getattr(f, '__func__', f)
+    if f is WaveSequence._flow:
+        return _lib.DIE_FLOW_WAVE
+    if f is PerlinNoiseSequence._flow:
+        return _lib.DIE_FLOW_PERLIN
+    return None
+
+
 class DataInitializer:
     """core/data_init.py:92-253 with the arrays in HBM: the static allocators of the reference under their names, and its
     builder — `DataInitializer(field_size, channels).with_const(...).with_noise(...).with_agents(...)

@@ -1,13 +1,16 @@
 """The evaluation half of the reference's examples/learning_agents.py (`run_epoch`, lines 20-38) for a whole population at
 once: R NeuralAutomataAgent candidates, each scored by the sum of its rewards over `epoch_iters` steps of its own world,
-all R worlds stepped together by die_amd.batch (L + 2 launches per step for an L-layer model).
+all R worlds stepped together by die_amd.batch (L + 2 launches per step for an L-layer model, L + 3 with a food flow).
 
-    python examples/population_eval.py [--replicas 10] [--size 96] [--iters 50] [--generations 0] [--compare]
+    python examples/population_eval.py [--replicas 10] [--size 96] [--iters 50] [--dynamics st-perlin-wide] [--generations 0] [--compare]
+
+--dynamics picks one of the reference's three worlds (learning_agents.py `dynamics_choice`): 'st-perlin', 'st-perlin-wide' or
+'dyn-pred', where the food flows in running waves (WaveSequence.get_flow_operator, one more launch per batched step).
 
 --generations G runs a plain Gaussian evolution strategy (antithetic samples, normalised fitness) on the mean parameter
 vector — the training loop itself (evotorch's PGPE, MLflow) stays out of scope.  --compare times the same population one
-candidate at a time through `Env` + `NeuralAutomataAgent` (what a direct port of run_epoch does), checks that both give the
-same fitness, and prints candidate-steps/s for both.
+candidate at a time through `Env` + `NeuralAutomataAgent` (what a direct port of run_epoch does; every world with a flow
+operator of its own), checks that both give the same fitness, and prints candidate-steps/s for both.
 """
 import argparse
 import os
@@ -19,16 +22,25 @@ from torch.nn.utils import parameters_to_vector
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from die_amd import Dynamics, Env, NeuralAutomataAgent                  # noqa: E402
+from die_amd import Dynamics, Env, NeuralAutomataAgent, WaveSequence    # noqa: E402
 from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent        # noqa: E402
 
 AGENT_KW = dict(kernel_sizes=[3, 3], scale=0.01, deposit=2.0)           # learning_agents.py
-DYNAMICS_KW = dict(food_infinite=True, rate_decay_chem=0.025, diffuse_sigma=.8)
+DYNAMICS = ('st-perlin', 'st-perlin-wide', 'dyn-pred')
 
 
-def make_population(size, template, rows, seed):
+def make_dynamics(choice, size):
+    """learning_agents.py's `dynamics_choice[choice]`, with a fresh flow operator (its time counter at 0) for 'dyn-pred'."""
+    if choice == 'st-perlin':
+        return Dynamics(food_infinite=True)
+    if choice == 'st-perlin-wide':
+        return Dynamics(food_infinite=True, rate_decay_chem=0.025, diffuse_sigma=.8)
+    return Dynamics(food_infinite=False, op_food_flow=WaveSequence((size, size), dt=0.01).get_flow_operator(scale=0.5, decay=0.5))
+
+
+def make_population(size, template, rows, seed, choice):
     R = rows.shape[0]
-    benv = BatchedEnv((size, size), Dynamics(**DYNAMICS_KW), replicas=R, seeds=[seed] * R)   # every world starts alike
+    benv = BatchedEnv((size, size), make_dynamics(choice, size), replicas=R, seeds=[seed] * R)   # every world starts alike
     return benv, BatchedNeuralAutomataAgent(benv, template, rows)
 
 
@@ -47,8 +59,8 @@ def run_epoch(env, agent, iters):
     return epoch_reward
 
 
-def one_at_a_time_worlds(size, R, seed):
-    return [Env((size, size), Dynamics(**DYNAMICS_KW), seed=seed, max_agents='alive') for _ in range(R)]
+def one_at_a_time_worlds(size, R, seed, choice):
+    return [Env((size, size), make_dynamics(choice, size), seed=seed, max_agents='alive') for _ in range(R)]
 
 
 def main():
@@ -56,6 +68,7 @@ def main():
     p.add_argument('--replicas', type=int, default=10)
     p.add_argument('--size', type=int, default=96)
     p.add_argument('--iters', type=int, default=50, help='epoch_iters: steps per evaluation')
+    p.add_argument('--dynamics', choices=DYNAMICS, default='st-perlin-wide')
     p.add_argument('--generations', type=int, default=0)
     p.add_argument('--sigma', type=float, default=0.1)
     p.add_argument('--lr', type=float, default=0.05)
@@ -70,9 +83,9 @@ def main():
         template.model.init_weights()
         cands.append(parameters_to_vector(template.model.parameters()).detach().clone())
     rows = torch.stack(cands)
-    print(f'{R} candidates of {rows.shape[1]} parameters, {args.size}x{args.size}, {args.iters} steps each', flush=True)
+    print(f'{R} candidates of {rows.shape[1]} parameters, {args.size}x{args.size}, {args.iters} steps each, {args.dynamics}', flush=True)
 
-    benv, pop = make_population(args.size, template, rows, args.seed)
+    benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics)
     fitness = evaluate_population(benv, pop, args.iters)
     for r, f in enumerate(fitness):
         print(f'candidate {r:2d}: fitness {f:.6f}')
@@ -83,14 +96,14 @@ def main():
         # only the stepping is timed (the worlds are built before); warm-up of both paths first
         dev = torch.device('cuda')
         agents = [pop.candidate(r).to(dev) for r in range(R)]
-        evaluate_population(*make_population(args.size, template, rows, args.seed), 2)
-        run_epoch(one_at_a_time_worlds(args.size, 1, args.seed)[0], agents[0], 2)
-        benv, pop = make_population(args.size, template, rows, args.seed)
+        evaluate_population(*make_population(args.size, template, rows, args.seed, args.dynamics), 2)
+        run_epoch(one_at_a_time_worlds(args.size, 1, args.seed, args.dynamics)[0], agents[0], 2)
+        benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         batched = evaluate_population(benv, pop, args.iters)
         t_batch = time.perf_counter() - t0
-        worlds = one_at_a_time_worlds(args.size, R, args.seed)
+        worlds = one_at_a_time_worlds(args.size, R, args.seed, args.dynamics)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         alone = [run_epoch(env, ag, args.iters) for env, ag in zip(worlds, agents)]
@@ -110,7 +123,7 @@ def main():
         half = torch.randn((R // 2, mean.numel()))
         noise = torch.cat([half, -half])                                    # antithetic pairs
         samples = mean + args.sigma * noise
-        fit = evaluate_population(*make_population(args.size, template, samples, args.seed + 1 + g), args.iters)
+        fit = evaluate_population(*make_population(args.size, template, samples, args.seed + 1 + g, args.dynamics), args.iters)
         f = torch.tensor(fit, dtype=torch.float32)
         f = (f - f.mean()) / (f.std() + 1e-8)
         mean = mean + args.lr / (noise.shape[0] * args.sigma) * (noise.T @ f)

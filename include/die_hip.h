@@ -343,6 +343,14 @@ int die_food_flow_wave(const die_medium* medium, double t, double scale, double 
 /* The same with PerlinNoiseSequence.__getitem__(t) (core/data_init.py:55-69) as the field: round(noise((x, y, t)), 3), `noise` =
  * 3-D gradient noise at (x, y, t) * octaves on the linspace(0, 1, n) labels, lattice gradients from Philox(seed, point). */
 int die_food_flow_perlin(const die_medium* medium, double t, int32_t octaves, double scale, double decay, uint64_t seed, void* stream);
+/* One of the two flows above on every replica of a die_batch, in one launch: `m` describes replica 0 (a whole world: gW <= 0,
+ * at least 2x2, H % 4 == 0), replica r's food plane starts r * b->plane_stride elements further.  Every replica sees the
+ * same field (same t; for Perlin the same octaves and seed), evaluated once per cell, so replica r ends exactly as
+ * die_food_flow_wave / die_food_flow_perlin on its plane alone would leave it.  `octaves` is read for DIE_FLOW_PERLIN only. */
+#define DIE_FLOW_WAVE   1
+#define DIE_FLOW_PERLIN 2
+int die_food_flow_batch(const die_medium* m, const die_batch* b, int32_t kind, double t, double scale, double decay,
+                        int32_t octaves, uint64_t seed, void* stream);
 
 /* Env._get_sense_mask (core/env.py:276-290): mask = ceil(round(gaussian(agents channel, sigma, mode 'nearest',
  * truncate 4), decimals)) as W*H bytes (the reference uses sigma 2.0, 3 decimals); float64 accumulation, axis 0
