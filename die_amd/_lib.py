@@ -110,6 +110,24 @@ class NcaBatch(C.Structure):         # die_nca_batch
                 ('scratch_bytes', C.c_int64)]
 
 
+DIE_PGPE_CLIPUP, DIE_PGPE_ADAM = 0, 1
+PGPE_MAX_BLOCKS = 256
+
+
+def pgpe_work_doubles(P: int) -> int:     # DIE_PGPE_WORK_DOUBLES
+    return 4 * PGPE_MAX_BLOCKS + int(P)
+
+
+class Pgpe(C.Structure):             # die_pgpe
+    _fields_ = [('replicas', C.c_int32), ('optimizer', C.c_int32), ('num_params', C.c_int64), ('seed', C.c_uint64),
+                ('center_lr', C.c_double), ('stdev_lr', C.c_double), ('max_speed', C.c_double), ('momentum', C.c_double),
+                ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double), ('stdev_max_change', C.c_double),
+                ('stdev_min', C.c_double), ('stdev_max', C.c_double),
+                ('center', C.c_void_p), ('stdev', C.c_void_p), ('opt_a', C.c_void_p), ('opt_b', C.c_void_p),
+                ('pop_best', C.c_void_p), ('best', C.c_void_p), ('fitness', C.c_void_p), ('evals', C.c_void_p),
+                ('history', C.c_void_p), ('history_rows', C.c_int64), ('work', C.c_void_p)]
+
+
 class Rect(C.Structure):
     _fields_ = [('plane', C.c_void_p), ('pitch', C.c_int32), ('r0', C.c_int32), ('r1', C.c_int32), ('c0', C.c_int32),
                 ('c1', C.c_int32), ('elem_bytes', C.c_int32), ('buf_offset', C.c_int64)]
@@ -184,6 +202,8 @@ _SIGNATURES = {
     'die_sense_mask': (C.c_int, [_P(Medium), C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'die_render_frames': (C.c_int, [_P(Medium), C.c_void_p, C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
+    'die_pgpe_sample': (C.c_int, [_P(Pgpe), C.c_void_p, C.c_int64, C.c_void_p]),
+    'die_pgpe_update': (C.c_int, [_P(Pgpe), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
     'die_rects_pack': (C.c_int, [_P(Rect), C.c_int32, C.c_void_p, C.c_void_p]),
     'die_pic_two_launch': (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32]),
     'die_pic_step_bound': (C.c_float, [C.c_float, C.c_float]),

@@ -69,6 +69,8 @@ class BatchedEnv:
             self.streams = [torch.cuda.Stream(device=self.device) for _ in range(self.R)]
             self._obs = [e._get_current_obs for e in self.envs]
             self._steps = 0
+            self._initial = [_env_snapshot(e) for e in self.envs]
+            self._flow_k0 = getattr(self.dynamics.op_food_flow, '_k', None)
             return
         # every replica starts as the stand-alone Env with seeds[r] would; its state is copied into slice r
         envs = [Env(field_size, d, seed=self.seeds[r], max_agents='alive', field_dtype=field_dtype, device=self.device, sort_every=0,
@@ -80,14 +82,17 @@ class BatchedEnv:
                                           'not modelled by the batched step')
         self.Nmax = max(self.n)
         R, W, H, Nm, dev = self.R, self.W, self.H, self.Nmax, self.device
-        self.owner = torch.zeros((R, W, H), dtype=torch.int64, device=dev)
-        self.food = torch.zeros((R, W, H), dtype=field_dtype, device=dev)
-        self.chem = torch.zeros((R, W, H), dtype=field_dtype, device=dev)
-        self.chem_next = torch.empty((R, W, H), dtype=field_dtype, device=dev)
-        self.x = torch.zeros((R, Nm), dtype=torch.int32, device=dev)
-        self.y = torch.zeros((R, Nm), dtype=torch.int32, device=dev)
-        self.alive = torch.zeros((R, Nm), dtype=torch.uint8, device=dev)
-        self.agent_food = torch.zeros((R, Nm), dtype=torch.float32, device=dev)
+        # the whole state of the batch is views into ONE allocation: reset() restores it with a single copy
+        views, total = [], 0
+        for name, shape, dt in (('owner', (R, W, H), torch.int64), ('food', (R, W, H), field_dtype), ('chem', (R, W, H), field_dtype),
+                                ('chem_next', (R, W, H), field_dtype), ('x', (R, Nm), torch.int32), ('y', (R, Nm), torch.int32),
+                                ('alive', (R, Nm), torch.uint8), ('agent_food', (R, Nm), torch.float32)):
+            nbytes = math.prod(shape) * torch.empty((), dtype=dt).element_size()
+            views.append((name, shape, dt, total, nbytes))
+            total += -(-nbytes // 256) * 256
+        self._state = torch.zeros(total, dtype=torch.uint8, device=dev)
+        for name, shape, dt, off, nbytes in views:
+            setattr(self, name, self._state[off:off + nbytes].view(dt).view(shape))
         for r, e in enumerate(envs):
             self.owner[r].copy_(e.medium.owner); self.food[r].copy_(e.medium.food); self.chem[r].copy_(e.medium.chem)
             k = self.n[r]
@@ -96,6 +101,25 @@ class BatchedEnv:
         self.epoch = 1
         self._ws = torch.zeros(int(_lib.lib.die_batch_workspace_bytes(R)), dtype=torch.uint8, device=dev)
         self._steps = 0
+        self._initial = (self._state.clone(), self.chem, self.chem_next)
+        self._flow_k0 = getattr(self.dynamics.op_food_flow, '_k', None)
+
+    def reset(self) -> None:
+        """Every replica back to the state it was constructed in: bit for bit a fresh BatchedEnv of the same arguments (and a
+        flow operator whose counter stands where this one's stood then).  Device copies from a snapshot taken at construction,
+        on the current stream (one copy in the small-world regime); nothing is rebuilt and nothing is read back (the device loop
+        of die_amd.search.PGPE)."""
+        if self._flow_k0 is not None:
+            self.dynamics.op_food_flow._k = self._flow_k0
+        self._steps = 0
+        if self.per_replica:
+            for e, snap in zip(self.envs, self._initial):
+                _env_restore(e, snap)
+            self._obs = [e._get_current_obs for e in self.envs]
+            return
+        self._state.copy_(self._initial[0])
+        self.chem, self.chem_next = self._initial[1:]
+        self.epoch = 1
 
     # ------------------------------------------------------------------
     def _structs(self):
@@ -236,6 +260,38 @@ class BatchedEnv:
         agents = np.stack([q(self.x), q(self.y), self.alive[r, :k].to(torch.float64).cpu().numpy(),
                            self.agent_food[r, :k].to(torch.float64).cpu().numpy()])
         return medium, agents
+
+
+def _env_snapshot(e: Env) -> dict:
+    """Device copies of what a step of a stand-alone Env changes (its medium planes and agent arrays), and the host words
+    that describe them."""
+    M, A = e.medium, e.agents
+    return dict(planes=(M.owner.clone(), M.food.clone(), M.chem.clone()), epoch=M.epoch, N=A.N,
+                agents=(A.x.clone(), A.y.clone(), A.alive.clone(), A.agent_food.clone()),
+                slot=None if A.slot is None else A.slot.clone(), all_alive=e._all_alive)
+
+
+def _env_restore(e: Env, snap: dict) -> None:
+    """The Env of `snap` again, as its constructor left it: planes copied back, agent arrays fresh copies (a re-sort or the
+    tile-binned step may have swapped the arrays themselves), the tile-binned state dropped (a fresh Env builds it at its first
+    step too), the step counter at 0.  No host read."""
+    M, A = e.medium, e.agents
+    e._agents_changed()
+    for dst, src in zip((M.owner, M.food, M.chem), snap['planes']):
+        dst.copy_(src)
+    M.epoch, M.owner_stale = snap['epoch'], None
+    A.x, A.y, A.alive, A.agent_food = (t.clone() for t in snap['agents'])
+    A.slot = None if snap['slot'] is None else snap['slot'].clone()
+    A.N = snap['N']
+    e._all_alive = snap['all_alive']
+    e._steps = 0
+    e._pic = None
+    e._frozen = None
+    e._fuse_forward = True
+    e._host_read_pending = False
+    e._pic_status_written = False
+    e._status_word = None
+    e.last_result = None
 
 
 class BatchedPhysarumAgent:

@@ -12,6 +12,7 @@
 #define DIE_STREAM_INIT_HEADING 5u
 #define DIE_STREAM_INIT_AGENT_FOOD 6u
 #define DIE_STREAM_BUILDER 7u
+#define DIE_STREAM_SEARCH 8u        // PGPE sampling (die_search.hip): oracle/rng.py normals2(seed, generation, n, stream=8, scale=1)[0]
 
 struct die_u32x4 { uint32_t v[4]; };
 

@@ -1,0 +1,201 @@
+"""PGPE on the device: the search half of the reference's examples/learning_agents.py (evotorch's `PGPE`, as `run_agent`
+configures it), with the whole searcher state in HBM (die_pgpe_sample / die_pgpe_update, die_amd/csrc/die_search.hip).
+
+    searcher = PGPE(10, center_init=rows0, radius_init=1.5, center_learning_rate=0.05, stdev_learning_rate=0.1,
+                    optimizer='clipup', optimizer_config=dict(max_speed=0.1, momentum=0.9))
+    searcher.for_population(pop, epoch_iters=30).run(100)        # pop: a BatchedNeuralAutomataAgent of 10 candidates
+    searcher.best_agent().save(...)
+
+A generation is ask (one launch: symmetric samples into the (R, P) parameter matrix), the batched worlds' reset (device copies),
+`epoch_iters` batched steps and tell (three or four launches: fitness, centred ranks, gradients, the optimiser's step, pop_best /
+best, one row of statistics) — a fixed chain of launches with no host read.  The generic interface, `ask(params)` /
+`tell(terms)`, works on any (R, P) float32 device matrix and any (T, R) float64 terms.
+
+Differences from evotorch: the noise comes from Philox (counter-based, seeded), so a run is reproducible here but
+not bit-equal to evotorch's; the fitness is the plain sum of a candidate's T terms."""
+import ctypes as C
+import math
+from typing import Optional, Tuple
+
+import torch
+
+from . import _lib
+from .device_array import _ptr, stream_ptr
+
+OPTIMIZERS = {'clipup': _lib.DIE_PGPE_CLIPUP, 'adam': _lib.DIE_PGPE_ADAM}
+HISTORY_COLUMNS = ('mean_eval', 'max_eval', 'min_eval', 'median_eval', 'grad_norm', 'mean_stdev')
+
+
+class PGPE:
+    """Policy-gradients with parameter-based exploration (Sehnke et al. 2010) with symmetric sampling and centred ranks, the
+    arguments of evotorch's PGPE.  `popsize` is R (even, 2..64); the searcher maximises."""
+
+    def __init__(self, popsize: int, num_params: Optional[int] = None, *, center_init=None,
+                 initial_bounds: Tuple[float, float] = (-0.5, 0.5), radius_init: Optional[float] = None,
+                 stdev_init=None, center_learning_rate: float, stdev_learning_rate: float, optimizer: str = 'clipup',
+                 optimizer_config: Optional[dict] = None, stdev_max_change: Optional[float] = 0.2,
+                 stdev_min: Optional[float] = None, stdev_max: Optional[float] = None, seed: int = 0, device=None):
+        R = int(popsize)
+        if R % 2 or not 2 <= R <= 64:
+            raise ValueError(f'popsize {R}: an even number in 2..64 (symmetric pairs of samples, one replica each)')
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f'optimizer {optimizer!r}: one of {sorted(OPTIMIZERS)}')
+        dev = torch.device(device if device is not None else 'cuda')
+        if dev.type == 'cuda' and dev.index is None:                 # ('cuda' is the current device: tensors say cuda:N)
+            dev = torch.device('cuda', torch.cuda.current_device())
+        self.device = dev
+        if center_init is not None:
+            center = torch.as_tensor(center_init, dtype=torch.float32).detach().reshape(-1).cpu()
+            if num_params is not None and center.numel() != int(num_params):
+                raise ValueError(f'center_init of {center.numel()} values for num_params={num_params}')
+        else:
+            if num_params is None:
+                raise ValueError('num_params, or a center_init to take it from')
+            lo, hi = (float(v) for v in initial_bounds)
+            g = torch.Generator().manual_seed(int(seed))          # NEProblem(initial_bounds=...): drawn once, on the host
+            center = lo + (hi - lo) * torch.rand(int(num_params), generator=g, dtype=torch.float32)
+        self.R, self.P, self.seed = R, int(center.numel()), int(seed)
+        if self.P < 1:
+            raise ValueError('at least one parameter')
+        if (radius_init is None) == (stdev_init is None):
+            raise ValueError('exactly one of radius_init and stdev_init')
+        if radius_init is not None:
+            if not radius_init > 0:
+                raise ValueError(f'radius_init {radius_init}: must be positive')
+            stdev = torch.full((self.P,), math.sqrt(float(radius_init) ** 2 / self.P), dtype=torch.float32)
+        else:
+            stdev = torch.as_tensor(stdev_init, dtype=torch.float32).detach().cpu().expand(self.P).clone()
+            if not bool((stdev > 0).all()):
+                raise ValueError('stdev_init: must be positive')
+        cfg = dict(optimizer_config or {})
+        opt = OPTIMIZERS[optimizer]
+        if opt == _lib.DIE_PGPE_CLIPUP:
+            max_speed = float(cfg.pop('max_speed', 2.0 * center_learning_rate))     # evotorch's ClipUp default
+            momentum = float(cfg.pop('momentum', 0.9))
+            beta1, beta2, eps = 0.9, 0.999, 1e-8
+        else:
+            beta1, beta2 = (float(b) for b in cfg.pop('betas', (0.9, 0.999)))
+            eps = float(cfg.pop('eps', 1e-8))
+            max_speed, momentum = 0.0, 0.0
+        if cfg:
+            raise ValueError(f'optimizer_config: unknown keys {sorted(cfg)} for {optimizer!r}')
+        dev, P = self.device, self.P
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.center = center.to(dev)
+        self.stdev = stdev.to(dev)
+        self._opt_a = torch.zeros(P, **f32)
+        self._opt_b = torch.zeros(P, **f32) if opt == _lib.DIE_PGPE_ADAM else None
+        self._pop_best = torch.zeros(P, **f32)
+        self._best = torch.zeros(P, **f32)
+        self.fitness = torch.zeros(R, dtype=torch.float64, device=dev)
+        self._evals = torch.tensor([-math.inf, -math.inf], dtype=torch.float64, device=dev)
+        self._history = torch.zeros((64, 6), dtype=torch.float64, device=dev)
+        self._work = torch.zeros(_lib.pgpe_work_doubles(P), dtype=torch.float64, device=dev)
+        self._s = _lib.Pgpe(R, opt, P, self.seed & 0xFFFFFFFFFFFFFFFF, float(center_learning_rate), float(stdev_learning_rate),
+                            max_speed, momentum, beta1, beta2, eps, -1.0 if stdev_max_change is None else float(stdev_max_change),
+                            -math.inf if stdev_min is None else float(stdev_min), math.inf if stdev_max is None else float(stdev_max),
+                            _ptr(self.center), _ptr(self.stdev), _ptr(self._opt_a), None if self._opt_b is None else _ptr(self._opt_b),
+                            _ptr(self._pop_best), _ptr(self._best), _ptr(self.fitness), _ptr(self._evals), _ptr(self._history),
+                            self._history.shape[0], _ptr(self._work))
+        self.iter = 0                                   # generations told so far
+        self._asked = None
+        self._pop = None
+
+    # ------------------------------------------------------------------ generic interface
+    def _check_params(self, params: torch.Tensor):
+        if tuple(params.shape) != (self.R, self.P) or params.dtype != torch.float32 or params.device != self.device \
+                or not params.is_contiguous():
+            raise ValueError(f'params: a contiguous ({self.R}, {self.P}) float32 tensor on {self.device}')
+
+    def ask(self, params: torch.Tensor) -> torch.Tensor:
+        """Fill `params` (R, P) with this generation's symmetric samples: rows 2i, 2i + 1 = center ± stdev·z_i.  One launch."""
+        self._check_params(params)
+        _lib.check(_lib.lib.die_pgpe_sample(C.byref(self._s), _ptr(params), self.iter, stream_ptr(self.device)), 'die_pgpe_sample')
+        self._asked = params
+        return params
+
+    def tell(self, terms: torch.Tensor, params: Optional[torch.Tensor] = None) -> None:
+        """Update from the evaluated rows (those of the last `ask` unless `params` is given): candidate r's fitness is the sum
+        over t of terms[t, r] — a (T, R) float64 tensor, or the (T, R, 2) die_step_result tensor of `BatchedEnv.run` (word 0:
+        the reward).  Three or four launches, no host read."""
+        params = self._asked if params is None else params
+        if params is None:
+            raise RuntimeError('tell() before ask()')
+        self._check_params(params)
+        if terms.dtype != torch.float64 or terms.device != self.device or terms.dim() not in (2, 3) \
+                or tuple(terms.shape[1:2]) != (self.R,) or (terms.dim() == 3 and terms.shape[2] < 1) or terms.shape[0] < 1:
+            raise ValueError(f'terms: a (T, {self.R}) or (T, {self.R}, 2) float64 tensor on {self.device}')
+        if self.iter >= self._history.shape[0]:         # grow the history on the device (no host read)
+            h = torch.zeros((2 * self._history.shape[0], 6), dtype=torch.float64, device=self.device)
+            h[:self._history.shape[0]].copy_(self._history)
+            self._history = h
+            self._s.history, self._s.history_rows = _ptr(h), h.shape[0]
+        _lib.check(_lib.lib.die_pgpe_update(C.byref(self._s), _ptr(params), _ptr(terms), terms.shape[0], terms.stride(0),
+                                            terms.stride(1), self.iter, stream_ptr(self.device)), 'die_pgpe_update')
+        self.iter += 1
+
+    # ------------------------------------------------------------------ a population of NeuralAutomataAgents
+    def for_population(self, pop, epoch_iters: int, env=None) -> 'PGPE':
+        """Bind to a BatchedNeuralAutomataAgent: `step()` is then ask into `pop.parameters`, `pop.env.reset()`, `epoch_iters`
+        batched steps, tell.  `env`, when given, must be the population's own BatchedEnv."""
+        from .batch import BatchedNeuralAutomataAgent
+        if not isinstance(pop, BatchedNeuralAutomataAgent):
+            raise TypeError('pop: a BatchedNeuralAutomataAgent')
+        if env is not None and env is not pop.env:
+            raise ValueError('this population was built for another BatchedEnv')
+        if pop.R != self.R:
+            raise ValueError(f'popsize {self.R} != the population\'s {pop.R} replicas')
+        if pop.P != self.P:
+            raise ValueError(f'{self.P} search parameters for a population of {pop.P}')
+        if pop.parameters.device != self.device:
+            raise ValueError(f'population on {pop.parameters.device}, searcher on {self.device}')
+        if int(epoch_iters) < 1:
+            raise ValueError('epoch_iters: at least 1')
+        self._pop, self._epoch_iters = pop, int(epoch_iters)
+        self._results = torch.empty((self._epoch_iters, self.R, 2), dtype=torch.float64, device=self.device)
+        return self
+
+    def step(self) -> None:
+        """One generation on the bound population (no host read)."""
+        if self._pop is None:
+            raise RuntimeError('step(): bind a population first (for_population)')
+        pop, env = self._pop, self._pop.env
+        self.ask(pop.parameters)
+        env.reset()
+        for t in range(self._epoch_iters):
+            env.step(pop, self._results[t])
+        self.tell(self._results)
+
+    def run(self, generations: int) -> None:
+        for _ in range(int(generations)):
+            self.step()
+
+    # ------------------------------------------------------------------ results (read on demand)
+    @property
+    def status(self) -> dict:
+        h = self.history()
+        ev = self._evals.cpu().tolist()
+        return dict(center=self.center.cpu(), stdev=self.stdev.cpu(), pop_best=self._pop_best.cpu(), pop_best_eval=ev[0],
+                    best=self._best.cpu(), best_eval=ev[1], mean_eval=float(h[-1, 0]) if len(h) else math.nan,
+                    median_eval=float(h[-1, 3]) if len(h) else math.nan, iter=self.iter)
+
+    def history(self) -> torch.Tensor:
+        """(G, 6) float64 on the host, one row per generation: HISTORY_COLUMNS."""
+        return self._history[:self.iter].cpu()
+
+    def _agent(self, row: torch.Tensor, template=None):
+        from .batch import BatchedNeuralAutomataAgent
+        template = template if template is not None else (self._pop.template if self._pop is not None else None)
+        if template is None:
+            raise RuntimeError('no NeuralAutomataAgent template: bind a population (for_population) or pass one')
+        return BatchedNeuralAutomataAgent.unpack(template, row.cpu())
+
+    def best_agent(self, template=None):
+        """The best candidate evaluated so far, as a stand-alone NeuralAutomataAgent (ready for save())."""
+        return self._agent(self._best, template)
+
+    def pop_best_agent(self, template=None):
+        return self._agent(self._pop_best, template)
+
+    def center_agent(self, template=None):
+        return self._agent(self.center, template)

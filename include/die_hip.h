@@ -630,6 +630,53 @@ int die_nca_env_step_batch(const die_medium* m, const die_agents* a, const die_n
                            const die_dynamics* d, const die_batch* b, die_step_result* results, void* workspace,
                            int64_t workspace_bytes, void* stream);
 
+/* ---- PGPE search over an (R, P) parameter matrix (die_search.hip; die_amd/search.py PGPE) ------------------------------
+ * The training half of the reference's examples/learning_agents.py (evotorch's PGPE with symmetric sampling and centred
+ * ranks).  R = replicas (even, 2..DIE_MAX_REPLICAS), n = R / 2 directions, P = parameters; the matrix is row-major fp32
+ * (the `parameters` of a BatchedNeuralAutomataAgent).  All arithmetic is float64; the state lives in the caller's device
+ * buffers below.  Neither call reads anything back to the host.
+ *   sample: z(i, p) = sqrt(-2 ln u1) cos(2 pi u2), u1 = (w0 + 1) / 2^32, u2 = w1 / 2^32 from the first two words of
+ *     Philox(counter = (i P + p, generation, DIE_STREAM_SEARCH), key = seed); eps = stdev[p] z; row 2i = fl32(center + eps),
+ *     row 2i + 1 = fl32(center - eps).  One launch.
+ *   update: f_r = sum over t ascending of terms[t stride_t + r stride_r] (the (T, R, 2) die_step_result words of T batched
+ *     steps: stride_t = 2R, stride_r = 2); centred ranks u_r = k / (R - 1) - 0.5 (ascending, ties by replica index); the
+ *     evaluated noise e(i, p) = row_2i[p] - center[p]; g_mu = (1/n) sum_i e (u_2i - u_2i+1) / 2,
+ *     g_sigma = (1/n) sum_i ((u_2i + u_2i+1) / 2) (e^2 - sigma^2) / sigma; the centre takes a ClipUp or Adam ascent step on
+ *     g_mu, sigma + stdev_lr g_sigma is clamped to [sigma (1 - d), sigma (1 + d)] and then to [stdev_min, stdev_max];
+ *     pop_best = the row of the highest f (lowest index on ties), best = the best row ever (replaced on a strictly greater f);
+ *     history row `generation` = (mean, max, min, median of f, |g_mu|, mean of the new sigma).  Three launches (Adam) or four
+ *     (ClipUp); the two norms are fixed-tree reductions (no float atomics): the same bits on every run. */
+#define DIE_PGPE_CLIPUP 0
+#define DIE_PGPE_ADAM 1
+#define DIE_PGPE_MAX_BLOCKS 256
+#define DIE_PGPE_WORK_DOUBLES(P) (4 * DIE_PGPE_MAX_BLOCKS + (int64_t)(P))
+typedef struct die_pgpe {
+    int32_t replicas;            /* R: even, 2..DIE_MAX_REPLICAS */
+    int32_t optimizer;           /* DIE_PGPE_CLIPUP / DIE_PGPE_ADAM */
+    int64_t num_params;          /* P >= 1 */
+    uint64_t seed;               /* Philox key of the sampling */
+    double center_lr;            /* ClipUp step size alpha / Adam lr, > 0 */
+    double stdev_lr;             /* > 0 */
+    double max_speed, momentum;  /* ClipUp: > 0, [0, 1) */
+    double beta1, beta2, eps;    /* Adam: [0, 1), [0, 1), > 0 */
+    double stdev_max_change;     /* d; negative: no relative clamp */
+    double stdev_min, stdev_max; /* absolute clamp (-inf / +inf: none) */
+    float* center;               /* [P] */
+    float* stdev;                /* [P] */
+    float* opt_a;                /* [P] ClipUp velocity / Adam first moment */
+    float* opt_b;                /* [P] Adam second moment (ClipUp: unused, may be NULL) */
+    float* pop_best;             /* [P] */
+    float* best;                 /* [P] */
+    double* fitness;             /* [R] f of the last update */
+    double* evals;               /* [2]: pop_best's f, best's f (set best's to -inf before the first update) */
+    double* history;             /* [history_rows][6] */
+    int64_t history_rows;        /* update needs generation < history_rows */
+    double* work;                /* DIE_PGPE_WORK_DOUBLES(P) float64 scratch */
+} die_pgpe;
+int die_pgpe_sample(const die_pgpe* s, float* params, int64_t generation, void* stream);
+int die_pgpe_update(const die_pgpe* s, const float* params, const double* terms, int64_t T, int64_t stride_t, int64_t stride_r,
+                    int64_t generation, void* stream);
+
 /* ---- message packing for decomposed worlds (die_amd/dist.py; no reference counterpart) ----------
  * A block [r0, r1) x [c0, c1) of a row-major plane (pitch in elements, 2/4/8-byte elements) copied
  * to / from byte offset buf_offset of one contiguous message buffer; up to 16 blocks per launch. */
