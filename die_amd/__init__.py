@@ -11,8 +11,8 @@ from .base_types import DataChannels
 from .data_init import DataInitializer, FieldSequence, PerlinNoiseSequence, WaveSequence
 from .device_array import DeviceAction, DeviceAgents, DeviceMedium
 from .env import BoundaryCondition, Dynamics, Env, linear_action_cost, zero_cost
-from .search import PGPE
+from .search import CMAES, PGPE
 
 __all__ = ['WaveSequence', 'PerlinNoiseSequence', 'FieldSequence', 'Env', 'Dynamics', 'BoundaryCondition', 'linear_action_cost', 'zero_cost', 'Agent', 'PhysarumAgent',
            'GradientAgent', 'BrownianAgent', 'ConstAgent', 'NeuralAutomataAgent', 'ConvolutionModel', 'DataInitializer', 'DataChannels', 'DeviceMedium',
-           'DeviceAgents', 'DeviceAction', 'PGPE']
+           'DeviceAgents', 'DeviceAction', 'PGPE', 'CMAES']

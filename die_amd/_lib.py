@@ -128,6 +128,23 @@ class Pgpe(C.Structure):             # die_pgpe
                 ('history', C.c_void_p), ('history_rows', C.c_int64), ('work', C.c_void_p)]
 
 
+CMAES_MAX_BLOCKS = 256
+MAX_REPLICAS = 64
+
+
+def cmaes_work_doubles(R: int, P: int) -> int:     # DIE_CMAES_WORK_DOUBLES
+    return (4 + int(R)) * CMAES_MAX_BLOCKS + int(P)
+
+
+class Cmaes(C.Structure):            # die_cmaes
+    _fields_ = [('replicas', C.c_int32), ('csa_squared', C.c_int32), ('num_params', C.c_int64), ('seed', C.c_uint64),
+                ('c_m', C.c_double), ('c_sigma', C.c_double), ('d_sigma', C.c_double), ('c_c', C.c_double), ('c_1', C.c_double),
+                ('c_mu', C.c_double), ('mu_eff', C.c_double), ('chi_d', C.c_double), ('weights', C.c_double * MAX_REPLICAS),
+                ('center', C.c_void_p), ('C', C.c_void_p), ('p_sigma', C.c_void_p), ('p_c', C.c_void_p), ('sigma', C.c_void_p),
+                ('pop_best', C.c_void_p), ('best', C.c_void_p), ('fitness', C.c_void_p), ('evals', C.c_void_p),
+                ('history', C.c_void_p), ('history_rows', C.c_int64), ('work', C.c_void_p)]
+
+
 class Rect(C.Structure):
     _fields_ = [('plane', C.c_void_p), ('pitch', C.c_int32), ('r0', C.c_int32), ('r1', C.c_int32), ('c0', C.c_int32),
                 ('c1', C.c_int32), ('elem_bytes', C.c_int32), ('buf_offset', C.c_int64)]
@@ -204,6 +221,8 @@ _SIGNATURES = {
                                     C.c_void_p]),
     'die_pgpe_sample': (C.c_int, [_P(Pgpe), C.c_void_p, C.c_int64, C.c_void_p]),
     'die_pgpe_update': (C.c_int, [_P(Pgpe), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    'die_cmaes_sample': (C.c_int, [_P(Cmaes), C.c_void_p, C.c_int64, C.c_void_p]),
+    'die_cmaes_update': (C.c_int, [_P(Cmaes), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
     'die_rects_pack': (C.c_int, [_P(Rect), C.c_int32, C.c_void_p, C.c_void_p]),
     'die_pic_two_launch': (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32]),
     'die_pic_step_bound': (C.c_float, [C.c_float, C.c_float]),

@@ -13,6 +13,7 @@
 #define DIE_STREAM_INIT_AGENT_FOOD 6u
 #define DIE_STREAM_BUILDER 7u
 #define DIE_STREAM_SEARCH 8u        // PGPE sampling (die_search.hip): oracle/rng.py normals2(seed, generation, n, stream=8, scale=1)[0]
+#define DIE_STREAM_CMAES 9u         // CMA-ES sampling (die_cmaes.hip): oracle/rng.py normals2(seed, generation, n, stream=9, scale=1)[0]
 
 struct die_u32x4 { uint32_t v[4]; };
 

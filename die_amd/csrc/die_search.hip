@@ -15,8 +15,7 @@
 //
 // Roofline: the update reads the R x P matrix once (R = 10, P = 162 for the reference's agent: a few KB) — these launches
 // are latency, not bandwidth; what matters is that there are few of them and that none waits for the host.
-#include "die_common.h"
-#include "die_rng.h"
+#include "die_search.h"
 
 namespace {
 
@@ -38,32 +37,11 @@ struct PgpeArgs {
 #define PGPE_W_VSQ 768           // [nb] partials of ClipUp's |v|^2
 #define PGPE_W_G 1024            // [P] g_mu, then ClipUp's unclipped velocity
 
-// Sum of one double per thread of a 256-thread workgroup, the same bits in every thread: xor butterfly inside each wave
-// (lane i and lane i ^ o add the same two values), then the four wave sums in a fixed order.
-__device__ double pgpe_block_sum(double v, double* lds) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, DIE_WAVE);
-    if ((threadIdx.x & (DIE_WAVE - 1)) == 0) lds[threadIdx.x / DIE_WAVE] = v;
-    __syncthreads();
-    const double t = (lds[0] + lds[1]) + (lds[2] + lds[3]);
-    __syncthreads();
-    return t;
-}
-
-// the sum of the nb workgroup partials at work[off]: the same bits in every workgroup that asks
-__device__ double pgpe_partials(const double* work, int off, int nb, double* lds) {
-    return pgpe_block_sum((int)threadIdx.x < nb ? work[off + threadIdx.x] : 0.0, lds);
-}
-
 __global__ __launch_bounds__(DIE_BLOCK) void k_pgpe_sample(PgpeArgs a, float* params, uint32_t generation) {
     const int64_t total = (int64_t)a.n * a.P;
     for (int64_t idx = (int64_t)blockIdx.x * DIE_BLOCK + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * DIE_BLOCK) {
         const int64_t i = idx / a.P, p = idx - i * a.P;
-        const die_u32x4 r = die_draw(a.seed, generation, (uint64_t)idx, DIE_STREAM_SEARCH);
-        const double u1 = ((double)r.v[0] + 1.0) * (1.0 / 4294967296.0);      // (0, 1]
-        const double u2 = (double)r.v[1] * (1.0 / 4294967296.0);              // [0, 1)
-        const double rad = sqrt(-2.0 * log(u1));
-        const double z = rad * cos(6.283185307179586 * u2);
+        const double z = die_search_normal(a.seed, generation, (uint64_t)idx, DIE_STREAM_SEARCH);
         const double c = (double)a.center[p];
         const double e = (double)a.stdev[p] * z;
         params[2 * i * a.P + p] = (float)(c + e);
@@ -75,19 +53,7 @@ __global__ __launch_bounds__(DIE_WAVE) void k_pgpe_rank(PgpeArgs a, const double
                                                         int64_t generation) {
     __shared__ double f[DIE_MAX_REPLICAS], sorted[DIE_MAX_REPLICAS];
     const int r = threadIdx.x, R = a.R;
-    if (r < R) {
-        const double* q = terms + r * sr;
-        double s = 0.0, v[8];
-        int64_t t = 0;
-        for (; t + 8 <= T; t += 8) {                    // eight loads in flight, then the adds in t order
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = q[(t + k) * st];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s += v[k];
-        }
-        for (; t < T; ++t) s += q[t * st];
-        f[r] = s;
-    }
+    if (r < R) f[r] = die_search_fitness(terms + r * sr, T, st);
     __syncthreads();
     if (r < R) {
         int k = 0;

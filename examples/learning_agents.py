@@ -2,10 +2,11 @@
 NeuralAutomataAgent candidates trained by PGPE (popsize 10, radius_init 1.5, ClipUp with max_speed 0.1 and momentum 0.9,
 center_learning_rate 0.05, stdev_learning_rate 0.1, the centre drawn in initial_bounds (-0.5, 0.5)), every generation one
 chain of launches on the GPU: sample into the population's parameter matrix, reset the batched worlds, `epoch_iters` batched
-steps, update (die_amd.search.PGPE).
+steps, update (die_amd.search.PGPE).  `--searcher cmaes` trains with the reference's other, commented-out searcher instead:
+separable CMA-ES with stdev_init 0.1 and popsize 10 (die_amd.search.CMAES), the same chain of launches.
 
-    python examples/learning_agents.py [--dynamics st-perlin-wide] [--size 96] [--generations 100] [--epoch-iters 30]
-                                       [--out saved_models/agent.pt] [--time]
+    python examples/learning_agents.py [--searcher pgpe|cmaes] [--dynamics st-perlin-wide] [--size 96] [--generations 100]
+                                       [--epoch-iters 30] [--out saved_models/agent.pt] [--time]
 
 Deliberate differences from the reference: every generation starts the R worlds from the same seeded state (the
 reference's run_epoch keeps stepping one env from candidate to candidate), no MLflow, and the noise is Philox's, so runs are
@@ -22,7 +23,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from die_amd import PGPE, Env, NeuralAutomataAgent                   # noqa: E402
+from die_amd import CMAES, PGPE, Env, NeuralAutomataAgent            # noqa: E402
 from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent    # noqa: E402
 from population_eval import AGENT_KW, DYNAMICS, evaluate_population, make_dynamics, make_population, run_epoch   # noqa: E402
 
@@ -30,15 +31,20 @@ RADIUS_INIT = 1.5
 MAX_SPEED = RADIUS_INIT / 15.              # the reference's rule of thumb
 SEARCH_KW = dict(radius_init=RADIUS_INIT, center_learning_rate=MAX_SPEED / 2., stdev_learning_rate=0.1, optimizer='clipup',
                  optimizer_config=dict(max_speed=MAX_SPEED, momentum=0.9))
+CMAES_KW = dict(stdev_init=0.1, separable=True)        # the reference's commented-out CMAES(problem, stdev_init=0.1, popsize=10, ...)
+SEARCHERS = ('pgpe', 'cmaes')
 
 
-def make_search(size, choice, popsize, epoch_iters, seed):
+def make_search(size, choice, popsize, epoch_iters, seed, searcher='pgpe'):
     torch.manual_seed(seed)
     template = NeuralAutomataAgent(**AGENT_KW)
     benv = BatchedEnv((size, size), make_dynamics(choice, size), replicas=popsize, seeds=[seed] * popsize)
     pop = BatchedNeuralAutomataAgent(benv, template)
-    searcher = PGPE(popsize, pop.P, seed=seed, **SEARCH_KW).for_population(pop, epoch_iters)
-    return searcher, pop
+    if searcher == 'cmaes':
+        search = CMAES(popsize, pop.P, seed=seed, **CMAES_KW)
+    else:
+        search = PGPE(popsize, pop.P, seed=seed, **SEARCH_KW)
+    return search.for_population(pop, epoch_iters), pop
 
 
 def host_generation(size, choice, template, mean, sigma, lr, iters, seed):
@@ -54,7 +60,7 @@ def host_generation(size, choice, template, mean, sigma, lr, iters, seed):
 
 def time_loops(args):
     G = args.generations
-    searcher, pop = make_search(args.size, args.dynamics, 10, args.epoch_iters, args.seed)
+    searcher, pop = make_search(args.size, args.dynamics, 10, args.epoch_iters, args.seed, args.searcher)
     searcher.run(2)                                               # warm-up: first launches, allocations
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -71,38 +77,41 @@ def time_loops(args):
         mean = host_generation(args.size, args.dynamics, template, mean, 0.1, 0.05, args.epoch_iters, args.seed)
     torch.cuda.synchronize()
     t_host = time.perf_counter() - t0
-    print(f'device loop (PGPE.run):     {G / t_dev:9.1f} generations/s  ({t_dev / G * 1e3:.3f} ms per generation)')
+    name = type(searcher).__name__ + '.run):'
+    print(f'device loop ({name:15s}{G / t_dev:9.1f} generations/s  ({t_dev / G * 1e3:.3f} ms per generation)')
     print(f'host-driven loop (rebuild): {G / t_host:9.1f} generations/s  ({t_host / G * 1e3:.3f} ms per generation)')
     print(f'speed-up: {t_host / t_dev:.2f}x  ({G} generations of 10 x {args.size}^2, {args.epoch_iters} steps, {args.dynamics})', flush=True)
 
 
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument('--searcher', choices=SEARCHERS, default='pgpe', help='PGPE (the reference\'s) or separable CMA-ES')
     p.add_argument('--dynamics', choices=DYNAMICS, default='st-perlin-wide')
     p.add_argument('--size', type=int, default=96)
     p.add_argument('--popsize', type=int, default=10)
-    p.add_argument('--generations', type=int, default=100, help='epochs of the reference: PGPE generations')
+    p.add_argument('--generations', type=int, default=100, help='epochs of the reference: search generations')
     p.add_argument('--epoch-iters', type=int, default=30, help='steps per evaluation')
     p.add_argument('--seed', type=int, default=0)
-    p.add_argument('--out', default=None, help='agent file for pop_best (default: saved_models/neuralautomataagent_pgpe_<G>x<T>.pt)')
+    p.add_argument('--out', default=None, help='agent file for pop_best (default: saved_models/neuralautomataagent_<searcher>_<G>x<T>.pt)')
     p.add_argument('--time', action='store_true')
     args = p.parse_args()
     if args.time:
         time_loops(args)
         return
-    searcher, pop = make_search(args.size, args.dynamics, args.popsize, args.epoch_iters, args.seed)
+    searcher, pop = make_search(args.size, args.dynamics, args.popsize, args.epoch_iters, args.seed, args.searcher)
     print(f'Network has {pop.P} parameters; {args.popsize} candidates on {args.size}x{args.size} {args.dynamics}, '
           f'{args.epoch_iters} steps each', flush=True)
     t0 = time.perf_counter()
     searcher.run(args.generations)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    for g, (mean, best, worst, median, gnorm, sd) in enumerate(searcher.history().tolist()):
+    col = '|grad|' if args.searcher == 'pgpe' else 'sigma'
+    for g, (mean, best, worst, median, col4, sd) in enumerate(searcher.history().tolist()):
         print(f'generation {g:4d}: mean {mean:10.4f}  median {median:10.4f}  best {best:10.4f}  worst {worst:10.4f}  '
-              f'|grad| {gnorm:.4f}  stdev {sd:.5f}')
+              f'{col} {col4:.4f}  stdev {sd:.5f}')
     st = searcher.status
     print(f'{args.generations} generations in {dt:.2f} s; best eval {st["best_eval"]:.4f}, last pop_best {st["pop_best_eval"]:.4f}')
-    out = args.out or os.path.join('saved_models', f'neuralautomataagent_pgpe_{args.generations}x{args.epoch_iters}.pt')
+    out = args.out or os.path.join('saved_models', f'neuralautomataagent_{args.searcher}_{args.generations}x{args.epoch_iters}.pt')
     os.makedirs(os.path.dirname(out) or '.', exist_ok=True)
     solution = searcher.pop_best_agent()
     solution.save(out)

@@ -677,6 +677,67 @@ int die_pgpe_sample(const die_pgpe* s, float* params, int64_t generation, void* 
 int die_pgpe_update(const die_pgpe* s, const float* params, const double* terms, int64_t T, int64_t stride_t, int64_t stride_r,
                     int64_t generation, void* stream);
 
+/* ---- separable CMA-ES over an (R, P) parameter matrix (die_cmaes.hip; die_amd/search.py CMAES) -------------------------
+ * The other searcher of the reference's examples/learning_agents.py (evotorch's CMAES(separable=True)): a diagonal
+ * covariance, cumulative step-size control, rank-one and rank-mu updates, optional active (negative) weights.
+ * lambda = R (2..DIE_MAX_REPLICAS, odd allowed), d = P, g = generation.  The state is float64 in the caller's device
+ * buffers; sigma is a device scalar, double-buffered by parity: generation g reads sigma[g & 1], its update writes
+ * sigma[(g + 1) & 1].  Neither call reads anything back to the host.
+ *   sample: z(i, p) = sqrt(-2 ln u1) cos(2 pi u2), u1 = (w0 + 1) / 2^32, u2 = w1 / 2^32 from the first two words of
+ *     Philox(counter = (i d + p, g, DIE_STREAM_CMAES), key = seed); row i = fl32(m_p + (sigma sqrt(C_p)) z(i, p)).  Not
+ *     symmetric.  One launch.
+ *   constants (the caller's, computed once on the host in float64 and stored below; die_amd/search.py cmaes_constants):
+ *     w'_k = ln((lambda + 1) / 2) - ln k, k = 1..lambda; mu = floor(lambda / 2); w_k = w'_k / sum_{j<=mu} w'_j for k <= mu,
+ *     mu_eff = 1 / sum_{k<=mu} w_k^2; mu_eff- = (sum w'-)^2 / sum (w'-)^2 over the k > mu (w'_k <= 0);
+ *     c_sigma = r_sigma (mu_eff + 2) / (d + mu_eff + 5); d_sigma = r_damp (1 + 2 max(0, sqrt((mu_eff - 1) / (d + 1)) - 1) + c_sigma);
+ *     c_c = r_c (1 + 1/d + mu_eff/d) / (sqrt(d) + 1/d + 2 mu_eff/d); c_1 = r_1 / (d + 2 sqrt(d) + mu_eff/d);
+ *     c_mu = r_mu min(1 - c_1, (0.25 + mu_eff + 1/mu_eff - 2) / (d + 4 sqrt(d) + mu_eff/2));
+ *     chi_d = sqrt(d) (1 - 1/(4d) + 1/(21 d^2)); for k > mu (active) w_k = w'_k min(a_mu, a_mueff, a_posdef) / sum |w'-| with
+ *     a_mu = 1 + c_1/c_mu, a_mueff = 1 + 2 mu_eff- / (mu_eff + 2), a_posdef = (1 - c_1 - c_mu) / (d c_mu); not active: 0.
+ *   update: f_r = sum over t ascending of terms[t stride_t + r stride_r] (the (T, R, 2) die_step_result words: stride_t = 2R,
+ *     stride_r = 2); ranks k = 1..lambda by descending f, ties to the lower replica index; z_i is regenerated from the counter
+ *     of generation g (nothing of sample is stored), y_i = sqrt(C_p) z_i.  In this order:
+ *       y_w = sum_{k<=mu} w_k y_{k:lambda}, z_w likewise (summed best first);   m <- m + (c_m sigma) y_w;
+ *       p_sigma <- (1 - c_sigma) p_sigma + sqrt(c_sigma (2 - c_sigma) mu_eff) z_w;
+ *       h_sigma = [|p_sigma| / sqrt(1 - (1 - c_sigma)^(2(g + 1))) < (1.4 + 2/(d + 1)) chi_d];
+ *       p_c <- (1 - c_c) p_c + h_sigma sqrt(c_c (2 - c_c) mu_eff) y_w;
+ *       C_p <- (1 + c_1 (1 - h_sigma) c_c (2 - c_c) - c_1 - c_mu sum_k w_k) C_p + c_1 p_c,p^2 + c_mu sum_k w°_k y_{k:lambda,p}^2,
+ *         w°_k = w_k (w_k >= 0), w_k d / |z_{k:lambda}|^2 (w_k < 0), y with the old C, summed best first;
+ *       sigma <- sigma exp((c_sigma / d_sigma) (|p_sigma| / chi_d - 1)), or with csa_squared
+ *       sigma <- sigma exp((c_sigma / (2 d_sigma)) (|p_sigma|^2 / d - 1)).
+ *     pop_best = the row of rank 1, best = the best row ever (replaced on a strictly greater f); history row g = (mean, max,
+ *     min, median of f, the new sigma, the mean over p of the new sigma sqrt(C_p)).  Four launches (rank, mean and paths,
+ *     covariance and sigma, statistics); |p_sigma|^2 and the lambda |z_i|^2 are fixed-tree reductions (no float atomics):
+ *     the same bits on every run.  `params` is the matrix the same generation's sample filled, read only for the two rows. */
+#define DIE_CMAES_MAX_BLOCKS 256
+#define DIE_CMAES_WORK_DOUBLES(R, P) ((4 + (int64_t)(R)) * DIE_CMAES_MAX_BLOCKS + (int64_t)(P))
+typedef struct die_cmaes {
+    int32_t replicas;                  /* lambda: 2..DIE_MAX_REPLICAS */
+    int32_t csa_squared;               /* 0: sigma from |p_sigma| / chi_d; 1: from |p_sigma|^2 / d */
+    int64_t num_params;                /* d >= 1 */
+    uint64_t seed;                     /* Philox key of the sampling */
+    double c_m;                        /* > 0 */
+    double c_sigma, d_sigma;           /* (0, 1], > 0 */
+    double c_c, c_1, c_mu;             /* (0, 1], >= 0, >= 0 with c_1 + c_mu <= 1 */
+    double mu_eff, chi_d;              /* >= 1, > 0 */
+    double weights[DIE_MAX_REPLICAS];  /* w_k of rank k + 1 (best first); w_1 > 0; entries lambda.. unused */
+    double* center;                    /* m [d] */
+    double* C;                         /* [d] diagonal covariance */
+    double* p_sigma;                   /* [d] */
+    double* p_c;                       /* [d] */
+    double* sigma;                     /* [2] by generation parity */
+    float* pop_best;                   /* [d] */
+    float* best;                       /* [d] */
+    double* fitness;                   /* [R] f of the last update */
+    double* evals;                     /* [2]: pop_best's f, best's f (set best's to -inf before the first update) */
+    double* history;                   /* [history_rows][6] */
+    int64_t history_rows;              /* update needs generation < history_rows */
+    double* work;                      /* DIE_CMAES_WORK_DOUBLES(R, P) float64 scratch */
+} die_cmaes;
+int die_cmaes_sample(const die_cmaes* s, float* params, int64_t generation, void* stream);
+int die_cmaes_update(const die_cmaes* s, const float* params, const double* terms, int64_t T, int64_t stride_t, int64_t stride_r,
+                     int64_t generation, void* stream);
+
 /* ---- message packing for decomposed worlds (die_amd/dist.py; no reference counterpart) ----------
  * A block [r0, r1) x [c0, c1) of a row-major plane (pitch in elements, 2/4/8-byte elements) copied
  * to / from byte offset buf_offset of one contiguous message buffer; up to 16 blocks per launch. */
