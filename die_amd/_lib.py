@@ -169,6 +169,7 @@ _SIGNATURES = {
     'die_forward_env_step': (C.c_int, [_P(Medium), _P(Agents), _P(GradientAgent), _P(Action), _P(Dynamics), C.c_void_p,
                                        C.c_void_p, C.c_int64, C.c_void_p]),
     'die_batch_workspace_bytes': (C.c_int64, [C.c_int32]),
+    'die_batch_lifecycle_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int64]),
     'die_forward_env_step_batch': (C.c_int, [_P(Medium), _P(Agents), _P(GradientAgent), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
                                              C.c_void_p, C.c_int64, C.c_void_p]),
     'die_nca_batch_scratch_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),

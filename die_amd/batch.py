@@ -14,7 +14,11 @@ NeuralAutomataAgent holding row r of the (R, P) parameter matrix — L + 2 launc
 A device food-flow operator (`WaveSequence` / `PerlinNoiseSequence.get_flow_operator`) runs on every replica: replica r is then
 the stand-alone run with a fresh operator over the same sequence whose counter starts where the batch's stood at the first
 batched step — every replica sees the same t, and the batch's operator advances once per batched step.  One more launch
-per step (`die_food_flow_batch`) in the small-world regime (tests/test_gpu_flow_batch.py)."""
+per step (`die_food_flow_batch`) in the small-world regime (tests/test_gpu_flow_batch.py).
+
+`Dynamics(agents_die=True)` (compat='intended') runs on the replicas too: replica r is then the stand-alone Env of that
+pressure, starved slots zeroed and `num_agents` falling.  One more launch per step in the small-world regime, the dead-slot +
+lifecycle pass of every replica (tests/test_gpu_batch_lifecycle.py)."""
 import ctypes as C
 import dataclasses
 import math
@@ -52,8 +56,14 @@ class BatchedEnv:
             raise ValueError(f'{len(seeds)} seeds for {replicas} replicas')
         self.dynamics = dynamics or Dynamics()
         d = self.dynamics
-        if d.agents_die or d.apply_sense_mask or d.diffuse_mode != 'wrap' or not isinstance(d.boundary, BoundaryCondition):
-            raise NotImplementedError('batched replicas: wrap diffusion, no agents_die, no sense mask')
+        if d.agents_die and d.compat != 'intended':
+            raise NotImplementedError(f"batched replicas: agents_die with compat={d.compat!r} (the host-driven frozen-indexer "
+                                      "sequence of Env); only compat='intended' is batched")
+        if d.apply_sense_mask:
+            raise NotImplementedError('batched replicas: apply_sense_mask is not batched')
+        if d.diffuse_mode != 'wrap' or not isinstance(d.boundary, BoundaryCondition):
+            raise NotImplementedError(f"batched replicas: diffuse_mode={d.diffuse_mode!r}, boundary={d.boundary!r}: only 'wrap' "
+                                      'diffusion and a BoundaryCondition are batched')
         self.R, self.seed = int(replicas), int(seed)
         self.seeds = [self.seed + r for r in range(self.R)] if seeds is None else [int(q) for q in seeds]
         self.W, self.H = int(field_size[0]), int(field_size[1])
@@ -99,7 +109,9 @@ class BatchedEnv:
             self.x[r, :k].copy_(e.agents.x); self.y[r, :k].copy_(e.agents.y)
             self.alive[r, :k].copy_(e.agents.alive); self.agent_food[r, :k].copy_(e.agents.agent_food)
         self.epoch = 1
-        self._ws = torch.zeros(int(_lib.lib.die_batch_workspace_bytes(R)), dtype=torch.uint8, device=dev)
+        # agents_die: the claim pass stashes every dead slot's feed and action cost for the lifecycle pass
+        ws = _lib.lib.die_batch_lifecycle_workspace_bytes(R, Nm) if d.agents_die else _lib.lib.die_batch_workspace_bytes(R)
+        self._ws = torch.zeros(int(ws), dtype=torch.uint8, device=dev)
         self._steps = 0
         self._initial = (self._state.clone(), self.chem, self.chem_next)
         self._flow_k0 = getattr(self.dynamics.op_food_flow, '_k', None)
@@ -130,7 +142,7 @@ class BatchedEnv:
         d = self.dynamics
         boundary = _lib.DIE_BOUNDARY_WRAP if d.boundary == BoundaryCondition.wrap else _lib.DIE_BOUNDARY_LIMIT
         cost = _lib.DIE_COST_LINEAR if d.op_action_cost is linear_action_cost else _lib.DIE_COST_ZERO
-        dyn = _lib.Dynamics(d.rate_feed, d.rate_decay_chem, d.diffuse_sigma, boundary, cost, 0.02, 0.01, int(d.food_infinite), 0, 0, 0, 0)
+        dyn = _lib.Dynamics(d.rate_feed, d.rate_decay_chem, d.diffuse_sigma, boundary, cost, 0.02, 0.01, int(d.food_infinite), int(d.agents_die), 0, 0, 0)
         b = _lib.Batch(self.R, 0, self.W * self.H, self.Nmax, 1, (C.c_int64 * 64)(*self.n))
         return m, a, dyn, b
 
@@ -145,7 +157,7 @@ class BatchedEnv:
     def step(self, agent: Union['BatchedPhysarumAgent', 'BatchedNeuralAutomataAgent'],
              results: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One step of every replica: `agent.forward` + `Env.step` fused, two launches for the whole batch (L + 2 for a
-        BatchedNeuralAutomataAgent of L layers).  Returns the (R, 2) float64 tensor of die_step_result words (device;
+        BatchedNeuralAutomataAgent of L layers; one more with agents_die).  Returns the (R, 2) float64 tensor of die_step_result words (device;
         `read_results` decodes)."""
         if isinstance(agent, BatchedNeuralAutomataAgent):
             return self._step_nca(agent, results)

@@ -7,6 +7,8 @@
 //                  _agent_lifecycle (:245-261) when agents_die; alive count
 //   k_reduce       fixed-order sum of the per-block partials → die_step_result (deterministic)
 //   k_diffuse      _medium_diffuse_decay (:136-145): separable gaussian, periodic, × (1 − decay)
+//   k_lifecycle_batch  k_resolve's dead-slot + lifecycle work for R replicas (blockIdx.y) when agents_die: dead-slot feed from the
+//                  claim pass's stash (consumed and action cost), starved slots zeroed, alive count per replica
 //   k_nca_move_claim_batch  a NeuralAutomataAgent population (die_nca_env_step_batch): every agent reads its action out of
 //                  its candidate's last conv planes (die_gather_scale's product, in registers), then k_move_claim's work
 //
@@ -45,6 +47,7 @@ struct StepArgs {
     int boundary, cost, food_infinite, agents_die, has_dead;
     int skip_scatter;      // fused step: the winner's chem/food writes are done by k_diffuse_rows
     float* stash;          // N floats, only when has_dead
+    float* stash_cost;     // batched lifecycle: the dead slots' action_cost next to `stash` (their actions stay in registers)
     long long* part_gain;  // gridDim.x fixed-point sums (die_fix)
     long long* part_alive; // gridDim.x
 };
@@ -105,7 +108,10 @@ __device__ __forceinline__ float move_claim_one(const StepArgs& a, const int64_t
         }
         return gained;
     }
-    if (a.has_dead) a.stash[n] = consumed;
+    if (a.has_dead) {
+        a.stash[n] = consumed;
+        if (a.stash_cost) a.stash_cost[n] = action_cost(a, dx, dy, dep);   // the same ops k_resolve performs on the stored action
+    }
     return 0.f;
 }
 
@@ -168,6 +174,17 @@ struct BatchArgs {
     int64_t n[DIE_MAX_REPLICAS];
 };
 
+// replica r's alive-count partials and dead-slot stash.  Without dead slots the claim pass writes the count partials; with
+// them the lifecycle pass (k_lifecycle_batch) does, and the claim pass stashes each dead slot's `consumed` and action cost in
+// replica r's [consumed | cost] pair of agent_stride floats (a.stash: replica 0's, behind the partials of every replica)
+__device__ __forceinline__ void batch_stash(StepArgs& a, const BatchArgs& b, int r) {
+    a.part_alive = a.has_dead ? nullptr : a.part_gain + 2 * DIE_MAX_PARTIALS;
+    if (a.has_dead) {
+        a.stash += 2 * b.agents * r;
+        a.stash_cost = a.stash + b.agents;
+    }
+}
+
 template <typename T, int KIND, bool LEAN = false>
 __global__ __launch_bounds__(DIE_STEP_BLOCK) void k_forward_move_claim_batch(FwdArgs f, StepArgs a, BatchArgs b) {
     if (LEAN) fwd_args_lean(f);
@@ -183,9 +200,10 @@ __global__ __launch_bounds__(DIE_STEP_BLOCK) void k_forward_move_claim_batch(Fwd
     if (a.slot) a.slot += pa;
     a.N = b.n[r];
     a.part_gain += (int64_t)DIE_MAX_PARTIALS * 3 * r;               // replica r's own workspace partials
-    a.part_alive = a.part_gain + 2 * DIE_MAX_PARTIALS;
+    batch_stash(a, b, r);
     forward_move_claim_body<T, KIND, false>(f, a);
-    if (blockIdx.x == 0 && threadIdx.x == 0) a.part_alive[0] = a.N;  // every slot is alive: the sweep's reduction reads the count here
+    // every slot is alive: the sweep's reduction reads the count here (with dead slots, k_lifecycle_batch counts them)
+    if (!a.has_dead && blockIdx.x == 0 && threadIdx.x == 0) a.part_alive[0] = a.N;
 }
 
 // NeuralAutomataAgent population (die_nca_env_step_batch): replica r's agents read their action out of the last layer's
@@ -205,7 +223,7 @@ __global__ __launch_bounds__(DIE_STEP_BLOCK) void k_nca_move_claim_batch(NcaRead
     a.x += pa; a.y += pa; a.alive += pa; a.agent_food += pa;
     a.N = b.n[r];
     a.part_gain += (int64_t)DIE_MAX_PARTIALS * 3 * r;
-    a.part_alive = a.part_gain + 2 * DIE_MAX_PARTIALS;
+    batch_stash(a, b, r);
     const float* s0 = q.sense + q.rep * r;
     const float* s1 = s0 + q.cells;
     const float* s2 = s1 + q.cells;
@@ -222,11 +240,11 @@ __global__ __launch_bounds__(DIE_STEP_BLOCK) void k_nca_move_claim_batch(NcaRead
         gsum += die_fix(move_claim_one<T, false>(a, n, X, Y, dx, dy, dep, (uint32_t)n, cnt));
     }
     block_sum_store(gsum, cnt, a.part_gain, a.part_alive);
-    if (blockIdx.x == 0 && threadIdx.x == 0) a.part_alive[0] = a.N;  // every slot is alive (as k_forward_move_claim_batch)
+    if (!a.has_dead && blockIdx.x == 0 && threadIdx.x == 0) a.part_alive[0] = a.N;  // every slot is alive (as k_forward_move_claim_batch)
 }
 
 template <typename T>
-__global__ __launch_bounds__(DIE_STEP_BLOCK) void k_resolve(StepArgs a) {
+__device__ __forceinline__ void resolve_body(const StepArgs& a) {
     T* food = (T*)a.food;
     T* chem = (T*)a.chem;
     long long gsum = 0;
@@ -248,7 +266,7 @@ __global__ __launch_bounds__(DIE_STEP_BLOCK) void k_resolve(StepArgs a) {
             }
         } else if (!alive && a.has_dead) {
             const float consumed = die_claim_occupied(a.owner[c], a.epoch) ? a.stash[n] : 0.f;
-            const float gained = consumed - action_cost(a, a.dx[n], a.dy[n], a.dep[n]);
+            const float gained = consumed - (a.stash_cost ? a.stash_cost[n] : action_cost(a, a.dx[n], a.dy[n], a.dep[n]));
             a.agent_food[n] += gained;
             if (owned) gsum += die_fix(gained);
         }
@@ -259,6 +277,25 @@ __global__ __launch_bounds__(DIE_STEP_BLOCK) void k_resolve(StepArgs a) {
         alive_cnt += (alive && owned) ? 1 : 0;
     }
     block_sum_store(gsum, alive_cnt, a.part_gain, a.part_alive);
+}
+
+template <typename T>
+__global__ __launch_bounds__(DIE_STEP_BLOCK) void k_resolve(StepArgs a) { resolve_body<T>(a); }
+
+// die_agent_dead_slots of R replicas in one launch (blockIdx.y = replica, the claim pass's x-grid): dead slots finish their
+// feed from the claim pass's stash, _agent_lifecycle, alive count.  Replica r's dead-slot gains go to its second partial array,
+// its counts to the third (the batched sweep's reduction sums both gain arrays).  No plane is written (skip_scatter).
+__global__ __launch_bounds__(DIE_STEP_BLOCK) void k_lifecycle_batch(StepArgs a, BatchArgs b) {
+    const int r = blockIdx.y;
+    const int64_t pa = b.agents * r;
+    a.owner += b.cells * r;
+    a.x += pa; a.y += pa; a.alive += pa; a.agent_food += pa;
+    a.N = b.n[r];
+    a.part_gain += (int64_t)DIE_MAX_PARTIALS * 3 * r;
+    batch_stash(a, b, r);
+    a.part_gain += DIE_MAX_PARTIALS;
+    a.part_alive = a.part_gain + DIE_MAX_PARTIALS;
+    resolve_body<float>(a);          // (skip_scatter: the planes' dtype is never touched)
 }
 
 __global__ __launch_bounds__(1024) void k_reduce(const long long* pa, int na, const long long* pb, int nb,
@@ -393,6 +430,7 @@ struct RowsArgs {
     // k_reduce folded in: workgroup (0, 0) first sums the claim pass's `n_part` partial gains (a kernel boundary lies
     // between their producer and this sweep) in k_reduce's order and writes the step result — one launch less per step
     const long long* part_gain;
+    const long long* part_gain2;       // NULL, or a second `n_part` partial gains (batched replicas' dead-slot pass)
     const long long* part_alive;       // NULL: num_alive = alive_const; else the sum of the claim pass's counts (ghost tiles)
     int n_part;
     die_step_result* result;
@@ -429,6 +467,7 @@ __global__ __launch_bounds__(DIF_BLOCK) void k_diffuse_rows(RowsArgs a) {
         if (FUSED) a.food = (T*)a.food + pc;
         if (a.result) {
             a.part_gain += (int64_t)DIE_MAX_PARTIALS * 3 * blockIdx.z;
+            if (a.part_gain2) a.part_gain2 += (int64_t)DIE_MAX_PARTIALS * 3 * blockIdx.z;
             if (a.part_alive) a.part_alive += (int64_t)DIE_MAX_PARTIALS * 3 * blockIdx.z;
             a.result += blockIdx.z;
         }
@@ -457,6 +496,7 @@ __global__ __launch_bounds__(DIF_BLOCK) void k_diffuse_rows(RowsArgs a) {
             return t;
         };
         long long g = strided_sum(a.part_gain);                    // fixed point: any order
+        if (FUSED == 1 && a.part_gain2) g += strided_sum(a.part_gain2);      // (batched replicas only)
         s_g[threadIdx.x] = g;
         __syncthreads();
         for (int o = DIF_BLOCK / 2; o > 0; o >>= 1) {
@@ -661,7 +701,7 @@ static int diffuse_decay_mode(const void* src, void* dst, int32_t W, int32_t H, 
         double wd[2 * DIF_MAXR + 1];
         gaussian_taps(sigma, wd);
         ra.src = src; ra.dst = dst; ra.claim = nullptr; ra.dep = nullptr; ra.food = nullptr; ra.W = W; ra.H = H; ra.epoch = 0; ra.halo = 0; ra.rep_cells = 0;
-        ra.wrapx = ra.wrapy = 1; ra.part_gain = nullptr; ra.part_alive = nullptr; ra.n_part = 0; ra.result = nullptr; ra.alive_const = 0;
+        ra.wrapx = ra.wrapy = 1; ra.part_gain = nullptr; ra.part_gain2 = nullptr; ra.part_alive = nullptr; ra.n_part = 0; ra.result = nullptr; ra.alive_const = 0;
         ra.food_infinite = 1; ra.keep = (float)(1.0 - (double)decay); ra.rate_feed = 0.f;
         for (int k = 0; k <= 2 * R; ++k) ra.w[k] = (float)wd[k];
         int rc2 = dtype == DIE_F32 ? launch_rows<float, 0>(ra, R, (hipStream_t)stream)
@@ -747,6 +787,7 @@ static int fill_args(StepArgs& k, const die_medium* m, const die_agents* a, cons
     // ghost-agent tiles: num_alive is the number of alive slots on OWNED cells, counted by the claim pass
     k.part_alive = k.g.own_x1 > 0 ? (long long*)ws + 2 * DIE_MAX_PARTIALS : nullptr;
     k.stash = (float*)(w + WS_PARTS + die_ws_scan_bytes(m->W, m->H));
+    k.stash_cost = nullptr;
     return DIE_OK;
 }
 
@@ -840,7 +881,7 @@ extern "C" int die_diffuse_decay_tile(const void* src, void* dst, int32_t W, int
     double wd[2 * DIF_MAXR + 1];
     gaussian_taps(sigma, wd);
     ra.src = src; ra.dst = dst; ra.claim = nullptr; ra.dep = nullptr; ra.food = nullptr; ra.W = W; ra.H = H; ra.epoch = 0; ra.halo = 0; ra.rep_cells = 0;
-    ra.wrapx = ra.wrapy = 0; ra.part_gain = nullptr; ra.part_alive = nullptr; ra.n_part = 0; ra.result = nullptr; ra.alive_const = 0;
+    ra.wrapx = ra.wrapy = 0; ra.part_gain = nullptr; ra.part_gain2 = nullptr; ra.part_alive = nullptr; ra.n_part = 0; ra.result = nullptr; ra.alive_const = 0;
     ra.food_infinite = 1; ra.keep = (float)(1.0 - (double)decay); ra.rate_feed = 0.f;
     for (int k = 0; k <= 2 * R; ++k) ra.w[k] = (float)wd[k];
     int rc = dtype == DIE_F32 ? launch_rows<float, 0, false>(ra, R, (hipStream_t)stream)
@@ -1036,6 +1077,27 @@ extern "C" int64_t die_batch_workspace_bytes(int32_t replicas) {
     return replicas >= 1 && replicas <= DIE_MAX_REPLICAS ? (int64_t)replicas * WS_PARTS : -1;
 }
 
+// with dead slots (agents_die / has_dead_slots): the partials of every replica, then per replica a [consumed | cost] stash
+// of agent_stride floats each (k_lifecycle_batch)
+extern "C" int64_t die_batch_lifecycle_workspace_bytes(int32_t replicas, int64_t agent_stride) {
+    if (replicas < 1 || replicas > DIE_MAX_REPLICAS || agent_stride < 1 || agent_stride > (int64_t)DIE_OWNER_SLOT_MASK) return -1;
+    const int64_t b = (int64_t)replicas * WS_PARTS + (int64_t)replicas * 2 * agent_stride * (int64_t)sizeof(float);
+    return (b + 255) & ~(int64_t)255;
+}
+
+// the workspace checks of both batched entry points (before anything else is read)
+static int batch_ws_check(const die_dynamics* d, const die_batch* b, int64_t ws_bytes, const char* who) {
+    DIE_REQUIRE(b->replicas >= 1 && b->replicas <= DIE_MAX_REPLICAS, "%s: 1..%d replicas", who, DIE_MAX_REPLICAS);
+    DIE_REQUIRE(ws_bytes >= die_batch_workspace_bytes(b->replicas), "%s: workspace too small", who);
+    if (d->agents_die || d->has_dead_slots) {
+        const int64_t need = die_batch_lifecycle_workspace_bytes(b->replicas, b->agent_stride);
+        DIE_REQUIRE(need > 0, "%s: bad agent stride %lld", who, (long long)b->agent_stride);
+        DIE_REQUIRE(ws_bytes >= need, "%s: workspace too small for dead slots (%lld < %lld: die_batch_lifecycle_workspace_bytes)", who,
+                    (long long)ws_bytes, (long long)need);
+    }
+    return DIE_OK;
+}
+
 // the step half's arguments of every replica (die_forward_env_step_batch, die_nca_env_step_batch), checked before any launch
 static int batch_step_args(StepArgs& k, BatchArgs& ba, int64_t& nmax, const die_medium* m, const die_agents* a, const die_action* act,
                            const die_dynamics* d, const die_batch* b, void* ws, const char* who) {
@@ -1053,7 +1115,10 @@ static int batch_step_args(StepArgs& k, BatchArgs& ba, int64_t& nmax, const die_
     k.dx = act ? act->dx : nullptr; k.dy = act ? act->dy : nullptr; k.dep = act ? act->deposit : nullptr;
     k.rate_feed = d->rate_feed; k.w_dep = d->cost_w_deposit; k.w_dist = d->cost_w_dist;
     k.boundary = d->boundary; k.cost = d->cost; k.food_infinite = d->food_infinite;
+    k.agents_die = d->agents_die; k.has_dead = d->has_dead_slots || d->agents_die;
+    k.skip_scatter = 1;                                 // (k_lifecycle_batch: the sweep writes the planes)
     k.part_gain = (long long*)ws;
+    k.stash = k.has_dead ? (float*)((char*)ws + (int64_t)b->replicas * WS_PARTS) : nullptr;   // batch_stash offsets it per replica
     ba.cells = b->plane_stride; ba.agents = b->agent_stride; ba.seed_stride = b->seed_stride;
     nmax = 0;
     for (int r = 0; r < DIE_MAX_REPLICAS; ++r) {
@@ -1064,7 +1129,16 @@ static int batch_step_args(StepArgs& k, BatchArgs& ba, int64_t& nmax, const die_
     return DIE_OK;
 }
 
+// with dead slots: the dead-slot pass + _agent_lifecycle of every replica in one launch, on the claim pass's grid
+static int batch_lifecycle(const StepArgs& k, const BatchArgs& ba, dim3 grid, hipStream_t s, const char* who) {
+    if (!k.has_dead) return DIE_OK;
+    k_lifecycle_batch<<<grid, DIE_STEP_BLOCK, 0, s>>>(k, ba);
+    DIE_CHECK_LAUNCH(who);
+    return DIE_OK;
+}
+
 // the field sweep of every replica in one launch (gridDim.z), each with its own reduction workgroup over the n_part partials
+// (and, with dead slots, over the lifecycle pass's n_part partial gains too)
 static int batch_sweep(const die_medium* m, const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws, int n_part,
                        hipStream_t s, const char* who) {
     const int R = (int)(4.0 * (double)d->diffuse_sigma + 0.5);
@@ -1075,6 +1149,7 @@ static int batch_sweep(const die_medium* m, const die_dynamics* d, const die_bat
     ra.W = m->W; ra.H = m->H; ra.epoch = m->epoch; ra.food_infinite = d->food_infinite; ra.halo = 0; ra.rep_cells = b->plane_stride;
     ra.wrapx = ra.wrapy = 1;
     ra.part_gain = (const long long*)ws; ra.part_alive = (const long long*)ws + 2 * DIE_MAX_PARTIALS; ra.n_part = n_part;
+    ra.part_gain2 = d->agents_die || d->has_dead_slots ? (const long long*)ws + DIE_MAX_PARTIALS : nullptr;
     ra.result = results; ra.alive_const = 0;
     ra.keep = (float)(1.0 - (double)d->rate_decay_chem); ra.rate_feed = d->rate_feed;
     for (int q = 0; q <= 2 * R; ++q) ra.w[q] = (float)wd[q];
@@ -1089,10 +1164,9 @@ extern "C" int die_forward_env_step_batch(const die_medium* m, const die_agents*
                                           int64_t ws_bytes, void* stream) {
     const char* who = "die_forward_env_step_batch";
     DIE_REQUIRE(m && a && g && d && b && results && ws, "%s: null argument", who);
-    DIE_REQUIRE(b->replicas >= 1 && b->replicas <= DIE_MAX_REPLICAS, "%s: 1..%d replicas", who, DIE_MAX_REPLICAS);
-    DIE_REQUIRE(ws_bytes >= die_batch_workspace_bytes(b->replicas), "%s: workspace too small", who);
-    DIE_REQUIRE(m->gW <= 0 && !m->sense_mask && !d->has_dead_slots && !d->agents_die && !d->staged,
-                "%s: periodic single-tile replicas with every slot alive (no agents_die, no sense mask)", who);
+    int rc = batch_ws_check(d, b, ws_bytes, who);
+    if (rc != DIE_OK) return rc;
+    DIE_REQUIRE(m->gW <= 0 && !m->sense_mask && !d->staged, "%s: periodic single-tile replicas (no sense mask)", who);
     DIE_REQUIRE(m->chem_next && m->chem_next != m->chem, "%s: chem_next must be a second plane", who);
     DIE_REQUIRE(b->plane_stride >= (int64_t)m->W * m->H && b->agent_stride >= a->N, "%s: strides smaller than a replica", who);
     if (!fused_step_applies(m, d)) {
@@ -1100,7 +1174,7 @@ extern "C" int die_forward_env_step_batch(const die_medium* m, const die_agents*
         return DIE_ERR_UNSUPPORTED;
     }
     FwdArgs f;
-    int rc = die_fill_fwd_args(f, m, a, g, act, who);
+    rc = die_fill_fwd_args(f, m, a, g, act, who);
     if (rc != DIE_OK) return rc;
     StepArgs k;
     BatchArgs ba;
@@ -1119,6 +1193,8 @@ extern "C" int die_forward_env_step_batch(const die_medium* m, const die_agents*
         else k_forward_move_claim_batch<__half, DIE_AGENT_PHYSARUM><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba);
     }
     DIE_CHECK_LAUNCH(who);
+    rc = batch_lifecycle(k, ba, grid, s, who);
+    if (rc != DIE_OK) return rc;
     return batch_sweep(m, d, b, results, ws, (int)grid.x, s, who);
 }
 
@@ -1131,10 +1207,10 @@ extern "C" int die_nca_env_step_batch(const die_medium* m, const die_agents* a, 
                                       int64_t ws_bytes, void* stream) {
     const char* who = "die_nca_env_step_batch";
     DIE_REQUIRE(m && a && nca && d && b && results && ws, "%s: null argument", who);
-    DIE_REQUIRE(b->replicas >= 1 && b->replicas <= DIE_MAX_REPLICAS, "%s: 1..%d replicas", who, DIE_MAX_REPLICAS);
-    DIE_REQUIRE(ws_bytes >= die_batch_workspace_bytes(b->replicas), "%s: workspace too small", who);
-    DIE_REQUIRE(m->gW <= 0 && !m->sense_mask && !d->has_dead_slots && !d->agents_die && !d->staged && !a->slot,
-                "%s: periodic single-tile replicas with every slot alive, in slot order (no agents_die, no sense mask)", who);
+    int rc = batch_ws_check(d, b, ws_bytes, who);
+    if (rc != DIE_OK) return rc;
+    DIE_REQUIRE(m->gW <= 0 && !m->sense_mask && !d->staged && !a->slot,
+                "%s: periodic single-tile replicas in slot order (no sense mask)", who);
     DIE_REQUIRE(m->food && m->chem && m->chem_next && m->chem_next != m->chem, "%s: null plane, or chem_next not a second plane", who);
     DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad field dtype %d", who, m->dtype);
     DIE_REQUIRE(a->x && a->y, "%s: null agent arrays", who);
@@ -1143,7 +1219,7 @@ extern "C" int die_nca_env_step_batch(const die_medium* m, const die_agents* a, 
         die_set_error("%s: only for periodic planes with H %% 4 == 0 and gaussian radius 1..4", who);
         return DIE_ERR_UNSUPPORTED;
     }
-    int rc = die_nca_batch_check(nca, m->W, m->H, b->replicas, who);
+    rc = die_nca_batch_check(nca, m->W, m->H, b->replicas, who);
     if (rc != DIE_OK) return rc;
     DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX && m->epoch == nca->sense_epoch % DIE_OWNER_EPOCH_MAX + 1,
                 "%s: claims at epoch %d cannot follow sensing at epoch %d", who, m->epoch, nca->sense_epoch);
@@ -1171,6 +1247,8 @@ extern "C" int die_nca_env_step_batch(const die_medium* m, const die_agents* a, 
     if (m->dtype == DIE_F32) k_nca_move_claim_batch<float><<<grid, DIE_STEP_BLOCK, 0, s>>>(q, k, ba);
     else k_nca_move_claim_batch<__half><<<grid, DIE_STEP_BLOCK, 0, s>>>(q, k, ba);
     DIE_CHECK_LAUNCH(who);
+    rc = batch_lifecycle(k, ba, grid, s, who);
+    if (rc != DIE_OK) return rc;
     return batch_sweep(m, d, b, results, ws, (int)grid.x, s, who);
 }
 
@@ -1193,7 +1271,7 @@ static int deposit_feed_diffuse(const die_medium* m, const die_dynamics* d, int 
     ra.src = m->chem; ra.dst = m->chem_next; ra.claim = (const unsigned long long*)m->owner; ra.dep = dep_plane; ra.food = m->food;
     ra.W = m->W; ra.H = m->H; ra.epoch = m->epoch; ra.food_infinite = d->food_infinite; ra.halo = halo; ra.rep_cells = 0;
     ra.wrapx = tile && m->gW > 0 && m->W == m->gW; ra.wrapy = tile && m->gW > 0 && m->H == m->gH;
-    ra.part_gain = part_gain; ra.part_alive = part_alive; ra.n_part = n_part; ra.result = result; ra.alive_const = alive_const;
+    ra.part_gain = part_gain; ra.part_gain2 = nullptr; ra.part_alive = part_alive; ra.n_part = n_part; ra.result = result; ra.alive_const = alive_const;
     ra.keep = (float)(1.0 - (double)d->rate_decay_chem); ra.rate_feed = d->rate_feed;
     for (int k = 0; k <= 2 * R; ++k) ra.w[k] = (float)wd[k];
     int rc;

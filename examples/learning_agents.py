@@ -6,7 +6,7 @@ steps, update (die_amd.search.PGPE).  `--searcher cmaes` trains with the referen
 separable CMA-ES with stdev_init 0.1 and popsize 10 (die_amd.search.CMAES), the same chain of launches.
 
     python examples/learning_agents.py [--searcher pgpe|cmaes] [--dynamics st-perlin-wide] [--size 96] [--generations 100]
-                                       [--epoch-iters 30] [--out saved_models/agent.pt] [--time]
+                                       [--epoch-iters 30] [--agents-die] [--out saved_models/agent.pt] [--time]
 
 Deliberate differences from the reference: every generation starts the R worlds from the same seeded state (the
 reference's run_epoch keeps stepping one env from candidate to candidate), no MLflow, and the noise is Philox's, so runs are
@@ -35,10 +35,10 @@ CMAES_KW = dict(stdev_init=0.1, separable=True)        # the reference's comment
 SEARCHERS = ('pgpe', 'cmaes')
 
 
-def make_search(size, choice, popsize, epoch_iters, seed, searcher='pgpe'):
+def make_search(size, choice, popsize, epoch_iters, seed, searcher='pgpe', agents_die=False):
     torch.manual_seed(seed)
     template = NeuralAutomataAgent(**AGENT_KW)
-    benv = BatchedEnv((size, size), make_dynamics(choice, size), replicas=popsize, seeds=[seed] * popsize)
+    benv = BatchedEnv((size, size), make_dynamics(choice, size, agents_die), replicas=popsize, seeds=[seed] * popsize)
     pop = BatchedNeuralAutomataAgent(benv, template)
     if searcher == 'cmaes':
         search = CMAES(popsize, pop.P, seed=seed, **CMAES_KW)
@@ -47,12 +47,12 @@ def make_search(size, choice, popsize, epoch_iters, seed, searcher='pgpe'):
     return search.for_population(pop, epoch_iters), pop
 
 
-def host_generation(size, choice, template, mean, sigma, lr, iters, seed):
+def host_generation(size, choice, template, mean, sigma, lr, iters, seed, agents_die=False):
     """One generation driven from the host (population_eval.py --generations): rebuild, evaluate, read back, update."""
     R = 10
     half = torch.randn((R // 2, mean.numel()))
     noise = torch.cat([half, -half])
-    fit = evaluate_population(*make_population(size, template, mean + sigma * noise, seed, choice), iters)
+    fit = evaluate_population(*make_population(size, template, mean + sigma * noise, seed, choice, agents_die), iters)
     f = torch.tensor(fit, dtype=torch.float32)
     f = (f - f.mean()) / (f.std() + 1e-8)
     return mean + lr / (noise.shape[0] * sigma) * (noise.T @ f)
@@ -60,7 +60,7 @@ def host_generation(size, choice, template, mean, sigma, lr, iters, seed):
 
 def time_loops(args):
     G = args.generations
-    searcher, pop = make_search(args.size, args.dynamics, 10, args.epoch_iters, args.seed, args.searcher)
+    searcher, pop = make_search(args.size, args.dynamics, 10, args.epoch_iters, args.seed, args.searcher, args.agents_die)
     searcher.run(2)                                               # warm-up: first launches, allocations
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -70,11 +70,11 @@ def time_loops(args):
     template = pop.template
     mean = pop.parameters[0].cpu()
     for _ in range(2):
-        mean = host_generation(args.size, args.dynamics, template, mean, 0.1, 0.05, args.epoch_iters, args.seed)
+        mean = host_generation(args.size, args.dynamics, template, mean, 0.1, 0.05, args.epoch_iters, args.seed, args.agents_die)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(G):
-        mean = host_generation(args.size, args.dynamics, template, mean, 0.1, 0.05, args.epoch_iters, args.seed)
+        mean = host_generation(args.size, args.dynamics, template, mean, 0.1, 0.05, args.epoch_iters, args.seed, args.agents_die)
     torch.cuda.synchronize()
     t_host = time.perf_counter() - t0
     name = type(searcher).__name__ + '.run):'
@@ -94,11 +94,12 @@ def main():
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--out', default=None, help='agent file for pop_best (default: saved_models/neuralautomataagent_<searcher>_<G>x<T>.pt)')
     p.add_argument('--time', action='store_true')
+    p.add_argument('--agents-die', action='store_true', help='Dynamics(agents_die=True): starved agents die, fitness feels it')
     args = p.parse_args()
     if args.time:
         time_loops(args)
         return
-    searcher, pop = make_search(args.size, args.dynamics, args.popsize, args.epoch_iters, args.seed, args.searcher)
+    searcher, pop = make_search(args.size, args.dynamics, args.popsize, args.epoch_iters, args.seed, args.searcher, args.agents_die)
     print(f'Network has {pop.P} parameters; {args.popsize} candidates on {args.size}x{args.size} {args.dynamics}, '
           f'{args.epoch_iters} steps each', flush=True)
     t0 = time.perf_counter()
@@ -117,7 +118,7 @@ def main():
     solution.save(out)
     print(f'Saving the agent to: {out}')
     # replay pop_best in its own world (the reference replays for epoch_iters * 100 steps with a plotter; here epoch_iters)
-    env = Env((args.size, args.size), make_dynamics(args.dynamics, args.size), seed=args.seed, max_agents='alive')
+    env = Env((args.size, args.size), make_dynamics(args.dynamics, args.size, args.agents_die), seed=args.seed, max_agents='alive')
     reward = run_epoch(env, solution.to(torch.device('cuda')), args.epoch_iters)
     print(f'Final reward of the pop_best solution over {args.epoch_iters} steps: {reward:.4f}  (its generation: {st["pop_best_eval"]:.4f})')
 

@@ -2,10 +2,11 @@
 once: R NeuralAutomataAgent candidates, each scored by the sum of its rewards over `epoch_iters` steps of its own world,
 all R worlds stepped together by die_amd.batch (L + 2 launches per step for an L-layer model, L + 3 with a food flow).
 
-    python examples/population_eval.py [--replicas 10] [--size 96] [--iters 50] [--dynamics st-perlin-wide] [--generations 0] [--compare]
+    python examples/population_eval.py [--replicas 10] [--size 96] [--iters 50] [--dynamics st-perlin-wide] [--generations 0] [--agents-die] [--compare]
 
 --dynamics picks one of the reference's three worlds (learning_agents.py `dynamics_choice`): 'st-perlin', 'st-perlin-wide' or
 'dyn-pred', where the food flows in running waves (WaveSequence.get_flow_operator, one more launch per batched step).
+--agents-die adds the death pressure (Dynamics(agents_die=True): starved agents are zeroed; one more launch per batched step).
 
 --generations G runs a plain Gaussian evolution strategy (antithetic samples, normalised fitness) on the mean parameter
 vector — the training loop itself (evotorch's PGPE, MLflow) stays out of scope.  --compare times the same population one
@@ -29,18 +30,20 @@ AGENT_KW = dict(kernel_sizes=[3, 3], scale=0.01, deposit=2.0)           # learni
 DYNAMICS = ('st-perlin', 'st-perlin-wide', 'dyn-pred')
 
 
-def make_dynamics(choice, size):
-    """learning_agents.py's `dynamics_choice[choice]`, with a fresh flow operator (its time counter at 0) for 'dyn-pred'."""
+def make_dynamics(choice, size, agents_die=False):
+    """learning_agents.py's `dynamics_choice[choice]`, with a fresh flow operator (its time counter at 0) for 'dyn-pred';
+    `agents_die`: starved agents die (the reference's 'not dying' pressure)."""
     if choice == 'st-perlin':
-        return Dynamics(food_infinite=True)
+        return Dynamics(food_infinite=True, agents_die=agents_die)
     if choice == 'st-perlin-wide':
-        return Dynamics(food_infinite=True, rate_decay_chem=0.025, diffuse_sigma=.8)
-    return Dynamics(food_infinite=False, op_food_flow=WaveSequence((size, size), dt=0.01).get_flow_operator(scale=0.5, decay=0.5))
+        return Dynamics(food_infinite=True, rate_decay_chem=0.025, diffuse_sigma=.8, agents_die=agents_die)
+    return Dynamics(food_infinite=False, op_food_flow=WaveSequence((size, size), dt=0.01).get_flow_operator(scale=0.5, decay=0.5),
+                    agents_die=agents_die)
 
 
-def make_population(size, template, rows, seed, choice):
+def make_population(size, template, rows, seed, choice, agents_die=False):
     R = rows.shape[0]
-    benv = BatchedEnv((size, size), make_dynamics(choice, size), replicas=R, seeds=[seed] * R)   # every world starts alike
+    benv = BatchedEnv((size, size), make_dynamics(choice, size, agents_die), replicas=R, seeds=[seed] * R)   # every world starts alike
     return benv, BatchedNeuralAutomataAgent(benv, template, rows)
 
 
@@ -59,8 +62,8 @@ def run_epoch(env, agent, iters):
     return epoch_reward
 
 
-def one_at_a_time_worlds(size, R, seed, choice):
-    return [Env((size, size), make_dynamics(choice, size), seed=seed, max_agents='alive') for _ in range(R)]
+def one_at_a_time_worlds(size, R, seed, choice, agents_die=False):
+    return [Env((size, size), make_dynamics(choice, size, agents_die), seed=seed, max_agents='alive') for _ in range(R)]
 
 
 def main():
@@ -74,6 +77,7 @@ def main():
     p.add_argument('--lr', type=float, default=0.05)
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--compare', action='store_true')
+    p.add_argument('--agents-die', action='store_true', help='Dynamics(agents_die=True): starved agents die')
     args = p.parse_args()
     R = args.replicas
     torch.manual_seed(args.seed)
@@ -83,9 +87,10 @@ def main():
         template.model.init_weights()
         cands.append(parameters_to_vector(template.model.parameters()).detach().clone())
     rows = torch.stack(cands)
-    print(f'{R} candidates of {rows.shape[1]} parameters, {args.size}x{args.size}, {args.iters} steps each, {args.dynamics}', flush=True)
+    print(f'{R} candidates of {rows.shape[1]} parameters, {args.size}x{args.size}, {args.iters} steps each, {args.dynamics}'
+          f'{" with agents_die" if args.agents_die else ""}', flush=True)
 
-    benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics)
+    benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die)
     fitness = evaluate_population(benv, pop, args.iters)
     for r, f in enumerate(fitness):
         print(f'candidate {r:2d}: fitness {f:.6f}')
@@ -96,14 +101,14 @@ def main():
         # only the stepping is timed (the worlds are built before); warm-up of both paths first
         dev = torch.device('cuda')
         agents = [pop.candidate(r).to(dev) for r in range(R)]
-        evaluate_population(*make_population(args.size, template, rows, args.seed, args.dynamics), 2)
-        run_epoch(one_at_a_time_worlds(args.size, 1, args.seed, args.dynamics)[0], agents[0], 2)
-        benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics)
+        evaluate_population(*make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die), 2)
+        run_epoch(one_at_a_time_worlds(args.size, 1, args.seed, args.dynamics, args.agents_die)[0], agents[0], 2)
+        benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         batched = evaluate_population(benv, pop, args.iters)
         t_batch = time.perf_counter() - t0
-        worlds = one_at_a_time_worlds(args.size, R, args.seed, args.dynamics)
+        worlds = one_at_a_time_worlds(args.size, R, args.seed, args.dynamics, args.agents_die)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         alone = [run_epoch(env, ag, args.iters) for env, ag in zip(worlds, agents)]
@@ -123,7 +128,7 @@ def main():
         half = torch.randn((R // 2, mean.numel()))
         noise = torch.cat([half, -half])                                    # antithetic pairs
         samples = mean + args.sigma * noise
-        fit = evaluate_population(*make_population(args.size, template, samples, args.seed + 1 + g, args.dynamics), args.iters)
+        fit = evaluate_population(*make_population(args.size, template, samples, args.seed + 1 + g, args.dynamics, args.agents_die), args.iters)
         f = torch.tensor(fit, dtype=torch.float32)
         f = (f - f.mean()) / (f.std() + 1e-8)
         mean = mean + args.lr / (noise.shape[0] * args.sigma) * (noise.T @ f)

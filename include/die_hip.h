@@ -209,9 +209,14 @@ int die_forward_env_step(const die_medium* m, const die_agents* a, die_gradient_
 
 /* R replicas of one world shape stepped in ONE launch pair (BASELINE configs[4]: batched env replicas; small grids are
  * launch-bound one at a time).  `m`, `a`, `g`, `act` describe replica 0; every array of replica r starts r strides further
- * (planes: plane_stride elements, per-agent arrays: agent_stride elements; results[r]); replica r holds n[r] agents (all
- * alive) and draws from Philox key g->seed + r * seed_stride — so replica r computes exactly what a stand-alone world with
- * that seed computes.  `act` may be NULL (no action written).  Same restrictions as die_forward_env_step. */
+ * (planes: plane_stride elements, per-agent arrays: agent_stride elements; results[r]); replica r holds n[r] agent slots
+ * and draws from Philox key g->seed + r * seed_stride — so replica r computes exactly what a stand-alone world with
+ * that seed computes.  `act` may be NULL (no action written).  Same restrictions as die_forward_env_step, and no sense mask.
+ *   d->agents_die (or d->has_dead_slots): one more launch between the claims and the sweep — die_agent_dead_slots of every
+ * replica (dead slots finish their feed, _agent_lifecycle zeroes the starved slots, num_alive counts the alive ones), so
+ * replica r's result words are die_forward_env_step's.  The claim pass stashes each dead slot's `consumed` and action cost
+ * (its action stays in registers); the workspace must then hold die_batch_lifecycle_workspace_bytes(replicas,
+ * agent_stride) bytes (−1: bad arguments), else the call is refused before any launch.  Without dead slots nothing changes. */
 #define DIE_MAX_REPLICAS 64
 typedef struct die_batch {
     int32_t replicas;
@@ -222,6 +227,7 @@ typedef struct die_batch {
     int64_t n[DIE_MAX_REPLICAS];
 } die_batch;
 int64_t die_batch_workspace_bytes(int32_t replicas);
+int64_t die_batch_lifecycle_workspace_bytes(int32_t replicas, int64_t agent_stride);
 int die_forward_env_step_batch(const die_medium* m, const die_agents* a, die_gradient_agent* g, const die_action* act,
                                const die_dynamics* d, const die_batch* b, die_step_result* results, void* workspace,
                                int64_t workspace_bytes, void* stream);
