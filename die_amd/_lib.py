@@ -209,6 +209,9 @@ _SIGNATURES = {
                                     C.c_void_p]),
     'die_init_medium': (C.c_int, [_P(Medium), C.c_double, C.c_uint64, _P(FoodSpec), C.c_void_p]),
     'die_init_agents': (C.c_int, [_P(Medium), _P(Agents), C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'die_init_batch_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    'die_init_batch': (C.c_int, [_P(Medium), _P(Agents), _P(Batch), C.c_double, C.c_uint64, C.c_uint64, _P(FoodSpec), C.c_void_p,
+                                 C.c_void_p, C.c_int64, C.c_void_p]),
     'die_init_heading': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_uint64, C.c_void_p]),
     'die_field_fill': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_uint32,
                                  C.c_uint32, C.c_void_p]),

@@ -18,7 +18,12 @@ per step (`die_food_flow_batch`) in the small-world regime (tests/test_gpu_flow_
 
 `Dynamics(agents_die=True)` (compat='intended') runs on the replicas too: replica r is then the stand-alone Env of that
 pressure, starved slots zeroed and `num_agents` falling.  One more launch per step in the small-world regime, the dead-slot +
-lifecycle pass of every replica (tests/test_gpu_batch_lifecycle.py)."""
+lifecycle pass of every replica (tests/test_gpu_batch_lifecycle.py).
+
+`max_agents=N` (an int, or None for W·H as the reference) gives every replica N slots — its K_r seeded agents first, then a
+dead tail — so that every world fits one layout and `reset(seed=...)` can seed new worlds on the device (`die_init_batch`: five
+launches for the whole batch, no host read).  Replica r is then `Env(field_size, dynamics, seed=seeds[r], max_agents=N)`, bit
+for bit; the step runs its dead-slot pass (one more launch per step, as under agents_die) (tests/test_gpu_reseed.py)."""
 import ctypes as C
 import dataclasses
 import math
@@ -31,7 +36,7 @@ from torch.nn.utils import parameters_to_vector, vector_to_parameters
 from . import _lib
 from .agent.evo import NeuralAutomataAgent
 from .agent.gradient import join64, split64
-from .data_init import DeviceFoodFlow, device_flow_kind
+from .data_init import DeviceFoodFlow, device_flow_kind, food_spec_from_seed
 from .device_array import Q32, _ptr, stream_ptr
 from .env import BoundaryCondition, Dynamics, Env, _identity_food_flow, linear_action_cost
 
@@ -45,11 +50,14 @@ class BatchedEnv:
         have.  Each replica is then a stand-alone `Env` stepped on its OWN HIP stream (the latency-bound agent kernel of one
         replica overlaps the bandwidth-bound field kernel of another); `step` fans out and joins the streams.
     Either way replica r is the stand-alone run of seeds[r] (default seed + r), bit for bit.  `seeds=[s] * R` starts every
-    replica from the same world (how a population of candidates is compared)."""
+    replica from the same world (how a population of candidates is compared).
+
+    `max_agents`: 'alive' (default) gives replica r exactly its K_r seeded agents; an int N, or None for W·H, gives every
+    replica N slots (alive first, then dead ones) — the layout `reset(seed=...)` needs, since a new world has a new K_r."""
 
     def __init__(self, field_size: Tuple[int, int], dynamics: Optional[Dynamics] = None, *, replicas: int, seed: int = 0,
                  field_dtype: torch.dtype = torch.float32, device=None, per_replica: Optional[bool] = None,
-                 seeds: Optional[Sequence[int]] = None):
+                 seeds: Optional[Sequence[int]] = None, max_agents: Union[str, int, None] = 'alive'):
         if not 1 <= replicas <= 64:
             raise ValueError('1..64 replicas')
         if seeds is not None and len(seeds) != replicas:
@@ -64,6 +72,17 @@ class BatchedEnv:
         if d.diffuse_mode != 'wrap' or not isinstance(d.boundary, BoundaryCondition):
             raise NotImplementedError(f"batched replicas: diffuse_mode={d.diffuse_mode!r}, boundary={d.boundary!r}: only 'wrap' "
                                       'diffusion and a BoundaryCondition are batched')
+        if isinstance(max_agents, str):
+            if max_agents != 'alive':
+                raise ValueError(f"max_agents={max_agents!r}: 'alive', a number of slots or None (W·H)")
+            self._fixed = None
+        elif max_agents is None:
+            self._fixed = int(field_size[0]) * int(field_size[1])
+        else:
+            if isinstance(max_agents, bool) or int(max_agents) != max_agents or int(max_agents) < 1:
+                raise ValueError(f'max_agents={max_agents!r}: at least one slot per replica')
+            self._fixed = int(max_agents)
+        slots = 'alive' if self._fixed is None else self._fixed
         self.R, self.seed = int(replicas), int(seed)
         self.seeds = [self.seed + r for r in range(self.R)] if seeds is None else [int(q) for q in seeds]
         self.W, self.H = int(field_size[0]), int(field_size[1])
@@ -72,7 +91,7 @@ class BatchedEnv:
         self.per_replica = (self.W * self.H >= Env.PIC_MIN_CELLS) if per_replica is None else bool(per_replica)
         if self.per_replica:
             # every replica Env gets its own Dynamics: its flow operator is its own (step keeps the counters in line)
-            self.envs = [Env(field_size, dataclasses.replace(d), seed=self.seeds[r], max_agents='alive', field_dtype=field_dtype,
+            self.envs = [Env(field_size, dataclasses.replace(d), seed=self.seeds[r], max_agents=slots, field_dtype=field_dtype,
                              device=self.device, sync=False) for r in range(self.R)]
             self.n = [e.agents.N for e in self.envs]
             self.Nmax = max(self.n)
@@ -83,11 +102,11 @@ class BatchedEnv:
             self._flow_k0 = getattr(self.dynamics.op_food_flow, '_k', None)
             return
         # every replica starts as the stand-alone Env with seeds[r] would; its state is copied into slice r
-        envs = [Env(field_size, d, seed=self.seeds[r], max_agents='alive', field_dtype=field_dtype, device=self.device, sort_every=0,
+        envs = [Env(field_size, d, seed=self.seeds[r], max_agents=slots, field_dtype=field_dtype, device=self.device, sort_every=0,
                     pic=False) for r in range(self.R)]
         self.n = [e.agents.N for e in envs]
         for r, e in enumerate(envs):
-            if not e._all_alive:            # (only a world seeded with no agent at all: 'alive' keeps one dead placeholder slot)
+            if self._fixed is None and not e._all_alive:            # (only a world seeded with no agent at all: 'alive' keeps one dead placeholder slot)
                 raise NotImplementedError(f'batched replicas: replica {r} (seed {self.seeds[r]}) has no alive agent; dead slots are '
                                           'not modelled by the batched step')
         self.Nmax = max(self.n)
@@ -109,21 +128,43 @@ class BatchedEnv:
             self.x[r, :k].copy_(e.agents.x); self.y[r, :k].copy_(e.agents.y)
             self.alive[r, :k].copy_(e.agents.alive); self.agent_food[r, :k].copy_(e.agents.agent_food)
         self.epoch = 1
-        # agents_die: the claim pass stashes every dead slot's feed and action cost for the lifecycle pass
-        ws = _lib.lib.die_batch_lifecycle_workspace_bytes(R, Nm) if d.agents_die else _lib.lib.die_batch_workspace_bytes(R)
+        # dead slots (agents_die, the fixed layout): the claim pass stashes every dead slot's feed and action cost for the
+        # lifecycle pass
+        dead = d.agents_die or self._fixed is not None
+        ws = _lib.lib.die_batch_lifecycle_workspace_bytes(R, Nm) if dead else _lib.lib.die_batch_workspace_bytes(R)
         self._ws = torch.zeros(int(ws), dtype=torch.uint8, device=dev)
+        if self._fixed is not None:                 # reset(seed=...): die_init_batch's scan workspace and (K_r, overflow) words
+            self._init_ws = torch.zeros(int(_lib.lib.die_init_batch_workspace_bytes(W, H, R)), dtype=torch.uint8, device=dev)
+            self._counts = torch.zeros((R, 2), dtype=torch.int64, device=dev)
         self._steps = 0
         self._initial = (self._state.clone(), self.chem, self.chem_next)
         self._flow_k0 = getattr(self.dynamics.op_food_flow, '_k', None)
 
-    def reset(self) -> None:
+    def reset(self, *, seed: Optional[int] = None, seed_stride: int = 1) -> None:
         """Every replica back to the state it was constructed in: bit for bit a fresh BatchedEnv of the same arguments (and a
         flow operator whose counter stands where this one's stood then).  Device copies from a snapshot taken at construction,
         on the current stream (one copy in the small-world regime); nothing is rebuilt and nothing is read back (the device loop
-        of die_amd.search.PGPE)."""
+        of die_amd.search.PGPE).
+
+        `seed`: new worlds instead — replica r becomes the world of seed + r·seed_stride, bit for bit a fresh BatchedEnv of
+        those seeds (same max_agents), and `seeds` says so.  Needs the fixed layout (`max_agents` an int or None).  Small worlds:
+        one die_init_batch call on the current stream, no host read and no allocation; a world seeding more than N agents is
+        clipped as Env's agents_from_medium clips it, and the next `check()` raises.  Large worlds (per_replica): `Env.reset`
+        of every replica, which reads each count back (and raises at once on such a world)."""
+        if seed is not None:
+            if self._fixed is None:
+                raise ValueError("reset(seed=...) needs every replica to hold the same number of slots: build the BatchedEnv "
+                                 "with max_agents=N (or None for W·H) instead of 'alive'")
+            if isinstance(seed_stride, bool) or int(seed_stride) != seed_stride or int(seed_stride) < 0:
+                raise ValueError(f'seed_stride={seed_stride!r}: a non-negative integer')
+            seed, seed_stride = int(seed), int(seed_stride)
+            seeds = [seed + r * seed_stride for r in range(self.R)]
         if self._flow_k0 is not None:
             self.dynamics.op_food_flow._k = self._flow_k0
         self._steps = 0
+        if seed is not None:
+            self._reseed(seeds, seed, seed_stride)
+            return
         if self.per_replica:
             for e, snap in zip(self.envs, self._initial):
                 _env_restore(e, snap)
@@ -132,6 +173,27 @@ class BatchedEnv:
         self._state.copy_(self._initial[0])
         self.chem, self.chem_next = self._initial[1:]
         self.epoch = 1
+
+    def _reseed(self, seeds: List[int], seed: int, seed_stride: int) -> None:
+        if self.per_replica:
+            for r, (e, q) in enumerate(zip(self.envs, seeds)):
+                try:
+                    e.reset(seed=q)
+                except ValueError as err:
+                    raise ValueError(f'replica {r} (seed {q}): {err}') from err
+            self.seeds = seeds
+            self._obs = [e._get_current_obs for e in self.envs]
+            return
+        self.chem, self.chem_next = self._initial[1:]
+        self.epoch = 1
+        m, a, _, b = self._structs()
+        # Env._init_data: the Perlin food of DataInitializer.init_medium (its spec holds no seed-drawn value the kernel reads)
+        spec = food_spec_from_seed(seed, scale=0.5, perlin_octaves=8, threshold=1.0)
+        mask = 0xFFFFFFFFFFFFFFFF
+        _lib.check(_lib.lib.die_init_batch(C.byref(m), C.byref(a), C.byref(b), float(self.dynamics.init_agent_ratio), seed & mask,
+                                           seed_stride & mask, C.byref(spec), _ptr(self._counts), _ptr(self._init_ws),
+                                           self._init_ws.numel(), stream_ptr(self.device)), 'die_init_batch')
+        self.seeds = seeds
 
     # ------------------------------------------------------------------
     def _structs(self):
@@ -142,17 +204,26 @@ class BatchedEnv:
         d = self.dynamics
         boundary = _lib.DIE_BOUNDARY_WRAP if d.boundary == BoundaryCondition.wrap else _lib.DIE_BOUNDARY_LIMIT
         cost = _lib.DIE_COST_LINEAR if d.op_action_cost is linear_action_cost else _lib.DIE_COST_ZERO
-        dyn = _lib.Dynamics(d.rate_feed, d.rate_decay_chem, d.diffuse_sigma, boundary, cost, 0.02, 0.01, int(d.food_infinite), int(d.agents_die), 0, 0, 0)
+        dyn = _lib.Dynamics(d.rate_feed, d.rate_decay_chem, d.diffuse_sigma, boundary, cost, 0.02, 0.01, int(d.food_infinite), int(d.agents_die),
+                            int(self._fixed is not None), 0, 0)
         b = _lib.Batch(self.R, 0, self.W * self.H, self.Nmax, 1, (C.c_int64 * 64)(*self.n))
         return m, a, dyn, b
 
     def check(self):
         """Synchronise; raise if a replica's tile-binned step reported a bookkeeping error since the last check (per-replica
-        regime: every replica is an `Env` of its own; the one-launch-pair regime runs the classic kernels, which have no such word)."""
+        regime: every replica is an `Env` of its own; the one-launch-pair regime runs the classic kernels, which have no such word),
+        or if a `reset(seed=...)` since the last check seeded more agents than a replica has slots (the flags are cleared)."""
         torch.cuda.synchronize(self.device)
         if self.per_replica:
             for e in self.envs:
                 e.check()
+        elif self._fixed is not None:
+            over = [r for r, f in enumerate(self._counts[:, 1].tolist()) if f]
+            if over:
+                self._counts[:, 1].zero_()
+                raise ValueError('reset(seed=...) seeded more agents than max_agents=' + str(self._fixed) + ' slots in ' +
+                                 ', '.join(f'replica {r} (seed {self.seeds[r]})' for r in over) + ' — the agents were clipped; '
+                                 '(a seed of an earlier reset since the last check() may be the one)')
 
     def step(self, agent: Union['BatchedPhysarumAgent', 'BatchedNeuralAutomataAgent'],
              results: Optional[torch.Tensor] = None) -> torch.Tensor:

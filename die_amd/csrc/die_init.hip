@@ -237,6 +237,208 @@ extern "C" int die_init_heading(uint32_t* heading_hi, uint32_t* heading_lo, floa
     return DIE_OK;
 }
 
+// ---- the worlds of every replica of a die_batch (BatchedEnv.reset(seed=...)) ------------------------------------------
+// Replica r (blockIdx.y) is die_init_medium + die_init_agents of seed + r·world_stride on its own planes and agent arrays:
+// the kernels below restate k_init_medium / k_count / k_scan_blocks / k_scatter / k_zero_tail with the replica's offsets
+// (a replica's plane is a whole world: no tile offsets), so every value is computed by the same expressions.  The scan
+// workspace of replica r is its own die_ws_scan_bytes slice.
+struct InitBatchArgs {
+    int64_t cells, agents;          // strides: cells per plane, agent slots per replica
+    uint64_t world_stride;
+    int64_t ws_stride;              // bytes of scan workspace per replica
+    int64_t nb;                     // scan tiles per plane
+    int64_t n[DIE_MAX_REPLICAS];    // slots of every replica
+};
+
+template <typename T>
+__global__ __launch_bounds__(DIE_BLOCK) void k_init_medium_batch(die_geo g, uint64_t* owner, T* food, T* chem, double ratio,
+                                                                 uint64_t seed, FoodArgs fa, InitBatchArgs b) {
+    const int r = blockIdx.y;
+    const uint64_t sr = seed + (uint64_t)r * b.world_stride;
+    owner += b.cells * r; food += b.cells * r; chem += b.cells * r;
+    const int H = g.H;
+    const int64_t C = (int64_t)g.W * H;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < C; c += stride) {
+        const int ix = (int)(c / H), iy = (int)(c - (int64_t)ix * H);
+        const uint64_t gc = (uint64_t)ix * (uint64_t)g.gH + (uint64_t)iy;
+        const int q = die_round3_units(die_draw(sr, 0, gc, DIE_STREAM_INIT_AGENTS).v[0]);
+        const double u = q / 1000.0;
+        owner[c] = (q > 0 && u <= ratio) ? 1ull : 0ull;
+        die_st(food, c, init_food_value(g, fa, sr, ix, iy));
+        die_st(chem, c, 0.f);
+    }
+}
+
+__global__ __launch_bounds__(DIE_BLOCK) void k_count_batch(const uint64_t* flag, int64_t C, char* ws, InitBatchArgs b) {
+    const int r = blockIdx.y;
+    flag += b.cells * r;
+    int32_t* block_sum = (int32_t*)(ws + b.ws_stride * r);
+    const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
+    int cnt = 0;
+#pragma unroll
+    for (int i = 0; i < SCAN_ITEMS; ++i) cnt += (base + i < C && flag[base + i] != 0) ? 1 : 0;
+    __shared__ int s[DIE_BLOCK];
+    s[threadIdx.x] = cnt;
+    __syncthreads();
+    for (int o = DIE_BLOCK / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) block_sum[blockIdx.x] = s[0];
+}
+
+// one workgroup per replica: counts[2r] = min(K_r, n[r]), counts[2r + 1] |= 1 when K_r > n[r] (never cleared here)
+__global__ __launch_bounds__(DIE_BLOCK) void k_scan_blocks_batch(char* ws, int64_t* counts, InitBatchArgs b) {
+    const int r = blockIdx.y;
+    const int nb = (int)b.nb;
+    const int32_t* block_sum = (const int32_t*)(ws + b.ws_stride * r);
+    int64_t* block_off = (int64_t*)(ws + b.ws_stride * r + ((b.nb * 4 + 255) & ~(int64_t)255));
+    const int64_t capacity = b.n[r];
+    __shared__ long long s[DIE_BLOCK];
+    const int per = (nb + DIE_BLOCK - 1) / DIE_BLOCK;
+    const int lo = threadIdx.x * per, hi = min(lo + per, nb);
+    long long t = 0;
+    for (int i = lo; i < hi; ++i) t += block_sum[i];
+    s[threadIdx.x] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long run = 0;
+        for (int i = 0; i < DIE_BLOCK; ++i) { long long v = s[i]; s[i] = run; run += v; }
+        counts[2 * r] = run < capacity ? run : capacity;
+        if (run > capacity) counts[2 * r + 1] |= 1;
+    }
+    __syncthreads();
+    long long run = s[threadIdx.x];
+    for (int i = lo; i < hi; ++i) { block_off[i] = run; run += block_sum[i]; }
+}
+
+__global__ __launch_bounds__(DIE_BLOCK) void k_scatter_batch(die_geo g, uint64_t* owner, const char* ws, uint32_t* x, uint32_t* y,
+                                                             uint8_t* alive, float* agent_food, uint64_t seed, InitBatchArgs b) {
+    const int r = blockIdx.y;
+    const uint64_t sr = seed + (uint64_t)r * b.world_stride;
+    const int64_t pa = b.agents * r;
+    owner += b.cells * r;
+    x += pa; y += pa; alive += pa; agent_food += pa;
+    const int64_t* block_off = (const int64_t*)(ws + b.ws_stride * r + ((b.nb * 4 + 255) & ~(int64_t)255));
+    const int64_t N = b.n[r];
+    const int H = g.H, W = g.gW;
+    const int64_t C = (int64_t)g.W * g.H;
+    const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
+    int flags = 0, cnt = 0;
+#pragma unroll
+    for (int i = 0; i < SCAN_ITEMS; ++i)
+        if (base + i < C && owner[base + i] != 0) { flags |= 1 << i; ++cnt; }
+    __shared__ int s[DIE_BLOCK];
+    s[threadIdx.x] = cnt;
+    __syncthreads();
+    for (int o = 1; o < DIE_BLOCK; o <<= 1) {          // Hillis–Steele inclusive scan
+        int v = (int)threadIdx.x >= o ? s[threadIdx.x - o] : 0;
+        __syncthreads();
+        s[threadIdx.x] += v;
+        __syncthreads();
+    }
+    int64_t k = block_off[blockIdx.x] + (s[threadIdx.x] - cnt);
+#pragma unroll
+    for (int i = 0; i < SCAN_ITEMS; ++i) {
+        const int64_t c = base + i;
+        if (c >= C) break;
+        if (flags & (1 << i)) {
+            if (k < N) {
+                const int ix = (int)(c / H), iy = (int)(c - (int64_t)ix * H);
+                const double qx = W > 1 ? (double)ix / (double)(W - 1) * 4294967296.0 : 0.0;
+                const double qy = g.gH > 1 ? (double)iy / (double)(g.gH - 1) * 4294967296.0 : 0.0;
+                const long long X = __double2ll_rn(qx), Y = __double2ll_rn(qy);
+                x[k] = (uint32_t)(X > 0xFFFFFFFFLL ? 0xFFFFFFFFLL : X);
+                y[k] = (uint32_t)(Y > 0xFFFFFFFFLL ? 0xFFFFFFFFLL : Y);
+                alive[k] = 1;
+                const int q = die_round3_units(die_draw(sr, 0, (uint64_t)k, DIE_STREAM_INIT_AGENT_FOOD).v[0]);
+                agent_food[k] = (float)(0.9 * (q / 1000.0) + 0.1);
+                owner[c] = die_claim(1, k, 0.f);
+            } else {
+                owner[c] = 0;
+            }
+            ++k;
+        }
+    }
+}
+
+__global__ __launch_bounds__(DIE_BLOCK) void k_zero_tail_batch(const int64_t* counts, uint32_t* x, uint32_t* y, uint8_t* alive,
+                                                               float* agent_food, InitBatchArgs b) {
+    const int r = blockIdx.y;
+    const int64_t pa = b.agents * r;
+    x += pa; y += pa; alive += pa; agent_food += pa;
+    const int64_t K = counts[2 * r], N = b.n[r];
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t n = K + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += stride) {
+        x[n] = 0; y[n] = 0; alive[n] = 0; agent_food[n] = 0.f;
+    }
+}
+
+extern "C" int64_t die_init_batch_workspace_bytes(int32_t W, int32_t H, int32_t replicas) {
+    if (W < 1 || H < 1 || replicas < 1 || replicas > DIE_MAX_REPLICAS) return -1;
+    if (((int64_t)W * H + SCAN_TILE - 1) / SCAN_TILE >= (1ll << 31)) return -1;
+    return (int64_t)replicas * die_ws_scan_bytes(W, H);
+}
+
+extern "C" int die_init_batch(const die_medium* m, const die_agents* a, const die_batch* b, double agent_ratio, uint64_t seed,
+                              uint64_t world_stride, const die_food_spec* food, int64_t* counts_dev, void* ws, int64_t ws_bytes,
+                              void* stream) {
+    const char* who = "die_init_batch";
+    DIE_REQUIRE(m && a && b && food && counts_dev && ws, "%s: null argument", who);
+    DIE_REQUIRE(m->W >= 1 && m->H >= 1 && m->owner && m->food && m->chem, "%s: bad medium", who);
+    DIE_REQUIRE(m->gW <= 0, "%s: a replica's plane is a whole world, not a tile", who);
+    DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad dtype %d", who, m->dtype);
+    DIE_REQUIRE(a->N > 0 && a->x && a->y && a->alive && a->agent_food, "%s: bad agents", who);
+    DIE_REQUIRE(b->replicas >= 1 && b->replicas <= DIE_MAX_REPLICAS, "%s: %d replicas, 1..%d expected", who, b->replicas, DIE_MAX_REPLICAS);
+    DIE_REQUIRE(b->plane_stride >= (int64_t)m->W * m->H && b->agent_stride >= a->N, "%s: strides smaller than a replica", who);
+    DIE_REQUIRE(b->agent_stride <= (int64_t)DIE_OWNER_SLOT_MASK - 1, "%s: agent stride %lld too large for the ownership word", who,
+                (long long)b->agent_stride);
+    for (int r = 0; r < b->replicas; ++r)
+        DIE_REQUIRE(b->n[r] >= 1 && b->n[r] <= b->agent_stride, "%s: replica %d has %lld slots, 1..%lld expected", who, r,
+                    (long long)b->n[r], (long long)b->agent_stride);
+    DIE_REQUIRE(food->n_waves >= 0 && food->n_waves <= 8, "%s: n_waves %d outside 0..8", who, food->n_waves);
+    DIE_REQUIRE(food->perlin_octaves >= 0 && food->perlin_octaves < (1 << 19), "%s: bad perlin_octaves %d", who, food->perlin_octaves);
+    // the sinusoid mix is drawn from the seed on the host: one spec is the food of one seed only
+    DIE_REQUIRE(food->perlin_octaves > 0 || world_stride == 0, "%s: a wave-mix food spec (perlin_octaves 0) with world_stride %llu: "
+                "its waves belong to one seed", who, (unsigned long long)world_stride);
+    const int64_t need = die_init_batch_workspace_bytes(m->W, m->H, b->replicas);
+    DIE_REQUIRE(need > 0, "%s: field too large", who);
+    DIE_REQUIRE(ws_bytes >= need, "%s: workspace too small (%lld < %lld: die_init_batch_workspace_bytes)", who, (long long)ws_bytes,
+                (long long)need);
+    FoodArgs fa;
+    fa.n_waves = food->n_waves;
+    fa.scale = food->scale;
+    fa.perlin_octaves = food->perlin_octaves;
+    fa.threshold = food->threshold;
+    for (int i = 0; i < 8; ++i) { fa.fx[i] = food->fx[i]; fa.fy[i] = food->fy[i]; fa.phase[i] = food->phase[i]; fa.amp[i] = food->amp[i]; }
+    const int64_t C = (int64_t)m->W * m->H;
+    InitBatchArgs ib;
+    ib.cells = b->plane_stride; ib.agents = b->agent_stride; ib.world_stride = world_stride;
+    ib.ws_stride = die_ws_scan_bytes(m->W, m->H);
+    ib.nb = (C + SCAN_TILE - 1) / SCAN_TILE;
+    int64_t nmax = 0;
+    for (int r = 0; r < DIE_MAX_REPLICAS; ++r) {
+        ib.n[r] = r < b->replicas ? b->n[r] : 0;
+        nmax = ib.n[r] > nmax ? ib.n[r] : nmax;
+    }
+    const die_geo g = die_geo_of(m);
+    const hipStream_t s = (hipStream_t)stream;
+    const int R = b->replicas;
+    char* w = (char*)ws;
+    const dim3 cells(init_grid(C), R), tiles((unsigned)ib.nb, R), slots(init_grid(nmax), R);
+    if (m->dtype == DIE_F32)
+        k_init_medium_batch<float><<<cells, DIE_BLOCK, 0, s>>>(g, m->owner, (float*)m->food, (float*)m->chem, agent_ratio, seed, fa, ib);
+    else
+        k_init_medium_batch<__half><<<cells, DIE_BLOCK, 0, s>>>(g, m->owner, (__half*)m->food, (__half*)m->chem, agent_ratio, seed, fa, ib);
+    k_count_batch<<<tiles, DIE_BLOCK, 0, s>>>(m->owner, C, w, ib);
+    k_scan_blocks_batch<<<dim3(1, R), DIE_BLOCK, 0, s>>>(w, counts_dev, ib);
+    k_scatter_batch<<<tiles, DIE_BLOCK, 0, s>>>(g, m->owner, w, a->x, a->y, a->alive, a->agent_food, seed, ib);
+    k_zero_tail_batch<<<slots, DIE_BLOCK, 0, s>>>(counts_dev, a->x, a->y, a->alive, a->agent_food, ib);
+    DIE_CHECK_LAUNCH(who);
+    return DIE_OK;
+}
+
 // ---- food flow: WaveSequence.get_flow_operator (core/data_init.py:29-38,71-89) --------------------------------
 // food ← scale·z(x, y, t) + (1 − decay)·food with the reference's running-wave field z; x varies along the last
 // axis and y along the first (core/utils.py:113-118 builds the grid from the reversed sizes).  float64 arithmetic,

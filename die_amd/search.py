@@ -75,9 +75,14 @@ class _PopulationSearch:
             self._s.history, self._s.history_rows = _ptr(h), h.shape[0]
 
     # ------------------------------------------------------------------ a population of NeuralAutomataAgents
-    def for_population(self, pop, epoch_iters: int, env=None):
+    def for_population(self, pop, epoch_iters: int, env=None, *, reseed: Optional[int] = None, reseed_stride: int = 0):
         """Bind to a BatchedNeuralAutomataAgent: `step()` is then ask into `pop.parameters`, `pop.env.reset()`, `epoch_iters`
-        batched steps, tell.  `env`, when given, must be the population's own BatchedEnv."""
+        batched steps, tell.  `env`, when given, must be the population's own BatchedEnv.
+
+        `reseed`: a new world every generation instead of the construction worlds — generation g (`iter` at ask) resets with
+        `pop.env.reset(seed=reseed + g·R, seed_stride=reseed_stride)`.  Stride 0 (default): every candidate of a generation is
+        evaluated on the same fresh world (what antithetic pairs and ranks compare); stride 1: a world per replica and
+        generation.  The population's BatchedEnv needs the fixed layout (`max_agents` an int or None)."""
         from .batch import BatchedNeuralAutomataAgent
         if not isinstance(pop, BatchedNeuralAutomataAgent):
             raise TypeError('pop: a BatchedNeuralAutomataAgent')
@@ -91,6 +96,15 @@ class _PopulationSearch:
             raise ValueError(f'population on {pop.parameters.device}, searcher on {self.device}')
         if int(epoch_iters) < 1:
             raise ValueError('epoch_iters: at least 1')
+        if reseed is not None:
+            if isinstance(reseed, bool) or not isinstance(reseed, int):
+                raise ValueError(f'reseed={reseed!r}: an integer seed, or None for the construction worlds')
+            if isinstance(reseed_stride, bool) or not isinstance(reseed_stride, int) or reseed_stride < 0:
+                raise ValueError(f'reseed_stride={reseed_stride!r}: a non-negative integer')
+            if pop.env._fixed is None:
+                raise ValueError("reseed needs a BatchedEnv with max_agents=N (or None for W·H): the 'alive' layout holds K_r slots "
+                                 'per replica, and a new world has a new K_r')
+        self._reseed, self._reseed_stride = reseed, int(reseed_stride)
         self._pop, self._epoch_iters = pop, int(epoch_iters)
         self._results = torch.empty((self._epoch_iters, self.R, 2), dtype=torch.float64, device=self.device)
         return self
@@ -100,8 +114,12 @@ class _PopulationSearch:
         if self._pop is None:
             raise RuntimeError('step(): bind a population first (for_population)')
         pop, env = self._pop, self._pop.env
+        g = self.iter
         self.ask(pop.parameters)
-        env.reset()
+        if self._reseed is None:
+            env.reset()
+        else:
+            env.reset(seed=self._reseed + g * self.R, seed_stride=self._reseed_stride)
         for t in range(self._epoch_iters):
             env.step(pop, self._results[t])
         self.tell(self._results)

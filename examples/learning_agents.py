@@ -6,13 +6,20 @@ steps, update (die_amd.search.PGPE).  `--searcher cmaes` trains with the referen
 separable CMA-ES with stdev_init 0.1 and popsize 10 (die_amd.search.CMAES), the same chain of launches.
 
     python examples/learning_agents.py [--searcher pgpe|cmaes] [--dynamics st-perlin-wide] [--size 96] [--generations 100]
-                                       [--epoch-iters 30] [--agents-die] [--out saved_models/agent.pt] [--time]
+                                       [--epoch-iters 30] [--agents-die] [--max-agents alive|full|tight|N]
+                                       [--reseed S] [--reseed-stride 0] [--out saved_models/agent.pt] [--time]
 
-Deliberate differences from the reference: every generation starts the R worlds from the same seeded state (the
-reference's run_epoch keeps stepping one env from candidate to candidate), no MLflow, and the noise is Philox's, so runs are
-reproducible here and not bit-equal to evotorch's.  --time runs G generations of this loop against the same population driven
-from the host (a fresh BatchedEnv per generation, host noise, fitness read back, plain Gaussian ES on the host: what
-examples/population_eval.py --generations does) and prints generations/s for both.
+--reseed S gives every generation a new world: generation g resets the batch to the world of seed S + g·popsize, seeded on the
+device (BatchedEnv.reset(seed=...), five launches, no host read); with --reseed-stride 0 (default) every candidate of a
+generation shares that world, with 1 each gets its own.  It needs a fixed slot layout (--max-agents; 'tight' when not given).
+
+Deliberate differences from the reference: without --reseed every generation starts the R worlds from the same
+seeded state, and with it from a new one each generation, where the reference's run_epoch keeps stepping one env from candidate
+to candidate, so that its candidates see the states their predecessors left; no MLflow; and the noise is Philox's, so runs are
+reproducible here and not bit-equal to evotorch's.  --time runs G generations of this loop — on the 'alive' layout, on the
+fixed layout, and on the fixed layout reseeding every generation — against the same population driven from the host (a fresh
+BatchedEnv per generation, host noise, fitness read back, plain Gaussian ES on the host: what examples/population_eval.py
+--generations does) and prints generations/s for each.
 """
 import argparse
 import os
@@ -25,7 +32,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from die_amd import CMAES, PGPE, Env, NeuralAutomataAgent            # noqa: E402
 from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent    # noqa: E402
-from population_eval import AGENT_KW, DYNAMICS, evaluate_population, make_dynamics, make_population, run_epoch   # noqa: E402
+from population_eval import AGENT_KW, DYNAMICS, evaluate_population, make_dynamics, make_population, run_epoch, slots   # noqa: E402
 
 RADIUS_INIT = 1.5
 MAX_SPEED = RADIUS_INIT / 15.              # the reference's rule of thumb
@@ -35,16 +42,18 @@ CMAES_KW = dict(stdev_init=0.1, separable=True)        # the reference's comment
 SEARCHERS = ('pgpe', 'cmaes')
 
 
-def make_search(size, choice, popsize, epoch_iters, seed, searcher='pgpe', agents_die=False):
+def make_search(size, choice, popsize, epoch_iters, seed, searcher='pgpe', agents_die=False, max_agents='alive', reseed=None,
+                reseed_stride=0):
     torch.manual_seed(seed)
     template = NeuralAutomataAgent(**AGENT_KW)
-    benv = BatchedEnv((size, size), make_dynamics(choice, size, agents_die), replicas=popsize, seeds=[seed] * popsize)
+    benv = BatchedEnv((size, size), make_dynamics(choice, size, agents_die), replicas=popsize, seeds=[seed] * popsize,
+                      max_agents=max_agents)
     pop = BatchedNeuralAutomataAgent(benv, template)
     if searcher == 'cmaes':
         search = CMAES(popsize, pop.P, seed=seed, **CMAES_KW)
     else:
         search = PGPE(popsize, pop.P, seed=seed, **SEARCH_KW)
-    return search.for_population(pop, epoch_iters), pop
+    return search.for_population(pop, epoch_iters, reseed=reseed, reseed_stride=reseed_stride), pop
 
 
 def host_generation(size, choice, template, mean, sigma, lr, iters, seed, agents_die=False):
@@ -58,15 +67,27 @@ def host_generation(size, choice, template, mean, sigma, lr, iters, seed, agents
     return mean + lr / (noise.shape[0] * sigma) * (noise.T @ f)
 
 
-def time_loops(args):
-    G = args.generations
-    searcher, pop = make_search(args.size, args.dynamics, 10, args.epoch_iters, args.seed, args.searcher, args.agents_die)
+def time_device_loop(args, G, max_agents, reseed):
+    searcher, pop = make_search(args.size, args.dynamics, 10, args.epoch_iters, args.seed, args.searcher, args.agents_die, max_agents,
+                                reseed, args.reseed_stride)
     searcher.run(2)                                               # warm-up: first launches, allocations
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     searcher.run(G)
     torch.cuda.synchronize()
-    t_dev = time.perf_counter() - t0
+    dt = time.perf_counter() - t0
+    if reseed is not None:
+        pop.env.check()                                           # no world seeded more agents than the slots hold
+    return searcher, pop, dt
+
+
+def time_loops(args, N):
+    G = args.generations
+    fixed = N if N != 'alive' else slots('tight', args.size, args.dynamics, args.agents_die)
+    reseed = args.reseed if args.reseed is not None else args.seed + 1
+    searcher, pop, t_dev = time_device_loop(args, G, 'alive', None)
+    _, _, t_fixed = time_device_loop(args, G, fixed, None)
+    _, _, t_reseed = time_device_loop(args, G, fixed, reseed)
     template = pop.template
     mean = pop.parameters[0].cpu()
     for _ in range(2):
@@ -78,7 +99,10 @@ def time_loops(args):
     torch.cuda.synchronize()
     t_host = time.perf_counter() - t0
     name = type(searcher).__name__ + '.run):'
-    print(f'device loop ({name:15s}{G / t_dev:9.1f} generations/s  ({t_dev / G * 1e3:.3f} ms per generation)')
+    print(f'device loop ({name:15s}{G / t_dev:9.1f} generations/s  ({t_dev / G * 1e3:.3f} ms per generation)  max_agents=alive')
+    print(f'  fixed slots:             {G / t_fixed:9.1f} generations/s  ({t_fixed / G * 1e3:.3f} ms per generation)  max_agents={fixed}')
+    print(f'  fixed slots, reseeding:  {G / t_reseed:9.1f} generations/s  ({t_reseed / G * 1e3:.3f} ms per generation)  '
+          f'max_agents={fixed}, reseed stride {args.reseed_stride}')
     print(f'host-driven loop (rebuild): {G / t_host:9.1f} generations/s  ({t_host / G * 1e3:.3f} ms per generation)')
     print(f'speed-up: {t_host / t_dev:.2f}x  ({G} generations of 10 x {args.size}^2, {args.epoch_iters} steps, {args.dynamics})', flush=True)
 
@@ -95,17 +119,27 @@ def main():
     p.add_argument('--out', default=None, help='agent file for pop_best (default: saved_models/neuralautomataagent_<searcher>_<G>x<T>.pt)')
     p.add_argument('--time', action='store_true')
     p.add_argument('--agents-die', action='store_true', help='Dynamics(agents_die=True): starved agents die, fitness feels it')
+    p.add_argument('--max-agents', default=None, help="slots per replica: 'alive' (default without --reseed), 'full' (W·H), "
+                                                      "'tight' (default with --reseed) or a number")
+    p.add_argument('--reseed', type=int, default=None, help='a new world every generation: seed S + g·popsize (device-seeded)')
+    p.add_argument('--reseed-stride', type=int, default=0, help='0: one world per generation; 1: one per candidate and generation')
     args = p.parse_args()
+    N = slots(args.max_agents or ('tight' if args.reseed is not None else 'alive'), args.size, args.dynamics, args.agents_die)
+    if args.reseed is not None and N == 'alive':
+        sys.exit("--reseed needs a fixed slot layout: --max-agents full, tight or a number")
     if args.time:
-        time_loops(args)
+        time_loops(args, N)
         return
-    searcher, pop = make_search(args.size, args.dynamics, args.popsize, args.epoch_iters, args.seed, args.searcher, args.agents_die)
+    searcher, pop = make_search(args.size, args.dynamics, args.popsize, args.epoch_iters, args.seed, args.searcher, args.agents_die, N,
+                                args.reseed, args.reseed_stride)
     print(f'Network has {pop.P} parameters; {args.popsize} candidates on {args.size}x{args.size} {args.dynamics}, '
-          f'{args.epoch_iters} steps each', flush=True)
+          f'{args.epoch_iters} steps each, max_agents={N}' + ('' if args.reseed is None else
+          f', a new world every generation (seed {args.reseed} + g·{args.popsize}, stride {args.reseed_stride})'), flush=True)
     t0 = time.perf_counter()
     searcher.run(args.generations)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    pop.env.check()
     col = '|grad|' if args.searcher == 'pgpe' else 'sigma'
     for g, (mean, best, worst, median, col4, sd) in enumerate(searcher.history().tolist()):
         print(f'generation {g:4d}: mean {mean:10.4f}  median {median:10.4f}  best {best:10.4f}  worst {worst:10.4f}  '

@@ -2,11 +2,16 @@
 once: R NeuralAutomataAgent candidates, each scored by the sum of its rewards over `epoch_iters` steps of its own world,
 all R worlds stepped together by die_amd.batch (L + 2 launches per step for an L-layer model, L + 3 with a food flow).
 
-    python examples/population_eval.py [--replicas 10] [--size 96] [--iters 50] [--dynamics st-perlin-wide] [--generations 0] [--agents-die] [--compare]
+    python examples/population_eval.py [--replicas 10] [--size 96] [--iters 50] [--dynamics st-perlin-wide] [--generations 0] [--agents-die]
+                                       [--max-agents alive|full|tight|N] [--reseed S] [--compare]
 
 --dynamics picks one of the reference's three worlds (learning_agents.py `dynamics_choice`): 'st-perlin', 'st-perlin-wide' or
 'dyn-pred', where the food flows in running waves (WaveSequence.get_flow_operator, one more launch per batched step).
 --agents-die adds the death pressure (Dynamics(agents_die=True): starved agents are zeroed; one more launch per batched step).
+--max-agents picks the replicas' slot layout: 'alive' (K_r slots, the seeded agents), 'full' (W·H, the reference's default),
+'tight' (the expected count plus six standard deviations) or a number; every layout but 'alive' runs the dead-slot pass.
+--reseed S (with --generations, a fixed layout): generation g evaluates on the world of seed S + g, seeded on the device by
+BatchedEnv.reset(seed=...) in the one batch built up front, instead of a batch rebuilt on the host.
 
 --generations G runs a plain Gaussian evolution strategy (antithetic samples, normalised fitness) on the mean parameter
 vector — the training loop itself (evotorch's PGPE, MLflow) stays out of scope.  --compare times the same population one
@@ -14,6 +19,7 @@ candidate at a time through `Env` + `NeuralAutomataAgent` (what a direct port of
 operator of its own), checks that both give the same fitness, and prints candidate-steps/s for both.
 """
 import argparse
+import math
 import os
 import sys
 import time
@@ -41,9 +47,23 @@ def make_dynamics(choice, size, agents_die=False):
                     agents_die=agents_die)
 
 
-def make_population(size, template, rows, seed, choice, agents_die=False):
+def slots(spec, size, choice, agents_die=False):
+    """BatchedEnv max_agents of a --max-agents value: 'alive', 'full' (None: W·H), 'tight' or a number.  'tight' is the expected
+    number of seeded agents plus six standard deviations, a bound every seed of the example's worlds stays under."""
+    if spec == 'alive':
+        return 'alive'
+    if spec == 'full':
+        return None
+    if spec == 'tight':
+        p, cells = make_dynamics(choice, size, agents_die).init_agent_ratio, size * size
+        return math.ceil(p * cells + 6.0 * math.sqrt(p * (1.0 - p) * cells))
+    return int(spec)
+
+
+def make_population(size, template, rows, seed, choice, agents_die=False, max_agents='alive'):
     R = rows.shape[0]
-    benv = BatchedEnv((size, size), make_dynamics(choice, size, agents_die), replicas=R, seeds=[seed] * R)   # every world starts alike
+    benv = BatchedEnv((size, size), make_dynamics(choice, size, agents_die), replicas=R, seeds=[seed] * R,   # every world starts alike
+                      max_agents=max_agents)
     return benv, BatchedNeuralAutomataAgent(benv, template, rows)
 
 
@@ -62,8 +82,8 @@ def run_epoch(env, agent, iters):
     return epoch_reward
 
 
-def one_at_a_time_worlds(size, R, seed, choice, agents_die=False):
-    return [Env((size, size), make_dynamics(choice, size, agents_die), seed=seed, max_agents='alive') for _ in range(R)]
+def one_at_a_time_worlds(size, R, seed, choice, agents_die=False, max_agents='alive'):
+    return [Env((size, size), make_dynamics(choice, size, agents_die), seed=seed, max_agents=max_agents) for _ in range(R)]
 
 
 def main():
@@ -78,8 +98,13 @@ def main():
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--compare', action='store_true')
     p.add_argument('--agents-die', action='store_true', help='Dynamics(agents_die=True): starved agents die')
+    p.add_argument('--max-agents', default='alive', help="slots per replica: 'alive', 'full' (W·H), 'tight' or a number")
+    p.add_argument('--reseed', type=int, default=None, help='--generations on the device-seeded world of seed S + g (fixed layout)')
     args = p.parse_args()
     R = args.replicas
+    N = slots(args.max_agents, args.size, args.dynamics, args.agents_die)
+    if args.reseed is not None and N == 'alive':
+        sys.exit("--reseed needs a fixed slot layout: --max-agents full, tight or a number")
     torch.manual_seed(args.seed)
     template = NeuralAutomataAgent(**AGENT_KW)
     cands = []
@@ -88,9 +113,9 @@ def main():
         cands.append(parameters_to_vector(template.model.parameters()).detach().clone())
     rows = torch.stack(cands)
     print(f'{R} candidates of {rows.shape[1]} parameters, {args.size}x{args.size}, {args.iters} steps each, {args.dynamics}'
-          f'{" with agents_die" if args.agents_die else ""}', flush=True)
+          f'{" with agents_die" if args.agents_die else ""}, max_agents={N}', flush=True)
 
-    benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die)
+    benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die, N)
     fitness = evaluate_population(benv, pop, args.iters)
     for r, f in enumerate(fitness):
         print(f'candidate {r:2d}: fitness {f:.6f}')
@@ -101,14 +126,14 @@ def main():
         # only the stepping is timed (the worlds are built before); warm-up of both paths first
         dev = torch.device('cuda')
         agents = [pop.candidate(r).to(dev) for r in range(R)]
-        evaluate_population(*make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die), 2)
-        run_epoch(one_at_a_time_worlds(args.size, 1, args.seed, args.dynamics, args.agents_die)[0], agents[0], 2)
-        benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die)
+        evaluate_population(*make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die, N), 2)
+        run_epoch(one_at_a_time_worlds(args.size, 1, args.seed, args.dynamics, args.agents_die, N)[0], agents[0], 2)
+        benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die, N)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         batched = evaluate_population(benv, pop, args.iters)
         t_batch = time.perf_counter() - t0
-        worlds = one_at_a_time_worlds(args.size, R, args.seed, args.dynamics, args.agents_die)
+        worlds = one_at_a_time_worlds(args.size, R, args.seed, args.dynamics, args.agents_die, N)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         alone = [run_epoch(env, ag, args.iters) for env, ag in zip(worlds, agents)]
@@ -128,7 +153,13 @@ def main():
         half = torch.randn((R // 2, mean.numel()))
         noise = torch.cat([half, -half])                                    # antithetic pairs
         samples = mean + args.sigma * noise
-        fit = evaluate_population(*make_population(args.size, template, samples, args.seed + 1 + g, args.dynamics, args.agents_die), args.iters)
+        if args.reseed is not None:                                         # the one batch, a new world seeded on the device
+            pop.set_parameters(samples)
+            benv.reset(seed=args.reseed + g, seed_stride=0)
+            fit = evaluate_population(benv, pop, args.iters)
+        else:
+            fit = evaluate_population(*make_population(args.size, template, samples, args.seed + 1 + g, args.dynamics, args.agents_die, N),
+                                      args.iters)
         f = torch.tensor(fit, dtype=torch.float32)
         f = (f - f.mean()) / (f.std() + 1e-8)
         mean = mean + args.lr / (noise.shape[0] * args.sigma) * (noise.T @ f)

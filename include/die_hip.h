@@ -321,6 +321,19 @@ int die_init_medium(const die_medium* m, double agent_ratio, uint64_t seed, cons
  * (K clipped, flag in num_alive_dev[1]) when K > a->N. */
 int die_init_agents(const die_medium* m, const die_agents* a, uint64_t seed, int64_t* num_alive_dev,
                     void* workspace, int64_t workspace_bytes, void* stream);
+/* The worlds of every replica of a die_batch at once (BatchedEnv.reset(seed=...)): replica r ends exactly as
+ * die_init_medium(m_r, agent_ratio, seed + r * world_stride, food) followed by die_init_agents(m_r, a_r of b->n[r] slots, same
+ * seed) would leave it — owner at epoch 1, food, the current chem plane (m->chem), x / y / alive / agent_food with the tail
+ * zeroed.  `m` and `a` describe replica 0 (a whole world: gW <= 0); replica r starts b->plane_stride / b->agent_stride
+ * elements further.  counts_dev[2r] receives min(K_r, n[r]) (the slots filled); counts_dev[2r + 1] gets 1 OR-ed in when K_r >
+ * n[r] (the agents are then clipped as die_init_agents clips them) and is never cleared here.  Five launches whatever the
+ * number of replicas, no allocation, no synchronisation (capturable).  A wave-mix spec (perlin_octaves == 0) is drawn from
+ * one seed on the host, so it is refused with world_stride != 0.  The workspace must hold
+ * die_init_batch_workspace_bytes(W, H, replicas) bytes (-1: bad sizes). */
+int64_t die_init_batch_workspace_bytes(int32_t W, int32_t H, int32_t replicas);
+int die_init_batch(const die_medium* m, const die_agents* a, const die_batch* b, double agent_ratio, uint64_t seed,
+                   uint64_t world_stride, const die_food_spec* food, int64_t* counts_dev, void* workspace, int64_t workspace_bytes,
+                   void* stream);
 /* GradientAgent/PhysarumAgent.__init__ state (:42-43,163): heading from N(0,.4) noise,
  * discretised to the turn lattice when turn_radians > 0; stored as the float64 of its fp32 rounding. */
 int die_init_heading(uint32_t* heading_hi, uint32_t* heading_lo, float* prev_gx, float* prev_gy, int64_t N, double turn_radians,
