@@ -11,8 +11,11 @@ from .base_types import DataChannels
 from .data_init import DataInitializer, FieldSequence, PerlinNoiseSequence, WaveSequence
 from .device_array import DeviceAction, DeviceAgents, DeviceMedium
 from .env import BoundaryCondition, Dynamics, Env, linear_action_cost, zero_cost
+from .batch import (BatchedEnv, BatchedNeuralAutomataAgent, BatchedPhysarumAgent, BatchedPhysarumPopulation,
+                    ParameterSpace)
 from .search import CMAES, PGPE
 
 __all__ = ['WaveSequence', 'PerlinNoiseSequence', 'FieldSequence', 'Env', 'Dynamics', 'BoundaryCondition', 'linear_action_cost', 'zero_cost', 'Agent', 'PhysarumAgent',
            'GradientAgent', 'BrownianAgent', 'ConstAgent', 'NeuralAutomataAgent', 'ConvolutionModel', 'DataInitializer', 'DataChannels', 'DeviceMedium',
-           'DeviceAgents', 'DeviceAction', 'PGPE', 'CMAES']
+           'DeviceAgents', 'DeviceAction', 'PGPE', 'CMAES', 'BatchedEnv', 'BatchedPhysarumAgent',
+           'BatchedNeuralAutomataAgent', 'BatchedPhysarumPopulation', 'ParameterSpace']

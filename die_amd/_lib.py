@@ -96,6 +96,20 @@ class Batch(C.Structure):
                 ('seed_stride', C.c_uint64), ('n', C.c_int64 * 64)]
 
 
+PHYSARUM_PARAMS = 6
+DIE_PHYSARUM_NATURAL, DIE_PHYSARUM_UNIT = 0, 1
+
+
+class PhysarumRow(C.Structure):      # die_physarum_row: one kernel-ready row of a PhysarumAgent population's table
+    _fields_ = [('scale', C.c_float), ('deposit', C.c_float), ('sense_offset', C.c_float), ('c_turn', C.c_float),
+                ('c_sense', C.c_float), ('reserved', C.c_float), ('turn_radians', C.c_double), ('sense_radians', C.c_double),
+                ('turn_tolerance', C.c_double), ('x_turn', C.c_double), ('atol', C.c_double)]
+
+
+class ParameterSpace(C.Structure):   # die_parameter_space
+    _fields_ = [('lo', C.c_float * PHYSARUM_PARAMS), ('hi', C.c_float * PHYSARUM_PARAMS)]
+
+
 NCA_MAX_LAYERS = 8
 
 
@@ -172,6 +186,10 @@ _SIGNATURES = {
     'die_batch_lifecycle_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int64]),
     'die_forward_env_step_batch': (C.c_int, [_P(Medium), _P(Agents), _P(GradientAgent), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
                                              C.c_void_p, C.c_int64, C.c_void_p]),
+    'die_physarum_decode_batch': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(ParameterSpace), C.c_void_p, C.c_void_p, C.c_void_p]),
+    'die_physarum_heading_batch': (C.c_int, [C.c_void_p, C.c_void_p, _P(Batch), C.c_void_p, C.c_uint64, C.c_void_p]),
+    'die_physarum_env_step_batch': (C.c_int, [_P(Medium), _P(Agents), _P(GradientAgent), C.c_void_p, _P(Action), _P(Dynamics), _P(Batch),
+                                              C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'die_nca_batch_scratch_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'die_nca_env_step_batch': (C.c_int, [_P(Medium), _P(Agents), _P(NcaBatch), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
                                          C.c_void_p, C.c_int64, C.c_void_p]),

@@ -23,7 +23,12 @@ lifecycle pass of every replica (tests/test_gpu_batch_lifecycle.py).
 `max_agents=N` (an int, or None for W·H as the reference) gives every replica N slots — its K_r seeded agents first, then a
 dead tail — so that every world fits one layout and `reset(seed=...)` can seed new worlds on the device (`die_init_batch`: five
 launches for the whole batch, no host read).  Replica r is then `Env(field_size, dynamics, seed=seeds[r], max_agents=N)`, bit
-for bit; the step runs its dead-slot pass (one more launch per step, as under agents_die) (tests/test_gpu_reseed.py)."""
+for bit; the step runs its dead-slot pass (one more launch per step, as under agents_die) (tests/test_gpu_reseed.py).
+
+`BatchedPhysarumPopulation` is a population of PhysarumAgent candidates whose six constructor arguments differ per replica
+(a parameter sweep, or the candidates of a search): replica r is `Env(field_size, dynamics, seed=seeds[r])` driven by
+`PhysarumAgent(max_agents=K_r, seed=seed + r, **row r)` — the same launch pair per step (`die_physarum_env_step_batch`), each
+workgroup fetching its replica's row of a device table, bit for bit the stand-alone runs (tests/test_gpu_physarum_pop.py)."""
 import ctypes as C
 import dataclasses
 import math
@@ -225,13 +230,15 @@ class BatchedEnv:
                                  ', '.join(f'replica {r} (seed {self.seeds[r]})' for r in over) + ' — the agents were clipped; '
                                  '(a seed of an earlier reset since the last check() may be the one)')
 
-    def step(self, agent: Union['BatchedPhysarumAgent', 'BatchedNeuralAutomataAgent'],
+    def step(self, agent: Union['BatchedPhysarumAgent', 'BatchedPhysarumPopulation', 'BatchedNeuralAutomataAgent'],
              results: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One step of every replica: `agent.forward` + `Env.step` fused, two launches for the whole batch (L + 2 for a
         BatchedNeuralAutomataAgent of L layers; one more with agents_die).  Returns the (R, 2) float64 tensor of die_step_result words (device;
         `read_results` decodes)."""
         if isinstance(agent, BatchedNeuralAutomataAgent):
             return self._step_nca(agent, results)
+        if isinstance(agent, BatchedPhysarumPopulation):
+            return self._step_physarum_population(agent, results)
         flow = self._flow_kind()                    # refused before anything is launched
         if results is None:
             results = torch.empty((self.R, 2), dtype=torch.float64, device=self.device)
@@ -247,6 +254,31 @@ class BatchedEnv:
                                                        _ptr(self._ws), self._ws.numel(), stream_ptr(self.device)),
                    'die_forward_env_step_batch')
         agent._calls += 1
+        self.chem, self.chem_next = self.chem_next, self.chem
+        self._food_flow(flow, m, b)
+        self._steps += 1
+        return results
+
+    def _step_physarum_population(self, pop: 'BatchedPhysarumPopulation', results: Optional[torch.Tensor]) -> torch.Tensor:
+        """`step` for a BatchedPhysarumPopulation: the same sequence with the population's table (two launches; one more
+        with dead slots, one more with a flow; a decode launch first when `parameters` was written since the last one)."""
+        pop._check_step(self)                       # every refusal before anything is launched
+        flow = self._flow_kind()
+        if results is None:
+            results = torch.empty((self.R, 2), dtype=torch.float64, device=self.device)
+        if self.per_replica:
+            return self._step_per_replica(pop, lambda r: pop.agents[r], flow, results)
+        pop._sync()
+        self.epoch += 1
+        if self.epoch > _lib.OWNER_EPOCH_MAX:
+            self.owner.zero_()
+            self.epoch = 1
+        m, a, dyn, b = self._structs()
+        g = pop._struct()
+        _lib.check(_lib.lib.die_physarum_env_step_batch(C.byref(m), C.byref(a), C.byref(g), _ptr(pop._table), None, C.byref(dyn), C.byref(b),
+                                                        _ptr(results), _ptr(self._ws), self._ws.numel(), stream_ptr(self.device)),
+                   'die_physarum_env_step_batch')
+        pop._calls += 1
         self.chem, self.chem_next = self.chem_next, self.chem
         self._food_flow(flow, m, b)
         self._steps += 1
@@ -320,7 +352,7 @@ class BatchedEnv:
         self._steps += 1
         return results
 
-    def run(self, agent: Union['BatchedPhysarumAgent', 'BatchedNeuralAutomataAgent'], n_steps: int) -> torch.Tensor:
+    def run(self, agent: Union['BatchedPhysarumAgent', 'BatchedPhysarumPopulation', 'BatchedNeuralAutomataAgent'], n_steps: int) -> torch.Tensor:
         out = torch.empty((n_steps, self.R, 2), dtype=torch.float64, device=self.device)
         for i in range(n_steps):
             self.step(agent, out[i])
@@ -418,6 +450,228 @@ class BatchedPhysarumAgent:
         return join64(self._hd_hi[r, :k].contiguous(), self._hd_lo[r, :k].contiguous()).cpu().numpy()
 
 
+PARAMETER_NAMES = ('scale', 'deposit', 'sense_offset', 'turn_angle', 'sense_angle', 'turn_tolerance')
+PHYSARUM_DEFAULTS = (0.005, 4.0, 0.03, 30.0, 90.0, 0.1)            # PhysarumAgent's constructor defaults, in that order
+
+
+def _check_physarum_values(v: np.ndarray, rows: Sequence) -> None:
+    """What a PhysarumAgent accepts, on (n, 6) float32 values; `rows` names each row in the error."""
+    checks = ((0, lambda c: c >= 0, '>= 0'), (2, lambda c: c >= 0, '>= 0'), (3, lambda c: (c > 0) & (c <= 180), 'in (0, 180]'),
+              (4, lambda c: (c >= 0) & (c <= 180), 'in [0, 180]'), (5, lambda c: c >= 0, '>= 0'))
+    if not np.all(np.isfinite(v)):
+        r, j = (int(i[0]) for i in np.nonzero(~np.isfinite(v)))
+        raise ValueError(f'row {rows[r]}, column {PARAMETER_NAMES[j]}: {v[r, j]} is not finite')
+    for j, ok, what in checks:
+        bad = np.nonzero(~ok(v[:, j]))[0]
+        if len(bad):
+            raise ValueError(f'row {rows[int(bad[0])]}, column {PARAMETER_NAMES[j]}: {v[bad[0], j]} must be {what}')
+
+
+class ParameterSpace:
+    """The box a unit-mode BatchedPhysarumPopulation is searched in: value j = lo[j] + (hi[j] - lo[j])·clamp(u[j], 0, 1) in
+    float32 (one product, one sum, each rounded), columns in PARAMETER_NAMES order.  The default brackets the reference's
+    PhysarumAgent defaults (0.005, 4.0, 0.03, 30, 90, 0.1):
+        lo = (0.001, 0.5, 0.005,  5,  10, 0.0)
+        hi = (0.02,  8.0, 0.1,   90, 180, 0.5)
+    Both ends of every decoded range must be values a PhysarumAgent accepts, so that every decoded row is."""
+    DEFAULT_LO = (0.001, 0.5, 0.005, 5.0, 10.0, 0.0)
+    DEFAULT_HI = (0.02, 8.0, 0.1, 90.0, 180.0, 0.5)
+
+    def __init__(self, lo: Optional[Sequence[float]] = None, hi: Optional[Sequence[float]] = None):
+        self.lo = np.array(self.DEFAULT_LO if lo is None else lo, dtype=np.float32).reshape(-1)
+        self.hi = np.array(self.DEFAULT_HI if hi is None else hi, dtype=np.float32).reshape(-1)
+        if self.lo.shape != (6,) or self.hi.shape != (6,):
+            raise ValueError(f'lo and hi: 6 values each, in the order {PARAMETER_NAMES}')
+        for j, name in enumerate(PARAMETER_NAMES):
+            if not (np.isfinite(self.lo[j]) and np.isfinite(self.hi[j]) and self.lo[j] <= self.hi[j]):
+                raise ValueError(f'column {name}: bounds ({self.lo[j]}, {self.hi[j]}) must be finite with lo <= hi')
+        _check_physarum_values(np.stack([self.lo, self.decode(np.ones(6, dtype=np.float32))]), ('lo', 'hi'))
+
+    def decode(self, u) -> np.ndarray:
+        """Search coordinates (..., 6) -> values, float32, by the expressions of die_physarum_decode_batch."""
+        u = np.asarray(u, dtype=np.float32)
+        c = np.fmin(np.fmax(u, np.float32(0)), np.float32(1))        # (a NaN coordinate reads as 0)
+        span = self.hi - self.lo
+        t = span * c
+        return (self.lo + t).astype(np.float32)
+
+    def encode(self, values) -> np.ndarray:
+        """Values -> search coordinates (float32; columns with lo == hi map to 0): where a search may start."""
+        span = (self.hi - self.lo).astype(np.float64)
+        v = np.asarray(values, dtype=np.float64)
+        return np.where(span > 0, (v - self.lo) / np.where(span > 0, span, 1.0), 0.0).astype(np.float32)
+
+    def _struct(self) -> _lib.ParameterSpace:
+        return _lib.ParameterSpace((C.c_float * 6)(*self.lo.tolist()), (C.c_float * 6)(*self.hi.tolist()))
+
+
+class BatchedPhysarumPopulation:
+    """R PhysarumAgent candidates whose scale, deposit, sense_offset, turn_angle, sense_angle and turn_tolerance differ per
+    replica; candidate r steps replica r of a BatchedEnv exactly as `candidate(r)` steps the stand-alone Env of seeds[r].
+    normalized_grad and grad_clip are shared (they choose the kernel), as a NeuralAutomataAgent population shares its
+    architecture.
+
+    `parameters` is ONE (R, 6) float32 device tensor, columns in PARAMETER_NAMES order:
+      * natural mode (`values=`, default: every row the reference's defaults): a row holds the constructor arguments
+        themselves (angles in degrees).  Checked on the host here and in `set_values`;
+      * unit mode (`parameters=`, `space=` a ParameterSpace, default ParameterSpace()): a row holds search coordinates, decoded
+        on the device as lo + (hi - lo)·clamp(u, 0, 1) — valid whatever a searcher writes.  What PGPE / CMAES bind to.
+    One launch (`die_physarum_decode_batch`) turns the rows into the table the step kernel reads.  It runs at construction,
+    in `reset()`, in `decode()`, and before a step when torch has counted an in-place write to `parameters` since — so
+    in-place torch writes are seen by the next step.  Two things to know: a write torch does not count (a kernel writing through
+    the raw pointer, such as a searcher's `ask(pop.parameters)` called by hand) is NOT seen until `decode()` or `reset()` — the
+    searchers' own generation calls `reset()`; and an in-place write to NATURAL rows is decoded unchecked (only the constructor
+    and `set_values` check on the host: a turn_angle of 0 or a NaN written in place reaches the kernels as it is) — use
+    `set_values`, or unit mode, where the device clamp keeps every row valid.
+
+    "Bit for bit the stand-alone run" has one caveat: the two cosines of a row (c_turn, c_sense) come from the device's float64
+    cos here and from the host's libm for a stand-alone agent; both are rounded to float32, so they differ only where the
+    libraries' last-bit difference straddles a float32 rounding boundary (about 1 row in 10^8; `table()` shows the values).
+
+    Small worlds: nothing here reads the device back except `values()`, `table()`, `candidate()` and
+    `direction_rads_numpy()`.  Large worlds (`env.per_replica`): R PhysarumAgent objects are built from `values()` at
+    construction and at `reset()` — a host read each time, and the only moments a write to `parameters` is taken up."""
+    PARAMETER_NAMES = PARAMETER_NAMES
+    P = 6
+
+    def __init__(self, env: BatchedEnv, values=None, *, parameters=None, space: Optional[ParameterSpace] = None,
+                 normalized_grad: bool = True, grad_clip: Optional[float] = 1e-5, seed: int = 0):
+        if values is not None and parameters is not None:
+            raise ValueError('values= (natural rows) or parameters= (unit rows with a space), not both')
+        self.natural = parameters is None
+        if self.natural and space is not None:
+            raise ValueError('space= goes with parameters= (unit mode); natural rows hold the values themselves')
+        if not self.natural and space is None:
+            space = ParameterSpace()
+        if space is not None and not isinstance(space, ParameterSpace):
+            raise TypeError('space: a ParameterSpace')
+        self.env, self.R, self.seed, self.space = env, env.R, int(seed), space
+        self.normalized_grad, self.grad_clip = bool(normalized_grad), grad_clip
+        dev = env.device
+        self.parameters = torch.empty((self.R, self.P), dtype=torch.float32, device=dev)
+        self._table = torch.zeros(self.R * C.sizeof(_lib.PhysarumRow), dtype=torch.uint8, device=dev)
+        self._values = torch.zeros((self.R, self.P), dtype=torch.float32, device=dev)
+        self._space_struct = None if space is None else space._struct()
+        self._seen = None                           # (`parameters`' address, its torch version counter) at the last decode
+        self._calls = 0
+        if self.natural:
+            rows = np.tile(np.float32(PHYSARUM_DEFAULTS), (self.R, 1)) if values is None else values
+            self.parameters.copy_(self._natural_rows(rows))
+        else:
+            self.parameters.copy_(self._rows(parameters, 'parameters'))
+        if not env.per_replica:
+            self._hd_hi = torch.zeros((env.R, env.Nmax), dtype=torch.int32, device=dev)
+            self._hd_lo = torch.zeros((env.R, env.Nmax), dtype=torch.int32, device=dev)
+        self.reset()
+
+    # ------------------------------------------------------------------ parameters
+    def _rows(self, rows, what: str) -> torch.Tensor:
+        t = torch.as_tensor(rows).detach().to(torch.float32)
+        if tuple(t.shape) != (self.R, self.P):
+            raise ValueError(f'{what} of shape {tuple(t.shape)}: ({self.R}, {self.P}) expected (R replicas x {PARAMETER_NAMES})')
+        return t
+
+    def _natural_rows(self, rows) -> torch.Tensor:
+        t = self._rows(rows, 'values')
+        _check_physarum_values(t.cpu().numpy(), range(self.R))
+        return t
+
+    def set_values(self, values) -> None:
+        """Natural mode: copy an (R, 6) matrix of constructor arguments in (checked on the host first)."""
+        if not self.natural:
+            raise ValueError('set_values: this population holds unit rows (set_parameters); its values are decoded from them')
+        self.parameters.copy_(self._natural_rows(values))
+        self.decode()
+
+    def set_parameters(self, parameters) -> None:
+        """Unit mode: copy an (R, 6) matrix of search coordinates in."""
+        if self.natural:
+            raise ValueError('set_parameters: this population holds natural rows (set_values checks them)')
+        self.parameters.copy_(self._rows(parameters, 'parameters'))
+        self.decode()
+
+    def decode(self) -> None:
+        """`parameters` -> the table and the decoded values.  One launch, no host read."""
+        self._check_parameters()
+        mode = _lib.DIE_PHYSARUM_NATURAL if self.natural else _lib.DIE_PHYSARUM_UNIT
+        _lib.check(_lib.lib.die_physarum_decode_batch(_ptr(self.parameters), self.R, mode,
+                                                      None if self._space_struct is None else C.byref(self._space_struct),
+                                                      _ptr(self._table), _ptr(self._values), stream_ptr(self.env.device)),
+                   'die_physarum_decode_batch')
+        self._seen = (self.parameters.data_ptr(), self.parameters._version)
+
+    def _sync(self) -> None:
+        if (self.parameters.data_ptr(), self.parameters._version) != self._seen:     # written in place, or rebound
+            self.decode()
+
+    def values(self) -> np.ndarray:
+        """The decoded (R, 6) float32 values (natural mode: the rows themselves), read from the device."""
+        self._sync()
+        return self._values.cpu().numpy().copy()
+
+    def table(self) -> np.ndarray:
+        """The device table as a structured array of R die_physarum_row records (read from the device)."""
+        self._sync()
+        return np.frombuffer(self._table.cpu().numpy().tobytes(), dtype=np.dtype(_lib.PhysarumRow)).copy()
+
+    def _agent(self, v: np.ndarray, max_agents: int, seed: Optional[int]):
+        from .agent.gradient import PhysarumAgent
+        return PhysarumAgent(max_agents=max_agents, scale=float(v[0]), deposit=float(v[1]), sense_offset=float(v[2]),
+                             normalized_grad=self.normalized_grad, grad_clip=self.grad_clip, turn_angle=float(v[3]),
+                             sense_angle=float(v[4]), turn_tolerance=float(v[5]), seed=seed)
+
+    def candidate(self, r: int):
+        """Candidate r as a stand-alone PhysarumAgent(max_agents=K_r, seed=seed + r, **decoded row r)."""
+        return self._agent(self.values()[r], self.env.n[r], self.seed + r)
+
+    def agent_from_row(self, row, max_agents: int = 10 ** 6, seed: Optional[int] = None):
+        """A stand-alone PhysarumAgent from one row of this population's kind (a searcher's best / centre), decoded on the
+        host with the device's float32 expressions."""
+        v = np.asarray(torch.as_tensor(row).detach().cpu().to(torch.float32).numpy()).reshape(self.P)
+        if not self.natural:
+            v = self.space.decode(v)
+        _check_physarum_values(v[None], ('given',))
+        return self._agent(v, max_agents, seed)
+
+    # ------------------------------------------------------------------ state
+    def reset(self) -> None:
+        """Headings and the forward-call counter as at construction, for the current `parameters` (the turn angle sets the
+        headings' lattice): the decode launch and one `die_physarum_heading_batch` launch, no host read (small worlds)."""
+        self._calls = 0
+        self.decode()
+        if self.env.per_replica:
+            v = self.values()
+            self.agents = [self._agent(v[r], self.env.n[r], self.seed + r) for r in range(self.R)]
+            return
+        env = self.env
+        b = _lib.Batch(env.R, 0, env.W * env.H, env.Nmax, 1, (C.c_int64 * 64)(*env.n))
+        _lib.check(_lib.lib.die_physarum_heading_batch(_ptr(self._hd_hi), _ptr(self._hd_lo), C.byref(b), _ptr(self._table),
+                                                       self.seed & 0xFFFFFFFFFFFFFFFF, stream_ptr(env.device)),
+                   'die_physarum_heading_batch')
+
+    def _check_parameters(self):
+        p = self.parameters
+        if tuple(p.shape) != (self.R, self.P) or p.dtype != torch.float32 or p.device != self.env.device or not p.is_contiguous():
+            raise ValueError(f'parameters must stay a contiguous ({self.R}, {self.P}) float32 tensor on {self.env.device}')
+
+    def _check_step(self, env: BatchedEnv):
+        if env is not self.env:
+            raise ValueError('this population was built for another BatchedEnv')
+        self._check_parameters()
+
+    def _struct(self) -> _lib.GradientAgent:
+        return _lib.GradientAgent(_lib.DIE_AGENT_PHYSARUM, int(self.normalized_grad), 0.0, 0.0, 0.0, 0.0, 0.0,
+                                  -1.0 if self.grad_clip is None else self.grad_clip, 0.0, 0.0, 0.0, _ptr(self._hd_hi), _ptr(self._hd_lo),
+                                  None, None, None, self.seed & 0xFFFFFFFFFFFFFFFF, self._calls & 0xFFFFFFFF, 0, None)
+
+    def direction_rads_numpy(self, r: int) -> np.ndarray:
+        if self.env.per_replica:
+            torch.cuda.synchronize(self.env.device)
+            return self.agents[r].direction_rads_numpy()
+        k = self.env.n[r]
+        return join64(self._hd_hi[r, :k].contiguous(), self._hd_lo[r, :k].contiguous()).cpu().numpy()
+
+
 def _architecture(agent: NeuralAutomataAgent) -> dict:
     """What every candidate of a population shares: the stack's shape, its boundary, the observed channels, the action scale."""
     layers = agent.model.conv_layers()
@@ -429,7 +683,8 @@ def _architecture(agent: NeuralAutomataAgent) -> dict:
 class BatchedNeuralAutomataAgent:
     """A population of R NeuralAutomataAgent candidates of one architecture, candidate r stepping replica r of a BatchedEnv.
     The weights are ONE (R, P) float32 device tensor `parameters`: row r is `parameters_to_vector(model.parameters())` of
-    candidate r — the layout evolution strategies hand around.  In-place writes to `parameters` are seen by the next step."""
+    candidate r — the layout evolution strategies hand around.  In-place writes to `parameters` are seen by the next step.
+    (No `reset()` method here, deliberately: the searchers call a population's `reset()` every generation when it has one.)"""
 
     def __init__(self, env: BatchedEnv, template: NeuralAutomataAgent, parameters=None):
         if not isinstance(template, NeuralAutomataAgent):

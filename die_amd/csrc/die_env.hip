@@ -185,10 +185,9 @@ __device__ __forceinline__ void batch_stash(StepArgs& a, const BatchArgs& b, int
     }
 }
 
-template <typename T, int KIND, bool LEAN = false>
-__global__ __launch_bounds__(DIE_STEP_BLOCK) void k_forward_move_claim_batch(FwdArgs f, StepArgs a, BatchArgs b) {
-    if (LEAN) fwd_args_lean(f);
-    const int r = blockIdx.y;
+// replica r's arrays, agent count, Philox key and workspace partials
+template <typename T>
+__device__ __forceinline__ void batch_replica_args(FwdArgs& f, StepArgs& a, const BatchArgs& b, const int r) {
     const int64_t pc = b.cells * r, pa = b.agents * r;
     f.chem = (const T*)f.chem + pc; f.food = (const T*)f.food + pc;
     f.x += pa; f.y += pa; f.heading_hi += pa; f.heading_lo += pa;
@@ -201,8 +200,33 @@ __global__ __launch_bounds__(DIE_STEP_BLOCK) void k_forward_move_claim_batch(Fwd
     a.N = b.n[r];
     a.part_gain += (int64_t)DIE_MAX_PARTIALS * 3 * r;               // replica r's own workspace partials
     batch_stash(a, b, r);
+}
+
+template <typename T, int KIND, bool LEAN = false>
+__global__ __launch_bounds__(DIE_STEP_BLOCK) void k_forward_move_claim_batch(FwdArgs f, StepArgs a, BatchArgs b) {
+    if (LEAN) fwd_args_lean(f);
+    const int r = blockIdx.y;
+    batch_replica_args<T>(f, a, b, r);
     forward_move_claim_body<T, KIND, false>(f, a);
     // every slot is alive: the sweep's reduction reads the count here (with dead slots, k_lifecycle_batch counts them)
+    if (!a.has_dead && blockIdx.x == 0 && threadIdx.x == 0) a.part_alive[0] = a.N;
+}
+
+// A PhysarumAgent population (die_physarum_env_step_batch): the kernel above, replica r stepping with row r of the table in
+// place of the shared scale / deposit / sense_offset / angles / tolerance and the constants derived from them.  The row is
+// uniform over the workgroup and read-only: one 64-byte scalar load into the by-value FwdArgs, ahead of the loop, so the
+// loop reads the same scalar registers it reads in the shared-parameter kernel.
+template <typename T, bool LEAN>
+__global__ __launch_bounds__(DIE_STEP_BLOCK) void k_physarum_move_claim_batch(FwdArgs f, StepArgs a, BatchArgs b,
+                                                                              const die_physarum_row* __restrict__ table) {
+    if (LEAN) fwd_args_lean(f);
+    const int r = blockIdx.y;
+    const die_physarum_row row = table[r];
+    f.scale = row.scale; f.deposit = row.deposit; f.sense_offset = row.sense_offset;
+    f.turn_rad = row.turn_radians; f.sense_rad = row.sense_radians; f.rtol = row.turn_tolerance;
+    f.x_turn = row.x_turn; f.atol = row.atol; f.c_turn = row.c_turn; f.c_sense = row.c_sense;
+    batch_replica_args<T>(f, a, b, r);
+    forward_move_claim_body<T, DIE_AGENT_PHYSARUM, false>(f, a);
     if (!a.has_dead && blockIdx.x == 0 && threadIdx.x == 0) a.part_alive[0] = a.N;
 }
 
@@ -1191,6 +1215,47 @@ extern "C" int die_forward_env_step_batch(const die_medium* m, const die_agents*
         if (g->kind != DIE_AGENT_PHYSARUM) k_forward_move_claim_batch<__half, DIE_AGENT_GRADIENT><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba);
         else if (fwd_is_lean(g)) k_forward_move_claim_batch<__half, DIE_AGENT_PHYSARUM, true><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba);
         else k_forward_move_claim_batch<__half, DIE_AGENT_PHYSARUM><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba);
+    }
+    DIE_CHECK_LAUNCH(who);
+    rc = batch_lifecycle(k, ba, grid, s, who);
+    if (rc != DIE_OK) return rc;
+    return batch_sweep(m, d, b, results, ws, (int)grid.x, s, who);
+}
+
+extern "C" int die_physarum_env_step_batch(const die_medium* m, const die_agents* a, die_gradient_agent* g, const die_physarum_row* table,
+                                           const die_action* act, const die_dynamics* d, const die_batch* b, die_step_result* results,
+                                           void* ws, int64_t ws_bytes, void* stream) {
+    const char* who = "die_physarum_env_step_batch";
+    DIE_REQUIRE(m && a && g && d && b && results && ws, "%s: null argument", who);
+    DIE_REQUIRE(table, "%s: null parameter table", who);
+    int rc = batch_ws_check(d, b, ws_bytes, who);
+    if (rc != DIE_OK) return rc;
+    DIE_REQUIRE(m->gW <= 0 && !m->sense_mask && !d->staged, "%s: periodic single-tile replicas (no sense mask)", who);
+    DIE_REQUIRE(m->chem_next && m->chem_next != m->chem, "%s: chem_next must be a second plane", who);
+    DIE_REQUIRE(b->plane_stride >= (int64_t)m->W * m->H && b->agent_stride >= a->N, "%s: strides smaller than a replica", who);
+    if (!fused_step_applies(m, d)) {
+        die_set_error("%s: only for periodic planes with H %% 4 == 0 and gaussian radius 1..4", who);
+        return DIE_ERR_UNSUPPORTED;
+    }
+    DIE_REQUIRE(g->kind == DIE_AGENT_PHYSARUM, "%s: kind %d: a population of PhysarumAgents", who, g->kind);
+    DIE_REQUIRE(g->inertia == 0.f && g->noise_scale == 0.f && !g->prev_gx && !g->prev_gy && !g->step_base,
+                "%s: no inertia, noise, prev_g* or step_base (they are state or constants of one agent, not of a population)", who);
+    FwdArgs f;
+    rc = die_fill_fwd_args(f, m, a, g, act, who);
+    if (rc != DIE_OK) return rc;
+    StepArgs k;
+    BatchArgs ba;
+    int64_t nmax;
+    rc = batch_step_args(k, ba, nmax, m, a, act, d, b, ws, who);
+    if (rc != DIE_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid(step_grid(nmax), b->replicas);
+    if (m->dtype == DIE_F32) {
+        if (fwd_is_lean(g)) k_physarum_move_claim_batch<float, true><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba, table);
+        else k_physarum_move_claim_batch<float, false><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba, table);
+    } else {
+        if (fwd_is_lean(g)) k_physarum_move_claim_batch<__half, true><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba, table);
+        else k_physarum_move_claim_batch<__half, false><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba, table);
     }
     DIE_CHECK_LAUNCH(who);
     rc = batch_lifecycle(k, ba, grid, s, who);

@@ -172,6 +172,37 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_init_heading(uint32_t* hhi, uint3
     }
 }
 
+// k_init_heading of every replica of a PhysarumAgent population (blockIdx.y = replica): replica r's n[r] slots lie r agent
+// strides further, its key is seed + r·seed_stride, its lattice the turn angle of its own table row
+struct HeadingBatchArgs {
+    int64_t agents;
+    uint64_t seed, seed_stride;
+    int64_t n[DIE_MAX_REPLICAS];
+};
+
+__global__ __launch_bounds__(DIE_BLOCK) void k_init_heading_batch(uint32_t* hhi, uint32_t* hlo, HeadingBatchArgs b,
+                                                                  const die_physarum_row* __restrict__ table) {
+    const int r = blockIdx.y;
+    const int64_t N = b.n[r];
+    const double turn = table[r].turn_radians;
+    const uint64_t seed = b.seed + b.seed_stride * (uint64_t)r;
+    hhi += b.agents * r; hlo += b.agents * r;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += stride) {
+        // k_init_heading's expressions, restated (that kernel stays as it is)
+        const die_u32x4 q = die_draw(seed, 0, (uint64_t)n, DIE_STREAM_INIT_HEADING);
+        const double u1 = ((double)q.v[0] + 1.0) * (1.0 / 4294967296.0);
+        const double u2 = (double)q.v[1] * (1.0 / 4294967296.0);
+        const double rad = 0.4 * sqrt(-2.0 * log(u1));
+        const double gx = rad * cos(6.283185307179586476925 * u2), gy = rad * sin(6.283185307179586476925 * u2);
+        double ang = atan2(gy, gx);
+        if (turn > 0.0) ang = floor(ang / turn) * turn;
+        const double h = (double)(float)ang;
+        hhi[n] = (uint32_t)__double2hiint(h);
+        hlo[n] = (uint32_t)__double2loint(h);
+    }
+}
+
 static int init_grid(int64_t n) {
     int64_t g = (n + DIE_BLOCK - 1) / DIE_BLOCK;
     return (int)(g < 8192 ? (g > 0 ? g : 1) : 8192);
@@ -234,6 +265,25 @@ extern "C" int die_init_heading(uint32_t* heading_hi, uint32_t* heading_lo, floa
     k_init_heading<<<init_grid(N), DIE_BLOCK, 0, (hipStream_t)stream>>>(heading_hi, heading_lo, prev_gx, prev_gy, N, turn_radians,
                                                                           seed);
     DIE_CHECK_LAUNCH("die_init_heading");
+    return DIE_OK;
+}
+
+extern "C" int die_physarum_heading_batch(uint32_t* heading_hi, uint32_t* heading_lo, const die_batch* b, const die_physarum_row* table,
+                                          uint64_t seed, void* stream) {
+    const char* who = "die_physarum_heading_batch";
+    DIE_REQUIRE(heading_hi && heading_lo && b && table, "%s: null argument", who);
+    DIE_REQUIRE(b->replicas >= 1 && b->replicas <= DIE_MAX_REPLICAS, "%s: 1..%d replicas", who, DIE_MAX_REPLICAS);
+    DIE_REQUIRE(b->agent_stride >= 1, "%s: bad agent stride %lld", who, (long long)b->agent_stride);
+    HeadingBatchArgs k;
+    k.agents = b->agent_stride; k.seed = seed; k.seed_stride = b->seed_stride;
+    int64_t nmax = 0;
+    for (int r = 0; r < DIE_MAX_REPLICAS; ++r) {
+        k.n[r] = r < b->replicas ? b->n[r] : 0;
+        DIE_REQUIRE(r >= b->replicas || (b->n[r] >= 1 && b->n[r] <= b->agent_stride), "%s: replica %d has %lld agents", who, r, (long long)b->n[r]);
+        if (k.n[r] > nmax) nmax = k.n[r];
+    }
+    k_init_heading_batch<<<dim3(init_grid(nmax), b->replicas), DIE_BLOCK, 0, (hipStream_t)stream>>>(heading_hi, heading_lo, k, table);
+    DIE_CHECK_LAUNCH(who);
     return DIE_OK;
 }
 

@@ -77,15 +77,20 @@ class _PopulationSearch:
     # ------------------------------------------------------------------ a population of NeuralAutomataAgents
     def for_population(self, pop, epoch_iters: int, env=None, *, reseed: Optional[int] = None, reseed_stride: int = 0):
         """Bind to a BatchedNeuralAutomataAgent: `step()` is then ask into `pop.parameters`, `pop.env.reset()`, `epoch_iters`
-        batched steps, tell.  `env`, when given, must be the population's own BatchedEnv.
+        batched steps, tell.  `env`, when given, must be the population's own BatchedEnv.  A BatchedPhysarumPopulation in unit
+        mode binds the same way (what is used: R, P, parameters, env, and `reset()` where the population has one — called
+        after the worlds' reset: it decodes the asked rows and re-draws the headings); best_agent() / pop_best_agent() /
+        center_agent() then return PhysarumAgents.
 
         `reseed`: a new world every generation instead of the construction worlds — generation g (`iter` at ask) resets with
         `pop.env.reset(seed=reseed + g·R, seed_stride=reseed_stride)`.  Stride 0 (default): every candidate of a generation is
         evaluated on the same fresh world (what antithetic pairs and ranks compare); stride 1: a world per replica and
         generation.  The population's BatchedEnv needs the fixed layout (`max_agents` an int or None)."""
-        from .batch import BatchedNeuralAutomataAgent
-        if not isinstance(pop, BatchedNeuralAutomataAgent):
-            raise TypeError('pop: a BatchedNeuralAutomataAgent')
+        if any(not hasattr(pop, name) for name in ('R', 'P', 'parameters', 'env')):
+            raise TypeError('pop: a BatchedNeuralAutomataAgent or a BatchedPhysarumPopulation (R, P, parameters, env)')
+        if getattr(pop, 'natural', False):
+            raise ValueError('a BatchedPhysarumPopulation of natural rows: one step size does not suit six units — build it in '
+                             'unit mode (parameters=, space=ParameterSpace(lo, hi)) to search it')
         if env is not None and env is not pop.env:
             raise ValueError('this population was built for another BatchedEnv')
         if pop.R != self.R:
@@ -106,6 +111,10 @@ class _PopulationSearch:
                                  'per replica, and a new world has a new K_r')
         self._reseed, self._reseed_stride = reseed, int(reseed_stride)
         self._pop, self._epoch_iters = pop, int(epoch_iters)
+        # a population with state of its own between generations (a PhysarumAgent population's headings and table) says so
+        # with a `reset()`.  BatchedNeuralAutomataAgent has none ON PURPOSE: its generation is ask, env.reset, steps, tell and
+        # nothing else — giving it a `reset` method would add a call to every NCA generation
+        self._pop_reset = getattr(pop, 'reset', None)
         self._results = torch.empty((self._epoch_iters, self.R, 2), dtype=torch.float64, device=self.device)
         return self
 
@@ -120,6 +129,8 @@ class _PopulationSearch:
             env.reset()
         else:
             env.reset(seed=self._reseed + g * self.R, seed_stride=self._reseed_stride)
+        if self._pop_reset is not None:
+            self._pop_reset()
         for t in range(self._epoch_iters):
             env.step(pop, self._results[t])
         self.tell(self._results)
@@ -135,13 +146,15 @@ class _PopulationSearch:
 
     def _agent(self, row: torch.Tensor, template=None):
         from .batch import BatchedNeuralAutomataAgent
+        if template is None and hasattr(self._pop, 'agent_from_row'):       # a BatchedPhysarumPopulation: a PhysarumAgent
+            return self._pop.agent_from_row(row)
         template = template if template is not None else (self._pop.template if self._pop is not None else None)
         if template is None:
             raise RuntimeError('no NeuralAutomataAgent template: bind a population (for_population) or pass one')
         return BatchedNeuralAutomataAgent.unpack(template, row.cpu())
 
     def best_agent(self, template=None):
-        """The best candidate evaluated so far, as a stand-alone NeuralAutomataAgent (ready for save())."""
+        """The best candidate evaluated so far, as a stand-alone agent of the population's kind (ready for save())."""
         return self._agent(self._best, template)
 
     def pop_best_agent(self, template=None):

@@ -232,6 +232,54 @@ int die_forward_env_step_batch(const die_medium* m, const die_agents* a, die_gra
                                const die_dynamics* d, const die_batch* b, die_step_result* results, void* workspace,
                                int64_t workspace_bytes, void* stream);
 
+/* ---- PhysarumAgent populations: per-replica parameters ----------------------------------------------------------------
+ * A device table of one kernel-ready row per replica: what a stand-alone PhysarumAgent of those constructor arguments hands
+ * the kernels (die_gradient_agent's scale, deposit, sense_offset, turn_radians, sense_radians, turn_tolerance) and the
+ * constants die_forward_env_step derives from them on the host (the np.isclose thresholds of _choose_turn and their cosines).
+ * kind, normalized_grad, grad_clip, inertia = 0 and noise_scale = 0 stay shared: they choose the kernel instantiation.
+ * 64 bytes, so that a workgroup fetches its replica's row with one scalar load. */
+typedef struct die_physarum_row {
+    float scale, deposit, sense_offset;
+    float c_turn, c_sense;   /* cos(x_turn), cos(sense_radians); 2 / -2 where the angle is outside [0, pi) */
+    float reserved;
+    double turn_radians, sense_radians, turn_tolerance;
+    double x_turn;           /* largest |x| np.isclose(0, x, rtol=1e-2, atol=turn_radians * turn_tolerance) accepts */
+    double atol;             /* turn_radians * turn_tolerance */
+} die_physarum_row;
+
+/* Column order of a parameter row: scale, deposit, sense_offset, turn_angle, sense_angle (degrees), turn_tolerance. */
+#define DIE_PHYSARUM_PARAMS 6
+#define DIE_PHYSARUM_NATURAL 0
+#define DIE_PHYSARUM_UNIT 1
+typedef struct die_parameter_space {
+    float lo[DIE_PHYSARUM_PARAMS];
+    float hi[DIE_PHYSARUM_PARAMS];
+} die_parameter_space;
+
+/* One launch: (replicas, 6) fp32 `rows` -> `table` (replicas rows) and `values` (replicas, 6) fp32, the decoded values.
+ *   DIE_PHYSARUM_NATURAL: a row holds the values themselves (`space` is ignored and may be NULL).
+ *   DIE_PHYSARUM_UNIT: a row holds search coordinates u; value j = lo[j] + (hi[j] - lo[j]) * clamp(u[j], 0, 1) in fp32, each
+ *     operation rounded by itself (a NaN coordinate reads as 0).  `space` is copied at the call; lo <= hi, both finite, and
+ *     both ends of every decoded range must be values a PhysarumAgent accepts (scale, sense_offset, turn_tolerance >= 0,
+ *     0 < turn_angle <= 180, 0 <= sense_angle <= 180), so that every decoded row is.
+ * Degrees become radians as (double)v * (pi / 180) (Python's math.radians); x_turn is found by the bisection
+ * die_forward_env_step runs on the host, the cosines by the device's float64 cos rounded to fp32. */
+int die_physarum_decode_batch(const float* rows, int32_t replicas, int32_t mode, const die_parameter_space* space,
+                              die_physarum_row* table, float* values, void* stream);
+
+/* die_init_heading of every replica in one launch: replica r covers n[r] slots r * agent_stride behind heading_hi / _lo,
+ * draws from key seed + r * seed_stride and discretises with table[r].turn_radians. */
+int die_physarum_heading_batch(uint32_t* heading_hi, uint32_t* heading_lo, const die_batch* b, const die_physarum_row* table,
+                               uint64_t seed, void* stream);
+
+/* die_forward_env_step_batch with the table: replica r steps with table[r] in place of g's scale, deposit, sense_offset,
+ * turn_radians, sense_radians and turn_tolerance (which are ignored).  g->kind must be DIE_AGENT_PHYSARUM, with no
+ * inertia, noise, prev_g* or step_base.  Otherwise the same call: same refusals before any launch, same dead-slot pass,
+ * fp16 planes, `act` may be NULL. */
+int die_physarum_env_step_batch(const die_medium* m, const die_agents* a, die_gradient_agent* g, const die_physarum_row* table,
+                                const die_action* act, const die_dynamics* d, const die_batch* b, die_step_result* results,
+                                void* workspace, int64_t workspace_bytes, void* stream);
+
 /* First kernel of die_forward_env_step alone (forward + move + claim + feeding of alive slots). */
 int die_forward_move_claim(const die_medium* m, const die_agents* a, die_gradient_agent* g, const die_action* act,
                            const die_dynamics* d, void* workspace, int64_t workspace_bytes, void* stream);
