@@ -12,10 +12,10 @@ from .data_init import DataInitializer, FieldSequence, PerlinNoiseSequence, Wave
 from .device_array import DeviceAction, DeviceAgents, DeviceMedium
 from .env import BoundaryCondition, Dynamics, Env, linear_action_cost, zero_cost
 from .batch import (BatchedEnv, BatchedNeuralAutomataAgent, BatchedPhysarumAgent, BatchedPhysarumPopulation,
-                    ParameterSpace)
+                    ParameterSpace, episode_seeds)
 from .search import CMAES, PGPE
 
 __all__ = ['WaveSequence', 'PerlinNoiseSequence', 'FieldSequence', 'Env', 'Dynamics', 'BoundaryCondition', 'linear_action_cost', 'zero_cost', 'Agent', 'PhysarumAgent',
            'GradientAgent', 'BrownianAgent', 'ConstAgent', 'NeuralAutomataAgent', 'ConvolutionModel', 'DataInitializer', 'DataChannels', 'DeviceMedium',
            'DeviceAgents', 'DeviceAction', 'PGPE', 'CMAES', 'BatchedEnv', 'BatchedPhysarumAgent',
-           'BatchedNeuralAutomataAgent', 'BatchedPhysarumPopulation', 'ParameterSpace']
+           'BatchedNeuralAutomataAgent', 'BatchedPhysarumPopulation', 'ParameterSpace', 'episode_seeds']

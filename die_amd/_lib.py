@@ -120,7 +120,7 @@ class NcaLayer(C.Structure):         # die_nca_layer
 
 class NcaBatch(C.Structure):         # die_nca_batch
     _fields_ = [('n_layers', C.c_int32), ('padding_mode', C.c_int32), ('with_agent_channel', C.c_int32), ('sense_epoch', C.c_int32),
-                ('layers', C.POINTER(NcaLayer)), ('coef', C.c_float * 3), ('reserved', C.c_int32), ('scratch', C.c_void_p),
+                ('layers', C.POINTER(NcaLayer)), ('coef', C.c_float * 3), ('episodes', C.c_int32), ('scratch', C.c_void_p),
                 ('scratch_bytes', C.c_int64)]
 
 
@@ -187,6 +187,8 @@ _SIGNATURES = {
     'die_forward_env_step_batch': (C.c_int, [_P(Medium), _P(Agents), _P(GradientAgent), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
                                              C.c_void_p, C.c_int64, C.c_void_p]),
     'die_physarum_decode_batch': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(ParameterSpace), C.c_void_p, C.c_void_p, C.c_void_p]),
+    'die_physarum_decode_episodes': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _P(ParameterSpace), C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
     'die_physarum_heading_batch': (C.c_int, [C.c_void_p, C.c_void_p, _P(Batch), C.c_void_p, C.c_uint64, C.c_void_p]),
     'die_physarum_env_step_batch': (C.c_int, [_P(Medium), _P(Agents), _P(GradientAgent), C.c_void_p, _P(Action), _P(Dynamics), _P(Batch),
                                               C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
@@ -230,6 +232,8 @@ _SIGNATURES = {
     'die_init_batch_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     'die_init_batch': (C.c_int, [_P(Medium), _P(Agents), _P(Batch), C.c_double, C.c_uint64, C.c_uint64, _P(FoodSpec), C.c_void_p,
                                  C.c_void_p, C.c_int64, C.c_void_p]),
+    'die_init_batch_seeds': (C.c_int, [_P(Medium), _P(Agents), _P(Batch), C.c_double, _P(C.c_uint64), C.c_int32, _P(FoodSpec), C.c_void_p,
+                                       C.c_void_p, C.c_int64, C.c_void_p]),
     'die_init_heading': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_uint64, C.c_void_p]),
     'die_field_fill': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_uint64, C.c_uint32,
                                  C.c_uint32, C.c_void_p]),
@@ -243,8 +247,12 @@ _SIGNATURES = {
                                     C.c_void_p]),
     'die_pgpe_sample': (C.c_int, [_P(Pgpe), C.c_void_p, C.c_int64, C.c_void_p]),
     'die_pgpe_update': (C.c_int, [_P(Pgpe), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    'die_pgpe_update_episodes': (C.c_int, [_P(Pgpe), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                           C.c_void_p, C.c_int64, C.c_void_p]),
     'die_cmaes_sample': (C.c_int, [_P(Cmaes), C.c_void_p, C.c_int64, C.c_void_p]),
     'die_cmaes_update': (C.c_int, [_P(Cmaes), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    'die_cmaes_update_episodes': (C.c_int, [_P(Cmaes), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.c_int64, C.c_void_p]),
     'die_rects_pack': (C.c_int, [_P(Rect), C.c_int32, C.c_void_p, C.c_void_p]),
     'die_pic_two_launch': (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32]),
     'die_pic_step_bound': (C.c_float, [C.c_float, C.c_float]),

@@ -28,7 +28,12 @@ for bit; the step runs its dead-slot pass (one more launch per step, as under ag
 `BatchedPhysarumPopulation` is a population of PhysarumAgent candidates whose six constructor arguments differ per replica
 (a parameter sweep, or the candidates of a search): replica r is `Env(field_size, dynamics, seed=seeds[r])` driven by
 `PhysarumAgent(max_agents=K_r, seed=seed + r, **row r)` — the same launch pair per step (`die_physarum_env_step_batch`), each
-workgroup fetching its replica's row of a device table, bit for bit the stand-alone runs (tests/test_gpu_physarum_pop.py)."""
+workgroup fetching its replica's row of a device table, bit for bit the stand-alone runs (tests/test_gpu_physarum_pop.py).
+
+Episodes: both populations take `episodes=E` — C = R / E candidates, each evaluated on E worlds in the same launches.  Replica
+r = c·E + e is candidate c on its e-th world (candidate-major), `parameters` stays ONE (C, P) matrix (the kernels read row r / E;
+nothing is expanded), and `reset(seeds=[...])` / `episode_seeds` give the replicas their worlds (`die_init_batch_seeds`).  The
+searchers fold the E sums of a candidate into its fitness (tests/test_gpu_episodes.py)."""
 import ctypes as C
 import dataclasses
 import math
@@ -145,7 +150,7 @@ class BatchedEnv:
         self._initial = (self._state.clone(), self.chem, self.chem_next)
         self._flow_k0 = getattr(self.dynamics.op_food_flow, '_k', None)
 
-    def reset(self, *, seed: Optional[int] = None, seed_stride: int = 1) -> None:
+    def reset(self, *, seed: Optional[int] = None, seed_stride: int = 1, seeds: Optional[Sequence[int]] = None) -> None:
         """Every replica back to the state it was constructed in: bit for bit a fresh BatchedEnv of the same arguments (and a
         flow operator whose counter stands where this one's stood then).  Device copies from a snapshot taken at construction,
         on the current stream (one copy in the small-world regime); nothing is rebuilt and nothing is read back (the device loop
@@ -155,7 +160,25 @@ class BatchedEnv:
         those seeds (same max_agents), and `seeds` says so.  Needs the fixed layout (`max_agents` an int or None).  Small worlds:
         one die_init_batch call on the current stream, no host read and no allocation; a world seeding more than N agents is
         clipped as Env's agents_from_medium clips it, and the next `check()` raises.  Large worlds (per_replica): `Env.reset`
-        of every replica, which reads each count back (and raises at once on such a world)."""
+        of every replica, which reads each count back (and raises at once on such a world).
+
+        `seeds`: the same with the world of every replica given — any R integers, repeats allowed, no pattern (the E worlds
+        of every candidate: `episode_seeds`).  Not together with `seed`.  Small worlds: one die_init_batch_seeds call, the same
+        five launches, the list handed to the kernels by value."""
+        listed = seeds is not None
+        if listed:
+            if seed is not None:
+                raise ValueError('reset: seed= (seed + r·seed_stride) or seeds= (a list of R seeds), not both')
+            if self._fixed is None:
+                raise ValueError("reset(seeds=...) needs every replica to hold the same number of slots: build the BatchedEnv "
+                                 "with max_agents=N (or None for W·H) instead of 'alive'")
+            seeds = list(seeds)
+            if len(seeds) != self.R:
+                raise ValueError(f'reset(seeds=...): {len(seeds)} seeds for {self.R} replicas')
+            for q in seeds:
+                if isinstance(q, bool) or int(q) != q:
+                    raise ValueError(f'reset(seeds=...): {q!r} is not an integer seed')
+            seeds = [int(q) for q in seeds]
         if seed is not None:
             if self._fixed is None:
                 raise ValueError("reset(seed=...) needs every replica to hold the same number of slots: build the BatchedEnv "
@@ -167,7 +190,7 @@ class BatchedEnv:
         if self._flow_k0 is not None:
             self.dynamics.op_food_flow._k = self._flow_k0
         self._steps = 0
-        if seed is not None:
+        if seed is not None or listed:
             self._reseed(seeds, seed, seed_stride)
             return
         if self.per_replica:
@@ -179,7 +202,8 @@ class BatchedEnv:
         self.chem, self.chem_next = self._initial[1:]
         self.epoch = 1
 
-    def _reseed(self, seeds: List[int], seed: int, seed_stride: int) -> None:
+    def _reseed(self, seeds: List[int], seed: Optional[int], seed_stride: int) -> None:
+        """The worlds of `seeds`; `seed` is None when they came as a list (else seeds[r] = seed + r·seed_stride)."""
         if self.per_replica:
             for r, (e, q) in enumerate(zip(self.envs, seeds)):
                 try:
@@ -193,8 +217,15 @@ class BatchedEnv:
         self.epoch = 1
         m, a, _, b = self._structs()
         # Env._init_data: the Perlin food of DataInitializer.init_medium (its spec holds no seed-drawn value the kernel reads)
-        spec = food_spec_from_seed(seed, scale=0.5, perlin_octaves=8, threshold=1.0)
+        spec = food_spec_from_seed(seeds[0] if seed is None else seed, scale=0.5, perlin_octaves=8, threshold=1.0)
         mask = 0xFFFFFFFFFFFFFFFF
+        if seed is None:
+            words = (C.c_uint64 * self.R)(*[q & mask for q in seeds])          # read during the call, passed by value
+            _lib.check(_lib.lib.die_init_batch_seeds(C.byref(m), C.byref(a), C.byref(b), float(self.dynamics.init_agent_ratio), words,
+                                                     self.R, C.byref(spec), _ptr(self._counts), _ptr(self._init_ws),
+                                                     self._init_ws.numel(), stream_ptr(self.device)), 'die_init_batch_seeds')
+            self.seeds = seeds
+            return
         _lib.check(_lib.lib.die_init_batch(C.byref(m), C.byref(a), C.byref(b), float(self.dynamics.init_agent_ratio), seed & mask,
                                            seed_stride & mask, C.byref(spec), _ptr(self._counts), _ptr(self._init_ws),
                                            self._init_ws.numel(), stream_ptr(self.device)), 'die_init_batch')
@@ -377,6 +408,26 @@ class BatchedEnv:
         return medium, agents
 
 
+def episode_seeds(seed: int, candidates: int, episodes: int, candidate_stride: int = 0) -> List[int]:
+    """The R = candidates·episodes seeds of `BatchedEnv.reset(seeds=...)` in candidate-major order: replica c·E + e gets
+    seed + e + candidate_stride·c·E.  Stride 0: every candidate sees the same E worlds; stride 1: every replica its own."""
+    for name, v, low in (('candidates', candidates, 1), ('episodes', episodes, 1), ('candidate_stride', candidate_stride, 0)):
+        if isinstance(v, bool) or int(v) != v or int(v) < low:
+            raise ValueError(f'{name}={v!r}: an integer >= {low}')
+    seed, C_, E, stride = int(seed), int(candidates), int(episodes), int(candidate_stride)
+    return [seed + e + stride * c * E for c in range(C_) for e in range(E)]
+
+
+def _episodes(env, episodes) -> int:
+    """`episodes` of a population on `env`, checked: R = candidates·episodes replicas."""
+    if isinstance(episodes, bool) or not isinstance(episodes, int) or episodes < 1:
+        raise ValueError(f'episodes={episodes!r}: an integer >= 1 (worlds per candidate)')
+    if env.R % episodes:
+        raise ValueError(f'episodes={episodes}: the BatchedEnv holds {env.R} replicas, not a multiple of {episodes} — replica c·E + e is '
+                         'candidate c on its e-th world')
+    return episodes
+
+
 def _env_snapshot(e: Env) -> dict:
     """Device copies of what a step of a stand-alone Env changes (its medium planes and agent arrays), and the host words
     that describe them."""
@@ -511,6 +562,11 @@ class BatchedPhysarumPopulation:
     normalized_grad and grad_clip are shared (they choose the kernel), as a NeuralAutomataAgent population shares its
     architecture.
 
+    `episodes=E`: C = R / E candidates (`candidates`), candidate c stepping the E replicas c·E … c·E + E − 1, each the
+    stand-alone Env of seeds[c·E + e] driven by `PhysarumAgent(max_agents=K_r, seed=seed + r, **row c)` — the headings stay per
+    replica.  `parameters`, `set_values`, `set_parameters` and `values()` are then (C, 6); `table()` keeps R rows (row r = row
+    r // E of the decode, written by the one decode launch).  Read "(R, 6)" below as "(C, 6)".
+
     `parameters` is ONE (R, 6) float32 device tensor, columns in PARAMETER_NAMES order:
       * natural mode (`values=`, default: every row the reference's defaults): a row holds the constructor arguments
         themselves (angles in degrees).  Checked on the host here and in `set_values`;
@@ -535,7 +591,9 @@ class BatchedPhysarumPopulation:
     P = 6
 
     def __init__(self, env: BatchedEnv, values=None, *, parameters=None, space: Optional[ParameterSpace] = None,
-                 normalized_grad: bool = True, grad_clip: Optional[float] = 1e-5, seed: int = 0):
+                 normalized_grad: bool = True, grad_clip: Optional[float] = 1e-5, seed: int = 0, episodes: int = 1):
+        self.episodes = _episodes(env, episodes)
+        self.candidates = env.R // self.episodes
         if values is not None and parameters is not None:
             raise ValueError('values= (natural rows) or parameters= (unit rows with a space), not both')
         self.natural = parameters is None
@@ -548,14 +606,14 @@ class BatchedPhysarumPopulation:
         self.env, self.R, self.seed, self.space = env, env.R, int(seed), space
         self.normalized_grad, self.grad_clip = bool(normalized_grad), grad_clip
         dev = env.device
-        self.parameters = torch.empty((self.R, self.P), dtype=torch.float32, device=dev)
+        self.parameters = torch.empty((self.candidates, self.P), dtype=torch.float32, device=dev)
         self._table = torch.zeros(self.R * C.sizeof(_lib.PhysarumRow), dtype=torch.uint8, device=dev)
-        self._values = torch.zeros((self.R, self.P), dtype=torch.float32, device=dev)
+        self._values = torch.zeros((self.candidates, self.P), dtype=torch.float32, device=dev)
         self._space_struct = None if space is None else space._struct()
         self._seen = None                           # (`parameters`' address, its torch version counter) at the last decode
         self._calls = 0
         if self.natural:
-            rows = np.tile(np.float32(PHYSARUM_DEFAULTS), (self.R, 1)) if values is None else values
+            rows = np.tile(np.float32(PHYSARUM_DEFAULTS), (self.candidates, 1)) if values is None else values
             self.parameters.copy_(self._natural_rows(rows))
         else:
             self.parameters.copy_(self._rows(parameters, 'parameters'))
@@ -567,13 +625,14 @@ class BatchedPhysarumPopulation:
     # ------------------------------------------------------------------ parameters
     def _rows(self, rows, what: str) -> torch.Tensor:
         t = torch.as_tensor(rows).detach().to(torch.float32)
-        if tuple(t.shape) != (self.R, self.P):
-            raise ValueError(f'{what} of shape {tuple(t.shape)}: ({self.R}, {self.P}) expected (R replicas x {PARAMETER_NAMES})')
+        if tuple(t.shape) != (self.candidates, self.P):
+            rows_are = 'R replicas' if self.episodes == 1 else f'{self.candidates} candidates of {self.episodes} episodes each'
+            raise ValueError(f'{what} of shape {tuple(t.shape)}: ({self.candidates}, {self.P}) expected ({rows_are} x {PARAMETER_NAMES})')
         return t
 
     def _natural_rows(self, rows) -> torch.Tensor:
         t = self._rows(rows, 'values')
-        _check_physarum_values(t.cpu().numpy(), range(self.R))
+        _check_physarum_values(t.cpu().numpy(), range(self.candidates))
         return t
 
     def set_values(self, values) -> None:
@@ -594,10 +653,14 @@ class BatchedPhysarumPopulation:
         """`parameters` -> the table and the decoded values.  One launch, no host read."""
         self._check_parameters()
         mode = _lib.DIE_PHYSARUM_NATURAL if self.natural else _lib.DIE_PHYSARUM_UNIT
-        _lib.check(_lib.lib.die_physarum_decode_batch(_ptr(self.parameters), self.R, mode,
-                                                      None if self._space_struct is None else C.byref(self._space_struct),
-                                                      _ptr(self._table), _ptr(self._values), stream_ptr(self.env.device)),
-                   'die_physarum_decode_batch')
+        space = None if self._space_struct is None else C.byref(self._space_struct)
+        if self.episodes == 1:
+            _lib.check(_lib.lib.die_physarum_decode_batch(_ptr(self.parameters), self.R, mode, space, _ptr(self._table),
+                                                          _ptr(self._values), stream_ptr(self.env.device)), 'die_physarum_decode_batch')
+        else:                                       # C rows in, the R-row table out: row c·E + e is candidate c's
+            _lib.check(_lib.lib.die_physarum_decode_episodes(_ptr(self.parameters), self.candidates, self.episodes, mode, space,
+                                                             _ptr(self._table), _ptr(self._values), stream_ptr(self.env.device)),
+                       'die_physarum_decode_episodes')
         self._seen = (self.parameters.data_ptr(), self.parameters._version)
 
     def _sync(self) -> None:
@@ -621,8 +684,13 @@ class BatchedPhysarumPopulation:
                              sense_angle=float(v[4]), turn_tolerance=float(v[5]), seed=seed)
 
     def candidate(self, r: int):
-        """Candidate r as a stand-alone PhysarumAgent(max_agents=K_r, seed=seed + r, **decoded row r)."""
-        return self._agent(self.values()[r], self.env.n[r], self.seed + r)
+        """Candidate r as a stand-alone PhysarumAgent(max_agents=K_r, seed=seed + r, **decoded row r) (with episodes: the
+        agent of its first replica, r·E)."""
+        return self._agent(self.values()[r], self.env.n[r * self.episodes], self.seed + r * self.episodes)
+
+    def replica_agent(self, r: int):
+        """The stand-alone PhysarumAgent replica r steps as: PhysarumAgent(max_agents=K_r, seed=seed + r, **decoded row r // E)."""
+        return self._agent(self.values()[r // self.episodes], self.env.n[r], self.seed + r)
 
     def agent_from_row(self, row, max_agents: int = 10 ** 6, seed: Optional[int] = None):
         """A stand-alone PhysarumAgent from one row of this population's kind (a searcher's best / centre), decoded on the
@@ -641,7 +709,7 @@ class BatchedPhysarumPopulation:
         self.decode()
         if self.env.per_replica:
             v = self.values()
-            self.agents = [self._agent(v[r], self.env.n[r], self.seed + r) for r in range(self.R)]
+            self.agents = [self._agent(v[r // self.episodes], self.env.n[r], self.seed + r) for r in range(self.R)]
             return
         env = self.env
         b = _lib.Batch(env.R, 0, env.W * env.H, env.Nmax, 1, (C.c_int64 * 64)(*env.n))
@@ -651,8 +719,8 @@ class BatchedPhysarumPopulation:
 
     def _check_parameters(self):
         p = self.parameters
-        if tuple(p.shape) != (self.R, self.P) or p.dtype != torch.float32 or p.device != self.env.device or not p.is_contiguous():
-            raise ValueError(f'parameters must stay a contiguous ({self.R}, {self.P}) float32 tensor on {self.env.device}')
+        if tuple(p.shape) != (self.candidates, self.P) or p.dtype != torch.float32 or p.device != self.env.device or not p.is_contiguous():
+            raise ValueError(f'parameters must stay a contiguous ({self.candidates}, {self.P}) float32 tensor on {self.env.device}')
 
     def _check_step(self, env: BatchedEnv):
         if env is not self.env:
@@ -684,11 +752,17 @@ class BatchedNeuralAutomataAgent:
     """A population of R NeuralAutomataAgent candidates of one architecture, candidate r stepping replica r of a BatchedEnv.
     The weights are ONE (R, P) float32 device tensor `parameters`: row r is `parameters_to_vector(model.parameters())` of
     candidate r — the layout evolution strategies hand around.  In-place writes to `parameters` are seen by the next step.
-    (No `reset()` method here, deliberately: the searchers call a population's `reset()` every generation when it has one.)"""
+    (No `reset()` method here, deliberately: the searchers call a population's `reset()` every generation when it has one.)
 
-    def __init__(self, env: BatchedEnv, template: NeuralAutomataAgent, parameters=None):
+    `episodes=E`: C = R / E candidates (`candidates`), candidate c stepping the E replicas c·E … c·E + E − 1 — replica c·E + e is
+    `Env(field_size, dynamics, seed=env.seeds[c·E + e], max_agents=...)` driven by the agent of row c, bit for bit.  `parameters`
+    is then ONE (C, P) matrix: the conv launches read row r / E (die_nca_batch.episodes), nothing is copied or expanded."""
+
+    def __init__(self, env: BatchedEnv, template: NeuralAutomataAgent, parameters=None, episodes: int = 1):
         if not isinstance(template, NeuralAutomataAgent):
             raise TypeError('template: a NeuralAutomataAgent')
+        self.episodes = _episodes(env, episodes)
+        self.candidates = env.R // self.episodes
         self.env, self.template, self.R = env, template, env.R
         self._arch = _architecture(template)
         layers = template.model.conv_layers()
@@ -705,27 +779,30 @@ class BatchedNeuralAutomataAgent:
             off += k.weight.numel()
         self.P = off
         if parameters is None:
-            parameters = parameters_to_vector(template.model.parameters()).detach().reshape(1, -1).expand(self.R, -1)
-        self.parameters = torch.empty((self.R, self.P), dtype=torch.float32, device=env.device)
+            parameters = parameters_to_vector(template.model.parameters()).detach().reshape(1, -1).expand(self.candidates, -1)
+        t = torch.as_tensor(parameters)
+        if tuple(t.shape) != (self.candidates, self.P):           # (before anything is allocated)
+            raise ValueError(self._shape_error(t))
+        self.parameters = torch.empty((self.candidates, self.P), dtype=torch.float32, device=env.device)
         self.set_parameters(parameters)
         self._calls = 0
         self._c = None                              # (parameters' address, NcaLayer array, NcaBatch) of the last step
         if env.per_replica:
-            self.agents = [self.unpack(template, self.parameters[r]) for r in range(self.R)]
+            self.agents = [self.unpack(template, self.parameters[r // self.episodes]) for r in range(self.R)]
             return
         self._scratch = torch.empty(int(_lib.lib.die_nca_batch_scratch_bytes(env.W, env.H, self.R, len(layers))) // 4,
                                     dtype=torch.float32, device=env.device)
 
     @classmethod
-    def from_agents(cls, env: BatchedEnv, agents: Sequence[NeuralAutomataAgent]) -> 'BatchedNeuralAutomataAgent':
+    def from_agents(cls, env: BatchedEnv, agents: Sequence[NeuralAutomataAgent], episodes: int = 1) -> 'BatchedNeuralAutomataAgent':
         """Candidate r = agents[r]; every agent must share agents[0]'s architecture."""
-        if len(agents) != env.R:
-            raise ValueError(f'{len(agents)} agents for {env.R} replicas')
+        if len(agents) * _episodes(env, episodes) != env.R:
+            raise ValueError(f'{len(agents)} agents for {env.R} replicas' + (f' of {episodes} episodes per candidate' if episodes != 1 else ''))
         want = _architecture(agents[0])
         for r, ag in enumerate(agents):
             if _architecture(ag) != want:
                 raise ValueError(f'agent {r}: architecture {_architecture(ag)} differs from agent 0\'s {want}')
-        return cls(env, agents[0], cls.pack(agents))
+        return cls(env, agents[0], cls.pack(agents), episodes)
 
     # ------------------------------------------------------------------ parameters
     @staticmethod
@@ -746,19 +823,23 @@ class BatchedNeuralAutomataAgent:
         return ag
 
     def set_parameters(self, parameters) -> None:
-        """Copy an (R, P) matrix of candidate rows in."""
+        """Copy an (R, P) matrix of candidate rows in ((C, P) with episodes: one row per candidate)."""
         t = torch.as_tensor(parameters)
-        if tuple(t.shape) != (self.R, self.P):
-            raise ValueError(f'parameters of shape {tuple(t.shape)}: ({self.R}, {self.P}) expected (R replicas x P weights)')
+        if tuple(t.shape) != (self.candidates, self.P):
+            raise ValueError(self._shape_error(t))
         self.parameters.copy_(t.detach())
+
+    def _shape_error(self, t: torch.Tensor) -> str:
+        rows_are = 'R replicas' if self.episodes == 1 else f'{self.candidates} candidates of {self.episodes} episodes each'
+        return f'parameters of shape {tuple(t.shape)}: ({self.candidates}, {self.P}) expected ({rows_are} x P weights)'
 
     def candidate(self, r: int) -> NeuralAutomataAgent:
         """Candidate r as a stand-alone NeuralAutomataAgent (on the host: `save()` the winner)."""
         return self.unpack(self.template, self.parameters[r].cpu())
 
     def _replica_agent(self, r: int) -> NeuralAutomataAgent:
-        ag = self.agents[r]                         # row r is reloaded every step: in-place writes are seen
-        vector_to_parameters(self.parameters[r].detach(), ag.model.parameters())
+        ag = self.agents[r]                         # its candidate's row is reloaded every step: in-place writes are seen
+        vector_to_parameters(self.parameters[r // self.episodes].detach(), ag.model.parameters())
         return ag
 
     # ------------------------------------------------------------------ step
@@ -766,8 +847,8 @@ class BatchedNeuralAutomataAgent:
         if env is not self.env:
             raise ValueError('this population was built for another BatchedEnv')
         p = self.parameters
-        if tuple(p.shape) != (self.R, self.P) or p.dtype != torch.float32 or p.device != env.device or not p.is_contiguous():
-            raise ValueError(f'parameters must stay a contiguous ({self.R}, {self.P}) float32 tensor on {env.device}')
+        if tuple(p.shape) != (self.candidates, self.P) or p.dtype != torch.float32 or p.device != env.device or not p.is_contiguous():
+            raise ValueError(f'parameters must stay a contiguous ({self.candidates}, {self.P}) float32 tensor on {env.device}')
         model = self.template.model
         if model.agent_dropout.p > 0 and model.training:
             raise NotImplementedError('p_agent_dropout > 0 in training mode: its mask is a host-RNG torch op, not batched '
@@ -779,7 +860,8 @@ class BatchedNeuralAutomataAgent:
             layers = (_lib.NcaLayer * len(self._layers))(*[_lib.NcaLayer(k, cin, cout, 0, base + 4 * off, self.P)
                                                             for k, cin, cout, off in self._layers])
             nca = _lib.NcaBatch(len(self._layers), _lib.PAD_MODES[self._arch['boundary'][0]], int(self._arch['with_agent_channel']), 0,
-                                layers, (C.c_float * 3)(*self.template.action_coefs), 0, _ptr(self._scratch),
+                                layers, (C.c_float * 3)(*self.template.action_coefs), 0 if self.episodes == 1 else self.episodes,
+                                _ptr(self._scratch),
                                 self._scratch.numel() * 4)
             self._c = (base, layers, nca)
         nca = self._c[2]

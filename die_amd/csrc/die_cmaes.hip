@@ -301,3 +301,22 @@ extern "C" int die_cmaes_update(const die_cmaes* s, const float* params, const d
     DIE_CHECK_LAUNCH(who);
     return DIE_OK;
 }
+
+extern "C" int die_cmaes_update_episodes(const die_cmaes* s, const float* params, const double* terms, int64_t T, int64_t stride_t,
+                                         int64_t stride_r, int32_t episodes, double* episode_fitness, double* folded,
+                                         int64_t generation, void* stream) {
+    const char* who = "die_cmaes_update_episodes";
+    CmaesArgs a;
+    int rc = cmaes_args(a, s, generation, who);
+    if (rc != DIE_OK) return rc;
+    DIE_REQUIRE(params && terms, "%s: null parameter matrix or terms", who);
+    DIE_REQUIRE(T >= 1, "%s: T %lld: at least one term per replica", who, (long long)T);
+    DIE_REQUIRE(stride_t > 0 && stride_r > 0, "%s: strides (%lld, %lld) must be positive", who, (long long)stride_t, (long long)stride_r);
+    DIE_REQUIRE(generation < s->history_rows, "%s: generation %lld beyond the %lld history rows", who, (long long)generation,
+                (long long)s->history_rows);
+    rc = die_episode_fold_check(s->replicas, episodes, episode_fitness, folded, who);
+    if (rc != DIE_OK) return rc;
+    rc = die_episode_fold_launch(terms, T, stride_t, stride_r, s->replicas, episodes, episode_fitness, folded, stream, who);
+    if (rc != DIE_OK) return rc;
+    return die_cmaes_update(s, params, folded, 1, 1, 1, generation, stream);      // f_c is the candidate's one term
+}

@@ -287,14 +287,15 @@ extern "C" int die_physarum_heading_batch(uint32_t* heading_hi, uint32_t* headin
     return DIE_OK;
 }
 
-// ---- the worlds of every replica of a die_batch (BatchedEnv.reset(seed=...)) ------------------------------------------
-// Replica r (blockIdx.y) is die_init_medium + die_init_agents of seed + r·world_stride on its own planes and agent arrays:
+// ---- the worlds of every replica of a die_batch (BatchedEnv.reset(seed=...) / reset(seeds=...)) ------------------------
+// Replica r (blockIdx.y) is die_init_medium + die_init_agents of seed[r] on its own planes and agent arrays (die_init_batch:
+// seed + r·world_stride, worked out on the host; die_init_batch_seeds: the caller's list, passed by value):
 // the kernels below restate k_init_medium / k_count / k_scan_blocks / k_scatter / k_zero_tail with the replica's offsets
 // (a replica's plane is a whole world: no tile offsets), so every value is computed by the same expressions.  The scan
 // workspace of replica r is its own die_ws_scan_bytes slice.
 struct InitBatchArgs {
     int64_t cells, agents;          // strides: cells per plane, agent slots per replica
-    uint64_t world_stride;
+    uint64_t seed[DIE_MAX_REPLICAS];    // the world of every replica
     int64_t ws_stride;              // bytes of scan workspace per replica
     int64_t nb;                     // scan tiles per plane
     int64_t n[DIE_MAX_REPLICAS];    // slots of every replica
@@ -302,9 +303,9 @@ struct InitBatchArgs {
 
 template <typename T>
 __global__ __launch_bounds__(DIE_BLOCK) void k_init_medium_batch(die_geo g, uint64_t* owner, T* food, T* chem, double ratio,
-                                                                 uint64_t seed, FoodArgs fa, InitBatchArgs b) {
+                                                                 FoodArgs fa, InitBatchArgs b) {
     const int r = blockIdx.y;
-    const uint64_t sr = seed + (uint64_t)r * b.world_stride;
+    const uint64_t sr = b.seed[r];
     owner += b.cells * r; food += b.cells * r; chem += b.cells * r;
     const int H = g.H;
     const int64_t C = (int64_t)g.W * H;
@@ -364,9 +365,9 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_scan_blocks_batch(char* ws, int64
 }
 
 __global__ __launch_bounds__(DIE_BLOCK) void k_scatter_batch(die_geo g, uint64_t* owner, const char* ws, uint32_t* x, uint32_t* y,
-                                                             uint8_t* alive, float* agent_food, uint64_t seed, InitBatchArgs b) {
+                                                             uint8_t* alive, float* agent_food, InitBatchArgs b) {
     const int r = blockIdx.y;
-    const uint64_t sr = seed + (uint64_t)r * b.world_stride;
+    const uint64_t sr = b.seed[r];
     const int64_t pa = b.agents * r;
     owner += b.cells * r;
     x += pa; y += pa; alive += pa; agent_food += pa;
@@ -431,10 +432,10 @@ extern "C" int64_t die_init_batch_workspace_bytes(int32_t W, int32_t H, int32_t 
     return (int64_t)replicas * die_ws_scan_bytes(W, H);
 }
 
-extern "C" int die_init_batch(const die_medium* m, const die_agents* a, const die_batch* b, double agent_ratio, uint64_t seed,
-                              uint64_t world_stride, const die_food_spec* food, int64_t* counts_dev, void* ws, int64_t ws_bytes,
-                              void* stream) {
-    const char* who = "die_init_batch";
+// both entry points: `seeds` is NULL for die_init_batch (seed + r·world_stride), else the n_seeds worlds of die_init_batch_seeds
+static int init_batch(const char* who, const die_medium* m, const die_agents* a, const die_batch* b, double agent_ratio, uint64_t seed,
+                      uint64_t world_stride, const uint64_t* seeds, int32_t n_seeds, const die_food_spec* food, int64_t* counts_dev,
+                      void* ws, int64_t ws_bytes, void* stream) {
     DIE_REQUIRE(m && a && b && food && counts_dev && ws, "%s: null argument", who);
     DIE_REQUIRE(m->W >= 1 && m->H >= 1 && m->owner && m->food && m->chem, "%s: bad medium", who);
     DIE_REQUIRE(m->gW <= 0, "%s: a replica's plane is a whole world, not a tile", who);
@@ -452,6 +453,12 @@ extern "C" int die_init_batch(const die_medium* m, const die_agents* a, const di
     // the sinusoid mix is drawn from the seed on the host: one spec is the food of one seed only
     DIE_REQUIRE(food->perlin_octaves > 0 || world_stride == 0, "%s: a wave-mix food spec (perlin_octaves 0) with world_stride %llu: "
                 "its waves belong to one seed", who, (unsigned long long)world_stride);
+    if (seeds) {
+        DIE_REQUIRE(n_seeds == b->replicas, "%s: %d seeds for %d replicas", who, n_seeds, b->replicas);
+        for (int r = 1; r < n_seeds; ++r)
+            DIE_REQUIRE(food->perlin_octaves > 0 || seeds[r] == seeds[0], "%s: a wave-mix food spec (perlin_octaves 0) with differing "
+                        "seeds (replica %d): its waves belong to one seed", who, r);
+    }
     const int64_t need = die_init_batch_workspace_bytes(m->W, m->H, b->replicas);
     DIE_REQUIRE(need > 0, "%s: field too large", who);
     DIE_REQUIRE(ws_bytes >= need, "%s: workspace too small (%lld < %lld: die_init_batch_workspace_bytes)", who, (long long)ws_bytes,
@@ -464,7 +471,9 @@ extern "C" int die_init_batch(const die_medium* m, const die_agents* a, const di
     for (int i = 0; i < 8; ++i) { fa.fx[i] = food->fx[i]; fa.fy[i] = food->fy[i]; fa.phase[i] = food->phase[i]; fa.amp[i] = food->amp[i]; }
     const int64_t C = (int64_t)m->W * m->H;
     InitBatchArgs ib;
-    ib.cells = b->plane_stride; ib.agents = b->agent_stride; ib.world_stride = world_stride;
+    ib.cells = b->plane_stride; ib.agents = b->agent_stride;
+    for (int r = 0; r < DIE_MAX_REPLICAS; ++r)
+        ib.seed[r] = r >= b->replicas ? 0 : seeds ? seeds[r] : seed + (uint64_t)r * world_stride;
     ib.ws_stride = die_ws_scan_bytes(m->W, m->H);
     ib.nb = (C + SCAN_TILE - 1) / SCAN_TILE;
     int64_t nmax = 0;
@@ -478,15 +487,31 @@ extern "C" int die_init_batch(const die_medium* m, const die_agents* a, const di
     char* w = (char*)ws;
     const dim3 cells(init_grid(C), R), tiles((unsigned)ib.nb, R), slots(init_grid(nmax), R);
     if (m->dtype == DIE_F32)
-        k_init_medium_batch<float><<<cells, DIE_BLOCK, 0, s>>>(g, m->owner, (float*)m->food, (float*)m->chem, agent_ratio, seed, fa, ib);
+        k_init_medium_batch<float><<<cells, DIE_BLOCK, 0, s>>>(g, m->owner, (float*)m->food, (float*)m->chem, agent_ratio, fa, ib);
     else
-        k_init_medium_batch<__half><<<cells, DIE_BLOCK, 0, s>>>(g, m->owner, (__half*)m->food, (__half*)m->chem, agent_ratio, seed, fa, ib);
+        k_init_medium_batch<__half><<<cells, DIE_BLOCK, 0, s>>>(g, m->owner, (__half*)m->food, (__half*)m->chem, agent_ratio, fa, ib);
     k_count_batch<<<tiles, DIE_BLOCK, 0, s>>>(m->owner, C, w, ib);
     k_scan_blocks_batch<<<dim3(1, R), DIE_BLOCK, 0, s>>>(w, counts_dev, ib);
-    k_scatter_batch<<<tiles, DIE_BLOCK, 0, s>>>(g, m->owner, w, a->x, a->y, a->alive, a->agent_food, seed, ib);
+    k_scatter_batch<<<tiles, DIE_BLOCK, 0, s>>>(g, m->owner, w, a->x, a->y, a->alive, a->agent_food, ib);
     k_zero_tail_batch<<<slots, DIE_BLOCK, 0, s>>>(counts_dev, a->x, a->y, a->alive, a->agent_food, ib);
     DIE_CHECK_LAUNCH(who);
     return DIE_OK;
+}
+
+extern "C" int die_init_batch(const die_medium* m, const die_agents* a, const die_batch* b, double agent_ratio, uint64_t seed,
+                              uint64_t world_stride, const die_food_spec* food, int64_t* counts_dev, void* ws, int64_t ws_bytes,
+                              void* stream) {
+    return init_batch("die_init_batch", m, a, b, agent_ratio, seed, world_stride, nullptr, 0, food, counts_dev, ws, ws_bytes, stream);
+}
+
+extern "C" int die_init_batch_seeds(const die_medium* m, const die_agents* a, const die_batch* b, double agent_ratio,
+                                    const uint64_t* seeds, int32_t n_seeds, const die_food_spec* food, int64_t* counts_dev, void* ws,
+                                    int64_t ws_bytes, void* stream) {
+    const char* who = "die_init_batch_seeds";
+    DIE_REQUIRE(seeds, "%s: null seed list", who);
+    DIE_REQUIRE(n_seeds >= 1 && n_seeds <= DIE_MAX_REPLICAS, "%s: %d seeds, 1..%d expected (one per replica)", who, n_seeds,
+                DIE_MAX_REPLICAS);
+    return init_batch(who, m, a, b, agent_ratio, 0, 0, seeds, n_seeds, food, counts_dev, ws, ws_bytes, stream);
 }
 
 // ---- food flow: WaveSequence.get_flow_operator (core/data_init.py:29-38,71-89) --------------------------------

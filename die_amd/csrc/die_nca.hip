@@ -31,6 +31,7 @@ struct ConvArgs {
     int W, H, cin, cout, k, epoch, apply_tanh;
     int pad;                     // die_pad_mode: how cells beyond the field are read ('same' padding of torch's Conv2d)
     int64_t rep_in, rep_w, rep_out;  // batch (gridDim.z = replicas): elements from replica r's planes / weights to r + 1's
+    int episodes;                // batch: replica r reads weight row r / episodes (1: a row per replica)
 };
 
 // index of the cell that stands in for coordinate v of an axis of n cells, or −1 for "reads as zero" (torch.nn.functional.pad:
@@ -53,7 +54,8 @@ __device__ __forceinline__ float nca_load(const void* p, int kind, int64_t i, in
 }
 
 // BATCH: replica blockIdx.z of die_nca_env_step_batch — its input planes, weights and output planes lie blockIdx.z strides
-// on; everything else (tile, LDS, summation order, tanh) is this one body.
+// on; everything else (tile, LDS, summation order, tanh) is this one body.  With episodes E > 1 (a candidate evaluated on E
+// worlds) the E replicas of a candidate share one weight row: row r / E, uniform over the workgroup (one scalar division).
 template <int K, bool BATCH = false>
 __global__ __launch_bounds__(DIE_BLOCK) void k_conv_circular(ConvArgs a) {
     constexpr int R = K / 2, LX = NCA_TX + 2 * R, LY = NCA_TY + 2 * R + 1;     // odd pitch: conflict-free column walks
@@ -62,7 +64,8 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_circular(ConvArgs a) {
     float* s_w = nca_smem + a.cin * LX * LY;                 // [cout][cin][K][K]
     const int x0 = blockIdx.y * NCA_TX, y0 = blockIdx.x * NCA_TY;
     const int64_t rep = BATCH ? (int64_t)blockIdx.z : 0;
-    const float* w = a.w + rep * a.rep_w;
+    const int64_t row = (BATCH && a.episodes > 1) ? (int64_t)((int)blockIdx.z / a.episodes) : rep;
+    const float* w = a.w + row * a.rep_w;
     const int nw = a.cout * a.cin * K * K;
     for (int i = threadIdx.x; i < nw; i += DIE_BLOCK) s_w[i] = w[i];
     constexpr int LYV = NCA_TY + 2 * R;
@@ -163,6 +166,7 @@ extern "C" int die_conv2d(int32_t W, int32_t H, int32_t cin, const die_conv_plan
     }
     a.w = weights; a.W = W; a.H = H; a.cin = cin; a.cout = cout; a.k = k; a.epoch = epoch; a.apply_tanh = apply_tanh; a.pad = padding_mode;
     a.rep_in = a.rep_w = a.rep_out = 0;
+    a.episodes = 1;
     launch_conv<false>(a, 1, (hipStream_t)stream);
     DIE_CHECK_LAUNCH("die_conv2d_circular");
     return DIE_OK;
@@ -216,6 +220,8 @@ int die_nca_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t 
     DIE_REQUIRE(nca->n_layers >= 1 && nca->n_layers <= DIE_NCA_MAX_LAYERS, "%s: 1..%d layers (got %d)", who, DIE_NCA_MAX_LAYERS, nca->n_layers);
     DIE_REQUIRE(nca->padding_mode >= DIE_PAD_CIRCULAR && nca->padding_mode <= DIE_PAD_REPLICATE, "%s: bad padding mode %d", who, nca->padding_mode);
     DIE_REQUIRE(nca->with_agent_channel == 0 || nca->with_agent_channel == 1, "%s: with_agent_channel is 0 or 1", who);
+    DIE_REQUIRE(nca->episodes >= 0 && replicas % (nca->episodes > 1 ? nca->episodes : 1) == 0, "%s: episodes %d: at least 1 (0 reads as 1) "
+                "and a divisor of the %d replicas", who, nca->episodes, replicas);
     const int64_t need = die_nca_batch_scratch_bytes(W, H, replicas, nca->n_layers);
     DIE_REQUIRE(need > 0 && nca->scratch_bytes >= need, "%s: scratch too small (%lld < %lld)", who, (long long)nca->scratch_bytes, (long long)need);
     int cin = 2 + nca->with_agent_channel;
@@ -249,6 +255,7 @@ int die_nca_sense_batch(const die_medium* m, const die_batch* b, const die_nca_b
     a.in[c] = m->chem; a.kind[c++] = fkind;
     a.rep_in = b->plane_stride;
     a.W = m->W; a.H = m->H; a.epoch = nca->sense_epoch; a.pad = nca->padding_mode;
+    a.episodes = nca->episodes > 1 ? nca->episodes : 1;
     float* out = nullptr;
     for (int l = 0; l < nca->n_layers; ++l) {
         const die_nca_layer& L = nca->layers[l];

@@ -4,7 +4,8 @@
 //   k_physarum_decode  one thread per replica: the six values (natural, or lo + (hi - lo)·clamp(u, 0, 1) in fp32), degrees to
 //                      radians, and what die_fill_fwd_args (die_agents.hip) derives on the host for a stand-alone agent:
 //                      atol = turn·rtol, x_turn (its bisection over the bit patterns of the doubles, restated), cos(x_turn),
-//                      cos(sense).
+//                      cos(sense).  With episodes E > 1 (die_physarum_decode_episodes) replica r decodes row r / E — the E
+//                      replicas of a candidate get the same table row — and the first of them writes the candidate's values.
 // One wave, a few hundred float64 operations: the launch is its whole cost.  tests/physarum_pop_model.py is its numpy twin.
 #include "die_common.h"
 #include <math.h>
@@ -13,6 +14,7 @@ namespace {
 
 struct DecodeArgs {
     int R, unit;
+    int E;                       // episodes: replica r decodes row r / E (1: a row per replica)
     die_parameter_space s;
 };
 
@@ -41,9 +43,11 @@ __global__ __launch_bounds__(DIE_WAVE) void k_physarum_decode(DecodeArgs a, cons
                                                               float* values) {
     const int r = threadIdx.x;
     if (r >= a.R) return;
+    const int c = r / a.E;
+    const bool first = r == c * a.E;
     float v[DIE_PHYSARUM_PARAMS];
     for (int j = 0; j < DIE_PHYSARUM_PARAMS; ++j) {
-        const float u = rows[r * DIE_PHYSARUM_PARAMS + j];
+        const float u = rows[c * DIE_PHYSARUM_PARAMS + j];
         if (a.unit) {
             // (one operation per statement: -ffp-contract=on must not fuse the product into the sum — the model rounds each)
             const float c = fminf(fmaxf(u, 0.f), 1.f);        // (fmaxf(NaN, 0) = 0)
@@ -53,7 +57,7 @@ __global__ __launch_bounds__(DIE_WAVE) void k_physarum_decode(DecodeArgs a, cons
         } else {
             v[j] = u;
         }
-        values[r * DIE_PHYSARUM_PARAMS + j] = v[j];
+        if (first) values[c * DIE_PHYSARUM_PARAMS + j] = v[j];
     }
     const double deg = 3.141592653589793 / 180.0;             // math.radians' constant
     die_physarum_row o;
@@ -74,14 +78,11 @@ __global__ __launch_bounds__(DIE_WAVE) void k_physarum_decode(DecodeArgs a, cons
 
 static_assert(sizeof(die_physarum_row) == 64, "die_physarum_row: one 64-byte scalar load");
 
-extern "C" int die_physarum_decode_batch(const float* rows, int32_t replicas, int32_t mode, const die_parameter_space* space,
-                                         die_physarum_row* table, float* values, void* stream) {
-    const char* who = "die_physarum_decode_batch";
-    DIE_REQUIRE(rows && table && values, "%s: null rows, table or values", who);
-    DIE_REQUIRE(replicas >= 1 && replicas <= DIE_MAX_REPLICAS, "%s: replicas %d: in 1..%d", who, replicas, DIE_MAX_REPLICAS);
+static int decode_rows(const char* who, const float* rows, int32_t replicas, int32_t episodes, int32_t mode,
+                       const die_parameter_space* space, die_physarum_row* table, float* values, void* stream) {
     DIE_REQUIRE(mode == DIE_PHYSARUM_NATURAL || mode == DIE_PHYSARUM_UNIT, "%s: mode %d: natural (0) or unit (1)", who, mode);
     DecodeArgs a{};
-    a.R = replicas; a.unit = mode == DIE_PHYSARUM_UNIT;
+    a.R = replicas; a.E = episodes; a.unit = mode == DIE_PHYSARUM_UNIT;
     if (a.unit) {
         DIE_REQUIRE(space, "%s: unit mode needs a parameter space", who);
         a.s = *space;
@@ -101,4 +102,22 @@ extern "C" int die_physarum_decode_batch(const float* rows, int32_t replicas, in
     k_physarum_decode<<<1, DIE_WAVE, 0, (hipStream_t)stream>>>(a, rows, table, values);
     DIE_CHECK_LAUNCH(who);
     return DIE_OK;
+}
+
+extern "C" int die_physarum_decode_batch(const float* rows, int32_t replicas, int32_t mode, const die_parameter_space* space,
+                                         die_physarum_row* table, float* values, void* stream) {
+    const char* who = "die_physarum_decode_batch";
+    DIE_REQUIRE(rows && table && values, "%s: null rows, table or values", who);
+    DIE_REQUIRE(replicas >= 1 && replicas <= DIE_MAX_REPLICAS, "%s: replicas %d: in 1..%d", who, replicas, DIE_MAX_REPLICAS);
+    return decode_rows(who, rows, replicas, 1, mode, space, table, values, stream);
+}
+
+extern "C" int die_physarum_decode_episodes(const float* rows, int32_t candidates, int32_t episodes, int32_t mode,
+                                            const die_parameter_space* space, die_physarum_row* table, float* values, void* stream) {
+    const char* who = "die_physarum_decode_episodes";
+    DIE_REQUIRE(rows && table && values, "%s: null rows, table or values", who);
+    DIE_REQUIRE(episodes >= 1, "%s: episodes %d: at least 1", who, episodes);
+    DIE_REQUIRE(candidates >= 1 && (int64_t)candidates * episodes <= DIE_MAX_REPLICAS, "%s: %d candidates x %d episodes: 1..%d replicas", who,
+                candidates, episodes, DIE_MAX_REPLICAS);
+    return decode_rows(who, rows, candidates * episodes, episodes, mode, space, table, values, stream);
 }

@@ -30,6 +30,13 @@ __device__ inline double die_search_normal(uint64_t seed, uint32_t generation, u
     return rad * cos(6.283185307179586 * u2);
 }
 
+// Episodes (a candidate evaluated on E worlds, replica c E + e its e-th): every check of the fold, then its one launch —
+// episode_fitness[c E + e] = F_{cE+e} (die_search_fitness of that replica), folded[c] = (((0 + F_{cE}) + F_{cE+1}) + …) / E.
+// die_search.hip; shared by die_pgpe_update_episodes and die_cmaes_update_episodes.
+int die_episode_fold_check(int32_t candidates, int32_t episodes, const double* episode_fitness, const double* folded, const char* who);
+int die_episode_fold_launch(const double* terms, int64_t T, int64_t stride_t, int64_t stride_r, int32_t candidates, int32_t episodes,
+                            double* episode_fitness, double* folded, void* stream, const char* who);
+
 // f_r = sum over t ascending of q[t * st], q = terms + r * sr: eight loads in flight, then the adds in t order
 __device__ inline double die_search_fitness(const double* q, int64_t T, int64_t st) {
     double s = 0.0, v[8];

@@ -10,6 +10,9 @@
 //   k_pgpe_step     every workgroup reduces the partials of g_mu^2 itself (same tree, same bits in all of them), then the
 //                   Adam step, or ClipUp's velocity before the clip (and the partials of its square).
 //   k_pgpe_clip     ClipUp only: every workgroup reduces |v|^2, clips, moves the centre.
+//   k_episode_fold  one wave, ahead of k_pgpe_rank / k_cmaes_rank when a candidate is evaluated on E worlds: thread r sums
+//                   replica r's terms (the per-episode fitness), thread c then averages candidate c's E sums in episode order.
+//                   The rank kernel reads the C averages as one term each.
 // Workgroups: min(ceil(P / 256), DIE_PGPE_MAX_BLOCKS), a function of P only, so every reduction has one fixed tree — a
 // wave's xor butterfly, the four waves in order, the workgroups' partials by the same block sum.  No float atomics.
 //
@@ -194,6 +197,23 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_pgpe_clip(PgpeArgs a) {
     }
 }
 
+__global__ __launch_bounds__(DIE_WAVE) void k_episode_fold(const double* terms, int64_t T, int64_t st, int64_t sr, int C, int E,
+                                                           double* episode_fitness, double* folded) {
+    __shared__ double F[DIE_MAX_REPLICAS];
+    const int r = threadIdx.x;
+    if (r < C * E) {
+        const double f = die_search_fitness(terms + r * sr, T, st);
+        F[r] = f;
+        episode_fitness[r] = f;
+    }
+    __syncthreads();
+    if (r < C) {
+        double s = 0.0;
+        for (int e = 0; e < E; ++e) s += F[r * E + e];
+        folded[r] = s / (double)E;
+    }
+}
+
 // every refusal of both entry points, before any launch
 int pgpe_args(PgpeArgs& a, const die_pgpe* s, int64_t generation, const char* who) {
     DIE_REQUIRE(s, "%s: null state", who);
@@ -231,6 +251,22 @@ int pgpe_args(PgpeArgs& a, const die_pgpe* s, int64_t generation, const char* wh
 }
 
 }  // namespace
+
+int die_episode_fold_check(int32_t candidates, int32_t episodes, const double* episode_fitness, const double* folded, const char* who) {
+    DIE_REQUIRE(episodes >= 1, "%s: episodes %d: at least 1", who, episodes);
+    DIE_REQUIRE(candidates >= 1 && (int64_t)candidates * episodes <= DIE_MAX_REPLICAS, "%s: %d candidates x %d episodes: at most %d replicas",
+                who, candidates, episodes, DIE_MAX_REPLICAS);
+    DIE_REQUIRE(episode_fitness && folded, "%s: null episode_fitness or folded buffer", who);
+    return DIE_OK;
+}
+
+int die_episode_fold_launch(const double* terms, int64_t T, int64_t stride_t, int64_t stride_r, int32_t candidates, int32_t episodes,
+                            double* episode_fitness, double* folded, void* stream, const char* who) {
+    static_assert(DIE_MAX_REPLICAS <= DIE_WAVE, "k_episode_fold: one thread per replica of one wave");
+    k_episode_fold<<<1, DIE_WAVE, 0, (hipStream_t)stream>>>(terms, T, stride_t, stride_r, candidates, episodes, episode_fitness, folded);
+    DIE_CHECK_LAUNCH(who);
+    return DIE_OK;
+}
 
 extern "C" int die_pgpe_sample(const die_pgpe* s, float* params, int64_t generation, void* stream) {
     const char* who = "die_pgpe_sample";
@@ -271,4 +307,23 @@ extern "C" int die_pgpe_update(const die_pgpe* s, const float* params, const dou
     k_pgpe_clip<<<a.nb, DIE_BLOCK, 0, st>>>(a);
     DIE_CHECK_LAUNCH(who);
     return DIE_OK;
+}
+
+extern "C" int die_pgpe_update_episodes(const die_pgpe* s, const float* params, const double* terms, int64_t T, int64_t stride_t,
+                                        int64_t stride_r, int32_t episodes, double* episode_fitness, double* folded,
+                                        int64_t generation, void* stream) {
+    const char* who = "die_pgpe_update_episodes";
+    PgpeArgs a;
+    int rc = pgpe_args(a, s, generation, who);
+    if (rc != DIE_OK) return rc;
+    DIE_REQUIRE(params && terms, "%s: null parameter matrix or terms", who);
+    DIE_REQUIRE(T >= 1, "%s: T %lld: at least one term per replica", who, (long long)T);
+    DIE_REQUIRE(stride_t > 0 && stride_r > 0, "%s: strides (%lld, %lld) must be positive", who, (long long)stride_t, (long long)stride_r);
+    DIE_REQUIRE(generation < s->history_rows, "%s: generation %lld beyond the %lld history rows", who, (long long)generation,
+                (long long)s->history_rows);
+    rc = die_episode_fold_check(s->replicas, episodes, episode_fitness, folded, who);
+    if (rc != DIE_OK) return rc;
+    rc = die_episode_fold_launch(terms, T, stride_t, stride_r, s->replicas, episodes, episode_fitness, folded, stream, who);
+    if (rc != DIE_OK) return rc;
+    return die_pgpe_update(s, params, folded, 1, 1, 1, generation, stream);       // f_c is the candidate's one term
 }

@@ -16,7 +16,11 @@ not bit-equal to evotorch's; the fitness is the plain sum of a candidate's T ter
 
 CMAES (die_cmaes_sample / die_cmaes_update, die_amd/csrc/die_cmaes.hip) is the reference's other searcher (evotorch's
 `CMAES(problem, stdev_init=0.1, popsize=10, separable=True)`): separable CMA-ES with the same population surface and the same
-no-host-read generation."""
+no-host-read generation.
+
+Episodes: a population built with `episodes=E` evaluates each of the searcher's `popsize` candidates on E worlds in the same
+launches (R = popsize·E replicas); `tell(terms, episodes=E)` folds the E sums of a candidate into its mean with one more
+launch (die_*_update_episodes) and keeps them in `episode_fitness`."""
 import ctypes as C
 import math
 from typing import Optional, Tuple
@@ -62,10 +66,32 @@ class _PopulationSearch:
                 or not params.is_contiguous():
             raise ValueError(f'params: a contiguous ({self.R}, {self.P}) float32 tensor on {self.device}')
 
-    def _check_terms(self, terms: torch.Tensor):
+    def _check_terms(self, terms: torch.Tensor, episodes: int = 1):
+        n = self.R * episodes
         if terms.dtype != torch.float64 or terms.device != self.device or terms.dim() not in (2, 3) \
-                or tuple(terms.shape[1:2]) != (self.R,) or (terms.dim() == 3 and terms.shape[2] < 1) or terms.shape[0] < 1:
-            raise ValueError(f'terms: a (T, {self.R}) or (T, {self.R}, 2) float64 tensor on {self.device}')
+                or tuple(terms.shape[1:2]) != (n,) or (terms.dim() == 3 and terms.shape[2] < 1) or terms.shape[0] < 1:
+            raise ValueError(f'terms: a (T, {n}) or (T, {n}, 2) float64 tensor on {self.device}' +
+                             (f' ({self.R} candidates x {episodes} episodes, candidate-major)' if episodes != 1 else ''))
+
+    def _check_episodes(self, episodes) -> int:
+        if isinstance(episodes, bool) or not isinstance(episodes, int) or episodes < 1:
+            raise ValueError(f'episodes={episodes!r}: an integer >= 1 (worlds per candidate)')
+        if self.R * episodes > _lib.MAX_REPLICAS:
+            raise ValueError(f'episodes={episodes}: {self.R} candidates x {episodes} episodes is more than {_lib.MAX_REPLICAS} replicas')
+        return episodes
+
+    @property
+    def episode_fitness(self) -> torch.Tensor:
+        """(C, E) float64 on the device: candidate c's sum of terms on each of its E worlds in the last `tell` (`fitness` is
+        their mean, summed in episode order); the spread over e is the luck of the worlds.  E = 1: `fitness` as a column."""
+        return self.fitness.view(self.R, 1) if self._episode_fitness is None else self._episode_fitness
+
+    def _fold_buffers(self, episodes: int):
+        """The (C, E) per-episode sums and the C folded terms of die_*_update_episodes, allocated at the first use of an E."""
+        if self._episode_fitness is None or self._episode_fitness.shape[1] != episodes:
+            self._episode_fitness = torch.zeros((self.R, episodes), dtype=torch.float64, device=self.device)
+            self._folded = torch.zeros(self.R, dtype=torch.float64, device=self.device)
+        return _ptr(self._episode_fitness), _ptr(self._folded)
 
     def _reserve_history(self):
         if self.iter >= self._history.shape[0]:         # grow the history on the device (no host read)
@@ -85,7 +111,13 @@ class _PopulationSearch:
         `reseed`: a new world every generation instead of the construction worlds — generation g (`iter` at ask) resets with
         `pop.env.reset(seed=reseed + g·R, seed_stride=reseed_stride)`.  Stride 0 (default): every candidate of a generation is
         evaluated on the same fresh world (what antithetic pairs and ranks compare); stride 1: a world per replica and
-        generation.  The population's BatchedEnv needs the fixed layout (`max_agents` an int or None)."""
+        generation.  The population's BatchedEnv needs the fixed layout (`max_agents` an int or None).
+
+        A population built with `episodes=E` binds when popsize is its number of CANDIDATES (`pop.candidates`; a population
+        without that attribute: `pop.R`): every generation then steps R = C·E replicas and `tell` folds with episodes=E.
+        With `reseed`, generation g gives replica (c, e) the world of reseed + g·C·E + e + reseed_stride·c·E through
+        `reset(seeds=...)` — stride 0: every candidate sees the same E fresh worlds; stride 1: every replica its own; E = 1:
+        the formula above."""
         if any(not hasattr(pop, name) for name in ('R', 'P', 'parameters', 'env')):
             raise TypeError('pop: a BatchedNeuralAutomataAgent or a BatchedPhysarumPopulation (R, P, parameters, env)')
         if getattr(pop, 'natural', False):
@@ -93,8 +125,11 @@ class _PopulationSearch:
                              'unit mode (parameters=, space=ParameterSpace(lo, hi)) to search it')
         if env is not None and env is not pop.env:
             raise ValueError('this population was built for another BatchedEnv')
-        if pop.R != self.R:
-            raise ValueError(f'popsize {self.R} != the population\'s {pop.R} replicas')
+        candidates, episodes = getattr(pop, 'candidates', pop.R), getattr(pop, 'episodes', 1)
+        if candidates != self.R:
+            raise ValueError(f'popsize {self.R} != the population\'s {candidates} ' +
+                             ('replicas' if episodes == 1 else f'candidates ({pop.R} replicas of {episodes} episodes each)'))
+        self._check_episodes(episodes)
         if pop.P != self.P:
             raise ValueError(f'{self.P} search parameters for a population of {pop.P}')
         if pop.parameters.device != self.device:
@@ -110,12 +145,16 @@ class _PopulationSearch:
                 raise ValueError("reseed needs a BatchedEnv with max_agents=N (or None for W·H): the 'alive' layout holds K_r slots "
                                  'per replica, and a new world has a new K_r')
         self._reseed, self._reseed_stride = reseed, int(reseed_stride)
-        self._pop, self._epoch_iters = pop, int(epoch_iters)
+        self._pop, self._epoch_iters, self._episodes = pop, int(epoch_iters), episodes
         # a population with state of its own between generations (a PhysarumAgent population's headings and table) says so
         # with a `reset()`.  BatchedNeuralAutomataAgent has none ON PURPOSE: its generation is ask, env.reset, steps, tell and
         # nothing else — giving it a `reset` method would add a call to every NCA generation
         self._pop_reset = getattr(pop, 'reset', None)
-        self._results = torch.empty((self._epoch_iters, self.R, 2), dtype=torch.float64, device=self.device)
+        self._results = torch.empty((self._epoch_iters, self.R * episodes, 2), dtype=torch.float64, device=self.device)
+        if episodes > 1:
+            self._fold_buffers(episodes)                # (allocated here, not in the first generation)
+        else:
+            self._episode_fitness = self._folded = None
         return self
 
     def step(self) -> None:
@@ -125,6 +164,8 @@ class _PopulationSearch:
         pop, env = self._pop, self._pop.env
         g = self.iter
         self.ask(pop.parameters)
+        if self._episodes != 1:
+            return self._step_episodes(pop, env, g)
         if self._reseed is None:
             env.reset()
         else:
@@ -134,6 +175,23 @@ class _PopulationSearch:
         for t in range(self._epoch_iters):
             env.step(pop, self._results[t])
         self.tell(self._results)
+
+    def _step_episodes(self, pop, env, g: int) -> None:
+        """`step` for a population with E > 1 episodes: the worlds from the seed list, the fold in tell."""
+        if self._reseed is None:
+            env.reset()
+        else:
+            env.reset(seeds=self._generation_seeds(g))
+        if self._pop_reset is not None:
+            self._pop_reset()
+        for t in range(self._epoch_iters):
+            env.step(pop, self._results[t])
+        self.tell(self._results, episodes=self._episodes)
+
+    def _generation_seeds(self, g: int):
+        """The worlds of generation g under `reseed`: replica c·E + e gets reseed + g·C·E + e + reseed_stride·c·E."""
+        from .batch import episode_seeds
+        return episode_seeds(self._reseed + g * self.R * self._episodes, self.R, self._episodes, self._reseed_stride)
 
     def run(self, generations: int) -> None:
         for _ in range(int(generations)):
@@ -226,6 +284,7 @@ class PGPE(_PopulationSearch):
         self.iter = 0                                   # generations told so far
         self._asked = None
         self._pop = None
+        self._episode_fitness = self._folded = None
 
     # ------------------------------------------------------------------ generic interface
     def ask(self, params: torch.Tensor) -> torch.Tensor:
@@ -235,18 +294,31 @@ class PGPE(_PopulationSearch):
         self._asked = params
         return params
 
-    def tell(self, terms: torch.Tensor, params: Optional[torch.Tensor] = None) -> None:
+    def tell(self, terms: torch.Tensor, params: Optional[torch.Tensor] = None, *, episodes: int = 1) -> None:
         """Update from the evaluated rows (those of the last `ask` unless `params` is given): candidate r's fitness is the sum
         over t of terms[t, r] — a (T, R) float64 tensor, or the (T, R, 2) die_step_result tensor of `BatchedEnv.run` (word 0:
-        the reward).  Three or four launches, no host read."""
+        the reward).  Three or four launches, no host read.
+
+        `episodes=E`: terms of (T, R·E[, 2]), replica c·E + e candidate c's e-th world; candidate c's fitness is the mean of
+        its E sums, added in episode order (float64) — one more launch; the sums stay in `episode_fitness`."""
         params = self._asked if params is None else params
         if params is None:
             raise RuntimeError('tell() before ask()')
         self._check_params(params)
-        self._check_terms(terms)
+        if type(episodes) is not int or episodes != 1:
+            episodes = self._check_episodes(episodes)
+        self._check_terms(terms, episodes)
         self._reserve_history()
-        _lib.check(_lib.lib.die_pgpe_update(C.byref(self._s), _ptr(params), _ptr(terms), terms.shape[0], terms.stride(0),
-                                            terms.stride(1), self.iter, stream_ptr(self.device)), 'die_pgpe_update')
+        if episodes == 1:
+            if self._episode_fitness is not None:
+                self._episode_fitness = self._folded = None
+            _lib.check(_lib.lib.die_pgpe_update(C.byref(self._s), _ptr(params), _ptr(terms), terms.shape[0], terms.stride(0),
+                                                terms.stride(1), self.iter, stream_ptr(self.device)), 'die_pgpe_update')
+        else:
+            ef, folded = self._fold_buffers(episodes)
+            _lib.check(_lib.lib.die_pgpe_update_episodes(C.byref(self._s), _ptr(params), _ptr(terms), terms.shape[0], terms.stride(0),
+                                                         terms.stride(1), episodes, ef, folded, self.iter, stream_ptr(self.device)),
+                       'die_pgpe_update_episodes')
         self.iter += 1
 
     # ------------------------------------------------------------------ results (read on demand)
@@ -357,6 +429,7 @@ class CMAES(_PopulationSearch):
         self._asked = None
         self._asked_iter = None
         self._pop = None
+        self._episode_fitness = self._folded = None
 
     # ------------------------------------------------------------------ generic interface
     def ask(self, params: torch.Tensor) -> torch.Tensor:
@@ -366,17 +439,30 @@ class CMAES(_PopulationSearch):
         self._asked, self._asked_iter = params, self.iter
         return params
 
-    def tell(self, terms: torch.Tensor) -> None:
+    def tell(self, terms: torch.Tensor, *, episodes: int = 1) -> None:
         """Update from the rows of this generation's `ask` (z is regenerated from its Philox counter, so the ask must be of the
         same generation): candidate r's fitness is the sum over t of terms[t, r] — a (T, R) float64 tensor, or the (T, R, 2)
-        die_step_result tensor of `BatchedEnv.run` (word 0: the reward).  Four launches, no host read."""
+        die_step_result tensor of `BatchedEnv.run` (word 0: the reward).  Four launches, no host read.
+
+        `episodes=E`: terms of (T, R·E[, 2]), replica c·E + e candidate c's e-th world; candidate c's fitness is the mean of
+        its E sums, added in episode order (float64) — one more launch; the sums stay in `episode_fitness`."""
         if self._asked is None or self._asked_iter != self.iter:
             raise RuntimeError(f'tell() before ask() of generation {self.iter}')
         self._check_params(self._asked)
-        self._check_terms(terms)
+        if type(episodes) is not int or episodes != 1:
+            episodes = self._check_episodes(episodes)
+        self._check_terms(terms, episodes)
         self._reserve_history()
-        _lib.check(_lib.lib.die_cmaes_update(C.byref(self._s), _ptr(self._asked), _ptr(terms), terms.shape[0], terms.stride(0),
-                                             terms.stride(1), self.iter, stream_ptr(self.device)), 'die_cmaes_update')
+        if episodes == 1:
+            if self._episode_fitness is not None:
+                self._episode_fitness = self._folded = None
+            _lib.check(_lib.lib.die_cmaes_update(C.byref(self._s), _ptr(self._asked), _ptr(terms), terms.shape[0], terms.stride(0),
+                                                 terms.stride(1), self.iter, stream_ptr(self.device)), 'die_cmaes_update')
+        else:
+            ef, folded = self._fold_buffers(episodes)
+            _lib.check(_lib.lib.die_cmaes_update_episodes(C.byref(self._s), _ptr(self._asked), _ptr(terms), terms.shape[0],
+                                                          terms.stride(0), terms.stride(1), episodes, ef, folded, self.iter,
+                                                          stream_ptr(self.device)), 'die_cmaes_update_episodes')
         self.iter += 1
 
     # ------------------------------------------------------------------ results (read on demand)

@@ -7,11 +7,16 @@ separable CMA-ES with stdev_init 0.1 and popsize 10 (die_amd.search.CMAES), the 
 
     python examples/learning_agents.py [--searcher pgpe|cmaes] [--dynamics st-perlin-wide] [--size 96] [--generations 100]
                                        [--epoch-iters 30] [--agents-die] [--max-agents alive|full|tight|N]
-                                       [--reseed S] [--reseed-stride 0] [--out saved_models/agent.pt] [--time]
+                                       [--reseed S] [--reseed-stride 0] [--episodes 1] [--out saved_models/agent.pt] [--time]
 
 --reseed S gives every generation a new world: generation g resets the batch to the world of seed S + g·popsize, seeded on the
 device (BatchedEnv.reset(seed=...), five launches, no host read); with --reseed-stride 0 (default) every candidate of a
 generation shares that world, with 1 each gets its own.  It needs a fixed slot layout (--max-agents; 'tight' when not given).
+
+--episodes E scores every candidate on E worlds per generation, its fitness their mean (evotorch's num_episodes): popsize·E
+batched replicas (at most 64) stepped by the same launches, one more launch per generation for the fold.  Without --reseed the E
+worlds are those of seeds seed … seed + E − 1 every generation; with it generation g takes the worlds of S + g·popsize·E + e
+(+ --reseed-stride·c·E for candidate c), seeded on the device from the list (BatchedEnv.reset(seeds=...)).
 
 Deliberate differences from the reference: without --reseed every generation starts the R worlds from the same
 seeded state, and with it from a new one each generation, where the reference's run_epoch keeps stepping one env from candidate
@@ -31,7 +36,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from die_amd import CMAES, PGPE, Env, NeuralAutomataAgent            # noqa: E402
-from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent    # noqa: E402
+from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent, episode_seeds   # noqa: E402
 from population_eval import AGENT_KW, DYNAMICS, evaluate_population, make_dynamics, make_population, run_epoch, slots   # noqa: E402
 
 RADIUS_INIT = 1.5
@@ -43,12 +48,12 @@ SEARCHERS = ('pgpe', 'cmaes')
 
 
 def make_search(size, choice, popsize, epoch_iters, seed, searcher='pgpe', agents_die=False, max_agents='alive', reseed=None,
-                reseed_stride=0):
+                reseed_stride=0, episodes=1):
     torch.manual_seed(seed)
     template = NeuralAutomataAgent(**AGENT_KW)
-    benv = BatchedEnv((size, size), make_dynamics(choice, size, agents_die), replicas=popsize, seeds=[seed] * popsize,
-                      max_agents=max_agents)
-    pop = BatchedNeuralAutomataAgent(benv, template)
+    benv = BatchedEnv((size, size), make_dynamics(choice, size, agents_die), replicas=popsize * episodes,
+                      seeds=episode_seeds(seed, popsize, episodes), max_agents=max_agents)
+    pop = BatchedNeuralAutomataAgent(benv, template, episodes=episodes)
     if searcher == 'cmaes':
         search = CMAES(popsize, pop.P, seed=seed, **CMAES_KW)
     else:
@@ -69,7 +74,7 @@ def host_generation(size, choice, template, mean, sigma, lr, iters, seed, agents
 
 def time_device_loop(args, G, max_agents, reseed):
     searcher, pop = make_search(args.size, args.dynamics, 10, args.epoch_iters, args.seed, args.searcher, args.agents_die, max_agents,
-                                reseed, args.reseed_stride)
+                                reseed, args.reseed_stride, args.episodes)
     searcher.run(2)                                               # warm-up: first launches, allocations
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -88,6 +93,15 @@ def time_loops(args, N):
     searcher, pop, t_dev = time_device_loop(args, G, 'alive', None)
     _, _, t_fixed = time_device_loop(args, G, fixed, None)
     _, _, t_reseed = time_device_loop(args, G, fixed, reseed)
+    E = args.episodes
+    if E > 1:                                                     # (the host-driven loop has no episodes: the device loops only)
+        name = type(searcher).__name__ + '.run):'
+        for what, t, n in ((f'device loop ({name:15s}', t_dev, 'alive'), ('  fixed slots:             ', t_fixed, fixed),
+                           ('  fixed slots, reseeding:  ', t_reseed, f'{fixed}, reseed stride {args.reseed_stride}')):
+            print(f'{what}{G / t:9.1f} generations/s  ({t / G * 1e3:.3f} ms per generation, {10 * E * G / t:9.1f} candidate-evaluations/s)  '
+                  f'max_agents={n}')
+        print(f'({G} generations of 10 candidates x {E} episodes x {args.size}^2, {args.epoch_iters} steps, {args.dynamics})', flush=True)
+        return
     template = pop.template
     mean = pop.parameters[0].cpu()
     for _ in range(2):
@@ -123,7 +137,10 @@ def main():
                                                       "'tight' (default with --reseed) or a number")
     p.add_argument('--reseed', type=int, default=None, help='a new world every generation: seed S + g·popsize (device-seeded)')
     p.add_argument('--reseed-stride', type=int, default=0, help='0: one world per generation; 1: one per candidate and generation')
+    p.add_argument('--episodes', type=int, default=1, help='worlds per candidate and generation (popsize x episodes <= 64)')
     args = p.parse_args()
+    if args.episodes < 1 or (10 if args.time else args.popsize) * args.episodes > 64:
+        p.error(f'--episodes {args.episodes}: at least 1, and popsize x episodes at most 64 replicas')
     N = slots(args.max_agents or ('tight' if args.reseed is not None else 'alive'), args.size, args.dynamics, args.agents_die)
     if args.reseed is not None and N == 'alive':
         sys.exit("--reseed needs a fixed slot layout: --max-agents full, tight or a number")
@@ -131,10 +148,11 @@ def main():
         time_loops(args, N)
         return
     searcher, pop = make_search(args.size, args.dynamics, args.popsize, args.epoch_iters, args.seed, args.searcher, args.agents_die, N,
-                                args.reseed, args.reseed_stride)
-    print(f'Network has {pop.P} parameters; {args.popsize} candidates on {args.size}x{args.size} {args.dynamics}, '
+                                args.reseed, args.reseed_stride, args.episodes)
+    print(f'Network has {pop.P} parameters; {args.popsize} candidates' + (f' x {args.episodes} episodes' if args.episodes > 1 else '') +
+          f' on {args.size}x{args.size} {args.dynamics}, '
           f'{args.epoch_iters} steps each, max_agents={N}' + ('' if args.reseed is None else
-          f', a new world every generation (seed {args.reseed} + g·{args.popsize}, stride {args.reseed_stride})'), flush=True)
+          f', new worlds every generation (seed {args.reseed} + g·{args.popsize * args.episodes}, stride {args.reseed_stride})'), flush=True)
     t0 = time.perf_counter()
     searcher.run(args.generations)
     torch.cuda.synchronize()

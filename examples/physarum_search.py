@@ -3,12 +3,14 @@ parameter sets stepped together on copies of one seeded world, one launch pair p
 
     python examples/physarum_search.py --sweep sense_angle=22.5:112.5:8 sense_offset=0.01:0.08:8 [--agents-die]
     python examples/physarum_search.py --searcher pgpe|cmaes [--generations 40] [--out best.json]
-    ... [--size 96] [--iters 30] [--replicas 10] [--seed 0] [--time]
+    ... [--size 96] [--iters 30] [--replicas 10] [--episodes 1] [--seed 0] [--time]
 
 --sweep NAME=LO:HI:N ... lays a grid over the named constructor arguments (the others at PhysarumAgent's defaults; at most 64
 cells) and prints, per cell, the mean reward per step and the agents alive at the end (they only fall with --agents-die).
 --searcher tunes the six parameters from the default ParameterSpace with the device-resident PGPE or separable CMA-ES (no host
 read inside a generation) and saves the best candidate's constructor arguments as JSON.
+--episodes E (search mode): every one of the --replicas candidates is scored on E worlds (seeds seed … seed + E − 1, the same E
+for every candidate) in the same launches, its fitness their mean; replicas·E may not exceed 64.
 --time: sweep mode prints candidate-steps/s of the batch against the same candidates stepped one at a time (a stand-alone Env +
 PhysarumAgent each); search mode prints generations/s.
 """
@@ -25,7 +27,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from die_amd import CMAES, PGPE, Dynamics, Env                                         # noqa: E402
-from die_amd.batch import PARAMETER_NAMES, PHYSARUM_DEFAULTS, BatchedEnv, BatchedPhysarumPopulation   # noqa: E402
+from die_amd.batch import PARAMETER_NAMES, PHYSARUM_DEFAULTS, BatchedEnv, BatchedPhysarumPopulation, episode_seeds   # noqa: E402
 
 
 def sweep_rows(specs):
@@ -87,9 +89,9 @@ def run_sweep(args, dynamics):
 
 
 def run_search(args, dynamics):
-    R = args.replicas
-    benv = BatchedEnv((args.size, args.size), dynamics(), replicas=R, seeds=[args.seed] * R)
-    pop = BatchedPhysarumPopulation(benv, parameters=torch.full((R, 6), 0.5), seed=args.seed)
+    R, E = args.replicas, args.episodes               # R candidates on R·E replicas
+    benv = BatchedEnv((args.size, args.size), dynamics(), replicas=R * E, seeds=episode_seeds(args.seed, R, E))
+    pop = BatchedPhysarumPopulation(benv, parameters=torch.full((R, 6), 0.5), seed=args.seed, episodes=E)
     center = torch.tensor(pop.space.encode(PHYSARUM_DEFAULTS))          # start at the reference's defaults
     if args.searcher == 'pgpe':
         s = PGPE(R, center_init=center, stdev_init=0.1, center_learning_rate=0.05, stdev_learning_rate=0.1,
@@ -113,7 +115,7 @@ def run_search(args, dynamics):
     with open(args.out, 'w') as f:
         json.dump(out, f, indent=1)
     if args.time:
-        print(f'{args.generations / dt:.1f} generations/s ({R} candidates x {args.iters} steps, {args.size}x{args.size})')
+        print(f'{args.generations / dt:.1f} generations/s ({R} candidates x {E} episodes x {args.iters} steps, {args.size}x{args.size})')
 
 
 def main():
@@ -123,6 +125,7 @@ def main():
     ap.add_argument('--size', type=int, default=96)
     ap.add_argument('--iters', type=int, default=30)
     ap.add_argument('--replicas', type=int, default=10)
+    ap.add_argument('--episodes', type=int, default=1, help='search mode: worlds per candidate and generation (replicas x episodes <= 64)')
     ap.add_argument('--generations', type=int, default=40)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--agents-die', action='store_true')
@@ -131,6 +134,8 @@ def main():
     args = ap.parse_args()
     if (args.sweep is None) == (args.searcher is None):
         ap.error('one of --sweep and --searcher')
+    if args.episodes < 1 or args.replicas * args.episodes > 64 or (args.sweep and args.episodes != 1):
+        ap.error(f'--episodes {args.episodes}: at least 1, {args.replicas} replicas x episodes at most 64, and search mode only')
     dynamics = lambda: Dynamics(agents_die=args.agents_die)
     if args.sweep:
         run_sweep(args, dynamics)

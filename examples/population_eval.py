@@ -3,7 +3,7 @@ once: R NeuralAutomataAgent candidates, each scored by the sum of its rewards ov
 all R worlds stepped together by die_amd.batch (L + 2 launches per step for an L-layer model, L + 3 with a food flow).
 
     python examples/population_eval.py [--replicas 10] [--size 96] [--iters 50] [--dynamics st-perlin-wide] [--generations 0] [--agents-die]
-                                       [--max-agents alive|full|tight|N] [--reseed S] [--compare]
+                                       [--max-agents alive|full|tight|N] [--reseed S] [--episodes 1] [--compare]
 
 --dynamics picks one of the reference's three worlds (learning_agents.py `dynamics_choice`): 'st-perlin', 'st-perlin-wide' or
 'dyn-pred', where the food flows in running waves (WaveSequence.get_flow_operator, one more launch per batched step).
@@ -12,6 +12,9 @@ all R worlds stepped together by die_amd.batch (L + 2 launches per step for an L
 'tight' (the expected count plus six standard deviations) or a number; every layout but 'alive' runs the dead-slot pass.
 --reseed S (with --generations, a fixed layout): generation g evaluates on the world of seed S + g, seeded on the device by
 BatchedEnv.reset(seed=...) in the one batch built up front, instead of a batch rebuilt on the host.
+
+--episodes E scores every candidate on E worlds (seeds seed … seed + E − 1, the same E for every candidate) in the same launches
+— replicas·E batched replicas, at most 64 — and prints the mean and the spread of its E sums.
 
 --generations G runs a plain Gaussian evolution strategy (antithetic samples, normalised fitness) on the mean parameter
 vector — the training loop itself (evotorch's PGPE, MLflow) stays out of scope.  --compare times the same population one
@@ -30,7 +33,7 @@ from torch.nn.utils import parameters_to_vector
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from die_amd import Dynamics, Env, NeuralAutomataAgent, WaveSequence    # noqa: E402
-from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent        # noqa: E402
+from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent, episode_seeds   # noqa: E402
 
 AGENT_KW = dict(kernel_sizes=[3, 3], scale=0.01, deposit=2.0)           # learning_agents.py
 DYNAMICS = ('st-perlin', 'st-perlin-wide', 'dyn-pred')
@@ -60,17 +63,22 @@ def slots(spec, size, choice, agents_die=False):
     return int(spec)
 
 
-def make_population(size, template, rows, seed, choice, agents_die=False, max_agents='alive'):
-    R = rows.shape[0]
-    benv = BatchedEnv((size, size), make_dynamics(choice, size, agents_die), replicas=R, seeds=[seed] * R,   # every world starts alike
+def make_population(size, template, rows, seed, choice, agents_die=False, max_agents='alive', episodes=1):
+    C = rows.shape[0]                                  # every candidate starts on the same world (with episodes: the same E worlds)
+    benv = BatchedEnv((size, size), make_dynamics(choice, size, agents_die), replicas=C * episodes, seeds=episode_seeds(seed, C, episodes),
                       max_agents=max_agents)
-    return benv, BatchedNeuralAutomataAgent(benv, template, rows)
+    return benv, BatchedNeuralAutomataAgent(benv, template, rows, episodes=episodes)
 
 
 def evaluate_population(benv, pop, iters):
-    """Fitness of every candidate: the sum of its world's rewards over `iters` steps (run_epoch for all of them)."""
+    """Fitness of every replica: the sum of its world's rewards over `iters` steps (run_epoch for all of them)."""
     rewards, _ = BatchedEnv.read_results(benv.run(pop, iters))
     return [sum(rewards[:, r].tolist()) for r in range(benv.R)]        # (summed in step order, like run_epoch)
+
+
+def candidate_fitness(sums, episodes):
+    """Per-replica sums -> per-candidate means over its E worlds, added in episode order (the searchers' fold)."""
+    return [sum(sums[c * episodes:(c + 1) * episodes], 0.0) / episodes for c in range(len(sums) // episodes)]
 
 
 def run_epoch(env, agent, iters):
@@ -82,8 +90,8 @@ def run_epoch(env, agent, iters):
     return epoch_reward
 
 
-def one_at_a_time_worlds(size, R, seed, choice, agents_die=False, max_agents='alive'):
-    return [Env((size, size), make_dynamics(choice, size, agents_die), seed=seed, max_agents=max_agents) for _ in range(R)]
+def one_at_a_time_worlds(size, R, seed, choice, agents_die=False, max_agents='alive', episodes=1):
+    return [Env((size, size), make_dynamics(choice, size, agents_die), seed=q, max_agents=max_agents) for q in episode_seeds(seed, R, episodes)]
 
 
 def main():
@@ -100,8 +108,11 @@ def main():
     p.add_argument('--agents-die', action='store_true', help='Dynamics(agents_die=True): starved agents die')
     p.add_argument('--max-agents', default='alive', help="slots per replica: 'alive', 'full' (W·H), 'tight' or a number")
     p.add_argument('--reseed', type=int, default=None, help='--generations on the device-seeded world of seed S + g (fixed layout)')
+    p.add_argument('--episodes', type=int, default=1, help='worlds per candidate (replicas x episodes <= 64)')
     args = p.parse_args()
-    R = args.replicas
+    R, E = args.replicas, args.episodes
+    if E < 1 or R * E > 64:
+        p.error(f'--episodes {E}: at least 1, and {R} replicas x episodes at most 64')
     N = slots(args.max_agents, args.size, args.dynamics, args.agents_die)
     if args.reseed is not None and N == 'alive':
         sys.exit("--reseed needs a fixed slot layout: --max-agents full, tight or a number")
@@ -112,34 +123,37 @@ def main():
         template.model.init_weights()
         cands.append(parameters_to_vector(template.model.parameters()).detach().clone())
     rows = torch.stack(cands)
-    print(f'{R} candidates of {rows.shape[1]} parameters, {args.size}x{args.size}, {args.iters} steps each, {args.dynamics}'
+    print(f'{R} candidates of {rows.shape[1]} parameters' + (f' on {E} worlds each' if E > 1 else '') +
+          f', {args.size}x{args.size}, {args.iters} steps each, {args.dynamics}'
           f'{" with agents_die" if args.agents_die else ""}, max_agents={N}', flush=True)
 
-    benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die, N)
-    fitness = evaluate_population(benv, pop, args.iters)
+    benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die, N, E)
+    sums = evaluate_population(benv, pop, args.iters)
+    fitness = candidate_fitness(sums, E)
     for r, f in enumerate(fitness):
-        print(f'candidate {r:2d}: fitness {f:.6f}')
+        worlds = sums[r * E:(r + 1) * E]
+        print(f'candidate {r:2d}: fitness {f:.6f}' + (f'  (its {E} worlds: {min(worlds):.6f} … {max(worlds):.6f})' if E > 1 else ''))
     best = max(range(R), key=lambda r: fitness[r])
     print(f'best: candidate {best} ({fitness[best]:.6f}); pop.candidate({best}).save(...) keeps it', flush=True)
 
     if args.compare:
         # only the stepping is timed (the worlds are built before); warm-up of both paths first
         dev = torch.device('cuda')
-        agents = [pop.candidate(r).to(dev) for r in range(R)]
-        evaluate_population(*make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die, N), 2)
+        agents = [pop.candidate(r // E).to(dev) for r in range(R * E)]       # replica r is stepped by its candidate's agent
+        evaluate_population(*make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die, N, E), 2)
         run_epoch(one_at_a_time_worlds(args.size, 1, args.seed, args.dynamics, args.agents_die, N)[0], agents[0], 2)
-        benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die, N)
+        benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die, N, E)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         batched = evaluate_population(benv, pop, args.iters)
         t_batch = time.perf_counter() - t0
-        worlds = one_at_a_time_worlds(args.size, R, args.seed, args.dynamics, args.agents_die, N)
+        worlds = one_at_a_time_worlds(args.size, R, args.seed, args.dynamics, args.agents_die, N, E)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         alone = [run_epoch(env, ag, args.iters) for env, ag in zip(worlds, agents)]
         torch.cuda.synchronize()
         t_alone = time.perf_counter() - t0
-        cs = R * args.iters
+        cs = R * E * args.iters
         print(f'batched:       {cs / t_batch:12.0f} candidate-steps/s  ({t_batch * 1e3:.2f} ms)')
         print(f'one at a time: {cs / t_alone:12.0f} candidate-steps/s  ({t_alone * 1e3:.2f} ms)')
         print(f'speed-up: {t_alone / t_batch:.2f}x   same fitness: {batched == alone}', flush=True)
@@ -155,11 +169,14 @@ def main():
         samples = mean + args.sigma * noise
         if args.reseed is not None:                                         # the one batch, a new world seeded on the device
             pop.set_parameters(samples)
-            benv.reset(seed=args.reseed + g, seed_stride=0)
-            fit = evaluate_population(benv, pop, args.iters)
+            if E == 1:
+                benv.reset(seed=args.reseed + g, seed_stride=0)
+            else:                                                           # E new worlds, the same for every candidate
+                benv.reset(seeds=episode_seeds(args.reseed + g * E, R, E))
+            fit = candidate_fitness(evaluate_population(benv, pop, args.iters), E)
         else:
-            fit = evaluate_population(*make_population(args.size, template, samples, args.seed + 1 + g, args.dynamics, args.agents_die, N),
-                                      args.iters)
+            fit = candidate_fitness(evaluate_population(*make_population(args.size, template, samples, args.seed + 1 + g * E, args.dynamics,
+                                                                         args.agents_die, N, E), args.iters), E)
         f = torch.tensor(fit, dtype=torch.float32)
         f = (f - f.mean()) / (f.std() + 1e-8)
         mean = mean + args.lr / (noise.shape[0] * args.sigma) * (noise.T @ f)

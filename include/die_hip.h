@@ -267,6 +267,12 @@ typedef struct die_parameter_space {
 int die_physarum_decode_batch(const float* rows, int32_t replicas, int32_t mode, const die_parameter_space* space,
                               die_physarum_row* table, float* values, void* stream);
 
+/* The same launch for a population with episodes: (candidates, 6) `rows` -> `table` of candidates * episodes rows, row c * E + e
+ * being candidate c's (the E replicas that evaluate a candidate step with the same values), and `values` (candidates, 6).
+ * candidates * episodes <= DIE_MAX_REPLICAS; episodes = 1 is die_physarum_decode_batch. */
+int die_physarum_decode_episodes(const float* rows, int32_t candidates, int32_t episodes, int32_t mode,
+                                 const die_parameter_space* space, die_physarum_row* table, float* values, void* stream);
+
 /* die_init_heading of every replica in one launch: replica r covers n[r] slots r * agent_stride behind heading_hi / _lo,
  * draws from key seed + r * seed_stride and discretises with table[r].turn_radians. */
 int die_physarum_heading_batch(uint32_t* heading_hi, uint32_t* heading_lo, const die_batch* b, const die_physarum_row* table,
@@ -382,6 +388,14 @@ int64_t die_init_batch_workspace_bytes(int32_t W, int32_t H, int32_t replicas);
 int die_init_batch(const die_medium* m, const die_agents* a, const die_batch* b, double agent_ratio, uint64_t seed,
                    uint64_t world_stride, const die_food_spec* food, int64_t* counts_dev, void* workspace, int64_t workspace_bytes,
                    void* stream);
+/* The same call with the world of every replica given: replica r is seeded from seeds[r] (BatchedEnv.reset(seeds=...); the E
+ * worlds of every candidate of a population with episodes).  `seeds` is a HOST array of n_seeds values, read during the call
+ * and passed to the kernels by value; n_seeds must be b->replicas (1..DIE_MAX_REPLICAS).  Any values, repeats included, no
+ * arithmetic pattern.  Otherwise die_init_batch's contract: same five launches, same counts_dev words, same workspace; a
+ * wave-mix spec is refused unless every seed is the same. */
+int die_init_batch_seeds(const die_medium* m, const die_agents* a, const die_batch* b, double agent_ratio, const uint64_t* seeds,
+                         int32_t n_seeds, const die_food_spec* food, int64_t* counts_dev, void* workspace, int64_t workspace_bytes,
+                         void* stream);
 /* GradientAgent/PhysarumAgent.__init__ state (:42-43,163): heading from N(0,.4) noise,
  * discretised to the turn lattice when turn_radians > 0; stored as the float64 of its fp32 rounding. */
 int die_init_heading(uint32_t* heading_hi, uint32_t* heading_lo, float* prev_gx, float* prev_gy, int64_t N, double turn_radians,
@@ -678,7 +692,8 @@ typedef struct die_nca_layer {
     int32_t k;                   /* odd, 1..7 */
     int32_t cin, cout;           /* 1..4; layer 0 reads 2 + with_agent_channel planes, the last gives 3 */
     int32_t reserved;
-    const float* weights;        /* device fp32: replica r's (cout, cin, k, k) block starts at weights + r * weight_stride */
+    const float* weights;        /* device fp32: replica r's (cout, cin, k, k) block starts at weights + r * weight_stride
+                                  * (with die_nca_batch.episodes = E > 1: at weights + (r / E) * weight_stride) */
     int64_t weight_stride;       /* elements, >= cout * cin * k * k (e.g. the row length of an (R, P) parameter matrix) */
 } die_nca_layer;
 typedef struct die_nca_batch {
@@ -688,7 +703,9 @@ typedef struct die_nca_batch {
     int32_t sense_epoch;
     const die_nca_layer* layers;
     float coef[3];               /* action = plane * coef: scale, scale, deposit */
-    int32_t reserved;
+    int32_t episodes;            /* E: replica r = c * E + e is candidate c on its e-th world and reads weight block r / E of every
+                                  * layer (weights + (r / E) * weight_stride); must divide b->replicas.  0 (the former
+                                  * `reserved`) reads as 1: a block per replica */
     float* scratch;
     int64_t scratch_bytes;
 } die_nca_batch;
@@ -743,6 +760,15 @@ typedef struct die_pgpe {
 int die_pgpe_sample(const die_pgpe* s, float* params, int64_t generation, void* stream);
 int die_pgpe_update(const die_pgpe* s, const float* params, const double* terms, int64_t T, int64_t stride_t, int64_t stride_r,
                     int64_t generation, void* stream);
+/* Episodes: candidate c of the C = s->replicas rows was evaluated on E = episodes worlds, replica c E + e its e-th, so `terms`
+ * holds C E replicas (C E <= DIE_MAX_REPLICAS).  One more launch ahead of die_pgpe_update's (one wave, no atomics):
+ *   F_r = sum over t ascending of terms[t stride_t + r stride_r], r < C E  ->  episode_fitness[r]   ((C, E) row-major doubles);
+ *   f_c = (((0 + F_{cE}) + F_{cE+1}) + ... + F_{cE+E-1}) / E               ->  folded[c]            (C doubles).
+ * Then exactly die_pgpe_update(s, params, folded, T = 1, 1, 1, generation): ranks, gradients, pop_best, best and the history
+ * row are those of f_c.  Both buffers are the caller's device memory. */
+int die_pgpe_update_episodes(const die_pgpe* s, const float* params, const double* terms, int64_t T, int64_t stride_t,
+                             int64_t stride_r, int32_t episodes, double* episode_fitness, double* folded, int64_t generation,
+                             void* stream);
 
 /* ---- separable CMA-ES over an (R, P) parameter matrix (die_cmaes.hip; die_amd/search.py CMAES) -------------------------
  * The other searcher of the reference's examples/learning_agents.py (evotorch's CMAES(separable=True)): a diagonal
@@ -804,6 +830,10 @@ typedef struct die_cmaes {
 int die_cmaes_sample(const die_cmaes* s, float* params, int64_t generation, void* stream);
 int die_cmaes_update(const die_cmaes* s, const float* params, const double* terms, int64_t T, int64_t stride_t, int64_t stride_r,
                      int64_t generation, void* stream);
+/* die_pgpe_update_episodes' fold (lambda candidates x `episodes` replicas), then die_cmaes_update on the folded f_c. */
+int die_cmaes_update_episodes(const die_cmaes* s, const float* params, const double* terms, int64_t T, int64_t stride_t,
+                              int64_t stride_r, int32_t episodes, double* episode_fitness, double* folded, int64_t generation,
+                              void* stream);
 
 /* ---- message packing for decomposed worlds (die_amd/dist.py; no reference counterpart) ----------
  * A block [r0, r1) x [c0, c1) of a row-major plane (pitch in elements, 2/4/8-byte elements) copied
