@@ -124,6 +124,15 @@ class NcaBatch(C.Structure):         # die_nca_batch
                 ('scratch_bytes', C.c_int64)]
 
 
+class NcaDropout(C.Structure):      # die_nca_dropout
+    _fields_ = [('p', C.c_double), ('seed', C.c_uint64), ('seed_stride', C.c_uint64), ('step', C.c_uint32), ('reserved', C.c_uint32)]
+
+
+def nca_dropout(p: float, seed: int, seed_stride: int, step: int) -> NcaDropout:
+    """die_nca_dropout of Python integers: key and stride mod 2^64, the forward-call counter mod 2^32."""
+    return NcaDropout(float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(seed_stride) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, 0)
+
+
 DIE_PGPE_CLIPUP, DIE_PGPE_ADAM = 0, 1
 PGPE_MAX_BLOCKS = 256
 
@@ -195,6 +204,9 @@ _SIGNATURES = {
     'die_nca_batch_scratch_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'die_nca_env_step_batch': (C.c_int, [_P(Medium), _P(Agents), _P(NcaBatch), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
                                          C.c_void_p, C.c_int64, C.c_void_p]),
+    'die_nca_env_step_batch_dropout': (C.c_int, [_P(Medium), _P(Agents), _P(NcaBatch), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
+                                                 C.c_void_p, C.c_int64, _P(NcaDropout), C.c_void_p]),
+    'die_dropout_mask': (C.c_int, [C.c_int32, C.c_int32, _P(NcaDropout), C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
     'die_forward_move_claim_tile': (C.c_int, [_P(Medium), _P(Agents), _P(GradientAgent), _P(Action), _P(Dynamics), C.c_void_p,
                                               C.c_int64, C.c_void_p]),
     'die_env_step_finish': (C.c_int, [_P(Medium), _P(Agents), _P(Action), _P(Dynamics), C.c_void_p, C.c_void_p, C.c_int64,
@@ -291,6 +303,8 @@ _SIGNATURES = {
                                       C.c_void_p, C.c_int32, C.c_void_p]),
     'die_conv2d': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P(ConvPlane), C.c_int32, C.c_int32, _P(C.c_void_p), C.c_int32,
                              C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    'die_conv2d_dropout': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P(ConvPlane), C.c_int32, C.c_int32, _P(C.c_void_p), C.c_int32,
+                                     C.c_void_p, C.c_int32, C.c_int32, _P(NcaDropout), C.c_void_p]),
     'die_gather_scale': (C.c_int, [_P(Medium), _P(Agents), _P(C.c_void_p), _P(C.c_float), _P(Action), C.c_void_p]),
     'die_sort_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
     'die_agents_sort': (C.c_int, [_P(Medium), _P(Agents), _P(Agents), C.c_int32, _P(C.c_void_p), _P(C.c_void_p), C.c_void_p,

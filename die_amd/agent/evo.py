@@ -88,18 +88,29 @@ class ConvolutionModel(nn.Module):
 
 
 class NeuralAutomataAgent(TorchAgent):
-    """core/agent/evo.py:121-209."""
+    """core/agent/evo.py:121-209.
+
+    `dropout_seed` (no reference counterpart) chooses where the mask of `p_agent_dropout` comes from in training mode:
+      * None (default): a torch-RNG `nn.Dropout` multiply after the device layers, as the reference draws it — not
+        reproducible per call;
+      * an int: the counter-based mask of include/die_hip.h (die_nca_dropout), a pure function of (dropout_seed, `dropout_step`,
+        cell), applied inside the last layer's launch (`die_conv2d_dropout`).  `dropout_step` is the forward-call counter: it
+        starts at 0, every `sense` advances it by one, and it may be read and written (setting it back replays the masks).
+    It is kept out of `init_params` while None, so saved files stay loadable by the reference."""
 
     def __init__(self,
                  scale: float = 0.1,
                  deposit: float = 1.0,
                  with_agent_channel: bool = True,
                  initial_obs=None,
+                 dropout_seed: Optional[int] = None,
                  **model_kwargs,
                  ):
         self._init_params = save_args(self.__init__, locals())
         self._init_params.pop('initial_obs', None)            # an observation is not a constructor parameter worth saving
         super().__init__()
+        self.dropout_seed = dropout_seed
+        self.dropout_step = 0
         self.obs_channels = list(DataChannels.medium) if with_agent_channel else list(DataChannels.medium[1:])
         self._model = ConvolutionModel(num_obs_channels=len(self.obs_channels), num_act_channels=len(DataChannels.actions),
                                        **model_kwargs)
@@ -114,6 +125,20 @@ class NeuralAutomataAgent(TorchAgent):
     @property
     def init_params(self) -> Dict[str, Any]:
         return self._init_params
+
+    @property
+    def dropout_seed(self) -> Optional[int]:
+        return self._dropout_seed
+
+    @dropout_seed.setter
+    def dropout_seed(self, seed: Optional[int]):
+        if seed is not None and (isinstance(seed, bool) or int(seed) != seed):
+            raise ValueError(f'dropout_seed={seed!r}: an integer, or None for the torch-RNG mask')
+        self._dropout_seed = None if seed is None else int(seed)
+        if seed is None:
+            self._init_params.pop('dropout_seed', None)
+        else:
+            self._init_params['dropout_seed'] = self._dropout_seed
 
     # ------------------------------------------------------------------
     def _device_weights(self, device):
@@ -144,6 +169,11 @@ class NeuralAutomataAgent(TorchAgent):
         src = {'agents': (medium.owner, _lib.DIE_PLANE_AGENTS), 'env_food': (medium.food, fkind), 'chem1': (medium.chem, fkind)}
         planes = [src[c] for c in self.obs_channels]
         sets = self._scratch(W, H, dev, 2)
+        p = self._model.agent_dropout.p
+        masked = p > 0 and self._model.training
+        drop = None                                              # the counter-based mask: inside the last layer's launch
+        if masked and self._dropout_seed is not None:
+            drop = _lib.nca_dropout(p, self._dropout_seed, 0, self.dropout_step)
         for li, w in enumerate(weights):
             cout, cin, k, k2 = w.shape
             if k != k2 or cin != len(planes):
@@ -151,12 +181,18 @@ class NeuralAutomataAgent(TorchAgent):
             dst = sets[li % 2]
             cin_arr = (_lib.ConvPlane * cin)(*[_lib.ConvPlane(t.data_ptr(), kind, 0) for t, kind in planes])
             out_arr = (C.c_void_p * cout)(*[dst[o].data_ptr() for o in range(cout)])
-            _lib.check(_lib.lib.die_conv2d(W, H, cin, cin_arr, medium.epoch, cout, out_arr, k, _ptr(w), int(li == len(weights) - 1),
-                                           _lib.PAD_MODES[self._model.conv_layers()[li].padding_mode], sp), 'die_conv2d')
+            last = li == len(weights) - 1
+            pad = _lib.PAD_MODES[self._model.conv_layers()[li].padding_mode]
+            if last and drop is not None:
+                _lib.check(_lib.lib.die_conv2d_dropout(W, H, cin, cin_arr, medium.epoch, cout, out_arr, k, _ptr(w), 1, pad, C.byref(drop), sp),
+                           'die_conv2d_dropout')
+            else:
+                _lib.check(_lib.lib.die_conv2d(W, H, cin, cin_arr, medium.epoch, cout, out_arr, k, _ptr(w), int(last), pad, sp), 'die_conv2d')
             planes = [(dst[o], _lib.DIE_PLANE_F32) for o in range(cout)]
         out = sets[(len(weights) - 1) % 2][:len(planes)]         # the last layer's planes (scratch: valid until the next call)
-        p = self._model.agent_dropout.p
-        if p > 0 and self._model.training:                       # rare path: the mask of core/agent/evo.py:114-116
+        if self._dropout_seed is not None:
+            self.dropout_step += 1                               # counts forward calls, masked or not
+        elif masked:                                             # rare path: the torch-RNG mask of core/agent/evo.py:114-116
             out = out * self._model.agent_dropout(th.ones((W, H), device=dev))
         return out
 

@@ -33,7 +33,12 @@ workgroup fetching its replica's row of a device table, bit for bit the stand-al
 Episodes: both populations take `episodes=E` — C = R / E candidates, each evaluated on E worlds in the same launches.  Replica
 r = c·E + e is candidate c on its e-th world (candidate-major), `parameters` stays ONE (C, P) matrix (the kernels read row r / E;
 nothing is expanded), and `reset(seeds=[...])` / `episode_seeds` give the replicas their worlds (`die_init_batch_seeds`).  The
-searchers fold the E sums of a candidate into its fitness (tests/test_gpu_episodes.py)."""
+searchers fold the E sums of a candidate into its fitness (tests/test_gpu_episodes.py).
+
+Agent dropout: `BatchedNeuralAutomataAgent(..., dropout_seed=S, dropout_seed_stride=K)` trains a template with
+`p_agent_dropout > 0` — replica r's sense planes are multiplied by the counter-based mask of key S + r·K at the population's
+`dropout_step`, inside the last conv launch (`die_nca_env_step_batch_dropout`); replica r is then the stand-alone run of
+`NeuralAutomataAgent(dropout_seed=S + r·K)`, bit for bit (tests/test_gpu_dropout.py)."""
 import ctypes as C
 import dataclasses
 import math
@@ -321,19 +326,28 @@ class BatchedEnv:
         if results is None:
             results = torch.empty((self.R, 2), dtype=torch.float64, device=self.device)
         if self.per_replica:
-            return self._step_per_replica(agent, agent._replica_agent, flow, results)
+            self._step_per_replica(agent, agent._replica_agent, flow, results)
+            agent._stepped()
+            return results
+        drop = agent._dropout()
         # the sensing reads the claim plane at the current epoch, the claims are made at the next one; at the wrap the
         # library clears the claim planes between the two (Env.step runs forward before its next_epoch the same way)
         sense_epoch = self.epoch
         self.epoch = sense_epoch % _lib.OWNER_EPOCH_MAX + 1
         m, a, dyn, b = self._structs()
         nca = agent._struct(sense_epoch)
-        rc = _lib.lib.die_nca_env_step_batch(C.byref(m), C.byref(a), C.byref(nca), None, C.byref(dyn), C.byref(b), _ptr(results),
-                                             _ptr(self._ws), self._ws.numel(), stream_ptr(self.device))
+        if drop is None:
+            rc = _lib.lib.die_nca_env_step_batch(C.byref(m), C.byref(a), C.byref(nca), None, C.byref(dyn), C.byref(b), _ptr(results),
+                                                 _ptr(self._ws), self._ws.numel(), stream_ptr(self.device))
+        else:                                       # the same step, its last conv launch masked
+            rc = _lib.lib.die_nca_env_step_batch_dropout(C.byref(m), C.byref(a), C.byref(nca), None, C.byref(dyn), C.byref(b),
+                                                         _ptr(results), _ptr(self._ws), self._ws.numel(), C.byref(drop),
+                                                         stream_ptr(self.device))
         if rc != _lib.DIE_OK:
             self.epoch = sense_epoch                # refused before any launch: nothing changed
-            _lib.check(rc, 'die_nca_env_step_batch')
+            _lib.check(rc, 'die_nca_env_step_batch' if drop is None else 'die_nca_env_step_batch_dropout')
         agent._calls += 1
+        agent._stepped()
         self.chem, self.chem_next = self.chem_next, self.chem
         self._food_flow(flow, m, b)
         self._steps += 1
@@ -756,11 +770,31 @@ class BatchedNeuralAutomataAgent:
 
     `episodes=E`: C = R / E candidates (`candidates`), candidate c stepping the E replicas c·E … c·E + E − 1 — replica c·E + e is
     `Env(field_size, dynamics, seed=env.seeds[c·E + e], max_agents=...)` driven by the agent of row c, bit for bit.  `parameters`
-    is then ONE (C, P) matrix: the conv launches read row r / E (die_nca_batch.episodes), nothing is copied or expanded."""
+    is then ONE (C, P) matrix: the conv launches read row r / E (die_nca_batch.episodes), nothing is copied or expanded.
 
-    def __init__(self, env: BatchedEnv, template: NeuralAutomataAgent, parameters=None, episodes: int = 1):
+    Agent dropout (a template with `p_agent_dropout > 0` in training mode — torch's default, and where evotorch leaves a model)
+    is opt-in through `dropout_seed`:
+      * None (default): such a template is refused at the first step (the stand-alone agent's torch-RNG mask cannot be
+        reproduced per replica);
+      * an int: replica r's sense planes are multiplied by the counter-based mask (include/die_hip.h die_nca_dropout) of key
+        `dropout_seed + r·dropout_seed_stride` — with episodes r = c·E + e — at forward call `dropout_step`, inside the last conv
+        launch: replica r is the stand-alone run of `NeuralAutomataAgent(dropout_seed=dropout_seed + r·dropout_seed_stride)`.
+        Stride 0 gives every replica the same mask (common random numbers across candidates).
+    `dropout_step` is a public counter: it starts at 0, every `env.step` advances it by one, it may be written (setting it back
+    replays the masks), and nothing resets it — not `env.reset()`, not the searchers — so every generation sees new masks.  In
+    eval mode, or with p = 0, nothing is masked and the step is the one without dropout."""
+
+    def __init__(self, env: BatchedEnv, template: NeuralAutomataAgent, parameters=None, episodes: int = 1, *,
+                 dropout_seed: Optional[int] = None, dropout_seed_stride: int = 1):
         if not isinstance(template, NeuralAutomataAgent):
             raise TypeError('template: a NeuralAutomataAgent')
+        if dropout_seed is not None and (isinstance(dropout_seed, bool) or int(dropout_seed) != dropout_seed):
+            raise ValueError(f'dropout_seed={dropout_seed!r}: an integer, or None')
+        if isinstance(dropout_seed_stride, bool) or int(dropout_seed_stride) != dropout_seed_stride or int(dropout_seed_stride) < 0:
+            raise ValueError(f'dropout_seed_stride={dropout_seed_stride!r}: a non-negative integer')
+        self.dropout_seed = None if dropout_seed is None else int(dropout_seed)
+        self.dropout_seed_stride = int(dropout_seed_stride)
+        self.dropout_step = 0
         self.episodes = _episodes(env, episodes)
         self.candidates = env.R // self.episodes
         self.env, self.template, self.R = env, template, env.R
@@ -794,7 +828,8 @@ class BatchedNeuralAutomataAgent:
                                     dtype=torch.float32, device=env.device)
 
     @classmethod
-    def from_agents(cls, env: BatchedEnv, agents: Sequence[NeuralAutomataAgent], episodes: int = 1) -> 'BatchedNeuralAutomataAgent':
+    def from_agents(cls, env: BatchedEnv, agents: Sequence[NeuralAutomataAgent], episodes: int = 1, *,
+                    dropout_seed: Optional[int] = None, dropout_seed_stride: int = 1) -> 'BatchedNeuralAutomataAgent':
         """Candidate r = agents[r]; every agent must share agents[0]'s architecture."""
         if len(agents) * _episodes(env, episodes) != env.R:
             raise ValueError(f'{len(agents)} agents for {env.R} replicas' + (f' of {episodes} episodes per candidate' if episodes != 1 else ''))
@@ -802,7 +837,7 @@ class BatchedNeuralAutomataAgent:
         for r, ag in enumerate(agents):
             if _architecture(ag) != want:
                 raise ValueError(f'agent {r}: architecture {_architecture(ag)} differs from agent 0\'s {want}')
-        return cls(env, agents[0], cls.pack(agents), episodes)
+        return cls(env, agents[0], cls.pack(agents), episodes, dropout_seed=dropout_seed, dropout_seed_stride=dropout_seed_stride)
 
     # ------------------------------------------------------------------ parameters
     @staticmethod
@@ -811,10 +846,13 @@ class BatchedNeuralAutomataAgent:
         return torch.stack([parameters_to_vector(ag.model.parameters()).detach().to(torch.float32) for ag in agents])
 
     @staticmethod
-    def unpack(template: NeuralAutomataAgent, row: torch.Tensor) -> NeuralAutomataAgent:
-        """A stand-alone agent of the template's constructor arguments whose weights are `row` (copied)."""
+    def unpack(template: NeuralAutomataAgent, row: torch.Tensor, dropout_seed: Optional[int] = None) -> NeuralAutomataAgent:
+        """A stand-alone agent of the template's constructor arguments whose weights are `row` (copied); `dropout_seed`, when
+        given, replaces the template's."""
         args = dict(template.init_params)
         args.update(args.pop('model_kwargs', {}))
+        if dropout_seed is not None:
+            args['dropout_seed'] = dropout_seed
         with torch.random.fork_rng(devices=[]):     # (the throw-away initial weights leave the caller's RNG alone)
             ag = NeuralAutomataAgent(**args)
         ag.model.train(template.model.training)
@@ -834,13 +872,37 @@ class BatchedNeuralAutomataAgent:
         return f'parameters of shape {tuple(t.shape)}: ({self.candidates}, {self.P}) expected ({rows_are} x P weights)'
 
     def candidate(self, r: int) -> NeuralAutomataAgent:
-        """Candidate r as a stand-alone NeuralAutomataAgent (on the host: `save()` the winner)."""
-        return self.unpack(self.template, self.parameters[r].cpu())
+        """Candidate r as a stand-alone NeuralAutomataAgent (on the host: `save()` the winner).  With a `dropout_seed` it carries
+        the key of its replica (with episodes: of its first replica, r·E), `dropout_seed + r·E·dropout_seed_stride`, and a
+        `dropout_step` of 0: set it to the population's counter at the step to be replayed."""
+        return self.unpack(self.template, self.parameters[r].cpu(), self._replica_dropout_seed(r * self.episodes))
+
+    def replica_agent(self, r: int) -> NeuralAutomataAgent:
+        """The stand-alone NeuralAutomataAgent replica r steps as: the weights of row r // E and, with a `dropout_seed`, the key
+        `dropout_seed + r·dropout_seed_stride` (its `dropout_step` starts at 0)."""
+        return self.unpack(self.template, self.parameters[r // self.episodes].cpu(), self._replica_dropout_seed(r))
+
+    def _replica_dropout_seed(self, r: int) -> Optional[int]:
+        return None if self.dropout_seed is None else self.dropout_seed + r * self.dropout_seed_stride
 
     def _replica_agent(self, r: int) -> NeuralAutomataAgent:
         ag = self.agents[r]                         # its candidate's row is reloaded every step: in-place writes are seen
         vector_to_parameters(self.parameters[r // self.episodes].detach(), ag.model.parameters())
+        if self.dropout_seed is not None:           # replica r's own key, at the population's counter
+            ag.dropout_seed, ag.dropout_step = self._replica_dropout_seed(r), self.dropout_step
+            ag.model.train(self.template.model.training)
         return ag
+
+    def _dropout(self) -> Optional[_lib.NcaDropout]:
+        """die_nca_dropout of the coming step, or None when nothing is masked (eval mode, p = 0)."""
+        model = self.template.model
+        if self.dropout_seed is None or not (model.agent_dropout.p > 0 and model.training):
+            return None
+        return _lib.nca_dropout(model.agent_dropout.p, self.dropout_seed, self.dropout_seed_stride, self.dropout_step)
+
+    def _stepped(self) -> None:
+        if self.dropout_seed is not None:
+            self.dropout_step += 1                  # counts forward calls, masked or not (as NeuralAutomataAgent.sense does)
 
     # ------------------------------------------------------------------ step
     def _check_step(self, env: BatchedEnv):
@@ -850,9 +912,10 @@ class BatchedNeuralAutomataAgent:
         if tuple(p.shape) != (self.candidates, self.P) or p.dtype != torch.float32 or p.device != env.device or not p.is_contiguous():
             raise ValueError(f'parameters must stay a contiguous ({self.candidates}, {self.P}) float32 tensor on {env.device}')
         model = self.template.model
-        if model.agent_dropout.p > 0 and model.training:
-            raise NotImplementedError('p_agent_dropout > 0 in training mode: its mask is a host-RNG torch op, not batched '
-                                      '(call model.eval(), or step the candidates one at a time)')
+        if model.agent_dropout.p > 0 and model.training and self.dropout_seed is None:
+            raise NotImplementedError('p_agent_dropout > 0 in training mode: without a dropout_seed its mask is a host-RNG torch op, '
+                                      'not batched (build the population with dropout_seed=S for the counter-based mask, call '
+                                      'model.eval(), or step the candidates one at a time)')
 
     def _struct(self, sense_epoch: int) -> _lib.NcaBatch:
         base = self.parameters.data_ptr()

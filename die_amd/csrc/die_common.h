@@ -39,6 +39,14 @@ __device__ __forceinline__ void die_store_result_i64(long long* p, long long v) 
 
 static inline int die_grid_for(int64_t n, int block = DIE_BLOCK) { return (int)((n + block - 1) / block); }
 
+// A checked die_nca_dropout as the words a kernel reads (die_nca.hip die_dropout_words; die_rng.h defines the mask)
+struct DropWords {
+    uint64_t seed, seed_stride;  // replica z is masked with key seed + z · seed_stride (mod 2^64)
+    uint64_t thr;                // a cell is dropped iff its word < thr = ceil(p · 2^32)
+    uint32_t step;               // the forward-call counter
+    float keep;                  // (float)(1 / (1 − p))
+};
+
 // ---- field element access (f32 / f16 planes) ---------------------------------------------
 __device__ __forceinline__ float die_ld(const float* p, int64_t i) { return p[i]; }
 __device__ __forceinline__ float die_ld(const __half* p, int64_t i) { return __half2float(p[i]); }

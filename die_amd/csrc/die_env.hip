@@ -1264,13 +1264,14 @@ extern "C" int die_physarum_env_step_batch(const die_medium* m, const die_agents
 }
 
 int die_nca_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who);       // die_nca.hip
+int die_dropout_words(const die_nca_dropout* drop, DropWords* out, const char* who);                                 // die_nca.hip
 int die_nca_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
-                        void* stream);
+                        const DropWords* drop, void* stream);
 
-extern "C" int die_nca_env_step_batch(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
-                                      const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws,
-                                      int64_t ws_bytes, void* stream) {
-    const char* who = "die_nca_env_step_batch";
+// die_nca_env_step_batch (drop null) and die_nca_env_step_batch_dropout: one body; the mask only changes the last conv launch
+static int nca_env_step_batch(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
+                              const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws, int64_t ws_bytes,
+                              const die_nca_dropout* drop, void* stream, const char* who) {
     DIE_REQUIRE(m && a && nca && d && b && results && ws, "%s: null argument", who);
     int rc = batch_ws_check(d, b, ws_bytes, who);
     if (rc != DIE_OK) return rc;
@@ -1294,9 +1295,14 @@ extern "C" int die_nca_env_step_batch(const die_medium* m, const die_agents* a, 
     int64_t nmax;
     rc = batch_step_args(k, ba, nmax, m, a, act, d, b, ws, who);
     if (rc != DIE_OK) return rc;
+    DropWords dw;
+    if (drop) {
+        rc = die_dropout_words(drop, &dw, who);
+        if (rc != DIE_OK) return rc;
+    }
     hipStream_t s = (hipStream_t)stream;
     NcaReadArgs q;
-    rc = die_nca_sense_batch(m, b, nca, &q.sense, &q.rep, stream);            // reads the claim plane at sense_epoch …
+    rc = die_nca_sense_batch(m, b, nca, &q.sense, &q.rep, drop ? &dw : nullptr, stream);   // reads the claim plane at sense_epoch …
     if (rc != DIE_OK) return rc;
     if (nca->sense_epoch == DIE_OWNER_EPOCH_MAX) {                    // … which is cleared before the tag 1 claims
         const int64_t words = (int64_t)(b->replicas - 1) * b->plane_stride + (int64_t)m->W * m->H;
@@ -1315,6 +1321,18 @@ extern "C" int die_nca_env_step_batch(const die_medium* m, const die_agents* a, 
     rc = batch_lifecycle(k, ba, grid, s, who);
     if (rc != DIE_OK) return rc;
     return batch_sweep(m, d, b, results, ws, (int)grid.x, s, who);
+}
+
+extern "C" int die_nca_env_step_batch(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
+                                      const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws,
+                                      int64_t ws_bytes, void* stream) {
+    return nca_env_step_batch(m, a, nca, act, d, b, results, ws, ws_bytes, nullptr, stream, "die_nca_env_step_batch");
+}
+
+extern "C" int die_nca_env_step_batch_dropout(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
+                                              const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws,
+                                              int64_t ws_bytes, const die_nca_dropout* drop, void* stream) {
+    return nca_env_step_batch(m, a, nca, act, d, b, results, ws, ws_bytes, drop, stream, "die_nca_env_step_batch_dropout");
 }
 
 static int deposit_feed_diffuse(const die_medium* m, const die_dynamics* d, int halo, bool tile, void* stream,

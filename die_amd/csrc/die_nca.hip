@@ -12,11 +12,18 @@
 //   die_nca_env_step_batch (a population of candidates on batched replicas) runs k_conv_circular<K, true>: the same body
 //                     with the replica in blockIdx.z (its planes, weights and outputs one stride further each); the read-out
 //                     and the step half are k_nca_move_claim_batch in die_env.hip.
+//   DROP              (k_conv_circular<K, BATCH, true>, the last layer of a stack whose agent dropout is on: die_conv2d_dropout,
+//                     die_nca_env_step_batch_dropout) multiplies the layer's outputs by the cells' dropout mask of die_rng.h in
+//                     the epilogue — one mask per (W, H) plane, shared by the output channels; nothing is stored for it.
+//   k_dropout_mask    the mask planes themselves (die_dropout_mask): 0 or keep per cell, for looking at and for the tests.
 //
 // Roofline: HBM.  A 3→3 channel 3×3 layer is 81 MAC per cell against 24 bytes per cell (3 planes in, 3 out): 6.75 flop
 // per byte, far below the ≈ 20 flop/byte at which fp32 vector math (157 TFLOP/s) meets 8 TB/s — no MFMA: the matrix
 // cores would sit idle behind the same memory stream.
+#include <math.h>
+#include <type_traits>
 #include "die_common.h"
+#include "die_rng.h"
 
 #define NCA_TX 16
 #define NCA_TY 64
@@ -33,6 +40,8 @@ struct ConvArgs {
     int64_t rep_in, rep_w, rep_out;  // batch (gridDim.z = replicas): elements from replica r's planes / weights to r + 1's
     int episodes;                // batch: replica r reads weight row r / episodes (1: a row per replica)
 };
+// what a DROP launch reads on top (the other instantiations keep ConvArgs as their whole argument)
+struct ConvDropArgs : ConvArgs { DropWords d; };
 
 // index of the cell that stands in for coordinate v of an axis of n cells, or −1 for "reads as zero" (torch.nn.functional.pad:
 // 'circular' wraps, 'zeros' pads with 0, 'reflect' mirrors WITHOUT repeating the edge cell, 'replicate' repeats it)
@@ -56,8 +65,12 @@ __device__ __forceinline__ float nca_load(const void* p, int kind, int64_t i, in
 // BATCH: replica blockIdx.z of die_nca_env_step_batch — its input planes, weights and output planes lie blockIdx.z strides
 // on; everything else (tile, LDS, summation order, tanh) is this one body.  With episodes E > 1 (a candidate evaluated on E
 // worlds) the E replicas of a candidate share one weight row: row r / E, uniform over the workgroup (one scalar division).
-template <int K, bool BATCH = false>
-__global__ __launch_bounds__(DIE_BLOCK) void k_conv_circular(ConvArgs a) {
+//
+// DROP: the epilogue multiplies by the dropout mask.  A thread owns 4 consecutive y from a multiple of 4; with H % 4 == 0 their
+// cells ix·H + iy … + 3 are one Philox block (one die_philox per thread, after the accumulation, before the stores); with any
+// other H (stand-alone layers only) the words are evaluated cell by cell — the same mask either way.
+template <int K, bool BATCH = false, bool DROP = false>
+__global__ __launch_bounds__(DIE_BLOCK) void k_conv_circular(typename std::conditional<DROP, ConvDropArgs, ConvArgs>::type a) {
     constexpr int R = K / 2, LX = NCA_TX + 2 * R, LY = NCA_TY + 2 * R + 1;     // odd pitch: conflict-free column walks
     extern __shared__ __align__(16) float nca_smem[];
     float* s_in = nca_smem;                                  // [cin][LX][LY]
@@ -104,6 +117,21 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_circular(ConvArgs a) {
     }
     const int gx = x0 + ti, gy = y0 + tj;
     if (gx >= a.W) return;
+    float mask[4] = {1.f, 1.f, 1.f, 1.f};
+    if constexpr (DROP) {
+        if (gy >= a.H) return;
+        const uint64_t key = a.d.seed + (uint64_t)blockIdx.z * a.d.seed_stride;
+        const uint64_t cell = (uint64_t)gx * (uint64_t)a.H + (uint64_t)gy;
+        if ((a.H & 3) == 0) {
+            const die_u32x4 r = die_draw(key, a.d.step, cell >> 2, DIE_STREAM_DROPOUT);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) mask[q] = die_dropout_factor(r.v[q], a.d.thr, a.d.keep);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (gy + q < a.H) mask[q] = die_dropout_factor(die_dropout_word(key, a.d.step, cell + q), a.d.thr, a.d.keep);
+        }
+    }
 #pragma unroll
     for (int o = 0; o < NCA_MAXC; ++o) {
         if (o < a.cout) {
@@ -111,6 +139,10 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_circular(ConvArgs a) {
             if (a.apply_tanh) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = tanhf(v[q]);
+            }
+            if constexpr (DROP) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = v[q] * mask[q];
             }
             float* dst = a.out[o] + rep * a.rep_out + (int64_t)gx * a.H + gy;
             if (gy + 3 < a.H && (a.H & 3) == 0) *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
@@ -122,11 +154,24 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_circular(ConvArgs a) {
     }
 }
 
+// `drop` (checked: die_dropout_words): the layer's outputs times the dropout mask, the DROP instantiation
 template <bool BATCH>
-static void launch_conv(const ConvArgs& a, int replicas, hipStream_t s) {
+static void launch_conv(const ConvArgs& a, int replicas, hipStream_t s, const DropWords* drop = nullptr) {
     const int R = a.k / 2;
     const size_t lds = ((size_t)a.cin * (NCA_TX + 2 * R) * (NCA_TY + 2 * R + 1) + (size_t)a.cout * a.cin * a.k * a.k) * sizeof(float);
     dim3 grid((a.H + NCA_TY - 1) / NCA_TY, (a.W + NCA_TX - 1) / NCA_TX, replicas);
+    if (drop) {
+        ConvDropArgs da;
+        static_cast<ConvArgs&>(da) = a;
+        da.d = *drop;
+        switch (a.k) {
+            case 1: k_conv_circular<1, BATCH, true><<<grid, DIE_BLOCK, lds, s>>>(da); break;
+            case 3: k_conv_circular<3, BATCH, true><<<grid, DIE_BLOCK, lds, s>>>(da); break;
+            case 5: k_conv_circular<5, BATCH, true><<<grid, DIE_BLOCK, lds, s>>>(da); break;
+            default: k_conv_circular<7, BATCH, true><<<grid, DIE_BLOCK, lds, s>>>(da); break;
+        }
+        return;
+    }
     switch (a.k) {
         case 1: k_conv_circular<1, BATCH><<<grid, DIE_BLOCK, lds, s>>>(a); break;
         case 3: k_conv_circular<3, BATCH><<<grid, DIE_BLOCK, lds, s>>>(a); break;
@@ -140,8 +185,19 @@ extern "C" int die_conv2d_circular(int32_t W, int32_t H, int32_t cin, const die_
     return die_conv2d(W, H, cin, in, epoch, cout, out, k, weights, apply_tanh, DIE_PAD_CIRCULAR, stream);
 }
 
-extern "C" int die_conv2d(int32_t W, int32_t H, int32_t cin, const die_conv_plane* in, int32_t epoch, int32_t cout,
-                          float* const* out, int32_t k, const float* weights, int32_t apply_tanh, int32_t padding_mode, void* stream) {
+// die_nca_dropout, checked, as the words the kernels read
+int die_dropout_words(const die_nca_dropout* drop, DropWords* out, const char* who) {
+    DIE_REQUIRE(drop, "%s: null dropout", who);
+    DIE_REQUIRE(drop->p > 0.0 && drop->p <= 1.0, "%s: dropout p = %g: 0 < p <= 1 (p = 0 is the call without a mask)", who, drop->p);   // (NaN fails both)
+    DIE_REQUIRE(drop->reserved == 0, "%s: die_nca_dropout.reserved must be 0", who);
+    out->seed = drop->seed; out->seed_stride = drop->seed_stride; out->step = drop->step;
+    out->thr = (uint64_t)ceil(drop->p * 4294967296.0);
+    out->keep = (float)(1.0 / (1.0 - drop->p));            // (p = 1: inf, never read: every word is below thr = 2^32)
+    return DIE_OK;
+}
+
+static int conv2d(int32_t W, int32_t H, int32_t cin, const die_conv_plane* in, int32_t epoch, int32_t cout, float* const* out, int32_t k,
+                  const float* weights, int32_t apply_tanh, int32_t padding_mode, const die_nca_dropout* drop, void* stream) {
     DIE_REQUIRE(padding_mode >= DIE_PAD_CIRCULAR && padding_mode <= DIE_PAD_REPLICATE, "die_conv2d: bad padding mode %d", padding_mode);
     if (padding_mode == DIE_PAD_REFLECT && (k / 2 >= W || k / 2 >= H)) {      // (torch refuses it too)
         die_set_error("die_conv2d: 'reflect' padding of %d cells needs a field larger than that (%dx%d)", k / 2, W, H);
@@ -167,8 +223,53 @@ extern "C" int die_conv2d(int32_t W, int32_t H, int32_t cin, const die_conv_plan
     a.w = weights; a.W = W; a.H = H; a.cin = cin; a.cout = cout; a.k = k; a.epoch = epoch; a.apply_tanh = apply_tanh; a.pad = padding_mode;
     a.rep_in = a.rep_w = a.rep_out = 0;
     a.episodes = 1;
-    launch_conv<false>(a, 1, (hipStream_t)stream);
+    DropWords dw;
+    if (drop) {
+        const int rc = die_dropout_words(drop, &dw, "die_conv2d_dropout");
+        if (rc != DIE_OK) return rc;
+    }
+    launch_conv<false>(a, 1, (hipStream_t)stream, drop ? &dw : nullptr);
     DIE_CHECK_LAUNCH("die_conv2d_circular");
+    return DIE_OK;
+}
+
+extern "C" int die_conv2d(int32_t W, int32_t H, int32_t cin, const die_conv_plane* in, int32_t epoch, int32_t cout,
+                          float* const* out, int32_t k, const float* weights, int32_t apply_tanh, int32_t padding_mode, void* stream) {
+    return conv2d(W, H, cin, in, epoch, cout, out, k, weights, apply_tanh, padding_mode, nullptr, stream);
+}
+
+extern "C" int die_conv2d_dropout(int32_t W, int32_t H, int32_t cin, const die_conv_plane* in, int32_t epoch, int32_t cout,
+                                  float* const* out, int32_t k, const float* weights, int32_t apply_tanh, int32_t padding_mode,
+                                  const die_nca_dropout* drop, void* stream) {
+    return conv2d(W, H, cin, in, epoch, cout, out, k, weights, apply_tanh, padding_mode, drop, stream);
+}
+
+// one thread per Philox block: cells 4i … 4i + 3 of replica blockIdx.y's plane
+__global__ __launch_bounds__(DIE_BLOCK) void k_dropout_mask(DropWords d, int64_t cells, int64_t plane_stride, float* out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (4 * i >= cells) return;
+    const die_u32x4 r = die_draw(d.seed + (uint64_t)blockIdx.y * d.seed_stride, d.step, (uint64_t)i, DIE_STREAM_DROPOUT);
+    float* dst = out + (int64_t)blockIdx.y * plane_stride + 4 * i;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        if (4 * i + q < cells) dst[q] = die_dropout_factor(r.v[q], d.thr, d.keep);
+}
+
+extern "C" int die_dropout_mask(int32_t W, int32_t H, const die_nca_dropout* drop, int32_t replicas, int64_t plane_stride, float* out,
+                                void* stream) {
+    const char* who = "die_dropout_mask";
+    DIE_REQUIRE(drop && out, "%s: null argument", who);
+    DIE_REQUIRE(W >= 1 && H >= 1, "%s: bad size %dx%d", who, W, H);
+    DIE_REQUIRE(replicas >= 1 && replicas <= DIE_MAX_REPLICAS, "%s: 1..%d replicas (got %d)", who, DIE_MAX_REPLICAS, replicas);
+    const int64_t cells = (int64_t)W * H;
+    DIE_REQUIRE(plane_stride >= cells, "%s: plane_stride %lld smaller than a plane (%lld cells)", who, (long long)plane_stride, (long long)cells);
+    DropWords dw;
+    const int rc = die_dropout_words(drop, &dw, who);
+    if (rc != DIE_OK) return rc;
+    const int64_t blocks = ((cells + 3) / 4 + DIE_BLOCK - 1) / DIE_BLOCK;
+    DIE_REQUIRE(blocks <= 0x7FFFFFFF, "%s: plane too large", who);
+    k_dropout_mask<<<dim3((unsigned)blocks, (unsigned)replicas), DIE_BLOCK, 0, (hipStream_t)stream>>>(dw, cells, plane_stride, out);
+    DIE_CHECK_LAUNCH(who);
     return DIE_OK;
 }
 
@@ -244,8 +345,9 @@ int die_nca_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t 
 }
 
 // the stack for every replica, one launch per layer; *sense = the last layer's planes of replica 0, replica r's *rep further
+// (`drop`: the checked words of die_nca_env_step_batch_dropout, or null — the last layer's launch is then the DROP one)
 int die_nca_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
-                        void* stream) {
+                        const DropWords* drop, void* stream) {
     const int64_t cells = (int64_t)m->W * m->H, rep_scratch = NCA_MAXC * cells;
     const int fkind = m->dtype == DIE_F32 ? DIE_PLANE_F32 : DIE_PLANE_F16;
     ConvArgs a = {};
@@ -263,7 +365,7 @@ int die_nca_sense_batch(const die_medium* m, const die_batch* b, const die_nca_b
         for (int o = 0; o < NCA_MAXC; ++o) a.out[o] = o < L.cout ? out + o * cells : nullptr;
         a.w = L.weights; a.rep_w = L.weight_stride; a.rep_out = rep_scratch;
         a.cin = L.cin; a.cout = L.cout; a.k = L.k; a.apply_tanh = l == nca->n_layers - 1;
-        launch_conv<true>(a, b->replicas, (hipStream_t)stream);
+        launch_conv<true>(a, b->replicas, (hipStream_t)stream, a.apply_tanh ? drop : nullptr);
         DIE_CHECK_LAUNCH("die_nca_env_step_batch(conv)");
         for (int o = 0; o < NCA_MAXC; ++o) { a.in[o] = a.out[o]; a.kind[o] = DIE_PLANE_F32; }
         a.rep_in = rep_scratch;

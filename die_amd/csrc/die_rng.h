@@ -14,6 +14,7 @@
 #define DIE_STREAM_BUILDER 7u
 #define DIE_STREAM_SEARCH 8u        // PGPE sampling (die_search.hip): oracle/rng.py normals2(seed, generation, n, stream=8, scale=1)[0]
 #define DIE_STREAM_CMAES 9u         // CMA-ES sampling (die_cmaes.hip): oracle/rng.py normals2(seed, generation, n, stream=9, scale=1)[0]
+#define DIE_STREAM_DROPOUT 10u      // agent dropout mask over cells (die_nca.hip): tests/dropout_model.py mask(seed, step, W, H, p)
 
 struct die_u32x4 { uint32_t v[4]; };
 
@@ -53,6 +54,22 @@ __host__ __device__ inline uint32_t die_turn_word(uint64_t seed, uint32_t step, 
 }
 __host__ __device__ inline uint32_t die_turn_bit(uint64_t seed, uint32_t step, uint32_t slot) {
     return (die_turn_word(seed, step, slot >> 5) >> (slot & 31u)) & 1u;
+}
+
+// Agent dropout of ConvolutionModel (core/agent/evo.py:98-118: an inverted-dropout mask over cells, drawn there from torch's
+// unseeded generator).  Here the mask is a pure function of (key, forward call, cell): for cell c = ix·H + iy, word(c) is word
+// (c & 3) of Philox(counter = (lo32(c >> 2), hi32(c >> 2), step, DROPOUT), key = seed) — die_draw(seed, step, c >> 2, DROPOUT), one
+// block per four consecutive cells; the cell is dropped iff (uint64)word < thr, thr = (uint64)ceil(p · 2^32) in float64 (p = 1:
+// thr = 2^32, every cell), and a kept cell is multiplied by keep = (float)(1 / (1 − p)).  tests/dropout_model.py is the numpy twin.
+__host__ __device__ inline uint32_t die_dropout_pick(const die_u32x4& r, uint32_t q) {     // word q & 3, by selects: see die_turn_word
+    const uint32_t lo = (q & 1u) ? r.v[1] : r.v[0], hi = (q & 1u) ? r.v[3] : r.v[2];
+    return (q & 2u) ? hi : lo;
+}
+__host__ __device__ inline uint32_t die_dropout_word(uint64_t seed, uint32_t step, uint64_t cell) {
+    return die_dropout_pick(die_draw(seed, step, cell >> 2, DIE_STREAM_DROPOUT), (uint32_t)cell & 3u);
+}
+__host__ __device__ inline float die_dropout_factor(uint32_t word, uint64_t thr, float keep) {
+    return (uint64_t)word < thr ? 0.f : keep;
 }
 
 // numerator r in [0, 1000] of `random_sample().round(3)` (core/data_init.py:168-169)

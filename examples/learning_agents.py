@@ -8,6 +8,12 @@ separable CMA-ES with stdev_init 0.1 and popsize 10 (die_amd.search.CMAES), the 
     python examples/learning_agents.py [--searcher pgpe|cmaes] [--dynamics st-perlin-wide] [--size 96] [--generations 100]
                                        [--epoch-iters 30] [--agents-die] [--max-agents alive|full|tight|N]
                                        [--reseed S] [--reseed-stride 0] [--episodes 1] [--out saved_models/agent.pt] [--time]
+                                       [--dropout P] [--dropout-seed S] [--dropout-stride K]
+
+--dropout P trains the agent with the reference's `p_agent_dropout=P` (its learning_agents.py carries 0.25): in every batched step
+replica r's sense planes are multiplied by the counter-based dropout mask of key --dropout-seed + r·--dropout-stride (default
+stride 1: every replica its own mask; 0: one mask for all, common random numbers across candidates), evaluated inside the last conv
+launch.  The mask counter runs on from generation to generation, so every generation sees new masks, and a run is reproducible.
 
 --reseed S gives every generation a new world: generation g resets the batch to the world of seed S + g·popsize, seeded on the
 device (BatchedEnv.reset(seed=...), five launches, no host read); with --reseed-stride 0 (default) every candidate of a
@@ -35,9 +41,10 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from die_amd import CMAES, PGPE, Env, NeuralAutomataAgent            # noqa: E402
+from die_amd import CMAES, PGPE, Env                                 # noqa: E402
 from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent, episode_seeds   # noqa: E402
-from population_eval import AGENT_KW, DYNAMICS, evaluate_population, make_dynamics, make_population, run_epoch, slots   # noqa: E402
+from population_eval import (DYNAMICS, dropout_keywords, evaluate_population, make_dynamics, make_population, make_template,   # noqa: E402
+                             run_epoch, slots)
 
 RADIUS_INIT = 1.5
 MAX_SPEED = RADIUS_INIT / 15.              # the reference's rule of thumb
@@ -48,12 +55,12 @@ SEARCHERS = ('pgpe', 'cmaes')
 
 
 def make_search(size, choice, popsize, epoch_iters, seed, searcher='pgpe', agents_die=False, max_agents='alive', reseed=None,
-                reseed_stride=0, episodes=1):
+                reseed_stride=0, episodes=1, drop_kw=None, dropout=0.):
     torch.manual_seed(seed)
-    template = NeuralAutomataAgent(**AGENT_KW)
+    template = make_template(dropout)
     benv = BatchedEnv((size, size), make_dynamics(choice, size, agents_die), replicas=popsize * episodes,
                       seeds=episode_seeds(seed, popsize, episodes), max_agents=max_agents)
-    pop = BatchedNeuralAutomataAgent(benv, template, episodes=episodes)
+    pop = BatchedNeuralAutomataAgent(benv, template, episodes=episodes, **(drop_kw or {}))
     if searcher == 'cmaes':
         search = CMAES(popsize, pop.P, seed=seed, **CMAES_KW)
     else:
@@ -61,12 +68,12 @@ def make_search(size, choice, popsize, epoch_iters, seed, searcher='pgpe', agent
     return search.for_population(pop, epoch_iters, reseed=reseed, reseed_stride=reseed_stride), pop
 
 
-def host_generation(size, choice, template, mean, sigma, lr, iters, seed, agents_die=False):
+def host_generation(size, choice, template, mean, sigma, lr, iters, seed, agents_die=False, drop_kw=None):
     """One generation driven from the host (population_eval.py --generations): rebuild, evaluate, read back, update."""
     R = 10
     half = torch.randn((R // 2, mean.numel()))
     noise = torch.cat([half, -half])
-    fit = evaluate_population(*make_population(size, template, mean + sigma * noise, seed, choice, agents_die), iters)
+    fit = evaluate_population(*make_population(size, template, mean + sigma * noise, seed, choice, agents_die, drop_kw=drop_kw), iters)
     f = torch.tensor(fit, dtype=torch.float32)
     f = (f - f.mean()) / (f.std() + 1e-8)
     return mean + lr / (noise.shape[0] * sigma) * (noise.T @ f)
@@ -74,7 +81,7 @@ def host_generation(size, choice, template, mean, sigma, lr, iters, seed, agents
 
 def time_device_loop(args, G, max_agents, reseed):
     searcher, pop = make_search(args.size, args.dynamics, 10, args.epoch_iters, args.seed, args.searcher, args.agents_die, max_agents,
-                                reseed, args.reseed_stride, args.episodes)
+                                reseed, args.reseed_stride, args.episodes, args.drop_kw, args.dropout)
     searcher.run(2)                                               # warm-up: first launches, allocations
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -105,11 +112,11 @@ def time_loops(args, N):
     template = pop.template
     mean = pop.parameters[0].cpu()
     for _ in range(2):
-        mean = host_generation(args.size, args.dynamics, template, mean, 0.1, 0.05, args.epoch_iters, args.seed, args.agents_die)
+        mean = host_generation(args.size, args.dynamics, template, mean, 0.1, 0.05, args.epoch_iters, args.seed, args.agents_die, args.drop_kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(G):
-        mean = host_generation(args.size, args.dynamics, template, mean, 0.1, 0.05, args.epoch_iters, args.seed, args.agents_die)
+        mean = host_generation(args.size, args.dynamics, template, mean, 0.1, 0.05, args.epoch_iters, args.seed, args.agents_die, args.drop_kw)
     torch.cuda.synchronize()
     t_host = time.perf_counter() - t0
     name = type(searcher).__name__ + '.run):'
@@ -138,7 +145,13 @@ def main():
     p.add_argument('--reseed', type=int, default=None, help='a new world every generation: seed S + g·popsize (device-seeded)')
     p.add_argument('--reseed-stride', type=int, default=0, help='0: one world per generation; 1: one per candidate and generation')
     p.add_argument('--episodes', type=int, default=1, help='worlds per candidate and generation (popsize x episodes <= 64)')
+    p.add_argument('--dropout', type=float, default=0., help='p_agent_dropout of the trained agent (0: none; the reference: 0.25)')
+    p.add_argument('--dropout-seed', type=int, default=0, help='key of the dropout masks: replica r uses seed + r·stride')
+    p.add_argument('--dropout-stride', type=int, default=1, help='0: every replica the same mask; 1: every replica its own')
     args = p.parse_args()
+    if not 0. <= args.dropout <= 1. or args.dropout_stride < 0:
+        p.error('--dropout in [0, 1], --dropout-stride >= 0')
+    args.drop_kw = dropout_keywords(args.dropout, args.dropout_seed, args.dropout_stride)
     if args.episodes < 1 or (10 if args.time else args.popsize) * args.episodes > 64:
         p.error(f'--episodes {args.episodes}: at least 1, and popsize x episodes at most 64 replicas')
     N = slots(args.max_agents or ('tight' if args.reseed is not None else 'alive'), args.size, args.dynamics, args.agents_die)
@@ -148,11 +161,12 @@ def main():
         time_loops(args, N)
         return
     searcher, pop = make_search(args.size, args.dynamics, args.popsize, args.epoch_iters, args.seed, args.searcher, args.agents_die, N,
-                                args.reseed, args.reseed_stride, args.episodes)
+                                args.reseed, args.reseed_stride, args.episodes, args.drop_kw, args.dropout)
     print(f'Network has {pop.P} parameters; {args.popsize} candidates' + (f' x {args.episodes} episodes' if args.episodes > 1 else '') +
           f' on {args.size}x{args.size} {args.dynamics}, '
           f'{args.epoch_iters} steps each, max_agents={N}' + ('' if args.reseed is None else
-          f', new worlds every generation (seed {args.reseed} + g·{args.popsize * args.episodes}, stride {args.reseed_stride})'), flush=True)
+          f', new worlds every generation (seed {args.reseed} + g·{args.popsize * args.episodes}, stride {args.reseed_stride})') +
+          (f', dropout {args.dropout} (seed {args.dropout_seed}, stride {args.dropout_stride})' if args.drop_kw else ''), flush=True)
     t0 = time.perf_counter()
     searcher.run(args.generations)
     torch.cuda.synchronize()
@@ -168,6 +182,8 @@ def main():
     os.makedirs(os.path.dirname(out) or '.', exist_ok=True)
     solution = searcher.pop_best_agent()
     solution.save(out)
+    if args.drop_kw:
+        solution.dropout_seed = args.dropout_seed                 # the replay below under the counter-based masks too
     print(f'Saving the agent to: {out}')
     # replay pop_best in its own world (the reference replays for epoch_iters * 100 steps with a plotter; here epoch_iters)
     env = Env((args.size, args.size), make_dynamics(args.dynamics, args.size, args.agents_die), seed=args.seed, max_agents='alive')

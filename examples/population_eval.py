@@ -4,6 +4,7 @@ all R worlds stepped together by die_amd.batch (L + 2 launches per step for an L
 
     python examples/population_eval.py [--replicas 10] [--size 96] [--iters 50] [--dynamics st-perlin-wide] [--generations 0] [--agents-die]
                                        [--max-agents alive|full|tight|N] [--reseed S] [--episodes 1] [--compare]
+                                       [--dropout P] [--dropout-seed S] [--dropout-stride K]
 
 --dynamics picks one of the reference's three worlds (learning_agents.py `dynamics_choice`): 'st-perlin', 'st-perlin-wide' or
 'dyn-pred', where the food flows in running waves (WaveSequence.get_flow_operator, one more launch per batched step).
@@ -15,6 +16,10 @@ BatchedEnv.reset(seed=...) in the one batch built up front, instead of a batch r
 
 --episodes E scores every candidate on E worlds (seeds seed … seed + E − 1, the same E for every candidate) in the same launches
 — replicas·E batched replicas, at most 64 — and prints the mean and the spread of its E sums.
+
+--dropout P gives the candidates the reference's `p_agent_dropout=P` (its learning_agents.py trains with 0.25) in training mode:
+replica r's sense planes are multiplied by the counter-based mask of key --dropout-seed + r·--dropout-stride (stride 0: one mask
+for every replica), new at every step, inside the last conv launch.
 
 --generations G runs a plain Gaussian evolution strategy (antithetic samples, normalised fitness) on the mean parameter
 vector — the training loop itself (evotorch's PGPE, MLflow) stays out of scope.  --compare times the same population one
@@ -63,11 +68,21 @@ def slots(spec, size, choice, agents_die=False):
     return int(spec)
 
 
-def make_population(size, template, rows, seed, choice, agents_die=False, max_agents='alive', episodes=1):
+def make_template(dropout=0.):
+    """The candidates' architecture; `dropout` > 0: with the reference's p_agent_dropout (the model stays in training mode)."""
+    return NeuralAutomataAgent(**AGENT_KW, **(dict(p_agent_dropout=dropout) if dropout > 0 else {}))
+
+
+def dropout_keywords(dropout, seed, stride):
+    """BatchedNeuralAutomataAgent's keywords for --dropout P --dropout-seed S --dropout-stride K (none for P = 0)."""
+    return dict(dropout_seed=seed, dropout_seed_stride=stride) if dropout > 0 else {}
+
+
+def make_population(size, template, rows, seed, choice, agents_die=False, max_agents='alive', episodes=1, drop_kw=None):
     C = rows.shape[0]                                  # every candidate starts on the same world (with episodes: the same E worlds)
     benv = BatchedEnv((size, size), make_dynamics(choice, size, agents_die), replicas=C * episodes, seeds=episode_seeds(seed, C, episodes),
                       max_agents=max_agents)
-    return benv, BatchedNeuralAutomataAgent(benv, template, rows, episodes=episodes)
+    return benv, BatchedNeuralAutomataAgent(benv, template, rows, episodes=episodes, **(drop_kw or {}))
 
 
 def evaluate_population(benv, pop, iters):
@@ -109,7 +124,13 @@ def main():
     p.add_argument('--max-agents', default='alive', help="slots per replica: 'alive', 'full' (W·H), 'tight' or a number")
     p.add_argument('--reseed', type=int, default=None, help='--generations on the device-seeded world of seed S + g (fixed layout)')
     p.add_argument('--episodes', type=int, default=1, help='worlds per candidate (replicas x episodes <= 64)')
+    p.add_argument('--dropout', type=float, default=0., help='p_agent_dropout of the candidates (0: none), masked on the device')
+    p.add_argument('--dropout-seed', type=int, default=0, help='key of the dropout masks: replica r uses seed + r·stride')
+    p.add_argument('--dropout-stride', type=int, default=1, help='0: every replica the same mask; 1: every replica its own')
     args = p.parse_args()
+    if not 0. <= args.dropout <= 1. or args.dropout_stride < 0:
+        p.error('--dropout in [0, 1], --dropout-stride >= 0')
+    drop_kw = dropout_keywords(args.dropout, args.dropout_seed, args.dropout_stride)
     R, E = args.replicas, args.episodes
     if E < 1 or R * E > 64:
         p.error(f'--episodes {E}: at least 1, and {R} replicas x episodes at most 64')
@@ -117,7 +138,7 @@ def main():
     if args.reseed is not None and N == 'alive':
         sys.exit("--reseed needs a fixed slot layout: --max-agents full, tight or a number")
     torch.manual_seed(args.seed)
-    template = NeuralAutomataAgent(**AGENT_KW)
+    template = make_template(args.dropout)
     cands = []
     for _ in range(R):
         template.model.init_weights()
@@ -125,9 +146,10 @@ def main():
     rows = torch.stack(cands)
     print(f'{R} candidates of {rows.shape[1]} parameters' + (f' on {E} worlds each' if E > 1 else '') +
           f', {args.size}x{args.size}, {args.iters} steps each, {args.dynamics}'
-          f'{" with agents_die" if args.agents_die else ""}, max_agents={N}', flush=True)
+          f'{" with agents_die" if args.agents_die else ""}, max_agents={N}' +
+          (f', dropout {args.dropout} (seed {args.dropout_seed}, stride {args.dropout_stride})' if drop_kw else ''), flush=True)
 
-    benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die, N, E)
+    benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die, N, E, drop_kw)
     sums = evaluate_population(benv, pop, args.iters)
     fitness = candidate_fitness(sums, E)
     for r, f in enumerate(fitness):
@@ -139,10 +161,11 @@ def main():
     if args.compare:
         # only the stepping is timed (the worlds are built before); warm-up of both paths first
         dev = torch.device('cuda')
-        agents = [pop.candidate(r // E).to(dev) for r in range(R * E)]       # replica r is stepped by its candidate's agent
-        evaluate_population(*make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die, N, E), 2)
+        agents = [pop.replica_agent(r).to(dev) for r in range(R * E)]        # replica r is stepped by its candidate's agent (and its own mask key)
+        evaluate_population(*make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die, N, E, drop_kw), 2)
         run_epoch(one_at_a_time_worlds(args.size, 1, args.seed, args.dynamics, args.agents_die, N)[0], agents[0], 2)
-        benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die, N, E)
+        agents[0].dropout_step = 0                                           # (the warm-up advanced its mask counter)
+        benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die, N, E, drop_kw)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         batched = evaluate_population(benv, pop, args.iters)
@@ -175,8 +198,9 @@ def main():
                 benv.reset(seeds=episode_seeds(args.reseed + g * E, R, E))
             fit = candidate_fitness(evaluate_population(benv, pop, args.iters), E)
         else:
-            fit = candidate_fitness(evaluate_population(*make_population(args.size, template, samples, args.seed + 1 + g * E, args.dynamics,
-                                                                         args.agents_die, N, E), args.iters), E)
+            gen_benv, gen_pop = make_population(args.size, template, samples, args.seed + 1 + g * E, args.dynamics, args.agents_die, N, E, drop_kw)
+            gen_pop.dropout_step = g * args.iters                           # (a fresh population: new masks every generation all the same)
+            fit = candidate_fitness(evaluate_population(gen_benv, gen_pop, args.iters), E)
         f = torch.tensor(fit, dtype=torch.float32)
         f = (f - f.mean()) / (f.std() + 1e-8)
         mean = mean + args.lr / (noise.shape[0] * args.sigma) * (noise.T @ f)

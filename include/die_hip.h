@@ -714,6 +714,40 @@ int die_nca_env_step_batch(const die_medium* m, const die_agents* a, const die_n
                            const die_dynamics* d, const die_batch* b, die_step_result* results, void* workspace,
                            int64_t workspace_bytes, void* stream);
 
+/* ---- Seeded agent dropout (core/agent/evo.py:98-118: ConvolutionModel's inverted-dropout mask over cells; die_nca.hip) -------
+ * New entry points only: no existing struct or call changes, so DIE_ABI_VERSION stays 24.
+ * The reference draws its mask from torch's unseeded generator; here it is a pure function of (key, forward call, cell).  For
+ * key s, forward-call counter t and cell c = ix * H + iy of a (W, H) plane:
+ *   word(c) = word (c & 3) of Philox4x32-10(counter = (lo32(c >> 2), hi32(c >> 2), t, DIE_STREAM_DROPOUT = 10), key = s): one block
+ *   per four consecutive cells; the cell is dropped iff (uint64)word(c) < thr, thr = (uint64)ceil(p * 2^32) in float64; a kept
+ *   cell is multiplied by keep = (float)(1 / (1 - p)).  p = 1 drops every cell (thr = 2^32).  One mask per plane, shared by the
+ *   layer's output channels: out = tanh(acc) * (0 or keep), one fp32 multiply — the reference's `sense_transform *= dropout_mask`.
+ * 0 < p <= 1; any other p (NaN included) is DIE_ERR_ARG, and `reserved` must be 0.  Replica r of a batch is masked with key
+ * seed + r * seed_stride (mod 2^64): stride 0 gives every replica the same mask.  Nothing is stored for the mask: the last
+ * layer's launch evaluates it in its epilogue (one Philox block per thread where H % 4 == 0), so the planes the layer writes —
+ * what die_gather_scale, the batched read-out and render() read — hold the masked values.  All arguments are checked before
+ * anything is launched. */
+typedef struct die_nca_dropout {
+    double p;
+    uint64_t seed;
+    uint64_t seed_stride;
+    uint32_t step;               /* t: the forward-call counter */
+    uint32_t reserved;
+} die_nca_dropout;
+/* die_conv2d with the mask of (drop->seed, drop->step) on its outputs (seed_stride unused); drop NULL: die_conv2d itself. */
+int die_conv2d_dropout(int32_t W, int32_t H, int32_t cin, const die_conv_plane* in, int32_t epoch, int32_t cout,
+                       float* const* out, int32_t k, const float* weights, int32_t apply_tanh, int32_t padding_mode,
+                       const die_nca_dropout* drop, void* stream);
+/* die_nca_env_step_batch whose last layer is masked, replica r with key drop->seed + r * drop->seed_stride; everything else in
+ * the step is die_nca_env_step_batch's.  drop NULL: die_nca_env_step_batch itself. */
+int die_nca_env_step_batch_dropout(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
+                                   const die_dynamics* d, const die_batch* b, die_step_result* results, void* workspace,
+                                   int64_t workspace_bytes, const die_nca_dropout* drop, void* stream);
+/* The mask planes themselves: out[r * plane_stride + c] = 0 or keep for every cell c of every replica r < replicas
+ * (1..DIE_MAX_REPLICAS; plane_stride >= W * H elements).  One launch. */
+int die_dropout_mask(int32_t W, int32_t H, const die_nca_dropout* drop, int32_t replicas, int64_t plane_stride, float* out,
+                     void* stream);
+
 /* ---- PGPE search over an (R, P) parameter matrix (die_search.hip; die_amd/search.py PGPE) ------------------------------
  * The training half of the reference's examples/learning_agents.py (evotorch's PGPE with symmetric sampling and centred
  * ranks).  R = replicas (even, 2..DIE_MAX_REPLICAS), n = R / 2 directions, P = parameters; the matrix is row-major fp32
