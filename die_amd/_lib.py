@@ -96,6 +96,11 @@ class Batch(C.Structure):
                 ('seed_stride', C.c_uint64), ('n', C.c_int64 * 64)]
 
 
+class DynamicsRow(C.Structure):      # die_dynamics_row: one replica's environment constants as the batched kernels consume them
+    _fields_ = [('rate_feed', C.c_float), ('keep', C.c_float), ('food_infinite', C.c_int32), ('radius', C.c_int32),
+                ('w', C.c_float * 9), ('reserved', C.c_float * 3)]
+
+
 PHYSARUM_PARAMS = 6
 DIE_PHYSARUM_NATURAL, DIE_PHYSARUM_UNIT = 0, 1
 
@@ -195,6 +200,15 @@ _SIGNATURES = {
     'die_batch_lifecycle_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int64]),
     'die_forward_env_step_batch': (C.c_int, [_P(Medium), _P(Agents), _P(GradientAgent), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
                                              C.c_void_p, C.c_int64, C.c_void_p]),
+    'die_dynamics_rows': (C.c_int, [_P(Dynamics), C.c_int32, C.c_int32, C.c_int32, _P(DynamicsRow)]),
+    'die_forward_env_step_batch_rows': (C.c_int, [_P(Medium), _P(Agents), _P(GradientAgent), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
+                                                  C.c_void_p, C.c_int64, C.c_void_p, _P(DynamicsRow), C.c_void_p]),
+    'die_physarum_env_step_batch_rows': (C.c_int, [_P(Medium), _P(Agents), _P(GradientAgent), C.c_void_p, _P(Action), _P(Dynamics), _P(Batch),
+                                                   C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, _P(DynamicsRow), C.c_void_p]),
+    'die_nca_env_step_batch_rows': (C.c_int, [_P(Medium), _P(Agents), _P(NcaBatch), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
+                                              C.c_void_p, C.c_int64, _P(NcaDropout), C.c_void_p, _P(DynamicsRow), C.c_void_p]),
+    'die_food_flow_batch_masked': (C.c_int, [_P(Medium), _P(Batch), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_uint64,
+                                             C.c_uint64, C.c_void_p]),
     'die_physarum_decode_batch': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(ParameterSpace), C.c_void_p, C.c_void_p, C.c_void_p]),
     'die_physarum_decode_episodes': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _P(ParameterSpace), C.c_void_p, C.c_void_p,
                                                C.c_void_p]),

@@ -38,7 +38,14 @@ searchers fold the E sums of a candidate into its fitness (tests/test_gpu_episod
 Agent dropout: `BatchedNeuralAutomataAgent(..., dropout_seed=S, dropout_seed_stride=K)` trains a template with
 `p_agent_dropout > 0` — replica r's sense planes are multiplied by the counter-based mask of key S + r·K at the population's
 `dropout_step`, inside the last conv launch (`die_nca_env_step_batch_dropout`); replica r is then the stand-alone run of
-`NeuralAutomataAgent(dropout_seed=S + r·K)`, bit for bit (tests/test_gpu_dropout.py)."""
+`NeuralAutomataAgent(dropout_seed=S + r·K)`, bit for bit (tests/test_gpu_dropout.py).
+
+Per-replica Dynamics: `BatchedEnv(field_size, dynamics=[d_0 … d_{R-1}], replicas=R)` puts replica r under d_r — rate_feed,
+rate_decay_chem, diffuse_sigma, food_infinite and whether the (one) food-flow operator reaches it may differ, everything else must
+agree.  Replica r is then `Env(field_size, d_r, seed=seeds[r], max_agents=...)`, bit for bit: the kernels fetch replica r's row of a
+device table built once at construction (`die_dynamics_rows`), the field sweep is launched once per gaussian radius present, and
+the flow is applied under a replica mask (`die_food_flow_batch_masked`).  `episode_dynamics` lays E dynamics out for a population
+with `episodes=E`: `episode_fitness[:, e]` of a searcher is then the score under dynamics e (tests/test_gpu_dynamics_rows.py)."""
 import ctypes as C
 import dataclasses
 import math
@@ -68,16 +75,28 @@ class BatchedEnv:
     replica from the same world (how a population of candidates is compared).
 
     `max_agents`: 'alive' (default) gives replica r exactly its K_r seeded agents; an int N, or None for W·H, gives every
-    replica N slots (alive first, then dead ones) — the layout `reset(seed=...)` needs, since a new world has a new K_r."""
+    replica N slots (alive first, then dead ones) — the layout `reset(seed=...)` needs, since a new world has a new K_r.
 
-    def __init__(self, field_size: Tuple[int, int], dynamics: Optional[Dynamics] = None, *, replicas: int, seed: int = 0,
+    `dynamics`: one `Dynamics` for every replica, or a sequence of R of them (replica r lives under dynamics[r]: domain
+    randomisation, a robustness sweep).  In a sequence rate_feed, rate_decay_chem, diffuse_sigma and food_infinite may differ;
+    op_food_flow is, per entry, the identity or ONE device operator object (it advances once per batched step and reaches the
+    replicas that name it); boundary, op_action_cost, strict_cost, agents_die, compat and init_agent_ratio must agree.
+    `replica_dynamics(r)` returns replica r's; `dynamics` keeps the shared fields (those of dynamics[0], with the operator).
+    A single `Dynamics` takes the launches it always took."""
+
+    def __init__(self, field_size: Tuple[int, int], dynamics: Union[Dynamics, Sequence[Dynamics], None] = None, *, replicas: int, seed: int = 0,
                  field_dtype: torch.dtype = torch.float32, device=None, per_replica: Optional[bool] = None,
                  seeds: Optional[Sequence[int]] = None, max_agents: Union[str, int, None] = 'alive'):
         if not 1 <= replicas <= 64:
             raise ValueError('1..64 replicas')
         if seeds is not None and len(seeds) != replicas:
             raise ValueError(f'{len(seeds)} seeds for {replicas} replicas')
-        self.dynamics = dynamics or Dynamics()
+        self._dyn = None                            # a sequence was given: replica r's Dynamics
+        self._flow_mask = None                      # … and the replicas its flow operator reaches (bit r)
+        if dynamics is not None and not isinstance(dynamics, Dynamics):
+            self.dynamics, self._dyn, self._flow_mask = _shared_dynamics(dynamics, replicas)
+        else:
+            self.dynamics = dynamics or Dynamics()
         d = self.dynamics
         if d.agents_die and d.compat != 'intended':
             raise NotImplementedError(f"batched replicas: agents_die with compat={d.compat!r} (the host-driven frozen-indexer "
@@ -106,8 +125,8 @@ class BatchedEnv:
         self.per_replica = (self.W * self.H >= Env.PIC_MIN_CELLS) if per_replica is None else bool(per_replica)
         if self.per_replica:
             # every replica Env gets its own Dynamics: its flow operator is its own (step keeps the counters in line)
-            self.envs = [Env(field_size, dataclasses.replace(d), seed=self.seeds[r], max_agents=slots, field_dtype=field_dtype,
-                             device=self.device, sync=False) for r in range(self.R)]
+            self.envs = [Env(field_size, dataclasses.replace(self.replica_dynamics(r)), seed=self.seeds[r], max_agents=slots,
+                             field_dtype=field_dtype, device=self.device, sync=False) for r in range(self.R)]
             self.n = [e.agents.N for e in self.envs]
             self.Nmax = max(self.n)
             self.streams = [torch.cuda.Stream(device=self.device) for _ in range(self.R)]
@@ -151,9 +170,21 @@ class BatchedEnv:
         if self._fixed is not None:                 # reset(seed=...): die_init_batch's scan workspace and (K_r, overflow) words
             self._init_ws = torch.zeros(int(_lib.lib.die_init_batch_workspace_bytes(W, H, R)), dtype=torch.uint8, device=dev)
             self._counts = torch.zeros((R, 2), dtype=torch.int64, device=dev)
+        self._rows = self._rows_host = None
+        if self._dyn is not None:                   # the table the kernels read: built once, not state (reset leaves it alone)
+            self._rows_host = (_lib.DynamicsRow * R)()
+            structs = (_lib.Dynamics * R)(*[self._dynamics_struct(q) for q in self._dyn])
+            _lib.check(_lib.lib.die_dynamics_rows(structs, R, W, H, self._rows_host), 'die_dynamics_rows')
+            self._rows = torch.frombuffer(bytearray(bytes(self._rows_host)), dtype=torch.uint8).to(dev)
         self._steps = 0
         self._initial = (self._state.clone(), self.chem, self.chem_next)
         self._flow_k0 = getattr(self.dynamics.op_food_flow, '_k', None)
+
+    def replica_dynamics(self, r: int) -> Dynamics:
+        """The Dynamics replica r lives under: dynamics[r] of a sequence, else the one `dynamics`."""
+        if not 0 <= r < self.R:
+            raise IndexError(f'replica {r} of {self.R}')
+        return self.dynamics if self._dyn is None else self._dyn[r]
 
     def reset(self, *, seed: Optional[int] = None, seed_stride: int = 1, seeds: Optional[Sequence[int]] = None) -> None:
         """Every replica back to the state it was constructed in: bit for bit a fresh BatchedEnv of the same arguments (and a
@@ -242,13 +273,14 @@ class BatchedEnv:
         m = _lib.Medium(self.W, self.H, fdt, self.epoch, _ptr(self.owner), _ptr(self.food), _ptr(self.chem), _ptr(self.chem_next),
                         0, 0, 0, 0, 0, 0, 0, 0, None)
         a = _lib.Agents(self.Nmax, _ptr(self.x), _ptr(self.y), _ptr(self.alive), _ptr(self.agent_food), None)
-        d = self.dynamics
+        b = _lib.Batch(self.R, 0, self.W * self.H, self.Nmax, 1, (C.c_int64 * 64)(*self.n))
+        return m, a, self._dynamics_struct(self.dynamics), b
+
+    def _dynamics_struct(self, d: Dynamics) -> _lib.Dynamics:
         boundary = _lib.DIE_BOUNDARY_WRAP if d.boundary == BoundaryCondition.wrap else _lib.DIE_BOUNDARY_LIMIT
         cost = _lib.DIE_COST_LINEAR if d.op_action_cost is linear_action_cost else _lib.DIE_COST_ZERO
-        dyn = _lib.Dynamics(d.rate_feed, d.rate_decay_chem, d.diffuse_sigma, boundary, cost, 0.02, 0.01, int(d.food_infinite), int(d.agents_die),
-                            int(self._fixed is not None), 0, 0)
-        b = _lib.Batch(self.R, 0, self.W * self.H, self.Nmax, 1, (C.c_int64 * 64)(*self.n))
-        return m, a, dyn, b
+        return _lib.Dynamics(d.rate_feed, d.rate_decay_chem, d.diffuse_sigma, boundary, cost, 0.02, 0.01, int(d.food_infinite), int(d.agents_die),
+                             int(self._fixed is not None), 0, 0)
 
     def check(self):
         """Synchronise; raise if a replica's tile-binned step reported a bookkeeping error since the last check (per-replica
@@ -286,9 +318,15 @@ class BatchedEnv:
             self.epoch = 1
         m, a, dyn, b = self._structs()
         g = agent._struct()
-        _lib.check(_lib.lib.die_forward_env_step_batch(C.byref(m), C.byref(a), C.byref(g), None, C.byref(dyn), C.byref(b), _ptr(results),
-                                                       _ptr(self._ws), self._ws.numel(), stream_ptr(self.device)),
-                   'die_forward_env_step_batch')
+        if self._rows is None:
+            _lib.check(_lib.lib.die_forward_env_step_batch(C.byref(m), C.byref(a), C.byref(g), None, C.byref(dyn), C.byref(b), _ptr(results),
+                                                           _ptr(self._ws), self._ws.numel(), stream_ptr(self.device)),
+                       'die_forward_env_step_batch')
+        else:                                       # per-replica Dynamics: the same step, each replica under its row
+            _lib.check(_lib.lib.die_forward_env_step_batch_rows(C.byref(m), C.byref(a), C.byref(g), None, C.byref(dyn), C.byref(b),
+                                                                _ptr(results), _ptr(self._ws), self._ws.numel(), _ptr(self._rows),
+                                                                self._rows_host, stream_ptr(self.device)),
+                       'die_forward_env_step_batch_rows')
         agent._calls += 1
         self.chem, self.chem_next = self.chem_next, self.chem
         self._food_flow(flow, m, b)
@@ -311,9 +349,15 @@ class BatchedEnv:
             self.epoch = 1
         m, a, dyn, b = self._structs()
         g = pop._struct()
-        _lib.check(_lib.lib.die_physarum_env_step_batch(C.byref(m), C.byref(a), C.byref(g), _ptr(pop._table), None, C.byref(dyn), C.byref(b),
-                                                        _ptr(results), _ptr(self._ws), self._ws.numel(), stream_ptr(self.device)),
-                   'die_physarum_env_step_batch')
+        if self._rows is None:
+            _lib.check(_lib.lib.die_physarum_env_step_batch(C.byref(m), C.byref(a), C.byref(g), _ptr(pop._table), None, C.byref(dyn), C.byref(b),
+                                                            _ptr(results), _ptr(self._ws), self._ws.numel(), stream_ptr(self.device)),
+                       'die_physarum_env_step_batch')
+        else:
+            _lib.check(_lib.lib.die_physarum_env_step_batch_rows(C.byref(m), C.byref(a), C.byref(g), _ptr(pop._table), None, C.byref(dyn),
+                                                                 C.byref(b), _ptr(results), _ptr(self._ws), self._ws.numel(),
+                                                                 _ptr(self._rows), self._rows_host, stream_ptr(self.device)),
+                       'die_physarum_env_step_batch_rows')
         pop._calls += 1
         self.chem, self.chem_next = self.chem_next, self.chem
         self._food_flow(flow, m, b)
@@ -336,7 +380,13 @@ class BatchedEnv:
         self.epoch = sense_epoch % _lib.OWNER_EPOCH_MAX + 1
         m, a, dyn, b = self._structs()
         nca = agent._struct(sense_epoch)
-        if drop is None:
+        name = 'die_nca_env_step_batch' if drop is None else 'die_nca_env_step_batch_dropout'
+        if self._rows is not None:                  # per-replica Dynamics: one entry for both, the mask nullable
+            name = 'die_nca_env_step_batch_rows'
+            rc = _lib.lib.die_nca_env_step_batch_rows(C.byref(m), C.byref(a), C.byref(nca), None, C.byref(dyn), C.byref(b), _ptr(results),
+                                                      _ptr(self._ws), self._ws.numel(), None if drop is None else C.byref(drop),
+                                                      _ptr(self._rows), self._rows_host, stream_ptr(self.device))
+        elif drop is None:
             rc = _lib.lib.die_nca_env_step_batch(C.byref(m), C.byref(a), C.byref(nca), None, C.byref(dyn), C.byref(b), _ptr(results),
                                                  _ptr(self._ws), self._ws.numel(), stream_ptr(self.device))
         else:                                       # the same step, its last conv launch masked
@@ -345,7 +395,7 @@ class BatchedEnv:
                                                          stream_ptr(self.device))
         if rc != _lib.DIE_OK:
             self.epoch = sense_epoch                # refused before any launch: nothing changed
-            _lib.check(rc, 'die_nca_env_step_batch' if drop is None else 'die_nca_env_step_batch_dropout')
+            _lib.check(rc, name)
         agent._calls += 1
         agent._stepped()
         self.chem, self.chem_next = self.chem_next, self.chem
@@ -372,14 +422,20 @@ class BatchedEnv:
         op = self.dynamics.op_food_flow
         seq = op.seq
         octaves, seed = (seq._octaves, seq._seed & 0xFFFFFFFFFFFFFFFF) if flow == _lib.DIE_FLOW_PERLIN else (0, 0)
-        _lib.check(_lib.lib.die_food_flow_batch(C.byref(m), C.byref(b), flow, op.next_t(), op.scale, op.decay, octaves, seed,
-                                                stream_ptr(self.device)), 'die_food_flow_batch')
+        if self._flow_mask is None:
+            _lib.check(_lib.lib.die_food_flow_batch(C.byref(m), C.byref(b), flow, op.next_t(), op.scale, op.decay, octaves, seed,
+                                                    stream_ptr(self.device)), 'die_food_flow_batch')
+        else:                                       # per-replica Dynamics: the replicas that name the operator
+            _lib.check(_lib.lib.die_food_flow_batch_masked(C.byref(m), C.byref(b), flow, op.next_t(), op.scale, op.decay, octaves, seed,
+                                                           self._flow_mask, stream_ptr(self.device)), 'die_food_flow_batch_masked')
 
     def _step_per_replica(self, agent, replica_agent, flow: Optional[int], results: torch.Tensor) -> torch.Tensor:
         """Large worlds: replica r is its own Env stepped by `replica_agent(r)` on its own stream.  With a flow, each Env gets
         an operator of its own over the batch's sequence, at the batch's counter: all apply the same t, each on its stream."""
         op = self.dynamics.op_food_flow
-        for e in self.envs:
+        for r, e in enumerate(self.envs):
+            if flow is not None and self._flow_mask is not None and not (self._flow_mask >> r) & 1:
+                continue                            # per-replica Dynamics: this replica's food does not flow (it keeps the identity)
             e.dynamics.op_food_flow = op if flow is None else DeviceFoodFlow(op.seq, op.scale, op.decay)
             if flow is not None:
                 e.dynamics.op_food_flow._k = op._k
@@ -430,6 +486,48 @@ def episode_seeds(seed: int, candidates: int, episodes: int, candidate_stride: i
             raise ValueError(f'{name}={v!r}: an integer >= {low}')
     seed, C_, E, stride = int(seed), int(candidates), int(episodes), int(candidate_stride)
     return [seed + e + stride * c * E for c in range(C_) for e in range(E)]
+
+
+def episode_dynamics(dynamics: Sequence[Dynamics], candidates: int) -> List[Dynamics]:
+    """The R = candidates·E dynamics of `BatchedEnv(dynamics=...)` for a population with `episodes=E = len(dynamics)`, in
+    candidate-major order: replica c·E + e gets dynamics[e] — every candidate is scored under every listed dynamics, and a
+    searcher's `episode_fitness[:, e]` is the score under dynamics[e].  The twin of `episode_seeds`."""
+    dynamics = list(dynamics)
+    if not dynamics or not all(isinstance(q, Dynamics) for q in dynamics):
+        raise ValueError('dynamics: a non-empty sequence of Dynamics')
+    if isinstance(candidates, bool) or int(candidates) != candidates or int(candidates) < 1:
+        raise ValueError(f'candidates={candidates!r}: an integer >= 1')
+    return [dynamics[e] for _ in range(int(candidates)) for e in range(len(dynamics))]
+
+
+_MUST_AGREE = ('boundary', 'op_action_cost', 'strict_cost', 'agents_die', 'agents_born', 'compat', 'init_agent_ratio', 'apply_sense_mask',
+               'diffuse_mode')
+
+
+def _shared_dynamics(dynamics, replicas: int):
+    """A sequence of per-replica Dynamics, checked: (the Dynamics of the shared fields, the list, the flow's replica mask)."""
+    dyn = list(dynamics)
+    if len(dyn) != replicas:
+        raise ValueError(f'{len(dyn)} dynamics for {replicas} replicas')
+    for r, q in enumerate(dyn):
+        if not isinstance(q, Dynamics):
+            raise TypeError(f'dynamics[{r}]: a Dynamics, not {type(q).__name__}')
+    first, op, mask = dyn[0], None, 0
+    for r, q in enumerate(dyn):
+        for name in _MUST_AGREE:
+            u, v = getattr(q, name), getattr(first, name)
+            if (u is not v) if callable(u) or callable(v) else (u != v):
+                raise ValueError(f'replica {r}: dynamics[{r}].{name}={u!r} differs from dynamics[0].{name}={v!r} — {name} must agree '
+                                 'across the replicas of a batch (rate_feed, rate_decay_chem, diffuse_sigma, food_infinite and the '
+                                 'food flow may differ)')
+        if q.op_food_flow is not _identity_food_flow:
+            if op is None:
+                op = q.op_food_flow
+            elif q.op_food_flow is not op:
+                raise ValueError(f'replica {r}: dynamics[{r}].op_food_flow is a second food-flow operator — every entry takes the '
+                                 'identity or the SAME operator object (it advances once per batched step)')
+            mask |= 1 << r
+    return dataclasses.replace(first, op_food_flow=_identity_food_flow if op is None else op), dyn, mask
 
 
 def _episodes(env, episodes) -> int:

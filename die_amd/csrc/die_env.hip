@@ -185,6 +185,17 @@ __device__ __forceinline__ void batch_stash(StepArgs& a, const BatchArgs& b, int
     }
 }
 
+// Per-replica Dynamics (die_*_env_step_batch_rows): the batched claim kernels take the device table of die_dynamics_row as an
+// optional last argument (`ROWS...`: nothing, or `const die_dynamics_row*`).  Given, replica r's row is fetched once per
+// workgroup ahead of the loop — uniform and read-only, so scalar loads, as k_physarum_move_claim_batch reads its table —
+// into the by-value StepArgs, so the loop body is the instruction stream of the shared-Dynamics kernel; not given, the kernel is
+// the shared-Dynamics kernel itself.  (The claim pass reads rate_feed only; k_lifecycle_batch reads neither, so it takes no row.)
+__device__ __forceinline__ void dynamics_row_args(StepArgs&, int) {}
+__device__ __forceinline__ void dynamics_row_args(StepArgs& a, const int r, const die_dynamics_row* __restrict__ rows) {
+    const die_dynamics_row row = rows[r];
+    a.rate_feed = row.rate_feed; a.food_infinite = row.food_infinite;
+}
+
 // replica r's arrays, agent count, Philox key and workspace partials
 template <typename T>
 __device__ __forceinline__ void batch_replica_args(FwdArgs& f, StepArgs& a, const BatchArgs& b, const int r) {
@@ -202,10 +213,11 @@ __device__ __forceinline__ void batch_replica_args(FwdArgs& f, StepArgs& a, cons
     batch_stash(a, b, r);
 }
 
-template <typename T, int KIND, bool LEAN = false>
-__global__ __launch_bounds__(DIE_STEP_BLOCK) void k_forward_move_claim_batch(FwdArgs f, StepArgs a, BatchArgs b) {
+template <typename T, int KIND, bool LEAN = false, typename... ROWS>
+__global__ __launch_bounds__(DIE_STEP_BLOCK) void k_forward_move_claim_batch(FwdArgs f, StepArgs a, BatchArgs b, ROWS... rows) {
     if (LEAN) fwd_args_lean(f);
     const int r = blockIdx.y;
+    dynamics_row_args(a, r, rows...);
     batch_replica_args<T>(f, a, b, r);
     forward_move_claim_body<T, KIND, false>(f, a);
     // every slot is alive: the sweep's reduction reads the count here (with dead slots, k_lifecycle_batch counts them)
@@ -216,15 +228,16 @@ __global__ __launch_bounds__(DIE_STEP_BLOCK) void k_forward_move_claim_batch(Fwd
 // place of the shared scale / deposit / sense_offset / angles / tolerance and the constants derived from them.  The row is
 // uniform over the workgroup and read-only: one 64-byte scalar load into the by-value FwdArgs, ahead of the loop, so the
 // loop reads the same scalar registers it reads in the shared-parameter kernel.
-template <typename T, bool LEAN>
+template <typename T, bool LEAN, typename... ROWS>
 __global__ __launch_bounds__(DIE_STEP_BLOCK) void k_physarum_move_claim_batch(FwdArgs f, StepArgs a, BatchArgs b,
-                                                                              const die_physarum_row* __restrict__ table) {
+                                                                              const die_physarum_row* __restrict__ table, ROWS... rows) {
     if (LEAN) fwd_args_lean(f);
     const int r = blockIdx.y;
     const die_physarum_row row = table[r];
     f.scale = row.scale; f.deposit = row.deposit; f.sense_offset = row.sense_offset;
     f.turn_rad = row.turn_radians; f.sense_rad = row.sense_radians; f.rtol = row.turn_tolerance;
     f.x_turn = row.x_turn; f.atol = row.atol; f.c_turn = row.c_turn; f.c_sense = row.c_sense;
+    dynamics_row_args(a, r, rows...);
     batch_replica_args<T>(f, a, b, r);
     forward_move_claim_body<T, DIE_AGENT_PHYSARUM, false>(f, a);
     if (!a.has_dead && blockIdx.x == 0 && threadIdx.x == 0) a.part_alive[0] = a.N;
@@ -239,9 +252,10 @@ struct NcaReadArgs {
     float* act[3];                 // replica 0's action arrays (agent_stride apart), or NULL
 };
 
-template <typename T>
-__global__ __launch_bounds__(DIE_STEP_BLOCK) void k_nca_move_claim_batch(NcaReadArgs q, StepArgs a, BatchArgs b) {
+template <typename T, typename... ROWS>
+__global__ __launch_bounds__(DIE_STEP_BLOCK) void k_nca_move_claim_batch(NcaReadArgs q, StepArgs a, BatchArgs b, ROWS... rows) {
     const int r = blockIdx.y;
+    dynamics_row_args(a, r, rows...);
     const int64_t pc = b.cells * r, pa = b.agents * r;
     a.owner += pc; a.food = (T*)a.food + pc; a.chem = (T*)a.chem + pc;
     a.x += pa; a.y += pa; a.alive += pa; a.agent_food += pa;
@@ -481,19 +495,40 @@ template <> struct Vec4<__half> {
     }
 };
 
-template <typename T, int R, int FUSED, bool WRAP>
-__global__ __launch_bounds__(DIF_BLOCK) void k_diffuse_rows(RowsArgs a) {
+// Per-replica Dynamics: the batched fused sweep of the replicas of ONE gaussian radius takes a table as an optional last argument
+// (`TABLE...`: nothing, or a RowsTable).  Workgroup plane blockIdx.z then sweeps replica idx[blockIdx.z] with the taps, keep,
+// rate_feed and food_infinite of that replica's row — scalar loads into the by-value RowsArgs ahead of the sweep, which
+// is the instantiation (and so the arithmetic per cell) a stand-alone world of that sigma takes.  The index list travels by value;
+// 64 rows would not fit the kernarg segment comfortably, hence the device table.
+struct RowsTable {
+    const die_dynamics_row* rows;
+    int32_t n;
+    uint8_t idx[DIE_MAX_REPLICAS];
+};
+
+__device__ __forceinline__ unsigned rows_replica(RowsArgs&, int) { return blockIdx.z; }
+__device__ __forceinline__ unsigned rows_replica(RowsArgs& a, const int R, const RowsTable& t) {
+    const unsigned z = t.idx[blockIdx.z];
+    const die_dynamics_row row = t.rows[z];
+    a.keep = row.keep; a.rate_feed = row.rate_feed; a.food_infinite = row.food_infinite;
+    for (int k = 0; k <= 2 * R; ++k) a.w[k] = row.w[k];
+    return z;
+}
+
+template <typename T, int R, int FUSED, bool WRAP, typename... TABLE>
+__global__ __launch_bounds__(DIF_BLOCK) void k_diffuse_rows(RowsArgs a, TABLE... table) {
     static_assert(R >= 1 && R <= 4, "one halo lane of 4 columns per side");
-    if (gridDim.z > 1) {                                    // replica blockIdx.z of a batch: same shape, arrays one stride apart
-        const int64_t pc = a.rep_cells * blockIdx.z;
+    const unsigned z = rows_replica(a, R, table...);        // the replica of a batch this workgroup sweeps
+    if (sizeof...(TABLE) > 0 || gridDim.z > 1) {            // replica z of a batch: same shape, arrays one stride apart
+        const int64_t pc = a.rep_cells * z;
         a.src = (const T*)a.src + pc; a.dst = (T*)a.dst + pc;
         if (FUSED == 1) a.claim += pc;
         if (FUSED) a.food = (T*)a.food + pc;
         if (a.result) {
-            a.part_gain += (int64_t)DIE_MAX_PARTIALS * 3 * blockIdx.z;
-            if (a.part_gain2) a.part_gain2 += (int64_t)DIE_MAX_PARTIALS * 3 * blockIdx.z;
-            if (a.part_alive) a.part_alive += (int64_t)DIE_MAX_PARTIALS * 3 * blockIdx.z;
-            a.result += blockIdx.z;
+            a.part_gain += (int64_t)DIE_MAX_PARTIALS * 3 * z;
+            if (a.part_gain2) a.part_gain2 += (int64_t)DIE_MAX_PARTIALS * 3 * z;
+            if (a.part_alive) a.part_alive += (int64_t)DIE_MAX_PARTIALS * 3 * z;
+            a.result += z;
         }
     }
     const int row0 = FUSED && a.result ? 1 : 0;             // grid rows ahead of the field's
@@ -1161,10 +1196,87 @@ static int batch_lifecycle(const StepArgs& k, const BatchArgs& ba, dim3 grid, hi
     return DIE_OK;
 }
 
+// Per-replica Dynamics: launch_rows' grid for the `grp.n` replicas of radius R (the rows-per-wave choice is the whole batch's, so
+// a batch of one radius is launched in the shared-Dynamics sweep's shape)
+template <typename T>
+static void launch_rows_table(RowsArgs a, int R, const RowsTable& grp, int replicas, hipStream_t s) {
+    const int strips = (a.H + DIF_WCOLS - 1) / DIF_WCOLS;
+    constexpr int WPB = DIF_BLOCK / DIE_WAVE;
+    a.rpw = rows_per_wave(a.W, a.H, replicas);
+    dim3 grid((strips + WPB - 1) / WPB, (a.W + a.rpw - 1) / a.rpw + 1, grp.n);
+    switch (R) {
+        case 1: k_diffuse_rows<T, 1, 1, true, RowsTable><<<grid, DIF_BLOCK, 0, s>>>(a, grp); break;
+        case 2: k_diffuse_rows<T, 2, 1, true, RowsTable><<<grid, DIF_BLOCK, 0, s>>>(a, grp); break;
+        case 3: k_diffuse_rows<T, 3, 1, true, RowsTable><<<grid, DIF_BLOCK, 0, s>>>(a, grp); break;
+        default: k_diffuse_rows<T, 4, 1, true, RowsTable><<<grid, DIF_BLOCK, 0, s>>>(a, grp); break;
+    }
+}
+
+// the sweep of a batch with per-replica rows: one launch per radius present among rows_host (checked to lie in 1..4)
+static int batch_sweep_rows(const die_medium* m, const RowsArgs& ra, const die_batch* b, hipStream_t s, const char* who,
+                            const die_dynamics_row* rows, const die_dynamics_row* rows_host) {
+    for (int R = 1; R <= 4; ++R) {
+        RowsTable grp;
+        grp.rows = rows;
+        grp.n = 0;
+        for (int r = 0; r < DIE_MAX_REPLICAS; ++r) grp.idx[r] = 0;
+        for (int r = 0; r < b->replicas; ++r)
+            if (rows_host[r].radius == R) grp.idx[grp.n++] = (uint8_t)r;
+        if (!grp.n) continue;
+        if (m->dtype == DIE_F32) launch_rows_table<float>(ra, R, grp, b->replicas, s);
+        else launch_rows_table<__half>(ra, R, grp, b->replicas, s);
+        DIE_CHECK_LAUNCH(who);
+    }
+    return DIE_OK;
+}
+
+// both tables of a *_rows entry point, after the parent's own checks
+static int batch_rows_check(const die_batch* b, const die_dynamics_row* rows, const die_dynamics_row* rows_host, const char* who) {
+    DIE_REQUIRE(rows, "%s: null dynamics rows (rows == NULL)", who);
+    DIE_REQUIRE(rows_host, "%s: null host copy of the dynamics rows (rows_host == NULL)", who);
+    for (int r = 0; r < b->replicas; ++r)
+        DIE_REQUIRE(rows_host[r].radius >= 1 && rows_host[r].radius <= 4, "%s: row %d has radius %d, outside 1..4", who, r, rows_host[r].radius);
+    return DIE_OK;
+}
+
+extern "C" int die_dynamics_rows(const die_dynamics* d, int32_t n, int32_t W, int32_t H, die_dynamics_row* rows_host) {
+    const char* who = "die_dynamics_rows";
+    DIE_REQUIRE(d && rows_host, "%s: null argument", who);
+    DIE_REQUIRE(n >= 1 && n <= DIE_MAX_REPLICAS, "%s: %d rows, 1..%d expected", who, n, DIE_MAX_REPLICAS);
+    DIE_REQUIRE(W >= 1 && H >= 1, "%s: bad size %dx%d", who, W, H);
+    for (int r = 0; r < n; ++r) {
+        const int R = (int)(4.0 * (double)d[r].diffuse_sigma + 0.5);
+        if (!(d[r].diffuse_sigma > 0.f) || R < 1 || !rows_kernel_applies(W, H, R)) {       // fused_step_applies, per row
+            die_set_error("%s: row %d: only for periodic planes with H %% 4 == 0 and gaussian radius 1..4 (W=%d H=%d sigma=%g radius %d)", who,
+                          r, W, H, (double)d[r].diffuse_sigma, R);
+            return DIE_ERR_UNSUPPORTED;
+        }
+        DIE_REQUIRE(d[r].diffuse_mode == DIE_DIFFUSE_WRAP, "%s: row %d: diffuse_mode %d: only WRAP is batched", who, r, d[r].diffuse_mode);
+        DIE_REQUIRE(!d[r].staged, "%s: row %d: staged steps are not batched", who, r);
+        DIE_REQUIRE(d[r].boundary == d[0].boundary, "%s: row %d disagrees with row 0 in boundary (%d != %d)", who, r, d[r].boundary, d[0].boundary);
+        DIE_REQUIRE(d[r].cost == d[0].cost, "%s: row %d disagrees with row 0 in cost (%d != %d)", who, r, d[r].cost, d[0].cost);
+        DIE_REQUIRE(d[r].cost_w_deposit == d[0].cost_w_deposit && d[r].cost_w_dist == d[0].cost_w_dist,
+                    "%s: row %d disagrees with row 0 in the cost weights", who, r);
+        DIE_REQUIRE(!d[r].agents_die == !d[0].agents_die, "%s: row %d disagrees with row 0 in agents_die", who, r);
+        DIE_REQUIRE(!d[r].has_dead_slots == !d[0].has_dead_slots, "%s: row %d disagrees with row 0 in has_dead_slots", who, r);
+    }
+    for (int r = 0; r < n; ++r) {
+        die_dynamics_row row = {};
+        double wd[2 * DIF_MAXR + 1];
+        row.radius = gaussian_taps(d[r].diffuse_sigma, wd);
+        row.rate_feed = d[r].rate_feed;
+        row.keep = (float)(1.0 - (double)d[r].rate_decay_chem);
+        row.food_infinite = d[r].food_infinite ? 1 : 0;
+        for (int k = 0; k <= 2 * row.radius; ++k) row.w[k] = (float)wd[k];
+        rows_host[r] = row;
+    }
+    return DIE_OK;
+}
+
 // the field sweep of every replica in one launch (gridDim.z), each with its own reduction workgroup over the n_part partials
 // (and, with dead slots, over the lifecycle pass's n_part partial gains too)
 static int batch_sweep(const die_medium* m, const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws, int n_part,
-                       hipStream_t s, const char* who) {
+                       hipStream_t s, const char* who, const die_dynamics_row* rows = nullptr, const die_dynamics_row* rows_host = nullptr) {
     const int R = (int)(4.0 * (double)d->diffuse_sigma + 0.5);
     RowsArgs ra;
     double wd[2 * DIF_MAXR + 1];
@@ -1177,16 +1289,18 @@ static int batch_sweep(const die_medium* m, const die_dynamics* d, const die_bat
     ra.result = results; ra.alive_const = 0;
     ra.keep = (float)(1.0 - (double)d->rate_decay_chem); ra.rate_feed = d->rate_feed;
     for (int q = 0; q <= 2 * R; ++q) ra.w[q] = (float)wd[q];
+    if (rows) return batch_sweep_rows(m, ra, b, s, who, rows, rows_host);
     const int rc = m->dtype == DIE_F32 ? launch_rows<float, 1, true>(ra, R, s, b->replicas) : launch_rows<__half, 1, true>(ra, R, s, b->replicas);
     if (rc != DIE_OK) return rc;
     DIE_CHECK_LAUNCH(who);
     return DIE_OK;
 }
 
-extern "C" int die_forward_env_step_batch(const die_medium* m, const die_agents* a, die_gradient_agent* g, const die_action* act,
-                                          const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws,
-                                          int64_t ws_bytes, void* stream) {
-    const char* who = "die_forward_env_step_batch";
+// die_forward_env_step_batch (with_rows false) and die_forward_env_step_batch_rows: one body
+static int forward_env_step_batch(const die_medium* m, const die_agents* a, die_gradient_agent* g, const die_action* act,
+                                  const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws, int64_t ws_bytes,
+                                  bool with_rows, const die_dynamics_row* rows, const die_dynamics_row* rows_host, void* stream,
+                                  const char* who) {
     DIE_REQUIRE(m && a && g && d && b && results && ws, "%s: null argument", who);
     int rc = batch_ws_check(d, b, ws_bytes, who);
     if (rc != DIE_OK) return rc;
@@ -1205,27 +1319,50 @@ extern "C" int die_forward_env_step_batch(const die_medium* m, const die_agents*
     int64_t nmax;
     rc = batch_step_args(k, ba, nmax, m, a, act, d, b, ws, who);
     if (rc != DIE_OK) return rc;
+    if (with_rows) {
+        rc = batch_rows_check(b, rows, rows_host, who);
+        if (rc != DIE_OK) return rc;
+    }
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(step_grid(nmax), b->replicas);
+#define DIE_FMCB(T, KIND, LEAN) do { \
+        if (with_rows) k_forward_move_claim_batch<T, KIND, LEAN, const die_dynamics_row*><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba, rows); \
+        else k_forward_move_claim_batch<T, KIND, LEAN><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba); } while (0)
     if (m->dtype == DIE_F32) {
-        if (g->kind != DIE_AGENT_PHYSARUM) k_forward_move_claim_batch<float, DIE_AGENT_GRADIENT><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba);
-        else if (fwd_is_lean(g)) k_forward_move_claim_batch<float, DIE_AGENT_PHYSARUM, true><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba);
-        else k_forward_move_claim_batch<float, DIE_AGENT_PHYSARUM><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba);
+        if (g->kind != DIE_AGENT_PHYSARUM) DIE_FMCB(float, DIE_AGENT_GRADIENT, false);
+        else if (fwd_is_lean(g)) DIE_FMCB(float, DIE_AGENT_PHYSARUM, true);
+        else DIE_FMCB(float, DIE_AGENT_PHYSARUM, false);
     } else {
-        if (g->kind != DIE_AGENT_PHYSARUM) k_forward_move_claim_batch<__half, DIE_AGENT_GRADIENT><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba);
-        else if (fwd_is_lean(g)) k_forward_move_claim_batch<__half, DIE_AGENT_PHYSARUM, true><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba);
-        else k_forward_move_claim_batch<__half, DIE_AGENT_PHYSARUM><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba);
+        if (g->kind != DIE_AGENT_PHYSARUM) DIE_FMCB(__half, DIE_AGENT_GRADIENT, false);
+        else if (fwd_is_lean(g)) DIE_FMCB(__half, DIE_AGENT_PHYSARUM, true);
+        else DIE_FMCB(__half, DIE_AGENT_PHYSARUM, false);
     }
+#undef DIE_FMCB
     DIE_CHECK_LAUNCH(who);
     rc = batch_lifecycle(k, ba, grid, s, who);
     if (rc != DIE_OK) return rc;
-    return batch_sweep(m, d, b, results, ws, (int)grid.x, s, who);
+    return batch_sweep(m, d, b, results, ws, (int)grid.x, s, who, rows, rows_host);
 }
 
-extern "C" int die_physarum_env_step_batch(const die_medium* m, const die_agents* a, die_gradient_agent* g, const die_physarum_row* table,
-                                           const die_action* act, const die_dynamics* d, const die_batch* b, die_step_result* results,
-                                           void* ws, int64_t ws_bytes, void* stream) {
-    const char* who = "die_physarum_env_step_batch";
+extern "C" int die_forward_env_step_batch(const die_medium* m, const die_agents* a, die_gradient_agent* g, const die_action* act,
+                                          const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws,
+                                          int64_t ws_bytes, void* stream) {
+    return forward_env_step_batch(m, a, g, act, d, b, results, ws, ws_bytes, false, nullptr, nullptr, stream, "die_forward_env_step_batch");
+}
+
+extern "C" int die_forward_env_step_batch_rows(const die_medium* m, const die_agents* a, die_gradient_agent* g, const die_action* act,
+                                               const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws,
+                                               int64_t ws_bytes, const die_dynamics_row* rows, const die_dynamics_row* rows_host,
+                                               void* stream) {
+    return forward_env_step_batch(m, a, g, act, d, b, results, ws, ws_bytes, true, rows, rows_host, stream,
+                                  "die_forward_env_step_batch_rows");
+}
+
+// die_physarum_env_step_batch (with_rows false) and die_physarum_env_step_batch_rows: one body
+static int physarum_env_step_batch(const die_medium* m, const die_agents* a, die_gradient_agent* g, const die_physarum_row* table,
+                                   const die_action* act, const die_dynamics* d, const die_batch* b, die_step_result* results,
+                                   void* ws, int64_t ws_bytes, bool with_rows, const die_dynamics_row* rows,
+                                   const die_dynamics_row* rows_host, void* stream, const char* who) {
     DIE_REQUIRE(m && a && g && d && b && results && ws, "%s: null argument", who);
     DIE_REQUIRE(table, "%s: null parameter table", who);
     int rc = batch_ws_check(d, b, ws_bytes, who);
@@ -1248,19 +1385,41 @@ extern "C" int die_physarum_env_step_batch(const die_medium* m, const die_agents
     int64_t nmax;
     rc = batch_step_args(k, ba, nmax, m, a, act, d, b, ws, who);
     if (rc != DIE_OK) return rc;
+    if (with_rows) {
+        rc = batch_rows_check(b, rows, rows_host, who);
+        if (rc != DIE_OK) return rc;
+    }
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(step_grid(nmax), b->replicas);
+#define DIE_PMCB(T, LEAN) do { if (with_rows) k_physarum_move_claim_batch<T, LEAN, const die_dynamics_row*><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba, table, rows); \
+                               else k_physarum_move_claim_batch<T, LEAN><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba, table); } while (0)
     if (m->dtype == DIE_F32) {
-        if (fwd_is_lean(g)) k_physarum_move_claim_batch<float, true><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba, table);
-        else k_physarum_move_claim_batch<float, false><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba, table);
+        if (fwd_is_lean(g)) DIE_PMCB(float, true);
+        else DIE_PMCB(float, false);
     } else {
-        if (fwd_is_lean(g)) k_physarum_move_claim_batch<__half, true><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba, table);
-        else k_physarum_move_claim_batch<__half, false><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba, table);
+        if (fwd_is_lean(g)) DIE_PMCB(__half, true);
+        else DIE_PMCB(__half, false);
     }
+#undef DIE_PMCB
     DIE_CHECK_LAUNCH(who);
     rc = batch_lifecycle(k, ba, grid, s, who);
     if (rc != DIE_OK) return rc;
-    return batch_sweep(m, d, b, results, ws, (int)grid.x, s, who);
+    return batch_sweep(m, d, b, results, ws, (int)grid.x, s, who, rows, rows_host);
+}
+
+extern "C" int die_physarum_env_step_batch(const die_medium* m, const die_agents* a, die_gradient_agent* g, const die_physarum_row* table,
+                                           const die_action* act, const die_dynamics* d, const die_batch* b, die_step_result* results,
+                                           void* ws, int64_t ws_bytes, void* stream) {
+    return physarum_env_step_batch(m, a, g, table, act, d, b, results, ws, ws_bytes, false, nullptr, nullptr, stream,
+                                   "die_physarum_env_step_batch");
+}
+
+extern "C" int die_physarum_env_step_batch_rows(const die_medium* m, const die_agents* a, die_gradient_agent* g,
+                                                const die_physarum_row* table, const die_action* act, const die_dynamics* d,
+                                                const die_batch* b, die_step_result* results, void* ws, int64_t ws_bytes,
+                                                const die_dynamics_row* rows, const die_dynamics_row* rows_host, void* stream) {
+    return physarum_env_step_batch(m, a, g, table, act, d, b, results, ws, ws_bytes, true, rows, rows_host, stream,
+                                   "die_physarum_env_step_batch_rows");
 }
 
 int die_nca_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who);       // die_nca.hip
@@ -1271,7 +1430,8 @@ int die_nca_sense_batch(const die_medium* m, const die_batch* b, const die_nca_b
 // die_nca_env_step_batch (drop null) and die_nca_env_step_batch_dropout: one body; the mask only changes the last conv launch
 static int nca_env_step_batch(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
                               const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws, int64_t ws_bytes,
-                              const die_nca_dropout* drop, void* stream, const char* who) {
+                              const die_nca_dropout* drop, void* stream, const char* who, bool with_rows = false,
+                              const die_dynamics_row* rows = nullptr, const die_dynamics_row* rows_host = nullptr) {
     DIE_REQUIRE(m && a && nca && d && b && results && ws, "%s: null argument", who);
     int rc = batch_ws_check(d, b, ws_bytes, who);
     if (rc != DIE_OK) return rc;
@@ -1300,6 +1460,10 @@ static int nca_env_step_batch(const die_medium* m, const die_agents* a, const di
         rc = die_dropout_words(drop, &dw, who);
         if (rc != DIE_OK) return rc;
     }
+    if (with_rows) {
+        rc = batch_rows_check(b, rows, rows_host, who);
+        if (rc != DIE_OK) return rc;
+    }
     hipStream_t s = (hipStream_t)stream;
     NcaReadArgs q;
     rc = die_nca_sense_batch(m, b, nca, &q.sense, &q.rep, drop ? &dw : nullptr, stream);   // reads the claim plane at sense_epoch …
@@ -1315,12 +1479,24 @@ static int nca_env_step_batch(const die_medium* m, const die_agents* a, const di
     for (int c = 0; c < 3; ++c) q.coef[c] = nca->coef[c];
     q.act[0] = act ? act->dx : nullptr; q.act[1] = act ? act->dy : nullptr; q.act[2] = act ? act->deposit : nullptr;
     dim3 grid(step_grid(nmax), b->replicas);
-    if (m->dtype == DIE_F32) k_nca_move_claim_batch<float><<<grid, DIE_STEP_BLOCK, 0, s>>>(q, k, ba);
-    else k_nca_move_claim_batch<__half><<<grid, DIE_STEP_BLOCK, 0, s>>>(q, k, ba);
+    if (with_rows) {
+        if (m->dtype == DIE_F32) k_nca_move_claim_batch<float, const die_dynamics_row*><<<grid, DIE_STEP_BLOCK, 0, s>>>(q, k, ba, rows);
+        else k_nca_move_claim_batch<__half, const die_dynamics_row*><<<grid, DIE_STEP_BLOCK, 0, s>>>(q, k, ba, rows);
+    } else {
+        if (m->dtype == DIE_F32) k_nca_move_claim_batch<float><<<grid, DIE_STEP_BLOCK, 0, s>>>(q, k, ba);
+        else k_nca_move_claim_batch<__half><<<grid, DIE_STEP_BLOCK, 0, s>>>(q, k, ba);
+    }
     DIE_CHECK_LAUNCH(who);
     rc = batch_lifecycle(k, ba, grid, s, who);
     if (rc != DIE_OK) return rc;
-    return batch_sweep(m, d, b, results, ws, (int)grid.x, s, who);
+    return batch_sweep(m, d, b, results, ws, (int)grid.x, s, who, rows, rows_host);
+}
+
+extern "C" int die_nca_env_step_batch_rows(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
+                                           const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws,
+                                           int64_t ws_bytes, const die_nca_dropout* drop, const die_dynamics_row* rows,
+                                           const die_dynamics_row* rows_host, void* stream) {
+    return nca_env_step_batch(m, a, nca, act, d, b, results, ws, ws_bytes, drop, stream, "die_nca_env_step_batch_rows", true, rows, rows_host);
 }
 
 extern "C" int die_nca_env_step_batch(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,

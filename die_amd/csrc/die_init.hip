@@ -642,9 +642,47 @@ static void launch_food_flow_batch(int32_t kind, T* food, int W, int H, int R, i
     else k_food_flow_batch<T, DIE_FLOW_PERLIN><<<grid, DIE_BLOCK, 0, s>>>(food, W, H, R, plane_stride, t, scale, keep, octaves, seed);
 }
 
+// die_food_flow_batch_masked: the same update on the replicas whose bit is set.  A row of workgroups per replica (blockIdx.y);
+// those of an unset replica exit at once, so a replica without a flow costs no memory traffic.  Each replica's workgroups
+// evaluate the field themselves — the expression of k_food_flow_batch, token for token, so a full mask leaves its bits.
+template <typename T, int KIND>
+__global__ __launch_bounds__(DIE_BLOCK) void k_food_flow_batch_masked(T* food, int W, int H, int64_t plane_stride, double t, double scale,
+                                                                      double keep, double octaves, uint64_t seed, uint64_t mask) {
+    if (!((mask >> blockIdx.y) & 1ull)) return;
+    food += (int64_t)blockIdx.y * plane_stride;
+    const int64_t total = (int64_t)W * H;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const int gi = (int)(i / H), gj = (int)(i - (int64_t)gi * H);
+        const double z = KIND == DIE_FLOW_WAVE ? flow_wave_z(gi, gj, W, H, t) : flow_perlin_z(gi, gj, W, H, t, octaves, seed);
+        const float v = die_ld(food, i);
+        die_st(food, i, (float)(scale * z + keep * (double)v));
+    }
+}
+
+template <typename T>
+static void launch_food_flow_batch_masked(int32_t kind, T* food, int W, int H, int R, int64_t plane_stride, double t, double scale,
+                                          double keep, double octaves, uint64_t seed, uint64_t mask, hipStream_t s) {
+    const dim3 grid(init_grid((int64_t)W * H), R);
+    if (kind == DIE_FLOW_WAVE) k_food_flow_batch_masked<T, DIE_FLOW_WAVE><<<grid, DIE_BLOCK, 0, s>>>(food, W, H, plane_stride, t, scale, keep, octaves, seed, mask);
+    else k_food_flow_batch_masked<T, DIE_FLOW_PERLIN><<<grid, DIE_BLOCK, 0, s>>>(food, W, H, plane_stride, t, scale, keep, octaves, seed, mask);
+}
+
+static int food_flow_batch(const die_medium* m, const die_batch* b, int32_t kind, double t, double scale, double decay, int32_t octaves,
+                           uint64_t seed, bool masked, uint64_t mask, void* stream, const char* who);
+
 extern "C" int die_food_flow_batch(const die_medium* m, const die_batch* b, int32_t kind, double t, double scale, double decay,
                                    int32_t octaves, uint64_t seed, void* stream) {
-    const char* who = "die_food_flow_batch";
+    return food_flow_batch(m, b, kind, t, scale, decay, octaves, seed, false, 0, stream, "die_food_flow_batch");
+}
+
+extern "C" int die_food_flow_batch_masked(const die_medium* m, const die_batch* b, int32_t kind, double t, double scale, double decay,
+                                          int32_t octaves, uint64_t seed, uint64_t replica_mask, void* stream) {
+    return food_flow_batch(m, b, kind, t, scale, decay, octaves, seed, true, replica_mask, stream, "die_food_flow_batch_masked");
+}
+
+static int food_flow_batch(const die_medium* m, const die_batch* b, int32_t kind, double t, double scale, double decay, int32_t octaves,
+                           uint64_t seed, bool masked, uint64_t mask, void* stream, const char* who) {
     DIE_REQUIRE(m && b && m->food, "%s: null argument", who);
     DIE_REQUIRE(b->replicas >= 1 && b->replicas <= DIE_MAX_REPLICAS, "%s: %d replicas, 1..%d expected", who, b->replicas, DIE_MAX_REPLICAS);
     DIE_REQUIRE(kind == DIE_FLOW_WAVE || kind == DIE_FLOW_PERLIN, "%s: unknown flow kind %d", who, kind);
@@ -657,6 +695,15 @@ extern "C" int die_food_flow_batch(const die_medium* m, const die_batch* b, int3
     DIE_REQUIRE(b->plane_stride >= (int64_t)m->W * m->H, "%s: plane_stride %lld smaller than a replica's %dx%d plane", who,
                 (long long)b->plane_stride, m->W, m->H);
     const hipStream_t s = (hipStream_t)stream;
+    if (masked) {
+        DIE_REQUIRE(b->replicas == 64 || !(mask >> b->replicas), "%s: replica_mask %#llx has bits beyond the %d replicas", who,
+                    (unsigned long long)mask, b->replicas);
+        if (!mask) return DIE_OK;
+        if (m->dtype == DIE_F32) launch_food_flow_batch_masked(kind, (float*)m->food, m->W, m->H, b->replicas, b->plane_stride, t, scale, 1.0 - decay, (double)octaves, seed, mask, s);
+        else launch_food_flow_batch_masked(kind, (__half*)m->food, m->W, m->H, b->replicas, b->plane_stride, t, scale, 1.0 - decay, (double)octaves, seed, mask, s);
+        DIE_CHECK_LAUNCH(who);
+        return DIE_OK;
+    }
     if (m->dtype == DIE_F32) launch_food_flow_batch(kind, (float*)m->food, m->W, m->H, b->replicas, b->plane_stride, t, scale, 1.0 - decay, (double)octaves, seed, s);
     else launch_food_flow_batch(kind, (__half*)m->food, m->W, m->H, b->replicas, b->plane_stride, t, scale, 1.0 - decay, (double)octaves, seed, s);
     DIE_CHECK_LAUNCH(who);

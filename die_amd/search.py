@@ -83,7 +83,8 @@ class _PopulationSearch:
     @property
     def episode_fitness(self) -> torch.Tensor:
         """(C, E) float64 on the device: candidate c's sum of terms on each of its E worlds in the last `tell` (`fitness` is
-        their mean, summed in episode order); the spread over e is the luck of the worlds.  E = 1: `fitness` as a column."""
+        their mean, summed in episode order); the spread over e is the luck of the worlds.  E = 1: `fitness` as a column.
+        On a `BatchedEnv(dynamics=episode_dynamics(dynamics, C))` column e is the score under dynamics[e]."""
         return self.fitness.view(self.R, 1) if self._episode_fitness is None else self._episode_fitness
 
     def _fold_buffers(self, episodes: int):

@@ -15,6 +15,11 @@ replica r's sense planes are multiplied by the counter-based dropout mask of key
 stride 1: every replica its own mask; 0: one mask for all, common random numbers across candidates), evaluated inside the last conv
 launch.  The mask counter runs on from generation to generation, so every generation sees new masks, and a run is reproducible.
 
+--dynamics takes one of the reference's three worlds or a comma list of them (e.g. st-perlin,st-perlin-wide,dyn-pred): every candidate
+is then scored under EVERY listed dynamics each generation, in the same launches (BatchedEnv(dynamics=[...]): per-replica Dynamics;
+episode e lives under dynamics e mod len).  The list implies --episodes len(list) unless --episodes is given (then a multiple of it);
+the fitness is the mean over the episodes, and the mean of `episode_fitness` under each dynamics is printed with the history.
+
 --reseed S gives every generation a new world: generation g resets the batch to the world of seed S + g·popsize, seeded on the
 device (BatchedEnv.reset(seed=...), five launches, no host read); with --reseed-stride 0 (default) every candidate of a
 generation shares that world, with 1 each gets its own.  It needs a fixed slot layout (--max-agents; 'tight' when not given).
@@ -43,8 +48,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from die_amd import CMAES, PGPE, Env                                 # noqa: E402
 from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent, episode_seeds   # noqa: E402
-from population_eval import (DYNAMICS, dropout_keywords, evaluate_population, make_dynamics, make_population, make_template,   # noqa: E402
-                             run_epoch, slots)
+from population_eval import (DYNAMICS, batch_dynamics, dropout_keywords, dynamics_names, evaluate_population, make_dynamics,   # noqa: E402
+                             make_population, make_template, per_dynamics_means, resolve_episodes, run_epoch, slots)
 
 RADIUS_INIT = 1.5
 MAX_SPEED = RADIUS_INIT / 15.              # the reference's rule of thumb
@@ -58,7 +63,7 @@ def make_search(size, choice, popsize, epoch_iters, seed, searcher='pgpe', agent
                 reseed_stride=0, episodes=1, drop_kw=None, dropout=0.):
     torch.manual_seed(seed)
     template = make_template(dropout)
-    benv = BatchedEnv((size, size), make_dynamics(choice, size, agents_die), replicas=popsize * episodes,
+    benv = BatchedEnv((size, size), batch_dynamics(choice, size, agents_die, popsize, episodes), replicas=popsize * episodes,
                       seeds=episode_seeds(seed, popsize, episodes), max_agents=max_agents)
     pop = BatchedNeuralAutomataAgent(benv, template, episodes=episodes, **(drop_kw or {}))
     if searcher == 'cmaes':
@@ -131,7 +136,7 @@ def time_loops(args, N):
 def main():
     p = argparse.ArgumentParser()
     p.add_argument('--searcher', choices=SEARCHERS, default='pgpe', help='PGPE (the reference\'s) or separable CMA-ES')
-    p.add_argument('--dynamics', choices=DYNAMICS, default='st-perlin-wide')
+    p.add_argument('--dynamics', default='st-perlin-wide', help=f'one of {", ".join(DYNAMICS)}, or a comma list: every candidate on each')
     p.add_argument('--size', type=int, default=96)
     p.add_argument('--popsize', type=int, default=10)
     p.add_argument('--generations', type=int, default=100, help='epochs of the reference: search generations')
@@ -144,7 +149,8 @@ def main():
                                                       "'tight' (default with --reseed) or a number")
     p.add_argument('--reseed', type=int, default=None, help='a new world every generation: seed S + g·popsize (device-seeded)')
     p.add_argument('--reseed-stride', type=int, default=0, help='0: one world per generation; 1: one per candidate and generation')
-    p.add_argument('--episodes', type=int, default=1, help='worlds per candidate and generation (popsize x episodes <= 64)')
+    p.add_argument('--episodes', type=int, default=None, help='worlds per candidate and generation (popsize x episodes <= 64); default 1, '
+                                                               'or the length of a --dynamics list (then a multiple of it)')
     p.add_argument('--dropout', type=float, default=0., help='p_agent_dropout of the trained agent (0: none; the reference: 0.25)')
     p.add_argument('--dropout-seed', type=int, default=0, help='key of the dropout masks: replica r uses seed + r·stride')
     p.add_argument('--dropout-stride', type=int, default=1, help='0: every replica the same mask; 1: every replica its own')
@@ -152,6 +158,11 @@ def main():
     if not 0. <= args.dropout <= 1. or args.dropout_stride < 0:
         p.error('--dropout in [0, 1], --dropout-stride >= 0')
     args.drop_kw = dropout_keywords(args.dropout, args.dropout_seed, args.dropout_stride)
+    try:
+        names = dynamics_names(args.dynamics)
+        args.episodes = resolve_episodes(names, args.episodes) if len(names) > 1 else (1 if args.episodes is None else args.episodes)
+    except ValueError as err:
+        p.error(str(err))
     if args.episodes < 1 or (10 if args.time else args.popsize) * args.episodes > 64:
         p.error(f'--episodes {args.episodes}: at least 1, and popsize x episodes at most 64 replicas')
     N = slots(args.max_agents or ('tight' if args.reseed is not None else 'alive'), args.size, args.dynamics, args.agents_die)
@@ -168,14 +179,21 @@ def main():
           f', new worlds every generation (seed {args.reseed} + g·{args.popsize * args.episodes}, stride {args.reseed_stride})') +
           (f', dropout {args.dropout} (seed {args.dropout_seed}, stride {args.dropout_stride})' if args.drop_kw else ''), flush=True)
     t0 = time.perf_counter()
-    searcher.run(args.generations)
+    per_episode = []                                              # a list of dynamics: every generation's (C, E) sums, kept on the device
+    if len(names) > 1:
+        for _ in range(args.generations):
+            searcher.step()
+            per_episode.append(searcher.episode_fitness.clone())
+    else:
+        searcher.run(args.generations)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     pop.env.check()
     col = '|grad|' if args.searcher == 'pgpe' else 'sigma'
     for g, (mean, best, worst, median, col4, sd) in enumerate(searcher.history().tolist()):
+        under = '' if not per_episode else '  ' + '  '.join(f'{q} {v:.4f}' for q, v in per_dynamics_means(args.dynamics, per_episode[g].cpu()))
         print(f'generation {g:4d}: mean {mean:10.4f}  median {median:10.4f}  best {best:10.4f}  worst {worst:10.4f}  '
-              f'{col} {col4:.4f}  stdev {sd:.5f}')
+              f'{col} {col4:.4f}  stdev {sd:.5f}{under}')
     st = searcher.status
     print(f'{args.generations} generations in {dt:.2f} s; best eval {st["best_eval"]:.4f}, last pop_best {st["pop_best_eval"]:.4f}')
     out = args.out or os.path.join('saved_models', f'neuralautomataagent_{args.searcher}_{args.generations}x{args.epoch_iters}.pt')
@@ -186,7 +204,7 @@ def main():
         solution.dropout_seed = args.dropout_seed                 # the replay below under the counter-based masks too
     print(f'Saving the agent to: {out}')
     # replay pop_best in its own world (the reference replays for epoch_iters * 100 steps with a plotter; here epoch_iters)
-    env = Env((args.size, args.size), make_dynamics(args.dynamics, args.size, args.agents_die), seed=args.seed, max_agents='alive')
+    env = Env((args.size, args.size), make_dynamics(names[0], args.size, args.agents_die), seed=args.seed, max_agents='alive')   # (a list: its first)
     reward = run_epoch(env, solution.to(torch.device('cuda')), args.epoch_iters)
     print(f'Final reward of the pop_best solution over {args.epoch_iters} steps: {reward:.4f}  (its generation: {st["pop_best_eval"]:.4f})')
 

@@ -8,6 +8,9 @@ all R worlds stepped together by die_amd.batch (L + 2 launches per step for an L
 
 --dynamics picks one of the reference's three worlds (learning_agents.py `dynamics_choice`): 'st-perlin', 'st-perlin-wide' or
 'dyn-pred', where the food flows in running waves (WaveSequence.get_flow_operator, one more launch per batched step).
+A comma list (e.g. st-perlin,st-perlin-wide,dyn-pred) scores every candidate under EVERY listed dynamics in the same launches
+(BatchedEnv(dynamics=[...]): per-replica Dynamics): it implies --episodes len(list) unless --episodes is given, which must then be a
+multiple of it (episode e lives under dynamics e mod len), and the mean score under each dynamics is printed.
 --agents-die adds the death pressure (Dynamics(agents_die=True): starved agents are zeroed; one more launch per batched step).
 --max-agents picks the replicas' slot layout: 'alive' (K_r slots, the seeded agents), 'full' (W·H, the reference's default),
 'tight' (the expected count plus six standard deviations) or a number; every layout but 'alive' runs the dead-slot pass.
@@ -38,7 +41,7 @@ from torch.nn.utils import parameters_to_vector
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from die_amd import Dynamics, Env, NeuralAutomataAgent, WaveSequence    # noqa: E402
-from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent, episode_seeds   # noqa: E402
+from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent, episode_dynamics, episode_seeds   # noqa: E402
 
 AGENT_KW = dict(kernel_sizes=[3, 3], scale=0.01, deposit=2.0)           # learning_agents.py
 DYNAMICS = ('st-perlin', 'st-perlin-wide', 'dyn-pred')
@@ -55,6 +58,45 @@ def make_dynamics(choice, size, agents_die=False):
                     agents_die=agents_die)
 
 
+def dynamics_names(spec):
+    """--dynamics: one name or a comma list of names -> the list, every name checked."""
+    names = [q.strip() for q in spec.split(',')]
+    for q in names:
+        if q not in DYNAMICS:
+            raise ValueError(f'--dynamics {q!r}: one of {", ".join(DYNAMICS)} (or a comma list of them)')
+    return names
+
+
+def resolve_episodes(names, episodes):
+    """--episodes for a --dynamics list of L names: L when not given (None), else a multiple of L."""
+    if episodes is None:
+        return len(names)
+    if episodes < 1 or episodes % len(names):
+        raise ValueError(f'--episodes {episodes}: a multiple of the {len(names)} dynamics of --dynamics')
+    return episodes
+
+
+def batch_dynamics(choice, size, agents_die, candidates, episodes):
+    """BatchedEnv's `dynamics` for --dynamics `choice`: the one Dynamics of a single name; for a list of L names the C·E per-replica
+    Dynamics in candidate-major order, episode e under dynamics e mod L ('dyn-pred' entries share ONE flow operator)."""
+    names = dynamics_names(choice)
+    if len(names) == 1:
+        return make_dynamics(names[0], size, agents_die)
+    made = {q: make_dynamics(q, size, agents_die) for q in set(names)}
+    return episode_dynamics([made[names[e % len(names)]] for e in range(episodes)], candidates)
+
+
+def per_dynamics_means(choice, episode_sums):
+    """(name, mean over candidates and that name's episodes) for a (C, E) nested list / tensor of per-episode sums."""
+    names = dynamics_names(choice)
+    rows = [list(map(float, row)) for row in episode_sums]
+    out = []
+    for j, q in enumerate(names):
+        vals = [row[e] for row in rows for e in range(j, len(row), len(names))]
+        out.append((q, sum(vals) / len(vals)))
+    return out
+
+
 def slots(spec, size, choice, agents_die=False):
     """BatchedEnv max_agents of a --max-agents value: 'alive', 'full' (None: W·H), 'tight' or a number.  'tight' is the expected
     number of seeded agents plus six standard deviations, a bound every seed of the example's worlds stays under."""
@@ -63,7 +105,7 @@ def slots(spec, size, choice, agents_die=False):
     if spec == 'full':
         return None
     if spec == 'tight':
-        p, cells = make_dynamics(choice, size, agents_die).init_agent_ratio, size * size
+        p, cells = make_dynamics(dynamics_names(choice)[0], size, agents_die).init_agent_ratio, size * size
         return math.ceil(p * cells + 6.0 * math.sqrt(p * (1.0 - p) * cells))
     return int(spec)
 
@@ -80,8 +122,8 @@ def dropout_keywords(dropout, seed, stride):
 
 def make_population(size, template, rows, seed, choice, agents_die=False, max_agents='alive', episodes=1, drop_kw=None):
     C = rows.shape[0]                                  # every candidate starts on the same world (with episodes: the same E worlds)
-    benv = BatchedEnv((size, size), make_dynamics(choice, size, agents_die), replicas=C * episodes, seeds=episode_seeds(seed, C, episodes),
-                      max_agents=max_agents)
+    benv = BatchedEnv((size, size), batch_dynamics(choice, size, agents_die, C, episodes), replicas=C * episodes,
+                      seeds=episode_seeds(seed, C, episodes), max_agents=max_agents)
     return benv, BatchedNeuralAutomataAgent(benv, template, rows, episodes=episodes, **(drop_kw or {}))
 
 
@@ -106,7 +148,9 @@ def run_epoch(env, agent, iters):
 
 
 def one_at_a_time_worlds(size, R, seed, choice, agents_die=False, max_agents='alive', episodes=1):
-    return [Env((size, size), make_dynamics(choice, size, agents_die), seed=q, max_agents=max_agents) for q in episode_seeds(seed, R, episodes)]
+    names = dynamics_names(choice)                   # replica c·E + e lives under dynamics e mod L, with a flow operator of its own
+    return [Env((size, size), make_dynamics(names[(r % episodes) % len(names)], size, agents_die), seed=q, max_agents=max_agents)
+            for r, q in enumerate(episode_seeds(seed, R, episodes))]
 
 
 def main():
@@ -114,7 +158,7 @@ def main():
     p.add_argument('--replicas', type=int, default=10)
     p.add_argument('--size', type=int, default=96)
     p.add_argument('--iters', type=int, default=50, help='epoch_iters: steps per evaluation')
-    p.add_argument('--dynamics', choices=DYNAMICS, default='st-perlin-wide')
+    p.add_argument('--dynamics', default='st-perlin-wide', help=f'one of {", ".join(DYNAMICS)}, or a comma list: every candidate on each')
     p.add_argument('--generations', type=int, default=0)
     p.add_argument('--sigma', type=float, default=0.1)
     p.add_argument('--lr', type=float, default=0.05)
@@ -123,7 +167,8 @@ def main():
     p.add_argument('--agents-die', action='store_true', help='Dynamics(agents_die=True): starved agents die')
     p.add_argument('--max-agents', default='alive', help="slots per replica: 'alive', 'full' (W·H), 'tight' or a number")
     p.add_argument('--reseed', type=int, default=None, help='--generations on the device-seeded world of seed S + g (fixed layout)')
-    p.add_argument('--episodes', type=int, default=1, help='worlds per candidate (replicas x episodes <= 64)')
+    p.add_argument('--episodes', type=int, default=None, help='worlds per candidate (replicas x episodes <= 64); default 1, or the '
+                                                               'length of a --dynamics list (then a multiple of it)')
     p.add_argument('--dropout', type=float, default=0., help='p_agent_dropout of the candidates (0: none), masked on the device')
     p.add_argument('--dropout-seed', type=int, default=0, help='key of the dropout masks: replica r uses seed + r·stride')
     p.add_argument('--dropout-stride', type=int, default=1, help='0: every replica the same mask; 1: every replica its own')
@@ -131,6 +176,11 @@ def main():
     if not 0. <= args.dropout <= 1. or args.dropout_stride < 0:
         p.error('--dropout in [0, 1], --dropout-stride >= 0')
     drop_kw = dropout_keywords(args.dropout, args.dropout_seed, args.dropout_stride)
+    try:
+        names = dynamics_names(args.dynamics)
+        args.episodes = resolve_episodes(names, args.episodes) if len(names) > 1 else (1 if args.episodes is None else args.episodes)
+    except ValueError as err:
+        p.error(str(err))
     R, E = args.replicas, args.episodes
     if E < 1 or R * E > 64:
         p.error(f'--episodes {E}: at least 1, and {R} replicas x episodes at most 64')
@@ -155,6 +205,9 @@ def main():
     for r, f in enumerate(fitness):
         worlds = sums[r * E:(r + 1) * E]
         print(f'candidate {r:2d}: fitness {f:.6f}' + (f'  (its {E} worlds: {min(worlds):.6f} … {max(worlds):.6f})' if E > 1 else ''))
+    if len(names) > 1:
+        print('mean score under each dynamics: ' + ', '.join(f'{q} {v:.6f}' for q, v in
+                                                              per_dynamics_means(args.dynamics, [sums[c * E:(c + 1) * E] for c in range(R)])))
     best = max(range(R), key=lambda r: fitness[r])
     print(f'best: candidate {best} ({fitness[best]:.6f}); pop.candidate({best}).save(...) keeps it', flush=True)
 

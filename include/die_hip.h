@@ -748,6 +748,57 @@ int die_nca_env_step_batch_dropout(const die_medium* m, const die_agents* a, con
 int die_dropout_mask(int32_t W, int32_t H, const die_nca_dropout* drop, int32_t replicas, int64_t plane_stride, float* out,
                      void* stream);
 
+/* ---- Per-replica Dynamics on batched replicas (die_env.hip, die_init.hip; BatchedEnv(dynamics=[...])) ---------------------
+ * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
+ * The replicas of a die_batch may live under different environment constants: rate_feed, rate_decay_chem, diffuse_sigma and
+ * food_infinite of replica r come from row r of a device table, everything else (boundary, cost and its weights, agents_die,
+ * has_dead_slots) stays shared in the die_dynamics of the call.  Replica r then computes, bit for bit, what a stand-alone world
+ * under its own Dynamics computes.
+ *   A row is one replica's constants as the kernels consume them.  64 bytes, so that a workgroup fetches its replica's row with
+ * one scalar load (as die_physarum_row). */
+typedef struct die_dynamics_row {
+    float rate_feed;
+    float keep;              /* (float)(1.0 - (double)rate_decay_chem): what the shared-Dynamics sweep multiplies by */
+    int32_t food_infinite;
+    int32_t radius;          /* (int)(4 * sigma + 0.5): 1..4 */
+    float w[9];              /* the 2 * radius + 1 gaussian taps, (float) of the library's float64 taps; the rest 0 */
+    float reserved[3];       /* 0 */
+} die_dynamics_row;
+
+/* n HOST rows from n die_dynamics for W x H replicas, with the taps the shared-Dynamics sweep computes for that sigma.  Nothing is
+ * written unless every row is accepted.  Refused: n outside 1..DIE_MAX_REPLICAS; a radius outside 1..4 or H % 4 != 0
+ * (DIE_ERR_UNSUPPORTED: the fused sweep does not apply); a diffuse_mode other than WRAP or staged != 0; a row that differs from
+ * row 0 in boundary, cost, the two cost weights, agents_die or has_dead_slots. */
+int die_dynamics_rows(const die_dynamics* d, int32_t n, int32_t W, int32_t H, die_dynamics_row* rows_host);
+
+/* The three batched steps with the table: `rows` is a DEVICE array of b->replicas rows, `rows_host` the host rows it was uploaded
+ * from (die_dynamics_rows' output; only the radii are read, to group the sweep's launches).  Replica r claims and feeds with
+ * rows[r].rate_feed and is swept with rows[r]'s taps, keep, rate_feed and food_infinite; `d` supplies what does not vary (its own
+ * rate_feed, rate_decay_chem, diffuse_sigma and food_infinite must still describe a valid world: they are checked as the parent
+ * call checks them, and otherwise unused).  Each entry runs its parent's checks in the parent's order, then requires both tables.
+ * The field sweep is launched once per distinct radius present (4 launches at most), each launch covering its replicas through a
+ * by-value list of replica indices and running the kernel instantiation a stand-alone world of that radius takes; every replica
+ * keeps its own reduction workgroup and result words.  With one radius the launch count is the parent's.
+ * die_nca_env_step_batch_rows takes a nullable `drop`: NULL is die_nca_env_step_batch, else die_nca_env_step_batch_dropout. */
+int die_forward_env_step_batch_rows(const die_medium* m, const die_agents* a, die_gradient_agent* g, const die_action* act,
+                                    const die_dynamics* d, const die_batch* b, die_step_result* results, void* workspace,
+                                    int64_t workspace_bytes, const die_dynamics_row* rows, const die_dynamics_row* rows_host,
+                                    void* stream);
+int die_physarum_env_step_batch_rows(const die_medium* m, const die_agents* a, die_gradient_agent* g, const die_physarum_row* table,
+                                     const die_action* act, const die_dynamics* d, const die_batch* b, die_step_result* results,
+                                     void* workspace, int64_t workspace_bytes, const die_dynamics_row* rows,
+                                     const die_dynamics_row* rows_host, void* stream);
+int die_nca_env_step_batch_rows(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
+                                const die_dynamics* d, const die_batch* b, die_step_result* results, void* workspace,
+                                int64_t workspace_bytes, const die_nca_dropout* drop, const die_dynamics_row* rows,
+                                const die_dynamics_row* rows_host, void* stream);
+
+/* die_food_flow_batch on the replicas whose bit is set in replica_mask (bit r = replica r); the others' planes are not touched.
+ * One launch: a row of workgroups per replica, those of unset replicas exit at once.  A full mask leaves exactly what
+ * die_food_flow_batch leaves; an empty mask launches nothing.  Bits at or above b->replicas must be 0. */
+int die_food_flow_batch_masked(const die_medium* m, const die_batch* b, int32_t kind, double t, double scale, double decay,
+                               int32_t octaves, uint64_t seed, uint64_t replica_mask, void* stream);
+
 /* ---- PGPE search over an (R, P) parameter matrix (die_search.hip; die_amd/search.py PGPE) ------------------------------
  * The training half of the reference's examples/learning_agents.py (evotorch's PGPE with symmetric sampling and centred
  * ranks).  R = replicas (even, 2..DIE_MAX_REPLICAS), n = R / 2 directions, P = parameters; the matrix is row-major fp32
