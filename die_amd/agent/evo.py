@@ -211,8 +211,162 @@ class NeuralAutomataAgent(TorchAgent):
         action._keepalive = sense
         return action
 
+    # ------------------------------------------------------------------ the differentiable twins (die_nca_grad.hip)
+    def differentiable_sense(self, medium) -> th.Tensor:
+        """`sense` with a `grad_fn`: (3, W, H) float32 on the medium's device, bit-identical to `sense`, whose backward is the
+        conv stack's adjoint on the device (die_conv2d_backward per layer).  Gradients land in `model.parameters()` wherever the
+        model lives (the weights go in through a differentiable `.to(device)`); the medium is no leaf and gets none.
+
+        Every layer's output goes into storage of its own (not the ping-pong scratch), and the first layer's inputs — the two
+        field planes and the claim plane — are COPIED (3 planes), so that `backward` may run after the medium has been stepped.
+        With a `dropout_seed` in training mode the last layer is launched twice, masked (the value returned) and unmasked
+        (tanh(z), kept for the backward, which recomputes the mask from its key); `dropout_step` advances once per call, as in
+        `sense`.  Boundaries 'circular' and 'zeros'; 'reflect' / 'replicate' raise NotImplementedError before any launch.
+        `sense` and `forward` are untouched by all this: never differentiable, same scratch, same launches."""
+        layers = self._model.conv_layers()
+        for k in layers:
+            if k.padding_mode not in ('circular', 'zeros'):
+                raise NotImplementedError(f"boundary={k.padding_mode!r} in differentiable mode: 'circular' or 'zeros' (sense() and "
+                                          f"forward() take all of {sorted(_lib.PAD_MODES)})")
+        medium.sensed()
+        dev = medium.device
+        weights = [k.weight.to(device=dev, dtype=th.float32).contiguous() for k in layers]
+        out = _DifferentiableSense.apply(self, medium, *weights)
+        p = self._model.agent_dropout.p
+        if self._dropout_seed is not None:
+            self.dropout_step += 1
+        elif p > 0 and self._model.training:                     # the torch-RNG mask: a torch multiply, autograd's own business
+            out = out * self._model.agent_dropout(th.ones((medium.W, medium.H), device=dev))
+        return out
+
+    def differentiable_action(self, obs) -> th.Tensor:
+        """`forward` with a `grad_fn`: (3, N) float32, rows dx, dy, deposit for EVERY slot in the agents' array order — the values
+        `forward(obs)` puts in its DeviceAction's `data[:, :N]`, bit for bit.  Its backward is the read-out's adjoint
+        (die_gather_scale_backward: the slots' gradients scattered onto their cells, then `differentiable_sense`'s backward).
+        The slots' coordinates are copied, so `backward` may run after the world has been stepped.  Where several slots with a
+        non-zero gradient stand on one cell their terms are summed by fp32 atomic adds in arrival order; otherwise (alive agents
+        never share a cell) the gradients are bit-reproducible run to run."""
+        agents, medium = obs
+        sense = self.differentiable_sense(medium)
+        self._sense_output = sense.detach()
+        return _DifferentiableReadOut.apply(sense, agents, medium, self.action_coefs)
+
     def render(self) -> Sequence[np.ndarray]:
         """:176-181: the transformed medium with the channel axis last."""
         if self._sense_output is None:
             return [np.ones((2, 2, 3))]
         return [th.moveaxis(self._sense_output, 0, -1).cpu().numpy()]
+
+
+class _DifferentiableSense(th.autograd.Function):
+    """NeuralAutomataAgent.differentiable_sense: the forward is `sense`'s launches into storage the graph owns, the backward
+    one die_conv2d_backward per layer, last layer first."""
+
+    @staticmethod
+    def forward(ctx, agent, medium, *weights):
+        dev, W, H = medium.device, medium.W, medium.H
+        sp = stream_ptr(dev)
+        medium._ensure_owner()
+        fkind = _lib.DIE_PLANE_F32 if medium.dtype == th.float32 else _lib.DIE_PLANE_F16
+        src = {'agents': (medium.owner, _lib.DIE_PLANE_AGENTS), 'env_food': (medium.food, fkind), 'chem1': (medium.chem, fkind)}
+        planes = src_planes = [(src[c][0].clone(), src[c][1]) for c in agent.obs_channels]     # as they are now: the medium will be stepped
+        p = agent._model.agent_dropout.p
+        drop = None
+        if p > 0 and agent._model.training and agent._dropout_seed is not None:
+            drop = _lib.nca_dropout(p, agent._dropout_seed, 0, agent.dropout_step)
+        pads = [_lib.PAD_MODES[k.padding_mode] for k in agent._model.conv_layers()]
+        first, hidden, out, tanh_out = [t for t, _ in planes], [], None, None
+        for li, w in enumerate(weights):
+            cout, cin, k, k2 = w.shape
+            if k != k2 or cin != len(planes):
+                raise ValueError(f'layer {li}: weight {tuple(w.shape)} does not fit {len(planes)} input planes')
+            last = li == len(weights) - 1
+            cin_arr = (_lib.ConvPlane * cin)(*[_lib.ConvPlane(t.data_ptr(), kind, 0) for t, kind in planes])
+
+            def launch(masked):
+                dst = th.empty((cout, W, H), dtype=th.float32, device=dev)
+                out_arr = (C.c_void_p * cout)(*[dst[o].data_ptr() for o in range(cout)])
+                if masked:
+                    _lib.check(_lib.lib.die_conv2d_dropout(W, H, cin, cin_arr, medium.epoch, cout, out_arr, k, _ptr(w), 1, pads[li],
+                                                           C.byref(drop), sp), 'die_conv2d_dropout')
+                else:
+                    _lib.check(_lib.lib.die_conv2d(W, H, cin, cin_arr, medium.epoch, cout, out_arr, k, _ptr(w), int(last), pads[li], sp),
+                               'die_conv2d')
+                return dst
+
+            out = tanh_out = launch(False)
+            if last and drop is not None:
+                out = launch(True)                               # what `sense` returns; tanh_out stays unmasked for the backward
+            planes = [(out[o], _lib.DIE_PLANE_F32) for o in range(cout)]
+            if not last:
+                hidden.append(out)
+        ctx.kinds, ctx.pads, ctx.epoch, ctx.size, ctx.dev = [kind for _, kind in src_planes], pads, medium.epoch, (W, H), dev
+        ctx.drop = None if drop is None else (drop.p, drop.seed, drop.step)
+        # everything the backward reads goes through save_for_backward: freed with the graph after a backward without retain_graph
+        ctx.save_for_backward(*weights, tanh_out, *first, *hidden)
+        return out
+
+    @staticmethod
+    @th.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        saved = ctx.saved_tensors
+        L, n_first = len(ctx.pads), len(ctx.kinds)
+        weights, tanh_out, first, hidden = saved[:L], saved[L], saved[L + 1:L + 1 + n_first], saved[L + 1 + n_first:]
+        (W, H), dev = ctx.size, ctx.dev
+        sp = stream_ptr(dev)
+        g = grad.to(dtype=th.float32).contiguous()
+        drop = None if ctx.drop is None else _lib.nca_dropout(ctx.drop[0], ctx.drop[1], 0, ctx.drop[2])
+        grads = [None] * L
+        need = [_lib.lib.die_conv2d_backward_workspace_bytes(W, H, w.shape[1], w.shape[0], w.shape[2]) for w in weights]
+        if min(need) < 0:
+            raise ValueError('a layer shape die_conv2d_backward does not take (1..4 channels, kernel size 1, 3, 5 or 7)')
+        ws = th.empty((max(need) // 4,), dtype=th.float32, device=dev)            # one workspace, sized for the largest layer
+        for li in reversed(range(L)):
+            w = weights[li]
+            cout, cin, k, _ = w.shape
+            last = li == L - 1
+            inputs = list(zip(first, ctx.kinds)) if li == 0 else [(hidden[li - 1][c], _lib.DIE_PLANE_F32) for c in range(cin)]
+            cin_arr = (_lib.ConvPlane * cin)(*[_lib.ConvPlane(t.data_ptr(), kind, 0) for t, kind in inputs])
+            g_arr = (C.c_void_p * cout)(*[g[o].data_ptr() for o in range(cout)])
+            grad_w = th.empty_like(w)
+            grad_in = th.empty((cin, W, H), dtype=th.float32, device=dev) if li > 0 else None
+            gin_arr = None if grad_in is None else (C.c_void_p * cin)(*[grad_in[c].data_ptr() for c in range(cin)])
+            t_arr = (C.c_void_p * cout)(*[tanh_out[o].data_ptr() for o in range(cout)]) if last else None
+            _lib.check(_lib.lib.die_conv2d_backward(W, H, cin, cin_arr, ctx.epoch, cout, g_arr, k, _ptr(w), _ptr(grad_w), gin_arr, t_arr,
+                                                    C.byref(drop) if last and drop is not None else None, ctx.pads[li], _ptr(ws),
+                                                    need[li], sp), 'die_conv2d_backward')
+            grads[li] = grad_w
+            g = grad_in
+        return (None, None, *grads)
+
+
+class _DifferentiableReadOut(th.autograd.Function):
+    """NeuralAutomataAgent.differentiable_action's last step: die_gather_scale forward, die_gather_scale_backward backward."""
+
+    @staticmethod
+    def forward(ctx, sense, agents, medium, coefs):
+        sense = sense.contiguous()
+        N, dev = agents.N, agents.device
+        out = th.empty((3, N), dtype=th.float32, device=dev)
+        planes = (C.c_void_p * 3)(*[sense[c].data_ptr() for c in range(3)])
+        cf = (C.c_float * 3)(*coefs)
+        m, a = medium.c_struct(need_owner=False), agents.c_struct()
+        u = _lib.Action(N, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
+        _lib.check(_lib.lib.die_gather_scale(C.byref(m), C.byref(a), planes, cf, C.byref(u), stream_ptr(dev)), 'die_gather_scale')
+        ctx.save_for_backward(agents.x.clone(), agents.y.clone())             # where the slots stand now: the world will be stepped
+        ctx.N, ctx.m, ctx.coefs, ctx.size, ctx.dev = N, m, tuple(coefs), (medium.W, medium.H), dev
+        return out
+
+    @staticmethod
+    @th.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        x, y = ctx.saved_tensors
+        g = grad.to(dtype=th.float32).contiguous()
+        planes = th.empty((3, *ctx.size), dtype=th.float32, device=ctx.dev)      # (cleared by the call)
+        p_arr = (C.c_void_p * 3)(*[planes[c].data_ptr() for c in range(3)])
+        cf = (C.c_float * 3)(*ctx.coefs)
+        a = _lib.Agents(ctx.N, _ptr(x), _ptr(y), None, None, None)
+        u = _lib.Action(ctx.N, g[0].data_ptr(), g[1].data_ptr(), g[2].data_ptr())
+        _lib.check(_lib.lib.die_gather_scale_backward(C.byref(ctx.m), C.byref(a), C.byref(u), cf, p_arr, stream_ptr(ctx.dev)),
+                   'die_gather_scale_backward')
+        return planes, None, None, None

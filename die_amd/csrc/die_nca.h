@@ -1,0 +1,31 @@
+// What the NeuralAutomataAgent kernels share (die_nca.hip: the forward; die_nca_grad.hip: its adjoint): the workgroup tile, the
+// limits, how a cell beyond the field is read and how a first-layer plane is loaded.
+#pragma once
+#include "die_common.h"
+
+#define NCA_TX 16
+#define NCA_TY 64
+#define NCA_MAXC 4
+#define NCA_MAXK 7
+
+// index of the cell that stands in for coordinate v of an axis of n cells, or −1 for "reads as zero" (torch.nn.functional.pad:
+// 'circular' wraps, 'zeros' pads with 0, 'reflect' mirrors WITHOUT repeating the edge cell, 'replicate' repeats it)
+__device__ __forceinline__ int nca_pad_index(int v, int n, int mode) {
+    if (v >= 0 && v < n) return v;
+    if (mode == DIE_PAD_CIRCULAR) { v %= n; return v < 0 ? v + n : v; }
+    if (mode == DIE_PAD_ZEROS) return -1;
+    if (mode == DIE_PAD_REPLICATE) return v < 0 ? 0 : n - 1;
+    if (n == 1) return 0;
+    const int period = 2 * (n - 1);                  // 'reflect': … 2 1 | 0 1 2 … n−1 | n−2 n−3 …
+    v %= period; v = v < 0 ? v + period : v;
+    return v < n ? v : period - v;
+}
+
+__device__ __forceinline__ float nca_load(const void* p, int kind, int64_t i, int epoch) {
+    if (kind == DIE_PLANE_F32) return ((const float*)p)[i];
+    if (kind == DIE_PLANE_F16) return __half2float(((const __half*)p)[i]);
+    return die_claim_occupied(((const unsigned long long*)p)[i], epoch) ? 1.f : 0.f;
+}
+
+// die_nca_dropout, checked, as the words the kernels read (die_nca.hip)
+int die_dropout_words(const die_nca_dropout* drop, DropWords* out, const char* who);

@@ -24,11 +24,7 @@
 #include <type_traits>
 #include "die_common.h"
 #include "die_rng.h"
-
-#define NCA_TX 16
-#define NCA_TY 64
-#define NCA_MAXC 4
-#define NCA_MAXK 7
+#include "die_nca.h"
 
 struct ConvArgs {
     const void* in[NCA_MAXC];
@@ -43,24 +39,7 @@ struct ConvArgs {
 // what a DROP launch reads on top (the other instantiations keep ConvArgs as their whole argument)
 struct ConvDropArgs : ConvArgs { DropWords d; };
 
-// index of the cell that stands in for coordinate v of an axis of n cells, or −1 for "reads as zero" (torch.nn.functional.pad:
-// 'circular' wraps, 'zeros' pads with 0, 'reflect' mirrors WITHOUT repeating the edge cell, 'replicate' repeats it)
-__device__ __forceinline__ int nca_pad_index(int v, int n, int mode) {
-    if (v >= 0 && v < n) return v;
-    if (mode == DIE_PAD_CIRCULAR) { v %= n; return v < 0 ? v + n : v; }
-    if (mode == DIE_PAD_ZEROS) return -1;
-    if (mode == DIE_PAD_REPLICATE) return v < 0 ? 0 : n - 1;
-    if (n == 1) return 0;
-    const int period = 2 * (n - 1);                  // 'reflect': … 2 1 | 0 1 2 … n−1 | n−2 n−3 …
-    v %= period; v = v < 0 ? v + period : v;
-    return v < n ? v : period - v;
-}
-
-__device__ __forceinline__ float nca_load(const void* p, int kind, int64_t i, int epoch) {
-    if (kind == DIE_PLANE_F32) return ((const float*)p)[i];
-    if (kind == DIE_PLANE_F16) return __half2float(((const __half*)p)[i]);
-    return die_claim_occupied(((const unsigned long long*)p)[i], epoch) ? 1.f : 0.f;
-}
+// (nca_pad_index — which cell stands in for one beyond the field — and nca_load — a first-layer plane's element — : die_nca.h)
 
 // BATCH: replica blockIdx.z of die_nca_env_step_batch — its input planes, weights and output planes lie blockIdx.z strides
 // on; everything else (tile, LDS, summation order, tanh) is this one body.  With episodes E > 1 (a candidate evaluated on E

@@ -1,0 +1,299 @@
+// The adjoint of NeuralAutomataAgent's sensing (gfx950): what die_nca.hip computes forward,
+//   z_l = conv_l(z_{l−1}) for l = 1..L (z_0: the medium's planes; nothing between the layers),   s = tanh(z_L) · mask,
+//   action[c, n] = s[c, cell(x_n), cell(y_n)] · coef[c] for every slot n,
+// differentiated with respect to the layers' weights — "backpropagation through agent indexing operation" (core/agent/evo.py:48).
+//
+//   k_gather_scale_backward   g_s[c, cell_n] += grad_action[c, n] · coef[c] into planes the entry point has zeroed: k_gather_scale's
+//                     indexing (die_cell / die_local), one fp32 atomic add per non-zero term.  Several slots may stand on one cell
+//                     (dead slots often do, alive agents never): the sum's order is then the arrival order.  The result is
+//                     bit-reproducible run to run whenever no two slots with a non-zero gradient share a cell.
+//   k_conv_backward   one layer, one launch: the forward's 16 × 64 tile.  A workgroup stages, for every channel, the input tile
+//                     plus halo (nca_load semantics for the first layer: fp32 / fp16 fields, the 'agents' channel from the claim
+//                     plane) and the tile plus halo of the gradient g_z arriving at the layer's outputs.  For the layer that
+//                     carried the tanh, g_z = g_s · mask · (1 − t²) is formed while staging, from t = tanh(z_L) as the forward
+//                     stored it UNMASKED and the mask recomputed from its key (die_rng.h: a pure function of key, step and
+//                     cell) — no launch of its own, no division by keep.
+//       weight gradient   grad_w[o, i, a, b] = Σ_{x, y} g_z[o, x, y] · in[i, pad(x + a − r), pad(y + b − r)].  A lane owns one column
+//                     of the tile and keeps its 16 g_z of every output channel in registers; a wave takes the units (i, b) wave,
+//                     wave + 4, …, reads the unit's input column (16 + 2r values, consecutive lanes on consecutive LDS words:
+//                     no bank conflict) and forms, for every (o, a), 16 products down the column, then a butterfly sum over the
+//                     64 lanes.  Lane 0 stores the term into the workgroup's partial row [cout · cin · k · k] — every element
+//                     of the row is written once, by one wave.  NO float atomics.
+//       input gradient    (layers ≥ 2 only; the first layer's input is the medium, no leaf) grad_in[i, x, y] = Σ_o Σ_a Σ_b
+//                     w[o, i, a, b] · g_z[o, pad'(x − a + r), pad'(y − b + r)]: the correlation with the flipped kernel, where
+//                     pad' is the padding's adjoint — 'circular' wraps, 'zeros' drops what falls outside.  Thread layout and
+//                     stores are the forward's (4 consecutive y per thread, 16-byte stores where H % 4 == 0).
+//   k_conv_backward_sum   the second launch: one thread per weight sums the partial rows in tile-index order (tile = row of tiles ·
+//                     tiles per row + column), in float64, and stores fp32.  Fixed order, fixed tree: the same inputs give the
+//                     same bits on every run.
+//
+// Roofline: as the forward (die_nca.hip) — a 3→3 3×3 layer reads 9 planes and writes 3 per cell for 2 × 81 MAC: no MFMA.
+#include <math.h>
+#include "die_common.h"
+#include "die_rng.h"
+#include "die_nca.h"
+
+struct ConvBwdArgs {
+    const void* in[NCA_MAXC];
+    int kind[NCA_MAXC];          // die_conv_plane.kind
+    const float* g[NCA_MAXC];    // gradient at the layer's outputs (before the tanh adjoint when t is given)
+    const float* t[NCA_MAXC];    // the layer's forward outputs tanh(z), unmasked, or all null
+    float* gin[NCA_MAXC];        // gradient at the layer's inputs, or all null
+    const float* w;              // [cout][cin][k][k]
+    float* part;                 // [tiles][cout · cin · k · k]
+    int W, H, cin, cout, epoch, pad;
+    int has_t, has_drop, has_gin;
+    DropWords d;
+};
+
+template <int K>
+__global__ __launch_bounds__(DIE_BLOCK) void k_conv_backward(ConvBwdArgs a) {
+    constexpr int R = K / 2, LX = NCA_TX + 2 * R, LYV = NCA_TY + 2 * R, LY = LYV + 1;     // odd pitch, as the forward
+    extern __shared__ __align__(16) float nca_grad_smem[];
+    float* s_in = nca_grad_smem;                             // [cin][LX][LY]
+    float* s_g = s_in + a.cin * LX * LY;                     // [cout][LX][LY]
+    float* s_w = s_g + a.cout * LX * LY;                     // [cout][cin][K][K]
+    const int x0 = blockIdx.y * NCA_TX, y0 = blockIdx.x * NCA_TY;
+    const int nw = a.cout * a.cin * K * K;
+    for (int i = threadIdx.x; i < nw; i += DIE_BLOCK) s_w[i] = a.w[i];
+    // every staged element stands for the virtual cell (x0 − R + li, y0 − R + lj), read through the padding: also past the field's
+    // last row / column inside a partial tile, where the input gradient of the cells before the edge needs the wrapped values
+    for (int i = threadIdx.x; i < LX * LYV; i += DIE_BLOCK) {
+        const int li = i / LYV, lj = i - li * LYV;
+        const int gx = nca_pad_index(x0 - R + li, a.W, a.pad), gy = nca_pad_index(y0 - R + lj, a.H, a.pad);
+        const bool in_field = gx >= 0 && gy >= 0;
+        const int64_t cell = in_field ? (int64_t)gx * a.H + gy : 0;
+        for (int c = 0; c < a.cin; ++c) s_in[(c * LX + li) * LY + lj] = in_field ? nca_load(a.in[c], a.kind[c], cell, a.epoch) : 0.f;
+        float m = 1.f;
+        if (a.has_drop && in_field) m = die_dropout_factor(die_dropout_word(a.d.seed, a.d.step, (uint64_t)cell), a.d.thr, a.d.keep);
+        for (int o = 0; o < a.cout; ++o) {
+            float v = 0.f;
+            if (in_field) {
+                v = a.g[o][cell];
+                if (a.has_t) {
+                    const float t = a.t[o][cell];
+                    v = a.has_drop ? v * m * (1.f - t * t) : v * (1.f - t * t);
+                }
+            }
+            s_g[(o * LX + li) * LY + lj] = v;
+        }
+    }
+    __syncthreads();
+
+    // ---- weight gradient: this tile's row of partial sums
+    {
+        const int lane = threadIdx.x & (DIE_WAVE - 1), wave = threadIdx.x / DIE_WAVE;
+        const bool col_ok = y0 + lane < a.H;
+        float greg[NCA_MAXC][NCA_TX];
+#pragma unroll
+        for (int o = 0; o < NCA_MAXC; ++o) {
+#pragma unroll
+            for (int r = 0; r < NCA_TX; ++r) {
+                greg[o][r] = 0.f;
+                if (o < a.cout && col_ok && x0 + r < a.W) greg[o][r] = s_g[(o * LX + r + R) * LY + lane + R];
+            }
+        }
+        float* prow = a.part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * nw;
+        for (int u = wave; u < a.cin * K; u += DIE_BLOCK / DIE_WAVE) {       // wave-uniform
+            const int i = u / K, b = u - i * K;
+            float col[LX];
+#pragma unroll
+            for (int r = 0; r < LX; ++r) col[r] = s_in[(i * LX + r) * LY + lane + b];
+#pragma unroll
+            for (int ka = 0; ka < K; ++ka) {
+#pragma unroll
+                for (int o = 0; o < NCA_MAXC; ++o) {
+                    if (o < a.cout) {
+                        float p = 0.f;
+#pragma unroll
+                        for (int r = 0; r < NCA_TX; ++r) p += greg[o][r] * col[r + ka];
+#pragma unroll
+                        for (int off = DIE_WAVE / 2; off > 0; off >>= 1) p += __shfl_xor(p, off, DIE_WAVE);
+                        if (lane == 0) prow[((o * a.cin + i) * K + ka) * K + b] = p;
+                    }
+                }
+            }
+        }
+    }
+    if (!a.has_gin) return;
+
+    // ---- input gradient: s_g row ti + a' is virtual x − R + a' = x − a + r for a = K − 1 − a'
+    const int ti = threadIdx.x / (NCA_TY / 4), tj = (threadIdx.x % (NCA_TY / 4)) * 4;
+    float acc[NCA_MAXC][4];
+#pragma unroll
+    for (int c = 0; c < NCA_MAXC; ++c) acc[c][0] = acc[c][1] = acc[c][2] = acc[c][3] = 0.f;
+    for (int o = 0; o < a.cout; ++o) {
+#pragma unroll
+        for (int ka = 0; ka < K; ++ka) {
+            float row[4 + K - 1];
+#pragma unroll
+            for (int q = 0; q < 4 + K - 1; ++q) row[q] = s_g[(o * LX + ti + ka) * LY + tj + q];
+#pragma unroll
+            for (int c = 0; c < NCA_MAXC; ++c) {
+                if (c < a.cin) {
+#pragma unroll
+                    for (int kb = 0; kb < K; ++kb) {
+                        const float wv = s_w[((o * a.cin + c) * K + (K - 1 - ka)) * K + (K - 1 - kb)];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) acc[c][q] += wv * row[q + kb];
+                    }
+                }
+            }
+        }
+    }
+    const int gx = x0 + ti, gy = y0 + tj;
+    if (gx >= a.W || gy >= a.H) return;
+#pragma unroll
+    for (int c = 0; c < NCA_MAXC; ++c) {
+        if (c < a.cin) {
+            float* dst = a.gin[c] + (int64_t)gx * a.H + gy;
+            if (gy + 3 < a.H && (a.H & 3) == 0) *(float4*)dst = make_float4(acc[c][0], acc[c][1], acc[c][2], acc[c][3]);
+            else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) if (gy + q < a.H) dst[q] = acc[c][q];
+            }
+        }
+    }
+}
+
+// one thread per weight: the tiles' partial rows in tile-index order, float64
+__global__ __launch_bounds__(DIE_BLOCK) void k_conv_backward_sum(const float* part, int64_t tiles, int nw, float* out) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nw) return;
+    double s = 0.0;
+#pragma unroll 8
+    for (int64_t t = 0; t < tiles; ++t) s += (double)part[t * nw + j];
+    out[j] = (float)s;
+}
+
+static bool conv_shape_ok(int32_t W, int32_t H, int32_t cin, int32_t cout, int32_t k) {
+    return W >= 1 && H >= 1 && cin >= 1 && cin <= NCA_MAXC && cout >= 1 && cout <= NCA_MAXC && (k == 1 || k == 3 || k == 5 || k == 7);
+}
+static int64_t conv_tiles(int32_t W, int32_t H) { return (int64_t)((W + NCA_TX - 1) / NCA_TX) * ((H + NCA_TY - 1) / NCA_TY); }
+
+extern "C" int64_t die_conv2d_backward_workspace_bytes(int32_t W, int32_t H, int32_t cin, int32_t cout, int32_t k) {
+    if (!conv_shape_ok(W, H, cin, cout, k)) return -1;
+    return conv_tiles(W, H) * cout * cin * k * k * (int64_t)sizeof(float);
+}
+
+extern "C" int die_conv2d_backward(int32_t W, int32_t H, int32_t cin, const die_conv_plane* in, int32_t epoch, int32_t cout,
+                                   const float* const* grad_out, int32_t k, const float* weights, float* grad_weights,
+                                   float* const* grad_in, const float* const* fwd_out, const die_nca_dropout* drop,
+                                   int32_t padding_mode, void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* who = "die_conv2d_backward";
+    DIE_REQUIRE(padding_mode >= DIE_PAD_CIRCULAR && padding_mode <= DIE_PAD_REPLICATE, "%s: bad padding mode %d", who, padding_mode);
+    if (padding_mode == DIE_PAD_REFLECT || padding_mode == DIE_PAD_REPLICATE) {
+        die_set_error("%s: the adjoint of 'reflect' / 'replicate' padding is not implemented ('circular' and 'zeros' are)", who);
+        return DIE_ERR_UNSUPPORTED;
+    }
+    DIE_REQUIRE(W >= 1 && H >= 1, "%s: bad size %dx%d", who, W, H);
+    DIE_REQUIRE(cin >= 1 && cin <= NCA_MAXC && cout >= 1 && cout <= NCA_MAXC, "%s: 1..%d channels (got %d -> %d)", who, NCA_MAXC, cin, cout);
+    if (!(k == 1 || k == 3 || k == 5 || k == 7)) {
+        die_set_error("%s: kernel size %d (odd sizes up to %d)", who, k, NCA_MAXK);
+        return DIE_ERR_UNSUPPORTED;
+    }
+    DIE_REQUIRE(in && grad_out && weights && grad_weights && workspace, "%s: null argument", who);
+    DIE_REQUIRE(grad_weights != weights, "%s: grad_weights is the weights", who);
+    DIE_REQUIRE(fwd_out || !drop, "%s: a dropout mask without the forward outputs it was applied to", who);
+    const int64_t need = die_conv2d_backward_workspace_bytes(W, H, cin, cout, k);
+    DIE_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%lld < %lld)", who, (long long)workspace_bytes, (long long)need);
+    ConvBwdArgs a = {};
+    for (int c = 0; c < cin; ++c) {
+        DIE_REQUIRE(in[c].data && in[c].kind >= DIE_PLANE_F32 && in[c].kind <= DIE_PLANE_AGENTS, "%s: bad input plane %d", who, c);
+        a.in[c] = in[c].data; a.kind[c] = in[c].kind;
+        if (grad_in) {
+            DIE_REQUIRE(grad_in[c], "%s: null grad_in plane %d", who, c);
+            a.gin[c] = grad_in[c];
+        }
+    }
+    for (int o = 0; o < cout; ++o) {
+        DIE_REQUIRE(grad_out[o], "%s: null gradient plane %d", who, o);
+        a.g[o] = grad_out[o];
+        if (fwd_out) {
+            DIE_REQUIRE(fwd_out[o], "%s: null forward output plane %d", who, o);
+            a.t[o] = fwd_out[o];
+        }
+    }
+    if (grad_in) {
+        for (int c = 0; c < cin; ++c) {
+            bool alias = false;
+            for (int q = 0; q < cin; ++q) alias |= (const void*)grad_in[c] == in[q].data || (q != c && grad_in[c] == grad_in[q]);
+            for (int o = 0; o < cout; ++o) alias |= grad_in[c] == grad_out[o] || (fwd_out && grad_in[c] == fwd_out[o]);
+            DIE_REQUIRE(!alias, "%s: in-place grad_in (plane %d is one of the call's other planes)", who, c);
+        }
+    }
+    DropWords dw = {};
+    if (drop) {
+        const int rc = die_dropout_words(drop, &dw, who);
+        if (rc != DIE_OK) return rc;
+    }
+    a.w = weights; a.part = (float*)workspace;
+    a.W = W; a.H = H; a.cin = cin; a.cout = cout; a.epoch = epoch; a.pad = padding_mode;
+    a.has_t = fwd_out != nullptr; a.has_drop = drop != nullptr; a.has_gin = grad_in != nullptr;
+    a.d = dw;
+    const int R = k / 2, nw = cout * cin * k * k;
+    const size_t lds = ((size_t)(cin + cout) * (NCA_TX + 2 * R) * (NCA_TY + 2 * R + 1) + (size_t)nw) * sizeof(float);
+    dim3 grid((H + NCA_TY - 1) / NCA_TY, (W + NCA_TX - 1) / NCA_TX);
+    DIE_REQUIRE(grid.y <= 65535u, "%s: field too tall (%d rows of tiles)", who, (int)grid.y);
+    hipStream_t s = (hipStream_t)stream;
+    switch (k) {
+        case 1: k_conv_backward<1><<<grid, DIE_BLOCK, lds, s>>>(a); break;
+        case 3: k_conv_backward<3><<<grid, DIE_BLOCK, lds, s>>>(a); break;
+        case 5: k_conv_backward<5><<<grid, DIE_BLOCK, lds, s>>>(a); break;
+        default: k_conv_backward<7><<<grid, DIE_BLOCK, lds, s>>>(a); break;
+    }
+    DIE_CHECK_LAUNCH(who);
+    k_conv_backward_sum<<<die_grid_for(nw), DIE_BLOCK, 0, s>>>(a.part, conv_tiles(W, H), nw, grad_weights);
+    DIE_CHECK_LAUNCH("die_conv2d_backward(sum)");
+    return DIE_OK;
+}
+
+// ---- the read-out's adjoint --------------------------------------------------------------------------------------------
+struct GatherBwdArgs {
+    die_geo g;
+    int64_t N;
+    const uint32_t *x, *y;
+    const float* grad[3];
+    float coef[3];
+    float* plane[3];
+};
+
+__global__ __launch_bounds__(DIE_BLOCK) void k_gather_scale_backward(GatherBwdArgs a) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < a.N; n += stride) {
+        const int64_t c = die_local(a.g, die_cell((int64_t)a.x[n], a.g.gW), die_cell((int64_t)a.y[n], a.g.gH));
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const float v = a.grad[q][n] * a.coef[q];
+            if (v != 0.f) atomicAdd(&a.plane[q][c], v);          // (a zero term changes no sum: dead slots with no gradient cost nothing)
+        }
+    }
+}
+
+extern "C" int die_gather_scale_backward(const die_medium* m, const die_agents* ag, const die_action* grad_action, const float* coefs,
+                                         float* const* grad_planes, void* stream) {
+    const char* who = "die_gather_scale_backward";
+    DIE_REQUIRE(m && ag && grad_action && coefs && grad_planes, "%s: null argument", who);
+    DIE_REQUIRE(m->W >= 1 && m->H >= 1, "%s: bad size %dx%d", who, m->W, m->H);
+    DIE_REQUIRE(ag->N > 0 && grad_action->N == ag->N && ag->x && ag->y && grad_action->dx && grad_action->dy && grad_action->deposit,
+                "%s: bad arrays", who);
+    GatherBwdArgs a;
+    a.g = die_geo_of(m); a.N = ag->N; a.x = ag->x; a.y = ag->y;
+    a.grad[0] = grad_action->dx; a.grad[1] = grad_action->dy; a.grad[2] = grad_action->deposit;
+    for (int q = 0; q < 3; ++q) {
+        DIE_REQUIRE(grad_planes[q], "%s: null plane %d", who, q);
+        for (int p = 0; p < q; ++p) DIE_REQUIRE(grad_planes[p] != grad_planes[q], "%s: planes %d and %d are one", who, p, q);
+        a.plane[q] = grad_planes[q]; a.coef[q] = coefs[q];
+    }
+    const size_t bytes = (size_t)m->W * m->H * sizeof(float);
+    for (int q = 0; q < 3; ++q) {
+        if (hipMemsetAsync(a.plane[q], 0, bytes, (hipStream_t)stream) != hipSuccess) {
+            die_set_error("%s: clearing plane %d failed", who, q);
+            return DIE_ERR_HIP;
+        }
+    }
+    const int64_t g = (ag->N + DIE_BLOCK - 1) / DIE_BLOCK;
+    k_gather_scale_backward<<<(int)(g < 8192 ? g : 8192), DIE_BLOCK, 0, (hipStream_t)stream>>>(a);
+    DIE_CHECK_LAUNCH(who);
+    return DIE_OK;
+}

@@ -8,7 +8,10 @@ separable CMA-ES with stdev_init 0.1 and popsize 10 (die_amd.search.CMAES), the 
     python examples/learning_agents.py [--searcher pgpe|cmaes] [--dynamics st-perlin-wide] [--size 96] [--generations 100]
                                        [--epoch-iters 30] [--agents-die] [--max-agents alive|full|tight|N]
                                        [--reseed S] [--reseed-stride 0] [--episodes 1] [--out saved_models/agent.pt] [--time]
-                                       [--dropout P] [--dropout-seed S] [--dropout-stride K]
+                                       [--dropout P] [--dropout-seed S] [--dropout-stride K] [--init-from FILE]
+
+--init-from FILE starts the search from a saved agent (e.g. the one examples/imitate_agent.py fits by gradient descent): its
+`parameters_to_vector` becomes the searcher's `center_init` instead of a centre drawn in initial_bounds.
 
 --dropout P trains the agent with the reference's `p_agent_dropout=P` (its learning_agents.py carries 0.25): in every batched step
 replica r's sense planes are multiplied by the counter-based dropout mask of key --dropout-seed + r·--dropout-stride (default
@@ -46,7 +49,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from die_amd import CMAES, PGPE, Env                                 # noqa: E402
+from die_amd import CMAES, PGPE, Env, NeuralAutomataAgent            # noqa: E402
 from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent, episode_seeds   # noqa: E402
 from population_eval import (DYNAMICS, batch_dynamics, dropout_keywords, dynamics_names, evaluate_population, make_dynamics,   # noqa: E402
                              make_population, make_template, per_dynamics_means, resolve_episodes, run_epoch, slots)
@@ -60,16 +63,16 @@ SEARCHERS = ('pgpe', 'cmaes')
 
 
 def make_search(size, choice, popsize, epoch_iters, seed, searcher='pgpe', agents_die=False, max_agents='alive', reseed=None,
-                reseed_stride=0, episodes=1, drop_kw=None, dropout=0.):
+                reseed_stride=0, episodes=1, drop_kw=None, dropout=0., center_init=None):
     torch.manual_seed(seed)
     template = make_template(dropout)
     benv = BatchedEnv((size, size), batch_dynamics(choice, size, agents_die, popsize, episodes), replicas=popsize * episodes,
                       seeds=episode_seeds(seed, popsize, episodes), max_agents=max_agents)
     pop = BatchedNeuralAutomataAgent(benv, template, episodes=episodes, **(drop_kw or {}))
     if searcher == 'cmaes':
-        search = CMAES(popsize, pop.P, seed=seed, **CMAES_KW)
+        search = CMAES(popsize, pop.P, seed=seed, center_init=center_init, **CMAES_KW)
     else:
-        search = PGPE(popsize, pop.P, seed=seed, **SEARCH_KW)
+        search = PGPE(popsize, pop.P, seed=seed, center_init=center_init, **SEARCH_KW)
     return search.for_population(pop, epoch_iters, reseed=reseed, reseed_stride=reseed_stride), pop
 
 
@@ -154,6 +157,7 @@ def main():
     p.add_argument('--dropout', type=float, default=0., help='p_agent_dropout of the trained agent (0: none; the reference: 0.25)')
     p.add_argument('--dropout-seed', type=int, default=0, help='key of the dropout masks: replica r uses seed + r·stride')
     p.add_argument('--dropout-stride', type=int, default=1, help='0: every replica the same mask; 1: every replica its own')
+    p.add_argument('--init-from', default=None, metavar='FILE', help='a saved NeuralAutomataAgent whose weights are the search\'s first centre')
     args = p.parse_args()
     if not 0. <= args.dropout <= 1. or args.dropout_stride < 0:
         p.error('--dropout in [0, 1], --dropout-stride >= 0')
@@ -171,8 +175,13 @@ def main():
     if args.time:
         time_loops(args, N)
         return
+    center_init = None
+    if args.init_from is not None:
+        loaded = NeuralAutomataAgent.load(args.init_from)
+        center_init = torch.nn.utils.parameters_to_vector(loaded.model.parameters()).detach()
+        print(f'Starting from {args.init_from} ({center_init.numel()} parameters)')
     searcher, pop = make_search(args.size, args.dynamics, args.popsize, args.epoch_iters, args.seed, args.searcher, args.agents_die, N,
-                                args.reseed, args.reseed_stride, args.episodes, args.drop_kw, args.dropout)
+                                args.reseed, args.reseed_stride, args.episodes, args.drop_kw, args.dropout, center_init)
     print(f'Network has {pop.P} parameters; {args.popsize} candidates' + (f' x {args.episodes} episodes' if args.episodes > 1 else '') +
           f' on {args.size}x{args.size} {args.dynamics}, '
           f'{args.epoch_iters} steps each, max_agents={N}' + ('' if args.reseed is None else

@@ -793,6 +793,42 @@ int die_nca_env_step_batch_rows(const die_medium* m, const die_agents* a, const 
                                 int64_t workspace_bytes, const die_nca_dropout* drop, const die_dynamics_row* rows,
                                 const die_dynamics_row* rows_host, void* stream);
 
+/* ---- The adjoint of the NeuralAutomataAgent sensing (die_nca_grad.hip; NeuralAutomataAgent.differentiable_sense / _action) -----
+ * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
+ * The forward is z_l = conv_l(z_{l-1}) (die_conv2d per layer, z_0 = the medium's planes), s = tanh(z_L) * mask (the last layer's
+ * launch), action[c, n] = s[c, cell_n] * coef[c] (die_gather_scale).  These calls give d loss / d weights of every layer from
+ * d loss / d action; every argument is checked on the host before anything is launched. */
+
+/* The read-out's adjoint: the three fp32 (m->W, m->H) planes are cleared (on `stream`), then
+ *   grad_planes[c][cell_n] += grad_action[c][n] * coefs[c]   for EVERY slot n < a->N,
+ * with die_gather_scale's indexing; grad_action's dx, dy, deposit arrays are the gradient's three rows.  fp32 atomic adds: where
+ * several slots with a non-zero gradient stand on one cell the order of their sum is not fixed; the result is bit-reproducible
+ * run to run whenever no two slots with a non-zero gradient share a cell (alive agents never do). */
+int die_gather_scale_backward(const die_medium* m, const die_agents* a, const die_action* grad_action, const float* coefs,
+                              float* const* grad_planes, void* stream);
+
+/* Bytes of die_conv2d_backward's workspace: one partial row of cout * cin * k * k floats per 16 x 64 tile,
+ *   ceil(W / 16) * ceil(H / 64) * cout * cin * k * k * 4;   -1 for a shape die_conv2d_backward refuses. */
+int64_t die_conv2d_backward_workspace_bytes(int32_t W, int32_t H, int32_t cin, int32_t cout, int32_t k);
+
+/* One layer's adjoint, two launches.  `in` / `epoch`: the layer's input planes as die_conv2d read them; `grad_out`: cout fp32
+ * planes, the gradient at the layer's outputs; `weights`: (cout, cin, k, k).
+ *   grad_weights[o, i, a, b] = sum_{x, y} g[o, x, y] * in[i, pad(x + a - r), pad(y + b - r)]   (cout * cin * k * k fp32, overwritten)
+ *   grad_in[i, x, y] = sum_{o, a, b} weights[o, i, a, b] * g[o, pad'(x - a + r), pad'(y - b + r)]   (cin fp32 planes, overwritten;
+ *       NULL: not wanted — the first layer's input is the medium.  pad': 'circular' wraps, 'zeros' drops what falls outside)
+ * where g = grad_out, or, for the layer that carried the tanh, g = grad_out * mask * (1 - t * t): `fwd_out` are then that
+ * layer's cout forward output planes t = tanh(z) WITHOUT the dropout mask (die_conv2d's, not die_conv2d_dropout's), and `drop`,
+ * if the forward was masked, the die_nca_dropout it was masked with (the mask is recomputed, 0 or keep per cell; nothing is
+ * divided by keep).  fwd_out NULL: no tanh in this layer (drop must then be NULL).
+ *   The weight gradient uses no float atomics: the first launch writes one partial row per tile into `workspace`
+ * (die_conv2d_backward_workspace_bytes), the second sums the rows in tile-index order in float64 and stores fp32 — the same
+ * inputs give the same bits on every run.  k in {1, 3, 5, 7}, 1..4 channels; padding_mode DIE_PAD_CIRCULAR or DIE_PAD_ZEROS
+ * (DIE_PAD_REFLECT / DIE_PAD_REPLICATE: DIE_ERR_UNSUPPORTED).  grad_in may be none of the call's other planes. */
+int die_conv2d_backward(int32_t W, int32_t H, int32_t cin, const die_conv_plane* in, int32_t epoch, int32_t cout,
+                        const float* const* grad_out, int32_t k, const float* weights, float* grad_weights,
+                        float* const* grad_in, const float* const* fwd_out, const die_nca_dropout* drop,
+                        int32_t padding_mode, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* die_food_flow_batch on the replicas whose bit is set in replica_mask (bit r = replica r); the others' planes are not touched.
  * One launch: a row of workgroups per replica, those of unset replicas exit at once.  A full mask leaves exactly what
  * die_food_flow_batch leaves; an empty mask launches nothing.  Bits at or above b->replicas must be 0. */
