@@ -113,7 +113,7 @@ class BatchedEnv:
         elif max_agents is None:
             self._fixed = int(field_size[0]) * int(field_size[1])
         else:
-            if isinstance(max_agents, bool) or int(max_agents) != max_agents or int(max_agents) < 1:
+            if not _is_integer(max_agents, 1):
                 raise ValueError(f'max_agents={max_agents!r}: at least one slot per replica')
             self._fixed = int(max_agents)
         slots = 'alive' if self._fixed is None else self._fixed
@@ -202,32 +202,30 @@ class BatchedEnv:
         of every candidate: `episode_seeds`).  Not together with `seed`.  Small worlds: one die_init_batch_seeds call, the same
         five launches, the list handed to the kernels by value."""
         listed = seeds is not None
+        if listed and seed is not None:
+            raise ValueError('reset: seed= (seed + r·seed_stride) or seeds= (a list of R seeds), not both')
+        if (listed or seed is not None) and self._fixed is None:
+            raise ValueError(f"reset({'seeds' if listed else 'seed'}=...) needs every replica to hold the same number of slots: build "
+                             "the BatchedEnv with max_agents=N (or None for W·H) instead of 'alive'")
         if listed:
-            if seed is not None:
-                raise ValueError('reset: seed= (seed + r·seed_stride) or seeds= (a list of R seeds), not both')
-            if self._fixed is None:
-                raise ValueError("reset(seeds=...) needs every replica to hold the same number of slots: build the BatchedEnv "
-                                 "with max_agents=N (or None for W·H) instead of 'alive'")
             seeds = list(seeds)
             if len(seeds) != self.R:
                 raise ValueError(f'reset(seeds=...): {len(seeds)} seeds for {self.R} replicas')
             for q in seeds:
-                if isinstance(q, bool) or int(q) != q:
+                if not _is_integer(q):
                     raise ValueError(f'reset(seeds=...): {q!r} is not an integer seed')
             seeds = [int(q) for q in seeds]
-        if seed is not None:
-            if self._fixed is None:
-                raise ValueError("reset(seed=...) needs every replica to hold the same number of slots: build the BatchedEnv "
-                                 "with max_agents=N (or None for W·H) instead of 'alive'")
-            if isinstance(seed_stride, bool) or int(seed_stride) != seed_stride or int(seed_stride) < 0:
+        elif seed is not None:
+            if not _is_integer(seed_stride, 0):
                 raise ValueError(f'seed_stride={seed_stride!r}: a non-negative integer')
             seed, seed_stride = int(seed), int(seed_stride)
             seeds = [seed + r * seed_stride for r in range(self.R)]
         if self._flow_k0 is not None:
             self.dynamics.op_food_flow._k = self._flow_k0
         self._steps = 0
-        if seed is not None or listed:
+        if seeds is not None:
             self._reseed(seeds, seed, seed_stride)
+            self.seeds = seeds
             return
         if self.per_replica:
             for e, snap in zip(self.envs, self._initial):
@@ -246,7 +244,6 @@ class BatchedEnv:
                     e.reset(seed=q)
                 except ValueError as err:
                     raise ValueError(f'replica {r} (seed {q}): {err}') from err
-            self.seeds = seeds
             self._obs = [e._get_current_obs for e in self.envs]
             return
         self.chem, self.chem_next = self._initial[1:]
@@ -255,17 +252,13 @@ class BatchedEnv:
         # Env._init_data: the Perlin food of DataInitializer.init_medium (its spec holds no seed-drawn value the kernel reads)
         spec = food_spec_from_seed(seeds[0] if seed is None else seed, scale=0.5, perlin_octaves=8, threshold=1.0)
         mask = 0xFFFFFFFFFFFFFFFF
-        if seed is None:
-            words = (C.c_uint64 * self.R)(*[q & mask for q in seeds])          # read during the call, passed by value
-            _lib.check(_lib.lib.die_init_batch_seeds(C.byref(m), C.byref(a), C.byref(b), float(self.dynamics.init_agent_ratio), words,
-                                                     self.R, C.byref(spec), _ptr(self._counts), _ptr(self._init_ws),
-                                                     self._init_ws.numel(), stream_ptr(self.device)), 'die_init_batch_seeds')
-            self.seeds = seeds
-            return
-        _lib.check(_lib.lib.die_init_batch(C.byref(m), C.byref(a), C.byref(b), float(self.dynamics.init_agent_ratio), seed & mask,
-                                           seed_stride & mask, C.byref(spec), _ptr(self._counts), _ptr(self._init_ws),
-                                           self._init_ws.numel(), stream_ptr(self.device)), 'die_init_batch')
-        self.seeds = seeds
+        if seed is None:                            # the list: read during the call, passed by value
+            name, worlds = 'die_init_batch_seeds', ((C.c_uint64 * self.R)(*[q & mask for q in seeds]), self.R)
+        else:
+            name, worlds = 'die_init_batch', (seed & mask, seed_stride & mask)
+        _lib.check(getattr(_lib.lib, name)(C.byref(m), C.byref(a), C.byref(b), float(self.dynamics.init_agent_ratio), *worlds,
+                                           C.byref(spec), _ptr(self._counts), _ptr(self._init_ws), self._init_ws.numel(),
+                                           stream_ptr(self.device)), name)
 
     # ------------------------------------------------------------------
     def _structs(self):
@@ -273,8 +266,10 @@ class BatchedEnv:
         m = _lib.Medium(self.W, self.H, fdt, self.epoch, _ptr(self.owner), _ptr(self.food), _ptr(self.chem), _ptr(self.chem_next),
                         0, 0, 0, 0, 0, 0, 0, 0, None)
         a = _lib.Agents(self.Nmax, _ptr(self.x), _ptr(self.y), _ptr(self.alive), _ptr(self.agent_food), None)
-        b = _lib.Batch(self.R, 0, self.W * self.H, self.Nmax, 1, (C.c_int64 * 64)(*self.n))
-        return m, a, self._dynamics_struct(self.dynamics), b
+        return m, a, self._dynamics_struct(self.dynamics), self._batch_struct()
+
+    def _batch_struct(self) -> _lib.Batch:
+        return _lib.Batch(self.R, 0, self.W * self.H, self.Nmax, 1, (C.c_int64 * 64)(*self.n))
 
     def _dynamics_struct(self, d: Dynamics) -> _lib.Dynamics:
         boundary = _lib.DIE_BOUNDARY_WRAP if d.boundary == BoundaryCondition.wrap else _lib.DIE_BOUNDARY_LIMIT
@@ -301,101 +296,32 @@ class BatchedEnv:
     def step(self, agent: Union['BatchedPhysarumAgent', 'BatchedPhysarumPopulation', 'BatchedNeuralAutomataAgent'],
              results: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One step of every replica: `agent.forward` + `Env.step` fused, two launches for the whole batch (L + 2 for a
-        BatchedNeuralAutomataAgent of L layers; one more with agents_die).  Returns the (R, 2) float64 tensor of die_step_result words (device;
-        `read_results` decodes)."""
-        if isinstance(agent, BatchedNeuralAutomataAgent):
-            return self._step_nca(agent, results)
-        if isinstance(agent, BatchedPhysarumPopulation):
-            return self._step_physarum_population(agent, results)
-        flow = self._flow_kind()                    # refused before anything is launched
-        if results is None:
-            results = torch.empty((self.R, 2), dtype=torch.float64, device=self.device)
-        if self.per_replica:
-            return self._step_per_replica(agent, lambda r: agent.agents[r], flow, results)
-        self.epoch += 1
-        if self.epoch > _lib.OWNER_EPOCH_MAX:
-            self.owner.zero_()
-            self.epoch = 1
-        m, a, dyn, b = self._structs()
-        g = agent._struct()
-        if self._rows is None:
-            _lib.check(_lib.lib.die_forward_env_step_batch(C.byref(m), C.byref(a), C.byref(g), None, C.byref(dyn), C.byref(b), _ptr(results),
-                                                           _ptr(self._ws), self._ws.numel(), stream_ptr(self.device)),
-                       'die_forward_env_step_batch')
-        else:                                       # per-replica Dynamics: the same step, each replica under its row
-            _lib.check(_lib.lib.die_forward_env_step_batch_rows(C.byref(m), C.byref(a), C.byref(g), None, C.byref(dyn), C.byref(b),
-                                                                _ptr(results), _ptr(self._ws), self._ws.numel(), _ptr(self._rows),
-                                                                self._rows_host, stream_ptr(self.device)),
-                       'die_forward_env_step_batch_rows')
-        agent._calls += 1
-        self.chem, self.chem_next = self.chem_next, self.chem
-        self._food_flow(flow, m, b)
-        self._steps += 1
-        return results
+        BatchedNeuralAutomataAgent of L layers; one more with dead slots, one more with a flow; for a BatchedPhysarumPopulation a
+        decode launch first when `parameters` was written since the last one).  Returns the (R, 2) float64 tensor of
+        die_step_result words (device; `read_results` decodes).
 
-    def _step_physarum_population(self, pop: 'BatchedPhysarumPopulation', results: Optional[torch.Tensor]) -> torch.Tensor:
-        """`step` for a BatchedPhysarumPopulation: the same sequence with the population's table (two launches; one more
-        with dead slots, one more with a flow; a decode launch first when `parameters` was written since the last one)."""
-        pop._check_step(self)                       # every refusal before anything is launched
-        flow = self._flow_kind()
-        if results is None:
-            results = torch.empty((self.R, 2), dtype=torch.float64, device=self.device)
-        if self.per_replica:
-            return self._step_per_replica(pop, lambda r: pop.agents[r], flow, results)
-        pop._sync()
-        self.epoch += 1
-        if self.epoch > _lib.OWNER_EPOCH_MAX:
-            self.owner.zero_()
-            self.epoch = 1
-        m, a, dyn, b = self._structs()
-        g = pop._struct()
-        if self._rows is None:
-            _lib.check(_lib.lib.die_physarum_env_step_batch(C.byref(m), C.byref(a), C.byref(g), _ptr(pop._table), None, C.byref(dyn), C.byref(b),
-                                                            _ptr(results), _ptr(self._ws), self._ws.numel(), stream_ptr(self.device)),
-                       'die_physarum_env_step_batch')
-        else:
-            _lib.check(_lib.lib.die_physarum_env_step_batch_rows(C.byref(m), C.byref(a), C.byref(g), _ptr(pop._table), None, C.byref(dyn),
-                                                                 C.byref(b), _ptr(results), _ptr(self._ws), self._ws.numel(),
-                                                                 _ptr(self._rows), self._rows_host, stream_ptr(self.device)),
-                       'die_physarum_env_step_batch_rows')
-        pop._calls += 1
-        self.chem, self.chem_next = self.chem_next, self.chem
-        self._food_flow(flow, m, b)
-        self._steps += 1
-        return results
-
-    def _step_nca(self, agent: 'BatchedNeuralAutomataAgent', results: Optional[torch.Tensor]) -> torch.Tensor:
+        One path for the three agent kinds.  What is particular to a kind it says itself: `_check_step(env)` (its refusals),
+        `_replica_agent(r)` (replica r's stand-alone agent, large worlds), `_claim_epoch(env)` (the epoch its claims are made
+        at), `_launch(...)` (its struct and its library entry point) and `_stepped()` (its counters after a step).  A step that is
+        refused leaves the batch as it was."""
         agent._check_step(self)                     # every refusal before anything is launched
         flow = self._flow_kind()
         if results is None:
             results = torch.empty((self.R, 2), dtype=torch.float64, device=self.device)
         if self.per_replica:
-            self._step_per_replica(agent, agent._replica_agent, flow, results)
+            self._step_per_replica(agent, flow, results)
             agent._stepped()
             return results
-        drop = agent._dropout()
-        # the sensing reads the claim plane at the current epoch, the claims are made at the next one; at the wrap the
-        # library clears the claim planes between the two (Env.step runs forward before its next_epoch the same way)
-        sense_epoch = self.epoch
-        self.epoch = sense_epoch % _lib.OWNER_EPOCH_MAX + 1
+        epoch = self.epoch
+        agent._claim_epoch(self)
         m, a, dyn, b = self._structs()
-        nca = agent._struct(sense_epoch)
-        name = 'die_nca_env_step_batch' if drop is None else 'die_nca_env_step_batch_dropout'
-        if self._rows is not None:                  # per-replica Dynamics: one entry for both, the mask nullable
-            name = 'die_nca_env_step_batch_rows'
-            rc = _lib.lib.die_nca_env_step_batch_rows(C.byref(m), C.byref(a), C.byref(nca), None, C.byref(dyn), C.byref(b), _ptr(results),
-                                                      _ptr(self._ws), self._ws.numel(), None if drop is None else C.byref(drop),
-                                                      _ptr(self._rows), self._rows_host, stream_ptr(self.device))
-        elif drop is None:
-            rc = _lib.lib.die_nca_env_step_batch(C.byref(m), C.byref(a), C.byref(nca), None, C.byref(dyn), C.byref(b), _ptr(results),
-                                                 _ptr(self._ws), self._ws.numel(), stream_ptr(self.device))
-        else:                                       # the same step, its last conv launch masked
-            rc = _lib.lib.die_nca_env_step_batch_dropout(C.byref(m), C.byref(a), C.byref(nca), None, C.byref(dyn), C.byref(b),
-                                                         _ptr(results), _ptr(self._ws), self._ws.numel(), C.byref(drop),
-                                                         stream_ptr(self.device))
-        if rc != _lib.DIE_OK:
-            self.epoch = sense_epoch                # refused before any launch: nothing changed
-            _lib.check(rc, name)
+        rows = () if self._rows is None else (_ptr(self._rows), self._rows_host)    # per-replica Dynamics: each replica under its row
+        try:
+            agent._launch((C.byref(m), C.byref(a)), (None, C.byref(dyn), C.byref(b), _ptr(results), _ptr(self._ws), self._ws.numel()),
+                          rows, stream_ptr(self.device))
+        except Exception:
+            self.epoch = epoch                      # refused before any launch: nothing changed
+            raise
         agent._calls += 1
         agent._stepped()
         self.chem, self.chem_next = self.chem_next, self.chem
@@ -429,8 +355,8 @@ class BatchedEnv:
             _lib.check(_lib.lib.die_food_flow_batch_masked(C.byref(m), C.byref(b), flow, op.next_t(), op.scale, op.decay, octaves, seed,
                                                            self._flow_mask, stream_ptr(self.device)), 'die_food_flow_batch_masked')
 
-    def _step_per_replica(self, agent, replica_agent, flow: Optional[int], results: torch.Tensor) -> torch.Tensor:
-        """Large worlds: replica r is its own Env stepped by `replica_agent(r)` on its own stream.  With a flow, each Env gets
+    def _step_per_replica(self, agent, flow: Optional[int], results: torch.Tensor) -> None:
+        """Large worlds: replica r is its own Env stepped by `agent._replica_agent(r)` on its own stream.  With a flow, each Env gets
         an operator of its own over the batch's sequence, at the batch's counter: all apply the same t, each on its stream."""
         op = self.dynamics.op_food_flow
         for r, e in enumerate(self.envs):
@@ -444,14 +370,13 @@ class BatchedEnv:
         for r, (e, st) in enumerate(zip(self.envs, self.streams)):
             st.wait_event(start)
             with torch.cuda.stream(st):
-                self._obs[r], res, *_ = e.step(replica_agent(r).forward(self._obs[r]))
+                self._obs[r], res, *_ = e.step(agent._replica_agent(r).forward(self._obs[r]))
                 results[r].copy_(res)
             cur.wait_stream(st)
         if flow is not None:
             op.next_t()
         agent._calls += 1
         self._steps += 1
-        return results
 
     def run(self, agent: Union['BatchedPhysarumAgent', 'BatchedPhysarumPopulation', 'BatchedNeuralAutomataAgent'], n_steps: int) -> torch.Tensor:
         out = torch.empty((n_steps, self.R, 2), dtype=torch.float64, device=self.device)
@@ -482,7 +407,7 @@ def episode_seeds(seed: int, candidates: int, episodes: int, candidate_stride: i
     """The R = candidates·episodes seeds of `BatchedEnv.reset(seeds=...)` in candidate-major order: replica c·E + e gets
     seed + e + candidate_stride·c·E.  Stride 0: every candidate sees the same E worlds; stride 1: every replica its own."""
     for name, v, low in (('candidates', candidates, 1), ('episodes', episodes, 1), ('candidate_stride', candidate_stride, 0)):
-        if isinstance(v, bool) or int(v) != v or int(v) < low:
+        if not _is_integer(v, low):
             raise ValueError(f'{name}={v!r}: an integer >= {low}')
     seed, C_, E, stride = int(seed), int(candidates), int(episodes), int(candidate_stride)
     return [seed + e + stride * c * E for c in range(C_) for e in range(E)]
@@ -495,7 +420,7 @@ def episode_dynamics(dynamics: Sequence[Dynamics], candidates: int) -> List[Dyna
     dynamics = list(dynamics)
     if not dynamics or not all(isinstance(q, Dynamics) for q in dynamics):
         raise ValueError('dynamics: a non-empty sequence of Dynamics')
-    if isinstance(candidates, bool) or int(candidates) != candidates or int(candidates) < 1:
+    if not _is_integer(candidates, 1):
         raise ValueError(f'candidates={candidates!r}: an integer >= 1')
     return [dynamics[e] for _ in range(int(candidates)) for e in range(len(dynamics))]
 
@@ -530,10 +455,24 @@ def _shared_dynamics(dynamics, replicas: int):
     return dataclasses.replace(first, op_food_flow=_identity_food_flow if op is None else op), dyn, mask
 
 
+def _is_integer(v, low: Optional[int] = None, exact: bool = False) -> bool:
+    """An integer, not a bool, at least `low`.  `exact`: an `int` itself (2.0 and numpy's integers are refused); otherwise any
+    value equal to its int()."""
+    if isinstance(v, bool) or (not isinstance(v, int) if exact else int(v) != v):
+        return False
+    return low is None or int(v) >= low
+
+
+def _worlds_per_candidate(episodes) -> int:
+    """An `episodes` argument, checked (the populations here and the searchers of die_amd.search)."""
+    if not _is_integer(episodes, 1, exact=True):
+        raise ValueError(f'episodes={episodes!r}: an integer >= 1 (worlds per candidate)')
+    return episodes
+
+
 def _episodes(env, episodes) -> int:
     """`episodes` of a population on `env`, checked: R = candidates·episodes replicas."""
-    if isinstance(episodes, bool) or not isinstance(episodes, int) or episodes < 1:
-        raise ValueError(f'episodes={episodes!r}: an integer >= 1 (worlds per candidate)')
+    _worlds_per_candidate(episodes)
     if env.R % episodes:
         raise ValueError(f'episodes={episodes}: the BatchedEnv holds {env.R} replicas, not a multiple of {episodes} — replica c·E + e is '
                          'candidate c on its e-th world')
@@ -572,7 +511,62 @@ def _env_restore(e: Env, snap: dict) -> None:
     e.last_result = None
 
 
-class BatchedPhysarumAgent:
+class _PhysarumReplicas:
+    """What BatchedPhysarumAgent and BatchedPhysarumPopulation share: a heading per agent slot of every replica (small worlds; a
+    list `agents` of R stand-alone PhysarumAgents in large ones), and a step that senses and claims at one epoch."""
+
+    def _alloc_headings(self) -> None:
+        env = self.env
+        self._hd_hi = torch.zeros((env.R, env.Nmax), dtype=torch.int32, device=env.device)
+        self._hd_lo = torch.zeros_like(self._hd_hi)
+
+    def direction_rads_numpy(self, r: int) -> np.ndarray:
+        if self.env.per_replica:
+            torch.cuda.synchronize(self.env.device)
+            return self.agents[r].direction_rads_numpy()
+        k = self.env.n[r]
+        return join64(self._hd_hi[r, :k].contiguous(), self._hd_lo[r, :k].contiguous()).cpu().numpy()
+
+    # ------------------------------------------------------------------ BatchedEnv.step
+    def _check_step(self, env: BatchedEnv) -> None:
+        pass
+
+    def _replica_agent(self, r: int):
+        return self.agents[r]
+
+    def _claim_epoch(self, env: BatchedEnv) -> None:
+        env.epoch += 1
+        if env.epoch > _lib.OWNER_EPOCH_MAX:
+            env.owner.zero_()
+            env.epoch = 1
+
+    def _stepped(self) -> None:
+        pass
+
+
+class _Population:
+    """What the two populations share: `parameters`, ONE (candidates, P) float32 device matrix, one row per candidate."""
+
+    def _matrix(self, rows, what: str, columns) -> torch.Tensor:
+        """`rows` as a tensor of one row per candidate, or the refusal (`what` names the argument, `columns` its P columns)."""
+        t = torch.as_tensor(rows).detach()
+        if tuple(t.shape) != (self.candidates, self.P):
+            rows_are = 'R replicas' if self.episodes == 1 else f'{self.candidates} candidates of {self.episodes} episodes each'
+            raise ValueError(f'{what} of shape {tuple(t.shape)}: ({self.candidates}, {self.P}) expected ({rows_are} x {columns})')
+        return t
+
+    def _check_parameters(self) -> None:
+        p = self.parameters
+        if tuple(p.shape) != (self.candidates, self.P) or p.dtype != torch.float32 or p.device != self.env.device or not p.is_contiguous():
+            raise ValueError(f'parameters must stay a contiguous ({self.candidates}, {self.P}) float32 tensor on {self.env.device}')
+
+    def _check_step(self, env: BatchedEnv) -> None:
+        if env is not self.env:
+            raise ValueError('this population was built for another BatchedEnv')
+        self._check_parameters()
+
+
+class BatchedPhysarumAgent(_PhysarumReplicas):
     """R PhysarumAgent objects as one: replica r's headings and Philox streams are those of
     `PhysarumAgent(max_agents=K_r, seed=seed + r, ...)` (core/agent/gradient.py:139-166)."""
 
@@ -590,14 +584,11 @@ class BatchedPhysarumAgent:
         self._p = dict(scale=scale, deposit=deposit, sense_offset=sense_offset, normalized=normalized_grad,
                        grad_clip=-1.0 if grad_clip is None else grad_clip, turn=math.radians(turn_angle),
                        sense=math.radians(sense_angle), rtol=turn_tolerance)
-        dev = env.device
-        self._hd_hi = torch.zeros((env.R, env.Nmax), dtype=torch.int32, device=dev)
-        self._hd_lo = torch.zeros((env.R, env.Nmax), dtype=torch.int32, device=dev)
+        self._alloc_headings()
         for r in range(env.R):                      # the headings a stand-alone agent of that seed starts with
             k = env.n[r]
             _lib.check(_lib.lib.die_init_heading(_ptr(self._hd_hi[r]), _ptr(self._hd_lo[r]), None, None, k, self._p['turn'],
-                                                 (self.seed + r) & 0xFFFFFFFFFFFFFFFF, stream_ptr(dev)), 'die_init_heading')
-        self._calls = 0
+                                                 (self.seed + r) & 0xFFFFFFFFFFFFFFFF, stream_ptr(env.device)), 'die_init_heading')
 
     def _struct(self) -> _lib.GradientAgent:
         p = self._p
@@ -605,12 +596,10 @@ class BatchedPhysarumAgent:
                                   p['grad_clip'], p['turn'], p['sense'], p['rtol'], _ptr(self._hd_hi), _ptr(self._hd_lo), None, None, None,
                                   self.seed & 0xFFFFFFFFFFFFFFFF, self._calls & 0xFFFFFFFF, 0, None)
 
-    def direction_rads_numpy(self, r: int) -> np.ndarray:
-        if self.env.per_replica:
-            torch.cuda.synchronize(self.env.device)
-            return self.agents[r].direction_rads_numpy()
-        k = self.env.n[r]
-        return join64(self._hd_hi[r, :k].contiguous(), self._hd_lo[r, :k].contiguous()).cpu().numpy()
+    def _launch(self, front: tuple, back: tuple, rows: tuple, stream) -> None:
+        """The library's step: (m, a), this agent's struct, (no action, d, b, results, workspace), the Dynamics rows, the stream."""
+        name = 'die_forward_env_step_batch_rows' if rows else 'die_forward_env_step_batch'
+        _lib.check(getattr(_lib.lib, name)(*front, C.byref(self._struct()), *back, *rows, stream), name)
 
 
 PARAMETER_NAMES = ('scale', 'deposit', 'sense_offset', 'turn_angle', 'sense_angle', 'turn_tolerance')
@@ -668,7 +657,7 @@ class ParameterSpace:
         return _lib.ParameterSpace((C.c_float * 6)(*self.lo.tolist()), (C.c_float * 6)(*self.hi.tolist()))
 
 
-class BatchedPhysarumPopulation:
+class BatchedPhysarumPopulation(_Population, _PhysarumReplicas):
     """R PhysarumAgent candidates whose scale, deposit, sense_offset, turn_angle, sense_angle and turn_tolerance differ per
     replica; candidate r steps replica r of a BatchedEnv exactly as `candidate(r)` steps the stand-alone Env of seeds[r].
     normalized_grad and grad_clip are shared (they choose the kernel), as a NeuralAutomataAgent population shares its
@@ -730,17 +719,12 @@ class BatchedPhysarumPopulation:
         else:
             self.parameters.copy_(self._rows(parameters, 'parameters'))
         if not env.per_replica:
-            self._hd_hi = torch.zeros((env.R, env.Nmax), dtype=torch.int32, device=dev)
-            self._hd_lo = torch.zeros((env.R, env.Nmax), dtype=torch.int32, device=dev)
+            self._alloc_headings()
         self.reset()
 
     # ------------------------------------------------------------------ parameters
     def _rows(self, rows, what: str) -> torch.Tensor:
-        t = torch.as_tensor(rows).detach().to(torch.float32)
-        if tuple(t.shape) != (self.candidates, self.P):
-            rows_are = 'R replicas' if self.episodes == 1 else f'{self.candidates} candidates of {self.episodes} episodes each'
-            raise ValueError(f'{what} of shape {tuple(t.shape)}: ({self.candidates}, {self.P}) expected ({rows_are} x {PARAMETER_NAMES})')
-        return t
+        return self._matrix(rows, what, PARAMETER_NAMES).to(torch.float32)
 
     def _natural_rows(self, rows) -> torch.Tensor:
         t = self._rows(rows, 'values')
@@ -823,33 +807,21 @@ class BatchedPhysarumPopulation:
             v = self.values()
             self.agents = [self._agent(v[r // self.episodes], self.env.n[r], self.seed + r) for r in range(self.R)]
             return
-        env = self.env
-        b = _lib.Batch(env.R, 0, env.W * env.H, env.Nmax, 1, (C.c_int64 * 64)(*env.n))
+        b = self.env._batch_struct()
         _lib.check(_lib.lib.die_physarum_heading_batch(_ptr(self._hd_hi), _ptr(self._hd_lo), C.byref(b), _ptr(self._table),
-                                                       self.seed & 0xFFFFFFFFFFFFFFFF, stream_ptr(env.device)),
+                                                       self.seed & 0xFFFFFFFFFFFFFFFF, stream_ptr(self.env.device)),
                    'die_physarum_heading_batch')
-
-    def _check_parameters(self):
-        p = self.parameters
-        if tuple(p.shape) != (self.candidates, self.P) or p.dtype != torch.float32 or p.device != self.env.device or not p.is_contiguous():
-            raise ValueError(f'parameters must stay a contiguous ({self.candidates}, {self.P}) float32 tensor on {self.env.device}')
-
-    def _check_step(self, env: BatchedEnv):
-        if env is not self.env:
-            raise ValueError('this population was built for another BatchedEnv')
-        self._check_parameters()
 
     def _struct(self) -> _lib.GradientAgent:
         return _lib.GradientAgent(_lib.DIE_AGENT_PHYSARUM, int(self.normalized_grad), 0.0, 0.0, 0.0, 0.0, 0.0,
                                   -1.0 if self.grad_clip is None else self.grad_clip, 0.0, 0.0, 0.0, _ptr(self._hd_hi), _ptr(self._hd_lo),
                                   None, None, None, self.seed & 0xFFFFFFFFFFFFFFFF, self._calls & 0xFFFFFFFF, 0, None)
 
-    def direction_rads_numpy(self, r: int) -> np.ndarray:
-        if self.env.per_replica:
-            torch.cuda.synchronize(self.env.device)
-            return self.agents[r].direction_rads_numpy()
-        k = self.env.n[r]
-        return join64(self._hd_hi[r, :k].contiguous(), self._hd_lo[r, :k].contiguous()).cpu().numpy()
+    def _launch(self, front: tuple, back: tuple, rows: tuple, stream) -> None:
+        """BatchedPhysarumAgent._launch with the population's table after the struct (decoded first if `parameters` was written)."""
+        self._sync()
+        name = 'die_physarum_env_step_batch_rows' if rows else 'die_physarum_env_step_batch'
+        _lib.check(getattr(_lib.lib, name)(*front, C.byref(self._struct()), _ptr(self._table), *back, *rows, stream), name)
 
 
 def _architecture(agent: NeuralAutomataAgent) -> dict:
@@ -860,7 +832,7 @@ def _architecture(agent: NeuralAutomataAgent) -> dict:
                 shapes=tuple(tuple(k.weight.shape) for k in layers))
 
 
-class BatchedNeuralAutomataAgent:
+class BatchedNeuralAutomataAgent(_Population):
     """A population of R NeuralAutomataAgent candidates of one architecture, candidate r stepping replica r of a BatchedEnv.
     The weights are ONE (R, P) float32 device tensor `parameters`: row r is `parameters_to_vector(model.parameters())` of
     candidate r — the layout evolution strategies hand around.  In-place writes to `parameters` are seen by the next step.
@@ -886,9 +858,9 @@ class BatchedNeuralAutomataAgent:
                  dropout_seed: Optional[int] = None, dropout_seed_stride: int = 1):
         if not isinstance(template, NeuralAutomataAgent):
             raise TypeError('template: a NeuralAutomataAgent')
-        if dropout_seed is not None and (isinstance(dropout_seed, bool) or int(dropout_seed) != dropout_seed):
+        if dropout_seed is not None and not _is_integer(dropout_seed):
             raise ValueError(f'dropout_seed={dropout_seed!r}: an integer, or None')
-        if isinstance(dropout_seed_stride, bool) or int(dropout_seed_stride) != dropout_seed_stride or int(dropout_seed_stride) < 0:
+        if not _is_integer(dropout_seed_stride, 0):
             raise ValueError(f'dropout_seed_stride={dropout_seed_stride!r}: a non-negative integer')
         self.dropout_seed = None if dropout_seed is None else int(dropout_seed)
         self.dropout_seed_stride = int(dropout_seed_stride)
@@ -912,9 +884,7 @@ class BatchedNeuralAutomataAgent:
         self.P = off
         if parameters is None:
             parameters = parameters_to_vector(template.model.parameters()).detach().reshape(1, -1).expand(self.candidates, -1)
-        t = torch.as_tensor(parameters)
-        if tuple(t.shape) != (self.candidates, self.P):           # (before anything is allocated)
-            raise ValueError(self._shape_error(t))
+        self._matrix(parameters, 'parameters', 'P weights')         # (refused before anything is allocated)
         self.parameters = torch.empty((self.candidates, self.P), dtype=torch.float32, device=env.device)
         self.set_parameters(parameters)
         self._calls = 0
@@ -960,14 +930,7 @@ class BatchedNeuralAutomataAgent:
 
     def set_parameters(self, parameters) -> None:
         """Copy an (R, P) matrix of candidate rows in ((C, P) with episodes: one row per candidate)."""
-        t = torch.as_tensor(parameters)
-        if tuple(t.shape) != (self.candidates, self.P):
-            raise ValueError(self._shape_error(t))
-        self.parameters.copy_(t.detach())
-
-    def _shape_error(self, t: torch.Tensor) -> str:
-        rows_are = 'R replicas' if self.episodes == 1 else f'{self.candidates} candidates of {self.episodes} episodes each'
-        return f'parameters of shape {tuple(t.shape)}: ({self.candidates}, {self.P}) expected ({rows_are} x P weights)'
+        self.parameters.copy_(self._matrix(parameters, 'parameters', 'P weights'))
 
     def candidate(self, r: int) -> NeuralAutomataAgent:
         """Candidate r as a stand-alone NeuralAutomataAgent (on the host: `save()` the winner).  With a `dropout_seed` it carries
@@ -1003,17 +966,30 @@ class BatchedNeuralAutomataAgent:
             self.dropout_step += 1                  # counts forward calls, masked or not (as NeuralAutomataAgent.sense does)
 
     # ------------------------------------------------------------------ step
-    def _check_step(self, env: BatchedEnv):
-        if env is not self.env:
-            raise ValueError('this population was built for another BatchedEnv')
-        p = self.parameters
-        if tuple(p.shape) != (self.candidates, self.P) or p.dtype != torch.float32 or p.device != env.device or not p.is_contiguous():
-            raise ValueError(f'parameters must stay a contiguous ({self.candidates}, {self.P}) float32 tensor on {env.device}')
+    def _check_step(self, env: BatchedEnv) -> None:
+        super()._check_step(env)
         model = self.template.model
         if model.agent_dropout.p > 0 and model.training and self.dropout_seed is None:
             raise NotImplementedError('p_agent_dropout > 0 in training mode: without a dropout_seed its mask is a host-RNG torch op, '
                                       'not batched (build the population with dropout_seed=S for the counter-based mask, call '
                                       'model.eval(), or step the candidates one at a time)')
+
+    def _claim_epoch(self, env: BatchedEnv) -> None:
+        # the sensing reads the claim plane at the current epoch, the claims are made at the next one; at the wrap the
+        # library clears the claim planes between the two (Env.step runs forward before its next_epoch the same way)
+        self._sense_epoch = env.epoch
+        env.epoch = env.epoch % _lib.OWNER_EPOCH_MAX + 1
+
+    def _launch(self, front: tuple, back: tuple, rows: tuple, stream) -> None:
+        """BatchedPhysarumAgent._launch with the dropout mask of the coming step after the workspace: one entry point without
+        it, one with it (the same step, its last conv launch masked), and with Dynamics rows one for both, the mask nullable."""
+        drop = self._dropout()
+        mask = () if drop is None else (C.byref(drop),)
+        if rows:
+            name, mask = 'die_nca_env_step_batch_rows', mask or (None,)
+        else:
+            name = 'die_nca_env_step_batch' if drop is None else 'die_nca_env_step_batch_dropout'
+        _lib.check(getattr(_lib.lib, name)(*front, C.byref(self._struct(self._sense_epoch)), *back, *mask, *rows, stream), name)
 
     def _struct(self, sense_epoch: int) -> _lib.NcaBatch:
         base = self.parameters.data_ptr()

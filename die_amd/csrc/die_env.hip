@@ -1157,9 +1157,19 @@ static int batch_ws_check(const die_dynamics* d, const die_batch* b, int64_t ws_
     return DIE_OK;
 }
 
-// the step half's arguments of every replica (die_forward_env_step_batch, die_nca_env_step_batch), checked before any launch
-static int batch_step_args(StepArgs& k, BatchArgs& ba, int64_t& nmax, const die_medium* m, const die_agents* a, const die_action* act,
-                           const die_dynamics* d, const die_batch* b, void* ws, const char* who) {
+// what the claim launch of a batched step and the launches after it take
+struct BatchLaunch {
+    StepArgs k;
+    BatchArgs ba;
+    dim3 grid;                                          // the claim pass's, kept by the lifecycle pass; grid.x partials per replica
+    hipStream_t s;
+};
+
+// the step half's arguments of every replica and the claim pass's grid, checked before any launch
+static int batch_step_args(BatchLaunch& L, const die_medium* m, const die_agents* a, const die_action* act, const die_dynamics* d,
+                           const die_batch* b, void* ws, void* stream, const char* who) {
+    StepArgs& k = L.k;
+    BatchArgs& ba = L.ba;
     // fill_args checks the per-replica workspace of the single-world step; here only the partial arrays are used
     DIE_REQUIRE(m->epoch >= 1 && m->epoch <= DIE_OWNER_EPOCH_MAX && m->owner && a->alive && a->agent_food, "%s: bad medium / agents", who);
     if (d->boundary != DIE_BOUNDARY_WRAP && d->boundary != DIE_BOUNDARY_LIMIT) {
@@ -1179,20 +1189,14 @@ static int batch_step_args(StepArgs& k, BatchArgs& ba, int64_t& nmax, const die_
     k.part_gain = (long long*)ws;
     k.stash = k.has_dead ? (float*)((char*)ws + (int64_t)b->replicas * WS_PARTS) : nullptr;   // batch_stash offsets it per replica
     ba.cells = b->plane_stride; ba.agents = b->agent_stride; ba.seed_stride = b->seed_stride;
-    nmax = 0;
+    int64_t nmax = 0;
     for (int r = 0; r < DIE_MAX_REPLICAS; ++r) {
         ba.n[r] = r < b->replicas ? b->n[r] : 0;
         DIE_REQUIRE(r >= b->replicas || (b->n[r] >= 1 && b->n[r] <= b->agent_stride), "%s: replica %d has %lld agents", who, r, (long long)b->n[r]);
         if (ba.n[r] > nmax) nmax = ba.n[r];
     }
-    return DIE_OK;
-}
-
-// with dead slots: the dead-slot pass + _agent_lifecycle of every replica in one launch, on the claim pass's grid
-static int batch_lifecycle(const StepArgs& k, const BatchArgs& ba, dim3 grid, hipStream_t s, const char* who) {
-    if (!k.has_dead) return DIE_OK;
-    k_lifecycle_batch<<<grid, DIE_STEP_BLOCK, 0, s>>>(k, ba);
-    DIE_CHECK_LAUNCH(who);
+    L.grid = dim3(step_grid(nmax), b->replicas);
+    L.s = (hipStream_t)stream;
     return DIE_OK;
 }
 
@@ -1230,8 +1234,10 @@ static int batch_sweep_rows(const die_medium* m, const RowsArgs& ra, const die_b
     return DIE_OK;
 }
 
-// both tables of a *_rows entry point, after the parent's own checks
-static int batch_rows_check(const die_batch* b, const die_dynamics_row* rows, const die_dynamics_row* rows_host, const char* who) {
+// both tables of a *_rows entry point (with_rows), after the parent's own checks
+static int batch_rows_check(bool with_rows, const die_batch* b, const die_dynamics_row* rows, const die_dynamics_row* rows_host,
+                            const char* who) {
+    if (!with_rows) return DIE_OK;
     DIE_REQUIRE(rows, "%s: null dynamics rows (rows == NULL)", who);
     DIE_REQUIRE(rows_host, "%s: null host copy of the dynamics rows (rows_host == NULL)", who);
     for (int r = 0; r < b->replicas; ++r)
@@ -1296,38 +1302,66 @@ static int batch_sweep(const die_medium* m, const die_dynamics* d, const die_bat
     return DIE_OK;
 }
 
+// ---- the three batched steps (a PhysarumAgent, a PhysarumAgent population, a NeuralAutomataAgent population) ----
+// Each body is its own checks, batch_world_check, more of its own checks, batch_step_args (+ batch_rows_check), its claim launch
+// and batch_step_tail.  The shared checks sit between each entry point's own ones, where they have always been made: when two
+// arguments are wrong, the message that wins does not depend on which step was asked for.
+
+// the workspace, the planes and the sizes of every replica.  The NCA step says two of these in its own words (its agents are in
+// slot order, its food and chem planes are read by the conv launches) and checks the dtype and the positions it reads itself
+static int batch_world_check(const die_medium* m, const die_agents* a, const die_dynamics* d, const die_batch* b, int64_t ws_bytes,
+                             bool nca, const char* who) {
+    const int rc = batch_ws_check(d, b, ws_bytes, who);
+    if (rc != DIE_OK) return rc;
+    if (nca) {
+        DIE_REQUIRE(m->gW <= 0 && !m->sense_mask && !d->staged && !a->slot,
+                    "%s: periodic single-tile replicas in slot order (no sense mask)", who);
+        DIE_REQUIRE(m->food && m->chem && m->chem_next && m->chem_next != m->chem, "%s: null plane, or chem_next not a second plane", who);
+        DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad field dtype %d", who, m->dtype);
+        DIE_REQUIRE(a->x && a->y, "%s: null agent arrays", who);
+    } else {
+        DIE_REQUIRE(m->gW <= 0 && !m->sense_mask && !d->staged, "%s: periodic single-tile replicas (no sense mask)", who);
+        DIE_REQUIRE(m->chem_next && m->chem_next != m->chem, "%s: chem_next must be a second plane", who);
+    }
+    DIE_REQUIRE(b->plane_stride >= (int64_t)m->W * m->H && b->agent_stride >= a->N, "%s: strides smaller than a replica", who);
+    if (!fused_step_applies(m, d)) {
+        die_set_error("%s: only for periodic planes with H %% 4 == 0 and gaussian radius 1..4", who);
+        return DIE_ERR_UNSUPPORTED;
+    }
+    return DIE_OK;
+}
+
+// after the claim launch: its status, then with dead slots the dead-slot pass + _agent_lifecycle of every replica in one launch
+// on the claim pass's grid, then the field sweep
+static int batch_step_tail(const BatchLaunch& L, const die_medium* m, const die_dynamics* d, const die_batch* b, die_step_result* results,
+                           void* ws, const die_dynamics_row* rows, const die_dynamics_row* rows_host, const char* who) {
+    DIE_CHECK_LAUNCH(who);
+    if (L.k.has_dead) {
+        k_lifecycle_batch<<<L.grid, DIE_STEP_BLOCK, 0, L.s>>>(L.k, L.ba);
+        DIE_CHECK_LAUNCH(who);
+    }
+    return batch_sweep(m, d, b, results, ws, (int)L.grid.x, L.s, who, rows, rows_host);
+}
+
 // die_forward_env_step_batch (with_rows false) and die_forward_env_step_batch_rows: one body
 static int forward_env_step_batch(const die_medium* m, const die_agents* a, die_gradient_agent* g, const die_action* act,
                                   const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws, int64_t ws_bytes,
                                   bool with_rows, const die_dynamics_row* rows, const die_dynamics_row* rows_host, void* stream,
                                   const char* who) {
     DIE_REQUIRE(m && a && g && d && b && results && ws, "%s: null argument", who);
-    int rc = batch_ws_check(d, b, ws_bytes, who);
+    int rc = batch_world_check(m, a, d, b, ws_bytes, false, who);
     if (rc != DIE_OK) return rc;
-    DIE_REQUIRE(m->gW <= 0 && !m->sense_mask && !d->staged, "%s: periodic single-tile replicas (no sense mask)", who);
-    DIE_REQUIRE(m->chem_next && m->chem_next != m->chem, "%s: chem_next must be a second plane", who);
-    DIE_REQUIRE(b->plane_stride >= (int64_t)m->W * m->H && b->agent_stride >= a->N, "%s: strides smaller than a replica", who);
-    if (!fused_step_applies(m, d)) {
-        die_set_error("%s: only for periodic planes with H %% 4 == 0 and gaussian radius 1..4", who);
-        return DIE_ERR_UNSUPPORTED;
-    }
     FwdArgs f;
     rc = die_fill_fwd_args(f, m, a, g, act, who);
     if (rc != DIE_OK) return rc;
-    StepArgs k;
-    BatchArgs ba;
-    int64_t nmax;
-    rc = batch_step_args(k, ba, nmax, m, a, act, d, b, ws, who);
+    BatchLaunch L;
+    rc = batch_step_args(L, m, a, act, d, b, ws, stream, who);
     if (rc != DIE_OK) return rc;
-    if (with_rows) {
-        rc = batch_rows_check(b, rows, rows_host, who);
-        if (rc != DIE_OK) return rc;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid(step_grid(nmax), b->replicas);
+    rc = batch_rows_check(with_rows, b, rows, rows_host, who);
+    if (rc != DIE_OK) return rc;
 #define DIE_FMCB(T, KIND, LEAN) do { \
-        if (with_rows) k_forward_move_claim_batch<T, KIND, LEAN, const die_dynamics_row*><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba, rows); \
-        else k_forward_move_claim_batch<T, KIND, LEAN><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba); } while (0)
+        if (with_rows) k_forward_move_claim_batch<T, KIND, LEAN, const die_dynamics_row*><<<L.grid, DIE_STEP_BLOCK, 0, L.s>>>(f, L.k, L.ba, rows); \
+        else k_forward_move_claim_batch<T, KIND, LEAN><<<L.grid, DIE_STEP_BLOCK, 0, L.s>>>(f, L.k, L.ba); } while (0)
     if (m->dtype == DIE_F32) {
         if (g->kind != DIE_AGENT_PHYSARUM) DIE_FMCB(float, DIE_AGENT_GRADIENT, false);
         else if (fwd_is_lean(g)) DIE_FMCB(float, DIE_AGENT_PHYSARUM, true);
@@ -1338,10 +1372,7 @@ static int forward_env_step_batch(const die_medium* m, const die_agents* a, die_
         else DIE_FMCB(__half, DIE_AGENT_PHYSARUM, false);
     }
 #undef DIE_FMCB
-    DIE_CHECK_LAUNCH(who);
-    rc = batch_lifecycle(k, ba, grid, s, who);
-    if (rc != DIE_OK) return rc;
-    return batch_sweep(m, d, b, results, ws, (int)grid.x, s, who, rows, rows_host);
+    return batch_step_tail(L, m, d, b, results, ws, rows, rows_host, who);
 }
 
 extern "C" int die_forward_env_step_batch(const die_medium* m, const die_agents* a, die_gradient_agent* g, const die_action* act,
@@ -1365,34 +1396,22 @@ static int physarum_env_step_batch(const die_medium* m, const die_agents* a, die
                                    const die_dynamics_row* rows_host, void* stream, const char* who) {
     DIE_REQUIRE(m && a && g && d && b && results && ws, "%s: null argument", who);
     DIE_REQUIRE(table, "%s: null parameter table", who);
-    int rc = batch_ws_check(d, b, ws_bytes, who);
+    int rc = batch_world_check(m, a, d, b, ws_bytes, false, who);
     if (rc != DIE_OK) return rc;
-    DIE_REQUIRE(m->gW <= 0 && !m->sense_mask && !d->staged, "%s: periodic single-tile replicas (no sense mask)", who);
-    DIE_REQUIRE(m->chem_next && m->chem_next != m->chem, "%s: chem_next must be a second plane", who);
-    DIE_REQUIRE(b->plane_stride >= (int64_t)m->W * m->H && b->agent_stride >= a->N, "%s: strides smaller than a replica", who);
-    if (!fused_step_applies(m, d)) {
-        die_set_error("%s: only for periodic planes with H %% 4 == 0 and gaussian radius 1..4", who);
-        return DIE_ERR_UNSUPPORTED;
-    }
     DIE_REQUIRE(g->kind == DIE_AGENT_PHYSARUM, "%s: kind %d: a population of PhysarumAgents", who, g->kind);
     DIE_REQUIRE(g->inertia == 0.f && g->noise_scale == 0.f && !g->prev_gx && !g->prev_gy && !g->step_base,
                 "%s: no inertia, noise, prev_g* or step_base (they are state or constants of one agent, not of a population)", who);
     FwdArgs f;
     rc = die_fill_fwd_args(f, m, a, g, act, who);
     if (rc != DIE_OK) return rc;
-    StepArgs k;
-    BatchArgs ba;
-    int64_t nmax;
-    rc = batch_step_args(k, ba, nmax, m, a, act, d, b, ws, who);
+    BatchLaunch L;
+    rc = batch_step_args(L, m, a, act, d, b, ws, stream, who);
     if (rc != DIE_OK) return rc;
-    if (with_rows) {
-        rc = batch_rows_check(b, rows, rows_host, who);
-        if (rc != DIE_OK) return rc;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid(step_grid(nmax), b->replicas);
-#define DIE_PMCB(T, LEAN) do { if (with_rows) k_physarum_move_claim_batch<T, LEAN, const die_dynamics_row*><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba, table, rows); \
-                               else k_physarum_move_claim_batch<T, LEAN><<<grid, DIE_STEP_BLOCK, 0, s>>>(f, k, ba, table); } while (0)
+    rc = batch_rows_check(with_rows, b, rows, rows_host, who);
+    if (rc != DIE_OK) return rc;
+#define DIE_PMCB(T, LEAN) do { \
+        if (with_rows) k_physarum_move_claim_batch<T, LEAN, const die_dynamics_row*><<<L.grid, DIE_STEP_BLOCK, 0, L.s>>>(f, L.k, L.ba, table, rows); \
+        else k_physarum_move_claim_batch<T, LEAN><<<L.grid, DIE_STEP_BLOCK, 0, L.s>>>(f, L.k, L.ba, table); } while (0)
     if (m->dtype == DIE_F32) {
         if (fwd_is_lean(g)) DIE_PMCB(float, true);
         else DIE_PMCB(float, false);
@@ -1401,10 +1420,7 @@ static int physarum_env_step_batch(const die_medium* m, const die_agents* a, die
         else DIE_PMCB(__half, false);
     }
 #undef DIE_PMCB
-    DIE_CHECK_LAUNCH(who);
-    rc = batch_lifecycle(k, ba, grid, s, who);
-    if (rc != DIE_OK) return rc;
-    return batch_sweep(m, d, b, results, ws, (int)grid.x, s, who, rows, rows_host);
+    return batch_step_tail(L, m, d, b, results, ws, rows, rows_host, who);
 }
 
 extern "C" int die_physarum_env_step_batch(const die_medium* m, const die_agents* a, die_gradient_agent* g, const die_physarum_row* table,
@@ -1433,44 +1449,29 @@ static int nca_env_step_batch(const die_medium* m, const die_agents* a, const di
                               const die_nca_dropout* drop, void* stream, const char* who, bool with_rows = false,
                               const die_dynamics_row* rows = nullptr, const die_dynamics_row* rows_host = nullptr) {
     DIE_REQUIRE(m && a && nca && d && b && results && ws, "%s: null argument", who);
-    int rc = batch_ws_check(d, b, ws_bytes, who);
+    int rc = batch_world_check(m, a, d, b, ws_bytes, true, who);
     if (rc != DIE_OK) return rc;
-    DIE_REQUIRE(m->gW <= 0 && !m->sense_mask && !d->staged && !a->slot,
-                "%s: periodic single-tile replicas in slot order (no sense mask)", who);
-    DIE_REQUIRE(m->food && m->chem && m->chem_next && m->chem_next != m->chem, "%s: null plane, or chem_next not a second plane", who);
-    DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad field dtype %d", who, m->dtype);
-    DIE_REQUIRE(a->x && a->y, "%s: null agent arrays", who);
-    DIE_REQUIRE(b->plane_stride >= (int64_t)m->W * m->H && b->agent_stride >= a->N, "%s: strides smaller than a replica", who);
-    if (!fused_step_applies(m, d)) {
-        die_set_error("%s: only for periodic planes with H %% 4 == 0 and gaussian radius 1..4", who);
-        return DIE_ERR_UNSUPPORTED;
-    }
     rc = die_nca_batch_check(nca, m->W, m->H, b->replicas, who);
     if (rc != DIE_OK) return rc;
     DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX && m->epoch == nca->sense_epoch % DIE_OWNER_EPOCH_MAX + 1,
                 "%s: claims at epoch %d cannot follow sensing at epoch %d", who, m->epoch, nca->sense_epoch);
     DIE_REQUIRE(!act || (act->dx && act->dy && act->deposit), "%s: bad action arrays", who);
-    StepArgs k;
-    BatchArgs ba;
-    int64_t nmax;
-    rc = batch_step_args(k, ba, nmax, m, a, act, d, b, ws, who);
+    BatchLaunch L;
+    rc = batch_step_args(L, m, a, act, d, b, ws, stream, who);
     if (rc != DIE_OK) return rc;
     DropWords dw;
     if (drop) {
         rc = die_dropout_words(drop, &dw, who);
         if (rc != DIE_OK) return rc;
     }
-    if (with_rows) {
-        rc = batch_rows_check(b, rows, rows_host, who);
-        if (rc != DIE_OK) return rc;
-    }
-    hipStream_t s = (hipStream_t)stream;
+    rc = batch_rows_check(with_rows, b, rows, rows_host, who);
+    if (rc != DIE_OK) return rc;
     NcaReadArgs q;
     rc = die_nca_sense_batch(m, b, nca, &q.sense, &q.rep, drop ? &dw : nullptr, stream);   // reads the claim plane at sense_epoch …
     if (rc != DIE_OK) return rc;
     if (nca->sense_epoch == DIE_OWNER_EPOCH_MAX) {                    // … which is cleared before the tag 1 claims
         const int64_t words = (int64_t)(b->replicas - 1) * b->plane_stride + (int64_t)m->W * m->H;
-        if (hipMemsetAsync(m->owner, 0, (size_t)words * sizeof(unsigned long long), s) != hipSuccess) {
+        if (hipMemsetAsync(m->owner, 0, (size_t)words * sizeof(unsigned long long), L.s) != hipSuccess) {
             die_set_error("%s: clearing the claim planes failed", who);
             return DIE_ERR_HIP;
         }
@@ -1478,18 +1479,14 @@ static int nca_env_step_batch(const die_medium* m, const die_agents* a, const di
     q.cells = (int64_t)m->W * m->H;
     for (int c = 0; c < 3; ++c) q.coef[c] = nca->coef[c];
     q.act[0] = act ? act->dx : nullptr; q.act[1] = act ? act->dy : nullptr; q.act[2] = act ? act->deposit : nullptr;
-    dim3 grid(step_grid(nmax), b->replicas);
     if (with_rows) {
-        if (m->dtype == DIE_F32) k_nca_move_claim_batch<float, const die_dynamics_row*><<<grid, DIE_STEP_BLOCK, 0, s>>>(q, k, ba, rows);
-        else k_nca_move_claim_batch<__half, const die_dynamics_row*><<<grid, DIE_STEP_BLOCK, 0, s>>>(q, k, ba, rows);
+        if (m->dtype == DIE_F32) k_nca_move_claim_batch<float, const die_dynamics_row*><<<L.grid, DIE_STEP_BLOCK, 0, L.s>>>(q, L.k, L.ba, rows);
+        else k_nca_move_claim_batch<__half, const die_dynamics_row*><<<L.grid, DIE_STEP_BLOCK, 0, L.s>>>(q, L.k, L.ba, rows);
     } else {
-        if (m->dtype == DIE_F32) k_nca_move_claim_batch<float><<<grid, DIE_STEP_BLOCK, 0, s>>>(q, k, ba);
-        else k_nca_move_claim_batch<__half><<<grid, DIE_STEP_BLOCK, 0, s>>>(q, k, ba);
+        if (m->dtype == DIE_F32) k_nca_move_claim_batch<float><<<L.grid, DIE_STEP_BLOCK, 0, L.s>>>(q, L.k, L.ba);
+        else k_nca_move_claim_batch<__half><<<L.grid, DIE_STEP_BLOCK, 0, L.s>>>(q, L.k, L.ba);
     }
-    DIE_CHECK_LAUNCH(who);
-    rc = batch_lifecycle(k, ba, grid, s, who);
-    if (rc != DIE_OK) return rc;
-    return batch_sweep(m, d, b, results, ws, (int)grid.x, s, who, rows, rows_host);
+    return batch_step_tail(L, m, d, b, results, ws, rows, rows_host, who);
 }
 
 extern "C" int die_nca_env_step_batch_rows(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,

@@ -28,6 +28,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
+from .batch import BatchedNeuralAutomataAgent, _is_integer, _worlds_per_candidate, episode_seeds
 from .device_array import _ptr, stream_ptr
 
 OPTIMIZERS = {'clipup': _lib.DIE_PGPE_CLIPUP, 'adam': _lib.DIE_PGPE_ADAM}
@@ -59,7 +60,7 @@ class _PopulationSearch:
     """What PGPE and CMAES share: an (R, P) float32 parameter matrix, a population binding whose generation is ask, reset,
     `epoch_iters` batched steps and tell, a (G, 6) history on the device, the pop_best / best rows as agents.  A subclass sets
     R, P, device, center, iter, _asked, _pop, _history, _s (its ctypes state, with history / history_rows), _pop_best, _best,
-    _evals, and defines ask / tell."""
+    _evals and _update (the name of its update entry point; `<_update>_episodes` folds), and defines ask / tell."""
 
     def _check_params(self, params: torch.Tensor):
         if tuple(params.shape) != (self.R, self.P) or params.dtype != torch.float32 or params.device != self.device \
@@ -74,8 +75,7 @@ class _PopulationSearch:
                              (f' ({self.R} candidates x {episodes} episodes, candidate-major)' if episodes != 1 else ''))
 
     def _check_episodes(self, episodes) -> int:
-        if isinstance(episodes, bool) or not isinstance(episodes, int) or episodes < 1:
-            raise ValueError(f'episodes={episodes!r}: an integer >= 1 (worlds per candidate)')
+        _worlds_per_candidate(episodes)
         if self.R * episodes > _lib.MAX_REPLICAS:
             raise ValueError(f'episodes={episodes}: {self.R} candidates x {episodes} episodes is more than {_lib.MAX_REPLICAS} replicas')
         return episodes
@@ -100,6 +100,22 @@ class _PopulationSearch:
             h[:self._history.shape[0]].copy_(self._history)
             self._history = h
             self._s.history, self._s.history_rows = _ptr(h), h.shape[0]
+
+    def _tell(self, params: torch.Tensor, terms: torch.Tensor, episodes) -> None:
+        """`tell` once the subclass has chosen the rows: the checks, the update (with E > 1 episodes the folding one), iter + 1."""
+        self._check_params(params)
+        if type(episodes) is not int or episodes != 1:
+            episodes = self._check_episodes(episodes)
+        self._check_terms(terms, episodes)
+        self._reserve_history()
+        if episodes == 1:
+            name, fold = self._update, ()
+            self._episode_fitness = self._folded = None
+        else:
+            name, fold = self._update + '_episodes', (episodes, *self._fold_buffers(episodes))
+        _lib.check(getattr(_lib.lib, name)(C.byref(self._s), _ptr(params), _ptr(terms), terms.shape[0], terms.stride(0), terms.stride(1),
+                                           *fold, self.iter, stream_ptr(self.device)), name)
+        self.iter += 1
 
     # ------------------------------------------------------------------ a population of NeuralAutomataAgents
     def for_population(self, pop, epoch_iters: int, env=None, *, reseed: Optional[int] = None, reseed_stride: int = 0):
@@ -138,9 +154,9 @@ class _PopulationSearch:
         if int(epoch_iters) < 1:
             raise ValueError('epoch_iters: at least 1')
         if reseed is not None:
-            if isinstance(reseed, bool) or not isinstance(reseed, int):
+            if not _is_integer(reseed, exact=True):
                 raise ValueError(f'reseed={reseed!r}: an integer seed, or None for the construction worlds')
-            if isinstance(reseed_stride, bool) or not isinstance(reseed_stride, int) or reseed_stride < 0:
+            if not _is_integer(reseed_stride, 0, exact=True):
                 raise ValueError(f'reseed_stride={reseed_stride!r}: a non-negative integer')
             if pop.env._fixed is None:
                 raise ValueError("reseed needs a BatchedEnv with max_agents=N (or None for W·H): the 'alive' layout holds K_r slots "
@@ -165,23 +181,11 @@ class _PopulationSearch:
         pop, env = self._pop, self._pop.env
         g = self.iter
         self.ask(pop.parameters)
-        if self._episodes != 1:
-            return self._step_episodes(pop, env, g)
         if self._reseed is None:
             env.reset()
-        else:
+        elif self._episodes == 1:
             env.reset(seed=self._reseed + g * self.R, seed_stride=self._reseed_stride)
-        if self._pop_reset is not None:
-            self._pop_reset()
-        for t in range(self._epoch_iters):
-            env.step(pop, self._results[t])
-        self.tell(self._results)
-
-    def _step_episodes(self, pop, env, g: int) -> None:
-        """`step` for a population with E > 1 episodes: the worlds from the seed list, the fold in tell."""
-        if self._reseed is None:
-            env.reset()
-        else:
+        else:                                           # E > 1: the worlds from the seed list (and the fold in tell)
             env.reset(seeds=self._generation_seeds(g))
         if self._pop_reset is not None:
             self._pop_reset()
@@ -191,7 +195,6 @@ class _PopulationSearch:
 
     def _generation_seeds(self, g: int):
         """The worlds of generation g under `reseed`: replica c·E + e gets reseed + g·C·E + e + reseed_stride·c·E."""
-        from .batch import episode_seeds
         return episode_seeds(self._reseed + g * self.R * self._episodes, self.R, self._episodes, self._reseed_stride)
 
     def run(self, generations: int) -> None:
@@ -204,7 +207,6 @@ class _PopulationSearch:
         return self._history[:self.iter].cpu()
 
     def _agent(self, row: torch.Tensor, template=None):
-        from .batch import BatchedNeuralAutomataAgent
         if template is None and hasattr(self._pop, 'agent_from_row'):       # a BatchedPhysarumPopulation: a PhysarumAgent
             return self._pop.agent_from_row(row)
         template = template if template is not None else (self._pop.template if self._pop is not None else None)
@@ -226,6 +228,7 @@ class _PopulationSearch:
 class PGPE(_PopulationSearch):
     """Policy-gradients with parameter-based exploration (Sehnke et al. 2010) with symmetric sampling and centred ranks, the
     arguments of evotorch's PGPE.  `popsize` is R (even, 2..64); the searcher maximises."""
+    _update = 'die_pgpe_update'
 
     def __init__(self, popsize: int, num_params: Optional[int] = None, *, center_init=None,
                  initial_bounds: Tuple[float, float] = (-0.5, 0.5), radius_init: Optional[float] = None,
@@ -305,22 +308,7 @@ class PGPE(_PopulationSearch):
         params = self._asked if params is None else params
         if params is None:
             raise RuntimeError('tell() before ask()')
-        self._check_params(params)
-        if type(episodes) is not int or episodes != 1:
-            episodes = self._check_episodes(episodes)
-        self._check_terms(terms, episodes)
-        self._reserve_history()
-        if episodes == 1:
-            if self._episode_fitness is not None:
-                self._episode_fitness = self._folded = None
-            _lib.check(_lib.lib.die_pgpe_update(C.byref(self._s), _ptr(params), _ptr(terms), terms.shape[0], terms.stride(0),
-                                                terms.stride(1), self.iter, stream_ptr(self.device)), 'die_pgpe_update')
-        else:
-            ef, folded = self._fold_buffers(episodes)
-            _lib.check(_lib.lib.die_pgpe_update_episodes(C.byref(self._s), _ptr(params), _ptr(terms), terms.shape[0], terms.stride(0),
-                                                         terms.stride(1), episodes, ef, folded, self.iter, stream_ptr(self.device)),
-                       'die_pgpe_update_episodes')
-        self.iter += 1
+        self._tell(params, terms, episodes)
 
     # ------------------------------------------------------------------ results (read on demand)
     @property
@@ -376,6 +364,7 @@ class CMAES(_PopulationSearch):
     4 + floor(3 ln P)); the searcher maximises.  The covariance is diagonal: separable=False (a P x P eigendecomposition per
     generation) is not here.  The state (m, C, p_sigma, p_c, sigma) is float64 on the device; `sigma`, `C`, `stdev`,
     `p_sigma` and `p_c` read it back on demand."""
+    _update = 'die_cmaes_update'
 
     def __init__(self, popsize: Optional[int] = None, num_params: Optional[int] = None, *, stdev_init: float, center_init=None,
                  initial_bounds: Tuple[float, float] = (-0.5, 0.5), c_m: float = 1.0, c_sigma_ratio: float = 1.0,
@@ -449,22 +438,7 @@ class CMAES(_PopulationSearch):
         its E sums, added in episode order (float64) — one more launch; the sums stay in `episode_fitness`."""
         if self._asked is None or self._asked_iter != self.iter:
             raise RuntimeError(f'tell() before ask() of generation {self.iter}')
-        self._check_params(self._asked)
-        if type(episodes) is not int or episodes != 1:
-            episodes = self._check_episodes(episodes)
-        self._check_terms(terms, episodes)
-        self._reserve_history()
-        if episodes == 1:
-            if self._episode_fitness is not None:
-                self._episode_fitness = self._folded = None
-            _lib.check(_lib.lib.die_cmaes_update(C.byref(self._s), _ptr(self._asked), _ptr(terms), terms.shape[0], terms.stride(0),
-                                                 terms.stride(1), self.iter, stream_ptr(self.device)), 'die_cmaes_update')
-        else:
-            ef, folded = self._fold_buffers(episodes)
-            _lib.check(_lib.lib.die_cmaes_update_episodes(C.byref(self._s), _ptr(self._asked), _ptr(terms), terms.shape[0],
-                                                          terms.stride(0), terms.stride(1), episodes, ef, folded, self.iter,
-                                                          stream_ptr(self.device)), 'die_cmaes_update_episodes')
-        self.iter += 1
+        self._tell(self._asked, terms, episodes)
 
     # ------------------------------------------------------------------ results (read on demand)
     @property
