@@ -294,11 +294,16 @@ class BatchedEnv:
                                  '(a seed of an earlier reset since the last check() may be the one)')
 
     def step(self, agent: Union['BatchedPhysarumAgent', 'BatchedPhysarumPopulation', 'BatchedNeuralAutomataAgent'],
-             results: Optional[torch.Tensor] = None) -> torch.Tensor:
+             results: Optional[torch.Tensor] = None, action: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One step of every replica: `agent.forward` + `Env.step` fused, two launches for the whole batch (L + 2 for a
         BatchedNeuralAutomataAgent of L layers; one more with dead slots, one more with a flow; for a BatchedPhysarumPopulation a
         decode launch first when `parameters` was written since the last one).  Returns the (R, 2) float64 tensor of
         die_step_result words (device; `read_results` decodes).
+
+        `action`: an optional contiguous (3, R, Nmax) float32 device tensor the step writes the agents' actions into (rows dx, dy,
+        deposit — the `act` argument of the library's batched steps): afterwards `action[:, r, :n[r]]` is what replica r's agent
+        did, bit for bit the stand-alone agent's `forward(obs).data` — a teacher's target for `differentiable_action`.  The slots
+        from n[r] on are left as they were.  The step itself does not change with it.  Small worlds only.
 
         One path for the three agent kinds.  What is particular to a kind it says itself: `_check_step(env)` (its refusals),
         `_replica_agent(r)` (replica r's stand-alone agent, large worlds), `_claim_epoch(env)` (the epoch its claims are made
@@ -306,6 +311,15 @@ class BatchedEnv:
         refused leaves the batch as it was."""
         agent._check_step(self)                     # every refusal before anything is launched
         flow = self._flow_kind()
+        act = None
+        if action is not None:
+            if self.per_replica:
+                raise NotImplementedError('step(action=...): large worlds (per_replica) step a stand-alone Env per replica; read '
+                                          'each agent\'s own action there')
+            if (not isinstance(action, torch.Tensor) or tuple(action.shape) != (3, self.R, self.Nmax) or action.dtype != torch.float32
+                    or action.device != self.device or not action.is_contiguous() or action.requires_grad):
+                raise ValueError(f'action: a contiguous (3, {self.R}, {self.Nmax}) float32 tensor on {self.device} (no grad)')
+            act = _lib.Action(self.Nmax, action[0].data_ptr(), action[1].data_ptr(), action[2].data_ptr())
         if results is None:
             results = torch.empty((self.R, 2), dtype=torch.float64, device=self.device)
         if self.per_replica:
@@ -317,7 +331,7 @@ class BatchedEnv:
         m, a, dyn, b = self._structs()
         rows = () if self._rows is None else (_ptr(self._rows), self._rows_host)    # per-replica Dynamics: each replica under its row
         try:
-            agent._launch((C.byref(m), C.byref(a)), (None, C.byref(dyn), C.byref(b), _ptr(results), _ptr(self._ws), self._ws.numel()),
+            agent._launch((C.byref(m), C.byref(a)), (None if act is None else C.byref(act), C.byref(dyn), C.byref(b), _ptr(results), _ptr(self._ws), self._ws.numel()),
                           rows, stream_ptr(self.device))
         except Exception:
             self.epoch = epoch                      # refused before any launch: nothing changed
@@ -555,8 +569,10 @@ class _Population:
             raise ValueError(f'{what} of shape {tuple(t.shape)}: ({self.candidates}, {self.P}) expected ({rows_are} x {columns})')
         return t
 
-    def _check_parameters(self) -> None:
-        p = self.parameters
+    def _check_parameters(self, p: Optional[torch.Tensor] = None) -> None:
+        p = self.parameters if p is None else p
+        if not isinstance(p, torch.Tensor):
+            raise ValueError(f'parameters: a ({self.candidates}, {self.P}) float32 tensor on {self.env.device}')
         if tuple(p.shape) != (self.candidates, self.P) or p.dtype != torch.float32 or p.device != self.env.device or not p.is_contiguous():
             raise ValueError(f'parameters must stay a contiguous ({self.candidates}, {self.P}) float32 tensor on {self.env.device}')
 
@@ -597,7 +613,7 @@ class BatchedPhysarumAgent(_PhysarumReplicas):
                                   self.seed & 0xFFFFFFFFFFFFFFFF, self._calls & 0xFFFFFFFF, 0, None)
 
     def _launch(self, front: tuple, back: tuple, rows: tuple, stream) -> None:
-        """The library's step: (m, a), this agent's struct, (no action, d, b, results, workspace), the Dynamics rows, the stream."""
+        """The library's step: (m, a), this agent's struct, (the action or None, d, b, results, workspace), the Dynamics rows, the stream."""
         name = 'die_forward_env_step_batch_rows' if rows else 'die_forward_env_step_batch'
         _lib.check(getattr(_lib.lib, name)(*front, C.byref(self._struct()), *back, *rows, stream), name)
 
@@ -930,7 +946,8 @@ class BatchedNeuralAutomataAgent(_Population):
 
     def set_parameters(self, parameters) -> None:
         """Copy an (R, P) matrix of candidate rows in ((C, P) with episodes: one row per candidate)."""
-        self.parameters.copy_(self._matrix(parameters, 'parameters', 'P weights'))
+        with torch.no_grad():                       # (`parameters` may be a leaf that requires grad: an optimiser's)
+            self.parameters.copy_(self._matrix(parameters, 'parameters', 'P weights'))
 
     def candidate(self, r: int) -> NeuralAutomataAgent:
         """Candidate r as a stand-alone NeuralAutomataAgent (on the host: `save()` the winner).  With a `dropout_seed` it carries
@@ -1005,6 +1022,58 @@ class BatchedNeuralAutomataAgent(_Population):
         nca.sense_epoch = sense_epoch
         return nca
 
+    # ------------------------------------------------------------------ the differentiable twins (die_nca_grad.hip, batched)
+    def _check_differentiable(self, parameters: Optional[torch.Tensor]) -> torch.Tensor:
+        """Every refusal of a differentiable call, before anything is launched; returns the matrix the call reads."""
+        env = self.env
+        if env.per_replica:
+            raise NotImplementedError('differentiable mode: large worlds (per_replica) are not batched — a large world fills the GPU '
+                                      'through the stand-alone NeuralAutomataAgent.differentiable_action (replica_agent(r))')
+        if self._arch['boundary'][0] not in ('circular', 'zeros'):
+            raise NotImplementedError(f"boundary={self._arch['boundary'][0]!r} in differentiable mode: 'circular' or 'zeros' (step() "
+                                      f"takes all of {sorted(_lib.PAD_MODES)})")
+        self._check_step(env)
+        p = self.parameters if parameters is None else parameters
+        self._check_parameters(p)
+        return p
+
+    def _grad_struct(self, parameters: torch.Tensor, sense_epoch: int):
+        """(layer array, die_nca_batch) reading `parameters`, without the step's scratch."""
+        base = parameters.data_ptr()
+        layers = (_lib.NcaLayer * len(self._layers))(*[_lib.NcaLayer(k, cin, cout, 0, base + 4 * off, self.P) for k, cin, cout, off in self._layers])
+        nca = _lib.NcaBatch(len(self._layers), _lib.PAD_MODES[self._arch['boundary'][0]], int(self._arch['with_agent_channel']), sense_epoch,
+                            layers, (C.c_float * 3)(*self.template.action_coefs), 0 if self.episodes == 1 else self.episodes, None, 0)
+        return layers, nca
+
+    def differentiable_sense(self, parameters: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The sense planes of every replica with a `grad_fn`: (R, 3, W, H) float32, `out[r]` bit for bit replica r's stand-alone
+        `differentiable_sense` (what the coming `env.step` would read).  `parameters`: the (C, P) float32 device matrix to read and
+        to differentiate with respect to — default `self.parameters`, which may have been marked `requires_grad_()`; its gradient
+        is a (C, P) tensor, row c the float64 sum over candidate c's E worlds of the stand-alone gradients, rounded once (E = 1:
+        the stand-alone gradient of replica c, bit for bit; no float atomics, the same bits on every run).
+
+        L conv launches forward for all R replicas (L + 1 with a dropout mask: masked for the value, unmasked for the graph) and
+        2 L backward.  Every layer's output lives in storage the graph owns and the first layer's inputs (claim, food and chem
+        planes of all replicas) are copied, so `backward` may run after `env.step`.  With a `dropout_seed`, in training mode and
+        p > 0, replica r is masked with key `dropout_seed + r·dropout_seed_stride` at `dropout_step`; the counter advances once per
+        call whenever a `dropout_seed` is set.  Small worlds, 'circular' / 'zeros' boundaries; anything else raises
+        NotImplementedError before any launch.  `step()` is untouched by all this."""
+        p = self._check_differentiable(parameters)
+        out = _BatchedSense.apply(self, p)
+        if self.dropout_seed is not None:
+            self.dropout_step += 1
+        return out
+
+    def differentiable_action(self, parameters: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The actions of every replica with a `grad_fn`: (3, R, Nmax) float32 in the batch's action layout (what
+        `env.step(..., action=...)` fills) — `out[:, r, :env.n[r]]` is replica r's stand-alone `differentiable_action`, bit for
+        bit; the padding slots from n[r] on are 0 and receive no gradient.  One more launch than `differentiable_sense` each way
+        (the read-out and its adjoint, die_gather_scale_batch / _backward_batch); the slots' coordinates are copied.  Where several
+        slots of a replica with a non-zero gradient stand on one cell their terms are added by fp32 atomics in arrival order;
+        otherwise (alive agents never share a cell) the gradient's bits are fixed."""
+        sense = self.differentiable_sense(parameters)
+        return _BatchedReadOut.apply(sense, self)
+
     def render(self, r: int) -> np.ndarray:
         """Replica r's last sense planes with the channel axis last: the stand-alone agent's `render()[0]`."""
         if self.env.per_replica:
@@ -1015,3 +1084,93 @@ class BatchedNeuralAutomataAgent(_Population):
         L, W, H = len(self._layers), self.env.W, self.env.H
         sets = self._scratch.view(-1, self.R, 4, W, H)
         return torch.moveaxis(sets[(L - 1) % sets.shape[0], r, :3], 0, -1).cpu().numpy()
+
+
+def _geometry(env: BatchedEnv) -> _lib.Medium:
+    """A die_medium that only says how large a replica is (the read-out's cell arithmetic)."""
+    return _lib.Medium(env.W, env.H, _lib.DIE_F32, 1, None, None, None, None, 0, 0, 0, 0, 0, 0, 0, 0, None)
+
+
+class _BatchedSense(torch.autograd.Function):
+    """BatchedNeuralAutomataAgent.differentiable_sense: die_nca_sense_batch_store forward, die_nca_backward_batch backward."""
+
+    @staticmethod
+    def forward(ctx, pop, parameters):
+        env = pop.env
+        R, W, H, L, dev = env.R, env.W, env.H, len(pop._layers), env.device
+        with_agents = pop._arch['with_agent_channel']
+        # as they are now: the worlds will be stepped (the claim plane only where the first layer reads it)
+        planes = [env.food.clone(), env.chem.clone()] + ([env.owner.clone()] if with_agents else [])
+        store = torch.empty((L, R, 4, W, H), dtype=torch.float32, device=dev)
+        drop = pop._dropout()
+        masked = None if drop is None else torch.empty((R, 4, W, H), dtype=torch.float32, device=dev)
+        ctx.epoch, ctx.fdt = env.epoch, _lib.DIE_F32 if env.dtype == torch.float32 else _lib.DIE_F16
+        ctx.batch, ctx.pop, ctx.size = env._batch_struct(), pop, (R, W, H, L)
+        ctx.drop = None if drop is None else (drop.p, drop.seed, drop.seed_stride, drop.step)
+        m = _BatchedSense._medium(ctx, planes)
+        layers, nca = pop._grad_struct(parameters, ctx.epoch)
+        _lib.check(_lib.lib.die_nca_sense_batch_store(C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), store.numel() * 4,
+                                                      None if masked is None else _ptr(masked),
+                                                      None if drop is None else C.byref(drop), stream_ptr(dev)),
+                   'die_nca_sense_batch_store')
+        # everything the backward reads goes through save_for_backward: freed with the graph after a backward without retain_graph
+        ctx.save_for_backward(parameters, store, *planes)
+        return (store[L - 1] if masked is None else masked)[:, :3]
+
+    @staticmethod
+    def _medium(ctx, planes) -> _lib.Medium:
+        R, W, H, _ = ctx.size
+        owner = _ptr(planes[2]) if len(planes) == 3 else None
+        return _lib.Medium(W, H, ctx.fdt, ctx.epoch, owner, _ptr(planes[0]), _ptr(planes[1]), None, 0, 0, 0, 0, 0, 0, 0, 0, None)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        parameters, store, *planes = ctx.saved_tensors
+        R, W, H, L = ctx.size
+        pop, dev = ctx.pop, store.device
+        g = grad.to(dtype=torch.float32).contiguous()               # (R, 3, W, H): three planes per replica
+        need = int(_lib.lib.die_nca_backward_batch_workspace_bytes(W, H, R, L))
+        ws = torch.empty((need // 4,), dtype=torch.float32, device=dev)
+        out = torch.empty_like(parameters)                          # (C, P): every element is written (the layers tile a row)
+        drop = None if ctx.drop is None else _lib.NcaDropout(*ctx.drop, 0)
+        m = _BatchedSense._medium(ctx, planes)
+        layers, nca = pop._grad_struct(parameters, ctx.epoch)
+        _lib.check(_lib.lib.die_nca_backward_batch(C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), _ptr(g), 3 * W * H, _ptr(out),
+                                                   pop.P, None if drop is None else C.byref(drop), _ptr(ws), need, stream_ptr(dev)),
+                   'die_nca_backward_batch')
+        return None, out
+
+
+class _BatchedReadOut(torch.autograd.Function):
+    """BatchedNeuralAutomataAgent.differentiable_action's last step: die_gather_scale_batch, die_gather_scale_backward_batch."""
+
+    @staticmethod
+    def forward(ctx, sense, pop):
+        env = pop.env
+        R, W, H, dev = env.R, env.W, env.H, env.device
+        if sense.stride()[1:] != (W * H, H, 1) or sense.stride(0) < 3 * W * H:
+            sense = sense.contiguous()
+        out = torch.empty((3, R, env.Nmax), dtype=torch.float32, device=dev)
+        x, y = env.x.clone(), env.y.clone()                          # where the slots stand now: the worlds will be stepped
+        ctx.m, ctx.batch, ctx.coefs, ctx.size = _geometry(env), env._batch_struct(), tuple(pop.template.action_coefs), (R, W, H, env.Nmax)
+        a = _lib.Agents(env.Nmax, _ptr(x), _ptr(y), None, None, None)
+        u = _lib.Action(env.Nmax, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
+        _lib.check(_lib.lib.die_gather_scale_batch(C.byref(ctx.m), C.byref(a), C.byref(ctx.batch), sense.data_ptr(), sense.stride(0),
+                                                   (C.c_float * 3)(*ctx.coefs), C.byref(u), stream_ptr(dev)), 'die_gather_scale_batch')
+        ctx.save_for_backward(x, y)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        x, y = ctx.saved_tensors
+        R, W, H, Nmax = ctx.size
+        g = grad.to(dtype=torch.float32).contiguous()
+        planes = torch.empty((R, 3, W, H), dtype=torch.float32, device=x.device)     # (cleared by the call)
+        a = _lib.Agents(Nmax, _ptr(x), _ptr(y), None, None, None)
+        u = _lib.Action(Nmax, g[0].data_ptr(), g[1].data_ptr(), g[2].data_ptr())
+        _lib.check(_lib.lib.die_gather_scale_backward_batch(C.byref(ctx.m), C.byref(a), C.byref(ctx.batch), C.byref(u),
+                                                            (C.c_float * 3)(*ctx.coefs), _ptr(planes), 3 * W * H, stream_ptr(x.device)),
+                   'die_gather_scale_backward_batch')
+        return planes, None

@@ -29,3 +29,8 @@ __device__ __forceinline__ float nca_load(const void* p, int kind, int64_t i, in
 
 // die_nca_dropout, checked, as the words the kernels read (die_nca.hip)
 int die_dropout_words(const die_nca_dropout* drop, DropWords* out, const char* who);
+
+// a die_nca_batch without the step's scratch (the calls that keep every layer in caller-owned storage), and the die_batch
+// of the batched read-out, sensing and adjoint: checked before anything is launched (die_nca.hip)
+int die_nca_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who);
+int die_nca_batch_shape_check(const die_medium* m, const die_batch* b, const char* who);

@@ -270,6 +270,34 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_gather_scale(GatherArgs a) {
     }
 }
 
+// die_gather_scale_batch: replica blockIdx.y — its planes `rep_plane` elements on, its slots `agents` on; slots n[r] … agents − 1
+// (the padding of a replica with fewer agents than the widest) read as 0; the loop body is k_gather_scale's, kept apart so that
+// the stand-alone kernel's code stays what it was
+struct GatherBatchArgs : GatherArgs {
+    int64_t rep_plane, agents;
+    int64_t n[DIE_MAX_REPLICAS];
+};
+
+__global__ __launch_bounds__(DIE_BLOCK) void k_gather_scale_batch(GatherBatchArgs b) {
+    const int r = blockIdx.y;
+    const int64_t pa = b.agents * r, nr = b.n[r];
+    GatherArgs a = b;
+    a.x += pa; a.y += pa;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { a.plane[q] += b.rep_plane * r; a.out[q] += pa; }
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < b.agents; n += stride) {
+        if (n < nr) {
+            const int64_t c = die_local(a.g, die_cell((int64_t)a.x[n], a.g.gW), die_cell((int64_t)a.y[n], a.g.gH));
+#pragma unroll
+            for (int q = 0; q < 3; ++q) a.out[q][n] = a.plane[q][c] * a.coef[q];
+        } else {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) a.out[q][n] = 0.f;
+        }
+    }
+}
+
 extern "C" int die_gather_scale(const die_medium* m, const die_agents* ag, const float* const* planes, const float* coefs,
                                 const die_action* out, void* stream) {
     DIE_REQUIRE(m && ag && planes && coefs && out, "die_gather_scale: null argument");
@@ -284,6 +312,38 @@ extern "C" int die_gather_scale(const die_medium* m, const die_agents* ag, const
     return DIE_OK;
 }
 
+// what the batched read-out and its adjoint require of a die_batch (die_nca_grad.hip uses it too)
+int die_nca_batch_shape_check(const die_medium* m, const die_batch* b, const char* who) {
+    DIE_REQUIRE(m->W >= 1 && m->H >= 1, "%s: bad size %dx%d", who, m->W, m->H);
+    DIE_REQUIRE(b->replicas >= 1 && b->replicas <= DIE_MAX_REPLICAS, "%s: 1..%d replicas (got %d)", who, DIE_MAX_REPLICAS, b->replicas);
+    DIE_REQUIRE(b->plane_stride >= (int64_t)m->W * m->H, "%s: plane_stride %lld smaller than a plane", who, (long long)b->plane_stride);
+    DIE_REQUIRE(b->agent_stride >= 1, "%s: agent_stride %lld", who, (long long)b->agent_stride);
+    for (int r = 0; r < b->replicas; ++r)
+        DIE_REQUIRE(b->n[r] >= 0 && b->n[r] <= b->agent_stride, "%s: replica %d has %lld agents", who, r, (long long)b->n[r]);
+    return DIE_OK;
+}
+
+extern "C" int die_gather_scale_batch(const die_medium* m, const die_agents* ag, const die_batch* b, const float* sense, int64_t sense_stride,
+                                      const float* coefs, const die_action* out, void* stream) {
+    const char* who = "die_gather_scale_batch";
+    DIE_REQUIRE(m && ag && b && sense && coefs && out, "%s: null argument", who);
+    int rc = die_nca_batch_shape_check(m, b, who);
+    if (rc != DIE_OK) return rc;
+    const int64_t cells = (int64_t)m->W * m->H;
+    DIE_REQUIRE(sense_stride >= 3 * cells, "%s: sense_stride %lld below three planes", who, (long long)sense_stride);
+    DIE_REQUIRE(ag->x && ag->y && out->dx && out->dy && out->deposit, "%s: bad arrays", who);
+    GatherBatchArgs a;
+    a.g = die_geo_of(m); a.N = b->agent_stride; a.x = ag->x; a.y = ag->y;
+    for (int q = 0; q < 3; ++q) { a.plane[q] = sense + q * cells; a.coef[q] = coefs[q]; }
+    a.out[0] = out->dx; a.out[1] = out->dy; a.out[2] = out->deposit;
+    a.rep_plane = sense_stride; a.agents = b->agent_stride;
+    for (int r = 0; r < DIE_MAX_REPLICAS; ++r) a.n[r] = r < b->replicas ? b->n[r] : 0;
+    const int64_t g = (b->agent_stride + DIE_BLOCK - 1) / DIE_BLOCK;
+    k_gather_scale_batch<<<dim3((unsigned)(g < 8192 ? g : 8192), (unsigned)b->replicas), DIE_BLOCK, 0, (hipStream_t)stream>>>(a);
+    DIE_CHECK_LAUNCH(who);
+    return DIE_OK;
+}
+
 // ---- die_nca_env_step_batch's sensing (the step itself: die_env.hip) --------------------------------------------------
 // Scratch: [set][replica][NCA_MAXC][W][H] fp32, set = layer % 2 (one set for a single layer); the last layer's planes stay
 // there until the next step (BatchedNeuralAutomataAgent.render).
@@ -295,15 +355,18 @@ extern "C" int64_t die_nca_batch_scratch_bytes(int32_t W, int32_t H, int32_t rep
 }
 
 // every argument of the stack, before anything is launched
-int die_nca_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who) {
-    DIE_REQUIRE(nca && nca->layers && nca->scratch, "%s: null stack, layer list or scratch", who);
+// (scratch: the ping-pong planes of the step; the calls that write into caller-owned storage check their own)
+static int nca_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool scratch) {
+    if (scratch) DIE_REQUIRE(nca && nca->layers && nca->scratch, "%s: null stack, layer list or scratch", who);
+    else DIE_REQUIRE(nca && nca->layers, "%s: null stack or layer list", who);
     DIE_REQUIRE(nca->n_layers >= 1 && nca->n_layers <= DIE_NCA_MAX_LAYERS, "%s: 1..%d layers (got %d)", who, DIE_NCA_MAX_LAYERS, nca->n_layers);
     DIE_REQUIRE(nca->padding_mode >= DIE_PAD_CIRCULAR && nca->padding_mode <= DIE_PAD_REPLICATE, "%s: bad padding mode %d", who, nca->padding_mode);
     DIE_REQUIRE(nca->with_agent_channel == 0 || nca->with_agent_channel == 1, "%s: with_agent_channel is 0 or 1", who);
     DIE_REQUIRE(nca->episodes >= 0 && replicas % (nca->episodes > 1 ? nca->episodes : 1) == 0, "%s: episodes %d: at least 1 (0 reads as 1) "
                 "and a divisor of the %d replicas", who, nca->episodes, replicas);
     const int64_t need = die_nca_batch_scratch_bytes(W, H, replicas, nca->n_layers);
-    DIE_REQUIRE(need > 0 && nca->scratch_bytes >= need, "%s: scratch too small (%lld < %lld)", who, (long long)nca->scratch_bytes, (long long)need);
+    DIE_REQUIRE(need > 0, "%s: bad size %dx%d or replicas %d outside 1..%d", who, W, H, replicas, DIE_MAX_REPLICAS);
+    if (scratch) DIE_REQUIRE(nca->scratch_bytes >= need, "%s: scratch too small (%lld < %lld)", who, (long long)nca->scratch_bytes, (long long)need);
     int cin = 2 + nca->with_agent_channel;
     for (int l = 0; l < nca->n_layers; ++l) {
         const die_nca_layer& L = nca->layers[l];
@@ -323,10 +386,18 @@ int die_nca_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t 
     return DIE_OK;
 }
 
-// the stack for every replica, one launch per layer; *sense = the last layer's planes of replica 0, replica r's *rep further
-// (`drop`: the checked words of die_nca_env_step_batch_dropout, or null — the last layer's launch is then the DROP one)
-int die_nca_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
-                        const DropWords* drop, void* stream) {
+int die_nca_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who) {
+    return nca_stack_check(nca, W, H, replicas, who, true);
+}
+int die_nca_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who) {
+    return nca_stack_check(nca, W, H, replicas, who, false);
+}
+
+// the stack for every replica, one launch per layer.  Layer l writes `dst` + set(l) · R · rep planes: set(l) = l % 2 for the
+// step's ping-pong scratch, l for caller-owned storage that keeps every layer.  `drop` (checked words, or null): the last layer's
+// launch is the DROP one — into `masked` when given (the unmasked launch then runs as well and keeps its place), else in place of it.
+static int sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* dst, bool pingpong, float* masked,
+                       const float** sense, int64_t* rep, const DropWords* drop, void* stream) {
     const int64_t cells = (int64_t)m->W * m->H, rep_scratch = NCA_MAXC * cells;
     const int fkind = m->dtype == DIE_F32 ? DIE_PLANE_F32 : DIE_PLANE_F16;
     ConvArgs a = {};
@@ -340,16 +411,58 @@ int die_nca_sense_batch(const die_medium* m, const die_batch* b, const die_nca_b
     float* out = nullptr;
     for (int l = 0; l < nca->n_layers; ++l) {
         const die_nca_layer& L = nca->layers[l];
-        out = nca->scratch + (l % nca_scratch_sets(nca->n_layers)) * b->replicas * rep_scratch;
+        out = dst + (pingpong ? l % nca_scratch_sets(nca->n_layers) : l) * b->replicas * rep_scratch;
         for (int o = 0; o < NCA_MAXC; ++o) a.out[o] = o < L.cout ? out + o * cells : nullptr;
         a.w = L.weights; a.rep_w = L.weight_stride; a.rep_out = rep_scratch;
         a.cin = L.cin; a.cout = L.cout; a.k = L.k; a.apply_tanh = l == nca->n_layers - 1;
-        launch_conv<true>(a, b->replicas, (hipStream_t)stream, a.apply_tanh ? drop : nullptr);
+        launch_conv<true>(a, b->replicas, (hipStream_t)stream, a.apply_tanh && !masked ? drop : nullptr);
         DIE_CHECK_LAUNCH("die_nca_env_step_batch(conv)");
+        if (a.apply_tanh && masked && drop) {
+            for (int o = 0; o < L.cout; ++o) a.out[o] = masked + o * cells;
+            launch_conv<true>(a, b->replicas, (hipStream_t)stream, drop);
+            DIE_CHECK_LAUNCH("die_nca_sense_batch_store(masked)");
+            out = masked;
+        }
         for (int o = 0; o < NCA_MAXC; ++o) { a.in[o] = a.out[o]; a.kind[o] = DIE_PLANE_F32; }
         a.rep_in = rep_scratch;
     }
     *sense = out;
     *rep = rep_scratch;
     return DIE_OK;
+}
+
+// *sense = the last layer's planes of replica 0 in the step's scratch, replica r's *rep further
+int die_nca_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
+                        const DropWords* drop, void* stream) {
+    return sense_batch(m, b, nca, nca->scratch, true, nullptr, sense, rep, drop, stream);
+}
+
+extern "C" int64_t die_nca_sense_batch_store_bytes(int32_t W, int32_t H, int32_t replicas, int32_t n_layers) {
+    if (W < 1 || H < 1 || replicas < 1 || replicas > DIE_MAX_REPLICAS || n_layers < 1 || n_layers > DIE_NCA_MAX_LAYERS) return -1;
+    return (int64_t)n_layers * replicas * NCA_MAXC * (int64_t)W * H * (int64_t)sizeof(float);
+}
+
+extern "C" int die_nca_sense_batch_store(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* store, int64_t store_bytes,
+                                         float* masked, const die_nca_dropout* drop, void* stream) {
+    const char* who = "die_nca_sense_batch_store";
+    DIE_REQUIRE(m && b && nca && store, "%s: null argument", who);
+    int rc = die_nca_batch_shape_check(m, b, who);
+    if (rc != DIE_OK) return rc;
+    rc = nca_stack_check(nca, m->W, m->H, b->replicas, who, false);
+    if (rc != DIE_OK) return rc;
+    DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad field dtype %d", who, m->dtype);
+    DIE_REQUIRE(m->food && m->chem && (m->owner || !nca->with_agent_channel), "%s: null plane", who);
+    DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX, "%s: sense_epoch %d", who, nca->sense_epoch);
+    const int64_t need = die_nca_sense_batch_store_bytes(m->W, m->H, b->replicas, nca->n_layers);
+    DIE_REQUIRE(store_bytes >= need, "%s: store too small (%lld < %lld)", who, (long long)store_bytes, (long long)need);
+    DIE_REQUIRE((m->W + NCA_TX - 1) / NCA_TX <= 65535, "%s: field too tall", who);
+    DropWords dw;
+    if (drop) {
+        DIE_REQUIRE(masked && masked != store, "%s: a dropout mask needs planes of its own for the masked values", who);
+        rc = die_dropout_words(drop, &dw, who);
+        if (rc != DIE_OK) return rc;
+    }
+    const float* sense;
+    int64_t rep;
+    return sense_batch(m, b, nca, store, false, drop ? masked : nullptr, &sense, &rep, drop ? &dw : nullptr, stream);
 }

@@ -27,8 +27,14 @@
 //                     tiles per row + column), in float64, and stores fp32.  Fixed order, fixed tree: the same inputs give the
 //                     same bits on every run.
 //
+//   die_nca_backward_batch / die_gather_scale_backward_batch   the same for every replica of a die_batch (a population's candidates):
+//                     k_conv_backward<K, true> with the replica in blockIdx.z, k_conv_backward_sum_batch folding a candidate's E
+//                     replicas in a fixed order, k_gather_scale_backward_batch with the replica in blockIdx.y.  Replica r is bit
+//                     for bit the stand-alone computation on its world.
+//
 // Roofline: as the forward (die_nca.hip) — a 3→3 3×3 layer reads 9 planes and writes 3 per cell for 2 × 81 MAC: no MFMA.
 #include <math.h>
+#include <type_traits>
 #include "die_common.h"
 #include "die_rng.h"
 #include "die_nca.h"
@@ -45,9 +51,17 @@ struct ConvBwdArgs {
     int has_t, has_drop, has_gin;
     DropWords d;
 };
+// what a BATCH launch reads on top (die_nca_backward_batch; the stand-alone instantiations keep ConvBwdArgs as their whole argument):
+// elements from replica r's planes / weights / partial rows to replica r + 1's
+struct ConvBwdBatchArgs : ConvBwdArgs {
+    int64_t rep_in, rep_g, rep_t, rep_gin, rep_w, rep_part;
+    int episodes;                // replica r stages weight row r / episodes (1: a row per replica)
+};
 
-template <int K>
-__global__ __launch_bounds__(DIE_BLOCK) void k_conv_backward(ConvBwdArgs a) {
+// BATCH: replica blockIdx.z of die_nca_backward_batch — its planes, its candidate's weights, its mask key (seed + z · seed_stride) and
+// its block of partial rows; tile, staging, register layout, butterfly and the tanh / mask adjoint are this one body.
+template <int K, bool BATCH = false>
+__global__ __launch_bounds__(DIE_BLOCK) void k_conv_backward(typename std::conditional<BATCH, ConvBwdBatchArgs, ConvBwdArgs>::type a) {
     constexpr int R = K / 2, LX = NCA_TX + 2 * R, LYV = NCA_TY + 2 * R, LY = LYV + 1;     // odd pitch, as the forward
     extern __shared__ __align__(16) float nca_grad_smem[];
     float* s_in = nca_grad_smem;                             // [cin][LX][LY]
@@ -55,7 +69,18 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_backward(ConvBwdArgs a) {
     float* s_w = s_g + a.cout * LX * LY;                     // [cout][cin][K][K]
     const int x0 = blockIdx.y * NCA_TX, y0 = blockIdx.x * NCA_TY;
     const int nw = a.cout * a.cin * K * K;
-    for (int i = threadIdx.x; i < nw; i += DIE_BLOCK) s_w[i] = a.w[i];
+    // replica z's offsets into the planes, weights and partial rows, and its mask key (BATCH only: every use below is the stand-alone
+    // expression when BATCH is off, so those instantiations compile to the code they always had)
+    [[maybe_unused]] int64_t o_in = 0, o_g = 0, o_t = 0, o_gin = 0, o_w = 0, o_part = 0;
+    [[maybe_unused]] uint64_t key = 0;
+    if constexpr (BATCH) {
+        const int64_t z = (int64_t)blockIdx.z;
+        o_in = z * a.rep_in; o_g = z * a.rep_g; o_t = z * a.rep_t; o_gin = z * a.rep_gin;
+        o_w = (int64_t)((int)blockIdx.z / a.episodes) * a.rep_w;
+        o_part = z * a.rep_part;
+        key = a.d.seed + (uint64_t)blockIdx.z * a.d.seed_stride;
+    }
+    for (int i = threadIdx.x; i < nw; i += DIE_BLOCK) s_w[i] = BATCH ? a.w[o_w + i] : a.w[i];
     // every staged element stands for the virtual cell (x0 − R + li, y0 − R + lj), read through the padding: also past the field's
     // last row / column inside a partial tile, where the input gradient of the cells before the edge needs the wrapped values
     for (int i = threadIdx.x; i < LX * LYV; i += DIE_BLOCK) {
@@ -63,15 +88,15 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_backward(ConvBwdArgs a) {
         const int gx = nca_pad_index(x0 - R + li, a.W, a.pad), gy = nca_pad_index(y0 - R + lj, a.H, a.pad);
         const bool in_field = gx >= 0 && gy >= 0;
         const int64_t cell = in_field ? (int64_t)gx * a.H + gy : 0;
-        for (int c = 0; c < a.cin; ++c) s_in[(c * LX + li) * LY + lj] = in_field ? nca_load(a.in[c], a.kind[c], cell, a.epoch) : 0.f;
+        for (int c = 0; c < a.cin; ++c) s_in[(c * LX + li) * LY + lj] = in_field ? nca_load(a.in[c], a.kind[c], BATCH ? o_in + cell : cell, a.epoch) : 0.f;
         float m = 1.f;
-        if (a.has_drop && in_field) m = die_dropout_factor(die_dropout_word(a.d.seed, a.d.step, (uint64_t)cell), a.d.thr, a.d.keep);
+        if (a.has_drop && in_field) m = die_dropout_factor(die_dropout_word(BATCH ? key : a.d.seed, a.d.step, (uint64_t)cell), a.d.thr, a.d.keep);
         for (int o = 0; o < a.cout; ++o) {
             float v = 0.f;
             if (in_field) {
-                v = a.g[o][cell];
+                v = a.g[o][BATCH ? o_g + cell : cell];
                 if (a.has_t) {
-                    const float t = a.t[o][cell];
+                    const float t = a.t[o][BATCH ? o_t + cell : cell];
                     v = a.has_drop ? v * m * (1.f - t * t) : v * (1.f - t * t);
                 }
             }
@@ -93,7 +118,7 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_backward(ConvBwdArgs a) {
                 if (o < a.cout && col_ok && x0 + r < a.W) greg[o][r] = s_g[(o * LX + r + R) * LY + lane + R];
             }
         }
-        float* prow = a.part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * nw;
+        float* prow = (BATCH ? a.part + o_part : a.part) + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * nw;
         for (int u = wave; u < a.cin * K; u += DIE_BLOCK / DIE_WAVE) {       // wave-uniform
             const int i = u / K, b = u - i * K;
             float col[LX];
@@ -146,7 +171,7 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_backward(ConvBwdArgs a) {
 #pragma unroll
     for (int c = 0; c < NCA_MAXC; ++c) {
         if (c < a.cin) {
-            float* dst = a.gin[c] + (int64_t)gx * a.H + gy;
+            float* dst = (BATCH ? a.gin[c] + o_gin : a.gin[c]) + (int64_t)gx * a.H + gy;
             if (gy + 3 < a.H && (a.H & 3) == 0) *(float4*)dst = make_float4(acc[c][0], acc[c][1], acc[c][2], acc[c][3]);
             else {
 #pragma unroll
@@ -164,6 +189,19 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_backward_sum(const float* pa
 #pragma unroll 8
     for (int64_t t = 0; t < tiles; ++t) s += (double)part[t * nw + j];
     out[j] = (float)s;
+}
+
+// die_nca_backward_batch's: one thread per (candidate blockIdx.y, weight j).  The E replicas of candidate c hold their partial rows
+// one behind the other ([replica][tile][nw], replica = c · E + e), so the fold "episode e = 0 … E − 1 outermost, tile index ascending
+// inside" is ONE ascending walk over E · tiles rows, in float64, rounded once — for E = 1 the loop above on replica c's rows.
+__global__ __launch_bounds__(DIE_BLOCK) void k_conv_backward_sum_batch(const float* part, int64_t rows, int nw, float* out, int64_t out_stride) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nw) return;
+    part += (int64_t)blockIdx.y * rows * nw;
+    double s = 0.0;
+#pragma unroll 8
+    for (int64_t t = 0; t < rows; ++t) s += (double)part[t * nw + j];
+    out[(int64_t)blockIdx.y * out_stride + j] = (float)s;
 }
 
 static bool conv_shape_ok(int32_t W, int32_t H, int32_t cin, int32_t cout, int32_t k) {
@@ -270,6 +308,31 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_gather_scale_backward(GatherBwdAr
     }
 }
 
+// die_gather_scale_backward_batch: replica blockIdx.y — its planes `rep_plane` elements on, its slots `agents` on, n[r] of them;
+// the loop is k_gather_scale_backward's, kept apart so that the stand-alone kernel's code stays what it was
+struct GatherBwdBatchArgs : GatherBwdArgs {
+    int64_t rep_plane, agents;
+    int64_t n[DIE_MAX_REPLICAS];
+};
+
+__global__ __launch_bounds__(DIE_BLOCK) void k_gather_scale_backward_batch(GatherBwdBatchArgs b) {
+    const int r = blockIdx.y;
+    const int64_t pa = b.agents * r;
+    GatherBwdArgs a = b;
+    a.N = b.n[r]; a.x += pa; a.y += pa;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { a.grad[q] += pa; a.plane[q] += b.rep_plane * r; }
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < a.N; n += stride) {
+        const int64_t c = die_local(a.g, die_cell((int64_t)a.x[n], a.g.gW), die_cell((int64_t)a.y[n], a.g.gH));
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const float v = a.grad[q][n] * a.coef[q];
+            if (v != 0.f) atomicAdd(&a.plane[q][c], v);
+        }
+    }
+}
+
 extern "C" int die_gather_scale_backward(const die_medium* m, const die_agents* ag, const die_action* grad_action, const float* coefs,
                                          float* const* grad_planes, void* stream) {
     const char* who = "die_gather_scale_backward";
@@ -295,5 +358,138 @@ extern "C" int die_gather_scale_backward(const die_medium* m, const die_agents* 
     const int64_t g = (ag->N + DIE_BLOCK - 1) / DIE_BLOCK;
     k_gather_scale_backward<<<(int)(g < 8192 ? g : 8192), DIE_BLOCK, 0, (hipStream_t)stream>>>(a);
     DIE_CHECK_LAUNCH(who);
+    return DIE_OK;
+}
+
+extern "C" int die_gather_scale_backward_batch(const die_medium* m, const die_agents* ag, const die_batch* b, const die_action* grad_action,
+                                               const float* coefs, float* grad_sense, int64_t sense_stride, void* stream) {
+    const char* who = "die_gather_scale_backward_batch";
+    DIE_REQUIRE(m && ag && b && grad_action && coefs && grad_sense, "%s: null argument", who);
+    int rc = die_nca_batch_shape_check(m, b, who);
+    if (rc != DIE_OK) return rc;
+    const int64_t cells = (int64_t)m->W * m->H;
+    DIE_REQUIRE(sense_stride >= 3 * cells, "%s: sense_stride %lld below three planes", who, (long long)sense_stride);
+    DIE_REQUIRE(ag->x && ag->y && grad_action->dx && grad_action->dy && grad_action->deposit, "%s: bad arrays", who);
+    GatherBwdBatchArgs a;
+    a.g = die_geo_of(m); a.N = 0; a.x = ag->x; a.y = ag->y;
+    a.grad[0] = grad_action->dx; a.grad[1] = grad_action->dy; a.grad[2] = grad_action->deposit;
+    for (int q = 0; q < 3; ++q) { a.plane[q] = grad_sense + q * cells; a.coef[q] = coefs[q]; }
+    a.rep_plane = sense_stride; a.agents = b->agent_stride;
+    int64_t nmax = 1;
+    for (int r = 0; r < DIE_MAX_REPLICAS; ++r) {
+        a.n[r] = r < b->replicas ? b->n[r] : 0;
+        if (a.n[r] > nmax) nmax = a.n[r];
+    }
+    // the 3 · R planes (and what lies between two replicas' planes where sense_stride leaves a gap)
+    const size_t span = (size_t)((int64_t)(b->replicas - 1) * sense_stride + 3 * cells) * sizeof(float);
+    if (hipMemsetAsync(grad_sense, 0, span, (hipStream_t)stream) != hipSuccess) {
+        die_set_error("%s: clearing the planes failed", who);
+        return DIE_ERR_HIP;
+    }
+    const int64_t g = (nmax + DIE_BLOCK - 1) / DIE_BLOCK;
+    k_gather_scale_backward_batch<<<dim3((unsigned)(g < 8192 ? g : 8192), (unsigned)b->replicas), DIE_BLOCK, 0, (hipStream_t)stream>>>(a);
+    DIE_CHECK_LAUNCH(who);
+    return DIE_OK;
+}
+
+// ---- the conv stack's adjoint for every replica of a batch ---------------------------------------------------------------
+// Workspace: [replica][tile][4 · 4 · 7 · 7] partial rows at most (a layer uses [replica][tile][cout · cin · k · k] of it), then
+// min(layers − 1, 2) sets of [replica][4][W][H] planes for the gradient travelling down the stack (ping-pong).
+static int64_t nca_backward_part_floats(int32_t W, int32_t H, int32_t replicas) {
+    return (int64_t)replicas * conv_tiles(W, H) * NCA_MAXC * NCA_MAXC * NCA_MAXK * NCA_MAXK;
+}
+static int nca_backward_gin_sets(int32_t n_layers) { return n_layers - 1 < 2 ? n_layers - 1 : 2; }
+
+extern "C" int64_t die_nca_backward_batch_workspace_bytes(int32_t W, int32_t H, int32_t replicas, int32_t n_layers) {
+    if (W < 1 || H < 1 || replicas < 1 || replicas > DIE_MAX_REPLICAS || n_layers < 1 || n_layers > DIE_NCA_MAX_LAYERS) return -1;
+    if ((W + NCA_TX - 1) / NCA_TX > 65535) return -1;
+    return (nca_backward_part_floats(W, H, replicas) + (int64_t)nca_backward_gin_sets(n_layers) * replicas * NCA_MAXC * (int64_t)W * H) *
+           (int64_t)sizeof(float);
+}
+
+extern "C" int die_nca_backward_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store,
+                                      const float* grad_sense, int64_t sense_stride, float* grad, int64_t grad_stride,
+                                      const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* who = "die_nca_backward_batch";
+    DIE_REQUIRE(m && b && nca && store && grad_sense && grad && workspace, "%s: null argument", who);
+    int rc = die_nca_batch_shape_check(m, b, who);
+    if (rc != DIE_OK) return rc;
+    rc = die_nca_stack_check(nca, m->W, m->H, b->replicas, who);
+    if (rc != DIE_OK) return rc;
+    if (nca->padding_mode == DIE_PAD_REFLECT || nca->padding_mode == DIE_PAD_REPLICATE) {
+        die_set_error("%s: the adjoint of 'reflect' / 'replicate' padding is not implemented ('circular' and 'zeros' are)", who);
+        return DIE_ERR_UNSUPPORTED;
+    }
+    DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad field dtype %d", who, m->dtype);
+    DIE_REQUIRE(m->food && m->chem && (m->owner || !nca->with_agent_channel), "%s: null plane", who);
+    DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX, "%s: sense_epoch %d", who, nca->sense_epoch);
+    const int64_t cells = (int64_t)m->W * m->H, rep_planes = NCA_MAXC * cells;
+    DIE_REQUIRE(sense_stride >= 3 * cells, "%s: sense_stride %lld below three planes", who, (long long)sense_stride);
+    int64_t P = 0;
+    for (int l = 0; l < nca->n_layers; ++l) {
+        const die_nca_layer& L = nca->layers[l];
+        P += (int64_t)L.cout * L.cin * L.k * L.k;
+        DIE_REQUIRE(grad != L.weights, "%s: grad is layer %d's weights", who, l);
+    }
+    DIE_REQUIRE(grad_stride >= P, "%s: grad_stride %lld below a row of %lld weights", who, (long long)grad_stride, (long long)P);
+    const int64_t need = die_nca_backward_batch_workspace_bytes(m->W, m->H, b->replicas, nca->n_layers);
+    DIE_REQUIRE(need > 0, "%s: field too tall", who);
+    DIE_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%lld < %lld)", who, (long long)workspace_bytes, (long long)need);
+    DropWords dw = {};
+    if (drop) {
+        rc = die_dropout_words(drop, &dw, who);
+        if (rc != DIE_OK) return rc;
+    }
+    const int E = nca->episodes > 1 ? nca->episodes : 1, R = b->replicas, L = nca->n_layers;
+    const int64_t tiles = conv_tiles(m->W, m->H);
+    float* part = (float*)workspace;
+    float* gin_sets = part + nca_backward_part_floats(m->W, m->H, R);
+    const int fkind = m->dtype == DIE_F32 ? DIE_PLANE_F32 : DIE_PLANE_F16;
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid((m->H + NCA_TY - 1) / NCA_TY, (m->W + NCA_TX - 1) / NCA_TX, R);
+    int64_t off = P;
+    const float* g = grad_sense;
+    int64_t rep_g = sense_stride;
+    for (int l = L - 1; l >= 0; --l) {
+        const die_nca_layer& Ly = nca->layers[l];
+        const int nw = Ly.cout * Ly.cin * Ly.k * Ly.k;
+        off -= nw;
+        ConvBwdBatchArgs a = {};
+        if (l == 0) {
+            int c = 0;
+            if (nca->with_agent_channel) { a.in[c] = m->owner; a.kind[c++] = DIE_PLANE_AGENTS; }
+            a.in[c] = m->food; a.kind[c++] = fkind;
+            a.in[c] = m->chem; a.kind[c++] = fkind;
+            a.rep_in = b->plane_stride;
+        } else {
+            for (int c = 0; c < Ly.cin; ++c) { a.in[c] = store + (int64_t)(l - 1) * R * rep_planes + c * cells; a.kind[c] = DIE_PLANE_F32; }
+            a.rep_in = rep_planes;
+        }
+        float* gin = l > 0 ? gin_sets + (int64_t)((L - 1 - l) % 2) * R * rep_planes : nullptr;
+        for (int c = 0; c < Ly.cin && gin; ++c) a.gin[c] = gin + c * cells;
+        for (int o = 0; o < Ly.cout; ++o) {
+            a.g[o] = g + o * cells;
+            if (l == L - 1) a.t[o] = store + (int64_t)l * R * rep_planes + o * cells;
+        }
+        a.rep_g = rep_g; a.rep_t = rep_planes; a.rep_gin = rep_planes;
+        a.w = Ly.weights; a.rep_w = Ly.weight_stride; a.episodes = E;
+        a.part = part; a.rep_part = tiles * nw;
+        a.W = m->W; a.H = m->H; a.cin = Ly.cin; a.cout = Ly.cout; a.epoch = nca->sense_epoch; a.pad = nca->padding_mode;
+        a.has_t = l == L - 1; a.has_drop = drop != nullptr && l == L - 1; a.has_gin = gin != nullptr;
+        a.d = dw;
+        const int Rk = Ly.k / 2;
+        const size_t lds = ((size_t)(Ly.cin + Ly.cout) * (NCA_TX + 2 * Rk) * (NCA_TY + 2 * Rk + 1) + (size_t)nw) * sizeof(float);
+        switch (Ly.k) {
+            case 1: k_conv_backward<1, true><<<grid, DIE_BLOCK, lds, s>>>(a); break;
+            case 3: k_conv_backward<3, true><<<grid, DIE_BLOCK, lds, s>>>(a); break;
+            case 5: k_conv_backward<5, true><<<grid, DIE_BLOCK, lds, s>>>(a); break;
+            default: k_conv_backward<7, true><<<grid, DIE_BLOCK, lds, s>>>(a); break;
+        }
+        DIE_CHECK_LAUNCH(who);
+        k_conv_backward_sum_batch<<<dim3((unsigned)die_grid_for(nw), (unsigned)(R / E)), DIE_BLOCK, 0, s>>>(part, (int64_t)E * tiles, nw, grad + off,
+                                                                                                    grad_stride);
+        DIE_CHECK_LAUNCH("die_nca_backward_batch(sum)");
+        g = gin; rep_g = rep_planes;
+    }
     return DIE_OK;
 }

@@ -829,6 +829,55 @@ int die_conv2d_backward(int32_t W, int32_t H, int32_t cin, const die_conv_plane*
                         float* const* grad_in, const float* const* fwd_out, const die_nca_dropout* drop,
                         int32_t padding_mode, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- The same adjoint for every replica of a die_batch (BatchedNeuralAutomataAgent.differentiable_sense / _action) ----------
+ * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
+ * `m` / `a` describe replica 0 and `b` the strides, as in die_nca_env_step_batch (b->n[r] may be 0 here); the die_nca_batch's
+ * `scratch` is not used by these calls and may be NULL.  Replica r computes, bit for bit, what the stand-alone calls above compute
+ * on its world; the replica rides in blockIdx.z (conv) or blockIdx.y (read-out), so the launch counts do not depend on R.  Every
+ * argument is checked on the host before anything is launched.
+ *
+ * die_nca_sense_batch_store: the L conv launches of die_nca_env_step_batch (replica r reads weight block r / E, the first layer
+ * the claim plane at nca->sense_epoch), layer l's output of every replica kept in `store`, [L][R][4][W][H] fp32
+ * (die_nca_sense_batch_store_bytes; -1 for a refused shape), instead of the ping-pong scratch.  With `drop` the last layer is
+ * launched twice: unmasked into `store` (tanh(z), what the adjoint reads) and masked with key seed + r * seed_stride into `masked`,
+ * [R][4][W][H] (required then, unused otherwise).  Nothing is stepped, claimed or moved. */
+int64_t die_nca_sense_batch_store_bytes(int32_t W, int32_t H, int32_t replicas, int32_t n_layers);
+int die_nca_sense_batch_store(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* store, int64_t store_bytes,
+                              float* masked, const die_nca_dropout* drop, void* stream);
+
+/* The read-out of every replica, one launch: `sense` = replica 0's (dx, dy, deposit) planes, W * H elements apart, replica r's
+ * sense_stride elements further (>= 3 * W * H);
+ *   out[c][r * agent_stride + n] = sense_r[c][cell_n] * coefs[c] for n < b->n[r]   (die_gather_scale's indexing and product),
+ *   out[c][r * agent_stride + n] = 0                              for b->n[r] <= n < agent_stride.   (out->N is not read.) */
+int die_gather_scale_batch(const die_medium* m, const die_agents* a, const die_batch* b, const float* sense, int64_t sense_stride,
+                           const float* coefs, const die_action* out, void* stream);
+
+/* Its adjoint: the span grad_sense[0 .. (R - 1) * sense_stride + 3 * W * H) is cleared (on `stream`), then, one launch,
+ *   grad_sense[r * sense_stride + c * W * H + cell_n] += grad_action[c][r * agent_stride + n] * coefs[c]   for n < b->n[r]
+ * (the padding slots are not read).  fp32 atomic adds, as die_gather_scale_backward: bit-reproducible run to run whenever no two
+ * slots of a replica with a non-zero gradient share a cell. */
+int die_gather_scale_backward_batch(const die_medium* m, const die_agents* a, const die_batch* b, const die_action* grad_action,
+                                    const float* coefs, float* grad_sense, int64_t sense_stride, void* stream);
+
+/* The conv stack's adjoint, 2 launches per layer from the last.  `m`: replica 0's first-layer input planes as
+ * die_nca_sense_batch_store read them (b->plane_stride apart); `store`: what that call wrote; `grad_sense`: the gradient at the
+ * sense planes (3 planes W * H apart per replica, sense_stride between replicas); `drop`: the die_nca_dropout the forward was
+ * masked with, or NULL.  Per layer, k_conv_backward with the replica in blockIdx.z — die_conv2d_backward's kernel body: replica r
+ * stages weight block r / E, recomputes its own mask key and writes its partial rows to workspace[r][tile][cout * cin * k * k] —
+ * then one thread per (candidate c, weight j) adds the partial rows of the candidate's E replicas in float64, episode e = 0 .. E - 1
+ * outermost and tile index ascending inside, and stores fp32 at
+ *   grad[c * grad_stride + offset_l + j],   offset_l = sum over the layers before l of cout * cin * k * k
+ * (the row layout of parameters_to_vector; grad_stride >= the row's length).  No float atomics: the same inputs give the same bits
+ * on every run; for E = 1 row r is die_conv2d_backward's gradient of replica r, bit for bit; for E > 1 row c is the float64 sum
+ * over its E worlds, rounded once.  The gradient at the inputs of layers >= 2 travels through the workspace.
+ *   Workspace (die_nca_backward_batch_workspace_bytes; -1 for a refused shape):
+ *   (R * ceil(W / 16) * ceil(H / 64) * 4 * 4 * 7 * 7  +  min(n_layers - 1, 2) * R * 4 * W * H) * 4 bytes.
+ * DIE_PAD_REFLECT / DIE_PAD_REPLICATE: DIE_ERR_UNSUPPORTED. */
+int64_t die_nca_backward_batch_workspace_bytes(int32_t W, int32_t H, int32_t replicas, int32_t n_layers);
+int die_nca_backward_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store,
+                           const float* grad_sense, int64_t sense_stride, float* grad, int64_t grad_stride,
+                           const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* die_food_flow_batch on the replicas whose bit is set in replica_mask (bit r = replica r); the others' planes are not touched.
  * One launch: a row of workgroups per replica, those of unset replicas exit at once.  A full mask leaves exactly what
  * die_food_flow_batch leaves; an empty mask launches nothing.  Bits at or above b->replicas must be 0. */
