@@ -215,7 +215,11 @@ class NeuralAutomataAgent(TorchAgent):
     def differentiable_sense(self, medium) -> th.Tensor:
         """`sense` with a `grad_fn`: (3, W, H) float32 on the medium's device, bit-identical to `sense`, whose backward is the
         conv stack's adjoint on the device (die_conv2d_backward per layer).  Gradients land in `model.parameters()` wherever the
-        model lives (the weights go in through a differentiable `.to(device)`); the medium is no leaf and gets none.
+        model lives (the weights go in through a differentiable `.to(device)`).  The medium gets none — unless it carries a chem
+        node (`Env.differentiable_chem` / `differentiable_step`, dropped by whatever else changes the field): then the node is an
+        input of the graph, the first layer's backward also asks die_conv2d_backward for `grad_in`, and the `chem1` channel's plane
+        of it goes to the node (the food and claim planes' gradients are discarded: they are constants of the parameters).  The
+        forward reads the medium's own planes either way: same values, same launches.
 
         Every layer's output goes into storage of its own (not the ping-pong scratch), and the first layer's inputs — the two
         field planes and the claim plane — are COPIED (3 planes), so that `backward` may run after the medium has been stepped.
@@ -231,7 +235,7 @@ class NeuralAutomataAgent(TorchAgent):
         medium.sensed()
         dev = medium.device
         weights = [k.weight.to(device=dev, dtype=th.float32).contiguous() for k in layers]
-        out = _DifferentiableSense.apply(self, medium, *weights)
+        out = _DifferentiableSense.apply(self, medium, getattr(medium, 'chem_node', None), *weights)
         p = self._model.agent_dropout.p
         if self._dropout_seed is not None:
             self.dropout_step += 1
@@ -263,8 +267,9 @@ class _DifferentiableSense(th.autograd.Function):
     one die_conv2d_backward per layer, last layer first."""
 
     @staticmethod
-    def forward(ctx, agent, medium, *weights):
+    def forward(ctx, agent, medium, chem_node, *weights):
         dev, W, H = medium.device, medium.W, medium.H
+        ctx.chem_channel = None if chem_node is None else agent.obs_channels.index('chem1')     # (its values ARE medium.chem's)
         sp = stream_ptr(dev)
         medium._ensure_owner()
         fkind = _lib.DIE_PLANE_F32 if medium.dtype == th.float32 else _lib.DIE_PLANE_F16
@@ -317,6 +322,7 @@ class _DifferentiableSense(th.autograd.Function):
         g = grad.to(dtype=th.float32).contiguous()
         drop = None if ctx.drop is None else _lib.nca_dropout(ctx.drop[0], ctx.drop[1], 0, ctx.drop[2])
         grads = [None] * L
+        to_node = ctx.chem_channel is not None and ctx.needs_input_grad[2]
         need = [_lib.lib.die_conv2d_backward_workspace_bytes(W, H, w.shape[1], w.shape[0], w.shape[2]) for w in weights]
         if min(need) < 0:
             raise ValueError('a layer shape die_conv2d_backward does not take (1..4 channels, kernel size 1, 3, 5 or 7)')
@@ -329,7 +335,8 @@ class _DifferentiableSense(th.autograd.Function):
             cin_arr = (_lib.ConvPlane * cin)(*[_lib.ConvPlane(t.data_ptr(), kind, 0) for t, kind in inputs])
             g_arr = (C.c_void_p * cout)(*[g[o].data_ptr() for o in range(cout)])
             grad_w = th.empty_like(w)
-            grad_in = th.empty((cin, W, H), dtype=th.float32, device=dev) if li > 0 else None
+            # the first layer's input is the medium: a gradient there only for a chem node that asks for one
+            grad_in = th.empty((cin, W, H), dtype=th.float32, device=dev) if li > 0 or to_node else None
             gin_arr = None if grad_in is None else (C.c_void_p * cin)(*[grad_in[c].data_ptr() for c in range(cin)])
             t_arr = (C.c_void_p * cout)(*[tanh_out[o].data_ptr() for o in range(cout)]) if last else None
             _lib.check(_lib.lib.die_conv2d_backward(W, H, cin, cin_arr, ctx.epoch, cout, g_arr, k, _ptr(w), _ptr(grad_w), gin_arr, t_arr,
@@ -337,7 +344,7 @@ class _DifferentiableSense(th.autograd.Function):
                                                     need[li], sp), 'die_conv2d_backward')
             grads[li] = grad_w
             g = grad_in
-        return (None, None, *grads)
+        return (None, None, g[ctx.chem_channel] if to_node else None, *grads)
 
 
 class _DifferentiableReadOut(th.autograd.Function):
@@ -370,3 +377,29 @@ class _DifferentiableReadOut(th.autograd.Function):
         _lib.check(_lib.lib.die_gather_scale_backward(C.byref(ctx.m), C.byref(a), C.byref(u), cf, p_arr, stream_ptr(ctx.dev)),
                    'die_gather_scale_backward')
         return planes, None, None, None
+
+
+class _DifferentiableFieldStep(th.autograd.Function):
+    """Env.differentiable_step's node: the value is a copy of the chem plane the step left, the backward die_env_step_backward —
+    the forward's own diffusion sweep on the gradient plane (on the torus Gᵀ = G) and a gather at the recorded winners' cells."""
+
+    @staticmethod
+    def forward(ctx, prev_node, action, cells, chem, sigma, decay):
+        ctx.save_for_backward(cells)
+        ctx.sigma, ctx.decay, ctx.size, ctx.dev = float(sigma), float(decay), tuple(chem.shape), chem.device
+        return chem.clone()
+
+    @staticmethod
+    @th.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        cells, = ctx.saved_tensors
+        (W, H), dev, N = ctx.size, ctx.dev, cells.numel()
+        g = grad.to(dtype=th.float32).contiguous()
+        grad_chem = th.empty((W, H), dtype=th.float32, device=dev)
+        grad_action = None
+        if ctx.needs_input_grad[1]:
+            grad_action = th.zeros((3, N), dtype=th.float32, device=dev)      # dx, dy: positions are constants of the parameters
+        _lib.check(_lib.lib.die_env_step_backward(W, H, _ptr(g), ctx.sigma, ctx.decay, N if grad_action is not None else 0, _ptr(cells),
+                                                  _ptr(grad_chem), None if grad_action is None else grad_action[2].data_ptr(),
+                                                  stream_ptr(dev)), 'die_env_step_backward')
+        return grad_chem if ctx.needs_input_grad[0] else None, grad_action, None, None, None, None

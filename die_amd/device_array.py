@@ -65,6 +65,9 @@ class DeviceMedium:
         # rank whose ghost refresh was left to travel under the next step (die_amd/dist.py) does it now instead.  The fused step
         # itself takes the planes through c_struct() and never triggers it
         self.before_sense = None
+        # the autograd handle of the chem plane (Env.differentiable_chem / differentiable_step): a (W, H) fp32 tensor holding a copy
+        # of `chem`, or None.  Whatever changes the field outside a differentiable step drops it
+        self.chem_node = None
 
     @property
     def shape(self):
@@ -143,6 +146,7 @@ class DeviceMedium:
         medium = np.asarray(medium)
         assert medium.shape == self.shape, (medium.shape, self.shape)
         self.owner_stale = None
+        self.chem_node = None
         occ = medium[0] > 0
         words = np.where(occ, np.uint64(((self.epoch << _lib.OWNER_EPOCH_SHIFT) | 1) << 32), np.uint64(0)).astype(np.uint64)
         self.owner.copy_(torch.from_numpy(words.view(np.int64)))
@@ -151,6 +155,7 @@ class DeviceMedium:
 
     def upload_channel(self, channel: str, data: np.ndarray):
         t = {'env_food': self.food, 'chem1': self.chem}[channel]
+        self.chem_node = None
         t.copy_(torch.from_numpy(np.ascontiguousarray(data, dtype=np.float32)))
 
 

@@ -305,6 +305,7 @@ class Env(_EnvBase):
 
     def step(self, action):
         """core/env.py:101-131 → (obs, reward, terminated, truncated, info)."""
+        self.medium.chem_node = None        # the field is about to change: an autograd handle of the chem plane ends here
         fused = binned = False
         burned = None
         if self.dynamics.op_action_cost not in (linear_action_cost, zero_cost):
@@ -386,6 +387,70 @@ class Env(_EnvBase):
         mean_gain = reward / num_agents if num_agents > 0 else 0.
         info = {'num_agents': num_agents, 'reward': _np_round(reward, 3), 'mean_reward': _np_round(mean_gain, 5)}
         return self._get_current_obs, reward, num_agents == 0, False, info
+
+    # ------------------------------------------------------------------ the differentiable step (die_env_grad.hip)
+    def _check_differentiable(self, what: str):
+        """What the chem adjoint covers; raises before anything is launched or changed."""
+        d, M = self.dynamics, self.medium
+        if M.dtype != torch.float32:
+            raise NotImplementedError(f'{what}: fp32 fields only (this medium is {M.dtype})')
+        if d.diffuse_mode != 'wrap':
+            raise NotImplementedError(f"{what}: diffuse_mode={d.diffuse_mode!r}: only 'wrap' — the adjoint of a non-periodic gaussian is "
+                                      f'not the forward sweep')
+        if d.apply_sense_mask:
+            raise NotImplementedError(f'{what}: apply_sense_mask is not differentiable here')
+        if d.agents_die and d.compat == 'reference':
+            raise NotImplementedError(f"{what}: agents_die with compat='reference' deposits at frozen positions; use compat='intended'")
+        if M.world is not None:
+            raise NotImplementedError(f'{what}: a decomposed medium (one tile of a larger world) is not supported')
+
+    def differentiable_chem(self) -> torch.Tensor:
+        """The chem node: a (W, H) fp32 tensor holding a copy of the current `chem1` plane, registered on the medium as the plane's
+        autograd handle.  On the first call, or after `reset`, a leaf with requires_grad=False; after a `differentiable_step` that
+        step's output, whose backward reaches the actions and the nodes of the steps before it.  The same tensor until the
+        world changes: `step`, `run`, the substeps and `upload` drop it without a word, which cuts the graph there."""
+        self._check_differentiable('differentiable_chem')
+        M = self.medium
+        if M.chem_node is None:
+            M.chem_node = M.chem.clone()
+        return M.chem_node
+
+    def differentiable_step(self, action: torch.Tensor):
+        """`step` with a graph through the chem plane.  `action`: the (3, N) fp32 tensor of `agent.differentiable_action(obs)`, in
+        the agents' array order right now.  The world is stepped by `step` itself on `action.detach()` — state, reward and info are
+        bit for bit those of `env.step` with the same values — and the medium's chem node becomes this step's output:
+            chem' = (1 − decay) · G(chem + D),   D[cell] = deposit of the slot that won the cell,
+        differentiated with respect to the previous node (if it is still current) and the action's deposit row
+        (die_env_step_backward).  Positions are piecewise constant in whatever produced the action, so dx and dy get zero
+        gradient, and food and the 'agents' channel none: that is their true gradient, not an approximation.  Who deposited where
+        (die_deposit_cells) is recorded before the step's periodic re-sort permutes the arrays and kept by the graph, so `backward`
+        may run after any number of further steps, re-sorts or a reset.  A slot starved by this very step (agents_die) is dead
+        when the record is made and gets no gradient for its last deposit."""
+        from .agent.evo import _DifferentiableFieldStep
+        self._check_differentiable('differentiable_step')
+        N = self.agents.N
+        if not isinstance(action, torch.Tensor) or action.dtype != torch.float32 or tuple(action.shape) != (3, N) \
+                or action.device != self.device:
+            raise NotImplementedError(f'differentiable_step: action must be a (3, {N}) float32 tensor on {self.device} '
+                                      f'(NeuralAutomataAgent.differentiable_action), got '
+                                      f'{(tuple(action.shape), action.dtype, str(action.device)) if isinstance(action, torch.Tensor) else type(action).__name__}')
+        M, d = self.medium, self.dynamics
+        prev = M.chem_node
+        act = DeviceAction(N, self.device, self.agents.slot)
+        act.data = action.detach().contiguous()
+        # the step's own re-sort waits until the winners are recorded: they are named in the array order the action came in
+        sort_every, self._sort_every = self._sort_every, 0
+        try:
+            out = self.step(act)
+        finally:
+            self._sort_every = sort_every
+        cells = torch.empty(N, dtype=torch.int32, device=self.device)
+        m, a = M.c_struct(), self.agents.c_struct()
+        _lib.check(_lib.lib.die_deposit_cells(C.byref(m), C.byref(a), _ptr(cells), stream_ptr(self.device)), 'die_deposit_cells')
+        if sort_every > 0 and self._steps % sort_every == 0:
+            self.sort_agents()
+        M.chem_node = _DifferentiableFieldStep.apply(prev, action, cells, M.chem, float(d.diffuse_sigma), float(d.rate_decay_chem))
+        return out
 
     def read_result(self, result: torch.Tensor) -> Tuple[float, int]:
         """(reward, num_agents) of a die_step_result buffer (synchronises).  A 3-word buffer (`Env(sync=True)` builds one per
@@ -539,6 +604,7 @@ class Env(_EnvBase):
         faster than the plain launch loop (256²: 33.8 vs 30.4 µs/step, 1024²: 49.0 vs 42.3, 4096²: 243 vs 224 —
         ≈ 5 µs per graph node), so the default is the loop."""
         from .agent.gradient import GradientAgent
+        self.medium.chem_node = None
         n_steps = int(n_steps)
         out = torch.empty((max(n_steps, 0), 2), dtype=torch.float64, device=self.device)
         sync, self._sync = self._sync, False
@@ -739,6 +805,7 @@ class Env(_EnvBase):
 
     def _stage(self, fn_name, action):
         self._agents_changed()
+        self.medium.chem_node = None
         act = self._as_action(action)
         m, a, u, d = self.medium.c_struct(), self.agents.c_struct(), act.c_struct(), self._c_dynamics()
         _lib.check(getattr(_lib.lib, fn_name)(C.byref(m), C.byref(a), C.byref(u), C.byref(d), _ptr(self._workspace),
@@ -746,6 +813,7 @@ class Env(_EnvBase):
 
     def _medium_deposit_feed_diffuse(self):
         """Deposit + feeding + diffusion in one field sweep (after `_stage('die_agent_move_claim')`)."""
+        self.medium.chem_node = None
         m, d = self.medium.c_struct(), self._c_dynamics()
         _lib.check(_lib.lib.die_medium_deposit_feed_diffuse(C.byref(m), C.byref(d), stream_ptr(self.device)),
                    'die_medium_deposit_feed_diffuse')
@@ -754,6 +822,7 @@ class Env(_EnvBase):
     def _medium_diffuse_decay(self):
         d = self.dynamics
         m = self.medium
+        m.chem_node = None
         _lib.check(_lib.lib.die_diffuse_decay_mode(_ptr(m.chem), _ptr(m.chem_next), m.W, m.H, m.c_struct().dtype,
                                                    d.diffuse_sigma, d.rate_decay_chem, _lib.DIFFUSE_MODES[d.diffuse_mode],
                                                    stream_ptr(self.device)), 'die_diffuse_decay_mode')

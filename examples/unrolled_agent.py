@@ -1,0 +1,91 @@
+"""Train a NeuralAutomataAgent through the world: grow a teacher's trail pattern by backpropagating through T steps of Env.step.
+
+    python examples/unrolled_agent.py [--size 96] [--steps 8] [--iters 100] [--lr 0.01] [--seed 0] [--time]
+
+A PhysarumAgent world is run `--steps` steps from the seed and its `chem1` plane kept as the target.  The student —
+NeuralAutomataAgent(kernel_sizes=[3, 3]) — is then unrolled the same number of steps from the same seed, every step
+`env.differentiable_step(student.differentiable_action(obs))`, and the loss is the mean squared error of `env.differentiable_chem()`
+against the target plus the reference's linear action cost (core/env.py:29-35) written in torch on the actions, per slot.
+`loss.backward()` walks the rollout backwards: per step the diffusion sweep on the gradient plane and a gather at the depositors'
+cells (die_env_step_backward), the read-out's and the conv stack's adjoints, and the first layer's input gradient carries on into
+the step before.  What the trail laid at step 1 does to what the colony senses at step 4 is in that gradient; where the agents
+walk is not (positions are piecewise constant in the weights).  Adam updates the 162 weights; the loss is printed per iteration.
+`--time` prints optimiser iterations per second instead (after a warm-up tenth of the run, both ends a device synchronise).
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from die_amd import Dynamics, Env, NeuralAutomataAgent, PhysarumAgent          # noqa: E402
+
+SCALE, DEPOSIT = 0.01, 2.0
+COST_W = (0.02, 0.01)                                             # linear_action_cost's weights
+
+
+def make_env(size, seed):
+    return Env((size, size), Dynamics(food_infinite=True, rate_decay_chem=0.05, diffuse_sigma=0.8), seed=seed, max_agents='alive')
+
+
+def teacher_trail(size, steps, seed):
+    env = make_env(size, seed)
+    teacher = PhysarumAgent(max_agents=env.agents.capacity, scale=SCALE, deposit=DEPOSIT, seed=seed)
+    obs = env._get_current_obs
+    for _ in range(steps):
+        obs = env.step(teacher.forward(obs))[0]
+    return env.medium.chem.clone()
+
+
+def action_cost(action):
+    """core/env.py:29-35 on a (3, N) tensor: w0 * |deposit| + w1 * |(dx, dy)|, summed over the slots."""
+    return (COST_W[0] * action[2].abs() + COST_W[1] * (action[0] ** 2 + action[1] ** 2 + 1e-12).sqrt()).sum()
+
+
+def rollout_loss(student, target, size, steps, seed):
+    env = make_env(size, seed)
+    obs = env._get_current_obs
+    cost = 0.
+    for _ in range(steps):
+        action = student.differentiable_action(obs)
+        cost = cost + action_cost(action)
+        obs = env.differentiable_step(action)[0]
+    return ((env.differentiable_chem() - target) ** 2).mean() + cost / (steps * env.agents.N)
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument('--size', type=int, default=96)
+    p.add_argument('--steps', type=int, default=8, help='T: the steps of one rollout')
+    p.add_argument('--iters', type=int, default=100, help='optimiser iterations (one rollout and one backward each)')
+    p.add_argument('--lr', type=float, default=0.01)
+    p.add_argument('--seed', type=int, default=0)
+    p.add_argument('--time', action='store_true', help='print optimiser iterations per second instead of the losses')
+    args = p.parse_args()
+    torch.manual_seed(args.seed)
+    target = teacher_trail(args.size, args.steps, args.seed)
+    student = NeuralAutomataAgent(kernel_sizes=[3, 3], scale=SCALE, deposit=DEPOSIT)
+    student.model.init_weights()
+    opt = torch.optim.Adam(student.model.parameters(), lr=args.lr)
+    warmup, t0 = max(1, args.iters // 10), None
+    for it in range(args.iters):
+        if args.time and it == warmup:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        loss = rollout_loss(student, target, args.size, args.steps, args.seed)
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        if not args.time:                                         # (a loss print reads the device: not inside a timed window)
+            print(f'iteration {it:4d}: loss {float(loss.detach()):.6f}')
+    if t0 is not None:
+        torch.cuda.synchronize()
+        n = args.iters - warmup
+        print(f'unrolled training, {args.size}x{args.size}, T = {args.steps}: {n / (time.perf_counter() - t0):.1f} optimiser iterations/s over {n}')
+
+
+if __name__ == '__main__':
+    main()

@@ -878,6 +878,33 @@ int die_nca_backward_batch(const die_medium* m, const die_batch* b, const die_nc
                            const float* grad_sense, int64_t sense_stride, float* grad, int64_t grad_stride,
                            const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- The adjoint of Env.step's chem path (die_env_grad.hip; Env.differentiable_step / Env.differentiable_chem) -----------------
+ * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
+ * One step maps (chem, deposit) to chem' = (1 - decay) * G(chem + D), D[cell] = deposit[n] where entry n won the cell; positions,
+ * food and the claim plane are piecewise constant in an agent's parameters and carry no gradient.  Stand-alone worlds, fp32
+ * planes, the periodic ('wrap') gaussian.  Every argument is checked on the host before anything is launched. */
+
+/* Who deposited where.  Called right after die_env_step (or one of its equivalents), with the step's m->epoch and the post-move
+ * coordinates; for array entry n with slot id s (a->slot[n], a->slot NULL: s = n)
+ *   cells_out[n] = ix * m->H + iy   if a->alive[n] and the claim word of cell (ix, iy) carries (m->epoch, s + 1),
+ *   cells_out[n] = -1               otherwise (dead slots; the losers of a shared cell),
+ * with ix, iy and the claim word read as the step's kernels read them.  One launch; a->N int32 words are written, a->N == 0
+ * launches nothing.  A slot that the step's lifecycle (agents_die) zeroed is dead by now and gets -1.  DIE_ERR_UNSUPPORTED for a
+ * decomposed medium (m->gW > 0) and for more than 2^31 - 1 cells. */
+int die_deposit_cells(const die_medium* m, const die_agents* a, int32_t* cells_out, void* stream);
+
+/* The step's adjoint:
+ *   grad_chem = (1 - decay) * G^T(grad_chem_next)                    (W x H fp32, overwritten)
+ *   grad_deposit[n] = cells[n] >= 0 ? grad_chem[cells[n]] : 0        (N fp32, overwritten; cells as die_deposit_cells wrote them)
+ * On the torus with symmetric taps G^T = G, so the field part is die_diffuse_decay itself on the gradient plane — the forward's
+ * taps and kernels (the row sweep where H % 4 == 0 and the radius is at most 4, the LDS-tiled kernel elsewhere); there is no
+ * second gaussian.  grad_deposit is a gather in plain loads and stores after the sweep: no atomics, every output written once,
+ * the same bits on every run; an index at or beyond W * H counts as negative.  grad_chem may not alias grad_chem_next, nor
+ * grad_deposit any other argument.  N == 0 or grad_deposit == NULL: the field part only (cells is not read).  sigma as
+ * die_diffuse_decay takes it (radius int(4 sigma + .5) in 1..8, else DIE_ERR_ARG / DIE_ERR_UNSUPPORTED). */
+int die_env_step_backward(int32_t W, int32_t H, const float* grad_chem_next, float sigma, float decay, int64_t N,
+                          const int32_t* cells, float* grad_chem, float* grad_deposit, void* stream);
+
 /* die_food_flow_batch on the replicas whose bit is set in replica_mask (bit r = replica r); the others' planes are not touched.
  * One launch: a row of workgroups per replica, those of unset replicas exit at once.  A full mask leaves exactly what
  * die_food_flow_batch leaves; an empty mask launches nothing.  Bits at or above b->replicas must be 0. */
