@@ -86,6 +86,7 @@ class PicSide(C.Structure):          # die_pic_side: one neighbour of the ghost 
                 ('cap', C.c_int64), ('send_counts', C.c_void_p), ('send_rec', C.c_void_p), ('recv_counts', C.c_void_p), ('recv_rec', C.c_void_p)]
 
 
+PIC_ORDER_READY, PIC_ORDER_NO_TAIL, PIC_ORDER_SLOTS_SHIFT = 1, 2, 8      # die_pic.order_ready (DIE_PIC_ORDER_*)
 PIC_GHOST_SUMMARY_WORDS = 19
 PIC_GHOST_FLAGS = {1: 'a tile holds another number of agents than its per-tile words say', 2: 'a band holds more agents than a message',
                    4: 'a received count is impossible', 8: 'the agents do not fit the local arrays'}

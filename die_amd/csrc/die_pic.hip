@@ -33,6 +33,8 @@
 // path: die_agents_mark_owner materialises it when somebody asks (DeviceMedium.occupied / owner_slots / render).
 #include "die_forward.h"
 #include <stdlib.h>
+#include <mutex>
+#include <vector>
 
 typedef uint32_t pic_u4v __attribute__((ext_vector_type(4)));
 typedef uint32_t pic_u2v __attribute__((ext_vector_type(2)));
@@ -124,8 +126,8 @@ struct PicArgs {
     const float *ipgx, *ipgy;
     float *opgx, *opgy;
     // ORDER TABLE (die_pic.order; NULL: the band mapping of pic_xcd_tile): XCD j = linear workgroup id mod 8 takes the tile
-    // order[j·order_len + k], k = id div 8 — a permutation of band j's tiles with the crowded ones first (k_pic_order), so that the tiles
-    // that live longest do not make up a launch's tail
+    // order[j·order_len + k], k = id div 8 — a permutation of band j's tiles with the crowded ones first or, without crowds, the lightest
+    // ones last (k_pic_order), so that the tiles that live longest do not make up a launch's tail
     const uint16_t* order;
     int order_len;                  // tiles per band = ntx · (nty / 8)
 };
@@ -1236,10 +1238,29 @@ __global__ __launch_bounds__((KbShape<XS, YS>::BLOCK), PIC_KB_MINW) void k_pic_r
 // tile sits in a launch's last rounds — a crowded tile in the middle of a launch delays nobody —, and tiles that are neighbours in space
 // should stay neighbours in time (they share the margins of their windows in one L2): with their bands of 2 048 / 8 192 tiles sorted as
 // a whole, or span by span, an 8192² / 16384² world LOST 2–3 % at the bench's window, where the 512-tile bands of 4096² gained.
-__global__ __launch_bounds__(PIC_ORDER_BLOCK) void k_pic_order(const uint32_t* n, int ntx, int nty, uint16_t* order) {
+//
+// TAIL FORM (spans without crowds; `slots` > 0: workgroups of the agent kernel the device holds at once = CUs × resident per CU, from
+// the host).  A launch of NT workgroups on `slots` places ends in a partial round of NT mod slots workgroups — 4096² fp32: 4 096 on 768,
+// 5.33 rounds — during which most places stand empty, so that round lasts as long as the tiles that happen to sit at the bands' ends.
+// Band j's share of it, its last `tail` table places (workgroup 8k + j ≥ NT − NT mod slots), is therefore filled with the span's `tail`
+// LIGHTEST tiles, in band order among themselves, and the places ahead keep the other tiles in band order: all but `tail` of the span's
+// tiles still run beside their neighbours in space.  No tail to shape — band order — when the last round is full or nearly so (NT mod
+// slots = 0 or above 7/8 of slots), when a band's share exceeds the span, or when it is the whole span.  The same for all eight bands
+// (their shares differ by one at most, where slots is no multiple of 8: decided on the largest).
+__device__ __forceinline__ int pic_order_tail(int blen, int slots, int j, int len) {
+    if (slots <= 0) return 0;
+    const int NT = blen * 8, r = NT % slots;
+    if (r == 0 || (int64_t)r * 8 > (int64_t)slots * 7) return 0;
+    const int first = NT - r;                               // the last round's first workgroup
+    if (blen - first / 8 > len) return 0;                   // (band 7's share, the largest)
+    return blen - (first - j + 7) / 8;
+}
+
+__global__ __launch_bounds__(PIC_ORDER_BLOCK) void k_pic_order(const uint32_t* n, int ntx, int nty, uint16_t* order, int slots) {
     __shared__ uint32_t s_cnt[8][PIC_ORDER_BLOCK];         // [class][thread]: tiles of that class in this thread's stretch of the span
     __shared__ uint32_t s_first[8];                        // first place of a class
     __shared__ uint32_t s_crowded;                         // tiles of four and more rounds in all eight bands' last spans
+    __shared__ uint32_t s_sel[3], s_wave[2][PIC_ORDER_BLOCK / DIE_WAVE];      // tail form: largest population, chosen bin, tiles below it; flags per wave
     const int j = blockIdx.x, wb = nty >> 3, blen = wb * ntx;
     // spans are counted from the band's END: the last one is whole, the first one takes what is left
     const int q1 = blen - (int)(gridDim.y - 1 - blockIdx.y) * PIC_ORDER_SPAN, q0 = max(q1 - PIC_ORDER_SPAN, 0), len = q1 - q0;
@@ -1277,7 +1298,7 @@ __global__ __launch_bounds__(PIC_ORDER_BLOCK) void k_pic_order(const uint32_t* n
         if (lane == 0) s_first[w] = run;                    // (the class's total, for now)
     }
     __syncthreads();
-    // Spans without crowds stay in band order: sorting costs the L2 sharing of neighbouring tiles' windows (counted traffic of a step
+    // Spans without crowds stay in band order but for the tail form's few tiles: sorting costs the L2 sharing of neighbouring tiles' windows (counted traffic of a step
     // 567 → 613 MB at the bench's window) and pays once enough tiles of four and more rounds — more than 1 536 agents: where the agent
     // kernel's workgroups live longest and the field kernel's rim lists overflow — could end up in the tail.  The bench world, 32-step
     // runs without / with every band sorted (profiles/r06_order_table_shipped.txt): 79–90 such tiles (world steps 416–544) 134.4 / 136.1 µs
@@ -1296,7 +1317,74 @@ __global__ __launch_bounds__(PIC_ORDER_BLOCK) void k_pic_order(const uint32_t* n
     __syncthreads();
     const bool sorted = (uint64_t)s_crowded * 4096u >= (uint64_t)PIC_ORDER_MIN_CROWDED * 8u * (uint32_t)len;
     if (!sorted) {
-        for (int q = lo; q < hi; ++q) order[(size_t)j * blen + q] = (uint16_t)tile_at(q);
+        const int tail = pic_order_tail(blen, slots, j, len);
+        if (tail <= 0 || tail >= len) {
+            for (int q = lo; q < hi; ++q) order[(size_t)j * blen + q] = (uint16_t)tile_at(q);
+            return;
+        }
+        // The tail form: one tile of the span per thread.  The population T below which `tail` tiles fall is found by a radix selection
+        // over the populations' bytes, from the highest byte any of them uses down: a 256-bin histogram of the tiles still undecided,
+        // the bin in which the running count reaches the number still wanted; lighter bins go to the tail, heavier ones stay.
+        static_assert(PIC_ORDER_SPAN <= PIC_ORDER_BLOCK, "one tile per thread");
+        uint32_t* hist = &s_cnt[0][0];                      // (the classes' counts are not needed on this path)
+        const int wave = threadIdx.x / DIE_WAVE, lane = threadIdx.x & (DIE_WAVE - 1);
+        const bool has = (int)threadIdx.x < len;
+        const int t = has ? tile_at(q0 + (int)threadIdx.x) : 0;
+        const uint32_t pop = has ? n[t] : 0u;
+        if (threadIdx.x == 0) s_sel[0] = 0;
+        __syncthreads();
+        {
+            uint32_t mx = pop;
+#pragma unroll
+            for (int o = DIE_WAVE / 2; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor(mx, o, DIE_WAVE));
+            if (lane == 0 && mx) atomicMax(&s_sel[0], mx);
+        }
+        __syncthreads();
+        bool cand = has, in_tail = false;
+        uint32_t want = (uint32_t)tail;                     // of the undecided tiles, how many go to the tail: 1 ≤ want ≤ their number
+        for (int sh = s_sel[0] ? (31 - __clz((int)s_sel[0])) & ~7 : 0; sh >= 0; sh -= 8) {
+            if (threadIdx.x < 256) hist[threadIdx.x] = 0;
+            __syncthreads();
+            const uint32_t d = (pop >> sh) & 255u;
+            if (cand) atomicAdd(&hist[d], 1u);
+            __syncthreads();
+            if (wave == 0) {                                // lane l: bins 4l … 4l + 3
+                uint32_t c[4], sum = 0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { c[i] = hist[4 * lane + i]; sum += c[i]; }
+                uint32_t x = sum;
+#pragma unroll
+                for (int o = 1; o < DIE_WAVE; o <<= 1) { const uint32_t u = __shfl_up(x, o, DIE_WAVE); if (lane >= o) x += u; }
+                uint32_t run = x - sum;
+                if (run < want && want <= x) {              // (exactly one lane)
+                    int b = 0;
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) if (run + c[i] < want && b == i) { run += c[i]; b = i + 1; }
+                    s_sel[1] = (uint32_t)(4 * lane + b); s_sel[2] = run;
+                }
+            }
+            __syncthreads();
+            if (cand && d != s_sel[1]) { in_tail = d < s_sel[1]; cand = false; }
+            want -= s_sel[2];
+        }
+        // the undecided tiles hold exactly T agents; `want` of them go to the tail: the last ones in band order
+        auto before = [&](bool f, uint32_t* s_w, uint32_t& total) {       // flagged tiles ahead of this thread's, and in all
+            const unsigned long long m = __ballot(f);
+            if (lane == 0) s_w[wave] = (uint32_t)__popcll(m);
+            __syncthreads();
+            uint32_t b = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            total = 0;
+            for (int w = 0; w < PIC_ORDER_BLOCK / DIE_WAVE; ++w) { const uint32_t v = s_w[w]; b += w < wave ? v : 0u; total += v; }
+            return b;
+        };
+        uint32_t n_eq, n_tail;
+        const uint32_t eq_before = before(cand, s_wave[0], n_eq);
+        in_tail = in_tail || (cand && eq_before + want >= n_eq);
+        const uint32_t tail_before = before(in_tail, s_wave[1], n_tail);
+        if (has) {
+            const uint32_t place = in_tail ? (uint32_t)(len - tail) + tail_before : threadIdx.x - tail_before;
+            order[(size_t)j * blen + q0 + place] = (uint16_t)t;
+        }
         return;
     }
     if (threadIdx.x == 0) {
@@ -1527,19 +1615,45 @@ static void launch_resolve(const PicArgs& k, float* dep_plane, int NT, bool f32,
     }
 }
 
+// the agent kernel's instantiation for an agent kind (`act`: the action is handed back; `mom`: GradientAgent with momentum)
+typedef void (*PicK1Fn)(FwdArgs, PicArgs);
+template <typename T, bool STAGE, bool RIM, bool TILED = false>
+static PicK1Fn forward_move_kernel(int kind, bool act, bool mom) {
+    if constexpr (!TILED) {
+        if (kind != DIE_AGENT_PHYSARUM && mom) return k_pic_forward_move<T, DIE_AGENT_GRADIENT, STAGE, true, RIM, false, true>;
+    }
+    if (kind != DIE_AGENT_PHYSARUM) return k_pic_forward_move<T, DIE_AGENT_GRADIENT, STAGE, true, RIM, TILED>;
+    if (act) return k_pic_forward_move<T, DIE_AGENT_PHYSARUM, STAGE, true, RIM, TILED>;
+    return k_pic_forward_move<T, DIE_AGENT_PHYSARUM, STAGE, false, RIM, TILED>;
+}
+
 template <typename T, bool STAGE, bool RIM, bool TILED = false>
 static void launch_forward_move(int kind, const FwdArgs& f, const PicArgs& k, int NT, int block, size_t lds, hipStream_t s, bool mom = false) {
     // (an order table covers exactly the tiles: 8 · order_len = ntx · nty workgroups, the same grid)
     const dim3 grid(k.sub_mode == 1 ? k.sub_nty : k.nty, k.sub_mode == 1 ? k.sub_ntx : k.ntx);
-    if constexpr (!TILED) {
-        if (kind != DIE_AGENT_PHYSARUM && mom) {
-            k_pic_forward_move<T, DIE_AGENT_GRADIENT, STAGE, true, RIM, false, true><<<grid, block, lds, s>>>(f, k);
-            return;
-        }
+    forward_move_kernel<T, STAGE, RIM, TILED>(kind, k.adx != nullptr, mom)<<<grid, block, lds, s>>>(f, k);
+}
+
+// Workgroups of an agent-kernel instantiation the device holds at once: CUs × resident workgroups per CU at this workgroup size and
+// LDS request (4096² fp32 on 256 CUs: 3 each, 768) — what k_pic_order's tail form measures a launch's last round by.  Asked of the
+// runtime once per (device, kernel, size, LDS); 0 when it cannot say: the table then keeps band order below the crowd threshold.
+static int pic_agent_slots(PicK1Fn fn, int block, size_t lds) {
+    struct Memo { int dev; PicK1Fn fn; int block; size_t lds; int slots; };
+    static std::mutex mu;
+    static std::vector<Memo> memo;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    std::lock_guard<std::mutex> lock(mu);
+    for (const Memo& e : memo) if (e.dev == dev && e.fn == fn && e.block == block && e.lds == lds) return e.slots;
+    int cus = 0, resident = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, (const void*)fn, block, lds) != hipSuccess) {
+        (void)hipGetLastError();
+        cus = resident = 0;
     }
-    if (kind != DIE_AGENT_PHYSARUM) k_pic_forward_move<T, DIE_AGENT_GRADIENT, STAGE, true, RIM, TILED><<<grid, block, lds, s>>>(f, k);
-    else if (k.adx) k_pic_forward_move<T, DIE_AGENT_PHYSARUM, STAGE, true, RIM, TILED><<<grid, block, lds, s>>>(f, k);
-    else k_pic_forward_move<T, DIE_AGENT_PHYSARUM, STAGE, false, RIM, TILED><<<grid, block, lds, s>>>(f, k);
+    const int slots = cus > 0 && resident > 0 ? cus * resident : 0;
+    memo.push_back({dev, fn, block, lds, slots});
+    return slots;
 }
 
 int die_gaussian_taps(float sigma, double* w);             // die_env.hip (scipy.ndimage._gaussian_kernel1d); w holds 2·8 + 1 taps
@@ -1705,8 +1819,21 @@ extern "C" int die_pic_forward_env_step(const die_medium* m, const die_pic* p, i
     // layout this step reads before its agent kernel — the first time, and every PIC_ORDER_PERIOD-th step
     if (p->order && two && !tiled && !p->sub_mode && (k.nty & 7) == 0 && NT <= 65536) {
         k.order = p->order; k.order_len = NT >> 3;
-        if ((stages & 1) && (!p->order_ready || (g->step % PIC_ORDER_PERIOD) == 0))
-            k_pic_order<<<dim3(8, ((NT >> 3) + PIC_ORDER_SPAN - 1) / PIC_ORDER_SPAN), PIC_ORDER_BLOCK, 0, s>>>(k.in.n, k.ntx, k.nty, p->order);
+        if ((stages & 1) && (!(p->order_ready & DIE_PIC_ORDER_READY) || (g->step % PIC_ORDER_PERIOD) == 0)) {
+            // the tail form's measure (k_pic_order): the caller's, else what the device holds of the agent kernel this step launches
+            int slots = 0;
+            if (!(p->order_ready & DIE_PIC_ORDER_NO_TAIL)) {
+                slots = (int)((uint32_t)p->order_ready >> DIE_PIC_ORDER_SLOTS_SHIFT);
+                if (slots == 0) {
+                    const bool act_out = k.adx != nullptr;
+                    const PicK1Fn fn = m->dtype == DIE_F32
+                        ? (stage ? forward_move_kernel<float, true, true>(g->kind, act_out, mom) : forward_move_kernel<float, false, true>(g->kind, act_out, mom))
+                        : (stage ? forward_move_kernel<__half, true, true>(g->kind, act_out, mom) : forward_move_kernel<__half, false, true>(g->kind, act_out, mom));
+                    slots = pic_agent_slots(fn, block, stage ? lds : 0);
+                }
+            }
+            k_pic_order<<<dim3(8, ((NT >> 3) + PIC_ORDER_SPAN - 1) / PIC_ORDER_SPAN), PIC_ORDER_BLOCK, 0, s>>>(k.in.n, k.ntx, k.nty, p->order, slots);
+        }
     }
     if (stages & 1) {
 #define DIE_PIC_K1(T, STAGE, LDS) do { if (two) launch_forward_move<T, STAGE, true>(g->kind, f, k, NT, block, LDS, s, mom); \
@@ -1816,7 +1943,7 @@ extern "C" int die_pic_run(const die_medium* m, const die_pic* p, int32_t from, 
         gg.step += 1u;                                                                   // the agent object's call counter
         // (the two-launch form's field kernel has left the next step's turn bits in the table; the three-launch form fills it itself)
         pp.turn_ready = 1;
-        pp.order_ready = 1;                                                              // (the first step has built the order table)
+        pp.order_ready |= DIE_PIC_ORDER_READY;                                           // (the first step has built the order table)
     }
     return DIE_OK;
 }

@@ -81,6 +81,11 @@ class PicState:
         self.order = torch.zeros(self.NT, dtype=torch.int16, device=dev) \
             if (self.fused and env.medium.world is None and nty % 8 == 0 and self.NT <= 65536 and os.environ.get('DIE_PIC_ORDER', '1') != '0') else None
         self._order_ready = False
+        # … and, below the crowd threshold, every band's lightest tiles in the launch's last, partial round (the tail form of
+        # k_pic_order; DIE_PIC_ORDER_TAIL=0: band order there).  `env._pic_order_slots` > 0 takes the place of the device's count of
+        # resident agent-kernel workgroups, by which that round is measured (tests: a partial last round on a small world)
+        self.order_slots = int(getattr(env, '_pic_order_slots', 0) or 0)
+        self.order_tail = os.environ.get('DIE_PIC_ORDER_TAIL', '1') != '0'
         # the reference's default slot layout (max_agents = W·H: most slots never lived): the alive agents in the tiles' segments,
         # the dead slots behind them (include/die_hip.h `die_pic.n_alive`); `occ`: this step's occupancy map (a byte per cell) for their feeding
         self.n_alive = int(getattr(env, '_pic_n_alive', 0) or 0)
@@ -135,6 +140,10 @@ class PicState:
         L[cur].slot, L[1 - cur].slot = ct[3].data_ptr(), ot[3].data_ptr()
         p.N, p.k1_threads, p.stages, p.status_out = self._n_agents, self.k1_threads, stages, status_out
         return p
+
+    def _order_flags(self) -> int:
+        """die_pic.order_ready (include/die_hip.h): DIE_PIC_ORDER_READY | DIE_PIC_ORDER_NO_TAIL | slots << DIE_PIC_ORDER_SLOTS_SHIFT."""
+        return int(self._order_ready) | (0 if self.order_tail else _lib.PIC_ORDER_NO_TAIL) | (self.order_slots << _lib.PIC_ORDER_SLOTS_SHIFT)
 
     def two_launch(self, env, agent) -> bool:
         """Does die_pic_forward_env_step take the two-launch form for this agent?  (The library decides by the same rule;
@@ -280,7 +289,7 @@ class PicState:
             p = self._struct(self.held, out, stages, status_out if two else None)
             p.halo_fresh = int(item[2]) if len(item) > 2 else 0      # (the agent kernel behind a refresh in place: die_pic_ghost_inplace)
             p.turn_ready = int(self._turn_for == turn_key)
-            p.order_ready = int(self._order_ready)
+            p.order_ready = self._order_flags()
             p.sub_mode, p.sub_tx0, p.sub_ty0, p.sub_ntx, p.sub_nty = sub if sub is not None else (0, 0, 0, 0, 0)
             if events is not None:
                 events[i].record()
@@ -320,7 +329,7 @@ class PicState:
         two = self.two_launch(env, agent)
         p = self._struct(held, out, 0, None)
         p.turn_ready = int(self._turn_for == turn_key)
-        p.order_ready = int(self._order_ready)
+        p.order_ready = self._order_flags()
         p.sub_mode, p.sub_tx0, p.sub_ty0, p.sub_ntx, p.sub_nty, p.halo_fresh = 0, 0, 0, 0, 0, 0
         m = env.medium.c_struct(need_owner=False)
         rc = _lib.lib.die_pic_run(C.byref(m), C.byref(p), self.cur, C.byref(g), C.byref(dyn), int(n), _ptr(results), stream_ptr(env.device))

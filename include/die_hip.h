@@ -517,7 +517,17 @@ typedef struct die_pic {
      * tiles whose rim lists overflow — no longer make up a launch's tail: 166 -> 144 us per step at world step 3 000 of the benchmark
      * world (round 6).  Used when tiles-per-row % 8 == 0, tiles <= 65 536, an undivided world, all tiles in one launch; ignored otherwise.
      * The caller allocates die_pic_tiles() 16-bit words (4-byte aligned) and sets order_ready = 1 once a step has run with them (the
-     * table stays a valid permutation across re-binning: it is only stale then). */
+     * table stays a valid permutation across re-binning: it is only stale then).
+     *   Below the crowd threshold the table keeps band order except for every band's share of the launch's last, partial round of agent-kernel
+     * workgroups: those last places take the band's LIGHTEST tiles, in band order among themselves (the tail form; see k_pic_order).  The
+     * round is measured in `slots`, the workgroups the device holds at once (CUs x resident workgroups of the agent kernel launched), which
+     * the library asks of the runtime; no tail is shaped when tiles % slots is 0 or above 7/8 of slots.
+     *   order_ready is a word of flags — 0 and 1 mean what they meant before: DIE_PIC_ORDER_READY as above; DIE_PIC_ORDER_NO_TAIL keeps band
+     * order below the crowd threshold; a value s > 0 in the bits from DIE_PIC_ORDER_SLOTS_SHIFT up takes the place of the runtime's `slots`
+     * (tests: a partial last round on a small world). */
+#define DIE_PIC_ORDER_READY 1
+#define DIE_PIC_ORDER_NO_TAIL 2
+#define DIE_PIC_ORDER_SLOTS_SHIFT 8
     int32_t order_ready;
     uint16_t* order;
     /* ONE launch (stages = 1 or 2) over a subset of the tiles: sub_mode 0 all tiles; 1 only the rectangle [sub_tx0, sub_tx0 +
