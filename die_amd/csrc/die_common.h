@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <string.h>
+#include <math.h>
 #include "../../include/die_hip.h"
 
 #define DIE_WAVE 64
@@ -129,6 +131,39 @@ __device__ __forceinline__ long long die_fix(float g) {
     const float t = g * 4294967296.0f;                       // exact (power-of-two scaling)
     if (fabsf(t) < 2147483520.0f) return (long long)__float2int_rn(t);
     return __double2ll_rn((double)g * DIE_FIX_ONE);
+}
+
+// np.isclose(0, x, rtol, atol): x <= atol + rtol·x as numpy evaluates it — the product rounded, then the sum (never one fma)
+__host__ __device__ inline bool die_isclose_ok(double x, double atol, double rtol) {
+#ifdef __HIP_DEVICE_COMPILE__
+    const double m = __dmul_rn(rtol, x), s = __dadd_rn(atol, m);
+#else
+    volatile double m = rtol * x;
+    volatile double s = atol + m;
+#endif
+    return x <= s;
+}
+
+// Largest x >= 0 that np.isclose(0, x, rtol, atol) accepts (core/agent/gradient.py:177-178).  The accepted set is an interval
+// [0, X] (for rtol < 1 the right-hand side grows a hundred times slower than x), so X is found by bisection over the bit patterns
+// of the non-negative doubles — a kernel then decides with ONE comparison per test, and the tie at the threshold falls exactly
+// where numpy puts it.  Host (die_fill_fwd_args) and device (k_physarum_decode) run this one function.
+__host__ __device__ inline double die_isclose_bound(double atol, double rtol) {
+    if (!die_isclose_ok(0.0, atol, rtol)) return -1.0;
+    if (!(rtol < 1.0)) return HUGE_VAL;
+    const double top = 2.0 * atol / (1.0 - rtol) + 1e-300;
+    if (die_isclose_ok(top, atol, rtol)) return HUGE_VAL;
+    uint64_t lo = 0, hi;
+    memcpy(&hi, &top, 8);
+    while (hi - lo > 1) {                       // ok(lo), !ok(hi); the distance halves: 64 rounds at most
+        const uint64_t mid = lo + (hi - lo) / 2;
+        double x;
+        memcpy(&x, &mid, 8);
+        if (die_isclose_ok(x, atol, rtol)) lo = mid; else hi = mid;
+    }
+    double x;
+    memcpy(&x, &lo, 8);
+    return x;
 }
 
 // "no agent on this cell" in the deposit plane of the tile-binned step (a NaN no deposit can carry)

@@ -1279,22 +1279,30 @@ extern "C" int die_dynamics_rows(const die_dynamics* d, int32_t n, int32_t W, in
     return DIE_OK;
 }
 
+// what every fused sweep takes from the medium and the dynamics (R: the gaussian radius of d->diffuse_sigma); the caller sets the
+// rest: dep, halo, rep_cells, the wrap flags, the partials and the result
+static RowsArgs rows_args_of(const die_medium* m, const die_dynamics* d, int R) {
+    RowsArgs ra;
+    double wd[2 * DIF_MAXR + 1];
+    gaussian_taps(d->diffuse_sigma, wd);
+    ra.src = m->chem; ra.dst = m->chem_next; ra.claim = (const unsigned long long*)m->owner; ra.food = m->food;
+    ra.W = m->W; ra.H = m->H; ra.epoch = m->epoch; ra.food_infinite = d->food_infinite;
+    ra.keep = (float)(1.0 - (double)d->rate_decay_chem); ra.rate_feed = d->rate_feed;
+    for (int k = 0; k <= 2 * R; ++k) ra.w[k] = (float)wd[k];
+    return ra;
+}
+
 // the field sweep of every replica in one launch (gridDim.z), each with its own reduction workgroup over the n_part partials
 // (and, with dead slots, over the lifecycle pass's n_part partial gains too)
 static int batch_sweep(const die_medium* m, const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws, int n_part,
                        hipStream_t s, const char* who, const die_dynamics_row* rows = nullptr, const die_dynamics_row* rows_host = nullptr) {
     const int R = (int)(4.0 * (double)d->diffuse_sigma + 0.5);
-    RowsArgs ra;
-    double wd[2 * DIF_MAXR + 1];
-    gaussian_taps(d->diffuse_sigma, wd);
-    ra.src = m->chem; ra.dst = m->chem_next; ra.claim = (const unsigned long long*)m->owner; ra.dep = nullptr; ra.food = m->food;
-    ra.W = m->W; ra.H = m->H; ra.epoch = m->epoch; ra.food_infinite = d->food_infinite; ra.halo = 0; ra.rep_cells = b->plane_stride;
+    RowsArgs ra = rows_args_of(m, d, R);
+    ra.dep = nullptr; ra.halo = 0; ra.rep_cells = b->plane_stride;
     ra.wrapx = ra.wrapy = 1;
     ra.part_gain = (const long long*)ws; ra.part_alive = (const long long*)ws + 2 * DIE_MAX_PARTIALS; ra.n_part = n_part;
     ra.part_gain2 = d->agents_die || d->has_dead_slots ? (const long long*)ws + DIE_MAX_PARTIALS : nullptr;
     ra.result = results; ra.alive_const = 0;
-    ra.keep = (float)(1.0 - (double)d->rate_decay_chem); ra.rate_feed = d->rate_feed;
-    for (int q = 0; q <= 2 * R; ++q) ra.w[q] = (float)wd[q];
     if (rows) return batch_sweep_rows(m, ra, b, s, who, rows, rows_host);
     const int rc = m->dtype == DIE_F32 ? launch_rows<float, 1, true>(ra, R, s, b->replicas) : launch_rows<__half, 1, true>(ra, R, s, b->replicas);
     if (rc != DIE_OK) return rc;
@@ -1521,15 +1529,10 @@ static int deposit_feed_diffuse(const die_medium* m, const die_dynamics* d, int 
                       (double)d->diffuse_sigma, halo);
         return DIE_ERR_UNSUPPORTED;
     }
-    RowsArgs ra;
-    double wd[2 * DIF_MAXR + 1];
-    gaussian_taps(d->diffuse_sigma, wd);
-    ra.src = m->chem; ra.dst = m->chem_next; ra.claim = (const unsigned long long*)m->owner; ra.dep = dep_plane; ra.food = m->food;
-    ra.W = m->W; ra.H = m->H; ra.epoch = m->epoch; ra.food_infinite = d->food_infinite; ra.halo = halo; ra.rep_cells = 0;
+    RowsArgs ra = rows_args_of(m, d, R);
+    ra.dep = dep_plane; ra.halo = halo; ra.rep_cells = 0;
     ra.wrapx = tile && m->gW > 0 && m->W == m->gW; ra.wrapy = tile && m->gW > 0 && m->H == m->gH;
     ra.part_gain = part_gain; ra.part_gain2 = nullptr; ra.part_alive = part_alive; ra.n_part = n_part; ra.result = result; ra.alive_const = alive_const;
-    ra.keep = (float)(1.0 - (double)d->rate_decay_chem); ra.rate_feed = d->rate_feed;
-    for (int k = 0; k <= 2 * R; ++k) ra.w[k] = (float)wd[k];
     int rc;
     if (dep_plane) {
         DIE_REQUIRE(!tile, "%s: the deposit-plane sweep is for periodic single-tile planes", who);

@@ -6,6 +6,8 @@
 //                   agents_from_medium (:133-150): stream compaction of the occupied cells in
 //                   row-major order into slots [0, K) — three passes, 4096 cells per workgroup
 //   k_init_heading  _get_some_noise → get_radians → discretize
+// Every computation is one device body (init_cell, count_tile, scan_blocks, scatter_tile, zero_tail, init_heading_one, flow_wave_z /
+// flow_perlin_z / flow_mix) that the stand-alone kernel and its batched twin (replica in blockIdx.y) both call.
 #include "die_common.h"
 #include "die_rng.h"
 
@@ -39,29 +41,44 @@ __device__ __forceinline__ float init_food_value(const die_geo& g, const FoodArg
     return (float)(rint(s * 1000.0) / 1000.0);   // .round(3) (:196)
 }
 
-template <typename T>
-__global__ __launch_bounds__(DIE_BLOCK) void k_init_medium(die_geo g, uint64_t* owner, T* food, T* chem, double ratio,
-                                                           uint64_t seed, FoodArgs fa) {
-    const int W = g.W, H = g.H;
-    const int64_t C = (int64_t)W * H;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < C; c += stride) {
-        // ceil(u·[0 ≤ u ≤ ratio]) with u = random_sample().round(3): occupied iff 0 < u ≤ ratio
-        // world cell of this element (a decomposed tile's halo wraps around the world)
-        const int lx = (int)(c / H), ly = (int)(c - (int64_t)lx * H);
-        int ix = (lx + g.ox) % g.gW, iy = (ly + g.oy) % g.gH;
+// world cell (ix, iy) of element c of the planes of `g`: a decomposed tile's halo wraps around the world (a whole world: ix = c / H,
+// iy = c % H, which TILE = false states without the division by the world size)
+template <bool TILE>
+__device__ __forceinline__ void world_cell(const die_geo& g, int64_t c, int& ix, int& iy) {
+    const int lx = (int)(c / g.H), ly = (int)(c - (int64_t)lx * g.H);
+    ix = lx; iy = ly;
+    if (TILE) {
+        ix = (lx + g.ox) % g.gW; iy = (ly + g.oy) % g.gH;
         ix = ix < 0 ? ix + g.gW : ix;
         iy = iy < 0 ? iy + g.gH : iy;
-        const uint64_t gc = (uint64_t)ix * (uint64_t)g.gH + (uint64_t)iy;
-        const int r = die_round3_units(die_draw(seed, 0, gc, DIE_STREAM_INIT_AGENTS).v[0]);
-        const double u = r / 1000.0;
-        owner[c] = (r > 0 && u <= ratio) ? 1ull : 0ull;    // provisional flag; k_scatter writes the claim word
-        die_st(food, c, init_food_value(g, fa, seed, ix, iy));
-        die_st(chem, c, 0.f);
     }
 }
 
-__global__ __launch_bounds__(DIE_BLOCK) void k_count(const uint64_t* flag, int64_t C, int32_t* block_sum) {
+// element c of the three planes of `g` under `seed`: the occupancy flag, the food value, zero chem
+template <bool TILE, typename T>
+__device__ __forceinline__ void init_cell(const die_geo& g, uint64_t* owner, T* food, T* chem, double ratio, uint64_t seed,
+                                          const FoodArgs& fa, int64_t c) {
+    int ix, iy;
+    world_cell<TILE>(g, c, ix, iy);
+    // ceil(u·[0 ≤ u ≤ ratio]) with u = random_sample().round(3): occupied iff 0 < u ≤ ratio
+    const uint64_t gc = (uint64_t)ix * (uint64_t)g.gH + (uint64_t)iy;
+    const int r = die_round3_units(die_draw(seed, 0, gc, DIE_STREAM_INIT_AGENTS).v[0]);
+    const double u = r / 1000.0;
+    owner[c] = (r > 0 && u <= ratio) ? 1ull : 0ull;    // provisional flag; scatter_tile writes the claim word
+    die_st(food, c, init_food_value(g, fa, seed, ix, iy));
+    die_st(chem, c, 0.f);
+}
+
+template <typename T>
+__global__ __launch_bounds__(DIE_BLOCK) void k_init_medium(die_geo g, uint64_t* owner, T* food, T* chem, double ratio,
+                                                           uint64_t seed, FoodArgs fa) {
+    const int64_t C = (int64_t)g.W * g.H;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < C; c += stride) init_cell<true>(g, owner, food, chem, ratio, seed, fa, c);
+}
+
+// the occupied cells of scan tile blockIdx.x → block_sum[blockIdx.x]
+__device__ __forceinline__ void count_tile(const uint64_t* flag, int64_t C, int32_t* block_sum) {
     const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
     int cnt = 0;
 #pragma unroll
@@ -76,9 +93,10 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_count(const uint64_t* flag, int64
     if (threadIdx.x == 0) block_sum[blockIdx.x] = s[0];
 }
 
-// single workgroup: exclusive scan of nb block sums → block_off (int64), total → *total
-__global__ __launch_bounds__(DIE_BLOCK) void k_scan_blocks(const int32_t* block_sum, int nb, int64_t* block_off,
-                                                            int64_t* total, int64_t capacity) {
+// one workgroup: exclusive scan of nb block sums → block_off (int64); total[0] = min(K, capacity); total[1], the overflow word
+// (more agents than slots), is assigned 0 / 1, or with STICKY only ever set (|= 1 on overflow, never cleared here)
+template <bool STICKY>
+__device__ __forceinline__ void scan_blocks(const int32_t* block_sum, int nb, int64_t* block_off, int64_t* total, int64_t capacity) {
     __shared__ long long s[DIE_BLOCK];
     const int per = (nb + DIE_BLOCK - 1) / DIE_BLOCK;
     const int lo = threadIdx.x * per, hi = min(lo + per, nb);
@@ -90,16 +108,19 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_scan_blocks(const int32_t* block_
         long long run = 0;
         for (int i = 0; i < DIE_BLOCK; ++i) { long long v = s[i]; s[i] = run; run += v; }
         total[0] = run < capacity ? run : capacity;
-        total[1] = run > capacity ? 1 : 0;           // overflow flag: more agents than slots
+        if (STICKY) { if (run > capacity) total[1] |= 1; }
+        else total[1] = run > capacity ? 1 : 0;
     }
     __syncthreads();
     long long run = s[threadIdx.x];
     for (int i = lo; i < hi; ++i) { block_off[i] = run; run += block_sum[i]; }
 }
 
-__global__ __launch_bounds__(DIE_BLOCK) void k_scatter(die_geo g, uint64_t* owner, const int64_t* block_off, int64_t N,
-                                                       uint32_t* x, uint32_t* y, uint8_t* alive, float* agent_food,
-                                                       uint64_t seed) {
+// the occupied cells of scan tile blockIdx.x, in row-major order, into slots block_off[blockIdx.x] … (below N: the rest are clipped)
+// (the geometry by value: through a reference the compiler converts W − 1 and gH − 1 to double once per cell, not once)
+template <bool TILE>
+__device__ __forceinline__ void scatter_tile(const die_geo g, uint64_t* owner, const int64_t* block_off, int64_t N, uint32_t* x,
+                                             uint32_t* y, uint8_t* alive, float* agent_food, uint64_t seed) {
     const int H = g.H, W = g.gW;             // labels are world coordinates: linspace(0, 1, gW)
     const int64_t C = (int64_t)g.W * g.H;
     const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
@@ -124,7 +145,7 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_scatter(die_geo g, uint64_t* owne
         if (flags & (1 << i)) {
             if (k < N) {
                 const int lx = (int)(c / H), ly = (int)(c - (int64_t)lx * H);
-                const int ix = lx + g.ox, iy = ly + g.oy;
+                const int ix = TILE ? lx + g.ox : lx, iy = TILE ? ly + g.oy : ly;
                 // x = linspace(0, 1, W)[ix] in Q0.32; the last label 1.0 is held as 2^32 − 1
                 const double qx = W > 1 ? (double)ix / (double)(W - 1) * 4294967296.0 : 0.0;
                 const double qy = g.gH > 1 ? (double)iy / (double)(g.gH - 1) * 4294967296.0 : 0.0;
@@ -144,31 +165,56 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_scatter(die_geo g, uint64_t* owne
     }
 }
 
-__global__ __launch_bounds__(DIE_BLOCK) void k_zero_tail(const int64_t* total, int64_t N, uint32_t* x, uint32_t* y,
-                                                         uint8_t* alive, float* agent_food) {
-    const int64_t K = total[0];
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t n = K + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += stride) {
+// slots K … N − 1: nobody.  (The caller's thread index and grid stride come as arguments: blockDim read in a device function
+// compiles to the form that allows a partial last workgroup, one more load at the head of the kernel.)
+__device__ __forceinline__ void zero_tail(int64_t K, int64_t N, int64_t thread, int64_t stride, uint32_t* x, uint32_t* y, uint8_t* alive,
+                                          float* agent_food) {
+    for (int64_t n = K + thread; n < N; n += stride) {
         x[n] = 0; y[n] = 0; alive[n] = 0; agent_food[n] = 0.f;
     }
+}
+
+__global__ __launch_bounds__(DIE_BLOCK) void k_count(const uint64_t* flag, int64_t C, int32_t* block_sum) { count_tile(flag, C, block_sum); }
+
+__global__ __launch_bounds__(DIE_BLOCK) void k_scan_blocks(const int32_t* block_sum, int nb, int64_t* block_off,
+                                                            int64_t* total, int64_t capacity) {
+    scan_blocks<false>(block_sum, nb, block_off, total, capacity);
+}
+
+__global__ __launch_bounds__(DIE_BLOCK) void k_scatter(die_geo g, uint64_t* owner, const int64_t* block_off, int64_t N,
+                                                       uint32_t* x, uint32_t* y, uint8_t* alive, float* agent_food,
+                                                       uint64_t seed) {
+    scatter_tile<true>(g, owner, block_off, N, x, y, alive, agent_food, seed);
+}
+
+__global__ __launch_bounds__(DIE_BLOCK) void k_zero_tail(const int64_t* total, int64_t N, uint32_t* x, uint32_t* y,
+                                                         uint8_t* alive, float* agent_food) {
+    zero_tail(total[0], N, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x, x, y, alive, agent_food);
+}
+
+// slot n's heading under `seed`: the float64 state (hi, lo words) and the Box–Muller pair (gx, gy) behind it
+__device__ __forceinline__ void init_heading_one(uint64_t seed, int64_t n, double turn, uint32_t* hi, uint32_t* lo, float* pgx, float* pgy) {
+    const die_u32x4 r = die_draw(seed, 0, (uint64_t)n, DIE_STREAM_INIT_HEADING);
+    // Box–Muller pair: its polar angle is 2π·u2, wrapped to (−π, π] like np.angle
+    const double u1 = ((double)r.v[0] + 1.0) * (1.0 / 4294967296.0);
+    const double u2 = (double)r.v[1] * (1.0 / 4294967296.0);
+    const double rad = 0.4 * sqrt(-2.0 * log(u1));
+    const double gx = rad * cos(6.283185307179586476925 * u2), gy = rad * sin(6.283185307179586476925 * u2);
+    double ang = atan2(gy, gx);
+    if (turn > 0.0) ang = floor(ang / turn) * turn;      // discretize (core/utils.py:183-184)
+    const double h = (double)(float)ang;                 // float64 state holding the fp32 rounding of the lattice angle
+    *hi = (uint32_t)__double2hiint(h);
+    *lo = (uint32_t)__double2loint(h);
+    *pgx = (float)gx; *pgy = (float)gy;
 }
 
 __global__ __launch_bounds__(DIE_BLOCK) void k_init_heading(uint32_t* hhi, uint32_t* hlo, float* pgx, float* pgy, int64_t N, double turn,
                                                             uint64_t seed) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += stride) {
-        const die_u32x4 r = die_draw(seed, 0, (uint64_t)n, DIE_STREAM_INIT_HEADING);
-        // Box–Muller pair: its polar angle is 2π·u2, wrapped to (−π, π] like np.angle
-        const double u1 = ((double)r.v[0] + 1.0) * (1.0 / 4294967296.0);
-        const double u2 = (double)r.v[1] * (1.0 / 4294967296.0);
-        const double rad = 0.4 * sqrt(-2.0 * log(u1));
-        const double gx = rad * cos(6.283185307179586476925 * u2), gy = rad * sin(6.283185307179586476925 * u2);
-        double ang = atan2(gy, gx);
-        if (turn > 0.0) ang = floor(ang / turn) * turn;      // discretize (core/utils.py:183-184)
-        const double h = (double)(float)ang;                 // float64 state holding the fp32 rounding of the lattice angle
-        hhi[n] = (uint32_t)__double2hiint(h);
-        hlo[n] = (uint32_t)__double2loint(h);
-        if (pgx) { pgx[n] = (float)gx; pgy[n] = (float)gy; }
+        float gx, gy;
+        init_heading_one(seed, n, turn, &hhi[n], &hlo[n], &gx, &gy);
+        if (pgx) { pgx[n] = gx; pgy[n] = gy; }
     }
 }
 
@@ -189,23 +235,25 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_init_heading_batch(uint32_t* hhi,
     hhi += b.agents * r; hlo += b.agents * r;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += stride) {
-        // k_init_heading's expressions, restated (that kernel stays as it is)
-        const die_u32x4 q = die_draw(seed, 0, (uint64_t)n, DIE_STREAM_INIT_HEADING);
-        const double u1 = ((double)q.v[0] + 1.0) * (1.0 / 4294967296.0);
-        const double u2 = (double)q.v[1] * (1.0 / 4294967296.0);
-        const double rad = 0.4 * sqrt(-2.0 * log(u1));
-        const double gx = rad * cos(6.283185307179586476925 * u2), gy = rad * sin(6.283185307179586476925 * u2);
-        double ang = atan2(gy, gx);
-        if (turn > 0.0) ang = floor(ang / turn) * turn;
-        const double h = (double)(float)ang;
-        hhi[n] = (uint32_t)__double2hiint(h);
-        hlo[n] = (uint32_t)__double2loint(h);
+        float gx, gy;                                    // (a population keeps no previous gradient: the pair is dropped)
+        init_heading_one(seed, n, turn, &hhi[n], &hlo[n], &gx, &gy);
     }
 }
 
 static int init_grid(int64_t n) {
     int64_t g = (n + DIE_BLOCK - 1) / DIE_BLOCK;
     return (int)(g < 8192 ? (g > 0 ? g : 1) : 8192);
+}
+
+// the kernels' copy of a die_food_spec whose n_waves the caller has checked (both callers check it ahead of other arguments)
+static int food_args_of(const char* who, const die_food_spec* food, FoodArgs* fa) {
+    DIE_REQUIRE(food->perlin_octaves >= 0 && food->perlin_octaves < (1 << 19), "%s: bad perlin_octaves %d", who, food->perlin_octaves);
+    fa->n_waves = food->n_waves;
+    fa->scale = food->scale;
+    fa->perlin_octaves = food->perlin_octaves;
+    fa->threshold = food->threshold;
+    for (int i = 0; i < 8; ++i) { fa->fx[i] = food->fx[i]; fa->fy[i] = food->fy[i]; fa->phase[i] = food->phase[i]; fa->amp[i] = food->amp[i]; }
+    return DIE_OK;
 }
 
 int64_t die_ws_scan_bytes(int32_t W, int32_t H) {
@@ -220,12 +268,8 @@ extern "C" int die_init_medium(const die_medium* m, double agent_ratio, uint64_t
     DIE_REQUIRE(food->n_waves >= 0 && food->n_waves <= 8, "die_init_medium: n_waves %d outside 0..8", food->n_waves);
     DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "die_init_medium: bad dtype %d", m->dtype);
     FoodArgs fa;
-    fa.n_waves = food->n_waves;
-    fa.scale = food->scale;
-    fa.perlin_octaves = food->perlin_octaves;
-    fa.threshold = food->threshold;
-    DIE_REQUIRE(food->perlin_octaves >= 0 && food->perlin_octaves < (1 << 19), "die_init_medium: bad perlin_octaves %d", food->perlin_octaves);
-    for (int i = 0; i < 8; ++i) { fa.fx[i] = food->fx[i]; fa.fy[i] = food->fy[i]; fa.phase[i] = food->phase[i]; fa.amp[i] = food->amp[i]; }
+    const int rc = food_args_of("die_init_medium", food, &fa);
+    if (rc != DIE_OK) return rc;
     const int grid = init_grid((int64_t)m->W * m->H);
     if (m->dtype == DIE_F32)
         k_init_medium<float><<<grid, DIE_BLOCK, 0, (hipStream_t)stream>>>(die_geo_of(m), m->owner, (float*)m->food,
@@ -290,9 +334,8 @@ extern "C" int die_physarum_heading_batch(uint32_t* heading_hi, uint32_t* headin
 // ---- the worlds of every replica of a die_batch (BatchedEnv.reset(seed=...) / reset(seeds=...)) ------------------------
 // Replica r (blockIdx.y) is die_init_medium + die_init_agents of seed[r] on its own planes and agent arrays (die_init_batch:
 // seed + r·world_stride, worked out on the host; die_init_batch_seeds: the caller's list, passed by value):
-// the kernels below restate k_init_medium / k_count / k_scan_blocks / k_scatter / k_zero_tail with the replica's offsets
-// (a replica's plane is a whole world: no tile offsets), so every value is computed by the same expressions.  The scan
-// workspace of replica r is its own die_ws_scan_bytes slice.
+// the kernels below hand init_cell / count_tile / scan_blocks / scatter_tile / zero_tail the replica's pointers (a replica's
+// plane is a whole world: no tile offsets).  The scan workspace of replica r is its own die_ws_scan_bytes slice.
 struct InitBatchArgs {
     int64_t cells, agents;          // strides: cells per plane, agent slots per replica
     uint64_t seed[DIE_MAX_REPLICAS];    // the world of every replica
@@ -301,129 +344,47 @@ struct InitBatchArgs {
     int64_t n[DIE_MAX_REPLICAS];    // slots of every replica
 };
 
+// the block sums and the block offsets in replica r's slice of the scan workspace
+__device__ __forceinline__ int32_t* ws_block_sum(char* ws, const InitBatchArgs& b, int r) { return (int32_t*)(ws + b.ws_stride * r); }
+__device__ __forceinline__ int64_t* ws_block_off(char* ws, const InitBatchArgs& b, int r) {
+    return (int64_t*)(ws + b.ws_stride * r + ((b.nb * 4 + 255) & ~(int64_t)255));
+}
+
 template <typename T>
 __global__ __launch_bounds__(DIE_BLOCK) void k_init_medium_batch(die_geo g, uint64_t* owner, T* food, T* chem, double ratio,
                                                                  FoodArgs fa, InitBatchArgs b) {
     const int r = blockIdx.y;
     const uint64_t sr = b.seed[r];
     owner += b.cells * r; food += b.cells * r; chem += b.cells * r;
-    const int H = g.H;
-    const int64_t C = (int64_t)g.W * H;
+    const int64_t C = (int64_t)g.W * g.H;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < C; c += stride) {
-        const int ix = (int)(c / H), iy = (int)(c - (int64_t)ix * H);
-        const uint64_t gc = (uint64_t)ix * (uint64_t)g.gH + (uint64_t)iy;
-        const int q = die_round3_units(die_draw(sr, 0, gc, DIE_STREAM_INIT_AGENTS).v[0]);
-        const double u = q / 1000.0;
-        owner[c] = (q > 0 && u <= ratio) ? 1ull : 0ull;
-        die_st(food, c, init_food_value(g, fa, sr, ix, iy));
-        die_st(chem, c, 0.f);
-    }
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < C; c += stride) init_cell<false>(g, owner, food, chem, ratio, sr, fa, c);
 }
 
 __global__ __launch_bounds__(DIE_BLOCK) void k_count_batch(const uint64_t* flag, int64_t C, char* ws, InitBatchArgs b) {
     const int r = blockIdx.y;
-    flag += b.cells * r;
-    int32_t* block_sum = (int32_t*)(ws + b.ws_stride * r);
-    const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
-    int cnt = 0;
-#pragma unroll
-    for (int i = 0; i < SCAN_ITEMS; ++i) cnt += (base + i < C && flag[base + i] != 0) ? 1 : 0;
-    __shared__ int s[DIE_BLOCK];
-    s[threadIdx.x] = cnt;
-    __syncthreads();
-    for (int o = DIE_BLOCK / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) block_sum[blockIdx.x] = s[0];
+    count_tile(flag + b.cells * r, C, ws_block_sum(ws, b, r));
 }
 
 // one workgroup per replica: counts[2r] = min(K_r, n[r]), counts[2r + 1] |= 1 when K_r > n[r] (never cleared here)
 __global__ __launch_bounds__(DIE_BLOCK) void k_scan_blocks_batch(char* ws, int64_t* counts, InitBatchArgs b) {
     const int r = blockIdx.y;
-    const int nb = (int)b.nb;
-    const int32_t* block_sum = (const int32_t*)(ws + b.ws_stride * r);
-    int64_t* block_off = (int64_t*)(ws + b.ws_stride * r + ((b.nb * 4 + 255) & ~(int64_t)255));
-    const int64_t capacity = b.n[r];
-    __shared__ long long s[DIE_BLOCK];
-    const int per = (nb + DIE_BLOCK - 1) / DIE_BLOCK;
-    const int lo = threadIdx.x * per, hi = min(lo + per, nb);
-    long long t = 0;
-    for (int i = lo; i < hi; ++i) t += block_sum[i];
-    s[threadIdx.x] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long run = 0;
-        for (int i = 0; i < DIE_BLOCK; ++i) { long long v = s[i]; s[i] = run; run += v; }
-        counts[2 * r] = run < capacity ? run : capacity;
-        if (run > capacity) counts[2 * r + 1] |= 1;
-    }
-    __syncthreads();
-    long long run = s[threadIdx.x];
-    for (int i = lo; i < hi; ++i) { block_off[i] = run; run += block_sum[i]; }
+    scan_blocks<true>(ws_block_sum(ws, b, r), (int)b.nb, ws_block_off(ws, b, r), counts + 2 * r, b.n[r]);
 }
 
 __global__ __launch_bounds__(DIE_BLOCK) void k_scatter_batch(die_geo g, uint64_t* owner, const char* ws, uint32_t* x, uint32_t* y,
                                                              uint8_t* alive, float* agent_food, InitBatchArgs b) {
     const int r = blockIdx.y;
-    const uint64_t sr = b.seed[r];
     const int64_t pa = b.agents * r;
-    owner += b.cells * r;
-    x += pa; y += pa; alive += pa; agent_food += pa;
-    const int64_t* block_off = (const int64_t*)(ws + b.ws_stride * r + ((b.nb * 4 + 255) & ~(int64_t)255));
-    const int64_t N = b.n[r];
-    const int H = g.H, W = g.gW;
-    const int64_t C = (int64_t)g.W * g.H;
-    const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
-    int flags = 0, cnt = 0;
-#pragma unroll
-    for (int i = 0; i < SCAN_ITEMS; ++i)
-        if (base + i < C && owner[base + i] != 0) { flags |= 1 << i; ++cnt; }
-    __shared__ int s[DIE_BLOCK];
-    s[threadIdx.x] = cnt;
-    __syncthreads();
-    for (int o = 1; o < DIE_BLOCK; o <<= 1) {          // Hillis–Steele inclusive scan
-        int v = (int)threadIdx.x >= o ? s[threadIdx.x - o] : 0;
-        __syncthreads();
-        s[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int64_t k = block_off[blockIdx.x] + (s[threadIdx.x] - cnt);
-#pragma unroll
-    for (int i = 0; i < SCAN_ITEMS; ++i) {
-        const int64_t c = base + i;
-        if (c >= C) break;
-        if (flags & (1 << i)) {
-            if (k < N) {
-                const int ix = (int)(c / H), iy = (int)(c - (int64_t)ix * H);
-                const double qx = W > 1 ? (double)ix / (double)(W - 1) * 4294967296.0 : 0.0;
-                const double qy = g.gH > 1 ? (double)iy / (double)(g.gH - 1) * 4294967296.0 : 0.0;
-                const long long X = __double2ll_rn(qx), Y = __double2ll_rn(qy);
-                x[k] = (uint32_t)(X > 0xFFFFFFFFLL ? 0xFFFFFFFFLL : X);
-                y[k] = (uint32_t)(Y > 0xFFFFFFFFLL ? 0xFFFFFFFFLL : Y);
-                alive[k] = 1;
-                const int q = die_round3_units(die_draw(sr, 0, (uint64_t)k, DIE_STREAM_INIT_AGENT_FOOD).v[0]);
-                agent_food[k] = (float)(0.9 * (q / 1000.0) + 0.1);
-                owner[c] = die_claim(1, k, 0.f);
-            } else {
-                owner[c] = 0;
-            }
-            ++k;
-        }
-    }
+    scatter_tile<false>(g, owner + b.cells * r, ws_block_off((char*)ws, b, r), b.n[r], x + pa, y + pa, alive + pa, agent_food + pa, b.seed[r]);   // (read only)
 }
 
 __global__ __launch_bounds__(DIE_BLOCK) void k_zero_tail_batch(const int64_t* counts, uint32_t* x, uint32_t* y, uint8_t* alive,
                                                                float* agent_food, InitBatchArgs b) {
     const int r = blockIdx.y;
     const int64_t pa = b.agents * r;
-    x += pa; y += pa; alive += pa; agent_food += pa;
-    const int64_t K = counts[2 * r], N = b.n[r];
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t n = K + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += stride) {
-        x[n] = 0; y[n] = 0; alive[n] = 0; agent_food[n] = 0.f;
-    }
+    zero_tail(counts[2 * r], b.n[r], (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x, x + pa, y + pa, alive + pa,
+              agent_food + pa);
 }
 
 extern "C" int64_t die_init_batch_workspace_bytes(int32_t W, int32_t H, int32_t replicas) {
@@ -449,7 +410,9 @@ static int init_batch(const char* who, const die_medium* m, const die_agents* a,
         DIE_REQUIRE(b->n[r] >= 1 && b->n[r] <= b->agent_stride, "%s: replica %d has %lld slots, 1..%lld expected", who, r,
                     (long long)b->n[r], (long long)b->agent_stride);
     DIE_REQUIRE(food->n_waves >= 0 && food->n_waves <= 8, "%s: n_waves %d outside 0..8", who, food->n_waves);
-    DIE_REQUIRE(food->perlin_octaves >= 0 && food->perlin_octaves < (1 << 19), "%s: bad perlin_octaves %d", who, food->perlin_octaves);
+    FoodArgs fa;
+    const int rc = food_args_of(who, food, &fa);
+    if (rc != DIE_OK) return rc;
     // the sinusoid mix is drawn from the seed on the host: one spec is the food of one seed only
     DIE_REQUIRE(food->perlin_octaves > 0 || world_stride == 0, "%s: a wave-mix food spec (perlin_octaves 0) with world_stride %llu: "
                 "its waves belong to one seed", who, (unsigned long long)world_stride);
@@ -463,12 +426,6 @@ static int init_batch(const char* who, const die_medium* m, const die_agents* a,
     DIE_REQUIRE(need > 0, "%s: field too large", who);
     DIE_REQUIRE(ws_bytes >= need, "%s: workspace too small (%lld < %lld: die_init_batch_workspace_bytes)", who, (long long)ws_bytes,
                 (long long)need);
-    FoodArgs fa;
-    fa.n_waves = food->n_waves;
-    fa.scale = food->scale;
-    fa.perlin_octaves = food->perlin_octaves;
-    fa.threshold = food->threshold;
-    for (int i = 0; i < 8; ++i) { fa.fx[i] = food->fx[i]; fa.fy[i] = food->fy[i]; fa.phase[i] = food->phase[i]; fa.amp[i] = food->amp[i]; }
     const int64_t C = (int64_t)m->W * m->H;
     InitBatchArgs ib;
     ib.cells = b->plane_stride; ib.agents = b->agent_stride;
@@ -518,25 +475,30 @@ extern "C" int die_init_batch_seeds(const die_medium* m, const die_agents* a, co
 // food ← scale·z(x, y, t) + (1 − decay)·food with the reference's running-wave field z; x varies along the last
 // axis and y along the first (core/utils.py:113-118 builds the grid from the reversed sizes).  float64 arithmetic,
 // one rounding to the field dtype.  Tiles evaluate z at their world cells.
+// (gi, gj): the world cell's index along the first (W) and the second (H) axis
+__device__ __forceinline__ double flow_wave_z(int gi, int gj, int gW, int gH, double t) {
+    const double pi = 3.141592653589793;
+    // np.linspace(0, 1, n)[k] = k·(1/(n−1)); then (v − 0.5)·2
+    const double x = ((double)gj * (1.0 / (double)(gH - 1)) - 0.5) * 2.0;
+    const double y = ((double)gi * (1.0 / (double)(gW - 1)) - 0.5) * 2.0;
+    const double r = sqrt(x * x + y * y);
+    const double rwave = r + cos(pi * x) + sin(0.4 * pi * y);
+    const double z_waves = cos(1.0 * pi * (rwave + t));
+    const double z_islands = sin(pi * x * 3.0 + t) + cos(pi * y * 3.0 + t);
+    return (1.0 - 0.25) * z_waves + 0.25 * z_islands;
+}
+
+// the update of one cell holding v, in every flow kernel: one expression, so one rounding
+__device__ __forceinline__ float flow_mix(double scale, double z, double keep, float v) { return (float)(scale * z + keep * (double)v); }
+
 template <typename T>
 __global__ __launch_bounds__(DIE_BLOCK) void k_food_flow_wave(T* food, die_geo g, double t, double scale, double keep) {
     const int64_t total = (int64_t)g.W * g.H;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const double pi = 3.141592653589793;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        const int li = (int)(i / g.H), lj = (int)(i - (int64_t)li * g.H);
-        int gi = (li + g.ox) % g.gW, gj = (lj + g.oy) % g.gH;
-        gi = gi < 0 ? gi + g.gW : gi;
-        gj = gj < 0 ? gj + g.gH : gj;
-        // np.linspace(0, 1, n)[k] = k·(1/(n−1)); then (v − 0.5)·2
-        const double x = ((double)gj * (1.0 / (double)(g.gH - 1)) - 0.5) * 2.0;
-        const double y = ((double)gi * (1.0 / (double)(g.gW - 1)) - 0.5) * 2.0;
-        const double r = sqrt(x * x + y * y);
-        const double rwave = r + cos(pi * x) + sin(0.4 * pi * y);
-        const double z_waves = cos(1.0 * pi * (rwave + t));
-        const double z_islands = sin(pi * x * 3.0 + t) + cos(pi * y * 3.0 + t);
-        const double z = (1.0 - 0.25) * z_waves + 0.25 * z_islands;
-        die_st(food, i, (float)(scale * z + keep * (double)die_ld(food, i)));
+        int gi, gj;
+        world_cell<true>(g, i, gi, gj);
+        die_st(food, i, flow_mix(scale, flow_wave_z(gi, gj, g.gW, g.gH, t), keep, die_ld(food, i)));
     }
 }
 
@@ -557,18 +519,20 @@ extern "C" int die_food_flow_wave(const die_medium* m, double t, double scale, d
 // PerlinNoiseSequence.__getitem__ (core/data_init.py:55-69) inside FieldSequence.get_flow_operator (:29-38):
 // food ← scale · round(noise((x, y, t)), 3) + (1 − decay) · food with x, y the linspace(0, 1, n) labels of the world cell and
 // `noise` the 3-D gradient noise at (x, y, t) · octaves.
+// (flatten: die_perlin3 is inlined here; called, it costs 32 B of scratch per lane)
+__device__ __forceinline__ __attribute__((flatten)) double flow_perlin_z(int gi, int gj, int gW, int gH, double t, double octaves, uint64_t seed) {
+    const double x = (double)gi / (double)(gW - 1), y = (double)gj / (double)(gH - 1);
+    return rint(die_perlin3(seed, x * octaves, y * octaves, t * octaves) * 1000.0) / 1000.0;
+}
+
 template <typename T>
 __global__ __launch_bounds__(DIE_BLOCK) void k_food_flow_perlin(T* food, die_geo g, double t, double octaves, double scale, double keep, uint64_t seed) {
     const int64_t total = (int64_t)g.W * g.H;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        const int li = (int)(i / g.H), lj = (int)(i - (int64_t)li * g.H);
-        int gi = (li + g.ox) % g.gW, gj = (lj + g.oy) % g.gH;
-        gi = gi < 0 ? gi + g.gW : gi;
-        gj = gj < 0 ? gj + g.gH : gj;
-        const double x = (double)gi / (double)(g.gW - 1), y = (double)gj / (double)(g.gH - 1);
-        const double z = rint(die_perlin3(seed, x * octaves, y * octaves, t * octaves) * 1000.0) / 1000.0;
-        die_st(food, i, (float)(scale * z + keep * (double)die_ld(food, i)));
+        int gi, gj;
+        world_cell<true>(g, i, gi, gj);
+        die_st(food, i, flow_mix(scale, flow_perlin_z(gi, gj, g.gW, g.gH, t, octaves, seed), keep, die_ld(food, i)));
     }
 }
 
@@ -591,27 +555,8 @@ extern "C" int die_food_flow_perlin(const die_medium* m, double t, int32_t octav
 // thread per cell evaluates z once and updates that cell in every plane, issuing a chunk's loads before its first store.
 // (One cell per thread, not a 4-cell vector: at 96² that is 36 workgroups instead of 9 to share the float64 field; the
 // planes themselves are small.)
-// A replica's plane is a whole world: gW = W, gH = H, no offsets.  The expressions restate those of k_food_flow_wave /
-// k_food_flow_perlin token for token (the library contracts a·b + c only inside one expression, so equal expressions
-// round alike); they are not shared with those kernels because hoisting them into a helper changed the old kernels' code.
-// (gi, gj): the cell's index along the first (W) and the second (H) axis.
-__device__ __forceinline__ double flow_wave_z(int gi, int gj, int gW, int gH, double t) {
-    const double pi = 3.141592653589793;
-    const double x = ((double)gj * (1.0 / (double)(gH - 1)) - 0.5) * 2.0;      // x along H, y along W, as k_food_flow_wave
-    const double y = ((double)gi * (1.0 / (double)(gW - 1)) - 0.5) * 2.0;
-    const double r = sqrt(x * x + y * y);
-    const double rwave = r + cos(pi * x) + sin(0.4 * pi * y);
-    const double z_waves = cos(1.0 * pi * (rwave + t));
-    const double z_islands = sin(pi * x * 3.0 + t) + cos(pi * y * 3.0 + t);
-    return (1.0 - 0.25) * z_waves + 0.25 * z_islands;
-}
-
-// (flatten: die_perlin3 is inlined here; called, as the one-plane kernel calls it, it costs 32 B of scratch per lane)
-__device__ __forceinline__ __attribute__((flatten)) double flow_perlin_z(int gi, int gj, int gW, int gH, double t, double octaves, uint64_t seed) {
-    const double x = (double)gi / (double)(gW - 1), y = (double)gj / (double)(gH - 1);      // x along W, as k_food_flow_perlin
-    return rint(die_perlin3(seed, x * octaves, y * octaves, t * octaves) * 1000.0) / 1000.0;
-}
-
+// A replica's plane is a whole world: gW = W, gH = H, no offsets; the field is flow_wave_z / flow_perlin_z and the update
+// flow_mix, as in k_food_flow_wave / k_food_flow_perlin.
 // Loads in flight per thread.  Replicas past the last one of a chunk re-load the last plane (in bounds) and store nothing.
 #define FLOW_BATCH_CHUNK 16
 
@@ -629,7 +574,7 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_food_flow_batch(T* food, int W, i
             for (int q = 0; q < FLOW_BATCH_CHUNK; ++q) v[q] = die_ld(food + (int64_t)min(r0 + q, R - 1) * plane_stride, i);
 #pragma unroll
             for (int q = 0; q < FLOW_BATCH_CHUNK; ++q)
-                if (r0 + q < R) die_st(food + (int64_t)(r0 + q) * plane_stride, i, (float)(scale * z + keep * (double)v[q]));
+                if (r0 + q < R) die_st(food + (int64_t)(r0 + q) * plane_stride, i, flow_mix(scale, z, keep, v[q]));
         }
     }
 }
@@ -644,7 +589,7 @@ static void launch_food_flow_batch(int32_t kind, T* food, int W, int H, int R, i
 
 // die_food_flow_batch_masked: the same update on the replicas whose bit is set.  A row of workgroups per replica (blockIdx.y);
 // those of an unset replica exit at once, so a replica without a flow costs no memory traffic.  Each replica's workgroups
-// evaluate the field themselves — the expression of k_food_flow_batch, token for token, so a full mask leaves its bits.
+// evaluate the field themselves, by the functions k_food_flow_batch calls, so a full mask leaves its bits.
 template <typename T, int KIND>
 __global__ __launch_bounds__(DIE_BLOCK) void k_food_flow_batch_masked(T* food, int W, int H, int64_t plane_stride, double t, double scale,
                                                                       double keep, double octaves, uint64_t seed, uint64_t mask) {
@@ -655,8 +600,7 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_food_flow_batch_masked(T* food, i
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
         const int gi = (int)(i / H), gj = (int)(i - (int64_t)gi * H);
         const double z = KIND == DIE_FLOW_WAVE ? flow_wave_z(gi, gj, W, H, t) : flow_perlin_z(gi, gj, W, H, t, octaves, seed);
-        const float v = die_ld(food, i);
-        die_st(food, i, (float)(scale * z + keep * (double)v));
+        die_st(food, i, flow_mix(scale, z, keep, die_ld(food, i)));
     }
 }
 

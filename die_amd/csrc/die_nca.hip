@@ -9,6 +9,7 @@
 //                     stores).  The first layer reads the medium's own planes: fp32 / fp16 fields, and the 'agents'
 //                     channel straight from the claim plane (occupied ⇔ epoch tag).  The last layer applies tanh.
 //   k_gather_scale    action[c, n] = plane[c][cell(x_n), cell(y_n)] · coef[c] for EVERY slot (only_alive = False).
+//                     k_gather_scale_batch (die_gather_scale_batch, replica in blockIdx.y) calls the same gather_scale_one.
 //   die_nca_env_step_batch (a population of candidates on batched replicas) runs k_conv_circular<K, true>: the same body
 //                     with the replica in blockIdx.z (its planes, weights and outputs one stride further each); the read-out
 //                     and the step half are k_nca_move_claim_batch in die_env.hip.
@@ -261,18 +262,20 @@ struct GatherArgs {
     float* out[3];
 };
 
+// slot n: the three planes at its cell, each times its coefficient
+__device__ __forceinline__ void gather_scale_one(const GatherArgs& a, int64_t n) {
+    const int64_t c = die_local(a.g, die_cell((int64_t)a.x[n], a.g.gW), die_cell((int64_t)a.y[n], a.g.gH));
+#pragma unroll
+    for (int q = 0; q < 3; ++q) a.out[q][n] = a.plane[q][c] * a.coef[q];
+}
+
 __global__ __launch_bounds__(DIE_BLOCK) void k_gather_scale(GatherArgs a) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < a.N; n += stride) {
-        const int64_t c = die_local(a.g, die_cell((int64_t)a.x[n], a.g.gW), die_cell((int64_t)a.y[n], a.g.gH));
-#pragma unroll
-        for (int q = 0; q < 3; ++q) a.out[q][n] = a.plane[q][c] * a.coef[q];
-    }
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < a.N; n += stride) gather_scale_one(a, n);
 }
 
 // die_gather_scale_batch: replica blockIdx.y — its planes `rep_plane` elements on, its slots `agents` on; slots n[r] … agents − 1
-// (the padding of a replica with fewer agents than the widest) read as 0; the loop body is k_gather_scale's, kept apart so that
-// the stand-alone kernel's code stays what it was
+// (the padding of a replica with fewer agents than the widest) read as 0
 struct GatherBatchArgs : GatherArgs {
     int64_t rep_plane, agents;
     int64_t n[DIE_MAX_REPLICAS];
@@ -288,9 +291,7 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_gather_scale_batch(GatherBatchArg
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < b.agents; n += stride) {
         if (n < nr) {
-            const int64_t c = die_local(a.g, die_cell((int64_t)a.x[n], a.g.gW), die_cell((int64_t)a.y[n], a.g.gH));
-#pragma unroll
-            for (int q = 0; q < 3; ++q) a.out[q][n] = a.plane[q][c] * a.coef[q];
+            gather_scale_one(a, n);
         } else {
 #pragma unroll
             for (int q = 0; q < 3; ++q) a.out[q][n] = 0.f;

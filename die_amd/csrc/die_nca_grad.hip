@@ -181,27 +181,26 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_backward(typename std::condi
     }
 }
 
-// one thread per weight: the tiles' partial rows in tile-index order, float64
-__global__ __launch_bounds__(DIE_BLOCK) void k_conv_backward_sum(const float* part, int64_t tiles, int nw, float* out) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= nw) return;
+// weight j: `rows` partial rows in ascending order, float64, rounded once
+__device__ __forceinline__ void conv_backward_sum_one(const float* part, int64_t rows, int nw, int j, float* out) {
     double s = 0.0;
 #pragma unroll 8
-    for (int64_t t = 0; t < tiles; ++t) s += (double)part[t * nw + j];
+    for (int64_t t = 0; t < rows; ++t) s += (double)part[t * nw + j];
     out[j] = (float)s;
+}
+
+// one thread per weight: the tiles' partial rows in tile-index order
+__global__ __launch_bounds__(DIE_BLOCK) void k_conv_backward_sum(const float* part, int64_t tiles, int nw, float* out) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < nw) conv_backward_sum_one(part, tiles, nw, j, out);
 }
 
 // die_nca_backward_batch's: one thread per (candidate blockIdx.y, weight j).  The E replicas of candidate c hold their partial rows
 // one behind the other ([replica][tile][nw], replica = c · E + e), so the fold "episode e = 0 … E − 1 outermost, tile index ascending
-// inside" is ONE ascending walk over E · tiles rows, in float64, rounded once — for E = 1 the loop above on replica c's rows.
+// inside" is ONE ascending walk over E · tiles rows — for E = 1 k_conv_backward_sum on replica c's rows.
 __global__ __launch_bounds__(DIE_BLOCK) void k_conv_backward_sum_batch(const float* part, int64_t rows, int nw, float* out, int64_t out_stride) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= nw) return;
-    part += (int64_t)blockIdx.y * rows * nw;
-    double s = 0.0;
-#pragma unroll 8
-    for (int64_t t = 0; t < rows; ++t) s += (double)part[t * nw + j];
-    out[(int64_t)blockIdx.y * out_stride + j] = (float)s;
+    if (j < nw) conv_backward_sum_one(part + (int64_t)blockIdx.y * rows * nw, rows, nw, j, out + (int64_t)blockIdx.y * out_stride);
 }
 
 static bool conv_shape_ok(int32_t W, int32_t H, int32_t cin, int32_t cout, int32_t k) {
@@ -296,20 +295,22 @@ struct GatherBwdArgs {
     float* plane[3];
 };
 
-__global__ __launch_bounds__(DIE_BLOCK) void k_gather_scale_backward(GatherBwdArgs a) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < a.N; n += stride) {
-        const int64_t c = die_local(a.g, die_cell((int64_t)a.x[n], a.g.gW), die_cell((int64_t)a.y[n], a.g.gH));
+// slot n: its gradient times the coefficients, added to the three planes at its cell
+__device__ __forceinline__ void gather_scale_backward_one(const GatherBwdArgs& a, int64_t n) {
+    const int64_t c = die_local(a.g, die_cell((int64_t)a.x[n], a.g.gW), die_cell((int64_t)a.y[n], a.g.gH));
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const float v = a.grad[q][n] * a.coef[q];
-            if (v != 0.f) atomicAdd(&a.plane[q][c], v);          // (a zero term changes no sum: dead slots with no gradient cost nothing)
-        }
+    for (int q = 0; q < 3; ++q) {
+        const float v = a.grad[q][n] * a.coef[q];
+        if (v != 0.f) atomicAdd(&a.plane[q][c], v);          // (a zero term changes no sum: dead slots with no gradient cost nothing)
     }
 }
 
-// die_gather_scale_backward_batch: replica blockIdx.y — its planes `rep_plane` elements on, its slots `agents` on, n[r] of them;
-// the loop is k_gather_scale_backward's, kept apart so that the stand-alone kernel's code stays what it was
+__global__ __launch_bounds__(DIE_BLOCK) void k_gather_scale_backward(GatherBwdArgs a) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < a.N; n += stride) gather_scale_backward_one(a, n);
+}
+
+// die_gather_scale_backward_batch: replica blockIdx.y — its planes `rep_plane` elements on, its slots `agents` on, n[r] of them
 struct GatherBwdBatchArgs : GatherBwdArgs {
     int64_t rep_plane, agents;
     int64_t n[DIE_MAX_REPLICAS];
@@ -323,14 +324,7 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_gather_scale_backward_batch(Gathe
 #pragma unroll
     for (int q = 0; q < 3; ++q) { a.grad[q] += pa; a.plane[q] += b.rep_plane * r; }
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < a.N; n += stride) {
-        const int64_t c = die_local(a.g, die_cell((int64_t)a.x[n], a.g.gW), die_cell((int64_t)a.y[n], a.g.gH));
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const float v = a.grad[q][n] * a.coef[q];
-            if (v != 0.f) atomicAdd(&a.plane[q][c], v);
-        }
-    }
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < a.N; n += stride) gather_scale_backward_one(a, n);
 }
 
 extern "C" int die_gather_scale_backward(const die_medium* m, const die_agents* ag, const die_action* grad_action, const float* coefs,

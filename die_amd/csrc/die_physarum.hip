@@ -3,7 +3,7 @@
 //
 //   k_physarum_decode  one thread per replica: the six values (natural, or lo + (hi - lo)·clamp(u, 0, 1) in fp32), degrees to
 //                      radians, and what die_fill_fwd_args (die_agents.hip) derives on the host for a stand-alone agent:
-//                      atol = turn·rtol, x_turn (its bisection over the bit patterns of the doubles, restated), cos(x_turn),
+//                      atol = turn·rtol, x_turn (die_isclose_bound, the function the host runs), cos(x_turn),
 //                      cos(sense).  With episodes E > 1 (die_physarum_decode_episodes) replica r decodes row r / E — the E
 //                      replicas of a candidate get the same table row — and the first of them writes the candidate's values.
 // One wave, a few hundred float64 operations: the launch is its whole cost.  tests/physarum_pop_model.py is its numpy twin.
@@ -17,27 +17,6 @@ struct DecodeArgs {
     int E;                       // episodes: replica r decodes row r / E (1: a row per replica)
     die_parameter_space s;
 };
-
-// np.isclose(0, x, rtol, atol): x <= atol + rtol·x, the product rounded, then the sum (isclose_bound's test, die_agents.hip)
-__device__ __forceinline__ bool isclose_ok(double x, double atol, double rtol) {
-    const double m = __dmul_rn(rtol, x);
-    const double s = __dadd_rn(atol, m);
-    return x <= s;
-}
-
-// isclose_bound (die_agents.hip) on the device: the largest x >= 0 the test accepts, by bisection over bit patterns
-__device__ double isclose_bound_dev(double atol, double rtol) {
-    if (!isclose_ok(0.0, atol, rtol)) return -1.0;
-    if (!(rtol < 1.0)) return HUGE_VAL;
-    const double top = 2.0 * atol / (1.0 - rtol) + 1e-300;
-    if (isclose_ok(top, atol, rtol)) return HUGE_VAL;
-    unsigned long long lo = 0, hi = (unsigned long long)__double_as_longlong(top);
-    for (int it = 0; it < 64 && hi - lo > 1; ++it) {          // ok(lo), !ok(hi); the distance halves: 64 rounds at most
-        const unsigned long long mid = lo + (hi - lo) / 2;
-        if (isclose_ok(__longlong_as_double((long long)mid), atol, rtol)) lo = mid; else hi = mid;
-    }
-    return __longlong_as_double((long long)lo);
-}
 
 __global__ __launch_bounds__(DIE_WAVE) void k_physarum_decode(DecodeArgs a, const float* __restrict__ rows, die_physarum_row* table,
                                                               float* values) {
@@ -66,7 +45,7 @@ __global__ __launch_bounds__(DIE_WAVE) void k_physarum_decode(DecodeArgs a, cons
     o.sense_radians = (double)v[4] * deg;
     o.turn_tolerance = (double)v[5];
     o.atol = o.turn_radians * o.turn_tolerance;
-    o.x_turn = isclose_bound_dev(o.atol, 1e-2);
+    o.x_turn = die_isclose_bound(o.atol, 1e-2);
     const double pi = 3.141592653589793;
     o.c_turn = o.x_turn < 0.0 ? 2.f : (o.x_turn >= pi ? -2.f : (float)cos(o.x_turn));
     o.c_sense = o.sense_radians < 0.0 ? 2.f : (o.sense_radians >= pi ? -2.f : (float)cos(o.sense_radians));
