@@ -208,6 +208,10 @@ _SIGNATURES = {
                                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, _P(DynamicsRow), C.c_void_p]),
     'die_nca_env_step_batch_rows': (C.c_int, [_P(Medium), _P(Agents), _P(NcaBatch), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
                                               C.c_void_p, C.c_int64, _P(NcaDropout), C.c_void_p, _P(DynamicsRow), C.c_void_p]),
+    'die_env_step_batch': (C.c_int, [_P(Medium), _P(Agents), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_void_p]),
+    'die_env_step_batch_rows': (C.c_int, [_P(Medium), _P(Agents), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.c_void_p, _P(DynamicsRow), C.c_void_p]),
     'die_food_flow_batch_masked': (C.c_int, [_P(Medium), _P(Batch), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_uint64,
                                              C.c_uint64, C.c_void_p]),
     'die_physarum_decode_batch': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(ParameterSpace), C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -335,9 +339,14 @@ _SIGNATURES = {
     'die_nca_backward_batch_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'die_nca_backward_batch': (C.c_int, [_P(Medium), _P(Batch), _P(NcaBatch), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                          _P(NcaDropout), C.c_void_p, C.c_int64, C.c_void_p]),
+    'die_nca_backward_batch_inputs': (C.c_int, [_P(Medium), _P(Batch), _P(NcaBatch), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                _P(NcaDropout), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     'die_deposit_cells': (C.c_int, [_P(Medium), _P(Agents), C.c_void_p, C.c_void_p]),
     'die_env_step_backward': (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_int64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    'die_deposit_cells_batch': (C.c_int, [_P(Medium), _P(Agents), _P(Batch), C.c_void_p, C.c_void_p]),
+    'die_env_step_backward_batch': (C.c_int, [C.c_int32, C.c_int32, _P(Batch), C.c_void_p, C.c_float, C.c_float, C.c_void_p,
+                                              _P(DynamicsRow), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'die_sort_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
     'die_agents_sort': (C.c_int, [_P(Medium), _P(Agents), _P(Agents), C.c_int32, _P(C.c_void_p), _P(C.c_void_p), C.c_void_p,
                                   C.c_int64, C.c_void_p]),

@@ -59,7 +59,7 @@ from . import _lib
 from .agent.evo import NeuralAutomataAgent
 from .agent.gradient import join64, split64
 from .data_init import DeviceFoodFlow, device_flow_kind, food_spec_from_seed
-from .device_array import Q32, _ptr, stream_ptr
+from .device_array import Q32, DeviceAction, _ptr, stream_ptr
 from .env import BoundaryCondition, Dynamics, Env, _identity_food_flow, linear_action_cost
 
 
@@ -123,6 +123,7 @@ class BatchedEnv:
         self.device = torch.device(device if device is not None else f'cuda:{torch.cuda.current_device()}')
         self.dtype = field_dtype
         self.per_replica = (self.W * self.H >= Env.PIC_MIN_CELLS) if per_replica is None else bool(per_replica)
+        self.chem_node = None                       # the chem planes' autograd handle (differentiable_chem / differentiable_step)
         if self.per_replica:
             # every replica Env gets its own Dynamics: its flow operator is its own (step keeps the counters in line)
             self.envs = [Env(field_size, dataclasses.replace(self.replica_dynamics(r)), seed=self.seeds[r], max_agents=slots,
@@ -223,6 +224,7 @@ class BatchedEnv:
         if self._flow_k0 is not None:
             self.dynamics.op_food_flow._k = self._flow_k0
         self._steps = 0
+        self.chem_node = None                       # the worlds start over: an autograd handle of the chem planes ends here
         if seeds is not None:
             self._reseed(seeds, seed, seed_stride)
             self.seeds = seeds
@@ -238,6 +240,7 @@ class BatchedEnv:
 
     def _reseed(self, seeds: List[int], seed: Optional[int], seed_stride: int) -> None:
         """The worlds of `seeds`; `seed` is None when they came as a list (else seeds[r] = seed + r·seed_stride)."""
+        self.chem_node = None
         if self.per_replica:
             for r, (e, q) in enumerate(zip(self.envs, seeds)):
                 try:
@@ -338,10 +341,119 @@ class BatchedEnv:
             raise
         agent._calls += 1
         agent._stepped()
+        self.chem_node = None                       # the field changed: an autograd handle of the chem planes ends here
         self.chem, self.chem_next = self.chem_next, self.chem
         self._food_flow(flow, m, b)
         self._steps += 1
         return results
+
+    def _check_action(self, action) -> None:
+        """The (3, R, Nmax) action tensor of `step_action`, or the ValueError that says what it must be."""
+        want = (3, self.R, self.Nmax)
+        if (not isinstance(action, torch.Tensor) or tuple(action.shape) != want or action.dtype != torch.float32
+                or action.device != self.device or not action.is_contiguous()):
+            got = (tuple(action.shape), action.dtype, str(action.device), action.stride()) if isinstance(action, torch.Tensor) \
+                else type(action).__name__
+            raise ValueError(f'action: a contiguous {want} float32 tensor on {self.device} (rows dx, dy, deposit; replica r reads '
+                             f'[:, r, :n[r]]), got {got}')
+
+    def step_action(self, action: torch.Tensor, results: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One step of every replica with the caller's actions: `Env.step(action)` of R worlds, no agent forward (an own torch
+        policy reading `medium_tensor()`, a replay of what `step(agent, action=buf)` recorded).  `action`: a contiguous
+        (3, R, Nmax) float32 tensor on the env's device, rows dx, dy, deposit; replica r reads `action[:, r, :n[r]]`, the padding is
+        never read; a tensor with a graph is read detached.  Replica r is bit for bit the stand-alone `Env.step` of those values
+        (tests/test_gpu_batch_step_action.py).  Small worlds: one claim launch for the whole batch (`die_env_step_batch`, `_rows`
+        under per-replica Dynamics), one more with dead slots, the sweep(s), one more with a flow.  Large worlds (per_replica): every
+        replica's own `Env.step` on its stream.  Returns the (R, 2) result words as `step` does; a refused step leaves the batch as
+        it was."""
+        self._check_action(action)                  # every refusal before anything is launched
+        flow = self._flow_kind()
+        action = action.detach()
+        if results is None:
+            results = torch.empty((self.R, 2), dtype=torch.float64, device=self.device)
+        if self.per_replica:
+            self._step_per_replica(_ReplicaActions(action, self.n), flow, results)
+            return results
+        epoch = self.epoch
+        self.epoch += 1                             # claims at the next epoch; at the wrap the claim planes start over
+        if self.epoch > _lib.OWNER_EPOCH_MAX:       # (as _PhysarumReplicas._claim_epoch)
+            self.owner.zero_()
+            self.epoch = 1
+        m, a, dyn, b = self._structs()
+        act = _lib.Action(self.Nmax, action[0].data_ptr(), action[1].data_ptr(), action[2].data_ptr())
+        args = (C.byref(m), C.byref(a), C.byref(act), C.byref(dyn), C.byref(b), _ptr(results), _ptr(self._ws), self._ws.numel())
+        if self._rows is None:
+            name, rows = 'die_env_step_batch', ()
+        else:
+            name, rows = 'die_env_step_batch_rows', (_ptr(self._rows), self._rows_host)
+        try:
+            _lib.check(getattr(_lib.lib, name)(*args, *rows, stream_ptr(self.device)), name)
+        except Exception:
+            self.epoch = epoch                      # refused before any launch: nothing changed
+            raise
+        self.chem_node = None                       # (differentiable_step sets this step's node afterwards)
+        self.chem, self.chem_next = self.chem_next, self.chem
+        self._food_flow(flow, m, b)
+        self._steps += 1
+        return results
+
+    # ------------------------------------------------------------------ the differentiable step (die_env_grad.hip, batched)
+    def _check_differentiable(self, what: str) -> None:
+        """What the batched chem adjoint covers; raises before anything is launched or changed (Env._check_differentiable: the
+        constructor has already refused a sense mask, a diffuse_mode other than 'wrap' and compat='reference')."""
+        if self.per_replica:
+            raise NotImplementedError(f'{what}: large worlds (per_replica) are not batched — every replica is a stand-alone Env: use '
+                                      f'envs[r].differentiable_step / envs[r].differentiable_chem, the stand-alone Env.differentiable_step')
+        if self.dtype != torch.float32:
+            raise NotImplementedError(f'{what}: fp32 fields only (this batch holds {self.dtype})')
+
+    def differentiable_chem(self) -> torch.Tensor:
+        """The chem node: an (R, W, H) fp32 tensor holding a copy of the current chem planes, kept as `chem_node`, the planes'
+        autograd handle.  On the first call, or after anything but `differentiable_step` changed the worlds, a leaf with
+        requires_grad=False; after a `differentiable_step` that step's output, whose backward reaches the actions and the nodes of
+        the steps before it.  `step`, `step_action`, `run` and `reset` (all forms) drop it, which cuts the graph there."""
+        self._check_differentiable('differentiable_chem')
+        if self.chem_node is None:
+            self.chem_node = self.chem.clone()
+        return self.chem_node
+
+    def differentiable_step(self, action: torch.Tensor, results: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`step_action` with a graph through the chem planes: `Env.differentiable_step` with an R in front.  `action`: the
+        (3, R, Nmax) fp32 tensor of `BatchedNeuralAutomataAgent.differentiable_action()` (or any fp32 tensor of that shape, with or
+        without a graph).  The worlds are stepped by `step_action(action.detach())` — state and result words bit for bit its — and
+        `chem_node` becomes this step's output,
+            chem'_r = (1 − decay_r) · G_r(chem_r + D_r),   D_r[cell] = deposit of the slot of replica r that won the cell,
+        differentiated with respect to the previous node (if it is still current) and the action's deposit row
+        (die_env_step_backward_batch: the sweep(s) on the gradient planes and one gather, R worlds per launch).  dx and dy get
+        zero gradient, as do the padding slots.  The agent is never called here: a replay through `step(agent, action=...)` would
+        advance its dropout counter a second time.  Who deposited where (die_deposit_cells_batch) and the diffusion constants —
+        sigma and decay, or the per-replica Dynamics table — are kept by the graph, so `backward` may run after further steps or a
+        reset.  agents_die, the fixed slot layout, a food flow, per-replica Dynamics and episodes are all taken; fp16 fields and
+        large worlds raise NotImplementedError, a wrong action ValueError, before anything is launched or changed."""
+        self._check_differentiable('differentiable_step')
+        want = (3, self.R, self.Nmax)
+        if not isinstance(action, torch.Tensor) or tuple(action.shape) != want or action.dtype != torch.float32 or action.device != self.device:
+            got = (tuple(action.shape), action.dtype, str(action.device)) if isinstance(action, torch.Tensor) else type(action).__name__
+            raise ValueError(f'action: a {want} float32 tensor on {self.device} (BatchedNeuralAutomataAgent.differentiable_action), '
+                             f'got {got}')
+        prev = self.chem_node
+        results = self.step_action(action.detach().contiguous(), results)
+        cells = torch.empty((self.R, self.Nmax), dtype=torch.int32, device=self.device)
+        m, a, _, b = self._structs()
+        _lib.check(_lib.lib.die_deposit_cells_batch(C.byref(m), C.byref(a), C.byref(b), _ptr(cells), stream_ptr(self.device)),
+                   'die_deposit_cells_batch')
+        self.chem_node = _BatchedFieldStep.apply(prev, action, cells, self.chem, self)
+        return results
+
+    def medium_tensor(self) -> torch.Tensor:
+        """The observation of every replica: (R, 3, W, H) float32 on the device, channels agents / food / chem — `replica_numpy(r)[0]`
+        for every r without leaving the device (the agents channel is 1 where the claim word carries the current epoch).  What an
+        external torch policy reads before `step_action`.  Torch ops only; small worlds."""
+        if self.per_replica:
+            raise NotImplementedError('medium_tensor: large worlds (per_replica) hold a stand-alone Env per replica; read '
+                                      'envs[r].medium there')
+        occ = ((self.owner >> (32 + _lib.OWNER_EPOCH_SHIFT)) & _lib.OWNER_EPOCH_MAX) == self.epoch
+        return torch.stack([occ.to(torch.float32), self.food.to(torch.float32), self.chem.to(torch.float32)], dim=1)
 
     def _flow_kind(self) -> Optional[int]:
         """The batched flow of `dynamics.op_food_flow` (DIE_FLOW_WAVE / DIE_FLOW_PERLIN; None for the identity).  Any other
@@ -415,6 +527,24 @@ class BatchedEnv:
         agents = np.stack([q(self.x), q(self.y), self.alive[r, :k].to(torch.float64).cpu().numpy(),
                            self.agent_food[r, :k].to(torch.float64).cpu().numpy()])
         return medium, agents
+
+
+class _ReplicaActions:
+    """`BatchedEnv.step_action` on large worlds: what `_step_per_replica` asks of an agent, answered from a (3, R, Nmax) action
+    tensor — replica r's 'agent' hands its Env `action[:, r, :n[r]]` as a DeviceAction in slot order."""
+
+    def __init__(self, action: torch.Tensor, n: Sequence[int]):
+        self._action, self._n, self._calls = action, n, 0
+
+    def _replica_agent(self, r: int) -> '_ReplicaActions':
+        self._r = r
+        return self
+
+    def forward(self, obs) -> DeviceAction:
+        k = self._n[self._r]
+        act = DeviceAction(k, self._action.device)
+        act.data = self._action[:, self._r, :k].contiguous()
+        return act
 
 
 def episode_seeds(seed: int, candidates: int, episodes: int, candidate_stride: int = 0) -> List[int]:
@@ -1059,7 +1189,7 @@ class BatchedNeuralAutomataAgent(_Population):
         call whenever a `dropout_seed` is set.  Small worlds, 'circular' / 'zeros' boundaries; anything else raises
         NotImplementedError before any launch.  `step()` is untouched by all this."""
         p = self._check_differentiable(parameters)
-        out = _BatchedSense.apply(self, p)
+        out = _BatchedSense.apply(self, p, self.env.chem_node)
         if self.dropout_seed is not None:
             self.dropout_step += 1
         return out
@@ -1091,11 +1221,42 @@ def _geometry(env: BatchedEnv) -> _lib.Medium:
     return _lib.Medium(env.W, env.H, _lib.DIE_F32, 1, None, None, None, None, 0, 0, 0, 0, 0, 0, 0, 0, None)
 
 
-class _BatchedSense(torch.autograd.Function):
-    """BatchedNeuralAutomataAgent.differentiable_sense: die_nca_sense_batch_store forward, die_nca_backward_batch backward."""
+class _BatchedFieldStep(torch.autograd.Function):
+    """BatchedEnv.differentiable_step's node: the value is a copy of the chem planes the step left, the backward
+    die_env_step_backward_batch — the forward's own sweep on the gradient planes and a gather at the recorded winners' cells."""
 
     @staticmethod
-    def forward(ctx, pop, parameters):
+    def forward(ctx, prev_node, action, cells, chem, env):
+        ctx.save_for_backward(cells)
+        d = env.dynamics
+        ctx.batch, ctx.size, ctx.dev = env._batch_struct(), (env.R, env.W, env.H, env.Nmax), chem.device
+        ctx.sigma, ctx.decay = float(d.diffuse_sigma), float(d.rate_decay_chem)
+        ctx.rows = None if env._rows is None else (env._rows, env._rows_host)      # per-replica Dynamics: built once, never written
+        return chem.clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        cells, = ctx.saved_tensors
+        (R, W, H, Nmax), dev = ctx.size, ctx.dev
+        g = grad.to(dtype=torch.float32).contiguous()
+        grad_chem = torch.empty((R, W, H), dtype=torch.float32, device=dev)
+        grad_action = None
+        if ctx.needs_input_grad[1]:
+            grad_action = torch.zeros((3, R, Nmax), dtype=torch.float32, device=dev)     # dx, dy: positions are constants of the parameters
+        rows = (None, None) if ctx.rows is None else (_ptr(ctx.rows[0]), ctx.rows[1])
+        _lib.check(_lib.lib.die_env_step_backward_batch(W, H, C.byref(ctx.batch), _ptr(g), ctx.sigma, ctx.decay, *rows, _ptr(cells),
+                                                        _ptr(grad_chem), None if grad_action is None else grad_action[2].data_ptr(),
+                                                        stream_ptr(dev)), 'die_env_step_backward_batch')
+        return grad_chem if ctx.needs_input_grad[0] else None, grad_action, None, None, None
+
+
+class _BatchedSense(torch.autograd.Function):
+    """BatchedNeuralAutomataAgent.differentiable_sense: die_nca_sense_batch_store forward, die_nca_backward_batch backward — or, with
+    the env's chem node as an input, die_nca_backward_batch_inputs, whose chem channel is the node's gradient."""
+
+    @staticmethod
+    def forward(ctx, pop, parameters, chem_node=None):
         env = pop.env
         R, W, H, L, dev = env.R, env.W, env.H, len(pop._layers), env.device
         with_agents = pop._arch['with_agent_channel']
@@ -1136,10 +1297,16 @@ class _BatchedSense(torch.autograd.Function):
         drop = None if ctx.drop is None else _lib.NcaDropout(*ctx.drop, 0)
         m = _BatchedSense._medium(ctx, planes)
         layers, nca = pop._grad_struct(parameters, ctx.epoch)
-        _lib.check(_lib.lib.die_nca_backward_batch(C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), _ptr(g), 3 * W * H, _ptr(out),
-                                                   pop.P, None if drop is None else C.byref(drop), _ptr(ws), need, stream_ptr(dev)),
-                   'die_nca_backward_batch')
-        return None, out
+        args = (C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), _ptr(g), 3 * W * H, _ptr(out), pop.P,
+                None if drop is None else C.byref(drop), _ptr(ws), need)
+        if not ctx.needs_input_grad[2]:             # no chem node, or one that asks for nothing (a leaf)
+            _lib.check(_lib.lib.die_nca_backward_batch(*args, stream_ptr(dev)), 'die_nca_backward_batch')
+            return None, out, None
+        # the first layer's inputs are ([agents,] food, chem): food and the claims are constants of the parameters, chem is the node
+        cin = len(planes)
+        grad_in = torch.empty((R, cin, W, H), dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib.die_nca_backward_batch_inputs(*args, _ptr(grad_in), cin * W * H, stream_ptr(dev)), 'die_nca_backward_batch_inputs')
+        return None, out, grad_in[:, cin - 1]
 
 
 class _BatchedReadOut(torch.autograd.Function):

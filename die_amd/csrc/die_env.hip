@@ -11,6 +11,8 @@
 //                  claim pass's stash (consumed and action cost), starved slots zeroed, alive count per replica
 //   k_nca_move_claim_batch  a NeuralAutomataAgent population (die_nca_env_step_batch): every agent reads its action out of
 //                  its candidate's last conv planes (die_gather_scale's product, in registers), then k_move_claim's work
+//   k_action_move_claim_batch  the caller's own actions (die_env_step_batch): three coalesced loads per slot instead of a forward, then
+//                  k_move_claim's work — BatchedEnv.step_action, the step under BatchedEnv.differentiable_step
 //
 // Why two agent passes: every slot on a cell must read the food value from BEFORE the step's
 // consumption (co-located agents each get the full amount, :224-225), so all reads of `food`
@@ -275,6 +277,32 @@ __global__ __launch_bounds__(DIE_STEP_BLOCK) void k_nca_move_claim_batch(NcaRead
         const float dy = s1[c] * q.coef[1];
         const float dep = s2[c] * q.coef[2];
         if (q.act[0]) { q.act[0][pa + n] = dx; q.act[1][pa + n] = dy; q.act[2][pa + n] = dep; }
+        gsum += die_fix(move_claim_one<T, false>(a, n, X, Y, dx, dy, dep, (uint32_t)n, cnt));
+    }
+    block_sum_store(gsum, cnt, a.part_gain, a.part_alive);
+    if (!a.has_dead && blockIdx.x == 0 && threadIdx.x == 0) a.part_alive[0] = a.N;  // every slot is alive (as k_forward_move_claim_batch)
+}
+
+// The caller's own actions (die_env_step_batch): k_nca_move_claim_batch with the three plane gathers replaced by three coalesced
+// loads of replica r's slot n (StepArgs' dx / dy / dep are replica 0's arrays, `agents` apart).  Agents in slot order.
+template <typename T, typename... ROWS>
+__global__ __launch_bounds__(DIE_STEP_BLOCK) void k_action_move_claim_batch(StepArgs a, BatchArgs b, ROWS... rows) {
+    const int r = blockIdx.y;
+    dynamics_row_args(a, r, rows...);
+    const int64_t pc = b.cells * r, pa = b.agents * r;
+    a.owner += pc; a.food = (T*)a.food + pc; a.chem = (T*)a.chem + pc;
+    a.x += pa; a.y += pa; a.alive += pa; a.agent_food += pa;
+    a.N = b.n[r];
+    a.part_gain += (int64_t)DIE_MAX_PARTIALS * 3 * r;
+    batch_stash(a, b, r);
+    long long gsum = 0;
+    long long cnt = 0;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < a.N; n += stride) {
+        const uint32_t X = a.x[n], Y = a.y[n];
+        const float dx = a.dx[pa + n];
+        const float dy = a.dy[pa + n];
+        const float dep = a.dep[pa + n];
         gsum += die_fix(move_claim_one<T, false>(a, n, X, Y, dx, dy, dep, (uint32_t)n, cnt));
     }
     block_sum_store(gsum, cnt, a.part_gain, a.part_alive);
@@ -1202,35 +1230,74 @@ static int batch_step_args(BatchLaunch& L, const die_medium* m, const die_agents
 
 // Per-replica Dynamics: launch_rows' grid for the `grp.n` replicas of radius R (the rows-per-wave choice is the whole batch's, so
 // a batch of one radius is launched in the shared-Dynamics sweep's shape)
-template <typename T>
+// FUSED = 0: the plain sweep of those replicas (the step's adjoint, die_diffuse_rows_batch), no reduction row ahead of the field's
+template <typename T, int FUSED = 1>
 static void launch_rows_table(RowsArgs a, int R, const RowsTable& grp, int replicas, hipStream_t s) {
     const int strips = (a.H + DIF_WCOLS - 1) / DIF_WCOLS;
     constexpr int WPB = DIF_BLOCK / DIE_WAVE;
     a.rpw = rows_per_wave(a.W, a.H, replicas);
-    dim3 grid((strips + WPB - 1) / WPB, (a.W + a.rpw - 1) / a.rpw + 1, grp.n);
+    dim3 grid((strips + WPB - 1) / WPB, (a.W + a.rpw - 1) / a.rpw + (FUSED ? 1 : 0), grp.n);
     switch (R) {
-        case 1: k_diffuse_rows<T, 1, 1, true, RowsTable><<<grid, DIF_BLOCK, 0, s>>>(a, grp); break;
-        case 2: k_diffuse_rows<T, 2, 1, true, RowsTable><<<grid, DIF_BLOCK, 0, s>>>(a, grp); break;
-        case 3: k_diffuse_rows<T, 3, 1, true, RowsTable><<<grid, DIF_BLOCK, 0, s>>>(a, grp); break;
-        default: k_diffuse_rows<T, 4, 1, true, RowsTable><<<grid, DIF_BLOCK, 0, s>>>(a, grp); break;
+        case 1: k_diffuse_rows<T, 1, FUSED, true, RowsTable><<<grid, DIF_BLOCK, 0, s>>>(a, grp); break;
+        case 2: k_diffuse_rows<T, 2, FUSED, true, RowsTable><<<grid, DIF_BLOCK, 0, s>>>(a, grp); break;
+        case 3: k_diffuse_rows<T, 3, FUSED, true, RowsTable><<<grid, DIF_BLOCK, 0, s>>>(a, grp); break;
+        default: k_diffuse_rows<T, 4, FUSED, true, RowsTable><<<grid, DIF_BLOCK, 0, s>>>(a, grp); break;
     }
+}
+
+// the replicas of radius R among rows_host, as the by-value index list of a sweep launch
+static RowsTable rows_group(const die_dynamics_row* rows, const die_dynamics_row* rows_host, int replicas, int R) {
+    RowsTable grp;
+    grp.rows = rows;
+    grp.n = 0;
+    for (int r = 0; r < DIE_MAX_REPLICAS; ++r) grp.idx[r] = 0;
+    for (int r = 0; r < replicas; ++r)
+        if (rows_host[r].radius == R) grp.idx[grp.n++] = (uint8_t)r;
+    return grp;
 }
 
 // the sweep of a batch with per-replica rows: one launch per radius present among rows_host (checked to lie in 1..4)
 static int batch_sweep_rows(const die_medium* m, const RowsArgs& ra, const die_batch* b, hipStream_t s, const char* who,
                             const die_dynamics_row* rows, const die_dynamics_row* rows_host) {
     for (int R = 1; R <= 4; ++R) {
-        RowsTable grp;
-        grp.rows = rows;
-        grp.n = 0;
-        for (int r = 0; r < DIE_MAX_REPLICAS; ++r) grp.idx[r] = 0;
-        for (int r = 0; r < b->replicas; ++r)
-            if (rows_host[r].radius == R) grp.idx[grp.n++] = (uint8_t)r;
+        const RowsTable grp = rows_group(rows, rows_host, b->replicas, R);
         if (!grp.n) continue;
         if (m->dtype == DIE_F32) launch_rows_table<float>(ra, R, grp, b->replicas, s);
         else launch_rows_table<__half>(ra, R, grp, b->replicas, s);
         DIE_CHECK_LAUNCH(who);
     }
+    return DIE_OK;
+}
+
+// (1 - decay) * G(src) of `replicas` fp32 planes `plane_stride` cells apart, without deposits or feeding (die_env_grad.hip:
+// die_env_step_backward_batch, whose checks precede this: H % 4 == 0, every radius in 1..4).  rows NULL: one launch, the taps and
+// `keep` of (sigma, decay) exactly as diffuse_decay_mode builds them, the kernel die_diffuse_decay launches with the replica in
+// gridDim.z.  Else replica r under rows[r]'s taps and keep: one launch per radius present, as batch_sweep_rows.
+int die_diffuse_rows_batch(const float* src, float* dst, int32_t W, int32_t H, int32_t replicas, int64_t plane_stride, float sigma,
+                           float decay, const die_dynamics_row* rows, const die_dynamics_row* rows_host, void* stream, const char* who) {
+    RowsArgs ra;
+    ra.src = src; ra.dst = dst; ra.claim = nullptr; ra.dep = nullptr; ra.food = nullptr; ra.W = W; ra.H = H; ra.epoch = 0; ra.halo = 0;
+    ra.rep_cells = plane_stride;
+    ra.wrapx = ra.wrapy = 1; ra.part_gain = nullptr; ra.part_gain2 = nullptr; ra.part_alive = nullptr; ra.n_part = 0; ra.result = nullptr; ra.alive_const = 0;
+    ra.food_infinite = 1; ra.keep = 0.f; ra.rate_feed = 0.f;
+    for (int k = 0; k <= 2 * 4; ++k) ra.w[k] = 0.f;
+    hipStream_t s = (hipStream_t)stream;
+    if (rows) {
+        for (int R = 1; R <= 4; ++R) {
+            const RowsTable grp = rows_group(rows, rows_host, replicas, R);
+            if (!grp.n) continue;
+            launch_rows_table<float, 0>(ra, R, grp, replicas, s);
+            DIE_CHECK_LAUNCH(who);
+        }
+        return DIE_OK;
+    }
+    double wd[2 * DIF_MAXR + 1];
+    const int R = gaussian_taps(sigma, wd);
+    ra.keep = (float)(1.0 - (double)decay);
+    for (int k = 0; k <= 2 * R; ++k) ra.w[k] = (float)wd[k];
+    const int rc = launch_rows<float, 0>(ra, R, s, replicas);
+    if (rc != DIE_OK) return rc;
+    DIE_CHECK_LAUNCH(who);
     return DIE_OK;
 }
 
@@ -1444,6 +1511,42 @@ extern "C" int die_physarum_env_step_batch_rows(const die_medium* m, const die_a
                                                 const die_dynamics_row* rows, const die_dynamics_row* rows_host, void* stream) {
     return physarum_env_step_batch(m, a, g, table, act, d, b, results, ws, ws_bytes, true, rows, rows_host, stream,
                                    "die_physarum_env_step_batch_rows");
+}
+
+// die_env_step_batch (with_rows false) and die_env_step_batch_rows: one body.  No forward: the claim pass reads the caller's actions
+static int env_step_batch(const die_medium* m, const die_agents* a, const die_action* act, const die_dynamics* d, const die_batch* b,
+                          die_step_result* results, void* ws, int64_t ws_bytes, bool with_rows, const die_dynamics_row* rows,
+                          const die_dynamics_row* rows_host, void* stream, const char* who) {
+    DIE_REQUIRE(m && a && act && d && b && results && ws, "%s: null argument", who);
+    int rc = batch_world_check(m, a, d, b, ws_bytes, false, who);
+    if (rc != DIE_OK) return rc;
+    DIE_REQUIRE(act->dx && act->dy && act->deposit, "%s: null action arrays", who);
+    DIE_REQUIRE(m->food && m->chem && a->x && a->y && !a->slot, "%s: null plane or agent array, or agents not in slot order", who);
+    DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad field dtype %d", who, m->dtype);
+    BatchLaunch L;
+    rc = batch_step_args(L, m, a, act, d, b, ws, stream, who);
+    if (rc != DIE_OK) return rc;
+    rc = batch_rows_check(with_rows, b, rows, rows_host, who);
+    if (rc != DIE_OK) return rc;
+    if (with_rows) {
+        if (m->dtype == DIE_F32) k_action_move_claim_batch<float, const die_dynamics_row*><<<L.grid, DIE_STEP_BLOCK, 0, L.s>>>(L.k, L.ba, rows);
+        else k_action_move_claim_batch<__half, const die_dynamics_row*><<<L.grid, DIE_STEP_BLOCK, 0, L.s>>>(L.k, L.ba, rows);
+    } else {
+        if (m->dtype == DIE_F32) k_action_move_claim_batch<float><<<L.grid, DIE_STEP_BLOCK, 0, L.s>>>(L.k, L.ba);
+        else k_action_move_claim_batch<__half><<<L.grid, DIE_STEP_BLOCK, 0, L.s>>>(L.k, L.ba);
+    }
+    return batch_step_tail(L, m, d, b, results, ws, rows, rows_host, who);
+}
+
+extern "C" int die_env_step_batch(const die_medium* m, const die_agents* a, const die_action* act, const die_dynamics* d,
+                                  const die_batch* b, die_step_result* results, void* ws, int64_t ws_bytes, void* stream) {
+    return env_step_batch(m, a, act, d, b, results, ws, ws_bytes, false, nullptr, nullptr, stream, "die_env_step_batch");
+}
+
+extern "C" int die_env_step_batch_rows(const die_medium* m, const die_agents* a, const die_action* act, const die_dynamics* d,
+                                       const die_batch* b, die_step_result* results, void* ws, int64_t ws_bytes,
+                                       const die_dynamics_row* rows, const die_dynamics_row* rows_host, void* stream) {
+    return env_step_batch(m, a, act, d, b, results, ws, ws_bytes, true, rows, rows_host, stream, "die_env_step_batch_rows");
 }
 
 int die_nca_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who);       // die_nca.hip

@@ -401,10 +401,12 @@ extern "C" int64_t die_nca_backward_batch_workspace_bytes(int32_t W, int32_t H, 
            (int64_t)sizeof(float);
 }
 
-extern "C" int die_nca_backward_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store,
-                                      const float* grad_sense, int64_t sense_stride, float* grad, int64_t grad_stride,
-                                      const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, void* stream) {
-    const char* who = "die_nca_backward_batch";
+// die_nca_backward_batch (grad_in null) and die_nca_backward_batch_inputs: one body.  grad_in: layer 0's launch also writes the
+// gradient at its cin input planes (has_gin, as the layers above it do into the workspace), replica r's at grad_in + r * grad_in_stride
+static int nca_backward_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store,
+                              const float* grad_sense, int64_t sense_stride, float* grad, int64_t grad_stride,
+                              const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, float* grad_in,
+                              int64_t grad_in_stride, void* stream, const char* who) {
     DIE_REQUIRE(m && b && nca && store && grad_sense && grad && workspace, "%s: null argument", who);
     int rc = die_nca_batch_shape_check(m, b, who);
     if (rc != DIE_OK) return rc;
@@ -429,6 +431,22 @@ extern "C" int die_nca_backward_batch(const die_medium* m, const die_batch* b, c
     const int64_t need = die_nca_backward_batch_workspace_bytes(m->W, m->H, b->replicas, nca->n_layers);
     DIE_REQUIRE(need > 0, "%s: field too tall", who);
     DIE_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%lld < %lld)", who, (long long)workspace_bytes, (long long)need);
+    if (grad_in) {
+        const int64_t in_planes = (int64_t)nca->layers[0].cin * cells;
+        DIE_REQUIRE(grad_in_stride >= in_planes, "%s: grad_in_stride %lld below the first layer's %d input planes", who,
+                    (long long)grad_in_stride, nca->layers[0].cin);
+        // the kernel stores four cells of a row at once where H % 4 == 0
+        DIE_REQUIRE(m->H % 4 != 0 || (((uintptr_t)grad_in & 15) == 0 && grad_in_stride % 4 == 0),
+                    "%s: grad_in must be 16-byte aligned and grad_in_stride a multiple of 4 where H %% 4 == 0", who);
+        const char* lo = (const char*)grad_in;
+        const char* hi = lo + ((int64_t)(b->replicas - 1) * grad_in_stride + in_planes) * (int64_t)sizeof(float);
+        auto inside = [&](const void* q) { return q && (const char*)q >= lo && (const char*)q < hi; };
+        const char* ws_hi = (const char*)workspace + need;
+        DIE_REQUIRE(!inside(store) && !inside(grad_sense) && !inside(grad) && !inside(workspace) && !inside(m->owner) && !inside(m->food) &&
+                        !inside(m->chem) && !((const char*)workspace <= lo && lo < ws_hi),
+                    "%s: grad_in aliases another buffer of the call", who);
+        for (int l = 0; l < nca->n_layers; ++l) DIE_REQUIRE(!inside(nca->layers[l].weights), "%s: grad_in aliases layer %d's weights", who, l);
+    }
     DropWords dw = {};
     if (drop) {
         rc = die_dropout_words(drop, &dw, who);
@@ -459,13 +477,13 @@ extern "C" int die_nca_backward_batch(const die_medium* m, const die_batch* b, c
             for (int c = 0; c < Ly.cin; ++c) { a.in[c] = store + (int64_t)(l - 1) * R * rep_planes + c * cells; a.kind[c] = DIE_PLANE_F32; }
             a.rep_in = rep_planes;
         }
-        float* gin = l > 0 ? gin_sets + (int64_t)((L - 1 - l) % 2) * R * rep_planes : nullptr;
+        float* gin = l > 0 ? gin_sets + (int64_t)((L - 1 - l) % 2) * R * rep_planes : grad_in;
         for (int c = 0; c < Ly.cin && gin; ++c) a.gin[c] = gin + c * cells;
         for (int o = 0; o < Ly.cout; ++o) {
             a.g[o] = g + o * cells;
             if (l == L - 1) a.t[o] = store + (int64_t)l * R * rep_planes + o * cells;
         }
-        a.rep_g = rep_g; a.rep_t = rep_planes; a.rep_gin = rep_planes;
+        a.rep_g = rep_g; a.rep_t = rep_planes; a.rep_gin = l > 0 ? rep_planes : grad_in_stride;
         a.w = Ly.weights; a.rep_w = Ly.weight_stride; a.episodes = E;
         a.part = part; a.rep_part = tiles * nw;
         a.W = m->W; a.H = m->H; a.cin = Ly.cin; a.cout = Ly.cout; a.epoch = nca->sense_epoch; a.pad = nca->padding_mode;
@@ -486,4 +504,21 @@ extern "C" int die_nca_backward_batch(const die_medium* m, const die_batch* b, c
         g = gin; rep_g = rep_planes;
     }
     return DIE_OK;
+}
+
+extern "C" int die_nca_backward_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store,
+                                      const float* grad_sense, int64_t sense_stride, float* grad, int64_t grad_stride,
+                                      const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, void* stream) {
+    return nca_backward_batch(m, b, nca, store, grad_sense, sense_stride, grad, grad_stride, drop, workspace, workspace_bytes, nullptr, 0,
+                              stream, "die_nca_backward_batch");
+}
+
+extern "C" int die_nca_backward_batch_inputs(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store,
+                                             const float* grad_sense, int64_t sense_stride, float* grad, int64_t grad_stride,
+                                             const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, float* grad_in,
+                                             int64_t grad_in_stride, void* stream) {
+    const char* who = "die_nca_backward_batch_inputs";
+    DIE_REQUIRE(grad_in, "%s: null argument (grad_in)", who);
+    return nca_backward_batch(m, b, nca, store, grad_sense, sense_stride, grad, grad_stride, drop, workspace, workspace_bytes, grad_in,
+                              grad_in_stride, stream, who);
 }

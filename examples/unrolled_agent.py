@@ -1,6 +1,7 @@
 """Train a NeuralAutomataAgent through the world: grow a teacher's trail pattern by backpropagating through T steps of Env.step.
 
     python examples/unrolled_agent.py [--size 96] [--steps 8] [--iters 100] [--lr 0.01] [--seed 0] [--time]
+                                      [--replicas R --students C [--episodes E]]
 
 A PhysarumAgent world is run `--steps` steps from the seed and its `chem1` plane kept as the target.  The student —
 NeuralAutomataAgent(kernel_sizes=[3, 3]) — is then unrolled the same number of steps from the same seed, every step
@@ -11,6 +12,12 @@ cells (die_env_step_backward), the read-out's and the conv stack's adjoints, and
 the step before.  What the trail laid at step 1 does to what the colony senses at step 4 is in that gradient; where the agents
 walk is not (positions are piecewise constant in the weights).  Adam updates the 162 weights; the loss is printed per iteration.
 `--time` prints optimiser iterations per second instead (after a warm-up tenth of the run, both ends a device synchronise).
+
+`--replicas R --students C` (R = C·E; `--episodes E` may say E instead of R) is the batched form: C students, each grown towards the
+teacher's trail on E worlds (seeds seed … seed + E − 1, the same E for every student) in ONE optimiser step — R worlds in one BatchedEnv,
+every step `benv.differentiable_step(pop.differentiable_action())`, the loss the sum of the R stand-alone losses, so that row c of
+`pop.parameters.grad` is student c's gradient summed over its worlds.  The launches of a step and of its adjoint are shared by the R
+worlds; the students start from different initialisations and Adam updates the (C, 162) matrix.
 """
 import argparse
 import os
@@ -22,13 +29,18 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from die_amd import Dynamics, Env, NeuralAutomataAgent, PhysarumAgent          # noqa: E402
+from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent, BatchedPhysarumAgent, episode_seeds          # noqa: E402
 
 SCALE, DEPOSIT = 0.01, 2.0
 COST_W = (0.02, 0.01)                                             # linear_action_cost's weights
 
 
+def make_dynamics():
+    return Dynamics(food_infinite=True, rate_decay_chem=0.05, diffuse_sigma=0.8)
+
+
 def make_env(size, seed):
-    return Env((size, size), Dynamics(food_infinite=True, rate_decay_chem=0.05, diffuse_sigma=0.8), seed=seed, max_agents='alive')
+    return Env((size, size), make_dynamics(), seed=seed, max_agents='alive')
 
 
 def teacher_trail(size, steps, seed):
@@ -56,6 +68,53 @@ def rollout_loss(student, target, size, steps, seed):
     return ((env.differentiable_chem() - target) ** 2).mean() + cost / (steps * env.agents.N)
 
 
+def train_batched(args, students, episodes):
+    """C students on R = C·E worlds: one rollout, one backward and one Adam step per iteration for all of them."""
+    R, size = students * episodes, args.size
+    seeds = episode_seeds(args.seed, students, episodes)
+    world = BatchedEnv((size, size), make_dynamics(), replicas=R, seeds=seeds)
+    teacher = BatchedPhysarumAgent(world, scale=SCALE, deposit=DEPOSIT, seed=args.seed)
+    world.run(teacher, args.steps)
+    target = world.chem.clone()                                   # (R, W, H): the trail every world's student is grown towards
+    benv = BatchedEnv((size, size), make_dynamics(), replicas=R, seeds=seeds)
+    template = NeuralAutomataAgent(kernel_sizes=[3, 3], scale=SCALE, deposit=DEPOSIT)
+    rows = []
+    for _ in range(students):                                     # different initialisations side by side
+        template.model.init_weights()
+        rows.append(torch.nn.utils.parameters_to_vector(template.model.parameters()).detach().clone())
+    pop = BatchedNeuralAutomataAgent(benv, template, torch.stack(rows), episodes)
+    pop.parameters.requires_grad_(True)
+    opt = torch.optim.Adam([pop.parameters], lr=args.lr)
+    n = torch.tensor(benv.n, dtype=torch.float32, device=benv.device)
+    slots = (torch.arange(benv.Nmax, device=benv.device)[None] < n[:, None]).to(torch.float32)       # (R, Nmax): 0 on the padding
+    warmup, t0 = max(1, args.iters // 10), None
+    for it in range(args.iters):
+        if args.time and it == warmup:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        benv.reset()
+        cost = 0.
+        for _ in range(args.steps):
+            action = pop.differentiable_action()
+            # action_cost per replica, the padding slots left out
+            cost = cost + ((COST_W[0] * action[2].abs() + COST_W[1] * (action[0] ** 2 + action[1] ** 2 + 1e-12).sqrt()) * slots).sum(dim=1)
+            benv.differentiable_step(action)
+        per_world = ((benv.differentiable_chem() - target) ** 2).mean(dim=(1, 2)) + cost / (args.steps * n)
+        loss = per_world.sum()                                    # row c of the gradient: student c's, summed over its E worlds
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        if not args.time:
+            per_student = per_world.detach().view(students, episodes).mean(dim=1)
+            print(f'iteration {it:4d}: loss per student ' + ' '.join(f'{v:.6f}' for v in per_student.tolist()))
+    if t0 is not None:
+        torch.cuda.synchronize()
+        k = args.iters - warmup
+        print(f'unrolled training, {students} students x {episodes} worlds of {size}x{size}, T = {args.steps}: '
+              f'{k / (time.perf_counter() - t0):.1f} optimiser iterations/s over {k}')
+    return pop
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument('--size', type=int, default=96)
@@ -64,8 +123,18 @@ def main():
     p.add_argument('--lr', type=float, default=0.01)
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--time', action='store_true', help='print optimiser iterations per second instead of the losses')
+    p.add_argument('--replicas', type=int, default=0, help='R worlds in one BatchedEnv (0: the single-world form)')
+    p.add_argument('--students', type=int, default=0, help='C students, R = C x E (default: one per replica)')
+    p.add_argument('--episodes', type=int, default=0, help='E worlds per student (default: R / C)')
     args = p.parse_args()
     torch.manual_seed(args.seed)
+    if args.replicas or args.students or args.episodes:
+        students = args.students or (args.replicas // max(args.episodes, 1) if args.replicas else 1)
+        episodes = args.episodes or (args.replicas // students if args.replicas else 1)
+        if students < 1 or episodes < 1 or (args.replicas and students * episodes != args.replicas):
+            raise SystemExit(f'--replicas {args.replicas} must be --students {students} x --episodes {episodes}')
+        train_batched(args, students, episodes)
+        return
     target = teacher_trail(args.size, args.steps, args.seed)
     student = NeuralAutomataAgent(kernel_sizes=[3, 3], scale=SCALE, deposit=DEPOSIT)
     student.model.init_weights()

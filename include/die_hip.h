@@ -803,6 +803,25 @@ int die_nca_env_step_batch_rows(const die_medium* m, const die_agents* a, const 
                                 int64_t workspace_bytes, const die_nca_dropout* drop, const die_dynamics_row* rows,
                                 const die_dynamics_row* rows_host, void* stream);
 
+/* ---- Batched replicas stepped with the caller's actions (die_env.hip; BatchedEnv.step_action) -------------------------------
+ * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
+ * die_env_step for R replicas: no agent forward runs, the claim pass reads `act` (required).  `m`, `a`, `act` describe replica 0;
+ * replica r's three action arrays start r * b->agent_stride elements further (the layout the other batched steps write `act` in)
+ * and only their first b->n[r] entries are read.  Replica r computes bit for bit what die_env_step computes on that world alone
+ * with those actions: one claim launch (replica in blockIdx.y), with dead slots (d->agents_die / d->has_dead_slots) the dead-slot +
+ * lifecycle launch, then the field sweep(s) of the other batched steps; the same workspace as they take.  Agents are in slot
+ * order (a->slot NULL).  m->epoch is the epoch the claims are made at: the caller advances it, and clears the claim planes when
+ * it wraps to 1.  Refused before any launch, in this order: a null argument (act included), the batched steps' world checks
+ * (1..DIE_MAX_REPLICAS replicas, workspace, no decomposed medium or sense mask, chem_next a second plane, strides of at least a
+ * replica, H % 4 == 0 and a gaussian radius of 1..4: DIE_ERR_UNSUPPORTED), a null action array, plane or agent array, the
+ * step's own arguments (epoch, boundary, cost, n[r] in 1..agent_stride) and, for _rows, either table missing or a radius
+ * outside 1..4. */
+int die_env_step_batch(const die_medium* m, const die_agents* a, const die_action* act, const die_dynamics* d, const die_batch* b,
+                       die_step_result* results, void* workspace, int64_t workspace_bytes, void* stream);
+int die_env_step_batch_rows(const die_medium* m, const die_agents* a, const die_action* act, const die_dynamics* d,
+                            const die_batch* b, die_step_result* results, void* workspace, int64_t workspace_bytes,
+                            const die_dynamics_row* rows, const die_dynamics_row* rows_host, void* stream);
+
 /* ---- The adjoint of the NeuralAutomataAgent sensing (die_nca_grad.hip; NeuralAutomataAgent.differentiable_sense / _action) -----
  * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
  * The forward is z_l = conv_l(z_{l-1}) (die_conv2d per layer, z_0 = the medium's planes), s = tanh(z_L) * mask (the last layer's
@@ -914,6 +933,44 @@ int die_deposit_cells(const die_medium* m, const die_agents* a, int32_t* cells_o
  * die_diffuse_decay takes it (radius int(4 sigma + .5) in 1..8, else DIE_ERR_ARG / DIE_ERR_UNSUPPORTED). */
 int die_env_step_backward(int32_t W, int32_t H, const float* grad_chem_next, float sigma, float decay, int64_t N,
                           const int32_t* cells, float* grad_chem, float* grad_deposit, void* stream);
+
+/* ---- The same adjoint for the replicas of a die_batch (die_env_grad.hip, die_nca_grad.hip; BatchedEnv.differentiable_step) -------
+ * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
+ * Replica r of every call below computes, bit for bit, what its stand-alone twin above computes on that world alone. */
+
+/* die_deposit_cells for every replica in one launch (replica in blockIdx.y).  `m`, `a` describe replica 0, the claim planes
+ * b->plane_stride and the agent arrays b->agent_stride apart; batched agents are in slot order (a->slot must be NULL), so entry
+ * n's slot id is n.  cells_out[r * agent_stride + n] = ix * m->H + iy (the cell within replica r's plane) under die_deposit_cells'
+ * rule for n < b->n[r], -1 otherwise; the padding b->n[r] <= n < agent_stride is written -1, so all replicas * agent_stride words
+ * are written.  Refused as die_deposit_cells refuses, and: replicas outside 1..DIE_MAX_REPLICAS, plane_stride < W * H,
+ * agent_stride < a->N, a b->n[r] outside 0..agent_stride. */
+int die_deposit_cells_batch(const die_medium* m, const die_agents* a, const die_batch* b, int32_t* cells_out, void* stream);
+
+/* die_env_step_backward for every replica: grad_chem_next and grad_chem are b->replicas fp32 planes b->plane_stride apart (16-byte
+ * aligned, plane_stride a multiple of 4), cells and grad_deposit rows of b->agent_stride entries.
+ *   rows == NULL (and rows_host == NULL): one sweep launch for all replicas with the taps and (1 - decay) of (sigma, decay), built as
+ *     die_diffuse_decay builds them.  Otherwise both tables of a die_*_env_step_batch_rows call: replica r is swept with rows[r]'s
+ *     taps and keep, one launch per radius present; sigma and decay are ignored.
+ *   Then one gather launch: grad_deposit[r * agent_stride + n] = cells[...] in [0, W * H) ? grad_chem_r[cells[...]] : 0 for
+ *     n < b->n[r], and 0 for the padding up to agent_stride.  grad_deposit == NULL: the field part only (cells, agent_stride and n[]
+ *     are not read).
+ * No atomics, every output written once.  Refused before any launch: a null plane or batch, replicas outside 1..DIE_MAX_REPLICAS,
+ * plane_stride < W * H, buffers that overlap (grad_chem with grad_chem_next; grad_deposit with either or with cells), one table
+ * without the other, H % 4 != 0 or a radius outside 1..4 (DIE_ERR_UNSUPPORTED: a batched world always has the row sweep),
+ * misaligned planes, and with grad_deposit null cells or a b->n[r] outside 0..agent_stride. */
+int die_env_step_backward_batch(int32_t W, int32_t H, const die_batch* b, const float* grad_chem_next, float sigma, float decay,
+                                const die_dynamics_row* rows, const die_dynamics_row* rows_host, const int32_t* cells,
+                                float* grad_chem, float* grad_deposit, void* stream);
+
+/* die_nca_backward_batch whose layer-0 launch also writes the gradient at the first layer's cin input planes (the kernel's has_gin
+ * path, as for the layers above it): replica r's planes start at grad_in + r * grad_in_stride, W * H apart, in the layer's channel
+ * order ([agents,] food, chem).  The weight gradient is bit for bit die_nca_backward_batch's; replica r's input gradient is bit for
+ * bit die_conv2d_backward's grad_in on that world.  grad_in_stride >= cin * W * H; where H % 4 == 0 grad_in is 16-byte aligned and
+ * grad_in_stride a multiple of 4; grad_in may overlap none of the call's other buffers. */
+int die_nca_backward_batch_inputs(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store,
+                                  const float* grad_sense, int64_t sense_stride, float* grad, int64_t grad_stride,
+                                  const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, float* grad_in,
+                                  int64_t grad_in_stride, void* stream);
 
 /* die_food_flow_batch on the replicas whose bit is set in replica_mask (bit r = replica r); the others' planes are not touched.
  * One launch: a row of workgroups per replica, those of unset replicas exit at once.  A full mask leaves exactly what
