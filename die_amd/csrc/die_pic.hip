@@ -33,6 +33,7 @@
 // path: die_agents_mark_owner materialises it when somebody asks (DeviceMedium.occupied / owner_slots / render).
 #include "die_forward.h"
 #include <stdlib.h>
+#include <atomic>
 #include <mutex>
 #include <vector>
 
@@ -204,8 +205,8 @@ template <bool TILED> __device__ __forceinline__ int pic_col(const die_geo& g, u
     const int c = die_cell((int64_t)Y, g.gH);
     return TILED ? die_plane_coord(c, g.oy, g.H, g.gH) : c;
 }
-template <bool TILED> __device__ __forceinline__ int pic_tile_of(const PicArgs& p, uint32_t X, uint32_t Y) {
-    return (pic_row<TILED>(p.g, X) >> p.xs) * p.nty + (pic_col<TILED>(p.g, Y) >> p.ys);
+template <bool TILED> __device__ __forceinline__ int pic_tile_of(const PicArgs& p, int xs, int ys, uint32_t X, uint32_t Y) {
+    return (pic_row<TILED>(p.g, X) >> xs) * p.nty + (pic_col<TILED>(p.g, Y) >> ys);
 }
 
 // The 9 index ranges that hold the agents standing on `tile` in layout L: [0] its own stayers, [1..8] the leavers of the
@@ -319,8 +320,59 @@ static_assert(PIC_LIST_CAP >= PIC_K1_BLOCK, "the first round of candidates is on
 // streams are out — they then issue their loads ahead of the resident workgroups' chunk loops: 83.5 → 81.4 µs —, at 0 through the
 // chunk loop, and at 3 again for the epilogue; raising the chunk loop, or the waves that take a second chunk, was worse
 // (LABBOOK.md, rounds 3 and 6).
-template <typename T, int KIND, bool STAGE, bool ACT, bool RIM, bool TILED, bool MOM = false>
+// What the host knows when it launches, as the kernel's LAST template argument (behind MOM: tools find the instantiations by the
+// prefix of their names).  PicK1Generic: everything is read from PicArgs, as ever.  PicK1Cfg: tile shape, margins, workgroup size,
+// boundary, cost operator, rim radius and rim capacity are constants of the instantiation — the host launches one only for a call
+// that matches all of them (pic_k1_matches) —, so their scalars, shifts, multiplies and branches fold away in the prologue, the
+// staging loops and the chunk loop.  ONE body: PicK1Shape hands out either the constant or the field.
+struct PicK1Generic { static constexpr bool FIXED = false; };
+// ON: an opaque copy of a wave-uniform / a per-lane value — what the compiler derives from it (a byte offset, a comparison's lane mask)
+// is computed again where it is used, on the cold path, instead of being carried through the chunk loop in a spilled scalar pair
+template <bool ON> __device__ __forceinline__ int pic_fresh_s(int v) { if constexpr (ON) asm volatile("" : "+s"(v)); return v; }
+template <bool ON> __device__ __forceinline__ uint32_t pic_fresh_v(uint32_t v) { if constexpr (ON) asm volatile("" : "+v"(v)); return v; }
+template <int XS_, int YS_, int P_, int FR_, int FC_, int BLOCK_, int BOUNDARY_, int COST_, int R_, int RIM_CAP_>
+struct PicK1Cfg {
+    static constexpr bool FIXED = true;
+    static constexpr int XS = XS_, YS = YS_, P = P_, FR = FR_, FC = FC_, BLOCK = BLOCK_, BOUNDARY = BOUNDARY_, COST = COST_, R = R_, RIM_CAP = RIM_CAP_;
+    static_assert(BLOCK_ % DIE_WAVE == 0 && BLOCK_ >= DIE_WAVE && BLOCK_ <= PIC_K1_BLOCK && RIM_CAP_ <= PIC_RIM_CAP_MAX && RIM_CAP_ % 4 == 0, "agent kernel configuration");
+    // the staged rows' lane groups (PicStageRows): 16-byte vectors per row, rows per pass, and the multiply-shift for thread / vpr
+    static constexpr int vpr(int cells, int esz) { return cells * esz / 16; }
+    static constexpr uint32_t mg(int v) { return ((1u << 20) + (uint32_t)v - 1u) / (uint32_t)v; }
+    static constexpr bool mg_ok(int v) {
+        for (int i = 0; i < BLOCK_; ++i) if ((int)(((uint32_t)i * mg(v)) >> 20) != i / v) return false;
+        return v >= 1 && v <= 64;
+    }
+};
+template <class CFG, typename T>
+struct PicK1Shape {
+    const PicArgs& p;
+#define PIC_K1_CONST(name, constant, field) \
+    __device__ __forceinline__ int name() const { if constexpr (CFG::FIXED) return CFG::constant; else return p.field; }
+    PIC_K1_CONST(xs, XS, xs) PIC_K1_CONST(ys, YS, ys) PIC_K1_CONST(margin, P, margin) PIC_K1_CONST(fm_r, FR, fm_r) PIC_K1_CONST(fm_c, FC, fm_c)
+    PIC_K1_CONST(boundary, BOUNDARY, boundary) PIC_K1_CONST(cost, COST, cost) PIC_K1_CONST(rim_r, R, rim_r) PIC_K1_CONST(rim_cap, RIM_CAP, rim_cap)
+#undef PIC_K1_CONST
+    __device__ __forceinline__ uint32_t block() const { if constexpr (CFG::FIXED) return (uint32_t)CFG::BLOCK; else return blockDim.x; }
+    __device__ __forceinline__ uint32_t mg_c() const {
+        if constexpr (CFG::FIXED) {
+            constexpr int v = CFG::vpr((1 << CFG::YS) + 2 * CFG::P, (int)sizeof(T));
+            static_assert(CFG::mg_ok(v) && CFG::P % (16 / (int)sizeof(T)) == 0, "staged chem rows");
+            return CFG::mg(v);
+        } else return p.mg_c;
+    }
+    __device__ __forceinline__ uint32_t mg_f() const {
+        if constexpr (CFG::FIXED) {
+            constexpr int v = CFG::vpr((1 << CFG::YS) + 2 * CFG::FC, (int)sizeof(T));
+            static_assert(CFG::mg_ok(v) && CFG::FC % (16 / (int)sizeof(T)) == 0, "staged food rows");
+            return CFG::mg(v);
+        } else return p.mg_f;
+    }
+    __device__ __forceinline__ int rp_c() const { if constexpr (CFG::FIXED) return CFG::BLOCK / CFG::vpr((1 << CFG::YS) + 2 * CFG::P, (int)sizeof(T)); else return p.rp_c; }
+    __device__ __forceinline__ int rp_f() const { if constexpr (CFG::FIXED) return CFG::BLOCK / CFG::vpr((1 << CFG::YS) + 2 * CFG::FC, (int)sizeof(T)); else return p.rp_f; }
+};
+template <typename T, int KIND, bool STAGE, bool ACT, bool RIM, bool TILED, bool MOM = false, class CFG = PicK1Generic>
 __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : PIC_K1_MINW)) void k_pic_forward_move(FwdArgs f, PicArgs p) {
+    static_assert(!CFG::FIXED || (STAGE && RIM && !TILED && !MOM), "compile-time shapes: the staged two-launch form of an undivided world");
+    const PicK1Shape<CFG, T> K = {p};
     // (a starting workgroup's FIRST instructions already run at raised priority: its ≈ 300 instructions of prologue otherwise queue
     // behind the resident workgroups' chunk loops — round 6, profiles/r06_cu_timeline_4096.txt)
     __builtin_amdgcn_s_setprio(3);
@@ -334,6 +386,7 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
     f.pgx = MOM ? (float*)p.ipgx : nullptr; f.pgy = MOM ? (float*)p.ipgy : nullptr; f.step_base = nullptr; f.mask = nullptr;
     if (!MOM) { f.inertia = 0.f; f.noise_scale = 0.f; }
     f.normalized = 1;
+    if constexpr (CFG::FIXED) { p.g.gW = p.g.W; p.g.gH = p.g.H; }      // (an undivided world — die_geo_of: the planes ARE the world; one scalar per axis)
     f.g = p.g;                            // one copy of the geometry
     // The array pointers are needed at a few places each — the streams once per chunk, the epilogue's once per tile.  Kept in
     // scalar registers from the kernel's entry they (106 registers + 70 spilled to vector lanes, every use a v_readlane and a
@@ -344,6 +397,9 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
     static_assert(alignof(FwdArgs) == 8 && alignof(PicArgs) == 8 && sizeof(FwdArgs) % 8 == 0, "kernel-argument layout of k_pic_forward_move");
     const volatile KArgs __attribute__((address_space(4)))* ka = (const volatile KArgs __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
 #define PIC_KP(field, type) ((type)ka->p.field)
+    // (… and, in a specialised instantiation, the pointers of the tile's last words and of the error word too: the last scalars it
+    // would otherwise carry through the chunk loop in vector lanes)
+#define PIC_KPF(field, type) (CFG::FIXED ? (type)ka->p.field : (type)p.field)
     extern __shared__ __align__(16) unsigned char pic_smem[];     // STAGE: chem of the tile ± margin, then food of the tile ± its margin
     __shared__ uint32_t s_base[9], s_pre[10];                     // ranges of the current tile
     __shared__ unsigned long long s_cnt;                           // stayers | leavers << 21 | rim entries << 42: one LDS atomic per wave and chunk
@@ -354,19 +410,19 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
     __shared__ long long s_gain[PIC_K1_BLOCK / DIE_WAVE];
     __shared__ uint32_t s_alv[TILED ? PIC_K1_BLOCK / DIE_WAVE : 1];   // TILED: agents this rank accounts for (die_medium.own_*)
     const int NT = p.ntx * p.nty;
-    const int TX = 1 << p.xs, TY = 1 << p.ys;
-    const int lane = threadIdx.x & (DIE_WAVE - 1), wave = threadIdx.x / DIE_WAVE, nwaves = blockDim.x / DIE_WAVE;
+    const int TX = 1 << K.xs(), TY = 1 << K.ys();
+    const int lane = threadIdx.x & (DIE_WAVE - 1), wave = threadIdx.x / DIE_WAVE, nwaves = K.block() / DIE_WAVE;
     const unsigned long long below = (1ull << lane) - 1ull;
     const T* food = (const T*)p.food;
     constexpr int SV = 16 / (int)sizeof(T);
-    const int P = p.margin, pitch = TY + 2 * P, rows = TX + 2 * P;
-    const int FR = p.fm_r, FC = p.fm_c, fpitch = TY + 2 * FC, frows = TX + 2 * FR;
+    const int P = K.margin(), pitch = TY + 2 * P, rows = TX + 2 * P;
+    const int FR = K.fm_r(), FC = K.fm_c(), fpitch = TY + 2 * FC, frows = TX + 2 * FR;
     // the tile of this workgroup
     int tx = (int)blockIdx.y, ty = (int)blockIdx.x;
     bool by_table = false;
     if (p.order && !pic_order_tile(p, blockIdx.y * (uint32_t)p.nty + blockIdx.x, tx, ty, by_table)) return;
-    if (!by_table && p.sub_mode == 0) pic_xcd_tile(tx, ty, p.ntx, 0, p.xcd_wb_mul, (uint32_t)p.nty);
-    if (!pic_sub_tile(p, tx, ty)) return;
+    if (!by_table && (CFG::FIXED || p.sub_mode == 0)) pic_xcd_tile(tx, ty, p.ntx, 0, p.xcd_wb_mul, (uint32_t)p.nty);
+    if constexpr (!CFG::FIXED) { if (!pic_sub_tile(p, tx, ty)) return; }      // (FIXED: all tiles — pic_k1_matches)
     const int tile = tx * p.nty + ty;
     (void)NT;
     // the per-tile counters
@@ -399,14 +455,14 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
             pA = PIC_AT(p.in.agent_food, const float, j);
         }
     };
-    const int x0 = tx << p.xs, y0 = ty << p.ys;
+    const int x0 = tx << K.xs(), y0 = ty << K.ys();
     __builtin_amdgcn_s_setprio(3);        // (already 3 since the entry; the loads below go out at 3, the chunk loop runs at 0)
     // 1st round trip: the per-tile words (small arrays, L2-resident).  Requested FIRST: vector loads return in order, so a
     // word requested behind the tile loads would only arrive after all of them (timestamps: 6 600 cycles for this phase).
     const PicMeta mt = pic_meta_load(p.in, tx, ty, p.ntx, p.nty);
     // the tiles to stage depend on nothing but the tile index: their loads go out next and overlap both round trips
-    const PicStageRows<T, false> st_c = {(const T*)f.chem, x0 - P, y0 - P, pitch / SV, rows, p.g.W, p.g.H, p.mg_c, p.rp_c};
-    const PicStageRows<T, true> st_f = {food, x0 - FR, y0 - FC, fpitch / SV, frows, p.g.W, p.g.H, p.mg_f, p.rp_f};
+    const PicStageRows<T, false> st_c = {(const T*)f.chem, x0 - P, y0 - P, pitch / SV, rows, p.g.W, p.g.H, K.mg_c(), K.rp_c()};
+    const PicStageRows<T, true> st_f = {food, x0 - FR, y0 - FC, fpitch / SV, frows, p.g.W, p.g.H, K.mg_f(), K.rp_f()};
     uint4 sc[4], sf[3];                   // 64×64 tile, 512 threads: chem ± 12 cells = 88 × 22 vectors, food ± 3 rows = 70 × 16
     if (STAGE) {
         st_c.issue(sc);
@@ -436,19 +492,19 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
     // compacted into s_list first so that the heavy part below runs on full waves.  One round unless a crowd arrives.
     for (uint32_t cb = 0; cb == 0 || cb < ncand; cb += PIC_LIST_CAP) {
         const uint32_t cend = min(cb + (uint32_t)PIC_LIST_CAP, ncand);
-        for (uint32_t c0 = cb; c0 < cend; c0 += blockDim.x) {      // wave-uniform trip count
+        for (uint32_t c0 = cb; c0 < cend; c0 += K.block()) {      // wave-uniform trip count
             const uint32_t c = c0 + threadIdx.x;
             bool hit = false;
             uint32_t j = 0;
             if (c0 == 0) {                                         // loaded above
                 j = cj;
-                hit = chas && pic_tile_of<TILED>(p, cX, cY) == tile;
+                hit = chas && pic_tile_of<TILED>(p, K.xs(), K.ys(), cX, cY) == tile;
             } else if (c < cend) {
                 const uint32_t idx = own + c;
                 int r = 1;
                 while (idx >= s_pre[r + 1]) ++r;
                 j = s_base[r] + (idx - s_pre[r]);
-                hit = pic_tile_of<TILED>(p, PIC_AT(p.in.x, const uint32_t, j), PIC_AT(p.in.y, const uint32_t, j)) == tile;
+                hit = pic_tile_of<TILED>(p, K.xs(), K.ys(), PIC_AT(p.in.x, const uint32_t, j), PIC_AT(p.in.y, const uint32_t, j)) == tile;
             }
             const unsigned long long m = __ballot(hit);
             uint32_t at = 0;
@@ -494,10 +550,13 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
                 const FwdOut o = STAGE ? die_forward_agent_mem<T, KIND, false, FwdTileMem<T, TILED>, true, false>(f, tm, X, Y, hd, sid, (int64_t)j)
                                        : die_forward_agent_mem<T, KIND, false, FwdGlobalMem<T, false>, true, false>(f, FwdGlobalMem<T, false>(f), X, Y, hd, sid, (int64_t)j);
                 if (MOM) { pux = o.ux; puy = o.uy; }
-                if (ACT && p.adx) { PIC_AT(p.adx, float, j) = o.dx; PIC_AT(p.ady, float, j) = o.dy; PIC_AT(p.adep, float, j) = o.dep; }   // ACT = false: the caller passed no action arrays
+                if (ACT && (CFG::FIXED || p.adx)) {       // ACT = false: the caller passed no action arrays (FIXED: ACT says it all — forward_move_kernel)
+                    float *adx_ = PIC_KPF(adx, float*), *ady_ = PIC_KPF(ady, float*), *adep_ = PIC_KPF(adep, float*);
+                    PIC_AT(adx_, float, j) = o.dx; PIC_AT(ady_, float, j) = o.dy; PIC_AT(adep_, float, j) = o.dep;
+                }
                 // _agent_move (core/env.py:163-172)
                 // (a step is shorter than a tile — checked on the host — so the fixed-point increment needs no float64 path)
-                if (p.boundary == DIE_BOUNDARY_WRAP) {
+                if (K.boundary() == DIE_BOUNDARY_WRAP) {
                     X += (uint32_t)die_q32_small(o.dx);
                     Y += (uint32_t)die_q32_small(o.dy);
                 } else {
@@ -508,7 +567,7 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
                 const int gcx = die_cell_u(X, p.g.gW), gcy = die_cell_u(Y, p.g.gH);                      // world cell …
                 const int cx = TILED ? die_plane_coord(gcx, p.g.ox, p.g.W, p.g.gW) : gcx;                // … and where the planes hold it
                 const int cy = TILED ? die_plane_coord(gcy, p.g.oy, p.g.H, p.g.gH) : gcy;
-                const int ntx_ = cx >> p.xs, nty_ = cy >> p.ys;
+                const int ntx_ = cx >> K.xs(), nty_ = cy >> K.ys();
                 stay = ntx_ == tx && nty_ == ty;
                 // _agent_feed for this (alive) agent (core/env.py:220-243): the food under it BEFORE this step's consumption —
                 // from the staged food block, whose margin holds every cell an agent of the tile can reach in one step (a flat
@@ -529,7 +588,7 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
                     fnew = die_ld(food, (int64_t)cx * p.g.H + cy);
                 }
                 const float consumed = p.rate_feed * fnew;
-                const float cost = p.cost == DIE_COST_LINEAR ? p.w_dep * fabsf(o.dep) + p.w_dist * die_sqrt1(o.dx * o.dx + o.dy * o.dy) : 0.f;
+                const float cost = K.cost() == DIE_COST_LINEAR ? p.w_dep * fabsf(o.dep) + p.w_dist * die_sqrt1(o.dx * o.dx + o.dy * o.dy) : 0.f;
                 const float gained = consumed - cost;
                 af += gained;
                 // (a ghost is its owner's to count; die_owned on the plane element: a cell beyond the planes maps to an edge element, never owned)
@@ -541,14 +600,14 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
                     ddx = ntx_ - tx; ddy = nty_ - ty;
                     ddx = ddx > 1 ? ddx - p.ntx : (ddx < -1 ? ddx + p.ntx : ddx);
                     ddy = ddy > 1 ? ddy - p.nty : (ddy < -1 ? ddy + p.nty : ddy);
-                    if (ddx < -1 || ddx > 1 || ddy < -1 || ddy > 1) { atomicOr(p.error, 2u); ddx = ddy = 0; }
+                    if (ddx < -1 || ddx > 1 || ddy < -1 || ddy > 1) { atomicOr(PIC_KPF(error, uint32_t*), 2u); ddx = ddy = 0; }
                     else atomicAdd(&s_inc[(ddx + 1) * 3 + ddy + 1], 1u);   // one global atomic per neighbour at the end (2.5 M
                 }                                                          // agents: 11 µs of contended global atomics otherwise)
                 if (RIM) {
                     // the field kernel of a tile diffuses that tile's cells and so needs the deposits on the R cells around it
                     // too: listed for it are the agents that walked off this tile and those that stand within R cells of a
                     // border of their (new) tile
-                    const int lx = cx & (TX - 1), ly = cy & (TY - 1), Rr = p.rim_r;
+                    const int lx = cx & (TX - 1), ly = cy & (TY - 1), Rr = K.rim_r();
                     const int ex = lx < Rr ? 0 : (lx >= TX - Rr ? 2 : 1), ey = ly < Rr ? 0 : (ly >= TY - Rr ? 2 : 1);
                     code = (uint32_t)(((ddx + 1) * 3 + ddy + 1) * 9 + ex * 3 + ey);
                     listed = !stay || ex != 1 || ey != 1;
@@ -566,9 +625,9 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
             const uint32_t k = stay ? bf + (uint32_t)__popcll(m_stay & below) : on - 1u - (bb + (uint32_t)__popcll(m_leave & below));
             if (RIM && act && listed) {
                 const uint32_t at = br + (uint32_t)__popcll(m_rim & below);
-                if (at < (uint32_t)p.rim_cap) {
+                if (at < (uint32_t)K.rim_cap()) {
                     s_rimc[at] = (uint8_t)code;
-                    PIC_KP(rim, uint4*)[(size_t)tile * p.rim_cap + at] = make_uint4(X, Y, sid, __float_as_uint(dep));
+                    PIC_KP(rim, uint4*)[(size_t)tile * K.rim_cap() + at] = make_uint4(X, Y, sid, __float_as_uint(dep));
                 }
             }
             if (act) {
@@ -593,7 +652,7 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
         }
         if (cb + PIC_LIST_CAP < ncand) {                           // another round (rare): reset the work counters
             PA_BARRIER();
-            if (threadIdx.x == 0) { s_next = 0; s_nlist = 0; }
+            if (pic_fresh_v<CFG::FIXED>(threadIdx.x) == 0) { s_next = 0; s_nlist = 0; }
             PA_BARRIER();
         }
     }
@@ -620,10 +679,10 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
     }
     if (RIM && wave == w_rim) {
         // (a segment too long for the 24-bit positions counts as an overflowing list: the reader scans it)
-        const uint32_t nr = on >= (1u << 21) ? (uint32_t)p.rim_cap + 1u : (uint32_t)(s_cnt >> 42) & 0x1FFFFFu;
+        const uint32_t nr = on >= (1u << 21) ? (uint32_t)K.rim_cap() + 1u : (uint32_t)(s_cnt >> 42) & 0x1FFFFFu;
         // (the address first, then the LDS read: the other order leaves the compiler other registers — the same work)
-        for (uint32_t i = (uint32_t)lane; i < (min(nr, (uint32_t)p.rim_cap) + 3u) / 4u; i += DIE_WAVE) {
-            uint32_t* const w = &((uint32_t*)e_rimc)[((size_t)tile * p.rim_cap) / 4 + i];
+        for (uint32_t i = (uint32_t)lane; i < (min(nr, (uint32_t)K.rim_cap()) + 3u) / 4u; i += DIE_WAVE) {
+            uint32_t* const w = &((uint32_t*)e_rimc)[((size_t)tile * K.rim_cap()) / 4 + i];
             *w = ((const uint32_t*)s_rimc)[i];
         }
         if (lane == 0) e_rimn[tile] = nr;
@@ -636,8 +695,8 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
             e_gain[tile] = t;
             if (TILED) e_gain[(size_t)p.ntx * p.nty + tile] = c;               // second half of the array: owned agents per tile
             const uint32_t nfront = (uint32_t)s_cnt & 0x1FFFFFu, nback = (uint32_t)(s_cnt >> 21) & 0x1FFFFFu;
-            p.out.s[tile] = nfront;
-            if (nfront + nback != on || on >= (1u << 21)) atomicOr(p.error, 1u);
+            PIC_KPF(out.s, uint32_t*)[pic_fresh_s<CFG::FIXED>(tile)] = nfront;
+            if (nfront + nback != on || on >= (1u << 21)) atomicOr(PIC_KPF(error, uint32_t*), 1u);
         }
     }
 }
@@ -1615,10 +1674,47 @@ static void launch_resolve(const PicArgs& k, float* dep_plane, int NT, bool f32,
     }
 }
 
-// the agent kernel's instantiation for an agent kind (`act`: the action is handed back; `mom`: GradientAgent with momentum)
+// The agent kernel's SPECIALISED instantiations (PicK1Cfg: shape, margins, workgroup size, boundary, cost, rim as constants): the
+// headline world's — fp32 planes, 64×64 tiles, a probe of up to 10 cells (chem margin 12), a step shorter than 2 cells (food margin
+// 3 rows) — and the fp16 default's, 32×128 tiles with the same agent (chem margin 16: whole 8-element vectors); both with 512
+// threads, periodic boundary, linear cost, gaussian radius 2.  A PhysarumAgent's staged two-launch step over all tiles of an undivided
+// world only; every other call takes the generic instantiation.
+template <typename T> struct PicK1Special;
+template <> struct PicK1Special<float> { typedef PicK1Cfg<6, 6, 12, 3, 0, 512, DIE_BOUNDARY_WRAP, DIE_COST_LINEAR, 2, KbShape<6, 6>::RIM_CAP> Cfg; };
+template <> struct PicK1Special<__half> { typedef PicK1Cfg<5, 7, 16, 3, 0, 512, DIE_BOUNDARY_WRAP, DIE_COST_LINEAR, 2, KbShape<5, 7>::RIM_CAP> Cfg; };
+template <class CFG> static bool pic_k1_matches(const PicArgs& k, int block) {
+    return k.xs == CFG::XS && k.ys == CFG::YS && k.margin == CFG::P && k.fm_r == CFG::FR && k.fm_c == CFG::FC && block == CFG::BLOCK &&
+           k.boundary == CFG::BOUNDARY && k.cost == CFG::COST && k.rim_r == CFG::R && k.rim_cap == CFG::RIM_CAP && k.sub_mode == 0;
+}
+// DIE_PIC_K1_GENERIC=1 in the environment (read once), or die_pic_k1_generic(1): every call takes the generic instantiation — the
+// same bits (tests/test_gpu_k1_specialised.py); for A/B measurements.  g_pic_k1_special: launches of a specialised instantiation.
+static std::atomic<int> g_pic_k1_generic{-1};
+static std::atomic<long long> g_pic_k1_special{0};
+static bool pic_k1_generic_forced() {
+    int v = g_pic_k1_generic.load(std::memory_order_relaxed);
+    if (v < 0) {
+        const char* e = getenv("DIE_PIC_K1_GENERIC");
+        v = e && e[0] == '1' && !e[1] ? 1 : 0;
+        g_pic_k1_generic.store(v, std::memory_order_relaxed);
+    }
+    return v != 0;
+}
+extern "C" void die_pic_k1_generic(int32_t force) { g_pic_k1_generic.store(force < 0 ? -1 : (force ? 1 : 0), std::memory_order_relaxed); }
+extern "C" int64_t die_pic_k1_specialised_launches(void) { return (int64_t)g_pic_k1_special.load(std::memory_order_relaxed); }
+
+// the agent kernel's instantiation for an agent kind (`act`: the action is handed back; `mom`: GradientAgent with momentum) and a
+// call's arguments (`k`, `block`: a specialised instantiation when they match one; k = NULL: the generic one)
 typedef void (*PicK1Fn)(FwdArgs, PicArgs);
 template <typename T, bool STAGE, bool RIM, bool TILED = false>
-static PicK1Fn forward_move_kernel(int kind, bool act, bool mom) {
+static PicK1Fn forward_move_kernel(int kind, bool act, bool mom, const PicArgs* k = nullptr, int block = 0, bool* special = nullptr) {
+    if constexpr (STAGE && RIM && !TILED) {
+        typedef typename PicK1Special<T>::Cfg Cfg;
+        if (k && kind == DIE_AGENT_PHYSARUM && !mom && pic_k1_matches<Cfg>(*k, block) && !pic_k1_generic_forced()) {
+            if (special) *special = true;
+            if (act) return k_pic_forward_move<T, DIE_AGENT_PHYSARUM, true, true, true, false, false, Cfg>;
+            return k_pic_forward_move<T, DIE_AGENT_PHYSARUM, true, false, true, false, false, Cfg>;
+        }
+    }
     if constexpr (!TILED) {
         if (kind != DIE_AGENT_PHYSARUM && mom) return k_pic_forward_move<T, DIE_AGENT_GRADIENT, STAGE, true, RIM, false, true>;
     }
@@ -1631,7 +1727,9 @@ template <typename T, bool STAGE, bool RIM, bool TILED = false>
 static void launch_forward_move(int kind, const FwdArgs& f, const PicArgs& k, int NT, int block, size_t lds, hipStream_t s, bool mom = false) {
     // (an order table covers exactly the tiles: 8 · order_len = ntx · nty workgroups, the same grid)
     const dim3 grid(k.sub_mode == 1 ? k.sub_nty : k.nty, k.sub_mode == 1 ? k.sub_ntx : k.ntx);
-    forward_move_kernel<T, STAGE, RIM, TILED>(kind, k.adx != nullptr, mom)<<<grid, block, lds, s>>>(f, k);
+    bool special = false;
+    forward_move_kernel<T, STAGE, RIM, TILED>(kind, k.adx != nullptr, mom, &k, block, &special)<<<grid, block, lds, s>>>(f, k);
+    if (special) g_pic_k1_special.fetch_add(1, std::memory_order_relaxed);
 }
 
 // Workgroups of an agent-kernel instantiation the device holds at once: CUs × resident workgroups per CU at this workgroup size and
@@ -1827,8 +1925,8 @@ extern "C" int die_pic_forward_env_step(const die_medium* m, const die_pic* p, i
                 if (slots == 0) {
                     const bool act_out = k.adx != nullptr;
                     const PicK1Fn fn = m->dtype == DIE_F32
-                        ? (stage ? forward_move_kernel<float, true, true>(g->kind, act_out, mom) : forward_move_kernel<float, false, true>(g->kind, act_out, mom))
-                        : (stage ? forward_move_kernel<__half, true, true>(g->kind, act_out, mom) : forward_move_kernel<__half, false, true>(g->kind, act_out, mom));
+                        ? (stage ? forward_move_kernel<float, true, true>(g->kind, act_out, mom, &k, block) : forward_move_kernel<float, false, true>(g->kind, act_out, mom))
+                        : (stage ? forward_move_kernel<__half, true, true>(g->kind, act_out, mom, &k, block) : forward_move_kernel<__half, false, true>(g->kind, act_out, mom));
                     slots = pic_agent_slots(fn, block, stage ? lds : 0);
                 }
             }

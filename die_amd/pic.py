@@ -95,6 +95,9 @@ class PicState:
         i32 = lambda: torch.empty(N, dtype=torch.int32, device=dev)
         self.spare = [i32(), i32(), torch.empty(N, dtype=torch.float32, device=dev), i32(), i32()]     # x, y, agent_food, heading hi / lo
         self.spare_pg = None         # GradientAgent with inertia: the (2, N) _prev_grad array of the layout that is not current (die_pic.prev_grad)
+        # DIE_PIC_K1_GENERIC=1: the agent kernel's generic instantiation even where a specialised one matches (include/die_hip.h
+        # die_pic_k1_generic; process-wide, set whenever a step's state is created) — the same bits, for A/B measurements
+        _lib.lib.die_pic_k1_generic(1 if os.environ.get('DIE_PIC_K1_GENERIC', '0') == '1' else 0)
         self.k1_threads = int(os.environ.get('DIE_PIC_THREADS', '0'))   # die_pic.k1_threads: 0 = library default, > 0: workgroup size of the agent kernel
         self.cur = 0                 # layout index that holds the agents
         self.held = None             # (x, y, agent_food, slot, heading hi, lo) tensors of layout[cur] — identity = validity

@@ -601,6 +601,16 @@ int die_pic_run(const die_medium* m, const die_pic* p, int32_t from, const die_g
  * launch) — the caller adopts the state those steps reach (layout (from + done) & 1, the chem plane roles exchanged `done`
  * times, step counter + done) before it reports the error.  ABI 22. */
 int32_t die_pic_run_completed(void);
+/* The agent kernel of die_pic_forward_env_step has SPECIALISED instantiations — tile shape, margins, workgroup size, boundary, cost
+ * operator and rim as compile-time constants: fp32 planes with 64x64 tiles and fp16 planes with 32x128 tiles, a PhysarumAgent probing
+ * up to 10 cells ahead and walking less than 2 cells per step, 512 threads, periodic boundary, linear cost, gaussian radius 2, the
+ * staged two-launch form over all tiles of an undivided world — which a call that matches one of them takes; every other call takes the
+ * generic instantiation.  Same bits either way.  die_pic_k1_generic(1) makes every call of this process take the generic one (A/B
+ * measurements, tests), (0) lifts that, (-1) goes by the environment: DIE_PIC_K1_GENERIC=1, read once at the next step.
+ * die_pic_k1_specialised_launches(): launches of a specialised instantiation by this process so far.
+ * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24. */
+void die_pic_k1_generic(int32_t force);
+int64_t die_pic_k1_specialised_launches(void);
 /* `act` of die_pic_forward_env_step may be NULL: the action then stays in registers.  For a normalised PhysarumAgent it can
  * still be produced afterwards — until the next step overwrites p->dep — from what the step left in layout[lay] (the layout it
  * WROTE): (dx, dy) = scale * polar2xy(1, heading'), deposit = p->dep; same bits as the action the step would have stored, in
