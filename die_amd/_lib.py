@@ -314,6 +314,7 @@ _SIGNATURES = {
     'die_pic_run_completed': (C.c_int32, []),
     'die_pic_k1_generic': (None, [C.c_int32]),
     'die_pic_k1_specialised_launches': (C.c_int64, []),
+    'die_wave_sum_i64_check': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     'die_agents_mark_owner': (C.c_int, [_P(Medium), _P(Agents), C.c_void_p]),
     'die_pic_action_physarum': (C.c_int, [_P(Pic), C.c_int32, _P(GradientAgent), _P(Action), C.c_void_p]),
     'die_pic_ghost_pack': (C.c_int, [_P(Medium), _P(Pic), C.c_int32, C.c_int32, _P(PicSide), C.c_void_p, C.c_void_p]),

@@ -231,6 +231,28 @@ __device__ __forceinline__ long long die_wave_sum(long long v) {
     for (int o = DIE_WAVE / 2; o > 0; o >>= 1) v += __shfl_down(v, o, DIE_WAVE);
     return v;
 }
+// The same sum for a WHOLE wave (all 64 lanes active: the caller's control flow must be wave-uniform here), without LDS: the
+// shuffle form above is six dependent pairs of ds_bpermute_b32, each an LDS round trip.  Data-parallel-primitive moves instead:
+// an inclusive scan inside each row of 16 lanes (row_shr 1/2/4/8; a lane without a source adds 0), then lane 15 of rows 0 and 2
+// into rows 1 and 3 (row_bcast:15, row mask 0xA) and lane 31 into rows 2 and 3 (row_bcast:31, row mask 0xC): lane 63 holds the
+// total, which comes back wave-uniform (v_readlane).  Both halves of a lane's value move together and are added as 64 bits, so
+// carries are exact at every step.
+template <int CTRL, int ROW_MASK> __device__ __forceinline__ long long die_dpp_i64(long long v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, ROW_MASK, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)((unsigned long long)v >> 32), CTRL, ROW_MASK, 0xF, false);
+    return (long long)(((unsigned long long)(uint32_t)hi << 32) | (unsigned long long)(uint32_t)lo);
+}
+__device__ __forceinline__ long long die_wave_sum_i64_dpp(long long v) {
+    v += die_dpp_i64<0x111, 0xF>(v);      // row_shr:1
+    v += die_dpp_i64<0x112, 0xF>(v);      // row_shr:2
+    v += die_dpp_i64<0x114, 0xF>(v);      // row_shr:4
+    v += die_dpp_i64<0x118, 0xF>(v);      // row_shr:8
+    v += die_dpp_i64<0x142, 0xA>(v);      // row_bcast:15 → rows 1, 3
+    v += die_dpp_i64<0x143, 0xC>(v);      // row_bcast:31 → rows 2, 3
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, DIE_WAVE - 1);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((unsigned long long)v >> 32), DIE_WAVE - 1);
+    return (long long)(((unsigned long long)hi << 32) | (unsigned long long)lo);
+}
 
 // Groups the active lanes of the wave by key (no memory traffic), then every group's first lane issues ONE atomicAdd of
 // the group's size — all of a wave's atomics are in flight together — and the lanes get base + rank inside the group

@@ -1699,6 +1699,23 @@ extern "C" int die_agent_dead_slots(const die_medium* m, const die_agents* a, co
     return DIE_OK;
 }
 
+// ---- self-check of die_wave_sum_i64_dpp (die_common.h): one total per wave of 64 values --------------------------------
+__global__ __launch_bounds__(DIE_BLOCK) void k_wave_sum_i64_check(const long long* in, int64_t n_waves, long long* out) {
+    const int64_t w = (int64_t)blockIdx.x * (DIE_BLOCK / DIE_WAVE) + threadIdx.x / DIE_WAVE;
+    if (w >= n_waves) return;                                   // (wave-uniform: the waves that go on are whole)
+    const int lane = threadIdx.x & (DIE_WAVE - 1);
+    const long long t = die_wave_sum_i64_dpp(in[w * DIE_WAVE + lane]);
+    if (lane == 0) out[w] = t;
+}
+
+extern "C" int die_wave_sum_i64_check(const void* in, int64_t n_waves, void* out, void* stream) {
+    DIE_REQUIRE(in && out, "die_wave_sum_i64_check: null array");
+    DIE_REQUIRE(n_waves >= 1 && n_waves <= (1 << 20), "die_wave_sum_i64_check: n_waves %lld outside [1, 2^20]", (long long)n_waves);
+    k_wave_sum_i64_check<<<die_grid_for(n_waves * DIE_WAVE), DIE_BLOCK, 0, (hipStream_t)stream>>>((const long long*)in, n_waves, (long long*)out);
+    DIE_CHECK_LAUNCH("die_wave_sum_i64_check");
+    return DIE_OK;
+}
+
 // ---- error plumbing ---------------------------------------------------------------------
 static thread_local char g_err[512] = "";
 

@@ -249,6 +249,37 @@ __device__ __forceinline__ void pic_ranges_finish(const PicMeta& mt, uint32_t* b
     PA_BARRIER();
 }
 
+// The agent kernel's form of the same: the nine lengths (words 0–8) and the nine bases (words 9–17) go to LDS behind ONE barrier, and
+// every thread then reads all of them with five 16-byte reads issued together — one LDS round trip — and forms the prefix sums itself.
+// (pic_ranges_finish's scan by thread 0 and its second barrier, then a search loop of dependent reads of pre[] — one round trip per
+// range a candidate lies beyond, 6–8 for a workgroup's last waves — stood in front of the first loads of the agent streams: round 9.)
+#define PIC_RNG_WORDS 20
+// (named words rather than arrays: every one a register by construction, whatever an instantiation unrolls)
+struct PicRanges { uint32_t l0, l1, l2, l3, l4, l5, l6, l7, l8, b0, b1, b2, b3, b4, b5, b6, b7, b8; };
+__device__ __forceinline__ void pic_ranges_publish(const PicMeta& mt, uint32_t* rng, bool no_arrivals) {
+    if (threadIdx.x < 9) {
+        const bool own = threadIdx.x == 0;
+        rng[9 + threadIdx.x] = own ? mt.o : mt.o + mt.s;
+        rng[threadIdx.x] = mt.s > mt.n ? 0u : (own ? mt.s : (no_arrivals ? 0u : mt.n - mt.s));     // (s > n: broken bookkeeping — never loop over garbage)
+    }
+    PA_BARRIER();
+}
+__device__ __forceinline__ PicRanges pic_ranges_read(const uint32_t* rng) {      // rng: 16-byte aligned, PIC_RNG_WORDS words (the last two unused)
+    const uint4 a = ((const uint4*)rng)[0], b = ((const uint4*)rng)[1], c = ((const uint4*)rng)[2], d = ((const uint4*)rng)[3], e = ((const uint4*)rng)[4];
+    return {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w, e.x, e.y};
+}
+__device__ __forceinline__ uint32_t pic_ranges_candidates(const PicRanges& R) { return R.l1 + R.l2 + R.l3 + R.l4 + R.l5 + R.l6 + R.l7 + R.l8; }
+// array index of candidate c (c < pic_ranges_candidates: the c-th agent of ranges 1..8 laid end to end) — the range is the LAST one
+// whose first candidate is not beyond c: r = 1 + Σ_{q = 2..8} (c >= start[q]), by comparisons and selects.  An empty range starts where
+// the next one does, so it is passed over together with it, as by the loop `while (c >= start[r + 1]) ++r`.
+__device__ __forceinline__ uint32_t pic_cand_source(const PicRanges& R, uint32_t c) {
+    uint32_t start = 0, jb = R.b1;
+#define PIC_CAND_STEP(len_before, base_q) start += R.len_before; jb = c >= start ? R.base_q - start : jb;
+    PIC_CAND_STEP(l1, b2) PIC_CAND_STEP(l2, b3) PIC_CAND_STEP(l3, b4) PIC_CAND_STEP(l4, b5) PIC_CAND_STEP(l5, b6) PIC_CAND_STEP(l6, b7) PIC_CAND_STEP(l7, b8)
+#undef PIC_CAND_STEP
+    return jb + c;
+}
+
 // copy a rows × (vpr·V)-element block of a plane into LDS with 16-byte accesses.  Lane groups of EXACTLY `vpr` threads per row
 // (row r0 = thread / vpr by a multiply-shift the host has verified, blockDim / vpr rows per pass; the last blockDim % vpr threads
 // idle); a thread keeps ONE column vector and walks down the rows: per vector one add, the row's wrap or clamp, a multiply-add, the
@@ -401,14 +432,14 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
     // would otherwise carry through the chunk loop in vector lanes)
 #define PIC_KPF(field, type) (CFG::FIXED ? (type)ka->p.field : (type)p.field)
     extern __shared__ __align__(16) unsigned char pic_smem[];     // STAGE: chem of the tile ± margin, then food of the tile ± its margin
-    __shared__ uint32_t s_base[9], s_pre[10];                     // ranges of the current tile
+    __shared__ __align__(16) uint32_t s_rng[PIC_RNG_WORDS];       // ranges of the current tile: nine lengths, nine bases (pic_ranges_publish)
     __shared__ unsigned long long s_cnt;                           // stayers | leavers << 21 | rim entries << 42: one LDS atomic per wave and chunk
     __shared__ uint32_t s_next, s_nlist;
     __shared__ uint32_t s_inc[9];                                  // arrivals this tile sends to each neighbour: (ddx + 1)·3 + ddy + 1
     __shared__ __align__(4) uint8_t s_rimc[RIM ? PIC_RIM_CAP_MAX : 4];   // RIM: the codes of this tile's list (flushed as words)
     __shared__ uint32_t s_list[PIC_LIST_CAP];
-    __shared__ long long s_gain[PIC_K1_BLOCK / DIE_WAVE];
-    __shared__ uint32_t s_alv[TILED ? PIC_K1_BLOCK / DIE_WAVE : 1];   // TILED: agents this rank accounts for (die_medium.own_*)
+    __shared__ unsigned long long s_gain;                          // the tile's reward partial: every wave adds its total (integers: any order)
+    __shared__ uint32_t s_alv;                                     // TILED: agents this rank accounts for (die_medium.own_*)
     const int NT = p.ntx * p.nty;
     const int TX = 1 << K.xs(), TY = 1 << K.ys();
     const int lane = threadIdx.x & (DIE_WAVE - 1), wave = threadIdx.x / DIE_WAVE, nwaves = K.block() / DIE_WAVE;
@@ -426,35 +457,8 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
     const int tile = tx * p.nty + ty;
     (void)NT;
     // the per-tile counters
-    if (threadIdx.x == 0) { s_cnt = 0ull; s_next = (uint32_t)(nwaves * DIE_WAVE); s_nlist = 0; }
+    if (threadIdx.x == 0) { s_cnt = 0ull; s_next = (uint32_t)(nwaves * DIE_WAVE); s_nlist = 0; s_gain = 0ull; if (TILED) s_alv = 0u; }
     if (threadIdx.x < 9) s_inc[threadIdx.x] = 0;
-    // what the first pass needs from memory besides the windows: this thread's first candidate arrival and the six streams of
-    // this wave's first chunk of stayers
-    uint32_t cj = 0, cX = 0, cY = 0, pX = 0, pY = 0, pS = 0, pHh = 0, pHl = 0;
-    float pA = 0.f;
-    bool chas = false;
-    auto prefetch_agents = [&]() {
-        const uint32_t own = s_pre[1], ncand = s_pre[9] - own, base0 = s_base[0];
-        // this thread's first candidate arrival and the agent streams of this wave's first chunk of stayers
-        cj = 0; cX = 0; cY = 0;
-        chas = threadIdx.x < ncand;
-        if (chas) {
-            const uint32_t idx = own + threadIdx.x;
-            int r = 1;
-            while (idx >= s_pre[r + 1]) ++r;
-            cj = s_base[r] + (idx - s_pre[r]);
-            cX = PIC_AT(p.in.x, const uint32_t, cj);
-            cY = PIC_AT(p.in.y, const uint32_t, cj);
-        }
-        const uint32_t pidx = (uint32_t)(wave * DIE_WAVE + lane);
-        pX = 0; pY = 0; pS = 0; pHh = 0; pHl = 0; pA = 0.f;
-        if (pidx < own) {
-            const uint32_t j = base0 + pidx;
-            pX = PIC_AT(p.in.x, const uint32_t, j); pY = PIC_AT(p.in.y, const uint32_t, j); pS = PIC_AT(p.in.slot, const uint32_t, j);
-            pHh = PIC_AT(p.in.hhi, const uint32_t, j); pHl = PIC_AT(p.in.hlo, const uint32_t, j);
-            pA = PIC_AT(p.in.agent_food, const float, j);
-        }
-    };
     const int x0 = tx << K.xs(), y0 = ty << K.ys();
     __builtin_amdgcn_s_setprio(3);        // (already 3 since the entry; the loads below go out at 3, the chunk loop runs at 0)
     // 1st round trip: the per-tile words (small arrays, L2-resident).  Requested FIRST: vector loads return in order, so a
@@ -471,9 +475,29 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
     const uint32_t obase = p.out.off[tile], on = p.out.n[tile];
     // (TILED, the step behind a refresh in place — die_pic_ghost_inplace: a halo tile holds exactly what arrived for it; the neighbours'
     // leavers that stand on it are stale copies of agents that came with the message)
-    pic_ranges_finish(mt, s_base, s_pre, TILED && p.halo_fresh && p.g.own_x1 > 0 && (x0 < p.g.own_x0 || x0 >= p.g.own_x1 || y0 < p.g.own_y0 || y0 >= p.g.own_y1));
-    prefetch_agents();
-    const uint32_t own = s_pre[1], ncand = s_pre[9] - own, base0 = s_base[0];
+    pic_ranges_publish(mt, s_rng, TILED && p.halo_fresh && p.g.own_x1 > 0 && (x0 < p.g.own_x0 || x0 >= p.g.own_x1 || y0 < p.g.own_y0 || y0 >= p.g.own_y1));
+    // what the first pass needs from memory besides the windows: the six streams of this wave's first chunk of stayers and this thread's
+    // first candidate arrival.  The ranges come to every thread's registers in one LDS round trip (pic_ranges_read).
+    const PicRanges R = pic_ranges_read(s_rng);
+    const uint32_t own = R.l0, base0 = R.b0, ncand = pic_ranges_candidates(R);
+    // the streams FIRST: they need nothing but the tile's own range, and they are the last loads of the workgroup to return — whatever
+    // stands in front of them delays the filter, its barrier and the first chunk
+    uint32_t pX = 0, pY = 0, pS = 0, pHh = 0, pHl = 0;
+    float pA = 0.f;
+    if ((uint32_t)(wave * DIE_WAVE + lane) < own) {
+        const uint32_t j = base0 + (uint32_t)(wave * DIE_WAVE + lane);
+        pX = PIC_AT(p.in.x, const uint32_t, j); pY = PIC_AT(p.in.y, const uint32_t, j); pS = PIC_AT(p.in.slot, const uint32_t, j);
+        pHh = PIC_AT(p.in.hhi, const uint32_t, j); pHl = PIC_AT(p.in.hlo, const uint32_t, j);
+        pA = PIC_AT(p.in.agent_food, const float, j);
+    }
+    // then the candidate: where it lies by comparisons and selects on the registers just read (pic_cand_source), its position requested
+    const bool chas = threadIdx.x < ncand;
+    const uint32_t cj = pic_cand_source(R, threadIdx.x);
+    uint32_t cX = 0, cY = 0;
+    if (chas) {
+        cX = PIC_AT(p.in.x, const uint32_t, cj);
+        cY = PIC_AT(p.in.y, const uint32_t, cj);
+    }
     __builtin_amdgcn_s_setprio(0);
     FwdTileMem<T, TILED> tm;
     tm.g = p.g;
@@ -500,10 +524,7 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
                 j = cj;
                 hit = chas && pic_tile_of<TILED>(p, K.xs(), K.ys(), cX, cY) == tile;
             } else if (c < cend) {
-                const uint32_t idx = own + c;
-                int r = 1;
-                while (idx >= s_pre[r + 1]) ++r;
-                j = s_base[r] + (idx - s_pre[r]);
+                j = pic_cand_source(pic_ranges_read(s_rng), c);        // (a later trip, rare: the ranges once more from LDS, not kept in registers)
                 hit = pic_tile_of<TILED>(p, K.xs(), K.ys(), PIC_AT(p.in.x, const uint32_t, j), PIC_AT(p.in.y, const uint32_t, j)) == tile;
             }
             const unsigned long long m = __ballot(hit);
@@ -620,6 +641,7 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
             unsigned long long base = 0;
             if (lane == 0) base = atomicAdd(&s_cnt, (unsigned long long)__popcll(m_stay) | ((unsigned long long)__popcll(m_leave) << 21) |
                                                     ((unsigned long long)__popcll(m_rim) << 42));
+            // (v_readfirstlane instead of the shuffle, here and at the two counters above, measured at nothing in round 9 — LABBOOK §24)
             base = __shfl(base, 0, DIE_WAVE);
             const uint32_t bf = (uint32_t)base & 0x1FFFFFu, bb = (uint32_t)(base >> 21) & 0x1FFFFFu, br = (uint32_t)(base >> 42) & 0x1FFFFFu;
             const uint32_t k = stay ? bf + (uint32_t)__popcll(m_stay & below) : on - 1u - (bb + (uint32_t)__popcll(m_leave & below));
@@ -657,11 +679,14 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
         }
     }
     __builtin_amdgcn_s_setprio(3);
-    gsum = die_wave_sum(gsum);
-    if (lane == 0) s_gain[threadIdx.x / DIE_WAVE] = gsum;
+    // the wave's sums without LDS shuffles (die_wave_sum_i64_dpp: whole waves — every wave of the workgroup arrives here with all 64
+    // lanes, the loops above being wave-uniform), then ONE LDS add per wave that returns nothing: the wave that took the last chunk is
+    // the one the final barrier waits for, and wave 0 behind it reads one word instead of reducing eight
+    gsum = die_wave_sum_i64_dpp(gsum);
+    if (lane == 0) atomicAdd(&s_gain, (unsigned long long)gsum);
     if (TILED) {
-        const long long c = die_wave_sum((long long)nowned);
-        if (lane == 0) s_alv[threadIdx.x / DIE_WAVE] = (uint32_t)c;
+        const long long c = die_wave_sum_i64_dpp((long long)nowned);
+        if (lane == 0) atomicAdd(&s_alv, (uint32_t)c);
     }
     // The tile's last words — arrival counts, rim codes, reward partial, stayer count — go out from THREE waves side by side, and the
     // pointers they go to are requested ahead of the barrier.  (Round 6: all of it in wave 0, one dependent scalar load after the other,
@@ -687,17 +712,13 @@ __global__ __launch_bounds__(PIC_K1_BLOCK, (sizeof(T) == 2 ? PIC_K1_MINW_F16 : P
         }
         if (lane == 0) e_rimn[tile] = nr;
     }
-    if (wave == 0) {
-        long long t = die_wave_sum(lane < nwaves ? s_gain[lane] : 0ll);          // (integers: any order)
-        [[maybe_unused]] long long c = 0;
-        if (TILED) c = die_wave_sum(lane < nwaves ? (long long)s_alv[lane] : 0ll);
-        if (lane == 0) {
-            e_gain[tile] = t;
-            if (TILED) e_gain[(size_t)p.ntx * p.nty + tile] = c;               // second half of the array: owned agents per tile
-            const uint32_t nfront = (uint32_t)s_cnt & 0x1FFFFFu, nback = (uint32_t)(s_cnt >> 21) & 0x1FFFFFu;
-            PIC_KPF(out.s, uint32_t*)[pic_fresh_s<CFG::FIXED>(tile)] = nfront;
-            if (nfront + nback != on || on >= (1u << 21)) atomicOr(PIC_KPF(error, uint32_t*), 1u);
-        }
+    // (thread 0 — the test on an opaque copy of the index: the prologue's `threadIdx.x == 0` mask is otherwise carried down here)
+    if (wave == 0 && pic_fresh_v<CFG::FIXED>(threadIdx.x) == 0) {
+        e_gain[tile] = (long long)s_gain;
+        if (TILED) e_gain[(size_t)p.ntx * p.nty + tile] = (long long)s_alv;   // second half of the array: owned agents per tile
+        const uint32_t nfront = (uint32_t)s_cnt & 0x1FFFFFu, nback = (uint32_t)(s_cnt >> 21) & 0x1FFFFFu;
+        PIC_KPF(out.s, uint32_t*)[pic_fresh_s<CFG::FIXED>(tile)] = nfront;
+        if (nfront + nback != on || on >= (1u << 21)) atomicOr(PIC_KPF(error, uint32_t*), 1u);
     }
 }
 

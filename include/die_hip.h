@@ -611,6 +611,10 @@ int32_t die_pic_run_completed(void);
  * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24. */
 void die_pic_k1_generic(int32_t force);
 int64_t die_pic_k1_specialised_launches(void);
+/* Self-check of the wave reduction the agent kernel's epilogue uses (die_wave_sum_i64_dpp: a 64-bit integer sum over a whole wave by
+ * data-parallel-primitive moves, no LDS): in = n_waves x 64 int64 on the device, out[w] = the sum of in[64 w .. 64 w + 63] modulo 2^64.
+ * 1 <= n_waves <= 2^20.  Added within ABI 24 like the two above: a new symbol only. */
+int die_wave_sum_i64_check(const void* in, int64_t n_waves, void* out, void* stream);
 /* `act` of die_pic_forward_env_step may be NULL: the action then stays in registers.  For a normalised PhysarumAgent it can
  * still be produced afterwards — until the next step overwrites p->dep — from what the step left in layout[lay] (the layout it
  * WROTE): (dx, dy) = scale * polar2xy(1, heading'), deposit = p->dep; same bits as the action the step would have stored, in
