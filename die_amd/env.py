@@ -529,9 +529,9 @@ class Env(_EnvBase):
         if ag._prev_grad is not None and ag._inertia == 0:
             return False                                         # (_prev_grad is kept up to date by the classic step only when nothing reads it: inertia 0 — ADVICE r4)
         W, H = self._field_size
-        from .pic import step_scale
+        from .pic import reach_cells, step_scale
         eff_scale = step_scale(ag)                               # |scale| · the bound of the vector it multiplies (momentum: die_pic_step_bound)
-        reach = abs(eff_scale) * (max(W, H) - 1)                 # cells per step, at most
+        reach = reach_cells(ag, max(W, H))                       # cells per step, at most (float32, as the library computes them)
         if self._pic_tile is None:
             from .pic import pick_tile
             # small worlds are bound by launches and their gaps, not by what the binned step saves.  Measured (r3, µs per step,

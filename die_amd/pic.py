@@ -39,6 +39,20 @@ def step_scale(agent) -> float:
     return value
 
 
+def reach_cells(agent, world_max: int) -> float:
+    """Cells per step, at most, in the library's own arithmetic (die_pic_forward_env_step: |scale · bound| · (n − 1) in float32), so that
+    the host's `reach <= min(TX, TY) − 1` and the library's refusal of longer steps agree at the limit itself: the float64 product of
+    the float32 scale put a step of exactly 31 cells on a 384-cell axis at 31.0000003 — the classic step, where the library takes it.
+    (Kept per agent, like step_scale: it is asked for at every step.)"""
+    scale = step_scale(agent)
+    hit = agent.__dict__.get('_pic_reach_cells')
+    if hit is not None and hit[0] == scale and hit[1] == world_max:
+        return hit[2]
+    value = float(np.float32(abs(scale)) * np.float32(world_max - 1))
+    agent.__dict__['_pic_reach_cells'] = (scale, world_max, value)
+    return value
+
+
 def lazy_ok(agent) -> bool:
     """Does the field kernel leave the next step's turn bits behind for this agent?  (A PhysarumAgent drawing from Philox.)"""
     return agent._kind == _lib.DIE_AGENT_PHYSARUM and agent._turn_sign is None

@@ -147,7 +147,7 @@ def fuzz_binned(n_cases=60, seed=0, verbose=True):
         medium, agents = random_state(W, H, N, N - int(dead * N), rs, collide=float(rs.choice([0.0, 0.3, 0.9])))
         f16 = bool(rs.rand() < 0.3)
         dyn = dict(boundary=die_amd.BoundaryCondition(rs.choice(['wrap', 'limit'])), food_infinite=bool(rs.rand() < 0.2),
-                   diffuse_sigma=float(rs.choice([0.4, 0.5, 0.8, 1.0])), rate_feed=float(rs.choice([0.1, 0.35])),
+                   diffuse_sigma=float(rs.choice([0.25, 0.3, 0.4, 0.5, 0.8, 1.0])), rate_feed=float(rs.choice([0.1, 0.35])),
                    rate_decay_chem=float(rs.choice([0.01, 0.2])))
         reach = [0.7, 1.53, min(TX, TY) - 1.001][reach_pick]                          # cells per step
         probe = float(rs.choice([1.2, 10.2, 21.5]))
