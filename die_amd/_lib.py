@@ -117,6 +117,9 @@ class ParameterSpace(C.Structure):   # die_parameter_space
 
 
 NCA_MAX_LAYERS = 8
+NCA_WIDE_MAX_CHANNELS = 32           # die_conv2d_wide / die_nca_wide_env_step_batch: channels in or out of a layer
+NCA_WIDE_KERNEL_SIZES = (1, 3, 5)
+NCA_ACTIVATIONS = {None: 0, 'tanh': 1, 'relu': 2}     # ConvolutionModel(hidden_activation=...) → die_nca_activation
 
 
 class NcaLayer(C.Structure):         # die_nca_layer
@@ -225,6 +228,11 @@ _SIGNATURES = {
                                          C.c_void_p, C.c_int64, C.c_void_p]),
     'die_nca_env_step_batch_dropout': (C.c_int, [_P(Medium), _P(Agents), _P(NcaBatch), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
                                                  C.c_void_p, C.c_int64, _P(NcaDropout), C.c_void_p]),
+    'die_conv2d_wide': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P(ConvPlane), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                                  C.c_void_p, C.c_int32, C.c_int32, _P(NcaDropout), C.c_void_p]),
+    'die_nca_wide_batch_scratch_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    'die_nca_wide_env_step_batch': (C.c_int, [_P(Medium), _P(Agents), _P(NcaBatch), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
+                                              C.c_void_p, C.c_int64, _P(NcaDropout), C.c_void_p, _P(DynamicsRow), C.c_void_p]),
     'die_dropout_mask': (C.c_int, [C.c_int32, C.c_int32, _P(NcaDropout), C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
     'die_forward_move_claim_tile': (C.c_int, [_P(Medium), _P(Agents), _P(GradientAgent), _P(Action), _P(Dynamics), C.c_void_p,
                                               C.c_int64, C.c_void_p]),

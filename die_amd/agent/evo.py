@@ -50,7 +50,14 @@ class ConvolutionModel(nn.Module):
     `kernel_sizes`; every layer keeps the observation channels except the last, which maps them to the action channels), a Tanh
     that brings the outputs into [-1, 1], and an (inverted-)dropout mask over cells.  The submodule names `kernels.<i>` and
     `agent_dropout` are the reference's, so state_dicts interchange; the device path (NeuralAutomataAgent.sense) reads the
-    layers' weights and never calls this module's forward."""
+    layers' weights and never calls this module's forward.
+
+    `hidden_channels` and `hidden_activation` (no reference counterpart; both None: exactly the module above) make a "wide stack":
+      * `hidden_channels=C`, 1 <= C <= 32: the layers are obs -> C, C -> C, ..., C -> actions (at least two layers);
+      * `hidden_activation` 'tanh' / 'relu' / None: applied after every layer but the last, as a module between the convs (the
+        convs' names `kernels.<i>` then skip the activations' indices); the last layer keeps the Tanh and the dropout mask.
+    A stack with either one set runs on the device through the wide layer kernel (die_conv2d_wide: kernel sizes 1, 3 and 5, every
+    boundary), also where its widths would fit the narrow one.  Both stay out of `init_params` while None."""
 
     def __init__(self,
                  num_obs_channels: int = 3,
@@ -59,19 +66,47 @@ class ConvolutionModel(nn.Module):
                  boundary: str = 'circular',
                  p_agent_dropout: float = 0.,
                  requires_grad: bool = True,
+                 hidden_channels: Optional[int] = None,
+                 hidden_activation: Optional[str] = None,
                  ):
         self._init_params = save_args(self.__init__, locals())
+        for name in ('hidden_channels', 'hidden_activation'):
+            if self._init_params[name] is None:
+                del self._init_params[name]
+        if hidden_channels is not None:
+            if isinstance(hidden_channels, bool) or int(hidden_channels) != hidden_channels or \
+                    not 1 <= hidden_channels <= _lib.NCA_WIDE_MAX_CHANNELS:
+                raise ValueError(f'hidden_channels={hidden_channels!r}: an integer in 1..{_lib.NCA_WIDE_MAX_CHANNELS}, or None')
+            if len(kernel_sizes) < 2:
+                raise ValueError('hidden_channels needs at least two layers (a single layer has no hidden channels)')
+            hidden_channels = int(hidden_channels)
+        if hidden_activation not in _lib.NCA_ACTIVATIONS:
+            raise ValueError(f"hidden_activation={hidden_activation!r}: 'tanh', 'relu' or None")
+        if hidden_channels is not None or hidden_activation is not None:
+            for size in kernel_sizes:
+                if size not in _lib.NCA_WIDE_KERNEL_SIZES:
+                    raise NotImplementedError(f'kernel size {size} in a wide stack (hidden_channels / hidden_activation): one of '
+                                              f'{_lib.NCA_WIDE_KERNEL_SIZES} (32 * 32 * 49 weights do not fit LDS next to a tile)')
         super().__init__()
+        self.hidden_channels, self.hidden_activation = hidden_channels, hidden_activation
         depth = len(kernel_sizes)
+        width = num_obs_channels if hidden_channels is None else hidden_channels
         stack = nn.Sequential()
         for level, size in enumerate(kernel_sizes):
             widens_to_actions = level == depth - 1
-            stack.append(nn.Conv2d(num_obs_channels, num_act_channels if widens_to_actions else num_obs_channels, size,
+            stack.append(nn.Conv2d(num_obs_channels if level == 0 else width, num_act_channels if widens_to_actions else width, size,
                                    padding='same', padding_mode=boundary, bias=False))
+            if hidden_activation is not None and not widens_to_actions:
+                stack.append(nn.Tanh() if hidden_activation == 'tanh' else nn.ReLU())
         stack.append(nn.Tanh())
         self.agent_dropout = nn.Dropout(p_agent_dropout)
         self.kernels = stack
         self.requires_grad_(requires_grad)
+
+    @property
+    def wide(self) -> bool:
+        """A stack with `hidden_channels` or `hidden_activation` set: every layer goes through the wide entry points."""
+        return self.hidden_channels is not None or self.hidden_activation is not None
 
     def conv_layers(self):
         return [layer for layer in self.kernels if isinstance(layer, nn.Conv2d)]
@@ -108,6 +143,9 @@ class NeuralAutomataAgent(TorchAgent):
                  ):
         self._init_params = save_args(self.__init__, locals())
         self._init_params.pop('initial_obs', None)            # an observation is not a constructor parameter worth saving
+        for name in ('hidden_channels', 'hidden_activation'):  # (kept out while None, as dropout_seed is: see ConvolutionModel)
+            if self._init_params['model_kwargs'].get(name, 0) is None:
+                del self._init_params['model_kwargs'][name]
         super().__init__()
         self.dropout_seed = dropout_seed
         self.dropout_step = 0
@@ -150,25 +188,40 @@ class NeuralAutomataAgent(TorchAgent):
         # loads each candidate — change neither `_version` nor `data_ptr()`, so no cheap key tells a stale copy apart
         return [k.weight.detach().to(device=device, dtype=th.float32).contiguous() for k in layers]
 
-    def _scratch(self, W, H, device, n_sets):
+    def _scratch(self, W, H, device, n_sets, channels=4):
         key = (W, H, str(device))
         sets = self._planes.get(key)
-        if sets is None or len(sets) < n_sets:
-            sets = [th.empty((4, W, H), dtype=th.float32, device=device) for _ in range(n_sets)]
+        if sets is None or len(sets) < n_sets or sets[0].shape[0] < channels:
+            sets = [th.empty((channels, W, H), dtype=th.float32, device=device) for _ in range(n_sets)]
             self._planes[key] = sets
         return sets
 
+    def _check_wide(self, what: str = None):
+        """A wide stack's refusals, before any launch: a kernel size the wide layer kernel does not take, or (`what`) a
+        differentiable call."""
+        if not self._model.wide:
+            return
+        if what is not None:
+            raise NotImplementedError(f'{what}: no gradients for a wide stack (hidden_channels / hidden_activation): the adjoint '
+                                      'kernels take the narrow layers only')
+        for k in self._model.conv_layers():
+            if int(k.kernel_size[0]) not in _lib.NCA_WIDE_KERNEL_SIZES:
+                raise NotImplementedError(f'kernel size {int(k.kernel_size[0])} in a wide stack (hidden_channels / hidden_activation): '
+                                          f'one of {_lib.NCA_WIDE_KERNEL_SIZES} (32 * 32 * 49 weights do not fit LDS next to a tile)')
+
     def sense(self, medium) -> th.Tensor:
         """ConvolutionModel.forward over the medium on the device → (3, W, H) float32 tensor."""
+        self._check_wide()
         medium.sensed()
         dev, W, H = medium.device, medium.W, medium.H
         weights = self._device_weights(dev)
         sp = stream_ptr(dev)
+        wide = self._model.wide
         medium._ensure_owner()
         fkind = _lib.DIE_PLANE_F32 if medium.dtype == th.float32 else _lib.DIE_PLANE_F16
         src = {'agents': (medium.owner, _lib.DIE_PLANE_AGENTS), 'env_food': (medium.food, fkind), 'chem1': (medium.chem, fkind)}
         planes = [src[c] for c in self.obs_channels]
-        sets = self._scratch(W, H, dev, 2)
+        sets = self._scratch(W, H, dev, 2, max(4, *(w.shape[0] for w in weights)) if wide else 4)
         p = self._model.agent_dropout.p
         masked = p > 0 and self._model.training
         drop = None                                              # the counter-based mask: inside the last layer's launch
@@ -183,7 +236,11 @@ class NeuralAutomataAgent(TorchAgent):
             out_arr = (C.c_void_p * cout)(*[dst[o].data_ptr() for o in range(cout)])
             last = li == len(weights) - 1
             pad = _lib.PAD_MODES[self._model.conv_layers()[li].padding_mode]
-            if last and drop is not None:
+            if wide:                                             # every layer of a wide stack: die_conv2d_wide
+                act = _lib.NCA_ACTIVATIONS['tanh' if last else self._model.hidden_activation]
+                _lib.check(_lib.lib.die_conv2d_wide(W, H, cin, cin_arr, medium.epoch, cout, dst.data_ptr(), W * H, k, _ptr(w), act, pad,
+                                                    C.byref(drop) if last and drop is not None else None, sp), 'die_conv2d_wide')
+            elif last and drop is not None:
                 _lib.check(_lib.lib.die_conv2d_dropout(W, H, cin, cin_arr, medium.epoch, cout, out_arr, k, _ptr(w), 1, pad, C.byref(drop), sp),
                            'die_conv2d_dropout')
             else:
@@ -226,7 +283,11 @@ class NeuralAutomataAgent(TorchAgent):
         With a `dropout_seed` in training mode the last layer is launched twice, masked (the value returned) and unmasked
         (tanh(z), kept for the backward, which recomputes the mask from its key); `dropout_step` advances once per call, as in
         `sense`.  Boundaries 'circular' and 'zeros'; 'reflect' / 'replicate' raise NotImplementedError before any launch.
-        `sense` and `forward` are untouched by all this: never differentiable, same scratch, same launches."""
+        `sense` and `forward` are untouched by all this: never differentiable, same scratch, same launches.
+
+        A wide stack (`hidden_channels` / `hidden_activation`) has no adjoint kernels: NotImplementedError, before any launch
+        and before `dropout_step` moves."""
+        self._check_wide('differentiable_sense')
         layers = self._model.conv_layers()
         for k in layers:
             if k.padding_mode not in ('circular', 'zeros'):
@@ -249,7 +310,9 @@ class NeuralAutomataAgent(TorchAgent):
         (die_gather_scale_backward: the slots' gradients scattered onto their cells, then `differentiable_sense`'s backward).
         The slots' coordinates are copied, so `backward` may run after the world has been stepped.  Where several slots with a
         non-zero gradient stand on one cell their terms are summed by fp32 atomic adds in arrival order; otherwise (alive agents
-        never share a cell) the gradients are bit-reproducible run to run."""
+        never share a cell) the gradients are bit-reproducible run to run.  A wide stack raises NotImplementedError, as in
+        `differentiable_sense`."""
+        self._check_wide('differentiable_action')
         agents, medium = obs
         sense = self.differentiable_sense(medium)
         self._sense_output = sense.detach()

@@ -975,7 +975,8 @@ def _architecture(agent: NeuralAutomataAgent) -> dict:
     layers = agent.model.conv_layers()
     return dict(kernel_sizes=tuple(int(k.kernel_size[0]) for k in layers), boundary=tuple(k.padding_mode for k in layers),
                 with_agent_channel=len(agent.obs_channels) == 3, scale=agent.action_coefs[0], deposit=agent.action_coefs[2],
-                shapes=tuple(tuple(k.weight.shape) for k in layers))
+                shapes=tuple(tuple(k.weight.shape) for k in layers), hidden_channels=agent.model.hidden_channels,
+                hidden_activation=agent.model.hidden_activation)
 
 
 class BatchedNeuralAutomataAgent(_Population):
@@ -1015,6 +1016,8 @@ class BatchedNeuralAutomataAgent(_Population):
         self.candidates = env.R // self.episodes
         self.env, self.template, self.R = env, template, env.R
         self._arch = _architecture(template)
+        self._wide = template.model.wide            # hidden_channels / hidden_activation: die_nca_wide_env_step_batch
+        template._check_wide()
         layers = template.model.conv_layers()
         for k in layers:
             if k.padding_mode not in _lib.PAD_MODES:
@@ -1022,11 +1025,16 @@ class BatchedNeuralAutomataAgent(_Population):
         if len(set(self._arch['boundary'])) != 1 or len(layers) > _lib.NCA_MAX_LAYERS:
             raise NotImplementedError(f'one boundary for every layer, at most {_lib.NCA_MAX_LAYERS} layers')
         self._layers = []                           # (k, cin, cout, offset in a row)
+        self._acts = []                             # die_nca_layer.reserved of every layer
         off = 0
-        for k in layers:
+        for li, k in enumerate(layers):
             cout, cin, kk, _ = k.weight.shape
+            # a wide stack's layers carry their activation in `reserved` (the last layer's is its tanh); a narrow one's say 0
+            act = _lib.NCA_ACTIVATIONS['tanh' if li == len(layers) - 1 else self._arch['hidden_activation']] if self._wide else 0
             self._layers.append((int(kk), int(cin), int(cout), off))
+            self._acts.append(act)
             off += k.weight.numel()
+        self._channels = max(cout for _, _, cout, _ in self._layers) if self._wide else 4      # planes per replica of a scratch set
         self.P = off
         if parameters is None:
             parameters = parameters_to_vector(template.model.parameters()).detach().reshape(1, -1).expand(self.candidates, -1)
@@ -1038,8 +1046,9 @@ class BatchedNeuralAutomataAgent(_Population):
         if env.per_replica:
             self.agents = [self.unpack(template, self.parameters[r // self.episodes]) for r in range(self.R)]
             return
-        self._scratch = torch.empty(int(_lib.lib.die_nca_batch_scratch_bytes(env.W, env.H, self.R, len(layers))) // 4,
-                                    dtype=torch.float32, device=env.device)
+        need = _lib.lib.die_nca_wide_batch_scratch_bytes(env.W, env.H, self.R, len(layers), self._channels) if self._wide else \
+            _lib.lib.die_nca_batch_scratch_bytes(env.W, env.H, self.R, len(layers))
+        self._scratch = torch.empty(int(need) // 4, dtype=torch.float32, device=env.device)
 
     @classmethod
     def from_agents(cls, env: BatchedEnv, agents: Sequence[NeuralAutomataAgent], episodes: int = 1, *,
@@ -1131,6 +1140,11 @@ class BatchedNeuralAutomataAgent(_Population):
         """BatchedPhysarumAgent._launch with the dropout mask of the coming step after the workspace: one entry point without
         it, one with it (the same step, its last conv launch masked), and with Dynamics rows one for both, the mask nullable."""
         drop = self._dropout()
+        if self._wide:                              # one entry point: the mask and the two tables are all nullable
+            _lib.check(_lib.lib.die_nca_wide_env_step_batch(*front, C.byref(self._struct(self._sense_epoch)), *back,
+                                                            None if drop is None else C.byref(drop), *(rows or (None, None)), stream),
+                       'die_nca_wide_env_step_batch')
+            return
         mask = () if drop is None else (C.byref(drop),)
         if rows:
             name, mask = 'die_nca_env_step_batch_rows', mask or (None,)
@@ -1141,8 +1155,8 @@ class BatchedNeuralAutomataAgent(_Population):
     def _struct(self, sense_epoch: int) -> _lib.NcaBatch:
         base = self.parameters.data_ptr()
         if self._c is None or self._c[0] != base:
-            layers = (_lib.NcaLayer * len(self._layers))(*[_lib.NcaLayer(k, cin, cout, 0, base + 4 * off, self.P)
-                                                            for k, cin, cout, off in self._layers])
+            layers = (_lib.NcaLayer * len(self._layers))(*[_lib.NcaLayer(k, cin, cout, act, base + 4 * off, self.P)
+                                                            for (k, cin, cout, off), act in zip(self._layers, self._acts)])
             nca = _lib.NcaBatch(len(self._layers), _lib.PAD_MODES[self._arch['boundary'][0]], int(self._arch['with_agent_channel']), 0,
                                 layers, (C.c_float * 3)(*self.template.action_coefs), 0 if self.episodes == 1 else self.episodes,
                                 _ptr(self._scratch),
@@ -1156,6 +1170,7 @@ class BatchedNeuralAutomataAgent(_Population):
     def _check_differentiable(self, parameters: Optional[torch.Tensor]) -> torch.Tensor:
         """Every refusal of a differentiable call, before anything is launched; returns the matrix the call reads."""
         env = self.env
+        self.template._check_wide('differentiable mode')
         if env.per_replica:
             raise NotImplementedError('differentiable mode: large worlds (per_replica) are not batched — a large world fills the GPU '
                                       'through the stand-alone NeuralAutomataAgent.differentiable_action (replica_agent(r))')
@@ -1187,7 +1202,9 @@ class BatchedNeuralAutomataAgent(_Population):
         planes of all replicas) are copied, so `backward` may run after `env.step`.  With a `dropout_seed`, in training mode and
         p > 0, replica r is masked with key `dropout_seed + r·dropout_seed_stride` at `dropout_step`; the counter advances once per
         call whenever a `dropout_seed` is set.  Small worlds, 'circular' / 'zeros' boundaries; anything else raises
-        NotImplementedError before any launch.  `step()` is untouched by all this."""
+        NotImplementedError before any launch.  `step()` is untouched by all this.  A population of wide stacks
+        (`hidden_channels` / `hidden_activation`) has no adjoint kernels: NotImplementedError too, before any launch and before
+        `dropout_step` moves."""
         p = self._check_differentiable(parameters)
         out = _BatchedSense.apply(self, p, self.env.chem_node)
         if self.dropout_seed is not None:
@@ -1212,7 +1229,7 @@ class BatchedNeuralAutomataAgent(_Population):
         if self._calls == 0:
             return np.ones((2, 2, 3))
         L, W, H = len(self._layers), self.env.W, self.env.H
-        sets = self._scratch.view(-1, self.R, 4, W, H)
+        sets = self._scratch.view(-1, self.R, self._channels, W, H)
         return torch.moveaxis(sets[(L - 1) % sets.shape[0], r, :3], 0, -1).cpu().numpy()
 
 

@@ -1553,16 +1553,21 @@ int die_nca_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t 
 int die_dropout_words(const die_nca_dropout* drop, DropWords* out, const char* who);                                 // die_nca.hip
 int die_nca_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
                         const DropWords* drop, void* stream);
+int die_nca_wide_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who);  // die_nca_wide.hip
+int die_nca_wide_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
+                             const DropWords* drop, void* stream);
 
-// die_nca_env_step_batch (drop null) and die_nca_env_step_batch_dropout: one body; the mask only changes the last conv launch
+// die_nca_env_step_batch (drop null) and die_nca_env_step_batch_dropout: one body; the mask only changes the last conv launch.
+// `wide` (die_nca_wide_env_step_batch): the stack's check and its sensing are die_nca_wide.hip's, which hand back the same
+// (sense pointer, replica stride); everything after the sensing is shared
 static int nca_env_step_batch(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
                               const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws, int64_t ws_bytes,
                               const die_nca_dropout* drop, void* stream, const char* who, bool with_rows = false,
-                              const die_dynamics_row* rows = nullptr, const die_dynamics_row* rows_host = nullptr) {
+                              const die_dynamics_row* rows = nullptr, const die_dynamics_row* rows_host = nullptr, bool wide = false) {
     DIE_REQUIRE(m && a && nca && d && b && results && ws, "%s: null argument", who);
     int rc = batch_world_check(m, a, d, b, ws_bytes, true, who);
     if (rc != DIE_OK) return rc;
-    rc = die_nca_batch_check(nca, m->W, m->H, b->replicas, who);
+    rc = wide ? die_nca_wide_batch_check(nca, m->W, m->H, b->replicas, who) : die_nca_batch_check(nca, m->W, m->H, b->replicas, who);
     if (rc != DIE_OK) return rc;
     DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX && m->epoch == nca->sense_epoch % DIE_OWNER_EPOCH_MAX + 1,
                 "%s: claims at epoch %d cannot follow sensing at epoch %d", who, m->epoch, nca->sense_epoch);
@@ -1578,7 +1583,7 @@ static int nca_env_step_batch(const die_medium* m, const die_agents* a, const di
     rc = batch_rows_check(with_rows, b, rows, rows_host, who);
     if (rc != DIE_OK) return rc;
     NcaReadArgs q;
-    rc = die_nca_sense_batch(m, b, nca, &q.sense, &q.rep, drop ? &dw : nullptr, stream);   // reads the claim plane at sense_epoch …
+    rc = (wide ? die_nca_wide_sense_batch : die_nca_sense_batch)(m, b, nca, &q.sense, &q.rep, drop ? &dw : nullptr, stream);   // reads the claim plane at sense_epoch …
     if (rc != DIE_OK) return rc;
     if (nca->sense_epoch == DIE_OWNER_EPOCH_MAX) {                    // … which is cleared before the tag 1 claims
         const int64_t words = (int64_t)(b->replicas - 1) * b->plane_stride + (int64_t)m->W * m->H;
@@ -1605,6 +1610,14 @@ extern "C" int die_nca_env_step_batch_rows(const die_medium* m, const die_agents
                                            int64_t ws_bytes, const die_nca_dropout* drop, const die_dynamics_row* rows,
                                            const die_dynamics_row* rows_host, void* stream) {
     return nca_env_step_batch(m, a, nca, act, d, b, results, ws, ws_bytes, drop, stream, "die_nca_env_step_batch_rows", true, rows, rows_host);
+}
+
+extern "C" int die_nca_wide_env_step_batch(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
+                                           const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws,
+                                           int64_t ws_bytes, const die_nca_dropout* drop, const die_dynamics_row* rows,
+                                           const die_dynamics_row* rows_host, void* stream) {
+    return nca_env_step_batch(m, a, nca, act, d, b, results, ws, ws_bytes, drop, stream, "die_nca_wide_env_step_batch", rows || rows_host,
+                              rows, rows_host, true);
 }
 
 extern "C" int die_nca_env_step_batch(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,

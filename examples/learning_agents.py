@@ -51,8 +51,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from die_amd import CMAES, PGPE, Env, NeuralAutomataAgent            # noqa: E402
 from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent, episode_seeds   # noqa: E402
-from population_eval import (DYNAMICS, batch_dynamics, dropout_keywords, dynamics_names, evaluate_population, make_dynamics,   # noqa: E402
-                             make_population, make_template, per_dynamics_means, resolve_episodes, run_epoch, slots)
+from population_eval import (DYNAMICS, add_wide_arguments, batch_dynamics, dropout_keywords, dynamics_names, evaluate_population, make_dynamics,   # noqa: E402
+                             make_population, make_template, per_dynamics_means, resolve_episodes, run_epoch, slots, wide_keywords)
 
 RADIUS_INIT = 1.5
 MAX_SPEED = RADIUS_INIT / 15.              # the reference's rule of thumb
@@ -63,9 +63,9 @@ SEARCHERS = ('pgpe', 'cmaes')
 
 
 def make_search(size, choice, popsize, epoch_iters, seed, searcher='pgpe', agents_die=False, max_agents='alive', reseed=None,
-                reseed_stride=0, episodes=1, drop_kw=None, dropout=0., center_init=None):
+                reseed_stride=0, episodes=1, drop_kw=None, dropout=0., center_init=None, wide_kw=None):
     torch.manual_seed(seed)
-    template = make_template(dropout)
+    template = make_template(dropout, wide_kw)
     benv = BatchedEnv((size, size), batch_dynamics(choice, size, agents_die, popsize, episodes), replicas=popsize * episodes,
                       seeds=episode_seeds(seed, popsize, episodes), max_agents=max_agents)
     pop = BatchedNeuralAutomataAgent(benv, template, episodes=episodes, **(drop_kw or {}))
@@ -89,7 +89,7 @@ def host_generation(size, choice, template, mean, sigma, lr, iters, seed, agents
 
 def time_device_loop(args, G, max_agents, reseed):
     searcher, pop = make_search(args.size, args.dynamics, 10, args.epoch_iters, args.seed, args.searcher, args.agents_die, max_agents,
-                                reseed, args.reseed_stride, args.episodes, args.drop_kw, args.dropout)
+                                reseed, args.reseed_stride, args.episodes, args.drop_kw, args.dropout, wide_kw=args.wide_kw)
     searcher.run(2)                                               # warm-up: first launches, allocations
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -158,7 +158,9 @@ def main():
     p.add_argument('--dropout-seed', type=int, default=0, help='key of the dropout masks: replica r uses seed + r·stride')
     p.add_argument('--dropout-stride', type=int, default=1, help='0: every replica the same mask; 1: every replica its own')
     p.add_argument('--init-from', default=None, metavar='FILE', help='a saved NeuralAutomataAgent whose weights are the search\'s first centre')
+    add_wide_arguments(p)
     args = p.parse_args()
+    args.wide_kw = wide_keywords(args)
     if not 0. <= args.dropout <= 1. or args.dropout_stride < 0:
         p.error('--dropout in [0, 1], --dropout-stride >= 0')
     args.drop_kw = dropout_keywords(args.dropout, args.dropout_seed, args.dropout_stride)
@@ -181,7 +183,7 @@ def main():
         center_init = torch.nn.utils.parameters_to_vector(loaded.model.parameters()).detach()
         print(f'Starting from {args.init_from} ({center_init.numel()} parameters)')
     searcher, pop = make_search(args.size, args.dynamics, args.popsize, args.epoch_iters, args.seed, args.searcher, args.agents_die, N,
-                                args.reseed, args.reseed_stride, args.episodes, args.drop_kw, args.dropout, center_init)
+                                args.reseed, args.reseed_stride, args.episodes, args.drop_kw, args.dropout, center_init, args.wide_kw)
     print(f'Network has {pop.P} parameters; {args.popsize} candidates' + (f' x {args.episodes} episodes' if args.episodes > 1 else '') +
           f' on {args.size}x{args.size} {args.dynamics}, '
           f'{args.epoch_iters} steps each, max_agents={N}' + ('' if args.reseed is None else

@@ -110,9 +110,26 @@ def slots(spec, size, choice, agents_die=False):
     return int(spec)
 
 
-def make_template(dropout=0.):
-    """The candidates' architecture; `dropout` > 0: with the reference's p_agent_dropout (the model stays in training mode)."""
-    return NeuralAutomataAgent(**AGENT_KW, **(dict(p_agent_dropout=dropout) if dropout > 0 else {}))
+def make_template(dropout=0., wide_kw=None):
+    """The candidates' architecture; `dropout` > 0: with the reference's p_agent_dropout (the model stays in training mode);
+    `wide_kw`: wide_keywords' hidden_channels / hidden_activation (none: the reference's 3-channel linear stack)."""
+    return NeuralAutomataAgent(**AGENT_KW, **(dict(p_agent_dropout=dropout) if dropout > 0 else {}), **(wide_kw or {}))
+
+
+def add_wide_arguments(p):
+    p.add_argument('--hidden-channels', type=int, default=None, metavar='C', help='width of the hidden layers, 1..32 (default: the '
+                                                                                  'observation\'s 3 channels, the narrow kernels)')
+    p.add_argument('--hidden-activation', choices=('tanh', 'relu', 'none'), default='none', help='activation after every layer but the last')
+
+
+def wide_keywords(args):
+    """NeuralAutomataAgent's keywords for --hidden-channels C --hidden-activation A (none when neither is given)."""
+    kw = {}
+    if args.hidden_channels is not None:
+        kw['hidden_channels'] = args.hidden_channels
+    if args.hidden_activation != 'none':
+        kw['hidden_activation'] = args.hidden_activation
+    return kw
 
 
 def dropout_keywords(dropout, seed, stride):
@@ -172,6 +189,7 @@ def main():
     p.add_argument('--dropout', type=float, default=0., help='p_agent_dropout of the candidates (0: none), masked on the device')
     p.add_argument('--dropout-seed', type=int, default=0, help='key of the dropout masks: replica r uses seed + r·stride')
     p.add_argument('--dropout-stride', type=int, default=1, help='0: every replica the same mask; 1: every replica its own')
+    add_wide_arguments(p)
     args = p.parse_args()
     if not 0. <= args.dropout <= 1. or args.dropout_stride < 0:
         p.error('--dropout in [0, 1], --dropout-stride >= 0')
@@ -188,7 +206,10 @@ def main():
     if args.reseed is not None and N == 'alive':
         sys.exit("--reseed needs a fixed slot layout: --max-agents full, tight or a number")
     torch.manual_seed(args.seed)
-    template = make_template(args.dropout)
+    try:
+        template = make_template(args.dropout, wide_keywords(args))
+    except ValueError as err:
+        p.error(str(err))
     cands = []
     for _ in range(R):
         template.model.init_weights()

@@ -986,6 +986,46 @@ int die_nca_backward_batch_inputs(const die_medium* m, const die_batch* b, const
                                   const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, float* grad_in,
                                   int64_t grad_in_stride, void* stream);
 
+/* ---- Wide NeuralAutomataAgent stacks: hidden channels and activations (die_nca_wide.hip; ConvolutionModel(hidden_channels=C,
+ * hidden_activation=...)) -----------------------------------------------------------------------------------------------------
+ * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.  die_conv2d,
+ * die_nca_env_step_batch and their kin keep their 1..4 channels, their kernels and their refusals; a stack whose layers are
+ * obs -> C -> ... -> C -> 3 with an activation after every layer takes the three entry points below for every layer.
+ *   A layer is die_conv2d's cross-correlation with 1..32 channels in and out and k = 1, 3 or 5 (32 * 32 * 49 weights would not fit
+ * LDS next to a tile), evaluated as an implicit GEMM on the fp32-input matrix instruction (v_mfma_f32_16x16x4_f32: exact fp32,
+ * bit for bit a k-ordered fmaf chain).  Each output is summed over (chunk of 4 input channels, a, b, channel in the chunk) in
+ * that order by one kernel body, which both calls launch: replica r of the batched step is the stand-alone call, bit for bit. */
+typedef enum die_nca_activation { DIE_NCA_ACT_NONE = 0, DIE_NCA_ACT_TANH = 1, DIE_NCA_ACT_RELU = 2 } die_nca_activation;
+/* One layer: out[o] = act(conv(in))[o] (* the dropout mask of `drop`, which may be NULL: as die_conv2d_dropout, after the
+ * activation) for o < cout, output plane o at out + o * out_stride (out_stride >= W * H elements; nothing else is written).
+ * `in`: cin planes as die_conv2d reads them (fp32 / fp16 fields, the claim plane at `epoch`); `weights`: (cout, cin, k, k) fp32 on
+ * the device; `activation`: a die_nca_activation; `padding_mode`: a die_pad_mode.  Every argument is checked before anything is
+ * launched, and all of these are DIE_ERR_ARG: W or H < 1, cin or cout outside 1..32, k other than 1, 3, 5, 'reflect' padding of a
+ * field no larger than k / 2, an unknown activation or padding mode, a null pointer, an input plane that is not one of the three
+ * kinds, out_stride below a plane, an input plane that overlaps the output planes (in-place), a bad `drop` (die_nca_dropout's
+ * rules).  Where H % 4 == 0, `out` is 16-byte aligned and out_stride a multiple of 4, the stores are 16 bytes wide. */
+int die_conv2d_wide(int32_t W, int32_t H, int32_t cin, const die_conv_plane* in, int32_t epoch, int32_t cout, float* out,
+                    int64_t out_stride, int32_t k, const float* weights, int32_t activation, int32_t padding_mode,
+                    const die_nca_dropout* drop, void* stream);
+/* Bytes of a batched wide stack's scratch, [set][replica][max_channels][W][H] fp32 with set = layer % 2 (one set for a single
+ * layer) and max_channels the largest cout of the stack:
+ *   (n_layers >= 2 ? 2 : 1) * replicas * max_channels * W * H * 4;
+ * -1 for W or H < 1, replicas outside 1..DIE_MAX_REPLICAS, n_layers outside 1..DIE_NCA_MAX_LAYERS, max_channels outside 1..32. */
+int64_t die_nca_wide_batch_scratch_bytes(int32_t W, int32_t H, int32_t replicas, int32_t n_layers, int32_t max_channels);
+/* die_nca_env_step_batch_rows for a wide stack: the same step (the same read-out and claim launch, lifecycle launch, sweeps
+ * and epoch-wrap clear) behind L launches of the wide layer kernel with the replica in blockIdx.z.  `nca` is a die_nca_batch
+ * whose layers may have 1..32 channels and k = 1, 3, 5, and whose die_nca_layer.reserved is READ, as the layer's
+ * die_nca_activation: any of the three for a hidden layer, DIE_NCA_ACT_TANH for the last (the other entry points ignore that
+ * word, as they always have).  nca->scratch holds die_nca_wide_batch_scratch_bytes(W, H, replicas, n_layers, largest cout)
+ * bytes; the last layer's (dx, dy, deposit) planes of replica r stay at set (n_layers - 1) % 2, replica stride
+ * largest cout * W * H, until the next call.  `drop` (nullable): the last layer is masked as in die_nca_env_step_batch_dropout.
+ * `rows` and `rows_host` (nullable, both or neither): per-replica Dynamics as in die_nca_env_step_batch_rows.  `act` may be NULL.
+ * Checked before anything is launched, in die_nca_env_step_batch's order with the wide limits in place of the narrow ones. */
+int die_nca_wide_env_step_batch(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
+                                const die_dynamics* d, const die_batch* b, die_step_result* results, void* workspace,
+                                int64_t workspace_bytes, const die_nca_dropout* drop, const die_dynamics_row* rows,
+                                const die_dynamics_row* rows_host, void* stream);
+
 /* die_food_flow_batch on the replicas whose bit is set in replica_mask (bit r = replica r); the others' planes are not touched.
  * One launch: a row of workgroups per replica, those of unset replicas exit at once.  A full mask leaves exactly what
  * die_food_flow_batch leaves; an empty mask launches nothing.  Bits at or above b->replicas must be 0. */
