@@ -6,6 +6,7 @@ All compute runs in libdie_hip.so (hand-written HIP for gfx950, include/die_hip.
 importing this package fails if that library is missing — there is no CPU fallback.
 """
 from . import _lib
+from . import functional
 from .agent import Agent, BrownianAgent, ConstAgent, ConvolutionModel, GradientAgent, NeuralAutomataAgent, PhysarumAgent
 from .base_types import DataChannels
 from .data_init import DataInitializer, FieldSequence, PerlinNoiseSequence, WaveSequence
@@ -18,4 +19,4 @@ from .search import CMAES, PGPE
 __all__ = ['WaveSequence', 'PerlinNoiseSequence', 'FieldSequence', 'Env', 'Dynamics', 'BoundaryCondition', 'linear_action_cost', 'zero_cost', 'Agent', 'PhysarumAgent',
            'GradientAgent', 'BrownianAgent', 'ConstAgent', 'NeuralAutomataAgent', 'ConvolutionModel', 'DataInitializer', 'DataChannels', 'DeviceMedium',
            'DeviceAgents', 'DeviceAction', 'PGPE', 'CMAES', 'BatchedEnv', 'BatchedPhysarumAgent',
-           'BatchedNeuralAutomataAgent', 'BatchedPhysarumPopulation', 'ParameterSpace', 'episode_seeds']
+           'BatchedNeuralAutomataAgent', 'BatchedPhysarumPopulation', 'ParameterSpace', 'episode_seeds', 'functional']

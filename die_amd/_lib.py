@@ -230,6 +230,10 @@ _SIGNATURES = {
                                                  C.c_void_p, C.c_int64, _P(NcaDropout), C.c_void_p]),
     'die_conv2d_wide': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P(ConvPlane), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
                                   C.c_void_p, C.c_int32, C.c_int32, _P(NcaDropout), C.c_void_p]),
+    'die_conv2d_wide_backward_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    'die_conv2d_wide_backward': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P(ConvPlane), C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                           C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, _P(NcaDropout), C.c_void_p,
+                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     'die_nca_wide_batch_scratch_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'die_nca_wide_env_step_batch': (C.c_int, [_P(Medium), _P(Agents), _P(NcaBatch), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
                                               C.c_void_p, C.c_int64, _P(NcaDropout), C.c_void_p, _P(DynamicsRow), C.c_void_p]),

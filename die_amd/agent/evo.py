@@ -121,6 +121,28 @@ class ConvolutionModel(nn.Module):
         keep = self.agent_dropout(th.ones(input.shape[-2:], device=input.device, dtype=input.dtype))
         return self.kernels(input) * keep
 
+    def forward_device(self, planes: th.Tensor, dropout=None) -> th.Tensor:
+        """A wide stack on the device, differentiable: `planes` (num_obs_channels, W, H), float32 on a GPU -> (num_act_channels, W,
+        H) with a `grad_fn`.  Every layer is one `die_amd.functional.conv2d_wide` (die_conv2d_wide forward, die_conv2d_wide_backward
+        backward): the hidden activation after every layer but the last, Tanh and the optional mask `dropout` = (p, seed, step) —
+        the counter-based mask of `NeuralAutomataAgent(dropout_seed=seed)` at `dropout_step` = step — after the last.  The weights
+        reach the device by a differentiable `.to()`, so gradients land in `parameters()` wherever the model lives.  The values are
+        bit for bit what `NeuralAutomataAgent.sense` returns on a medium holding those planes: the same launches.  Boundaries
+        'circular' and 'zeros' where a gradient is needed.  A narrow model (neither `hidden_channels` nor `hidden_activation`)
+        raises ValueError: it has `NeuralAutomataAgent.differentiable_sense`."""
+        from ..functional import conv2d_wide
+        if not self.wide:
+            raise ValueError('forward_device: a narrow model (hidden_channels and hidden_activation both None) is differentiated by '
+                             'NeuralAutomataAgent.differentiable_sense')
+        layers = self.conv_layers()
+        out = planes
+        for li, layer in enumerate(layers):
+            last = li == len(layers) - 1
+            weight = layer.weight.to(device=planes.device, dtype=th.float32).contiguous()
+            out = conv2d_wide(out, weight, activation='tanh' if last else self.hidden_activation, padding_mode=layer.padding_mode,
+                              dropout=dropout if last else None)
+        return out
+
 
 class NeuralAutomataAgent(TorchAgent):
     """core/agent/evo.py:121-209.
@@ -285,8 +307,8 @@ class NeuralAutomataAgent(TorchAgent):
         `sense`.  Boundaries 'circular' and 'zeros'; 'reflect' / 'replicate' raise NotImplementedError before any launch.
         `sense` and `forward` are untouched by all this: never differentiable, same scratch, same launches.
 
-        A wide stack (`hidden_channels` / `hidden_activation`) has no adjoint kernels: NotImplementedError, before any launch
-        and before `dropout_step` moves."""
+        A wide stack (`hidden_channels` / `hidden_activation`) is refused here: NotImplementedError, before any launch and before
+        `dropout_step` moves.  Its gradients come from `ConvolutionModel.forward_device` and `die_amd.functional`."""
         self._check_wide('differentiable_sense')
         layers = self._model.conv_layers()
         for k in layers:

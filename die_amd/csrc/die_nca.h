@@ -8,6 +8,11 @@
 #define NCA_MAXC 4
 #define NCA_MAXK 7
 
+// the wide layer kernels (die_nca_wide.hip: the forward; die_nca_wide_grad.hip: its adjoint)
+#define NCAW_MAXC 32             // channels in or out of one layer
+#define NCAW_CH 4                // input channels per staged chunk: one MFMA K-step per tap
+typedef float ncaw_f32x4 __attribute__((ext_vector_type(4)));
+
 // index of the cell that stands in for coordinate v of an axis of n cells, or −1 for "reads as zero" (torch.nn.functional.pad:
 // 'circular' wraps, 'zeros' pads with 0, 'reflect' mirrors WITHOUT repeating the edge cell, 'replicate' repeats it)
 __device__ __forceinline__ int nca_pad_index(int v, int n, int mode) {
@@ -34,3 +39,6 @@ int die_dropout_words(const die_nca_dropout* drop, DropWords* out, const char* w
 // of the batched read-out, sensing and adjoint: checked before anything is launched (die_nca.hip)
 int die_nca_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who);
 int die_nca_batch_shape_check(const die_medium* m, const die_batch* b, const char* who);
+
+// k_conv_backward_sum on `tiles` partial rows of nw weights (die_nca_grad.hip), for the wide adjoint's rows as well
+void die_conv_backward_fold(const float* part, int64_t tiles, int nw, float* out, hipStream_t s);

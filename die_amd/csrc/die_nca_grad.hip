@@ -195,6 +195,11 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_backward_sum(const float* pa
     if (j < nw) conv_backward_sum_one(part, tiles, nw, j, out);
 }
 
+// the same launch for die_conv2d_wide_backward's partial rows (die_nca_wide_grad.hip)
+void die_conv_backward_fold(const float* part, int64_t tiles, int nw, float* out, hipStream_t s) {
+    k_conv_backward_sum<<<die_grid_for(nw), DIE_BLOCK, 0, s>>>(part, tiles, nw, out);
+}
+
 // die_nca_backward_batch's: one thread per (candidate blockIdx.y, weight j).  The E replicas of candidate c hold their partial rows
 // one behind the other ([replica][tile][nw], replica = c · E + e), so the fold "episode e = 0 … E − 1 outermost, tile index ascending
 // inside" is ONE ascending walk over E · tiles rows — for E = 1 k_conv_backward_sum on replica c's rows.

@@ -36,11 +36,6 @@
 #include "die_rng.h"
 #include "die_nca.h"
 
-#define NCAW_MAXC 32             // channels in or out of one layer
-#define NCAW_CH 4                // input channels per staged chunk: one MFMA K-step per tap
-
-typedef float ncaw_f32x4 __attribute__((ext_vector_type(4)));
-
 struct WideArgs {
     const void* in[NCAW_MAXC];
     int kind[NCAW_MAXC];         // die_conv_plane.kind

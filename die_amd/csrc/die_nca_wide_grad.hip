@@ -1,0 +1,424 @@
+// The adjoint of one wide NeuralAutomataAgent layer (gfx950): what die_nca_wide.hip's k_conv_wide computes forward,
+//   y = act(conv(x, w)) (* the dropout mask), up to 32 channels in and out, kernel sizes 1, 3 and 5,
+// differentiated with respect to the weights and, where asked, the inputs — both GEMMs on v_mfma_f32_16x16x4_f32
+// (__builtin_amdgcn_mfma_f32_16x16x4f32), as the forward.  The gradient at the pre-activation,
+//   g_z = g * mask * act'(t),   act'(t) = 1 - t^2 (tanh), t > 0 ? 1 : 0 (relu, torch's convention from the stored output), 1 (none),
+// is formed while a kernel stages its operands, from the gradient g at the returned value, the layer's UNMASKED output
+// t = act(z) and the mask recomputed from its key (die_rng.h) — no launch and no buffer of its own, no division by keep.
+//
+//   k_conv_wide_gin<K, NB>   grad_in[i, x, y] = sum_o sum_a sum_b w[o, i, a, b] * g_z[o, pad'(x - a + r), pad'(y - b + r)].  For
+//                       'circular' and 'zeros' the padding's adjoint is the padding itself (also where the radius exceeds the
+//                       field), so this IS the forward's implicit GEMM over the g_z planes with the weight read as
+//                       w'[i][o][a][b] = w[o][i][k-1-a][k-1-b] and no activation: k_conv_wide's body — the 16 x 64 tile and its 4
+//                       waves, chunks of 4 channels through LDS with the next chunk's global loads issued before this chunk's
+//                       MFMAs, s_in with its channel stride of 16 mod 64 words, s_w with the output fastest, 16-byte stores
+//                       where H % 4 == 0 — with g_z formed between the registers and LDS.  A second kernel, not a template
+//                       parameter on k_conv_wide: the forward's instantiations stay the code they were.
+//   k_conv_wide_gw<K, GO, GI>   grad_w[o, i, a, b] = sum_xy g_z[o, x, y] * in[i, pad(x + a - r), pad(y + b - r)]: per tile and tap
+//                       a (cout x cells) . (cells x cin) GEMM with the tile's cells as the K dimension.  One MFMA covers 4
+//                       consecutive y of one row: A = g_z[o = lane & 15][cell c0 + (lane >> 4)], B = in[i = lane & 15][that cell +
+//                       tap], both 64 consecutive LDS words of planes staged [cell][16 channels], channel fastest (GO / GI = 1 or
+//                       2 groups of 16 output / input channels; channels past cout / cin are zeros).  The k^2 taps are dealt to
+//                       the 4 waves as w, w + 4, ... (at most 7 at k = 5), a wave keeps GO * GI accumulator blocks per tap (at most
+//                       112 VGPRs) and the tile is walked in strips of SR rows, SR the largest of 4, 2, 1 whose g_z strip and
+//                       input strip with halo fit 64 KB of LDS next to the tile's mask factors (4 KB, worked out once, so
+//                       that the Philox key schedule is not live over the strips).  Cells of a partial tile past W or H are staged as
+//                       g_z = 0; the input cells are read through nca_pad_index, the first layer's through nca_load.  An element
+//                       of the tile's partial row [cout * cin * k * k] is summed over (strip, row, 4 cells, cell) in that order
+//                       and written exactly once, by one lane.  NO float atomics.
+//   the fold            die_nca_grad.hip's k_conv_backward_sum: one thread per weight adds the partial rows in tile-index order
+//                       in float64 and stores fp32.  Fixed order, fixed tree: the same inputs give the same bits on every run.
+//
+// Roofline.  Both GEMMs are 2 C^2 k^2 flop per cell, the forward's count, against 12 C bytes (g, t and the inputs in; the input
+// gradient out): a C -> C layer with C >= 16 at k >= 3 is compute-bound on the fp32 matrix rate (157 TFLOP/s, 64 flop per clock
+// per SIMD) in either kernel.  The layers touching 3 channels stay HBM-bound and pay for the padding to 4 (a chunk) and 16 (a
+// block): 3 -> 16's weight gradient issues 16 / 3 of the MFMAs its 3 input channels need.
+#include <math.h>
+#include "die_common.h"
+#include "die_rng.h"
+#include "die_nca.h"
+
+struct WideBwdArgs {
+    const void* in[NCAW_MAXC];   // the layer's inputs
+    int kind[NCAW_MAXC];         // die_conv_plane.kind
+    const float* g;              // gradient at the returned value: plane o at g + o * g_stride
+    const float* t;              // the unmasked forward output act(z), plane o at t + o * t_stride (read where act != none)
+    int64_t g_stride, t_stride;
+    const float* w;              // [cout][cin][k][k]
+    float* gin;                  // gradient at the inputs: plane i at gin + i * gin_stride
+    int64_t gin_stride;
+    float* part;                 // [tiles][cout * cin * k * k]
+    int W, H, cin, cout, epoch;
+    int act;                     // die_nca_activation of the forward's epilogue
+    int pad;                     // die_pad_mode: circular or zeros
+    int vec;                     // 16-byte stores of grad_in: H % 4 == 0 (the entry point has checked the alignment)
+    int drop;                    // 1: g_z carries the dropout mask of `d`
+    DropWords d;
+};
+
+// g_z of one cell and channel: the gradient at the returned value through the mask and the activation
+__device__ __forceinline__ float ncaw_gz(float g, float t, float mask, int act, int drop) {
+    float v = g;
+    if (drop) v = v * mask;
+    if (act == DIE_NCA_ACT_TANH) v = v * (1.f - t * t);
+    else if (act == DIE_NCA_ACT_RELU) v = t > 0.f ? v : 0.f;
+    return v;
+}
+
+// ---- input gradient: k_conv_wide over the g_z planes with the flipped, transposed weight ---------------------------------
+template <int K, int NB>
+__global__ __launch_bounds__(DIE_BLOCK) void k_conv_wide_gin(WideBwdArgs a) {
+    constexpr int R = K / 2, LX = NCA_TX + 2 * R, LY = NCA_TY + 2 * R;
+    constexpr int CS = (LX * LY - 16 + 63) / 64 * 64 + 16;         // channel stride: 16 mod 64 words
+    constexpr int MB = 16;                                          // M-blocks per wave: 4 rows x 4 blocks of 16 y
+    __shared__ __align__(16) float s_in[NCAW_CH * CS];
+    __shared__ __align__(16) float s_w[K * K * NB * NCAW_CH * 16];
+    const int x0 = blockIdx.y * NCA_TX, y0 = blockIdx.x * NCA_TY;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lk = lane >> 4, ln = lane & 15;
+    const bool has_t = a.act != DIE_NCA_ACT_NONE;
+
+    ncaw_f32x4 acc[MB][NB];
+#pragma unroll
+    for (int m = 0; m < MB; ++m)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) acc[m][nb] = ncaw_f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // the forward's staging plan: tile words i = tid, tid + 256, ... of every g_z plane and the weight words likewise, their
+    // addresses worked out once — and the mask of every tile word, which no chunk changes
+    constexpr int NI = (LX * LY + DIE_BLOCK - 1) / DIE_BLOCK, NWI = (K * K * NB * NCAW_CH * 16 + DIE_BLOCK - 1) / DIE_BLOCK;
+    int64_t cell[NI];
+    float mask[NI];
+    int wbase[NWI];                                                // the word's offset in w for chunk 0 (0 for a zero word)
+    unsigned live = 0, wlive = 0;
+#pragma unroll
+    for (int t = 0; t < NI; ++t) {
+        const int i = threadIdx.x + t * DIE_BLOCK, li = i / LY, lj = i - li * LY;
+        // (rows / columns past the last tile's outputs wrap like a circular field whatever the mode: never used)
+        const int vx = x0 - R + li, vy = y0 - R + lj;
+        const int gx = nca_pad_index(vx < a.W + R ? vx : vx % a.W, a.W, a.pad), gy = nca_pad_index(vy < a.H + R ? vy : vy % a.H, a.H, a.pad);
+        const bool ok = i < LX * LY && gx >= 0 && gy >= 0;
+        cell[t] = ok ? (int64_t)gx * a.H + gy : 0;
+        live |= ok ? 1u << t : 0u;
+        mask[t] = a.drop ? die_dropout_factor(die_dropout_word(a.d.seed, a.d.step, (uint64_t)cell[t]), a.d.thr, a.d.keep) : 1.f;
+    }
+    // s_w[a][b][nb][c][i]: the word of output (input channel of the layer) i = nb * 16 + (word & 15), chunk channel c (an output
+    // channel of the layer), tap (a, b) is w[c][i][k-1-a][k-1-b]
+#pragma unroll
+    for (int t = 0; t < NWI; ++t) {
+        const int i = threadIdx.x + t * DIE_BLOCK, o = ((i >> 6) % NB) * 16 + (i & 15), tap = i / (64 * NB);
+        const bool ok = i < K * K * NB * NCAW_CH * 16 && o < a.cin;
+        wbase[t] = ok ? (((i >> 4) & 3) * a.cin + o) * (K * K) + (K * K - 1 - tap) : 0;
+        wlive |= ok ? 1u << t : 0u;
+    }
+    float pre[NI][NCAW_CH], pret[NI][NCAW_CH], wpre[NWI];
+    auto fetch = [&](int c0) {
+#pragma unroll
+        for (int t = 0; t < NWI; ++t) {
+            const int c = c0 + (((threadIdx.x + t * DIE_BLOCK) >> 4) & 3);
+            wpre[t] = a.w[c < a.cout ? wbase[t] + c0 * a.cin * (K * K) : 0];
+        }
+#pragma unroll
+        for (int j = 0; j < NCAW_CH; ++j) {
+            const int c = c0 + j;                                   // (uniform)
+            if (c >= a.cout) continue;
+            const float* gp = a.g + (int64_t)c * a.g_stride;
+#pragma unroll
+            for (int t = 0; t < NI; ++t) pre[t][j] = gp[cell[t]];
+            if (has_t) {
+                const float* tp = a.t + (int64_t)c * a.t_stride;
+#pragma unroll
+                for (int t = 0; t < NI; ++t) pret[t][j] = tp[cell[t]];
+            }
+        }
+    };
+#pragma unroll
+    for (int t = 0; t < NI; ++t)
+#pragma unroll
+        for (int j = 0; j < NCAW_CH; ++j) pre[t][j] = pret[t][j] = 0.f;
+    fetch(0);
+    for (int c0 = 0; c0 < a.cout; c0 += NCAW_CH) {
+        if (c0) __syncthreads();                                    // the previous chunk has been read
+#pragma unroll
+        for (int t = 0; t < NWI; ++t) {
+            const int i = threadIdx.x + t * DIE_BLOCK;
+            const int c = c0 + ((i >> 4) & 3);
+            if (i < K * K * NB * NCAW_CH * 16) s_w[i] = ((wlive >> t) & 1) && c < a.cout ? wpre[t] : 0.f;
+        }
+#pragma unroll
+        for (int t = 0; t < NI; ++t) {
+            const int i = threadIdx.x + t * DIE_BLOCK;
+            if (i < LX * LY) {
+#pragma unroll
+                for (int j = 0; j < NCAW_CH; ++j)
+                    s_in[j * CS + i] = ((live >> t) & 1) && c0 + j < a.cout ? ncaw_gz(pre[t][j], pret[t][j], mask[t], a.act, a.drop) : 0.f;
+            }
+        }
+        __syncthreads();
+        if (c0 + NCAW_CH < a.cout) fetch(c0 + NCAW_CH);
+#pragma unroll
+        for (int ka = 0; ka < K; ++ka) {
+#pragma unroll
+            for (int kb = 0; kb < K; ++kb) {
+                float bv[NB];
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb) bv[nb] = s_w[((ka * K + kb) * NB + nb) * 64 + lane];
+#pragma unroll
+                for (int m = 0; m < MB; ++m) {
+                    const float av = s_in[lk * CS + (wave * 4 + (m >> 2) + ka) * LY + (m & 3) * 16 + ln + kb];
+#pragma unroll
+                    for (int nb = 0; nb < NB; ++nb) acc[m][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[nb], acc[m][nb], 0, 0, 0);
+                }
+            }
+        }
+    }
+
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+        const int gx = x0 + wave * 4 + (m >> 2), gy = y0 + (m & 3) * 16 + lk * 4;      // this lane's 4 cells: (gx, gy .. gy + 3)
+        if (gx >= a.W || gy >= a.H) continue;
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) {
+            const int i = nb * 16 + ln;
+            if (i >= a.cin) continue;
+            float* dst = a.gin + (int64_t)i * a.gin_stride + (int64_t)gx * a.H + gy;
+            if (a.vec) *(float4*)dst = make_float4(acc[m][nb][0], acc[m][nb][1], acc[m][nb][2], acc[m][nb][3]);
+            else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) if (gy + q < a.H) dst[q] = acc[m][nb][q];
+            }
+        }
+    }
+}
+
+// ---- weight gradient: one partial row per tile ---------------------------------------------------------------------------
+// rows per strip: the largest of 4, 2, 1 whose g_z strip [GO][SR][64][16] and input strip [GI][SR + 2r][64 + 2r][16] fit 64 KB
+// next to the tile's 4 KB of mask factors
+template <int K, int GO, int GI>
+constexpr int ncaw_gw_strip() {
+    constexpr int R = K / 2;
+    for (int sr = 4; sr > 1; sr >>= 1)
+        if (((GO * sr * NCA_TY + GI * (sr + 2 * R) * (NCA_TY + 2 * R)) * 16 + NCA_TX * NCA_TY) * 4 <= 65536) return sr;
+    return 1;
+}
+
+template <int K, int GO, int GI>
+__global__ __launch_bounds__(DIE_BLOCK) void k_conv_wide_gw(WideBwdArgs a) {
+    constexpr int R = K / 2, SR = ncaw_gw_strip<K, GO, GI>(), LY = NCA_TY + 2 * R, XR = SR + 2 * R;
+    constexpr int NT = (K * K + 3) / 4;                             // taps per wave: wave, wave + 4, ...
+    constexpr int GCELLS = SR * NCA_TY, XCELLS = XR * LY;
+    static_assert(((GO * GCELLS + GI * XCELLS) * 16 + NCA_TX * NCA_TY) * 4 <= 65536, "the strips do not fit LDS");
+    static_assert(NCA_TX % SR == 0 && DIE_BLOCK % GCELLS == 0, "strips tile the rows, a strip's cells the workgroup");
+    __shared__ __align__(16) float s_g[GO * GCELLS * 16];           // [group of 16 o][row][y][o]
+    __shared__ __align__(16) float s_x[GI * XCELLS * 16];           // [group of 16 i][row + halo][y + halo][i]
+    __shared__ float s_m[NCA_TX * NCA_TY];                          // the tile's mask factors (written and read with a mask only)
+    const int x0 = blockIdx.y * NCA_TX, y0 = blockIdx.x * NCA_TY;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lk = lane >> 4, ln = lane & 15;
+    const bool has_t = a.act != DIE_NCA_ACT_NONE;
+
+    ncaw_f32x4 acc[NT][GO][GI];
+    int toff[NT];                                                   // tap (ta, tb)'s offset in s_x, in cells
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int tap = wave + 4 * j, ta = tap / K, tb = tap - ta * K;
+        toff[j] = ta * LY + tb;
+#pragma unroll
+        for (int og = 0; og < GO; ++og)
+#pragma unroll
+            for (int ig = 0; ig < GI; ++ig) acc[j][og][ig] = ncaw_f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    // the mask of every cell of the tile, once (the Philox key schedule does not stay live over the strips)
+    if (a.drop) {
+#pragma unroll
+        for (int n = 0; n < NCA_TX * NCA_TY / DIE_BLOCK; ++n) {
+            const int i = threadIdx.x + n * DIE_BLOCK, gx = x0 + i / NCA_TY, gy = y0 + i % NCA_TY;
+            const uint64_t cell = gx < a.W && gy < a.H ? (uint64_t)gx * (uint64_t)a.H + (uint64_t)gy : 0;
+            s_m[i] = die_dropout_factor(die_dropout_word(a.d.seed, a.d.step, cell), a.d.thr, a.d.keep);
+        }
+        __syncthreads();
+    }
+
+#pragma unroll 1
+    for (int r0 = 0; r0 < NCA_TX && x0 + r0 < a.W; r0 += SR) {      // (a strip past the field holds g_z = 0 only)
+        if (r0) __syncthreads();                                    // the previous strip has been read
+        // g_z: a thread stages ONE cell of the strip, tid % GCELLS (consecutive lanes on consecutive y: a plane's loads coalesce),
+        // for the quads of channels tid / GCELLS, that + 256 / GCELLS, ...: one 16-byte LDS store per quad
+        {
+            const int ci = threadIdx.x % GCELLS, gx = x0 + r0 + ci / NCA_TY, gy = y0 + ci % NCA_TY;
+            const bool ok = gx < a.W && gy < a.H;
+            const int64_t cell = ok ? (int64_t)gx * a.H + gy : 0;
+            const float m = a.drop ? s_m[r0 * NCA_TY + ci] : 1.f;
+#pragma unroll 1
+            for (int q = threadIdx.x / GCELLS; q < 4 * GO; q += DIE_BLOCK / GCELLS) {
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int o = 4 * q + e;
+                    v[e] = 0.f;
+                    if (o < a.cout && ok) {
+                        const float g = a.g[(int64_t)o * a.g_stride + cell];
+                        const float t = has_t ? a.t[(int64_t)o * a.t_stride + cell] : 0.f;
+                        v[e] = ncaw_gz(g, t, m, a.act, a.drop);
+                    }
+                }
+                *(float4*)&s_g[((q >> 2) * GCELLS + ci) * 16 + (q & 3) * 4] = make_float4(v[0], v[1], v[2], v[3]);
+            }
+        }
+        // the inputs under the strip and its halo, through the padding (a cell past the field in a partial tile reads whatever
+        // the padding gives: its g_z is 0)
+#pragma unroll 1
+        for (int cj = threadIdx.x; cj < XCELLS; cj += DIE_BLOCK) {
+            const int li = cj / LY, lj = cj - li * LY;
+            const int gx = nca_pad_index(x0 + r0 - R + li, a.W, a.pad), gy = nca_pad_index(y0 - R + lj, a.H, a.pad);
+            const bool ok = gx >= 0 && gy >= 0;
+            const int64_t cell = ok ? (int64_t)gx * a.H + gy : 0;
+#pragma unroll 1
+            for (int q = 0; q < 4 * GI; ++q) {
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int c = 4 * q + e;                        // (uniform: the plane's pointer and kind are scalar loads)
+                    v[e] = 0.f;
+                    if (c < a.cin) {
+                        const void* p = a.in[c];
+                        const int kind = a.kind[c];
+                        if (ok) v[e] = nca_load(p, kind, cell, a.epoch);
+                    }
+                }
+                *(float4*)&s_x[((q >> 2) * XCELLS + cj) * 16 + (q & 3) * 4] = make_float4(v[0], v[1], v[2], v[3]);
+            }
+        }
+        __syncthreads();
+        // one K-step = 4 consecutive y of one row; lane (lk, ln) reads word lane of the step's 64 in either operand
+        for (int s = 0; s < SR * (NCA_TY / 4); ++s) {
+            const int gcell = (s >> 4) * NCA_TY + (s & 15) * 4 + lk, xcell = (s >> 4) * LY + (s & 15) * 4 + lk;
+            float av[GO];
+#pragma unroll
+            for (int og = 0; og < GO; ++og) av[og] = s_g[(og * GCELLS + gcell) * 16 + ln];
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                if (wave + 4 * j < K * K) {                         // (wave-uniform)
+                    float bv[GI];
+#pragma unroll
+                    for (int ig = 0; ig < GI; ++ig) bv[ig] = s_x[(ig * XCELLS + xcell + toff[j]) * 16 + ln];
+#pragma unroll
+                    for (int og = 0; og < GO; ++og)
+#pragma unroll
+                        for (int ig = 0; ig < GI; ++ig)
+                            acc[j][og][ig] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[og], bv[ig], acc[j][og][ig], 0, 0, 0);
+                }
+            }
+        }
+    }
+
+    // accumulator block (og, ig) of tap (ta, tb): column lane & 15 = input channel, rows 4 (lane >> 4) + q = output channel
+    const int nw = a.cout * a.cin * K * K;
+    float* prow = a.part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * nw;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int tap = wave + 4 * j;
+        if (tap >= K * K) continue;
+#pragma unroll
+        for (int og = 0; og < GO; ++og) {
+#pragma unroll
+            for (int ig = 0; ig < GI; ++ig) {
+                const int i = ig * 16 + ln;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int o = og * 16 + lk * 4 + q;
+                    if (o < a.cout && i < a.cin) prow[(o * a.cin + i) * (K * K) + tap] = acc[j][og][ig][q];
+                }
+            }
+        }
+    }
+}
+
+template <int K>
+static void launch_wide_backward(const WideBwdArgs& a, bool want_gin, hipStream_t s) {
+    dim3 grid((a.H + NCA_TY - 1) / NCA_TY, (a.W + NCA_TX - 1) / NCA_TX);
+    const bool go2 = a.cout > 16, gi2 = a.cin > 16;
+    if (go2 && gi2) k_conv_wide_gw<K, 2, 2><<<grid, DIE_BLOCK, 0, s>>>(a);
+    else if (go2) k_conv_wide_gw<K, 2, 1><<<grid, DIE_BLOCK, 0, s>>>(a);
+    else if (gi2) k_conv_wide_gw<K, 1, 2><<<grid, DIE_BLOCK, 0, s>>>(a);
+    else k_conv_wide_gw<K, 1, 1><<<grid, DIE_BLOCK, 0, s>>>(a);
+    if (!want_gin) return;
+    if (gi2) k_conv_wide_gin<K, 2><<<grid, DIE_BLOCK, 0, s>>>(a);
+    else k_conv_wide_gin<K, 1><<<grid, DIE_BLOCK, 0, s>>>(a);
+}
+
+static bool wide_shape_ok(int32_t W, int32_t H, int32_t cin, int32_t cout, int32_t k) {
+    return W >= 1 && H >= 1 && (W + NCA_TX - 1) / NCA_TX <= 65535 && cin >= 1 && cin <= NCAW_MAXC && cout >= 1 && cout <= NCAW_MAXC &&
+           (k == 1 || k == 3 || k == 5);
+}
+static int64_t wide_tiles(int32_t W, int32_t H) { return (int64_t)((W + NCA_TX - 1) / NCA_TX) * ((H + NCA_TY - 1) / NCA_TY); }
+
+extern "C" int64_t die_conv2d_wide_backward_workspace_bytes(int32_t W, int32_t H, int32_t cin, int32_t cout, int32_t k) {
+    if (!wide_shape_ok(W, H, cin, cout, k)) return -1;
+    return wide_tiles(W, H) * cout * cin * k * k * (int64_t)sizeof(float);
+}
+
+extern "C" int die_conv2d_wide_backward(int32_t W, int32_t H, int32_t cin, const die_conv_plane* in, int32_t epoch, int32_t cout,
+                                        const float* grad_out, int64_t grad_out_stride, const float* fwd_out, int64_t fwd_out_stride,
+                                        int32_t k, const float* weights, int32_t activation, int32_t padding_mode,
+                                        const die_nca_dropout* drop, float* grad_weights, float* grad_in, int64_t grad_in_stride,
+                                        void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* who = "die_conv2d_wide_backward";
+    DIE_REQUIRE(padding_mode >= DIE_PAD_CIRCULAR && padding_mode <= DIE_PAD_REPLICATE, "%s: bad padding mode %d", who, padding_mode);
+    if (padding_mode == DIE_PAD_REFLECT || padding_mode == DIE_PAD_REPLICATE) {
+        die_set_error("%s: the adjoint of 'reflect' / 'replicate' padding is not implemented ('circular' and 'zeros' are)", who);
+        return DIE_ERR_UNSUPPORTED;
+    }
+    DIE_REQUIRE(W >= 1 && H >= 1, "%s: bad size %dx%d", who, W, H);
+    DIE_REQUIRE((W + NCA_TX - 1) / NCA_TX <= 65535, "%s: field too tall", who);
+    DIE_REQUIRE(cin >= 1 && cin <= NCAW_MAXC && cout >= 1 && cout <= NCAW_MAXC, "%s: 1..%d channels (got %d -> %d)", who, NCAW_MAXC, cin, cout);
+    DIE_REQUIRE(k == 1 || k == 3 || k == 5, "%s: kernel size %d (1, 3 or 5)", who, k);
+    DIE_REQUIRE(activation >= DIE_NCA_ACT_NONE && activation <= DIE_NCA_ACT_RELU, "%s: bad activation %d", who, activation);
+    DIE_REQUIRE(in && grad_out && weights && grad_weights && workspace, "%s: null argument", who);
+    DIE_REQUIRE(fwd_out || (activation == DIE_NCA_ACT_NONE && !drop), "%s: an activation or a dropout mask without the forward outputs "
+                "it was applied to", who);
+    DIE_REQUIRE(grad_weights != weights, "%s: grad_weights is the weights", who);
+    const int64_t cells = (int64_t)W * H, nw = (int64_t)cout * cin * k * k;
+    DIE_REQUIRE(grad_out_stride >= cells, "%s: grad_out_stride %lld smaller than a plane (%lld cells)", who, (long long)grad_out_stride,
+                (long long)cells);
+    DIE_REQUIRE(!fwd_out || fwd_out_stride >= cells, "%s: fwd_out_stride %lld smaller than a plane (%lld cells)", who,
+                (long long)fwd_out_stride, (long long)cells);
+    DIE_REQUIRE(!grad_in || grad_in_stride >= cells, "%s: grad_in_stride %lld smaller than a plane (%lld cells)", who,
+                (long long)grad_in_stride, (long long)cells);
+    const int64_t need = die_conv2d_wide_backward_workspace_bytes(W, H, cin, cout, k);
+    DIE_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%lld < %lld)", who, (long long)workspace_bytes, (long long)need);
+    WideBwdArgs a = {};
+    const char* lo = (const char*)grad_in;
+    const char* hi = grad_in ? lo + ((int64_t)(cin - 1) * grad_in_stride + cells) * (int64_t)sizeof(float) : lo;
+    auto overlaps = [&](const void* p, int64_t bytes) { return grad_in && p && (const char*)p < hi && (const char*)p + bytes > lo; };
+    for (int c = 0; c < cin; ++c) {
+        DIE_REQUIRE(in[c].data && in[c].kind >= DIE_PLANE_F32 && in[c].kind <= DIE_PLANE_AGENTS, "%s: bad input plane %d", who, c);
+        const int64_t bytes = cells * (in[c].kind == DIE_PLANE_F32 ? 4 : in[c].kind == DIE_PLANE_F16 ? 2 : 8);
+        DIE_REQUIRE(!overlaps(in[c].data, bytes), "%s: grad_in aliases another buffer of the call (input plane %d)", who, c);
+        a.in[c] = in[c].data; a.kind[c] = in[c].kind;
+    }
+    DIE_REQUIRE(!overlaps(grad_out, ((int64_t)(cout - 1) * grad_out_stride + cells) * 4) &&
+                    !overlaps(fwd_out, ((int64_t)(cout - 1) * fwd_out_stride + cells) * 4) && !overlaps(weights, nw * 4) &&
+                    !overlaps(grad_weights, nw * 4) && !overlaps(workspace, need),
+                "%s: grad_in aliases another buffer of the call", who);
+    // the kernel stores four cells of a row at once where H % 4 == 0
+    DIE_REQUIRE(!grad_in || H % 4 != 0 || (((uintptr_t)grad_in & 15) == 0 && grad_in_stride % 4 == 0),
+                "%s: grad_in must be 16-byte aligned and grad_in_stride a multiple of 4 where H %% 4 == 0", who);
+    if (drop) {
+        const int rc = die_dropout_words(drop, &a.d, who);
+        if (rc != DIE_OK) return rc;
+        a.drop = 1;
+    }
+    a.g = grad_out; a.g_stride = grad_out_stride; a.t = fwd_out; a.t_stride = fwd_out_stride;
+    a.w = weights; a.gin = grad_in; a.gin_stride = grad_in_stride; a.part = (float*)workspace;
+    a.W = W; a.H = H; a.cin = cin; a.cout = cout; a.epoch = epoch; a.act = activation; a.pad = padding_mode;
+    a.vec = H % 4 == 0;
+    hipStream_t s = (hipStream_t)stream;
+    switch (k) {
+        case 1: launch_wide_backward<1>(a, grad_in != nullptr, s); break;
+        case 3: launch_wide_backward<3>(a, grad_in != nullptr, s); break;
+        default: launch_wide_backward<5>(a, grad_in != nullptr, s); break;
+    }
+    DIE_CHECK_LAUNCH(who);
+    die_conv_backward_fold((const float*)workspace, wide_tiles(W, H), (int)nw, grad_weights, s);
+    DIE_CHECK_LAUNCH("die_conv2d_wide_backward(sum)");
+    return DIE_OK;
+}

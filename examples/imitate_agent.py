@@ -3,6 +3,7 @@ examples/learning_agents.py, and a way to give its searchers a warm start (`lear
 
     python examples/imitate_agent.py [--size 96] [--steps 300] [--lr 0.01] [--dynamics st-perlin-wide] [--seed 0]
                                      [--out saved_models/imitated_agent.pt] [--replicas R [--students C]] [--time]
+                                     [--hidden-channels C] [--hidden-activation {tanh,relu,none}]
 
 The teacher is a GradientAgent without noise and without momentum; it steps the world.  Every step the student — the searchers'
 architecture, kernel_sizes=[3, 3] — looks at the same observation through `differentiable_action` (one forward launch per layer
@@ -10,6 +11,11 @@ and the read-out), the loss is the mean squared error of its (dx, dy) against th
 scale², and `loss.backward()` runs the adjoint kernels (die_conv2d_backward per layer, die_gather_scale_backward): one forward
 plus one backward per world step, nothing of the field leaves the device.  Adam updates the 162 weights; the loss is printed
 every 10 steps and the agent is saved with `save()`.
+
+`--hidden-channels C --hidden-activation A` (the stand-alone student only) make the student a wide stack, 3 -> C -> 3 with A after
+the first layer.  It is fitted through `model.forward_device(planes)` on the observation's float32 planes — one
+`die_amd.functional.conv2d_wide` per layer, whose backward is die_conv2d_wide_backward (the MFMA adjoint kernels) — and
+`functional.gather_scale`, the same read-out; the student's own `differentiable_action` refuses a wide stack.
 
 `--replicas R` (with `--students C`, R = C·E; default C = R) is the batched form: R worlds in one BatchedEnv seeded seed … seed + R − 1,
 the teacher a BatchedPhysarumAgent that steps them and hands its actions out through `step(..., action=target)`, the students one
@@ -27,18 +33,29 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from die_amd import Env, GradientAgent, NeuralAutomataAgent          # noqa: E402
+from die_amd import Env, GradientAgent, NeuralAutomataAgent, functional          # noqa: E402
 from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent, BatchedPhysarumAgent    # noqa: E402
-from population_eval import AGENT_KW, DYNAMICS, make_dynamics        # noqa: E402
+from population_eval import AGENT_KW, DYNAMICS, add_wide_arguments, make_dynamics, wide_keywords        # noqa: E402
 
 
-def imitate(size, steps, lr, dynamics, seed, log=print, clock=None):
+def student_action(student, obs):
+    """(3, N) with a `grad_fn`: a narrow student's own differentiable_action; a wide one through the model's forward_device on the
+    observation's planes and the read-out."""
+    if not student.model.wide:
+        return student.differentiable_action(obs)
+    medium = obs[1]
+    medium.sensed()
+    planes = torch.stack([medium.sel(c).float() for c in student.obs_channels])
+    return functional.gather_scale(student.model.forward_device(planes), obs, student.action_coefs)
+
+
+def imitate(size, steps, lr, dynamics, seed, log=print, clock=None, wide_kw=None):
     torch.manual_seed(seed)
     env = Env((size, size), make_dynamics(dynamics, size), seed=seed)
     scale = AGENT_KW['scale']
     teacher = GradientAgent(max_agents=env.agents.capacity, scale=scale, deposit=AGENT_KW['deposit'], inertia=0., noise_scale=0., seed=seed)
     teacher.lazy = False                                          # its action is the target: computed now, not inside the step
-    student = NeuralAutomataAgent(**AGENT_KW)
+    student = NeuralAutomataAgent(**AGENT_KW, **(wide_kw or {}))
     student.model.init_weights()
     opt = torch.optim.Adam(student.model.parameters(), lr=lr)
     obs = env._get_current_obs
@@ -49,7 +66,7 @@ def imitate(size, steps, lr, dynamics, seed, log=print, clock=None):
         action = teacher.forward(obs)
         target = action.data[:2, :agents.N]
         alive = agents.alive[:agents.N] > 0
-        got = student.differentiable_action(obs)
+        got = student_action(student, obs)
         loss = (((got[:2] - target) / scale)[:, alive] ** 2).mean()
         opt.zero_grad()
         loss.backward()
@@ -126,7 +143,10 @@ def main():
     p.add_argument('--replicas', type=int, default=0, help='R worlds in one BatchedEnv (0: the single-world form)')
     p.add_argument('--students', type=int, default=0, help='C students, R = C x E (default: one per replica)')
     p.add_argument('--time', action='store_true', help='print optimiser steps per second')
+    add_wide_arguments(p)
     args = p.parse_args()
+    if args.replicas and wide_keywords(args):
+        raise SystemExit('--hidden-channels / --hidden-activation: the stand-alone student only (no --replicas)')
     if args.replicas:
         clock = _Clock(args.steps, args.time)
         quiet = (lambda *a: None) if args.time else print         # (a loss print reads the device: not inside a timed window)
@@ -138,7 +158,7 @@ def main():
         if args.students:
             raise SystemExit('--students needs --replicas')
         student = imitate(args.size, args.steps, args.lr, args.dynamics, args.seed, log=(lambda *a: None) if args.time else print,
-                          clock=_Clock(args.steps, args.time))
+                          clock=_Clock(args.steps, args.time), wide_kw=wide_keywords(args))
     os.makedirs(os.path.dirname(args.out) or '.', exist_ok=True)
     student.save(args.out)
     print(f'Saving the agent to: {args.out}')

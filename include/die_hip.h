@@ -1007,6 +1007,30 @@ typedef enum die_nca_activation { DIE_NCA_ACT_NONE = 0, DIE_NCA_ACT_TANH = 1, DI
 int die_conv2d_wide(int32_t W, int32_t H, int32_t cin, const die_conv_plane* in, int32_t epoch, int32_t cout, float* out,
                     int64_t out_stride, int32_t k, const float* weights, int32_t activation, int32_t padding_mode,
                     const die_nca_dropout* drop, void* stream);
+/* Bytes of die_conv2d_wide_backward's workspace: one partial row of cout * cin * k * k floats per 16 x 64 tile,
+ *   ceil(W / 16) * ceil(H / 64) * cout * cin * k * k * 4;   -1 for a shape die_conv2d_wide_backward refuses. */
+int64_t die_conv2d_wide_backward_workspace_bytes(int32_t W, int32_t H, int32_t cin, int32_t cout, int32_t k);
+/* The adjoint of one die_conv2d_wide layer (die_nca_wide_grad.hip; added within ABI 24: new symbols only).  The forward returned
+ * y = act(conv(in, weights)) (* the mask of `drop`); given the gradient at y (`grad_out`, plane o at grad_out + o * grad_out_stride)
+ * and the layer's UNMASKED output t = act(z) (`fwd_out`, plane o at fwd_out + o * fwd_out_stride; NULL only with DIE_NCA_ACT_NONE
+ * and no drop), the gradient at z is g_z = grad_out * mask * act'(t) — act'(t) = 1 - t^2 for tanh, (t > 0 ? 1 : 0) for relu, 1 for
+ * none; the mask recomputed from its key, never divided out — formed while the kernels stage their operands, and
+ *   grad_weights[o, i, a, b] = sum_xy g_z[o, x, y] * in[i, pad(x + a - r), pad(y + b - r)]        (cout, cin, k, k) fp32,
+ *   grad_in[i, x, y] = sum_o sum_a sum_b weights[o, i, a, b] * g_z[o, pad'(x - a + r), pad'(y - b + r)]   (nullable; plane i at
+ *                      grad_in + i * grad_in_stride),
+ * both on v_mfma_f32_16x16x4_f32.  At most three launches: the weight-gradient kernel writes one partial row per tile into the
+ * workspace (every element once, no float atomics), the input-gradient kernel runs when grad_in is given, and the fold sums the
+ * rows in tile-index order in float64 (die_conv2d_backward's) — the same inputs give the same bits on every run.  Shapes as
+ * die_conv2d_wide: 1..32 channels, k = 1, 3, 5; `in` as die_conv2d_wide reads it.  Every argument is checked before anything is
+ * launched: DIE_PAD_REFLECT / DIE_PAD_REPLICATE are DIE_ERR_UNSUPPORTED; DIE_ERR_ARG for a bad size, channel count, kernel size,
+ * activation or padding mode, a null pointer, a NULL fwd_out where it is needed, a stride below a plane, grad_weights == weights,
+ * grad_in overlapping any other buffer of the call, a workspace below die_conv2d_wide_backward_workspace_bytes, a bad `drop`, and,
+ * where H % 4 == 0 (16-byte stores), a grad_in that is not 16-byte aligned or a grad_in_stride that is no multiple of 4. */
+int die_conv2d_wide_backward(int32_t W, int32_t H, int32_t cin, const die_conv_plane* in, int32_t epoch, int32_t cout,
+                             const float* grad_out, int64_t grad_out_stride, const float* fwd_out, int64_t fwd_out_stride,
+                             int32_t k, const float* weights, int32_t activation, int32_t padding_mode,
+                             const die_nca_dropout* drop, float* grad_weights, float* grad_in, int64_t grad_in_stride,
+                             void* workspace, int64_t workspace_bytes, void* stream);
 /* Bytes of a batched wide stack's scratch, [set][replica][max_channels][W][H] fp32 with set = layer % 2 (one set for a single
  * layer) and max_channels the largest cout of the stack:
  *   (n_layers >= 2 ? 2 : 1) * replicas * max_channels * W * H * 4;
