@@ -237,6 +237,12 @@ _SIGNATURES = {
     'die_nca_wide_batch_scratch_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'die_nca_wide_env_step_batch': (C.c_int, [_P(Medium), _P(Agents), _P(NcaBatch), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
                                               C.c_void_p, C.c_int64, _P(NcaDropout), C.c_void_p, _P(DynamicsRow), C.c_void_p]),
+    'die_nca_wide_sense_batch_store_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    'die_nca_wide_sense_batch_store': (C.c_int, [_P(Medium), _P(Batch), _P(NcaBatch), C.c_void_p, C.c_int64, C.c_void_p, _P(NcaDropout),
+                                                 C.c_void_p]),
+    'die_nca_wide_backward_batch_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, _P(NcaBatch)]),
+    'die_nca_wide_backward_batch': (C.c_int, [_P(Medium), _P(Batch), _P(NcaBatch), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                              _P(NcaDropout), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     'die_dropout_mask': (C.c_int, [C.c_int32, C.c_int32, _P(NcaDropout), C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
     'die_forward_move_claim_tile': (C.c_int, [_P(Medium), _P(Agents), _P(GradientAgent), _P(Action), _P(Dynamics), C.c_void_p,
                                               C.c_int64, C.c_void_p]),

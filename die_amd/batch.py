@@ -1183,9 +1183,11 @@ class BatchedNeuralAutomataAgent(_Population):
         return p
 
     def _grad_struct(self, parameters: torch.Tensor, sense_epoch: int):
-        """(layer array, die_nca_batch) reading `parameters`, without the step's scratch."""
+        """(layer array, die_nca_batch) reading `parameters`, without the step's scratch (a wide stack's layers carry their
+        activation, 0 for a narrow one's)."""
         base = parameters.data_ptr()
-        layers = (_lib.NcaLayer * len(self._layers))(*[_lib.NcaLayer(k, cin, cout, 0, base + 4 * off, self.P) for k, cin, cout, off in self._layers])
+        layers = (_lib.NcaLayer * len(self._layers))(*[_lib.NcaLayer(k, cin, cout, act, base + 4 * off, self.P)
+                                                        for (k, cin, cout, off), act in zip(self._layers, self._acts)])
         nca = _lib.NcaBatch(len(self._layers), _lib.PAD_MODES[self._arch['boundary'][0]], int(self._arch['with_agent_channel']), sense_epoch,
                             layers, (C.c_float * 3)(*self.template.action_coefs), 0 if self.episodes == 1 else self.episodes, None, 0)
         return layers, nca
@@ -1203,8 +1205,8 @@ class BatchedNeuralAutomataAgent(_Population):
         p > 0, replica r is masked with key `dropout_seed + r·dropout_seed_stride` at `dropout_step`; the counter advances once per
         call whenever a `dropout_seed` is set.  Small worlds, 'circular' / 'zeros' boundaries; anything else raises
         NotImplementedError before any launch.  `step()` is untouched by all this.  A population of wide stacks
-        (`hidden_channels` / `hidden_activation`) has no adjoint kernels: NotImplementedError too, before any launch and before
-        `dropout_step` moves."""
+        (`hidden_channels` / `hidden_activation`) is refused here: NotImplementedError too, before any launch and before
+        `dropout_step` moves.  Its gradients come from `forward_device` and `die_amd.functional.gather_scale_batch`."""
         p = self._check_differentiable(parameters)
         out = _BatchedSense.apply(self, p, self.env.chem_node)
         if self.dropout_seed is not None:
@@ -1220,6 +1222,41 @@ class BatchedNeuralAutomataAgent(_Population):
         otherwise (alive agents never share a cell) the gradient's bits are fixed."""
         sense = self.differentiable_sense(parameters)
         return _BatchedReadOut.apply(sense, self)
+
+    def forward_device(self, parameters: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """A population of wide stacks on the device, differentiable — the wide twin of `differentiable_sense`, and the batched
+        twin of `ConvolutionModel.forward_device`: (R, 3, W, H) float32 with a `grad_fn`, `out[r]` bit for bit what the coming
+        `env.step` would sense on replica r and what `replica_agent(r).model.forward_device` returns on its planes.
+        `parameters`: the (C, P) float32 device matrix to read and to differentiate with respect to — default `self.parameters`;
+        its gradient is a (C, P) tensor, row c the float64 sum over candidate c's E worlds rounded once (E = 1: the stand-alone
+        gradient of replica c, bit for bit; no float atomics, the same bits on every run).
+
+        L launches of the wide layer kernel forward for all R replicas (L + 1 with a dropout mask) and 3 L − 1 backward
+        (die_nca_wide_backward_batch: both adjoint GEMMs on the fp32 matrix instruction with the replica in blockIdx.z, and the
+        fold), 3 L when the env carries a chem node that needs a gradient (`benv.differentiable_step`): the chem channel's planes
+        of the first layer's input gradient then go to that node.  Every layer's output lives in storage the graph owns and the
+        first layer's inputs are copied, so `backward` may run after `env.step`.  With a `dropout_seed`, in training mode and
+        p > 0, replica r is masked with key `dropout_seed + r·dropout_seed_stride` at `dropout_step`; the counter advances once per
+        call whenever a `dropout_seed` is set.  Refused before any launch and before `dropout_step` moves: a narrow population
+        (ValueError: it has `differentiable_sense`), large worlds (`per_replica`) and 'reflect' / 'replicate' boundaries
+        (NotImplementedError)."""
+        if not self._wide:
+            raise ValueError('forward_device: a narrow population (hidden_channels and hidden_activation both None) is differentiated '
+                             'by differentiable_sense')
+        env = self.env
+        if env.per_replica:
+            raise NotImplementedError('forward_device: large worlds (per_replica) are not batched — a large world fills the GPU '
+                                      'through the stand-alone ConvolutionModel.forward_device (replica_agent(r).model)')
+        if self._arch['boundary'][0] not in ('circular', 'zeros'):
+            raise NotImplementedError(f"boundary={self._arch['boundary'][0]!r} in forward_device: 'circular' or 'zeros' (step() "
+                                      f"takes all of {sorted(_lib.PAD_MODES)})")
+        self._check_step(env)
+        p = self.parameters if parameters is None else parameters
+        self._check_parameters(p)
+        out = _BatchedWideSense.apply(self, p, env.chem_node)
+        if self.dropout_seed is not None:
+            self.dropout_step += 1
+        return out
 
     def render(self, r: int) -> np.ndarray:
         """Replica r's last sense planes with the channel axis last: the stand-alone agent's `render()[0]`."""
@@ -1324,6 +1361,58 @@ class _BatchedSense(torch.autograd.Function):
         grad_in = torch.empty((R, cin, W, H), dtype=torch.float32, device=dev)
         _lib.check(_lib.lib.die_nca_backward_batch_inputs(*args, _ptr(grad_in), cin * W * H, stream_ptr(dev)), 'die_nca_backward_batch_inputs')
         return None, out, grad_in[:, cin - 1]
+
+
+class _BatchedWideSense(torch.autograd.Function):
+    """BatchedNeuralAutomataAgent.forward_device: die_nca_wide_sense_batch_store forward, die_nca_wide_backward_batch backward — with
+    the env's chem node as an input that needs a gradient, the call is given `grad_in`, whose chem channel is the node's gradient."""
+
+    @staticmethod
+    def forward(ctx, pop, parameters, chem_node=None):
+        env = pop.env
+        R, W, H, L, dev, Cm = env.R, env.W, env.H, len(pop._layers), env.device, pop._channels
+        with_agents = pop._arch['with_agent_channel']
+        # as they are now: the worlds will be stepped (the claim plane only where the first layer reads it)
+        planes = [env.food.clone(), env.chem.clone()] + ([env.owner.clone()] if with_agents else [])
+        store = torch.empty((L, R, Cm, W, H), dtype=torch.float32, device=dev)
+        drop = pop._dropout()
+        masked = None if drop is None else torch.empty((R, Cm, W, H), dtype=torch.float32, device=dev)
+        ctx.epoch, ctx.fdt = env.epoch, _lib.DIE_F32 if env.dtype == torch.float32 else _lib.DIE_F16
+        ctx.batch, ctx.pop, ctx.size = env._batch_struct(), pop, (R, W, H, L)
+        ctx.drop = None if drop is None else (drop.p, drop.seed, drop.seed_stride, drop.step)
+        m = _BatchedSense._medium(ctx, planes)
+        layers, nca = pop._grad_struct(parameters, ctx.epoch)
+        _lib.check(_lib.lib.die_nca_wide_sense_batch_store(C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), store.numel() * 4,
+                                                           None if masked is None else _ptr(masked),
+                                                           None if drop is None else C.byref(drop), stream_ptr(dev)),
+                   'die_nca_wide_sense_batch_store')
+        # everything the backward reads goes through save_for_backward: freed with the graph after a backward without retain_graph
+        ctx.save_for_backward(parameters, store, *planes)
+        return (store[L - 1] if masked is None else masked)[:, :3]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        parameters, store, *planes = ctx.saved_tensors
+        R, W, H, L = ctx.size
+        pop, dev = ctx.pop, store.device
+        g = grad.to(dtype=torch.float32).contiguous()               # (R, 3, W, H): three planes per replica
+        m = _BatchedSense._medium(ctx, planes)
+        layers, nca = pop._grad_struct(parameters, ctx.epoch)
+        need = int(_lib.lib.die_nca_wide_backward_batch_workspace_bytes(W, H, R, C.byref(nca)))
+        if need < 0:
+            raise ValueError('a stack or shape die_nca_wide_backward_batch does not take')
+        ws = torch.empty((need // 4,), dtype=torch.float32, device=dev)
+        out = torch.empty_like(parameters)                          # (C, P): every element is written (the layers tile a row)
+        drop = None if ctx.drop is None else _lib.NcaDropout(*ctx.drop, 0)
+        # the first layer's inputs are ([agents,] food, chem): food and the claims are constants of the parameters, chem is the node;
+        # without a node that needs a gradient the first layer's input-gradient kernel is not launched
+        cin = len(planes)
+        grad_in = torch.empty((R, cin, W, H), dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
+        _lib.check(_lib.lib.die_nca_wide_backward_batch(C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), _ptr(g), 3 * W * H,
+                                                        _ptr(out), pop.P, None if drop is None else C.byref(drop), _ptr(ws), need,
+                                                        _ptr(grad_in), cin * W * H, stream_ptr(dev)), 'die_nca_wide_backward_batch')
+        return None, out, None if grad_in is None else grad_in[:, cin - 1]
 
 
 class _BatchedReadOut(torch.autograd.Function):

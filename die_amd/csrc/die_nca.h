@@ -39,6 +39,11 @@ int die_dropout_words(const die_nca_dropout* drop, DropWords* out, const char* w
 // of the batched read-out, sensing and adjoint: checked before anything is launched (die_nca.hip)
 int die_nca_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who);
 int die_nca_batch_shape_check(const die_medium* m, const die_batch* b, const char* who);
+// the same for a wide stack (die_nca_wide.hip: 1..32 channels, k in 1, 3, 5, an activation per layer in die_nca_layer.reserved)
+int die_nca_wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who);
 
 // k_conv_backward_sum on `tiles` partial rows of nw weights (die_nca_grad.hip), for the wide adjoint's rows as well
 void die_conv_backward_fold(const float* part, int64_t tiles, int nw, float* out, hipStream_t s);
+// k_conv_backward_sum_batch: candidate c's `rows` consecutive partial rows (its E replicas' tiles, [candidate][rows][nw]) in ascending
+// order, float64, into out + c * out_stride — for the wide stack's batched adjoint
+void die_conv_backward_fold_batch(const float* part, int64_t rows, int nw, int candidates, float* out, int64_t out_stride, hipStream_t s);

@@ -208,6 +208,11 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_backward_sum_batch(const flo
     if (j < nw) conv_backward_sum_one(part + (int64_t)blockIdx.y * rows * nw, rows, nw, j, out + (int64_t)blockIdx.y * out_stride);
 }
 
+// the same launch for die_nca_wide_backward_batch's partial rows (die_nca_wide_grad.hip): candidate c's `rows` rows into out + c * out_stride
+void die_conv_backward_fold_batch(const float* part, int64_t rows, int nw, int candidates, float* out, int64_t out_stride, hipStream_t s) {
+    k_conv_backward_sum_batch<<<dim3((unsigned)die_grid_for(nw), (unsigned)candidates), DIE_BLOCK, 0, s>>>(part, rows, nw, out, out_stride);
+}
+
 static bool conv_shape_ok(int32_t W, int32_t H, int32_t cin, int32_t cout, int32_t k) {
     return W >= 1 && H >= 1 && cin >= 1 && cin <= NCA_MAXC && cout >= 1 && cout <= NCA_MAXC && (k == 1 || k == 3 || k == 5 || k == 7);
 }

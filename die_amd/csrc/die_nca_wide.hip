@@ -270,8 +270,10 @@ static int wide_max_channels(const die_nca_batch* nca) {
 }
 
 // every argument of the stack, before anything is launched
-int die_nca_wide_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who) {
-    DIE_REQUIRE(nca && nca->layers && nca->scratch, "%s: null stack, layer list or scratch", who);
+// (scratch: the ping-pong planes of the step; the calls that keep every layer in caller-owned storage check their own)
+static int wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool scratch) {
+    if (scratch) DIE_REQUIRE(nca && nca->layers && nca->scratch, "%s: null stack, layer list or scratch", who);
+    else DIE_REQUIRE(nca && nca->layers, "%s: null stack or layer list", who);
     DIE_REQUIRE(nca->n_layers >= 1 && nca->n_layers <= DIE_NCA_MAX_LAYERS, "%s: 1..%d layers (got %d)", who, DIE_NCA_MAX_LAYERS, nca->n_layers);
     DIE_REQUIRE(nca->padding_mode >= DIE_PAD_CIRCULAR && nca->padding_mode <= DIE_PAD_REPLICATE, "%s: bad padding mode %d", who, nca->padding_mode);
     DIE_REQUIRE(nca->with_agent_channel == 0 || nca->with_agent_channel == 1, "%s: with_agent_channel is 0 or 1", who);
@@ -296,15 +298,26 @@ int die_nca_wide_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int
         cin = L.cout;
     }
     DIE_REQUIRE(cin == 3, "%s: the last layer gives %d planes (dx, dy, deposit: 3)", who, cin);
+    if (!scratch) return DIE_OK;
     const int64_t need = die_nca_wide_batch_scratch_bytes(W, H, replicas, nca->n_layers, wide_max_channels(nca));
     DIE_REQUIRE(nca->scratch_bytes >= need, "%s: scratch too small (%lld < %lld)", who, (long long)nca->scratch_bytes, (long long)need);
     return DIE_OK;
 }
 
-// the stack for every replica, one launch per layer; *sense = the last layer's planes of replica 0, replica r's *rep further
-// (what die_nca_sense_batch returns for a narrow stack: k_nca_move_claim_batch reads either)
-int die_nca_wide_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
-                             const DropWords* drop, void* stream) {
+int die_nca_wide_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who) {
+    return wide_stack_check(nca, W, H, replicas, who, true);
+}
+int die_nca_wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who) {
+    return wide_stack_check(nca, W, H, replicas, who, false);
+}
+
+// the stack for every replica, one launch per layer.  Layer l writes `dst` + set(l) * R * rep planes: set(l) = l % 2 for the
+// step's ping-pong scratch, l for caller-owned storage that keeps every layer.  `drop` (checked words, or null): the last layer's
+// launch is the masked one — into `masked` when given (the unmasked launch then runs as well and keeps its place), else in place
+// of it.  *sense = the last layer's planes of replica 0, replica r's *rep further (what die_nca_sense_batch returns for a narrow
+// stack: k_nca_move_claim_batch reads either)
+static int wide_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* dst, bool pingpong, float* masked,
+                            const float** sense, int64_t* rep, const DropWords* drop, void* stream) {
     const int64_t cells = (int64_t)m->W * m->H, rep_scratch = wide_max_channels(nca) * cells;
     const int fkind = m->dtype == DIE_F32 ? DIE_PLANE_F32 : DIE_PLANE_F16;
     WideArgs a = {};
@@ -319,18 +332,61 @@ int die_nca_wide_sense_batch(const die_medium* m, const die_batch* b, const die_
     for (int l = 0; l < nca->n_layers; ++l) {
         const die_nca_layer& L = nca->layers[l];
         const bool last = l == nca->n_layers - 1;
-        a.out = nca->scratch + (l % wide_sets(nca->n_layers)) * b->replicas * rep_scratch;
+        a.out = dst + (pingpong ? l % wide_sets(nca->n_layers) : l) * b->replicas * rep_scratch;
         a.w = L.weights; a.rep_w = L.weight_stride;
         a.cin = L.cin; a.cout = L.cout; a.act = L.reserved;
         a.vec = wide_vec(a.out, a.out_stride, a.rep_out, a.H);
-        a.drop = last && drop;
-        if (a.drop) a.d = *drop;
+        a.drop = last && drop && !masked;
+        if (last && drop) a.d = *drop;
         launch_wide(a, L.k, b->replicas, (hipStream_t)stream);
         DIE_CHECK_LAUNCH("die_nca_wide_env_step_batch(conv)");
+        if (last && drop && masked) {
+            a.out = masked;
+            a.vec = wide_vec(a.out, a.out_stride, a.rep_out, a.H);
+            a.drop = 1;
+            launch_wide(a, L.k, b->replicas, (hipStream_t)stream);
+            DIE_CHECK_LAUNCH("die_nca_wide_sense_batch_store(masked)");
+        }
         for (int o = 0; o < L.cout; ++o) { a.in[o] = a.out + o * cells; a.kind[o] = DIE_PLANE_F32; }
         a.rep_in = rep_scratch;
     }
     *sense = a.out;
     *rep = rep_scratch;
     return DIE_OK;
+}
+
+int die_nca_wide_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
+                             const DropWords* drop, void* stream) {
+    return wide_sense_batch(m, b, nca, nca->scratch, true, nullptr, sense, rep, drop, stream);
+}
+
+// ---- the same launches into storage that keeps every layer (the forward of die_nca_wide_backward_batch) -----------------
+extern "C" int64_t die_nca_wide_sense_batch_store_bytes(int32_t W, int32_t H, int32_t replicas, int32_t n_layers, int32_t max_channels) {
+    if (W < 1 || H < 1 || replicas < 1 || replicas > DIE_MAX_REPLICAS || n_layers < 1 || n_layers > DIE_NCA_MAX_LAYERS ||
+        max_channels < 1 || max_channels > NCAW_MAXC || (W + NCA_TX - 1) / NCA_TX > 65535) return -1;
+    return (int64_t)n_layers * replicas * max_channels * (int64_t)W * H * (int64_t)sizeof(float);
+}
+
+extern "C" int die_nca_wide_sense_batch_store(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* store,
+                                              int64_t store_bytes, float* masked, const die_nca_dropout* drop, void* stream) {
+    const char* who = "die_nca_wide_sense_batch_store";
+    DIE_REQUIRE(m && b && nca && store, "%s: null argument", who);
+    int rc = die_nca_batch_shape_check(m, b, who);
+    if (rc != DIE_OK) return rc;
+    rc = wide_stack_check(nca, m->W, m->H, b->replicas, who, false);
+    if (rc != DIE_OK) return rc;
+    DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad field dtype %d", who, m->dtype);
+    DIE_REQUIRE(m->food && m->chem && (m->owner || !nca->with_agent_channel), "%s: null plane", who);
+    DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX, "%s: sense_epoch %d", who, nca->sense_epoch);
+    const int64_t need = die_nca_wide_sense_batch_store_bytes(m->W, m->H, b->replicas, nca->n_layers, wide_max_channels(nca));
+    DIE_REQUIRE(store_bytes >= need, "%s: store too small (%lld < %lld)", who, (long long)store_bytes, (long long)need);
+    DropWords dw;
+    if (drop) {
+        DIE_REQUIRE(masked && masked != store, "%s: a dropout mask needs planes of its own for the masked values", who);
+        rc = die_dropout_words(drop, &dw, who);
+        if (rc != DIE_OK) return rc;
+    }
+    const float* sense;
+    int64_t rep;
+    return wide_sense_batch(m, b, nca, store, false, drop ? masked : nullptr, &sense, &rep, drop ? &dw : nullptr, stream);
 }

@@ -28,12 +28,20 @@
 //                       and written exactly once, by one lane.  NO float atomics.
 //   the fold            die_nca_grad.hip's k_conv_backward_sum: one thread per weight adds the partial rows in tile-index order
 //                       in float64 and stores fp32.  Fixed order, fixed tree: the same inputs give the same bits on every run.
+//   die_nca_wide_backward_batch   the same for every replica of a die_batch (a population's candidates), a whole stack per call:
+//                       both kernels with BATCH on and the replica in blockIdx.z — its planes, weight block r / E, mask key
+//                       seed + r * seed_stride, partial rows (r * tiles + tile) and input gradient, the offsets scalars added to
+//                       the pointers once — then k_conv_backward_sum_batch folding a candidate's E * tiles rows in ascending
+//                       order.  One arithmetic body: for E = 1 replica r is die_conv2d_wide_backward on its world, bit for bit.
+//                       The stand-alone instantiations (BATCH off) keep WideBwdArgs as their whole argument and the registers,
+//                       LDS and occupancy they had.
 //
 // Roofline.  Both GEMMs are 2 C^2 k^2 flop per cell, the forward's count, against 12 C bytes (g, t and the inputs in; the input
 // gradient out): a C -> C layer with C >= 16 at k >= 3 is compute-bound on the fp32 matrix rate (157 TFLOP/s, 64 flop per clock
 // per SIMD) in either kernel.  The layers touching 3 channels stay HBM-bound and pay for the padding to 4 (a chunk) and 16 (a
 // block): 3 -> 16's weight gradient issues 16 / 3 of the MFMAs its 3 input channels need.
 #include <math.h>
+#include <type_traits>
 #include "die_common.h"
 #include "die_rng.h"
 #include "die_nca.h"
@@ -55,6 +63,16 @@ struct WideBwdArgs {
     int drop;                    // 1: g_z carries the dropout mask of `d`
     DropWords d;
 };
+// what a BATCH launch reads on top (die_nca_wide_backward_batch; the stand-alone instantiations keep WideBwdArgs as their whole
+// argument): elements from replica r's planes / gradients / outputs / weights / input gradients / partial rows to replica r + 1's
+struct WideBwdBatchArgs : WideBwdArgs {
+    int64_t rep_in, rep_g, rep_t, rep_w, rep_gin, rep_part;
+    int episodes;                // replica r reads weight block r / episodes (1: a block per replica)
+};
+template <bool BATCH> using WideBwdArgsOf = typename std::conditional<BATCH, WideBwdBatchArgs, WideBwdArgs>::type;
+
+// bytes per cell of a first-layer plane (die_conv_plane.kind): a replica's offset into it, in bytes
+__device__ __forceinline__ int64_t ncaw_plane_bytes(int kind) { return kind == DIE_PLANE_F32 ? 4 : kind == DIE_PLANE_F16 ? 2 : 8; }
 
 // g_z of one cell and channel: the gradient at the returned value through the mask and the activation
 __device__ __forceinline__ float ncaw_gz(float g, float t, float mask, int act, int drop) {
@@ -66,8 +84,11 @@ __device__ __forceinline__ float ncaw_gz(float g, float t, float mask, int act, 
 }
 
 // ---- input gradient: k_conv_wide over the g_z planes with the flipped, transposed weight ---------------------------------
-template <int K, int NB>
-__global__ __launch_bounds__(DIE_BLOCK) void k_conv_wide_gin(WideBwdArgs a) {
+// BATCH (both kernels): replica blockIdx.z of die_nca_wide_backward_batch — its planes, its candidate's weights, its mask key
+// (seed + z * seed_stride), its partial rows and its input gradient.  The offsets are scalars, added to the pointers once at the
+// kernel's entry; with BATCH off every pointer below IS the argument's, so those instantiations compile to the code they always were.
+template <int K, int NB, bool BATCH = false>
+__global__ __launch_bounds__(DIE_BLOCK) void k_conv_wide_gin(WideBwdArgsOf<BATCH> a) {
     constexpr int R = K / 2, LX = NCA_TX + 2 * R, LY = NCA_TY + 2 * R;
     constexpr int CS = (LX * LY - 16 + 63) / 64 * 64 + 16;         // channel stride: 16 mod 64 words
     constexpr int MB = 16;                                          // M-blocks per wave: 4 rows x 4 blocks of 16 y
@@ -76,6 +97,12 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_wide_gin(WideBwdArgs a) {
     const int x0 = blockIdx.y * NCA_TX, y0 = blockIdx.x * NCA_TY;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lk = lane >> 4, ln = lane & 15;
     const bool has_t = a.act != DIE_NCA_ACT_NONE;
+    uint64_t key = a.d.seed;
+    [[maybe_unused]] int wrow = 0;                                  // the replica's weight block
+    if constexpr (BATCH) {
+        wrow = (int)blockIdx.z / a.episodes;
+        key += (uint64_t)blockIdx.z * a.d.seed_stride;
+    }
 
     ncaw_f32x4 acc[MB][NB];
 #pragma unroll
@@ -99,7 +126,7 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_wide_gin(WideBwdArgs a) {
         const bool ok = i < LX * LY && gx >= 0 && gy >= 0;
         cell[t] = ok ? (int64_t)gx * a.H + gy : 0;
         live |= ok ? 1u << t : 0u;
-        mask[t] = a.drop ? die_dropout_factor(die_dropout_word(a.d.seed, a.d.step, (uint64_t)cell[t]), a.d.thr, a.d.keep) : 1.f;
+        mask[t] = a.drop ? die_dropout_factor(die_dropout_word(key, a.d.step, (uint64_t)cell[t]), a.d.thr, a.d.keep) : 1.f;
     }
     // s_w[a][b][nb][c][i]: the word of output (input channel of the layer) i = nb * 16 + (word & 15), chunk channel c (an output
     // channel of the layer), tap (a, b) is w[c][i][k-1-a][k-1-b]
@@ -112,20 +139,26 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_wide_gin(WideBwdArgs a) {
     }
     float pre[NI][NCAW_CH], pret[NI][NCAW_CH], wpre[NWI];
     auto fetch = [&](int c0) {
+        // the replica's bases: scalars from the arguments, worked out per chunk (a handful of scalar operations) so that no
+        // pointer pair stays live over the MFMAs
+        const float *gbase = a.g, *tbase = a.t, *w = a.w;
+        if constexpr (BATCH) {
+            gbase += (int64_t)blockIdx.z * a.rep_g; tbase += (int64_t)blockIdx.z * a.rep_t; w += (int64_t)wrow * a.rep_w;
+        }
 #pragma unroll
         for (int t = 0; t < NWI; ++t) {
             const int c = c0 + (((threadIdx.x + t * DIE_BLOCK) >> 4) & 3);
-            wpre[t] = a.w[c < a.cout ? wbase[t] + c0 * a.cin * (K * K) : 0];
+            wpre[t] = w[c < a.cout ? wbase[t] + c0 * a.cin * (K * K) : 0];
         }
 #pragma unroll
         for (int j = 0; j < NCAW_CH; ++j) {
             const int c = c0 + j;                                   // (uniform)
             if (c >= a.cout) continue;
-            const float* gp = a.g + (int64_t)c * a.g_stride;
+            const float* gp = gbase + (int64_t)c * a.g_stride;
 #pragma unroll
             for (int t = 0; t < NI; ++t) pre[t][j] = gp[cell[t]];
             if (has_t) {
-                const float* tp = a.t + (int64_t)c * a.t_stride;
+                const float* tp = tbase + (int64_t)c * a.t_stride;
 #pragma unroll
                 for (int t = 0; t < NI; ++t) pret[t][j] = tp[cell[t]];
             }
@@ -172,6 +205,8 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_wide_gin(WideBwdArgs a) {
         }
     }
 
+    float* ginbase = a.gin;                                         // (worked out here: not live over the chunks)
+    if constexpr (BATCH) ginbase += (int64_t)blockIdx.z * a.rep_gin;
 #pragma unroll
     for (int m = 0; m < MB; ++m) {
         const int gx = x0 + wave * 4 + (m >> 2), gy = y0 + (m & 3) * 16 + lk * 4;      // this lane's 4 cells: (gx, gy .. gy + 3)
@@ -180,7 +215,7 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_wide_gin(WideBwdArgs a) {
         for (int nb = 0; nb < NB; ++nb) {
             const int i = nb * 16 + ln;
             if (i >= a.cin) continue;
-            float* dst = a.gin + (int64_t)i * a.gin_stride + (int64_t)gx * a.H + gy;
+            float* dst = ginbase + (int64_t)i * a.gin_stride + (int64_t)gx * a.H + gy;
             if (a.vec) *(float4*)dst = make_float4(acc[m][nb][0], acc[m][nb][1], acc[m][nb][2], acc[m][nb][3]);
             else {
 #pragma unroll
@@ -201,8 +236,8 @@ constexpr int ncaw_gw_strip() {
     return 1;
 }
 
-template <int K, int GO, int GI>
-__global__ __launch_bounds__(DIE_BLOCK) void k_conv_wide_gw(WideBwdArgs a) {
+template <int K, int GO, int GI, bool BATCH = false>
+__global__ __launch_bounds__(DIE_BLOCK) void k_conv_wide_gw(WideBwdArgsOf<BATCH> a) {
     constexpr int R = K / 2, SR = ncaw_gw_strip<K, GO, GI>(), LY = NCA_TY + 2 * R, XR = SR + 2 * R;
     constexpr int NT = (K * K + 3) / 4;                             // taps per wave: wave, wave + 4, ...
     constexpr int GCELLS = SR * NCA_TY, XCELLS = XR * LY;
@@ -214,6 +249,15 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_wide_gw(WideBwdArgs a) {
     const int x0 = blockIdx.y * NCA_TX, y0 = blockIdx.x * NCA_TY;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lk = lane >> 4, ln = lane & 15;
     const bool has_t = a.act != DIE_NCA_ACT_NONE;
+    const float *gbase = a.g, *tbase = a.t;
+    uint64_t key = a.d.seed;
+    [[maybe_unused]] int64_t o_in = 0;                              // replica z's offset into an input plane, in cells
+    if constexpr (BATCH) {
+        const int64_t z = (int64_t)blockIdx.z;
+        gbase += z * a.rep_g; tbase += z * a.rep_t;
+        o_in = z * a.rep_in;
+        key += (uint64_t)blockIdx.z * a.d.seed_stride;
+    }
 
     ncaw_f32x4 acc[NT][GO][GI];
     int toff[NT];                                                   // tap (ta, tb)'s offset in s_x, in cells
@@ -232,7 +276,7 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_wide_gw(WideBwdArgs a) {
         for (int n = 0; n < NCA_TX * NCA_TY / DIE_BLOCK; ++n) {
             const int i = threadIdx.x + n * DIE_BLOCK, gx = x0 + i / NCA_TY, gy = y0 + i % NCA_TY;
             const uint64_t cell = gx < a.W && gy < a.H ? (uint64_t)gx * (uint64_t)a.H + (uint64_t)gy : 0;
-            s_m[i] = die_dropout_factor(die_dropout_word(a.d.seed, a.d.step, cell), a.d.thr, a.d.keep);
+            s_m[i] = die_dropout_factor(die_dropout_word(key, a.d.step, cell), a.d.thr, a.d.keep);
         }
         __syncthreads();
     }
@@ -255,8 +299,8 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_wide_gw(WideBwdArgs a) {
                     const int o = 4 * q + e;
                     v[e] = 0.f;
                     if (o < a.cout && ok) {
-                        const float g = a.g[(int64_t)o * a.g_stride + cell];
-                        const float t = has_t ? a.t[(int64_t)o * a.t_stride + cell] : 0.f;
+                        const float g = gbase[(int64_t)o * a.g_stride + cell];
+                        const float t = has_t ? tbase[(int64_t)o * a.t_stride + cell] : 0.f;
                         v[e] = ncaw_gz(g, t, m, a.act, a.drop);
                     }
                 }
@@ -281,6 +325,7 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_wide_gw(WideBwdArgs a) {
                     if (c < a.cin) {
                         const void* p = a.in[c];
                         const int kind = a.kind[c];
+                        if constexpr (BATCH) p = (const char*)p + o_in * ncaw_plane_bytes(kind);      // (scalar: once per plane)
                         if (ok) v[e] = nca_load(p, kind, cell, a.epoch);
                     }
                 }
@@ -312,7 +357,9 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_wide_gw(WideBwdArgs a) {
 
     // accumulator block (og, ig) of tap (ta, tb): column lane & 15 = input channel, rows 4 (lane >> 4) + q = output channel
     const int nw = a.cout * a.cin * K * K;
-    float* prow = a.part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * nw;
+    float* part = a.part;                                           // (worked out here: not live over the strips)
+    if constexpr (BATCH) part += (int64_t)blockIdx.z * a.rep_part;
+    float* prow = part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * nw;
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
         const int tap = wave + 4 * j;
@@ -332,17 +379,18 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_conv_wide_gw(WideBwdArgs a) {
     }
 }
 
-template <int K>
-static void launch_wide_backward(const WideBwdArgs& a, bool want_gin, hipStream_t s) {
-    dim3 grid((a.H + NCA_TY - 1) / NCA_TY, (a.W + NCA_TX - 1) / NCA_TX);
+// the two launches of one layer: gridDim.z = replicas for BATCH, 1 (and WideBwdArgs alone) otherwise
+template <int K, bool BATCH>
+static void launch_wide_backward(const WideBwdArgsOf<BATCH>& a, bool want_gin, int replicas, hipStream_t s) {
+    dim3 grid((a.H + NCA_TY - 1) / NCA_TY, (a.W + NCA_TX - 1) / NCA_TX, replicas);
     const bool go2 = a.cout > 16, gi2 = a.cin > 16;
-    if (go2 && gi2) k_conv_wide_gw<K, 2, 2><<<grid, DIE_BLOCK, 0, s>>>(a);
-    else if (go2) k_conv_wide_gw<K, 2, 1><<<grid, DIE_BLOCK, 0, s>>>(a);
-    else if (gi2) k_conv_wide_gw<K, 1, 2><<<grid, DIE_BLOCK, 0, s>>>(a);
-    else k_conv_wide_gw<K, 1, 1><<<grid, DIE_BLOCK, 0, s>>>(a);
+    if (go2 && gi2) k_conv_wide_gw<K, 2, 2, BATCH><<<grid, DIE_BLOCK, 0, s>>>(a);
+    else if (go2) k_conv_wide_gw<K, 2, 1, BATCH><<<grid, DIE_BLOCK, 0, s>>>(a);
+    else if (gi2) k_conv_wide_gw<K, 1, 2, BATCH><<<grid, DIE_BLOCK, 0, s>>>(a);
+    else k_conv_wide_gw<K, 1, 1, BATCH><<<grid, DIE_BLOCK, 0, s>>>(a);
     if (!want_gin) return;
-    if (gi2) k_conv_wide_gin<K, 2><<<grid, DIE_BLOCK, 0, s>>>(a);
-    else k_conv_wide_gin<K, 1><<<grid, DIE_BLOCK, 0, s>>>(a);
+    if (gi2) k_conv_wide_gin<K, 2, BATCH><<<grid, DIE_BLOCK, 0, s>>>(a);
+    else k_conv_wide_gin<K, 1, BATCH><<<grid, DIE_BLOCK, 0, s>>>(a);
 }
 
 static bool wide_shape_ok(int32_t W, int32_t H, int32_t cin, int32_t cout, int32_t k) {
@@ -413,12 +461,162 @@ extern "C" int die_conv2d_wide_backward(int32_t W, int32_t H, int32_t cin, const
     a.vec = H % 4 == 0;
     hipStream_t s = (hipStream_t)stream;
     switch (k) {
-        case 1: launch_wide_backward<1>(a, grad_in != nullptr, s); break;
-        case 3: launch_wide_backward<3>(a, grad_in != nullptr, s); break;
-        default: launch_wide_backward<5>(a, grad_in != nullptr, s); break;
+        case 1: launch_wide_backward<1, false>(a, grad_in != nullptr, 1, s); break;
+        case 3: launch_wide_backward<3, false>(a, grad_in != nullptr, 1, s); break;
+        default: launch_wide_backward<5, false>(a, grad_in != nullptr, 1, s); break;
     }
     DIE_CHECK_LAUNCH(who);
     die_conv_backward_fold((const float*)workspace, wide_tiles(W, H), (int)nw, grad_weights, s);
     DIE_CHECK_LAUNCH("die_conv2d_wide_backward(sum)");
+    return DIE_OK;
+}
+
+// ---- the wide stack's adjoint for every replica of a batch ---------------------------------------------------------------
+// Workspace: min(layers - 1, 2) sets of [replica][Cmax][W][H] planes for the gradient travelling down the stack (ping-pong), Cmax
+// the widest cout: the store's plane count — first, so that their 16-byte stores stay aligned whatever the rows' length — then
+// [replica][tile][the largest cout * cin * k * k of the stack] partial rows (a layer uses [replica][tile][its own nw] of it).
+static int wide_bwd_max_channels(const die_nca_batch* nca) {
+    int mc = 1;
+    for (int l = 0; l < nca->n_layers; ++l) mc = nca->layers[l].cout > mc ? nca->layers[l].cout : mc;
+    return mc;
+}
+static int64_t wide_bwd_max_weights(const die_nca_batch* nca) {
+    int64_t mw = 0;
+    for (int l = 0; l < nca->n_layers; ++l) {
+        const die_nca_layer& L = nca->layers[l];
+        const int64_t nw = (int64_t)L.cout * L.cin * L.k * L.k;
+        mw = nw > mw ? nw : mw;
+    }
+    return mw;
+}
+static int wide_bwd_gin_sets(int32_t n_layers) { return n_layers - 1 < 2 ? n_layers - 1 : 2; }
+
+// the shapes the byte query answers for (the call itself checks everything again, with messages)
+static bool wide_bwd_stack_ok(int32_t W, int32_t H, int32_t replicas, const die_nca_batch* nca) {
+    if (W < 1 || H < 1 || replicas < 1 || replicas > DIE_MAX_REPLICAS || (W + NCA_TX - 1) / NCA_TX > 65535) return false;
+    if (!nca || !nca->layers || nca->n_layers < 1 || nca->n_layers > DIE_NCA_MAX_LAYERS) return false;
+    if (nca->with_agent_channel != 0 && nca->with_agent_channel != 1) return false;
+    if (nca->padding_mode != DIE_PAD_CIRCULAR && nca->padding_mode != DIE_PAD_ZEROS) return false;
+    if (nca->episodes < 0 || replicas % (nca->episodes > 1 ? nca->episodes : 1) != 0) return false;
+    int cin = 2 + nca->with_agent_channel;
+    for (int l = 0; l < nca->n_layers; ++l) {
+        const die_nca_layer& L = nca->layers[l];
+        if (!wide_shape_ok(W, H, L.cin, L.cout, L.k) || L.cin != cin) return false;
+        if (L.reserved < DIE_NCA_ACT_NONE || L.reserved > DIE_NCA_ACT_RELU) return false;
+        if (l == nca->n_layers - 1 && L.reserved != DIE_NCA_ACT_TANH) return false;
+        cin = L.cout;
+    }
+    return cin == 3;
+}
+
+extern "C" int64_t die_nca_wide_backward_batch_workspace_bytes(int32_t W, int32_t H, int32_t replicas, const die_nca_batch* nca) {
+    if (!wide_bwd_stack_ok(W, H, replicas, nca)) return -1;
+    return ((int64_t)replicas * wide_tiles(W, H) * wide_bwd_max_weights(nca) +
+            (int64_t)wide_bwd_gin_sets(nca->n_layers) * replicas * wide_bwd_max_channels(nca) * (int64_t)W * H) * (int64_t)sizeof(float);
+}
+
+extern "C" int die_nca_wide_backward_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store,
+                                           const float* grad_sense, int64_t sense_stride, float* grad, int64_t grad_stride,
+                                           const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, float* grad_in,
+                                           int64_t grad_in_stride, void* stream) {
+    const char* who = "die_nca_wide_backward_batch";
+    DIE_REQUIRE(m && b && nca && store && grad_sense && grad && workspace, "%s: null argument", who);
+    int rc = die_nca_batch_shape_check(m, b, who);
+    if (rc != DIE_OK) return rc;
+    rc = die_nca_wide_stack_check(nca, m->W, m->H, b->replicas, who);
+    if (rc != DIE_OK) return rc;
+    if (nca->padding_mode == DIE_PAD_REFLECT || nca->padding_mode == DIE_PAD_REPLICATE) {
+        die_set_error("%s: the adjoint of 'reflect' / 'replicate' padding is not implemented ('circular' and 'zeros' are)", who);
+        return DIE_ERR_UNSUPPORTED;
+    }
+    DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad field dtype %d", who, m->dtype);
+    DIE_REQUIRE(m->food && m->chem && (m->owner || !nca->with_agent_channel), "%s: null plane", who);
+    DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX, "%s: sense_epoch %d", who, nca->sense_epoch);
+    const int Cmax = wide_bwd_max_channels(nca);
+    const int64_t cells = (int64_t)m->W * m->H, rep_planes = Cmax * cells;
+    DIE_REQUIRE(sense_stride >= 3 * cells, "%s: sense_stride %lld below three planes", who, (long long)sense_stride);
+    int64_t P = 0;
+    for (int l = 0; l < nca->n_layers; ++l) {
+        const die_nca_layer& L = nca->layers[l];
+        P += (int64_t)L.cout * L.cin * L.k * L.k;
+        DIE_REQUIRE(grad != L.weights, "%s: grad is layer %d's weights", who, l);
+    }
+    DIE_REQUIRE(grad_stride >= P, "%s: grad_stride %lld below a row of %lld weights", who, (long long)grad_stride, (long long)P);
+    const int64_t need = die_nca_wide_backward_batch_workspace_bytes(m->W, m->H, b->replicas, nca);
+    DIE_REQUIRE(need > 0, "%s: a shape the call does not take", who);
+    DIE_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%lld < %lld)", who, (long long)workspace_bytes, (long long)need);
+    // the input-gradient kernel stores four cells of a row at once where H % 4 == 0, into the workspace's planes too
+    DIE_REQUIRE(m->H % 4 != 0 || nca->n_layers < 2 || ((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned where H %% 4 == 0", who);
+    const int E = nca->episodes > 1 ? nca->episodes : 1, R = b->replicas, L = nca->n_layers;
+    if (grad_in) {
+        const int64_t in_planes = (int64_t)nca->layers[0].cin * cells;
+        DIE_REQUIRE(grad_in_stride >= in_planes, "%s: grad_in_stride %lld below the first layer's %d input planes", who,
+                    (long long)grad_in_stride, nca->layers[0].cin);
+        // the kernel stores four cells of a row at once where H % 4 == 0
+        DIE_REQUIRE(m->H % 4 != 0 || (((uintptr_t)grad_in & 15) == 0 && grad_in_stride % 4 == 0),
+                    "%s: grad_in must be 16-byte aligned and grad_in_stride a multiple of 4 where H %% 4 == 0", who);
+        const char* lo = (const char*)grad_in;
+        const char* hi = lo + ((int64_t)(R - 1) * grad_in_stride + in_planes) * (int64_t)sizeof(float);
+        auto overlaps = [&](const void* p, int64_t bytes) { return p && (const char*)p < hi && (const char*)p + bytes > lo; };
+        const int64_t fbytes = ((int64_t)(R - 1) * b->plane_stride + cells) * (m->dtype == DIE_F32 ? 4 : 2);
+        DIE_REQUIRE(!overlaps(store, (int64_t)L * R * rep_planes * 4) && !overlaps(grad_sense, ((int64_t)(R - 1) * sense_stride + 3 * cells) * 4) &&
+                        !overlaps(grad, ((int64_t)(R / E - 1) * grad_stride + P) * 4) && !overlaps(workspace, need) &&
+                        !overlaps(m->owner, ((int64_t)(R - 1) * b->plane_stride + cells) * 8) && !overlaps(m->food, fbytes) &&
+                        !overlaps(m->chem, fbytes),
+                    "%s: grad_in aliases another buffer of the call", who);
+        for (int l = 0; l < L; ++l) {
+            const die_nca_layer& Ly = nca->layers[l];
+            DIE_REQUIRE(!overlaps(Ly.weights, ((int64_t)(R / E - 1) * Ly.weight_stride + (int64_t)Ly.cout * Ly.cin * Ly.k * Ly.k) * 4),
+                        "%s: grad_in aliases layer %d's weights", who, l);
+        }
+    }
+    DropWords dw = {};
+    if (drop) {
+        rc = die_dropout_words(drop, &dw, who);
+        if (rc != DIE_OK) return rc;
+    }
+    const int64_t tiles = wide_tiles(m->W, m->H);
+    float* gin_sets = (float*)workspace;
+    float* part = gin_sets + (int64_t)wide_bwd_gin_sets(L) * R * rep_planes;
+    const int fkind = m->dtype == DIE_F32 ? DIE_PLANE_F32 : DIE_PLANE_F16;
+    hipStream_t s = (hipStream_t)stream;
+    int64_t off = P;
+    const float* g = grad_sense;
+    int64_t rep_g = sense_stride;
+    for (int l = L - 1; l >= 0; --l) {
+        const die_nca_layer& Ly = nca->layers[l];
+        const int nw = Ly.cout * Ly.cin * Ly.k * Ly.k;
+        off -= nw;
+        WideBwdBatchArgs a = {};
+        if (l == 0) {
+            int c = 0;
+            if (nca->with_agent_channel) { a.in[c] = m->owner; a.kind[c++] = DIE_PLANE_AGENTS; }
+            a.in[c] = m->food; a.kind[c++] = fkind;
+            a.in[c] = m->chem; a.kind[c++] = fkind;
+            a.rep_in = b->plane_stride;
+        } else {
+            for (int c = 0; c < Ly.cin; ++c) { a.in[c] = store + (int64_t)(l - 1) * R * rep_planes + c * cells; a.kind[c] = DIE_PLANE_F32; }
+            a.rep_in = rep_planes;
+        }
+        float* gin = l > 0 ? gin_sets + (int64_t)((L - 1 - l) % 2) * R * rep_planes : grad_in;
+        a.g = g; a.g_stride = cells; a.rep_g = rep_g;
+        a.t = store + (int64_t)l * R * rep_planes; a.t_stride = cells; a.rep_t = rep_planes;
+        a.w = Ly.weights; a.rep_w = Ly.weight_stride; a.episodes = E;
+        a.gin = gin; a.gin_stride = cells; a.rep_gin = l > 0 ? rep_planes : grad_in_stride;
+        a.part = part; a.rep_part = tiles * nw;
+        a.W = m->W; a.H = m->H; a.cin = Ly.cin; a.cout = Ly.cout; a.epoch = nca->sense_epoch; a.act = Ly.reserved; a.pad = nca->padding_mode;
+        a.vec = m->H % 4 == 0;
+        a.drop = drop != nullptr && l == L - 1;
+        a.d = dw;
+        switch (Ly.k) {
+            case 1: launch_wide_backward<1, true>(a, gin != nullptr, R, s); break;
+            case 3: launch_wide_backward<3, true>(a, gin != nullptr, R, s); break;
+            default: launch_wide_backward<5, true>(a, gin != nullptr, R, s); break;
+        }
+        DIE_CHECK_LAUNCH(who);
+        die_conv_backward_fold_batch(part, (int64_t)E * tiles, nw, R / E, grad + off, grad_stride, s);
+        DIE_CHECK_LAUNCH("die_nca_wide_backward_batch(sum)");
+        g = gin; rep_g = rep_planes;
+    }
     return DIE_OK;
 }

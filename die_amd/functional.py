@@ -6,7 +6,11 @@
     gather_scale(sense, obs, coefs)
         the per-agent read-out of a (3, W, H) sense tensor, NeuralAutomataAgent.differentiable_action's last step.
 
-`ConvolutionModel.forward_device` evaluates a whole wide stack through `conv2d_wide`.  There is no eager fallback: a shape the
+    gather_scale_batch(sense, population)
+        the same read-out for every replica of a BatchedNeuralAutomataAgent's worlds: (R, 3, W, H) -> (3, R, Nmax).
+
+`ConvolutionModel.forward_device` evaluates a whole wide stack through `conv2d_wide`; `BatchedNeuralAutomataAgent.forward_device`
+a population of them in one launch per layer (die_nca_wide_backward_batch backward).  There is no eager fallback: a shape the
 kernels do not take raises."""
 import ctypes as C
 from typing import Optional, Sequence, Tuple
@@ -118,3 +122,23 @@ def gather_scale(sense: th.Tensor, obs, coefs: Sequence[float]) -> th.Tensor:
     from .agent.evo import _DifferentiableReadOut
     agents, medium = obs
     return _DifferentiableReadOut.apply(sense, agents, medium, tuple(float(c) for c in coefs))
+
+
+def gather_scale_batch(sense: th.Tensor, population) -> th.Tensor:
+    """The read-out of an (R, 3, W, H) float32 `sense` tensor (`BatchedNeuralAutomataAgent.forward_device` or
+    `differentiable_sense`) at every agent slot of the population's worlds as they stand now: (3, R, Nmax) float32 in the batch's
+    action layout (what `env.step(..., action=...)` and `env.differentiable_step` take), action[c, r, n] = sense[r, c, cell of
+    replica r's slot n] * action_coefs[c] (die_gather_scale_batch); the padding slots from n[r] on are 0 and receive no gradient.
+    The backward scatters the slots' gradients onto their cells (die_gather_scale_backward_batch: fp32 atomics in arrival order
+    where several slots of a replica with a non-zero gradient share a cell — alive agents never do).  The slots' coordinates are
+    copied, so `backward` may run after the worlds have been stepped.  The node does not care what produced `sense`: narrow and
+    wide stacks alike."""
+    from .batch import BatchedNeuralAutomataAgent, _BatchedReadOut
+    if not isinstance(population, BatchedNeuralAutomataAgent):
+        raise TypeError('population: a BatchedNeuralAutomataAgent')
+    env = population.env
+    if env.per_replica:
+        raise NotImplementedError('gather_scale_batch: large worlds (per_replica) are not batched')
+    if not isinstance(sense, th.Tensor) or sense.dtype != th.float32 or not sense.is_cuda or tuple(sense.shape) != (env.R, 3, env.W, env.H):
+        raise ValueError(f'sense: a float32 CUDA tensor of shape {(env.R, 3, env.W, env.H)}')
+    return _BatchedReadOut.apply(sense, population)

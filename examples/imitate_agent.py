@@ -12,10 +12,12 @@ scale², and `loss.backward()` runs the adjoint kernels (die_conv2d_backward per
 plus one backward per world step, nothing of the field leaves the device.  Adam updates the 162 weights; the loss is printed
 every 10 steps and the agent is saved with `save()`.
 
-`--hidden-channels C --hidden-activation A` (the stand-alone student only) make the student a wide stack, 3 -> C -> 3 with A after
-the first layer.  It is fitted through `model.forward_device(planes)` on the observation's float32 planes — one
-`die_amd.functional.conv2d_wide` per layer, whose backward is die_conv2d_wide_backward (the MFMA adjoint kernels) — and
-`functional.gather_scale`, the same read-out; the student's own `differentiable_action` refuses a wide stack.
+`--hidden-channels C --hidden-activation A` make the student a wide stack, 3 -> C -> 3 with A after the first layer.  It is fitted
+through `model.forward_device(planes)` on the observation's float32 planes — one `die_amd.functional.conv2d_wide` per layer, whose
+backward is die_conv2d_wide_backward (the MFMA adjoint kernels) — and `functional.gather_scale`, the same read-out; the student's
+own `differentiable_action` refuses a wide stack.  With `--replicas` the wide students go through
+`BatchedNeuralAutomataAgent.forward_device` (die_nca_wide_backward_batch: the same kernels with the replica in blockIdx.z, L
+launches forward and 3 L - 1 backward whatever R is) and `functional.gather_scale_batch`.
 
 `--replicas R` (with `--students C`, R = C·E; default C = R) is the batched form: R worlds in one BatchedEnv seeded seed … seed + R − 1,
 the teacher a BatchedPhysarumAgent that steps them and hands its actions out through `step(..., action=target)`, the students one
@@ -97,15 +99,16 @@ class _Clock:
             log(f'{what}: {n / (time.perf_counter() - self.t0):.1f} optimiser steps/s over {n} steps')
 
 
-def imitate_batched(size, steps, lr, dynamics, seed, replicas, students, log=print, clock=None):
-    """R worlds, C students, E = R / C worlds per student; returns the BatchedNeuralAutomataAgent."""
+def imitate_batched(size, steps, lr, dynamics, seed, replicas, students, log=print, clock=None, wide_kw=None):
+    """R worlds, C students, E = R / C worlds per student; returns the BatchedNeuralAutomataAgent.  `wide_kw`: the students are
+    wide stacks, fitted through `forward_device` and `functional.gather_scale_batch`."""
     if replicas % students:
         raise SystemExit(f'--students {students} must divide --replicas {replicas}')
     torch.manual_seed(seed)
     env = BatchedEnv((size, size), make_dynamics(dynamics, size), replicas=replicas, seed=seed)
     scale = AGENT_KW['scale']
     teacher = BatchedPhysarumAgent(env, scale=scale, deposit=AGENT_KW['deposit'], seed=seed)
-    template = NeuralAutomataAgent(**AGENT_KW)
+    template = NeuralAutomataAgent(**AGENT_KW, **(wide_kw or {}))
     rows = []
     for _ in range(students):                                     # different initialisations side by side
         template.model.init_weights()
@@ -120,7 +123,8 @@ def imitate_batched(size, steps, lr, dynamics, seed, replicas, students, log=pri
     for t in range(steps):
         if clock is not None:
             clock.tick(t)
-        got = pop.differentiable_action()                         # the students look at the worlds the teacher is about to act on
+        # the students look at the worlds the teacher is about to act on
+        got = functional.gather_scale_batch(pop.forward_device(), pop) if template.model.wide else pop.differentiable_action()
         live = exists & (env.alive > 0)
         env.step(teacher, action=target)                          # its actions on those worlds: the targets
         loss = (((got[:2] - target[:2]) / scale)[:, live] ** 2).mean()
@@ -145,13 +149,11 @@ def main():
     p.add_argument('--time', action='store_true', help='print optimiser steps per second')
     add_wide_arguments(p)
     args = p.parse_args()
-    if args.replicas and wide_keywords(args):
-        raise SystemExit('--hidden-channels / --hidden-activation: the stand-alone student only (no --replicas)')
     if args.replicas:
         clock = _Clock(args.steps, args.time)
         quiet = (lambda *a: None) if args.time else print         # (a loss print reads the device: not inside a timed window)
         pop = imitate_batched(args.size, args.steps, args.lr, args.dynamics, args.seed, args.replicas, args.students or args.replicas,
-                              log=quiet, clock=clock)
+                              log=quiet, clock=clock, wide_kw=wide_keywords(args))
         clock.report(print, f'batched imitation, {args.replicas} worlds, {args.students or args.replicas} students')
         student = pop.candidate(0)
     else:

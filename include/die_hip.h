@@ -1050,6 +1050,48 @@ int die_nca_wide_env_step_batch(const die_medium* m, const die_agents* a, const 
                                 int64_t workspace_bytes, const die_nca_dropout* drop, const die_dynamics_row* rows,
                                 const die_dynamics_row* rows_host, void* stream);
 
+/* ---- The wide stack's adjoint for every replica of a die_batch (BatchedNeuralAutomataAgent.forward_device) -----------------
+ * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
+ * The wide twins of die_nca_sense_batch_store / die_nca_backward_batch_inputs: `m` describes replica 0 and `b` the strides,
+ * nca->scratch is not used and may be NULL, die_nca_layer.reserved is READ as the layer's activation (as
+ * die_nca_wide_env_step_batch reads it), the replica rides in blockIdx.z and replica r reads weight block r / E.
+ *
+ * die_nca_wide_sense_batch_store: die_nca_wide_env_step_batch's L launches of the wide layer kernel, layer l's unmasked output
+ * act(z) of every replica kept in `store`, [L][R][Cmax][W][H] fp32 with Cmax the largest cout of the stack
+ * (die_nca_wide_sense_batch_store_bytes = n_layers * replicas * max_channels * W * H * 4; -1 for a refused shape).  With `drop`
+ * the last layer is launched twice: unmasked into `store` and masked with key seed + r * seed_stride into `masked`,
+ * [R][Cmax][W][H] (required then, unused otherwise).  Nothing is stepped, claimed or moved. */
+int64_t die_nca_wide_sense_batch_store_bytes(int32_t W, int32_t H, int32_t replicas, int32_t n_layers, int32_t max_channels);
+int die_nca_wide_sense_batch_store(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* store, int64_t store_bytes,
+                                   float* masked, const die_nca_dropout* drop, void* stream);
+
+/* The stack's adjoint.  `m`: replica 0's first-layer planes as die_nca_wide_sense_batch_store read them (fp32, fp16 or the
+ * claim plane at nca->sense_epoch, b->plane_stride apart); `store`: what that call wrote; `grad_sense`: the gradient at the sense
+ * planes (3 planes W * H apart per replica, sense_stride between replicas); `drop`: the die_nca_dropout the forward was masked
+ * with, or NULL.  Per layer, from the last to the first: die_conv2d_wide_backward's weight-gradient kernel with gridDim.z = R
+ * (replica r writes its partial rows at workspace rows (r * tiles + tile)), its input-gradient kernel (layers >= 1 into a
+ * ping-pong pair of [R][Cmax][W][H] sets in the workspace; layer 0 only when `grad_in` is given: replica r's cin_0 planes at
+ * grad_in + r * grad_in_stride, in channel order ([agents,] food, chem)), and the fold: one thread per (candidate c, weight j)
+ * adds the candidate's E * tiles partial rows in ascending order in float64 and stores fp32 at
+ *   grad[c * grad_stride + offset_l + j]   (the row layout of parameters_to_vector; grad_stride >= the row's length).
+ * 3 L - 1 launches, 3 L with grad_in.  One kernel body serves this call and die_conv2d_wide_backward: for E = 1 row r is that
+ * call's gradient on replica r's world, bit for bit; for E > 1 row c is the float64 sum over its E worlds, rounded once.  No float
+ * atomics: the same inputs give the same bits on every run.
+ *   Workspace (die_nca_wide_backward_batch_workspace_bytes; -1 for any stack or shape the call refuses), in floats:
+ *   R * ceil(W / 16) * ceil(H / 64) * max_l(cout_l * cin_l * k_l^2)  +  min(L - 1, 2) * R * Cmax * W * H;
+ * 16-byte aligned where H % 4 == 0 and L >= 2 (the planes come first in it).
+ * Every argument is checked on the host before anything is launched, in die_nca_backward_batch's order with the wide limits.
+ * DIE_PAD_REFLECT / DIE_PAD_REPLICATE: DIE_ERR_UNSUPPORTED.  DIE_ERR_ARG: null arguments, replicas outside
+ * 1..DIE_MAX_REPLICAS, episodes not dividing R, a layer outside 1..32 channels or k not in {1, 3, 5}, a last layer that is not 3
+ * planes of tanh, an unknown activation, sense_epoch out of range, strides below their minimum, `grad` equal to a layer's
+ * weights, a short workspace, a bad `drop`, a grad_in that is not 16-byte aligned or whose stride is not a multiple of 4 where
+ * H % 4 == 0, and grad_in overlapping any other buffer of the call. */
+int64_t die_nca_wide_backward_batch_workspace_bytes(int32_t W, int32_t H, int32_t replicas, const die_nca_batch* nca);
+int die_nca_wide_backward_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store,
+                                const float* grad_sense, int64_t sense_stride, float* grad, int64_t grad_stride,
+                                const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, float* grad_in,
+                                int64_t grad_in_stride, void* stream);
+
 /* die_food_flow_batch on the replicas whose bit is set in replica_mask (bit r = replica r); the others' planes are not touched.
  * One launch: a row of workgroups per replica, those of unset replicas exit at once.  A full mask leaves exactly what
  * die_food_flow_batch leaves; an empty mask launches nothing.  Bits at or above b->replicas must be 0. */
