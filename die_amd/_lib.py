@@ -97,6 +97,11 @@ class Batch(C.Structure):
                 ('seed_stride', C.c_uint64), ('n', C.c_int64 * 64)]
 
 
+class Births(C.Structure):           # die_births
+    _fields_ = [('born_threshold', C.c_float), ('boundary', C.c_int32), ('born_spread', C.c_double), ('world_step', C.c_uint32),
+                ('reserved', C.c_uint32)]
+
+
 class DynamicsRow(C.Structure):      # die_dynamics_row: one replica's environment constants as the batched kernels consume them
     _fields_ = [('rate_feed', C.c_float), ('keep', C.c_float), ('food_infinite', C.c_int32), ('radius', C.c_int32),
                 ('w', C.c_float * 9), ('reserved', C.c_float * 3)]
@@ -258,6 +263,9 @@ _SIGNATURES = {
                                    C.c_int32, C.c_void_p, C.c_void_p]),
     'die_step_reduce_ex': (C.c_int, [_P(Agents), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p]),
     'die_agents_lifecycle': (C.c_int, [_P(Agents), C.c_void_p]),
+    'die_births_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int64]),
+    'die_agent_births': (C.c_int, [_P(Agents), _P(Births), C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'die_agent_births_batch': (C.c_int, [_P(Agents), _P(Batch), _P(Births), _P(C.c_uint64), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'die_gradient_render': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     'die_agent_claim_feed': (C.c_int, [_P(Medium), _P(Agents), _P(Action), _P(Dynamics), C.c_void_p, C.c_int64,
                                        C.c_void_p]),

@@ -45,7 +45,11 @@ rate_decay_chem, diffuse_sigma, food_infinite and whether the (one) food-flow op
 agree.  Replica r is then `Env(field_size, d_r, seed=seeds[r], max_agents=...)`, bit for bit: the kernels fetch replica r's row of a
 device table built once at construction (`die_dynamics_rows`), the field sweep is launched once per gaussian radius present, and
 the flow is applied under a replica mask (`die_food_flow_batch_masked`).  `episode_dynamics` lays E dynamics out for a population
-with `episodes=E`: `episode_fitness[:, e]` of a searcher is then the score under dynamics e (tests/test_gpu_dynamics_rows.py)."""
+with `episodes=E`: `episode_fitness[:, e]` of a searcher is then the score under dynamics e (tests/test_gpu_dynamics_rows.py).
+
+`Dynamics(agents_born=True)`: after a step's deaths every replica's well-fed agents breed into its dead slots, in slot order
+(`die_agent_births_batch`: three more launches per step whatever R, the step's last) — replica r is the stand-alone Env of that
+rule at the same world step, `num_agents` rising where colonies grow (tests/test_gpu_births.py)."""
 import ctypes as C
 import dataclasses
 import math
@@ -101,6 +105,10 @@ class BatchedEnv:
         if d.agents_die and d.compat != 'intended':
             raise NotImplementedError(f"batched replicas: agents_die with compat={d.compat!r} (the host-driven frozen-indexer "
                                       "sequence of Env); only compat='intended' is batched")
+        if d.agents_born:
+            Env._check_births(d)
+            if d.compat != 'intended':
+                raise NotImplementedError(f"batched replicas: agents_born with compat={d.compat!r}; only compat='intended' has births")
         if d.apply_sense_mask:
             raise NotImplementedError('batched replicas: apply_sense_mask is not batched')
         if d.diffuse_mode != 'wrap' or not isinstance(d.boundary, BoundaryCondition):
@@ -141,7 +149,9 @@ class BatchedEnv:
                     pic=False) for r in range(self.R)]
         self.n = [e.agents.N for e in envs]
         for r, e in enumerate(envs):
-            if self._fixed is None and not e._all_alive:            # (only a world seeded with no agent at all: 'alive' keeps one dead placeholder slot)
+            # (only a world seeded with no agent at all: 'alive' keeps one dead placeholder slot; e._num_seeded, not e._all_alive,
+            # which agents_born makes False by rule)
+            if self._fixed is None and e._num_seeded < e.agents.N:
                 raise NotImplementedError(f'batched replicas: replica {r} (seed {self.seeds[r]}) has no alive agent; dead slots are '
                                           'not modelled by the batched step')
         self.Nmax = max(self.n)
@@ -167,7 +177,14 @@ class BatchedEnv:
         # lifecycle pass
         dead = d.agents_die or self._fixed is not None
         ws = _lib.lib.die_batch_lifecycle_workspace_bytes(R, Nm) if dead else _lib.lib.die_batch_workspace_bytes(R)
-        self._ws = torch.zeros(int(ws), dtype=torch.uint8, device=dev)
+        self._births_ws = None
+        if d.agents_born:                           # the birth pass's counts and rank lists, behind the step's workspace
+            ws = -(-int(ws) // 256) * 256
+            births = int(_lib.lib.die_births_workspace_bytes(R, Nm))
+            self._ws = torch.zeros(ws + births, dtype=torch.uint8, device=dev)
+            self._births_ws = self._ws[ws:]
+        else:
+            self._ws = torch.zeros(int(ws), dtype=torch.uint8, device=dev)
         if self._fixed is not None:                 # reset(seed=...): die_init_batch's scan workspace and (K_r, overflow) words
             self._init_ws = torch.zeros(int(_lib.lib.die_init_batch_workspace_bytes(W, H, R)), dtype=torch.uint8, device=dev)
             self._counts = torch.zeros((R, 2), dtype=torch.int64, device=dev)
@@ -280,6 +297,16 @@ class BatchedEnv:
         return _lib.Dynamics(d.rate_feed, d.rate_decay_chem, d.diffuse_sigma, boundary, cost, 0.02, 0.01, int(d.food_infinite), int(d.agents_die),
                              int(self._fixed is not None), 0, 0)
 
+    def _births(self, a: _lib.Agents, b: _lib.Batch, results: torch.Tensor) -> None:
+        """`Dynamics(agents_born=True)`: the birth pass of every replica (die_agent_births_batch, three launches whatever R) as the
+        step's last launches — replica r breeds as the stand-alone Env of seeds[r] does at this world step."""
+        d = self.dynamics
+        p = _lib.Births(float(d.born_threshold), _lib.DIE_BOUNDARY_WRAP if d.boundary == BoundaryCondition.wrap else _lib.DIE_BOUNDARY_LIMIT,
+                        float(d.born_spread), self._steps & 0xFFFFFFFF, 0)
+        seeds = (C.c_uint64 * self.R)(*[q & 0xFFFFFFFFFFFFFFFF for q in self.seeds])
+        _lib.check(_lib.lib.die_agent_births_batch(C.byref(a), C.byref(b), C.byref(p), seeds, _ptr(results), _ptr(self._births_ws),
+                                                   self._births_ws.numel(), stream_ptr(self.device)), 'die_agent_births_batch')
+
     def check(self):
         """Synchronise; raise if a replica's tile-binned step reported a bookkeeping error since the last check (per-replica
         regime: every replica is an `Env` of its own; the one-launch-pair regime runs the classic kernels, which have no such word),
@@ -341,6 +368,8 @@ class BatchedEnv:
             raise
         agent._calls += 1
         agent._stepped()
+        if self.dynamics.agents_born:
+            self._births(a, b, results)
         self.chem_node = None                       # the field changed: an autograd handle of the chem planes ends here
         self.chem, self.chem_next = self.chem_next, self.chem
         self._food_flow(flow, m, b)
@@ -391,6 +420,8 @@ class BatchedEnv:
         except Exception:
             self.epoch = epoch                      # refused before any launch: nothing changed
             raise
+        if self.dynamics.agents_born:
+            self._births(a, b, results)
         self.chem_node = None                       # (differentiable_step sets this step's node afterwards)
         self.chem, self.chem_next = self.chem_next, self.chem
         self._food_flow(flow, m, b)
@@ -431,6 +462,8 @@ class BatchedEnv:
         reset.  agents_die, the fixed slot layout, a food flow, per-replica Dynamics and episodes are all taken; fp16 fields and
         large worlds raise NotImplementedError, a wrong action ValueError, before anything is launched or changed."""
         self._check_differentiable('differentiable_step')
+        if self.dynamics.agents_born:
+            raise NotImplementedError('differentiable_step: agents_born is not supported (a newborn has no action to differentiate)')
         want = (3, self.R, self.Nmax)
         if not isinstance(action, torch.Tensor) or tuple(action.shape) != want or action.dtype != torch.float32 or action.device != self.device:
             got = (tuple(action.shape), action.dtype, str(action.device)) if isinstance(action, torch.Tensor) else type(action).__name__
@@ -569,8 +602,8 @@ def episode_dynamics(dynamics: Sequence[Dynamics], candidates: int) -> List[Dyna
     return [dynamics[e] for _ in range(int(candidates)) for e in range(len(dynamics))]
 
 
-_MUST_AGREE = ('boundary', 'op_action_cost', 'strict_cost', 'agents_die', 'agents_born', 'compat', 'init_agent_ratio', 'apply_sense_mask',
-               'diffuse_mode')
+_MUST_AGREE = ('boundary', 'op_action_cost', 'strict_cost', 'agents_die', 'agents_born', 'born_threshold', 'born_spread', 'compat',
+               'init_agent_ratio', 'apply_sense_mask', 'diffuse_mode')
 
 
 def _shared_dynamics(dynamics, replicas: int):

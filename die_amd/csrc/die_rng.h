@@ -15,6 +15,7 @@
 #define DIE_STREAM_SEARCH 8u        // PGPE sampling (die_search.hip): oracle/rng.py normals2(seed, generation, n, stream=8, scale=1)[0]
 #define DIE_STREAM_CMAES 9u         // CMA-ES sampling (die_cmaes.hip): oracle/rng.py normals2(seed, generation, n, stream=9, scale=1)[0]
 #define DIE_STREAM_DROPOUT 10u      // agent dropout mask over cells (die_nca.hip): tests/dropout_model.py mask(seed, step, W, H, p)
+#define DIE_STREAM_BIRTH 11u        // a newborn's displacement from its parent (die_births.hip): tests/births_model.py, die_draw(world seed, world step, parent slot)
 
 struct die_u32x4 { uint32_t v[4]; };
 

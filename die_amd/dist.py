@@ -352,6 +352,9 @@ class DistEnv:
             raise NotImplementedError('apply_sense_mask is implemented for single-tile worlds only')
         if self.dynamics.diffuse_mode != 'wrap':
             raise NotImplementedError("decomposed worlds diffuse on the torus (diffuse_mode='wrap') only")
+        if self.dynamics.agents_born:
+            raise NotImplementedError('agents_born is implemented for single-tile worlds only: parents and free slots are matched in '
+                                      'the slot order of the whole world, which no rank holds')
         self.comm = Comm(group)
         R = int(4.0 * float(self.dynamics.diffuse_sigma) + 0.5)
         # guard band: agents may stay on a rank for `migrate_every` steps after leaving its interior (their

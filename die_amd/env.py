@@ -115,6 +115,13 @@ class Dynamics:
     # step on deposits, the agents channel, feeding and `num_agents` use the positions / alive flags frozen at the end
     # of the first step's move, while the agents the policy sees keep moving, starving and being zeroed
     compat: str = 'intended'
+    # not reference fields — the birth rule of `agents_born` (the reference has only a TODO, core/env.py:256-261), inert
+    # without it: after a step's deaths a slot that is alive with agent_food > born_threshold (fp32) is a parent; parents and dead
+    # slots are matched in slot order, the child takes half the parent's food and stands within ±born_spread (unit coordinates,
+    # at most 0.5) of it.  Per-slot state an agent object keeps (Physarum headings, a GradientAgent's momentum) is not touched:
+    # the reference advances it for dead slots too, so a newborn takes what its slot holds
+    born_threshold: float = 0.5
+    born_spread: float = 0.02
 
 
 class Env(_EnvBase):
@@ -143,6 +150,7 @@ class Env(_EnvBase):
         self._field_dtype = field_dtype
         self._sync = sync
         self._sort_every = self._auto_sort_every(field_size, sort_every)
+        self._sort_asked = sort_every
         self._staged = bool(staged)       # cross-checks: one kernel per stage of the step instead of the fused sweep
         self._pic_enabled = bool(pic)     # tile-binned step (die_amd/pic.py) whenever it applies
         self._seed = int.from_bytes(os.urandom(8), 'little') if seed is None else int(seed)
@@ -163,6 +171,22 @@ class Env(_EnvBase):
                                       'lifecycle inside the step would see agent_food before the cost: use linear_action_cost or zero_cost')
         if self._field_size[0] < 2 or self._field_size[1] < 2:
             raise ValueError('field must be at least 2x2')
+        if d.agents_born:
+            self._check_births(d)
+            if d.compat == 'reference':
+                raise NotImplementedError("agents_born with compat='reference': births are defined for the intended lifecycle only "
+                                          "(the reference's frozen indexer would never see a newborn)")
+            if self._sort_asked is not None and int(self._sort_asked) > 0:
+                raise ValueError(f'sort_every={self._sort_asked} with agents_born: parents and free slots are matched by storage order, '
+                                 'which must stay slot order; leave sort_every unset (the periodic re-sort is off under agents_born)')
+            self._sort_every = 0
+
+    @staticmethod
+    def _check_births(d):
+        if not 0.0 <= float(d.born_spread) <= 0.5:
+            raise ValueError(f'born_spread={d.born_spread!r}: a half-width in unit coordinates, 0 .. 0.5')
+        if float(d.born_threshold) != float(d.born_threshold):
+            raise ValueError('born_threshold is NaN')
 
     def _init_data(self, field_size):
         """core/env.py:74-86."""
@@ -173,7 +197,10 @@ class Env(_EnvBase):
 
     def _after_state_change(self):
         self._workspace = DataInitializer.workspace(self._field_size, self.agents.N, self.device)
-        self._all_alive = bool(self.agents.alive.all().item())
+        self._all_alive = bool(self.agents.alive.all().item()) and not self.dynamics.agents_born
+        self._births_ws = None
+        if self.dynamics.agents_born:       # (before the first step, like the re-sort's buffers)
+            self._alloc_births_ws()
         self._steps = 0
         self._shadow = None
         self._sort_ws = None
@@ -215,6 +242,7 @@ class Env(_EnvBase):
         env._field_dtype = kw.get('field_dtype', torch.float32)
         env._sync = kw.get('sync', True)
         env._sort_every = cls._auto_sort_every(env._field_size, kw.get('sort_every'))
+        env._sort_asked = kw.get('sort_every')
         env._staged = bool(kw.get('staged', False))
         env._pic_enabled = bool(kw.get('pic', True))
         env._seed = int(kw.get('seed', 0))
@@ -305,6 +333,9 @@ class Env(_EnvBase):
 
     def step(self, action):
         """core/env.py:101-131 → (obs, reward, terminated, truncated, info)."""
+        born = self.dynamics.agents_born
+        if born:
+            self._check_births_apply('step')        # (every refusal before any launch or state change)
         self.medium.chem_node = None        # the field is about to change: an autograd handle of the chem plane ends here
         fused = binned = False
         burned = None
@@ -315,7 +346,8 @@ class Env(_EnvBase):
         # into pinned host memory, where the host waits for exactly those words instead of a 24-byte copy behind a stream
         # synchronisation (≈ 20 µs of a 187-µs step at 4096², most of a step at 256²).  A custom cost corrects the result on
         # the device afterwards: that case keeps the copy.
-        host = self._sync and burned is None and self._host_result_buffer() is not None
+        # agents_born: the birth pass adds to num_alive after the step's last kernel — the words are read by copy, behind it
+        host = self._sync and burned is None and not born and self._host_result_buffer() is not None
         if host:
             res3 = self._host_res
             if self._host_read_pending:
@@ -365,6 +397,8 @@ class Env(_EnvBase):
             self._agents_changed()          # a classic step moved the agents in place: the tile order is gone, bin again
         if burned is not None:
             self._apply_custom_cost(burned, result)
+        if born:                            # the second half of _agent_lifecycle: agent arrays only, so the step's last launches
+            self._launch_births(self._steps, result)
         self.medium.swap_chem()
         if self.dynamics.op_food_flow is not _identity_food_flow:
             self._food_flow()
@@ -382,7 +416,7 @@ class Env(_EnvBase):
             self.last_result = res3[:2].clone()
         else:
             reward, num_agents = self.read_result(res3)
-        if self.dynamics.agents_die:
+        if self.dynamics.agents_die or born:
             self._all_alive = False
         mean_gain = reward / num_agents if num_agents > 0 else 0.
         info = {'num_agents': num_agents, 'reward': _np_round(reward, 3), 'mean_reward': _np_round(mean_gain, 5)}
@@ -428,6 +462,8 @@ class Env(_EnvBase):
         when the record is made and gets no gradient for its last deposit."""
         from .agent.evo import _DifferentiableFieldStep
         self._check_differentiable('differentiable_step')
+        if self.dynamics.agents_born:
+            raise NotImplementedError('differentiable_step: agents_born is not supported (a newborn has no action to differentiate)')
         N = self.agents.N
         if not isinstance(action, torch.Tensor) or action.dtype != torch.float32 or tuple(action.shape) != (3, N) \
                 or action.device != self.device:
@@ -517,7 +553,8 @@ class Env(_EnvBase):
         if self._pic_tile is False:                              # (settled at the first step: this world is too small / does not divide into tiles)
             return False
         # (dead slots — the reference's default max_agents = W·H — ride behind the tiles' segments: without agents_die they stay dead)
-        if not (self._pic_enabled and not d.agents_die and not d.apply_sense_mask and not self._staged
+        # (agents_born: births fill dead slots in slot order, the binned layout keeps its own order: the step does not apply)
+        if not (self._pic_enabled and not d.agents_die and not d.agents_born and not d.apply_sense_mask and not self._staged
                 and self.medium.world is None and isinstance(d.boundary, BoundaryCondition) and d.diffuse_mode == 'wrap'
                 and 1 <= int(4.0 * float(d.diffuse_sigma) + 0.5) <= 4):
             return False
@@ -604,13 +641,17 @@ class Env(_EnvBase):
         faster than the plain launch loop (256²: 33.8 vs 30.4 µs/step, 1024²: 49.0 vs 42.3, 4096²: 243 vs 224 —
         ≈ 5 µs per graph node), so the default is the loop."""
         from .agent.gradient import GradientAgent
+        if graph and self.dynamics.agents_born:
+            raise NotImplementedError('Env.run(graph=True): agents_born is not captured (the world step of the birth pass is a launch '
+                                      'argument, frozen in a graph); use the step loop')
         self.medium.chem_node = None
         n_steps = int(n_steps)
         out = torch.empty((max(n_steps, 0), 2), dtype=torch.float64, device=self.device)
         sync, self._sync = self._sync, False
         try:
             ok = isinstance(agent, GradientAgent) and agent.lazy and agent._turn_sign is None and \
-                self.dynamics.op_food_flow is _identity_food_flow and not self.dynamics.agents_die and self._fuse_forward
+                self.dynamics.op_food_flow is _identity_food_flow and not self.dynamics.agents_die and not self.dynamics.agents_born \
+                and self._fuse_forward
             if graph is None:
                 graph = False
             elif graph and not ok:
@@ -769,6 +810,8 @@ class Env(_EnvBase):
         Invisible to callers: slot ids travel with the agents, attached Agent objects have their
         per-slot state permuted alongside."""
         A = self.agents
+        if self.dynamics.agents_born:
+            raise ValueError('sort_agents with agents_born: parents and free slots are matched by storage order, which must stay slot order')
         if self._shadow is None:
             self._alloc_sort_buffers()
         ox, oy, oalive, ofood = self._shadow[:4]
@@ -795,6 +838,53 @@ class Env(_EnvBase):
         for obj, n in owners:
             obj._die_state_permuted(outs[k:k + n], A.slot)
             k += n
+
+    # ------------------------------------------------------------------ births (die_births.hip)
+    def _check_births_apply(self, what: str):
+        """What the birth pass needs of this world; raises before anything is launched or changed."""
+        d = self.dynamics
+        self._check_births(d)
+        if not isinstance(d.boundary, BoundaryCondition):
+            raise NotImplementedError(f'{what}: births need a BoundaryCondition (boundary={d.boundary!r})')
+        if self.medium.world is not None:
+            raise NotImplementedError(f'{what}: births on a decomposed medium (one tile of a larger world) are not supported: parents and '
+                                      'free slots are matched in the slot order of the whole world')
+        if self.agents.slot is not None:
+            raise ValueError(f'{what}: the agent arrays were re-sorted; births match parents and free slots by storage order, which '
+                             'must be slot order (build the Env with sort_every=0)')
+        if self.agents.N > _lib.OWNER_SLOT_MASK:
+            raise ValueError(f'{what}: {self.agents.N} slots (births rank at most {_lib.OWNER_SLOT_MASK})')
+
+    def _alloc_births_ws(self):
+        n = int(_lib.lib.die_births_workspace_bytes(1, self.agents.N))
+        if n < 0:
+            raise ValueError(f'agents_born: {self.agents.N} slots (births rank at most {_lib.OWNER_SLOT_MASK})')
+        self._births_ws = (self.agents.N, torch.empty(n, dtype=torch.uint8, device=self.device))
+
+    def _launch_births(self, world_step: int, result):
+        d, A = self.dynamics, self.agents
+        if self._births_ws is None or self._births_ws[0] != A.N:
+            self._alloc_births_ws()
+        ws = self._births_ws[1]
+        p = _lib.Births(float(d.born_threshold), _lib.DIE_BOUNDARY_WRAP if d.boundary == BoundaryCondition.wrap else _lib.DIE_BOUNDARY_LIMIT,
+                        float(d.born_spread), int(world_step) & 0xFFFFFFFF, 0)
+        a = A.c_struct()
+        _lib.check(_lib.lib.die_agent_births(C.byref(a), C.byref(p), self._seed & 0xFFFFFFFFFFFFFFFF, None if result is None else _ptr(result),
+                                             _ptr(ws), ws.numel(), stream_ptr(self.device)), 'die_agent_births')
+
+    def apply_births(self, step: Optional[int] = None, result: Optional[torch.Tensor] = None):
+        """The birth pass of `Dynamics(agents_born=True)` alone (die_agent_births), for custom update cycles such as `_manual_step`
+        of examples/simple_agents.py — whatever `dynamics.agents_born` says; born_threshold, born_spread and boundary are read from
+        `dynamics`.  `step`: the world step the newborns' displacements are drawn at (default: the steps taken so far; `Env.step`
+        itself draws at the number of steps taken BEFORE it).  `result`: a (2,) float64 device tensor of die_step_result words
+        (`last_result`) whose num_agents word gets the number born added, or None.  Nothing is read back."""
+        self._check_births_apply('apply_births')
+        if result is not None and (not isinstance(result, torch.Tensor) or result.dtype != torch.float64 or result.numel() < 2
+                                   or result.device != self.device or not result.is_contiguous()):
+            raise ValueError(f'apply_births: result must be a contiguous float64 tensor of 2 words on {self.device}')
+        self._agents_changed()
+        self._launch_births(self._steps if step is None else int(step), result)
+        self._all_alive = False
 
     # substeps, for custom update cycles (examples/simple_agents.py:16-30)
     def _agents_changed(self):

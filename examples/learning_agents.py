@@ -6,7 +6,7 @@ steps, update (die_amd.search.PGPE).  `--searcher cmaes` trains with the referen
 separable CMA-ES with stdev_init 0.1 and popsize 10 (die_amd.search.CMAES), the same chain of launches.
 
     python examples/learning_agents.py [--searcher pgpe|cmaes] [--dynamics st-perlin-wide] [--size 96] [--generations 100]
-                                       [--epoch-iters 30] [--agents-die] [--max-agents alive|full|tight|N]
+                                       [--epoch-iters 30] [--agents-die] [--agents-born] [--max-agents alive|full|tight|N]
                                        [--reseed S] [--reseed-stride 0] [--episodes 1] [--out saved_models/agent.pt] [--time]
                                        [--dropout P] [--dropout-seed S] [--dropout-stride K] [--init-from FILE]
 
@@ -22,6 +22,10 @@ launch.  The mask counter runs on from generation to generation, so every genera
 is then scored under EVERY listed dynamics each generation, in the same launches (BatchedEnv(dynamics=[...]): per-replica Dynamics;
 episode e lives under dynamics e mod len).  The list implies --episodes len(list) unless --episodes is given (then a multiple of it);
 the fitness is the mean over the episodes, and the mean of `episode_fitness` under each dynamics is printed with the history.
+
+--agents-die trains under the death pressure (Dynamics(agents_die=True)); --agents-born adds births (Dynamics(agents_born=True):
+after a step's deaths the agents with more than 0.5 food breed into dead slots, three more launches per batched step), so that a
+candidate is rewarded for thriving and not only for not starving.
 
 --reseed S gives every generation a new world: generation g resets the batch to the world of seed S + g·popsize, seeded on the
 device (BatchedEnv.reset(seed=...), five launches, no host read); with --reseed-stride 0 (default) every candidate of a
@@ -51,7 +55,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from die_amd import CMAES, PGPE, Env, NeuralAutomataAgent            # noqa: E402
 from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent, episode_seeds   # noqa: E402
-from population_eval import (DYNAMICS, add_wide_arguments, batch_dynamics, dropout_keywords, dynamics_names, evaluate_population, make_dynamics,   # noqa: E402
+from population_eval import (DYNAMICS, add_wide_arguments, batch_dynamics, dropout_keywords, dynamics_names, evaluate_population, lifecycle, make_dynamics,   # noqa: E402
                              make_population, make_template, per_dynamics_means, resolve_episodes, run_epoch, slots, wide_keywords)
 
 RADIUS_INIT = 1.5
@@ -148,6 +152,7 @@ def main():
     p.add_argument('--out', default=None, help='agent file for pop_best (default: saved_models/neuralautomataagent_<searcher>_<G>x<T>.pt)')
     p.add_argument('--time', action='store_true')
     p.add_argument('--agents-die', action='store_true', help='Dynamics(agents_die=True): starved agents die, fitness feels it')
+    p.add_argument('--agents-born', action='store_true', help='Dynamics(agents_born=True): well-fed agents breed into dead slots')
     p.add_argument('--max-agents', default=None, help="slots per replica: 'alive' (default without --reseed), 'full' (W·H), "
                                                       "'tight' (default with --reseed) or a number")
     p.add_argument('--reseed', type=int, default=None, help='a new world every generation: seed S + g·popsize (device-seeded)')
@@ -161,6 +166,7 @@ def main():
     add_wide_arguments(p)
     args = p.parse_args()
     args.wide_kw = wide_keywords(args)
+    args.agents_die = lifecycle(args.agents_die, args.agents_born)      # (what the helpers hand to make_dynamics)
     if not 0. <= args.dropout <= 1. or args.dropout_stride < 0:
         p.error('--dropout in [0, 1], --dropout-stride >= 0')
     args.drop_kw = dropout_keywords(args.dropout, args.dropout_seed, args.dropout_stride)

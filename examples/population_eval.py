@@ -2,7 +2,7 @@
 once: R NeuralAutomataAgent candidates, each scored by the sum of its rewards over `epoch_iters` steps of its own world,
 all R worlds stepped together by die_amd.batch (L + 2 launches per step for an L-layer model, L + 3 with a food flow).
 
-    python examples/population_eval.py [--replicas 10] [--size 96] [--iters 50] [--dynamics st-perlin-wide] [--generations 0] [--agents-die]
+    python examples/population_eval.py [--replicas 10] [--size 96] [--iters 50] [--dynamics st-perlin-wide] [--generations 0] [--agents-die] [--agents-born]
                                        [--max-agents alive|full|tight|N] [--reseed S] [--episodes 1] [--compare]
                                        [--dropout P] [--dropout-seed S] [--dropout-stride K]
 
@@ -12,6 +12,9 @@ A comma list (e.g. st-perlin,st-perlin-wide,dyn-pred) scores every candidate und
 (BatchedEnv(dynamics=[...]): per-replica Dynamics): it implies --episodes len(list) unless --episodes is given, which must then be a
 multiple of it (episode e lives under dynamics e mod len), and the mean score under each dynamics is printed.
 --agents-die adds the death pressure (Dynamics(agents_die=True): starved agents are zeroed; one more launch per batched step).
+--agents-born adds births (Dynamics(agents_born=True): after a step's deaths the agents with more than 0.5 food breed into dead
+slots, in slot order; three more launches per batched step).  Colonies can only grow where there are dead slots: use it with
+--agents-die or a --max-agents layout other than 'alive'.
 --max-agents picks the replicas' slot layout: 'alive' (K_r slots, the seeded agents), 'full' (W·H, the reference's default),
 'tight' (the expected count plus six standard deviations) or a number; every layout but 'alive' runs the dead-slot pass.
 --reseed S (with --generations, a fixed layout): generation g evaluates on the world of seed S + g, seeded on the device by
@@ -49,13 +52,19 @@ DYNAMICS = ('st-perlin', 'st-perlin-wide', 'dyn-pred')
 
 def make_dynamics(choice, size, agents_die=False):
     """learning_agents.py's `dynamics_choice[choice]`, with a fresh flow operator (its time counter at 0) for 'dyn-pred';
-    `agents_die`: starved agents die (the reference's 'not dying' pressure)."""
+    `agents_die`: starved agents die (the reference's 'not dying' pressure) — True / False, or `lifecycle(...)`'s dict of the
+    lifecycle fields when births are on too (every helper below hands it through to here)."""
+    life = dict(agents_die) if isinstance(agents_die, dict) else dict(agents_die=bool(agents_die))
     if choice == 'st-perlin':
-        return Dynamics(food_infinite=True, agents_die=agents_die)
+        return Dynamics(food_infinite=True, **life)
     if choice == 'st-perlin-wide':
-        return Dynamics(food_infinite=True, rate_decay_chem=0.025, diffuse_sigma=.8, agents_die=agents_die)
-    return Dynamics(food_infinite=False, op_food_flow=WaveSequence((size, size), dt=0.01).get_flow_operator(scale=0.5, decay=0.5),
-                    agents_die=agents_die)
+        return Dynamics(food_infinite=True, rate_decay_chem=0.025, diffuse_sigma=.8, **life)
+    return Dynamics(food_infinite=False, op_food_flow=WaveSequence((size, size), dt=0.01).get_flow_operator(scale=0.5, decay=0.5), **life)
+
+
+def lifecycle(agents_die, agents_born):
+    """--agents-die / --agents-born as the `agents_die` argument of the helpers here: the plain flag without births."""
+    return dict(agents_die=bool(agents_die), agents_born=True) if agents_born else bool(agents_die)
 
 
 def dynamics_names(spec):
@@ -182,6 +191,7 @@ def main():
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--compare', action='store_true')
     p.add_argument('--agents-die', action='store_true', help='Dynamics(agents_die=True): starved agents die')
+    p.add_argument('--agents-born', action='store_true', help='Dynamics(agents_born=True): well-fed agents breed into dead slots')
     p.add_argument('--max-agents', default='alive', help="slots per replica: 'alive', 'full' (W·H), 'tight' or a number")
     p.add_argument('--reseed', type=int, default=None, help='--generations on the device-seeded world of seed S + g (fixed layout)')
     p.add_argument('--episodes', type=int, default=None, help='worlds per candidate (replicas x episodes <= 64); default 1, or the '
@@ -200,6 +210,8 @@ def main():
     except ValueError as err:
         p.error(str(err))
     R, E = args.replicas, args.episodes
+    pressures = (' with agents_die' if args.agents_die else '') + (' with agents_born' if args.agents_born else '')
+    args.agents_die = lifecycle(args.agents_die, args.agents_born)
     if E < 1 or R * E > 64:
         p.error(f'--episodes {E}: at least 1, and {R} replicas x episodes at most 64')
     N = slots(args.max_agents, args.size, args.dynamics, args.agents_die)
@@ -217,7 +229,7 @@ def main():
     rows = torch.stack(cands)
     print(f'{R} candidates of {rows.shape[1]} parameters' + (f' on {E} worlds each' if E > 1 else '') +
           f', {args.size}x{args.size}, {args.iters} steps each, {args.dynamics}'
-          f'{" with agents_die" if args.agents_die else ""}, max_agents={N}' +
+          f'{pressures}, max_agents={N}' +
           (f', dropout {args.dropout} (seed {args.dropout_seed}, stride {args.dropout_stride})' if drop_kw else ''), flush=True)
 
     benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die, N, E, drop_kw)

@@ -28,6 +28,7 @@ def manual_step(env: Env, action):
         _agent_move                                      die_agent_move_claim   (move + who-stands-where claims + the agents'
         _agent_deposit_and_layout, _agent_feed           die_agent_resolve       own gain)  /  (deposit and the field's loss)
         _agent_lifecycle                                 die_agents_lifecycle   (only with Dynamics(agents_die=True))
+                                                         env.apply_births()     (only with Dynamics(agents_born=True))
         _medium_resource_dynamics                        env._food_flow()
         _medium_diffuse_decay                            env._medium_diffuse_decay()
     """
@@ -40,7 +41,10 @@ def manual_step(env: Env, action):
     _lib.check(_lib.lib.die_agent_resolve(C.byref(m), C.byref(a), C.byref(u), C.byref(d), ws, wsn, sp), 'die_agent_resolve')
     if env.dynamics.agents_die:
         _lib.check(_lib.lib.die_agents_lifecycle(C.byref(a), sp), 'die_agents_lifecycle')
-    env._food_flow()                     # identity unless the dynamics carries a flow operator
+    if env.dynamics.agents_born:         # the lifecycle's other half: the well-fed breed into dead slots, drawn at this world
+        env.apply_births()               # step — which a hand-made cycle counts itself
+        env._steps += 1
+    env._food_flow()                    # identity unless the dynamics carries a flow operator
     env._medium_diffuse_decay()
     return env._get_current_obs, 0, False, False, {}
 

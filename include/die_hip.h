@@ -344,6 +344,32 @@ int die_step_reduce_ex(const die_agents* a, die_step_result* result, void* works
  * the reference-compatible agents_die mode (die_amd/env.py Env._step_compat), whose claim / feeding lookups run on a frozen
  * copy of the agent array — the reference's stale AgentIndexer (core/env.py:249 vs core/utils.py:22). */
 int die_agents_lifecycle(const die_agents* a, void* stream);
+
+/* ---- Dynamics.agents_born (no reference counterpart: core/env.py:256-261 is a TODO) ------------------------
+ * The birth half of _agent_lifecycle, run after a step's deaths.  A PARENT is a slot that is alive with agent_food >
+ * born_threshold (fp32 compare); a FREE slot is a dead slot below n.  Both are ranked by slot index; parent j breeds into free
+ * slot j for j < min(#parents, #free): the child is alive with 0.5f * agent_food, the parent keeps agent_food - child (both
+ * exact), and the child stands at the parent's position displaced by (ox, oy) = ((int64)(int32)w.x * q) >> 31, likewise w.y,
+ * w = Philox(key world_seed, counter (parent slot, world_step, stream 11)), q = round(born_spread * 2^32) — applied with the
+ * move's boundary code (wrapping add / clamp to [0, 2^32 - 1]).  Only the agent arrays are written; `result` (may be NULL)
+ * gets the number born added to num_alive.  Three launches, no atomics, the same bits on every run.  The arrays must be in
+ * slot order (a->slot == NULL).  The workspace holds die_births_workspace_bytes(replicas, agent_stride) bytes (-1: bad
+ * sizes); every refusal happens before any launch. */
+typedef struct die_births {
+    float born_threshold;
+    int32_t boundary;        /* die_boundary: WRAP or LIMIT */
+    double born_spread;      /* unit coordinates, 0 .. 0.5 */
+    uint32_t world_step;     /* steps since construction / reset */
+    uint32_t reserved;
+} die_births;
+int64_t die_births_workspace_bytes(int32_t replicas, int64_t agent_stride);
+int die_agent_births(const die_agents* a, const die_births* p, uint64_t world_seed, die_step_result* result, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+/* The same pass on every replica of a die_batch in the same three launches: `a` describes replica 0, replica r's arrays start
+ * r * b->agent_stride elements further and hold b->n[r] slots; world_seeds is a HOST array of b->replicas keys, read during the
+ * call; results[r] (may be NULL) gets replica r's number born.  Replica r ends exactly as die_agent_births on it alone. */
+int die_agent_births_batch(const die_agents* a, const die_batch* b, const die_births* p, const uint64_t* world_seeds,
+                           die_step_result* results, void* workspace, int64_t workspace_bytes, void* stream);
 /* Decomposed step, second half: claim + feeding of die_agent_move_claim without the move. */
 int die_agent_claim_feed(const die_medium* m, const die_agents* a, const die_action* act, const die_dynamics* d,
                          void* workspace, int64_t workspace_bytes, void* stream);
