@@ -59,7 +59,7 @@ class ConvPlane(C.Structure):
     _fields_ = [('data', C.c_void_p), ('kind', C.c_int32), ('reserved', C.c_int32)]
 
 
-DIE_PLANE_F32, DIE_PLANE_F16, DIE_PLANE_AGENTS = 0, 1, 2
+DIE_PLANE_F32, DIE_PLANE_F16, DIE_PLANE_AGENTS, DIE_PLANE_STOCK = 0, 1, 2, 3
 PAD_MODES = {'circular': 0, 'zeros': 1, 'reflect': 2, 'replicate': 3}        # torch.nn.Conv2d padding_mode → die_pad_mode
 DIE_FIELD_CONST, DIE_FIELD_NOISE, DIE_FIELD_AGENTS, DIE_FIELD_PERLIN = 0, 1, 2, 3
 
@@ -242,6 +242,13 @@ _SIGNATURES = {
     'die_nca_wide_batch_scratch_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'die_nca_wide_env_step_batch': (C.c_int, [_P(Medium), _P(Agents), _P(NcaBatch), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
                                               C.c_void_p, C.c_int64, _P(NcaDropout), C.c_void_p, _P(DynamicsRow), C.c_void_p]),
+    'die_stock_plane': (C.c_int, [_P(Medium), _P(Agents), C.c_int32, C.c_void_p, C.c_void_p]),
+    'die_stock_plane_batch': (C.c_int, [_P(Medium), _P(Agents), _P(Batch), C.c_int32, C.c_void_p, C.c_void_p]),
+    'die_nca_env_step_batch_stock': (C.c_int, [_P(Medium), _P(Agents), _P(NcaBatch), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
+                                               C.c_void_p, C.c_int64, _P(NcaDropout), C.c_void_p, _P(DynamicsRow), C.c_void_p, C.c_void_p]),
+    'die_nca_wide_env_step_batch_stock': (C.c_int, [_P(Medium), _P(Agents), _P(NcaBatch), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
+                                                    C.c_void_p, C.c_int64, _P(NcaDropout), C.c_void_p, _P(DynamicsRow), C.c_void_p,
+                                                    C.c_void_p]),
     'die_nca_wide_sense_batch_store_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'die_nca_wide_sense_batch_store': (C.c_int, [_P(Medium), _P(Batch), _P(NcaBatch), C.c_void_p, C.c_int64, C.c_void_p, _P(NcaDropout),
                                                  C.c_void_p]),

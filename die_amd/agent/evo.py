@@ -153,7 +153,20 @@ class NeuralAutomataAgent(TorchAgent):
       * an int: the counter-based mask of include/die_hip.h (die_nca_dropout), a pure function of (dropout_seed, `dropout_step`,
         cell), applied inside the last layer's launch (`die_conv2d_dropout`).  `dropout_step` is the forward-call counter: it
         starts at 0, every `sense` advances it by one, and it may be read and written (setting it back replays the masks).
-    It is kept out of `init_params` while None, so saved files stay loadable by the reference."""
+    It is kept out of `init_params` while None, so saved files stay loadable by the reference.
+
+    `with_stock_channel` (no reference counterpart; core/agent/evo.py leaves it as "TODO: agents should have access to their own
+    resource stock"): True appends a last observation channel `'agent_food'` — a (W, H) float32 plane holding, on every cell, the
+    `agent_food` of the agent standing there as `sense` finds the agents (after the previous step's feed, deaths and births):
+    alive slots only, the highest slot id where several share a cell, 0 elsewhere, negative stocks kept.  The
+    first channels of `kernels.0.weight` keep their meaning.  `sense(medium, agents)` then needs the agents (ValueError before any
+    launch without them; `forward(obs)` passes its own), builds the plane on the device (die_stock_plane at `medium.epoch`, one
+    launch more) and hands it to the first layer as DIE_PLANE_STOCK.  The agent owns one stock plane per (W, H, device), zeroed
+    when it is allocated and whenever `medium.epoch` is not greater than the epoch of its last build on it.  Narrow and wide
+    stacks, fp16 fields, every boundary, both dropout masks and tile-binned worlds take it.  Refused with the channel on, each
+    with NotImplementedError before any launch and before `dropout_step` moves: `differentiable_sense` and
+    `differentiable_action` (the plane is piecewise constant in the weights and the adjoint calls do not take its kind), and a
+    decomposed medium (die_amd/dist.py).  Kept out of `init_params` while False, saved and restored by `load` while True."""
 
     def __init__(self,
                  scale: float = 0.1,
@@ -161,10 +174,18 @@ class NeuralAutomataAgent(TorchAgent):
                  with_agent_channel: bool = True,
                  initial_obs=None,
                  dropout_seed: Optional[int] = None,
+                 with_stock_channel: bool = False,
                  **model_kwargs,
                  ):
         self._init_params = save_args(self.__init__, locals())
         self._init_params.pop('initial_obs', None)            # an observation is not a constructor parameter worth saving
+        if not isinstance(with_stock_channel, (bool, np.bool_)):
+            raise ValueError(f'with_stock_channel={with_stock_channel!r}: True or False')
+        self.with_stock_channel = bool(with_stock_channel)
+        if self.with_stock_channel:
+            self._init_params['with_stock_channel'] = True
+        else:                                                 # (kept out while False, as dropout_seed is while None)
+            del self._init_params['with_stock_channel']
         for name in ('hidden_channels', 'hidden_activation'):  # (kept out while None, as dropout_seed is: see ConvolutionModel)
             if self._init_params['model_kwargs'].get(name, 0) is None:
                 del self._init_params['model_kwargs'][name]
@@ -172,6 +193,9 @@ class NeuralAutomataAgent(TorchAgent):
         self.dropout_seed = dropout_seed
         self.dropout_step = 0
         self.obs_channels = list(DataChannels.medium) if with_agent_channel else list(DataChannels.medium[1:])
+        if self.with_stock_channel:
+            self.obs_channels.append(DataChannels.agents[3])   # 'agent_food': always the LAST observation channel
+        self._stock = {}                                       # (W, H, device) -> [uint64 stock plane, epoch of its last build]
         self._model = ConvolutionModel(num_obs_channels=len(self.obs_channels), num_act_channels=len(DataChannels.actions),
                                        **model_kwargs)
         self.action_coefs = (float(scale), float(scale), float(deposit))
@@ -231,9 +255,39 @@ class NeuralAutomataAgent(TorchAgent):
                 raise NotImplementedError(f'kernel size {int(k.kernel_size[0])} in a wide stack (hidden_channels / hidden_activation): '
                                           f'one of {_lib.NCA_WIDE_KERNEL_SIZES} (32 * 32 * 49 weights do not fit LDS next to a tile)')
 
-    def sense(self, medium) -> th.Tensor:
-        """ConvolutionModel.forward over the medium on the device → (3, W, H) float32 tensor."""
+    def _check_stock(self, what: str = None, medium=None):
+        """The stock channel's refusals, before any launch: (`what`) a differentiable call, (`medium`) a decomposed world."""
+        if not self.with_stock_channel:
+            return
+        if what is not None:
+            raise NotImplementedError(f'{what}: no gradients with the stock channel (with_stock_channel=True): its plane is piecewise '
+                                      'constant in the weights and the adjoint kernels do not take its kind')
+        if medium is not None and getattr(medium, 'world', None) is not None:
+            raise NotImplementedError('with_stock_channel=True on a decomposed medium (die_amd/dist.py): the stock plane is built for '
+                                      'periodic single-tile planes only')
+
+    def _stock_plane(self, medium, agents) -> th.Tensor:
+        """The agents' stocks on their cells, built at `medium.epoch` on the plane this agent owns for (W, H, device)."""
+        dev, W, H = medium.device, medium.W, medium.H
+        key = (W, H, str(dev))
+        entry = self._stock.get(key)
+        if entry is None:
+            entry = self._stock[key] = [th.zeros((W, H), dtype=th.int64, device=dev), medium.epoch]
+        elif medium.epoch <= entry[1]:                           # a word of this or a later epoch would read as an agent: start over
+            entry[0].zero_()
+        entry[1] = medium.epoch
+        m, a = medium.c_struct(need_owner=False), agents.c_struct()
+        _lib.check(_lib.lib.die_stock_plane(C.byref(m), C.byref(a), medium.epoch, _ptr(entry[0]), stream_ptr(dev)), 'die_stock_plane')
+        return entry[0]
+
+    def sense(self, medium, agents=None) -> th.Tensor:
+        """ConvolutionModel.forward over the medium on the device → (3, W, H) float32 tensor.  `agents`: the DeviceAgents whose
+        stocks the `'agent_food'` channel shows — required with `with_stock_channel=True` (ValueError before any launch), unused
+        otherwise."""
         self._check_wide()
+        self._check_stock(medium=medium)
+        if self.with_stock_channel and agents is None:
+            raise ValueError("sense(medium, agents): with_stock_channel=True needs the agents whose stocks the 'agent_food' channel shows")
         medium.sensed()
         dev, W, H = medium.device, medium.W, medium.H
         weights = self._device_weights(dev)
@@ -242,6 +296,8 @@ class NeuralAutomataAgent(TorchAgent):
         medium._ensure_owner()
         fkind = _lib.DIE_PLANE_F32 if medium.dtype == th.float32 else _lib.DIE_PLANE_F16
         src = {'agents': (medium.owner, _lib.DIE_PLANE_AGENTS), 'env_food': (medium.food, fkind), 'chem1': (medium.chem, fkind)}
+        if self.with_stock_channel:
+            src['agent_food'] = (self._stock_plane(medium, agents), _lib.DIE_PLANE_STOCK)
         planes = [src[c] for c in self.obs_channels]
         sets = self._scratch(W, H, dev, 2, max(4, *(w.shape[0] for w in weights)) if wide else 4)
         p = self._model.agent_dropout.p
@@ -278,7 +334,7 @@ class NeuralAutomataAgent(TorchAgent):
     def forward(self, obs) -> DeviceAction:
         """:150-174."""
         agents, medium = obs
-        sense = self.sense(medium)
+        sense = self.sense(medium, agents)
         self._sense_output = sense
         action = DeviceAction(agents.N, agents.device, agents.slot, capacity=agents.capacity)
         action.global_slots = agents.global_slots
@@ -308,8 +364,10 @@ class NeuralAutomataAgent(TorchAgent):
         `sense` and `forward` are untouched by all this: never differentiable, same scratch, same launches.
 
         A wide stack (`hidden_channels` / `hidden_activation`) is refused here: NotImplementedError, before any launch and before
-        `dropout_step` moves.  Its gradients come from `ConvolutionModel.forward_device` and `die_amd.functional`."""
+        `dropout_step` moves.  Its gradients come from `ConvolutionModel.forward_device` and `die_amd.functional`.  An agent with
+        the stock channel (`with_stock_channel=True`) is refused the same way: its plane is piecewise constant in the weights."""
         self._check_wide('differentiable_sense')
+        self._check_stock('differentiable_sense')
         layers = self._model.conv_layers()
         for k in layers:
             if k.padding_mode not in ('circular', 'zeros'):
@@ -333,8 +391,9 @@ class NeuralAutomataAgent(TorchAgent):
         The slots' coordinates are copied, so `backward` may run after the world has been stepped.  Where several slots with a
         non-zero gradient stand on one cell their terms are summed by fp32 atomic adds in arrival order; otherwise (alive agents
         never share a cell) the gradients are bit-reproducible run to run.  A wide stack raises NotImplementedError, as in
-        `differentiable_sense`."""
+        `differentiable_sense`, and so does an agent with the stock channel."""
         self._check_wide('differentiable_action')
+        self._check_stock('differentiable_action')
         agents, medium = obs
         sense = self.differentiable_sense(medium)
         self._sense_output = sense.detach()

@@ -88,6 +88,12 @@ class BatchedEnv:
     `replica_dynamics(r)` returns replica r's; `dynamics` keeps the shared fields (those of dynamics[0], with the operator).
     A single `Dynamics` takes the launches it always took."""
 
+    # the R stock planes of a population that senses its agents' stocks (NeuralAutomataAgent(with_stock_channel=True); small
+    # worlds): lazy, and zeroed again whenever the preceding step did not build them (`_stock_planes`)
+    _stock = None
+    _serial = 0                                     # steps and resets of any kind so far
+    _stock_serial = -1                              # `_serial` right after the last step that built the stock planes
+
     def __init__(self, field_size: Tuple[int, int], dynamics: Union[Dynamics, Sequence[Dynamics], None] = None, *, replicas: int, seed: int = 0,
                  field_dtype: torch.dtype = torch.float32, device=None, per_replica: Optional[bool] = None,
                  seeds: Optional[Sequence[int]] = None, max_agents: Union[str, int, None] = 'alive'):
@@ -241,6 +247,7 @@ class BatchedEnv:
         if self._flow_k0 is not None:
             self.dynamics.op_food_flow._k = self._flow_k0
         self._steps = 0
+        self._serial += 1                           # (the stock planes of an earlier step say nothing about the worlds to come)
         self.chem_node = None                       # the worlds start over: an autograd handle of the chem planes ends here
         if seeds is not None:
             self._reseed(seeds, seed, seed_stride)
@@ -288,6 +295,17 @@ class BatchedEnv:
         a = _lib.Agents(self.Nmax, _ptr(self.x), _ptr(self.y), _ptr(self.alive), _ptr(self.agent_food), None)
         return m, a, self._dynamics_struct(self.dynamics), self._batch_struct()
 
+    def _stock_planes(self) -> torch.Tensor:
+        """The (R, W, H) uint64 stock planes a stock-channel population's step builds and reads (die_nca_env_step_batch_stock).
+        Zeroed on allocation, and again unless the step just before this one built them: then every word they hold carries an
+        earlier epoch of the current 1..31 cycle (the library clears them with the claim planes on the wrap).  After anything else
+        — a plain population's step, `step_action`, a reset — a tag of an earlier build could read as occupied, so they start over."""
+        if self._stock is None:
+            self._stock = torch.zeros((self.R, self.W, self.H), dtype=torch.int64, device=self.device)
+        elif self._stock_serial != self._serial:
+            self._stock.zero_()
+        return self._stock
+
     def _batch_struct(self) -> _lib.Batch:
         return _lib.Batch(self.R, 0, self.W * self.H, self.Nmax, 1, (C.c_int64 * 64)(*self.n))
 
@@ -326,7 +344,8 @@ class BatchedEnv:
     def step(self, agent: Union['BatchedPhysarumAgent', 'BatchedPhysarumPopulation', 'BatchedNeuralAutomataAgent'],
              results: Optional[torch.Tensor] = None, action: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One step of every replica: `agent.forward` + `Env.step` fused, two launches for the whole batch (L + 2 for a
-        BatchedNeuralAutomataAgent of L layers; one more with dead slots, one more with a flow; for a BatchedPhysarumPopulation a
+        BatchedNeuralAutomataAgent of L layers, L + 3 when it senses the agents' stocks: the build of the R stock planes this
+        BatchedEnv owns; one more with dead slots, one more with a flow; for a BatchedPhysarumPopulation a
         decode launch first when `parameters` was written since the last one).  Returns the (R, 2) float64 tensor of
         die_step_result words (device; `read_results` decodes).
 
@@ -368,6 +387,9 @@ class BatchedEnv:
             raise
         agent._calls += 1
         agent._stepped()
+        self._serial += 1
+        if getattr(agent, '_stock_channel', False):  # this step built the stock planes: the next one may build on top of them
+            self._stock_serial = self._serial
         if self.dynamics.agents_born:
             self._births(a, b, results)
         self.chem_node = None                       # the field changed: an autograd handle of the chem planes ends here
@@ -420,6 +442,7 @@ class BatchedEnv:
         except Exception:
             self.epoch = epoch                      # refused before any launch: nothing changed
             raise
+        self._serial += 1
         if self.dynamics.agents_born:
             self._births(a, b, results)
         self.chem_node = None                       # (differentiable_step sets this step's node afterwards)
@@ -1007,7 +1030,7 @@ def _architecture(agent: NeuralAutomataAgent) -> dict:
     """What every candidate of a population shares: the stack's shape, its boundary, the observed channels, the action scale."""
     layers = agent.model.conv_layers()
     return dict(kernel_sizes=tuple(int(k.kernel_size[0]) for k in layers), boundary=tuple(k.padding_mode for k in layers),
-                with_agent_channel=len(agent.obs_channels) == 3, scale=agent.action_coefs[0], deposit=agent.action_coefs[2],
+                with_agent_channel='agents' in agent.obs_channels, with_stock_channel=agent.with_stock_channel, scale=agent.action_coefs[0], deposit=agent.action_coefs[2],
                 shapes=tuple(tuple(k.weight.shape) for k in layers), hidden_channels=agent.model.hidden_channels,
                 hidden_activation=agent.model.hidden_activation)
 
@@ -1032,7 +1055,17 @@ class BatchedNeuralAutomataAgent(_Population):
         Stride 0 gives every replica the same mask (common random numbers across candidates).
     `dropout_step` is a public counter: it starts at 0, every `env.step` advances it by one, it may be written (setting it back
     replays the masks), and nothing resets it — not `env.reset()`, not the searchers — so every generation sees new masks.  In
-    eval mode, or with p = 0, nothing is masked and the step is the one without dropout."""
+    eval mode, or with p = 0, nothing is masked and the step is the one without dropout.
+
+    The stock channel (a template built with `with_stock_channel=True`; every candidate then has it, `from_agents` refuses a
+    mixed population): layer 0 reads one plane more, the `agent_food` of the agent standing on each cell.  `env.step` takes
+    die_nca_env_step_batch_stock / die_nca_wide_env_step_batch_stock: one launch more (L + 3), which builds all R stock planes —
+    owned by the BatchedEnv — from the agents as the step finds them; replica r stays the stand-alone run of `replica_agent(r)`,
+    a stock-channel agent, bit for bit.  P grows by the first layer's extra input channel; episodes, agents_die, agents_born,
+    max_agents, flows, per-replica Dynamics, dropout_seed, `action=` and both searchers take it as they are, and large worlds
+    (`per_replica`) go through the stand-alone agents.  Refused with NotImplementedError before any launch and before
+    `dropout_step` moves: `differentiable_sense`, `differentiable_action` and `forward_device` (so no action with a graph
+    through such a population ever reaches `env.differentiable_step`)."""
 
     def __init__(self, env: BatchedEnv, template: NeuralAutomataAgent, parameters=None, episodes: int = 1, *,
                  dropout_seed: Optional[int] = None, dropout_seed_stride: int = 1):
@@ -1050,6 +1083,7 @@ class BatchedNeuralAutomataAgent(_Population):
         self.env, self.template, self.R = env, template, env.R
         self._arch = _architecture(template)
         self._wide = template.model.wide            # hidden_channels / hidden_activation: die_nca_wide_env_step_batch
+        self._stock_channel = template.with_stock_channel      # the *_stock entry points: one launch more, layer 0 one plane more
         template._check_wide()
         layers = template.model.conv_layers()
         for k in layers:
@@ -1173,6 +1207,12 @@ class BatchedNeuralAutomataAgent(_Population):
         """BatchedPhysarumAgent._launch with the dropout mask of the coming step after the workspace: one entry point without
         it, one with it (the same step, its last conv launch masked), and with Dynamics rows one for both, the mask nullable."""
         drop = self._dropout()
+        if self._stock_channel:                     # the mask and the two tables nullable, the env's stock planes after them
+            name = 'die_nca_wide_env_step_batch_stock' if self._wide else 'die_nca_env_step_batch_stock'
+            _lib.check(getattr(_lib.lib, name)(*front, C.byref(self._struct(self._sense_epoch)), *back,
+                                               None if drop is None else C.byref(drop), *(rows or (None, None)),
+                                               _ptr(self.env._stock_planes()), stream), name)
+            return
         if self._wide:                              # one entry point: the mask and the two tables are all nullable
             _lib.check(_lib.lib.die_nca_wide_env_step_batch(*front, C.byref(self._struct(self._sense_epoch)), *back,
                                                             None if drop is None else C.byref(drop), *(rows or (None, None)), stream),
@@ -1204,6 +1244,7 @@ class BatchedNeuralAutomataAgent(_Population):
         """Every refusal of a differentiable call, before anything is launched; returns the matrix the call reads."""
         env = self.env
         self.template._check_wide('differentiable mode')
+        self.template._check_stock('differentiable mode')
         if env.per_replica:
             raise NotImplementedError('differentiable mode: large worlds (per_replica) are not batched — a large world fills the GPU '
                                       'through the stand-alone NeuralAutomataAgent.differentiable_action (replica_agent(r))')
@@ -1239,7 +1280,9 @@ class BatchedNeuralAutomataAgent(_Population):
         call whenever a `dropout_seed` is set.  Small worlds, 'circular' / 'zeros' boundaries; anything else raises
         NotImplementedError before any launch.  `step()` is untouched by all this.  A population of wide stacks
         (`hidden_channels` / `hidden_activation`) is refused here: NotImplementedError too, before any launch and before
-        `dropout_step` moves.  Its gradients come from `forward_device` and `die_amd.functional.gather_scale_batch`."""
+        `dropout_step` moves.  Its gradients come from `forward_device` and `die_amd.functional.gather_scale_batch`.  A
+        population with the stock channel (`with_stock_channel=True`) is refused the same way, here, in `differentiable_action`
+        and in `forward_device`: the stock plane is piecewise constant in the weights and the adjoint calls do not take its kind."""
         p = self._check_differentiable(parameters)
         out = _BatchedSense.apply(self, p, self.env.chem_node)
         if self.dropout_seed is not None:
@@ -1271,8 +1314,9 @@ class BatchedNeuralAutomataAgent(_Population):
         first layer's inputs are copied, so `backward` may run after `env.step`.  With a `dropout_seed`, in training mode and
         p > 0, replica r is masked with key `dropout_seed + r·dropout_seed_stride` at `dropout_step`; the counter advances once per
         call whenever a `dropout_seed` is set.  Refused before any launch and before `dropout_step` moves: a narrow population
-        (ValueError: it has `differentiable_sense`), large worlds (`per_replica`) and 'reflect' / 'replicate' boundaries
-        (NotImplementedError)."""
+        (ValueError: it has `differentiable_sense`), a population with the stock channel, large worlds (`per_replica`) and
+        'reflect' / 'replicate' boundaries (NotImplementedError)."""
+        self.template._check_stock('forward_device')
         if not self._wide:
             raise ValueError('forward_device: a narrow population (hidden_channels and hidden_activation both None) is differentiated '
                              'by differentiable_sense')

@@ -1549,25 +1549,32 @@ extern "C" int die_env_step_batch_rows(const die_medium* m, const die_agents* a,
     return env_step_batch(m, a, act, d, b, results, ws, ws_bytes, true, rows, rows_host, stream, "die_env_step_batch_rows");
 }
 
-int die_nca_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who);       // die_nca.hip
+int die_nca_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool stock);       // die_nca.hip
 int die_dropout_words(const die_nca_dropout* drop, DropWords* out, const char* who);                                 // die_nca.hip
 int die_nca_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
-                        const DropWords* drop, void* stream);
-int die_nca_wide_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who);  // die_nca_wide.hip
+                        const DropWords* drop, void* stream, const unsigned long long* stock);
+int die_nca_wide_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool stock);  // die_nca_wide.hip
 int die_nca_wide_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
-                             const DropWords* drop, void* stream);
+                             const DropWords* drop, void* stream, const unsigned long long* stock);
+int die_stock_launch(const die_medium* m, const die_agents* a, int32_t replicas, const int64_t* n, int64_t agent_stride,
+                     int64_t plane_stride, int32_t epoch, unsigned long long* planes, void* stream, const char* who);  // die_stock.hip
 
 // die_nca_env_step_batch (drop null) and die_nca_env_step_batch_dropout: one body; the mask only changes the last conv launch.
 // `wide` (die_nca_wide_env_step_batch): the stack's check and its sensing are die_nca_wide.hip's, which hand back the same
-// (sense pointer, replica stride); everything after the sensing is shared
+// (sense pointer, replica stride); everything after the sensing is shared.
+// `stock` (die_nca_env_step_batch_stock / die_nca_wide_env_step_batch_stock; null: the call without it): the R stock planes of
+// die_stock.hip.  Layer 0 then reads one plane more; after every check the planes are built at sense_epoch (one launch more,
+// L + 3 in all), layer 0 reads them as its last input, and on the epoch wrap they are cleared with the claim planes.
 static int nca_env_step_batch(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
                               const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws, int64_t ws_bytes,
                               const die_nca_dropout* drop, void* stream, const char* who, bool with_rows = false,
-                              const die_dynamics_row* rows = nullptr, const die_dynamics_row* rows_host = nullptr, bool wide = false) {
+                              const die_dynamics_row* rows = nullptr, const die_dynamics_row* rows_host = nullptr, bool wide = false,
+                              unsigned long long* stock = nullptr) {
     DIE_REQUIRE(m && a && nca && d && b && results && ws, "%s: null argument", who);
     int rc = batch_world_check(m, a, d, b, ws_bytes, true, who);
     if (rc != DIE_OK) return rc;
-    rc = wide ? die_nca_wide_batch_check(nca, m->W, m->H, b->replicas, who) : die_nca_batch_check(nca, m->W, m->H, b->replicas, who);
+    rc = wide ? die_nca_wide_batch_check(nca, m->W, m->H, b->replicas, who, stock != nullptr)
+              : die_nca_batch_check(nca, m->W, m->H, b->replicas, who, stock != nullptr);
     if (rc != DIE_OK) return rc;
     DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX && m->epoch == nca->sense_epoch % DIE_OWNER_EPOCH_MAX + 1,
                 "%s: claims at epoch %d cannot follow sensing at epoch %d", who, m->epoch, nca->sense_epoch);
@@ -1583,12 +1590,21 @@ static int nca_env_step_batch(const die_medium* m, const die_agents* a, const di
     rc = batch_rows_check(with_rows, b, rows, rows_host, who);
     if (rc != DIE_OK) return rc;
     NcaReadArgs q;
-    rc = (wide ? die_nca_wide_sense_batch : die_nca_sense_batch)(m, b, nca, &q.sense, &q.rep, drop ? &dw : nullptr, stream);   // reads the claim plane at sense_epoch …
+    if (stock) {                                                      // every replica's stocks as they are now, tagged sense_epoch
+        rc = die_stock_launch(m, a, b->replicas, b->n, b->agent_stride, b->plane_stride, nca->sense_epoch, stock, stream, who);
+        if (rc != DIE_OK) return rc;
+    }
+    rc = (wide ? die_nca_wide_sense_batch : die_nca_sense_batch)(m, b, nca, &q.sense, &q.rep, drop ? &dw : nullptr, stream, stock);   // reads the claim plane at sense_epoch …
     if (rc != DIE_OK) return rc;
     if (nca->sense_epoch == DIE_OWNER_EPOCH_MAX) {                    // … which is cleared before the tag 1 claims
         const int64_t words = (int64_t)(b->replicas - 1) * b->plane_stride + (int64_t)m->W * m->H;
         if (hipMemsetAsync(m->owner, 0, (size_t)words * sizeof(unsigned long long), L.s) != hipSuccess) {
             die_set_error("%s: clearing the claim planes failed", who);
+            return DIE_ERR_HIP;
+        }
+        // (the stock planes start their 1..31 cycle over with them: the next build is tagged 1)
+        if (stock && hipMemsetAsync(stock, 0, (size_t)words * sizeof(unsigned long long), L.s) != hipSuccess) {
+            die_set_error("%s: clearing the stock planes failed", who);
             return DIE_ERR_HIP;
         }
     }
@@ -1618,6 +1634,25 @@ extern "C" int die_nca_wide_env_step_batch(const die_medium* m, const die_agents
                                            const die_dynamics_row* rows_host, void* stream) {
     return nca_env_step_batch(m, a, nca, act, d, b, results, ws, ws_bytes, drop, stream, "die_nca_wide_env_step_batch", rows || rows_host,
                               rows, rows_host, true);
+}
+
+// stock null: the parent call itself, under its own name
+extern "C" int die_nca_env_step_batch_stock(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
+                                            const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws,
+                                            int64_t ws_bytes, const die_nca_dropout* drop, const die_dynamics_row* rows,
+                                            const die_dynamics_row* rows_host, unsigned long long* stock, void* stream) {
+    if (!stock) return die_nca_env_step_batch_rows(m, a, nca, act, d, b, results, ws, ws_bytes, drop, rows, rows_host, stream);
+    return nca_env_step_batch(m, a, nca, act, d, b, results, ws, ws_bytes, drop, stream, "die_nca_env_step_batch_stock", rows || rows_host, rows,
+                              rows_host, false, stock);
+}
+
+extern "C" int die_nca_wide_env_step_batch_stock(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
+                                                 const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws,
+                                                 int64_t ws_bytes, const die_nca_dropout* drop, const die_dynamics_row* rows,
+                                                 const die_dynamics_row* rows_host, unsigned long long* stock, void* stream) {
+    if (!stock) return die_nca_wide_env_step_batch(m, a, nca, act, d, b, results, ws, ws_bytes, drop, rows, rows_host, stream);
+    return nca_env_step_batch(m, a, nca, act, d, b, results, ws, ws_bytes, drop, stream, "die_nca_wide_env_step_batch_stock",
+                              rows || rows_host, rows, rows_host, true, stock);
 }
 
 extern "C" int die_nca_env_step_batch(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,

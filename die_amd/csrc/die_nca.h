@@ -29,7 +29,10 @@ __device__ __forceinline__ int nca_pad_index(int v, int n, int mode) {
 __device__ __forceinline__ float nca_load(const void* p, int kind, int64_t i, int epoch) {
     if (kind == DIE_PLANE_F32) return ((const float*)p)[i];
     if (kind == DIE_PLANE_F16) return __half2float(((const __half*)p)[i]);
-    return die_claim_occupied(((const unsigned long long*)p)[i], epoch) ? 1.f : 0.f;
+    const unsigned long long word = ((const unsigned long long*)p)[i];
+    // DIE_PLANE_STOCK (die_stock.hip): the claim plane's word with the standing agent's stock as its payload
+    if (kind == DIE_PLANE_STOCK) return die_claim_occupied(word, epoch) ? die_claim_deposit(word) : 0.f;
+    return die_claim_occupied(word, epoch) ? 1.f : 0.f;
 }
 
 // die_nca_dropout, checked, as the words the kernels read (die_nca.hip)

@@ -7,7 +7,8 @@
 //                     x).  A workgroup stages the (16 + 2r) × (64 + 2r) input tile of every input channel in LDS and the
 //                     layer's weights next to it; a thread produces 4 consecutive y of every output channel (16-byte
 //                     stores).  The first layer reads the medium's own planes: fp32 / fp16 fields, and the 'agents'
-//                     channel straight from the claim plane (occupied ⇔ epoch tag).  The last layer applies tanh.
+//                     channel straight from the claim plane (occupied ⇔ epoch tag) — and, for an agent that senses its own
+//                     stock, the stock plane of die_stock.hip (DIE_PLANE_STOCK: occupied ? payload : 0).  The last layer applies tanh.
 //   k_gather_scale    action[c, n] = plane[c][cell(x_n), cell(y_n)] · coef[c] for EVERY slot (only_alive = False).
 //                     k_gather_scale_batch (die_gather_scale_batch, replica in blockIdx.y) calls the same gather_scale_one.
 //   die_nca_env_step_batch (a population of candidates on batched replicas) runs k_conv_circular<K, true>: the same body
@@ -196,7 +197,9 @@ static int conv2d(int32_t W, int32_t H, int32_t cin, const die_conv_plane* in, i
         a.in[c] = c < cin ? in[c].data : nullptr;
         a.kind[c] = c < cin ? in[c].kind : 0;
         a.out[c] = c < cout ? out[c] : nullptr;
-        DIE_REQUIRE(c >= cin || (in[c].data && in[c].kind >= DIE_PLANE_F32 && in[c].kind <= DIE_PLANE_AGENTS), "die_conv2d_circular: bad input plane %d", c);
+        // (a stock plane is the observation's LAST channel, DESIGN §6: kind 3 anywhere else is a plane of no kind, as it always was)
+        DIE_REQUIRE(c >= cin || (in[c].data && in[c].kind >= DIE_PLANE_F32 && in[c].kind <= (c == cin - 1 ? DIE_PLANE_STOCK : DIE_PLANE_AGENTS)),
+                    "die_conv2d_circular: bad input plane %d", c);
         DIE_REQUIRE(c >= cout || out[c], "die_conv2d_circular: null output plane %d", c);
         for (int q = 0; q < cout && c < cin; ++q) DIE_REQUIRE((const void*)out[q] != in[c].data, "die_conv2d_circular: in-place convolution");
     }
@@ -357,7 +360,8 @@ extern "C" int64_t die_nca_batch_scratch_bytes(int32_t W, int32_t H, int32_t rep
 
 // every argument of the stack, before anything is launched
 // (scratch: the ping-pong planes of the step; the calls that write into caller-owned storage check their own)
-static int nca_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool scratch) {
+// (stock: layer 0 reads one plane more, the stock plane of die_stock.hip as its last input)
+static int nca_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool scratch, bool stock = false) {
     if (scratch) DIE_REQUIRE(nca && nca->layers && nca->scratch, "%s: null stack, layer list or scratch", who);
     else DIE_REQUIRE(nca && nca->layers, "%s: null stack or layer list", who);
     DIE_REQUIRE(nca->n_layers >= 1 && nca->n_layers <= DIE_NCA_MAX_LAYERS, "%s: 1..%d layers (got %d)", who, DIE_NCA_MAX_LAYERS, nca->n_layers);
@@ -368,7 +372,7 @@ static int nca_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32
     const int64_t need = die_nca_batch_scratch_bytes(W, H, replicas, nca->n_layers);
     DIE_REQUIRE(need > 0, "%s: bad size %dx%d or replicas %d outside 1..%d", who, W, H, replicas, DIE_MAX_REPLICAS);
     if (scratch) DIE_REQUIRE(nca->scratch_bytes >= need, "%s: scratch too small (%lld < %lld)", who, (long long)nca->scratch_bytes, (long long)need);
-    int cin = 2 + nca->with_agent_channel;
+    int cin = 2 + nca->with_agent_channel + (stock ? 1 : 0);
     for (int l = 0; l < nca->n_layers; ++l) {
         const die_nca_layer& L = nca->layers[l];
         if (!(L.k == 1 || L.k == 3 || L.k == 5 || L.k == 7)) {
@@ -387,8 +391,8 @@ static int nca_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32
     return DIE_OK;
 }
 
-int die_nca_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who) {
-    return nca_stack_check(nca, W, H, replicas, who, true);
+int die_nca_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool stock) {
+    return nca_stack_check(nca, W, H, replicas, who, true, stock);
 }
 int die_nca_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who) {
     return nca_stack_check(nca, W, H, replicas, who, false);
@@ -397,8 +401,9 @@ int die_nca_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t 
 // the stack for every replica, one launch per layer.  Layer l writes `dst` + set(l) · R · rep planes: set(l) = l % 2 for the
 // step's ping-pong scratch, l for caller-owned storage that keeps every layer.  `drop` (checked words, or null): the last layer's
 // launch is the DROP one — into `masked` when given (the unmasked launch then runs as well and keeps its place), else in place of it.
+// `stock` (or null): the R stock planes of die_stock.hip, b->plane_stride apart, built at sense_epoch — layer 0's last input.
 static int sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* dst, bool pingpong, float* masked,
-                       const float** sense, int64_t* rep, const DropWords* drop, void* stream) {
+                       const float** sense, int64_t* rep, const DropWords* drop, void* stream, const unsigned long long* stock = nullptr) {
     const int64_t cells = (int64_t)m->W * m->H, rep_scratch = NCA_MAXC * cells;
     const int fkind = m->dtype == DIE_F32 ? DIE_PLANE_F32 : DIE_PLANE_F16;
     ConvArgs a = {};
@@ -406,6 +411,7 @@ static int sense_batch(const die_medium* m, const die_batch* b, const die_nca_ba
     if (nca->with_agent_channel) { a.in[c] = m->owner; a.kind[c++] = DIE_PLANE_AGENTS; }
     a.in[c] = m->food; a.kind[c++] = fkind;
     a.in[c] = m->chem; a.kind[c++] = fkind;
+    if (stock) { a.in[c] = stock; a.kind[c++] = DIE_PLANE_STOCK; }
     a.rep_in = b->plane_stride;
     a.W = m->W; a.H = m->H; a.epoch = nca->sense_epoch; a.pad = nca->padding_mode;
     a.episodes = nca->episodes > 1 ? nca->episodes : 1;
@@ -434,8 +440,8 @@ static int sense_batch(const die_medium* m, const die_batch* b, const die_nca_ba
 
 // *sense = the last layer's planes of replica 0 in the step's scratch, replica r's *rep further
 int die_nca_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
-                        const DropWords* drop, void* stream) {
-    return sense_batch(m, b, nca, nca->scratch, true, nullptr, sense, rep, drop, stream);
+                        const DropWords* drop, void* stream, const unsigned long long* stock) {
+    return sense_batch(m, b, nca, nca->scratch, true, nullptr, sense, rep, drop, stream, stock);
 }
 
 extern "C" int64_t die_nca_sense_batch_store_bytes(int32_t W, int32_t H, int32_t replicas, int32_t n_layers) {

@@ -232,7 +232,9 @@ extern "C" int die_conv2d_wide(int32_t W, int32_t H, int32_t cin, const die_conv
     WideArgs a = {};
     const char *o0 = (const char*)out, *o1 = (const char*)(out + (int64_t)(cout - 1) * out_stride + cells);
     for (int c = 0; c < cin; ++c) {
-        DIE_REQUIRE(in[c].data && in[c].kind >= DIE_PLANE_F32 && in[c].kind <= DIE_PLANE_AGENTS, "%s: bad input plane %d", who, c);
+        // (a stock plane is the observation's LAST channel, DESIGN §6: kind 3 anywhere else is a plane of no kind, as it always was)
+        DIE_REQUIRE(in[c].data && in[c].kind >= DIE_PLANE_F32 && in[c].kind <= (c == cin - 1 ? DIE_PLANE_STOCK : DIE_PLANE_AGENTS),
+                    "%s: bad input plane %d", who, c);
         const int64_t bytes = cells * (in[c].kind == DIE_PLANE_F32 ? 4 : in[c].kind == DIE_PLANE_F16 ? 2 : 8);
         const char* p = (const char*)in[c].data;
         DIE_REQUIRE(p + bytes <= o0 || p >= o1, "%s: in-place convolution (input plane %d lies in the output planes)", who, c);
@@ -271,7 +273,8 @@ static int wide_max_channels(const die_nca_batch* nca) {
 
 // every argument of the stack, before anything is launched
 // (scratch: the ping-pong planes of the step; the calls that keep every layer in caller-owned storage check their own)
-static int wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool scratch) {
+// (stock: layer 0 reads one plane more, the stock plane of die_stock.hip as its last input)
+static int wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool scratch, bool stock = false) {
     if (scratch) DIE_REQUIRE(nca && nca->layers && nca->scratch, "%s: null stack, layer list or scratch", who);
     else DIE_REQUIRE(nca && nca->layers, "%s: null stack or layer list", who);
     DIE_REQUIRE(nca->n_layers >= 1 && nca->n_layers <= DIE_NCA_MAX_LAYERS, "%s: 1..%d layers (got %d)", who, DIE_NCA_MAX_LAYERS, nca->n_layers);
@@ -282,7 +285,7 @@ static int wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int3
     DIE_REQUIRE(W >= 1 && H >= 1 && replicas >= 1 && replicas <= DIE_MAX_REPLICAS, "%s: bad size %dx%d or replicas %d outside 1..%d", who,
                 W, H, replicas, DIE_MAX_REPLICAS);
     DIE_REQUIRE((W + NCA_TX - 1) / NCA_TX <= 65535, "%s: field too tall", who);
-    int cin = 2 + nca->with_agent_channel;
+    int cin = 2 + nca->with_agent_channel + (stock ? 1 : 0);
     for (int l = 0; l < nca->n_layers; ++l) {
         const die_nca_layer& L = nca->layers[l];
         const bool last = l == nca->n_layers - 1;
@@ -304,8 +307,8 @@ static int wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int3
     return DIE_OK;
 }
 
-int die_nca_wide_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who) {
-    return wide_stack_check(nca, W, H, replicas, who, true);
+int die_nca_wide_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool stock) {
+    return wide_stack_check(nca, W, H, replicas, who, true, stock);
 }
 int die_nca_wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who) {
     return wide_stack_check(nca, W, H, replicas, who, false);
@@ -316,8 +319,9 @@ int die_nca_wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int
 // launch is the masked one — into `masked` when given (the unmasked launch then runs as well and keeps its place), else in place
 // of it.  *sense = the last layer's planes of replica 0, replica r's *rep further (what die_nca_sense_batch returns for a narrow
 // stack: k_nca_move_claim_batch reads either)
+// `stock` (or null): the R stock planes of die_stock.hip, b->plane_stride apart, built at sense_epoch — layer 0's last input
 static int wide_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* dst, bool pingpong, float* masked,
-                            const float** sense, int64_t* rep, const DropWords* drop, void* stream) {
+                            const float** sense, int64_t* rep, const DropWords* drop, void* stream, const unsigned long long* stock = nullptr) {
     const int64_t cells = (int64_t)m->W * m->H, rep_scratch = wide_max_channels(nca) * cells;
     const int fkind = m->dtype == DIE_F32 ? DIE_PLANE_F32 : DIE_PLANE_F16;
     WideArgs a = {};
@@ -325,6 +329,7 @@ static int wide_sense_batch(const die_medium* m, const die_batch* b, const die_n
     if (nca->with_agent_channel) { a.in[c] = m->owner; a.kind[c++] = DIE_PLANE_AGENTS; }
     a.in[c] = m->food; a.kind[c++] = fkind;
     a.in[c] = m->chem; a.kind[c++] = fkind;
+    if (stock) { a.in[c] = stock; a.kind[c++] = DIE_PLANE_STOCK; }
     a.rep_in = b->plane_stride;
     a.W = m->W; a.H = m->H; a.epoch = nca->sense_epoch; a.pad = nca->padding_mode;
     a.episodes = nca->episodes > 1 ? nca->episodes : 1;
@@ -356,8 +361,8 @@ static int wide_sense_batch(const die_medium* m, const die_batch* b, const die_n
 }
 
 int die_nca_wide_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
-                             const DropWords* drop, void* stream) {
-    return wide_sense_batch(m, b, nca, nca->scratch, true, nullptr, sense, rep, drop, stream);
+                             const DropWords* drop, void* stream, const unsigned long long* stock) {
+    return wide_sense_batch(m, b, nca, nca->scratch, true, nullptr, sense, rep, drop, stream, stock);
 }
 
 // ---- the same launches into storage that keeps every layer (the forward of die_nca_wide_backward_batch) -----------------

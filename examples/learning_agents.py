@@ -9,9 +9,16 @@ separable CMA-ES with stdev_init 0.1 and popsize 10 (die_amd.search.CMAES), the 
                                        [--epoch-iters 30] [--agents-die] [--agents-born] [--max-agents alive|full|tight|N]
                                        [--reseed S] [--reseed-stride 0] [--episodes 1] [--out saved_models/agent.pt] [--time]
                                        [--dropout P] [--dropout-seed S] [--dropout-stride K] [--init-from FILE]
+                                       [--stock-channel]
 
 --init-from FILE starts the search from a saved agent (e.g. the one examples/imitate_agent.py fits by gradient descent): its
-`parameters_to_vector` becomes the searcher's `center_init` instead of a centre drawn in initial_bounds.
+`parameters_to_vector` becomes the searcher's `center_init` instead of a centre drawn in initial_bounds.  A file whose agent
+observes another number of channels than this run's (saved without --stock-channel, searched with it, or the other way round)
+is refused with a message naming both counts.
+
+--stock-channel trains agents that sense their own food stock (NeuralAutomataAgent(with_stock_channel=True)): a fourth observation
+channel holding, on every cell, the `agent_food` of the agent standing there, built on the device by one more launch per batched
+step.  With --agents-die / --agents-born that is the quantity that decides whether an agent dies or breeds.
 
 --dropout P trains the agent with the reference's `p_agent_dropout=P` (its learning_agents.py carries 0.25): in every batched step
 replica r's sense planes are multiplied by the counter-based dropout mask of key --dropout-seed + r·--dropout-stride (default
@@ -78,6 +85,16 @@ def make_search(size, choice, popsize, epoch_iters, seed, searcher='pgpe', agent
     else:
         search = PGPE(popsize, pop.P, seed=seed, center_init=center_init, **SEARCH_KW)
     return search.for_population(pop, epoch_iters, reseed=reseed, reseed_stride=reseed_stride), pop
+
+
+def init_from_mismatch(loaded, template, file):
+    """The message that refuses an --init-from agent observing another number of channels than this run's template; None if they agree."""
+    have, want = loaded.obs_channels, template.obs_channels
+    if len(have) == len(want):
+        return None
+    return (f'--init-from {file}: the saved agent observes {len(have)} channels ({", ".join(have)}), this run\'s agents observe '
+            f'{len(want)} ({", ".join(want)}): its weights do not fit' +
+            (' (run with --stock-channel)' if 'agent_food' in have else ' (run without --stock-channel)' if 'agent_food' in want else ''))
 
 
 def host_generation(size, choice, template, mean, sigma, lr, iters, seed, agents_die=False, drop_kw=None):
@@ -186,6 +203,9 @@ def main():
     center_init = None
     if args.init_from is not None:
         loaded = NeuralAutomataAgent.load(args.init_from)
+        mismatch = init_from_mismatch(loaded, make_template(args.dropout, args.wide_kw), args.init_from)
+        if mismatch:
+            sys.exit(mismatch)
         center_init = torch.nn.utils.parameters_to_vector(loaded.model.parameters()).detach()
         print(f'Starting from {args.init_from} ({center_init.numel()} parameters)')
     searcher, pop = make_search(args.size, args.dynamics, args.popsize, args.epoch_iters, args.seed, args.searcher, args.agents_die, N,

@@ -4,7 +4,11 @@ all R worlds stepped together by die_amd.batch (L + 2 launches per step for an L
 
     python examples/population_eval.py [--replicas 10] [--size 96] [--iters 50] [--dynamics st-perlin-wide] [--generations 0] [--agents-die] [--agents-born]
                                        [--max-agents alive|full|tight|N] [--reseed S] [--episodes 1] [--compare]
-                                       [--dropout P] [--dropout-seed S] [--dropout-stride K]
+                                       [--dropout P] [--dropout-seed S] [--dropout-stride K] [--stock-channel]
+
+--stock-channel gives the candidates a fourth observation channel, `'agent_food'`: on every cell the stock of the agent standing
+there (NeuralAutomataAgent(with_stock_channel=True)), built on the device by one more launch per batched step — what lets a policy
+tell a starving agent from a well-fed one under --agents-die / --agents-born.
 
 --dynamics picks one of the reference's three worlds (learning_agents.py `dynamics_choice`): 'st-perlin', 'st-perlin-wide' or
 'dyn-pred', where the food flows in running waves (WaveSequence.get_flow_operator, one more launch per batched step).
@@ -129,11 +133,15 @@ def add_wide_arguments(p):
     p.add_argument('--hidden-channels', type=int, default=None, metavar='C', help='width of the hidden layers, 1..32 (default: the '
                                                                                   'observation\'s 3 channels, the narrow kernels)')
     p.add_argument('--hidden-activation', choices=('tanh', 'relu', 'none'), default='none', help='activation after every layer but the last')
+    p.add_argument('--stock-channel', action='store_true', help="the candidates sense their own food stock: a last observation channel "
+                                                                "'agent_food' (with_stock_channel=True; one more launch per batched step)")
 
 
 def wide_keywords(args):
-    """NeuralAutomataAgent's keywords for --hidden-channels C --hidden-activation A (none when neither is given)."""
+    """NeuralAutomataAgent's keywords for --hidden-channels C --hidden-activation A --stock-channel (none when none is given)."""
     kw = {}
+    if getattr(args, 'stock_channel', False):
+        kw['with_stock_channel'] = True
     if args.hidden_channels is not None:
         kw['hidden_channels'] = args.hidden_channels
     if args.hidden_activation != 'none':

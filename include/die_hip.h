@@ -709,7 +709,12 @@ int die_agents_mark_owner(const die_medium* m, const die_agents* a, void* stream
  * k odd (1, 3, 5, 7), at most 4 channels in and out, weights (cout, cin, k, k) fp32 in device memory; the last layer of the
  * stack applies tanh (:97-99).  Input planes may be the medium's own: fp32 / fp16 fields, or the 'agents' channel read
  * from the claim plane (occupied cells are 1.0; `epoch` = die_medium.epoch).  Outputs are fp32 planes, never an input. */
-typedef enum die_plane_kind { DIE_PLANE_F32 = 0, DIE_PLANE_F16 = 1, DIE_PLANE_AGENTS = 2 } die_plane_kind;
+/* DIE_PLANE_STOCK (die_stock.hip, below): a uint64 plane of die_stock_plane, read as
+ * occupied at `epoch` ? the payload (the standing agent's agent_food) : 0.  The FORWARD layer calls take it (die_conv2d,
+ * die_conv2d_circular, die_conv2d_dropout, die_conv2d_wide) as their LAST input plane, in[cin - 1] — the stock channel is the
+ * observation's last (one stock plane a layer) —; at any other position kind 3 is refused as a plane of no kind, as it always
+ * was, and the adjoint calls refuse it everywhere. */
+typedef enum die_plane_kind { DIE_PLANE_F32 = 0, DIE_PLANE_F16 = 1, DIE_PLANE_AGENTS = 2, DIE_PLANE_STOCK = 3 } die_plane_kind;
 typedef struct die_conv_plane {
     const void* data;
     int32_t kind;            /* die_plane_kind */
@@ -740,7 +745,7 @@ int die_gather_scale(const die_medium* m, const die_agents* a, const float* cons
 #define DIE_NCA_MAX_LAYERS 8
 typedef struct die_nca_layer {
     int32_t k;                   /* odd, 1..7 */
-    int32_t cin, cout;           /* 1..4; layer 0 reads 2 + with_agent_channel planes, the last gives 3 */
+    int32_t cin, cout;           /* 1..4; layer 0 reads 2 + with_agent_channel planes (one more in the *_stock calls), the last gives 3 */
     int32_t reserved;
     const float* weights;        /* device fp32: replica r's (cout, cin, k, k) block starts at weights + r * weight_stride
                                   * (with die_nca_batch.episodes = E > 1: at weights + (r / E) * weight_stride) */
@@ -1027,7 +1032,7 @@ typedef enum die_nca_activation { DIE_NCA_ACT_NONE = 0, DIE_NCA_ACT_TANH = 1, DI
  * `in`: cin planes as die_conv2d reads them (fp32 / fp16 fields, the claim plane at `epoch`); `weights`: (cout, cin, k, k) fp32 on
  * the device; `activation`: a die_nca_activation; `padding_mode`: a die_pad_mode.  Every argument is checked before anything is
  * launched, and all of these are DIE_ERR_ARG: W or H < 1, cin or cout outside 1..32, k other than 1, 3, 5, 'reflect' padding of a
- * field no larger than k / 2, an unknown activation or padding mode, a null pointer, an input plane that is not one of the three
+ * field no larger than k / 2, an unknown activation or padding mode, a null pointer, an input plane that is not one of the four
  * kinds, out_stride below a plane, an input plane that overlaps the output planes (in-place), a bad `drop` (die_nca_dropout's
  * rules).  Where H % 4 == 0, `out` is 16-byte aligned and out_stride a multiple of 4, the stores are 16 bytes wide. */
 int die_conv2d_wide(int32_t W, int32_t H, int32_t cin, const die_conv_plane* in, int32_t epoch, int32_t cout, float* out,
@@ -1075,6 +1080,45 @@ int die_nca_wide_env_step_batch(const die_medium* m, const die_agents* a, const 
                                 const die_dynamics* d, const die_batch* b, die_step_result* results, void* workspace,
                                 int64_t workspace_bytes, const die_nca_dropout* drop, const die_dynamics_row* rows,
                                 const die_dynamics_row* rows_host, void* stream);
+
+/* ---- The stock channel: agents sense their own agent_food (die_stock.hip; NeuralAutomataAgent(with_stock_channel=True)) ------
+ * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
+ * A stock plane is a W * H plane of uint64 words in the claim plane's format, the stock in place of the deposit:
+ *   word = ((epoch << DIE_OWNER_EPOCH_SHIFT | slot id + 1) << 32) | float bits of agent_food.
+ * die_stock_plane takes the agents as they are and, for every ALIVE slot in ascending slot id, sets the word of the cell it
+ * stands on (the nearest label, as every cell lookup here): where several alive agents share a cell the highest slot id wins
+ * (numpy's last writer, the deposit claim's rule), dead slots contribute nothing, negative and denormal stocks keep their bits.
+ * One launch, one thread per slot, one 64-bit atomicMax per alive slot with slot id `agents->slot ? slot[n] : n`: no float
+ * atomics, the result does not depend on the storage order and is the same on every run.
+ *   The call does NOT clear.  `plane` must be zero, or hold only words tagged with earlier epochs of the same 1..31 cycle (they
+ * lose against this build's words and read as empty afterwards); a word of the same or a later epoch would survive and read as
+ * an agent that is not there.  Whoever owns the plane zeroes it when the epoch does not grow (NeuralAutomataAgent, BatchedEnv).
+ *   A layer call reads the plane as DIE_PLANE_STOCK with the call's one `epoch`: occupied ? payload : 0.f, fp32 whatever the field
+ * dtype.
+ * Checked before the launch: a null pointer (m, agents, plane, or one of x, y, alive, agent_food), W or H < 1, a decomposed
+ * medium (m->gW > 0: DIE_ERR_UNSUPPORTED), epoch outside 1..DIE_OWNER_EPOCH_MAX, more slots than a claim word can name. */
+int die_stock_plane(const die_medium* m, const die_agents* agents, int32_t epoch, unsigned long long* plane, void* stream);
+/* R planes in ONE launch (the replica in blockIdx.y): replica r's slots start at r * b->agent_stride, its plane at
+ * planes + r * b->plane_stride; the padding slots n >= b->n[r] are skipped.  Checked as die_stock_plane, and: a null batch,
+ * replicas outside 1..DIE_MAX_REPLICAS, plane_stride below a plane, agent_stride < 1, n[r] outside 0..agent_stride. */
+int die_stock_plane_batch(const die_medium* m, const die_agents* agents, const die_batch* b, int32_t epoch,
+                          unsigned long long* planes, void* stream);
+/* die_nca_env_step_batch_rows / die_nca_wide_env_step_batch for a population that senses its stock.  `stock`: R stock planes,
+ * b->plane_stride apart.  stock == NULL: the parent call itself.  Otherwise, in order: the parent's checks in the parent's order
+ * with layer 0 reading 2 + with_agent_channel + 1 planes (`drop` nullable; `rows` and `rows_host` nullable, both or neither, for
+ * the narrow stack as well); the stock build at nca->sense_epoch from the agents as the call finds them; the parent's launches
+ * with the stock plane as layer 0's LAST input: L + 3 launches per step.  Where the parent clears the claim planes (sense_epoch ==
+ * DIE_OWNER_EPOCH_MAX) the stock planes are cleared with them.  The planes must satisfy die_stock_plane's rule on entry:
+ * consecutive calls on the same planes do by themselves; after anything else the caller zeroes them.  A narrow stack stays
+ * within 4 channels (4 -> 4 hidden layers; the scratch holds 4 planes per replica already). */
+int die_nca_env_step_batch_stock(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
+                                 const die_dynamics* d, const die_batch* b, die_step_result* results, void* workspace,
+                                 int64_t workspace_bytes, const die_nca_dropout* drop, const die_dynamics_row* rows,
+                                 const die_dynamics_row* rows_host, unsigned long long* stock, void* stream);
+int die_nca_wide_env_step_batch_stock(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
+                                      const die_dynamics* d, const die_batch* b, die_step_result* results, void* workspace,
+                                      int64_t workspace_bytes, const die_nca_dropout* drop, const die_dynamics_row* rows,
+                                      const die_dynamics_row* rows_host, unsigned long long* stock, void* stream);
 
 /* ---- The wide stack's adjoint for every replica of a die_batch (BatchedNeuralAutomataAgent.forward_device) -----------------
  * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
