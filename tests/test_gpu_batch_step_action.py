@@ -50,7 +50,7 @@ def build(case, per_replica=False):
     op = _wave(W, H) if case.get('flow') else None
     benv = BatchedEnv((W, H), make_dynamics(case, W, H, R, op), replicas=R, seed=case.get('seed', 3), field_dtype=dt, per_replica=per_replica,
                       max_agents=slots)
-    assert benv.per_replica == per_replica
+    assert per_replica is None or benv.per_replica == per_replica      # (None: the regime BatchedEnv picks by the world's size)
     twins = []
     for r in range(R):
         d = make_dynamics(case, W, H, R, _wave(W, H) if case.get('flow') else None)      # (a fresh operator at the same counter)
@@ -97,16 +97,17 @@ def host_winners(env, action, W, H):
     return deposit_cells(cx, cy, alive, None, H), cx * H + cy, alive > 0
 
 
-def run_twins(case, benv, twins, actions):
+def run_twins(case, benv, twins, actions, winners=None):
     """The stand-alone runs: per replica the result words of every step, the state after every step (device tensors), and whether
-    the drawn actions made alive slots share a cell and lose it."""
+    the drawn actions made alive slots share a cell and lose it.  `winners`: host_winners, or a faster twin of it (millions of
+    slots: tests/test_gpu_batch_midsize.py)."""
     W, H = case['shape']
     want, shared = [], []
     for r, env in enumerate(twins):
         k, seen, rows = benv.n[r], False, []
         for t in range(actions.shape[0]):
             a = actions[t, :, r, :k]
-            cells, where, alive = host_winners(env, a, W, H)
+            cells, where, alive = (winners or host_winners)(env, a, W, H)
             losers = alive & (cells < 0)
             seen |= bool(losers.any()) and len(set(where[alive])) < int(alive.sum())
             act = DeviceAction(k, env.device)

@@ -1,4 +1,5 @@
-"""Dynamics(agents_born=True) on the device: the entry points against the numpy model (tests/births_model.py) bit for bit, a
+"""Dynamics(agents_born=True) on the device: the entry points against the numpy model (tests/births_model.py) bit for bit (at a
+few slots, and past every grid cap of the three kernels: tests/midsize_shapes.py), a
 stepped Env against the same world stepped without births plus `apply_births()`, batched replicas against their stand-alone Envs
 (NCA narrow and wide, Physarum with headings; across reset(), with episodes, through step_action), one PGPE generation, and the
 refusals."""
@@ -13,6 +14,7 @@ from die_amd import _lib
 from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent, BatchedPhysarumAgent
 from die_amd.search import PGPE
 from tests import births_model as M
+from tests.midsize_shapes import BIRTH_BATCH_NS, BIRTH_NS, BIRTH_PATTERNS
 
 pytestmark = pytest.mark.gpu
 
@@ -90,6 +92,72 @@ def test_entry_point_equals_the_model(n, boundary):
         again = _call(_dev(x, y, alive, food), n, seed, step, boundary, spread, count0)      # the same bits on every run
         assert _same(again, got), (n, name)
         assert got[4] == int(got[2].sum()), (n, name)
+
+
+# Past the grid caps (tests/test_batch_midsize_cpu.py recomputes why each n): 65 537 gives 257 workgroups — the rank pass's sum over
+# the workgroups before it takes a second trip; 131 073 is one chunk past BIRTH_MAX_GROUPS — every workgroup walks two chunks, carrying
+# its running ranks across the barriers, and the last one gets an empty range; 262 145 walks three; 2 097 665 with every second
+# slot a parent has more pairs than the spawn grid has threads.
+@pytest.mark.parametrize('boundary', [M.WRAP, M.LIMIT], ids=['wrap', 'limit'])
+@pytest.mark.parametrize('n', BIRTH_NS)
+def test_entry_point_equals_the_model_past_the_grid_caps(n, boundary):
+    rs = np.random.RandomState(100 + n)
+    spread, seed, step = 0.3, 0x1234567890ABCDEF + n, 17 + n
+    pats = _patterns(n, rs)
+    for name in BIRTH_PATTERNS:
+        alive, food = pats[name]
+        x = rs.randint(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
+        y = rs.randint(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
+        x[alive == 0] = 0; y[alive == 0] = 0
+        count0 = int(alive.sum())
+        wx, wy, wa, wf, born = M.births(x, y, alive, food, world_seed=seed, world_step=step, born_spread=spread, boundary=boundary)
+        assert born > 0, (n, name)
+        if name == 'equal counts' and n == BIRTH_NS[-1]:
+            assert born > 4096 * 256                                   # the spawn loop strides
+        want = (wx, wy, wa, wf, count0 + born)
+        got = _call(_dev(x, y, alive, food), n, seed, step, boundary, spread, count0)
+        assert _same(got, want), (n, name)
+        again = _call(_dev(x, y, alive, food), n, seed, step, boundary, spread, count0)      # the same bits on every run
+        assert _same(again, got), (n, name)
+        assert got[4] == int(got[2].sum()), (n, name)
+
+
+def test_batched_entry_equals_stand_alone_calls_past_the_grid_caps():
+    """One call, stride 131 073: replica 0 walks two chunks a workgroup, replica 1 (65 537 slots) has workgroups without a slot
+    in the same grid, replica 2 fits one workgroup.  Each ends as its stand-alone call; the padding behind n[r] stays."""
+    rs = np.random.RandomState(8)
+    ns, spread, step = BIRTH_BATCH_NS, 0.3, 5
+    stride, R = max(ns), len(ns)
+    seeds = [11, 2 ** 63 + 5, 11]
+    worlds = []
+    for n in ns:
+        alive, food = _patterns(n, rs)['interleaved at random']
+        x = rs.randint(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
+        y = rs.randint(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
+        worlds.append((x, y, alive, food))
+    for boundary in (M.WRAP, M.LIMIT):
+        pad = lambda v, fill: np.r_[v, np.full(stride - len(v), fill, v.dtype)]
+        # (the padding behind n[r] looks like parents AND must stay untouched: only slots < n count)
+        batch = _dev(*[np.stack([pad(w[i], f) for w in worlds]) for i, f in ((0, 77), (1, 77), (2, 1), (3, 9.0))])
+        before = [t.clone() for t in batch]
+        res = torch.zeros((R, 2), dtype=torch.float64, device=DEV)
+        ws = torch.empty(_lib.lib.die_births_workspace_bytes(R, stride), dtype=torch.uint8, device=DEV)
+        a = _lib.Agents(stride, *[t.data_ptr() for t in batch], None)
+        b = _lib.Batch(R, 0, 0, stride, 0, (C.c_int64 * 64)(*ns))
+        p = _lib.Births(0.5, boundary, spread, step, 0)
+        rc = _lib.lib.die_agent_births_batch(C.byref(a), C.byref(b), C.byref(p), (C.c_uint64 * R)(*seeds), res.data_ptr(), ws.data_ptr(),
+                                             ws.numel(), None)
+        assert rc == 0, _lib.lib.die_last_error()
+        torch.cuda.synchronize()
+        counts = res.cpu().view(torch.int64)[:, 1].tolist()
+        for r, n in enumerate(ns):
+            alone = _call(_dev(*worlds[r]), n, seeds[r], step, boundary, spread, 0)
+            got = (batch[0][r, :n].cpu().numpy().view(np.uint32), batch[1][r, :n].cpu().numpy().view(np.uint32),
+                   batch[2][r, :n].cpu().numpy(), batch[3][r, :n].cpu().numpy(), counts[r])
+            assert _same(got, alone), (r, boundary)
+            assert alone[4] > 0
+            for t, t0 in zip(batch, before):
+                assert torch.equal(t[r, n:], t0[r, n:]), r
 
 
 def test_batched_entry_equals_stand_alone_calls():

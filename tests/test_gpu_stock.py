@@ -1,5 +1,5 @@
 """The stock channel on the device (die_stock.hip; NeuralAutomataAgent(with_stock_channel=True)): the plane build against the
-numpy model word for word, rebuilds on one plane, the conv loaders' fourth plane kind, the stand-alone agent, and populations
+numpy model word for word (300 slots, and 2 M slots: more than the grid has threads), rebuilds on one plane, the conv loaders' fourth plane kind, the stand-alone agent, and populations
 whose replica r is, bit for bit, the stand-alone run of a stock-channel agent — across the epoch wrap, interleaved with a plain
 population on one BatchedEnv, and under both searchers."""
 import ctypes as C
@@ -14,6 +14,7 @@ from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent
 from die_amd.device_array import DeviceAgents, stream_ptr
 from die_amd.search import CMAES, PGPE
 from tests import stock_plane_model as M
+from tests.midsize_shapes import STOCK_BATCH_N, STOCK_N, STOCK_PLANE, stock_plane_fast, stock_winners_fast, stock_world
 
 pytestmark = pytest.mark.gpu
 
@@ -128,6 +129,63 @@ def test_stock_planes_of_three_replicas_in_one_launch():
     for r in range(R):
         _assert_plane_is(planes[r, :W * H].reshape(W, H), epoch, W, H, *worlds[r], f'replica {r}')
     assert not planes[:, W * H:].any()
+
+
+def _assert_plane_is_fast(words, epoch, W, H, x, y, alive, food, what):
+    """_assert_plane_is at 2 M slots: the model's winners without its Python loop (tests/test_batch_midsize_cpu.py checks that
+    they are the model's)."""
+    occ, slot, bits, _ = M.decode(words.cpu().numpy().view(np.uint64), epoch)
+    want_occ, want_slot = stock_winners_fast(W, H, x, y, alive)
+    assert np.array_equal(occ, want_occ), what
+    assert np.array_equal(slot, want_slot), what
+    assert np.array_equal(bits, stock_plane_fast(W, H, x, y, alive, food).view(np.uint32)), what
+
+
+def test_stock_plane_past_the_grid_cap():
+    """2 097 665 slots, more than the 8192 x 256 threads of the grid: every thread takes a second slot, and the last 513 slots
+    are reached only by that second trip.  256 x 256 cells for a million alive slots: every cell is shared, the highest slot
+    id must win whichever trip issued it.  Stored shuffled, with a slot array, then in slot order without one."""
+    (W, H), N, epoch = STOCK_PLANE, STOCK_N, 9
+    rs = np.random.RandomState(1)
+    x, y, alive, food = stock_world(W, H, N, rs)
+    assert alive[-513:].any() and alive.sum() > 8 * W * H
+    perm = rs.permutation(N)
+    planes = []
+    for order, with_slots in ((perm, True), (np.arange(N), False)):
+        tx, ty, ta, tf, ts = _upload(x, y, alive, food, order)
+        plane = torch.zeros((W, H), dtype=torch.int64, device=DEV)
+        a = _lib.Agents(N, tx.data_ptr(), ty.data_ptr(), ta.data_ptr(), tf.data_ptr(), ts.data_ptr() if with_slots else None)
+        _lib.check(_lib.lib.die_stock_plane(C.byref(_medium(W, H)), C.byref(a), epoch, plane.data_ptr(), stream_ptr(plane.device)), 'die_stock_plane')
+        _assert_plane_is_fast(plane, epoch, W, H, x, y, alive, food, 'shuffled' if with_slots else 'slot order')
+        planes.append(plane)
+    assert torch.equal(planes[0], planes[1])
+    host = planes[0].cpu().numpy().view(np.uint64)
+    assert (M.decode(host, epoch)[3] == epoch).all()                             # every cell holds a word of this build
+
+
+def test_stock_planes_past_the_grid_cap_two_replicas():
+    """R = 2 in one launch, n = (2 097 665, 300): replica 1's threads beyond its 300 slots idle through both trips, and its
+    plane holds its own 300 slots' words and nothing of replica 0's."""
+    (W, H), n, epoch, R = STOCK_PLANE, STOCK_BATCH_N, 31, 2
+    stride = max(n)
+    rs = np.random.RandomState(2)
+    worlds = [tuple(v[:n[r]] for v in stock_world(W, H, stride, rs)) for r in range(R)]
+    arrays = [np.zeros((R, stride), dtype=t) for t in (np.uint32, np.uint32, np.uint8, np.float32)]
+    for r in range(R):
+        for dst, src in zip(arrays, worlds[r]):
+            dst[r, :n[r]] = src
+        # the padding slots n >= n[r]: alive, well fed and standing on a cell of their own — they must be skipped
+        arrays[0][r, n[r]:], arrays[1][r, n[r]:], arrays[2][r, n[r]:], arrays[3][r, n[r]:] = _label(7, W), _label(33, H), 1, 99.0
+    tx, ty, ta, tf = _i32(arrays[0]), _i32(arrays[1]), _dev(arrays[2], torch.uint8), _dev(arrays[3], torch.float32)
+    planes = torch.zeros((R, W * H), dtype=torch.int64, device=DEV)
+    a = _lib.Agents(stride, tx.data_ptr(), ty.data_ptr(), ta.data_ptr(), tf.data_ptr(), None)
+    b = _lib.Batch(R, 0, W * H, stride, 1, (C.c_int64 * 64)(*n))
+    _lib.check(_lib.lib.die_stock_plane_batch(C.byref(_medium(W, H)), C.byref(a), C.byref(b), epoch, planes.data_ptr(),
+                                              stream_ptr(planes.device)), 'die_stock_plane_batch')
+    for r in range(R):
+        _assert_plane_is_fast(planes[r].reshape(W, H), epoch, W, H, *worlds[r], f'replica {r}')
+    small = M.decode(planes[1].cpu().numpy().view(np.uint64), epoch)
+    assert 0 < small[0].sum() <= worlds[1][2].sum() and small[1].max() < n[1]    # at most 300 words, of slots below 300
 
 
 # ---------------------------------------------------------------------------------------------------- 2. rebuilds
