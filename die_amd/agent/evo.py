@@ -57,7 +57,11 @@ class ConvolutionModel(nn.Module):
       * `hidden_activation` 'tanh' / 'relu' / None: applied after every layer but the last, as a module between the convs (the
         convs' names `kernels.<i>` then skip the activations' indices); the last layer keeps the Tanh and the dropout mask.
     A stack with either one set runs on the device through the wide layer kernel (die_conv2d_wide: kernel sizes 1, 3 and 5, every
-    boundary), also where its widths would fit the narrow one.  Both stay out of `init_params` while None."""
+    boundary), also where its widths would fit the narrow one.  Both stay out of `init_params` while None.
+
+    `memory_channels=M` > 0 (NeuralAutomataAgent(memory_channels=M), which also counts the M planes into `num_obs_channels` and
+    `num_act_channels`): the stack is a wide stack whatever the two arguments above say — a single layer obs -> actions included
+    — and `forward_device` refuses it (no gradients through memory).  Kept out of `init_params` while 0."""
 
     def __init__(self,
                  num_obs_channels: int = 3,
@@ -68,11 +72,14 @@ class ConvolutionModel(nn.Module):
                  requires_grad: bool = True,
                  hidden_channels: Optional[int] = None,
                  hidden_activation: Optional[str] = None,
+                 memory_channels: int = 0,
                  ):
         self._init_params = save_args(self.__init__, locals())
         for name in ('hidden_channels', 'hidden_activation'):
             if self._init_params[name] is None:
                 del self._init_params[name]
+        if not memory_channels:
+            del self._init_params['memory_channels']
         if hidden_channels is not None:
             if isinstance(hidden_channels, bool) or int(hidden_channels) != hidden_channels or \
                     not 1 <= hidden_channels <= _lib.NCA_WIDE_MAX_CHANNELS:
@@ -82,13 +89,17 @@ class ConvolutionModel(nn.Module):
             hidden_channels = int(hidden_channels)
         if hidden_activation not in _lib.NCA_ACTIVATIONS:
             raise ValueError(f"hidden_activation={hidden_activation!r}: 'tanh', 'relu' or None")
-        if hidden_channels is not None or hidden_activation is not None:
+        if hidden_channels is not None or hidden_activation is not None or memory_channels:
             for size in kernel_sizes:
                 if size not in _lib.NCA_WIDE_KERNEL_SIZES:
-                    raise NotImplementedError(f'kernel size {size} in a wide stack (hidden_channels / hidden_activation): one of '
-                                              f'{_lib.NCA_WIDE_KERNEL_SIZES} (32 * 32 * 49 weights do not fit LDS next to a tile)')
+                    raise NotImplementedError(f'kernel size {size} in a wide stack (hidden_channels / hidden_activation / '
+                                              f'memory_channels): one of {_lib.NCA_WIDE_KERNEL_SIZES} (32 * 32 * 49 weights do not fit '
+                                              'LDS next to a tile)')
+        if memory_channels and max(num_obs_channels, num_act_channels) > _lib.NCA_WIDE_MAX_CHANNELS:
+            raise ValueError(f'{num_obs_channels} -> {num_act_channels} channels: at most {_lib.NCA_WIDE_MAX_CHANNELS} a layer')
         super().__init__()
         self.hidden_channels, self.hidden_activation = hidden_channels, hidden_activation
+        self.memory_channels = int(memory_channels)
         depth = len(kernel_sizes)
         width = num_obs_channels if hidden_channels is None else hidden_channels
         stack = nn.Sequential()
@@ -105,8 +116,9 @@ class ConvolutionModel(nn.Module):
 
     @property
     def wide(self) -> bool:
-        """A stack with `hidden_channels` or `hidden_activation` set: every layer goes through the wide entry points."""
-        return self.hidden_channels is not None or self.hidden_activation is not None
+        """A stack with `hidden_channels`, `hidden_activation` or `memory_channels` set: every layer goes through the wide entry
+        points."""
+        return self.hidden_channels is not None or self.hidden_activation is not None or self.memory_channels > 0
 
     def conv_layers(self):
         return [layer for layer in self.kernels if isinstance(layer, nn.Conv2d)]
@@ -131,6 +143,9 @@ class ConvolutionModel(nn.Module):
         'circular' and 'zeros' where a gradient is needed.  A narrow model (neither `hidden_channels` nor `hidden_activation`)
         raises ValueError: it has `NeuralAutomataAgent.differentiable_sense`."""
         from ..functional import conv2d_wide
+        if self.memory_channels:
+            raise NotImplementedError('forward_device: no gradients through memory channels (memory_channels > 0): the read-out into '
+                                      'the memory and the expand onto the field have no adjoint')
         if not self.wide:
             raise ValueError('forward_device: a narrow model (hidden_channels and hidden_activation both None) is differentiated by '
                              'NeuralAutomataAgent.differentiable_sense')
@@ -166,7 +181,34 @@ class NeuralAutomataAgent(TorchAgent):
     stacks, fp16 fields, every boundary, both dropout masks and tile-binned worlds take it.  Refused with the channel on, each
     with NotImplementedError before any launch and before `dropout_step` moves: `differentiable_sense` and
     `differentiable_action` (the plane is piecewise constant in the weights and the adjoint calls do not take its kind), and a
-    decomposed medium (die_amd/dist.py).  Kept out of `init_params` while False, saved and restored by `load` while True."""
+    decomposed medium (die_amd/dist.py).  Kept out of `init_params` while False, saved and restored by `load` while True.
+
+    `memory_channels=M`, 1 <= M <= 8 (no reference counterpart; core/agent/learning.py: "TODO: need joint channels info for the
+    system"; 0 / None: absent, nothing changes): every agent carries M values from one forward to the next.
+      * The stack is a wide stack (die_conv2d_wide: kernel sizes 1, 3, 5; `hidden_channels` None: hidden layers as wide as the
+        observation; a single layer obs -> 3 + M is allowed).  The observation channels are `[agents]`, `env_food`, `chem1`,
+        `memory_0` .. `memory_{M-1}`, `[agent_food]` — the stock plane stays last — and `kernels.0.weight` has that many input
+        channels in that order.  The last layer has 3 + M output channels: rows 0..2 are dx, dy, deposit as ever, rows 3.. the new
+        memory; the last layer's tanh and the dropout mask apply to every one of them (a masked cell yields memory 0).
+        `render()` keeps showing the first three planes.
+      * `memory`: the (M, N) float32 device tensor, indexed by SLOT ID (`agents.slot[i]` where a slot array exists, else the
+        storage index), so it follows an agent through every re-sort.  None until the first `sense` / `forward`, which allocates
+        it as zeros for `agents.N` slots; it may be assigned (a contiguous (M, N) float32 tensor on the medium's device).
+        `reset_memory()` zeroes it and lets the next forward take another N; until then a forward with a different N raises
+        ValueError before any launch.
+      * One `forward(obs)`: the standing plane (die_stock_plane at `medium.epoch`: alive slots only, the highest slot id on a
+        shared cell — the stock channel's own plane, one build for both) is expanded into M fp32 planes `P_j[c] = memory[j][winner
+        of c]`, 0 on empty cells (die_memory_planes); the stack runs; `die_gather_scale` reads planes 0..2 into the action; and
+        die_gather_memory writes `memory[j][slot] = S[3 + j][cell of the slot]` for alive slots, +0 for dead ones (no
+        coefficient; a slot's next occupant starts blank; two agents sharing a cell get the same memory).  `sense(medium, agents)`
+        needs the agents (ValueError before any launch without them) and returns all 3 + M planes; `memory_planes(medium, agents)`
+        gives the M planes the coming forward would sense.
+      * Refused with NotImplementedError before any launch, and before `dropout_step` or `memory` change:
+        `differentiable_sense`, `differentiable_action`, `model.forward_device`, and a decomposed medium (die_amd/dist.py).
+        `Dynamics(agents_born=True)` is refused together with memory too (a slot can die and be refilled within one step, so a
+        newborn would inherit a dead agent's memory) — but a stand-alone agent cannot see the Dynamics, so that refusal sits
+        where the Dynamics is known: the `BatchedNeuralAutomataAgent` constructor.  With a stand-alone `Env` it is the caller's.
+    Kept out of `init_params` while 0, saved and restored by `load` while positive (the memory itself is state, not saved)."""
 
     def __init__(self,
                  scale: float = 0.1,
@@ -175,10 +217,24 @@ class NeuralAutomataAgent(TorchAgent):
                  initial_obs=None,
                  dropout_seed: Optional[int] = None,
                  with_stock_channel: bool = False,
+                 memory_channels: Optional[int] = 0,
                  **model_kwargs,
                  ):
         self._init_params = save_args(self.__init__, locals())
         self._init_params.pop('initial_obs', None)            # an observation is not a constructor parameter worth saving
+        if memory_channels is None:
+            memory_channels = 0
+        if isinstance(memory_channels, (bool, np.bool_)) or not isinstance(memory_channels, (int, float, np.integer, np.floating)) or \
+                int(memory_channels) != memory_channels or not 0 <= memory_channels <= _lib.MEMORY_MAX_CHANNELS:
+            raise ValueError(f'memory_channels={memory_channels!r}: an integer in 1..{_lib.MEMORY_MAX_CHANNELS}, or 0 / None for none')
+        self.memory_channels = int(memory_channels)
+        if self.memory_channels:
+            self._init_params['memory_channels'] = self.memory_channels
+        else:                                                 # (kept out while 0, as with_stock_channel is while False)
+            del self._init_params['memory_channels']
+        self.memory: Optional[th.Tensor] = None                # (M, N) float32 by slot id, from the first forward on
+        self._memory_rebind = True                             # the next forward may allocate for its own N
+        self._memory_planes = {}                               # (W, H, device) -> (M, W, H) float32: the expanded memory
         if not isinstance(with_stock_channel, (bool, np.bool_)):
             raise ValueError(f'with_stock_channel={with_stock_channel!r}: True or False')
         self.with_stock_channel = bool(with_stock_channel)
@@ -193,11 +249,14 @@ class NeuralAutomataAgent(TorchAgent):
         self.dropout_seed = dropout_seed
         self.dropout_step = 0
         self.obs_channels = list(DataChannels.medium) if with_agent_channel else list(DataChannels.medium[1:])
+        self.obs_channels += [f'memory_{j}' for j in range(self.memory_channels)]      # after the field's planes, before the stock's
         if self.with_stock_channel:
             self.obs_channels.append(DataChannels.agents[3])   # 'agent_food': always the LAST observation channel
         self._stock = {}                                       # (W, H, device) -> [uint64 stock plane, epoch of its last build]
-        self._model = ConvolutionModel(num_obs_channels=len(self.obs_channels), num_act_channels=len(DataChannels.actions),
-                                       **model_kwargs)
+        if self.memory_channels:                               # (a model without memory is built exactly as before)
+            model_kwargs = dict(model_kwargs, memory_channels=self.memory_channels)
+        self._model = ConvolutionModel(num_obs_channels=len(self.obs_channels),
+                                       num_act_channels=len(DataChannels.actions) + self.memory_channels, **model_kwargs)
         self.action_coefs = (float(scale), float(scale), float(deposit))
         self._sense_output: Optional[th.Tensor] = None         # (3, W, H) on the device after the first forward
         self._planes = {}                                      # device scratch by (W, H, device): ping-pong plane sets
@@ -266,6 +325,72 @@ class NeuralAutomataAgent(TorchAgent):
             raise NotImplementedError('with_stock_channel=True on a decomposed medium (die_amd/dist.py): the stock plane is built for '
                                       'periodic single-tile planes only')
 
+    def _check_memory(self, what: str = None, medium=None):
+        """The memory channels' refusals, before any launch: (`what`) a differentiable call, (`medium`) a decomposed world."""
+        if not self.memory_channels:
+            return
+        if what is not None:
+            raise NotImplementedError(f'{what}: no gradients through memory channels (memory_channels={self.memory_channels}): the '
+                                      'read-out into the memory and the expand onto the field have no adjoint')
+        if medium is not None and getattr(medium, 'world', None) is not None:
+            raise NotImplementedError(f'memory_channels={self.memory_channels} on a decomposed medium (die_amd/dist.py): the standing '
+                                      'plane is built for periodic single-tile planes only')
+
+    def reset_memory(self) -> None:
+        """Blank memory: zero it where it is, and let the next forward allocate anew if its agents have another N."""
+        if self.memory is not None:
+            self.memory.zero_()
+        self._memory_rebind = True
+
+    def _check_memory_slots(self, medium, agents) -> None:
+        """What `sense` needs of the agents and of `memory`, before any launch and before anything is allocated."""
+        M = self.memory_channels
+        if agents is None:
+            raise ValueError(f'sense(medium, agents): memory_channels={M} needs the agents whose memory the planes show')
+        if getattr(agents, 'global_slots', False):
+            raise NotImplementedError(f'memory_channels={M} on a decomposed world (die_amd/dist.py): its slots carry world ids')
+        mem = self.memory
+        if mem is None:
+            return
+        if not isinstance(mem, th.Tensor) or mem.dim() != 2 or mem.shape[0] != M or mem.dtype != th.float32 or not mem.is_contiguous() \
+                or mem.device != medium.device:
+            if self._memory_rebind and isinstance(mem, th.Tensor) and mem.device != medium.device:
+                return                                           # reset since: the next forward allocates on this device
+            raise ValueError(f'memory: a contiguous ({M}, N) float32 tensor on {medium.device}')
+        if mem.shape[1] != agents.N and not self._memory_rebind:
+            raise ValueError(f'memory holds {mem.shape[1]} slots, the agents have {agents.N}: call reset_memory() to start blank with them')
+
+    def _memory_for(self, medium, agents) -> th.Tensor:
+        """`memory` for these agents: allocated as zeros at the first forward (and at the first after `reset_memory()` with
+        another N)."""
+        mem = self.memory
+        if mem is None or mem.shape[1] != agents.N or mem.device != medium.device:
+            mem = self.memory = th.zeros((self.memory_channels, agents.N), dtype=th.float32, device=medium.device)
+        self._memory_rebind = False
+        return mem
+
+    def memory_planes(self, medium, agents) -> th.Tensor:
+        """The (M, W, H) float32 planes a forward would sense now: on every cell the memory of the agent standing there (alive
+        slots only, the highest slot id on a shared cell), +0 elsewhere.  Builds the standing plane at `medium.epoch` and expands
+        `memory` into planes this agent owns (valid until the next call); allocates `memory` as `sense` does."""
+        if not self.memory_channels:
+            raise ValueError('memory_planes: an agent without memory channels has none')
+        self._check_memory(medium=medium)
+        self._check_memory_slots(medium, agents)
+        return self._expand_memory(medium, agents, self._stock_plane(medium, agents))
+
+    def _expand_memory(self, medium, agents, standing: th.Tensor) -> th.Tensor:
+        dev, W, H, M = medium.device, medium.W, medium.H, self.memory_channels
+        mem = self._memory_for(medium, agents)
+        key = (W, H, str(dev))
+        planes = self._memory_planes.get(key)
+        if planes is None:
+            planes = self._memory_planes[key] = th.empty((M, W, H), dtype=th.float32, device=dev)
+        m = medium.c_struct(need_owner=False)
+        _lib.check(_lib.lib.die_memory_planes(C.byref(m), _ptr(standing), medium.epoch, M, _ptr(mem), max(agents.N, 1), agents.N,
+                                              _ptr(planes), W * H, stream_ptr(dev)), 'die_memory_planes')
+        return planes
+
     def _stock_plane(self, medium, agents) -> th.Tensor:
         """The agents' stocks on their cells, built at `medium.epoch` on the plane this agent owns for (W, H, device)."""
         dev, W, H = medium.device, medium.W, medium.H
@@ -283,11 +408,15 @@ class NeuralAutomataAgent(TorchAgent):
     def sense(self, medium, agents=None) -> th.Tensor:
         """ConvolutionModel.forward over the medium on the device → (3, W, H) float32 tensor.  `agents`: the DeviceAgents whose
         stocks the `'agent_food'` channel shows — required with `with_stock_channel=True` (ValueError before any launch), unused
-        otherwise."""
+        otherwise.  With `memory_channels=M` the agents are required as well, and the tensor holds all 3 + M planes of the last
+        layer (planes 3.. are what `forward` reads out into `memory`)."""
         self._check_wide()
         self._check_stock(medium=medium)
+        self._check_memory(medium=medium)
         if self.with_stock_channel and agents is None:
             raise ValueError("sense(medium, agents): with_stock_channel=True needs the agents whose stocks the 'agent_food' channel shows")
+        if self.memory_channels:
+            self._check_memory_slots(medium, agents)
         medium.sensed()
         dev, W, H = medium.device, medium.W, medium.H
         weights = self._device_weights(dev)
@@ -296,8 +425,13 @@ class NeuralAutomataAgent(TorchAgent):
         medium._ensure_owner()
         fkind = _lib.DIE_PLANE_F32 if medium.dtype == th.float32 else _lib.DIE_PLANE_F16
         src = {'agents': (medium.owner, _lib.DIE_PLANE_AGENTS), 'env_food': (medium.food, fkind), 'chem1': (medium.chem, fkind)}
+        standing = self._stock_plane(medium, agents) if self.with_stock_channel or self.memory_channels else None
         if self.with_stock_channel:
-            src['agent_food'] = (self._stock_plane(medium, agents), _lib.DIE_PLANE_STOCK)
+            src['agent_food'] = (standing, _lib.DIE_PLANE_STOCK)
+        if self.memory_channels:                                 # the one standing plane serves both: here its payload is ignored
+            expanded = self._expand_memory(medium, agents, standing)
+            for j in range(self.memory_channels):
+                src[f'memory_{j}'] = (expanded[j], _lib.DIE_PLANE_F32)
         planes = [src[c] for c in self.obs_channels]
         sets = self._scratch(W, H, dev, 2, max(4, *(w.shape[0] for w in weights)) if wide else 4)
         p = self._model.agent_dropout.p
@@ -335,7 +469,7 @@ class NeuralAutomataAgent(TorchAgent):
         """:150-174."""
         agents, medium = obs
         sense = self.sense(medium, agents)
-        self._sense_output = sense
+        self._sense_output = sense[:3]                           # (with memory channels the planes 3.. follow: not rendered)
         action = DeviceAction(agents.N, agents.device, agents.slot, capacity=agents.capacity)
         action.global_slots = agents.global_slots
         planes = (C.c_void_p * 3)(*[sense[c].data_ptr() for c in range(3)])
@@ -343,6 +477,10 @@ class NeuralAutomataAgent(TorchAgent):
         m, a, u = medium.c_struct(need_owner=False), agents.c_struct(), action.c_struct()
         _lib.check(_lib.lib.die_gather_scale(C.byref(m), C.byref(a), planes, coefs, C.byref(u), stream_ptr(agents.device)),
                    'die_gather_scale')
+        if self.memory_channels:                                 # planes 3.. at the agents' cells, before anything moves
+            W, H = medium.W, medium.H
+            _lib.check(_lib.lib.die_gather_memory(C.byref(m), C.byref(a), self.memory_channels, sense[3].data_ptr(), W * H,
+                                                  _ptr(self.memory), max(agents.N, 1), stream_ptr(agents.device)), 'die_gather_memory')
         action._keepalive = sense
         return action
 
@@ -366,6 +504,7 @@ class NeuralAutomataAgent(TorchAgent):
         A wide stack (`hidden_channels` / `hidden_activation`) is refused here: NotImplementedError, before any launch and before
         `dropout_step` moves.  Its gradients come from `ConvolutionModel.forward_device` and `die_amd.functional`.  An agent with
         the stock channel (`with_stock_channel=True`) is refused the same way: its plane is piecewise constant in the weights."""
+        self._check_memory('differentiable_sense')
         self._check_wide('differentiable_sense')
         self._check_stock('differentiable_sense')
         layers = self._model.conv_layers()
@@ -392,6 +531,7 @@ class NeuralAutomataAgent(TorchAgent):
         non-zero gradient stand on one cell their terms are summed by fp32 atomic adds in arrival order; otherwise (alive agents
         never share a cell) the gradients are bit-reproducible run to run.  A wide stack raises NotImplementedError, as in
         `differentiable_sense`, and so does an agent with the stock channel."""
+        self._check_memory('differentiable_action')
         self._check_wide('differentiable_action')
         self._check_stock('differentiable_action')
         agents, medium = obs

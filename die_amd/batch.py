@@ -345,7 +345,8 @@ class BatchedEnv:
              results: Optional[torch.Tensor] = None, action: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One step of every replica: `agent.forward` + `Env.step` fused, two launches for the whole batch (L + 2 for a
         BatchedNeuralAutomataAgent of L layers, L + 3 when it senses the agents' stocks: the build of the R stock planes this
-        BatchedEnv owns; one more with dead slots, one more with a flow; for a BatchedPhysarumPopulation a
+        BatchedEnv owns, L + 5 when its agents carry memory channels: that build, the expand and the memory read-out; one more
+        with dead slots, one more with a flow; for a BatchedPhysarumPopulation a
         decode launch first when `parameters` was written since the last one).  Returns the (R, 2) float64 tensor of
         die_step_result words (device; `read_results` decodes).
 
@@ -388,7 +389,8 @@ class BatchedEnv:
         agent._calls += 1
         agent._stepped()
         self._serial += 1
-        if getattr(agent, '_stock_channel', False):  # this step built the stock planes: the next one may build on top of them
+        # this step built the stock planes (a population with memory builds them as its standing planes): the next may build on top
+        if getattr(agent, '_stock_channel', False) or getattr(agent, '_memory_channels', 0):
             self._stock_serial = self._serial
         if self.dynamics.agents_born:
             self._births(a, b, results)
@@ -1032,7 +1034,7 @@ def _architecture(agent: NeuralAutomataAgent) -> dict:
     return dict(kernel_sizes=tuple(int(k.kernel_size[0]) for k in layers), boundary=tuple(k.padding_mode for k in layers),
                 with_agent_channel='agents' in agent.obs_channels, with_stock_channel=agent.with_stock_channel, scale=agent.action_coefs[0], deposit=agent.action_coefs[2],
                 shapes=tuple(tuple(k.weight.shape) for k in layers), hidden_channels=agent.model.hidden_channels,
-                hidden_activation=agent.model.hidden_activation)
+                hidden_activation=agent.model.hidden_activation, memory_channels=agent.memory_channels)
 
 
 class BatchedNeuralAutomataAgent(_Population):
@@ -1065,12 +1067,33 @@ class BatchedNeuralAutomataAgent(_Population):
     max_agents, flows, per-replica Dynamics, dropout_seed, `action=` and both searchers take it as they are, and large worlds
     (`per_replica`) go through the stand-alone agents.  Refused with NotImplementedError before any launch and before
     `dropout_step` moves: `differentiable_sense`, `differentiable_action` and `forward_device` (so no action with a graph
-    through such a population ever reaches `env.differentiable_step`)."""
+    through such a population ever reaches `env.differentiable_step`).
+
+    Memory channels (a template built with `memory_channels=M`; every candidate then has them, `from_agents` refuses a mix):
+    `memory` is ONE (R, M, Nmax) float32 device tensor, `memory[r, :, :n[r]]` the stand-alone `replica_agent(r).memory` — by slot
+    id, which is the storage index here.  `env.step` takes die_nca_wide_env_step_batch_memory: the standing build (the
+    BatchedEnv's stock planes: one build serves the stock channel too), the expand into R·M planes this population owns, the L
+    wide layers giving 3 + M planes, the memory read-out, then the parent's launches — L + 5 in all — and replica r stays the
+    stand-alone run of `replica_agent(r)`, memory included, bit for bit.  With `episodes=E` every replica has its own memory: it
+    is state of the world run, not of the candidate.  Large worlds (`per_replica`) go through the stand-alone agents, each
+    keeping its own (`memory` is then None: read `agents[r].memory`).  `replica_agent(r)` / `candidate(r)` return agents with
+    blank memory.  `reset_memory()` zeroes every replica's; a population WITH memory also carries an instance attribute `reset`
+    bound to it — the searchers call a population's `reset()` every generation when it has one, after `env.reset()` — so every
+    generation starts from blank memory, while a memoryless population still has no `reset`.  agents_die, max_agents and
+    `reset(seed=...)`, flows, per-replica Dynamics, dropout_seed, `action=`, the stock channel and both searchers take memory as
+    they are.  Refused with NotImplementedError: `Dynamics(agents_born=True)` together with memory, HERE in the constructor — a
+    slot can die and be refilled within one step, so a newborn would inherit a dead agent's memory, and the stand-alone agent
+    cannot see the Dynamics to refuse it itself —; and `differentiable_sense`, `differentiable_action` and `forward_device`,
+    before any launch and before `dropout_step` or `memory` change."""
 
     def __init__(self, env: BatchedEnv, template: NeuralAutomataAgent, parameters=None, episodes: int = 1, *,
                  dropout_seed: Optional[int] = None, dropout_seed_stride: int = 1):
         if not isinstance(template, NeuralAutomataAgent):
             raise TypeError('template: a NeuralAutomataAgent')
+        if template.memory_channels and env.dynamics.agents_born:
+            raise NotImplementedError(f'memory_channels={template.memory_channels} with Dynamics(agents_born=True): a slot can die and '
+                                      'be refilled within one step, so a newborn would inherit a dead agent\'s memory (inheritance at '
+                                      'birth is not defined yet)')
         if dropout_seed is not None and not _is_integer(dropout_seed):
             raise ValueError(f'dropout_seed={dropout_seed!r}: an integer, or None')
         if not _is_integer(dropout_seed_stride, 0):
@@ -1084,6 +1107,10 @@ class BatchedNeuralAutomataAgent(_Population):
         self._arch = _architecture(template)
         self._wide = template.model.wide            # hidden_channels / hidden_activation: die_nca_wide_env_step_batch
         self._stock_channel = template.with_stock_channel      # the *_stock entry points: one launch more, layer 0 one plane more
+        self._memory_channels = template.memory_channels       # die_nca_wide_env_step_batch_memory: L + 5 launches
+        self.memory = None                          # (R, M, Nmax) float32 by slot id (small worlds; large ones: agents[r].memory)
+        if self._memory_channels:
+            self.reset = self.reset_memory          # on the INSTANCE: the searchers call `reset()` where a population has one
         template._check_wide()
         layers = template.model.conv_layers()
         for k in layers:
@@ -1116,6 +1143,19 @@ class BatchedNeuralAutomataAgent(_Population):
         need = _lib.lib.die_nca_wide_batch_scratch_bytes(env.W, env.H, self.R, len(layers), self._channels) if self._wide else \
             _lib.lib.die_nca_batch_scratch_bytes(env.W, env.H, self.R, len(layers))
         self._scratch = torch.empty(int(need) // 4, dtype=torch.float32, device=env.device)
+        if self._memory_channels:
+            M = self._memory_channels
+            self.memory = torch.zeros((self.R, M, env.Nmax), dtype=torch.float32, device=env.device)
+            # plane j of replica r at (j·R + r)·W·H: a batched layer launch reads plane j of every replica one plane apart
+            self._memory_planes = torch.empty((M, self.R, env.W, env.H), dtype=torch.float32, device=env.device)
+
+    def reset_memory(self) -> None:
+        """Blank memory for every replica (large worlds: for every stand-alone agent).  A population without memory channels
+        has nothing to reset."""
+        if self.memory is not None:
+            self.memory.zero_()
+        for ag in getattr(self, 'agents', ()):
+            ag.reset_memory()
 
     @classmethod
     def from_agents(cls, env: BatchedEnv, agents: Sequence[NeuralAutomataAgent], episodes: int = 1, *,
@@ -1207,6 +1247,13 @@ class BatchedNeuralAutomataAgent(_Population):
         """BatchedPhysarumAgent._launch with the dropout mask of the coming step after the workspace: one entry point without
         it, one with it (the same step, its last conv launch masked), and with Dynamics rows one for both, the mask nullable."""
         drop = self._dropout()
+        if self._memory_channels:                   # as the stock call, then M, the memory, its planes, and whether layer 0 reads the stock
+            name = 'die_nca_wide_env_step_batch_memory'
+            _lib.check(getattr(_lib.lib, name)(*front, C.byref(self._struct(self._sense_epoch)), *back,
+                                               None if drop is None else C.byref(drop), *(rows or (None, None)),
+                                               _ptr(self.env._stock_planes()), self._memory_channels, _ptr(self.memory),
+                                               _ptr(self._memory_planes), int(self._stock_channel), stream), name)
+            return
         if self._stock_channel:                     # the mask and the two tables nullable, the env's stock planes after them
             name = 'die_nca_wide_env_step_batch_stock' if self._wide else 'die_nca_env_step_batch_stock'
             _lib.check(getattr(_lib.lib, name)(*front, C.byref(self._struct(self._sense_epoch)), *back,
@@ -1243,6 +1290,7 @@ class BatchedNeuralAutomataAgent(_Population):
     def _check_differentiable(self, parameters: Optional[torch.Tensor]) -> torch.Tensor:
         """Every refusal of a differentiable call, before anything is launched; returns the matrix the call reads."""
         env = self.env
+        self.template._check_memory('differentiable mode')
         self.template._check_wide('differentiable mode')
         self.template._check_stock('differentiable mode')
         if env.per_replica:
@@ -1316,6 +1364,7 @@ class BatchedNeuralAutomataAgent(_Population):
         call whenever a `dropout_seed` is set.  Refused before any launch and before `dropout_step` moves: a narrow population
         (ValueError: it has `differentiable_sense`), a population with the stock channel, large worlds (`per_replica`) and
         'reflect' / 'replicate' boundaries (NotImplementedError)."""
+        self.template._check_memory('forward_device')
         self.template._check_stock('forward_device')
         if not self._wide:
             raise ValueError('forward_device: a narrow population (hidden_channels and hidden_activation both None) is differentiated '

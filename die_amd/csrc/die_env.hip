@@ -1558,6 +1558,23 @@ int die_nca_wide_sense_batch(const die_medium* m, const die_batch* b, const die_
                              const DropWords* drop, void* stream, const unsigned long long* stock);
 int die_stock_launch(const die_medium* m, const die_agents* a, int32_t replicas, const int64_t* n, int64_t agent_stride,
                      int64_t plane_stride, int32_t epoch, unsigned long long* planes, void* stream, const char* who);  // die_stock.hip
+int die_nca_wide_batch_check_memory(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool stock, int memory);
+int die_nca_wide_sense_batch_memory(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
+                                    const DropWords* drop, void* stream, const unsigned long long* stock, const float* mem_planes, int memory);
+int die_memory_planes_launch(int32_t W, int32_t H, int32_t replicas, const int64_t* n, const unsigned long long* standing,
+                             int64_t standing_rep, int32_t epoch, int32_t M, const float* mem, int64_t mem_row, int64_t mem_rep,
+                             float* planes, int64_t plane_j, int64_t plane_rep, void* stream, const char* who);          // die_memory.hip
+int die_gather_memory_launch(const die_medium* m, const die_agents* a, int32_t replicas, const int64_t* n, int64_t agent_stride, int32_t M,
+                             const float* planes, int64_t plane_j, int64_t plane_rep, float* mem, int64_t mem_row, int64_t mem_rep,
+                             void* stream, const char* who);                                                             // die_memory.hip
+
+// die_nca_wide_env_step_batch_memory's own arguments (die_memory.hip: the agents' memory channels)
+struct MemoryStep {
+    int M;                       // memory channels, 1..DIE_MEMORY_MAX_CHANNELS
+    float* mem;                  // (R, M, agent_stride)
+    float* planes;               // plane j of replica r at (j * R + r) * plane_stride
+    bool with_stock;             // layer 0 also reads the standing planes as its stock channel
+};
 
 // die_nca_env_step_batch (drop null) and die_nca_env_step_batch_dropout: one body; the mask only changes the last conv launch.
 // `wide` (die_nca_wide_env_step_batch): the stack's check and its sensing are die_nca_wide.hip's, which hand back the same
@@ -1565,15 +1582,20 @@ int die_stock_launch(const die_medium* m, const die_agents* a, int32_t replicas,
 // `stock` (die_nca_env_step_batch_stock / die_nca_wide_env_step_batch_stock; null: the call without it): the R stock planes of
 // die_stock.hip.  Layer 0 then reads one plane more; after every check the planes are built at sense_epoch (one launch more,
 // L + 3 in all), layer 0 reads them as its last input, and on the epoch wrap they are cleared with the claim planes.
+// `ms` (die_nca_wide_env_step_batch_memory; wide stacks only, `stock` then holds the standing planes whether or not layer 0 reads
+// them): after the build the memory is expanded into its planes, layer 0 reads them after the field's, the last layer gives
+// 3 + M planes and the planes 3.. are read out into the memory before the claim launch moves anything: L + 5 launches.
 static int nca_env_step_batch(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
                               const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws, int64_t ws_bytes,
                               const die_nca_dropout* drop, void* stream, const char* who, bool with_rows = false,
                               const die_dynamics_row* rows = nullptr, const die_dynamics_row* rows_host = nullptr, bool wide = false,
-                              unsigned long long* stock = nullptr) {
+                              unsigned long long* stock = nullptr, const MemoryStep* ms = nullptr) {
     DIE_REQUIRE(m && a && nca && d && b && results && ws, "%s: null argument", who);
     int rc = batch_world_check(m, a, d, b, ws_bytes, true, who);
     if (rc != DIE_OK) return rc;
-    rc = wide ? die_nca_wide_batch_check(nca, m->W, m->H, b->replicas, who, stock != nullptr)
+    const bool sense_stock = stock && (!ms || ms->with_stock);
+    rc = ms ? die_nca_wide_batch_check_memory(nca, m->W, m->H, b->replicas, who, sense_stock, ms->M)
+         : wide ? die_nca_wide_batch_check(nca, m->W, m->H, b->replicas, who, stock != nullptr)
               : die_nca_batch_check(nca, m->W, m->H, b->replicas, who, stock != nullptr);
     if (rc != DIE_OK) return rc;
     DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX && m->epoch == nca->sense_epoch % DIE_OWNER_EPOCH_MAX + 1,
@@ -1594,7 +1616,20 @@ static int nca_env_step_batch(const die_medium* m, const die_agents* a, const di
         rc = die_stock_launch(m, a, b->replicas, b->n, b->agent_stride, b->plane_stride, nca->sense_epoch, stock, stream, who);
         if (rc != DIE_OK) return rc;
     }
-    rc = (wide ? die_nca_wide_sense_batch : die_nca_sense_batch)(m, b, nca, &q.sense, &q.rep, drop ? &dw : nullptr, stream, stock);   // reads the claim plane at sense_epoch …
+    if (ms) {                                                         // the memory of whoever stands on a cell, as planes
+        rc = die_memory_planes_launch(m->W, m->H, b->replicas, b->n, stock, b->plane_stride, nca->sense_epoch, ms->M, ms->mem, b->agent_stride,
+                                      (int64_t)ms->M * b->agent_stride, ms->planes, (int64_t)b->replicas * b->plane_stride, b->plane_stride,
+                                      stream, who);
+        if (rc != DIE_OK) return rc;
+        rc = die_nca_wide_sense_batch_memory(m, b, nca, &q.sense, &q.rep, drop ? &dw : nullptr, stream, sense_stock ? stock : nullptr,
+                                             ms->planes, ms->M);
+        if (rc != DIE_OK) return rc;
+        // planes 3.. at the cells the agents stand on NOW: before the claim launch moves anything
+        rc = die_gather_memory_launch(m, a, b->replicas, b->n, b->agent_stride, ms->M, q.sense + 3 * (int64_t)m->W * m->H, (int64_t)m->W * m->H,
+                                      q.rep, ms->mem, b->agent_stride, (int64_t)ms->M * b->agent_stride, stream, who);
+    } else {
+        rc = (wide ? die_nca_wide_sense_batch : die_nca_sense_batch)(m, b, nca, &q.sense, &q.rep, drop ? &dw : nullptr, stream, stock);   // reads the claim plane at sense_epoch …
+    }
     if (rc != DIE_OK) return rc;
     if (nca->sense_epoch == DIE_OWNER_EPOCH_MAX) {                    // … which is cleared before the tag 1 claims
         const int64_t words = (int64_t)(b->replicas - 1) * b->plane_stride + (int64_t)m->W * m->H;
@@ -1653,6 +1688,21 @@ extern "C" int die_nca_wide_env_step_batch_stock(const die_medium* m, const die_
     if (!stock) return die_nca_wide_env_step_batch(m, a, nca, act, d, b, results, ws, ws_bytes, drop, rows, rows_host, stream);
     return nca_env_step_batch(m, a, nca, act, d, b, results, ws, ws_bytes, drop, stream, "die_nca_wide_env_step_batch_stock",
                               rows || rows_host, rows, rows_host, true, stock);
+}
+
+extern "C" int die_nca_wide_env_step_batch_memory(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
+                                                  const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws,
+                                                  int64_t ws_bytes, const die_nca_dropout* drop, const die_dynamics_row* rows,
+                                                  const die_dynamics_row* rows_host, unsigned long long* standing, int32_t memory_channels,
+                                                  float* memory, float* memory_planes, int32_t with_stock, void* stream) {
+    const char* who = "die_nca_wide_env_step_batch_memory";
+    DIE_REQUIRE(standing && memory && memory_planes, "%s: null standing planes, memory or memory planes", who);
+    DIE_REQUIRE(memory_channels >= 1 && memory_channels <= DIE_MEMORY_MAX_CHANNELS, "%s: %d memory channels outside 1..%d", who, memory_channels,
+                DIE_MEMORY_MAX_CHANNELS);
+    DIE_REQUIRE(with_stock == 0 || with_stock == 1, "%s: with_stock is 0 or 1", who);
+    const MemoryStep ms = {memory_channels, memory, memory_planes, with_stock == 1};
+    return nca_env_step_batch(m, a, nca, act, d, b, results, ws, ws_bytes, drop, stream, who, rows || rows_host, rows, rows_host, true, standing,
+                              &ms);
 }
 
 extern "C" int die_nca_env_step_batch(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,

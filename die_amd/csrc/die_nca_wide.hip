@@ -274,7 +274,9 @@ static int wide_max_channels(const die_nca_batch* nca) {
 // every argument of the stack, before anything is launched
 // (scratch: the ping-pong planes of the step; the calls that keep every layer in caller-owned storage check their own)
 // (stock: layer 0 reads one plane more, the stock plane of die_stock.hip as its last input)
-static int wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool scratch, bool stock = false) {
+// (memory: layer 0 reads `memory` fp32 planes more, between the field's and the stock's, and the last layer gives 3 + memory)
+static int wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool scratch, bool stock = false,
+                            int memory = 0) {
     if (scratch) DIE_REQUIRE(nca && nca->layers && nca->scratch, "%s: null stack, layer list or scratch", who);
     else DIE_REQUIRE(nca && nca->layers, "%s: null stack or layer list", who);
     DIE_REQUIRE(nca->n_layers >= 1 && nca->n_layers <= DIE_NCA_MAX_LAYERS, "%s: 1..%d layers (got %d)", who, DIE_NCA_MAX_LAYERS, nca->n_layers);
@@ -285,7 +287,7 @@ static int wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int3
     DIE_REQUIRE(W >= 1 && H >= 1 && replicas >= 1 && replicas <= DIE_MAX_REPLICAS, "%s: bad size %dx%d or replicas %d outside 1..%d", who,
                 W, H, replicas, DIE_MAX_REPLICAS);
     DIE_REQUIRE((W + NCA_TX - 1) / NCA_TX <= 65535, "%s: field too tall", who);
-    int cin = 2 + nca->with_agent_channel + (stock ? 1 : 0);
+    int cin = 2 + nca->with_agent_channel + memory + (stock ? 1 : 0);
     for (int l = 0; l < nca->n_layers; ++l) {
         const die_nca_layer& L = nca->layers[l];
         const bool last = l == nca->n_layers - 1;
@@ -300,7 +302,9 @@ static int wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int3
                     "needs a field larger than that (%dx%d)", who, l, L.k / 2, W, H);
         cin = L.cout;
     }
-    DIE_REQUIRE(cin == 3, "%s: the last layer gives %d planes (dx, dy, deposit: 3)", who, cin);
+    if (memory) DIE_REQUIRE(cin == 3 + memory, "%s: the last layer gives %d planes (dx, dy, deposit and %d memory planes: %d)", who, cin,
+                            memory, 3 + memory);
+    else DIE_REQUIRE(cin == 3, "%s: the last layer gives %d planes (dx, dy, deposit: 3)", who, cin);
     if (!scratch) return DIE_OK;
     const int64_t need = die_nca_wide_batch_scratch_bytes(W, H, replicas, nca->n_layers, wide_max_channels(nca));
     DIE_REQUIRE(nca->scratch_bytes >= need, "%s: scratch too small (%lld < %lld)", who, (long long)nca->scratch_bytes, (long long)need);
@@ -309,6 +313,9 @@ static int wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int3
 
 int die_nca_wide_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool stock) {
     return wide_stack_check(nca, W, H, replicas, who, true, stock);
+}
+int die_nca_wide_batch_check_memory(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool stock, int memory) {
+    return wide_stack_check(nca, W, H, replicas, who, true, stock, memory);
 }
 int die_nca_wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who) {
     return wide_stack_check(nca, W, H, replicas, who, false);
@@ -320,8 +327,11 @@ int die_nca_wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int
 // of it.  *sense = the last layer's planes of replica 0, replica r's *rep further (what die_nca_sense_batch returns for a narrow
 // stack: k_nca_move_claim_batch reads either)
 // `stock` (or null): the R stock planes of die_stock.hip, b->plane_stride apart, built at sense_epoch — layer 0's last input
+// `mem_planes` (or null): the R * `memory` fp32 planes of die_memory.hip, plane j of replica r at (j * R + r) * b->plane_stride —
+// layer 0's inputs after the field's planes and before the stock's
 static int wide_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* dst, bool pingpong, float* masked,
-                            const float** sense, int64_t* rep, const DropWords* drop, void* stream, const unsigned long long* stock = nullptr) {
+                            const float** sense, int64_t* rep, const DropWords* drop, void* stream, const unsigned long long* stock = nullptr,
+                            const float* mem_planes = nullptr, int memory = 0) {
     const int64_t cells = (int64_t)m->W * m->H, rep_scratch = wide_max_channels(nca) * cells;
     const int fkind = m->dtype == DIE_F32 ? DIE_PLANE_F32 : DIE_PLANE_F16;
     WideArgs a = {};
@@ -329,6 +339,8 @@ static int wide_sense_batch(const die_medium* m, const die_batch* b, const die_n
     if (nca->with_agent_channel) { a.in[c] = m->owner; a.kind[c++] = DIE_PLANE_AGENTS; }
     a.in[c] = m->food; a.kind[c++] = fkind;
     a.in[c] = m->chem; a.kind[c++] = fkind;
+    if (mem_planes)
+        for (int j = 0; j < memory; ++j) { a.in[c] = mem_planes + (int64_t)j * b->replicas * b->plane_stride; a.kind[c++] = DIE_PLANE_F32; }
     if (stock) { a.in[c] = stock; a.kind[c++] = DIE_PLANE_STOCK; }
     a.rep_in = b->plane_stride;
     a.W = m->W; a.H = m->H; a.epoch = nca->sense_epoch; a.pad = nca->padding_mode;
@@ -363,6 +375,11 @@ static int wide_sense_batch(const die_medium* m, const die_batch* b, const die_n
 int die_nca_wide_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
                              const DropWords* drop, void* stream, const unsigned long long* stock) {
     return wide_sense_batch(m, b, nca, nca->scratch, true, nullptr, sense, rep, drop, stream, stock);
+}
+
+int die_nca_wide_sense_batch_memory(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
+                                    const DropWords* drop, void* stream, const unsigned long long* stock, const float* mem_planes, int memory) {
+    return wide_sense_batch(m, b, nca, nca->scratch, true, nullptr, sense, rep, drop, stream, stock, mem_planes, memory);
 }
 
 // ---- the same launches into storage that keeps every layer (the forward of die_nca_wide_backward_batch) -----------------

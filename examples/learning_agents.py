@@ -9,7 +9,7 @@ separable CMA-ES with stdev_init 0.1 and popsize 10 (die_amd.search.CMAES), the 
                                        [--epoch-iters 30] [--agents-die] [--agents-born] [--max-agents alive|full|tight|N]
                                        [--reseed S] [--reseed-stride 0] [--episodes 1] [--out saved_models/agent.pt] [--time]
                                        [--dropout P] [--dropout-seed S] [--dropout-stride K] [--init-from FILE]
-                                       [--stock-channel]
+                                       [--stock-channel] [--memory-channels M]
 
 --init-from FILE starts the search from a saved agent (e.g. the one examples/imitate_agent.py fits by gradient descent): its
 `parameters_to_vector` becomes the searcher's `center_init` instead of a centre drawn in initial_bounds.  A file whose agent
@@ -19,6 +19,11 @@ is refused with a message naming both counts.
 --stock-channel trains agents that sense their own food stock (NeuralAutomataAgent(with_stock_channel=True)): a fourth observation
 channel holding, on every cell, the `agent_food` of the agent standing there, built on the device by one more launch per batched
 step.  With --agents-die / --agents-born that is the quantity that decides whether an agent dies or breeds.
+
+--memory-channels M (1..8) trains recurrent agents (NeuralAutomataAgent(memory_channels=M)): every agent carries M values from one
+step to the next, read by the stack as M more observation planes and written as M more output planes.  The stack is then a wide
+stack (--hidden-channels defaults to the observation's width), every generation starts from blank memory, and --agents-born is
+refused (a newborn would inherit a dead agent's memory).
 
 --dropout P trains the agent with the reference's `p_agent_dropout=P` (its learning_agents.py carries 0.25): in every batched step
 replica r's sense planes are multiplied by the counter-based dropout mask of key --dropout-seed + r·--dropout-stride (default
@@ -183,6 +188,8 @@ def main():
     add_wide_arguments(p)
     args = p.parse_args()
     args.wide_kw = wide_keywords(args)
+    if not 0 <= args.memory_channels <= 8 or (args.memory_channels and args.agents_born):
+        p.error('--memory-channels in 0..8, and not together with --agents-born (a newborn would inherit a dead agent\'s memory)')
     args.agents_die = lifecycle(args.agents_die, args.agents_born)      # (what the helpers hand to make_dynamics)
     if not 0. <= args.dropout <= 1. or args.dropout_stride < 0:
         p.error('--dropout in [0, 1], --dropout-stride >= 0')

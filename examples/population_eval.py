@@ -4,11 +4,15 @@ all R worlds stepped together by die_amd.batch (L + 2 launches per step for an L
 
     python examples/population_eval.py [--replicas 10] [--size 96] [--iters 50] [--dynamics st-perlin-wide] [--generations 0] [--agents-die] [--agents-born]
                                        [--max-agents alive|full|tight|N] [--reseed S] [--episodes 1] [--compare]
-                                       [--dropout P] [--dropout-seed S] [--dropout-stride K] [--stock-channel]
+                                       [--dropout P] [--dropout-seed S] [--dropout-stride K] [--stock-channel] [--memory-channels M]
 
 --stock-channel gives the candidates a fourth observation channel, `'agent_food'`: on every cell the stock of the agent standing
 there (NeuralAutomataAgent(with_stock_channel=True)), built on the device by one more launch per batched step — what lets a policy
 tell a starving agent from a well-fed one under --agents-die / --agents-born.
+
+--memory-channels M (1..8) gives every agent M values it carries from one step to the next (NeuralAutomataAgent(memory_channels=M)):
+the stack becomes a wide stack that reads them as M more observation planes and writes them as M more output planes (three more
+launches per batched step).  Every evaluation and every search generation starts from blank memory.  Not with --agents-born.
 
 --dynamics picks one of the reference's three worlds (learning_agents.py `dynamics_choice`): 'st-perlin', 'st-perlin-wide' or
 'dyn-pred', where the food flows in running waves (WaveSequence.get_flow_operator, one more launch per batched step).
@@ -135,13 +139,19 @@ def add_wide_arguments(p):
     p.add_argument('--hidden-activation', choices=('tanh', 'relu', 'none'), default='none', help='activation after every layer but the last')
     p.add_argument('--stock-channel', action='store_true', help="the candidates sense their own food stock: a last observation channel "
                                                                 "'agent_food' (with_stock_channel=True; one more launch per batched step)")
+    p.add_argument('--memory-channels', type=int, default=0, metavar='M', help='values every agent carries between steps, 1..8 (memory_channels=M: '
+                                                                               'a wide stack, three more launches per batched step; not with '
+                                                                               '--agents-born)')
 
 
 def wide_keywords(args):
-    """NeuralAutomataAgent's keywords for --hidden-channels C --hidden-activation A --stock-channel (none when none is given)."""
+    """NeuralAutomataAgent's keywords for --hidden-channels C --hidden-activation A --stock-channel --memory-channels M (none when
+    none is given)."""
     kw = {}
     if getattr(args, 'stock_channel', False):
         kw['with_stock_channel'] = True
+    if getattr(args, 'memory_channels', 0):
+        kw['memory_channels'] = args.memory_channels
     if args.hidden_channels is not None:
         kw['hidden_channels'] = args.hidden_channels
     if args.hidden_activation != 'none':
@@ -259,6 +269,7 @@ def main():
         evaluate_population(*make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die, N, E, drop_kw), 2)
         run_epoch(one_at_a_time_worlds(args.size, 1, args.seed, args.dynamics, args.agents_die, N)[0], agents[0], 2)
         agents[0].dropout_step = 0                                           # (the warm-up advanced its mask counter)
+        agents[0].reset_memory()                                             # (… and left its memory, with --memory-channels)
         benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die, N, E, drop_kw)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -290,6 +301,8 @@ def main():
                 benv.reset(seed=args.reseed + g, seed_stride=0)
             else:                                                           # E new worlds, the same for every candidate
                 benv.reset(seeds=episode_seeds(args.reseed + g * E, R, E))
+            if pop.memory is not None:                                      # --memory-channels: a new world starts from blank memory
+                pop.reset_memory()
             fit = candidate_fitness(evaluate_population(benv, pop, args.iters), E)
         else:
             gen_benv, gen_pop = make_population(args.size, template, samples, args.seed + 1 + g * E, args.dynamics, args.agents_die, N, E, drop_kw)

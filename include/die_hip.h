@@ -1120,6 +1120,64 @@ int die_nca_wide_env_step_batch_stock(const die_medium* m, const die_agents* a, 
                                       int64_t workspace_bytes, const die_nca_dropout* drop, const die_dynamics_row* rows,
                                       const die_dynamics_row* rows_host, unsigned long long* stock, void* stream);
 
+/* ---- Memory channels: agents carry M values between forwards (die_memory.hip; NeuralAutomataAgent(memory_channels=M)) ------
+ * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
+ * The memory is an (M, N) fp32 array indexed by SLOT ID (agents->slot ? slot[n] : n), row j at memory + j * row_stride.  One
+ * forward: a standing plane (die_stock_plane's words at `epoch`: who stands on each cell, the highest slot id of
+ * the alive ones; the payload is ignored) is expanded into M fp32 observation planes, the wide stack runs with them as plain
+ * DIE_PLANE_F32 inputs and gives 3 + M planes, and the planes 3.. are read out at the agents' cells into the memory.
+ *
+ * die_memory_planes — the expand, one launch: P_j[c] = occupied(c at epoch) ? memory[j][winner(c)] : +0.0f for every cell c and
+ * j < memory_channels, plane j at planes + j * plane_stride.  EVERY cell of every plane is written (nobody clears them); the
+ * words between two planes (plane_stride > W * H) are left alone; the values are moved as 32-bit words (negative zero, denormals
+ * and negative values keep their bits); a winner id >= n_slots reads as empty.  16-byte stores where H % 4 == 0 and the planes
+ * and strides are 16-byte aligned.  Checked before the launch (DIE_ERR_ARG): a null pointer, W or H < 1, memory_channels outside
+ * 1..DIE_MEMORY_MAX_CHANNELS, epoch outside 1..DIE_OWNER_EPOCH_MAX, n_slots outside 0..DIE_OWNER_SLOT_MASK - 1, row_stride <
+ * max(n_slots, 1), plane_stride < W * H, output planes that overlap the standing plane or the memory; a decomposed medium
+ * (m->gW > 0) is DIE_ERR_UNSUPPORTED.  Of `m` only W, H and gW are read. */
+#define DIE_MEMORY_MAX_CHANNELS 8
+int die_memory_planes(const die_medium* m, const unsigned long long* standing, int32_t epoch, int32_t memory_channels,
+                      const float* memory, int64_t row_stride, int64_t n_slots, float* planes, int64_t plane_stride, void* stream);
+/* R replicas in ONE launch (the replica in blockIdx.y).  Replica r: standing plane at standing + r * b->plane_stride, memory
+ * rows at memory + (r * memory_channels + j) * row_stride with b->n[r] slots, output plane j at planes + (j * R + r) *
+ * b->plane_stride — the layout in which a batched layer launch reads plane j of every replica b->plane_stride apart.  Checked as
+ * die_memory_planes, and: a null batch, replicas outside 1..DIE_MAX_REPLICAS, b->plane_stride < W * H, agent_stride < 1, n[r]
+ * outside 0..agent_stride, row_stride < agent_stride. */
+int die_memory_planes_batch(const die_medium* m, const die_batch* b, const unsigned long long* standing, int32_t epoch,
+                            int32_t memory_channels, const float* memory, int64_t row_stride, float* planes, void* stream);
+/* die_gather_memory — the read-out, one launch, one thread per stored slot n < agents->N, no atomics (slot ids are distinct):
+ *   memory[j][id] = alive[n] ? planes_j[cell of slot n] : +0.0f,  id = agents->slot ? slot[n] : n,  j < memory_channels,
+ * plane j at planes + j * plane_stride (the stack's planes 3..: no coefficient).  Dead slots are zeroed; an id >= agents->N is
+ * skipped.  Checked before the launch (DIE_ERR_ARG): a null pointer (m, agents, planes, memory, or one of x, y, alive), W or H
+ * < 1, memory_channels outside 1..DIE_MEMORY_MAX_CHANNELS, N outside 0..DIE_OWNER_SLOT_MASK - 1, plane_stride < W * H,
+ * row_stride < max(N, 1), a memory that overlaps the planes; a decomposed medium is DIE_ERR_UNSUPPORTED. */
+int die_gather_memory(const die_medium* m, const die_agents* agents, int32_t memory_channels, const float* planes,
+                      int64_t plane_stride, float* memory, int64_t row_stride, void* stream);
+/* R replicas in ONE launch (blockIdx.y): replica r's slots start at r * b->agent_stride (slot order: agents->slot must be NULL),
+ * its planes at planes + r * replica_stride + j * plane_stride, its memory rows at memory + (r * memory_channels + j) *
+ * row_stride.  The padding slots n >= b->n[r] are neither read nor written.  Checked as die_gather_memory, and: a null batch, a
+ * slot array, replicas outside 1..DIE_MAX_REPLICAS, b->plane_stride or plane_stride < W * H, replica_stride below a replica's
+ * planes, agent_stride < 1, n[r] outside 0..agent_stride, row_stride < agent_stride. */
+int die_gather_memory_batch(const die_medium* m, const die_agents* agents, const die_batch* b, int32_t memory_channels,
+                            const float* planes, int64_t plane_stride, int64_t replica_stride, float* memory, int64_t row_stride,
+                            void* stream);
+/* die_nca_wide_env_step_batch_stock for a population whose agents carry memory.  Its arguments, and: `standing`, R uint64
+ * planes b->plane_stride apart (the stock planes' rule: zero, or words of earlier epochs of the cycle); memory_channels = M in
+ * 1..DIE_MEMORY_MAX_CHANNELS; `memory`, the dense (R, M, b->agent_stride) array; `memory_planes`, R * M fp32 planes laid out as
+ * die_memory_planes_batch writes them; with_stock (0 / 1): layer 0 also reads the standing planes as DIE_PLANE_STOCK, its last
+ * input.  In order: the parent's checks in the parent's order, with layer 0 reading 2 + with_agent_channel + M + with_stock
+ * planes ([agents], food, chem, memory_0 .. memory_{M-1}, [stock]) and the last layer giving 3 + M; the standing build at
+ * nca->sense_epoch (die_stock_plane_batch's launch: with_stock = 0 simply ignores the payload); the expand; the L wide layer
+ * launches (the last layer's tanh and mask on all 3 + M planes); the memory read-out of planes 3.. — before anything moves —;
+ * the parent's read-out-and-claim launch on planes 0..2, lifecycle and sweeps: L + 5 launches.  On the epoch wrap the standing
+ * planes are cleared with the claim planes.  Also refused (DIE_ERR_ARG): a null standing / memory / memory_planes, M out of
+ * range, with_stock not 0 or 1. */
+int die_nca_wide_env_step_batch_memory(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
+                                       const die_dynamics* d, const die_batch* b, die_step_result* results, void* workspace,
+                                       int64_t workspace_bytes, const die_nca_dropout* drop, const die_dynamics_row* rows,
+                                       const die_dynamics_row* rows_host, unsigned long long* standing, int32_t memory_channels,
+                                       float* memory, float* memory_planes, int32_t with_stock, void* stream);
+
 /* ---- The wide stack's adjoint for every replica of a die_batch (BatchedNeuralAutomataAgent.forward_device) -----------------
  * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
  * The wide twins of die_nca_sense_batch_store / die_nca_backward_batch_inputs: `m` describes replica 0 and `b` the strides,
