@@ -11,7 +11,9 @@ Ceilings, none of them taken from what the device gives:
 
 Every ctypes call writes into buffers with a sentinel tail that must come back untouched.  Shapes: 24 x 68 straddles conv tiles with
 H % 4 == 0, 16 x 64 is one tile, 8 x 12 is smaller than one (sigma 0.8 -> radius 3); R = 3 with differing n[r], R = 6 as 2
-candidates x 3 worlds, R = 64 once (the end of the index list of a sweep launch and of n[64])."""
+candidates x 3 worlds, R = 64 once (the end of the index list of a sweep launch and of n[64]).  The entry points at full blocks
+(LABBOOK §33; sizes in tests/grad_midsize_shapes.py): the batched gather at a stride of 3077 entries, die_deposit_cells_batch and
+die_gather_scale_backward_batch with a row of 2 097 665 slots beside short ones."""
 import ctypes as C
 import dataclasses
 
@@ -27,6 +29,7 @@ from die_amd.device_array import DeviceAction, _ptr, stream_ptr
 from tests import dropout_model as D
 from tests import field_step_adjoint_model as F
 from tests import field_step_batch_model as B
+from tests import grad_midsize_shapes as S
 from tests.test_gpu_batch_step_action import CASES as WORLDS, _cell, build, draw_actions
 
 pytestmark = pytest.mark.gpu
@@ -79,6 +82,83 @@ def test_deposit_cells_batch_is_deposit_cells_per_replica(name):
     assert all(losers), losers                                      # every replica had alive slots that lost a shared cell
     if case.get('agents_die'):
         assert starved > 0
+
+
+def test_deposit_cells_batch_past_the_grid_cap():
+    """Gap 2 of LABBOOK §33 (k_deposit_cells_batch): one launch sized by the largest row, n = (2 097 665, 65 537, 300) at stride
+    2 097 665 — row 0 strides through the capped 8192-workgroup grid a second time, rows 1 and 2 end after 257 and 2 workgroups and
+    write -1 from there on.  Every replica's claim plane and arrays are those of a stand-alone Env of n[r] slots after one step;
+    replica r equals die_deposit_cells on that Env and the loop-free winners' rule, the padding (alive slots on real cells) is -1."""
+    from tests.test_gpu_field_step_grad import stepped_slot_env
+    (W, H), n, R = S.DEPOSIT_PLANE, S.DEPOSIT_BATCH_N, 3
+    stride = max(n)
+    rs = np.random.RandomState(23)
+    owner = torch.zeros((R, W * H), dtype=torch.int64, device=DEV)
+    x = torch.from_numpy(rs.randint(-2 ** 31, 2 ** 31, (R, stride)).astype(np.int32)).to(DEV)      # the padding: alive, anywhere
+    y = torch.from_numpy(rs.randint(-2 ** 31, 2 ** 31, (R, stride)).astype(np.int32)).to(DEV)
+    alive = torch.ones((R, stride), dtype=torch.uint8, device=DEV)
+    wants, epoch = [], None
+    for r in range(R):
+        env, xw, yw, up = stepped_slot_env(W, H, n[r], rs)
+        epoch = env.medium.epoch if epoch is None else epoch
+        assert env.medium.epoch == epoch
+        owner[r].copy_(env.medium.owner.view(-1))
+        x[r, :n[r]].copy_(env.agents.x); y[r, :n[r]].copy_(env.agents.y); alive[r, :n[r]].copy_(env.agents.alive)
+        want = torch.full((n[r] + TAIL,), SENT_I, dtype=torch.int32, device=DEV)
+        ms, as_ = env.medium.c_struct(), env.agents.c_struct()
+        L.check(L.lib.die_deposit_cells(C.byref(ms), C.byref(as_), _ptr(want), stream_ptr(DEV)), 'die_deposit_cells')
+        want = want.cpu().numpy()
+        assert np.all(want[n[r]:] == SENT_I)
+        assert np.array_equal(want[:n[r]], S.winner_cells(W, H, xw, yw, up)), r
+        assert (want[:n[r]] >= 0).sum() > min(n[r] // 4, W * H // 2)                  # winners, and in the crowded rows losers
+        assert n[r] < W * H // 4 or ((want[:n[r]] < 0) & (up > 0)).sum() > n[r] // 16
+        wants.append(want[:n[r]])
+        del env
+    buf = torch.full((R * stride + TAIL,), SENT_I, dtype=torch.int32, device=DEV)
+    m = L.Medium(W, H, L.DIE_F32, epoch, _ptr(owner), None, None, None, 0, 0, 0, 0, 0, 0, 0, 0, None)
+    a = L.Agents(stride, _ptr(x), _ptr(y), _ptr(alive), None, None)
+    b = L.Batch(R, 0, W * H, stride, 1, (C.c_int64 * 64)(*(list(n) + [0] * (64 - R))))
+    L.check(L.lib.die_deposit_cells_batch(C.byref(m), C.byref(a), C.byref(b), _ptr(buf), stream_ptr(DEV)), 'die_deposit_cells_batch')
+    got = buf.cpu().numpy()
+    assert np.all(got[R * stride:] == SENT_I), 'written behind R * agent_stride words'
+    got = got[:R * stride].reshape(R, stride)
+    for r in range(R):
+        assert np.array_equal(got[r, :n[r]], wants[r]), (r, np.flatnonzero(got[r, :n[r]] != wants[r])[:8])
+        assert np.all(got[r, n[r]:] == -1), (r, 'padding')
+
+
+def test_gather_scale_backward_batch_past_the_grid_cap():
+    """Gap 2 of LABBOOK §33 (k_gather_scale_backward_batch): the launch is sized by the largest n[r] — n = (2 097 665, 300) on
+    1028 x 1024, so row 0 takes the stride loop's second trip while row 1's threads idle from its second workgroup on.  The
+    reference and the bound are those of the stand-alone test (float64 over the exact fp32 products; one term: its bits; n terms:
+    (n - 1) * 2^-24 * sum|terms|); the planes of the short replica are +0 wherever none of its 300 slots stands."""
+    (W, H), n, coefs, R = S.SCATTER_PLANE, S.SCATTER_BATCH_N, S.SCATTER_COEFS, 2
+    stride = max(n)
+    worlds = [S.scatter_world(W, H, stride, np.random.RandomState(41 + r)) for r in range(R)]        # (the padding holds slots and gradients too)
+    x, y = (torch.from_numpy(np.stack([w[q] for w in worlds]).view(np.int32).copy()).to(DEV) for q in (0, 1))
+    grads = np.ascontiguousarray(np.stack([w[2] for w in worlds], axis=1))                           # (3, R, stride)
+    g_dev = torch.from_numpy(grads).to(DEV)
+    planes = _sentinel(R * 3 * W * H + TAIL)
+    m = L.Medium(W, H, L.DIE_F32, 1, None, None, None, None, 0, 0, 0, 0, 0, 0, 0, 0, None)
+    a = L.Agents(stride, _ptr(x), _ptr(y), None, None, None)
+    u = L.Action(stride, g_dev[0].data_ptr(), g_dev[1].data_ptr(), g_dev[2].data_ptr())
+    b = L.Batch(R, 0, W * H, stride, 1, (C.c_int64 * 64)(*(list(n) + [0] * (64 - R))))
+    L.check(L.lib.die_gather_scale_backward_batch(C.byref(m), C.byref(a), C.byref(b), C.byref(u), (C.c_float * 3)(*coefs), _ptr(planes),
+                                                  3 * W * H, stream_ptr(DEV)), 'die_gather_scale_backward_batch')
+    torch.cuda.synchronize()
+    got = planes.cpu().numpy()
+    assert np.all(got[R * 3 * W * H:] == SENT), 'written behind the planes'
+    got = got[:R * 3 * W * H].reshape(R, 3, W * H)
+    for r in range(R):
+        xw, yw, gr = (v[..., :n[r]] for v in worlds[r])
+        total, mag, count = S.scatter_reference(W, H, xw, yw, gr, coefs)
+        one, many, worst = S.check_scatter(got[r], total, mag, count, f'replica {r}')
+        print(f'gather_scale_backward_batch replica {r}, {n[r]} slots on {W}x{H}: {one} cells with one term (bits), {many} with several: '
+              f'worst error {worst:.3f} of the bound')
+        if r == 0:
+            assert one > 3 * W * H // 4 and many > 3 * W * H * 2 // 5
+        else:
+            assert 0 < np.count_nonzero(got[r]) <= 3 * n[r] and one > 2 * n[r]     # 300 slots' terms and nothing of replica 0's
 
 
 # ------------------------------------------------------------------------------------------------ 2. the entry point
@@ -154,6 +234,43 @@ def test_env_step_backward_batch_is_env_step_backward_per_replica(name):
         assert np.all(gd[r, n[r]:].view(np.uint32) == 0), (r, 'padding')                          # exactly +0
         assert gd[r, 2] == 0 and gd[r, 3] == 0 and gd[r, 0] == gc[r, 0] and gd[r, 1] == gc[r, W * H - 1]
     assert np.abs(gc).max() > 0
+
+
+def test_env_step_backward_batch_gathers_full_blocks():
+    """Gap 1 of LABBOOK §33 (k_gather_cells_batch): R = 3 rows of agent_stride = 3 * 1024 + 5 entries with n = (3077, 1025, 0) —
+    four workgroups a row, every run q = 0 .. 3 loaded and stored, row 1's n[r] inside workgroup 1's first run while agent_stride
+    goes on (the padding store of +0 from later runs and later workgroups), row 2 padding only.  Behind n[r] the cells hold valid
+    indices of the plane: read as an index they would fetch a gradient.  Replica r is the stand-alone call on its row, bit for bit."""
+    (W, H), R, stride, n = S.GATHER_PLANE, 3, S.GATHER_BATCH_STRIDE, S.GATHER_BATCH_N
+    sigma, decay = 0.8, 0.1
+    g_host, cells_host, junk = S.gather_batch_case()
+    g, cells = torch.from_numpy(g_host).to(DEV), torch.from_numpy(cells_host).to(DEV)
+    b = L.Batch(R, 0, W * H, stride, 1, (C.c_int64 * 64)(*(list(n) + [0] * (64 - R))))
+    runs = []
+    for _ in range(2):
+        gc, gd = _sentinel(R * W * H + TAIL), _sentinel(R * stride + TAIL)
+        rc = L.lib.die_env_step_backward_batch(W, H, C.byref(b), _ptr(g), sigma, decay, None, None, _ptr(cells), _ptr(gc), _ptr(gd), stream_ptr(DEV))
+        assert rc == 0, L.lib.die_last_error()
+        runs.append((gc, gd))
+    torch.cuda.synchronize()
+    gc, gd = runs[0][0].cpu().numpy(), runs[0][1].cpu().numpy()
+    assert np.all(gc[R * W * H:] == SENT) and np.all(gd[R * stride:] == SENT), 'written behind the buffers'
+    assert np.array_equal(runs[1][0].cpu().numpy().view(np.uint32), gc.view(np.uint32))             # two runs, the same bits
+    assert np.array_equal(runs[1][1].cpu().numpy().view(np.uint32), gd.view(np.uint32))
+    assert np.array_equal(cells.cpu().numpy(), cells_host)
+    gc, gd = gc[:R * W * H].reshape(R, W * H), gd[:R * stride].reshape(R, stride)
+    for r in range(R):
+        want_c, want_d = _sentinel(W * H + TAIL), _sentinel(n[r] + TAIL)
+        rc = L.lib.die_env_step_backward(W, H, _ptr(g[r]), sigma, decay, n[r], _ptr(cells[r]), _ptr(want_c), _ptr(want_d), stream_ptr(DEV))
+        assert rc == 0, L.lib.die_last_error()
+        want_d = want_d.cpu().numpy()
+        assert np.all(want_d[n[r]:] == SENT)
+        assert np.array_equal(gc[r].view(np.uint32), want_c.cpu().numpy()[:W * H].view(np.uint32)), r
+        assert np.array_equal(gd[r, :n[r]].view(np.uint32), want_d[:n[r]].view(np.uint32)), r
+        assert np.array_equal(gd[r, :n[r]].view(np.uint32), S.gather_want(gc[r], cells_host[r, :n[r]]).view(np.uint32)), r
+        assert np.all(gd[r, n[r]:].view(np.uint32) == 0), (r, 'padding')                          # exactly +0
+        assert junk[r, n[r]:].all() and np.count_nonzero(S.gather_want(gc[r], cells_host[r, n[r]:])) == stride - n[r]   # (read, it would show)
+        assert n[r] == 0 or np.count_nonzero(gd[r, :n[r]]) > n[r] // 2
 
 
 # ------------------------------------------------------------------------------------------------ 3. <A x, y> = <x, A^T y>

@@ -13,7 +13,9 @@ Ceilings, none of them taken from what the device gives:
 
 Every ctypes call writes into buffers with a sentinel tail that must come back untouched; a test enqueues its launches on one
 stream and synchronises before it reads anything back.  Shapes: 16 x 64 is one conv tile, 24 x 68 straddles tiles with H % 4 == 0
-(the row sweep), 17 x 66 takes the LDS-tiled diffusion, 8 x 12 is smaller than a tile."""
+(the row sweep), 17 x 66 takes the LDS-tiled diffusion, 8 x 12 is smaller than a tile.  The entry points at full blocks (LABBOOK
+§33; sizes in tests/grad_midsize_shapes.py, their premises in tests/test_grad_midsize_cpu.py): the gather at 255 ... 8 389 637
+entries, die_deposit_cells and die_gather_scale_backward at 2 097 665 slots."""
 import ctypes as C
 
 import numpy as np
@@ -26,6 +28,7 @@ from die_amd.device_array import _ptr, stream_ptr, unpermute
 from oracle import cpu_ref as R
 from tests import dropout_model as D
 from tests import field_step_adjoint_model as F
+from tests import grad_midsize_shapes as S
 
 pytestmark = pytest.mark.gpu
 
@@ -106,11 +109,11 @@ def test_differentiable_step_equals_step(W, H, sigma, sort_every):
 
 
 # ------------------------------------------------------------------------------------------------ 2. who deposited where
-def _ref_cells(env, slot=None):
-    """The oracle's ownership on the device's coordinates: RefEnv's cells and alive index, the reference's fancy-index assignment
-    (the LAST alive slot in index order stays), entry n's cell if it is that slot."""
-    a = env.agents.to_numpy()                                     # slot order
-    ref = R.RefEnv(env.medium.to_numpy(), a)
+def ref_cells_of(medium, agents, slot=None):
+    """The oracle's ownership on given (3, W, H) / (4, N) host arrays in slot order: RefEnv's cells and alive index, the reference's
+    fancy-index assignment (the LAST alive slot in index order stays), entry n's cell if it is that slot."""
+    a = np.asarray(agents)
+    ref = R.RefEnv(medium, a)
     W, H = ref.field_size
     ix, iy = ref.cells_of(ref.agents[[0, 1]])
     idx = ref.alive_index()
@@ -118,6 +121,11 @@ def _ref_cells(env, slot=None):
     owner[ix[idx], iy[idx]] = idx
     want = np.where((a[2] > 0) & (owner[ix, iy] == np.arange(a.shape[1])), ix * H + iy, -1).astype(np.int32)
     return want if slot is None else want[slot]
+
+
+def _ref_cells(env, slot=None):
+    """ref_cells_of on the device's coordinates."""
+    return ref_cells_of(env.medium.to_numpy(), env.agents.to_numpy(), slot)
 
 
 def _deposit_cells(env, agents_struct, N):
@@ -163,6 +171,45 @@ def test_deposit_cells_against_the_oracle_ownership():
     # 111 alive slots hop over 1024 cells: about six more lose a cell they walked onto, per step; slot 11 keeps its cell unless a
     # higher slot id walks onto it
     assert winners > 33 * 0.8 * N and top >= 17
+
+
+def stepped_slot_env(W, H, N, rs):
+    """An Env of N slots in slot order, about half of them alive anywhere on the plane, after one step of random hops and deposits:
+    its claim plane is what die_deposit_cells reads.  Returns (env, x words, y words, alive) of the device's arrays after the step."""
+    alive = rs.rand(N) < 0.5
+    agents = np.stack([rs.rand(N), rs.rand(N), alive.astype(np.float64), np.ones(N)])
+    occ = np.zeros((W, H))
+    occ[R.cell(agents[0][alive], W), R.cell(agents[1][alive], H)] = 1.0
+    env = die.Env.from_numpy(np.stack([occ, rs.rand(W, H), rs.rand(W, H)]), agents, die.Dynamics(), device=DEV, sort_every=0)
+    env.step(np.stack([rs.uniform(-0.05, 0.05, N), rs.uniform(-0.05, 0.05, N), rs.uniform(0.5, 2.0, N)]).astype(np.float32))
+    assert env.agents.slot is None and env.agents.N == N
+    x, y, up = (t.cpu().numpy() for t in (env.agents.x, env.agents.y, env.agents.alive))
+    return env, x.view(np.uint32), y.view(np.uint32), up
+
+
+def test_deposit_cells_past_the_grid_cap():
+    """Gap 2 of LABBOOK §33 (k_deposit_cells): 2 097 665 slots, more than the 8192 x 256 threads of the capped grid — every thread
+    takes a second slot and the last 513 slots are reached only by that second trip.  About half the slots are alive on 256 x 256
+    cells, so nearly every cell is shared and the highest alive slot id must own it whichever trip read it.  The claim plane is
+    the one an Env of that many slots leaves after one step; the winners are the loop-free rule of tests/grad_midsize_shapes.py
+    (checked against `ref_cells_of` in tests/test_grad_midsize_cpu.py).  In slot order, and permuted with a slot array."""
+    (W, H), N = S.DEPOSIT_PLANE, S.SLOT_N
+    rs = np.random.RandomState(21)
+    env, x, y, up = stepped_slot_env(W, H, N, rs)
+    A = env.agents
+    want = S.winner_cells(W, H, x, y, up)
+    n_alive, n_won = int((up > 0).sum()), int((want >= 0).sum())
+    assert 0.4 * N < n_alive < 0.6 * N and up[-513:].any()
+    assert n_won > 0.99 * W * H and n_won < n_alive // 8             # nearly every cell is owned, and by one of many standing on it
+    assert (want[-513:] >= 0).any()                                  # the second trip alone reaches a winner
+    got = _deposit_cells(env, A.c_struct(), N)
+    assert np.array_equal(got, want), np.flatnonzero(got != want)[:8]
+    perm = rs.permutation(N)
+    p = torch.from_numpy(perm).to(DEV)
+    xs, ys, al, slot = A.x[p].contiguous(), A.y[p].contiguous(), A.alive[p].contiguous(), p.to(torch.int32).contiguous()
+    got = _deposit_cells(env, L.Agents(N, _ptr(xs), _ptr(ys), _ptr(al), _ptr(A.agent_food), _ptr(slot)), N)
+    assert np.array_equal(got, want[perm]), np.flatnonzero(got != want[perm])[:8]
+    assert np.array_equal(got, S.winner_cells(W, H, x[perm], y[perm], up[perm], perm))
 
 
 # ------------------------------------------------------------------------------------------------ 3. the entry point
@@ -219,6 +266,60 @@ def test_env_step_backward_entry_point(W, H, sigma):
     assert np.array_equal(g.cpu().numpy(), g_host) and np.all(in_place[2].cpu().numpy() == SENT)
     for rc, c2, d2 in bad:
         assert rc == -1 and np.all(c2.cpu().numpy() == SENT) and np.all(d2.cpu().numpy() == SENT)
+
+
+@pytest.mark.parametrize('N', S.GATHER_NS)
+def test_env_step_backward_gathers_full_blocks(N):
+    """Gap 1 of LABBOOK §33 (k_gather_cells): a workgroup takes 4 runs of 256 entries, n = base + q * 256, and no test had more than
+    about 150 entries — q >= 1 had never loaded or stored, no second workgroup (N > 1024) and no second grid-stride trip
+    (N > 8192 * 1024) had run.  Every size around a run, around a workgroup, four workgroups with a ragged last one, and 8 389 637
+    entries (the second trip fills workgroup 0 and starts workgroup 1).  grad_deposit word for word against the device's own
+    grad_chem; an index at or past W * H and INT32_MIN store +0; the tail stays; two runs give the same bits."""
+    (W, H), sigma, decay = S.GATHER_PLANE, 0.8, 0.1
+    g_host, cells_host = S.gather_case(N)
+    g, cells = torch.from_numpy(g_host).to(DEV), torch.from_numpy(cells_host).to(DEV)
+    runs = [_step_backward(W, H, g, sigma, decay, cells) for _ in range(2)]
+    torch.cuda.synchronize()
+    assert all(rc == 0 for rc, _, _ in runs), L.lib.die_last_error()
+    gc = _host(runs[0][1], W * H, 'grad_chem')
+    gd = _host(runs[0][2], N, 'grad_deposit')
+    ref = F.diffuse_decay(torch.as_tensor(g_host.astype(np.float64)), sigma, decay).numpy().reshape(-1)
+    assert float(np.abs(gc - ref).max() / max(1.0, np.abs(ref).max())) <= FWD_TOL
+    want = S.gather_want(gc, cells_host)
+    assert np.array_equal(gd.view(np.uint32), want.view(np.uint32)), np.flatnonzero(gd.view(np.uint32) != want.view(np.uint32))[:8]
+    out = (cells_host < 0) | (cells_host >= W * H)
+    assert np.all(gd[out].view(np.uint32) == 0)                   # exactly +0: losers, an index past the plane, INT32_MIN
+    assert {int(S.INT32_MIN), W * H, -1} <= set(cells_host[:7].tolist()) and {int(S.INT32_MIN), W * H, -1} <= set(cells_host[-7:].tolist())
+    assert 0.25 * N < out.sum() < 0.4 * N and np.count_nonzero(gd[~out]) == (~out).sum()      # the rest carries a gradient
+    assert gd[0] == gc[0] and gd[1] == gc[W * H - 1] and gd[-1] == gc[0] and gd[-2] == gc[W * H - 1]
+    assert np.array_equal(_host(runs[1][1], W * H, 'grad_chem').view(np.uint32), gc.view(np.uint32))
+    assert np.array_equal(_host(runs[1][2], N, 'grad_deposit').view(np.uint32), gd.view(np.uint32))
+    assert np.array_equal(cells.cpu().numpy(), cells_host)
+
+
+def test_gather_scale_backward_past_the_grid_cap():
+    """Gap 2 of LABBOOK §33 (k_gather_scale_backward): 2 097 665 slots, more than the capped grid's 8192 x 256 threads, on
+    1028 x 1024 cells — two slots a cell on average.  Against the float64 sum of the fp32 products the device forms exactly: a cell
+    with one non-zero term holds that term's bits, a cell with n terms is within (n - 1) * 2^-24 * sum|terms| (the worst case of an
+    fp32 sum in any order; the atomics fix none), a cell without a term is +0.  Both kinds of cell occur in good number."""
+    (W, H), N, coefs = S.SCATTER_PLANE, S.SLOT_N, S.SCATTER_COEFS
+    x, y, grads = S.scatter_world(W, H, N, np.random.RandomState(31))
+    xd, yd = (torch.from_numpy(v.view(np.int32).copy()).to(DEV) for v in (x, y))
+    g_dev = torch.from_numpy(grads).to(DEV)
+    planes = _sentinel(3 * W * H + TAIL)
+    m = L.Medium(W, H, L.DIE_F32, 1, None, None, None, None, 0, 0, 0, 0, 0, 0, 0, 0, None)         # the read-out reads the geometry only
+    a = L.Agents(N, _ptr(xd), _ptr(yd), None, None, None)
+    u = L.Action(N, g_dev[0].data_ptr(), g_dev[1].data_ptr(), g_dev[2].data_ptr())
+    ptrs = (C.c_void_p * 3)(*[planes.data_ptr() + 4 * q * W * H for q in range(3)])
+    L.check(L.lib.die_gather_scale_backward(C.byref(m), C.byref(a), C.byref(u), (C.c_float * 3)(*coefs), ptrs, stream_ptr(DEV)),
+            'die_gather_scale_backward')
+    torch.cuda.synchronize()
+    got = _host(planes, 3 * W * H, 'grad planes')
+    one, many, worst = S.check_scatter(got, *S.scatter_reference(W, H, x, y, grads, coefs))
+    print(f'gather_scale_backward {N} slots on {W}x{H}: {one} cells with one term (bits), {many} with several: worst error {worst:.3f} of '
+          f'the bound (n - 1) * 2^-24 * sum|terms|')
+    assert one > 3 * W * H // 4 and many > 3 * W * H * 2 // 5        # about 0.32 and 0.47 of the 3 * W * H cells (1.6 terms a cell)
+    assert np.array_equal(g_dev.cpu().numpy(), grads)
 
 
 # ------------------------------------------------------------------------------------------------ 4. <A x, y> = <x, A^T y>
