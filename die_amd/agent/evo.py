@@ -22,6 +22,24 @@ from .base import Agent, save_args
 _CHECKPOINT_KEYS = ('params_dict', 'model_state')      # the layout of a saved agent (core/agent/evo.py:24-42): kept, so that files interchange
 
 
+def _omit_defaults(params: Dict[str, Any], *names: str) -> None:
+    """Takes the named constructor arguments out of `params` (an `init_params` dict) while they are at their default — None, 0 or
+    False: the arguments the reference does not have, so that a saved agent without them stays loadable by the reference."""
+    for name in names:
+        if name in params and not params[name]:
+            del params[name]
+
+
+def _layer_arrays(li: int, w: th.Tensor, planes, dst: th.Tensor):
+    """What a narrow layer launch takes beside its weights `w`: the input `planes` [(tensor, DIE_PLANE_* kind)] as a die_conv_plane
+    array and the first cout planes of `dst` as a pointer array — or the ValueError of a weight that does not fit the planes."""
+    cout, cin, k, k2 = w.shape
+    if k != k2 or cin != len(planes):
+        raise ValueError(f'layer {li}: weight {tuple(w.shape)} does not fit {len(planes)} input planes')
+    return ((_lib.ConvPlane * cin)(*[_lib.ConvPlane(t.data_ptr(), kind, 0) for t, kind in planes]),
+            (C.c_void_p * cout)(*[dst[o].data_ptr() for o in range(cout)]))
+
+
 class TorchAgent(Agent, nn.Module):
     """An agent whose behaviour is a torch model (core/agent/evo.py:18-42): `save` writes the constructor arguments and the
     model's state_dict under the reference's two keys, `load` rebuilds the agent from them."""
@@ -75,11 +93,7 @@ class ConvolutionModel(nn.Module):
                  memory_channels: int = 0,
                  ):
         self._init_params = save_args(self.__init__, locals())
-        for name in ('hidden_channels', 'hidden_activation'):
-            if self._init_params[name] is None:
-                del self._init_params[name]
-        if not memory_channels:
-            del self._init_params['memory_channels']
+        _omit_defaults(self._init_params, 'hidden_channels', 'hidden_activation', 'memory_channels')
         if hidden_channels is not None:
             if isinstance(hidden_channels, bool) or int(hidden_channels) != hidden_channels or \
                     not 1 <= hidden_channels <= _lib.NCA_WIDE_MAX_CHANNELS:
@@ -228,23 +242,16 @@ class NeuralAutomataAgent(TorchAgent):
                 int(memory_channels) != memory_channels or not 0 <= memory_channels <= _lib.MEMORY_MAX_CHANNELS:
             raise ValueError(f'memory_channels={memory_channels!r}: an integer in 1..{_lib.MEMORY_MAX_CHANNELS}, or 0 / None for none')
         self.memory_channels = int(memory_channels)
-        if self.memory_channels:
-            self._init_params['memory_channels'] = self.memory_channels
-        else:                                                 # (kept out while 0, as with_stock_channel is while False)
-            del self._init_params['memory_channels']
         self.memory: Optional[th.Tensor] = None                # (M, N) float32 by slot id, from the first forward on
         self._memory_rebind = True                             # the next forward may allocate for its own N
         self._memory_planes = {}                               # (W, H, device) -> (M, W, H) float32: the expanded memory
         if not isinstance(with_stock_channel, (bool, np.bool_)):
             raise ValueError(f'with_stock_channel={with_stock_channel!r}: True or False')
         self.with_stock_channel = bool(with_stock_channel)
-        if self.with_stock_channel:
-            self._init_params['with_stock_channel'] = True
-        else:                                                 # (kept out while False, as dropout_seed is while None)
-            del self._init_params['with_stock_channel']
-        for name in ('hidden_channels', 'hidden_activation'):  # (kept out while None, as dropout_seed is: see ConvolutionModel)
-            if self._init_params['model_kwargs'].get(name, 0) is None:
-                del self._init_params['model_kwargs'][name]
+        # (saved as the checked values; kept out while at their defaults, as dropout_seed is while None: see ConvolutionModel)
+        self._init_params.update(memory_channels=self.memory_channels, with_stock_channel=self.with_stock_channel)
+        _omit_defaults(self._init_params, 'memory_channels', 'with_stock_channel')
+        _omit_defaults(self._init_params['model_kwargs'], 'hidden_channels', 'hidden_activation')
         super().__init__()
         self.dropout_seed = dropout_seed
         self.dropout_step = 0
@@ -336,6 +343,28 @@ class NeuralAutomataAgent(TorchAgent):
             raise NotImplementedError(f'memory_channels={self.memory_channels} on a decomposed medium (die_amd/dist.py): the standing '
                                       'plane is built for periodic single-tile planes only')
 
+    def _check_differentiable(self, what: str, wide_ok: bool = False):
+        """What no differentiable call takes — memory channels, a wide stack (unless `wide_ok`: the wide twin,
+        BatchedNeuralAutomataAgent.forward_device), the stock channel — refused in that order, before any launch."""
+        self._check_memory(what)
+        if not wide_ok:
+            self._check_wide(what)
+        self._check_stock(what)
+
+    def _field_planes(self, medium) -> Dict[str, Any]:
+        """The observation channels the medium itself holds, as first-layer source planes: channel -> (tensor, DIE_PLANE_* kind)."""
+        medium._ensure_owner()
+        fkind = _lib.DIE_PLANE_F32 if medium.dtype == th.float32 else _lib.DIE_PLANE_F16
+        return {'agents': (medium.owner, _lib.DIE_PLANE_AGENTS), 'env_food': (medium.food, fkind), 'chem1': (medium.chem, fkind)}
+
+    def _dropout(self) -> Optional[_lib.NcaDropout]:
+        """die_nca_dropout of the coming call — the counter-based mask of `dropout_seed` at `dropout_step`, applied inside the last
+        layer's launch — or None where nothing is masked that way (no seed, eval mode, p = 0)."""
+        model = self._model
+        if self._dropout_seed is None or not (model.agent_dropout.p > 0 and model.training):
+            return None
+        return _lib.nca_dropout(model.agent_dropout.p, self._dropout_seed, 0, self.dropout_step)
+
     def reset_memory(self) -> None:
         """Blank memory: zero it where it is, and let the next forward allocate anew if its agents have another N."""
         if self.memory is not None:
@@ -422,9 +451,7 @@ class NeuralAutomataAgent(TorchAgent):
         weights = self._device_weights(dev)
         sp = stream_ptr(dev)
         wide = self._model.wide
-        medium._ensure_owner()
-        fkind = _lib.DIE_PLANE_F32 if medium.dtype == th.float32 else _lib.DIE_PLANE_F16
-        src = {'agents': (medium.owner, _lib.DIE_PLANE_AGENTS), 'env_food': (medium.food, fkind), 'chem1': (medium.chem, fkind)}
+        src = self._field_planes(medium)
         standing = self._stock_plane(medium, agents) if self.with_stock_channel or self.memory_channels else None
         if self.with_stock_channel:
             src['agent_food'] = (standing, _lib.DIE_PLANE_STOCK)
@@ -434,18 +461,11 @@ class NeuralAutomataAgent(TorchAgent):
                 src[f'memory_{j}'] = (expanded[j], _lib.DIE_PLANE_F32)
         planes = [src[c] for c in self.obs_channels]
         sets = self._scratch(W, H, dev, 2, max(4, *(w.shape[0] for w in weights)) if wide else 4)
-        p = self._model.agent_dropout.p
-        masked = p > 0 and self._model.training
-        drop = None                                              # the counter-based mask: inside the last layer's launch
-        if masked and self._dropout_seed is not None:
-            drop = _lib.nca_dropout(p, self._dropout_seed, 0, self.dropout_step)
+        drop = self._dropout()
         for li, w in enumerate(weights):
-            cout, cin, k, k2 = w.shape
-            if k != k2 or cin != len(planes):
-                raise ValueError(f'layer {li}: weight {tuple(w.shape)} does not fit {len(planes)} input planes')
+            cout, cin, k, _ = w.shape
             dst = sets[li % 2]
-            cin_arr = (_lib.ConvPlane * cin)(*[_lib.ConvPlane(t.data_ptr(), kind, 0) for t, kind in planes])
-            out_arr = (C.c_void_p * cout)(*[dst[o].data_ptr() for o in range(cout)])
+            cin_arr, out_arr = _layer_arrays(li, w, planes, dst)
             last = li == len(weights) - 1
             pad = _lib.PAD_MODES[self._model.conv_layers()[li].padding_mode]
             if wide:                                             # every layer of a wide stack: die_conv2d_wide
@@ -461,7 +481,7 @@ class NeuralAutomataAgent(TorchAgent):
         out = sets[(len(weights) - 1) % 2][:len(planes)]         # the last layer's planes (scratch: valid until the next call)
         if self._dropout_seed is not None:
             self.dropout_step += 1                               # counts forward calls, masked or not
-        elif masked:                                             # rare path: the torch-RNG mask of core/agent/evo.py:114-116
+        elif self._model.agent_dropout.p > 0 and self._model.training:     # rare path: the torch-RNG mask of core/agent/evo.py:114-116
             out = out * self._model.agent_dropout(th.ones((W, H), device=dev))
         return out
 
@@ -504,9 +524,7 @@ class NeuralAutomataAgent(TorchAgent):
         A wide stack (`hidden_channels` / `hidden_activation`) is refused here: NotImplementedError, before any launch and before
         `dropout_step` moves.  Its gradients come from `ConvolutionModel.forward_device` and `die_amd.functional`.  An agent with
         the stock channel (`with_stock_channel=True`) is refused the same way: its plane is piecewise constant in the weights."""
-        self._check_memory('differentiable_sense')
-        self._check_wide('differentiable_sense')
-        self._check_stock('differentiable_sense')
+        self._check_differentiable('differentiable_sense')
         layers = self._model.conv_layers()
         for k in layers:
             if k.padding_mode not in ('circular', 'zeros'):
@@ -531,9 +549,7 @@ class NeuralAutomataAgent(TorchAgent):
         non-zero gradient stand on one cell their terms are summed by fp32 atomic adds in arrival order; otherwise (alive agents
         never share a cell) the gradients are bit-reproducible run to run.  A wide stack raises NotImplementedError, as in
         `differentiable_sense`, and so does an agent with the stock channel."""
-        self._check_memory('differentiable_action')
-        self._check_wide('differentiable_action')
-        self._check_stock('differentiable_action')
+        self._check_differentiable('differentiable_action')
         agents, medium = obs
         sense = self.differentiable_sense(medium)
         self._sense_output = sense.detach()
@@ -555,26 +571,18 @@ class _DifferentiableSense(th.autograd.Function):
         dev, W, H = medium.device, medium.W, medium.H
         ctx.chem_channel = None if chem_node is None else agent.obs_channels.index('chem1')     # (its values ARE medium.chem's)
         sp = stream_ptr(dev)
-        medium._ensure_owner()
-        fkind = _lib.DIE_PLANE_F32 if medium.dtype == th.float32 else _lib.DIE_PLANE_F16
-        src = {'agents': (medium.owner, _lib.DIE_PLANE_AGENTS), 'env_food': (medium.food, fkind), 'chem1': (medium.chem, fkind)}
+        src = agent._field_planes(medium)
         planes = src_planes = [(src[c][0].clone(), src[c][1]) for c in agent.obs_channels]     # as they are now: the medium will be stepped
-        p = agent._model.agent_dropout.p
-        drop = None
-        if p > 0 and agent._model.training and agent._dropout_seed is not None:
-            drop = _lib.nca_dropout(p, agent._dropout_seed, 0, agent.dropout_step)
+        drop = agent._dropout()
         pads = [_lib.PAD_MODES[k.padding_mode] for k in agent._model.conv_layers()]
         first, hidden, out, tanh_out = [t for t, _ in planes], [], None, None
         for li, w in enumerate(weights):
-            cout, cin, k, k2 = w.shape
-            if k != k2 or cin != len(planes):
-                raise ValueError(f'layer {li}: weight {tuple(w.shape)} does not fit {len(planes)} input planes')
+            cout, cin, k, _ = w.shape
             last = li == len(weights) - 1
-            cin_arr = (_lib.ConvPlane * cin)(*[_lib.ConvPlane(t.data_ptr(), kind, 0) for t, kind in planes])
 
             def launch(masked):
                 dst = th.empty((cout, W, H), dtype=th.float32, device=dev)
-                out_arr = (C.c_void_p * cout)(*[dst[o].data_ptr() for o in range(cout)])
+                cin_arr, out_arr = _layer_arrays(li, w, planes, dst)
                 if masked:
                     _lib.check(_lib.lib.die_conv2d_dropout(W, H, cin, cin_arr, medium.epoch, cout, out_arr, k, _ptr(w), 1, pads[li],
                                                            C.byref(drop), sp), 'die_conv2d_dropout')

@@ -357,8 +357,8 @@ class BatchedEnv:
 
         One path for the three agent kinds.  What is particular to a kind it says itself: `_check_step(env)` (its refusals),
         `_replica_agent(r)` (replica r's stand-alone agent, large worlds), `_claim_epoch(env)` (the epoch its claims are made
-        at), `_launch(...)` (its struct and its library entry point) and `_stepped()` (its counters after a step).  A step that is
-        refused leaves the batch as it was."""
+        at), `_launch(...)` (its struct and its library entry point), `_stepped()` (its counters after a step) and
+        `_builds_stock_planes` (whether its step builds the env's stock planes).  A step that is refused leaves the batch as it was."""
         agent._check_step(self)                     # every refusal before anything is launched
         flow = self._flow_kind()
         act = None
@@ -366,9 +366,7 @@ class BatchedEnv:
             if self.per_replica:
                 raise NotImplementedError('step(action=...): large worlds (per_replica) step a stand-alone Env per replica; read '
                                           'each agent\'s own action there')
-            if (not isinstance(action, torch.Tensor) or tuple(action.shape) != (3, self.R, self.Nmax) or action.dtype != torch.float32
-                    or action.device != self.device or not action.is_contiguous() or action.requires_grad):
-                raise ValueError(f'action: a contiguous (3, {self.R}, {self.Nmax}) float32 tensor on {self.device} (no grad)')
+            self._check_action(action, 'no grad', no_grad=True)
             act = _lib.Action(self.Nmax, action[0].data_ptr(), action[1].data_ptr(), action[2].data_ptr())
         if results is None:
             results = torch.empty((self.R, 2), dtype=torch.float64, device=self.device)
@@ -388,27 +386,43 @@ class BatchedEnv:
             raise
         agent._calls += 1
         agent._stepped()
+        return self._launched(flow, m, a, b, results, agent._builds_stock_planes)
+
+    def _launched(self, flow: Optional[int], m, a, b, results: torch.Tensor, built_stock_planes: bool = False) -> torch.Tensor:
+        """What follows the launches of `step` and of `step_action` alike: the births, the plane swap, the flow, the counters."""
         self._serial += 1
-        # this step built the stock planes (a population with memory builds them as its standing planes): the next may build on top
-        if getattr(agent, '_stock_channel', False) or getattr(agent, '_memory_channels', 0):
+        if built_stock_planes:                      # (a population with memory builds them as its standing planes): the next may build on top
             self._stock_serial = self._serial
         if self.dynamics.agents_born:
             self._births(a, b, results)
         self.chem_node = None                       # the field changed: an autograd handle of the chem planes ends here
-        self.chem, self.chem_next = self.chem_next, self.chem
+        self.chem, self.chem_next = self.chem_next, self.chem      # (differentiable_step sets this step's node afterwards)
         self._food_flow(flow, m, b)
         self._steps += 1
         return results
 
-    def _check_action(self, action) -> None:
-        """The (3, R, Nmax) action tensor of `step_action`, or the ValueError that says what it must be."""
-        want = (3, self.R, self.Nmax)
-        if (not isinstance(action, torch.Tensor) or tuple(action.shape) != want or action.dtype != torch.float32
-                or action.device != self.device or not action.is_contiguous()):
-            got = (tuple(action.shape), action.dtype, str(action.device), action.stride()) if isinstance(action, torch.Tensor) \
-                else type(action).__name__
-            raise ValueError(f'action: a contiguous {want} float32 tensor on {self.device} (rows dx, dy, deposit; replica r reads '
-                             f'[:, r, :n[r]]), got {got}')
+    def _advance_claim_epoch(self) -> None:
+        """Claims at the next epoch; at the wrap the claim planes start over.  For every step whose sensing does not read the
+        claim planes: the two Physarum kinds' (their `_claim_epoch`) and `step_action`'s."""
+        self.epoch += 1
+        if self.epoch > _lib.OWNER_EPOCH_MAX:
+            self.owner.zero_()
+            self.epoch = 1
+
+    def _check_action(self, action, note: str, contiguous: bool = True, no_grad: bool = False) -> None:
+        """The (3, R, Nmax) float32 action tensor of `step(action=...)`, `step_action` and `differentiable_step`, or the ValueError
+        that says what it must be — `note`: what the caller adds in brackets; `no_grad`: the tensor the recording step writes into,
+        which says only what it takes; the others also what they got."""
+        want, tensor = (3, self.R, self.Nmax), isinstance(action, torch.Tensor)
+        if (tensor and tuple(action.shape) == want and action.dtype == torch.float32 and action.device == self.device
+                and (action.is_contiguous() or not contiguous) and not (no_grad and action.requires_grad)):
+            return
+        got = ''
+        if not no_grad and not tensor:
+            got = f', got {type(action).__name__}'
+        elif not no_grad:
+            got = f', got {(tuple(action.shape), action.dtype, str(action.device)) + ((action.stride(),) if contiguous else ())}'
+        raise ValueError(f"action: a {'contiguous ' if contiguous else ''}{want} float32 tensor on {self.device} ({note}){got}")
 
     def step_action(self, action: torch.Tensor, results: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One step of every replica with the caller's actions: `Env.step(action)` of R worlds, no agent forward (an own torch
@@ -419,7 +433,7 @@ class BatchedEnv:
         under per-replica Dynamics), one more with dead slots, the sweep(s), one more with a flow.  Large worlds (per_replica): every
         replica's own `Env.step` on its stream.  Returns the (R, 2) result words as `step` does; a refused step leaves the batch as
         it was."""
-        self._check_action(action)                  # every refusal before anything is launched
+        self._check_action(action, 'rows dx, dy, deposit; replica r reads [:, r, :n[r]]')      # every refusal before anything is launched
         flow = self._flow_kind()
         action = action.detach()
         if results is None:
@@ -428,10 +442,7 @@ class BatchedEnv:
             self._step_per_replica(_ReplicaActions(action, self.n), flow, results)
             return results
         epoch = self.epoch
-        self.epoch += 1                             # claims at the next epoch; at the wrap the claim planes start over
-        if self.epoch > _lib.OWNER_EPOCH_MAX:       # (as _PhysarumReplicas._claim_epoch)
-            self.owner.zero_()
-            self.epoch = 1
+        self._advance_claim_epoch()
         m, a, dyn, b = self._structs()
         act = _lib.Action(self.Nmax, action[0].data_ptr(), action[1].data_ptr(), action[2].data_ptr())
         args = (C.byref(m), C.byref(a), C.byref(act), C.byref(dyn), C.byref(b), _ptr(results), _ptr(self._ws), self._ws.numel())
@@ -444,14 +455,7 @@ class BatchedEnv:
         except Exception:
             self.epoch = epoch                      # refused before any launch: nothing changed
             raise
-        self._serial += 1
-        if self.dynamics.agents_born:
-            self._births(a, b, results)
-        self.chem_node = None                       # (differentiable_step sets this step's node afterwards)
-        self.chem, self.chem_next = self.chem_next, self.chem
-        self._food_flow(flow, m, b)
-        self._steps += 1
-        return results
+        return self._launched(flow, m, a, b, results)
 
     # ------------------------------------------------------------------ the differentiable step (die_env_grad.hip, batched)
     def _check_differentiable(self, what: str) -> None:
@@ -489,11 +493,7 @@ class BatchedEnv:
         self._check_differentiable('differentiable_step')
         if self.dynamics.agents_born:
             raise NotImplementedError('differentiable_step: agents_born is not supported (a newborn has no action to differentiate)')
-        want = (3, self.R, self.Nmax)
-        if not isinstance(action, torch.Tensor) or tuple(action.shape) != want or action.dtype != torch.float32 or action.device != self.device:
-            got = (tuple(action.shape), action.dtype, str(action.device)) if isinstance(action, torch.Tensor) else type(action).__name__
-            raise ValueError(f'action: a {want} float32 tensor on {self.device} (BatchedNeuralAutomataAgent.differentiable_action), '
-                             f'got {got}')
+        self._check_action(action, 'BatchedNeuralAutomataAgent.differentiable_action', contiguous=False)
         prev = self.chem_node
         results = self.step_action(action.detach().contiguous(), results)
         cells = torch.empty((self.R, self.Nmax), dtype=torch.int32, device=self.device)
@@ -736,11 +736,8 @@ class _PhysarumReplicas:
     def _replica_agent(self, r: int):
         return self.agents[r]
 
-    def _claim_epoch(self, env: BatchedEnv) -> None:
-        env.epoch += 1
-        if env.epoch > _lib.OWNER_EPOCH_MAX:
-            env.owner.zero_()
-            env.epoch = 1
+    _claim_epoch = staticmethod(BatchedEnv._advance_claim_epoch)      # `_claim_epoch(env)`: senses and claims at one epoch, the next
+    _builds_stock_planes = False                    # (a step of this kind leaves the env's stock planes alone)
 
     def _stepped(self) -> None:
         pass
@@ -1108,6 +1105,8 @@ class BatchedNeuralAutomataAgent(_Population):
         self._wide = template.model.wide            # hidden_channels / hidden_activation: die_nca_wide_env_step_batch
         self._stock_channel = template.with_stock_channel      # the *_stock entry points: one launch more, layer 0 one plane more
         self._memory_channels = template.memory_channels       # die_nca_wide_env_step_batch_memory: L + 5 launches
+        # this population's step builds the env's stock planes (with memory: as its standing planes), so the next may build on top
+        self._builds_stock_planes = bool(self._stock_channel or self._memory_channels)
         self.memory = None                          # (R, M, Nmax) float32 by slot id (small worlds; large ones: agents[r].memory)
         if self._memory_channels:
             self.reset = self.reset_memory          # on the INSTANCE: the searchers call `reset()` where a population has one
@@ -1247,72 +1246,76 @@ class BatchedNeuralAutomataAgent(_Population):
         """BatchedPhysarumAgent._launch with the dropout mask of the coming step after the workspace: one entry point without
         it, one with it (the same step, its last conv launch masked), and with Dynamics rows one for both, the mask nullable."""
         drop = self._dropout()
-        if self._memory_channels:                   # as the stock call, then M, the memory, its planes, and whether layer 0 reads the stock
-            name = 'die_nca_wide_env_step_batch_memory'
-            _lib.check(getattr(_lib.lib, name)(*front, C.byref(self._struct(self._sense_epoch)), *back,
-                                               None if drop is None else C.byref(drop), *(rows or (None, None)),
-                                               _ptr(self.env._stock_planes()), self._memory_channels, _ptr(self.memory),
-                                               _ptr(self._memory_planes), int(self._stock_channel), stream), name)
-            return
-        if self._stock_channel:                     # the mask and the two tables nullable, the env's stock planes after them
-            name = 'die_nca_wide_env_step_batch_stock' if self._wide else 'die_nca_env_step_batch_stock'
-            _lib.check(getattr(_lib.lib, name)(*front, C.byref(self._struct(self._sense_epoch)), *back,
-                                               None if drop is None else C.byref(drop), *(rows or (None, None)),
-                                               _ptr(self.env._stock_planes()), stream), name)
-            return
-        if self._wide:                              # one entry point: the mask and the two tables are all nullable
-            _lib.check(_lib.lib.die_nca_wide_env_step_batch(*front, C.byref(self._struct(self._sense_epoch)), *back,
-                                                            None if drop is None else C.byref(drop), *(rows or (None, None)), stream),
-                       'die_nca_wide_env_step_batch')
-            return
-        mask = () if drop is None else (C.byref(drop),)
-        if rows:
-            name, mask = 'die_nca_env_step_batch_rows', mask or (None,)
+        mask = None if drop is None else C.byref(drop)
+        if self._wide or self._stock_channel:       # ONE entry point whatever is set: the mask and the two tables are all nullable
+            tail = (mask, *(rows or (None, None)))
+            if self._memory_channels:               # then the env's stock planes, M, the memory, its planes, whether layer 0 reads the stock
+                name = 'die_nca_wide_env_step_batch_memory'
+                tail += (_ptr(self.env._stock_planes()), self._memory_channels, _ptr(self.memory), _ptr(self._memory_planes),
+                         int(self._stock_channel))
+            elif self._stock_channel:               # then the env's stock planes
+                name = 'die_nca_wide_env_step_batch_stock' if self._wide else 'die_nca_env_step_batch_stock'
+                tail += (_ptr(self.env._stock_planes()),)
+            else:
+                name = 'die_nca_wide_env_step_batch'
+        elif rows:
+            name, tail = 'die_nca_env_step_batch_rows', (mask, *rows)
+        elif drop is None:
+            name, tail = 'die_nca_env_step_batch', ()
         else:
-            name = 'die_nca_env_step_batch' if drop is None else 'die_nca_env_step_batch_dropout'
-        _lib.check(getattr(_lib.lib, name)(*front, C.byref(self._struct(self._sense_epoch)), *back, *mask, *rows, stream), name)
+            name, tail = 'die_nca_env_step_batch_dropout', (mask,)
+        _lib.check(getattr(_lib.lib, name)(*front, C.byref(self._struct(self._sense_epoch)), *back, *tail, stream), name)
+
+    def _nca_batch(self, base: int, sense_epoch: int, scratch: Optional[torch.Tensor] = None):
+        """(layer array, die_nca_batch) reading the (C, P) matrix at address `base` (a wide stack's layers carry their activation,
+        0 for a narrow one's); `scratch`: the step's planes, none for the calls that keep every layer in caller-owned storage."""
+        layers = (_lib.NcaLayer * len(self._layers))(*[_lib.NcaLayer(k, cin, cout, act, base + 4 * off, self.P)
+                                                        for (k, cin, cout, off), act in zip(self._layers, self._acts)])
+        nca = _lib.NcaBatch(len(self._layers), _lib.PAD_MODES[self._arch['boundary'][0]], int(self._arch['with_agent_channel']), sense_epoch,
+                            layers, (C.c_float * 3)(*self.template.action_coefs), 0 if self.episodes == 1 else self.episodes,
+                            _ptr(scratch), 0 if scratch is None else scratch.numel() * 4)
+        return layers, nca
 
     def _struct(self, sense_epoch: int) -> _lib.NcaBatch:
+        """The step's die_nca_batch: built once per `parameters` storage, only the sensing epoch is written every step."""
         base = self.parameters.data_ptr()
         if self._c is None or self._c[0] != base:
-            layers = (_lib.NcaLayer * len(self._layers))(*[_lib.NcaLayer(k, cin, cout, act, base + 4 * off, self.P)
-                                                            for (k, cin, cout, off), act in zip(self._layers, self._acts)])
-            nca = _lib.NcaBatch(len(self._layers), _lib.PAD_MODES[self._arch['boundary'][0]], int(self._arch['with_agent_channel']), 0,
-                                layers, (C.c_float * 3)(*self.template.action_coefs), 0 if self.episodes == 1 else self.episodes,
-                                _ptr(self._scratch),
-                                self._scratch.numel() * 4)
-            self._c = (base, layers, nca)
+            self._c = (base, *self._nca_batch(base, 0, self._scratch))
         nca = self._c[2]
         nca.sense_epoch = sense_epoch
         return nca
 
     # ------------------------------------------------------------------ the differentiable twins (die_nca_grad.hip, batched)
-    def _check_differentiable(self, parameters: Optional[torch.Tensor]) -> torch.Tensor:
-        """Every refusal of a differentiable call, before anything is launched; returns the matrix the call reads."""
+    def _check_differentiable(self, parameters: Optional[torch.Tensor], what: str = 'differentiable mode') -> torch.Tensor:
+        """Every refusal of a differentiable call, before anything is launched; returns the matrix the call reads.  `what`: the
+        word the messages carry — 'differentiable mode' for the narrow calls, 'forward_device' for the wide twin, which takes a wide
+        stack and refuses a narrow one."""
+        wide = what == 'forward_device'
+        self.template._check_differentiable(what, wide_ok=wide)
+        if wide and not self._wide:
+            raise ValueError('forward_device: a narrow population (hidden_channels and hidden_activation both None) is differentiated '
+                             'by differentiable_sense')
         env = self.env
-        self.template._check_memory('differentiable mode')
-        self.template._check_wide('differentiable mode')
-        self.template._check_stock('differentiable mode')
         if env.per_replica:
-            raise NotImplementedError('differentiable mode: large worlds (per_replica) are not batched — a large world fills the GPU '
-                                      'through the stand-alone NeuralAutomataAgent.differentiable_action (replica_agent(r))')
+            alone = 'ConvolutionModel.forward_device (replica_agent(r).model)' if wide else \
+                'NeuralAutomataAgent.differentiable_action (replica_agent(r))'
+            raise NotImplementedError(f'{what}: large worlds (per_replica) are not batched — a large world fills the GPU '
+                                      f'through the stand-alone {alone}')
         if self._arch['boundary'][0] not in ('circular', 'zeros'):
-            raise NotImplementedError(f"boundary={self._arch['boundary'][0]!r} in differentiable mode: 'circular' or 'zeros' (step() "
+            raise NotImplementedError(f"boundary={self._arch['boundary'][0]!r} in {what}: 'circular' or 'zeros' (step() "
                                       f"takes all of {sorted(_lib.PAD_MODES)})")
         self._check_step(env)
         p = self.parameters if parameters is None else parameters
         self._check_parameters(p)
         return p
 
-    def _grad_struct(self, parameters: torch.Tensor, sense_epoch: int):
-        """(layer array, die_nca_batch) reading `parameters`, without the step's scratch (a wide stack's layers carry their
-        activation, 0 for a narrow one's)."""
-        base = parameters.data_ptr()
-        layers = (_lib.NcaLayer * len(self._layers))(*[_lib.NcaLayer(k, cin, cout, act, base + 4 * off, self.P)
-                                                        for (k, cin, cout, off), act in zip(self._layers, self._acts)])
-        nca = _lib.NcaBatch(len(self._layers), _lib.PAD_MODES[self._arch['boundary'][0]], int(self._arch['with_agent_channel']), sense_epoch,
-                            layers, (C.c_float * 3)(*self.template.action_coefs), 0 if self.episodes == 1 else self.episodes, None, 0)
-        return layers, nca
+    def _differentiable(self, parameters: Optional[torch.Tensor], what: str) -> torch.Tensor:
+        """`differentiable_sense` and `forward_device` alike: the refusals, the graph's node, the dropout counter."""
+        p = self._check_differentiable(parameters, what)
+        out = _BatchedSense.apply(self, p, self.env.chem_node)
+        if self.dropout_seed is not None:
+            self.dropout_step += 1
+        return out
 
     def differentiable_sense(self, parameters: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The sense planes of every replica with a `grad_fn`: (R, 3, W, H) float32, `out[r]` bit for bit replica r's stand-alone
@@ -1331,11 +1334,7 @@ class BatchedNeuralAutomataAgent(_Population):
         `dropout_step` moves.  Its gradients come from `forward_device` and `die_amd.functional.gather_scale_batch`.  A
         population with the stock channel (`with_stock_channel=True`) is refused the same way, here, in `differentiable_action`
         and in `forward_device`: the stock plane is piecewise constant in the weights and the adjoint calls do not take its kind."""
-        p = self._check_differentiable(parameters)
-        out = _BatchedSense.apply(self, p, self.env.chem_node)
-        if self.dropout_seed is not None:
-            self.dropout_step += 1
-        return out
+        return self._differentiable(parameters, 'differentiable mode')
 
     def differentiable_action(self, parameters: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The actions of every replica with a `grad_fn`: (3, R, Nmax) float32 in the batch's action layout (what
@@ -1364,25 +1363,7 @@ class BatchedNeuralAutomataAgent(_Population):
         call whenever a `dropout_seed` is set.  Refused before any launch and before `dropout_step` moves: a narrow population
         (ValueError: it has `differentiable_sense`), a population with the stock channel, large worlds (`per_replica`) and
         'reflect' / 'replicate' boundaries (NotImplementedError)."""
-        self.template._check_memory('forward_device')
-        self.template._check_stock('forward_device')
-        if not self._wide:
-            raise ValueError('forward_device: a narrow population (hidden_channels and hidden_activation both None) is differentiated '
-                             'by differentiable_sense')
-        env = self.env
-        if env.per_replica:
-            raise NotImplementedError('forward_device: large worlds (per_replica) are not batched — a large world fills the GPU '
-                                      'through the stand-alone ConvolutionModel.forward_device (replica_agent(r).model)')
-        if self._arch['boundary'][0] not in ('circular', 'zeros'):
-            raise NotImplementedError(f"boundary={self._arch['boundary'][0]!r} in forward_device: 'circular' or 'zeros' (step() "
-                                      f"takes all of {sorted(_lib.PAD_MODES)})")
-        self._check_step(env)
-        p = self.parameters if parameters is None else parameters
-        self._check_parameters(p)
-        out = _BatchedWideSense.apply(self, p, env.chem_node)
-        if self.dropout_seed is not None:
-            self.dropout_step += 1
-        return out
+        return self._differentiable(parameters, 'forward_device')
 
     def render(self, r: int) -> np.ndarray:
         """Replica r's last sense planes with the channel axis last: the stand-alone agent's `render()[0]`."""
@@ -1432,28 +1413,30 @@ class _BatchedFieldStep(torch.autograd.Function):
 
 
 class _BatchedSense(torch.autograd.Function):
-    """BatchedNeuralAutomataAgent.differentiable_sense: die_nca_sense_batch_store forward, die_nca_backward_batch backward — or, with
-    the env's chem node as an input, die_nca_backward_batch_inputs, whose chem channel is the node's gradient."""
+    """BatchedNeuralAutomataAgent.differentiable_sense and, for a population of wide stacks (`pop._wide`), forward_device.  Narrow:
+    die_nca_sense_batch_store forward, die_nca_backward_batch backward — or, with the env's chem node as an input that needs a
+    gradient, die_nca_backward_batch_inputs, whose chem channel is the node's gradient.  Wide: die_nca_wide_sense_batch_store and
+    die_nca_wide_backward_batch, ONE call which is given `grad_in` for such a node and null without one."""
 
     @staticmethod
     def forward(ctx, pop, parameters, chem_node=None):
         env = pop.env
-        R, W, H, L, dev = env.R, env.W, env.H, len(pop._layers), env.device
+        R, W, H, L, dev, Cm = env.R, env.W, env.H, len(pop._layers), env.device, pop._channels
         with_agents = pop._arch['with_agent_channel']
         # as they are now: the worlds will be stepped (the claim plane only where the first layer reads it)
         planes = [env.food.clone(), env.chem.clone()] + ([env.owner.clone()] if with_agents else [])
-        store = torch.empty((L, R, 4, W, H), dtype=torch.float32, device=dev)
+        store = torch.empty((L, R, Cm, W, H), dtype=torch.float32, device=dev)
         drop = pop._dropout()
-        masked = None if drop is None else torch.empty((R, 4, W, H), dtype=torch.float32, device=dev)
+        masked = None if drop is None else torch.empty((R, Cm, W, H), dtype=torch.float32, device=dev)
         ctx.epoch, ctx.fdt = env.epoch, _lib.DIE_F32 if env.dtype == torch.float32 else _lib.DIE_F16
         ctx.batch, ctx.pop, ctx.size = env._batch_struct(), pop, (R, W, H, L)
         ctx.drop = None if drop is None else (drop.p, drop.seed, drop.seed_stride, drop.step)
         m = _BatchedSense._medium(ctx, planes)
-        layers, nca = pop._grad_struct(parameters, ctx.epoch)
-        _lib.check(_lib.lib.die_nca_sense_batch_store(C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), store.numel() * 4,
-                                                      None if masked is None else _ptr(masked),
-                                                      None if drop is None else C.byref(drop), stream_ptr(dev)),
-                   'die_nca_sense_batch_store')
+        layers, nca = pop._nca_batch(parameters.data_ptr(), ctx.epoch)
+        name = 'die_nca_wide_sense_batch_store' if pop._wide else 'die_nca_sense_batch_store'
+        _lib.check(getattr(_lib.lib, name)(C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), store.numel() * 4,
+                                           None if masked is None else _ptr(masked), None if drop is None else C.byref(drop),
+                                           stream_ptr(dev)), name)
         # everything the backward reads goes through save_for_backward: freed with the graph after a backward without retain_graph
         ctx.save_for_backward(parameters, store, *planes)
         return (store[L - 1] if masked is None else masked)[:, :3]
@@ -1471,73 +1454,30 @@ class _BatchedSense(torch.autograd.Function):
         R, W, H, L = ctx.size
         pop, dev = ctx.pop, store.device
         g = grad.to(dtype=torch.float32).contiguous()               # (R, 3, W, H): three planes per replica
-        need = int(_lib.lib.die_nca_backward_batch_workspace_bytes(W, H, R, L))
+        m = _BatchedSense._medium(ctx, planes)
+        layers, nca = pop._nca_batch(parameters.data_ptr(), ctx.epoch)
+        if pop._wide:
+            need = int(_lib.lib.die_nca_wide_backward_batch_workspace_bytes(W, H, R, C.byref(nca)))
+            if need < 0:
+                raise ValueError('a stack or shape die_nca_wide_backward_batch does not take')
+        else:
+            need = int(_lib.lib.die_nca_backward_batch_workspace_bytes(W, H, R, L))
         ws = torch.empty((need // 4,), dtype=torch.float32, device=dev)
         out = torch.empty_like(parameters)                          # (C, P): every element is written (the layers tile a row)
         drop = None if ctx.drop is None else _lib.NcaDropout(*ctx.drop, 0)
-        m = _BatchedSense._medium(ctx, planes)
-        layers, nca = pop._grad_struct(parameters, ctx.epoch)
         args = (C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), _ptr(g), 3 * W * H, _ptr(out), pop.P,
                 None if drop is None else C.byref(drop), _ptr(ws), need)
-        if not ctx.needs_input_grad[2]:             # no chem node, or one that asks for nothing (a leaf)
-            _lib.check(_lib.lib.die_nca_backward_batch(*args, stream_ptr(dev)), 'die_nca_backward_batch')
-            return None, out, None
-        # the first layer's inputs are ([agents,] food, chem): food and the claims are constants of the parameters, chem is the node
-        cin = len(planes)
-        grad_in = torch.empty((R, cin, W, H), dtype=torch.float32, device=dev)
-        _lib.check(_lib.lib.die_nca_backward_batch_inputs(*args, _ptr(grad_in), cin * W * H, stream_ptr(dev)), 'die_nca_backward_batch_inputs')
-        return None, out, grad_in[:, cin - 1]
-
-
-class _BatchedWideSense(torch.autograd.Function):
-    """BatchedNeuralAutomataAgent.forward_device: die_nca_wide_sense_batch_store forward, die_nca_wide_backward_batch backward — with
-    the env's chem node as an input that needs a gradient, the call is given `grad_in`, whose chem channel is the node's gradient."""
-
-    @staticmethod
-    def forward(ctx, pop, parameters, chem_node=None):
-        env = pop.env
-        R, W, H, L, dev, Cm = env.R, env.W, env.H, len(pop._layers), env.device, pop._channels
-        with_agents = pop._arch['with_agent_channel']
-        # as they are now: the worlds will be stepped (the claim plane only where the first layer reads it)
-        planes = [env.food.clone(), env.chem.clone()] + ([env.owner.clone()] if with_agents else [])
-        store = torch.empty((L, R, Cm, W, H), dtype=torch.float32, device=dev)
-        drop = pop._dropout()
-        masked = None if drop is None else torch.empty((R, Cm, W, H), dtype=torch.float32, device=dev)
-        ctx.epoch, ctx.fdt = env.epoch, _lib.DIE_F32 if env.dtype == torch.float32 else _lib.DIE_F16
-        ctx.batch, ctx.pop, ctx.size = env._batch_struct(), pop, (R, W, H, L)
-        ctx.drop = None if drop is None else (drop.p, drop.seed, drop.seed_stride, drop.step)
-        m = _BatchedSense._medium(ctx, planes)
-        layers, nca = pop._grad_struct(parameters, ctx.epoch)
-        _lib.check(_lib.lib.die_nca_wide_sense_batch_store(C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), store.numel() * 4,
-                                                           None if masked is None else _ptr(masked),
-                                                           None if drop is None else C.byref(drop), stream_ptr(dev)),
-                   'die_nca_wide_sense_batch_store')
-        # everything the backward reads goes through save_for_backward: freed with the graph after a backward without retain_graph
-        ctx.save_for_backward(parameters, store, *planes)
-        return (store[L - 1] if masked is None else masked)[:, :3]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad):
-        parameters, store, *planes = ctx.saved_tensors
-        R, W, H, L = ctx.size
-        pop, dev = ctx.pop, store.device
-        g = grad.to(dtype=torch.float32).contiguous()               # (R, 3, W, H): three planes per replica
-        m = _BatchedSense._medium(ctx, planes)
-        layers, nca = pop._grad_struct(parameters, ctx.epoch)
-        need = int(_lib.lib.die_nca_wide_backward_batch_workspace_bytes(W, H, R, C.byref(nca)))
-        if need < 0:
-            raise ValueError('a stack or shape die_nca_wide_backward_batch does not take')
-        ws = torch.empty((need // 4,), dtype=torch.float32, device=dev)
-        out = torch.empty_like(parameters)                          # (C, P): every element is written (the layers tile a row)
-        drop = None if ctx.drop is None else _lib.NcaDropout(*ctx.drop, 0)
         # the first layer's inputs are ([agents,] food, chem): food and the claims are constants of the parameters, chem is the node;
-        # without a node that needs a gradient the first layer's input-gradient kernel is not launched
+        # without a node that needs a gradient (none, or a leaf that asks for nothing) no input gradient is computed
         cin = len(planes)
         grad_in = torch.empty((R, cin, W, H), dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
-        _lib.check(_lib.lib.die_nca_wide_backward_batch(C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), _ptr(g), 3 * W * H,
-                                                        _ptr(out), pop.P, None if drop is None else C.byref(drop), _ptr(ws), need,
-                                                        _ptr(grad_in), cin * W * H, stream_ptr(dev)), 'die_nca_wide_backward_batch')
+        if pop._wide:                               # one call, `grad_in` nullable
+            name, args = 'die_nca_wide_backward_batch', args + (_ptr(grad_in), cin * W * H)
+        elif grad_in is None:
+            name = 'die_nca_backward_batch'
+        else:
+            name, args = 'die_nca_backward_batch_inputs', args + (_ptr(grad_in), cin * W * H)
+        _lib.check(getattr(_lib.lib, name)(*args, stream_ptr(dev)), name)
         return None, out, None if grad_in is None else grad_in[:, cin - 1]
 
 

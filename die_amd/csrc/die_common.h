@@ -41,6 +41,15 @@ __device__ __forceinline__ void die_store_result_i64(long long* p, long long v) 
 
 static inline int die_grid_for(int64_t n, int block = DIE_BLOCK) { return (int)((n + block - 1) / block); }
 
+// ---- host functions one .hip file defines and another calls (not exported; the NeuralAutomataAgent's are in die_nca.h, the
+// tile-binned step's in die_forward.h).  Every such function is declared in exactly one header, which the defining file
+// includes too: the compiler checks the definition against it.
+// bytes of the scan scratch inside a step's workspace (die_init.hip; die_env.hip lays the workspace out)
+int64_t die_ws_scan_bytes(int32_t W, int32_t H);
+// (1 - decay) * G(src) of `replicas` fp32 planes, one (sigma, decay) or a row per replica (die_env.hip; die_env_grad.hip's adjoint)
+int die_diffuse_rows_batch(const float* src, float* dst, int32_t W, int32_t H, int32_t replicas, int64_t plane_stride, float sigma,
+                           float decay, const die_dynamics_row* rows, const die_dynamics_row* rows_host, void* stream, const char* who);
+
 // A checked die_nca_dropout as the words a kernel reads (die_nca.hip die_dropout_words; die_rng.h defines the mask)
 struct DropWords {
     uint64_t seed, seed_stride;  // replica z is masked with key seed + z · seed_stride (mod 2^64)

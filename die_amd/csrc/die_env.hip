@@ -19,6 +19,7 @@
 // (pass 1) are separated from the single write per occupied cell (pass 2) by a kernel boundary.
 // "Last writer wins" of the fancy-index assignment at :211 is an atomicMax on the slot id.
 #include "die_forward.h"
+#include "die_nca.h"
 
 #define DIE_MAX_PARTIALS 8192
 // workgroup size of the per-agent step kernels (claim pass, dead-slot pass).  Swept on MI355X at 2.5 M agents, step time in
@@ -831,8 +832,6 @@ static int step_grid(int64_t N) {
 // workspace layout: [part_gain_a | part_gain_b | part_alive | scan scratch (die_init) | stash (N floats)]
 static const int64_t WS_PARTS = (int64_t)DIE_MAX_PARTIALS * 8 * 3;
 
-int64_t die_ws_scan_bytes(int32_t W, int32_t H);   // die_init.hip
-
 extern "C" int64_t die_workspace_bytes(int32_t W, int32_t H, int64_t N) {
     if (W < 1 || H < 1 || N < 0) return -1;
     int64_t b = WS_PARTS + die_ws_scan_bytes(W, H) + N * (int64_t)sizeof(float);
@@ -1549,25 +1548,6 @@ extern "C" int die_env_step_batch_rows(const die_medium* m, const die_agents* a,
     return env_step_batch(m, a, act, d, b, results, ws, ws_bytes, true, rows, rows_host, stream, "die_env_step_batch_rows");
 }
 
-int die_nca_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool stock);       // die_nca.hip
-int die_dropout_words(const die_nca_dropout* drop, DropWords* out, const char* who);                                 // die_nca.hip
-int die_nca_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
-                        const DropWords* drop, void* stream, const unsigned long long* stock);
-int die_nca_wide_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool stock);  // die_nca_wide.hip
-int die_nca_wide_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
-                             const DropWords* drop, void* stream, const unsigned long long* stock);
-int die_stock_launch(const die_medium* m, const die_agents* a, int32_t replicas, const int64_t* n, int64_t agent_stride,
-                     int64_t plane_stride, int32_t epoch, unsigned long long* planes, void* stream, const char* who);  // die_stock.hip
-int die_nca_wide_batch_check_memory(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool stock, int memory);
-int die_nca_wide_sense_batch_memory(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
-                                    const DropWords* drop, void* stream, const unsigned long long* stock, const float* mem_planes, int memory);
-int die_memory_planes_launch(int32_t W, int32_t H, int32_t replicas, const int64_t* n, const unsigned long long* standing,
-                             int64_t standing_rep, int32_t epoch, int32_t M, const float* mem, int64_t mem_row, int64_t mem_rep,
-                             float* planes, int64_t plane_j, int64_t plane_rep, void* stream, const char* who);          // die_memory.hip
-int die_gather_memory_launch(const die_medium* m, const die_agents* a, int32_t replicas, const int64_t* n, int64_t agent_stride, int32_t M,
-                             const float* planes, int64_t plane_j, int64_t plane_rep, float* mem, int64_t mem_row, int64_t mem_rep,
-                             void* stream, const char* who);                                                             // die_memory.hip
-
 // die_nca_wide_env_step_batch_memory's own arguments (die_memory.hip: the agents' memory channels)
 struct MemoryStep {
     int M;                       // memory channels, 1..DIE_MEMORY_MAX_CHANNELS
@@ -1594,8 +1574,7 @@ static int nca_env_step_batch(const die_medium* m, const die_agents* a, const di
     int rc = batch_world_check(m, a, d, b, ws_bytes, true, who);
     if (rc != DIE_OK) return rc;
     const bool sense_stock = stock && (!ms || ms->with_stock);
-    rc = ms ? die_nca_wide_batch_check_memory(nca, m->W, m->H, b->replicas, who, sense_stock, ms->M)
-         : wide ? die_nca_wide_batch_check(nca, m->W, m->H, b->replicas, who, stock != nullptr)
+    rc = wide ? die_nca_wide_batch_check(nca, m->W, m->H, b->replicas, who, sense_stock, ms ? ms->M : 0)
               : die_nca_batch_check(nca, m->W, m->H, b->replicas, who, stock != nullptr);
     if (rc != DIE_OK) return rc;
     DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX && m->epoch == nca->sense_epoch % DIE_OWNER_EPOCH_MAX + 1,
@@ -1621,16 +1600,17 @@ static int nca_env_step_batch(const die_medium* m, const die_agents* a, const di
                                       (int64_t)ms->M * b->agent_stride, ms->planes, (int64_t)b->replicas * b->plane_stride, b->plane_stride,
                                       stream, who);
         if (rc != DIE_OK) return rc;
-        rc = die_nca_wide_sense_batch_memory(m, b, nca, &q.sense, &q.rep, drop ? &dw : nullptr, stream, sense_stock ? stock : nullptr,
-                                             ms->planes, ms->M);
-        if (rc != DIE_OK) return rc;
-        // planes 3.. at the cells the agents stand on NOW: before the claim launch moves anything
+    }
+    // reads the claim plane at sense_epoch …
+    rc = wide ? die_nca_wide_sense_batch(m, b, nca, &q.sense, &q.rep, drop ? &dw : nullptr, stream, sense_stock ? stock : nullptr,
+                                         ms ? ms->planes : nullptr, ms ? ms->M : 0)
+              : die_nca_sense_batch(m, b, nca, &q.sense, &q.rep, drop ? &dw : nullptr, stream, stock);
+    if (rc != DIE_OK) return rc;
+    if (ms) {                                                         // planes 3.. at the cells the agents stand on NOW: before the claim launch moves anything
         rc = die_gather_memory_launch(m, a, b->replicas, b->n, b->agent_stride, ms->M, q.sense + 3 * (int64_t)m->W * m->H, (int64_t)m->W * m->H,
                                       q.rep, ms->mem, b->agent_stride, (int64_t)ms->M * b->agent_stride, stream, who);
-    } else {
-        rc = (wide ? die_nca_wide_sense_batch : die_nca_sense_batch)(m, b, nca, &q.sense, &q.rep, drop ? &dw : nullptr, stream, stock);   // reads the claim plane at sense_epoch …
+        if (rc != DIE_OK) return rc;
     }
-    if (rc != DIE_OK) return rc;
     if (nca->sense_epoch == DIE_OWNER_EPOCH_MAX) {                    // … which is cleared before the tag 1 claims
         const int64_t words = (int64_t)(b->replicas - 1) * b->plane_stride + (int64_t)m->W * m->H;
         if (hipMemsetAsync(m->owner, 0, (size_t)words * sizeof(unsigned long long), L.s) != hipSuccess) {

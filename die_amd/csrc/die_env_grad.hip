@@ -256,10 +256,6 @@ extern "C" int die_deposit_cells_batch(const die_medium* m, const die_agents* ag
     return DIE_OK;
 }
 
-int die_diffuse_rows_batch(const float* src, float* dst, int32_t W, int32_t H, int32_t replicas, int64_t plane_stride, float sigma,
-                           float decay, const die_dynamics_row* rows, const die_dynamics_row* rows_host, void* stream,
-                           const char* who);                                                                     // die_env.hip
-
 extern "C" int die_env_step_backward_batch(int32_t W, int32_t H, const die_batch* b, const float* grad_chem_next, float sigma, float decay,
                                            const die_dynamics_row* rows, const die_dynamics_row* rows_host, const int32_t* cells,
                                            float* grad_chem, float* grad_deposit, void* stream) {

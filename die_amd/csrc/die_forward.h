@@ -323,3 +323,12 @@ __device__ __forceinline__ FwdOut die_forward_agent(const FwdArgs& a, const uint
 // host side: validate and fill FwdArgs (shared by die_gradient_forward and die_forward_env_step)
 int die_fill_fwd_args(FwdArgs& k, const die_medium* m, const die_agents* a, const die_gradient_agent* g,
                       const die_action* out, const char* who);
+
+// what the tile-binned step (die_pic.hip) takes from the classic one (die_env.hip)
+// the field half of the tile-binned step: the sweep reads the winners' deposits from a float plane
+int die_sweep_dep_plane(const die_medium* m, const die_dynamics* d, const float* dep_plane, const long long* part_gain, int n_part,
+                        die_step_result* result, long long alive_const, void* stream);
+// periodic planes, H % 4 == 0, radius 1..4
+bool fused_step_shape_ok(const die_medium* m, const die_dynamics* d);
+// scipy.ndimage._gaussian_kernel1d; w holds 2·8 + 1 taps
+int die_gaussian_taps(float sigma, double* w);

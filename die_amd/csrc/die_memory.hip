@@ -20,6 +20,7 @@
 // read-out a few thousand words; both are far below what the memory system notices, and the launch itself is the cost — as
 // for the stock build (LABBOOK §31: 3.6 us).
 #include "die_common.h"
+#include "die_nca.h"
 
 struct MemPlanesArgs {
     const unsigned long long* standing;      // replica r's plane standing_rep words on

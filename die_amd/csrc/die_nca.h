@@ -44,6 +44,31 @@ int die_nca_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t 
 int die_nca_batch_shape_check(const die_medium* m, const die_batch* b, const char* who);
 // the same for a wide stack (die_nca_wide.hip: 1..32 channels, k in 1, 3, 5, an activation per layer in die_nca_layer.reserved)
 int die_nca_wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who);
+// what die_nca_sense_batch_store and die_nca_wide_sense_batch_store check alike, in their order: the arguments, the die_batch, the
+// stack (`wide`: die_nca_wide_stack_check), the field's dtype and planes, sense_epoch (die_nca.hip)
+int die_nca_store_check(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store, bool wide, const char* who);
+
+// ---- what the batched step (die_env.hip: nca_env_step_batch) calls, in its order ----
+// the stack WITH the step's scratch (die_nca.hip; `stock`: layer 0 reads the stock plane as its last input) …
+int die_nca_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool stock);
+// … and a wide one (die_nca_wide.hip; `memory`: layer 0 reads that many planes more, the last layer gives 3 + memory)
+int die_nca_wide_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool stock, int memory);
+// every replica's stock plane at `epoch` (die_stock.hip)
+int die_stock_launch(const die_medium* m, const die_agents* a, int32_t replicas, const int64_t* n, int64_t agent_stride,
+                     int64_t plane_stride, int32_t epoch, unsigned long long* planes, void* stream, const char* who);
+// the memory of whoever stands on a cell as planes, and the planes read back into the memory (die_memory.hip)
+int die_memory_planes_launch(int32_t W, int32_t H, int32_t replicas, const int64_t* n, const unsigned long long* standing,
+                             int64_t standing_rep, int32_t epoch, int32_t M, const float* mem, int64_t mem_row, int64_t mem_rep,
+                             float* planes, int64_t plane_j, int64_t plane_rep, void* stream, const char* who);
+int die_gather_memory_launch(const die_medium* m, const die_agents* a, int32_t replicas, const int64_t* n, int64_t agent_stride, int32_t M,
+                             const float* planes, int64_t plane_j, int64_t plane_rep, float* mem, int64_t mem_row, int64_t mem_rep,
+                             void* stream, const char* who);
+// the stack into the step's scratch: *sense = the last layer's planes of replica 0, replica r's *rep further (die_nca.hip) …
+int die_nca_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
+                        const DropWords* drop, void* stream, const unsigned long long* stock);
+// … and a wide one (die_nca_wide.hip; `stock`, `mem_planes` with `memory`: null / 0 without them)
+int die_nca_wide_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
+                             const DropWords* drop, void* stream, const unsigned long long* stock, const float* mem_planes, int memory);
 
 // k_conv_backward_sum on `tiles` partial rows of nw weights (die_nca_grad.hip), for the wide adjoint's rows as well
 void die_conv_backward_fold(const float* part, int64_t tiles, int nw, float* out, hipStream_t s);

@@ -444,6 +444,18 @@ int die_nca_sense_batch(const die_medium* m, const die_batch* b, const die_nca_b
     return sense_batch(m, b, nca, nca->scratch, true, nullptr, sense, rep, drop, stream, stock);
 }
 
+int die_nca_store_check(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store, bool wide, const char* who) {
+    DIE_REQUIRE(m && b && nca && store, "%s: null argument", who);
+    int rc = die_nca_batch_shape_check(m, b, who);
+    if (rc != DIE_OK) return rc;
+    rc = (wide ? die_nca_wide_stack_check : die_nca_stack_check)(nca, m->W, m->H, b->replicas, who);
+    if (rc != DIE_OK) return rc;
+    DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad field dtype %d", who, m->dtype);
+    DIE_REQUIRE(m->food && m->chem && (m->owner || !nca->with_agent_channel), "%s: null plane", who);
+    DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX, "%s: sense_epoch %d", who, nca->sense_epoch);
+    return DIE_OK;
+}
+
 extern "C" int64_t die_nca_sense_batch_store_bytes(int32_t W, int32_t H, int32_t replicas, int32_t n_layers) {
     if (W < 1 || H < 1 || replicas < 1 || replicas > DIE_MAX_REPLICAS || n_layers < 1 || n_layers > DIE_NCA_MAX_LAYERS) return -1;
     return (int64_t)n_layers * replicas * NCA_MAXC * (int64_t)W * H * (int64_t)sizeof(float);
@@ -452,14 +464,8 @@ extern "C" int64_t die_nca_sense_batch_store_bytes(int32_t W, int32_t H, int32_t
 extern "C" int die_nca_sense_batch_store(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* store, int64_t store_bytes,
                                          float* masked, const die_nca_dropout* drop, void* stream) {
     const char* who = "die_nca_sense_batch_store";
-    DIE_REQUIRE(m && b && nca && store, "%s: null argument", who);
-    int rc = die_nca_batch_shape_check(m, b, who);
+    int rc = die_nca_store_check(m, b, nca, store, false, who);
     if (rc != DIE_OK) return rc;
-    rc = nca_stack_check(nca, m->W, m->H, b->replicas, who, false);
-    if (rc != DIE_OK) return rc;
-    DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad field dtype %d", who, m->dtype);
-    DIE_REQUIRE(m->food && m->chem && (m->owner || !nca->with_agent_channel), "%s: null plane", who);
-    DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX, "%s: sense_epoch %d", who, nca->sense_epoch);
     const int64_t need = die_nca_sense_batch_store_bytes(m->W, m->H, b->replicas, nca->n_layers);
     DIE_REQUIRE(store_bytes >= need, "%s: store too small (%lld < %lld)", who, (long long)store_bytes, (long long)need);
     DIE_REQUIRE((m->W + NCA_TX - 1) / NCA_TX <= 65535, "%s: field too tall", who);

@@ -311,10 +311,7 @@ static int wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int3
     return DIE_OK;
 }
 
-int die_nca_wide_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool stock) {
-    return wide_stack_check(nca, W, H, replicas, who, true, stock);
-}
-int die_nca_wide_batch_check_memory(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool stock, int memory) {
+int die_nca_wide_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool stock, int memory) {
     return wide_stack_check(nca, W, H, replicas, who, true, stock, memory);
 }
 int die_nca_wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who) {
@@ -373,12 +370,7 @@ static int wide_sense_batch(const die_medium* m, const die_batch* b, const die_n
 }
 
 int die_nca_wide_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
-                             const DropWords* drop, void* stream, const unsigned long long* stock) {
-    return wide_sense_batch(m, b, nca, nca->scratch, true, nullptr, sense, rep, drop, stream, stock);
-}
-
-int die_nca_wide_sense_batch_memory(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
-                                    const DropWords* drop, void* stream, const unsigned long long* stock, const float* mem_planes, int memory) {
+                             const DropWords* drop, void* stream, const unsigned long long* stock, const float* mem_planes, int memory) {
     return wide_sense_batch(m, b, nca, nca->scratch, true, nullptr, sense, rep, drop, stream, stock, mem_planes, memory);
 }
 
@@ -392,14 +384,8 @@ extern "C" int64_t die_nca_wide_sense_batch_store_bytes(int32_t W, int32_t H, in
 extern "C" int die_nca_wide_sense_batch_store(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* store,
                                               int64_t store_bytes, float* masked, const die_nca_dropout* drop, void* stream) {
     const char* who = "die_nca_wide_sense_batch_store";
-    DIE_REQUIRE(m && b && nca && store, "%s: null argument", who);
-    int rc = die_nca_batch_shape_check(m, b, who);
+    int rc = die_nca_store_check(m, b, nca, store, true, who);
     if (rc != DIE_OK) return rc;
-    rc = wide_stack_check(nca, m->W, m->H, b->replicas, who, false);
-    if (rc != DIE_OK) return rc;
-    DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad field dtype %d", who, m->dtype);
-    DIE_REQUIRE(m->food && m->chem && (m->owner || !nca->with_agent_channel), "%s: null plane", who);
-    DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX, "%s: sense_epoch %d", who, nca->sense_epoch);
     const int64_t need = die_nca_wide_sense_batch_store_bytes(m->W, m->H, b->replicas, nca->n_layers, wide_max_channels(nca));
     DIE_REQUIRE(store_bytes >= need, "%s: store too small (%lld < %lld)", who, (long long)store_bytes, (long long)need);
     DropWords dw;

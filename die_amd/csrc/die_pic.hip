@@ -1575,11 +1575,7 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_mark_owner(die_geo g, int64_t N, 
     }
 }
 
-// ---- host side ----------------------------------------------------------------------------------------------------
-int die_sweep_dep_plane(const die_medium* m, const die_dynamics* d, const float* dep_plane, const long long* part_gain, int n_part,
-                        die_step_result* result, long long alive_const, void* stream);   // die_env.hip
-bool fused_step_shape_ok(const die_medium* m, const die_dynamics* d);                     // die_env.hip: periodic planes, H % 4 == 0, radius 1..4
-
+// ---- host side (die_forward.h declares what die_env.hip lends it: die_sweep_dep_plane, fused_step_shape_ok, die_gaussian_taps) ----
 static bool pic_shape_ok(int xs, int ys) { return (xs == 6 && ys == 6) || (xs == 5 && ys == 7) || (xs == 5 && ys == 6) || (xs == 4 && ys == 5); }
 
 static int pic_check(const die_medium* m, const die_pic* p, const char* who) {
@@ -1774,8 +1770,6 @@ static int pic_agent_slots(PicK1Fn fn, int block, size_t lds) {
     memo.push_back({dev, fn, block, lds, slots});
     return slots;
 }
-
-int die_gaussian_taps(float sigma, double* w);             // die_env.hip (scipy.ndimage._gaussian_kernel1d); w holds 2·8 + 1 taps
 
 template <typename T, int XS, int YS, bool TILED>
 static void launch_resolve_diffuse(const PicArgs& k, const KbArgs& a, int R, hipStream_t s) {

@@ -18,6 +18,7 @@
 // Roofline: latency.  One launch of N threads, 13 bytes read and one 8-byte atomic per alive slot: at 10 x 96^2 worlds a few
 // thousand atomics, far below anything the memory system notices; the launch itself is the cost.
 #include "die_common.h"
+#include "die_nca.h"
 
 struct StockArgs {
     const uint32_t *x, *y, *slot;
