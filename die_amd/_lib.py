@@ -260,6 +260,11 @@ _SIGNATURES = {
     'die_nca_wide_env_step_batch_memory': (C.c_int, [_P(Medium), _P(Agents), _P(NcaBatch), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
                                                      C.c_void_p, C.c_int64, _P(NcaDropout), C.c_void_p, _P(DynamicsRow), C.c_void_p,
                                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    'die_memory_cells': (C.c_int, [_P(Medium), _P(Agents), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'die_memory_planes_backward': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                             C.c_int64, C.c_void_p]),
+    'die_gather_memory_backward': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                             C.c_int64, C.c_void_p]),
     'die_nca_wide_sense_batch_store_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'die_nca_wide_sense_batch_store': (C.c_int, [_P(Medium), _P(Batch), _P(NcaBatch), C.c_void_p, C.c_int64, C.c_void_p, _P(NcaDropout),
                                                  C.c_void_p]),

@@ -79,7 +79,8 @@ class ConvolutionModel(nn.Module):
 
     `memory_channels=M` > 0 (NeuralAutomataAgent(memory_channels=M), which also counts the M planes into `num_obs_channels` and
     `num_act_channels`): the stack is a wide stack whatever the two arguments above say — a single layer obs -> actions included
-    — and `forward_device` refuses it (no gradients through memory).  Kept out of `init_params` while 0."""
+    — and `forward_device` refuses it: the planes alone do not say whose memory they hold, its gradients come from
+    `NeuralAutomataAgent.recurrent_action`.  Kept out of `init_params` while 0."""
 
     def __init__(self,
                  num_obs_channels: int = 3,
@@ -156,13 +157,18 @@ class ConvolutionModel(nn.Module):
         bit for bit what `NeuralAutomataAgent.sense` returns on a medium holding those planes: the same launches.  Boundaries
         'circular' and 'zeros' where a gradient is needed.  A narrow model (neither `hidden_channels` nor `hidden_activation`)
         raises ValueError: it has `NeuralAutomataAgent.differentiable_sense`."""
-        from ..functional import conv2d_wide
         if self.memory_channels:
             raise NotImplementedError('forward_device: no gradients through memory channels (memory_channels > 0): the read-out into '
                                       'the memory and the expand onto the field have no adjoint')
         if not self.wide:
             raise ValueError('forward_device: a narrow model (hidden_channels and hidden_activation both None) is differentiated by '
                              'NeuralAutomataAgent.differentiable_sense')
+        return self._stack_device(planes, dropout)
+
+    def _stack_device(self, planes: th.Tensor, dropout=None) -> th.Tensor:
+        """`forward_device`'s layers, for the callers that have made their own refusals (`forward_device`, and
+        `NeuralAutomataAgent.recurrent_action` for a stack with memory channels)."""
+        from ..functional import conv2d_wide
         layers = self.conv_layers()
         out = planes
         for li, layer in enumerate(layers):
@@ -217,7 +223,10 @@ class NeuralAutomataAgent(TorchAgent):
         coefficient; a slot's next occupant starts blank; two agents sharing a cell get the same memory).  `sense(medium, agents)`
         needs the agents (ValueError before any launch without them) and returns all 3 + M planes; `memory_planes(medium, agents)`
         gives the M planes the coming forward would sense.
-      * Refused with NotImplementedError before any launch, and before `dropout_step` or `memory` change:
+      * Gradients: `recurrent_action(obs, memory=None) -> (action, memory_next)` is `forward` with a graph through the read-out,
+        the stack and the expand (die_memory_grad.hip); chaining `memory_next` is backpropagation through time.  Not for
+        populations, the stock channel, fp16 fields or decomposed worlds.
+      * Refused with NotImplementedError before any launch, and before `dropout_step` or `memory` change: the memoryless
         `differentiable_sense`, `differentiable_action`, `model.forward_device`, and a decomposed medium (die_amd/dist.py).
         `Dynamics(agents_born=True)` is refused together with memory too (a slot can die and be refilled within one step, so a
         newborn would inherit a dead agent's memory) — but a stand-alone agent cannot see the Dynamics, so that refusal sits
@@ -337,6 +346,7 @@ class NeuralAutomataAgent(TorchAgent):
         if not self.memory_channels:
             return
         if what is not None:
+            # (the text is pinned word for word by tests/test_gpu_nca_call_sequence.py; recurrent_action is the call that has the adjoints)
             raise NotImplementedError(f'{what}: no gradients through memory channels (memory_channels={self.memory_channels}): the '
                                       'read-out into the memory and the expand onto the field have no adjoint')
         if medium is not None and getattr(medium, 'world', None) is not None:
@@ -554,6 +564,78 @@ class NeuralAutomataAgent(TorchAgent):
         sense = self.differentiable_sense(medium)
         self._sense_output = sense.detach()
         return _DifferentiableReadOut.apply(sense, agents, medium, self.action_coefs)
+
+    def recurrent_action(self, obs, memory: Optional[th.Tensor] = None):
+        """`forward` of an agent with memory channels, with a graph: `(action, memory_next)`, (3, N) and (M, N) float32, both with a
+        `grad_fn`.  `action` holds, bit for bit, what `forward(obs)` puts in its DeviceAction's `data[:, :N]` (the agents' array
+        order), `memory_next` what `forward` leaves in `self.memory` (slot order), given the same incoming memory.
+
+        `memory`: None — `self.memory`, allocated as `forward` allocates it and a constant of the graph — or an (M, N) float32
+        tensor on the medium's device, used as given: the `memory_next` of the previous call gives backpropagation through time,
+        its `.detach()` truncates the gradient there, a leaf that requires grad receives one.
+
+        In order: the standing plane (die_stock_plane, the agent's own plane), the record of where every slot stands
+        (`functional.memory_record`: die_memory_cells), the expand (`functional.memory_planes`), the observation planes stacked in
+        `obs_channels` order, the wide stack (`functional.conv2d_wide` per layer), `functional.gather_scale` on planes 0..2 and
+        `functional.gather_memory` on planes 3.. .  The record is kept by the graph, so `backward` may run after the world has
+        been stepped, re-sorted or reset.  If the medium carries a chem node (`Env.differentiable_chem` / `differentiable_step`)
+        the node is the stack's chem plane, as in `differentiable_sense`: `env.differentiable_step(action)` followed by another
+        `recurrent_action` backpropagates through the world as well as through the memory.
+
+        The agent is left as `forward(obs)` would leave it: `self.memory` holds a copy of `memory_next`'s values, `dropout_step`
+        has advanced once if a `dropout_seed` is set, `_sense_output` is set.  An unseeded `p_agent_dropout` > 0 in training mode
+        is a torch mask multiply on all 3 + M planes, as in `differentiable_sense`.
+
+        Refused before any launch, and before `dropout_step` or `memory` change: an agent without memory channels (ValueError: it
+        has `differentiable_action`); with NotImplementedError the stock channel (the adjoint calls do not take its plane kind), a
+        decomposed medium, fp16 fields and the boundaries 'reflect' / 'replicate'; with ValueError a `memory` of the wrong shape,
+        dtype or device."""
+        from ..functional import gather_memory, gather_scale, memory_planes, memory_record
+        M = self.memory_channels
+        if not M:
+            raise ValueError('recurrent_action: an agent without memory channels (memory_channels=0) is differentiated by '
+                             'differentiable_action')
+        if self.with_stock_channel:
+            raise NotImplementedError('recurrent_action: no gradients with the stock channel (with_stock_channel=True): its plane is '
+                                      'piecewise constant in the weights and the adjoint kernels do not take its kind')
+        for k in self._model.conv_layers():
+            if k.padding_mode not in ('circular', 'zeros'):
+                raise NotImplementedError(f"recurrent_action: boundary={k.padding_mode!r} in differentiable mode: 'circular' or 'zeros' "
+                                          f"(sense() and forward() take all of {sorted(_lib.PAD_MODES)})")
+        agents, medium = obs
+        self._check_memory(medium=medium)
+        if medium.dtype != th.float32:
+            raise NotImplementedError(f'recurrent_action: fp32 fields only (this medium is {medium.dtype})')
+        if memory is None:
+            self._check_memory_slots(medium, agents)
+        elif not isinstance(memory, th.Tensor) or memory.dtype != th.float32 or tuple(memory.shape) != (M, agents.N) or \
+                memory.device != medium.device:
+            raise ValueError(f'recurrent_action: memory must be a ({M}, {agents.N}) float32 tensor on {medium.device}, got '
+                             f'{(tuple(memory.shape), memory.dtype, str(memory.device)) if isinstance(memory, th.Tensor) else type(memory).__name__}')
+        elif getattr(agents, 'global_slots', False):
+            raise NotImplementedError(f'memory_channels={M} on a decomposed world (die_amd/dist.py): its slots carry world ids')
+        medium.sensed()
+        dev, W, H = medium.device, medium.W, medium.H
+        if memory is None:
+            memory = self._memory_for(medium, agents)
+        record = memory_record(obs, self._stock_plane(medium, agents))
+        expanded = memory_planes(memory, record)
+        node = getattr(medium, 'chem_node', None)
+        src = {c: (node if c == 'chem1' and node is not None else medium.sel(c).float()) for c in self.obs_channels if not c.startswith('memory_')}
+        planes = th.stack([expanded[int(c[len('memory_'):])] if c.startswith('memory_') else src[c] for c in self.obs_channels])
+        p, training = self._model.agent_dropout.p, self._model.training
+        seeded = self._dropout_seed is not None
+        sense = self._model._stack_device(planes, (p, self._dropout_seed, self.dropout_step) if seeded and p > 0 and training else None)
+        if seeded:
+            self.dropout_step += 1
+        elif p > 0 and training:                                 # the torch-RNG mask: a torch multiply, autograd's own business
+            sense = sense * self._model.agent_dropout(th.ones((W, H), device=dev))
+        self._sense_output = sense.detach()[:3]
+        action = gather_scale(sense[:3], obs, self.action_coefs)
+        memory_next = gather_memory(sense[3:], record)
+        self.memory = memory_next.detach().clone()               # the agent's own copy, not the graph's tensor
+        self._memory_rebind = False
+        return action, memory_next
 
     def render(self) -> Sequence[np.ndarray]:
         """:176-181: the transformed medium with the channel axis last."""

@@ -1,0 +1,168 @@
+// The adjoints of a NeuralAutomataAgent's memory channels (gfx950): what backpropagation through time needs of die_memory.hip
+// (NeuralAutomataAgent.recurrent_action, die_amd.functional.memory_record / memory_planes / gather_memory).
+//
+//   k_memory_cells            the record: one thread per stored entry n < N.  With id = slot ? slot[n] : n it writes
+//                             cell[id] = the entry's cell (ix * H + iy, die_cell_u) for an alive slot, -1 for a dead one, and
+//                             win[id] = that cell where the standing word there, at `epoch`, names id + 1, else -1 — dead
+//                             slots and the losers of a shared cell.  die_deposit_cells' idea on the sense side: with the two
+//                             arrays in hand both adjoints below are index-only and never look at the world again, so a graph
+//                             survives every step, re-sort and reset.
+//   k_memory_planes_backward  the expand's adjoint, a pure gather: one thread per slot id, grad_memory[j][id] = win[id] inside
+//                             the plane ? grad_planes[j][win[id]] : +0.  Every word of the M rows is written once; the values
+//                             travel as 32-bit words; plain loads and stores, the same bits on every run.  (Only a cell's
+//                             winner was read by the expand, so only the winner gets the cell's gradient.)
+//   k_gather_memory_backward  the read-out's adjoint, a scatter: the M planes are cleared on the stream, then one thread per slot
+//                             id adds grad_memory[j][id] to grad_planes[j][cell[id]] where cell[id] is inside the plane — fp32
+//                             atomic adds, die_gather_scale_backward's method; a zero term is skipped.  Every alive slot of a
+//                             shared cell read the cell, so every one of them adds.
+//
+// Roofline: latency, as die_memory.hip's own note says of the forward pair: a few thousand words move, the launch is the cost.
+#include "die_common.h"
+
+struct MemCellsArgs {
+    const uint32_t *x, *y, *slot;
+    const uint8_t* alive;
+    const unsigned long long* standing;
+    int32_t *cell, *win;
+    int64_t N;
+    int W, H, epoch;
+};
+
+__global__ __launch_bounds__(DIE_BLOCK) void k_memory_cells(MemCellsArgs a) {
+    const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= a.N) return;
+    const int64_t id = a.slot ? (int64_t)a.slot[n] : n;
+    if (id >= a.N) return;                                   // (slot ids are 0 .. N - 1: never past the arrays)
+    const bool alive = a.alive[n] != 0;
+    const int c = die_cell_u(a.x[n], a.W) * a.H + die_cell_u(a.y[n], a.H);       // < W * H <= 2^31 - 1 (checked on the host)
+    const bool won = alive && (uint32_t)(a.standing[c] >> 32) == die_owner_word(a.epoch, id);
+    a.cell[id] = alive ? c : -1;
+    a.win[id] = won ? c : -1;
+}
+
+struct MemIndexArgs {
+    const int32_t* index;                    // win (the expand's adjoint) or cell (the read-out's), by slot id
+    const uint32_t* src;                     // what is read: row j / plane j at src + j * src_stride
+    uint32_t* dst;                           // what is written: row j / plane j at dst + j * dst_stride
+    int64_t n_slots, src_stride, dst_stride;
+    uint32_t cells;
+    int M;
+};
+
+__global__ __launch_bounds__(DIE_BLOCK) void k_memory_planes_backward(MemIndexArgs a) {
+    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= a.n_slots) return;
+    const uint32_t c = (uint32_t)a.index[id];                // (-1 is 2^32 - 1: outside, as every index from W * H on)
+    const bool in = c < a.cells;
+    for (int j = 0; j < a.M; ++j) a.dst[a.dst_stride * j + id] = in ? a.src[a.src_stride * j + c] : 0u;
+}
+
+__global__ __launch_bounds__(DIE_BLOCK) void k_gather_memory_backward(MemIndexArgs a) {
+    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= a.n_slots) return;
+    const uint32_t c = (uint32_t)a.index[id];
+    if (c >= a.cells) return;
+    for (int j = 0; j < a.M; ++j) {
+        const float v = __uint_as_float(a.src[a.src_stride * j + id]);
+        if (v != 0.f) atomicAdd((float*)a.dst + a.dst_stride * j + c, v);        // (a zero term changes no sum)
+    }
+}
+
+// ---- the entry points: every argument checked before anything is launched -------------------------------------------------
+static bool grad_overlap(const void* p, int64_t p_bytes, const void* q, int64_t q_bytes) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + (uintptr_t)q_bytes && b < a + (uintptr_t)p_bytes;
+}
+
+static int index_check(int32_t W, int32_t H, int32_t M, int64_t n_slots, int64_t row_stride, int64_t plane_stride, const char* who) {
+    DIE_REQUIRE(W >= 1 && H >= 1, "%s: bad size %dx%d", who, W, H);
+    DIE_REQUIRE(M >= 1 && M <= DIE_MEMORY_MAX_CHANNELS, "%s: %d memory channels outside 1..%d", who, M, DIE_MEMORY_MAX_CHANNELS);
+    const int64_t cells = (int64_t)W * H;
+    DIE_REQUIRE(cells <= (int64_t)INT32_MAX, "%s: %dx%d cells do not fit the int32 cell index", who, W, H);
+    DIE_REQUIRE(n_slots >= 0 && n_slots <= (int64_t)DIE_OWNER_SLOT_MASK - 1, "%s: %lld slots outside 0..%lld", who, (long long)n_slots,
+                (long long)DIE_OWNER_SLOT_MASK - 1);
+    DIE_REQUIRE(row_stride >= n_slots && row_stride >= 1, "%s: row_stride %lld smaller than a row (%lld slots)", who, (long long)row_stride,
+                (long long)n_slots);
+    DIE_REQUIRE(plane_stride >= cells, "%s: plane_stride %lld smaller than a plane (%lld cells)", who, (long long)plane_stride, (long long)cells);
+    return DIE_OK;
+}
+
+extern "C" int die_memory_cells(const die_medium* m, const die_agents* agents, const unsigned long long* standing, int32_t epoch,
+                                int32_t* cell_out, int32_t* win_out, void* stream) {
+    const char* who = "die_memory_cells";
+    DIE_REQUIRE(m && agents && standing && cell_out && win_out, "%s: null argument", who);
+    DIE_REQUIRE(m->W >= 1 && m->H >= 1, "%s: bad size %dx%d", who, m->W, m->H);
+    if (m->gW > 0) {
+        die_set_error("%s: a decomposed medium has no standing plane (periodic single-tile planes only)", who);
+        return DIE_ERR_UNSUPPORTED;
+    }
+    const int64_t cells = (int64_t)m->W * m->H, N = agents->N;
+    DIE_REQUIRE(cells <= (int64_t)INT32_MAX, "%s: %dx%d cells do not fit the int32 cell index", who, m->W, m->H);
+    DIE_REQUIRE(epoch >= 1 && epoch <= DIE_OWNER_EPOCH_MAX, "%s: epoch %d outside 1..%d", who, epoch, DIE_OWNER_EPOCH_MAX);
+    DIE_REQUIRE(N >= 0 && N <= (int64_t)DIE_OWNER_SLOT_MASK - 1, "%s: %lld slots outside 0..%lld", who, (long long)N,
+                (long long)DIE_OWNER_SLOT_MASK - 1);
+    DIE_REQUIRE(N == 0 || (agents->x && agents->y && agents->alive), "%s: null agent array", who);
+    int32_t* const outs[2] = {cell_out, win_out};
+    DIE_REQUIRE(!grad_overlap(cell_out, N * 4, win_out, N * 4), "%s: the two records overlap", who);
+    for (int q = 0; q < 2 && N > 0; ++q) {
+        DIE_REQUIRE(!grad_overlap(outs[q], N * 4, standing, cells * 8), "%s: a record overlaps the standing plane", who);
+        DIE_REQUIRE(!grad_overlap(outs[q], N * 4, agents->x, N * 4) && !grad_overlap(outs[q], N * 4, agents->y, N * 4) &&
+                    !grad_overlap(outs[q], N * 4, agents->alive, N) && !(agents->slot && grad_overlap(outs[q], N * 4, agents->slot, N * 4)),
+                    "%s: a record overlaps the agent arrays", who);
+    }
+    if (N == 0) return DIE_OK;                               // no stored entry: nothing to write
+    MemCellsArgs k;
+    k.x = agents->x; k.y = agents->y; k.slot = agents->slot; k.alive = agents->alive;
+    k.standing = standing; k.cell = cell_out; k.win = win_out; k.N = N; k.W = m->W; k.H = m->H; k.epoch = epoch;
+    k_memory_cells<<<(unsigned)((N + DIE_BLOCK - 1) / DIE_BLOCK), DIE_BLOCK, 0, (hipStream_t)stream>>>(k);
+    DIE_CHECK_LAUNCH(who);
+    return DIE_OK;
+}
+
+extern "C" int die_memory_planes_backward(int32_t W, int32_t H, int32_t memory_channels, int64_t n_slots, const int32_t* win,
+                                          const float* grad_planes, int64_t plane_stride, float* grad_memory, int64_t row_stride,
+                                          void* stream) {
+    const char* who = "die_memory_planes_backward";
+    DIE_REQUIRE(win && grad_planes && grad_memory, "%s: null argument", who);
+    const int rc = index_check(W, H, memory_channels, n_slots, row_stride, plane_stride, who);
+    if (rc != DIE_OK) return rc;
+    const int64_t cells = (int64_t)W * H, M = memory_channels;
+    const int64_t out_bytes = ((M - 1) * row_stride + n_slots) * 4;
+    DIE_REQUIRE(!grad_overlap(grad_memory, out_bytes, win, n_slots * 4), "%s: the memory gradient overlaps the record", who);
+    DIE_REQUIRE(!grad_overlap(grad_memory, out_bytes, grad_planes, ((M - 1) * plane_stride + cells) * 4),
+                "%s: the memory gradient overlaps the planes' gradient", who);
+    if (n_slots == 0) return DIE_OK;                         // no slot: nothing to write
+    MemIndexArgs k;
+    k.index = win; k.src = (const uint32_t*)grad_planes; k.dst = (uint32_t*)grad_memory;
+    k.n_slots = n_slots; k.src_stride = plane_stride; k.dst_stride = row_stride; k.cells = (uint32_t)cells; k.M = memory_channels;
+    k_memory_planes_backward<<<(unsigned)((n_slots + DIE_BLOCK - 1) / DIE_BLOCK), DIE_BLOCK, 0, (hipStream_t)stream>>>(k);
+    DIE_CHECK_LAUNCH(who);
+    return DIE_OK;
+}
+
+extern "C" int die_gather_memory_backward(int32_t W, int32_t H, int32_t memory_channels, int64_t n_slots, const int32_t* cell,
+                                          const float* grad_memory, int64_t row_stride, float* grad_planes, int64_t plane_stride,
+                                          void* stream) {
+    const char* who = "die_gather_memory_backward";
+    DIE_REQUIRE(cell && grad_memory && grad_planes, "%s: null argument", who);
+    const int rc = index_check(W, H, memory_channels, n_slots, row_stride, plane_stride, who);
+    if (rc != DIE_OK) return rc;
+    const int64_t cells = (int64_t)W * H, M = memory_channels;
+    const int64_t out_bytes = ((M - 1) * plane_stride + cells) * 4;
+    DIE_REQUIRE(!grad_overlap(grad_planes, out_bytes, cell, n_slots * 4), "%s: the planes' gradient overlaps the record", who);
+    DIE_REQUIRE(!grad_overlap(grad_planes, out_bytes, grad_memory, ((M - 1) * row_stride + n_slots) * 4),
+                "%s: the planes' gradient overlaps the memory gradient", who);
+    for (int j = 0; j < memory_channels; ++j) {              // the cells of every plane; the words between two planes are left alone
+        if (hipMemsetAsync(grad_planes + plane_stride * j, 0, (size_t)cells * sizeof(float), (hipStream_t)stream) != hipSuccess) {
+            die_set_error("%s: clearing plane %d failed", who, j);
+            return DIE_ERR_HIP;
+        }
+    }
+    if (n_slots == 0) return DIE_OK;                         // no slot: the cleared planes are the answer
+    MemIndexArgs k;
+    k.index = cell; k.src = (const uint32_t*)grad_memory; k.dst = (uint32_t*)grad_planes;
+    k.n_slots = n_slots; k.src_stride = row_stride; k.dst_stride = plane_stride; k.cells = (uint32_t)cells; k.M = memory_channels;
+    k_gather_memory_backward<<<(unsigned)((n_slots + DIE_BLOCK - 1) / DIE_BLOCK), DIE_BLOCK, 0, (hipStream_t)stream>>>(k);
+    DIE_CHECK_LAUNCH(who);
+    return DIE_OK;
+}

@@ -8,6 +8,10 @@
 
     gather_scale_batch(sense, population)
         the same read-out for every replica of a BatchedNeuralAutomataAgent's worlds: (R, 3, W, H) -> (3, R, Nmax).
+    memory_record(obs, standing=None), memory_planes(memory, record), gather_memory(sense_tail, record)
+        the memory channels of a stand-alone NeuralAutomataAgent (die_memory_grad.hip): where every slot stands (die_memory_cells),
+        the expand (M, N) -> (M, W, H) and the read-out (M, W, H) -> (M, N), each with a `grad_fn` that keeps the record
+        (die_memory_planes_backward, die_gather_memory_backward).  NeuralAutomataAgent.recurrent_action composes them.
 
 `ConvolutionModel.forward_device` evaluates a whole wide stack through `conv2d_wide`; `BatchedNeuralAutomataAgent.forward_device`
 a population of them in one launch per layer (die_nca_wide_backward_batch backward).  There is no eager fallback: a shape the
@@ -122,6 +126,120 @@ def gather_scale(sense: th.Tensor, obs, coefs: Sequence[float]) -> th.Tensor:
     from .agent.evo import _DifferentiableReadOut
     agents, medium = obs
     return _DifferentiableReadOut.apply(sense, agents, medium, tuple(float(c) for c in coefs))
+
+
+class MemoryRecord:
+    """Where every slot stood at one forward (die_memory_cells), by SLOT ID: `cell` (N,) int32, the slot's cell `ix * H + iy` or
+    -1 for a dead slot, and `win` (N,) int32, that cell where the slot is the one the standing plane names there (the highest
+    alive slot id of the cell), else -1; and the sizes `W`, `H`, `N`.  Both adjoints are driven by these two arrays alone, so a
+    graph that keeps the record survives every step, re-sort and reset of the world.  The record also remembers the standing
+    plane and epoch it was taken from, for `memory_planes`' forward only: expand before that plane is built again."""
+    __slots__ = ('cell', 'win', 'W', 'H', 'N', '_standing', '_epoch')
+
+    def __init__(self, cell, win, W, H, N, standing, epoch):
+        self.cell, self.win, self.W, self.H, self.N, self._standing, self._epoch = cell, win, int(W), int(H), int(N), standing, int(epoch)
+
+
+def memory_record(obs, standing: Optional[th.Tensor] = None) -> MemoryRecord:
+    """The record of `obs` = (agents, medium) as they stand now: one die_memory_cells launch.  `standing`: the (W, H) int64
+    standing plane built for these agents at `medium.epoch` (die_stock_plane; NeuralAutomataAgent builds one per forward), or
+    None to build one here (a plane of its own, one launch more)."""
+    agents, medium = obs
+    dev, W, H, N = medium.device, medium.W, medium.H, agents.N
+    if N < 1:
+        raise ValueError('memory_record: the agents have no slot')
+    m, a = medium.c_struct(need_owner=False), agents.c_struct()
+    sp = stream_ptr(dev)
+    if standing is None:
+        standing = th.zeros((W, H), dtype=th.int64, device=dev)
+        _lib.check(_lib.lib.die_stock_plane(C.byref(m), C.byref(a), medium.epoch, _ptr(standing), sp), 'die_stock_plane')
+    elif not isinstance(standing, th.Tensor) or standing.dtype != th.int64 or tuple(standing.shape) != (W, H) or \
+            standing.device != dev or not standing.is_contiguous():
+        raise ValueError(f'standing: a contiguous ({W}, {H}) int64 tensor on {dev}')
+    cell = th.full((N,), -1, dtype=th.int32, device=dev)
+    win = th.full((N,), -1, dtype=th.int32, device=dev)
+    _lib.check(_lib.lib.die_memory_cells(C.byref(m), C.byref(a), _ptr(standing), medium.epoch, _ptr(cell), _ptr(win), sp), 'die_memory_cells')
+    return MemoryRecord(cell, win, W, H, N, standing, medium.epoch)
+
+
+def _index_gather(W, H, index, planes, N):
+    """die_memory_planes_backward as the index-only gather it is: (M, W, H) planes -> (M, N) rows, row[j][id] = planes[j][index[id]],
+    +0 where the index is negative, the values moved as 32-bit words."""
+    M = planes.shape[0]
+    out = th.empty((M, N), dtype=th.float32, device=planes.device)
+    _lib.check(_lib.lib.die_memory_planes_backward(W, H, M, N, _ptr(index), _ptr(planes), W * H, _ptr(out), N, stream_ptr(planes.device)),
+               'die_memory_planes_backward')
+    return out
+
+
+def _check_memory_op(name, t, record, tail):
+    """`t` must be a float32 (M, *tail(record)) tensor on the record's device, 1 <= M <= 8."""
+    if not isinstance(record, MemoryRecord):
+        raise TypeError('record: a MemoryRecord (die_amd.functional.memory_record)')
+    shape = tail(record)
+    if not isinstance(t, th.Tensor) or t.dtype != th.float32 or t.dim() != 1 + len(shape) or tuple(t.shape[1:]) != shape or \
+            not 1 <= t.shape[0] <= _lib.MEMORY_MAX_CHANNELS or t.device != record.cell.device:
+        raise ValueError(f'{name}: a float32 tensor of shape (M, {", ".join(str(s) for s in shape)}) with M in 1..'
+                         f'{_lib.MEMORY_MAX_CHANNELS} on {record.cell.device}')
+
+
+class _MemoryPlanes(th.autograd.Function):
+    """memory_planes: die_memory_planes forward into storage the graph owns, die_memory_planes_backward backward."""
+
+    @staticmethod
+    def forward(ctx, memory, record):
+        W, H, N, M = record.W, record.H, record.N, memory.shape[0]
+        planes = th.empty((M, W, H), dtype=th.float32, device=memory.device)
+        m = _lib.Medium(W, H, _lib.DIE_F32, record._epoch, None, None, None, None, 0, 0, 0, 0, 0, 0, 0, 0, None)     # (W, H, gW are read)
+        _lib.check(_lib.lib.die_memory_planes(C.byref(m), _ptr(record._standing), record._epoch, M, _ptr(memory), N, N, _ptr(planes), W * H,
+                                              stream_ptr(memory.device)), 'die_memory_planes')
+        ctx.record = record
+        return planes
+
+    @staticmethod
+    @th.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        r = ctx.record
+        return _index_gather(r.W, r.H, r.win, grad.to(dtype=th.float32).contiguous(), r.N), None
+
+
+class _GatherMemory(th.autograd.Function):
+    """gather_memory: the read-out driven by the record's cells (die_gather_memory's values, bit for bit) forward,
+    die_gather_memory_backward backward."""
+
+    @staticmethod
+    def forward(ctx, sense_tail, record):
+        ctx.record, ctx.M = record, sense_tail.shape[0]
+        return _index_gather(record.W, record.H, record.cell, sense_tail, record.N)
+
+    @staticmethod
+    @th.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        r, M = ctx.record, ctx.M
+        g = grad.to(dtype=th.float32).contiguous()
+        planes = th.empty((M, r.W, r.H), dtype=th.float32, device=g.device)      # (cleared by the call)
+        _lib.check(_lib.lib.die_gather_memory_backward(r.W, r.H, M, r.N, _ptr(r.cell), _ptr(g), r.N, _ptr(planes), r.W * r.H,
+                                                       stream_ptr(g.device)), 'die_gather_memory_backward')
+        return planes, None
+
+
+def memory_planes(memory: th.Tensor, record: MemoryRecord) -> th.Tensor:
+    """The expand with a `grad_fn`: an (M, N) float32 memory by slot id -> the (M, W, H) planes a forward senses, P_j[c] =
+    memory[j][winner of c], +0 on empty cells (die_memory_planes on the record's standing plane, into storage the graph owns).
+    The backward is die_memory_planes_backward: grad_memory[j][id] = grad_planes[j][record.win[id]], +0 for dead slots and the
+    losers of a shared cell — a gather, bit-reproducible."""
+    _check_memory_op('memory', memory, record, lambda r: (r.N,))
+    return _MemoryPlanes.apply(memory.contiguous(), record)
+
+
+def gather_memory(sense_tail: th.Tensor, record: MemoryRecord) -> th.Tensor:
+    """The memory read-out with a `grad_fn`: the stack's planes 3.. as an (M, W, H) float32 tensor -> (M, N) by slot id,
+    memory[j][id] = sense_tail[j][record.cell[id]] for an alive slot, +0 for a dead one: die_gather_memory's values bit for bit,
+    read through the record (die_memory_planes_backward's gather with `cell` for an index) so that nothing looks at the world
+    again.  The backward is die_gather_memory_backward: the slots' gradients added onto their cells by fp32 atomic adds —
+    bit-reproducible run to run whenever no cell holds more than two alive slots with a non-zero gradient."""
+    _check_memory_op('sense_tail', sense_tail, record, lambda r: (r.W, r.H))
+    return _GatherMemory.apply(sense_tail.contiguous(), record)
 
 
 def gather_scale_batch(sense: th.Tensor, population) -> th.Tensor:

@@ -1,0 +1,128 @@
+"""Backpropagation through time for a NeuralAutomataAgent with memory channels: a recurrent student fitted to a teacher that a
+memoryless policy cannot express.
+
+The teacher is a `GradientAgent` with `inertia > 0` and no noise: its heading is a blend of the chem gradient it senses now and
+the heading it had a step ago, so its action is a function of the observation AND of its own past.  The teacher drives the world.
+Every optimiser step is one episode: the world is reset to its seed, a fresh teacher takes `--warm` steps alone (trails to follow),
+then comes a window of `--unroll T` env steps in which the student — `NeuralAutomataAgent(memory_channels=M)`, a wide stack, its
+memory blank at the window's start — computes `recurrent_action(obs, memory)` on each of the T observations, handing `memory_next`
+of one step to the next, so that `loss.backward()` runs through the read-out into the memory (die_gather_memory_backward), the
+stack (die_conv2d_wide_backward) and the expand onto the field (die_memory_planes_backward) of every step of the window;
+`--detach-every K` cuts the memory's gradient every K steps inside a window (K = 1: no gradient through memory at all).  The loss
+is the mean squared error of (dx, dy) against the teacher's over the alive agents and the window's steps, in units of scale².
+
+`--memory-channels 0` trains the same stack without memory through `model.forward_device` and `functional.gather_scale`: the
+baseline.  With M > 0 the baseline is trained as well, on a world seeded alike, and both final losses are printed — side by side,
+with no claim about which is smaller.  `--time` prints optimiser steps per second.
+
+    python examples/recurrent_agent.py --size 96 --memory-channels 2 --unroll 8 --steps 200
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from die_amd import Dynamics, Env, GradientAgent, NeuralAutomataAgent, functional          # noqa: E402
+
+SCALE, DEPOSIT = 0.01, 2.0
+
+
+def make_student(memory_channels, hidden_channels=8, seed=0):
+    torch.manual_seed(seed)
+    student = NeuralAutomataAgent(kernel_sizes=[3, 3], scale=SCALE, deposit=DEPOSIT, hidden_channels=hidden_channels, hidden_activation='tanh',
+                                  memory_channels=memory_channels)
+    student.model.init_weights()
+    return student
+
+
+def student_step(student, obs, memory):
+    """One step of the student on `obs`: ((3, N) action with a `grad_fn`, the memory to hand on — None without memory channels)."""
+    if student.memory_channels:
+        return student.recurrent_action(obs, memory)
+    medium = obs[1]
+    medium.sensed()
+    planes = torch.stack([medium.sel(c).float() for c in student.obs_channels])
+    return functional.gather_scale(student.model.forward_device(planes), obs, student.action_coefs), None
+
+
+def window_loss(student, teacher, env, obs, memory, unroll, detach_every):
+    """`unroll` env steps driven by the teacher, the student unrolled beside it: (loss, the observation after the window, the
+    memory after the window)."""
+    loss = 0.
+    for t in range(unroll):
+        if memory is not None and detach_every and t % detach_every == 0:
+            memory = memory.detach()
+        agents = obs[0]
+        action = teacher.forward(obs)
+        target = action.data[:2, :agents.N]
+        alive = agents.alive[:agents.N] > 0
+        got, memory = student_step(student, obs, memory)
+        loss = loss + (((got[:2] - target) / SCALE)[:, alive] ** 2).mean()
+        obs = env.step(action)[0]
+    return loss / unroll, obs, memory
+
+
+def train(size, memory_channels, unroll, detach_every, steps, lr=1e-2, seed=0, inertia=0.9, hidden_channels=8, warm=4, log=print, timed=False):
+    """`steps` Adam steps, each on one episode: the world reset to its seed, a fresh teacher, `warm` steps of the teacher alone (so that
+    there are trails to follow), then the window of `unroll` steps with the student beside it, its memory blank at the window's start.
+    Returns (the student, the list of episode losses)."""
+    env = Env((size, size), Dynamics(food_infinite=True, rate_decay_chem=0.025, diffuse_sigma=.8), seed=seed)
+    student = make_student(memory_channels, hidden_channels, seed)
+    opt = torch.optim.Adam(student.model.parameters(), lr=lr)
+    losses, t0 = [], None
+    warmup = max(1, steps // 10)
+    for it in range(steps):
+        if timed and it == warmup:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        obs = env.reset(seed=seed)[0]
+        teacher = GradientAgent(max_agents=env.agents.capacity, scale=SCALE, deposit=DEPOSIT, inertia=inertia, noise_scale=0., seed=seed)
+        teacher.lazy = False                                      # its action is the target: computed now, not inside the step
+        for _ in range(warm):
+            obs = env.step(teacher.forward(obs))[0]
+        student.reset_memory()
+        loss, obs, _ = window_loss(student, teacher, env, obs, None, unroll, detach_every)
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        losses.append(float(loss.detach()))
+        if it % 10 == 0 or it == steps - 1:
+            log(f'M={memory_channels} step {it:5d}: loss {losses[-1]:.6f}')
+    if t0 is not None and steps > warmup:
+        torch.cuda.synchronize()
+        log(f'M={memory_channels}, T={unroll}: {(steps - warmup) / (time.perf_counter() - t0):.2f} optimiser steps/s over {steps - warmup} steps')
+    return student, losses
+
+
+def main():
+    p = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
+    p.add_argument('--size', type=int, default=96)
+    p.add_argument('--memory-channels', type=int, default=2, metavar='M', help='values every agent carries between steps, 1..8; 0: the '
+                                                                                'memoryless baseline alone')
+    p.add_argument('--unroll', type=int, default=8, metavar='T', help='env steps per optimiser step')
+    p.add_argument('--detach-every', type=int, default=0, metavar='K', help="cut the memory's gradient every K steps of a window (0: never)")
+    p.add_argument('--steps', type=int, default=200, help='optimiser steps')
+    p.add_argument('--warm', type=int, default=4, help="steps the teacher takes alone before every window")
+    p.add_argument('--hidden-channels', type=int, default=8)
+    p.add_argument('--inertia', type=float, default=0.9, help="the teacher's")
+    p.add_argument('--lr', type=float, default=1e-2)
+    p.add_argument('--seed', type=int, default=0)
+    p.add_argument('--time', action='store_true', help='print optimiser steps per second')
+    args = p.parse_args()
+    if args.unroll < 1 or args.steps < 1 or args.detach_every < 0:
+        raise SystemExit('--unroll and --steps are at least 1, --detach-every at least 0')
+    final = {}
+    for M in dict.fromkeys((args.memory_channels, 0)):
+        _, losses = train(args.size, M, args.unroll, args.detach_every, args.steps, args.lr, args.seed, args.inertia, args.hidden_channels,
+                          args.warm, timed=args.time)
+        final[M] = losses[-1]
+    for M, loss in final.items():
+        print(f'final loss, {"memoryless baseline" if M == 0 else f"{M} memory channels"}: {loss:.6f}')
+
+
+if __name__ == '__main__':
+    main()

@@ -1178,6 +1178,41 @@ int die_nca_wide_env_step_batch_memory(const die_medium* m, const die_agents* a,
                                        const die_dynamics_row* rows_host, unsigned long long* standing, int32_t memory_channels,
                                        float* memory, float* memory_planes, int32_t with_stock, void* stream);
 
+/* ---- The memory channels' adjoints: backpropagation through time for a stand-alone agent (die_memory_grad.hip) -------------
+ * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
+ * All records and memories are indexed by SLOT ID (agents->slot ? slot[n] : n), as die_gather_memory indexes the memory, so
+ * what a graph keeps survives every re-sort of the storage.
+ *
+ * die_memory_cells — the record of one forward, taken after the standing plane is built (die_stock_plane at `epoch`) and before
+ * anything moves; one launch, one thread per stored entry, two int32 arrays of agents->N words:
+ *   cell_out[id] = ix * m->H + iy (die_cell_u of the entry's coordinates) for an alive slot, -1 for a dead one;
+ *   win_out[id]  = that cell where the standing word there, at `epoch`, names id + 1, else -1 (dead slots and the losers of a
+ *                  shared cell).
+ * An id >= agents->N is skipped; N == 0 launches nothing.  Checked before the launch (DIE_ERR_ARG): a null pointer (m, agents,
+ * standing, an output, or one of x, y, alive while N > 0), W or H < 1, more than 2^31 - 1 cells, epoch outside
+ * 1..DIE_OWNER_EPOCH_MAX, N outside 0..DIE_OWNER_SLOT_MASK - 1, an output that overlaps the other one, the standing plane or an
+ * agent array; a decomposed medium (m->gW > 0) is DIE_ERR_UNSUPPORTED.  Of `m` only W, H and gW are read. */
+int die_memory_cells(const die_medium* m, const die_agents* agents, const unsigned long long* standing, int32_t epoch,
+                     int32_t* cell_out, int32_t* win_out, void* stream);
+/* die_memory_planes_backward — die_memory_planes' adjoint, one launch, a pure gather in plain loads and stores:
+ *   grad_memory[j][id] = 0 <= win[id] < W * H ? grad_planes[j][win[id]] : +0.0f     for every id < n_slots and j < memory_channels
+ * (row j at grad_memory + j * row_stride, plane j at grad_planes + j * plane_stride; `win` as die_memory_cells wrote it).  Every
+ * word of the M rows is written exactly once, the values are moved as 32-bit words, no atomics: the same bits on every run.
+ * n_slots == 0 launches nothing.  Checked before the launch (DIE_ERR_ARG): a null pointer, W or H < 1, more than 2^31 - 1 cells,
+ * memory_channels outside 1..DIE_MEMORY_MAX_CHANNELS, n_slots outside 0..DIE_OWNER_SLOT_MASK - 1, row_stride < max(n_slots, 1),
+ * plane_stride < W * H, a grad_memory that overlaps `win` or grad_planes. */
+int die_memory_planes_backward(int32_t W, int32_t H, int32_t memory_channels, int64_t n_slots, const int32_t* win,
+                               const float* grad_planes, int64_t plane_stride, float* grad_memory, int64_t row_stride, void* stream);
+/* die_gather_memory_backward — die_gather_memory's adjoint: the W * H cells of each of the M planes are cleared on `stream` (the
+ * words between two planes are left alone), then one launch adds
+ *   grad_planes[j][cell[id]] += grad_memory[j][id]     for every id < n_slots with 0 <= cell[id] < W * H and j < memory_channels
+ * (`cell` as die_memory_cells wrote it; a zero term is skipped).  fp32 atomic adds, as die_gather_scale_backward: the result is
+ * bit-reproducible run to run whenever no cell holds more than two alive slots with a non-zero gradient (two addends commute,
+ * three need not).  n_slots == 0 clears the planes and launches nothing.  Checked before anything is cleared (DIE_ERR_ARG): as
+ * die_memory_planes_backward, with grad_planes the output that may overlap neither `cell` nor grad_memory. */
+int die_gather_memory_backward(int32_t W, int32_t H, int32_t memory_channels, int64_t n_slots, const int32_t* cell,
+                               const float* grad_memory, int64_t row_stride, float* grad_planes, int64_t plane_stride, void* stream);
+
 /* ---- The wide stack's adjoint for every replica of a die_batch (BatchedNeuralAutomataAgent.forward_device) -----------------
  * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
  * The wide twins of die_nca_sense_batch_store / die_nca_backward_batch_inputs: `m` describes replica 0 and `b` the strides,
