@@ -41,6 +41,15 @@ __device__ __forceinline__ void die_store_result_i64(long long* p, long long v) 
 
 static inline int die_grid_for(int64_t n, int block = DIE_BLOCK) { return (int)((n + block - 1) / block); }
 
+// scipy.ndimage._gaussian_kernel1d's radius int(4σ + .5).  Compared in double BEFORE the cast: the conversion of a value
+// beyond int's range (sigma inf, 1e30) is undefined, and a caller's `R > max` refusal must not rest on what it happens to give.
+// Saturates at INT32_MAX / INT32_MIN, NaN gives INT32_MIN (never a radius); every value in range converts as before.
+static inline int die_gaussian_radius(float sigma) {
+    const double r = 4.0 * (double)sigma + 0.5;
+    if (r >= (double)INT32_MAX) return INT32_MAX;
+    return r > (double)INT32_MIN ? (int)r : INT32_MIN;
+}
+
 // ---- host functions one .hip file defines and another calls (not exported; the NeuralAutomataAgent's are in die_nca.h, the
 // tile-binned step's in die_forward.h).  Every such function is declared in exactly one header, which the defining file
 // includes too: the compiler checks the definition against it.

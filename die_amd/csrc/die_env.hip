@@ -744,7 +744,7 @@ static bool rows_kernel_applies(int W, int H, int R) { return R <= 4 && H % 4 ==
 
 static int gaussian_taps(float sigma, double* w) {
     // scipy.ndimage._gaussian_kernel1d: radius int(4σ + .5), exp(−x²/2σ²) normalised
-    const int R = (int)(4.0 * (double)sigma + 0.5);
+    const int R = die_gaussian_radius(sigma);
     double sum = 0.0;
     for (int k = -R; k <= R && R <= DIF_MAXR; ++k) { w[k + R] = exp(-0.5 / ((double)sigma * (double)sigma) * k * k); sum += w[k + R]; }
     for (int k = 0; k <= 2 * R && R <= DIF_MAXR; ++k) w[k] /= sum;
@@ -777,7 +777,7 @@ static int diffuse_decay_mode(const void* src, void* dst, int32_t W, int32_t H, 
     DIE_REQUIRE(sigma > 0.f, "die_diffuse_decay: sigma must be positive");
     DIE_REQUIRE(dtype == DIE_F32 || dtype == DIE_F16, "die_diffuse_decay: bad dtype %d", dtype);
     // scipy.ndimage._gaussian_kernel1d: radius int(4σ + .5), exp(−x²/2σ²) normalised
-    const int R = (int)(4.0 * (double)sigma + 0.5);
+    const int R = die_gaussian_radius(sigma);
     DIE_REQUIRE(R >= 1, "die_diffuse_decay: sigma %g gives an empty kernel", (double)sigma);
     if (R > DIF_MAXR) {
         die_set_error("die_diffuse_decay: sigma %g needs radius %d > %d", (double)sigma, R, DIF_MAXR);
@@ -958,7 +958,7 @@ extern "C" int die_diffuse_decay_tile(const void* src, void* dst, int32_t W, int
     DIE_REQUIRE(src && dst && src != dst, "die_diffuse_decay_tile: src/dst must be distinct non-null planes");
     DIE_REQUIRE(dtype == DIE_F32 || dtype == DIE_F16, "die_diffuse_decay_tile: bad dtype %d", dtype);
     DIE_REQUIRE(sigma > 0.f, "die_diffuse_decay_tile: sigma must be positive");
-    const int R = (int)(4.0 * (double)sigma + 0.5);
+    const int R = die_gaussian_radius(sigma);
     if (!(R >= 1 && R <= 4 && H % 4 == 0 && H >= 8 && W >= 2 * R + 1)) {
         die_set_error("die_diffuse_decay_tile: needs H %% 4 == 0, H >= 8, radius 1..4 (W=%d H=%d sigma=%g)", W, H, (double)sigma);
         return DIE_ERR_UNSUPPORTED;
@@ -1043,7 +1043,7 @@ extern "C" int die_agent_dead_slots(const die_medium* m, const die_agents* a, co
                                     void* ws, int64_t ws_bytes, void* stream);
 
 static bool fused_step_applies(const die_medium* m, const die_dynamics* d) {
-    const int R = (int)(4.0 * (double)d->diffuse_sigma + 0.5);
+    const int R = die_gaussian_radius(d->diffuse_sigma);
     return m->gW <= 0 && d->diffuse_mode == DIE_DIFFUSE_WRAP && rows_kernel_applies(m->W, m->H, R) && R >= 1 && !d->staged;
 }
 
@@ -1317,7 +1317,7 @@ extern "C" int die_dynamics_rows(const die_dynamics* d, int32_t n, int32_t W, in
     DIE_REQUIRE(n >= 1 && n <= DIE_MAX_REPLICAS, "%s: %d rows, 1..%d expected", who, n, DIE_MAX_REPLICAS);
     DIE_REQUIRE(W >= 1 && H >= 1, "%s: bad size %dx%d", who, W, H);
     for (int r = 0; r < n; ++r) {
-        const int R = (int)(4.0 * (double)d[r].diffuse_sigma + 0.5);
+        const int R = die_gaussian_radius(d[r].diffuse_sigma);
         if (!(d[r].diffuse_sigma > 0.f) || R < 1 || !rows_kernel_applies(W, H, R)) {       // fused_step_applies, per row
             die_set_error("%s: row %d: only for periodic planes with H %% 4 == 0 and gaussian radius 1..4 (W=%d H=%d sigma=%g radius %d)", who,
                           r, W, H, (double)d[r].diffuse_sigma, R);
@@ -1362,7 +1362,7 @@ static RowsArgs rows_args_of(const die_medium* m, const die_dynamics* d, int R) 
 // (and, with dead slots, over the lifecycle pass's n_part partial gains too)
 static int batch_sweep(const die_medium* m, const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws, int n_part,
                        hipStream_t s, const char* who, const die_dynamics_row* rows = nullptr, const die_dynamics_row* rows_host = nullptr) {
-    const int R = (int)(4.0 * (double)d->diffuse_sigma + 0.5);
+    const int R = die_gaussian_radius(d->diffuse_sigma);
     RowsArgs ra = rows_args_of(m, d, R);
     ra.dep = nullptr; ra.halo = 0; ra.rep_cells = b->plane_stride;
     ra.wrapx = ra.wrapy = 1;
@@ -1704,7 +1704,7 @@ static int deposit_feed_diffuse(const die_medium* m, const die_dynamics* d, int 
     DIE_REQUIRE((m->owner || dep_plane) && m->food && m->chem && m->chem_next && m->chem_next != m->chem, "%s: null or aliased plane", who);
     DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad dtype %d", who, m->dtype);
     DIE_REQUIRE(dep_plane || (m->epoch >= 1 && m->epoch <= DIE_OWNER_EPOCH_MAX), "%s: bad epoch %d", who, m->epoch);
-    const int R = (int)(4.0 * (double)d->diffuse_sigma + 0.5);
+    const int R = die_gaussian_radius(d->diffuse_sigma);
     if (!(rows_kernel_applies(m->W, m->H, R) && R >= 1 && (!tile || (m->H >= 8 && m->W >= 2 * R + 1 && halo >= 0)))) {
         die_set_error("%s: needs H %% 4 == 0 and radius 1..4 (W=%d H=%d sigma=%g halo=%d)", who, m->W, m->H,
                       (double)d->diffuse_sigma, halo);

@@ -123,7 +123,7 @@ extern "C" int die_env_step_backward(int32_t W, int32_t H, const float* grad_che
         die_set_error("%s: %dx%d cells do not fit the int32 cell index", who, W, H);
         return DIE_ERR_UNSUPPORTED;
     }
-    const int R = (int)(4.0 * (double)sigma + 0.5);                   // gaussian_taps' radius: refused here, before any launch
+    const int R = die_gaussian_radius(sigma);                   // gaussian_taps' radius: refused here, before any launch
     DIE_REQUIRE(R >= 1, "%s: sigma %g gives an empty kernel", who, (double)sigma);
     if (R > 8) {
         die_set_error("%s: sigma %g needs radius %d > 8", who, (double)sigma, R);
@@ -289,7 +289,7 @@ extern "C" int die_env_step_backward_batch(int32_t W, int32_t H, const die_batch
     } else {
         DIE_REQUIRE(sigma > 0.f, "%s: sigma must be positive", who);      // (NaN fails too)
         DIE_REQUIRE(decay == decay, "%s: decay is not a number", who);
-        const int R = (int)(4.0 * (double)sigma + 0.5);
+        const int R = die_gaussian_radius(sigma);
         if (R < 1 || R > 4) {
             die_set_error("%s: only for periodic planes with H %% 4 == 0 and gaussian radius 1..4 (sigma %g gives radius %d)", who,
                           (double)sigma, R);
