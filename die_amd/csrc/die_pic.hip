@@ -1644,11 +1644,17 @@ static int pic_bin(const die_medium* m, const die_agents* a, const uint32_t* hea
                    const float* prev_gx, const float* prev_gy, const die_pic* p, int32_t into, void* stream) {
     int rc = pic_check(m, p, "die_pic_bin");
     if (rc != DIE_OK) return rc;
+    // (pic_check has refused W or H < 1; a decomposed medium's cells come from gW x gH)
+    DIE_REQUIRE(m->gW <= 0 || m->gH >= 1, "die_pic_bin: bad world extents %dx%d of a decomposed medium", m->gW, m->gH);
     DIE_REQUIRE(a && a->N == p->N && a->x && a->y && a->agent_food && heading_hi && heading_lo, "die_pic_bin: bad agent arrays");
     DIE_REQUIRE(into == 0 || into == 1, "die_pic_bin: layout index %d", into);
     DIE_REQUIRE(a->x != p->layout[into].x, "die_pic_bin: the agents are already held in layout %d: bin into the other one", into);
     const bool dead = p->n_alive > 0 && p->n_alive < p->N;
     DIE_REQUIRE(p->n_alive >= 0 && p->n_alive <= p->N && (!dead || a->alive), "die_pic_bin: n_alive %lld of %lld slots needs the alive flags", (long long)p->n_alive, (long long)p->N);
+    // (checked before the memset below: a refusal leaves nothing in the stream)
+    DIE_REQUIRE((prev_gx != nullptr) == (prev_gy != nullptr) &&
+                    (!prev_gx || (p->prev_grad[into][0] && p->prev_grad[into][1] && p->prev_grad[into][0] != prev_gx)),
+                "die_pic_bin: _prev_grad given without die_pic.prev_grad[%d] to carry it into", into);
     const int NT = (int)die_pic_tiles(m->W, m->H, p->tile_xs, p->tile_ys);
     hipStream_t s = (hipStream_t)stream;
     uint32_t* hist = (uint32_t*)p->part_gain;                 // 2·NT 64-bit words of scratch: histogram, cursors, the dead slots' cursor
@@ -1661,8 +1667,6 @@ static int pic_bin(const die_medium* m, const die_agents* a, const uint32_t* hea
     b.out = pic_layout(p->layout[into]); b.cursor = cursor;
     b.alive = dead ? a->alive : nullptr; b.n_alive = dead ? (uint32_t)p->n_alive : (uint32_t)p->N; b.dead_cursor = hist + 2 * NT;
     b.pgx = prev_gx; b.pgy = prev_gy; b.opgx = p->prev_grad[into][0]; b.opgy = p->prev_grad[into][1];
-    DIE_REQUIRE((prev_gx != nullptr) == (prev_gy != nullptr) && (!prev_gx || (b.opgx && b.opgy && b.opgx != prev_gx)),
-                "die_pic_bin: _prev_grad given without die_pic.prev_grad[%d] to carry it into", into);
     int64_t g = (a->N + DIE_BLOCK - 1) / DIE_BLOCK;
     const int grid = (int)(g < 4096 ? g : 4096);
     k_pic_hist<<<grid, DIE_BLOCK, 0, s>>>(b, hist);

@@ -136,6 +136,10 @@ extern "C" int die_agents_sort(const die_medium* m, const die_agents* in, const 
                                const float* const* extra_in, float* const* extra_out, void* ws, int64_t ws_bytes,
                                void* stream) {
     DIE_REQUIRE(m && in && out && ws, "die_agents_sort: null argument");
+    // (die_sort_workspace_bytes is -1 for such extents: every workspace would pass the comparison below, and sort_key would clamp
+    // to W - 1 < 0 — a negative bucket)
+    DIE_REQUIRE(m->W >= 1 && m->H >= 1, "die_agents_sort: bad extents %dx%d", m->W, m->H);
+    DIE_REQUIRE(m->gW <= 0 || m->gH >= 1, "die_agents_sort: bad world extents %dx%d of a decomposed medium", m->gW, m->gH);
     DIE_REQUIRE(in->N > 0 && in->N == out->N && in->N < ((int64_t)1 << 31), "die_agents_sort: bad slot counts");
     DIE_REQUIRE(in->x && in->y && in->alive && in->agent_food && out->x && out->y && out->alive && out->agent_food && out->slot,
                 "die_agents_sort: null device pointer (out->slot is required)");

@@ -474,7 +474,8 @@ int die_render_frames(const die_medium* medium, float* trace, float trace_decay,
 
 /* ---- spatial re-ordering of the agent arrays (no reference counterpart; see die_sort.hip) ----
  * Writes `in` permuted into `out` (different arrays, out->slot required) so that array
- * neighbours are grid neighbours: stable sort by the (ix/8, iy/64) bucket of each agent's cell.
+ * neighbours are grid neighbours: counting sort by the (ix/16, iy/32) bucket of each agent's cell
+ * (the order inside a bucket is free).  DIE_ERR_ARG for m->W or m->H < 1, like die_sort_workspace_bytes' -1.
  * Up to 4 further per-slot float arrays (agent-object state such as headings) are permuted
  * alongside.  Results of forward/step are independent of the order. */
 int64_t die_sort_workspace_bytes(int32_t W, int32_t H, int64_t N);

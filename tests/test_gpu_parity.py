@@ -1299,7 +1299,7 @@ def test_free_run_from_the_default_start_per_agent(die):
 
 def test_agent_sort_is_a_bucket_ordered_permutation(die):
     """die_agents_sort: output is a permutation (slot ids carried), non-decreasing in the
-    (ix/8, iy/64) bucket key, and invisible through the slot-order accessors."""
+    (ix/16, iy/32) bucket key, and invisible through the slot-order accessors."""
     W, H, N = 300, 520, 50000
     rs = np.random.RandomState(3)
     medium, agents = random_state(W, H, N, K=40000, rs=rs)
