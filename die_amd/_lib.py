@@ -265,6 +265,17 @@ _SIGNATURES = {
                                              C.c_int64, C.c_void_p]),
     'die_gather_memory_backward': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                              C.c_int64, C.c_void_p]),
+    'die_memory_cells_batch': (C.c_int, [_P(Medium), _P(Agents), _P(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'die_memory_planes_backward_batch': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P(Batch), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                                   C.c_void_p, C.c_int64, C.c_void_p]),
+    'die_gather_memory_backward_batch': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P(Batch), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                   C.c_int64, C.c_int64, C.c_void_p]),
+    'die_nca_wide_sense_batch_store_memory': (C.c_int, [_P(Medium), _P(Batch), _P(NcaBatch), C.c_void_p, C.c_int64, C.c_void_p,
+                                                        _P(NcaDropout), C.c_void_p, C.c_int32, C.c_void_p]),
+    'die_nca_wide_backward_batch_memory_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, _P(NcaBatch), C.c_int32]),
+    'die_nca_wide_backward_batch_memory': (C.c_int, [_P(Medium), _P(Batch), _P(NcaBatch), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                     C.c_int64, _P(NcaDropout), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                                     C.c_int32, C.c_void_p]),
     'die_nca_wide_sense_batch_store_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'die_nca_wide_sense_batch_store': (C.c_int, [_P(Medium), _P(Batch), _P(NcaBatch), C.c_void_p, C.c_int64, C.c_void_p, _P(NcaDropout),
                                                  C.c_void_p]),

@@ -1081,7 +1081,10 @@ class BatchedNeuralAutomataAgent(_Population):
     they are.  Refused with NotImplementedError: `Dynamics(agents_born=True)` together with memory, HERE in the constructor — a
     slot can die and be refilled within one step, so a newborn would inherit a dead agent's memory, and the stand-alone agent
     cannot see the Dynamics to refuse it itself —; and `differentiable_sense`, `differentiable_action` and `forward_device`,
-    before any launch and before `dropout_step` or `memory` change."""
+    before any launch and before `dropout_step` or `memory` change.  The differentiable call of a population with memory is
+    `recurrent_action(memory=None, parameters=None) -> (action, memory_next)`: the step's forward half with a graph through the
+    read-outs, the stack and the expand, a `(C, P)` gradient, and `memory_next` chained from call to call for backpropagation
+    through time (die_memory_grad.hip's batched twins, die_nca_wide_sense_batch_store_memory / _backward_batch_memory)."""
 
     def __init__(self, env: BatchedEnv, template: NeuralAutomataAgent, parameters=None, episodes: int = 1, *,
                  dropout_seed: Optional[int] = None, dropout_seed_stride: int = 1):
@@ -1365,6 +1368,69 @@ class BatchedNeuralAutomataAgent(_Population):
         'reflect' / 'replicate' boundaries (NotImplementedError)."""
         return self._differentiable(parameters, 'forward_device')
 
+    def recurrent_action(self, memory: Optional[torch.Tensor] = None, parameters: Optional[torch.Tensor] = None):
+        """`env.step`'s forward half for a population with memory channels, with a graph: `(action, memory_next)`, (3, R, Nmax)
+        and (R, M, Nmax) float32, both with a `grad_fn` — the batched twin of `NeuralAutomataAgent.recurrent_action`.
+        `action[:, r, :n[r]]` and `memory_next[r, :, :n[r]]` are bit for bit `replica_agent(r).recurrent_action(obs_r,
+        memory[r, :, :n[r]])`; `action` is also what `env.step(pop, action=buf)` records and `memory_next` what that step leaves in
+        `pop.memory`.  The padding slots from n[r] on are 0 and receive no gradient.
+
+        `memory`: None — `self.memory`, a constant of the graph — or an (R, M, Nmax) float32 tensor on the env's device, used as
+        given: the `memory_next` of the previous call gives backpropagation through time, its `.detach()` truncates the gradient
+        there, a leaf that requires grad receives one.  `parameters`: the (C, P) matrix to read and differentiate with respect
+        to (default `self.parameters`); its gradient is a (C, P) tensor, row c the float64 sum over candidate c's E worlds rounded
+        once (E = 1: replica c's stand-alone gradient, bit for bit at one step).
+
+        In order: the standing planes and the record (`functional.memory_record_batch`: a buffer this population owns, not the
+        env's stock planes), the expand (`functional.memory_planes_batch`), the wide stack (die_nca_wide_sense_batch_store_memory:
+        L launches, L + 1 with a mask), the read-out of planes 0..2 (die_gather_scale_batch) and of planes 3.. through the record:
+        L + 5 launches forward.  Backward: the two scatters into ONE (R, 3 + M, W, H) buffer, the stack's adjoint
+        (die_nca_wide_backward_batch_memory: 3 L with the first layer's input gradient, which the incoming memory's graph or a
+        chem node asks for, else 3 L - 1) and the expand's gather.  Records, planes and every layer's output are kept by the
+        graph, so `backward` may run after the worlds have been stepped or reset.  With `env.chem_node` current the node is the
+        stack's chem plane: `env.differentiable_step(action)` between two calls unrolls through the worlds too.
+
+        The population is left as a step's forward would leave it: `self.memory` holds a copy of `memory_next`'s values in its
+        own storage, `dropout_step` has advanced once if a `dropout_seed` is set.  episodes, agents_die, max_agents, per-replica
+        Dynamics, a food flow and seeded dropout are taken.  Refused before any launch, and before `dropout_step` or `memory`
+        change: a population without memory (ValueError: it has `forward_device`); with NotImplementedError the stock channel,
+        large worlds (`per_replica`), fp16 fields, 'reflect' / 'replicate' and an unseeded `p_agent_dropout` > 0 in training
+        mode; with ValueError a `memory` of the wrong shape, dtype or device."""
+        from .functional import memory_planes_batch, memory_record_batch
+        M, env = self._memory_channels, self.env
+        if not M:
+            raise ValueError('recurrent_action: a population without memory channels (memory_channels=0) is differentiated by '
+                             'forward_device / differentiable_action')
+        if self._stock_channel:
+            raise NotImplementedError('recurrent_action: no gradients with the stock channel (with_stock_channel=True): its plane is '
+                                      'piecewise constant in the weights and the adjoint kernels do not take its kind')
+        if env.per_replica:
+            raise NotImplementedError('recurrent_action: large worlds (per_replica) are not batched — a large world fills the GPU '
+                                      'through the stand-alone NeuralAutomataAgent.recurrent_action (replica_agent(r))')
+        if env.dtype != torch.float32:
+            raise NotImplementedError(f'recurrent_action: fp32 fields only (this batch holds {env.dtype})')
+        if self._arch['boundary'][0] not in ('circular', 'zeros'):
+            raise NotImplementedError(f"recurrent_action: boundary={self._arch['boundary'][0]!r} in differentiable mode: 'circular' or "
+                                      f"'zeros' (step() takes all of {sorted(_lib.PAD_MODES)})")
+        self._check_step(env)
+        p = self.parameters if parameters is None else parameters
+        self._check_parameters(p)
+        want = (self.R, M, env.Nmax)
+        if memory is None:
+            memory = self.memory
+        elif not isinstance(memory, torch.Tensor) or memory.dtype != torch.float32 or tuple(memory.shape) != want or memory.device != env.device:
+            got = (tuple(memory.shape), memory.dtype, str(memory.device)) if isinstance(memory, torch.Tensor) else type(memory).__name__
+            raise ValueError(f'recurrent_action: memory must be a {want} float32 tensor on {env.device}, got {got}')
+        record = memory_record_batch(self)
+        expanded = memory_planes_batch(memory, record)
+        sense = _BatchedMemorySense.apply(self, p, env.chem_node, expanded)
+        if self.dropout_seed is not None:
+            self.dropout_step += 1
+        action, memory_next = _BatchedRecurrentReadOut.apply(sense, self, record)
+        with torch.no_grad():
+            self.memory.copy_(memory_next)          # the population's own copy, not the graph's tensor
+        return action, memory_next
+
     def render(self, r: int) -> np.ndarray:
         """Replica r's last sense planes with the channel axis last: the stand-alone agent's `render()[0]`."""
         if self.env.per_replica:
@@ -1513,3 +1579,109 @@ class _BatchedReadOut(torch.autograd.Function):
                                                             (C.c_float * 3)(*ctx.coefs), _ptr(planes), 3 * W * H, stream_ptr(x.device)),
                    'die_gather_scale_backward_batch')
         return planes, None
+
+
+class _BatchedMemorySense(torch.autograd.Function):
+    """BatchedNeuralAutomataAgent.recurrent_action's stack: `_BatchedSense` for a wide stack whose first layer also reads the M
+    expanded memory planes of every replica and whose last layer gives 3 + M planes — die_nca_wide_sense_batch_store_memory
+    forward, die_nca_wide_backward_batch_memory backward.  Returns (R, 3 + M, W, H); the backward hands the (C, P) gradient to
+    `parameters`, the chem channel of the first layer's input gradient to the env's chem node and its M memory channels — a
+    view, in the expand's (M, R, W, H) shape — to the expand."""
+
+    @staticmethod
+    def forward(ctx, pop, parameters, chem_node, mem_planes):
+        env = pop.env
+        R, W, H, L, dev, Cm, M = env.R, env.W, env.H, len(pop._layers), env.device, pop._channels, pop._memory_channels
+        with_agents = pop._arch['with_agent_channel']
+        # as they are now: the worlds will be stepped (the claim plane only where the first layer reads it)
+        planes = [env.food.clone(), env.chem.clone()] + ([env.owner.clone()] if with_agents else [])
+        mem_planes = mem_planes.contiguous()                         # (M, R, W, H): the expand's own storage, as the launch reads it
+        store = torch.empty((L, R, Cm, W, H), dtype=torch.float32, device=dev)
+        drop = pop._dropout()
+        masked = None if drop is None else torch.empty((R, Cm, W, H), dtype=torch.float32, device=dev)
+        ctx.epoch, ctx.fdt = env.epoch, _lib.DIE_F32
+        ctx.batch, ctx.pop, ctx.size = env._batch_struct(), pop, (R, W, H, L)
+        ctx.drop = None if drop is None else (drop.p, drop.seed, drop.seed_stride, drop.step)
+        m = _BatchedSense._medium(ctx, planes)
+        layers, nca = pop._nca_batch(parameters.data_ptr(), ctx.epoch)
+        _lib.check(_lib.lib.die_nca_wide_sense_batch_store_memory(C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), store.numel() * 4,
+                                                                  None if masked is None else _ptr(masked),
+                                                                  None if drop is None else C.byref(drop), _ptr(mem_planes), M,
+                                                                  stream_ptr(dev)), 'die_nca_wide_sense_batch_store_memory')
+        ctx.save_for_backward(parameters, store, mem_planes, *planes)
+        return (store[L - 1] if masked is None else masked)[:, :3 + M]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        parameters, store, mem_planes, *planes = ctx.saved_tensors
+        R, W, H, L = ctx.size
+        pop, dev, M = ctx.pop, store.device, mem_planes.shape[0]
+        g = grad.to(dtype=torch.float32).contiguous()               # (R, 3 + M, W, H)
+        m = _BatchedSense._medium(ctx, planes)
+        layers, nca = pop._nca_batch(parameters.data_ptr(), ctx.epoch)
+        need = int(_lib.lib.die_nca_wide_backward_batch_memory_workspace_bytes(W, H, R, C.byref(nca), M))
+        if need < 0:
+            raise ValueError('a stack or shape die_nca_wide_backward_batch_memory does not take')
+        ws = torch.empty((need // 4,), dtype=torch.float32, device=dev)
+        out = torch.empty_like(parameters)                          # (C, P): every element is written (the layers tile a row)
+        drop = None if ctx.drop is None else _lib.NcaDropout(*ctx.drop, 0)
+        # the first layer's inputs are ([agents,] food, chem, memory_0 ..): chem is the env's node, the memory planes the expand's
+        # output; with neither asking for a gradient no input gradient is computed
+        to_node, to_memory = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        first = len(planes)                                         # the memory planes' first channel
+        cin = first + M
+        grad_in = torch.empty((R, cin, W, H), dtype=torch.float32, device=dev) if to_node or to_memory else None
+        _lib.check(_lib.lib.die_nca_wide_backward_batch_memory(C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), _ptr(g),
+                                                               (3 + M) * W * H, _ptr(out), pop.P, None if drop is None else C.byref(drop),
+                                                               _ptr(ws), need, _ptr(grad_in), cin * W * H, _ptr(mem_planes), M,
+                                                               stream_ptr(dev)), 'die_nca_wide_backward_batch_memory')
+        return (None, out, grad_in[:, first - 1] if to_node else None, grad_in[:, first:].permute(1, 0, 2, 3) if to_memory else None)
+
+
+class _BatchedRecurrentReadOut(torch.autograd.Function):
+    """BatchedNeuralAutomataAgent.recurrent_action's last step, ONE node for both read-outs of the (R, 3 + M, W, H) sense planes:
+    die_gather_scale_batch on planes 0..2 and the record's gather on planes 3.. forward; backward one (R, 3 + M, W, H) buffer that
+    the two scatters clear and fill between them (die_gather_scale_backward_batch, then die_gather_memory_backward_batch) — the
+    gradient at the sense planes is assembled where the stack's adjoint reads it, no slicing or padding in between."""
+
+    @staticmethod
+    def forward(ctx, sense, pop, record):
+        from .functional import _index_gather_batch
+        env = pop.env
+        R, W, H, dev, M = env.R, env.W, env.H, env.device, pop._memory_channels
+        if sense.stride()[1:] != (W * H, H, 1) or sense.stride(0) < (3 + M) * W * H:
+            sense = sense.contiguous()
+        action = torch.empty((3, R, env.Nmax), dtype=torch.float32, device=dev)
+        x, y = env.x.clone(), env.y.clone()                          # where the slots stand now: the worlds will be stepped
+        ctx.m, ctx.batch, ctx.coefs = _geometry(env), env._batch_struct(), tuple(pop.template.action_coefs)
+        ctx.size, ctx.record = (R, W, H, env.Nmax, M), record
+        a = _lib.Agents(env.Nmax, _ptr(x), _ptr(y), None, None, None)
+        u = _lib.Action(env.Nmax, action[0].data_ptr(), action[1].data_ptr(), action[2].data_ptr())
+        _lib.check(_lib.lib.die_gather_scale_batch(C.byref(ctx.m), C.byref(a), C.byref(ctx.batch), sense.data_ptr(), sense.stride(0),
+                                                   (C.c_float * 3)(*ctx.coefs), C.byref(u), stream_ptr(dev)), 'die_gather_scale_batch')
+        memory_next = _index_gather_batch(record, record.cell, sense[:, 3:], W * H, sense.stride(0), M)
+        ctx.save_for_backward(x, y)
+        return action, memory_next
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_action, grad_memory):
+        x, y = ctx.saved_tensors
+        R, W, H, Nmax, M = ctx.size
+        r, dev = ctx.record, x.device
+        ga = grad_action.to(dtype=torch.float32).contiguous()
+        gm = grad_memory.to(dtype=torch.float32).contiguous()
+        planes = torch.empty((R, 3 + M, W, H), dtype=torch.float32, device=dev)      # (cleared by the two calls between them)
+        stride = (3 + M) * W * H
+        a = _lib.Agents(Nmax, _ptr(x), _ptr(y), None, None, None)
+        u = _lib.Action(Nmax, ga[0].data_ptr(), ga[1].data_ptr(), ga[2].data_ptr())
+        sp = stream_ptr(dev)
+        # (the first call clears from its first plane to its last, the memory planes of all replicas but the last among them; the
+        # second clears its own M planes of every replica: in this order nothing either adds is wiped)
+        _lib.check(_lib.lib.die_gather_scale_backward_batch(C.byref(ctx.m), C.byref(a), C.byref(ctx.batch), C.byref(u),
+                                                            (C.c_float * 3)(*ctx.coefs), _ptr(planes), stride, sp),
+                   'die_gather_scale_backward_batch')
+        _lib.check(_lib.lib.die_gather_memory_backward_batch(W, H, M, C.byref(r._batch), _ptr(r.cell), _ptr(gm), Nmax,
+                                                             planes[:, 3:].data_ptr(), W * H, stride, sp), 'die_gather_memory_backward_batch')
+        return planes, None, None

@@ -44,6 +44,8 @@ int die_nca_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t 
 int die_nca_batch_shape_check(const die_medium* m, const die_batch* b, const char* who);
 // the same for a wide stack (die_nca_wide.hip: 1..32 channels, k in 1, 3, 5, an activation per layer in die_nca_layer.reserved)
 int die_nca_wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who);
+// … whose layer 0 reads `memory` fp32 planes more and whose last layer gives 3 + memory (the *_memory store / backward pair)
+int die_nca_wide_stack_check_memory(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, int memory);
 // what die_nca_sense_batch_store and die_nca_wide_sense_batch_store check alike, in their order: the arguments, the die_batch, the
 // stack (`wide`: die_nca_wide_stack_check), the field's dtype and planes, sense_epoch (die_nca.hip)
 int die_nca_store_check(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store, bool wide, const char* who);

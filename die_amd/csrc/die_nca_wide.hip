@@ -398,3 +398,47 @@ extern "C" int die_nca_wide_sense_batch_store(const die_medium* m, const die_bat
     int64_t rep;
     return wide_sense_batch(m, b, nca, store, false, drop ? masked : nullptr, &sense, &rep, drop ? &dw : nullptr, stream);
 }
+
+// ---- the same for a population whose agents carry memory (the forward of die_nca_wide_backward_batch_memory) --------------
+int die_nca_wide_stack_check_memory(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, int memory) {
+    return wide_stack_check(nca, W, H, replicas, who, false, false, memory);
+}
+
+// Layer 0 reads ([agents,] food, chem, memory_0 .. memory_{M-1}), the last layer gives 3 + M planes; the tanh and the mask fall
+// on all of them (k_conv_wide's epilogue knows no plane from another).  The launches are die_nca_wide_sense_batch_store's.
+// Roofline: k_conv_wide's, above — the M planes are M more fp32 planes in and out of the first and the last layer (HBM-bound
+// both, 4 bytes a cell and plane): the last layer's 3 + M outputs stay inside one 16-channel block up to M = 8, layer 0 stages
+// ceil((3 + M) / 4) chunks of 4 input channels where it staged one.
+extern "C" int die_nca_wide_sense_batch_store_memory(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* store,
+                                                     int64_t store_bytes, float* masked, const die_nca_dropout* drop, const float* mem_planes,
+                                                     int32_t memory_channels, void* stream) {
+    const char* who = "die_nca_wide_sense_batch_store_memory";
+    DIE_REQUIRE(m && b && nca && store && mem_planes, "%s: null argument", who);
+    DIE_REQUIRE(memory_channels >= 1 && memory_channels <= DIE_MEMORY_MAX_CHANNELS, "%s: %d memory channels outside 1..%d", who,
+                memory_channels, DIE_MEMORY_MAX_CHANNELS);
+    int rc = die_nca_batch_shape_check(m, b, who);
+    if (rc != DIE_OK) return rc;
+    rc = wide_stack_check(nca, m->W, m->H, b->replicas, who, false, false, memory_channels);
+    if (rc != DIE_OK) return rc;
+    DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad field dtype %d", who, m->dtype);
+    DIE_REQUIRE(m->food && m->chem && (m->owner || !nca->with_agent_channel), "%s: null plane", who);
+    DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX, "%s: sense_epoch %d", who, nca->sense_epoch);
+    const int64_t need = die_nca_wide_sense_batch_store_bytes(m->W, m->H, b->replicas, nca->n_layers, wide_max_channels(nca));
+    DIE_REQUIRE(store_bytes >= need, "%s: store too small (%lld < %lld)", who, (long long)store_bytes, (long long)need);
+    DropWords dw;
+    if (drop) {
+        DIE_REQUIRE(masked && masked != store, "%s: a dropout mask needs planes of its own for the masked values", who);
+        rc = die_dropout_words(drop, &dw, who);
+        if (rc != DIE_OK) return rc;
+    }
+    // the memory planes are read by layer 0 while the store (and the masked planes) are written
+    const int64_t cells = (int64_t)m->W * m->H;
+    const char *p0 = (const char*)mem_planes, *p1 = p0 + (((int64_t)memory_channels * b->replicas - 1) * b->plane_stride + cells) * 4;
+    auto overlaps = [&](const void* q, int64_t bytes) { return q && (const char*)q < p1 && (const char*)q + bytes > p0; };
+    DIE_REQUIRE(!overlaps(store, need) && !(drop && overlaps(masked, (int64_t)b->replicas * wide_max_channels(nca) * cells * 4)),
+                "%s: the memory planes overlap the store or the masked planes", who);
+    const float* sense;
+    int64_t rep;
+    return wide_sense_batch(m, b, nca, store, false, drop ? masked : nullptr, &sense, &rep, drop ? &dw : nullptr, stream, nullptr,
+                            mem_planes, memory_channels);
+}

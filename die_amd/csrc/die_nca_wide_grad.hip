@@ -35,6 +35,14 @@
 //                       order.  One arithmetic body: for E = 1 replica r is die_conv2d_wide_backward on its world, bit for bit.
 //                       The stand-alone instantiations (BATCH off) keep WideBwdArgs as their whole argument and the registers,
 //                       LDS and occupancy they had.
+//   die_nca_wide_backward_batch_memory   that call for a population whose agents carry memory (BatchedNeuralAutomataAgent.
+//                       recurrent_action): the same host body and the same launches with 3 + M planes at the top of the stack and
+//                       the R * M expanded memory planes (die_memory_planes_batch's layout) among layer 0's inputs; grad_in then
+//                       holds replica r's 2 + with_agent_channel + M planes, the chem plane for the env's chem node, the last M for
+//                       die_memory_planes_backward_batch.  Roofline: the parent's — the M planes widen layer 0's weight gradient
+//                       and the last layer's two GEMMs by M of their C channels (5 -> 8 -> 5 instead of 3 -> 8 -> 3 at M = 2),
+//                       inside the same 16-channel MFMA blocks up to M = 8; at 16 x 96^2 the weight-gradient kernel is the
+//                       largest launch of a training step (LABBOOK §38).
 //
 // Roofline.  Both GEMMs are 2 C^2 k^2 flop per cell, the forward's count, against 12 C bytes (g, t and the inputs in; the input
 // gradient out): a C -> C layer with C >= 16 at k >= 3 is compute-bound on the fp32 matrix rate (157 TFLOP/s, 64 flop per clock
@@ -492,13 +500,14 @@ static int64_t wide_bwd_max_weights(const die_nca_batch* nca) {
 static int wide_bwd_gin_sets(int32_t n_layers) { return n_layers - 1 < 2 ? n_layers - 1 : 2; }
 
 // the shapes the byte query answers for (the call itself checks everything again, with messages)
-static bool wide_bwd_stack_ok(int32_t W, int32_t H, int32_t replicas, const die_nca_batch* nca) {
+// (memory: layer 0 reads that many planes more, the last layer gives 3 + memory)
+static bool wide_bwd_stack_ok(int32_t W, int32_t H, int32_t replicas, const die_nca_batch* nca, int memory = 0) {
     if (W < 1 || H < 1 || replicas < 1 || replicas > DIE_MAX_REPLICAS || (W + NCA_TX - 1) / NCA_TX > 65535) return false;
     if (!nca || !nca->layers || nca->n_layers < 1 || nca->n_layers > DIE_NCA_MAX_LAYERS) return false;
     if (nca->with_agent_channel != 0 && nca->with_agent_channel != 1) return false;
     if (nca->padding_mode != DIE_PAD_CIRCULAR && nca->padding_mode != DIE_PAD_ZEROS) return false;
     if (nca->episodes < 0 || replicas % (nca->episodes > 1 ? nca->episodes : 1) != 0) return false;
-    int cin = 2 + nca->with_agent_channel;
+    int cin = 2 + nca->with_agent_channel + memory;
     for (int l = 0; l < nca->n_layers; ++l) {
         const die_nca_layer& L = nca->layers[l];
         if (!wide_shape_ok(W, H, L.cin, L.cout, L.k) || L.cin != cin) return false;
@@ -506,24 +515,34 @@ static bool wide_bwd_stack_ok(int32_t W, int32_t H, int32_t replicas, const die_
         if (l == nca->n_layers - 1 && L.reserved != DIE_NCA_ACT_TANH) return false;
         cin = L.cout;
     }
-    return cin == 3;
+    return cin == 3 + memory;
 }
 
-extern "C" int64_t die_nca_wide_backward_batch_workspace_bytes(int32_t W, int32_t H, int32_t replicas, const die_nca_batch* nca) {
-    if (!wide_bwd_stack_ok(W, H, replicas, nca)) return -1;
+static int64_t wide_bwd_workspace_bytes(int32_t W, int32_t H, int32_t replicas, const die_nca_batch* nca, int memory) {
+    if (!wide_bwd_stack_ok(W, H, replicas, nca, memory)) return -1;
     return ((int64_t)replicas * wide_tiles(W, H) * wide_bwd_max_weights(nca) +
             (int64_t)wide_bwd_gin_sets(nca->n_layers) * replicas * wide_bwd_max_channels(nca) * (int64_t)W * H) * (int64_t)sizeof(float);
 }
 
-extern "C" int die_nca_wide_backward_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store,
-                                           const float* grad_sense, int64_t sense_stride, float* grad, int64_t grad_stride,
-                                           const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, float* grad_in,
-                                           int64_t grad_in_stride, void* stream) {
-    const char* who = "die_nca_wide_backward_batch";
-    DIE_REQUIRE(m && b && nca && store && grad_sense && grad && workspace, "%s: null argument", who);
+extern "C" int64_t die_nca_wide_backward_batch_workspace_bytes(int32_t W, int32_t H, int32_t replicas, const die_nca_batch* nca) {
+    return wide_bwd_workspace_bytes(W, H, replicas, nca, 0);
+}
+
+extern "C" int64_t die_nca_wide_backward_batch_memory_workspace_bytes(int32_t W, int32_t H, int32_t replicas, const die_nca_batch* nca,
+                                                                      int32_t memory_channels) {
+    if (memory_channels < 1 || memory_channels > DIE_MEMORY_MAX_CHANNELS) return -1;
+    return wide_bwd_workspace_bytes(W, H, replicas, nca, memory_channels);
+}
+
+// die_nca_wide_backward_batch (memory = 0, mem_planes null) and die_nca_wide_backward_batch_memory: one body, the same launches
+static int wide_backward_batch(const char* who, const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store,
+                               const float* grad_sense, int64_t sense_stride, float* grad, int64_t grad_stride,
+                               const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, float* grad_in,
+                               int64_t grad_in_stride, const float* mem_planes, int memory, void* stream) {
     int rc = die_nca_batch_shape_check(m, b, who);
     if (rc != DIE_OK) return rc;
-    rc = die_nca_wide_stack_check(nca, m->W, m->H, b->replicas, who);
+    rc = memory ? die_nca_wide_stack_check_memory(nca, m->W, m->H, b->replicas, who, memory)
+                : die_nca_wide_stack_check(nca, m->W, m->H, b->replicas, who);
     if (rc != DIE_OK) return rc;
     if (nca->padding_mode == DIE_PAD_REFLECT || nca->padding_mode == DIE_PAD_REPLICATE) {
         die_set_error("%s: the adjoint of 'reflect' / 'replicate' padding is not implemented ('circular' and 'zeros' are)", who);
@@ -534,7 +553,9 @@ extern "C" int die_nca_wide_backward_batch(const die_medium* m, const die_batch*
     DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX, "%s: sense_epoch %d", who, nca->sense_epoch);
     const int Cmax = wide_bwd_max_channels(nca);
     const int64_t cells = (int64_t)m->W * m->H, rep_planes = Cmax * cells;
-    DIE_REQUIRE(sense_stride >= 3 * cells, "%s: sense_stride %lld below three planes", who, (long long)sense_stride);
+    const int n_sense = 3 + memory;                          // planes per replica at the top of the stack
+    if (memory) DIE_REQUIRE(sense_stride >= n_sense * cells, "%s: sense_stride %lld below %d planes", who, (long long)sense_stride, n_sense);
+    else DIE_REQUIRE(sense_stride >= 3 * cells, "%s: sense_stride %lld below three planes", who, (long long)sense_stride);
     int64_t P = 0;
     for (int l = 0; l < nca->n_layers; ++l) {
         const die_nca_layer& L = nca->layers[l];
@@ -542,7 +563,7 @@ extern "C" int die_nca_wide_backward_batch(const die_medium* m, const die_batch*
         DIE_REQUIRE(grad != L.weights, "%s: grad is layer %d's weights", who, l);
     }
     DIE_REQUIRE(grad_stride >= P, "%s: grad_stride %lld below a row of %lld weights", who, (long long)grad_stride, (long long)P);
-    const int64_t need = die_nca_wide_backward_batch_workspace_bytes(m->W, m->H, b->replicas, nca);
+    const int64_t need = wide_bwd_workspace_bytes(m->W, m->H, b->replicas, nca, memory);
     DIE_REQUIRE(need > 0, "%s: a shape the call does not take", who);
     DIE_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%lld < %lld)", who, (long long)workspace_bytes, (long long)need);
     // the input-gradient kernel stores four cells of a row at once where H % 4 == 0, into the workspace's planes too
@@ -559,10 +580,11 @@ extern "C" int die_nca_wide_backward_batch(const die_medium* m, const die_batch*
         const char* hi = lo + ((int64_t)(R - 1) * grad_in_stride + in_planes) * (int64_t)sizeof(float);
         auto overlaps = [&](const void* p, int64_t bytes) { return p && (const char*)p < hi && (const char*)p + bytes > lo; };
         const int64_t fbytes = ((int64_t)(R - 1) * b->plane_stride + cells) * (m->dtype == DIE_F32 ? 4 : 2);
-        DIE_REQUIRE(!overlaps(store, (int64_t)L * R * rep_planes * 4) && !overlaps(grad_sense, ((int64_t)(R - 1) * sense_stride + 3 * cells) * 4) &&
+        DIE_REQUIRE(!overlaps(store, (int64_t)L * R * rep_planes * 4) && !overlaps(grad_sense, ((int64_t)(R - 1) * sense_stride + n_sense * cells) * 4) &&
                         !overlaps(grad, ((int64_t)(R / E - 1) * grad_stride + P) * 4) && !overlaps(workspace, need) &&
                         !overlaps(m->owner, ((int64_t)(R - 1) * b->plane_stride + cells) * 8) && !overlaps(m->food, fbytes) &&
-                        !overlaps(m->chem, fbytes),
+                        !overlaps(m->chem, fbytes) &&
+                        !overlaps(mem_planes, (((int64_t)memory * R - 1) * b->plane_stride + cells) * 4),
                     "%s: grad_in aliases another buffer of the call", who);
         for (int l = 0; l < L; ++l) {
             const die_nca_layer& Ly = nca->layers[l];
@@ -593,6 +615,8 @@ extern "C" int die_nca_wide_backward_batch(const die_medium* m, const die_batch*
             if (nca->with_agent_channel) { a.in[c] = m->owner; a.kind[c++] = DIE_PLANE_AGENTS; }
             a.in[c] = m->food; a.kind[c++] = fkind;
             a.in[c] = m->chem; a.kind[c++] = fkind;
+            // plane j of replica r at (j * R + r) * plane_stride, as die_memory_planes_batch writes them: one plane_stride a replica
+            for (int j = 0; j < memory; ++j) { a.in[c] = mem_planes + (int64_t)j * R * b->plane_stride; a.kind[c++] = DIE_PLANE_F32; }
             a.rep_in = b->plane_stride;
         } else {
             for (int c = 0; c < Ly.cin; ++c) { a.in[c] = store + (int64_t)(l - 1) * R * rep_planes + c * cells; a.kind[c] = DIE_PLANE_F32; }
@@ -619,4 +643,26 @@ extern "C" int die_nca_wide_backward_batch(const die_medium* m, const die_batch*
         g = gin; rep_g = rep_planes;
     }
     return DIE_OK;
+}
+
+extern "C" int die_nca_wide_backward_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store,
+                                           const float* grad_sense, int64_t sense_stride, float* grad, int64_t grad_stride,
+                                           const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, float* grad_in,
+                                           int64_t grad_in_stride, void* stream) {
+    const char* who = "die_nca_wide_backward_batch";
+    DIE_REQUIRE(m && b && nca && store && grad_sense && grad && workspace, "%s: null argument", who);
+    return wide_backward_batch(who, m, b, nca, store, grad_sense, sense_stride, grad, grad_stride, drop, workspace, workspace_bytes, grad_in,
+                               grad_in_stride, nullptr, 0, stream);
+}
+
+extern "C" int die_nca_wide_backward_batch_memory(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store,
+                                                  const float* grad_sense, int64_t sense_stride, float* grad, int64_t grad_stride,
+                                                  const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, float* grad_in,
+                                                  int64_t grad_in_stride, const float* mem_planes, int32_t memory_channels, void* stream) {
+    const char* who = "die_nca_wide_backward_batch_memory";
+    DIE_REQUIRE(m && b && nca && store && grad_sense && grad && workspace && mem_planes, "%s: null argument", who);
+    DIE_REQUIRE(memory_channels >= 1 && memory_channels <= DIE_MEMORY_MAX_CHANNELS, "%s: %d memory channels outside 1..%d", who,
+                memory_channels, DIE_MEMORY_MAX_CHANNELS);
+    return wide_backward_batch(who, m, b, nca, store, grad_sense, sense_stride, grad, grad_stride, drop, workspace, workspace_bytes, grad_in,
+                               grad_in_stride, mem_planes, memory_channels, stream);
 }

@@ -12,6 +12,10 @@
         the memory channels of a stand-alone NeuralAutomataAgent (die_memory_grad.hip): where every slot stands (die_memory_cells),
         the expand (M, N) -> (M, W, H) and the read-out (M, W, H) -> (M, N), each with a `grad_fn` that keeps the record
         (die_memory_planes_backward, die_gather_memory_backward).  NeuralAutomataAgent.recurrent_action composes them.
+    memory_record_batch(population), memory_planes_batch(memory, record), gather_memory_batch(sense_tail, record)
+        the same three for every replica of a BatchedNeuralAutomataAgent's worlds, one launch each (die_memory_cells_batch,
+        die_memory_planes_backward_batch, die_gather_memory_backward_batch): (R, Nmax) records, (R, M, Nmax) memories, the expand
+        as (M, R, W, H) planes.  BatchedNeuralAutomataAgent.recurrent_action composes them.
 
 `ConvolutionModel.forward_device` evaluates a whole wide stack through `conv2d_wide`; `BatchedNeuralAutomataAgent.forward_device`
 a population of them in one launch per layer (die_nca_wide_backward_batch backward).  There is no eager fallback: a shape the
@@ -260,3 +264,141 @@ def gather_scale_batch(sense: th.Tensor, population) -> th.Tensor:
     if not isinstance(sense, th.Tensor) or sense.dtype != th.float32 or not sense.is_cuda or tuple(sense.shape) != (env.R, 3, env.W, env.H):
         raise ValueError(f'sense: a float32 CUDA tensor of shape {(env.R, 3, env.W, env.H)}')
     return _BatchedReadOut.apply(sense, population)
+
+
+# ---------------------------------------------------------------------------------------------------- memory channels, batched
+class BatchedMemoryRecord:
+    """Where every slot of every replica stood at one forward (die_memory_cells_batch): `cell` and `win`, (R, Nmax) int32 by slot
+    id — `MemoryRecord`'s two arrays with an R in front, the padding slots from n[r] on -1 in both — and the sizes `W`, `H`, `R`,
+    `Nmax`, `n`.  Both batched adjoints are driven by these two arrays alone, so a graph that keeps the record survives every
+    step and reset of the worlds.  The record also remembers the standing planes (the population's own buffer) and the epoch it
+    was taken at, for `memory_planes_batch`'s forward only: expand before the next record is taken."""
+    __slots__ = ('cell', 'win', 'W', 'H', 'R', 'Nmax', 'n', '_batch', '_standing', '_epoch')
+
+    def __init__(self, cell, win, W, H, n, batch, standing, epoch):
+        self.cell, self.win, self.W, self.H, self.R, self.Nmax = cell, win, int(W), int(H), int(cell.shape[0]), int(cell.shape[1])
+        self.n, self._batch, self._standing, self._epoch = tuple(n), batch, standing, int(epoch)
+
+
+def _memory_population(population, what: str):
+    from .batch import BatchedNeuralAutomataAgent
+    if not isinstance(population, BatchedNeuralAutomataAgent):
+        raise TypeError('population: a BatchedNeuralAutomataAgent')
+    if not population._memory_channels:
+        raise ValueError(f'{what}: a population without memory channels (memory_channels=0) has no record')
+    if population.env.per_replica:
+        raise NotImplementedError(f'{what}: large worlds (per_replica) are not batched — every replica is a stand-alone agent: use '
+                                  'replica_agent(r).recurrent_action / functional.memory_record')
+    return population.env
+
+
+def memory_record_batch(population) -> BatchedMemoryRecord:
+    """The record of a BatchedNeuralAutomataAgent's worlds as they stand now: the R standing planes built at the env's epoch
+    (die_stock_plane_batch) in a buffer the POPULATION owns and zeroes on every call — not the env's stock planes, so a later
+    `env.step(population)` finds those as it left them, and two calls at one epoch are safe — then one die_memory_cells_batch
+    launch.  Small worlds; a population with memory channels."""
+    env = _memory_population(population, 'memory_record_batch')
+    dev, R, W, H, Nmax = env.device, env.R, env.W, env.H, env.Nmax
+    standing = getattr(population, '_standing', None)
+    if standing is None:
+        standing = population._standing = th.zeros((R, W, H), dtype=th.int64, device=dev)
+    else:
+        standing.zero_()
+    m, a, _, b = env._structs()
+    sp = stream_ptr(dev)
+    _lib.check(_lib.lib.die_stock_plane_batch(C.byref(m), C.byref(a), C.byref(b), env.epoch, _ptr(standing), sp), 'die_stock_plane_batch')
+    cell = th.empty((R, Nmax), dtype=th.int32, device=dev)           # (every word is written: the padding slots -1)
+    win = th.empty((R, Nmax), dtype=th.int32, device=dev)
+    _lib.check(_lib.lib.die_memory_cells_batch(C.byref(m), C.byref(a), C.byref(b), _ptr(standing), env.epoch, _ptr(cell), _ptr(win), sp),
+               'die_memory_cells_batch')
+    return BatchedMemoryRecord(cell, win, W, H, env.n, b, standing, env.epoch)
+
+
+def _index_gather_batch(record, index, planes, plane_stride, replica_stride, M):
+    """die_memory_planes_backward_batch as the index-only gather it is: planes of R replicas -> (R, M, Nmax) rows, +0 where the
+    index is negative (the padding included), the values moved as 32-bit words."""
+    out = th.empty((record.R, M, record.Nmax), dtype=th.float32, device=planes.device)
+    _lib.check(_lib.lib.die_memory_planes_backward_batch(record.W, record.H, M, C.byref(record._batch), _ptr(index), _ptr(planes), plane_stride,
+                                                         replica_stride, _ptr(out), record.Nmax, stream_ptr(planes.device)),
+               'die_memory_planes_backward_batch')
+    return out
+
+
+def _plane_strides(t: th.Tensor, replica_dim: int, plane_dim: int, W: int, H: int):
+    """(tensor, plane_stride, replica_stride) of a 4-d tensor of planes whose planes are dense: as it is where its strides say
+    so (a slice of a larger buffer, a permuted view), else a contiguous copy."""
+    if t.stride()[2:] != (H, 1) or t.stride(plane_dim) < W * H or t.stride(replica_dim) < W * H:
+        t = t.contiguous()
+    return t, t.stride(plane_dim), t.stride(replica_dim)
+
+
+def _check_batched_memory_op(name, t, record, tail):
+    """`t` must be a float32 (R, M, *tail(record)) tensor on the record's device, 1 <= M <= 8."""
+    if not isinstance(record, BatchedMemoryRecord):
+        raise TypeError('record: a BatchedMemoryRecord (die_amd.functional.memory_record_batch)')
+    shape = tail(record)
+    if not isinstance(t, th.Tensor) or t.dtype != th.float32 or t.dim() != 2 + len(shape) or t.shape[0] != record.R or \
+            tuple(t.shape[2:]) != shape or not 1 <= t.shape[1] <= _lib.MEMORY_MAX_CHANNELS or t.device != record.cell.device:
+        raise ValueError(f'{name}: a float32 tensor of shape ({record.R}, M, {", ".join(str(s) for s in shape)}) with M in 1..'
+                         f'{_lib.MEMORY_MAX_CHANNELS} on {record.cell.device}')
+
+
+class _BatchedMemoryPlanes(th.autograd.Function):
+    """memory_planes_batch: die_memory_planes_batch forward into storage the graph owns, die_memory_planes_backward_batch backward."""
+
+    @staticmethod
+    def forward(ctx, memory, record):
+        R, W, H, M = record.R, record.W, record.H, memory.shape[1]
+        # plane j of replica r at (j * R + r) * W * H: a batched layer launch reads plane j of every replica one plane apart
+        planes = th.empty((M, R, W, H), dtype=th.float32, device=memory.device)
+        m = _lib.Medium(W, H, _lib.DIE_F32, record._epoch, None, None, None, None, 0, 0, 0, 0, 0, 0, 0, 0, None)     # (W, H, gW are read)
+        _lib.check(_lib.lib.die_memory_planes_batch(C.byref(m), C.byref(record._batch), _ptr(record._standing), record._epoch, M, _ptr(memory),
+                                                    record.Nmax, _ptr(planes), stream_ptr(memory.device)), 'die_memory_planes_batch')
+        ctx.record, ctx.M = record, M
+        return planes
+
+    @staticmethod
+    @th.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        r = ctx.record
+        g, plane_stride, replica_stride = _plane_strides(grad.to(dtype=th.float32), 1, 0, r.W, r.H)
+        return _index_gather_batch(r, r.win, g, plane_stride, replica_stride, ctx.M), None
+
+
+class _BatchedGatherMemory(th.autograd.Function):
+    """gather_memory_batch: the read-out driven by the record's cells forward, die_gather_memory_backward_batch backward."""
+
+    @staticmethod
+    def forward(ctx, sense_tail, record):
+        ctx.record, ctx.M = record, sense_tail.shape[1]
+        t, plane_stride, replica_stride = _plane_strides(sense_tail, 0, 1, record.W, record.H)
+        return _index_gather_batch(record, record.cell, t, plane_stride, replica_stride, ctx.M)
+
+    @staticmethod
+    @th.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        r, M = ctx.record, ctx.M
+        g = grad.to(dtype=th.float32).contiguous()
+        planes = th.empty((r.R, M, r.W, r.H), dtype=th.float32, device=g.device)      # (cleared by the call)
+        _lib.check(_lib.lib.die_gather_memory_backward_batch(r.W, r.H, M, C.byref(r._batch), _ptr(r.cell), _ptr(g), r.Nmax, _ptr(planes),
+                                                             r.W * r.H, M * r.W * r.H, stream_ptr(g.device)),
+                   'die_gather_memory_backward_batch')
+        return planes, None
+
+
+def memory_planes_batch(memory: th.Tensor, record: BatchedMemoryRecord) -> th.Tensor:
+    """The expand of every replica with a `grad_fn`: an (R, M, Nmax) float32 memory by slot id -> (M, R, W, H) planes — plane j of
+    replica r one plane after replica r - 1's, the layout in which a batched layer launch reads them — in storage the graph owns
+    (die_memory_planes_batch on the record's standing planes).  `out[j, r]` is bit for bit the stand-alone `memory_planes` of
+    replica r.  The backward is die_memory_planes_backward_batch: a gather, bit-reproducible; the padding slots get +0."""
+    _check_batched_memory_op('memory', memory, record, lambda r: (r.Nmax,))
+    return _BatchedMemoryPlanes.apply(memory.contiguous(), record)
+
+
+def gather_memory_batch(sense_tail: th.Tensor, record: BatchedMemoryRecord) -> th.Tensor:
+    """The memory read-out of every replica with a `grad_fn`: the stacks' planes 3.. as an (R, M, W, H) float32 tensor (a slice
+    `sense[:, 3:]` is read where it lies) -> (R, M, Nmax) by slot id, bit for bit die_gather_memory_batch's values, read through
+    the record; dead and padding slots +0.  The backward is die_gather_memory_backward_batch: fp32 atomic adds, replica r the
+    stand-alone bits wherever no cell holds more than two alive slots with a non-zero gradient."""
+    _check_batched_memory_op('sense_tail', sense_tail, record, lambda r: (r.W, r.H))
+    return _BatchedGatherMemory.apply(sense_tail, record)

@@ -15,7 +15,14 @@ is the mean squared error of (dx, dy) against the teacher's over the alive agent
 baseline.  With M > 0 the baseline is trained as well, on a world seeded alike, and both final losses are printed — side by side,
 with no claim about which is smaller.  `--time` prints optimiser steps per second.
 
+`--replicas R [--students C]` runs the window loop on a `BatchedEnv` of R worlds instead: the teacher is a `BatchedPhysarumAgent`
+— its heading is state, so a memoryless student cannot express it either — which hands out its targets through
+`step(..., action=target)`, and C students (E = R / C worlds each; default C = R) are trained in ONE optimiser step through
+`BatchedNeuralAutomataAgent.recurrent_action`: one launch per kernel for all R worlds, a (C, P) gradient.  The stand-alone path
+above is untouched by it.
+
     python examples/recurrent_agent.py --size 96 --memory-channels 2 --unroll 8 --steps 200
+    python examples/recurrent_agent.py --size 96 --memory-channels 2 --unroll 8 --steps 200 --replicas 16 --students 16
 """
 import argparse
 import os
@@ -27,6 +34,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from die_amd import Dynamics, Env, GradientAgent, NeuralAutomataAgent, functional          # noqa: E402
+from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent, BatchedPhysarumAgent   # noqa: E402
 
 SCALE, DEPOSIT = 0.01, 2.0
 
@@ -98,6 +106,66 @@ def train(size, memory_channels, unroll, detach_every, steps, lr=1e-2, seed=0, i
     return student, losses
 
 
+def train_batched(size, memory_channels, unroll, detach_every, steps, lr=1e-2, seed=0, hidden_channels=8, warm=4, replicas=4, students=None,
+                  log=print, timed=False):
+    """`train` on R = `replicas` worlds at once: `students` candidates (default R) of E = R / students worlds each, one Adam step per
+    episode for all of them.  Every episode: the worlds reset, a fresh BatchedPhysarumAgent takes `warm` steps alone, then the window
+    of `unroll` steps — the students look at the worlds through `recurrent_action`, handing `memory_next` on, the teacher steps them
+    and leaves its actions in `target`.  The loss is the sum over the students of their mean squared error, so that every student's
+    row of the (C, P) gradient is its own.  Returns (the BatchedNeuralAutomataAgent, the list of episode losses)."""
+    students = replicas if students is None else students
+    if memory_channels < 1:
+        raise SystemExit('--replicas trains students with memory: --memory-channels at least 1')
+    if students < 1 or replicas % students:
+        raise SystemExit(f'--students {students} must divide --replicas {replicas}')
+    env = BatchedEnv((size, size), Dynamics(food_infinite=True, rate_decay_chem=0.025, diffuse_sigma=.8), replicas=replicas, seed=seed)
+    template = make_student(memory_channels, hidden_channels, seed)
+    rows = []
+    for _ in range(students):                                     # different initialisations side by side
+        template.model.init_weights()
+        rows.append(torch.nn.utils.parameters_to_vector(template.model.parameters()).detach().clone())
+    pop = BatchedNeuralAutomataAgent(env, template, torch.stack(rows), replicas // students)
+    pop.parameters.requires_grad_()
+    opt = torch.optim.Adam([pop.parameters], lr=lr)
+    target = torch.zeros((3, env.R, env.Nmax), device=env.device)
+    exists = torch.zeros((env.R, env.Nmax), dtype=torch.bool, device=env.device)
+    for r in range(env.R):
+        exists[r, :env.n[r]] = True
+    losses, t0 = [], None
+    warmup = max(1, steps // 10)
+    for it in range(steps):
+        if timed and it == warmup:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        env.reset()
+        teacher = BatchedPhysarumAgent(env, scale=SCALE, deposit=DEPOSIT, seed=seed)
+        for _ in range(warm):
+            env.step(teacher)
+        pop.reset_memory()
+        memory, loss = None, 0.
+        for t in range(unroll):
+            if memory is not None and detach_every and t % detach_every == 0:
+                memory = memory.detach()
+            got, memory = pop.recurrent_action(memory)            # the students look at the worlds the teacher is about to act on
+            live = (exists & (env.alive > 0)).reshape(students, -1)
+            env.step(teacher, action=target)                      # its actions on those worlds: the targets
+            err = (((got[:2] - target[:2]) / SCALE) ** 2).sum(0).reshape(students, -1)
+            loss = loss + ((err * live).sum(1) / (2 * live.sum(1).clamp(min=1))).sum()
+        loss = loss / unroll
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        losses.append(float(loss.detach()) / students)
+        if it % 10 == 0 or it == steps - 1:
+            log(f'M={memory_channels} R={replicas} C={students} step {it:5d}: mean loss per student {losses[-1]:.6f}')
+    if t0 is not None and steps > warmup:
+        torch.cuda.synchronize()
+        rate = (steps - warmup) / (time.perf_counter() - t0)
+        log(f'M={memory_channels}, T={unroll}, R={replicas}, C={students}: {rate:.2f} optimiser steps/s over {steps - warmup} steps '
+            f'({rate * replicas * unroll:.0f} world-steps/s)')
+    return pop, losses
+
+
 def main():
     p = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
     p.add_argument('--size', type=int, default=96)
@@ -112,9 +180,16 @@ def main():
     p.add_argument('--lr', type=float, default=1e-2)
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--time', action='store_true', help='print optimiser steps per second')
+    p.add_argument('--replicas', type=int, default=0, metavar='R', help='train on R batched worlds (0: the stand-alone path)')
+    p.add_argument('--students', type=int, default=None, metavar='C', help='with --replicas: C students of R / C worlds each (default R)')
     args = p.parse_args()
     if args.unroll < 1 or args.steps < 1 or args.detach_every < 0:
         raise SystemExit('--unroll and --steps are at least 1, --detach-every at least 0')
+    if args.replicas:
+        _, losses = train_batched(args.size, args.memory_channels, args.unroll, args.detach_every, args.steps, args.lr, args.seed,
+                                  args.hidden_channels, args.warm, args.replicas, args.students, timed=args.time)
+        print(f'final mean loss per student, {args.memory_channels} memory channels on {args.replicas} worlds: {losses[-1]:.6f}')
+        return
     final = {}
     for M in dict.fromkeys((args.memory_channels, 0)):
         _, losses = train(args.size, M, args.unroll, args.detach_every, args.steps, args.lr, args.seed, args.inertia, args.hidden_channels,

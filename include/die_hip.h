@@ -1256,6 +1256,63 @@ int die_nca_wide_backward_batch(const die_medium* m, const die_batch* b, const d
                                 const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, float* grad_in,
                                 int64_t grad_in_stride, void* stream);
 
+/* ---- Batched BPTT: the memory channels' adjoints for every replica of a die_batch (BatchedNeuralAutomataAgent.recurrent_action) --
+ * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
+ * The batched twins of die_memory_cells / die_memory_planes_backward / die_gather_memory_backward: ONE launch each for all R
+ * replicas, the replica in blockIdx.y (as die_memory_planes_batch / die_gather_memory_batch), the device bodies those of the
+ * stand-alone kernels.  Records are [R][b->agent_stride] int32, replica r's row at r * b->agent_stride; memories and their
+ * gradients are dense (R, M, row) arrays, row j of replica r at (r * memory_channels + j) * row_stride; planes are plane j of
+ * replica r at r * replica_stride + j * plane_stride.
+ *
+ * die_memory_cells_batch — the record of every replica.  Replica r's slots start at r * b->agent_stride (slot order:
+ * agents->slot must be NULL), its standing plane (die_stock_plane_batch at `epoch`) at standing + r * b->plane_stride.  For n <
+ * b->n[r] the two words are die_memory_cells' of replica r; the padding slots n >= b->n[r] are written -1 in both arrays, so
+ * the two adjoints never need n[] again.  Checked before the launch as die_memory_cells, and: a null batch, a slot array,
+ * replicas outside 1..DIE_MAX_REPLICAS, agent_stride outside 1..DIE_OWNER_SLOT_MASK - 1, n[r] outside 0..agent_stride,
+ * b->plane_stride < W * H. */
+int die_memory_cells_batch(const die_medium* m, const die_agents* agents, const die_batch* b, const unsigned long long* standing,
+                           int32_t epoch, int32_t* cell_out, int32_t* win_out, void* stream);
+/* die_memory_planes_backward_batch — the expand's adjoint, a gather:
+ *   grad_memory[r][j][id] = 0 <= win[r][id] < W * H ? grad_planes_r,j[win[r][id]] : +0.0f     for every id < b->agent_stride.
+ * Every word of every row, padding included, is written exactly once; the values move as 32-bit words; no atomics.  With
+ * `cell` for an index the same call is the read-out's forward through the record.  Checked as die_memory_planes_backward, and:
+ * the die_batch as above, row_stride < agent_stride, and strides under which two of the R * M planes would share words: the
+ * planes may lie replica-major (replica_stride >= (M - 1) * plane_stride + W * H: a sense gradient, a grad_in) or plane-major
+ * (plane_stride >= (R - 1) * replica_stride + W * H: die_memory_planes_batch's layout). */
+int die_memory_planes_backward_batch(int32_t W, int32_t H, int32_t memory_channels, const die_batch* b, const int32_t* win,
+                                     const float* grad_planes, int64_t plane_stride, int64_t replica_stride, float* grad_memory,
+                                     int64_t row_stride, void* stream);
+/* die_gather_memory_backward_batch — the read-out's adjoint: the W * H cells of each of the R * M planes are cleared on `stream`
+ * (the words between two planes and between two replicas are left alone), then ONE launch adds
+ *   grad_planes_r,j[cell[r][id]] += grad_memory[r][j][id]     wherever 0 <= cell[r][id] < W * H; a zero term is skipped.
+ * fp32 atomic adds, the stand-alone method: replica r has die_gather_memory_backward's bits wherever no cell holds more than two
+ * alive slots with a non-zero gradient.  Checked before anything is cleared, as die_memory_planes_backward_batch with grad_planes
+ * the output. */
+int die_gather_memory_backward_batch(int32_t W, int32_t H, int32_t memory_channels, const die_batch* b, const int32_t* cell,
+                                     const float* grad_memory, int64_t row_stride, float* grad_planes, int64_t plane_stride,
+                                     int64_t replica_stride, void* stream);
+/* die_nca_wide_sense_batch_store for a population whose agents carry memory: layer 0 reads ([agents,] food, chem, memory_0 ..
+ * memory_{M-1}), `mem_planes` laid out as die_memory_planes_batch writes them (plane j of replica r at (j * R + r) *
+ * b->plane_stride), and the last layer gives 3 + M planes; the tanh and the mask fall on all of them.  Checked as the parent, in
+ * its order, with those channel counts, and: null mem_planes, memory_channels outside 1..DIE_MEMORY_MAX_CHANNELS, memory planes
+ * that overlap the store or the masked planes. */
+int die_nca_wide_sense_batch_store_memory(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* store,
+                                          int64_t store_bytes, float* masked, const die_nca_dropout* drop, const float* mem_planes,
+                                          int32_t memory_channels, void* stream);
+/* die_nca_wide_backward_batch for such a stack: grad_sense holds 3 + M planes per replica, layer 0's inputs include the memory
+ * planes, and `grad_in`, when given, holds replica r's 2 + with_agent_channel + M planes in channel order — the caller takes the
+ * chem plane for the env's chem node and the M memory planes for die_memory_planes_backward_batch.  The same two adjoint kernels
+ * and the same float64 fold: 3 L - 1 launches, 3 L with grad_in; for E = 1 row r is bit for bit the stand-alone per-layer
+ * die_conv2d_wide_backward gradients of replica r.  A population whose incoming memory has a graph always passes grad_in; with
+ * neither that nor a chem node, NULL skips the kernel.  Checked as the parent, in its order; the byte query gives -1 for a
+ * refused shape (the parent's query and call keep refusing a 3 + M stack). */
+int64_t die_nca_wide_backward_batch_memory_workspace_bytes(int32_t W, int32_t H, int32_t replicas, const die_nca_batch* nca,
+                                                           int32_t memory_channels);
+int die_nca_wide_backward_batch_memory(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store,
+                                       const float* grad_sense, int64_t sense_stride, float* grad, int64_t grad_stride,
+                                       const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, float* grad_in,
+                                       int64_t grad_in_stride, const float* mem_planes, int32_t memory_channels, void* stream);
+
 /* die_food_flow_batch on the replicas whose bit is set in replica_mask (bit r = replica r); the others' planes are not touched.
  * One launch: a row of workgroups per replica, those of unset replicas exit at once.  A full mask leaves exactly what
  * die_food_flow_batch leaves; an empty mask launches nothing.  Bits at or above b->replicas must be 0. */
