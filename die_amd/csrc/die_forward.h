@@ -255,14 +255,16 @@ __device__ __forceinline__ FwdOut die_forward_agent_mem(const FwdArgs& a, const 
             unseen = fabs(delta) > a.sense_rad;
             right = delta > a.atol;
         } else {
-            // any other direction: the same tests on |u|·cos and |u|·sin of delta = heading − angle(u), from the heading's
-            // (cos, sin) — no arctangent, no float64.  A decision differs from the float64 one only within ≈ 3e-7 rad of a
-            // threshold (the fp32 arctangent this replaces was no closer).
-            const float nrm = a.normalized ? 1.f : norm;
-            const float c = cd * ux + sd * uy, s = sd * ux - cd * uy;
-            und_grad = ux > 0.f && fabsf(uy) <= a.t_grad * ux;
-            und_turn = c >= a.c_turn * nrm;
-            unseen = c < a.c_sense * nrm;
+            // any other direction: the same tests on cos and sin of delta = heading − angle(u), from the heading's (cos, sin)
+            // and the UNIT vector u / |u| — no arctangent, no float64.  (Always the unit vector: a raw gradient in the
+            // denormals has a few bits left, and its products with cos and sin none.)  A decision can differ from the
+            // float64 one where |delta| is within a few fp32 ulps of cos, divided by |sin threshold|, of a threshold: seen at
+            // up to 2.9e-6 rad of x_turn (0.03 .. 0.08 rad), 1.3e-7 rad of sense_rad = 90°, 120° and of |delta| = π; the
+            // bound tests/forward_tie_cases.py derives and holds every slot to is 2.7e-5 / 1.8e-6 rad at the defaults.
+            const float c = cd * nx + sd * ny, s = sd * nx - cd * ny;
+            und_grad = nx > 0.f && fabsf(ny) <= a.t_grad * nx;
+            und_turn = c >= a.c_turn;
+            unseen = c < a.c_sense;
             right = s > 0.f;
         }
         const bool und = und_grad || und_turn || unseen;
@@ -279,7 +281,7 @@ __device__ __forceinline__ FwdOut die_forward_agent_mem(const FwdArgs& a, const 
         die_polar2xy_heading(d2_64, r, &ux, &uy);
         dep_mask = (und_grad || und_turn) ? 0.1f : 1.0f;   // clip(mask, .1, 1) (gradient.py:210-214)
         d_new = d2_64;            // (the reference re-derives it as angle(exp(i·d2)): the same value up to one ulp of libm noise)
-        heading_from_vector = !a.normalized;               // |g| may be 0 there: angle(0) = 0
+        heading_from_vector = !a.normalized && r == 0.f;   // |g| may be 0 there: angle(0) = 0; any other length leaves d2
     }
     // _process_momentum (gradient.py:82-91)
     if (a.inertia != 0.f || a.noise_scale != 0.f) {
