@@ -59,6 +59,35 @@ int64_t die_ws_scan_bytes(int32_t W, int32_t H);
 int die_diffuse_rows_batch(const float* src, float* dst, int32_t W, int32_t H, int32_t replicas, int64_t plane_stride, float sigma,
                            float decay, const die_dynamics_row* rows, const die_dynamics_row* rows_host, void* stream, const char* who);
 
+// ---- what the host side of several files asks alike: each stated here, once ------------------------------------------------
+// do [p, p + p_bytes) and [q, q + q_bytes) share a byte?  (a null pointer is no range)
+static inline bool die_ranges_overlap(const void* p, int64_t p_bytes, const void* q, int64_t q_bytes) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return p && q && a < b + (uintptr_t)q_bytes && b < a + (uintptr_t)p_bytes;
+}
+// a die_batch's n[0 .. replicas) as a kernel's n[DIE_MAX_REPLICAS], 0 past the last replica; returns the largest
+static inline int64_t die_replica_counts(int64_t* dst, const int64_t* n, int32_t replicas) {
+    int64_t nmax = 0;
+    for (int r = 0; r < DIE_MAX_REPLICAS; ++r) {
+        dst[r] = r < replicas ? n[r] : 0;
+        if (dst[r] > nmax) nmax = dst[r];
+    }
+    return nmax;
+}
+// a die_batch's own fields, as the batched stock and memory calls require them (cells < 0: the call has no plane_stride rule of its
+// own at this point).  die_nca_batch_shape_check and the steps of die_env.hip, die_init.hip and die_births.hip word theirs otherwise.
+static inline int die_batch_check(const die_batch* b, int64_t cells, const char* who) {
+    DIE_REQUIRE(b->replicas >= 1 && b->replicas <= DIE_MAX_REPLICAS, "%s: 1..%d replicas (got %d)", who, DIE_MAX_REPLICAS, b->replicas);
+    DIE_REQUIRE(cells < 0 || b->plane_stride >= cells, "%s: plane_stride %lld smaller than a plane (%lld cells)", who,
+                (long long)b->plane_stride, (long long)cells);
+    DIE_REQUIRE(b->agent_stride >= 1 && b->agent_stride <= (int64_t)DIE_OWNER_SLOT_MASK - 1, "%s: agent_stride %lld outside 1..%lld", who,
+                (long long)b->agent_stride, (long long)DIE_OWNER_SLOT_MASK - 1);
+    for (int r = 0; r < b->replicas; ++r)
+        DIE_REQUIRE(b->n[r] >= 0 && b->n[r] <= b->agent_stride, "%s: replica %d has %lld agents (0..%lld)", who, r, (long long)b->n[r],
+                    (long long)b->agent_stride);
+    return DIE_OK;
+}
+
 // A checked die_nca_dropout as the words a kernel reads (die_nca.hip die_dropout_words; die_rng.h defines the mask)
 struct DropWords {
     uint64_t seed, seed_stride;  // replica z is masked with key seed + z · seed_stride (mod 2^64)

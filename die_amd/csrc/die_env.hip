@@ -1574,8 +1574,7 @@ static int nca_env_step_batch(const die_medium* m, const die_agents* a, const di
     int rc = batch_world_check(m, a, d, b, ws_bytes, true, who);
     if (rc != DIE_OK) return rc;
     const bool sense_stock = stock && (!ms || ms->with_stock);
-    rc = wide ? die_nca_wide_batch_check(nca, m->W, m->H, b->replicas, who, sense_stock, ms ? ms->M : 0)
-              : die_nca_batch_check(nca, m->W, m->H, b->replicas, who, stock != nullptr);
+    rc = die_nca_stack_check(wide ? DIE_NCA_WIDE : DIE_NCA_NARROW, nca, m->W, m->H, b->replicas, who, true, sense_stock, ms ? ms->M : 0);
     if (rc != DIE_OK) return rc;
     DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX && m->epoch == nca->sense_epoch % DIE_OWNER_EPOCH_MAX + 1,
                 "%s: claims at epoch %d cannot follow sensing at epoch %d", who, m->epoch, nca->sense_epoch);

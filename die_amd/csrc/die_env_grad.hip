@@ -249,7 +249,7 @@ extern "C" int die_deposit_cells_batch(const die_medium* m, const die_agents* ag
     a.owner = (const unsigned long long*)m->owner;
     a.x = (const uint32_t*)ag->x; a.y = (const uint32_t*)ag->y; a.alive = (const uint8_t*)ag->alive;
     a.cells = cells_out;
-    for (int r = 0; r < DIE_MAX_REPLICAS; ++r) a.n[r] = r < b->replicas ? b->n[r] : 0;
+    die_replica_counts(a.n, b->n, b->replicas);
     const int64_t g = (b->agent_stride + DIE_BLOCK - 1) / DIE_BLOCK;
     k_deposit_cells_batch<<<dim3((unsigned)(g < 8192 ? g : 8192), (unsigned)b->replicas), DIE_BLOCK, 0, (hipStream_t)stream>>>(a);
     DIE_CHECK_LAUNCH(who);
@@ -314,7 +314,7 @@ extern "C" int die_env_step_backward_batch(int32_t W, int32_t H, const die_batch
     BatchGatherArgs a;
     a.plane = grad_chem; a.cells = cells; a.out = grad_deposit; a.n_cells = (uint32_t)n_cells;
     a.plane_stride = b->plane_stride; a.agent_stride = b->agent_stride;
-    for (int r = 0; r < DIE_MAX_REPLICAS; ++r) a.n[r] = r < b->replicas ? b->n[r] : 0;
+    die_replica_counts(a.n, b->n, b->replicas);
     const int64_t per_block = (int64_t)DIE_BLOCK * GATHER_PER_THREAD;
     const int64_t g = (b->agent_stride + per_block - 1) / per_block;
     k_gather_cells_batch<<<dim3((unsigned)(g < 8192 ? g : 8192), (unsigned)b->replicas), DIE_BLOCK, 0, (hipStream_t)stream>>>(a);

@@ -433,11 +433,7 @@ static int init_batch(const char* who, const die_medium* m, const die_agents* a,
         ib.seed[r] = r >= b->replicas ? 0 : seeds ? seeds[r] : seed + (uint64_t)r * world_stride;
     ib.ws_stride = die_ws_scan_bytes(m->W, m->H);
     ib.nb = (C + SCAN_TILE - 1) / SCAN_TILE;
-    int64_t nmax = 0;
-    for (int r = 0; r < DIE_MAX_REPLICAS; ++r) {
-        ib.n[r] = r < b->replicas ? b->n[r] : 0;
-        nmax = ib.n[r] > nmax ? ib.n[r] : nmax;
-    }
+    const int64_t nmax = die_replica_counts(ib.n, b->n, b->replicas);
     const die_geo g = die_geo_of(m);
     const hipStream_t s = (hipStream_t)stream;
     const int R = b->replicas;

@@ -99,7 +99,7 @@ int die_memory_planes_launch(int32_t W, int32_t H, int32_t replicas, const int64
     // 16-byte accesses: whole groups of 4 cells, and every plane of every replica starting on a 16-byte boundary
     k.vec = (H & 3) == 0 && (plane_j & 3) == 0 && (plane_rep & 3) == 0 && ((uintptr_t)planes & 15) == 0 && (standing_rep & 1) == 0 &&
             ((uintptr_t)standing & 15) == 0;
-    for (int r = 0; r < DIE_MAX_REPLICAS; ++r) k.n[r] = r < replicas ? n[r] : 0;
+    die_replica_counts(k.n, n, replicas);
     const int64_t units = k.vec ? k.cells / 4 : k.cells, g = (units + DIE_BLOCK - 1) / DIE_BLOCK;
     DIE_REQUIRE(g <= 0x7FFFFFFF, "%s: field too large (%lld cells)", who, (long long)k.cells);
     k_memory_planes<<<dim3((unsigned)g, (unsigned)replicas), DIE_BLOCK, 0, (hipStream_t)stream>>>(k);
@@ -115,11 +115,7 @@ int die_gather_memory_launch(const die_medium* m, const die_agents* a, int32_t r
     k.planes = (const uint32_t*)planes; k.mem = (uint32_t*)mem;
     k.agent_stride = agent_stride; k.plane_j = plane_j; k.plane_rep = plane_rep; k.mem_row = mem_row; k.mem_rep = mem_rep;
     k.W = m->W; k.H = m->H; k.M = M;
-    int64_t nmax = 0;
-    for (int r = 0; r < DIE_MAX_REPLICAS; ++r) {
-        k.n[r] = r < replicas ? n[r] : 0;
-        if (k.n[r] > nmax) nmax = k.n[r];
-    }
+    const int64_t nmax = die_replica_counts(k.n, n, replicas);
     if (nmax == 0) return DIE_OK;                            // no slot anywhere: nothing to write
     k_gather_memory<<<dim3((unsigned)((nmax + DIE_BLOCK - 1) / DIE_BLOCK), (unsigned)replicas), DIE_BLOCK, 0, (hipStream_t)stream>>>(k);
     DIE_CHECK_LAUNCH(who);
@@ -127,11 +123,6 @@ int die_gather_memory_launch(const die_medium* m, const die_agents* a, int32_t r
 }
 
 // ---- the stand-alone entry points: every argument checked before anything is launched ---------------------------------
-static bool mem_overlap(const void* p, int64_t p_bytes, const void* q, int64_t q_bytes) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + (uintptr_t)q_bytes && b < a + (uintptr_t)p_bytes;
-}
-
 static int memory_world_check(const die_medium* m, int32_t M, const char* who) {
     DIE_REQUIRE(m->W >= 1 && m->H >= 1, "%s: bad size %dx%d", who, m->W, m->H);
     if (m->gW > 0) {
@@ -139,18 +130,6 @@ static int memory_world_check(const die_medium* m, int32_t M, const char* who) {
         return DIE_ERR_UNSUPPORTED;
     }
     DIE_REQUIRE(M >= 1 && M <= DIE_MEMORY_MAX_CHANNELS, "%s: %d memory channels outside 1..%d", who, M, DIE_MEMORY_MAX_CHANNELS);
-    return DIE_OK;
-}
-
-static int batch_check(const die_batch* b, int64_t cells, const char* who) {
-    DIE_REQUIRE(b->replicas >= 1 && b->replicas <= DIE_MAX_REPLICAS, "%s: 1..%d replicas (got %d)", who, DIE_MAX_REPLICAS, b->replicas);
-    DIE_REQUIRE(b->plane_stride >= cells, "%s: plane_stride %lld smaller than a plane (%lld cells)", who, (long long)b->plane_stride,
-                (long long)cells);
-    DIE_REQUIRE(b->agent_stride >= 1 && b->agent_stride <= (int64_t)DIE_OWNER_SLOT_MASK - 1, "%s: agent_stride %lld outside 1..%lld", who,
-                (long long)b->agent_stride, (long long)DIE_OWNER_SLOT_MASK - 1);
-    for (int r = 0; r < b->replicas; ++r)
-        DIE_REQUIRE(b->n[r] >= 0 && b->n[r] <= b->agent_stride, "%s: replica %d has %lld agents (0..%lld)", who, r, (long long)b->n[r],
-                    (long long)b->agent_stride);
     return DIE_OK;
 }
 
@@ -169,8 +148,8 @@ extern "C" int die_memory_planes(const die_medium* m, const unsigned long long* 
                 (long long)n_slots);
     DIE_REQUIRE(plane_stride >= cells, "%s: plane_stride %lld smaller than a plane (%lld cells)", who, (long long)plane_stride, (long long)cells);
     const int64_t out_bytes = ((int64_t)(memory_channels - 1) * plane_stride + cells) * 4;
-    DIE_REQUIRE(!mem_overlap(planes, out_bytes, standing, cells * 8), "%s: the output planes overlap the standing plane", who);
-    DIE_REQUIRE(!mem_overlap(planes, out_bytes, memory, ((int64_t)(memory_channels - 1) * row_stride + n_slots) * 4),
+    DIE_REQUIRE(!die_ranges_overlap(planes, out_bytes, standing, cells * 8), "%s: the output planes overlap the standing plane", who);
+    DIE_REQUIRE(!die_ranges_overlap(planes, out_bytes, memory, ((int64_t)(memory_channels - 1) * row_stride + n_slots) * 4),
                 "%s: the output planes overlap the memory", who);
     return die_memory_planes_launch(m->W, m->H, 1, &n_slots, standing, 0, epoch, memory_channels, memory, row_stride, 0, planes, plane_stride,
                                     0, stream, who);
@@ -184,15 +163,15 @@ extern "C" int die_memory_planes_batch(const die_medium* m, const die_batch* b, 
     if (rc != DIE_OK) return rc;
     const int64_t cells = (int64_t)m->W * m->H;
     DIE_REQUIRE(epoch >= 1 && epoch <= DIE_OWNER_EPOCH_MAX, "%s: epoch %d outside 1..%d", who, epoch, DIE_OWNER_EPOCH_MAX);
-    rc = batch_check(b, cells, who);
+    rc = die_batch_check(b, cells, who);
     if (rc != DIE_OK) return rc;
     DIE_REQUIRE(row_stride >= b->agent_stride, "%s: row_stride %lld smaller than a row (%lld slots)", who, (long long)row_stride,
                 (long long)b->agent_stride);
     const int64_t R = b->replicas, M = memory_channels;
     const int64_t out_bytes = ((M * R - 1) * b->plane_stride + cells) * 4;
-    DIE_REQUIRE(!mem_overlap(planes, out_bytes, standing, ((R - 1) * b->plane_stride + cells) * 8), "%s: the output planes overlap the "
+    DIE_REQUIRE(!die_ranges_overlap(planes, out_bytes, standing, ((R - 1) * b->plane_stride + cells) * 8), "%s: the output planes overlap the "
                 "standing planes", who);
-    DIE_REQUIRE(!mem_overlap(planes, out_bytes, memory, R * M * row_stride * 4), "%s: the output planes overlap the memory", who);
+    DIE_REQUIRE(!die_ranges_overlap(planes, out_bytes, memory, R * M * row_stride * 4), "%s: the output planes overlap the memory", who);
     return die_memory_planes_launch(m->W, m->H, b->replicas, b->n, standing, b->plane_stride, epoch, memory_channels, memory, row_stride,
                                     M * row_stride, planes, R * b->plane_stride, b->plane_stride, stream, who);
 }
@@ -213,7 +192,7 @@ extern "C" int die_gather_memory(const die_medium* m, const die_agents* agents, 
                 (long long)DIE_OWNER_SLOT_MASK - 1);
     DIE_REQUIRE(plane_stride >= cells, "%s: plane_stride %lld smaller than a plane (%lld cells)", who, (long long)plane_stride, (long long)cells);
     DIE_REQUIRE(row_stride >= N && row_stride >= 1, "%s: row_stride %lld smaller than a row (%lld slots)", who, (long long)row_stride, (long long)N);
-    DIE_REQUIRE(!mem_overlap(memory, ((int64_t)(memory_channels - 1) * row_stride + N) * 4, planes,
+    DIE_REQUIRE(!die_ranges_overlap(memory, ((int64_t)(memory_channels - 1) * row_stride + N) * 4, planes,
                              ((int64_t)(memory_channels - 1) * plane_stride + cells) * 4), "%s: the memory overlaps the planes", who);
     return die_gather_memory_launch(m, agents, 1, &N, 0, memory_channels, planes, plane_stride, 0, memory, row_stride, 0, stream, who);
 }
@@ -227,14 +206,14 @@ extern "C" int die_gather_memory_batch(const die_medium* m, const die_agents* ag
     if (rc != DIE_OK) return rc;
     DIE_REQUIRE(!agents->slot, "%s: replicas hold their agents in slot order (no slot array)", who);
     const int64_t cells = (int64_t)m->W * m->H, R = b->replicas, M = memory_channels;
-    rc = batch_check(b, cells, who);
+    rc = die_batch_check(b, cells, who);
     if (rc != DIE_OK) return rc;
     DIE_REQUIRE(plane_stride >= cells, "%s: plane_stride %lld smaller than a plane (%lld cells)", who, (long long)plane_stride, (long long)cells);
     DIE_REQUIRE(replica_stride >= (M - 1) * plane_stride + cells, "%s: replica_stride %lld smaller than a replica's %lld planes", who,
                 (long long)replica_stride, (long long)M);
     DIE_REQUIRE(row_stride >= b->agent_stride, "%s: row_stride %lld smaller than a row (%lld slots)", who, (long long)row_stride,
                 (long long)b->agent_stride);
-    DIE_REQUIRE(!mem_overlap(memory, R * M * row_stride * 4, planes, ((R - 1) * replica_stride + (M - 1) * plane_stride + cells) * 4),
+    DIE_REQUIRE(!die_ranges_overlap(memory, R * M * row_stride * 4, planes, ((R - 1) * replica_stride + (M - 1) * plane_stride + cells) * 4),
                 "%s: the memory overlaps the planes", who);
     return die_gather_memory_launch(m, agents, b->replicas, b->n, b->agent_stride, memory_channels, planes, plane_stride, replica_stride,
                                     memory, row_stride, M * row_stride, stream, who);

@@ -132,11 +132,6 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_gather_memory_backward_batch(MemI
 }
 
 // ---- the entry points: every argument checked before anything is launched -------------------------------------------------
-static bool grad_overlap(const void* p, int64_t p_bytes, const void* q, int64_t q_bytes) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + (uintptr_t)q_bytes && b < a + (uintptr_t)p_bytes;
-}
-
 static int index_check(int32_t W, int32_t H, int32_t M, int64_t n_slots, int64_t row_stride, int64_t plane_stride, const char* who) {
     DIE_REQUIRE(W >= 1 && H >= 1, "%s: bad size %dx%d", who, W, H);
     DIE_REQUIRE(M >= 1 && M <= DIE_MEMORY_MAX_CHANNELS, "%s: %d memory channels outside 1..%d", who, M, DIE_MEMORY_MAX_CHANNELS);
@@ -166,11 +161,11 @@ extern "C" int die_memory_cells(const die_medium* m, const die_agents* agents, c
                 (long long)DIE_OWNER_SLOT_MASK - 1);
     DIE_REQUIRE(N == 0 || (agents->x && agents->y && agents->alive), "%s: null agent array", who);
     int32_t* const outs[2] = {cell_out, win_out};
-    DIE_REQUIRE(!grad_overlap(cell_out, N * 4, win_out, N * 4), "%s: the two records overlap", who);
+    DIE_REQUIRE(!die_ranges_overlap(cell_out, N * 4, win_out, N * 4), "%s: the two records overlap", who);
     for (int q = 0; q < 2 && N > 0; ++q) {
-        DIE_REQUIRE(!grad_overlap(outs[q], N * 4, standing, cells * 8), "%s: a record overlaps the standing plane", who);
-        DIE_REQUIRE(!grad_overlap(outs[q], N * 4, agents->x, N * 4) && !grad_overlap(outs[q], N * 4, agents->y, N * 4) &&
-                    !grad_overlap(outs[q], N * 4, agents->alive, N) && !(agents->slot && grad_overlap(outs[q], N * 4, agents->slot, N * 4)),
+        DIE_REQUIRE(!die_ranges_overlap(outs[q], N * 4, standing, cells * 8), "%s: a record overlaps the standing plane", who);
+        DIE_REQUIRE(!die_ranges_overlap(outs[q], N * 4, agents->x, N * 4) && !die_ranges_overlap(outs[q], N * 4, agents->y, N * 4) &&
+                    !die_ranges_overlap(outs[q], N * 4, agents->alive, N) && !die_ranges_overlap(outs[q], N * 4, agents->slot, N * 4),
                     "%s: a record overlaps the agent arrays", who);
     }
     if (N == 0) return DIE_OK;                               // no stored entry: nothing to write
@@ -191,8 +186,8 @@ extern "C" int die_memory_planes_backward(int32_t W, int32_t H, int32_t memory_c
     if (rc != DIE_OK) return rc;
     const int64_t cells = (int64_t)W * H, M = memory_channels;
     const int64_t out_bytes = ((M - 1) * row_stride + n_slots) * 4;
-    DIE_REQUIRE(!grad_overlap(grad_memory, out_bytes, win, n_slots * 4), "%s: the memory gradient overlaps the record", who);
-    DIE_REQUIRE(!grad_overlap(grad_memory, out_bytes, grad_planes, ((M - 1) * plane_stride + cells) * 4),
+    DIE_REQUIRE(!die_ranges_overlap(grad_memory, out_bytes, win, n_slots * 4), "%s: the memory gradient overlaps the record", who);
+    DIE_REQUIRE(!die_ranges_overlap(grad_memory, out_bytes, grad_planes, ((M - 1) * plane_stride + cells) * 4),
                 "%s: the memory gradient overlaps the planes' gradient", who);
     if (n_slots == 0) return DIE_OK;                         // no slot: nothing to write
     MemIndexArgs k;
@@ -212,8 +207,8 @@ extern "C" int die_gather_memory_backward(int32_t W, int32_t H, int32_t memory_c
     if (rc != DIE_OK) return rc;
     const int64_t cells = (int64_t)W * H, M = memory_channels;
     const int64_t out_bytes = ((M - 1) * plane_stride + cells) * 4;
-    DIE_REQUIRE(!grad_overlap(grad_planes, out_bytes, cell, n_slots * 4), "%s: the planes' gradient overlaps the record", who);
-    DIE_REQUIRE(!grad_overlap(grad_planes, out_bytes, grad_memory, ((M - 1) * row_stride + n_slots) * 4),
+    DIE_REQUIRE(!die_ranges_overlap(grad_planes, out_bytes, cell, n_slots * 4), "%s: the planes' gradient overlaps the record", who);
+    DIE_REQUIRE(!die_ranges_overlap(grad_planes, out_bytes, grad_memory, ((M - 1) * row_stride + n_slots) * 4),
                 "%s: the planes' gradient overlaps the memory gradient", who);
     for (int j = 0; j < memory_channels; ++j) {              // the cells of every plane; the words between two planes are left alone
         if (hipMemsetAsync(grad_planes + plane_stride * j, 0, (size_t)cells * sizeof(float), (hipStream_t)stream) != hipSuccess) {
@@ -231,16 +226,6 @@ extern "C" int die_gather_memory_backward(int32_t W, int32_t H, int32_t memory_c
 }
 
 // ---- the batched entry points (the replica in blockIdx.y): every argument checked before anything is launched -------------
-static int grad_batch_check(const die_batch* b, const char* who) {
-    DIE_REQUIRE(b->replicas >= 1 && b->replicas <= DIE_MAX_REPLICAS, "%s: 1..%d replicas (got %d)", who, DIE_MAX_REPLICAS, b->replicas);
-    DIE_REQUIRE(b->agent_stride >= 1 && b->agent_stride <= (int64_t)DIE_OWNER_SLOT_MASK - 1, "%s: agent_stride %lld outside 1..%lld", who,
-                (long long)b->agent_stride, (long long)DIE_OWNER_SLOT_MASK - 1);
-    for (int r = 0; r < b->replicas; ++r)
-        DIE_REQUIRE(b->n[r] >= 0 && b->n[r] <= b->agent_stride, "%s: replica %d has %lld agents (0..%lld)", who, r, (long long)b->n[r],
-                    (long long)b->agent_stride);
-    return DIE_OK;
-}
-
 extern "C" int die_memory_cells_batch(const die_medium* m, const die_agents* agents, const die_batch* b, const unsigned long long* standing,
                                       int32_t epoch, int32_t* cell_out, int32_t* win_out, void* stream) {
     const char* who = "die_memory_cells_batch";
@@ -253,7 +238,7 @@ extern "C" int die_memory_cells_batch(const die_medium* m, const die_agents* age
     const int64_t cells = (int64_t)m->W * m->H;
     DIE_REQUIRE(cells <= (int64_t)INT32_MAX, "%s: %dx%d cells do not fit the int32 cell index", who, m->W, m->H);
     DIE_REQUIRE(epoch >= 1 && epoch <= DIE_OWNER_EPOCH_MAX, "%s: epoch %d outside 1..%d", who, epoch, DIE_OWNER_EPOCH_MAX);
-    const int rc = grad_batch_check(b, who);
+    const int rc = die_batch_check(b, -1, who);
     if (rc != DIE_OK) return rc;
     DIE_REQUIRE(b->plane_stride >= cells, "%s: plane_stride %lld smaller than a plane (%lld cells)", who, (long long)b->plane_stride,
                 (long long)cells);
@@ -261,18 +246,18 @@ extern "C" int die_memory_cells_batch(const die_medium* m, const die_agents* age
     DIE_REQUIRE(!agents->slot, "%s: replicas hold their agents in slot order (no slot array)", who);
     const int64_t R = b->replicas, slots = R * b->agent_stride;
     int32_t* const outs[2] = {cell_out, win_out};
-    DIE_REQUIRE(!grad_overlap(cell_out, slots * 4, win_out, slots * 4), "%s: the two records overlap", who);
+    DIE_REQUIRE(!die_ranges_overlap(cell_out, slots * 4, win_out, slots * 4), "%s: the two records overlap", who);
     for (int q = 0; q < 2; ++q) {
-        DIE_REQUIRE(!grad_overlap(outs[q], slots * 4, standing, ((R - 1) * b->plane_stride + cells) * 8), "%s: a record overlaps the standing "
+        DIE_REQUIRE(!die_ranges_overlap(outs[q], slots * 4, standing, ((R - 1) * b->plane_stride + cells) * 8), "%s: a record overlaps the standing "
                     "planes", who);
-        DIE_REQUIRE(!grad_overlap(outs[q], slots * 4, agents->x, slots * 4) && !grad_overlap(outs[q], slots * 4, agents->y, slots * 4) &&
-                    !grad_overlap(outs[q], slots * 4, agents->alive, slots), "%s: a record overlaps the agent arrays", who);
+        DIE_REQUIRE(!die_ranges_overlap(outs[q], slots * 4, agents->x, slots * 4) && !die_ranges_overlap(outs[q], slots * 4, agents->y, slots * 4) &&
+                    !die_ranges_overlap(outs[q], slots * 4, agents->alive, slots), "%s: a record overlaps the agent arrays", who);
     }
     MemCellsBatchArgs k;
     k.x = agents->x; k.y = agents->y; k.slot = nullptr; k.alive = agents->alive;
     k.standing = standing; k.cell = cell_out; k.win = win_out; k.N = 0; k.W = m->W; k.H = m->H; k.epoch = epoch;
     k.rep_plane = b->plane_stride; k.agents = b->agent_stride;
-    for (int r = 0; r < DIE_MAX_REPLICAS; ++r) k.n[r] = r < b->replicas ? b->n[r] : 0;
+    die_replica_counts(k.n, b->n, b->replicas);
     k_memory_cells_batch<<<dim3((unsigned)((b->agent_stride + DIE_BLOCK - 1) / DIE_BLOCK), (unsigned)R), DIE_BLOCK, 0, (hipStream_t)stream>>>(k);
     DIE_CHECK_LAUNCH(who);
     return DIE_OK;
@@ -285,7 +270,7 @@ static int index_batch_check(int32_t W, int32_t H, int32_t M, const die_batch* b
     DIE_REQUIRE(M >= 1 && M <= DIE_MEMORY_MAX_CHANNELS, "%s: %d memory channels outside 1..%d", who, M, DIE_MEMORY_MAX_CHANNELS);
     const int64_t cells = (int64_t)W * H;
     DIE_REQUIRE(cells <= (int64_t)INT32_MAX, "%s: %dx%d cells do not fit the int32 cell index", who, W, H);
-    const int rc = grad_batch_check(b, who);
+    const int rc = die_batch_check(b, -1, who);
     if (rc != DIE_OK) return rc;
     DIE_REQUIRE(row_stride >= b->agent_stride, "%s: row_stride %lld smaller than a row (%lld slots)", who, (long long)row_stride,
                 (long long)b->agent_stride);
@@ -314,8 +299,8 @@ extern "C" int die_memory_planes_backward_batch(int32_t W, int32_t H, int32_t me
     if (rc != DIE_OK) return rc;
     const int64_t cells = (int64_t)W * H, M = memory_channels, R = b->replicas, S = b->agent_stride;
     const int64_t out_bytes = ((R * M - 1) * row_stride + S) * 4;
-    DIE_REQUIRE(!grad_overlap(grad_memory, out_bytes, win, R * S * 4), "%s: the memory gradient overlaps the record", who);
-    DIE_REQUIRE(!grad_overlap(grad_memory, out_bytes, grad_planes, ((R - 1) * replica_stride + (M - 1) * plane_stride + cells) * 4),
+    DIE_REQUIRE(!die_ranges_overlap(grad_memory, out_bytes, win, R * S * 4), "%s: the memory gradient overlaps the record", who);
+    DIE_REQUIRE(!die_ranges_overlap(grad_memory, out_bytes, grad_planes, ((R - 1) * replica_stride + (M - 1) * plane_stride + cells) * 4),
                 "%s: the memory gradient overlaps the planes' gradient", who);
     MemIndexBatchArgs k = index_batch_args(W, H, memory_channels, b, win);
     k.src = (const uint32_t*)grad_planes; k.src_stride = plane_stride; k.rep_src = replica_stride;
@@ -334,8 +319,8 @@ extern "C" int die_gather_memory_backward_batch(int32_t W, int32_t H, int32_t me
     if (rc != DIE_OK) return rc;
     const int64_t cells = (int64_t)W * H, M = memory_channels, R = b->replicas, S = b->agent_stride;
     const int64_t out_bytes = ((R - 1) * replica_stride + (M - 1) * plane_stride + cells) * 4;
-    DIE_REQUIRE(!grad_overlap(grad_planes, out_bytes, cell, R * S * 4), "%s: the planes' gradient overlaps the record", who);
-    DIE_REQUIRE(!grad_overlap(grad_planes, out_bytes, grad_memory, ((R * M - 1) * row_stride + S) * 4),
+    DIE_REQUIRE(!die_ranges_overlap(grad_planes, out_bytes, cell, R * S * 4), "%s: the planes' gradient overlaps the record", who);
+    DIE_REQUIRE(!die_ranges_overlap(grad_planes, out_bytes, grad_memory, ((R * M - 1) * row_stride + S) * 4),
                 "%s: the planes' gradient overlaps the memory gradient", who);
     // the cells of every plane of every replica; the words between two planes and between two replicas are left alone: one
     // strided clear over the replicas where a replica's planes are dense, one per plane otherwise

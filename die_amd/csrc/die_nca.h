@@ -1,5 +1,8 @@
-// What the NeuralAutomataAgent kernels share (die_nca.hip: the forward; die_nca_grad.hip: its adjoint): the workgroup tile, the
-// limits, how a cell beyond the field is read and how a first-layer plane is loaded.
+// What the NeuralAutomataAgent files share.  Device side (die_nca.hip / die_nca_wide.hip: the forward; die_nca_grad.hip /
+// die_nca_wide_grad.hip: its adjoint): the workgroup tile, the limits, how a cell beyond the field is read and how a first-layer plane
+// is loaded.  Host side, each rule stated once: layer 0's input list (die_nca_layer0_planes), the field's planes (die_nca_field_check)
+// and the paddings without an adjoint (die_nca_pad_adjoint_check) in die_nca.hip; what a valid stack is, narrow or wide
+// (die_nca_stack_check), in die_nca_wide.hip; the sizes both directions derive from a stack (tiles, ping-pong sets, widest layer) here.
 #pragma once
 #include "die_common.h"
 
@@ -38,23 +41,42 @@ __device__ __forceinline__ float nca_load(const void* p, int kind, int64_t i, in
 // die_nca_dropout, checked, as the words the kernels read (die_nca.hip)
 int die_dropout_words(const die_nca_dropout* drop, DropWords* out, const char* who);
 
-// a die_nca_batch without the step's scratch (the calls that keep every layer in caller-owned storage), and the die_batch
-// of the batched read-out, sensing and adjoint: checked before anything is launched (die_nca.hip)
-int die_nca_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who);
+// ---- the host-side rules of a stack ----
+// the forward's 16 x 64 tiles over a W x H field: a layer's partial rows, one per tile
+static inline int64_t die_nca_tiles(int32_t W, int32_t H) { return (int64_t)((W + NCA_TX - 1) / NCA_TX) * ((H + NCA_TY - 1) / NCA_TY); }
+// the step's scratch holds set = layer % 2 of the layers' outputs; the adjoint's workspace as many sets of the gradient going down
+static inline int die_nca_pingpong_sets(int32_t n_layers) { return n_layers >= 2 ? 2 : 1; }
+static inline int die_nca_gin_sets(int32_t n_layers) { return n_layers - 1 < 2 ? n_layers - 1 : 2; }
+// the widest cout of a stack: the planes a replica has in a wide stack's scratch, store and workspace
+static inline int die_nca_max_channels(const die_nca_batch* nca) {
+    int mc = 1;
+    for (int l = 0; l < nca->n_layers; ++l) mc = nca->layers[l].cout > mc ? nca->layers[l].cout : mc;
+    return mc;
+}
+// Layer 0's input planes, in THE order: the agents plane if with_agent_channel, food, chem, then the `memory` planes of
+// die_memory.hip (mem_planes null: none; plane j of replica 0 at mem_planes + j * replicas * plane_stride), then the stock plane of
+// die_stock.hip (null: none).  Fills in[] / kind[] (a kernel argument's arrays) and returns the count; *rep_in: replica r's planes lie
+// r * b->plane_stride elements on, every one of them.  The forward and the adjoint of both kinds read their list here.
+int die_nca_layer0_planes(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* mem_planes, int memory,
+                          const unsigned long long* stock, const void* in[], int kind[], int64_t* rep_in);
+// every argument of a stack, before anything is launched, in the order its kind has always checked them (narrow: the scratch's size
+// before the layers; wide: after them).  `scratch`: the step's ping-pong planes are required (the calls that keep every layer in
+// caller-owned storage check their own); `stock`: layer 0 reads the stock plane as its last input; `memory`: layer 0 reads that many
+// planes more and the last layer gives 3 + memory (die_nca_wide.hip, beside the wider kind's limits)
+enum die_nca_kind { DIE_NCA_NARROW = 0, DIE_NCA_WIDE = 1 };     // die_nca.hip's kernels / die_nca_wide.hip's
+int die_nca_stack_check(die_nca_kind kind, const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool scratch,
+                        bool stock = false, int memory = 0);
+// the die_batch of the batched read-out, sensing and adjoint
 int die_nca_batch_shape_check(const die_medium* m, const die_batch* b, const char* who);
-// the same for a wide stack (die_nca_wide.hip: 1..32 channels, k in 1, 3, 5, an activation per layer in die_nca_layer.reserved)
-int die_nca_wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who);
-// … whose layer 0 reads `memory` fp32 planes more and whose last layer gives 3 + memory (the *_memory store / backward pair)
-int die_nca_wide_stack_check_memory(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, int memory);
-// what die_nca_sense_batch_store and die_nca_wide_sense_batch_store check alike, in their order: the arguments, the die_batch, the
-// stack (`wide`: die_nca_wide_stack_check), the field's dtype and planes, sense_epoch (die_nca.hip)
-int die_nca_store_check(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store, bool wide, const char* who);
+// the field a stack senses: its dtype, its planes, sense_epoch
+int die_nca_field_check(const die_medium* m, const die_nca_batch* nca, const char* who);
+// 'reflect' and 'replicate' padding have no adjoint kernel: DIE_ERR_UNSUPPORTED
+int die_nca_pad_adjoint_check(int32_t padding_mode, const char* who);
+// what the *_sense_batch_store calls check alike, in their order: the arguments, the die_batch, the stack, the field
+int die_nca_store_check(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store, die_nca_kind kind, const char* who,
+                        int memory = 0);
 
-// ---- what the batched step (die_env.hip: nca_env_step_batch) calls, in its order ----
-// the stack WITH the step's scratch (die_nca.hip; `stock`: layer 0 reads the stock plane as its last input) …
-int die_nca_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool stock);
-// … and a wide one (die_nca_wide.hip; `memory`: layer 0 reads that many planes more, the last layer gives 3 + memory)
-int die_nca_wide_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool stock, int memory);
+// ---- what the batched step (die_env.hip: nca_env_step_batch) calls after die_nca_stack_check, in its order ----
 // every replica's stock plane at `epoch` (die_stock.hip)
 int die_stock_launch(const die_medium* m, const die_agents* a, int32_t replicas, const int64_t* n, int64_t agent_stride,
                      int64_t plane_stride, int32_t epoch, unsigned long long* planes, void* stream, const char* who);

@@ -18,6 +18,10 @@
 //                     die_nca_env_step_batch_dropout) multiplies the layer's outputs by the cells' dropout mask of die_rng.h in
 //                     the epilogue — one mask per (W, H) plane, shared by the output channels; nothing is stored for it.
 //   k_dropout_mask    the mask planes themselves (die_dropout_mask): 0 or keep per cell, for looking at and for the tests.
+//   Host rules shared with die_nca_wide.hip and the two adjoint files (declared in die_nca.h, each defined once): here layer 0's input
+//                     list (die_nca_layer0_planes), the read-out's die_batch (die_nca_batch_shape_check), the field's planes
+//                     (die_nca_field_check), the paddings without an adjoint (die_nca_pad_adjoint_check) and the store calls' checks
+//                     (die_nca_store_check); the stack's own rules, narrow and wide (die_nca_stack_check): die_nca_wide.hip.
 //
 // Roofline: HBM.  A 3→3 channel 3×3 layer is 81 MAC per cell against 24 bytes per cell (3 planes in, 3 out): 6.75 flop
 // per byte, far below the ≈ 20 flop/byte at which fp32 vector math (157 TFLOP/s) meets 8 TB/s — no MFMA: the matrix
@@ -341,7 +345,7 @@ extern "C" int die_gather_scale_batch(const die_medium* m, const die_agents* ag,
     for (int q = 0; q < 3; ++q) { a.plane[q] = sense + q * cells; a.coef[q] = coefs[q]; }
     a.out[0] = out->dx; a.out[1] = out->dy; a.out[2] = out->deposit;
     a.rep_plane = sense_stride; a.agents = b->agent_stride;
-    for (int r = 0; r < DIE_MAX_REPLICAS; ++r) a.n[r] = r < b->replicas ? b->n[r] : 0;
+    die_replica_counts(a.n, b->n, b->replicas);
     const int64_t g = (b->agent_stride + DIE_BLOCK - 1) / DIE_BLOCK;
     k_gather_scale_batch<<<dim3((unsigned)(g < 8192 ? g : 8192), (unsigned)b->replicas), DIE_BLOCK, 0, (hipStream_t)stream>>>(a);
     DIE_CHECK_LAUNCH(who);
@@ -351,74 +355,40 @@ extern "C" int die_gather_scale_batch(const die_medium* m, const die_agents* ag,
 // ---- die_nca_env_step_batch's sensing (the step itself: die_env.hip) --------------------------------------------------
 // Scratch: [set][replica][NCA_MAXC][W][H] fp32, set = layer % 2 (one set for a single layer); the last layer's planes stay
 // there until the next step (BatchedNeuralAutomataAgent.render).
-static int64_t nca_scratch_sets(int32_t n_layers) { return n_layers >= 2 ? 2 : 1; }
-
 extern "C" int64_t die_nca_batch_scratch_bytes(int32_t W, int32_t H, int32_t replicas, int32_t n_layers) {
     if (W < 1 || H < 1 || replicas < 1 || replicas > DIE_MAX_REPLICAS || n_layers < 1 || n_layers > DIE_NCA_MAX_LAYERS) return -1;
-    return nca_scratch_sets(n_layers) * replicas * NCA_MAXC * (int64_t)W * H * (int64_t)sizeof(float);
+    return (int64_t)die_nca_pingpong_sets(n_layers) * replicas * NCA_MAXC * (int64_t)W * H * (int64_t)sizeof(float);
 }
 
-// every argument of the stack, before anything is launched
-// (scratch: the ping-pong planes of the step; the calls that write into caller-owned storage check their own)
-// (stock: layer 0 reads one plane more, the stock plane of die_stock.hip as its last input)
-static int nca_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool scratch, bool stock = false) {
-    if (scratch) DIE_REQUIRE(nca && nca->layers && nca->scratch, "%s: null stack, layer list or scratch", who);
-    else DIE_REQUIRE(nca && nca->layers, "%s: null stack or layer list", who);
-    DIE_REQUIRE(nca->n_layers >= 1 && nca->n_layers <= DIE_NCA_MAX_LAYERS, "%s: 1..%d layers (got %d)", who, DIE_NCA_MAX_LAYERS, nca->n_layers);
-    DIE_REQUIRE(nca->padding_mode >= DIE_PAD_CIRCULAR && nca->padding_mode <= DIE_PAD_REPLICATE, "%s: bad padding mode %d", who, nca->padding_mode);
-    DIE_REQUIRE(nca->with_agent_channel == 0 || nca->with_agent_channel == 1, "%s: with_agent_channel is 0 or 1", who);
-    DIE_REQUIRE(nca->episodes >= 0 && replicas % (nca->episodes > 1 ? nca->episodes : 1) == 0, "%s: episodes %d: at least 1 (0 reads as 1) "
-                "and a divisor of the %d replicas", who, nca->episodes, replicas);
-    const int64_t need = die_nca_batch_scratch_bytes(W, H, replicas, nca->n_layers);
-    DIE_REQUIRE(need > 0, "%s: bad size %dx%d or replicas %d outside 1..%d", who, W, H, replicas, DIE_MAX_REPLICAS);
-    if (scratch) DIE_REQUIRE(nca->scratch_bytes >= need, "%s: scratch too small (%lld < %lld)", who, (long long)nca->scratch_bytes, (long long)need);
-    int cin = 2 + nca->with_agent_channel + (stock ? 1 : 0);
-    for (int l = 0; l < nca->n_layers; ++l) {
-        const die_nca_layer& L = nca->layers[l];
-        if (!(L.k == 1 || L.k == 3 || L.k == 5 || L.k == 7)) {
-            die_set_error("%s: layer %d: kernel size %d (odd sizes up to %d)", who, l, L.k, NCA_MAXK);
-            return DIE_ERR_ARG;
-        }
-        DIE_REQUIRE(L.cin == cin && L.cout >= 1 && L.cout <= NCA_MAXC, "%s: layer %d: %d -> %d channels (input has %d, at most %d out)", who,
-                    l, L.cin, L.cout, cin, NCA_MAXC);
-        DIE_REQUIRE(L.weights && L.weight_stride >= (int64_t)L.cout * L.cin * L.k * L.k, "%s: layer %d: null weights or stride below a "
-                    "replica's block", who, l);
-        DIE_REQUIRE(nca->padding_mode != DIE_PAD_REFLECT || (L.k / 2 < W && L.k / 2 < H), "%s: layer %d: 'reflect' padding of %d cells "
-                    "needs a field larger than that (%dx%d)", who, l, L.k / 2, W, H);
-        cin = L.cout;
-    }
-    DIE_REQUIRE(cin == 3, "%s: the last layer gives %d planes (dx, dy, deposit: 3)", who, cin);
-    return DIE_OK;
-}
-
-int die_nca_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool stock) {
-    return nca_stack_check(nca, W, H, replicas, who, true, stock);
-}
-int die_nca_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who) {
-    return nca_stack_check(nca, W, H, replicas, who, false);
+int die_nca_layer0_planes(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* mem_planes, int memory,
+                          const unsigned long long* stock, const void* in[], int kind[], int64_t* rep_in) {
+    const int fkind = m->dtype == DIE_F32 ? DIE_PLANE_F32 : DIE_PLANE_F16;
+    int c = 0;
+    if (nca->with_agent_channel) { in[c] = m->owner; kind[c++] = DIE_PLANE_AGENTS; }
+    in[c] = m->food; kind[c++] = fkind;
+    in[c] = m->chem; kind[c++] = fkind;
+    // plane j of replica r at (j * R + r) * plane_stride, as die_memory_planes_batch writes them: one plane_stride a replica
+    for (int j = 0; mem_planes && j < memory; ++j) { in[c] = mem_planes + (int64_t)j * b->replicas * b->plane_stride; kind[c++] = DIE_PLANE_F32; }
+    if (stock) { in[c] = stock; kind[c++] = DIE_PLANE_STOCK; }
+    *rep_in = b->plane_stride;
+    return c;
 }
 
 // the stack for every replica, one launch per layer.  Layer l writes `dst` + set(l) · R · rep planes: set(l) = l % 2 for the
 // step's ping-pong scratch, l for caller-owned storage that keeps every layer.  `drop` (checked words, or null): the last layer's
 // launch is the DROP one — into `masked` when given (the unmasked launch then runs as well and keeps its place), else in place of it.
-// `stock` (or null): the R stock planes of die_stock.hip, b->plane_stride apart, built at sense_epoch — layer 0's last input.
+// `stock` (or null): the R stock planes of die_stock.hip, built at sense_epoch — layer 0's last input (die_nca_layer0_planes).
 static int sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* dst, bool pingpong, float* masked,
                        const float** sense, int64_t* rep, const DropWords* drop, void* stream, const unsigned long long* stock = nullptr) {
     const int64_t cells = (int64_t)m->W * m->H, rep_scratch = NCA_MAXC * cells;
-    const int fkind = m->dtype == DIE_F32 ? DIE_PLANE_F32 : DIE_PLANE_F16;
     ConvArgs a = {};
-    int c = 0;
-    if (nca->with_agent_channel) { a.in[c] = m->owner; a.kind[c++] = DIE_PLANE_AGENTS; }
-    a.in[c] = m->food; a.kind[c++] = fkind;
-    a.in[c] = m->chem; a.kind[c++] = fkind;
-    if (stock) { a.in[c] = stock; a.kind[c++] = DIE_PLANE_STOCK; }
-    a.rep_in = b->plane_stride;
+    die_nca_layer0_planes(m, b, nca, nullptr, 0, stock, a.in, a.kind, &a.rep_in);
     a.W = m->W; a.H = m->H; a.epoch = nca->sense_epoch; a.pad = nca->padding_mode;
     a.episodes = nca->episodes > 1 ? nca->episodes : 1;
     float* out = nullptr;
     for (int l = 0; l < nca->n_layers; ++l) {
         const die_nca_layer& L = nca->layers[l];
-        out = dst + (pingpong ? l % nca_scratch_sets(nca->n_layers) : l) * b->replicas * rep_scratch;
+        out = dst + (pingpong ? l % die_nca_pingpong_sets(nca->n_layers) : l) * b->replicas * rep_scratch;
         for (int o = 0; o < NCA_MAXC; ++o) a.out[o] = o < L.cout ? out + o * cells : nullptr;
         a.w = L.weights; a.rep_w = L.weight_stride; a.rep_out = rep_scratch;
         a.cin = L.cin; a.cout = L.cout; a.k = L.k; a.apply_tanh = l == nca->n_layers - 1;
@@ -444,16 +414,27 @@ int die_nca_sense_batch(const die_medium* m, const die_batch* b, const die_nca_b
     return sense_batch(m, b, nca, nca->scratch, true, nullptr, sense, rep, drop, stream, stock);
 }
 
-int die_nca_store_check(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store, bool wide, const char* who) {
-    DIE_REQUIRE(m && b && nca && store, "%s: null argument", who);
-    int rc = die_nca_batch_shape_check(m, b, who);
-    if (rc != DIE_OK) return rc;
-    rc = (wide ? die_nca_wide_stack_check : die_nca_stack_check)(nca, m->W, m->H, b->replicas, who);
-    if (rc != DIE_OK) return rc;
+int die_nca_field_check(const die_medium* m, const die_nca_batch* nca, const char* who) {
     DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad field dtype %d", who, m->dtype);
     DIE_REQUIRE(m->food && m->chem && (m->owner || !nca->with_agent_channel), "%s: null plane", who);
     DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX, "%s: sense_epoch %d", who, nca->sense_epoch);
     return DIE_OK;
+}
+
+int die_nca_pad_adjoint_check(int32_t padding_mode, const char* who) {
+    if (padding_mode != DIE_PAD_REFLECT && padding_mode != DIE_PAD_REPLICATE) return DIE_OK;
+    die_set_error("%s: the adjoint of 'reflect' / 'replicate' padding is not implemented ('circular' and 'zeros' are)", who);
+    return DIE_ERR_UNSUPPORTED;
+}
+
+int die_nca_store_check(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store, die_nca_kind kind, const char* who,
+                        int memory) {
+    DIE_REQUIRE(m && b && nca && store, "%s: null argument", who);
+    int rc = die_nca_batch_shape_check(m, b, who);
+    if (rc != DIE_OK) return rc;
+    rc = die_nca_stack_check(kind, nca, m->W, m->H, b->replicas, who, false, false, memory);
+    if (rc != DIE_OK) return rc;
+    return die_nca_field_check(m, nca, who);
 }
 
 extern "C" int64_t die_nca_sense_batch_store_bytes(int32_t W, int32_t H, int32_t replicas, int32_t n_layers) {
@@ -464,7 +445,7 @@ extern "C" int64_t die_nca_sense_batch_store_bytes(int32_t W, int32_t H, int32_t
 extern "C" int die_nca_sense_batch_store(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* store, int64_t store_bytes,
                                          float* masked, const die_nca_dropout* drop, void* stream) {
     const char* who = "die_nca_sense_batch_store";
-    int rc = die_nca_store_check(m, b, nca, store, false, who);
+    int rc = die_nca_store_check(m, b, nca, store, DIE_NCA_NARROW, who);
     if (rc != DIE_OK) return rc;
     const int64_t need = die_nca_sense_batch_store_bytes(m->W, m->H, b->replicas, nca->n_layers);
     DIE_REQUIRE(store_bytes >= need, "%s: store too small (%lld < %lld)", who, (long long)store_bytes, (long long)need);

@@ -216,11 +216,10 @@ void die_conv_backward_fold_batch(const float* part, int64_t rows, int nw, int c
 static bool conv_shape_ok(int32_t W, int32_t H, int32_t cin, int32_t cout, int32_t k) {
     return W >= 1 && H >= 1 && cin >= 1 && cin <= NCA_MAXC && cout >= 1 && cout <= NCA_MAXC && (k == 1 || k == 3 || k == 5 || k == 7);
 }
-static int64_t conv_tiles(int32_t W, int32_t H) { return (int64_t)((W + NCA_TX - 1) / NCA_TX) * ((H + NCA_TY - 1) / NCA_TY); }
 
 extern "C" int64_t die_conv2d_backward_workspace_bytes(int32_t W, int32_t H, int32_t cin, int32_t cout, int32_t k) {
     if (!conv_shape_ok(W, H, cin, cout, k)) return -1;
-    return conv_tiles(W, H) * cout * cin * k * k * (int64_t)sizeof(float);
+    return die_nca_tiles(W, H) * cout * cin * k * k * (int64_t)sizeof(float);
 }
 
 extern "C" int die_conv2d_backward(int32_t W, int32_t H, int32_t cin, const die_conv_plane* in, int32_t epoch, int32_t cout,
@@ -229,10 +228,7 @@ extern "C" int die_conv2d_backward(int32_t W, int32_t H, int32_t cin, const die_
                                    int32_t padding_mode, void* workspace, int64_t workspace_bytes, void* stream) {
     const char* who = "die_conv2d_backward";
     DIE_REQUIRE(padding_mode >= DIE_PAD_CIRCULAR && padding_mode <= DIE_PAD_REPLICATE, "%s: bad padding mode %d", who, padding_mode);
-    if (padding_mode == DIE_PAD_REFLECT || padding_mode == DIE_PAD_REPLICATE) {
-        die_set_error("%s: the adjoint of 'reflect' / 'replicate' padding is not implemented ('circular' and 'zeros' are)", who);
-        return DIE_ERR_UNSUPPORTED;
-    }
+    if (die_nca_pad_adjoint_check(padding_mode, who) != DIE_OK) return DIE_ERR_UNSUPPORTED;
     DIE_REQUIRE(W >= 1 && H >= 1, "%s: bad size %dx%d", who, W, H);
     DIE_REQUIRE(cin >= 1 && cin <= NCA_MAXC && cout >= 1 && cout <= NCA_MAXC, "%s: 1..%d channels (got %d -> %d)", who, NCA_MAXC, cin, cout);
     if (!(k == 1 || k == 3 || k == 5 || k == 7)) {
@@ -290,7 +286,7 @@ extern "C" int die_conv2d_backward(int32_t W, int32_t H, int32_t cin, const die_
         default: k_conv_backward<7><<<grid, DIE_BLOCK, lds, s>>>(a); break;
     }
     DIE_CHECK_LAUNCH(who);
-    k_conv_backward_sum<<<die_grid_for(nw), DIE_BLOCK, 0, s>>>(a.part, conv_tiles(W, H), nw, grad_weights);
+    k_conv_backward_sum<<<die_grid_for(nw), DIE_BLOCK, 0, s>>>(a.part, die_nca_tiles(W, H), nw, grad_weights);
     DIE_CHECK_LAUNCH("die_conv2d_backward(sum)");
     return DIE_OK;
 }
@@ -379,11 +375,8 @@ extern "C" int die_gather_scale_backward_batch(const die_medium* m, const die_ag
     a.grad[0] = grad_action->dx; a.grad[1] = grad_action->dy; a.grad[2] = grad_action->deposit;
     for (int q = 0; q < 3; ++q) { a.plane[q] = grad_sense + q * cells; a.coef[q] = coefs[q]; }
     a.rep_plane = sense_stride; a.agents = b->agent_stride;
-    int64_t nmax = 1;
-    for (int r = 0; r < DIE_MAX_REPLICAS; ++r) {
-        a.n[r] = r < b->replicas ? b->n[r] : 0;
-        if (a.n[r] > nmax) nmax = a.n[r];
-    }
+    int64_t nmax = die_replica_counts(a.n, b->n, b->replicas);
+    if (nmax < 1) nmax = 1;
     // the 3 · R planes (and what lies between two replicas' planes where sense_stride leaves a gap)
     const size_t span = (size_t)((int64_t)(b->replicas - 1) * sense_stride + 3 * cells) * sizeof(float);
     if (hipMemsetAsync(grad_sense, 0, span, (hipStream_t)stream) != hipSuccess) {
@@ -400,14 +393,13 @@ extern "C" int die_gather_scale_backward_batch(const die_medium* m, const die_ag
 // Workspace: [replica][tile][4 · 4 · 7 · 7] partial rows at most (a layer uses [replica][tile][cout · cin · k · k] of it), then
 // min(layers − 1, 2) sets of [replica][4][W][H] planes for the gradient travelling down the stack (ping-pong).
 static int64_t nca_backward_part_floats(int32_t W, int32_t H, int32_t replicas) {
-    return (int64_t)replicas * conv_tiles(W, H) * NCA_MAXC * NCA_MAXC * NCA_MAXK * NCA_MAXK;
+    return (int64_t)replicas * die_nca_tiles(W, H) * NCA_MAXC * NCA_MAXC * NCA_MAXK * NCA_MAXK;
 }
-static int nca_backward_gin_sets(int32_t n_layers) { return n_layers - 1 < 2 ? n_layers - 1 : 2; }
 
 extern "C" int64_t die_nca_backward_batch_workspace_bytes(int32_t W, int32_t H, int32_t replicas, int32_t n_layers) {
     if (W < 1 || H < 1 || replicas < 1 || replicas > DIE_MAX_REPLICAS || n_layers < 1 || n_layers > DIE_NCA_MAX_LAYERS) return -1;
     if ((W + NCA_TX - 1) / NCA_TX > 65535) return -1;
-    return (nca_backward_part_floats(W, H, replicas) + (int64_t)nca_backward_gin_sets(n_layers) * replicas * NCA_MAXC * (int64_t)W * H) *
+    return (nca_backward_part_floats(W, H, replicas) + (int64_t)die_nca_gin_sets(n_layers) * replicas * NCA_MAXC * (int64_t)W * H) *
            (int64_t)sizeof(float);
 }
 
@@ -420,15 +412,10 @@ static int nca_backward_batch(const die_medium* m, const die_batch* b, const die
     DIE_REQUIRE(m && b && nca && store && grad_sense && grad && workspace, "%s: null argument", who);
     int rc = die_nca_batch_shape_check(m, b, who);
     if (rc != DIE_OK) return rc;
-    rc = die_nca_stack_check(nca, m->W, m->H, b->replicas, who);
+    rc = die_nca_stack_check(DIE_NCA_NARROW, nca, m->W, m->H, b->replicas, who, false);
+    if (rc == DIE_OK) rc = die_nca_pad_adjoint_check(nca->padding_mode, who);
+    if (rc == DIE_OK) rc = die_nca_field_check(m, nca, who);
     if (rc != DIE_OK) return rc;
-    if (nca->padding_mode == DIE_PAD_REFLECT || nca->padding_mode == DIE_PAD_REPLICATE) {
-        die_set_error("%s: the adjoint of 'reflect' / 'replicate' padding is not implemented ('circular' and 'zeros' are)", who);
-        return DIE_ERR_UNSUPPORTED;
-    }
-    DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad field dtype %d", who, m->dtype);
-    DIE_REQUIRE(m->food && m->chem && (m->owner || !nca->with_agent_channel), "%s: null plane", who);
-    DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX, "%s: sense_epoch %d", who, nca->sense_epoch);
     const int64_t cells = (int64_t)m->W * m->H, rep_planes = NCA_MAXC * cells;
     DIE_REQUIRE(sense_stride >= 3 * cells, "%s: sense_stride %lld below three planes", who, (long long)sense_stride);
     int64_t P = 0;
@@ -463,10 +450,9 @@ static int nca_backward_batch(const die_medium* m, const die_batch* b, const die
         if (rc != DIE_OK) return rc;
     }
     const int E = nca->episodes > 1 ? nca->episodes : 1, R = b->replicas, L = nca->n_layers;
-    const int64_t tiles = conv_tiles(m->W, m->H);
+    const int64_t tiles = die_nca_tiles(m->W, m->H);
     float* part = (float*)workspace;
     float* gin_sets = part + nca_backward_part_floats(m->W, m->H, R);
-    const int fkind = m->dtype == DIE_F32 ? DIE_PLANE_F32 : DIE_PLANE_F16;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((m->H + NCA_TY - 1) / NCA_TY, (m->W + NCA_TX - 1) / NCA_TX, R);
     int64_t off = P;
@@ -478,11 +464,7 @@ static int nca_backward_batch(const die_medium* m, const die_batch* b, const die
         off -= nw;
         ConvBwdBatchArgs a = {};
         if (l == 0) {
-            int c = 0;
-            if (nca->with_agent_channel) { a.in[c] = m->owner; a.kind[c++] = DIE_PLANE_AGENTS; }
-            a.in[c] = m->food; a.kind[c++] = fkind;
-            a.in[c] = m->chem; a.kind[c++] = fkind;
-            a.rep_in = b->plane_stride;
+            die_nca_layer0_planes(m, b, nca, nullptr, 0, nullptr, a.in, a.kind, &a.rep_in);
         } else {
             for (int c = 0; c < Ly.cin; ++c) { a.in[c] = store + (int64_t)(l - 1) * R * rep_planes + c * cells; a.kind[c] = DIE_PLANE_F32; }
             a.rep_in = rep_planes;

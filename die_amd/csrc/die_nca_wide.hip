@@ -1,7 +1,9 @@
 // NeuralAutomataAgent sensing for wide stacks (gfx950): ConvolutionModel(hidden_channels=C, hidden_activation=...), layers of up
 // to 32 channels in and out, kernel sizes 1, 3 and 5, an activation after every layer (none / tanh / relu; the last layer's tanh
 // and its dropout mask as in die_nca.hip).  The narrow kernels of die_nca.hip stay what they are; a stack with either argument
-// set takes these entry points for every layer, also where it would fit the narrow ones.
+// set takes these entry points for every layer, also where it would fit the narrow ones.  What a valid stack is — narrow or wide, one
+// walk over two sets of limits — is checked here (die_nca_stack_check); layer 0's input list, the field check and the store calls'
+// checks are die_nca.hip's, the sizes derived from a stack die_nca.h's.
 //
 //   k_conv_wide<K, NB>  one layer as an implicit GEMM on v_mfma_f32_16x16x4_f32 (__builtin_amdgcn_mfma_f32_16x16x4f32):
 //                       M = 16 consecutive y of one row x, N = 16 output channels (NB = 1 or 2 blocks of them, the weights of
@@ -254,29 +256,18 @@ extern "C" int die_conv2d_wide(int32_t W, int32_t H, int32_t cin, const die_conv
     return DIE_OK;
 }
 
-// ---- die_nca_wide_env_step_batch's sensing (the step itself: die_env.hip) ---------------------------------------------
-// Scratch: [set][replica][max_channels][W][H] fp32, set = layer % 2 (one set for a single layer), max_channels the widest
-// cout of the stack; the last layer's three planes stay there until the next step (BatchedNeuralAutomataAgent.render).
-static int64_t wide_sets(int32_t n_layers) { return n_layers >= 2 ? 2 : 1; }
+// ---- what a valid stack is, narrow (die_nca.hip's kernels) or wide: one walk, and the two kinds' limits -------------------------
+struct NcaLimits {
+    int max_channels, max_k;     // cout in 1..max_channels, k odd in 1..max_k
+    const char* k_text;          // … as the refusal names them (a format: %d is max_k)
+    bool activation;             // die_nca_layer.reserved is the layer's die_nca_activation (the last layer's: tanh)
+};
+static const NcaLimits nca_limits[2] = {{NCA_MAXC, NCA_MAXK, "odd sizes up to %d", false}, {NCAW_MAXC, 5, "1, 3 or 5", true}};
 
-extern "C" int64_t die_nca_wide_batch_scratch_bytes(int32_t W, int32_t H, int32_t replicas, int32_t n_layers, int32_t max_channels) {
-    if (W < 1 || H < 1 || replicas < 1 || replicas > DIE_MAX_REPLICAS || n_layers < 1 || n_layers > DIE_NCA_MAX_LAYERS ||
-        max_channels < 1 || max_channels > NCAW_MAXC) return -1;
-    return wide_sets(n_layers) * replicas * max_channels * (int64_t)W * H * (int64_t)sizeof(float);
-}
-
-static int wide_max_channels(const die_nca_batch* nca) {
-    int mc = 1;
-    for (int l = 0; l < nca->n_layers; ++l) mc = nca->layers[l].cout > mc ? nca->layers[l].cout : mc;
-    return mc;
-}
-
-// every argument of the stack, before anything is launched
-// (scratch: the ping-pong planes of the step; the calls that keep every layer in caller-owned storage check their own)
-// (stock: layer 0 reads one plane more, the stock plane of die_stock.hip as its last input)
-// (memory: layer 0 reads `memory` fp32 planes more, between the field's and the stock's, and the last layer gives 3 + memory)
-static int wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool scratch, bool stock = false,
-                            int memory = 0) {
+int die_nca_stack_check(die_nca_kind kind, const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool scratch,
+                        bool stock, int memory) {
+    const bool wide = kind == DIE_NCA_WIDE;
+    const NcaLimits& lim = nca_limits[kind];
     if (scratch) DIE_REQUIRE(nca && nca->layers && nca->scratch, "%s: null stack, layer list or scratch", who);
     else DIE_REQUIRE(nca && nca->layers, "%s: null stack or layer list", who);
     DIE_REQUIRE(nca->n_layers >= 1 && nca->n_layers <= DIE_NCA_MAX_LAYERS, "%s: 1..%d layers (got %d)", who, DIE_NCA_MAX_LAYERS, nca->n_layers);
@@ -286,15 +277,27 @@ static int wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int3
                 "and a divisor of the %d replicas", who, nca->episodes, replicas);
     DIE_REQUIRE(W >= 1 && H >= 1 && replicas >= 1 && replicas <= DIE_MAX_REPLICAS, "%s: bad size %dx%d or replicas %d outside 1..%d", who,
                 W, H, replicas, DIE_MAX_REPLICAS);
-    DIE_REQUIRE((W + NCA_TX - 1) / NCA_TX <= 65535, "%s: field too tall", who);
+    // the ping-pong planes: NCA_MAXC a replica for a narrow stack, asked for before its layers; the widest cout for a wide one, after
+    auto scratch_check = [&](int channels) -> int {
+        const int64_t need = (int64_t)die_nca_pingpong_sets(nca->n_layers) * replicas * channels * (int64_t)W * H * (int64_t)sizeof(float);
+        DIE_REQUIRE(nca->scratch_bytes >= need, "%s: scratch too small (%lld < %lld)", who, (long long)nca->scratch_bytes, (long long)need);
+        return DIE_OK;
+    };
+    if (wide) DIE_REQUIRE((W + NCA_TX - 1) / NCA_TX <= 65535, "%s: field too tall", who);
+    else if (scratch && scratch_check(NCA_MAXC) != DIE_OK) return DIE_ERR_ARG;
     int cin = 2 + nca->with_agent_channel + memory + (stock ? 1 : 0);
     for (int l = 0; l < nca->n_layers; ++l) {
         const die_nca_layer& L = nca->layers[l];
-        const bool last = l == nca->n_layers - 1;
-        DIE_REQUIRE(L.k == 1 || L.k == 3 || L.k == 5, "%s: layer %d: kernel size %d (1, 3 or 5)", who, l, L.k);
-        DIE_REQUIRE(L.cin == cin && L.cout >= 1 && L.cout <= NCAW_MAXC, "%s: layer %d: %d -> %d channels (input has %d, at most %d out)", who,
-                    l, L.cin, L.cout, cin, NCAW_MAXC);
-        DIE_REQUIRE(L.reserved >= DIE_NCA_ACT_NONE && L.reserved <= DIE_NCA_ACT_RELU && (!last || L.reserved == DIE_NCA_ACT_TANH),
+        if (!(L.k >= 1 && L.k <= lim.max_k && (L.k & 1))) {
+            char sizes[32];
+            snprintf(sizes, sizeof(sizes), lim.k_text, lim.max_k);
+            die_set_error("%s: layer %d: kernel size %d (%s)", who, l, L.k, sizes);
+            return DIE_ERR_ARG;
+        }
+        DIE_REQUIRE(L.cin == cin && L.cout >= 1 && L.cout <= lim.max_channels, "%s: layer %d: %d -> %d channels (input has %d, at most %d out)",
+                    who, l, L.cin, L.cout, cin, lim.max_channels);
+        DIE_REQUIRE(!lim.activation || (L.reserved >= DIE_NCA_ACT_NONE && L.reserved <= DIE_NCA_ACT_RELU &&
+                                        (l < nca->n_layers - 1 || L.reserved == DIE_NCA_ACT_TANH)),
                     "%s: layer %d: activation %d (0 none, 1 tanh, 2 relu; the last layer's is tanh)", who, l, L.reserved);
         DIE_REQUIRE(L.weights && L.weight_stride >= (int64_t)L.cout * L.cin * L.k * L.k, "%s: layer %d: null weights or stride below a "
                     "replica's block", who, l);
@@ -305,17 +308,16 @@ static int wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int3
     if (memory) DIE_REQUIRE(cin == 3 + memory, "%s: the last layer gives %d planes (dx, dy, deposit and %d memory planes: %d)", who, cin,
                             memory, 3 + memory);
     else DIE_REQUIRE(cin == 3, "%s: the last layer gives %d planes (dx, dy, deposit: 3)", who, cin);
-    if (!scratch) return DIE_OK;
-    const int64_t need = die_nca_wide_batch_scratch_bytes(W, H, replicas, nca->n_layers, wide_max_channels(nca));
-    DIE_REQUIRE(nca->scratch_bytes >= need, "%s: scratch too small (%lld < %lld)", who, (long long)nca->scratch_bytes, (long long)need);
-    return DIE_OK;
+    return wide && scratch ? scratch_check(die_nca_max_channels(nca)) : DIE_OK;
 }
 
-int die_nca_wide_batch_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool stock, int memory) {
-    return wide_stack_check(nca, W, H, replicas, who, true, stock, memory);
-}
-int die_nca_wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who) {
-    return wide_stack_check(nca, W, H, replicas, who, false);
+// ---- die_nca_wide_env_step_batch's sensing (the step itself: die_env.hip) ---------------------------------------------
+// Scratch: [set][replica][max_channels][W][H] fp32, set = layer % 2 (one set for a single layer), max_channels the widest
+// cout of the stack; the last layer's three planes stay there until the next step (BatchedNeuralAutomataAgent.render).
+extern "C" int64_t die_nca_wide_batch_scratch_bytes(int32_t W, int32_t H, int32_t replicas, int32_t n_layers, int32_t max_channels) {
+    if (W < 1 || H < 1 || replicas < 1 || replicas > DIE_MAX_REPLICAS || n_layers < 1 || n_layers > DIE_NCA_MAX_LAYERS ||
+        max_channels < 1 || max_channels > NCAW_MAXC) return -1;
+    return (int64_t)die_nca_pingpong_sets(n_layers) * replicas * max_channels * (int64_t)W * H * (int64_t)sizeof(float);
 }
 
 // the stack for every replica, one launch per layer.  Layer l writes `dst` + set(l) * R * rep planes: set(l) = l % 2 for the
@@ -323,30 +325,21 @@ int die_nca_wide_stack_check(const die_nca_batch* nca, int32_t W, int32_t H, int
 // launch is the masked one — into `masked` when given (the unmasked launch then runs as well and keeps its place), else in place
 // of it.  *sense = the last layer's planes of replica 0, replica r's *rep further (what die_nca_sense_batch returns for a narrow
 // stack: k_nca_move_claim_batch reads either)
-// `stock` (or null): the R stock planes of die_stock.hip, b->plane_stride apart, built at sense_epoch — layer 0's last input
-// `mem_planes` (or null): the R * `memory` fp32 planes of die_memory.hip, plane j of replica r at (j * R + r) * b->plane_stride —
-// layer 0's inputs after the field's planes and before the stock's
+// `stock`, `mem_planes` with `memory` (or null / 0): the stock planes built at sense_epoch and the memory planes, layer 0's inputs
+// after the field's (die_nca.h die_nca_layer0_planes: the one list of them)
 static int wide_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* dst, bool pingpong, float* masked,
                             const float** sense, int64_t* rep, const DropWords* drop, void* stream, const unsigned long long* stock = nullptr,
                             const float* mem_planes = nullptr, int memory = 0) {
-    const int64_t cells = (int64_t)m->W * m->H, rep_scratch = wide_max_channels(nca) * cells;
-    const int fkind = m->dtype == DIE_F32 ? DIE_PLANE_F32 : DIE_PLANE_F16;
+    const int64_t cells = (int64_t)m->W * m->H, rep_scratch = die_nca_max_channels(nca) * cells;
     WideArgs a = {};
-    int c = 0;
-    if (nca->with_agent_channel) { a.in[c] = m->owner; a.kind[c++] = DIE_PLANE_AGENTS; }
-    a.in[c] = m->food; a.kind[c++] = fkind;
-    a.in[c] = m->chem; a.kind[c++] = fkind;
-    if (mem_planes)
-        for (int j = 0; j < memory; ++j) { a.in[c] = mem_planes + (int64_t)j * b->replicas * b->plane_stride; a.kind[c++] = DIE_PLANE_F32; }
-    if (stock) { a.in[c] = stock; a.kind[c++] = DIE_PLANE_STOCK; }
-    a.rep_in = b->plane_stride;
+    die_nca_layer0_planes(m, b, nca, mem_planes, memory, stock, a.in, a.kind, &a.rep_in);
     a.W = m->W; a.H = m->H; a.epoch = nca->sense_epoch; a.pad = nca->padding_mode;
     a.episodes = nca->episodes > 1 ? nca->episodes : 1;
     a.out_stride = cells; a.rep_out = rep_scratch;
     for (int l = 0; l < nca->n_layers; ++l) {
         const die_nca_layer& L = nca->layers[l];
         const bool last = l == nca->n_layers - 1;
-        a.out = dst + (pingpong ? l % wide_sets(nca->n_layers) : l) * b->replicas * rep_scratch;
+        a.out = dst + (pingpong ? l % die_nca_pingpong_sets(nca->n_layers) : l) * b->replicas * rep_scratch;
         a.w = L.weights; a.rep_w = L.weight_stride;
         a.cin = L.cin; a.cout = L.cout; a.act = L.reserved;
         a.vec = wide_vec(a.out, a.out_stride, a.rep_out, a.H);
@@ -384,9 +377,9 @@ extern "C" int64_t die_nca_wide_sense_batch_store_bytes(int32_t W, int32_t H, in
 extern "C" int die_nca_wide_sense_batch_store(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* store,
                                               int64_t store_bytes, float* masked, const die_nca_dropout* drop, void* stream) {
     const char* who = "die_nca_wide_sense_batch_store";
-    int rc = die_nca_store_check(m, b, nca, store, true, who);
+    int rc = die_nca_store_check(m, b, nca, store, DIE_NCA_WIDE, who);
     if (rc != DIE_OK) return rc;
-    const int64_t need = die_nca_wide_sense_batch_store_bytes(m->W, m->H, b->replicas, nca->n_layers, wide_max_channels(nca));
+    const int64_t need = die_nca_wide_sense_batch_store_bytes(m->W, m->H, b->replicas, nca->n_layers, die_nca_max_channels(nca));
     DIE_REQUIRE(store_bytes >= need, "%s: store too small (%lld < %lld)", who, (long long)store_bytes, (long long)need);
     DropWords dw;
     if (drop) {
@@ -400,10 +393,6 @@ extern "C" int die_nca_wide_sense_batch_store(const die_medium* m, const die_bat
 }
 
 // ---- the same for a population whose agents carry memory (the forward of die_nca_wide_backward_batch_memory) --------------
-int die_nca_wide_stack_check_memory(const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, int memory) {
-    return wide_stack_check(nca, W, H, replicas, who, false, false, memory);
-}
-
 // Layer 0 reads ([agents,] food, chem, memory_0 .. memory_{M-1}), the last layer gives 3 + M planes; the tanh and the mask fall
 // on all of them (k_conv_wide's epilogue knows no plane from another).  The launches are die_nca_wide_sense_batch_store's.
 // Roofline: k_conv_wide's, above — the M planes are M more fp32 planes in and out of the first and the last layer (HBM-bound
@@ -416,14 +405,9 @@ extern "C" int die_nca_wide_sense_batch_store_memory(const die_medium* m, const 
     DIE_REQUIRE(m && b && nca && store && mem_planes, "%s: null argument", who);
     DIE_REQUIRE(memory_channels >= 1 && memory_channels <= DIE_MEMORY_MAX_CHANNELS, "%s: %d memory channels outside 1..%d", who,
                 memory_channels, DIE_MEMORY_MAX_CHANNELS);
-    int rc = die_nca_batch_shape_check(m, b, who);
+    int rc = die_nca_store_check(m, b, nca, store, DIE_NCA_WIDE, who, memory_channels);
     if (rc != DIE_OK) return rc;
-    rc = wide_stack_check(nca, m->W, m->H, b->replicas, who, false, false, memory_channels);
-    if (rc != DIE_OK) return rc;
-    DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad field dtype %d", who, m->dtype);
-    DIE_REQUIRE(m->food && m->chem && (m->owner || !nca->with_agent_channel), "%s: null plane", who);
-    DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX, "%s: sense_epoch %d", who, nca->sense_epoch);
-    const int64_t need = die_nca_wide_sense_batch_store_bytes(m->W, m->H, b->replicas, nca->n_layers, wide_max_channels(nca));
+    const int64_t need = die_nca_wide_sense_batch_store_bytes(m->W, m->H, b->replicas, nca->n_layers, die_nca_max_channels(nca));
     DIE_REQUIRE(store_bytes >= need, "%s: store too small (%lld < %lld)", who, (long long)store_bytes, (long long)need);
     DropWords dw;
     if (drop) {
@@ -433,9 +417,9 @@ extern "C" int die_nca_wide_sense_batch_store_memory(const die_medium* m, const 
     }
     // the memory planes are read by layer 0 while the store (and the masked planes) are written
     const int64_t cells = (int64_t)m->W * m->H;
-    const char *p0 = (const char*)mem_planes, *p1 = p0 + (((int64_t)memory_channels * b->replicas - 1) * b->plane_stride + cells) * 4;
-    auto overlaps = [&](const void* q, int64_t bytes) { return q && (const char*)q < p1 && (const char*)q + bytes > p0; };
-    DIE_REQUIRE(!overlaps(store, need) && !(drop && overlaps(masked, (int64_t)b->replicas * wide_max_channels(nca) * cells * 4)),
+    const int64_t mem_bytes = (((int64_t)memory_channels * b->replicas - 1) * b->plane_stride + cells) * 4;
+    auto overlaps = [&](const void* q, int64_t bytes) { return die_ranges_overlap(mem_planes, mem_bytes, q, bytes); };
+    DIE_REQUIRE(!overlaps(store, need) && !(drop && overlaps(masked, (int64_t)b->replicas * die_nca_max_channels(nca) * cells * 4)),
                 "%s: the memory planes overlap the store or the masked planes", who);
     const float* sense;
     int64_t rep;

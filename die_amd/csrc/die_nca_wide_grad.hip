@@ -405,11 +405,10 @@ static bool wide_shape_ok(int32_t W, int32_t H, int32_t cin, int32_t cout, int32
     return W >= 1 && H >= 1 && (W + NCA_TX - 1) / NCA_TX <= 65535 && cin >= 1 && cin <= NCAW_MAXC && cout >= 1 && cout <= NCAW_MAXC &&
            (k == 1 || k == 3 || k == 5);
 }
-static int64_t wide_tiles(int32_t W, int32_t H) { return (int64_t)((W + NCA_TX - 1) / NCA_TX) * ((H + NCA_TY - 1) / NCA_TY); }
 
 extern "C" int64_t die_conv2d_wide_backward_workspace_bytes(int32_t W, int32_t H, int32_t cin, int32_t cout, int32_t k) {
     if (!wide_shape_ok(W, H, cin, cout, k)) return -1;
-    return wide_tiles(W, H) * cout * cin * k * k * (int64_t)sizeof(float);
+    return die_nca_tiles(W, H) * cout * cin * k * k * (int64_t)sizeof(float);
 }
 
 extern "C" int die_conv2d_wide_backward(int32_t W, int32_t H, int32_t cin, const die_conv_plane* in, int32_t epoch, int32_t cout,
@@ -419,10 +418,7 @@ extern "C" int die_conv2d_wide_backward(int32_t W, int32_t H, int32_t cin, const
                                         void* workspace, int64_t workspace_bytes, void* stream) {
     const char* who = "die_conv2d_wide_backward";
     DIE_REQUIRE(padding_mode >= DIE_PAD_CIRCULAR && padding_mode <= DIE_PAD_REPLICATE, "%s: bad padding mode %d", who, padding_mode);
-    if (padding_mode == DIE_PAD_REFLECT || padding_mode == DIE_PAD_REPLICATE) {
-        die_set_error("%s: the adjoint of 'reflect' / 'replicate' padding is not implemented ('circular' and 'zeros' are)", who);
-        return DIE_ERR_UNSUPPORTED;
-    }
+    if (die_nca_pad_adjoint_check(padding_mode, who) != DIE_OK) return DIE_ERR_UNSUPPORTED;
     DIE_REQUIRE(W >= 1 && H >= 1, "%s: bad size %dx%d", who, W, H);
     DIE_REQUIRE((W + NCA_TX - 1) / NCA_TX <= 65535, "%s: field too tall", who);
     DIE_REQUIRE(cin >= 1 && cin <= NCAW_MAXC && cout >= 1 && cout <= NCAW_MAXC, "%s: 1..%d channels (got %d -> %d)", who, NCAW_MAXC, cin, cout);
@@ -442,9 +438,8 @@ extern "C" int die_conv2d_wide_backward(int32_t W, int32_t H, int32_t cin, const
     const int64_t need = die_conv2d_wide_backward_workspace_bytes(W, H, cin, cout, k);
     DIE_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%lld < %lld)", who, (long long)workspace_bytes, (long long)need);
     WideBwdArgs a = {};
-    const char* lo = (const char*)grad_in;
-    const char* hi = grad_in ? lo + ((int64_t)(cin - 1) * grad_in_stride + cells) * (int64_t)sizeof(float) : lo;
-    auto overlaps = [&](const void* p, int64_t bytes) { return grad_in && p && (const char*)p < hi && (const char*)p + bytes > lo; };
+    const int64_t gin_bytes = ((int64_t)(cin - 1) * grad_in_stride + cells) * (int64_t)sizeof(float);
+    auto overlaps = [&](const void* p, int64_t bytes) { return die_ranges_overlap(grad_in, gin_bytes, p, bytes); };
     for (int c = 0; c < cin; ++c) {
         DIE_REQUIRE(in[c].data && in[c].kind >= DIE_PLANE_F32 && in[c].kind <= DIE_PLANE_AGENTS, "%s: bad input plane %d", who, c);
         const int64_t bytes = cells * (in[c].kind == DIE_PLANE_F32 ? 4 : in[c].kind == DIE_PLANE_F16 ? 2 : 8);
@@ -474,7 +469,7 @@ extern "C" int die_conv2d_wide_backward(int32_t W, int32_t H, int32_t cin, const
         default: launch_wide_backward<5, false>(a, grad_in != nullptr, 1, s); break;
     }
     DIE_CHECK_LAUNCH(who);
-    die_conv_backward_fold((const float*)workspace, wide_tiles(W, H), (int)nw, grad_weights, s);
+    die_conv_backward_fold((const float*)workspace, die_nca_tiles(W, H), (int)nw, grad_weights, s);
     DIE_CHECK_LAUNCH("die_conv2d_wide_backward(sum)");
     return DIE_OK;
 }
@@ -483,11 +478,6 @@ extern "C" int die_conv2d_wide_backward(int32_t W, int32_t H, int32_t cin, const
 // Workspace: min(layers - 1, 2) sets of [replica][Cmax][W][H] planes for the gradient travelling down the stack (ping-pong), Cmax
 // the widest cout: the store's plane count — first, so that their 16-byte stores stay aligned whatever the rows' length — then
 // [replica][tile][the largest cout * cin * k * k of the stack] partial rows (a layer uses [replica][tile][its own nw] of it).
-static int wide_bwd_max_channels(const die_nca_batch* nca) {
-    int mc = 1;
-    for (int l = 0; l < nca->n_layers; ++l) mc = nca->layers[l].cout > mc ? nca->layers[l].cout : mc;
-    return mc;
-}
 static int64_t wide_bwd_max_weights(const die_nca_batch* nca) {
     int64_t mw = 0;
     for (int l = 0; l < nca->n_layers; ++l) {
@@ -497,7 +487,6 @@ static int64_t wide_bwd_max_weights(const die_nca_batch* nca) {
     }
     return mw;
 }
-static int wide_bwd_gin_sets(int32_t n_layers) { return n_layers - 1 < 2 ? n_layers - 1 : 2; }
 
 // the shapes the byte query answers for (the call itself checks everything again, with messages)
 // (memory: layer 0 reads that many planes more, the last layer gives 3 + memory)
@@ -520,8 +509,8 @@ static bool wide_bwd_stack_ok(int32_t W, int32_t H, int32_t replicas, const die_
 
 static int64_t wide_bwd_workspace_bytes(int32_t W, int32_t H, int32_t replicas, const die_nca_batch* nca, int memory) {
     if (!wide_bwd_stack_ok(W, H, replicas, nca, memory)) return -1;
-    return ((int64_t)replicas * wide_tiles(W, H) * wide_bwd_max_weights(nca) +
-            (int64_t)wide_bwd_gin_sets(nca->n_layers) * replicas * wide_bwd_max_channels(nca) * (int64_t)W * H) * (int64_t)sizeof(float);
+    return ((int64_t)replicas * die_nca_tiles(W, H) * wide_bwd_max_weights(nca) +
+            (int64_t)die_nca_gin_sets(nca->n_layers) * replicas * die_nca_max_channels(nca) * (int64_t)W * H) * (int64_t)sizeof(float);
 }
 
 extern "C" int64_t die_nca_wide_backward_batch_workspace_bytes(int32_t W, int32_t H, int32_t replicas, const die_nca_batch* nca) {
@@ -541,17 +530,11 @@ static int wide_backward_batch(const char* who, const die_medium* m, const die_b
                                int64_t grad_in_stride, const float* mem_planes, int memory, void* stream) {
     int rc = die_nca_batch_shape_check(m, b, who);
     if (rc != DIE_OK) return rc;
-    rc = memory ? die_nca_wide_stack_check_memory(nca, m->W, m->H, b->replicas, who, memory)
-                : die_nca_wide_stack_check(nca, m->W, m->H, b->replicas, who);
+    rc = die_nca_stack_check(DIE_NCA_WIDE, nca, m->W, m->H, b->replicas, who, false, false, memory);
+    if (rc == DIE_OK) rc = die_nca_pad_adjoint_check(nca->padding_mode, who);
+    if (rc == DIE_OK) rc = die_nca_field_check(m, nca, who);
     if (rc != DIE_OK) return rc;
-    if (nca->padding_mode == DIE_PAD_REFLECT || nca->padding_mode == DIE_PAD_REPLICATE) {
-        die_set_error("%s: the adjoint of 'reflect' / 'replicate' padding is not implemented ('circular' and 'zeros' are)", who);
-        return DIE_ERR_UNSUPPORTED;
-    }
-    DIE_REQUIRE(m->dtype == DIE_F32 || m->dtype == DIE_F16, "%s: bad field dtype %d", who, m->dtype);
-    DIE_REQUIRE(m->food && m->chem && (m->owner || !nca->with_agent_channel), "%s: null plane", who);
-    DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX, "%s: sense_epoch %d", who, nca->sense_epoch);
-    const int Cmax = wide_bwd_max_channels(nca);
+    const int Cmax = die_nca_max_channels(nca);
     const int64_t cells = (int64_t)m->W * m->H, rep_planes = Cmax * cells;
     const int n_sense = 3 + memory;                          // planes per replica at the top of the stack
     if (memory) DIE_REQUIRE(sense_stride >= n_sense * cells, "%s: sense_stride %lld below %d planes", who, (long long)sense_stride, n_sense);
@@ -576,9 +559,8 @@ static int wide_backward_batch(const char* who, const die_medium* m, const die_b
         // the kernel stores four cells of a row at once where H % 4 == 0
         DIE_REQUIRE(m->H % 4 != 0 || (((uintptr_t)grad_in & 15) == 0 && grad_in_stride % 4 == 0),
                     "%s: grad_in must be 16-byte aligned and grad_in_stride a multiple of 4 where H %% 4 == 0", who);
-        const char* lo = (const char*)grad_in;
-        const char* hi = lo + ((int64_t)(R - 1) * grad_in_stride + in_planes) * (int64_t)sizeof(float);
-        auto overlaps = [&](const void* p, int64_t bytes) { return p && (const char*)p < hi && (const char*)p + bytes > lo; };
+        const int64_t gin_bytes = ((int64_t)(R - 1) * grad_in_stride + in_planes) * (int64_t)sizeof(float);
+        auto overlaps = [&](const void* p, int64_t bytes) { return die_ranges_overlap(grad_in, gin_bytes, p, bytes); };
         const int64_t fbytes = ((int64_t)(R - 1) * b->plane_stride + cells) * (m->dtype == DIE_F32 ? 4 : 2);
         DIE_REQUIRE(!overlaps(store, (int64_t)L * R * rep_planes * 4) && !overlaps(grad_sense, ((int64_t)(R - 1) * sense_stride + n_sense * cells) * 4) &&
                         !overlaps(grad, ((int64_t)(R / E - 1) * grad_stride + P) * 4) && !overlaps(workspace, need) &&
@@ -597,10 +579,9 @@ static int wide_backward_batch(const char* who, const die_medium* m, const die_b
         rc = die_dropout_words(drop, &dw, who);
         if (rc != DIE_OK) return rc;
     }
-    const int64_t tiles = wide_tiles(m->W, m->H);
+    const int64_t tiles = die_nca_tiles(m->W, m->H);
     float* gin_sets = (float*)workspace;
-    float* part = gin_sets + (int64_t)wide_bwd_gin_sets(L) * R * rep_planes;
-    const int fkind = m->dtype == DIE_F32 ? DIE_PLANE_F32 : DIE_PLANE_F16;
+    float* part = gin_sets + (int64_t)die_nca_gin_sets(L) * R * rep_planes;
     hipStream_t s = (hipStream_t)stream;
     int64_t off = P;
     const float* g = grad_sense;
@@ -611,13 +592,7 @@ static int wide_backward_batch(const char* who, const die_medium* m, const die_b
         off -= nw;
         WideBwdBatchArgs a = {};
         if (l == 0) {
-            int c = 0;
-            if (nca->with_agent_channel) { a.in[c] = m->owner; a.kind[c++] = DIE_PLANE_AGENTS; }
-            a.in[c] = m->food; a.kind[c++] = fkind;
-            a.in[c] = m->chem; a.kind[c++] = fkind;
-            // plane j of replica r at (j * R + r) * plane_stride, as die_memory_planes_batch writes them: one plane_stride a replica
-            for (int j = 0; j < memory; ++j) { a.in[c] = mem_planes + (int64_t)j * R * b->plane_stride; a.kind[c++] = DIE_PLANE_F32; }
-            a.rep_in = b->plane_stride;
+            die_nca_layer0_planes(m, b, nca, mem_planes, memory, nullptr, a.in, a.kind, &a.rep_in);
         } else {
             for (int c = 0; c < Ly.cin; ++c) { a.in[c] = store + (int64_t)(l - 1) * R * rep_planes + c * cells; a.kind[c] = DIE_PLANE_F32; }
             a.rep_in = rep_planes;

@@ -50,11 +50,7 @@ int die_stock_launch(const die_medium* m, const die_agents* a, int32_t replicas,
     k.x = a->x; k.y = a->y; k.slot = a->slot; k.alive = a->alive; k.agent_food = a->agent_food;
     k.plane = planes; k.W = m->W; k.H = m->H; k.epoch = epoch;
     k.agent_stride = agent_stride; k.plane_stride = plane_stride;
-    int64_t nmax = 0;
-    for (int r = 0; r < DIE_MAX_REPLICAS; ++r) {
-        k.n[r] = r < replicas ? n[r] : 0;
-        if (k.n[r] > nmax) nmax = k.n[r];
-    }
+    const int64_t nmax = die_replica_counts(k.n, n, replicas);
     if (nmax == 0) return DIE_OK;                        // no slot anywhere: the planes stay as they are
     const int64_t g = (nmax + DIE_BLOCK - 1) / DIE_BLOCK;
     k_stock_plane<<<dim3((unsigned)(g < 8192 ? g : 8192), (unsigned)replicas), DIE_BLOCK, 0, (hipStream_t)stream>>>(k);
@@ -87,15 +83,9 @@ extern "C" int die_stock_plane_batch(const die_medium* m, const die_agents* agen
                                      unsigned long long* planes, void* stream) {
     const char* who = "die_stock_plane_batch";
     DIE_REQUIRE(b, "%s: null argument", who);
-    const int rc = stock_check(m, agents, epoch, planes, who);
+    int rc = stock_check(m, agents, epoch, planes, who);
     if (rc != DIE_OK) return rc;
-    DIE_REQUIRE(b->replicas >= 1 && b->replicas <= DIE_MAX_REPLICAS, "%s: 1..%d replicas (got %d)", who, DIE_MAX_REPLICAS, b->replicas);
-    DIE_REQUIRE(b->plane_stride >= (int64_t)m->W * m->H, "%s: plane_stride %lld smaller than a plane (%lld cells)", who,
-                (long long)b->plane_stride, (long long)m->W * m->H);
-    DIE_REQUIRE(b->agent_stride >= 1 && b->agent_stride <= (int64_t)DIE_OWNER_SLOT_MASK - 1, "%s: agent_stride %lld outside 1..%lld", who,
-                (long long)b->agent_stride, (long long)DIE_OWNER_SLOT_MASK - 1);
-    for (int r = 0; r < b->replicas; ++r)
-        DIE_REQUIRE(b->n[r] >= 0 && b->n[r] <= b->agent_stride, "%s: replica %d has %lld agents (0..%lld)", who, r, (long long)b->n[r],
-                    (long long)b->agent_stride);
+    rc = die_batch_check(b, (int64_t)m->W * m->H, who);
+    if (rc != DIE_OK) return rc;
     return die_stock_launch(m, agents, b->replicas, b->n, b->agent_stride, b->plane_stride, epoch, planes, stream, who);
 }
