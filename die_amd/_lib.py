@@ -125,6 +125,7 @@ NCA_MAX_LAYERS = 8
 NCA_WIDE_MAX_CHANNELS = 32           # die_conv2d_wide / die_nca_wide_env_step_batch: channels in or out of a layer
 NCA_WIDE_KERNEL_SIZES = (1, 3, 5)
 MEMORY_MAX_CHANNELS = 8              # DIE_MEMORY_MAX_CHANNELS: NeuralAutomataAgent(memory_channels=M)
+SIGNAL_MAX_CHANNELS = 8              # DIE_SIGNAL_MAX_CHANNELS: NeuralAutomataAgent(signal_channels=K)
 NCA_ACTIVATIONS = {None: 0, 'tanh': 1, 'relu': 2}     # ConvolutionModel(hidden_activation=...) → die_nca_activation
 
 
@@ -260,6 +261,14 @@ _SIGNATURES = {
     'die_nca_wide_env_step_batch_memory': (C.c_int, [_P(Medium), _P(Agents), _P(NcaBatch), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
                                                      C.c_void_p, C.c_int64, _P(NcaDropout), C.c_void_p, _P(DynamicsRow), C.c_void_p,
                                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    'die_signal_step': (C.c_int, [_P(Medium), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                  C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    'die_signal_step_batch': (C.c_int, [_P(Medium), _P(Batch), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                        C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    'die_nca_wide_env_step_batch_signal': (C.c_int, [_P(Medium), _P(Agents), _P(NcaBatch), _P(Action), _P(Dynamics), _P(Batch), C.c_void_p,
+                                                     C.c_void_p, C.c_int64, _P(NcaDropout), C.c_void_p, _P(DynamicsRow), C.c_void_p,
+                                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                     C.c_float, C.c_float, C.c_float, C.c_void_p]),
     'die_memory_cells': (C.c_int, [_P(Medium), _P(Agents), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'die_memory_planes_backward': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                              C.c_int64, C.c_void_p]),

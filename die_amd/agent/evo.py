@@ -30,6 +30,35 @@ def _omit_defaults(params: Dict[str, Any], *names: str) -> None:
             del params[name]
 
 
+_SIGNAL_ARGUMENTS = ('signal_channels', 'signal_deposit', 'signal_sigma', 'signal_decay')
+SIGNAL_MAX_RADIUS = 8                                      # die_signal_step takes die_diffuse_decay's radii
+
+
+def signal_radius(sigma: float) -> int:
+    """The gaussian's radius as the library computes it from the float32 sigma (scipy's int(truncate * sigma + .5), truncate 4)."""
+    return int(4.0 * float(np.float32(sigma)) + 0.5)
+
+
+def _signal_arguments(channels, deposit, sigma, decay):
+    """NeuralAutomataAgent's four signal arguments, checked: (K, (deposit, sigma, decay)) or the ValueError that says which is wrong."""
+    if channels is None:
+        channels = 0
+    if isinstance(channels, (bool, np.bool_)) or not isinstance(channels, (int, float, np.integer, np.floating)) or \
+            int(channels) != channels or not 0 <= channels <= _lib.SIGNAL_MAX_CHANNELS:
+        raise ValueError(f'signal_channels={channels!r}: an integer in 1..{_lib.SIGNAL_MAX_CHANNELS}, or 0 / None for none')
+    try:
+        deposit, sigma, decay = float(deposit), float(sigma), float(decay)
+    except (TypeError, ValueError):
+        raise ValueError(f'signal_deposit={deposit!r}, signal_sigma={sigma!r}, signal_decay={decay!r}: three numbers') from None
+    if not np.isfinite(deposit):
+        raise ValueError(f'signal_deposit={deposit!r}: a finite number')
+    if not (np.isfinite(sigma) and sigma > 0 and 1 <= signal_radius(sigma) <= SIGNAL_MAX_RADIUS):
+        raise ValueError(f'signal_sigma={sigma!r}: its radius int(4 sigma + .5) must lie in 1..{SIGNAL_MAX_RADIUS}')
+    if not 0.0 <= decay <= 1.0:
+        raise ValueError(f'signal_decay={decay!r}: a number in [0, 1]')
+    return int(channels), (deposit, sigma, decay)
+
+
 def _layer_arrays(li: int, w: th.Tensor, planes, dst: th.Tensor):
     """What a narrow layer launch takes beside its weights `w`: the input `planes` [(tensor, DIE_PLANE_* kind)] as a die_conv_plane
     array and the first cout planes of `dst` as a pointer array — or the ValueError of a weight that does not fit the planes."""
@@ -80,7 +109,11 @@ class ConvolutionModel(nn.Module):
     `memory_channels=M` > 0 (NeuralAutomataAgent(memory_channels=M), which also counts the M planes into `num_obs_channels` and
     `num_act_channels`): the stack is a wide stack whatever the two arguments above say — a single layer obs -> actions included
     — and `forward_device` refuses it: the planes alone do not say whose memory they hold, its gradients come from
-    `NeuralAutomataAgent.recurrent_action`.  Kept out of `init_params` while 0."""
+    `NeuralAutomataAgent.recurrent_action`.  Kept out of `init_params` while 0.
+
+    `signal_channels=K` > 0 (NeuralAutomataAgent(signal_channels=K), which counts the K planes into `num_obs_channels` and
+    `num_act_channels` as well): a wide stack too, whatever else is set, and `forward_device` refuses it — the field's update has no
+    adjoint.  Kept out of `init_params` while 0."""
 
     def __init__(self,
                  num_obs_channels: int = 3,
@@ -92,9 +125,10 @@ class ConvolutionModel(nn.Module):
                  hidden_channels: Optional[int] = None,
                  hidden_activation: Optional[str] = None,
                  memory_channels: int = 0,
+                 signal_channels: int = 0,
                  ):
         self._init_params = save_args(self.__init__, locals())
-        _omit_defaults(self._init_params, 'hidden_channels', 'hidden_activation', 'memory_channels')
+        _omit_defaults(self._init_params, 'hidden_channels', 'hidden_activation', 'memory_channels', 'signal_channels')
         if hidden_channels is not None:
             if isinstance(hidden_channels, bool) or int(hidden_channels) != hidden_channels or \
                     not 1 <= hidden_channels <= _lib.NCA_WIDE_MAX_CHANNELS:
@@ -104,17 +138,18 @@ class ConvolutionModel(nn.Module):
             hidden_channels = int(hidden_channels)
         if hidden_activation not in _lib.NCA_ACTIVATIONS:
             raise ValueError(f"hidden_activation={hidden_activation!r}: 'tanh', 'relu' or None")
-        if hidden_channels is not None or hidden_activation is not None or memory_channels:
+        if hidden_channels is not None or hidden_activation is not None or memory_channels or signal_channels:
             for size in kernel_sizes:
                 if size not in _lib.NCA_WIDE_KERNEL_SIZES:
                     raise NotImplementedError(f'kernel size {size} in a wide stack (hidden_channels / hidden_activation / '
                                               f'memory_channels): one of {_lib.NCA_WIDE_KERNEL_SIZES} (32 * 32 * 49 weights do not fit '
                                               'LDS next to a tile)')
-        if memory_channels and max(num_obs_channels, num_act_channels) > _lib.NCA_WIDE_MAX_CHANNELS:
+        if (memory_channels or signal_channels) and max(num_obs_channels, num_act_channels) > _lib.NCA_WIDE_MAX_CHANNELS:
             raise ValueError(f'{num_obs_channels} -> {num_act_channels} channels: at most {_lib.NCA_WIDE_MAX_CHANNELS} a layer')
         super().__init__()
         self.hidden_channels, self.hidden_activation = hidden_channels, hidden_activation
         self.memory_channels = int(memory_channels)
+        self.signal_channels = int(signal_channels)
         depth = len(kernel_sizes)
         width = num_obs_channels if hidden_channels is None else hidden_channels
         stack = nn.Sequential()
@@ -131,9 +166,9 @@ class ConvolutionModel(nn.Module):
 
     @property
     def wide(self) -> bool:
-        """A stack with `hidden_channels`, `hidden_activation` or `memory_channels` set: every layer goes through the wide entry
-        points."""
-        return self.hidden_channels is not None or self.hidden_activation is not None or self.memory_channels > 0
+        """A stack with `hidden_channels`, `hidden_activation`, `memory_channels` or `signal_channels` set: every layer goes through the
+        wide entry points."""
+        return self.hidden_channels is not None or self.hidden_activation is not None or self.memory_channels > 0 or self.signal_channels > 0
 
     def conv_layers(self):
         return [layer for layer in self.kernels if isinstance(layer, nn.Conv2d)]
@@ -157,6 +192,9 @@ class ConvolutionModel(nn.Module):
         bit for bit what `NeuralAutomataAgent.sense` returns on a medium holding those planes: the same launches.  Boundaries
         'circular' and 'zeros' where a gradient is needed.  A narrow model (neither `hidden_channels` nor `hidden_activation`)
         raises ValueError: it has `NeuralAutomataAgent.differentiable_sense`."""
+        if self.signal_channels:
+            raise NotImplementedError(f'forward_device: no gradients through signal channels (signal_channels={self.signal_channels}): '
+                                      'the field\'s update has no adjoint')
         if self.memory_channels:
             raise NotImplementedError('forward_device: no gradients through memory channels (memory_channels > 0): the read-out into '
                                       'the memory and the expand onto the field have no adjoint')
@@ -231,7 +269,29 @@ class NeuralAutomataAgent(TorchAgent):
         `Dynamics(agents_born=True)` is refused together with memory too (a slot can die and be refilled within one step, so a
         newborn would inherit a dead agent's memory) — but a stand-alone agent cannot see the Dynamics, so that refusal sits
         where the Dynamics is known: the `BatchedNeuralAutomataAgent` constructor.  With a stand-alone `Env` it is the caller's.
-    Kept out of `init_params` while 0, saved and restored by `load` while positive (the memory itself is state, not saved)."""
+    Kept out of `init_params` while 0, saved and restored by `load` while positive (the memory itself is state, not saved).
+
+    `signal_channels=K`, 1 <= K <= 8, with `signal_deposit`, `signal_sigma`, `signal_decay` (no reference counterpart; core/__init__.py
+    of the reference: "abstracted actionable channels: let the medium have channels rgbc, and enable the Agent to sense 'rgb' and to
+    act on 'g' and 'c'"; 0 / None: absent, nothing changes): the agents write and read a field of K planes that stays where it was
+    written, diffuses and decays — memory's public counterpart.
+      * A wide stack, as with memory.  The observation channels are `[agents]`, `env_food`, `chem1`, `signal_0` .. `signal_{K-1}`,
+        `memory_0` .. `memory_{M-1}`, `[agent_food]`; the last layer has 3 + K + M output channels: rows 0..2 dx, dy, deposit, rows
+        3 .. 3 + K - 1 the emissions, then the memory rows.  Tanh and the dropout mask fall on every plane (a masked cell emits 0).
+      * `signals`: the (K, W, H) float32 device tensor, whatever the field's dtype; None until the first `sense` / `forward`, which
+        allocates it as zeros for the medium's (W, H, device).  `reset_signals()` zeroes it and lets the next forward take another
+        shape; until then a forward on a medium of another shape raises ValueError before any launch.
+      * One `forward(obs)`: the stack reads F_k as plain fp32 planes; actions and the memory read-out as ever; then die_signal_step:
+        `E_k[c] = occupied(c) ? signal_deposit * S[3 + k][c] : +0` on the standing plane's cells (alive slots only — the stock and
+        memory build, one for all three; agents sharing a cell emit once; emissions may be negative, so agents can erase) and
+        `F_k <- (1 - signal_decay) * gaussian(F_k + E_k, signal_sigma, mode='wrap', truncate=4)` in fp32, into a second buffer that
+        is then swapped.  `sense()` alone leaves the field untouched: its clock is the agent's forward count, as memory's is.
+        Signalling is free of action cost.
+      * Refused with NotImplementedError before any launch, and before `dropout_step`, `memory` or `signals` change: every
+        differentiable call (`differentiable_sense`, `differentiable_action`, `model.forward_device`, `recurrent_action`) and a
+        decomposed medium.  `signal_sigma` must give a radius int(4 sigma + .5) in 1..8, `signal_decay` lie in [0, 1],
+        `signal_deposit` be finite: ValueError in the constructor.
+    All four are kept out of `init_params` while K is 0, saved and restored by `load` while positive (the field is state, not saved)."""
 
     def __init__(self,
                  scale: float = 0.1,
@@ -241,10 +301,24 @@ class NeuralAutomataAgent(TorchAgent):
                  dropout_seed: Optional[int] = None,
                  with_stock_channel: bool = False,
                  memory_channels: Optional[int] = 0,
+                 signal_channels: Optional[int] = 0,
+                 signal_deposit: float = 1.0,
+                 signal_sigma: float = 0.5,
+                 signal_decay: float = 0.1,
                  **model_kwargs,
                  ):
         self._init_params = save_args(self.__init__, locals())
         self._init_params.pop('initial_obs', None)            # an observation is not a constructor parameter worth saving
+        self.signal_channels, self.signal_constants = _signal_arguments(signal_channels, signal_deposit, signal_sigma, signal_decay)
+        self.signals: Optional[th.Tensor] = None               # (K, W, H) float32, from the first forward on
+        self._signals_next: Optional[th.Tensor] = None         # the second buffer the update writes, swapped in afterwards
+        self._signals_rebind = True                            # the next forward may allocate for its own medium
+        self._standing: Optional[th.Tensor] = None             # the standing plane of the last sense with agents
+        for name, value in zip(_SIGNAL_ARGUMENTS, (self.signal_channels, *self.signal_constants)):
+            if self.signal_channels:                           # (saved as the checked values; all four kept out while K is 0)
+                self._init_params[name] = value
+            else:
+                self._init_params.pop(name, None)
         if memory_channels is None:
             memory_channels = 0
         if isinstance(memory_channels, (bool, np.bool_)) or not isinstance(memory_channels, (int, float, np.integer, np.floating)) or \
@@ -265,14 +339,18 @@ class NeuralAutomataAgent(TorchAgent):
         self.dropout_seed = dropout_seed
         self.dropout_step = 0
         self.obs_channels = list(DataChannels.medium) if with_agent_channel else list(DataChannels.medium[1:])
-        self.obs_channels += [f'memory_{j}' for j in range(self.memory_channels)]      # after the field's planes, before the stock's
+        self.obs_channels += [f'signal_{k}' for k in range(self.signal_channels)]      # after the field's planes, before the memory's
+        self.obs_channels += [f'memory_{j}' for j in range(self.memory_channels)]      # … which come before the stock's
         if self.with_stock_channel:
             self.obs_channels.append(DataChannels.agents[3])   # 'agent_food': always the LAST observation channel
         self._stock = {}                                       # (W, H, device) -> [uint64 stock plane, epoch of its last build]
         if self.memory_channels:                               # (a model without memory is built exactly as before)
             model_kwargs = dict(model_kwargs, memory_channels=self.memory_channels)
+        if self.signal_channels:                               # (nor does a model without signals say anything about them)
+            model_kwargs = dict(model_kwargs, signal_channels=self.signal_channels)
         self._model = ConvolutionModel(num_obs_channels=len(self.obs_channels),
-                                       num_act_channels=len(DataChannels.actions) + self.memory_channels, **model_kwargs)
+                                       num_act_channels=len(DataChannels.actions) + self.signal_channels + self.memory_channels,
+                                       **model_kwargs)
         self.action_coefs = (float(scale), float(scale), float(deposit))
         self._sense_output: Optional[th.Tensor] = None         # (3, W, H) on the device after the first forward
         self._planes = {}                                      # device scratch by (W, H, device): ping-pong plane sets
@@ -353,9 +431,48 @@ class NeuralAutomataAgent(TorchAgent):
             raise NotImplementedError(f'memory_channels={self.memory_channels} on a decomposed medium (die_amd/dist.py): the standing '
                                       'plane is built for periodic single-tile planes only')
 
+    def _check_signals(self, what: str = None, medium=None):
+        """The signal channels' refusals, before any launch: (`what`) a differentiable call, (`medium`) a decomposed world, or a
+        medium of another shape or device than the field was allocated for (ValueError, until `reset_signals()`)."""
+        K = self.signal_channels
+        if not K:
+            return
+        if what is not None:
+            raise NotImplementedError(f'{what}: no gradients through signal channels (signal_channels={K}): the field\'s update has '
+                                      'no adjoint')
+        if medium is None:
+            return
+        if getattr(medium, 'world', None) is not None:
+            raise NotImplementedError(f'signal_channels={K} on a decomposed medium (die_amd/dist.py): the signal field is kept for '
+                                      'periodic single-tile planes only')
+        sig = self.signals
+        if sig is not None and not self._signals_rebind and (tuple(sig.shape) != (K, medium.W, medium.H) or sig.device != medium.device):
+            raise ValueError(f'signals holds a {tuple(sig.shape[1:])} field on {sig.device}, the medium is {(medium.W, medium.H)} on '
+                             f'{medium.device}: call reset_signals() to start blank on it')
+
+    def reset_signals(self) -> None:
+        """A blank field: zero it where it is, and let the next forward allocate anew if its medium has another shape."""
+        if self.signals is not None:
+            self.signals.zero_()
+        self._signals_rebind = True
+
+    def _signals_for(self, medium) -> th.Tensor:
+        """`signals` for this medium: allocated as zeros at the first forward (and at the first after `reset_signals()` on a
+        medium of another shape), with the second buffer the update writes."""
+        shape = (self.signal_channels, medium.W, medium.H)
+        sig = self.signals
+        if sig is None or tuple(sig.shape) != shape or sig.device != medium.device:
+            sig = self.signals = th.zeros(shape, dtype=th.float32, device=medium.device)
+        nxt = self._signals_next
+        if nxt is None or tuple(nxt.shape) != shape or nxt.device != medium.device:
+            self._signals_next = th.empty(shape, dtype=th.float32, device=medium.device)
+        self._signals_rebind = False
+        return sig
+
     def _check_differentiable(self, what: str, wide_ok: bool = False):
-        """What no differentiable call takes — memory channels, a wide stack (unless `wide_ok`: the wide twin,
+        """What no differentiable call takes — signal channels, memory channels, a wide stack (unless `wide_ok`: the wide twin,
         BatchedNeuralAutomataAgent.forward_device), the stock channel — refused in that order, before any launch."""
+        self._check_signals(what)
         self._check_memory(what)
         if not wide_ok:
             self._check_wide(what)
@@ -448,10 +565,14 @@ class NeuralAutomataAgent(TorchAgent):
         """ConvolutionModel.forward over the medium on the device → (3, W, H) float32 tensor.  `agents`: the DeviceAgents whose
         stocks the `'agent_food'` channel shows — required with `with_stock_channel=True` (ValueError before any launch), unused
         otherwise.  With `memory_channels=M` the agents are required as well, and the tensor holds all 3 + M planes of the last
-        layer (planes 3.. are what `forward` reads out into `memory`)."""
+        layer (planes 3.. are what `forward` reads out into `memory`).  With `signal_channels=K` the stack reads `signals` (allocated
+        here as zeros at the first call) and the tensor holds 3 + K + M planes: 3 .. 3 + K - 1 the emissions, then the memory's.
+        The field itself is left as it is — only `forward` advances it — and the agents, where given, get their standing plane
+        built for it."""
         self._check_wide()
         self._check_stock(medium=medium)
         self._check_memory(medium=medium)
+        self._check_signals(medium=medium)
         if self.with_stock_channel and agents is None:
             raise ValueError("sense(medium, agents): with_stock_channel=True needs the agents whose stocks the 'agent_food' channel shows")
         if self.memory_channels:
@@ -462,9 +583,15 @@ class NeuralAutomataAgent(TorchAgent):
         sp = stream_ptr(dev)
         wide = self._model.wide
         src = self._field_planes(medium)
-        standing = self._stock_plane(medium, agents) if self.with_stock_channel or self.memory_channels else None
+        # ONE build serves the stock channel, memory and signals (a bare `sense(medium)` of a signal agent needs none: it emits nothing)
+        needs_standing = self.with_stock_channel or self.memory_channels or (self.signal_channels and agents is not None)
+        standing = self._standing = self._stock_plane(medium, agents) if needs_standing else None
         if self.with_stock_channel:
             src['agent_food'] = (standing, _lib.DIE_PLANE_STOCK)
+        if self.signal_channels:                                 # the field as it is now, plain fp32 planes whatever the medium's dtype
+            field = self._signals_for(medium)
+            for k in range(self.signal_channels):
+                src[f'signal_{k}'] = (field[k], _lib.DIE_PLANE_F32)
         if self.memory_channels:                                 # the one standing plane serves both: here its payload is ignored
             expanded = self._expand_memory(medium, agents, standing)
             for j in range(self.memory_channels):
@@ -499,7 +626,7 @@ class NeuralAutomataAgent(TorchAgent):
         """:150-174."""
         agents, medium = obs
         sense = self.sense(medium, agents)
-        self._sense_output = sense[:3]                           # (with memory channels the planes 3.. follow: not rendered)
+        self._sense_output = sense[:3]                           # (with signal or memory channels the planes 3.. follow: not rendered)
         action = DeviceAction(agents.N, agents.device, agents.slot, capacity=agents.capacity)
         action.global_slots = agents.global_slots
         planes = (C.c_void_p * 3)(*[sense[c].data_ptr() for c in range(3)])
@@ -507,10 +634,16 @@ class NeuralAutomataAgent(TorchAgent):
         m, a, u = medium.c_struct(need_owner=False), agents.c_struct(), action.c_struct()
         _lib.check(_lib.lib.die_gather_scale(C.byref(m), C.byref(a), planes, coefs, C.byref(u), stream_ptr(agents.device)),
                    'die_gather_scale')
-        if self.memory_channels:                                 # planes 3.. at the agents' cells, before anything moves
-            W, H = medium.W, medium.H
-            _lib.check(_lib.lib.die_gather_memory(C.byref(m), C.byref(a), self.memory_channels, sense[3].data_ptr(), W * H,
+        K, (W, H) = self.signal_channels, (medium.W, medium.H)
+        if self.memory_channels:                                 # planes 3 + K .. at the agents' cells, before anything moves
+            _lib.check(_lib.lib.die_gather_memory(C.byref(m), C.byref(a), self.memory_channels, sense[3 + K].data_ptr(), W * H,
                                                   _ptr(self.memory), max(agents.N, 1), stream_ptr(agents.device)), 'die_gather_memory')
+        if K:                                                    # planes 3 .. 3 + K - 1 at the standing plane's cells: the field's next state
+            deposit, sigma, decay = self.signal_constants
+            _lib.check(_lib.lib.die_signal_step(C.byref(m), _ptr(self._standing), medium.epoch, K, sense[3].data_ptr(), W * H, _ptr(self.signals),
+                                                _ptr(self._signals_next), W * H, deposit, sigma, decay, stream_ptr(agents.device)),
+                       'die_signal_step')
+            self.signals, self._signals_next = self._signals_next, self.signals
         action._keepalive = sense
         return action
 
@@ -591,6 +724,7 @@ class NeuralAutomataAgent(TorchAgent):
         decomposed medium, fp16 fields and the boundaries 'reflect' / 'replicate'; with ValueError a `memory` of the wrong shape,
         dtype or device."""
         from ..functional import gather_memory, gather_scale, memory_planes, memory_record
+        self._check_signals('recurrent_action')
         M = self.memory_channels
         if not M:
             raise ValueError('recurrent_action: an agent without memory channels (memory_channels=0) is differentiated by '

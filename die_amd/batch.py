@@ -345,8 +345,8 @@ class BatchedEnv:
              results: Optional[torch.Tensor] = None, action: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One step of every replica: `agent.forward` + `Env.step` fused, two launches for the whole batch (L + 2 for a
         BatchedNeuralAutomataAgent of L layers, L + 3 when it senses the agents' stocks: the build of the R stock planes this
-        BatchedEnv owns, L + 5 when its agents carry memory channels: that build, the expand and the memory read-out; one more
-        with dead slots, one more with a flow; for a BatchedPhysarumPopulation a
+        BatchedEnv owns, L + 5 when its agents carry memory channels: that build, the expand and the memory read-out, L + 4
+        with signal channels: that build and the field's update, L + 6 with both; one more with dead slots, one more with a flow; for a BatchedPhysarumPopulation a
         decode launch first when `parameters` was written since the last one).  Returns the (R, 2) float64 tensor of
         die_step_result words (device; `read_results` decodes).
 
@@ -1031,7 +1031,8 @@ def _architecture(agent: NeuralAutomataAgent) -> dict:
     return dict(kernel_sizes=tuple(int(k.kernel_size[0]) for k in layers), boundary=tuple(k.padding_mode for k in layers),
                 with_agent_channel='agents' in agent.obs_channels, with_stock_channel=agent.with_stock_channel, scale=agent.action_coefs[0], deposit=agent.action_coefs[2],
                 shapes=tuple(tuple(k.weight.shape) for k in layers), hidden_channels=agent.model.hidden_channels,
-                hidden_activation=agent.model.hidden_activation, memory_channels=agent.memory_channels)
+                hidden_activation=agent.model.hidden_activation, memory_channels=agent.memory_channels,
+                signal_channels=agent.signal_channels, signal_constants=agent.signal_constants if agent.signal_channels else None)
 
 
 class BatchedNeuralAutomataAgent(_Population):
@@ -1084,7 +1085,24 @@ class BatchedNeuralAutomataAgent(_Population):
     before any launch and before `dropout_step` or `memory` change.  The differentiable call of a population with memory is
     `recurrent_action(memory=None, parameters=None) -> (action, memory_next)`: the step's forward half with a graph through the
     read-outs, the stack and the expand, a `(C, P)` gradient, and `memory_next` chained from call to call for backpropagation
-    through time (die_memory_grad.hip's batched twins, die_nca_wide_sense_batch_store_memory / _backward_batch_memory)."""
+    through time (die_memory_grad.hip's batched twins, die_nca_wide_sense_batch_store_memory / _backward_batch_memory).
+
+    Signal channels (a template built with `signal_channels=K`; every candidate then has them and the same three constants,
+    `from_agents` refuses a mix): the population holds the fields of all replicas, `signals` an (R, K, W, H) float32 view of them —
+    `signals[r]` the stand-alone `replica_agent(r).signals`, bit for bit.  `env.step` takes die_nca_wide_env_step_batch_signal: the
+    standing build, the expand if M > 0, the L wide layers giving 3 + K + M planes, the memory read-out if M > 0, ONE launch that
+    updates all K·R planes (die_signal.hip) into a second buffer that is then swapped, and the parent's launches — L + 4 in all,
+    L + 6 with memory.  With `episodes=E` every replica has its own field.  Large worlds (`per_replica`) keep one stand-alone agent
+    per replica, each with its own field (`signals` is then None: read `agents[r].signals`).  `reset_signals()` zeroes every
+    replica's, and the instance attribute `reset` a memory population carries exists with K > 0 alone too and zeroes the memory and
+    the fields — so the searchers score every candidate from a blank field.  agents_die, max_agents and `reset(seed=...)`, flows,
+    per-replica Dynamics, dropout_seed, `action=`, the stock channel, memory and both searchers take signals as they are, and so
+    does `Dynamics(agents_born=True)` while M = 0: the field has no per-slot state.  Refused with NotImplementedError before any
+    launch and before `dropout_step`, `memory` or `signals` change: `differentiable_sense`, `differentiable_action`,
+    `forward_device` and `recurrent_action`."""
+
+    _signal_channels = 0                            # (a population without signal channels has neither)
+    _signals = _signals_next = None
 
     def __init__(self, env: BatchedEnv, template: NeuralAutomataAgent, parameters=None, episodes: int = 1, *,
                  dropout_seed: Optional[int] = None, dropout_seed_stride: int = 1):
@@ -1109,10 +1127,14 @@ class BatchedNeuralAutomataAgent(_Population):
         self._stock_channel = template.with_stock_channel      # the *_stock entry points: one launch more, layer 0 one plane more
         self._memory_channels = template.memory_channels       # die_nca_wide_env_step_batch_memory: L + 5 launches
         # this population's step builds the env's stock planes (with memory: as its standing planes), so the next may build on top
-        self._builds_stock_planes = bool(self._stock_channel or self._memory_channels)
+        self._signal_channels = template.signal_channels       # die_nca_wide_env_step_batch_signal: L + 4 launches, L + 6 with memory
+        self._builds_stock_planes = bool(self._stock_channel or self._memory_channels or self._signal_channels)
         self.memory = None                          # (R, M, Nmax) float32 by slot id (small worlds; large ones: agents[r].memory)
-        if self._memory_channels:
-            self.reset = self.reset_memory          # on the INSTANCE: the searchers call `reset()` where a population has one
+        self._signals = self._signals_next = None   # (K, R, W, H) float32 each (small worlds; large ones: agents[r].signals)
+        if self._signal_channels:
+            self.reset = self.reset_state           # on the INSTANCE: the searchers call `reset()` where a population has one
+        elif self._memory_channels:
+            self.reset = self.reset_memory
         template._check_wide()
         layers = template.model.conv_layers()
         for k in layers:
@@ -1150,6 +1172,29 @@ class BatchedNeuralAutomataAgent(_Population):
             self.memory = torch.zeros((self.R, M, env.Nmax), dtype=torch.float32, device=env.device)
             # plane j of replica r at (j·R + r)·W·H: a batched layer launch reads plane j of every replica one plane apart
             self._memory_planes = torch.empty((M, self.R, env.W, env.H), dtype=torch.float32, device=env.device)
+        if self._signal_channels:
+            # plane k of replica r at (k·R + r)·W·H, as the memory planes lie: layer 0 reads plane k of every replica one plane apart
+            self._signals = torch.zeros((self._signal_channels, self.R, env.W, env.H), dtype=torch.float32, device=env.device)
+            self._signals_next = torch.empty_like(self._signals)
+
+    @property
+    def signals(self) -> Optional[torch.Tensor]:
+        """The signal fields of every replica as an (R, K, W, H) float32 view (None without signal channels, and on large worlds,
+        where every stand-alone agent keeps its own).  The view is of the current buffer: take it again after a step."""
+        return None if self._signals is None else self._signals.permute(1, 0, 2, 3)
+
+    def reset_signals(self) -> None:
+        """A blank field for every replica (large worlds: for every stand-alone agent).  A population without signal channels has
+        nothing to reset."""
+        if self._signals is not None:
+            self._signals.zero_()
+        for ag in getattr(self, 'agents', ()):
+            ag.reset_signals()
+
+    def reset_state(self) -> None:
+        """Blank memory and blank fields: what the searchers' `reset()` does for a population with signal channels."""
+        self.reset_memory()
+        self.reset_signals()
 
     def reset_memory(self) -> None:
         """Blank memory for every replica (large worlds: for every stand-alone agent).  A population without memory channels
@@ -1229,6 +1274,8 @@ class BatchedNeuralAutomataAgent(_Population):
     def _stepped(self) -> None:
         if self.dropout_seed is not None:
             self.dropout_step += 1                  # counts forward calls, masked or not (as NeuralAutomataAgent.sense does)
+        if self._signals is not None:               # the step wrote every replica's next field into the second buffer
+            self._signals, self._signals_next = self._signals_next, self._signals
 
     # ------------------------------------------------------------------ step
     def _check_step(self, env: BatchedEnv) -> None:
@@ -1252,7 +1299,12 @@ class BatchedNeuralAutomataAgent(_Population):
         mask = None if drop is None else C.byref(drop)
         if self._wide or self._stock_channel:       # ONE entry point whatever is set: the mask and the two tables are all nullable
             tail = (mask, *(rows or (None, None)))
-            if self._memory_channels:               # then the env's stock planes, M, the memory, its planes, whether layer 0 reads the stock
+            if self._signal_channels:               # the memory variant's tail (M = 0: no memory), then K, both field buffers, the constants
+                name = 'die_nca_wide_env_step_batch_signal'
+                tail += (_ptr(self.env._stock_planes()), self._memory_channels, _ptr(self.memory) if self._memory_channels else None,
+                         _ptr(self._memory_planes) if self._memory_channels else None, int(self._stock_channel), self._signal_channels,
+                         _ptr(self._signals), _ptr(self._signals_next), *self.template.signal_constants)
+            elif self._memory_channels:             # then the env's stock planes, M, the memory, its planes, whether layer 0 reads the stock
                 name = 'die_nca_wide_env_step_batch_memory'
                 tail += (_ptr(self.env._stock_planes()), self._memory_channels, _ptr(self.memory), _ptr(self._memory_planes),
                          int(self._stock_channel))
@@ -1397,6 +1449,8 @@ class BatchedNeuralAutomataAgent(_Population):
         large worlds (`per_replica`), fp16 fields, 'reflect' / 'replicate' and an unseeded `p_agent_dropout` > 0 in training
         mode; with ValueError a `memory` of the wrong shape, dtype or device."""
         from .functional import memory_planes_batch, memory_record_batch
+        if self._signal_channels:
+            self.template._check_signals('recurrent_action')
         M, env = self._memory_channels, self.env
         if not M:
             raise ValueError('recurrent_action: a population without memory channels (memory_channels=0) is differentiated by '

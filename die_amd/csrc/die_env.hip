@@ -390,86 +390,8 @@ __global__ __launch_bounds__(1024) void k_reduce(const long long* pa, int na, co
 }
 
 // ---- diffusion --------------------------------------------------------------------------
-#define DIF_TX 16      // tile rows (x, stride H)
-#define DIF_TY 256     // tile columns (y, contiguous)
-#define DIF_MAXR 8
-
-struct DiffuseArgs {
-    const void* src;
-    void* dst;
-    int W, H;
-    float keep;                 // 1 − decay
-    int mode;                   // die_diffuse_mode: what lies beyond the edges
-    float w[2 * DIF_MAXR + 1];  // w[k + R], k = −R..R
-};
-
-__device__ __forceinline__ int wrap_idx(int v, int n) {
-    v %= n;
-    return v < 0 ? v + n : v;
-}
-
-// scipy.ndimage boundary modes (what skimage.filters.gaussian passes through, core/env.py:140-143): the index that
-// stands in for v outside [0, n), or −1 for 'constant' (cval = 0)
-__device__ __forceinline__ int edge_idx(int v, int n, int mode) {
-    if (v >= 0 && v < n) return v;
-    switch (mode) {
-        case DIE_DIFFUSE_NEAREST: return v < 0 ? 0 : n - 1;
-        case DIE_DIFFUSE_REFLECT: {                    // d c b a | a b c d | d c b a   (period 2n)
-            int m = v % (2 * n);
-            m = m < 0 ? m + 2 * n : m;
-            return m < n ? m : 2 * n - 1 - m;
-        }
-        case DIE_DIFFUSE_MIRROR: {                     // d c b | a b c d | c b a       (period 2n − 2)
-            if (n == 1) return 0;
-            const int p = 2 * n - 2;
-            int m = v % p;
-            m = m < 0 ? m + p : m;
-            return m < n ? m : p - m;
-        }
-        case DIE_DIFFUSE_CONSTANT: return -1;
-        default: return wrap_idx(v, n);
-    }
-}
-
-// LDS-tiled separable gaussian on the torus: the (TX+2R)×(TY+2R) input tile is staged once,
-// filtered along x (axis 0, as scipy does first) into a second LDS plane, then along y.
-template <typename T, int R>
-__global__ __launch_bounds__(DIE_BLOCK) void k_diffuse(DiffuseArgs a) {
-    constexpr int LW = DIF_TY + 2 * R + 1;    // odd pitch: bank-conflict-free column walks
-    constexpr int LH = DIF_TX + 2 * R;
-    __shared__ float s_in[LH * LW];
-    __shared__ float s_mid[DIF_TX * LW];
-    const T* src = (const T*)a.src;
-    T* dst = (T*)a.dst;
-    const int x0 = blockIdx.y * DIF_TX, y0 = blockIdx.x * DIF_TY;
-    const int H = a.H, W = a.W;
-    constexpr int LWV = DIF_TY + 2 * R;       // valid columns
-    for (int idx = threadIdx.x; idx < LH * LWV; idx += DIE_BLOCK) {
-        const int li = idx / LWV, lj = idx - li * LWV;
-        const int gx = edge_idx(x0 - R + li, W, a.mode), gy = edge_idx(y0 - R + lj, H, a.mode);
-        s_in[li * LW + lj] = (gx < 0 || gy < 0) ? 0.f : die_ld(src, (int64_t)gx * H + gy);
-    }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < DIF_TX * LWV; idx += DIE_BLOCK) {
-        const int i = idx / LWV, j = idx - i * LWV;
-        float t = a.w[R] * s_in[(i + R) * LW + j];            // scipy's correlate1d on a symmetric kernel: the centre, then
-#pragma unroll
-        for (int k = 0; k < R; ++k) t += (s_in[(i + k) * LW + j] + s_in[(i + 2 * R - k) * LW + j]) * a.w[k];   // pairs, outermost first
-        s_mid[i * LW + j] = t;
-    }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < DIF_TX * DIF_TY; idx += DIE_BLOCK) {
-        const int i = idx / DIF_TY, j = idx - i * DIF_TY;
-        const int gx = x0 + i, gy = y0 + j;
-        if (gx < W && gy < H) {
-            float o = a.w[R] * s_mid[i * LW + j + R];
-#pragma unroll
-            for (int k = 0; k < R; ++k) o += (s_mid[i * LW + j + k] + s_mid[i * LW + j + 2 * R - k]) * a.w[k];
-            die_st(dst, (int64_t)gx * H + gy, o * a.keep);
-        }
-    }
-}
-
+// What the two kernels share with die_signal.hip's twins is die_diffuse.h (argument structs, edge rules, 16-byte accessors) and the
+// two sweeps' text, die_diffuse_tile.inc / die_diffuse_rows.inc; here a cell is read as the plane holds it.
 // ---- row-marching diffusion, optionally fused with deposit + feeding -----------------------
 // One wave owns a strip of 248 columns (62 lanes × 4 contiguous cells; lanes 0 and 63 only load
 // the 4-column halo to the left / right) and marches down DIF_ROWS rows.  Per row a lane loads its
@@ -483,65 +405,15 @@ __global__ __launch_bounds__(DIE_BLOCK) void k_diffuse(DiffuseArgs a) {
 #define DIF_WCOLS 248          // output columns per wave
 #define DIF_BLOCK 128          // waves are independent (no LDS, no barrier): small workgroups balance better
 
-struct RowsArgs {
-    const void* src;
-    void* dst;
-    const unsigned long long* claim;   // FUSED == 1: the 64-bit claim plane
-    const float* dep;                  // FUSED == 2: per cell the winner's deposit, or DIE_DEP_EMPTY (tile-binned step, die_pic.hip)
-    void* food;                        // FUSED only
-    int W, H, epoch, food_infinite;
-    int64_t rep_cells;                 // batched replicas (gridDim.z > 1): plane stride in cells; partials / results stride per replica
-    int halo;                          // tile mode: cells within `halo` of the array border belong to neighbours
-    int rpw;                           // rows per wave (rows_per_wave): DIF_ROWS on large fields, fewer on small ones
-    int wrapx, wrapy;                  // tile mode: this axis spans the whole world (one rank along it) and is periodic
-    // k_reduce folded in: workgroup (0, 0) first sums the claim pass's `n_part` partial gains (a kernel boundary lies
-    // between their producer and this sweep) in k_reduce's order and writes the step result — one launch less per step
-    const long long* part_gain;
-    const long long* part_gain2;       // NULL, or a second `n_part` partial gains (batched replicas' dead-slot pass)
-    const long long* part_alive;       // NULL: num_alive = alive_const; else the sum of the claim pass's counts (ghost tiles)
-    int n_part;
-    die_step_result* result;
-    long long alive_const;
-    float keep, rate_feed;
-    float w[2 * 4 + 1];
-};
+#include "die_diffuse.h"
 
-template <typename T> struct Vec4;
-template <> struct Vec4<float> {
-    static __device__ __forceinline__ void ld(const float* p, float v[4]) { const float4 t = *(const float4*)p; v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-    static __device__ __forceinline__ void st(float* p, const float v[4]) { *(float4*)p = make_float4(v[0], v[1], v[2], v[3]); }
-};
-template <> struct Vec4<__half> {
-    static __device__ __forceinline__ void ld(const __half* p, float v[4]) {
-        const uint2 t = *(const uint2*)p;
-        const __half2 a = *(const __half2*)&t.x, b = *(const __half2*)&t.y;
-        v[0] = __low2float(a); v[1] = __high2float(a); v[2] = __low2float(b); v[3] = __high2float(b);
-    }
-    static __device__ __forceinline__ void st(__half* p, const float v[4]) {
-        const __half2 a = __halves2half2(die_f2h(v[0]), die_f2h(v[1])), b = __halves2half2(die_f2h(v[2]), die_f2h(v[3]));
-        uint2 t; t.x = *(const uint32_t*)&a; t.y = *(const uint32_t*)&b;
-        *(uint2*)p = t;
-    }
-};
-
-// Per-replica Dynamics: the batched fused sweep of the replicas of ONE gaussian radius takes a table as an optional last argument
-// (`TABLE...`: nothing, or a RowsTable).  Workgroup plane blockIdx.z then sweeps replica idx[blockIdx.z] with the taps, keep,
-// rate_feed and food_infinite of that replica's row — scalar loads into the by-value RowsArgs ahead of the sweep, which
-// is the instantiation (and so the arithmetic per cell) a stand-alone world of that sigma takes.  The index list travels by value;
-// 64 rows would not fit the kernarg segment comfortably, hence the device table.
-struct RowsTable {
-    const die_dynamics_row* rows;
-    int32_t n;
-    uint8_t idx[DIE_MAX_REPLICAS];
-};
-
-__device__ __forceinline__ unsigned rows_replica(RowsArgs&, int) { return blockIdx.z; }
-__device__ __forceinline__ unsigned rows_replica(RowsArgs& a, const int R, const RowsTable& t) {
-    const unsigned z = t.idx[blockIdx.z];
-    const die_dynamics_row row = t.rows[z];
-    a.keep = row.keep; a.rate_feed = row.rate_feed; a.food_infinite = row.food_infinite;
-    for (int k = 0; k <= 2 * R; ++k) a.w[k] = row.w[k];
-    return z;
+// LDS-tiled separable gaussian on the torus: the (TX+2R)×(TY+2R) input tile is staged once,
+// filtered along x (axis 0, as scipy does first) into a second LDS plane, then along y.
+template <typename T, int R>
+__global__ __launch_bounds__(DIE_BLOCK) void k_diffuse(DiffuseArgs a) {
+#define DIF_LOAD(src, i) die_ld(src, i)
+#include "die_diffuse_tile.inc"
+#undef DIF_LOAD
 }
 
 template <typename T, int R, int FUSED, bool WRAP, typename... TABLE>
@@ -609,111 +481,9 @@ __global__ __launch_bounds__(DIF_BLOCK) void k_diffuse_rows(RowsArgs a, TABLE...
         }
         return;
     }
-    const T* src = (const T*)a.src;
-    T* dst = (T*)a.dst;
-    T* food = (T*)a.food;
-    const int W = a.W, H = a.H;
-    const int lane = threadIdx.x & (DIE_WAVE - 1);
-    const int strip = blockIdx.x * (DIF_BLOCK / DIE_WAVE) + (threadIdx.x >> 6);
-    const int yb = strip * DIF_WCOLS;                       // first output column of this wave
-    if (yb >= H) return;                                    // whole wave idle (nothing below synchronises)
-    const int nout = min(DIF_WCOLS, H - yb) / 4;            // output lanes are 1..nout (H % 4 == 0)
-    const bool need = lane <= nout + 1;                     // + the two halo lanes
-    const bool outl = lane >= 1 && lane <= nout;
-    const bool wx = WRAP || a.wrapx, wy = WRAP || a.wrapy;
-    const int hx = wx ? 0 : a.halo, hy = wy ? 0 : a.halo;
-    const int col = wy ? wrap_idx(yb + 4 * (lane - 1), H)    // 16-byte aligned since H % 4 == 0
-                       : min(max(yb + 4 * (lane - 1), 0), H - 4);     // tile: clamp, border ring is don't-care
-    const int x0 = ((int)blockIdx.y - row0) * a.rpw;
-    const int rows = min(a.rpw, W - x0);
-
-    float win[2 * R + 1][4];
-#pragma unroll
-    for (int k = 0; k <= 2 * R; ++k) { win[k][0] = win[k][1] = win[k][2] = win[k][3] = 0.f; }
-
-    auto load_row = [&](int i, float v[4]) {
-        v[0] = v[1] = v[2] = v[3] = 0.f;
-        if (!need) return;
-        const int r = wx ? wrap_idx(x0 + i, W) : min(max(x0 + i, 0), W - 1);
-        const int64_t off = (int64_t)r * H + col;
-        Vec4<T>::ld(src + off, v);
-        if (FUSED) {
-            bool occ[4];
-            bool any = false;
-            if (FUSED == 1) {
-                const ulonglong2 c01 = *(const ulonglong2*)(a.claim + off), c23 = *(const ulonglong2*)(a.claim + off + 2);
-                const unsigned long long c[4] = {c01.x, c01.y, c23.x, c23.y};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    occ[j] = die_claim_occupied(c[j], a.epoch);
-                    if (occ[j]) v[j] = die_as_stored<T>(v[j] + die_claim_deposit(c[j]));     // chem[cell] + deposit of the last writer
-                    any |= occ[j];
-                }
-            } else {
-                const uint4 d4 = *(const uint4*)(a.dep + off);
-                const uint32_t d[4] = {d4.x, d4.y, d4.z, d4.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    occ[j] = d[j] != DIE_DEP_EMPTY;
-                    if (occ[j]) v[j] = die_as_stored<T>(v[j] + __uint_as_float(d[j]));
-                    any |= occ[j];
-                }
-            }
-            // feeding: this wave owns rows [x0, x0+rows) × its output lanes (tile mode: interior cells only)
-            const bool own_row = i >= 0 && i < rows && r >= hx && r < W - hx;
-            if (any && outl && own_row && !a.food_infinite) {
-                float f[4];
-                Vec4<T>::ld(food + off, f);
-                bool changed = false;                           // (an occupied cell without food stays as it is: a group in which nothing changes is not written)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const bool mine = col + j >= hy && col + j < H - hy;
-                    if (occ[j] && mine && f[j] != 0.f) { f[j] = f[j] - a.rate_feed * f[j]; changed = true; }
-                }
-                if (changed) Vec4<T>::st(food + off, f);
-            }
-        }
-    };
-
-    float nxt[4];
-    load_row(-R, nxt);
-    for (int i = -R; i < rows + R; ++i) {
-        float cur[4] = {nxt[0], nxt[1], nxt[2], nxt[3]};
-        if (i + 1 < rows + R) load_row(i + 1, nxt);            // prefetch one row ahead
-#pragma unroll
-        for (int k = 0; k < 2 * R; ++k) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) win[k][j] = win[k + 1][j];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) win[2 * R][j] = cur[j];
-        const int orow = i - R;                                // the window is centred on this row
-        if (orow < 0) continue;
-        float xf[4 + 2 * 4];                                   // [4 − R .. 4 + 4 + R): own 4 at [4..8)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float t = a.w[R] * win[R][j];                      // centre, then symmetric pairs from the outermost inwards: mirror
-#pragma unroll
-            for (int k = 0; k < R; ++k) t += (win[k][j] + win[2 * R - k][j]) * a.w[k];      // cells get identical sums, as in scipy
-            xf[4 + j] = t;
-        }
-#pragma unroll
-        for (int j = 0; j < R; ++j) {
-            xf[4 - R + j] = __shfl_up(xf[4 + 4 - R + j], 1, DIE_WAVE);      // left lane's last R cells
-            xf[8 + j] = __shfl_down(xf[4 + j], 1, DIE_WAVE);                 // right lane's first R cells
-        }
-        if (outl) {
-            float o[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float t = a.w[R] * xf[4 + j];
-#pragma unroll
-                for (int k = 0; k < R; ++k) t += (xf[4 + j - R + k] + xf[4 + j + R - k]) * a.w[k];
-                o[j] = t * a.keep;
-            }
-            Vec4<T>::st(dst + (int64_t)(x0 + orow) * H + col, o);
-        }
-    }
+#define DIF_EMIT(off, v)
+#include "die_diffuse_rows.inc"
+#undef DIF_EMIT
 }
 
 // A wave marches down its rows one dependent load at a time (one row of prefetch): on a large field the other waves of
@@ -740,7 +510,7 @@ static int launch_rows(RowsArgs a, int R, hipStream_t s, int replicas = 1) {
     return DIE_OK;
 }
 
-static bool rows_kernel_applies(int W, int H, int R) { return R <= 4 && H % 4 == 0 && H >= 4 && W >= 1; }
+int die_rows_per_wave(int W, int H, int planes) { return rows_per_wave(W, H, planes); }      // (die_signal.hip's launch of the same sweep)
 
 static int gaussian_taps(float sigma, double* w) {
     // scipy.ndimage._gaussian_kernel1d: radius int(4σ + .5), exp(−x²/2σ²) normalised
@@ -1556,6 +1326,15 @@ struct MemoryStep {
     bool with_stock;             // layer 0 also reads the standing planes as its stock channel
 };
 
+// die_nca_wide_env_step_batch_signal's own arguments (die_signal.hip: the field the agents write and read)
+struct SignalStep {
+    int K;                       // signal channels, 1..DIE_SIGNAL_MAX_CHANNELS
+    const float* field_in;       // plane k of replica r at (k * R + r) * plane_stride: layer 0 reads them, the update reads them again
+    float* field_out;            // … and writes these, laid out alike
+    float deposit, sigma, decay;
+    bool with_stock;             // layer 0 also reads the standing planes as its stock channel (with or without memory)
+};
+
 // die_nca_env_step_batch (drop null) and die_nca_env_step_batch_dropout: one body; the mask only changes the last conv launch.
 // `wide` (die_nca_wide_env_step_batch): the stack's check and its sensing are die_nca_wide.hip's, which hand back the same
 // (sense pointer, replica stride); everything after the sensing is shared.
@@ -1565,16 +1344,20 @@ struct MemoryStep {
 // `ms` (die_nca_wide_env_step_batch_memory; wide stacks only, `stock` then holds the standing planes whether or not layer 0 reads
 // them): after the build the memory is expanded into its planes, layer 0 reads them after the field's, the last layer gives
 // 3 + M planes and the planes 3.. are read out into the memory before the claim launch moves anything: L + 5 launches.
+// `ss` (die_nca_wide_env_step_batch_signal; wide stacks only, `stock` the standing planes, `ms` null for M = 0): layer 0 reads the
+// K field planes after chem, the last layer gives 3 + K + M planes — the memory read-out then starts at plane 3 + K — and after
+// the read-outs ONE launch updates the field from the planes 3 .. 3 + K - 1 at the standing planes' cells: L + 4, L + 6 with memory.
 static int nca_env_step_batch(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
                               const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws, int64_t ws_bytes,
                               const die_nca_dropout* drop, void* stream, const char* who, bool with_rows = false,
                               const die_dynamics_row* rows = nullptr, const die_dynamics_row* rows_host = nullptr, bool wide = false,
-                              unsigned long long* stock = nullptr, const MemoryStep* ms = nullptr) {
+                              unsigned long long* stock = nullptr, const MemoryStep* ms = nullptr, const SignalStep* ss = nullptr) {
     DIE_REQUIRE(m && a && nca && d && b && results && ws, "%s: null argument", who);
     int rc = batch_world_check(m, a, d, b, ws_bytes, true, who);
     if (rc != DIE_OK) return rc;
-    const bool sense_stock = stock && (!ms || ms->with_stock);
-    rc = die_nca_stack_check(wide ? DIE_NCA_WIDE : DIE_NCA_NARROW, nca, m->W, m->H, b->replicas, who, true, sense_stock, ms ? ms->M : 0);
+    const bool sense_stock = stock && (ss ? ss->with_stock : !ms || ms->with_stock);
+    rc = die_nca_stack_check(wide ? DIE_NCA_WIDE : DIE_NCA_NARROW, nca, m->W, m->H, b->replicas, who, true, sense_stock, ms ? ms->M : 0,
+                             ss ? ss->K : 0);
     if (rc != DIE_OK) return rc;
     DIE_REQUIRE(nca->sense_epoch >= 1 && nca->sense_epoch <= DIE_OWNER_EPOCH_MAX && m->epoch == nca->sense_epoch % DIE_OWNER_EPOCH_MAX + 1,
                 "%s: claims at epoch %d cannot follow sensing at epoch %d", who, m->epoch, nca->sense_epoch);
@@ -1589,6 +1372,17 @@ static int nca_env_step_batch(const die_medium* m, const die_agents* a, const di
     }
     rc = batch_rows_check(with_rows, b, rows, rows_host, who);
     if (rc != DIE_OK) return rc;
+    const int64_t cells = (int64_t)m->W * m->H;
+    if (ss) {                                                         // the field's own rules, after the parent's and before any launch
+        rc = die_signal_check(m, ss->K, nca->sense_epoch, ss->deposit, ss->sigma, ss->decay, who);
+        if (rc != DIE_OK) return rc;
+        const int64_t planes = (int64_t)b->replicas * b->plane_stride;
+        rc = die_signal_overlap_check(ss->field_in, ss->field_out, (((int64_t)ss->K * b->replicas - 1) * b->plane_stride + cells) * 4, nca->scratch,
+                                      nca->scratch_bytes, stock, ((int64_t)(b->replicas - 1) * b->plane_stride + cells) * 8, who);
+        if (rc != DIE_OK) return rc;
+        DIE_REQUIRE(!ms || !die_ranges_overlap(ss->field_out, ss->K * planes * 4, ms->planes, ms->M * planes * 4),
+                    "%s: field_out overlaps the memory planes", who);
+    }
     NcaReadArgs q;
     if (stock) {                                                      // every replica's stocks as they are now, tagged sense_epoch
         rc = die_stock_launch(m, a, b->replicas, b->n, b->agent_stride, b->plane_stride, nca->sense_epoch, stock, stream, who);
@@ -1602,12 +1396,17 @@ static int nca_env_step_batch(const die_medium* m, const die_agents* a, const di
     }
     // reads the claim plane at sense_epoch …
     rc = wide ? die_nca_wide_sense_batch(m, b, nca, &q.sense, &q.rep, drop ? &dw : nullptr, stream, sense_stock ? stock : nullptr,
-                                         ms ? ms->planes : nullptr, ms ? ms->M : 0)
+                                         ms ? ms->planes : nullptr, ms ? ms->M : 0, ss ? ss->field_in : nullptr, ss ? ss->K : 0)
               : die_nca_sense_batch(m, b, nca, &q.sense, &q.rep, drop ? &dw : nullptr, stream, stock);
     if (rc != DIE_OK) return rc;
     if (ms) {                                                         // planes 3.. at the cells the agents stand on NOW: before the claim launch moves anything
-        rc = die_gather_memory_launch(m, a, b->replicas, b->n, b->agent_stride, ms->M, q.sense + 3 * (int64_t)m->W * m->H, (int64_t)m->W * m->H,
-                                      q.rep, ms->mem, b->agent_stride, (int64_t)ms->M * b->agent_stride, stream, who);
+        rc = die_gather_memory_launch(m, a, b->replicas, b->n, b->agent_stride, ms->M, q.sense + (3 + (ss ? ss->K : 0)) * (int64_t)m->W * m->H,
+                                      (int64_t)m->W * m->H, q.rep, ms->mem, b->agent_stride, (int64_t)ms->M * b->agent_stride, stream, who);
+        if (rc != DIE_OK) return rc;
+    }
+    if (ss) {                                                         // planes 3 .. 3 + K - 1 at the standing planes' cells, into the second buffer
+        rc = die_signal_launch(m->W, m->H, b->replicas, ss->K, stock, b->plane_stride, nca->sense_epoch, q.sense + 3 * cells, cells, q.rep,
+                               ss->field_in, ss->field_out, b->plane_stride, ss->deposit, ss->sigma, ss->decay, stream, who);
         if (rc != DIE_OK) return rc;
     }
     if (nca->sense_epoch == DIE_OWNER_EPOCH_MAX) {                    // … which is cleared before the tag 1 claims
@@ -1682,6 +1481,29 @@ extern "C" int die_nca_wide_env_step_batch_memory(const die_medium* m, const die
     const MemoryStep ms = {memory_channels, memory, memory_planes, with_stock == 1};
     return nca_env_step_batch(m, a, nca, act, d, b, results, ws, ws_bytes, drop, stream, who, rows || rows_host, rows, rows_host, true, standing,
                               &ms);
+}
+
+// the memory variant's arguments (memory_channels = 0 with null memory pointers: none) and the signal field's
+extern "C" int die_nca_wide_env_step_batch_signal(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
+                                                  const die_dynamics* d, const die_batch* b, die_step_result* results, void* ws,
+                                                  int64_t ws_bytes, const die_nca_dropout* drop, const die_dynamics_row* rows,
+                                                  const die_dynamics_row* rows_host, unsigned long long* standing, int32_t memory_channels,
+                                                  float* memory, float* memory_planes, int32_t with_stock, int32_t signal_channels,
+                                                  const float* field_in, float* field_out, float deposit, float sigma, float decay,
+                                                  void* stream) {
+    const char* who = "die_nca_wide_env_step_batch_signal";
+    DIE_REQUIRE(standing && field_in && field_out, "%s: null standing planes or signal field", who);
+    DIE_REQUIRE(memory_channels >= 0 && memory_channels <= DIE_MEMORY_MAX_CHANNELS, "%s: %d memory channels outside 0..%d", who, memory_channels,
+                DIE_MEMORY_MAX_CHANNELS);
+    DIE_REQUIRE(memory_channels ? memory && memory_planes : !memory && !memory_planes, "%s: %d memory channels need both the memory and its "
+                "planes, none needs neither", who, memory_channels);
+    DIE_REQUIRE(with_stock == 0 || with_stock == 1, "%s: with_stock is 0 or 1", who);
+    DIE_REQUIRE(signal_channels >= 1 && signal_channels <= DIE_SIGNAL_MAX_CHANNELS, "%s: %d signal channels outside 1..%d", who, signal_channels,
+                DIE_SIGNAL_MAX_CHANNELS);
+    const MemoryStep ms = {memory_channels, memory, memory_planes, with_stock == 1};
+    const SignalStep ss = {signal_channels, field_in, field_out, deposit, sigma, decay, with_stock == 1};
+    return nca_env_step_batch(m, a, nca, act, d, b, results, ws, ws_bytes, drop, stream, who, rows || rows_host, rows, rows_host, true, standing,
+                              memory_channels ? &ms : nullptr, &ss);
 }
 
 extern "C" int die_nca_env_step_batch(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,

@@ -57,15 +57,19 @@ static inline int die_nca_max_channels(const die_nca_batch* nca) {
 // die_memory.hip (mem_planes null: none; plane j of replica 0 at mem_planes + j * replicas * plane_stride), then the stock plane of
 // die_stock.hip (null: none).  Fills in[] / kind[] (a kernel argument's arrays) and returns the count; *rep_in: replica r's planes lie
 // r * b->plane_stride elements on, every one of them.  The forward and the adjoint of both kinds read their list here.
+// `signal_planes` with `signals` (die_signal.hip; null / 0: none): the signal field's planes, laid out as the memory planes are, read
+// as plain fp32 planes AFTER chem and BEFORE the memory planes: [agents], food, chem, signal_0 .., memory_0 .., [stock].
 int die_nca_layer0_planes(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* mem_planes, int memory,
-                          const unsigned long long* stock, const void* in[], int kind[], int64_t* rep_in);
+                          const unsigned long long* stock, const void* in[], int kind[], int64_t* rep_in,
+                          const float* signal_planes = nullptr, int signals = 0);
 // every argument of a stack, before anything is launched, in the order its kind has always checked them (narrow: the scratch's size
 // before the layers; wide: after them).  `scratch`: the step's ping-pong planes are required (the calls that keep every layer in
 // caller-owned storage check their own); `stock`: layer 0 reads the stock plane as its last input; `memory`: layer 0 reads that many
-// planes more and the last layer gives 3 + memory (die_nca_wide.hip, beside the wider kind's limits)
+// planes more and the last layer gives 3 + memory (die_nca_wide.hip, beside the wider kind's limits); `signals`: layer 0 reads that
+// many planes more as well and the last layer gives 3 + signals + memory, the emissions ahead of the memory
 enum die_nca_kind { DIE_NCA_NARROW = 0, DIE_NCA_WIDE = 1 };     // die_nca.hip's kernels / die_nca_wide.hip's
 int die_nca_stack_check(die_nca_kind kind, const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool scratch,
-                        bool stock = false, int memory = 0);
+                        bool stock = false, int memory = 0, int signals = 0);
 // the die_batch of the batched read-out, sensing and adjoint
 int die_nca_batch_shape_check(const die_medium* m, const die_batch* b, const char* who);
 // the field a stack senses: its dtype, its planes, sense_epoch
@@ -92,7 +96,16 @@ int die_nca_sense_batch(const die_medium* m, const die_batch* b, const die_nca_b
                         const DropWords* drop, void* stream, const unsigned long long* stock);
 // … and a wide one (die_nca_wide.hip; `stock`, `mem_planes` with `memory`: null / 0 without them)
 int die_nca_wide_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
-                             const DropWords* drop, void* stream, const unsigned long long* stock, const float* mem_planes, int memory);
+                             const DropWords* drop, void* stream, const unsigned long long* stock, const float* mem_planes, int memory,
+                             const float* signal_planes = nullptr, int signals = 0);
+// the signal field's update (die_signal.hip): the checks its entry points and the batched step share, then the one launch for the K
+// planes of every replica — field plane k of replica r at (k * replicas + r) * field_stride, in and out alike
+int die_signal_check(const die_medium* m, int32_t K, int32_t epoch, float deposit, float sigma, float decay, const char* who);
+int die_signal_overlap_check(const float* field_in, const float* field_out, int64_t field_bytes, const float* emission, int64_t em_bytes,
+                             const unsigned long long* standing, int64_t standing_bytes, const char* who);
+int die_signal_launch(int32_t W, int32_t H, int32_t replicas, int32_t K, const unsigned long long* standing, int64_t standing_rep, int32_t epoch,
+                      const float* emission, int64_t em_plane, int64_t em_rep, const float* field_in, float* field_out, int64_t field_stride,
+                      float deposit, float sigma, float decay, void* stream, const char* who);
 
 // k_conv_backward_sum on `tiles` partial rows of nw weights (die_nca_grad.hip), for the wide adjoint's rows as well
 void die_conv_backward_fold(const float* part, int64_t tiles, int nw, float* out, hipStream_t s);

@@ -361,12 +361,15 @@ extern "C" int64_t die_nca_batch_scratch_bytes(int32_t W, int32_t H, int32_t rep
 }
 
 int die_nca_layer0_planes(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* mem_planes, int memory,
-                          const unsigned long long* stock, const void* in[], int kind[], int64_t* rep_in) {
+                          const unsigned long long* stock, const void* in[], int kind[], int64_t* rep_in, const float* signal_planes,
+                          int signals) {
     const int fkind = m->dtype == DIE_F32 ? DIE_PLANE_F32 : DIE_PLANE_F16;
     int c = 0;
     if (nca->with_agent_channel) { in[c] = m->owner; kind[c++] = DIE_PLANE_AGENTS; }
     in[c] = m->food; kind[c++] = fkind;
     in[c] = m->chem; kind[c++] = fkind;
+    // the signal field (die_signal.hip): plane k of replica r at (k * R + r) * plane_stride too, fp32 whatever the field's dtype
+    for (int k = 0; signal_planes && k < signals; ++k) { in[c] = signal_planes + (int64_t)k * b->replicas * b->plane_stride; kind[c++] = DIE_PLANE_F32; }
     // plane j of replica r at (j * R + r) * plane_stride, as die_memory_planes_batch writes them: one plane_stride a replica
     for (int j = 0; mem_planes && j < memory; ++j) { in[c] = mem_planes + (int64_t)j * b->replicas * b->plane_stride; kind[c++] = DIE_PLANE_F32; }
     if (stock) { in[c] = stock; kind[c++] = DIE_PLANE_STOCK; }

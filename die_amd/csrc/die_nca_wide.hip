@@ -265,7 +265,7 @@ struct NcaLimits {
 static const NcaLimits nca_limits[2] = {{NCA_MAXC, NCA_MAXK, "odd sizes up to %d", false}, {NCAW_MAXC, 5, "1, 3 or 5", true}};
 
 int die_nca_stack_check(die_nca_kind kind, const die_nca_batch* nca, int32_t W, int32_t H, int32_t replicas, const char* who, bool scratch,
-                        bool stock, int memory) {
+                        bool stock, int memory, int signals) {
     const bool wide = kind == DIE_NCA_WIDE;
     const NcaLimits& lim = nca_limits[kind];
     if (scratch) DIE_REQUIRE(nca && nca->layers && nca->scratch, "%s: null stack, layer list or scratch", who);
@@ -285,7 +285,7 @@ int die_nca_stack_check(die_nca_kind kind, const die_nca_batch* nca, int32_t W, 
     };
     if (wide) DIE_REQUIRE((W + NCA_TX - 1) / NCA_TX <= 65535, "%s: field too tall", who);
     else if (scratch && scratch_check(NCA_MAXC) != DIE_OK) return DIE_ERR_ARG;
-    int cin = 2 + nca->with_agent_channel + memory + (stock ? 1 : 0);
+    int cin = 2 + nca->with_agent_channel + signals + memory + (stock ? 1 : 0);
     for (int l = 0; l < nca->n_layers; ++l) {
         const die_nca_layer& L = nca->layers[l];
         if (!(L.k >= 1 && L.k <= lim.max_k && (L.k & 1))) {
@@ -305,7 +305,9 @@ int die_nca_stack_check(die_nca_kind kind, const die_nca_batch* nca, int32_t W, 
                     "needs a field larger than that (%dx%d)", who, l, L.k / 2, W, H);
         cin = L.cout;
     }
-    if (memory) DIE_REQUIRE(cin == 3 + memory, "%s: the last layer gives %d planes (dx, dy, deposit and %d memory planes: %d)", who, cin,
+    if (signals) DIE_REQUIRE(cin == 3 + signals + memory, "%s: the last layer gives %d planes (dx, dy, deposit, %d signal and %d memory planes: %d)",
+                             who, cin, signals, memory, 3 + signals + memory);
+    else if (memory) DIE_REQUIRE(cin == 3 + memory, "%s: the last layer gives %d planes (dx, dy, deposit and %d memory planes: %d)", who, cin,
                             memory, 3 + memory);
     else DIE_REQUIRE(cin == 3, "%s: the last layer gives %d planes (dx, dy, deposit: 3)", who, cin);
     return wide && scratch ? scratch_check(die_nca_max_channels(nca)) : DIE_OK;
@@ -329,10 +331,10 @@ extern "C" int64_t die_nca_wide_batch_scratch_bytes(int32_t W, int32_t H, int32_
 // after the field's (die_nca.h die_nca_layer0_planes: the one list of them)
 static int wide_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* dst, bool pingpong, float* masked,
                             const float** sense, int64_t* rep, const DropWords* drop, void* stream, const unsigned long long* stock = nullptr,
-                            const float* mem_planes = nullptr, int memory = 0) {
+                            const float* mem_planes = nullptr, int memory = 0, const float* signal_planes = nullptr, int signals = 0) {
     const int64_t cells = (int64_t)m->W * m->H, rep_scratch = die_nca_max_channels(nca) * cells;
     WideArgs a = {};
-    die_nca_layer0_planes(m, b, nca, mem_planes, memory, stock, a.in, a.kind, &a.rep_in);
+    die_nca_layer0_planes(m, b, nca, mem_planes, memory, stock, a.in, a.kind, &a.rep_in, signal_planes, signals);
     a.W = m->W; a.H = m->H; a.epoch = nca->sense_epoch; a.pad = nca->padding_mode;
     a.episodes = nca->episodes > 1 ? nca->episodes : 1;
     a.out_stride = cells; a.rep_out = rep_scratch;
@@ -363,8 +365,9 @@ static int wide_sense_batch(const die_medium* m, const die_batch* b, const die_n
 }
 
 int die_nca_wide_sense_batch(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float** sense, int64_t* rep,
-                             const DropWords* drop, void* stream, const unsigned long long* stock, const float* mem_planes, int memory) {
-    return wide_sense_batch(m, b, nca, nca->scratch, true, nullptr, sense, rep, drop, stream, stock, mem_planes, memory);
+                             const DropWords* drop, void* stream, const unsigned long long* stock, const float* mem_planes, int memory,
+                             const float* signal_planes, int signals) {
+    return wide_sense_batch(m, b, nca, nca->scratch, true, nullptr, sense, rep, drop, stream, stock, mem_planes, memory, signal_planes, signals);
 }
 
 // ---- the same launches into storage that keeps every layer (the forward of die_nca_wide_backward_batch) -----------------

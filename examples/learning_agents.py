@@ -10,6 +10,7 @@ separable CMA-ES with stdev_init 0.1 and popsize 10 (die_amd.search.CMAES), the 
                                        [--reseed S] [--reseed-stride 0] [--episodes 1] [--out saved_models/agent.pt] [--time]
                                        [--dropout P] [--dropout-seed S] [--dropout-stride K] [--init-from FILE]
                                        [--stock-channel] [--memory-channels M]
+                                       [--signal-channels K [--signal-sigma S --signal-decay D --signal-deposit G]]
 
 --init-from FILE starts the search from a saved agent (e.g. the one examples/imitate_agent.py fits by gradient descent): its
 `parameters_to_vector` becomes the searcher's `center_init` instead of a centre drawn in initial_bounds.  A file whose agent
@@ -24,6 +25,12 @@ step.  With --agents-die / --agents-born that is the quantity that decides wheth
 step to the next, read by the stack as M more observation planes and written as M more output planes.  The stack is then a wide
 stack (--hidden-channels defaults to the observation's width), every generation starts from blank memory, and --agents-born is
 refused (a newborn would inherit a dead agent's memory).
+
+--signal-channels K (1..8) trains agents that signal (NeuralAutomataAgent(signal_channels=K)): a field of K planes the stack reads as
+K more observation channels and writes through K more output planes at the cells the agents stand on; it diffuses (--signal-sigma),
+decays (--signal-decay) and is read by whoever comes by; --signal-deposit scales the emission.  A wide stack, two more launches per
+batched step, every generation from a blank field; signalling is free of action cost.  With --agents-born it is fine as long as
+--memory-channels is 0.  K = 0, 1, 2, 4 varies the medium's capacity for message passing under one searcher.
 
 --dropout P trains the agent with the reference's `p_agent_dropout=P` (its learning_agents.py carries 0.25): in every batched step
 replica r's sense planes are multiplied by the counter-based dropout mask of key --dropout-seed + r·--dropout-stride (default
@@ -190,6 +197,8 @@ def main():
     args.wide_kw = wide_keywords(args)
     if not 0 <= args.memory_channels <= 8 or (args.memory_channels and args.agents_born):
         p.error('--memory-channels in 0..8, and not together with --agents-born (a newborn would inherit a dead agent\'s memory)')
+    if not 0 <= args.signal_channels <= 8:
+        p.error('--signal-channels in 0..8')
     args.agents_die = lifecycle(args.agents_die, args.agents_born)      # (what the helpers hand to make_dynamics)
     if not 0. <= args.dropout <= 1. or args.dropout_stride < 0:
         p.error('--dropout in [0, 1], --dropout-stride >= 0')

@@ -5,6 +5,7 @@ all R worlds stepped together by die_amd.batch (L + 2 launches per step for an L
     python examples/population_eval.py [--replicas 10] [--size 96] [--iters 50] [--dynamics st-perlin-wide] [--generations 0] [--agents-die] [--agents-born]
                                        [--max-agents alive|full|tight|N] [--reseed S] [--episodes 1] [--compare]
                                        [--dropout P] [--dropout-seed S] [--dropout-stride K] [--stock-channel] [--memory-channels M]
+                                       [--signal-channels K [--signal-sigma S --signal-decay D --signal-deposit G]]
 
 --stock-channel gives the candidates a fourth observation channel, `'agent_food'`: on every cell the stock of the agent standing
 there (NeuralAutomataAgent(with_stock_channel=True)), built on the device by one more launch per batched step — what lets a policy
@@ -13,6 +14,12 @@ tell a starving agent from a well-fed one under --agents-die / --agents-born.
 --memory-channels M (1..8) gives every agent M values it carries from one step to the next (NeuralAutomataAgent(memory_channels=M)):
 the stack becomes a wide stack that reads them as M more observation planes and writes them as M more output planes (three more
 launches per batched step).  Every evaluation and every search generation starts from blank memory.  Not with --agents-born.
+
+--signal-channels K (1..8) gives the agents a field of K planes they write and read (NeuralAutomataAgent(signal_channels=K)): the
+stack, a wide stack, reads the planes as K more observation channels and emits into them through K more output planes at the
+cells the agents stand on; the field then diffuses (--signal-sigma, default 0.5) and decays (--signal-decay, default 0.1), two
+more launches per batched step.  --signal-deposit scales the emission.  Every evaluation and every search generation starts from
+a blank field.  K = 0, 1, 2, 4 varies the medium's capacity for message passing.
 
 --dynamics picks one of the reference's three worlds (learning_agents.py `dynamics_choice`): 'st-perlin', 'st-perlin-wide' or
 'dyn-pred', where the food flows in running waves (WaveSequence.get_flow_operator, one more launch per batched step).
@@ -142,16 +149,26 @@ def add_wide_arguments(p):
     p.add_argument('--memory-channels', type=int, default=0, metavar='M', help='values every agent carries between steps, 1..8 (memory_channels=M: '
                                                                                'a wide stack, three more launches per batched step; not with '
                                                                                '--agents-born)')
+    p.add_argument('--signal-channels', type=int, default=0, metavar='K', help='planes of a field the agents write and read, 1..8 '
+                                                                               '(signal_channels=K: a wide stack, two more launches per batched step)')
+    p.add_argument('--signal-sigma', type=float, default=None, metavar='S', help="the signal field's gaussian sigma (default 0.5; radius int(4 S + .5) in 1..8)")
+    p.add_argument('--signal-decay', type=float, default=None, metavar='D', help="the signal field's decay per step, in [0, 1] (default 0.1)")
+    p.add_argument('--signal-deposit', type=float, default=None, metavar='G', help='what an emission of 1 adds to a cell (default 1.0)')
 
 
 def wide_keywords(args):
-    """NeuralAutomataAgent's keywords for --hidden-channels C --hidden-activation A --stock-channel --memory-channels M (none when
-    none is given)."""
+    """NeuralAutomataAgent's keywords for --hidden-channels C --hidden-activation A --stock-channel --memory-channels M
+    --signal-channels K with its three constants (none when none is given; the constants only beside K > 0)."""
     kw = {}
     if getattr(args, 'stock_channel', False):
         kw['with_stock_channel'] = True
     if getattr(args, 'memory_channels', 0):
         kw['memory_channels'] = args.memory_channels
+    if getattr(args, 'signal_channels', 0):
+        kw['signal_channels'] = args.signal_channels
+        for name in ('signal_sigma', 'signal_decay', 'signal_deposit'):
+            if getattr(args, name, None) is not None:
+                kw[name] = getattr(args, name)
     if args.hidden_channels is not None:
         kw['hidden_channels'] = args.hidden_channels
     if args.hidden_activation != 'none':
@@ -270,6 +287,7 @@ def main():
         run_epoch(one_at_a_time_worlds(args.size, 1, args.seed, args.dynamics, args.agents_die, N)[0], agents[0], 2)
         agents[0].dropout_step = 0                                           # (the warm-up advanced its mask counter)
         agents[0].reset_memory()                                             # (… and left its memory, with --memory-channels)
+        agents[0].reset_signals()                                            # (… and its field, with --signal-channels)
         benv, pop = make_population(args.size, template, rows, args.seed, args.dynamics, args.agents_die, N, E, drop_kw)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -303,6 +321,7 @@ def main():
                 benv.reset(seeds=episode_seeds(args.reseed + g * E, R, E))
             if pop.memory is not None:                                      # --memory-channels: a new world starts from blank memory
                 pop.reset_memory()
+            pop.reset_signals()                                             # --signal-channels: … and from a blank field
             fit = candidate_fitness(evaluate_population(benv, pop, args.iters), E)
         else:
             gen_benv, gen_pop = make_population(args.size, template, samples, args.seed + 1 + g * E, args.dynamics, args.agents_die, N, E, drop_kw)

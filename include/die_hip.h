@@ -1179,6 +1179,50 @@ int die_nca_wide_env_step_batch_memory(const die_medium* m, const die_agents* a,
                                        const die_dynamics_row* rows_host, unsigned long long* standing, int32_t memory_channels,
                                        float* memory, float* memory_planes, int32_t with_stock, void* stream);
 
+/* ---- Signal channels: a field the agents write and read (die_signal.hip; NeuralAutomataAgent(signal_channels=K)) -----------
+ * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
+ * The field is K fp32 planes, whatever the medium's dtype.  One forward: the wide stack reads them as plain
+ * DIE_PLANE_F32 inputs (after chem, before the memory planes) and gives 3 + K + M planes; the planes 3 .. 3 + K - 1 are the
+ * emissions, and the field is updated from them at the occupied cells of a standing plane (die_stock_plane's words at `epoch`:
+ * alive slots only; the payload is ignored, so agents sharing a cell emit once).
+ *
+ * die_signal_step — the update, one launch for all K planes:
+ *   E_k[c] = occupied(c at epoch) ? deposit * emission_k[c] : +0.0f          (one fp32 multiply)
+ *   field_out_k = (1 - decay) * gaussian(field_in_k + E_k, sigma, mode 'wrap', truncate 4)
+ * in fp32: one fp32 add, then exactly die_diffuse_decay's arithmetic (the same device bodies with another loader).  Emission plane
+ * k at emission_planes + k * plane_stride, field plane k at field_in / field_out + k * field_stride.  EVERY cell of every output
+ * plane is written (nobody clears them); the words between two planes are left alone.  The row-marching kernel with 16-byte
+ * accesses runs where H % 4 == 0, the radius is at most 4 and every pointer and stride is 16-byte aligned; the LDS-tiled one
+ * elsewhere.  Checked before the launch (DIE_ERR_ARG): a null pointer, W or H < 1, signal_channels outside
+ * 1..DIE_SIGNAL_MAX_CHANNELS, epoch outside 1..DIE_OWNER_EPOCH_MAX, a sigma whose radius int(4 sigma + .5) lies outside 1..8, decay
+ * outside [0, 1], a deposit that is not finite, plane_stride or field_stride < W * H, a field_out that overlaps field_in, the emission
+ * planes or the standing plane; a decomposed medium (m->gW > 0) is DIE_ERR_UNSUPPORTED.  Of `m` only W, H and gW are read. */
+#define DIE_SIGNAL_MAX_CHANNELS 8
+int die_signal_step(const die_medium* m, const unsigned long long* standing, int32_t epoch, int32_t signal_channels,
+                    const float* emission_planes, int64_t plane_stride, const float* field_in, float* field_out, int64_t field_stride,
+                    float deposit, float sigma, float decay, void* stream);
+/* All K planes of all R replicas in ONE launch (plane k of replica r is blockIdx.z = k * R + r).  Replica r: standing plane at
+ * standing + r * b->plane_stride, emission plane k at emission_planes + r * replica_stride + k * plane_stride (a stack's scratch),
+ * field plane k at field_in / field_out + (k * R + r) * b->plane_stride — the layout in which a batched layer launch reads plane k
+ * of every replica b->plane_stride apart.  Checked as die_signal_step, and: a null batch, replicas outside 1..DIE_MAX_REPLICAS,
+ * b->plane_stride < W * H, agent_stride < 1, n[r] outside 0..agent_stride, replica_stride below a replica's K planes. */
+int die_signal_step_batch(const die_medium* m, const die_batch* b, const unsigned long long* standing, int32_t epoch,
+                          int32_t signal_channels, const float* emission_planes, int64_t plane_stride, int64_t replica_stride,
+                          const float* field_in, float* field_out, float deposit, float sigma, float decay, void* stream);
+/* die_nca_wide_env_step_batch_memory for a population whose agents also write a signal field.  Its arguments — memory_channels = 0
+ * with null memory and memory_planes is allowed: no memory — and: signal_channels = K in 1..DIE_SIGNAL_MAX_CHANNELS; field_in and
+ * field_out, K * R fp32 planes each, laid out as die_signal_step_batch reads them; the three constants.  In order: the parent's
+ * checks in the parent's order, with layer 0 reading 2 + with_agent_channel + K + M + with_stock planes ([agents], food, chem,
+ * signal_0 .., memory_0 .., [stock]) and the last layer giving 3 + K + M; die_signal_step's checks; the standing build; the expand if
+ * M > 0; the L wide layer launches; the memory read-out of planes 3 + K .. if M > 0; the signal step on planes 3 .. 3 + K - 1; the
+ * parent's claim, lifecycle and sweeps: L + 4 launches, L + 6 with memory.  The caller swaps field_in and field_out afterwards. */
+int die_nca_wide_env_step_batch_signal(const die_medium* m, const die_agents* a, const die_nca_batch* nca, const die_action* act,
+                                       const die_dynamics* d, const die_batch* b, die_step_result* results, void* workspace,
+                                       int64_t workspace_bytes, const die_nca_dropout* drop, const die_dynamics_row* rows,
+                                       const die_dynamics_row* rows_host, unsigned long long* standing, int32_t memory_channels,
+                                       float* memory, float* memory_planes, int32_t with_stock, int32_t signal_channels,
+                                       const float* field_in, float* field_out, float deposit, float sigma, float decay, void* stream);
+
 /* ---- The memory channels' adjoints: backpropagation through time for a stand-alone agent (die_memory_grad.hip) -------------
  * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
  * All records and memories are indexed by SLOT ID (agents->slot ? slot[n] : n), as die_gather_memory indexes the memory, so
