@@ -269,6 +269,9 @@ _SIGNATURES = {
                                                      C.c_void_p, C.c_int64, _P(NcaDropout), C.c_void_p, _P(DynamicsRow), C.c_void_p,
                                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                                      C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    'die_signal_cells': (C.c_int, [_P(Medium), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    'die_signal_step_backward': (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_int64, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     'die_memory_cells': (C.c_int, [_P(Medium), _P(Agents), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'die_memory_planes_backward': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                              C.c_int64, C.c_void_p]),

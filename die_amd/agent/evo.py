@@ -287,8 +287,11 @@ class NeuralAutomataAgent(TorchAgent):
         `F_k <- (1 - signal_decay) * gaussian(F_k + E_k, signal_sigma, mode='wrap', truncate=4)` in fp32, into a second buffer that
         is then swapped.  `sense()` alone leaves the field untouched: its clock is the agent's forward count, as memory's is.
         Signalling is free of action cost.
-      * Refused with NotImplementedError before any launch, and before `dropout_step`, `memory` or `signals` change: every
-        differentiable call (`differentiable_sense`, `differentiable_action`, `model.forward_device`, `recurrent_action`) and a
+      * Gradients: `signalling_action(obs, signals=None, memory=None) -> (action, signals_next, memory_next)` is `forward` with a
+        graph through the read-outs, the stack and the field's update (die_signal_grad.hip); chaining `signals_next` is
+        backpropagation through time through the field.  Not for populations, the stock channel, fp16 fields or decomposed worlds.
+      * Refused with NotImplementedError before any launch, and before `dropout_step`, `memory` or `signals` change: the other
+        differentiable calls (`differentiable_sense`, `differentiable_action`, `model.forward_device`, `recurrent_action`) and a
         decomposed medium.  `signal_sigma` must give a radius int(4 sigma + .5) in 1..8, `signal_decay` lie in [0, 1],
         `signal_deposit` be finite: ValueError in the constructor.
     All four are kept out of `init_params` while K is 0, saved and restored by `load` while positive (the field is state, not saved)."""
@@ -770,6 +773,106 @@ class NeuralAutomataAgent(TorchAgent):
         self.memory = memory_next.detach().clone()               # the agent's own copy, not the graph's tensor
         self._memory_rebind = False
         return action, memory_next
+
+    def signalling_action(self, obs, signals: Optional[th.Tensor] = None, memory: Optional[th.Tensor] = None):
+        """`forward` of an agent with signal channels, with a graph: `(action, signals_next, memory_next)` — (3, N), (K, W, H) and
+        (M, N) float32, each with a `grad_fn`; `memory_next` is None without memory channels.  `action` holds, bit for bit, what
+        `forward(obs)` puts in its DeviceAction's `data[:, :N]`, `signals_next` what it leaves in `self.signals` and `memory_next`
+        what it leaves in `self.memory`, given the same incoming field and memory.
+
+        `signals`: None — `self.signals`, allocated or bound as `forward` does it and a constant of the graph — or a (K, W, H)
+        float32 tensor on the medium's device, used as given: the `signals_next` of the previous call gives backpropagation through
+        time through the field, its `.detach()` truncates the gradient there, a leaf that requires grad receives one.  `memory`: as
+        in `recurrent_action`.
+
+        In order: the standing plane (die_stock_plane, the agent's own plane, one build for both records), the record of the cells
+        stood on (`functional.signal_record`: die_signal_cells) and, with memory, of where every slot stands
+        (`functional.memory_record`), the expand (`functional.memory_planes`), the observation planes stacked in `obs_channels`
+        order — `signal_k` is `signals[k]`, `chem1` the medium's chem node where it carries one — the wide stack
+        (`functional.conv2d_wide` per layer), `functional.gather_scale` on planes 0..2, `functional.signal_step` on planes
+        3 .. 3 + K - 1 and `functional.gather_memory` on planes 3 + K .. .  The records are kept by the graph, so `backward` may run
+        after the world has been stepped, re-sorted or reset and after `reset_signals()`.  Two gradients reach a `signals_next`
+        that is handed on — the next stack's input gradient and the next link's field gradient — and autograd sums them.
+
+        The agent is left as `forward(obs)` would leave it: `self.signals` and `self.memory` hold copies of the values (not the
+        graph's tensors), `dropout_step` has advanced once if a `dropout_seed` is set, `_sense_output` is set.  An unseeded
+        `p_agent_dropout` > 0 in training mode is a torch mask multiply on all planes, as in `recurrent_action`.
+
+        Refused before any launch, and before `dropout_step`, `signals` or `memory` change: an agent without signal channels
+        (ValueError: it has `recurrent_action` / `differentiable_action`); with NotImplementedError the stock channel (its
+        gradients are out of scope), a decomposed medium, fp16 fields and the boundaries 'reflect' / 'replicate'; with ValueError
+        a `signals` or `memory` of the wrong shape, dtype or device, and a medium of another shape than the one `self.signals` is
+        bound to (until `reset_signals()`).  Populations keep refusing: `BatchedNeuralAutomataAgent` has no such call yet."""
+        from ..functional import gather_memory, gather_scale, memory_planes, memory_record, signal_record, signal_step
+        K, M = self.signal_channels, self.memory_channels
+        if not K:
+            raise ValueError('signalling_action: an agent without signal channels (signal_channels=0) is differentiated by '
+                             'recurrent_action (memory channels) or differentiable_action')
+        if self.with_stock_channel:
+            raise NotImplementedError('signalling_action: no gradients with the stock channel (with_stock_channel=True): its plane is '
+                                      'piecewise constant in the weights and the adjoint kernels do not take its kind')
+        for k in self._model.conv_layers():
+            if k.padding_mode not in ('circular', 'zeros'):
+                raise NotImplementedError(f"signalling_action: boundary={k.padding_mode!r} in differentiable mode: 'circular' or 'zeros' "
+                                          f"(sense() and forward() take all of {sorted(_lib.PAD_MODES)})")
+        agents, medium = obs
+        if getattr(medium, 'world', None) is not None:
+            raise NotImplementedError(f'signal_channels={K} on a decomposed medium (die_amd/dist.py): the signal field is kept for '
+                                      'periodic single-tile planes only')
+        if medium.dtype != th.float32:
+            raise NotImplementedError(f'signalling_action: fp32 fields only (this medium is {medium.dtype})')
+        if signals is not None and (not isinstance(signals, th.Tensor) or signals.dtype != th.float32 or
+                                    tuple(signals.shape) != (K, medium.W, medium.H) or signals.device != medium.device):
+            raise ValueError(f'signalling_action: signals must be a ({K}, {medium.W}, {medium.H}) float32 tensor on {medium.device}, got '
+                             f'{(tuple(signals.shape), signals.dtype, str(signals.device)) if isinstance(signals, th.Tensor) else type(signals).__name__}')
+        if memory is not None and not M:
+            raise ValueError('signalling_action: memory given to an agent without memory channels (memory_channels=0)')
+        if M and memory is None:
+            self._check_memory_slots(medium, agents)
+        elif M and (not isinstance(memory, th.Tensor) or memory.dtype != th.float32 or tuple(memory.shape) != (M, agents.N) or
+                    memory.device != medium.device):
+            raise ValueError(f'signalling_action: memory must be a ({M}, {agents.N}) float32 tensor on {medium.device}, got '
+                             f'{(tuple(memory.shape), memory.dtype, str(memory.device)) if isinstance(memory, th.Tensor) else type(memory).__name__}')
+        elif M and getattr(agents, 'global_slots', False):
+            raise NotImplementedError(f'memory_channels={M} on a decomposed world (die_amd/dist.py): its slots carry world ids')
+        self._check_signals(medium=medium)                       # a field bound to another shape: ValueError until reset_signals()
+        medium.sensed()
+        dev, W, H = medium.device, medium.W, medium.H
+        own = self._signals_for(medium)                          # allocated or bound as `forward` does it
+        field = own if signals is None else signals
+        if M and memory is None:
+            memory = self._memory_for(medium, agents)
+        standing = self._standing = self._stock_plane(medium, agents)
+        cells = signal_record(obs, standing)
+        record = memory_record(obs, standing) if M else None
+        expanded = memory_planes(memory, record) if M else None
+        node = getattr(medium, 'chem_node', None)
+
+        def plane(c):
+            if c.startswith('signal_'):
+                return field[int(c[len('signal_'):])]
+            if c.startswith('memory_'):
+                return expanded[int(c[len('memory_'):])]
+            return node if c == 'chem1' and node is not None else medium.sel(c).float()
+
+        planes = th.stack([plane(c) for c in self.obs_channels])
+        p, training = self._model.agent_dropout.p, self._model.training
+        seeded = self._dropout_seed is not None
+        sense = self._model._stack_device(planes, (p, self._dropout_seed, self.dropout_step) if seeded and p > 0 and training else None)
+        if seeded:
+            self.dropout_step += 1
+        elif p > 0 and training:                                 # the torch-RNG mask: a torch multiply, autograd's own business
+            sense = sense * self._model.agent_dropout(th.ones((W, H), device=dev))
+        self._sense_output = sense.detach()[:3]
+        action = gather_scale(sense[:3], obs, self.action_coefs)
+        deposit, sigma, decay = self.signal_constants
+        signals_next = signal_step(field, sense[3:3 + K], cells, deposit=deposit, sigma=sigma, decay=decay)
+        memory_next = gather_memory(sense[3 + K:], record) if M else None
+        self.signals = signals_next.detach().clone()             # the agent's own copies, not the graph's tensors
+        if M:
+            self.memory = memory_next.detach().clone()
+            self._memory_rebind = False
+        return action, signals_next, memory_next
 
     def render(self) -> Sequence[np.ndarray]:
         """:176-181: the transformed medium with the channel axis last."""

@@ -2,7 +2,8 @@
 // themselves — the LDS-tiled sweep and the row-marching one — are die_diffuse_tile.inc and die_diffuse_rows.inc,
 // written once and included INSIDE each kernel that runs them, between the definitions of the one thing that differs: how a cell
 // is loaded.  die_env.hip's k_diffuse / k_diffuse_rows read the plane as it is, die_signal.hip's kernels add the agents' emission
-// first.  Text, not a function: the compiler sees in k_diffuse / k_diffuse_rows the very tokens it always saw, so their code does
+// first.  die_signal_grad.hip's kernels differ at the other end: they define DIF_STORE, what becomes of a finished output — left
+// undefined it is the plain store, the statement every other kernel has always had.  Text, not a function: the compiler sees in k_diffuse / k_diffuse_rows the very tokens it always saw, so their code does
 // not move when a twin is added (an inlined body function changed register allocation in every instantiation), and every twin sums
 // in the same order.
 #pragma once

@@ -2,7 +2,13 @@
 // a kernel of DIF_BLOCK threads that has in scope: T, R, FUSED, WRAP (constant expressions), `RowsArgs a` with src / dst / food
 // already at this workgroup's plane, `row0` (the grid rows ahead of the field's), and the macro DIF_EMIT(off, v) — a statement that
 // adds to the 4 cells v[] just read at plane offset `off` (a multiple of 4) what the filter is to see beside them, ahead of the
-// deposits; empty for the plane as it is.
+// deposits; empty for the plane as it is.  A kernel that does something else with a finished group of 4 outputs than store it defines
+// DIF_STORE(dst, off, o) — a statement given the output plane, the group's plane offset and its 4 values — ahead of the include; left
+// undefined it is the plain 16-byte store, token for token the statement that stood here before the hook.
+#ifndef DIF_STORE
+#define DIF_STORE(dst, off, o) Vec4<T>::st(dst + off, o);
+#define DIF_STORE_IS_DEFAULT
+#endif
     const T* src = (const T*)a.src;
     T* dst = (T*)a.dst;
     T* food = (T*)a.food;
@@ -106,6 +112,10 @@
                 for (int k = 0; k < R; ++k) t += (xf[4 + j - R + k] + xf[4 + j + R - k]) * a.w[k];
                 o[j] = t * a.keep;
             }
-            Vec4<T>::st(dst + (int64_t)(x0 + orow) * H + col, o);
+            DIF_STORE(dst, (int64_t)(x0 + orow) * H + col, o)
         }
     }
+#ifdef DIF_STORE_IS_DEFAULT
+#undef DIF_STORE
+#undef DIF_STORE_IS_DEFAULT
+#endif

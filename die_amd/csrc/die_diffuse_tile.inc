@@ -1,7 +1,13 @@
 // The body of an LDS-tiled separable gaussian kernel on the torus (die_diffuse.h): the (TX+2R)×(TY+2R) input tile is staged once,
 // filtered along x (axis 0, as scipy does first) into a second LDS plane, then along y.  Included inside a kernel of DIE_BLOCK
 // threads that has in scope: the type T of a cell, the radius R (constant expressions), `DiffuseArgs a`, and the macro
-// DIF_LOAD(src, i) — cell i of the plane `src` (a.src as const T*) as the filter is to see it.
+// DIF_LOAD(src, i) — cell i of the plane `src` (a.src as const T*) as the filter is to see it.  A kernel that does something
+// else with a finished cell than store it defines DIF_STORE(dst, i, v) — a statement given the output plane, the cell and its value —
+// ahead of the include; left undefined it is the plain store, token for token the statement that stood here before the hook.
+#ifndef DIF_STORE
+#define DIF_STORE(dst, i, v) die_st(dst, i, v);
+#define DIF_STORE_IS_DEFAULT
+#endif
     constexpr int LW = DIF_TY + 2 * R + 1;    // odd pitch: bank-conflict-free column walks
     constexpr int LH = DIF_TX + 2 * R;
     __shared__ float s_in[LH * LW];
@@ -32,6 +38,10 @@
             float o = a.w[R] * s_mid[i * LW + j + R];
 #pragma unroll
             for (int k = 0; k < R; ++k) o += (s_mid[i * LW + j + k] + s_mid[i * LW + j + 2 * R - k]) * a.w[k];
-            die_st(dst, (int64_t)gx * H + gy, o * a.keep);
+            DIF_STORE(dst, (int64_t)gx * H + gy, o * a.keep)
         }
     }
+#ifdef DIF_STORE_IS_DEFAULT
+#undef DIF_STORE
+#undef DIF_STORE_IS_DEFAULT
+#endif

@@ -106,6 +106,11 @@ int die_signal_overlap_check(const float* field_in, const float* field_out, int6
 int die_signal_launch(int32_t W, int32_t H, int32_t replicas, int32_t K, const unsigned long long* standing, int64_t standing_rep, int32_t epoch,
                       const float* emission, int64_t em_plane, int64_t em_rep, const float* field_in, float* field_out, int64_t field_stride,
                       float deposit, float sigma, float decay, void* stream, const char* who);
+// … and its adjoint's (die_signal_grad.hip): the same sweep on the gradient planes, laid out as the field's; replica r's occupancy bytes
+// occ_rep on, its emission gradient's plane k at grad_emission + k * em_plane + r * em_rep; grad_field or grad_emission may be null
+int die_signal_backward_launch(int32_t W, int32_t H, int32_t replicas, int32_t K, const uint8_t* occupied, int64_t occ_rep, const float* grad_next,
+                               float* grad_field, int64_t field_stride, float* grad_emission, int64_t em_plane, int64_t em_rep, float deposit,
+                               float sigma, float decay, void* stream, const char* who);
 
 // k_conv_backward_sum on `tiles` partial rows of nw weights (die_nca_grad.hip), for the wide adjoint's rows as well
 void die_conv_backward_fold(const float* part, int64_t tiles, int nw, float* out, hipStream_t s);

@@ -12,6 +12,10 @@
         the memory channels of a stand-alone NeuralAutomataAgent (die_memory_grad.hip): where every slot stands (die_memory_cells),
         the expand (M, N) -> (M, W, H) and the read-out (M, W, H) -> (M, N), each with a `grad_fn` that keeps the record
         (die_memory_planes_backward, die_gather_memory_backward).  NeuralAutomataAgent.recurrent_action composes them.
+    signal_record(obs, standing=None), signal_step(field, emission, record, *, deposit, sigma, decay)
+        the signal channels of a stand-alone NeuralAutomataAgent (die_signal_grad.hip): which cells are stood on (die_signal_cells,
+        a byte plane) and the field's update (K, W, H) -> (K, W, H) with a `grad_fn` that keeps the record (die_signal_step forward,
+        one die_signal_step_backward launch backward).  NeuralAutomataAgent.signalling_action composes them.
     memory_record_batch(population), memory_planes_batch(memory, record), gather_memory_batch(sense_tail, record)
         the same three for every replica of a BatchedNeuralAutomataAgent's worlds, one launch each (die_memory_cells_batch,
         die_memory_planes_backward_batch, die_gather_memory_backward_batch): (R, Nmax) records, (R, M, Nmax) memories, the expand
@@ -244,6 +248,90 @@ def gather_memory(sense_tail: th.Tensor, record: MemoryRecord) -> th.Tensor:
     bit-reproducible run to run whenever no cell holds more than two alive slots with a non-zero gradient."""
     _check_memory_op('sense_tail', sense_tail, record, lambda r: (r.W, r.H))
     return _GatherMemory.apply(sense_tail.contiguous(), record)
+
+
+class SignalRecord:
+    """Which cells were stood on at one forward (die_signal_cells): `occupied`, a (W, H) uint8 plane — 1 where the standing plane
+    named an alive slot at its epoch, else 0 — and the sizes `W`, `H`.  The adjoint of the field's update is driven by this plane
+    alone, so a graph that keeps the record survives the next standing build, every step, re-sort and `reset_signals()`; it holds
+    1 byte per cell where a copy of the standing plane would hold 8.  The record also remembers the standing plane and epoch it
+    was taken from, for `signal_step`'s forward only: step before that plane is built again."""
+    __slots__ = ('occupied', 'W', 'H', '_standing', '_epoch')
+
+    def __init__(self, occupied, W, H, standing, epoch):
+        self.occupied, self.W, self.H, self._standing, self._epoch = occupied, int(W), int(H), standing, int(epoch)
+
+
+def _bare_medium(W, H, epoch):
+    return _lib.Medium(W, H, _lib.DIE_F32, epoch, None, None, None, None, 0, 0, 0, 0, 0, 0, 0, 0, None)     # (W, H, gW are read)
+
+
+def signal_record(obs, standing: Optional[th.Tensor] = None) -> SignalRecord:
+    """The record of `obs` = (agents, medium) as they stand now: one die_signal_cells launch.  `standing`: the (W, H) int64
+    standing plane built for these agents at `medium.epoch` (die_stock_plane; NeuralAutomataAgent builds one per forward), or
+    None to build one here (a plane of its own, one launch more)."""
+    agents, medium = obs
+    dev, W, H = medium.device, medium.W, medium.H
+    m = medium.c_struct(need_owner=False)
+    sp = stream_ptr(dev)
+    if standing is None:
+        standing = th.zeros((W, H), dtype=th.int64, device=dev)
+        a = agents.c_struct()
+        _lib.check(_lib.lib.die_stock_plane(C.byref(m), C.byref(a), medium.epoch, _ptr(standing), sp), 'die_stock_plane')
+    elif not isinstance(standing, th.Tensor) or standing.dtype != th.int64 or tuple(standing.shape) != (W, H) or \
+            standing.device != dev or not standing.is_contiguous():
+        raise ValueError(f'standing: a contiguous ({W}, {H}) int64 tensor on {dev}')
+    occupied = th.empty((W, H), dtype=th.uint8, device=dev)                   # (every byte is written by the call)
+    _lib.check(_lib.lib.die_signal_cells(C.byref(m), _ptr(standing), medium.epoch, _ptr(occupied), sp), 'die_signal_cells')
+    return SignalRecord(occupied, W, H, standing, medium.epoch)
+
+
+class _SignalStep(th.autograd.Function):
+    """signal_step: die_signal_step forward into storage the graph owns, one die_signal_step_backward launch backward — the
+    forward's own sweep on the gradient planes (on the torus Gᵀ = G) with the masked multiply at its store."""
+
+    @staticmethod
+    def forward(ctx, field, emission, record, deposit, sigma, decay):
+        K, W, H = field.shape
+        out = th.empty((K, W, H), dtype=th.float32, device=field.device)
+        m = _bare_medium(W, H, record._epoch)
+        _lib.check(_lib.lib.die_signal_step(C.byref(m), _ptr(record._standing), record._epoch, K, _ptr(emission), W * H, _ptr(field),
+                                            _ptr(out), W * H, deposit, sigma, decay, stream_ptr(field.device)), 'die_signal_step')
+        ctx.record, ctx.constants = record, (deposit, sigma, decay)
+        return out
+
+    @staticmethod
+    @th.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        r, (deposit, sigma, decay) = ctx.record, ctx.constants
+        want_field, want_emission = ctx.needs_input_grad[:2]
+        if not (want_field or want_emission):
+            return None, None, None, None, None, None
+        g = grad.to(dtype=th.float32).contiguous()
+        K = g.shape[0]
+        grad_field = th.empty_like(g) if want_field else None                  # (every cell is written by the call)
+        grad_emission = th.empty_like(g) if want_emission else None
+        _lib.check(_lib.lib.die_signal_step_backward(r.W, r.H, _ptr(r.occupied), K, _ptr(g), r.W * r.H, _ptr(grad_field), _ptr(grad_emission),
+                                                     r.W * r.H, deposit, sigma, decay, stream_ptr(g.device)), 'die_signal_step_backward')
+        return grad_field, grad_emission, None, None, None, None
+
+
+def signal_step(field: th.Tensor, emission: th.Tensor, record: SignalRecord, *, deposit: float, sigma: float, decay: float) -> th.Tensor:
+    """The signal field's update with a `grad_fn`: `field` and `emission` (K, W, H) float32 on the record's device, 1 <= K <= 8 ->
+    `(1 - decay) * gaussian(field + occupied * deposit * emission, sigma, mode='wrap', truncate=4)`, die_signal_step's launch and
+    bits on the record's standing plane, into storage the graph owns.  The backward is ONE die_signal_step_backward launch, which
+    produces only the gradients asked for: grad_field = (1 - decay) * gaussian(grad) — the same sweep — and grad_emission =
+    occupied ? deposit * grad_field : +0.  A sweep and a mask: no atomics, bit-reproducible."""
+    if not isinstance(record, SignalRecord):
+        raise TypeError('record: a SignalRecord (die_amd.functional.signal_record)')
+    dev = record.occupied.device
+    for name, t in (('field', field), ('emission', emission)):
+        if not isinstance(t, th.Tensor) or t.dtype != th.float32 or t.dim() != 3 or tuple(t.shape[1:]) != (record.W, record.H) or \
+                not 1 <= t.shape[0] <= _lib.SIGNAL_MAX_CHANNELS or t.device != dev:
+            raise ValueError(f'{name}: a float32 tensor of shape (K, {record.W}, {record.H}) with K in 1..{_lib.SIGNAL_MAX_CHANNELS} on {dev}')
+    if field.shape[0] != emission.shape[0]:
+        raise ValueError(f'field has {field.shape[0]} planes, emission {emission.shape[0]}')
+    return _SignalStep.apply(field.contiguous(), emission.contiguous(), record, float(deposit), float(sigma), float(decay))
 
 
 def gather_scale_batch(sense: th.Tensor, population) -> th.Tensor:

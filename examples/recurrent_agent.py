@@ -11,6 +11,12 @@ stack (die_conv2d_wide_backward) and the expand onto the field (die_memory_plane
 `--detach-every K` cuts the memory's gradient every K steps inside a window (K = 1: no gradient through memory at all).  The loss
 is the mean squared error of (dx, dy) against the teacher's over the alive agents and the window's steps, in units of scale².
 
+`--signal-channels K` gives the student a signal field of K planes as well (`NeuralAutomataAgent(signal_channels=K)`, with or
+without memory): every step is then `signalling_action(obs, signals, memory)`, the field blank at the window's start and
+`signals_next` handed from step to step, so that `loss.backward()` also runs through the field's update of every step
+(die_signal_step_backward: what an agent wrote is read, diffused and decayed, by whoever comes by later in the window);
+`--detach-every` cuts the field's gradient with the memory's.  Stand-alone only: with `--replicas` it is refused, populations come next.
+
 `--memory-channels 0` trains the same stack without memory through `model.forward_device` and `functional.gather_scale`: the
 baseline.  With M > 0 the baseline is trained as well, on a world seeded alike, and both final losses are printed — side by side,
 with no claim about which is smaller.  `--time` prints optimiser steps per second.
@@ -39,48 +45,57 @@ from die_amd.batch import BatchedEnv, BatchedNeuralAutomataAgent, BatchedPhysaru
 SCALE, DEPOSIT = 0.01, 2.0
 
 
-def make_student(memory_channels, hidden_channels=8, seed=0):
+def make_student(memory_channels, hidden_channels=8, seed=0, signal_channels=0):
     torch.manual_seed(seed)
     student = NeuralAutomataAgent(kernel_sizes=[3, 3], scale=SCALE, deposit=DEPOSIT, hidden_channels=hidden_channels, hidden_activation='tanh',
-                                  memory_channels=memory_channels)
+                                  memory_channels=memory_channels, signal_channels=signal_channels)
     student.model.init_weights()
     return student
 
 
-def student_step(student, obs, memory):
-    """One step of the student on `obs`: ((3, N) action with a `grad_fn`, the memory to hand on — None without memory channels)."""
+def student_step(student, obs, state):
+    """One step of the student on `obs`: ((3, N) action with a `grad_fn`, the state to hand on).  `state` = (signals, memory): the
+    field and the memory of the step before, each None at a window's start and where the student has no such channels."""
+    signals, memory = state
+    if student.signal_channels:
+        action, signals, memory = student.signalling_action(obs, signals, memory)
+        return action, (signals, memory)
     if student.memory_channels:
-        return student.recurrent_action(obs, memory)
+        action, memory = student.recurrent_action(obs, memory)
+        return action, (None, memory)
     medium = obs[1]
     medium.sensed()
     planes = torch.stack([medium.sel(c).float() for c in student.obs_channels])
-    return functional.gather_scale(student.model.forward_device(planes), obs, student.action_coefs), None
+    return functional.gather_scale(student.model.forward_device(planes), obs, student.action_coefs), (None, None)
 
 
-def window_loss(student, teacher, env, obs, memory, unroll, detach_every):
+def window_loss(student, teacher, env, obs, state, unroll, detach_every):
     """`unroll` env steps driven by the teacher, the student unrolled beside it: (loss, the observation after the window, the
-    memory after the window)."""
+    state — (signals, memory) — after the window)."""
     loss = 0.
     for t in range(unroll):
-        if memory is not None and detach_every and t % detach_every == 0:
-            memory = memory.detach()
+        if detach_every and t % detach_every == 0:
+            state = tuple(None if v is None else v.detach() for v in state)
         agents = obs[0]
         action = teacher.forward(obs)
         target = action.data[:2, :agents.N]
         alive = agents.alive[:agents.N] > 0
-        got, memory = student_step(student, obs, memory)
+        got, state = student_step(student, obs, state)
         loss = loss + (((got[:2] - target) / SCALE)[:, alive] ** 2).mean()
         obs = env.step(action)[0]
-    return loss / unroll, obs, memory
+    return loss / unroll, obs, state
 
 
-def train(size, memory_channels, unroll, detach_every, steps, lr=1e-2, seed=0, inertia=0.9, hidden_channels=8, warm=4, log=print, timed=False):
+def train(size, memory_channels, unroll, detach_every, steps, lr=1e-2, seed=0, inertia=0.9, hidden_channels=8, warm=4, log=print, timed=False,
+          signal_channels=0):
     """`steps` Adam steps, each on one episode: the world reset to its seed, a fresh teacher, `warm` steps of the teacher alone (so that
-    there are trails to follow), then the window of `unroll` steps with the student beside it, its memory blank at the window's start.
+    there are trails to follow), then the window of `unroll` steps with the student beside it, its memory (and its signal field, with
+    `signal_channels` > 0) blank at the window's start.
     Returns (the student, the list of episode losses)."""
     env = Env((size, size), Dynamics(food_infinite=True, rate_decay_chem=0.025, diffuse_sigma=.8), seed=seed)
-    student = make_student(memory_channels, hidden_channels, seed)
+    student = make_student(memory_channels, hidden_channels, seed, signal_channels)
     opt = torch.optim.Adam(student.model.parameters(), lr=lr)
+    tag = f'M={memory_channels}' + (f' K={signal_channels}' if signal_channels else '')
     losses, t0 = [], None
     warmup = max(1, steps // 10)
     for it in range(steps):
@@ -93,16 +108,17 @@ def train(size, memory_channels, unroll, detach_every, steps, lr=1e-2, seed=0, i
         for _ in range(warm):
             obs = env.step(teacher.forward(obs))[0]
         student.reset_memory()
-        loss, obs, _ = window_loss(student, teacher, env, obs, None, unroll, detach_every)
+        student.reset_signals()
+        loss, obs, _ = window_loss(student, teacher, env, obs, (None, None), unroll, detach_every)
         opt.zero_grad()
         loss.backward()
         opt.step()
         losses.append(float(loss.detach()))
         if it % 10 == 0 or it == steps - 1:
-            log(f'M={memory_channels} step {it:5d}: loss {losses[-1]:.6f}')
+            log(f'{tag} step {it:5d}: loss {losses[-1]:.6f}')
     if t0 is not None and steps > warmup:
         torch.cuda.synchronize()
-        log(f'M={memory_channels}, T={unroll}: {(steps - warmup) / (time.perf_counter() - t0):.2f} optimiser steps/s over {steps - warmup} steps')
+        log(f'{tag}, T={unroll}: {(steps - warmup) / (time.perf_counter() - t0):.2f} optimiser steps/s over {steps - warmup} steps')
     return student, losses
 
 
@@ -171,6 +187,8 @@ def main():
     p.add_argument('--size', type=int, default=96)
     p.add_argument('--memory-channels', type=int, default=2, metavar='M', help='values every agent carries between steps, 1..8; 0: the '
                                                                                 'memoryless baseline alone')
+    p.add_argument('--signal-channels', type=int, default=0, metavar='K', help='planes of the signal field the agents write and read, 1..8 '
+                                                                               '(0: none); stand-alone only')
     p.add_argument('--unroll', type=int, default=8, metavar='T', help='env steps per optimiser step')
     p.add_argument('--detach-every', type=int, default=0, metavar='K', help="cut the memory's gradient every K steps of a window (0: never)")
     p.add_argument('--steps', type=int, default=200, help='optimiser steps')
@@ -185,18 +203,21 @@ def main():
     args = p.parse_args()
     if args.unroll < 1 or args.steps < 1 or args.detach_every < 0:
         raise SystemExit('--unroll and --steps are at least 1, --detach-every at least 0')
+    if args.replicas and args.signal_channels:
+        raise SystemExit('--signal-channels trains a stand-alone student: populations (--replicas) come next')
     if args.replicas:
         _, losses = train_batched(args.size, args.memory_channels, args.unroll, args.detach_every, args.steps, args.lr, args.seed,
                                   args.hidden_channels, args.warm, args.replicas, args.students, timed=args.time)
         print(f'final mean loss per student, {args.memory_channels} memory channels on {args.replicas} worlds: {losses[-1]:.6f}')
         return
     final = {}
-    for M in dict.fromkeys((args.memory_channels, 0)):
+    for M, K in dict.fromkeys(((args.memory_channels, args.signal_channels), (args.memory_channels, 0), (0, 0))):
         _, losses = train(args.size, M, args.unroll, args.detach_every, args.steps, args.lr, args.seed, args.inertia, args.hidden_channels,
-                          args.warm, timed=args.time)
-        final[M] = losses[-1]
-    for M, loss in final.items():
-        print(f'final loss, {"memoryless baseline" if M == 0 else f"{M} memory channels"}: {loss:.6f}')
+                          args.warm, timed=args.time, signal_channels=K)
+        final[M, K] = losses[-1]
+    for (M, K), loss in final.items():
+        name = ' and '.join(([f'{M} memory channels'] if M else []) + ([f'{K} signal channels'] if K else [])) or 'memoryless baseline'
+        print(f'final loss, {name}: {loss:.6f}')
 
 
 if __name__ == '__main__':

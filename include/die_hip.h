@@ -1223,6 +1223,36 @@ int die_nca_wide_env_step_batch_signal(const die_medium* m, const die_agents* a,
                                        float* memory, float* memory_planes, int32_t with_stock, int32_t signal_channels,
                                        const float* field_in, float* field_out, float deposit, float sigma, float decay, void* stream);
 
+/* ---- The signal channels' adjoint: backpropagation through the field for a stand-alone agent (die_signal_grad.hip) ----------
+ * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
+ * die_signal_step is F' = (1 - decay) * G(F + occ * deposit * S) with G the periodic symmetric gaussian; on the torus G^T = G, so
+ *   grad_F = (1 - decay) * G(grad_F')                 the forward's own sweep on the gradient planes
+ *   grad_S_k[c] = occ[c] ? deposit * grad_F_k[c] : +0.0f     (one fp32 multiply of the value about to be stored)
+ *
+ * die_signal_cells — the record of one forward, taken after the standing plane is built (die_stock_plane at `epoch`): one launch,
+ *   occupied_out[c] = (standing[c] is occupied at epoch) ? 1 : 0     for all m->W * m->H cells, one byte each.
+ * EVERY byte is written (16-byte stores where both planes are 16-byte aligned, single bytes elsewhere and on the tail); nothing
+ * beyond W * H is touched.  A graph that keeps this plane survives the next standing build, every step, re-sort and reset of the
+ * field; it costs 1 byte per cell where a copy of the standing plane costs 8.  Checked before the launch (DIE_ERR_ARG): a null
+ * pointer, W or H < 1, epoch outside 1..DIE_OWNER_EPOCH_MAX, an output that overlaps the standing plane; a decomposed medium
+ * (m->gW > 0) is DIE_ERR_UNSUPPORTED.  Of `m` only W, H and gW are read.
+ *
+ * die_signal_step_backward — one launch for all K planes: the forward's sweep on grad_field_next (plane k at k * field_stride);
+ * at the store the value o goes to grad_field + k * field_stride and occupied[c] ? deposit * o : +0.0f to grad_emission +
+ * k * plane_stride.  Either output may be null (its store is skipped; the other gets the same bits), not both: the first link of
+ * a chain, whose incoming field is a constant, needs the emission gradient alone.  grad_field is bit for bit what die_signal_step
+ * writes for the field grad_field_next where nobody stands.  EVERY cell of every output plane is written; the words between two
+ * planes are left alone; the inputs are only read.  The row-marching kernel runs where H % 4 == 0, the radius is at most 4, every
+ * float pointer and stride is 16-byte aligned and `occupied` 4-byte aligned (a lane reads the mask of its 4 cells as one word);
+ * the LDS-tiled one elsewhere.  Checked before the launch (DIE_ERR_ARG): a null occupied or grad_field_next, both outputs null, W
+ * or H < 1, signal_channels outside 1..DIE_SIGNAL_MAX_CHANNELS, a sigma whose radius lies outside 1..8, decay outside [0, 1], a
+ * deposit that is not finite, field_stride < W * H, plane_stride < W * H with a grad_emission, an output that overlaps an input or
+ * the other output. */
+int die_signal_cells(const die_medium* m, const unsigned long long* standing, int32_t epoch, uint8_t* occupied_out, void* stream);
+int die_signal_step_backward(int32_t W, int32_t H, const uint8_t* occupied, int32_t signal_channels, const float* grad_field_next,
+                             int64_t field_stride, float* grad_field, float* grad_emission, int64_t plane_stride, float deposit,
+                             float sigma, float decay, void* stream);
+
 /* ---- The memory channels' adjoints: backpropagation through time for a stand-alone agent (die_memory_grad.hip) -------------
  * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
  * All records and memories are indexed by SLOT ID (agents->slot ? slot[n] : n), as die_gather_memory indexes the memory, so
