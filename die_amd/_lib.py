@@ -288,6 +288,15 @@ _SIGNATURES = {
     'die_nca_wide_backward_batch_memory': (C.c_int, [_P(Medium), _P(Batch), _P(NcaBatch), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                      C.c_int64, _P(NcaDropout), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                                      C.c_int32, C.c_void_p]),
+    'die_signal_cells_batch': (C.c_int, [_P(Medium), _P(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    'die_signal_step_backward_batch': (C.c_int, [C.c_int32, C.c_int32, _P(Batch), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    'die_nca_wide_sense_batch_store_signal': (C.c_int, [_P(Medium), _P(Batch), _P(NcaBatch), C.c_void_p, C.c_int64, C.c_void_p,
+                                                        _P(NcaDropout), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    'die_nca_wide_backward_batch_signal_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, _P(NcaBatch), C.c_int32, C.c_int32]),
+    'die_nca_wide_backward_batch_signal': (C.c_int, [_P(Medium), _P(Batch), _P(NcaBatch), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                     C.c_int64, _P(NcaDropout), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                                     C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     'die_nca_wide_sense_batch_store_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'die_nca_wide_sense_batch_store': (C.c_int, [_P(Medium), _P(Batch), _P(NcaBatch), C.c_void_p, C.c_int64, C.c_void_p, _P(NcaDropout),
                                                  C.c_void_p]),

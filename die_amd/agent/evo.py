@@ -802,7 +802,8 @@ class NeuralAutomataAgent(TorchAgent):
         (ValueError: it has `recurrent_action` / `differentiable_action`); with NotImplementedError the stock channel (its
         gradients are out of scope), a decomposed medium, fp16 fields and the boundaries 'reflect' / 'replicate'; with ValueError
         a `signals` or `memory` of the wrong shape, dtype or device, and a medium of another shape than the one `self.signals` is
-        bound to (until `reset_signals()`).  Populations keep refusing: `BatchedNeuralAutomataAgent` has no such call yet."""
+        bound to (until `reset_signals()`).  Populations have the batched twin, `BatchedNeuralAutomataAgent.signalling_action`: one
+        launch per kernel for all replicas, the same bits per replica."""
         from ..functional import gather_memory, gather_scale, memory_planes, memory_record, signal_record, signal_step
         K, M = self.signal_channels, self.memory_channels
         if not K:

@@ -1099,7 +1099,8 @@ class BatchedNeuralAutomataAgent(_Population):
     per-replica Dynamics, dropout_seed, `action=`, the stock channel, memory and both searchers take signals as they are, and so
     does `Dynamics(agents_born=True)` while M = 0: the field has no per-slot state.  Refused with NotImplementedError before any
     launch and before `dropout_step`, `memory` or `signals` change: `differentiable_sense`, `differentiable_action`,
-    `forward_device` and `recurrent_action`."""
+    `forward_device` and `recurrent_action`.  The call that has the adjoints is `signalling_action`: a step's forward half with a graph,
+    through the field, the stack, the memory and, with `env.differentiable_step`, the worlds."""
 
     _signal_channels = 0                            # (a population without signal channels has neither)
     _signals = _signals_next = None
@@ -1485,6 +1486,95 @@ class BatchedNeuralAutomataAgent(_Population):
             self.memory.copy_(memory_next)          # the population's own copy, not the graph's tensor
         return action, memory_next
 
+    def signalling_action(self, signals: Optional[torch.Tensor] = None, memory: Optional[torch.Tensor] = None,
+                          parameters: Optional[torch.Tensor] = None):
+        """`env.step`'s forward half for a population with signal channels, with a graph: `(action, signals_next, memory_next)`,
+        (3, R, Nmax), (R, K, W, H) and (R, M, Nmax) float32, each with a `grad_fn` (`memory_next` is None without memory) — the
+        batched twin of `NeuralAutomataAgent.signalling_action`.  `action[:, r, :n[r]]`, `signals_next[r]` and `memory_next[r, :,
+        :n[r]]` are bit for bit `replica_agent(r).signalling_action(obs_r, signals[r], memory[r, :, :n[r]])`; `action` is also what
+        `env.step(pop, action=buf)` records, `signals_next` what that step leaves in `pop.signals` and `memory_next` what it leaves
+        in `pop.memory`.
+
+        `signals`: None — `self.signals`, a constant of the graph — or an (R, K, W, H) float32 tensor on the env's device, of any
+        strides (inside, the fields lie (K, R, W, H); gradients come back in the shape given): the `signals_next` of the previous
+        call gives backpropagation through time through the medium, its `.detach()` truncates the gradient there, a leaf that
+        requires grad receives one.  `memory` and `parameters`: as in `recurrent_action` — the gradient of `parameters` is a
+        (C, P) tensor, row c the float64 sum over candidate c's E worlds rounded once.  With `env.chem_node` current the node is
+        the stack's chem plane: `env.differentiable_step(action)` between two calls unrolls through the worlds too.
+
+        In order: the standing planes (a buffer this population owns, one build for both records), `functional.signal_record_batch`
+        (ONE die_signal_cells_batch launch), with memory `functional.memory_record_batch` and `memory_planes_batch`, the wide stack
+        (die_nca_wide_sense_batch_store_signal: L launches, L + 1 with a mask), the read-out of planes 0..2
+        (die_gather_scale_batch), `functional.signal_step_batch` on planes 3 .. 3 + K - 1 and `functional.gather_memory_batch` on
+        planes 3 + K .. .  Backward: the scatters, ONE die_signal_step_backward_batch launch for all K·R planes, the stack's adjoint
+        (die_nca_wide_backward_batch_signal: 3 L with the first layer's input gradient, which an incoming field or memory with a
+        graph or a chem node asks for, else 3 L - 1) and the expand's gather.  Two gradients reach a `signals_next` that is handed
+        on — the next stack's input gradient and the next link's field gradient — and autograd sums them.  Records, planes and
+        every layer's output are kept by the graph, so `backward` may run after the worlds were stepped, reset or reseeded and
+        after `reset_signals()`.
+
+        The population is left as a step's forward leaves it: `self.signals` and `self.memory` hold copies of the values in their
+        own storage, `dropout_step` has advanced once if a `dropout_seed` is set.  Refused before any launch, and before
+        `dropout_step`, `signals` or `memory` change: a population without signal channels (ValueError: it has `recurrent_action`
+        / `forward_device`); with NotImplementedError the stock channel, large worlds (`per_replica`), fp16 fields, 'reflect' /
+        'replicate' and an unseeded `p_agent_dropout` > 0 in training mode; with ValueError a `signals` or `memory` of the wrong
+        shape, dtype, device or type, and a `memory` given to a population without memory channels."""
+        from .functional import gather_memory_batch, memory_planes_batch, memory_record_batch, signal_record_batch, signal_step_batch
+        from .functional import _standing_planes_batch
+        K, M, env = self._signal_channels, self._memory_channels, self.env
+        if not K:
+            raise ValueError('signalling_action: a population without signal channels (signal_channels=0) is differentiated by '
+                             'recurrent_action (memory channels) or forward_device / differentiable_action')
+        if self._stock_channel:
+            raise NotImplementedError('signalling_action: no gradients with the stock channel (with_stock_channel=True): its plane is '
+                                      'piecewise constant in the weights and the adjoint kernels do not take its kind')
+        if env.per_replica:
+            raise NotImplementedError('signalling_action: large worlds (per_replica) are not batched — a large world fills the GPU '
+                                      'through the stand-alone NeuralAutomataAgent.signalling_action (replica_agent(r))')
+        if env.dtype != torch.float32:
+            raise NotImplementedError(f'signalling_action: fp32 fields only (this batch holds {env.dtype})')
+        if self._arch['boundary'][0] not in ('circular', 'zeros'):
+            raise NotImplementedError(f"signalling_action: boundary={self._arch['boundary'][0]!r} in differentiable mode: 'circular' or "
+                                      f"'zeros' (step() takes all of {sorted(_lib.PAD_MODES)})")
+        self._check_step(env)
+        p = self.parameters if parameters is None else parameters
+        self._check_parameters(p)
+
+        def refuse(name, t, want):
+            got = (tuple(t.shape), t.dtype, str(t.device)) if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f'signalling_action: {name} must be a {want} float32 tensor on {env.device}, got {got}')
+
+        want = (self.R, K, env.W, env.H)
+        if signals is not None and (not isinstance(signals, torch.Tensor) or signals.dtype != torch.float32 or
+                                    tuple(signals.shape) != want or signals.device != env.device):
+            refuse('signals', signals, want)
+        if memory is not None and not M:
+            raise ValueError('signalling_action: memory given to a population without memory channels (memory_channels=0)')
+        want = (self.R, M, env.Nmax)
+        if memory is not None and (not isinstance(memory, torch.Tensor) or memory.dtype != torch.float32 or
+                                   tuple(memory.shape) != want or memory.device != env.device):
+            refuse('memory', memory, want)
+        # the fields as the launches read them, (K, R, W, H); the population's own are copied: they are written below, the graph's stay
+        field = self._signals.clone() if signals is None else signals.permute(1, 0, 2, 3).contiguous()
+        if M and memory is None:
+            memory = self.memory
+        standing = _standing_planes_batch(self)
+        cells = signal_record_batch(self, standing)
+        record = memory_record_batch(self, standing) if M else None
+        expanded = memory_planes_batch(memory, record) if M else None
+        sense = _BatchedSignalSense.apply(self, p, env.chem_node, field, expanded)
+        if self.dropout_seed is not None:
+            self.dropout_step += 1
+        action = _BatchedReadOut.apply(sense[:, :3], self)
+        deposit, sigma, decay = self.template.signal_constants
+        signals_next = signal_step_batch(field.permute(1, 0, 2, 3), sense[:, 3:3 + K], cells, deposit=deposit, sigma=sigma, decay=decay)
+        memory_next = gather_memory_batch(sense[:, 3 + K:], record) if M else None
+        with torch.no_grad():                       # the population's own copies, not the graph's tensors
+            self._signals.copy_(signals_next.permute(1, 0, 2, 3))
+            if M:
+                self.memory.copy_(memory_next)
+        return action, signals_next, memory_next
+
     def render(self, r: int) -> np.ndarray:
         """Replica r's last sense planes with the channel axis last: the stand-alone agent's `render()[0]`."""
         if self.env.per_replica:
@@ -1691,6 +1781,69 @@ class _BatchedMemorySense(torch.autograd.Function):
                                                                _ptr(ws), need, _ptr(grad_in), cin * W * H, _ptr(mem_planes), M,
                                                                stream_ptr(dev)), 'die_nca_wide_backward_batch_memory')
         return (None, out, grad_in[:, first - 1] if to_node else None, grad_in[:, first:].permute(1, 0, 2, 3) if to_memory else None)
+
+
+class _BatchedSignalSense(torch.autograd.Function):
+    """BatchedNeuralAutomataAgent.signalling_action's stack: `_BatchedMemorySense` for a wide stack whose first layer also reads
+    the K signal planes of every replica, ahead of the M memory planes (M = 0: `mem_planes` None), and whose last layer gives
+    3 + K + M planes — die_nca_wide_sense_batch_store_signal forward, die_nca_wide_backward_batch_signal backward.  `field` is
+    the (K, R, W, H) contiguous field as the launches read it.  Returns (R, 3 + K + M, W, H); the backward hands the (C, P)
+    gradient to `parameters`, the chem channel of the first layer's input gradient to the env's chem node, its K signal channels
+    to `field` and its M memory channels to the expand — views, in their (·, R, W, H) shapes."""
+
+    @staticmethod
+    def forward(ctx, pop, parameters, chem_node, field, mem_planes):
+        env = pop.env
+        R, W, H, L, dev, Cm = env.R, env.W, env.H, len(pop._layers), env.device, pop._channels
+        K, M = pop._signal_channels, pop._memory_channels
+        with_agents = pop._arch['with_agent_channel']
+        # as they are now: the worlds will be stepped (the claim plane only where the first layer reads it)
+        planes = [env.food.clone(), env.chem.clone()] + ([env.owner.clone()] if with_agents else [])
+        mem = [mem_planes.contiguous()] if M else []                 # (M, R, W, H): the expand's own storage, as the launch reads it
+        store = torch.empty((L, R, Cm, W, H), dtype=torch.float32, device=dev)
+        drop = pop._dropout()
+        masked = None if drop is None else torch.empty((R, Cm, W, H), dtype=torch.float32, device=dev)
+        ctx.epoch, ctx.fdt = env.epoch, _lib.DIE_F32
+        ctx.batch, ctx.pop, ctx.size, ctx.channels = env._batch_struct(), pop, (R, W, H, L), (K, M)
+        ctx.drop = None if drop is None else (drop.p, drop.seed, drop.seed_stride, drop.step)
+        m = _BatchedSense._medium(ctx, planes)
+        layers, nca = pop._nca_batch(parameters.data_ptr(), ctx.epoch)
+        _lib.check(_lib.lib.die_nca_wide_sense_batch_store_signal(C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), store.numel() * 4,
+                                                                  None if masked is None else _ptr(masked),
+                                                                  None if drop is None else C.byref(drop), _ptr(mem[0]) if M else None, M,
+                                                                  _ptr(field), K, stream_ptr(dev)), 'die_nca_wide_sense_batch_store_signal')
+        ctx.save_for_backward(parameters, store, field, *mem, *planes)
+        return (store[L - 1] if masked is None else masked)[:, :3 + K + M]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        (K, M), (R, W, H, L) = ctx.channels, ctx.size
+        parameters, store, field, *rest = ctx.saved_tensors
+        mem_planes, planes = (rest[0], rest[1:]) if M else (None, rest)
+        pop, dev = ctx.pop, store.device
+        g = grad.to(dtype=torch.float32).contiguous()               # (R, 3 + K + M, W, H)
+        m = _BatchedSense._medium(ctx, planes)
+        layers, nca = pop._nca_batch(parameters.data_ptr(), ctx.epoch)
+        need = int(_lib.lib.die_nca_wide_backward_batch_signal_workspace_bytes(W, H, R, C.byref(nca), M, K))
+        if need < 0:
+            raise ValueError('a stack or shape die_nca_wide_backward_batch_signal does not take')
+        ws = torch.empty((need // 4,), dtype=torch.float32, device=dev)
+        out = torch.empty_like(parameters)                          # (C, P): every element is written (the layers tile a row)
+        drop = None if ctx.drop is None else _lib.NcaDropout(*ctx.drop, 0)
+        # the first layer's inputs are ([agents,] food, chem, signal_0 .., memory_0 ..): chem is the env's node, the signal planes the
+        # incoming field, the memory planes the expand's output; with none of them asking for a gradient no input gradient is computed
+        to_node, to_field, to_memory = ctx.needs_input_grad[2:5]
+        first = len(planes)                                         # the signal planes' first channel
+        cin = first + K + M
+        grad_in = torch.empty((R, cin, W, H), dtype=torch.float32, device=dev) if to_node or to_field or to_memory else None
+        _lib.check(_lib.lib.die_nca_wide_backward_batch_signal(C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), _ptr(g),
+                                                               (3 + K + M) * W * H, _ptr(out), pop.P, None if drop is None else C.byref(drop),
+                                                               _ptr(ws), need, _ptr(grad_in), cin * W * H, _ptr(mem_planes), M, _ptr(field), K,
+                                                               stream_ptr(dev)), 'die_nca_wide_backward_batch_signal')
+        return (None, out, grad_in[:, first - 1] if to_node else None,
+                grad_in[:, first:first + K].permute(1, 0, 2, 3) if to_field else None,
+                grad_in[:, first + K:].permute(1, 0, 2, 3) if to_memory else None)
 
 
 class _BatchedRecurrentReadOut(torch.autograd.Function):

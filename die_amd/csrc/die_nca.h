@@ -78,7 +78,7 @@ int die_nca_field_check(const die_medium* m, const die_nca_batch* nca, const cha
 int die_nca_pad_adjoint_check(int32_t padding_mode, const char* who);
 // what the *_sense_batch_store calls check alike, in their order: the arguments, the die_batch, the stack, the field
 int die_nca_store_check(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store, die_nca_kind kind, const char* who,
-                        int memory = 0);
+                        int memory = 0, int signals = 0);
 
 // ---- what the batched step (die_env.hip: nca_env_step_batch) calls after die_nca_stack_check, in its order ----
 // every replica's stock plane at `epoch` (die_stock.hip)

@@ -431,11 +431,11 @@ int die_nca_pad_adjoint_check(int32_t padding_mode, const char* who) {
 }
 
 int die_nca_store_check(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store, die_nca_kind kind, const char* who,
-                        int memory) {
+                        int memory, int signals) {
     DIE_REQUIRE(m && b && nca && store, "%s: null argument", who);
     int rc = die_nca_batch_shape_check(m, b, who);
     if (rc != DIE_OK) return rc;
-    rc = die_nca_stack_check(kind, nca, m->W, m->H, b->replicas, who, false, false, memory);
+    rc = die_nca_stack_check(kind, nca, m->W, m->H, b->replicas, who, false, false, memory, signals);
     if (rc != DIE_OK) return rc;
     return die_nca_field_check(m, nca, who);
 }

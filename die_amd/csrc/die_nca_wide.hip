@@ -429,3 +429,41 @@ extern "C" int die_nca_wide_sense_batch_store_memory(const die_medium* m, const 
     return wide_sense_batch(m, b, nca, store, false, drop ? masked : nullptr, &sense, &rep, drop ? &dw : nullptr, stream, nullptr,
                             mem_planes, memory_channels);
 }
+
+// ---- the same for a population whose agents also write a signal field (the forward of die_nca_wide_backward_batch_signal) --------
+// Layer 0 reads ([agents,] food, chem, signal_0 .., memory_0 ..), the last layer gives 3 + K + M planes; M = 0 with null mem_planes:
+// no memory.  The launches are die_nca_wide_sense_batch_store's; the K planes cost what M more memory planes would (above).
+extern "C" int die_nca_wide_sense_batch_store_signal(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* store,
+                                                     int64_t store_bytes, float* masked, const die_nca_dropout* drop, const float* mem_planes,
+                                                     int32_t memory_channels, const float* signal_planes, int32_t signal_channels,
+                                                     void* stream) {
+    const char* who = "die_nca_wide_sense_batch_store_signal";
+    DIE_REQUIRE(m && b && nca && store && signal_planes, "%s: null argument", who);
+    DIE_REQUIRE(memory_channels >= 0 && memory_channels <= DIE_MEMORY_MAX_CHANNELS && (memory_channels > 0) == (mem_planes != nullptr),
+                "%s: %d memory channels outside 0..%d, or not 0 exactly where the memory planes are null", who, memory_channels,
+                DIE_MEMORY_MAX_CHANNELS);
+    DIE_REQUIRE(signal_channels >= 1 && signal_channels <= DIE_SIGNAL_MAX_CHANNELS, "%s: %d signal channels outside 1..%d", who,
+                signal_channels, DIE_SIGNAL_MAX_CHANNELS);
+    int rc = die_nca_store_check(m, b, nca, store, DIE_NCA_WIDE, who, memory_channels, signal_channels);
+    if (rc != DIE_OK) return rc;
+    const int64_t need = die_nca_wide_sense_batch_store_bytes(m->W, m->H, b->replicas, nca->n_layers, die_nca_max_channels(nca));
+    DIE_REQUIRE(store_bytes >= need, "%s: store too small (%lld < %lld)", who, (long long)store_bytes, (long long)need);
+    DropWords dw;
+    if (drop) {
+        DIE_REQUIRE(masked && masked != store, "%s: a dropout mask needs planes of its own for the masked values", who);
+        rc = die_dropout_words(drop, &dw, who);
+        if (rc != DIE_OK) return rc;
+    }
+    // the memory and the signal planes are read by layer 0 while the store (and the masked planes) are written
+    const int64_t cells = (int64_t)m->W * m->H, masked_bytes = (int64_t)b->replicas * die_nca_max_channels(nca) * cells * 4;
+    auto planes_bytes = [&](int n) { return (((int64_t)n * b->replicas - 1) * b->plane_stride + cells) * 4; };
+    auto overlaps = [&](const void* p, int64_t bytes) {
+        return die_ranges_overlap(p, bytes, store, need) || (drop && die_ranges_overlap(p, bytes, masked, masked_bytes));
+    };
+    DIE_REQUIRE(!overlaps(mem_planes, planes_bytes(memory_channels)), "%s: the memory planes overlap the store or the masked planes", who);
+    DIE_REQUIRE(!overlaps(signal_planes, planes_bytes(signal_channels)), "%s: the signal planes overlap the store or the masked planes", who);
+    const float* sense;
+    int64_t rep;
+    return wide_sense_batch(m, b, nca, store, false, drop ? masked : nullptr, &sense, &rep, drop ? &dw : nullptr, stream, nullptr,
+                            mem_planes, memory_channels, signal_planes, signal_channels);
+}

@@ -489,14 +489,14 @@ static int64_t wide_bwd_max_weights(const die_nca_batch* nca) {
 }
 
 // the shapes the byte query answers for (the call itself checks everything again, with messages)
-// (memory: layer 0 reads that many planes more, the last layer gives 3 + memory)
-static bool wide_bwd_stack_ok(int32_t W, int32_t H, int32_t replicas, const die_nca_batch* nca, int memory = 0) {
+// (memory, signals: layer 0 reads that many planes more, the last layer gives 3 + signals + memory)
+static bool wide_bwd_stack_ok(int32_t W, int32_t H, int32_t replicas, const die_nca_batch* nca, int memory = 0, int signals = 0) {
     if (W < 1 || H < 1 || replicas < 1 || replicas > DIE_MAX_REPLICAS || (W + NCA_TX - 1) / NCA_TX > 65535) return false;
     if (!nca || !nca->layers || nca->n_layers < 1 || nca->n_layers > DIE_NCA_MAX_LAYERS) return false;
     if (nca->with_agent_channel != 0 && nca->with_agent_channel != 1) return false;
     if (nca->padding_mode != DIE_PAD_CIRCULAR && nca->padding_mode != DIE_PAD_ZEROS) return false;
     if (nca->episodes < 0 || replicas % (nca->episodes > 1 ? nca->episodes : 1) != 0) return false;
-    int cin = 2 + nca->with_agent_channel + memory;
+    int cin = 2 + nca->with_agent_channel + signals + memory;
     for (int l = 0; l < nca->n_layers; ++l) {
         const die_nca_layer& L = nca->layers[l];
         if (!wide_shape_ok(W, H, L.cin, L.cout, L.k) || L.cin != cin) return false;
@@ -504,11 +504,11 @@ static bool wide_bwd_stack_ok(int32_t W, int32_t H, int32_t replicas, const die_
         if (l == nca->n_layers - 1 && L.reserved != DIE_NCA_ACT_TANH) return false;
         cin = L.cout;
     }
-    return cin == 3 + memory;
+    return cin == 3 + signals + memory;
 }
 
-static int64_t wide_bwd_workspace_bytes(int32_t W, int32_t H, int32_t replicas, const die_nca_batch* nca, int memory) {
-    if (!wide_bwd_stack_ok(W, H, replicas, nca, memory)) return -1;
+static int64_t wide_bwd_workspace_bytes(int32_t W, int32_t H, int32_t replicas, const die_nca_batch* nca, int memory, int signals = 0) {
+    if (!wide_bwd_stack_ok(W, H, replicas, nca, memory, signals)) return -1;
     return ((int64_t)replicas * die_nca_tiles(W, H) * wide_bwd_max_weights(nca) +
             (int64_t)die_nca_gin_sets(nca->n_layers) * replicas * die_nca_max_channels(nca) * (int64_t)W * H) * (int64_t)sizeof(float);
 }
@@ -523,21 +523,30 @@ extern "C" int64_t die_nca_wide_backward_batch_memory_workspace_bytes(int32_t W,
     return wide_bwd_workspace_bytes(W, H, replicas, nca, memory_channels);
 }
 
-// die_nca_wide_backward_batch (memory = 0, mem_planes null) and die_nca_wide_backward_batch_memory: one body, the same launches
+extern "C" int64_t die_nca_wide_backward_batch_signal_workspace_bytes(int32_t W, int32_t H, int32_t replicas, const die_nca_batch* nca,
+                                                                      int32_t memory_channels, int32_t signal_channels) {
+    if (memory_channels < 0 || memory_channels > DIE_MEMORY_MAX_CHANNELS || signal_channels < 1 || signal_channels > DIE_SIGNAL_MAX_CHANNELS)
+        return -1;
+    return wide_bwd_workspace_bytes(W, H, replicas, nca, memory_channels, signal_channels);
+}
+
+// die_nca_wide_backward_batch (memory = 0, mem_planes null), die_nca_wide_backward_batch_memory and die_nca_wide_backward_batch_signal
+// (signals > 0 with signal_planes): one body, the same launches
 static int wide_backward_batch(const char* who, const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store,
                                const float* grad_sense, int64_t sense_stride, float* grad, int64_t grad_stride,
                                const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, float* grad_in,
-                               int64_t grad_in_stride, const float* mem_planes, int memory, void* stream) {
+                               int64_t grad_in_stride, const float* mem_planes, int memory, void* stream,
+                               const float* signal_planes = nullptr, int signals = 0) {
     int rc = die_nca_batch_shape_check(m, b, who);
     if (rc != DIE_OK) return rc;
-    rc = die_nca_stack_check(DIE_NCA_WIDE, nca, m->W, m->H, b->replicas, who, false, false, memory);
+    rc = die_nca_stack_check(DIE_NCA_WIDE, nca, m->W, m->H, b->replicas, who, false, false, memory, signals);
     if (rc == DIE_OK) rc = die_nca_pad_adjoint_check(nca->padding_mode, who);
     if (rc == DIE_OK) rc = die_nca_field_check(m, nca, who);
     if (rc != DIE_OK) return rc;
     const int Cmax = die_nca_max_channels(nca);
     const int64_t cells = (int64_t)m->W * m->H, rep_planes = Cmax * cells;
-    const int n_sense = 3 + memory;                          // planes per replica at the top of the stack
-    if (memory) DIE_REQUIRE(sense_stride >= n_sense * cells, "%s: sense_stride %lld below %d planes", who, (long long)sense_stride, n_sense);
+    const int n_sense = 3 + signals + memory;                // planes per replica at the top of the stack
+    if (memory || signals) DIE_REQUIRE(sense_stride >= n_sense * cells, "%s: sense_stride %lld below %d planes", who, (long long)sense_stride, n_sense);
     else DIE_REQUIRE(sense_stride >= 3 * cells, "%s: sense_stride %lld below three planes", who, (long long)sense_stride);
     int64_t P = 0;
     for (int l = 0; l < nca->n_layers; ++l) {
@@ -546,7 +555,7 @@ static int wide_backward_batch(const char* who, const die_medium* m, const die_b
         DIE_REQUIRE(grad != L.weights, "%s: grad is layer %d's weights", who, l);
     }
     DIE_REQUIRE(grad_stride >= P, "%s: grad_stride %lld below a row of %lld weights", who, (long long)grad_stride, (long long)P);
-    const int64_t need = wide_bwd_workspace_bytes(m->W, m->H, b->replicas, nca, memory);
+    const int64_t need = wide_bwd_workspace_bytes(m->W, m->H, b->replicas, nca, memory, signals);
     DIE_REQUIRE(need > 0, "%s: a shape the call does not take", who);
     DIE_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%lld < %lld)", who, (long long)workspace_bytes, (long long)need);
     // the input-gradient kernel stores four cells of a row at once where H % 4 == 0, into the workspace's planes too
@@ -566,7 +575,8 @@ static int wide_backward_batch(const char* who, const die_medium* m, const die_b
                         !overlaps(grad, ((int64_t)(R / E - 1) * grad_stride + P) * 4) && !overlaps(workspace, need) &&
                         !overlaps(m->owner, ((int64_t)(R - 1) * b->plane_stride + cells) * 8) && !overlaps(m->food, fbytes) &&
                         !overlaps(m->chem, fbytes) &&
-                        !overlaps(mem_planes, (((int64_t)memory * R - 1) * b->plane_stride + cells) * 4),
+                        !overlaps(mem_planes, (((int64_t)memory * R - 1) * b->plane_stride + cells) * 4) &&
+                        !overlaps(signal_planes, (((int64_t)signals * R - 1) * b->plane_stride + cells) * 4),
                     "%s: grad_in aliases another buffer of the call", who);
         for (int l = 0; l < L; ++l) {
             const die_nca_layer& Ly = nca->layers[l];
@@ -592,7 +602,7 @@ static int wide_backward_batch(const char* who, const die_medium* m, const die_b
         off -= nw;
         WideBwdBatchArgs a = {};
         if (l == 0) {
-            die_nca_layer0_planes(m, b, nca, mem_planes, memory, nullptr, a.in, a.kind, &a.rep_in);
+            die_nca_layer0_planes(m, b, nca, mem_planes, memory, nullptr, a.in, a.kind, &a.rep_in, signal_planes, signals);
         } else {
             for (int c = 0; c < Ly.cin; ++c) { a.in[c] = store + (int64_t)(l - 1) * R * rep_planes + c * cells; a.kind[c] = DIE_PLANE_F32; }
             a.rep_in = rep_planes;
@@ -640,4 +650,20 @@ extern "C" int die_nca_wide_backward_batch_memory(const die_medium* m, const die
                 memory_channels, DIE_MEMORY_MAX_CHANNELS);
     return wide_backward_batch(who, m, b, nca, store, grad_sense, sense_stride, grad, grad_stride, drop, workspace, workspace_bytes, grad_in,
                                grad_in_stride, mem_planes, memory_channels, stream);
+}
+
+extern "C" int die_nca_wide_backward_batch_signal(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store,
+                                                  const float* grad_sense, int64_t sense_stride, float* grad, int64_t grad_stride,
+                                                  const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, float* grad_in,
+                                                  int64_t grad_in_stride, const float* mem_planes, int32_t memory_channels,
+                                                  const float* signal_planes, int32_t signal_channels, void* stream) {
+    const char* who = "die_nca_wide_backward_batch_signal";
+    DIE_REQUIRE(m && b && nca && store && grad_sense && grad && workspace && signal_planes, "%s: null argument", who);
+    DIE_REQUIRE(memory_channels >= 0 && memory_channels <= DIE_MEMORY_MAX_CHANNELS && (memory_channels > 0) == (mem_planes != nullptr),
+                "%s: %d memory channels outside 0..%d, or not 0 exactly where the memory planes are null", who, memory_channels,
+                DIE_MEMORY_MAX_CHANNELS);
+    DIE_REQUIRE(signal_channels >= 1 && signal_channels <= DIE_SIGNAL_MAX_CHANNELS, "%s: %d signal channels outside 1..%d", who,
+                signal_channels, DIE_SIGNAL_MAX_CHANNELS);
+    return wide_backward_batch(who, m, b, nca, store, grad_sense, sense_stride, grad, grad_stride, drop, workspace, workspace_bytes, grad_in,
+                               grad_in_stride, mem_planes, memory_channels, stream, signal_planes, signal_channels);
 }

@@ -13,6 +13,8 @@
 //                           unroll holds 1 byte per cell and step instead of the standing plane's 8, and the backward sweep reads 1.
 //                           16 cells per thread: 128 bytes of words in, one 16-byte store out; the tail and an unaligned plane go
 //                           byte by byte.  Plain vector loads and stores.
+//   k_signal_cells_batch    the same body for every replica of a die_batch in ONE launch, the replica in blockIdx.y (as the batched
+//                           memory kernels): replica r's words b->plane_stride on, its bytes occupied_stride on.
 //   k_signal_back_rows<R>   the row-marching sweep with the plane read as it is (an empty DIF_EMIT) and a DIF_STORE that writes the 4
 //   k_signal_back_tile<R>   finished values o to grad_field and occ ? deposit * o : +0 to grad_emission (the LDS-tiled sweep: cell by
 //                           cell, a plain DIF_LOAD).  Either output may be absent.  One launch for all K planes of all replicas,
@@ -31,6 +33,29 @@
 template <bool VEC>
 __global__ __launch_bounds__(DIE_BLOCK) void k_signal_cells(const unsigned long long* __restrict__ standing, int64_t cells, int epoch,
                                                             uint8_t* __restrict__ out) {
+    const int64_t groups = VEC ? cells / CELLS_PER_THREAD : 0;                  // whole 16-byte groups, then the tail byte by byte
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x, t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int64_t g = t0; g < groups; g += stride) {
+        const int64_t base = g * CELLS_PER_THREAD;
+        uint32_t w[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const ulonglong2 c01 = *(const ulonglong2*)(standing + base + 4 * q), c23 = *(const ulonglong2*)(standing + base + 4 * q + 2);
+            w[q] = (die_claim_occupied(c01.x, epoch) ? 1u : 0u) | (die_claim_occupied(c01.y, epoch) ? 1u << 8 : 0u) |
+                   (die_claim_occupied(c23.x, epoch) ? 1u << 16 : 0u) | (die_claim_occupied(c23.y, epoch) ? 1u << 24 : 0u);
+        }
+        *(uint4*)(out + base) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    for (int64_t c = groups * CELLS_PER_THREAD + t0; c < cells; c += stride) out[c] = die_claim_occupied(standing[c], epoch) ? 1 : 0;
+}
+
+// the record of every replica: replica r = blockIdx.y, its standing plane standing_rep words on, its byte plane out_rep bytes on; from
+// there k_signal_cells' statements (a kernel of its own: as a shared inlined body they moved k_signal_cells' registers)
+template <bool VEC>
+__global__ __launch_bounds__(DIE_BLOCK) void k_signal_cells_batch(const unsigned long long* __restrict__ standing, int64_t standing_rep,
+                                                                  int64_t cells, int epoch, uint8_t* __restrict__ out, int64_t out_rep) {
+    standing += standing_rep * blockIdx.y;
+    out += out_rep * blockIdx.y;
     const int64_t groups = VEC ? cells / CELLS_PER_THREAD : 0;                  // whole 16-byte groups, then the tail byte by byte
     const int64_t stride = (int64_t)gridDim.x * blockDim.x, t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     for (int64_t g = t0; g < groups; g += stride) {
@@ -198,6 +223,31 @@ extern "C" int die_signal_cells(const die_medium* m, const unsigned long long* s
     return DIE_OK;
 }
 
+extern "C" int die_signal_cells_batch(const die_medium* m, const die_batch* b, const unsigned long long* standing, int32_t epoch,
+                                      uint8_t* occupied_out, int64_t occupied_stride, void* stream) {
+    const char* who = "die_signal_cells_batch";
+    DIE_REQUIRE(m && b && standing && occupied_out, "%s: null argument", who);
+    int rc = die_signal_check(m, 1, epoch, 0.f, 0.5f, 0.f, who);                // (size, a decomposed medium, the epoch: die_signal_cells' rules)
+    if (rc != DIE_OK) return rc;
+    const int64_t cells = (int64_t)m->W * m->H;
+    rc = die_batch_check(b, cells, who);
+    if (rc != DIE_OK) return rc;
+    const int64_t R = b->replicas;
+    DIE_REQUIRE(occupied_stride >= cells, "%s: occupied_stride %lld smaller than a plane (%lld cells)", who, (long long)occupied_stride,
+                (long long)cells);
+    DIE_REQUIRE(!die_ranges_overlap(occupied_out, (R - 1) * occupied_stride + cells, standing, ((R - 1) * b->plane_stride + cells) * 8),
+                "%s: occupied_out overlaps the standing planes", who);
+    // 16-byte accesses: every replica's words and bytes on a 16-byte boundary
+    const bool vec = aligned16(standing) && aligned16(occupied_out) && (b->plane_stride & 1) == 0 && (occupied_stride & 15) == 0;
+    const int64_t threads = vec ? (cells + CELLS_PER_THREAD - 1) / CELLS_PER_THREAD : cells;
+    const int64_t g = (threads + DIE_BLOCK - 1) / DIE_BLOCK;
+    const dim3 grid((unsigned)(g < 8192 ? g : 8192), (unsigned)R);
+    if (vec) k_signal_cells_batch<true><<<grid, DIE_BLOCK, 0, (hipStream_t)stream>>>(standing, b->plane_stride, cells, epoch, occupied_out, occupied_stride);
+    else k_signal_cells_batch<false><<<grid, DIE_BLOCK, 0, (hipStream_t)stream>>>(standing, b->plane_stride, cells, epoch, occupied_out, occupied_stride);
+    DIE_CHECK_LAUNCH(who);
+    return DIE_OK;
+}
+
 extern "C" int die_signal_step_backward(int32_t W, int32_t H, const uint8_t* occupied, int32_t signal_channels, const float* grad_field_next,
                                         int64_t field_stride, float* grad_field, float* grad_emission, int64_t plane_stride, float deposit,
                                         float sigma, float decay, void* stream) {
@@ -220,4 +270,42 @@ extern "C" int die_signal_step_backward(int32_t W, int32_t H, const uint8_t* occ
     DIE_REQUIRE(!die_ranges_overlap(grad_emission, em_bytes, grad_field, field_bytes), "%s: grad_emission overlaps grad_field", who);
     return die_signal_backward_launch(W, H, 1, signal_channels, occupied, 0, grad_field_next, grad_field, field_stride, grad_emission,
                                       grad_emission ? plane_stride : 0, 0, deposit, sigma, decay, stream, who);
+}
+
+extern "C" int die_signal_step_backward_batch(int32_t W, int32_t H, const die_batch* b, const uint8_t* occupied, int64_t occupied_stride,
+                                              int32_t signal_channels, const float* grad_field_next, float* grad_field, float* grad_emission,
+                                              int64_t plane_stride, int64_t replica_stride, float deposit, float sigma, float decay,
+                                              void* stream) {
+    const char* who = "die_signal_step_backward_batch";
+    DIE_REQUIRE(b && occupied && grad_field_next, "%s: null argument", who);
+    DIE_REQUIRE(grad_field || grad_emission, "%s: null argument (grad_field and grad_emission are both absent)", who);
+    die_medium m = {};
+    m.W = W; m.H = H;
+    int rc = die_signal_check(&m, signal_channels, 1, deposit, sigma, decay, who);            // (the forward's rules for K and the constants)
+    if (rc != DIE_OK) return rc;
+    const int64_t cells = (int64_t)W * H, K = signal_channels;
+    rc = die_batch_check(b, cells, who);
+    if (rc != DIE_OK) return rc;
+    const int64_t R = b->replicas;
+    DIE_REQUIRE(occupied_stride >= cells, "%s: occupied_stride %lld smaller than a plane (%lld cells)", who, (long long)occupied_stride,
+                (long long)cells);
+    if (grad_emission) {
+        DIE_REQUIRE(plane_stride >= cells, "%s: plane_stride %lld smaller than a plane (%lld cells)", who, (long long)plane_stride, (long long)cells);
+        // replica-major ([R][K] planes: a sense gradient at plane 3) or plane-major ([K][R]: the field's layout): either way no two
+        // of the K * R planes share a word
+        DIE_REQUIRE(replica_stride >= cells && (replica_stride >= (K - 1) * plane_stride + cells || plane_stride >= (R - 1) * replica_stride + cells),
+                    "%s: replica_stride %lld with plane_stride %lld: the %d x %d planes would share words", who, (long long)replica_stride,
+                    (long long)plane_stride, b->replicas, signal_channels);
+    }
+    // every range over the whole K * R span
+    const int64_t field_bytes = ((K * R - 1) * b->plane_stride + cells) * 4, em_bytes = ((R - 1) * replica_stride + (K - 1) * plane_stride + cells) * 4,
+                  occ_bytes = (R - 1) * occupied_stride + cells;
+    DIE_REQUIRE(!die_ranges_overlap(grad_field, field_bytes, grad_field_next, field_bytes), "%s: grad_field overlaps grad_field_next", who);
+    DIE_REQUIRE(!die_ranges_overlap(grad_field, field_bytes, occupied, occ_bytes), "%s: grad_field overlaps the occupancy planes", who);
+    DIE_REQUIRE(!die_ranges_overlap(grad_emission, em_bytes, grad_field_next, field_bytes), "%s: grad_emission overlaps grad_field_next", who);
+    DIE_REQUIRE(!die_ranges_overlap(grad_emission, em_bytes, occupied, occ_bytes), "%s: grad_emission overlaps the occupancy planes", who);
+    DIE_REQUIRE(!die_ranges_overlap(grad_emission, em_bytes, grad_field, field_bytes), "%s: grad_emission overlaps grad_field", who);
+    return die_signal_backward_launch(W, H, b->replicas, signal_channels, occupied, occupied_stride, grad_field_next, grad_field, b->plane_stride,
+                                      grad_emission, grad_emission ? plane_stride : 0, grad_emission ? replica_stride : 0, deposit, sigma, decay,
+                                      stream, who);
 }

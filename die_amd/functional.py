@@ -20,6 +20,10 @@
         the same three for every replica of a BatchedNeuralAutomataAgent's worlds, one launch each (die_memory_cells_batch,
         die_memory_planes_backward_batch, die_gather_memory_backward_batch): (R, Nmax) records, (R, M, Nmax) memories, the expand
         as (M, R, W, H) planes.  BatchedNeuralAutomataAgent.recurrent_action composes them.
+    signal_record_batch(population, standing=None), signal_step_batch(field, emission, record, *, deposit, sigma, decay)
+        the signal channels of every replica, one launch each (die_signal_cells_batch; die_signal_step_batch forward, ONE
+        die_signal_step_backward_batch backward): (R, W, H) byte planes, (R, K, W, H) fields of any strides.
+        BatchedNeuralAutomataAgent.signalling_action composes them with the three above.
 
 `ConvolutionModel.forward_device` evaluates a whole wide stack through `conv2d_wide`; `BatchedNeuralAutomataAgent.forward_device`
 a population of them in one launch per layer (die_nca_wide_backward_batch backward).  There is no eager fallback: a shape the
@@ -380,21 +384,21 @@ def _memory_population(population, what: str):
     return population.env
 
 
-def memory_record_batch(population) -> BatchedMemoryRecord:
+def memory_record_batch(population, standing: Optional[th.Tensor] = None) -> BatchedMemoryRecord:
     """The record of a BatchedNeuralAutomataAgent's worlds as they stand now: the R standing planes built at the env's epoch
     (die_stock_plane_batch) in a buffer the POPULATION owns and zeroes on every call — not the env's stock planes, so a later
     `env.step(population)` finds those as it left them, and two calls at one epoch are safe — then one die_memory_cells_batch
-    launch.  Small worlds; a population with memory channels."""
+    launch.  `standing`: such planes already built for these worlds at this epoch (a `signal_record_batch`'s), taken as they
+    are.  Small worlds; a population with memory channels."""
     env = _memory_population(population, 'memory_record_batch')
     dev, R, W, H, Nmax = env.device, env.R, env.W, env.H, env.Nmax
-    standing = getattr(population, '_standing', None)
     if standing is None:
-        standing = population._standing = th.zeros((R, W, H), dtype=th.int64, device=dev)
-    else:
-        standing.zero_()
+        standing = _standing_planes_batch(population)
+    elif not isinstance(standing, th.Tensor) or standing.dtype != th.int64 or tuple(standing.shape) != (R, W, H) or \
+            standing.device != dev or not standing.is_contiguous():
+        raise ValueError(f'standing: a contiguous ({R}, {W}, {H}) int64 tensor on {dev}')
     m, a, _, b = env._structs()
     sp = stream_ptr(dev)
-    _lib.check(_lib.lib.die_stock_plane_batch(C.byref(m), C.byref(a), C.byref(b), env.epoch, _ptr(standing), sp), 'die_stock_plane_batch')
     cell = th.empty((R, Nmax), dtype=th.int32, device=dev)           # (every word is written: the padding slots -1)
     win = th.empty((R, Nmax), dtype=th.int32, device=dev)
     _lib.check(_lib.lib.die_memory_cells_batch(C.byref(m), C.byref(a), C.byref(b), _ptr(standing), env.epoch, _ptr(cell), _ptr(win), sp),
@@ -490,3 +494,118 @@ def gather_memory_batch(sense_tail: th.Tensor, record: BatchedMemoryRecord) -> t
     stand-alone bits wherever no cell holds more than two alive slots with a non-zero gradient."""
     _check_batched_memory_op('sense_tail', sense_tail, record, lambda r: (r.W, r.H))
     return _BatchedGatherMemory.apply(sense_tail, record)
+
+
+# ---------------------------------------------------------------------------------------------------- signal channels, batched
+class SignalRecordBatch:
+    """Which cells of every replica were stood on at one forward (die_signal_cells_batch): `occupied`, an (R, W, H) uint8 view —
+    `SignalRecord`'s plane with an R in front, replica r's plane a multiple of 16 bytes after replica r - 1's — and the sizes `W`,
+    `H`, `R`.  The batched adjoint of the fields' update is driven by these planes alone, so a graph that keeps the record survives
+    every step, reset and reseeding of the worlds and `reset_signals()`.  The record also remembers the standing planes and the
+    epoch it was taken at, for `signal_step_batch`'s forward only: step before those planes are built again."""
+    __slots__ = ('occupied', 'W', 'H', 'R', '_batch', '_standing', '_epoch')
+
+    def __init__(self, occupied, W, H, batch, standing, epoch):
+        self.occupied, self.W, self.H, self.R = occupied, int(W), int(H), int(occupied.shape[0])
+        self._batch, self._standing, self._epoch = batch, standing, int(epoch)
+
+
+def _standing_planes_batch(population) -> th.Tensor:
+    """The R standing planes of a population's worlds as they stand now, built at the env's epoch (die_stock_plane_batch) in a
+    buffer the POPULATION owns and zeroes on every call — not the env's stock planes."""
+    env = population.env
+    standing = getattr(population, '_standing', None)
+    if standing is None:
+        standing = population._standing = th.zeros((env.R, env.W, env.H), dtype=th.int64, device=env.device)
+    else:
+        standing.zero_()
+    m, a, _, b = env._structs()
+    _lib.check(_lib.lib.die_stock_plane_batch(C.byref(m), C.byref(a), C.byref(b), env.epoch, _ptr(standing), stream_ptr(env.device)),
+               'die_stock_plane_batch')
+    return standing
+
+
+def signal_record_batch(population, standing: Optional[th.Tensor] = None) -> SignalRecordBatch:
+    """The record of a BatchedNeuralAutomataAgent's worlds as they stand now: ONE die_signal_cells_batch launch for all R
+    replicas.  `standing`: the contiguous (R, W, H) int64 standing planes built for these worlds at the env's epoch
+    (die_stock_plane_batch), or None to build them here, in the buffer the population owns (`memory_record_batch`'s: one launch
+    more).  Small worlds; a population with signal channels."""
+    from .batch import BatchedNeuralAutomataAgent
+    if not isinstance(population, BatchedNeuralAutomataAgent):
+        raise TypeError('population: a BatchedNeuralAutomataAgent')
+    if not population._signal_channels:
+        raise ValueError('signal_record_batch: a population without signal channels (signal_channels=0) has no record')
+    env = population.env
+    if env.per_replica:
+        raise NotImplementedError('signal_record_batch: large worlds (per_replica) are not batched — every replica is a stand-alone '
+                                  'agent: use replica_agent(r).signalling_action / functional.signal_record')
+    dev, R, W, H = env.device, env.R, env.W, env.H
+    if standing is None:
+        standing = _standing_planes_batch(population)
+    elif not isinstance(standing, th.Tensor) or standing.dtype != th.int64 or tuple(standing.shape) != (R, W, H) or \
+            standing.device != dev or not standing.is_contiguous():
+        raise ValueError(f'standing: a contiguous ({R}, {W}, {H}) int64 tensor on {dev}')
+    m, _, _, b = env._structs()
+    stride = (W * H + 15) // 16 * 16                                          # every replica's bytes on a 16-byte boundary
+    store = th.empty((R, stride), dtype=th.uint8, device=dev)                  # (every byte of every plane is written by the call)
+    _lib.check(_lib.lib.die_signal_cells_batch(C.byref(m), C.byref(b), _ptr(standing), env.epoch, _ptr(store), stride, stream_ptr(dev)),
+               'die_signal_cells_batch')
+    return SignalRecordBatch(store[:, :W * H].view(R, W, H), W, H, b, standing, env.epoch)
+
+
+class _SignalStepBatch(th.autograd.Function):
+    """signal_step_batch: die_signal_step_batch forward into storage the graph owns, ONE die_signal_step_backward_batch launch
+    backward.  Inside, the field and its gradient lie (K, R, W, H) — plane k of every replica one plane apart, as a batched layer
+    launch reads them; outside they are (R, K, W, H) views of that."""
+
+    @staticmethod
+    def forward(ctx, field, emission, record, deposit, sigma, decay):
+        R, K, W, H = field.shape
+        field = field.permute(1, 0, 2, 3).contiguous()                         # (free for a view of this op's own output)
+        emission, plane_stride, replica_stride = _plane_strides(emission, 0, 1, W, H)
+        if replica_stride < (K - 1) * plane_stride + W * H:                    # (the launch reads a replica's K planes together)
+            emission = emission.contiguous()
+            plane_stride, replica_stride = W * H, K * W * H
+        out = th.empty((K, R, W, H), dtype=th.float32, device=field.device)
+        m = _bare_medium(W, H, record._epoch)
+        _lib.check(_lib.lib.die_signal_step_batch(C.byref(m), C.byref(record._batch), _ptr(record._standing), record._epoch, K, _ptr(emission),
+                                                  plane_stride, replica_stride, _ptr(field), _ptr(out), deposit, sigma, decay,
+                                                  stream_ptr(field.device)), 'die_signal_step_batch')
+        ctx.record, ctx.constants = record, (deposit, sigma, decay)
+        return out.permute(1, 0, 2, 3)
+
+    @staticmethod
+    @th.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        r, (deposit, sigma, decay) = ctx.record, ctx.constants
+        want_field, want_emission = ctx.needs_input_grad[:2]
+        if not (want_field or want_emission):
+            return None, None, None, None, None, None
+        g = grad.to(dtype=th.float32).permute(1, 0, 2, 3).contiguous()         # (K, R, W, H)
+        K, cells = g.shape[0], r.W * r.H
+        grad_field = th.empty_like(g) if want_field else None                  # (every cell is written by the call)
+        grad_emission = th.empty((r.R, K, r.W, r.H), dtype=th.float32, device=g.device) if want_emission else None
+        _lib.check(_lib.lib.die_signal_step_backward_batch(r.W, r.H, C.byref(r._batch), _ptr(r.occupied), r.occupied.stride(0), K, _ptr(g),
+                                                           _ptr(grad_field), _ptr(grad_emission), cells, K * cells, deposit, sigma, decay,
+                                                           stream_ptr(g.device)), 'die_signal_step_backward_batch')
+        return None if grad_field is None else grad_field.permute(1, 0, 2, 3), grad_emission, None, None, None, None
+
+
+def signal_step_batch(field: th.Tensor, emission: th.Tensor, record: SignalRecordBatch, *, deposit: float, sigma: float,
+                      decay: float) -> th.Tensor:
+    """The update of every replica's signal field with a `grad_fn`: `field` and `emission` (R, K, W, H) float32 on the record's
+    device, of any strides (a slice `sense[:, 3:3 + K]` is read where it lies), 1 <= K <= 8 -> the (R, K, W, H) next fields,
+    `out[r]` bit for bit the stand-alone `signal_step` of replica r: ONE die_signal_step_batch launch on the record's standing
+    planes, into storage the graph owns.  The backward is ONE die_signal_step_backward_batch launch for all K·R planes, which
+    produces only the gradients asked for.  A sweep and a mask: no atomics, bit-reproducible."""
+    if not isinstance(record, SignalRecordBatch):
+        raise TypeError('record: a SignalRecordBatch (die_amd.functional.signal_record_batch)')
+    dev = record.occupied.device
+    for name, t in (('field', field), ('emission', emission)):
+        if not isinstance(t, th.Tensor) or t.dtype != th.float32 or t.dim() != 4 or t.shape[0] != record.R or \
+                tuple(t.shape[2:]) != (record.W, record.H) or not 1 <= t.shape[1] <= _lib.SIGNAL_MAX_CHANNELS or t.device != dev:
+            raise ValueError(f'{name}: a float32 tensor of shape ({record.R}, K, {record.W}, {record.H}) with K in 1..'
+                             f'{_lib.SIGNAL_MAX_CHANNELS} on {dev}')
+    if field.shape[1] != emission.shape[1]:
+        raise ValueError(f'field has {field.shape[1]} planes a replica, emission {emission.shape[1]}')
+    return _SignalStepBatch.apply(field, emission, record, float(deposit), float(sigma), float(decay))

@@ -15,7 +15,8 @@ is the mean squared error of (dx, dy) against the teacher's over the alive agent
 without memory): every step is then `signalling_action(obs, signals, memory)`, the field blank at the window's start and
 `signals_next` handed from step to step, so that `loss.backward()` also runs through the field's update of every step
 (die_signal_step_backward: what an agent wrote is read, diffused and decayed, by whoever comes by later in the window);
-`--detach-every` cuts the field's gradient with the memory's.  Stand-alone only: with `--replicas` it is refused, populations come next.
+`--detach-every` cuts the field's gradient with the memory's.  Stand-alone only: with `--replicas` it is refused — populations with
+signal channels are trained by examples/signalling_population.py.
 
 `--memory-channels 0` trains the same stack without memory through `model.forward_device` and `functional.gather_scale`: the
 baseline.  With M > 0 the baseline is trained as well, on a world seeded alike, and both final losses are printed — side by side,
@@ -204,7 +205,7 @@ def main():
     if args.unroll < 1 or args.steps < 1 or args.detach_every < 0:
         raise SystemExit('--unroll and --steps are at least 1, --detach-every at least 0')
     if args.replicas and args.signal_channels:
-        raise SystemExit('--signal-channels trains a stand-alone student: populations (--replicas) come next')
+        raise SystemExit('--signal-channels trains a stand-alone student here; populations with signal channels: examples/signalling_population.py')
     if args.replicas:
         _, losses = train_batched(args.size, args.memory_channels, args.unroll, args.detach_every, args.steps, args.lr, args.seed,
                                   args.hidden_channels, args.warm, args.replicas, args.students, timed=args.time)

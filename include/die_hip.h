@@ -1387,6 +1387,61 @@ int die_nca_wide_backward_batch_memory(const die_medium* m, const die_batch* b, 
                                        const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, float* grad_in,
                                        int64_t grad_in_stride, const float* mem_planes, int32_t memory_channels, void* stream);
 
+/* ---- Batched BPTT through the signal channels (BatchedNeuralAutomataAgent.signalling_action; die_signal_grad.hip) -------------
+ * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
+ * The batched twins of die_signal_cells / die_signal_step_backward and the signal-aware forms of the two calls above.
+ *
+ * die_signal_cells_batch — the record of all R replicas in ONE launch, the replica in blockIdx.y (as the batched memory
+ * kernels), the device body that of die_signal_cells.  Replica r's standing plane (die_stock_plane_batch at `epoch`) at standing +
+ * r * b->plane_stride, its byte plane at occupied_out + r * occupied_stride.  EVERY byte of every plane is written; the bytes
+ * between two planes and beyond the last are left alone.  16-byte stores where both base pointers are 16-byte aligned,
+ * b->plane_stride is even and occupied_stride % 16 == 0; single bytes elsewhere and on the tail.  Checked before the launch, in
+ * order: die_signal_cells' checks (a null pointer, the batch included; W or H < 1; a decomposed medium: DIE_ERR_UNSUPPORTED; the
+ * epoch), die_signal_step_batch's die_batch checks (replicas outside 1..DIE_MAX_REPLICAS, b->plane_stride < W * H, agent_stride
+ * < 1, n[r] outside 0..agent_stride), occupied_stride < W * H, an output that overlaps the standing planes. */
+int die_signal_cells_batch(const die_medium* m, const die_batch* b, const unsigned long long* standing, int32_t epoch,
+                           uint8_t* occupied_out, int64_t occupied_stride, void* stream);
+/* die_signal_step_backward_batch — die_signal_step_backward for all K * R planes in ONE launch (plane k of replica r is
+ * blockIdx.z = k * R + r, the kernels those of the stand-alone call: with one replica it is that call).  Gradient plane k of
+ * replica r at grad_field_next / grad_field + (k * R + r) * b->plane_stride (die_signal_step_batch's field layout); replica r's
+ * mask at occupied + r * occupied_stride; its emission gradient's plane k at grad_emission + r * replica_stride + k *
+ * plane_stride — replica-major (replica_stride >= (K - 1) * plane_stride + W * H: plane 3 of an (R, 3 + K + M, W, H)
+ * sense-gradient buffer, whose other planes are left alone) or plane-major (plane_stride >= (R - 1) * replica_stride + W * H).
+ * Either output may be null (its store is skipped, the other gets the same bits), not both.  EVERY cell of every output plane
+ * is written, nothing between them; the inputs are only read.  The row-marching kernel runs where H % 4 == 0, the radius is at
+ * most 4, every float pointer and stride is 16-byte aligned and `occupied` and occupied_stride 4-byte aligned; the LDS-tiled one
+ * elsewhere.  Checked before the launch (DIE_ERR_ARG), in order: die_signal_step_backward's checks (a null b, occupied or
+ * grad_field_next; both outputs null; size, K and the three constants), the die_batch checks above, occupied_stride < W * H, with
+ * a grad_emission plane_stride < W * H and strides under which two of its K * R planes would share words, then every overlap
+ * between an output and an input, the masks or the other output, each taken over its whole K * R span. */
+int die_signal_step_backward_batch(int32_t W, int32_t H, const die_batch* b, const uint8_t* occupied, int64_t occupied_stride,
+                                   int32_t signal_channels, const float* grad_field_next, float* grad_field, float* grad_emission,
+                                   int64_t plane_stride, int64_t replica_stride, float deposit, float sigma, float decay, void* stream);
+/* die_nca_wide_sense_batch_store_memory for a population whose agents also write a signal field: layer 0 reads ([agents,] food,
+ * chem, signal_0 .., memory_0 ..), `signal_planes` laid out as die_signal_step_batch reads the field (plane k of replica r at
+ * (k * R + r) * b->plane_stride), and the last layer gives 3 + K + M planes; the tanh and the mask fall on all of them.
+ * memory_channels = 0 with null mem_planes is allowed: no memory.  The parent's L launches (L + 1 with a mask).  Checked as the
+ * parent, in its order, with those channel counts, and: null signal_planes, memory_channels outside 0..DIE_MEMORY_MAX_CHANNELS or
+ * not 0 exactly where mem_planes is null, signal_channels outside 1..DIE_SIGNAL_MAX_CHANNELS, memory or signal planes that
+ * overlap the store or the masked planes. */
+int die_nca_wide_sense_batch_store_signal(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* store,
+                                          int64_t store_bytes, float* masked, const die_nca_dropout* drop, const float* mem_planes,
+                                          int32_t memory_channels, const float* signal_planes, int32_t signal_channels, void* stream);
+/* die_nca_wide_backward_batch_memory for such a stack — the one host body and the same two adjoint kernels and float64 fold,
+ * given the signal planes as further layer-0 inputs: grad_sense holds 3 + K + M planes per replica, and `grad_in`, when given,
+ * replica r's 2 + with_agent_channel + K + M planes in channel order — the caller takes the chem plane for the env's chem node,
+ * the K signal planes for the incoming field and the M memory planes for die_memory_planes_backward_batch.  3 L - 1 launches,
+ * 3 L with grad_in.  Checked as the parent, in its order (memory_channels = 0 with null mem_planes allowed, signal_planes
+ * required, grad_in against the signal planes too); the byte query gives -1 for a refused shape.  The two older entry points
+ * keep refusing a stack with signal planes. */
+int64_t die_nca_wide_backward_batch_signal_workspace_bytes(int32_t W, int32_t H, int32_t replicas, const die_nca_batch* nca,
+                                                           int32_t memory_channels, int32_t signal_channels);
+int die_nca_wide_backward_batch_signal(const die_medium* m, const die_batch* b, const die_nca_batch* nca, const float* store,
+                                       const float* grad_sense, int64_t sense_stride, float* grad, int64_t grad_stride,
+                                       const die_nca_dropout* drop, void* workspace, int64_t workspace_bytes, float* grad_in,
+                                       int64_t grad_in_stride, const float* mem_planes, int32_t memory_channels,
+                                       const float* signal_planes, int32_t signal_channels, void* stream);
+
 /* die_food_flow_batch on the replicas whose bit is set in replica_mask (bit r = replica r); the others' planes are not touched.
  * One launch: a row of workgroups per replica, those of unset replicas exit at once.  A full mask leaves exactly what
  * die_food_flow_batch leaves; an empty mask launches nothing.  Bits at or above b->replicas must be 0. */
