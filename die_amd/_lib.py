@@ -126,6 +126,7 @@ NCA_WIDE_MAX_CHANNELS = 32           # die_conv2d_wide / die_nca_wide_env_step_b
 NCA_WIDE_KERNEL_SIZES = (1, 3, 5)
 MEMORY_MAX_CHANNELS = 8              # DIE_MEMORY_MAX_CHANNELS: NeuralAutomataAgent(memory_channels=M)
 SIGNAL_MAX_CHANNELS = 8              # DIE_SIGNAL_MAX_CHANNELS: NeuralAutomataAgent(signal_channels=K)
+INHERIT_MODES = {'blank': 0, 'copy': 1}                # NeuralAutomataAgent(memory_inherit=...) → DIE_INHERIT_BLANK / DIE_INHERIT_COPY
 NCA_ACTIVATIONS = {None: 0, 'tanh': 1, 'relu': 2}     # ConvolutionModel(hidden_activation=...) → die_nca_activation
 
 
@@ -321,6 +322,16 @@ _SIGNATURES = {
     'die_births_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int64]),
     'die_agent_births': (C.c_int, [_P(Agents), _P(Births), C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'die_agent_births_batch': (C.c_int, [_P(Agents), _P(Batch), _P(Births), _P(C.c_uint64), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'die_births_record': (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'die_births_record_batch': (C.c_int, [_P(Batch), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'die_memory_inherit': (C.c_int, [C.c_int32, C.c_float, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint32,
+                                     C.c_void_p]),
+    'die_memory_inherit_batch': (C.c_int, [C.c_int32, C.c_float, C.c_int32, _P(Batch), C.c_void_p, C.c_void_p, _P(C.c_uint64), C.c_uint32,
+                                           C.c_void_p]),
+    'die_memory_inherit_backward': (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                              C.c_void_p]),
+    'die_memory_inherit_backward_batch': (C.c_int, [C.c_int32, C.c_int32, _P(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]),
     'die_gradient_render': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     'die_agent_claim_feed': (C.c_int, [_P(Medium), _P(Agents), _P(Action), _P(Dynamics), C.c_void_p, C.c_int64,
                                        C.c_void_p]),

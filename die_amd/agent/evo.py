@@ -59,6 +59,25 @@ def _signal_arguments(channels, deposit, sigma, decay):
     return int(channels), (deposit, sigma, decay)
 
 
+_HEREDITY_ARGUMENTS = ('memory_inherit', 'memory_mutation')
+
+
+def _heredity_arguments(mode, mutation, memory_channels: int):
+    """NeuralAutomataAgent's two heredity arguments, checked: (mode or None, mutation as a float) or the ValueError that says which is
+    wrong — a mode other than 'blank' / 'copy', a mutation that is no finite float >= 0 or comes without 'copy', either without
+    memory channels."""
+    from ..functional import inherit_arguments
+    if mode is None:
+        inherit_arguments('copy', mutation, 'NeuralAutomataAgent')          # (a bad number is a bad number whatever the mode)
+        if float(mutation) != 0.0:
+            raise ValueError(f"memory_mutation={mutation!r} needs memory_inherit='copy'")
+        return None, 0.0
+    mode, mutation = inherit_arguments(mode, mutation, 'NeuralAutomataAgent')
+    if not memory_channels:
+        raise ValueError(f'memory_inherit={mode!r} without memory channels (memory_channels=0): there is nothing to inherit')
+    return mode, mutation
+
+
 def _layer_arrays(li: int, w: th.Tensor, planes, dst: th.Tensor):
     """What a narrow layer launch takes beside its weights `w`: the input `planes` [(tensor, DIE_PLANE_* kind)] as a die_conv_plane
     array and the first cout planes of `dst` as a pointer array — or the ValueError of a weight that does not fit the planes."""
@@ -266,9 +285,21 @@ class NeuralAutomataAgent(TorchAgent):
         populations, the stock channel, fp16 fields or decomposed worlds.
       * Refused with NotImplementedError before any launch, and before `dropout_step` or `memory` change: the memoryless
         `differentiable_sense`, `differentiable_action`, `model.forward_device`, and a decomposed medium (die_amd/dist.py).
-        `Dynamics(agents_born=True)` is refused together with memory too (a slot can die and be refilled within one step, so a
-        newborn would inherit a dead agent's memory) — but a stand-alone agent cannot see the Dynamics, so that refusal sits
-        where the Dynamics is known: the `BatchedNeuralAutomataAgent` constructor.  With a stand-alone `Env` it is the caller's.
+        `Dynamics(agents_born=True)` is refused together with memory too while no rule of inheritance is set (`memory_inherit`
+        None: a slot can die and be refilled within one step, so a newborn would inherit a dead agent's memory) — but a
+        stand-alone agent cannot see the Dynamics, so that refusal sits where the Dynamics is known: the
+        `BatchedNeuralAutomataAgent` constructor.  With a stand-alone `Env` it is the caller's.
+      * Heredity: `memory_inherit` 'blank' / 'copy' (None: no rule, nothing changes) and `memory_mutation` = a >= 0 (only with
+        'copy') say what a newborn's memory holds under `Dynamics(agents_born=True)`.  After a step's birth pass
+        has matched parent p to free slot f, and on the memory as this step's read-out left it: 'blank' `memory[m][f] = +0`;
+        'copy' `memory[m][f] = memory[m][p]`, bits preserved; 'copy' with a > 0 the parent's value plus `a * u`, u uniform in
+        [-1, 1] from the births' own Philox key and step on a stream of its own (two separately rounded fp32 operations).  The
+        parent keeps its memory, every other slot is left alone (die_memory_inherit, one launch).  With a rule `forward(obs)`
+        marks the action it returns, and `Env.step` hands the record of its birth pass (`env.births_record()`) to
+        `inherit_memory`: `env.step(agent.forward(obs))` and `Env.run(agent, n)` inherit without a further call; a refilled slot's
+        memory is always overwritten, so the refusal above is gone.  Both arguments are kept out of `init_params` while the mode
+        is None and are saved and restored otherwise.  ValueError in the constructor: another mode, a mutation that is negative,
+        not finite or no number, a mutation with 'blank', either argument without memory channels.
     Kept out of `init_params` while 0, saved and restored by `load` while positive (the memory itself is state, not saved).
 
     `signal_channels=K`, 1 <= K <= 8, with `signal_deposit`, `signal_sigma`, `signal_decay` (no reference counterpart; core/__init__.py
@@ -308,6 +339,8 @@ class NeuralAutomataAgent(TorchAgent):
                  signal_deposit: float = 1.0,
                  signal_sigma: float = 0.5,
                  signal_decay: float = 0.1,
+                 memory_inherit: Optional[str] = None,
+                 memory_mutation: float = 0.0,
                  **model_kwargs,
                  ):
         self._init_params = save_args(self.__init__, locals())
@@ -328,6 +361,12 @@ class NeuralAutomataAgent(TorchAgent):
                 int(memory_channels) != memory_channels or not 0 <= memory_channels <= _lib.MEMORY_MAX_CHANNELS:
             raise ValueError(f'memory_channels={memory_channels!r}: an integer in 1..{_lib.MEMORY_MAX_CHANNELS}, or 0 / None for none')
         self.memory_channels = int(memory_channels)
+        self.memory_inherit, self.memory_mutation = _heredity_arguments(memory_inherit, memory_mutation, self.memory_channels)
+        for name, value in zip(_HEREDITY_ARGUMENTS, (self.memory_inherit, self.memory_mutation)):
+            if self.memory_inherit is not None:                # (saved as the checked values; both kept out while the mode is None)
+                self._init_params[name] = value
+            else:
+                self._init_params.pop(name, None)
         self.memory: Optional[th.Tensor] = None                # (M, N) float32 by slot id, from the first forward on
         self._memory_rebind = True                             # the next forward may allocate for its own N
         self._memory_planes = {}                               # (W, H, device) -> (M, W, H) float32: the expanded memory
@@ -648,7 +687,39 @@ class NeuralAutomataAgent(TorchAgent):
                        'die_signal_step')
             self.signals, self._signals_next = self._signals_next, self.signals
         action._keepalive = sense
+        if self.memory_inherit is not None:                      # `env.step(agent.forward(obs))` under agents_born: the step's birth
+            action._heredity_agent = self                        # pass hands its record to this agent's `inherit_memory`
         return action
+
+    def inherit_memory(self, record, memory: Optional[th.Tensor] = None) -> th.Tensor:
+        """Heredity (`memory_inherit` 'blank' / 'copy', `memory_mutation`): the newborns of one birth pass receive
+        their memory.  `record`: the `BirthsRecord` of `env.births_record()`, taken after the step (or `apply_births()`) that ran the
+        pass and after this agent's forward of that step.
+
+        `memory` None: `self.memory` is updated in place (die_memory_inherit, one launch) and returned.  `Env.step` does exactly
+        this by itself for the action of this agent's `forward` — the loop `env.step(agent.forward(obs))` and `Env.run(agent, n)`
+        need no further call.  An action that carries no agent (`step_action`, a tensor, `apply_births()`) needs the call.
+
+        `memory`: an (M, N) float32 tensor on the record's device — the `memory_next` of `recurrent_action` / `signalling_action`:
+        returns `functional.inherit_memory(memory, record, mode, mutation)`, a new tensor with a `grad_fn` (a child's gradient
+        reaches its parent under 'copy'), and leaves `self.memory` holding a copy of the same bits, as `recurrent_action` does.
+
+        Refused with ValueError before any launch, `memory` untouched: an agent without memory channels or without a mode, a
+        record that is no stand-alone BirthsRecord, a memory of the wrong shape, dtype or device."""
+        from ..functional import check_inherit_operands, inherit_memory, inherit_memory_
+        M = self.memory_channels
+        if not M:
+            raise ValueError('inherit_memory: an agent without memory channels (memory_channels=0) has nothing to inherit')
+        if self.memory_inherit is None:
+            raise ValueError("inherit_memory: this agent has no rule (memory_inherit=None): build it with memory_inherit='blank' or 'copy'")
+        if memory is None:
+            check_inherit_operands('inherit_memory (self.memory)', self.memory, record, False, M, contiguous=True)
+            return inherit_memory_(self.memory, record, self.memory_inherit, self.memory_mutation)
+        check_inherit_operands('inherit_memory', memory, record, False, M)
+        out = inherit_memory(memory, record, self.memory_inherit, self.memory_mutation)
+        self.memory = out.detach().clone()                       # the agent's own copy, not the graph's tensor
+        self._memory_rebind = False
+        return out
 
     # ------------------------------------------------------------------ the differentiable twins (die_nca_grad.hip)
     def differentiable_sense(self, medium) -> th.Tensor:
@@ -721,6 +792,17 @@ class NeuralAutomataAgent(TorchAgent):
         The agent is left as `forward(obs)` would leave it: `self.memory` holds a copy of `memory_next`'s values, `dropout_step`
         has advanced once if a `dropout_seed` is set, `_sense_output` is set.  An unseeded `p_agent_dropout` > 0 in training mode
         is a torch mask multiply on all 3 + M planes, as in `differentiable_sense`.
+
+        Under `Dynamics(agents_born=True)` (an agent with `memory_inherit` set) the chain goes through the births: the actions
+        are tensors, which carry no agent, so the link after every step is the caller's —
+
+            action, memory_next = agent.recurrent_action(obs, memory)
+            obs, *_ = env.step(action)                               # a plain step: deaths, then the birth pass
+            memory = agent.inherit_memory(env.births_record(), memory_next)
+
+        `inherit_memory` with a tensor has a `grad_fn` (a gather: under 'copy' a child's gradient is added to its parent's), so
+        the loop is backpropagation through time across births; the world itself is not differentiated there
+        (`differentiable_step` refuses `agents_born`).
 
         Refused before any launch, and before `dropout_step` or `memory` change: an agent without memory channels (ValueError: it
         has `differentiable_action`); with NotImplementedError the stock channel (the adjoint calls do not take its plane kind), a

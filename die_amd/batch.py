@@ -201,6 +201,7 @@ class BatchedEnv:
             _lib.check(_lib.lib.die_dynamics_rows(structs, R, W, H, self._rows_host), 'die_dynamics_rows')
             self._rows = torch.frombuffer(bytearray(bytes(self._rows_host)), dtype=torch.uint8).to(dev)
         self._steps = 0
+        self._births_pass = None                    # the world step of the birth pass whose lists the workspace holds (births_record)
         self._initial = (self._state.clone(), self.chem, self.chem_next)
         self._flow_k0 = getattr(self.dynamics.op_food_flow, '_k', None)
 
@@ -247,6 +248,7 @@ class BatchedEnv:
         if self._flow_k0 is not None:
             self.dynamics.op_food_flow._k = self._flow_k0
         self._steps = 0
+        self._births_pass = None
         self._serial += 1                           # (the stock planes of an earlier step say nothing about the worlds to come)
         self.chem_node = None                       # the worlds start over: an autograd handle of the chem planes ends here
         if seeds is not None:
@@ -324,6 +326,28 @@ class BatchedEnv:
         seeds = (C.c_uint64 * self.R)(*[q & 0xFFFFFFFFFFFFFFFF for q in self.seeds])
         _lib.check(_lib.lib.die_agent_births_batch(C.byref(a), C.byref(b), C.byref(p), seeds, _ptr(results), _ptr(self._births_ws),
                                                    self._births_ws.numel(), stream_ptr(self.device)), 'die_agent_births_batch')
+        self._births_pass = self._steps
+
+    def births_record(self):
+        """Who was born to whom in every replica's birth pass of the step that just ran: a `die_amd.functional.BirthsRecord` whose
+        `parent_of` and `child_of` are (R, Nmax) int32 device tensors by slot id — row r the stand-alone `Env.births_record()` of
+        replica r, the slots from n[r] on -1 — freshly allocated per call, with every replica's world seed and the world step.  One
+        launch for all R (die_births_record_batch), only when asked.  Valid after a step that ran the pass (`step`, `step_action`)
+        and until the next step or reset; otherwise ValueError.  Large worlds (`per_replica`) hold a stand-alone Env per replica:
+        `envs[r].births_record()`."""
+        from .functional import BirthsRecord
+        if self.per_replica:
+            raise NotImplementedError('births_record: large worlds (per_replica) are not batched — every replica is a stand-alone Env: '
+                                      'use envs[r].births_record()')
+        if not self.dynamics.agents_born:
+            raise ValueError('births_record: these worlds have no births (Dynamics(agents_born=False))')
+        if self._births_pass is None:
+            raise ValueError('births_record: no birth pass yet (valid after a step, until the next step or reset)')
+        out = torch.empty((2, self.R, self.Nmax), dtype=torch.int32, device=self.device)
+        b = self._batch_struct()
+        _lib.check(_lib.lib.die_births_record_batch(C.byref(b), _ptr(self._births_ws), self._births_ws.numel(), _ptr(out[0]), _ptr(out[1]),
+                                                    stream_ptr(self.device)), 'die_births_record_batch')
+        return BirthsRecord(out[0], out[1], self.seeds, self._births_pass, self.n)
 
     def check(self):
         """Synchronise; raise if a replica's tile-binned step reported a bookkeeping error since the last check (per-replica
@@ -357,7 +381,8 @@ class BatchedEnv:
 
         One path for the three agent kinds.  What is particular to a kind it says itself: `_check_step(env)` (its refusals),
         `_replica_agent(r)` (replica r's stand-alone agent, large worlds), `_claim_epoch(env)` (the epoch its claims are made
-        at), `_launch(...)` (its struct and its library entry point), `_stepped()` (its counters after a step) and
+        at), `_launch(...)` (its struct and its library entry point), `_stepped()` (its counters after a step), `_inherit(env)` (what
+        its newborns receive after the births: nothing for the two Physarum kinds) and
         `_builds_stock_planes` (whether its step builds the env's stock planes).  A step that is refused leaves the batch as it was."""
         agent._check_step(self)                     # every refusal before anything is launched
         flow = self._flow_kind()
@@ -386,7 +411,9 @@ class BatchedEnv:
             raise
         agent._calls += 1
         agent._stepped()
-        return self._launched(flow, m, a, b, results, agent._builds_stock_planes)
+        results = self._launched(flow, m, a, b, results, agent._builds_stock_planes)
+        agent._inherit(self)                        # (after the births: what the newborns receive from their parents)
+        return results
 
     def _launched(self, flow: Optional[int], m, a, b, results: torch.Tensor, built_stock_planes: bool = False) -> torch.Tensor:
         """What follows the launches of `step` and of `step_action` alike: the births, the plane swap, the flow, the counters."""
@@ -704,6 +731,7 @@ def _env_restore(e: Env, snap: dict) -> None:
     A.N = snap['N']
     e._all_alive = snap['all_alive']
     e._steps = 0
+    e._births_pass, e._births_consumed = None, False
     e._pic = None
     e._frozen = None
     e._fuse_forward = True
@@ -741,6 +769,9 @@ class _PhysarumReplicas:
 
     def _stepped(self) -> None:
         pass
+
+    def _inherit(self, env: BatchedEnv) -> None:
+        pass                                        # (headings are not heritable: a newborn takes its slot's)
 
 
 class _Population:
@@ -1032,7 +1063,8 @@ def _architecture(agent: NeuralAutomataAgent) -> dict:
                 with_agent_channel='agents' in agent.obs_channels, with_stock_channel=agent.with_stock_channel, scale=agent.action_coefs[0], deposit=agent.action_coefs[2],
                 shapes=tuple(tuple(k.weight.shape) for k in layers), hidden_channels=agent.model.hidden_channels,
                 hidden_activation=agent.model.hidden_activation, memory_channels=agent.memory_channels,
-                signal_channels=agent.signal_channels, signal_constants=agent.signal_constants if agent.signal_channels else None)
+                signal_channels=agent.signal_channels, signal_constants=agent.signal_constants if agent.signal_channels else None,
+                memory_inherit=agent.memory_inherit, memory_mutation=agent.memory_mutation)
 
 
 class BatchedNeuralAutomataAgent(_Population):
@@ -1079,9 +1111,13 @@ class BatchedNeuralAutomataAgent(_Population):
     bound to it — the searchers call a population's `reset()` every generation when it has one, after `env.reset()` — so every
     generation starts from blank memory, while a memoryless population still has no `reset`.  agents_die, max_agents and
     `reset(seed=...)`, flows, per-replica Dynamics, dropout_seed, `action=`, the stock channel and both searchers take memory as
-    they are.  Refused with NotImplementedError: `Dynamics(agents_born=True)` together with memory, HERE in the constructor — a
-    slot can die and be refilled within one step, so a newborn would inherit a dead agent's memory, and the stand-alone agent
-    cannot see the Dynamics to refuse it itself —; and `differentiable_sense`, `differentiable_action` and `forward_device`,
+    they are.  Refused with NotImplementedError: `Dynamics(agents_born=True)` together with memory and no rule of inheritance
+    (`memory_inherit=None`), HERE in the constructor — a slot can die and be refilled within one step, so a newborn would inherit a
+    dead agent's memory, and the stand-alone agent cannot see the Dynamics to refuse it itself.  With a rule
+    (`memory_inherit='blank'` / `'copy'`, `memory_mutation`) the population breeds: `env.step(pop)` runs one more hook after the
+    births, `inherit_memory(env.births_record())` — the record launch and die_memory_inherit_batch, two launches for all R — and
+    replica r stays the stand-alone run of `replica_agent(r)`, which carries the rule.  Also refused: `differentiable_sense`,
+    `differentiable_action` and `forward_device`,
     before any launch and before `dropout_step` or `memory` change.  The differentiable call of a population with memory is
     `recurrent_action(memory=None, parameters=None) -> (action, memory_next)`: the step's forward half with a graph through the
     read-outs, the stack and the expand, a `(C, P)` gradient, and `memory_next` chained from call to call for backpropagation
@@ -1109,7 +1145,7 @@ class BatchedNeuralAutomataAgent(_Population):
                  dropout_seed: Optional[int] = None, dropout_seed_stride: int = 1):
         if not isinstance(template, NeuralAutomataAgent):
             raise TypeError('template: a NeuralAutomataAgent')
-        if template.memory_channels and env.dynamics.agents_born:
+        if template.memory_channels and env.dynamics.agents_born and template.memory_inherit is None:
             raise NotImplementedError(f'memory_channels={template.memory_channels} with Dynamics(agents_born=True): a slot can die and '
                                       'be refilled within one step, so a newborn would inherit a dead agent\'s memory (inheritance at '
                                       'birth is not defined yet)')
@@ -1277,6 +1313,40 @@ class BatchedNeuralAutomataAgent(_Population):
             self.dropout_step += 1                  # counts forward calls, masked or not (as NeuralAutomataAgent.sense does)
         if self._signals is not None:               # the step wrote every replica's next field into the second buffer
             self._signals, self._signals_next = self._signals_next, self._signals
+
+    def _inherit(self, env: BatchedEnv) -> None:
+        """BatchedEnv.step's hook after the births: with a rule (`memory_inherit`) the newborns of every replica receive their memory."""
+        if self.template.memory_inherit is not None and env.dynamics.agents_born:
+            self.inherit_memory(env.births_record())
+
+    def inherit_memory(self, record, memory: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`NeuralAutomataAgent.inherit_memory` for every replica in one launch (die_memory_inherit_batch): `record` the
+        `env.births_record()` of the step that just ran.  `memory` None: `self.memory`, the (R, M, Nmax) tensor, is updated in place
+        and returned — `env.step(population)` does this by itself after the births where the template has a rule; after
+        `env.step_action(...)` it is the caller's.  `memory`: an (R, M, Nmax) float32 tensor on the env's device, the `memory_next`
+        of `recurrent_action` / `signalling_action`: returns `functional.inherit_memory_batch(...)` with a `grad_fn` and leaves
+        `self.memory` holding the same bits.  Replica r is the stand-alone `replica_agent(r).inherit_memory` on the record of its
+        own stand-alone Env, bit for bit.  Refused with ValueError before any launch, `memory` untouched: a population without
+        memory channels or without a rule, a record that is no batched BirthsRecord, a memory of the wrong shape, dtype or
+        device; large worlds (`per_replica`) with NotImplementedError: `agents[r].inherit_memory(env.envs[r].births_record())`."""
+        from .functional import check_inherit_operands, inherit_memory_, inherit_memory_batch
+        t, M = self.template, self._memory_channels
+        if not M:
+            raise ValueError('inherit_memory: a population without memory channels (memory_channels=0) has nothing to inherit')
+        if t.memory_inherit is None:
+            raise ValueError("inherit_memory: this population has no rule (memory_inherit=None): build its template with "
+                             "memory_inherit='blank' or 'copy'")
+        if self.env.per_replica:
+            raise NotImplementedError('inherit_memory: large worlds (per_replica) are not batched — every replica steps a stand-alone '
+                                      'agent: use agents[r].inherit_memory(env.envs[r].births_record())')
+        if memory is None:
+            check_inherit_operands('inherit_memory (self.memory)', self.memory, record, True, M, contiguous=True)
+            return inherit_memory_(self.memory, record, t.memory_inherit, t.memory_mutation)
+        check_inherit_operands('inherit_memory', memory, record, True, M)
+        out = inherit_memory_batch(memory, record, t.memory_inherit, t.memory_mutation)
+        with torch.no_grad():
+            self.memory.copy_(out)                  # the population's own copy, not the graph's tensor
+        return out
 
     # ------------------------------------------------------------------ step
     def _check_step(self, env: BatchedEnv) -> None:

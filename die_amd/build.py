@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OUT = os.path.join(HERE, 'libdie_hip.so')
-SOURCES = ['die_agents.hip', 'die_env.hip', 'die_init.hip', 'die_sort.hip', 'die_pack.hip', 'die_ghost.hip', 'die_render.hip', 'die_pic.hip', 'die_pic_refresh.hip', 'die_nca.hip', 'die_nca_wide.hip', 'die_nca_grad.hip', 'die_nca_wide_grad.hip', 'die_env_grad.hip', 'die_search.hip', 'die_cmaes.hip', 'die_physarum.hip', 'die_births.hip', 'die_stock.hip', 'die_memory.hip', 'die_memory_grad.hip', 'die_signal.hip', 'die_signal_grad.hip']
+SOURCES = ['die_agents.hip', 'die_env.hip', 'die_init.hip', 'die_sort.hip', 'die_pack.hip', 'die_ghost.hip', 'die_render.hip', 'die_pic.hip', 'die_pic_refresh.hip', 'die_nca.hip', 'die_nca_wide.hip', 'die_nca_grad.hip', 'die_nca_wide_grad.hip', 'die_env_grad.hip', 'die_search.hip', 'die_cmaes.hip', 'die_physarum.hip', 'die_births.hip', 'die_heredity.hip', 'die_stock.hip', 'die_memory.hip', 'die_memory_grad.hip', 'die_signal.hip', 'die_signal_grad.hip']
 HEADERS = ['die_common.h', 'die_rng.h', 'die_forward.h', 'die_search.h', 'die_nca.h', 'die_diffuse.h', 'die_diffuse_tile.inc', 'die_diffuse_rows.inc', os.path.join('..', '..', 'include', 'die_hip.h')]
 # -ffp-contract=on: fuse a*b+c only inside one source expression.  hipcc's default (fast) fuses across
 # statements, so the same inlined device function could round differently in two kernels (the fused and the

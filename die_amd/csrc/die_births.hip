@@ -9,6 +9,11 @@
 //   k_births_spawn  thread j < min writes the child into free_of_rank[j], halves parent_of_rank[j] and draws the displacement;
 //                   one thread adds the number born to the step result's count
 // tests/births_model.py is the numpy twin.
+//
+// The record (die_births_record / _batch; tests/heredity_model.py `record`): one more launch, only for a caller that asks who was
+// born to whom.  The workspace still holds the two lists and the totals after the pass, both lists ascending in slot id, so
+//   k_births_record every slot s < agent_stride looks itself up among the first `born` parents and the first `born` free slots (two
+//                   binary searches) and writes parent_of[s] and child_of[s], -1 where it is neither — a gather, every word one writer
 #include "die_common.h"
 #include "die_rng.h"
 
@@ -230,4 +235,87 @@ extern "C" int die_agent_births(const die_agents* a, const die_births* p, uint64
 extern "C" int die_agent_births_batch(const die_agents* a, const die_batch* b, const die_births* p, const uint64_t* world_seeds,
                                       die_step_result* results, void* ws, int64_t ws_bytes, void* stream) {
     return births_launch(a, b, p, world_seeds, results, ws, ws_bytes, stream, "die_agent_births_batch");
+}
+
+// ---- the record of the pass that just ran ------------------------------------------------------------------------------
+#define BIRTH_RECORD_MAX_GROUPS 256   // workgroups per replica at most; a thread walks its slots one grid apart
+
+struct BirthRecordArgs {
+    const uint32_t* ws;           // as BirthArgs.ws, after the pass
+    int64_t ws_stride, agent_stride;
+    int32_t *parent_of, *child_of;                // replica r's agent_stride words r * agent_stride on
+    int64_t n[DIE_MAX_REPLICAS];
+};
+
+// rank of `s` in the ascending list key(0) < key(1) < ... < key(born - 1), or -1
+template <typename Key> __device__ __forceinline__ int64_t birth_find(int64_t born, uint32_t s, Key key) {
+    int64_t lo = 0, hi = born;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (key(mid) < s) lo = mid + 1; else hi = mid;
+    }
+    return lo < born && key(lo) == s ? lo : -1;
+}
+
+__global__ __launch_bounds__(BIRTH_BLOCK) void k_births_record(BirthRecordArgs a) {
+    const int r = blockIdx.y;
+    const int64_t base = a.agent_stride * r, n = a.n[r];
+    const uint32_t* ws = a.ws + a.ws_stride * r;
+    const uint32_t* list = ws + BIRTH_WS_HEAD;
+    const uint32_t np = ws[2 * BIRTH_MAX_GROUPS], nf = ws[2 * BIRTH_MAX_GROUPS + 1];
+    int64_t born = np < nf ? np : nf;
+    if (born > n / 2) born = n / 2;                            // (what a pass leaves never exceeds it: no index leaves the lists)
+    const int64_t last = a.agent_stride - 1;
+    const int64_t stride = (int64_t)gridDim.x * BIRTH_BLOCK;
+    for (int64_t s = (int64_t)blockIdx.x * BIRTH_BLOCK + threadIdx.x; s < a.agent_stride; s += stride) {
+        int32_t parent = -1, child = -1;
+        if (s < n) {
+            const int64_t jp = birth_find(born, (uint32_t)s, [&](int64_t j) { return list[j]; });
+            const int64_t jf = jp >= 0 ? -1 : birth_find(born, (uint32_t)s, [&](int64_t j) { return list[last - j]; });
+            if (jp >= 0 && (int64_t)list[last - jp] < n) child = (int32_t)list[last - jp];
+            if (jf >= 0 && (int64_t)list[jf] < n) parent = (int32_t)list[jf];
+        }
+        a.parent_of[base + s] = parent;
+        a.child_of[base + s] = child;
+    }
+}
+
+static int births_record_launch(const die_batch* b, const void* ws, int64_t ws_bytes, int32_t* parent_of, int32_t* child_of, void* stream,
+                                const char* who) {
+    DIE_REQUIRE(b && ws && parent_of && child_of, "%s: null argument", who);
+    DIE_REQUIRE(b->replicas >= 1 && b->replicas <= DIE_MAX_REPLICAS, "%s: 1..%d replicas", who, DIE_MAX_REPLICAS);
+    const int64_t need = die_births_workspace_bytes(b->replicas, b->agent_stride);
+    DIE_REQUIRE(need > 0, "%s: bad agent stride %lld", who, (long long)b->agent_stride);
+    DIE_REQUIRE(ws_bytes >= need, "%s: workspace too small (%lld < %lld: die_births_workspace_bytes)", who, (long long)ws_bytes, (long long)need);
+    DIE_REQUIRE(((uintptr_t)ws & 3u) == 0, "%s: the workspace must be 4-byte aligned", who);
+    const int64_t out_bytes = (int64_t)b->replicas * b->agent_stride * 4;
+    DIE_REQUIRE(!die_ranges_overlap(parent_of, out_bytes, child_of, out_bytes), "%s: parent_of overlaps child_of", who);
+    DIE_REQUIRE(!die_ranges_overlap(parent_of, out_bytes, ws, need) && !die_ranges_overlap(child_of, out_bytes, ws, need),
+                "%s: an output overlaps the workspace", who);
+    BirthRecordArgs k{};
+    k.ws = (const uint32_t*)ws; k.ws_stride = births_ws_words(b->agent_stride); k.agent_stride = b->agent_stride;
+    k.parent_of = parent_of; k.child_of = child_of;
+    for (int r = 0; r < b->replicas; ++r) {
+        DIE_REQUIRE(b->n[r] >= 1 && b->n[r] <= b->agent_stride, "%s: replica %d has %lld agents (stride %lld)", who, r, (long long)b->n[r],
+                    (long long)b->agent_stride);
+        k.n[r] = b->n[r];
+    }
+    const int64_t chunks = (b->agent_stride + BIRTH_BLOCK - 1) / BIRTH_BLOCK;
+    const dim3 grid((unsigned)(chunks < BIRTH_RECORD_MAX_GROUPS ? chunks : BIRTH_RECORD_MAX_GROUPS), (unsigned)b->replicas);
+    k_births_record<<<grid, BIRTH_BLOCK, 0, (hipStream_t)stream>>>(k);
+    DIE_CHECK_LAUNCH(who);
+    return DIE_OK;
+}
+
+extern "C" int die_births_record(int64_t n_slots, const void* ws, int64_t ws_bytes, int32_t* parent_of, int32_t* child_of, void* stream) {
+    DIE_REQUIRE(n_slots >= 1 && n_slots <= (int64_t)DIE_OWNER_SLOT_MASK, "die_births_record: %lld slots (1..%u)", (long long)n_slots,
+                DIE_OWNER_SLOT_MASK);
+    die_batch b{};
+    b.replicas = 1; b.agent_stride = n_slots; b.n[0] = n_slots;
+    return births_record_launch(&b, ws, ws_bytes, parent_of, child_of, stream, "die_births_record");
+}
+
+extern "C" int die_births_record_batch(const die_batch* b, const void* ws, int64_t ws_bytes, int32_t* parent_of, int32_t* child_of,
+                                       void* stream) {
+    return births_record_launch(b, ws, ws_bytes, parent_of, child_of, stream, "die_births_record_batch");
 }

@@ -16,6 +16,7 @@
 #define DIE_STREAM_CMAES 9u         // CMA-ES sampling (die_cmaes.hip): oracle/rng.py normals2(seed, generation, n, stream=9, scale=1)[0]
 #define DIE_STREAM_DROPOUT 10u      // agent dropout mask over cells (die_nca.hip): tests/dropout_model.py mask(seed, step, W, H, p)
 #define DIE_STREAM_BIRTH 11u        // a newborn's displacement from its parent (die_births.hip): tests/births_model.py, die_draw(world seed, world step, parent slot)
+#define DIE_STREAM_HEREDITY 12u     // the mutation of an inherited memory channel (die_heredity.hip): tests/heredity_model.py, die_draw(world seed, world step, parent slot | (m >> 2) << 32)
 
 struct die_u32x4 { uint32_t v[4]; };
 

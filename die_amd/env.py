@@ -199,6 +199,8 @@ class Env(_EnvBase):
         self._workspace = DataInitializer.workspace(self._field_size, self.agents.N, self.device)
         self._all_alive = bool(self.agents.alive.all().item()) and not self.dynamics.agents_born
         self._births_ws = None
+        self._births_pass = None            # the world step of the birth pass whose lists the workspace still holds (births_record)
+        self._births_consumed = False       # a pass ran and a later step has gone over it
         if self.dynamics.agents_born:       # (before the first step, like the re-sort's buffers)
             self._alloc_births_ws()
         self._steps = 0
@@ -336,6 +338,8 @@ class Env(_EnvBase):
         born = self.dynamics.agents_born
         if born:
             self._check_births_apply('step')        # (every refusal before any launch or state change)
+        if self._births_pass is not None:   # the record of an earlier pass ends with the step after it
+            self._births_pass, self._births_consumed = None, True
         self.medium.chem_node = None        # the field is about to change: an autograd handle of the chem plane ends here
         fused = binned = False
         burned = None
@@ -399,6 +403,9 @@ class Env(_EnvBase):
             self._apply_custom_cost(burned, result)
         if born:                            # the second half of _agent_lifecycle: agent arrays only, so the step's last launches
             self._launch_births(self._steps, result)
+            heir = getattr(action, '_heredity_agent', None)     # NeuralAutomataAgent.forward's mark (memory_inherit set): the
+            if heir is not None:                                # newborns receive their memory inside the step
+                heir.inherit_memory(self.births_record())
         self.medium.swap_chem()
         if self.dynamics.op_food_flow is not _identity_food_flow:
             self._food_flow()
@@ -871,6 +878,29 @@ class Env(_EnvBase):
         a = A.c_struct()
         _lib.check(_lib.lib.die_agent_births(C.byref(a), C.byref(p), self._seed & 0xFFFFFFFFFFFFFFFF, None if result is None else _ptr(result),
                                              _ptr(ws), ws.numel(), stream_ptr(self.device)), 'die_agent_births')
+        self._births_pass = int(world_step)
+
+    def births_record(self):
+        """Who was born to whom in the birth pass that just ran: a `die_amd.functional.BirthsRecord` — `parent_of`, `child_of`, two
+        (N,) int32 device tensors by slot id (the parent of a slot born in the pass, the child of a slot that bred in it, -1
+        otherwise), freshly allocated per call so that a graph may keep them, with the world seed and the world step the pass drew
+        at.  One launch (die_births_record), only when asked: a world nobody asks pays nothing.  Valid after a `step` (or
+        `apply_births()`) that ran the pass and until the next step; otherwise ValueError — no pass yet, a pass since consumed
+        by a later step, or a world without births.  What it is for: `NeuralAutomataAgent.inherit_memory(record)`."""
+        from .functional import BirthsRecord
+        if self._births_pass is None:
+            if self._births_consumed:
+                raise ValueError('births_record: the last birth pass was consumed by a later step (the record is valid until the next step)')
+            if not self.dynamics.agents_born:
+                raise ValueError('births_record: this world has no births (Dynamics(agents_born=False)) and apply_births() has not run')
+            raise ValueError('births_record: no birth pass yet (valid after a step)')
+        N = self.agents.N
+        if self._births_ws is None or self._births_ws[0] != N:
+            raise ValueError(f'births_record: the agents have {N} slots, the birth pass ran on another number')
+        ws = self._births_ws[1]
+        out = torch.empty((2, N), dtype=torch.int32, device=self.device)
+        _lib.check(_lib.lib.die_births_record(N, _ptr(ws), ws.numel(), _ptr(out[0]), _ptr(out[1]), stream_ptr(self.device)), 'die_births_record')
+        return BirthsRecord(out[0], out[1], (self._seed,), self._births_pass, (N,))
 
     def apply_births(self, step: Optional[int] = None, result: Optional[torch.Tensor] = None):
         """The birth pass of `Dynamics(agents_born=True)` alone (die_agent_births), for custom update cycles such as `_manual_step`

@@ -25,12 +25,19 @@
         die_signal_step_backward_batch backward): (R, W, H) byte planes, (R, K, W, H) fields of any strides.
         BatchedNeuralAutomataAgent.signalling_action composes them with the three above.
 
+    inherit_memory(memory, record, mode, mutation=0.0), inherit_memory_batch(memory, record, mode, mutation=0.0)
+        heredity (die_heredity.hip): what the newborns of one birth pass — `record`, a BirthsRecord from `Env.births_record()` /
+        `BatchedEnv.births_record()` — hold in their memory channels, (M, N) -> (M, N) or (R, M, Nmax) -> (R, M, Nmax), with a
+        `grad_fn` that keeps the record (die_memory_inherit on a clone forward, die_memory_inherit_backward backward).
+        `NeuralAutomataAgent.inherit_memory` / `BatchedNeuralAutomataAgent.inherit_memory` call them.
+
 `ConvolutionModel.forward_device` evaluates a whole wide stack through `conv2d_wide`; `BatchedNeuralAutomataAgent.forward_device`
 a population of them in one launch per layer (die_nca_wide_backward_batch backward).  There is no eager fallback: a shape the
 kernels do not take raises."""
 import ctypes as C
 from typing import Optional, Sequence, Tuple
 
+import numpy as np
 import torch as th
 
 from . import _lib
@@ -609,3 +616,125 @@ def signal_step_batch(field: th.Tensor, emission: th.Tensor, record: SignalRecor
     if field.shape[1] != emission.shape[1]:
         raise ValueError(f'field has {field.shape[1]} planes a replica, emission {emission.shape[1]}')
     return _SignalStepBatch.apply(field, emission, record, float(deposit), float(sigma), float(decay))
+
+
+# ---- heredity: the memory a newborn receives (die_heredity.hip) ---------------------------------------------------------------
+class BirthsRecord:
+    """Who was born to whom in one birth pass (die_births_record), by SLOT ID: `parent_of` and `child_of`, int32 device tensors of
+    shape (N,) — or (R, Nmax) for a BatchedEnv, the slots from n[r] on -1 — with parent_of[s] the parent of a slot born in the
+    pass and child_of[s] the child of a slot that bred in it, -1 otherwise; `seeds`, the world seed of every replica (`seed`: the
+    first, a stand-alone world's own), `step`, the world step the pass drew at, and `n`, the slots of every replica.  Freshly
+    allocated by every `births_record()` call, so a graph may keep it through later steps and resets."""
+    __slots__ = ('parent_of', 'child_of', 'seeds', 'step', 'n')
+
+    def __init__(self, parent_of, child_of, seeds, step, n):
+        self.parent_of, self.child_of = parent_of, child_of
+        self.seeds, self.step, self.n = tuple(int(q) for q in seeds), int(step), tuple(int(k) for k in n)
+
+    @property
+    def seed(self) -> int:
+        return self.seeds[0]
+
+    @property
+    def batched(self) -> bool:
+        return self.parent_of.dim() == 2
+
+    def _batch(self) -> _lib.Batch:
+        return _lib.Batch(len(self.n), 0, 0, self.parent_of.shape[1], 1, (C.c_int64 * 64)(*self.n))
+
+    def _seed_words(self):
+        return (C.c_uint64 * len(self.seeds))(*[q & 0xFFFFFFFFFFFFFFFF for q in self.seeds])
+
+
+def inherit_arguments(mode, mutation, what: str = 'inherit_memory'):
+    """(mode, mutation) checked — 'blank' or 'copy', and a real number a >= 0 that float32 holds, 0 unless the mode is 'copy' — or
+    the ValueError that says which is wrong."""
+    if not isinstance(mode, str) or mode not in _lib.INHERIT_MODES:
+        raise ValueError(f"{what}: memory_inherit={mode!r}: 'blank' or 'copy'")
+    if isinstance(mutation, (bool, np.bool_)) or not isinstance(mutation, (int, float, np.integer, np.floating)):
+        raise ValueError(f'{what}: memory_mutation={mutation!r}: a float >= 0')
+    a = float(mutation)
+    if not 0.0 <= a <= float(np.finfo(np.float32).max):
+        raise ValueError(f'{what}: memory_mutation={mutation!r}: a finite float >= 0 (float32)')
+    if a > 0.0 and mode != 'copy':
+        raise ValueError(f"{what}: memory_mutation={mutation!r} needs memory_inherit='copy' (a blank newborn has nothing to mutate)")
+    return mode, a
+
+
+def check_inherit_operands(what: str, memory, record, batched: bool, M: Optional[int] = None, contiguous: bool = False) -> None:
+    """A BirthsRecord of the right kind and a float32 memory of its shape on its device ((M, N), or (R, M, Nmax)), or the ValueError."""
+    if not isinstance(record, BirthsRecord) or record.batched != batched:
+        kind = 'BatchedEnv.births_record()' if batched else 'Env.births_record()'
+        raise ValueError(f'{what}: record must be the BirthsRecord of {kind}, got {type(record).__name__}' +
+                         (' of the other kind' if isinstance(record, BirthsRecord) else ''))
+    dev, lead = record.parent_of.device, tuple(record.parent_of.shape)
+    ok = isinstance(memory, th.Tensor) and memory.dtype == th.float32 and memory.device == dev and memory.dim() == len(lead) + 1 and \
+        (not contiguous or memory.is_contiguous())
+    if ok:
+        Mc = memory.shape[-2]
+        ok = 1 <= Mc <= _lib.MEMORY_MAX_CHANNELS and (M is None or Mc == M) and tuple(memory.shape) == lead[:-1] + (Mc, lead[-1])
+    if not ok:
+        want = lead[:-1] + ('M' if M is None else M, lead[-1])
+        got = (tuple(memory.shape), memory.dtype, str(memory.device)) if isinstance(memory, th.Tensor) else type(memory).__name__
+        raise ValueError(f"{what}: memory must be a {'contiguous ' if contiguous else ''}float32 tensor of shape "
+                         f"({', '.join(str(v) for v in want)}) on {dev}, got {got}")
+
+
+def inherit_memory_(memory: th.Tensor, record: BirthsRecord, mode: str, mutation: float) -> th.Tensor:
+    """die_memory_inherit / _batch IN PLACE on a contiguous memory; every argument has been checked by the caller."""
+    code, sp = _lib.INHERIT_MODES[mode], stream_ptr(memory.device)
+    M, N = memory.shape[-2], memory.shape[-1]
+    if record.batched:
+        b = record._batch()
+        _lib.check(_lib.lib.die_memory_inherit_batch(code, mutation, M, C.byref(b), _ptr(record.parent_of), _ptr(memory), record._seed_words(),
+                                                     record.step & 0xFFFFFFFF, sp), 'die_memory_inherit_batch')
+    else:
+        _lib.check(_lib.lib.die_memory_inherit(code, mutation, M, N, _ptr(record.parent_of), _ptr(memory), N, record.seed & 0xFFFFFFFFFFFFFFFF,
+                                               record.step & 0xFFFFFFFF, sp), 'die_memory_inherit')
+    return memory
+
+
+class _InheritMemory(th.autograd.Function):
+    """inherit_memory / inherit_memory_batch: a clone and the in-place kernel forward, the gather of die_memory_inherit_backward backward."""
+
+    @staticmethod
+    def forward(ctx, memory, record, mode, mutation):
+        ctx.record, ctx.mode = record, mode
+        return inherit_memory_(memory.detach().clone(memory_format=th.contiguous_format), record, mode, mutation)
+
+    @staticmethod
+    @th.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        r, code = ctx.record, _lib.INHERIT_MODES[ctx.mode]
+        g = grad.to(dtype=th.float32).contiguous()
+        out = th.empty_like(g)
+        M, N, sp = g.shape[-2], g.shape[-1], stream_ptr(g.device)
+        if r.batched:
+            b = r._batch()
+            _lib.check(_lib.lib.die_memory_inherit_backward_batch(code, M, C.byref(b), _ptr(r.parent_of), _ptr(r.child_of), _ptr(g), _ptr(out), sp),
+                       'die_memory_inherit_backward_batch')
+        else:
+            _lib.check(_lib.lib.die_memory_inherit_backward(code, M, N, _ptr(r.parent_of), _ptr(r.child_of), _ptr(g), _ptr(out), N, sp),
+                       'die_memory_inherit_backward')
+        return out, None, None, None
+
+
+def inherit_memory(memory: th.Tensor, record: BirthsRecord, mode: str, mutation: float = 0.0) -> th.Tensor:
+    """Heredity with a `grad_fn`: the (M, N) float32 memory by slot id as a step's read-out left it -> the memory after the
+    newborns of `record` (`Env.births_record()`) have received theirs.  For every child f of parent p: +0 ('blank'), the parent's
+    word ('copy'), or the parent's value plus `mutation` times a uniform draw in [-1, 1] from the births' own key and step
+    ('copy', mutation > 0); every other slot keeps its bits.  The input is left alone (the kernel runs on a clone).
+    Backward, one gather launch: a parent's gradient is its own plus its child's ('copy'; 'blank': its own), a child's +0, every
+    other slot's passes through — bit-reproducible."""
+    mode, mutation = inherit_arguments(mode, mutation)
+    check_inherit_operands('inherit_memory', memory, record, False)
+    return _InheritMemory.apply(memory, record, mode, mutation)
+
+
+def inherit_memory_batch(memory: th.Tensor, record: BirthsRecord, mode: str, mutation: float = 0.0) -> th.Tensor:
+    """`inherit_memory` for every replica of a BatchedEnv in one launch: (R, M, Nmax) -> (R, M, Nmax), `record` the
+    `BatchedEnv.births_record()` of the pass; replica r is `inherit_memory` on its own record and world seed, bit for bit, and the
+    padding slots from n[r] on pass through, values and gradients alike."""
+    mode, mutation = inherit_arguments(mode, mutation, 'inherit_memory_batch')
+    check_inherit_operands('inherit_memory_batch', memory, record, True)
+    return _InheritMemory.apply(memory, record, mode, mutation)

@@ -9,7 +9,7 @@ separable CMA-ES with stdev_init 0.1 and popsize 10 (die_amd.search.CMAES), the 
                                        [--epoch-iters 30] [--agents-die] [--agents-born] [--max-agents alive|full|tight|N]
                                        [--reseed S] [--reseed-stride 0] [--episodes 1] [--out saved_models/agent.pt] [--time]
                                        [--dropout P] [--dropout-seed S] [--dropout-stride K] [--init-from FILE]
-                                       [--stock-channel] [--memory-channels M]
+                                       [--stock-channel] [--memory-channels M [--memory-inherit blank|copy [--memory-mutation A]]]
                                        [--signal-channels K [--signal-sigma S --signal-decay D --signal-deposit G]]
 
 --init-from FILE starts the search from a saved agent (e.g. the one examples/imitate_agent.py fits by gradient descent): its
@@ -23,8 +23,10 @@ step.  With --agents-die / --agents-born that is the quantity that decides wheth
 
 --memory-channels M (1..8) trains recurrent agents (NeuralAutomataAgent(memory_channels=M)): every agent carries M values from one
 step to the next, read by the stack as M more observation planes and written as M more output planes.  The stack is then a wide
-stack (--hidden-channels defaults to the observation's width), every generation starts from blank memory, and --agents-born is
-refused (a newborn would inherit a dead agent's memory).
+stack (--hidden-channels defaults to the observation's width), every generation starts from blank memory, and --agents-born
+needs --memory-inherit {blank,copy} [--memory-mutation A] beside it: what a newborn's memory holds — blank, its parent's, or its
+parent's plus uniform noise of half-width A (NeuralAutomataAgent(memory_inherit=..., memory_mutation=A)).  Without
+a rule the combination stays refused (a newborn would inherit a dead agent's memory).
 
 --signal-channels K (1..8) trains agents that signal (NeuralAutomataAgent(signal_channels=K)): a field of K planes the stack reads as
 K more observation channels and writes through K more output planes at the cells the agents stand on; it diffuses (--signal-sigma),
@@ -195,8 +197,11 @@ def main():
     add_wide_arguments(p)
     args = p.parse_args()
     args.wide_kw = wide_keywords(args)
-    if not 0 <= args.memory_channels <= 8 or (args.memory_channels and args.agents_born):
-        p.error('--memory-channels in 0..8, and not together with --agents-born (a newborn would inherit a dead agent\'s memory)')
+    if not 0 <= args.memory_channels <= 8 or (args.memory_channels and args.agents_born and args.memory_inherit is None):
+        p.error('--memory-channels in 0..8, and together with --agents-born only with --memory-inherit blank|copy (without a rule a '
+                'newborn would inherit a dead agent\'s memory)')
+    if args.memory_inherit is not None and not args.memory_channels:
+        p.error('--memory-inherit needs --memory-channels M')
     if not 0 <= args.signal_channels <= 8:
         p.error('--signal-channels in 0..8')
     args.agents_die = lifecycle(args.agents_die, args.agents_born)      # (what the helpers hand to make_dynamics)

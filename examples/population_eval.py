@@ -4,7 +4,7 @@ all R worlds stepped together by die_amd.batch (L + 2 launches per step for an L
 
     python examples/population_eval.py [--replicas 10] [--size 96] [--iters 50] [--dynamics st-perlin-wide] [--generations 0] [--agents-die] [--agents-born]
                                        [--max-agents alive|full|tight|N] [--reseed S] [--episodes 1] [--compare]
-                                       [--dropout P] [--dropout-seed S] [--dropout-stride K] [--stock-channel] [--memory-channels M]
+                                       [--dropout P] [--dropout-seed S] [--dropout-stride K] [--stock-channel] [--memory-channels M [--memory-inherit blank|copy [--memory-mutation A]]]
                                        [--signal-channels K [--signal-sigma S --signal-decay D --signal-deposit G]]
 
 --stock-channel gives the candidates a fourth observation channel, `'agent_food'`: on every cell the stock of the agent standing
@@ -13,7 +13,10 @@ tell a starving agent from a well-fed one under --agents-die / --agents-born.
 
 --memory-channels M (1..8) gives every agent M values it carries from one step to the next (NeuralAutomataAgent(memory_channels=M)):
 the stack becomes a wide stack that reads them as M more observation planes and writes them as M more output planes (three more
-launches per batched step).  Every evaluation and every search generation starts from blank memory.  Not with --agents-born.
+launches per batched step).  Every evaluation and every search generation starts from blank memory.  With --agents-born it needs
+--memory-inherit {blank,copy} [--memory-mutation A]: what a newborn's memory holds (NeuralAutomataAgent(memory_inherit=...,
+memory_mutation=A): blank, its parent's, or its parent's plus uniform noise of half-width A; one more launch per batched step, two
+in the first step after a birth pass is asked for its record).
 
 --signal-channels K (1..8) gives the agents a field of K planes they write and read (NeuralAutomataAgent(signal_channels=K)): the
 stack, a wide stack, reads the planes as K more observation channels and emits into them through K more output planes at the
@@ -147,8 +150,12 @@ def add_wide_arguments(p):
     p.add_argument('--stock-channel', action='store_true', help="the candidates sense their own food stock: a last observation channel "
                                                                 "'agent_food' (with_stock_channel=True; one more launch per batched step)")
     p.add_argument('--memory-channels', type=int, default=0, metavar='M', help='values every agent carries between steps, 1..8 (memory_channels=M: '
-                                                                               'a wide stack, three more launches per batched step; not with '
-                                                                               '--agents-born)')
+                                                                               'a wide stack, three more launches per batched step; with '
+                                                                               '--agents-born it needs --memory-inherit)')
+    p.add_argument('--memory-inherit', choices=('blank', 'copy'), default=None, help="what a newborn's memory holds under --agents-born: "
+                                                                                      "blank, or a copy of its parent's (memory_inherit=...)")
+    p.add_argument('--memory-mutation', type=float, default=0.0, metavar='A', help="with --memory-inherit copy: uniform noise of half-width A "
+                                                                                   "added to the parent's values (memory_mutation=A)")
     p.add_argument('--signal-channels', type=int, default=0, metavar='K', help='planes of a field the agents write and read, 1..8 '
                                                                                '(signal_channels=K: a wide stack, two more launches per batched step)')
     p.add_argument('--signal-sigma', type=float, default=None, metavar='S', help="the signal field's gaussian sigma (default 0.5; radius int(4 S + .5) in 1..8)")
@@ -164,6 +171,8 @@ def wide_keywords(args):
         kw['with_stock_channel'] = True
     if getattr(args, 'memory_channels', 0):
         kw['memory_channels'] = args.memory_channels
+    if getattr(args, 'memory_inherit', None) is not None:
+        kw.update(memory_inherit=args.memory_inherit, memory_mutation=args.memory_mutation)
     if getattr(args, 'signal_channels', 0):
         kw['signal_channels'] = args.signal_channels
         for name in ('signal_sigma', 'signal_decay', 'signal_deposit'):
@@ -252,6 +261,8 @@ def main():
     N = slots(args.max_agents, args.size, args.dynamics, args.agents_die)
     if args.reseed is not None and N == 'alive':
         sys.exit("--reseed needs a fixed slot layout: --max-agents full, tight or a number")
+    if args.memory_channels and args.agents_born and args.memory_inherit is None:
+        p.error('--memory-channels with --agents-born needs --memory-inherit blank|copy (what a newborn\'s memory holds)')
     torch.manual_seed(args.seed)
     try:
         template = make_template(args.dropout, wide_keywords(args))

@@ -370,6 +370,54 @@ int die_agent_births(const die_agents* a, const die_births* p, uint64_t world_se
  * call; results[r] (may be NULL) gets replica r's number born.  Replica r ends exactly as die_agent_births on it alone. */
 int die_agent_births_batch(const die_agents* a, const die_batch* b, const die_births* p, const uint64_t* world_seeds,
                            die_step_result* results, void* workspace, int64_t workspace_bytes, void* stream);
+/* ---- The record of a birth pass, and heredity (die_births.hip, die_heredity.hip) ------------------------------
+ * Added within ABI 24: new symbols only, no existing struct or call changes, so DIE_ABI_VERSION stays 24.
+ *
+ * die_births_record — who was born to whom in the pass that JUST ran on this workspace (die_agent_births with n_slots slots;
+ * nothing may have written the workspace since): parent_of[s] = the parent's slot if s was born in the pass, else -1; child_of[s]
+ * = the child's slot if s bred in the pass, else -1; both n_slots int32 words.  One launch, a gather (every slot looks itself up
+ * in the pass's two ascending lists), launched only for a caller that asks.  Checked before the launch: null pointers, n_slots
+ * outside 1..DIE_OWNER_SLOT_MASK, a workspace smaller than die_births_workspace_bytes(1, n_slots) or not 4-byte aligned, outputs
+ * that overlap each other or the workspace. */
+int die_births_record(int64_t n_slots, const void* workspace, int64_t workspace_bytes, int32_t* parent_of, int32_t* child_of,
+                      void* stream);
+/* The same for the pass die_agent_births_batch ran: ONE launch for all replicas (the replica in blockIdx.y), replica r's words
+ * r * b->agent_stride on; the slots b->n[r] <= s < b->agent_stride are -1 in both arrays.  Checked as the pass checks its batch. */
+int die_births_record_batch(const die_batch* b, const void* workspace, int64_t workspace_bytes, int32_t* parent_of, int32_t* child_of,
+                            void* stream);
+
+/* die_memory_inherit — what a newborn's memory channels hold (NeuralAutomataAgent(memory_inherit=..., memory_mutation=a)), applied
+ * IN PLACE to the (memory_channels, n_slots) fp32 memory by slot id (row m at memory + m * row_stride) after a birth pass and
+ * after the step's read-out.  For every slot s with p = parent_of[s] >= 0 and every channel m:
+ *   DIE_INHERIT_BLANK                memory[m][s] = +0.0f
+ *   DIE_INHERIT_COPY, mutation == 0  memory[m][s] = memory[m][p], moved as a 32-bit word
+ *   DIE_INHERIT_COPY, mutation  > 0  memory[m][s] = fadd_rn(memory[m][p], fmul_rn(mutation, u)), u = (float)(int32)word * 2^-31,
+ *       word = word (m & 3) of Philox4x32-10(counter = (p, m >> 2, world_step, DIE_STREAM_HEREDITY = 12), key = world_seed) — the
+ *       births' key and step on their own stream; two separately rounded fp32 operations.
+ * Every other word is left alone (the parent keeps its memory).  One launch; parents and children are disjoint, so no word is
+ * read by one thread and written by another.  A record word outside 0..n_slots - 1 reads as -1.  Checked before the launch: null
+ * pointers, an unknown mode, memory_channels outside 1..DIE_MEMORY_MAX_CHANNELS, n_slots outside 1..DIE_OWNER_SLOT_MASK - 1,
+ * row_stride < n_slots, a mutation that is negative or not finite, a mutation > 0 with DIE_INHERIT_BLANK, a memory that overlaps
+ * the record. */
+#define DIE_INHERIT_BLANK 0
+#define DIE_INHERIT_COPY 1
+int die_memory_inherit(int32_t mode, float mutation, int32_t memory_channels, int64_t n_slots, const int32_t* parent_of, float* memory,
+                       int64_t row_stride, uint64_t world_seed, uint32_t world_step, void* stream);
+/* Every replica in ONE launch: memory the dense (R, memory_channels, b->agent_stride) array, parent_of (R, b->agent_stride) as
+ * die_births_record_batch writes it, world_seeds a HOST array of b->replicas keys read during the call (the births' own). */
+int die_memory_inherit_batch(int32_t mode, float mutation, int32_t memory_channels, const die_batch* b, const int32_t* parent_of,
+                             float* memory, const uint64_t* world_seeds, uint32_t world_step, void* stream);
+/* The adjoint, out of place, one launch, plain loads and stores (a parent has at most one child a pass: no atomics).  With the
+ * incoming gradient `grad` laid out as the memory, for every slot s and channel m:
+ *   child_of[s] >= 0 (a parent)   grad_memory[m][s] = grad[m][s] + grad[m][child_of[s]] (COPY: one fp32 add) or grad[m][s] (BLANK)
+ *   parent_of[s] >= 0 (a child)   +0.0f
+ *   neither                       grad[m][s], moved as a 32-bit word
+ * The mutation has unit Jacobian and does not appear.  Checked as die_memory_inherit, and: null child_of / grad / grad_memory, an
+ * output that overlaps the incoming gradient or the record.  The batched twin also passes a replica's padding slots through. */
+int die_memory_inherit_backward(int32_t mode, int32_t memory_channels, int64_t n_slots, const int32_t* parent_of, const int32_t* child_of,
+                                const float* grad, float* grad_memory, int64_t row_stride, void* stream);
+int die_memory_inherit_backward_batch(int32_t mode, int32_t memory_channels, const die_batch* b, const int32_t* parent_of,
+                                      const int32_t* child_of, const float* grad, float* grad_memory, void* stream);
 /* Decomposed step, second half: claim + feeding of die_agent_move_claim without the move. */
 int die_agent_claim_feed(const die_medium* m, const die_agents* a, const die_action* act, const die_dynamics* d,
                          void* workspace, int64_t workspace_bytes, void* stream);
