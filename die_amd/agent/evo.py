@@ -78,6 +78,14 @@ def _heredity_arguments(mode, mutation, memory_channels: int):
     return mode, mutation
 
 
+def check_given(what: str, name: str, t, want: tuple, device) -> None:
+    """A `signals` or `memory` tensor handed to `recurrent_action` / `signalling_action` (the agent's and the population's), or
+    the ValueError that says what it must be and what it got."""
+    if not isinstance(t, th.Tensor) or t.dtype != th.float32 or tuple(t.shape) != want or t.device != device:
+        got = (tuple(t.shape), t.dtype, str(t.device)) if isinstance(t, th.Tensor) else type(t).__name__
+        raise ValueError(f'{what}: {name} must be a {want} float32 tensor on {device}, got {got}')
+
+
 def _layer_arrays(li: int, w: th.Tensor, planes, dst: th.Tensor):
     """What a narrow layer launch takes beside its weights `w`: the input `planes` [(tensor, DIE_PLANE_* kind)] as a die_conv_plane
     array and the first cout planes of `dst` as a pointer array — or the ValueError of a weight that does not fit the planes."""
@@ -520,6 +528,13 @@ class NeuralAutomataAgent(TorchAgent):
             self._check_wide(what)
         self._check_stock(what)
 
+    def _check_boundary(self, prefix: str = ''):
+        """The boundaries the adjoint kernels take, before any launch (`prefix`: the caller's name where its texts carry one)."""
+        for k in self._model.conv_layers():
+            if k.padding_mode not in ('circular', 'zeros'):
+                raise NotImplementedError(f"{prefix}boundary={k.padding_mode!r} in differentiable mode: 'circular' or 'zeros' "
+                                          f"(sense() and forward() take all of {sorted(_lib.PAD_MODES)})")
+
     def _field_planes(self, medium) -> Dict[str, Any]:
         """The observation channels the medium itself holds, as first-layer source planes: channel -> (tensor, DIE_PLANE_* kind)."""
         medium._ensure_owner()
@@ -743,20 +758,20 @@ class NeuralAutomataAgent(TorchAgent):
         the stock channel (`with_stock_channel=True`) is refused the same way: its plane is piecewise constant in the weights."""
         self._check_differentiable('differentiable_sense')
         layers = self._model.conv_layers()
-        for k in layers:
-            if k.padding_mode not in ('circular', 'zeros'):
-                raise NotImplementedError(f"boundary={k.padding_mode!r} in differentiable mode: 'circular' or 'zeros' (sense() and "
-                                          f"forward() take all of {sorted(_lib.PAD_MODES)})")
+        self._check_boundary()
         medium.sensed()
         dev = medium.device
         weights = [k.weight.to(device=dev, dtype=th.float32).contiguous() for k in layers]
-        out = _DifferentiableSense.apply(self, medium, getattr(medium, 'chem_node', None), *weights)
-        p = self._model.agent_dropout.p
+        return self._dropout_applied(_DifferentiableSense.apply(self, medium, getattr(medium, 'chem_node', None), *weights), medium)
+
+    def _dropout_applied(self, sense: th.Tensor, medium) -> th.Tensor:
+        """What follows the stack of every differentiable call: with a `dropout_seed` the counter advances (the stack masked the
+        planes itself), without one the torch-RNG mask falls on all planes."""
         if self._dropout_seed is not None:
             self.dropout_step += 1
-        elif p > 0 and self._model.training:                     # the torch-RNG mask: a torch multiply, autograd's own business
-            out = out * self._model.agent_dropout(th.ones((medium.W, medium.H), device=dev))
-        return out
+        elif self._model.agent_dropout.p > 0 and self._model.training:     # a torch multiply, autograd's own business
+            sense = sense * self._model.agent_dropout(th.ones((medium.W, medium.H), device=medium.device))
+        return sense
 
     def differentiable_action(self, obs) -> th.Tensor:
         """`forward` with a `grad_fn`: (3, N) float32, rows dx, dy, deposit for EVERY slot in the agents' array order — the values
@@ -808,52 +823,11 @@ class NeuralAutomataAgent(TorchAgent):
         has `differentiable_action`); with NotImplementedError the stock channel (the adjoint calls do not take its plane kind), a
         decomposed medium, fp16 fields and the boundaries 'reflect' / 'replicate'; with ValueError a `memory` of the wrong shape,
         dtype or device."""
-        from ..functional import gather_memory, gather_scale, memory_planes, memory_record
         self._check_signals('recurrent_action')
-        M = self.memory_channels
-        if not M:
+        if not self.memory_channels:
             raise ValueError('recurrent_action: an agent without memory channels (memory_channels=0) is differentiated by '
                              'differentiable_action')
-        if self.with_stock_channel:
-            raise NotImplementedError('recurrent_action: no gradients with the stock channel (with_stock_channel=True): its plane is '
-                                      'piecewise constant in the weights and the adjoint kernels do not take its kind')
-        for k in self._model.conv_layers():
-            if k.padding_mode not in ('circular', 'zeros'):
-                raise NotImplementedError(f"recurrent_action: boundary={k.padding_mode!r} in differentiable mode: 'circular' or 'zeros' "
-                                          f"(sense() and forward() take all of {sorted(_lib.PAD_MODES)})")
-        agents, medium = obs
-        self._check_memory(medium=medium)
-        if medium.dtype != th.float32:
-            raise NotImplementedError(f'recurrent_action: fp32 fields only (this medium is {medium.dtype})')
-        if memory is None:
-            self._check_memory_slots(medium, agents)
-        elif not isinstance(memory, th.Tensor) or memory.dtype != th.float32 or tuple(memory.shape) != (M, agents.N) or \
-                memory.device != medium.device:
-            raise ValueError(f'recurrent_action: memory must be a ({M}, {agents.N}) float32 tensor on {medium.device}, got '
-                             f'{(tuple(memory.shape), memory.dtype, str(memory.device)) if isinstance(memory, th.Tensor) else type(memory).__name__}')
-        elif getattr(agents, 'global_slots', False):
-            raise NotImplementedError(f'memory_channels={M} on a decomposed world (die_amd/dist.py): its slots carry world ids')
-        medium.sensed()
-        dev, W, H = medium.device, medium.W, medium.H
-        if memory is None:
-            memory = self._memory_for(medium, agents)
-        record = memory_record(obs, self._stock_plane(medium, agents))
-        expanded = memory_planes(memory, record)
-        node = getattr(medium, 'chem_node', None)
-        src = {c: (node if c == 'chem1' and node is not None else medium.sel(c).float()) for c in self.obs_channels if not c.startswith('memory_')}
-        planes = th.stack([expanded[int(c[len('memory_'):])] if c.startswith('memory_') else src[c] for c in self.obs_channels])
-        p, training = self._model.agent_dropout.p, self._model.training
-        seeded = self._dropout_seed is not None
-        sense = self._model._stack_device(planes, (p, self._dropout_seed, self.dropout_step) if seeded and p > 0 and training else None)
-        if seeded:
-            self.dropout_step += 1
-        elif p > 0 and training:                                 # the torch-RNG mask: a torch multiply, autograd's own business
-            sense = sense * self._model.agent_dropout(th.ones((W, H), device=dev))
-        self._sense_output = sense.detach()[:3]
-        action = gather_scale(sense[:3], obs, self.action_coefs)
-        memory_next = gather_memory(sense[3:], record)
-        self.memory = memory_next.detach().clone()               # the agent's own copy, not the graph's tensor
-        self._memory_rebind = False
+        action, _, memory_next = self._stateful_action('recurrent_action', obs, None, memory)
         return action, memory_next
 
     def signalling_action(self, obs, signals: Optional[th.Tensor] = None, memory: Optional[th.Tensor] = None):
@@ -886,47 +860,54 @@ class NeuralAutomataAgent(TorchAgent):
         a `signals` or `memory` of the wrong shape, dtype or device, and a medium of another shape than the one `self.signals` is
         bound to (until `reset_signals()`).  Populations have the batched twin, `BatchedNeuralAutomataAgent.signalling_action`: one
         launch per kernel for all replicas, the same bits per replica."""
-        from ..functional import gather_memory, gather_scale, memory_planes, memory_record, signal_record, signal_step
-        K, M = self.signal_channels, self.memory_channels
-        if not K:
+        if not self.signal_channels:
             raise ValueError('signalling_action: an agent without signal channels (signal_channels=0) is differentiated by '
                              'recurrent_action (memory channels) or differentiable_action')
-        if self.with_stock_channel:
-            raise NotImplementedError('signalling_action: no gradients with the stock channel (with_stock_channel=True): its plane is '
-                                      'piecewise constant in the weights and the adjoint kernels do not take its kind')
-        for k in self._model.conv_layers():
-            if k.padding_mode not in ('circular', 'zeros'):
-                raise NotImplementedError(f"signalling_action: boundary={k.padding_mode!r} in differentiable mode: 'circular' or 'zeros' "
-                                          f"(sense() and forward() take all of {sorted(_lib.PAD_MODES)})")
+        return self._stateful_action('signalling_action', obs, signals, memory)
+
+    def _check_stateful(self, what: str, obs, signals, memory) -> None:
+        """Every refusal `recurrent_action` and `signalling_action` share, in their one order, before any launch (`what`: the
+        caller's name, the prefix of the texts).  On a decomposed medium the signal channels speak where the agent has them, else
+        the memory channels; a field bound to another shape speaks last."""
+        K, M = self.signal_channels, self.memory_channels
+        self._check_stock(what)
+        self._check_boundary(f'{what}: ')
         agents, medium = obs
         if getattr(medium, 'world', None) is not None:
-            raise NotImplementedError(f'signal_channels={K} on a decomposed medium (die_amd/dist.py): the signal field is kept for '
-                                      'periodic single-tile planes only')
+            self._check_signals(medium=medium)
+            self._check_memory(medium=medium)
         if medium.dtype != th.float32:
-            raise NotImplementedError(f'signalling_action: fp32 fields only (this medium is {medium.dtype})')
-        if signals is not None and (not isinstance(signals, th.Tensor) or signals.dtype != th.float32 or
-                                    tuple(signals.shape) != (K, medium.W, medium.H) or signals.device != medium.device):
-            raise ValueError(f'signalling_action: signals must be a ({K}, {medium.W}, {medium.H}) float32 tensor on {medium.device}, got '
-                             f'{(tuple(signals.shape), signals.dtype, str(signals.device)) if isinstance(signals, th.Tensor) else type(signals).__name__}')
+            raise NotImplementedError(f'{what}: fp32 fields only (this medium is {medium.dtype})')
+        if signals is not None:
+            check_given(what, 'signals', signals, (K, medium.W, medium.H), medium.device)
         if memory is not None and not M:
-            raise ValueError('signalling_action: memory given to an agent without memory channels (memory_channels=0)')
+            raise ValueError(f'{what}: memory given to an agent without memory channels (memory_channels=0)')
         if M and memory is None:
             self._check_memory_slots(medium, agents)
-        elif M and (not isinstance(memory, th.Tensor) or memory.dtype != th.float32 or tuple(memory.shape) != (M, agents.N) or
-                    memory.device != medium.device):
-            raise ValueError(f'signalling_action: memory must be a ({M}, {agents.N}) float32 tensor on {medium.device}, got '
-                             f'{(tuple(memory.shape), memory.dtype, str(memory.device)) if isinstance(memory, th.Tensor) else type(memory).__name__}')
-        elif M and getattr(agents, 'global_slots', False):
-            raise NotImplementedError(f'memory_channels={M} on a decomposed world (die_amd/dist.py): its slots carry world ids')
+        elif M:
+            check_given(what, 'memory', memory, (M, agents.N), medium.device)
+            if getattr(agents, 'global_slots', False):
+                raise NotImplementedError(f'memory_channels={M} on a decomposed world (die_amd/dist.py): its slots carry world ids')
         self._check_signals(medium=medium)                       # a field bound to another shape: ValueError until reset_signals()
+
+    def _stateful_action(self, what: str, obs, signals, memory):
+        """The one body of `recurrent_action` (K = 0: no field, `signals_next` None) and `signalling_action`: the refusals, the
+        standing plane and the records, the expand, the stack, the read-outs, the agent's own copies."""
+        from ..functional import gather_memory, gather_scale, memory_planes, memory_record, signal_record, signal_step
+        K, M = self.signal_channels, self.memory_channels
+        self._check_stateful(what, obs, signals, memory)
+        agents, medium = obs
         medium.sensed()
-        dev, W, H = medium.device, medium.W, medium.H
-        own = self._signals_for(medium)                          # allocated or bound as `forward` does it
-        field = own if signals is None else signals
+        field = None
+        if K:
+            own = self._signals_for(medium)                      # allocated or bound as `forward` does it
+            field = own if signals is None else signals
         if M and memory is None:
             memory = self._memory_for(medium, agents)
-        standing = self._standing = self._stock_plane(medium, agents)
-        cells = signal_record(obs, standing)
+        standing = self._stock_plane(medium, agents)
+        if K:
+            self._standing = standing
+        cells = signal_record(obs, standing) if K else None
         record = memory_record(obs, standing) if M else None
         expanded = memory_planes(memory, record) if M else None
         node = getattr(medium, 'chem_node', None)
@@ -939,20 +920,18 @@ class NeuralAutomataAgent(TorchAgent):
             return node if c == 'chem1' and node is not None else medium.sel(c).float()
 
         planes = th.stack([plane(c) for c in self.obs_channels])
-        p, training = self._model.agent_dropout.p, self._model.training
-        seeded = self._dropout_seed is not None
-        sense = self._model._stack_device(planes, (p, self._dropout_seed, self.dropout_step) if seeded and p > 0 and training else None)
-        if seeded:
-            self.dropout_step += 1
-        elif p > 0 and training:                                 # the torch-RNG mask: a torch multiply, autograd's own business
-            sense = sense * self._model.agent_dropout(th.ones((W, H), device=dev))
+        p, seed = self._model.agent_dropout.p, self._dropout_seed
+        masked = seed is not None and p > 0 and self._model.training
+        sense = self._dropout_applied(self._model._stack_device(planes, (p, seed, self.dropout_step) if masked else None), medium)
         self._sense_output = sense.detach()[:3]
         action = gather_scale(sense[:3], obs, self.action_coefs)
-        deposit, sigma, decay = self.signal_constants
-        signals_next = signal_step(field, sense[3:3 + K], cells, deposit=deposit, sigma=sigma, decay=decay)
-        memory_next = gather_memory(sense[3 + K:], record) if M else None
-        self.signals = signals_next.detach().clone()             # the agent's own copies, not the graph's tensors
+        signals_next = memory_next = None
+        if K:
+            deposit, sigma, decay = self.signal_constants
+            signals_next = signal_step(field, sense[3:3 + K], cells, deposit=deposit, sigma=sigma, decay=decay)
+            self.signals = signals_next.detach().clone()         # the agent's own copies, not the graph's tensors
         if M:
+            memory_next = gather_memory(sense[3 + K:], record)
             self.memory = memory_next.detach().clone()
             self._memory_rebind = False
         return action, signals_next, memory_next

@@ -60,11 +60,12 @@ import torch
 from torch.nn.utils import parameters_to_vector, vector_to_parameters
 
 from . import _lib
-from .agent.evo import NeuralAutomataAgent
+from .agent.evo import NeuralAutomataAgent, check_given
 from .agent.gradient import join64, split64
 from .data_init import DeviceFoodFlow, device_flow_kind, food_spec_from_seed
 from .device_array import Q32, DeviceAction, _ptr, stream_ptr
 from .env import BoundaryCondition, Dynamics, Env, _identity_food_flow, linear_action_cost
+from .functional import _bare_medium
 
 
 class BatchedEnv:
@@ -1412,6 +1413,11 @@ class BatchedNeuralAutomataAgent(_Population):
         return nca
 
     # ------------------------------------------------------------------ the differentiable twins (die_nca_grad.hip, batched)
+    def _refuse_large_worlds(self, what: str, alone: str) -> None:
+        if self.env.per_replica:
+            raise NotImplementedError(f'{what}: large worlds (per_replica) are not batched — a large world fills the GPU '
+                                      f'through the stand-alone {alone}')
+
     def _check_differentiable(self, parameters: Optional[torch.Tensor], what: str = 'differentiable mode') -> torch.Tensor:
         """Every refusal of a differentiable call, before anything is launched; returns the matrix the call reads.  `what`: the
         word the messages carry — 'differentiable mode' for the narrow calls, 'forward_device' for the wide twin, which takes a wide
@@ -1422,11 +1428,8 @@ class BatchedNeuralAutomataAgent(_Population):
             raise ValueError('forward_device: a narrow population (hidden_channels and hidden_activation both None) is differentiated '
                              'by differentiable_sense')
         env = self.env
-        if env.per_replica:
-            alone = 'ConvolutionModel.forward_device (replica_agent(r).model)' if wide else \
-                'NeuralAutomataAgent.differentiable_action (replica_agent(r))'
-            raise NotImplementedError(f'{what}: large worlds (per_replica) are not batched — a large world fills the GPU '
-                                      f'through the stand-alone {alone}')
+        self._refuse_large_worlds(what, 'ConvolutionModel.forward_device (replica_agent(r).model)' if wide else
+                                  'NeuralAutomataAgent.differentiable_action (replica_agent(r))')
         if self._arch['boundary'][0] not in ('circular', 'zeros'):
             raise NotImplementedError(f"boundary={self._arch['boundary'][0]!r} in {what}: 'circular' or 'zeros' (step() "
                                       f"takes all of {sorted(_lib.PAD_MODES)})")
@@ -1438,7 +1441,7 @@ class BatchedNeuralAutomataAgent(_Population):
     def _differentiable(self, parameters: Optional[torch.Tensor], what: str) -> torch.Tensor:
         """`differentiable_sense` and `forward_device` alike: the refusals, the graph's node, the dropout counter."""
         p = self._check_differentiable(parameters, what)
-        out = _BatchedSense.apply(self, p, self.env.chem_node)
+        out = _BatchedSense.apply(self, p, self.env.chem_node, None, None)
         if self.dropout_seed is not None:
             self.dropout_step += 1
         return out
@@ -1519,41 +1522,12 @@ class BatchedNeuralAutomataAgent(_Population):
         change: a population without memory (ValueError: it has `forward_device`); with NotImplementedError the stock channel,
         large worlds (`per_replica`), fp16 fields, 'reflect' / 'replicate' and an unseeded `p_agent_dropout` > 0 in training
         mode; with ValueError a `memory` of the wrong shape, dtype or device."""
-        from .functional import memory_planes_batch, memory_record_batch
         if self._signal_channels:
             self.template._check_signals('recurrent_action')
-        M, env = self._memory_channels, self.env
-        if not M:
+        if not self._memory_channels:
             raise ValueError('recurrent_action: a population without memory channels (memory_channels=0) is differentiated by '
                              'forward_device / differentiable_action')
-        if self._stock_channel:
-            raise NotImplementedError('recurrent_action: no gradients with the stock channel (with_stock_channel=True): its plane is '
-                                      'piecewise constant in the weights and the adjoint kernels do not take its kind')
-        if env.per_replica:
-            raise NotImplementedError('recurrent_action: large worlds (per_replica) are not batched — a large world fills the GPU '
-                                      'through the stand-alone NeuralAutomataAgent.recurrent_action (replica_agent(r))')
-        if env.dtype != torch.float32:
-            raise NotImplementedError(f'recurrent_action: fp32 fields only (this batch holds {env.dtype})')
-        if self._arch['boundary'][0] not in ('circular', 'zeros'):
-            raise NotImplementedError(f"recurrent_action: boundary={self._arch['boundary'][0]!r} in differentiable mode: 'circular' or "
-                                      f"'zeros' (step() takes all of {sorted(_lib.PAD_MODES)})")
-        self._check_step(env)
-        p = self.parameters if parameters is None else parameters
-        self._check_parameters(p)
-        want = (self.R, M, env.Nmax)
-        if memory is None:
-            memory = self.memory
-        elif not isinstance(memory, torch.Tensor) or memory.dtype != torch.float32 or tuple(memory.shape) != want or memory.device != env.device:
-            got = (tuple(memory.shape), memory.dtype, str(memory.device)) if isinstance(memory, torch.Tensor) else type(memory).__name__
-            raise ValueError(f'recurrent_action: memory must be a {want} float32 tensor on {env.device}, got {got}')
-        record = memory_record_batch(self)
-        expanded = memory_planes_batch(memory, record)
-        sense = _BatchedMemorySense.apply(self, p, env.chem_node, expanded)
-        if self.dropout_seed is not None:
-            self.dropout_step += 1
-        action, memory_next = _BatchedRecurrentReadOut.apply(sense, self, record)
-        with torch.no_grad():
-            self.memory.copy_(memory_next)          # the population's own copy, not the graph's tensor
+        action, _, memory_next = self._stateful_action('recurrent_action', None, memory, parameters)
         return action, memory_next
 
     def signalling_action(self, signals: Optional[torch.Tensor] = None, memory: Optional[torch.Tensor] = None,
@@ -1589,58 +1563,69 @@ class BatchedNeuralAutomataAgent(_Population):
         / `forward_device`); with NotImplementedError the stock channel, large worlds (`per_replica`), fp16 fields, 'reflect' /
         'replicate' and an unseeded `p_agent_dropout` > 0 in training mode; with ValueError a `signals` or `memory` of the wrong
         shape, dtype, device or type, and a `memory` given to a population without memory channels."""
-        from .functional import gather_memory_batch, memory_planes_batch, memory_record_batch, signal_record_batch, signal_step_batch
-        from .functional import _standing_planes_batch
-        K, M, env = self._signal_channels, self._memory_channels, self.env
-        if not K:
+        if not self._signal_channels:
             raise ValueError('signalling_action: a population without signal channels (signal_channels=0) is differentiated by '
                              'recurrent_action (memory channels) or forward_device / differentiable_action')
+        return self._stateful_action('signalling_action', signals, memory, parameters)
+
+    def _check_stateful(self, what: str, parameters: Optional[torch.Tensor]) -> torch.Tensor:
+        """Every refusal `recurrent_action` and `signalling_action` share, before anything is launched (`what`: the caller's name,
+        the prefix of the texts and the stand-alone method that large worlds are sent to); returns the matrix the call reads."""
+        env = self.env
         if self._stock_channel:
-            raise NotImplementedError('signalling_action: no gradients with the stock channel (with_stock_channel=True): its plane is '
+            raise NotImplementedError(f'{what}: no gradients with the stock channel (with_stock_channel=True): its plane is '
                                       'piecewise constant in the weights and the adjoint kernels do not take its kind')
-        if env.per_replica:
-            raise NotImplementedError('signalling_action: large worlds (per_replica) are not batched — a large world fills the GPU '
-                                      'through the stand-alone NeuralAutomataAgent.signalling_action (replica_agent(r))')
+        self._refuse_large_worlds(what, f'NeuralAutomataAgent.{what} (replica_agent(r))')
         if env.dtype != torch.float32:
-            raise NotImplementedError(f'signalling_action: fp32 fields only (this batch holds {env.dtype})')
+            raise NotImplementedError(f'{what}: fp32 fields only (this batch holds {env.dtype})')
         if self._arch['boundary'][0] not in ('circular', 'zeros'):
-            raise NotImplementedError(f"signalling_action: boundary={self._arch['boundary'][0]!r} in differentiable mode: 'circular' or "
+            raise NotImplementedError(f"{what}: boundary={self._arch['boundary'][0]!r} in differentiable mode: 'circular' or "
                                       f"'zeros' (step() takes all of {sorted(_lib.PAD_MODES)})")
         self._check_step(env)
         p = self.parameters if parameters is None else parameters
         self._check_parameters(p)
+        return p
 
-        def refuse(name, t, want):
-            got = (tuple(t.shape), t.dtype, str(t.device)) if isinstance(t, torch.Tensor) else type(t).__name__
-            raise ValueError(f'signalling_action: {name} must be a {want} float32 tensor on {env.device}, got {got}')
-
-        want = (self.R, K, env.W, env.H)
-        if signals is not None and (not isinstance(signals, torch.Tensor) or signals.dtype != torch.float32 or
-                                    tuple(signals.shape) != want or signals.device != env.device):
-            refuse('signals', signals, want)
+    def _stateful_action(self, what: str, signals, memory, parameters):
+        """The one body of `recurrent_action` (K = 0: no field, `signals_next` None) and `signalling_action`: the refusals, the
+        standing planes and the records, the expand, the stack (`_BatchedSense`), the read-outs, the population's own copies.
+        One branch: without a field the read-out is the fused node `_BatchedRecurrentReadOut` — ONE gradient buffer that its two
+        scatters fill — with a field three nodes whose gradients autograd adds; other launches and another order of sums, so
+        neither form replaces the other bit for bit."""
+        from .functional import (_standing_planes_batch, gather_memory_batch, memory_planes_batch, memory_record_batch,
+                                 signal_record_batch, signal_step_batch)
+        K, M, env = self._signal_channels, self._memory_channels, self.env
+        p = self._check_stateful(what, parameters)
+        if signals is not None:
+            check_given(what, 'signals', signals, (self.R, K, env.W, env.H), env.device)
         if memory is not None and not M:
-            raise ValueError('signalling_action: memory given to a population without memory channels (memory_channels=0)')
-        want = (self.R, M, env.Nmax)
-        if memory is not None and (not isinstance(memory, torch.Tensor) or memory.dtype != torch.float32 or
-                                   tuple(memory.shape) != want or memory.device != env.device):
-            refuse('memory', memory, want)
-        # the fields as the launches read them, (K, R, W, H); the population's own are copied: they are written below, the graph's stay
-        field = self._signals.clone() if signals is None else signals.permute(1, 0, 2, 3).contiguous()
+            raise ValueError(f'{what}: memory given to a population without memory channels (memory_channels=0)')
+        if memory is not None:
+            check_given(what, 'memory', memory, (self.R, M, env.Nmax), env.device)
+        field = None
+        if K:
+            # the fields as the launches read them, (K, R, W, H); the population's own are copied: they are written below, the graph's stay
+            field = self._signals.clone() if signals is None else signals.permute(1, 0, 2, 3).contiguous()
         if M and memory is None:
             memory = self.memory
         standing = _standing_planes_batch(self)
-        cells = signal_record_batch(self, standing)
+        cells = signal_record_batch(self, standing) if K else None
         record = memory_record_batch(self, standing) if M else None
         expanded = memory_planes_batch(memory, record) if M else None
-        sense = _BatchedSignalSense.apply(self, p, env.chem_node, field, expanded)
+        sense = _BatchedSense.apply(self, p, env.chem_node, field, expanded)
         if self.dropout_seed is not None:
             self.dropout_step += 1
-        action = _BatchedReadOut.apply(sense[:, :3], self)
-        deposit, sigma, decay = self.template.signal_constants
-        signals_next = signal_step_batch(field.permute(1, 0, 2, 3), sense[:, 3:3 + K], cells, deposit=deposit, sigma=sigma, decay=decay)
-        memory_next = gather_memory_batch(sense[:, 3 + K:], record) if M else None
+        signals_next = None
+        if not K:
+            action, memory_next = _BatchedRecurrentReadOut.apply(sense, self, record)
+        else:
+            action = _BatchedReadOut.apply(sense[:, :3], self)
+            deposit, sigma, decay = self.template.signal_constants
+            signals_next = signal_step_batch(field.permute(1, 0, 2, 3), sense[:, 3:3 + K], cells, deposit=deposit, sigma=sigma, decay=decay)
+            memory_next = gather_memory_batch(sense[:, 3 + K:], record) if M else None
         with torch.no_grad():                       # the population's own copies, not the graph's tensors
-            self._signals.copy_(signals_next.permute(1, 0, 2, 3))
+            if K:
+                self._signals.copy_(signals_next.permute(1, 0, 2, 3))
             if M:
                 self.memory.copy_(memory_next)
         return action, signals_next, memory_next
@@ -1659,7 +1644,7 @@ class BatchedNeuralAutomataAgent(_Population):
 
 def _geometry(env: BatchedEnv) -> _lib.Medium:
     """A die_medium that only says how large a replica is (the read-out's cell arithmetic)."""
-    return _lib.Medium(env.W, env.H, _lib.DIE_F32, 1, None, None, None, None, 0, 0, 0, 0, 0, 0, 0, 0, None)
+    return _bare_medium(env.W, env.H, 1)
 
 
 class _BatchedFieldStep(torch.autograd.Function):
@@ -1692,34 +1677,65 @@ class _BatchedFieldStep(torch.autograd.Function):
         return grad_chem if ctx.needs_input_grad[0] else None, grad_action, None, None, None
 
 
+# the stack's entry points by the kind of population: (store, the adjoint's workspace query, the adjoint).  The stateful kinds'
+# calls end in the planes their first layer reads besides the field's: (mem_planes, M) and (mem_planes, M, signal_planes, K)
+_SENSE_CALLS = {
+    'narrow': ('die_nca_sense_batch_store', 'die_nca_backward_batch_workspace_bytes', 'die_nca_backward_batch'),    # (or `_inputs`, below)
+    'wide': ('die_nca_wide_sense_batch_store', 'die_nca_wide_backward_batch_workspace_bytes', 'die_nca_wide_backward_batch'),
+    'memory': ('die_nca_wide_sense_batch_store_memory', 'die_nca_wide_backward_batch_memory_workspace_bytes',
+               'die_nca_wide_backward_batch_memory'),
+    'signal': ('die_nca_wide_sense_batch_store_signal', 'die_nca_wide_backward_batch_signal_workspace_bytes',
+               'die_nca_wide_backward_batch_signal'),
+}
+
+
+def _sense_kind(pop, K: int, M: int) -> str:
+    return 'signal' if K else 'memory' if M else 'wide' if pop._wide else 'narrow'
+
+
+def _state_planes(K: int, M: int, field, mem_planes) -> tuple:
+    """What the stateful kinds' three calls end in (nothing for a narrow or a plain wide stack)."""
+    memory = (_ptr(mem_planes) if M else None, M)
+    return memory + (_ptr(field), K) if K else memory if M else ()
+
+
 class _BatchedSense(torch.autograd.Function):
-    """BatchedNeuralAutomataAgent.differentiable_sense and, for a population of wide stacks (`pop._wide`), forward_device.  Narrow:
-    die_nca_sense_batch_store forward, die_nca_backward_batch backward — or, with the env's chem node as an input that needs a
-    gradient, die_nca_backward_batch_inputs, whose chem channel is the node's gradient.  Wide: die_nca_wide_sense_batch_store and
-    die_nca_wide_backward_batch, ONE call which is given `grad_in` for such a node and null without one."""
+    """The stack of every differentiable call of a BatchedNeuralAutomataAgent, ONE node: differentiable_sense (narrow),
+    forward_device (wide), recurrent_action (a wide stack whose first layer also reads the M expanded memory planes of every replica,
+    `mem_planes`, and whose last layer gives M planes more) and signalling_action (the K signal planes too, `field`, the (K, R, W, H)
+    contiguous field as the launches read it, ahead of the memory's).  `field` / `mem_planes` are None where the population has no
+    such channels.  The entry points: `_SENSE_CALLS`.  A narrow stack has two adjoints — die_nca_backward_batch, or with the env's chem
+    node as an input that needs a gradient die_nca_backward_batch_inputs; every wide kind ONE, whose `grad_in` is null where nothing
+    asks for it.  Returns (R, 3 + K + M, W, H); the backward hands the (C, P) gradient to `parameters`, the chem channel of the first
+    layer's input gradient to the env's chem node, its K signal channels to `field` and its M memory channels to the expand —
+    views, in their (·, R, W, H) shapes."""
 
     @staticmethod
-    def forward(ctx, pop, parameters, chem_node=None):
+    def forward(ctx, pop, parameters, chem_node, field, mem_planes):
         env = pop.env
         R, W, H, L, dev, Cm = env.R, env.W, env.H, len(pop._layers), env.device, pop._channels
+        K, M = (pop._signal_channels if field is not None else 0), (pop._memory_channels if mem_planes is not None else 0)
         with_agents = pop._arch['with_agent_channel']
         # as they are now: the worlds will be stepped (the claim plane only where the first layer reads it)
         planes = [env.food.clone(), env.chem.clone()] + ([env.owner.clone()] if with_agents else [])
+        # (M, R, W, H): the expand's own storage, as the launch reads it
+        state = ([field] if K else []) + ([mem_planes.contiguous()] if M else [])
         store = torch.empty((L, R, Cm, W, H), dtype=torch.float32, device=dev)
         drop = pop._dropout()
         masked = None if drop is None else torch.empty((R, Cm, W, H), dtype=torch.float32, device=dev)
+        # (the stateful calls refuse fp16 fields before they come here)
         ctx.epoch, ctx.fdt = env.epoch, _lib.DIE_F32 if env.dtype == torch.float32 else _lib.DIE_F16
-        ctx.batch, ctx.pop, ctx.size = env._batch_struct(), pop, (R, W, H, L)
+        ctx.batch, ctx.pop, ctx.size, ctx.channels = env._batch_struct(), pop, (R, W, H, L), (K, M)
         ctx.drop = None if drop is None else (drop.p, drop.seed, drop.seed_stride, drop.step)
         m = _BatchedSense._medium(ctx, planes)
         layers, nca = pop._nca_batch(parameters.data_ptr(), ctx.epoch)
-        name = 'die_nca_wide_sense_batch_store' if pop._wide else 'die_nca_sense_batch_store'
+        name = _SENSE_CALLS[_sense_kind(pop, K, M)][0]
         _lib.check(getattr(_lib.lib, name)(C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), store.numel() * 4,
                                            None if masked is None else _ptr(masked), None if drop is None else C.byref(drop),
-                                           stream_ptr(dev)), name)
+                                           *_state_planes(K, M, field, state[-1] if M else None), stream_ptr(dev)), name)
         # everything the backward reads goes through save_for_backward: freed with the graph after a backward without retain_graph
-        ctx.save_for_backward(parameters, store, *planes)
-        return (store[L - 1] if masked is None else masked)[:, :3]
+        ctx.save_for_backward(parameters, store, *state, *planes)
+        return (store[L - 1] if masked is None else masked)[:, :3 + K + M]
 
     @staticmethod
     def _medium(ctx, planes) -> _lib.Medium:
@@ -1730,35 +1746,40 @@ class _BatchedSense(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad):
+        (K, M), (R, W, H, L) = ctx.channels, ctx.size
         parameters, store, *planes = ctx.saved_tensors
-        R, W, H, L = ctx.size
+        field = planes.pop(0) if K else None
+        mem_planes = planes.pop(0) if M else None
         pop, dev = ctx.pop, store.device
-        g = grad.to(dtype=torch.float32).contiguous()               # (R, 3, W, H): three planes per replica
+        kind = _sense_kind(pop, K, M)
+        _, query, name = _SENSE_CALLS[kind]
+        state = _state_planes(K, M, field, mem_planes)
+        g = grad.to(dtype=torch.float32).contiguous()               # (R, 3 + K + M, W, H)
         m = _BatchedSense._medium(ctx, planes)
         layers, nca = pop._nca_batch(parameters.data_ptr(), ctx.epoch)
-        if pop._wide:
-            need = int(_lib.lib.die_nca_wide_backward_batch_workspace_bytes(W, H, R, C.byref(nca)))
-            if need < 0:
-                raise ValueError('a stack or shape die_nca_wide_backward_batch does not take')
-        else:
-            need = int(_lib.lib.die_nca_backward_batch_workspace_bytes(W, H, R, L))
+        need = int(getattr(_lib.lib, query)(W, H, R, L if kind == 'narrow' else C.byref(nca), *state[1::2]))
+        if need < 0:
+            raise ValueError(f'a stack or shape {name} does not take')
         ws = torch.empty((need // 4,), dtype=torch.float32, device=dev)
         out = torch.empty_like(parameters)                          # (C, P): every element is written (the layers tile a row)
         drop = None if ctx.drop is None else _lib.NcaDropout(*ctx.drop, 0)
-        args = (C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), _ptr(g), 3 * W * H, _ptr(out), pop.P,
+        args = (C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), _ptr(g), (3 + K + M) * W * H, _ptr(out), pop.P,
                 None if drop is None else C.byref(drop), _ptr(ws), need)
-        # the first layer's inputs are ([agents,] food, chem): food and the claims are constants of the parameters, chem is the node;
-        # without a node that needs a gradient (none, or a leaf that asks for nothing) no input gradient is computed
-        cin = len(planes)
-        grad_in = torch.empty((R, cin, W, H), dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
-        if pop._wide:                               # one call, `grad_in` nullable
-            name, args = 'die_nca_wide_backward_batch', args + (_ptr(grad_in), cin * W * H)
-        elif grad_in is None:
-            name = 'die_nca_backward_batch'
-        else:
+        # the first layer's inputs are ([agents,] food, chem, signal_0 .., memory_0 ..): food and the claims are constants of the
+        # parameters, chem is the env's node, the signal planes the incoming field, the memory planes the expand's output; with none
+        # of them asking for a gradient (no node, or a leaf that asks for nothing) no input gradient is computed
+        to_node, to_field, to_memory = ctx.needs_input_grad[2:5]
+        first = len(planes)                                         # the signal planes' first channel
+        cin = first + K + M
+        grad_in = torch.empty((R, cin, W, H), dtype=torch.float32, device=dev) if to_node or to_field or to_memory else None
+        if kind != 'narrow':                        # one call, `grad_in` nullable
+            args += (_ptr(grad_in), cin * W * H, *state)
+        elif grad_in is not None:
             name, args = 'die_nca_backward_batch_inputs', args + (_ptr(grad_in), cin * W * H)
         _lib.check(getattr(_lib.lib, name)(*args, stream_ptr(dev)), name)
-        return None, out, None if grad_in is None else grad_in[:, cin - 1]
+        return (None, out, grad_in[:, first - 1] if to_node else None,
+                grad_in[:, first:first + K].permute(1, 0, 2, 3) if to_field else None,
+                grad_in[:, first + K:].permute(1, 0, 2, 3) if to_memory else None)
 
 
 class _BatchedReadOut(torch.autograd.Function):
@@ -1793,127 +1814,6 @@ class _BatchedReadOut(torch.autograd.Function):
                                                             (C.c_float * 3)(*ctx.coefs), _ptr(planes), 3 * W * H, stream_ptr(x.device)),
                    'die_gather_scale_backward_batch')
         return planes, None
-
-
-class _BatchedMemorySense(torch.autograd.Function):
-    """BatchedNeuralAutomataAgent.recurrent_action's stack: `_BatchedSense` for a wide stack whose first layer also reads the M
-    expanded memory planes of every replica and whose last layer gives 3 + M planes — die_nca_wide_sense_batch_store_memory
-    forward, die_nca_wide_backward_batch_memory backward.  Returns (R, 3 + M, W, H); the backward hands the (C, P) gradient to
-    `parameters`, the chem channel of the first layer's input gradient to the env's chem node and its M memory channels — a
-    view, in the expand's (M, R, W, H) shape — to the expand."""
-
-    @staticmethod
-    def forward(ctx, pop, parameters, chem_node, mem_planes):
-        env = pop.env
-        R, W, H, L, dev, Cm, M = env.R, env.W, env.H, len(pop._layers), env.device, pop._channels, pop._memory_channels
-        with_agents = pop._arch['with_agent_channel']
-        # as they are now: the worlds will be stepped (the claim plane only where the first layer reads it)
-        planes = [env.food.clone(), env.chem.clone()] + ([env.owner.clone()] if with_agents else [])
-        mem_planes = mem_planes.contiguous()                         # (M, R, W, H): the expand's own storage, as the launch reads it
-        store = torch.empty((L, R, Cm, W, H), dtype=torch.float32, device=dev)
-        drop = pop._dropout()
-        masked = None if drop is None else torch.empty((R, Cm, W, H), dtype=torch.float32, device=dev)
-        ctx.epoch, ctx.fdt = env.epoch, _lib.DIE_F32
-        ctx.batch, ctx.pop, ctx.size = env._batch_struct(), pop, (R, W, H, L)
-        ctx.drop = None if drop is None else (drop.p, drop.seed, drop.seed_stride, drop.step)
-        m = _BatchedSense._medium(ctx, planes)
-        layers, nca = pop._nca_batch(parameters.data_ptr(), ctx.epoch)
-        _lib.check(_lib.lib.die_nca_wide_sense_batch_store_memory(C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), store.numel() * 4,
-                                                                  None if masked is None else _ptr(masked),
-                                                                  None if drop is None else C.byref(drop), _ptr(mem_planes), M,
-                                                                  stream_ptr(dev)), 'die_nca_wide_sense_batch_store_memory')
-        ctx.save_for_backward(parameters, store, mem_planes, *planes)
-        return (store[L - 1] if masked is None else masked)[:, :3 + M]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad):
-        parameters, store, mem_planes, *planes = ctx.saved_tensors
-        R, W, H, L = ctx.size
-        pop, dev, M = ctx.pop, store.device, mem_planes.shape[0]
-        g = grad.to(dtype=torch.float32).contiguous()               # (R, 3 + M, W, H)
-        m = _BatchedSense._medium(ctx, planes)
-        layers, nca = pop._nca_batch(parameters.data_ptr(), ctx.epoch)
-        need = int(_lib.lib.die_nca_wide_backward_batch_memory_workspace_bytes(W, H, R, C.byref(nca), M))
-        if need < 0:
-            raise ValueError('a stack or shape die_nca_wide_backward_batch_memory does not take')
-        ws = torch.empty((need // 4,), dtype=torch.float32, device=dev)
-        out = torch.empty_like(parameters)                          # (C, P): every element is written (the layers tile a row)
-        drop = None if ctx.drop is None else _lib.NcaDropout(*ctx.drop, 0)
-        # the first layer's inputs are ([agents,] food, chem, memory_0 ..): chem is the env's node, the memory planes the expand's
-        # output; with neither asking for a gradient no input gradient is computed
-        to_node, to_memory = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
-        first = len(planes)                                         # the memory planes' first channel
-        cin = first + M
-        grad_in = torch.empty((R, cin, W, H), dtype=torch.float32, device=dev) if to_node or to_memory else None
-        _lib.check(_lib.lib.die_nca_wide_backward_batch_memory(C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), _ptr(g),
-                                                               (3 + M) * W * H, _ptr(out), pop.P, None if drop is None else C.byref(drop),
-                                                               _ptr(ws), need, _ptr(grad_in), cin * W * H, _ptr(mem_planes), M,
-                                                               stream_ptr(dev)), 'die_nca_wide_backward_batch_memory')
-        return (None, out, grad_in[:, first - 1] if to_node else None, grad_in[:, first:].permute(1, 0, 2, 3) if to_memory else None)
-
-
-class _BatchedSignalSense(torch.autograd.Function):
-    """BatchedNeuralAutomataAgent.signalling_action's stack: `_BatchedMemorySense` for a wide stack whose first layer also reads
-    the K signal planes of every replica, ahead of the M memory planes (M = 0: `mem_planes` None), and whose last layer gives
-    3 + K + M planes — die_nca_wide_sense_batch_store_signal forward, die_nca_wide_backward_batch_signal backward.  `field` is
-    the (K, R, W, H) contiguous field as the launches read it.  Returns (R, 3 + K + M, W, H); the backward hands the (C, P)
-    gradient to `parameters`, the chem channel of the first layer's input gradient to the env's chem node, its K signal channels
-    to `field` and its M memory channels to the expand — views, in their (·, R, W, H) shapes."""
-
-    @staticmethod
-    def forward(ctx, pop, parameters, chem_node, field, mem_planes):
-        env = pop.env
-        R, W, H, L, dev, Cm = env.R, env.W, env.H, len(pop._layers), env.device, pop._channels
-        K, M = pop._signal_channels, pop._memory_channels
-        with_agents = pop._arch['with_agent_channel']
-        # as they are now: the worlds will be stepped (the claim plane only where the first layer reads it)
-        planes = [env.food.clone(), env.chem.clone()] + ([env.owner.clone()] if with_agents else [])
-        mem = [mem_planes.contiguous()] if M else []                 # (M, R, W, H): the expand's own storage, as the launch reads it
-        store = torch.empty((L, R, Cm, W, H), dtype=torch.float32, device=dev)
-        drop = pop._dropout()
-        masked = None if drop is None else torch.empty((R, Cm, W, H), dtype=torch.float32, device=dev)
-        ctx.epoch, ctx.fdt = env.epoch, _lib.DIE_F32
-        ctx.batch, ctx.pop, ctx.size, ctx.channels = env._batch_struct(), pop, (R, W, H, L), (K, M)
-        ctx.drop = None if drop is None else (drop.p, drop.seed, drop.seed_stride, drop.step)
-        m = _BatchedSense._medium(ctx, planes)
-        layers, nca = pop._nca_batch(parameters.data_ptr(), ctx.epoch)
-        _lib.check(_lib.lib.die_nca_wide_sense_batch_store_signal(C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), store.numel() * 4,
-                                                                  None if masked is None else _ptr(masked),
-                                                                  None if drop is None else C.byref(drop), _ptr(mem[0]) if M else None, M,
-                                                                  _ptr(field), K, stream_ptr(dev)), 'die_nca_wide_sense_batch_store_signal')
-        ctx.save_for_backward(parameters, store, field, *mem, *planes)
-        return (store[L - 1] if masked is None else masked)[:, :3 + K + M]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad):
-        (K, M), (R, W, H, L) = ctx.channels, ctx.size
-        parameters, store, field, *rest = ctx.saved_tensors
-        mem_planes, planes = (rest[0], rest[1:]) if M else (None, rest)
-        pop, dev = ctx.pop, store.device
-        g = grad.to(dtype=torch.float32).contiguous()               # (R, 3 + K + M, W, H)
-        m = _BatchedSense._medium(ctx, planes)
-        layers, nca = pop._nca_batch(parameters.data_ptr(), ctx.epoch)
-        need = int(_lib.lib.die_nca_wide_backward_batch_signal_workspace_bytes(W, H, R, C.byref(nca), M, K))
-        if need < 0:
-            raise ValueError('a stack or shape die_nca_wide_backward_batch_signal does not take')
-        ws = torch.empty((need // 4,), dtype=torch.float32, device=dev)
-        out = torch.empty_like(parameters)                          # (C, P): every element is written (the layers tile a row)
-        drop = None if ctx.drop is None else _lib.NcaDropout(*ctx.drop, 0)
-        # the first layer's inputs are ([agents,] food, chem, signal_0 .., memory_0 ..): chem is the env's node, the signal planes the
-        # incoming field, the memory planes the expand's output; with none of them asking for a gradient no input gradient is computed
-        to_node, to_field, to_memory = ctx.needs_input_grad[2:5]
-        first = len(planes)                                         # the signal planes' first channel
-        cin = first + K + M
-        grad_in = torch.empty((R, cin, W, H), dtype=torch.float32, device=dev) if to_node or to_field or to_memory else None
-        _lib.check(_lib.lib.die_nca_wide_backward_batch_signal(C.byref(m), C.byref(ctx.batch), C.byref(nca), _ptr(store), _ptr(g),
-                                                               (3 + K + M) * W * H, _ptr(out), pop.P, None if drop is None else C.byref(drop),
-                                                               _ptr(ws), need, _ptr(grad_in), cin * W * H, _ptr(mem_planes), M, _ptr(field), K,
-                                                               stream_ptr(dev)), 'die_nca_wide_backward_batch_signal')
-        return (None, out, grad_in[:, first - 1] if to_node else None,
-                grad_in[:, first:first + K].permute(1, 0, 2, 3) if to_field else None,
-                grad_in[:, first + K:].permute(1, 0, 2, 3) if to_memory else None)
 
 
 class _BatchedRecurrentReadOut(torch.autograd.Function):

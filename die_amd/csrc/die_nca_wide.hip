@@ -377,10 +377,13 @@ extern "C" int64_t die_nca_wide_sense_batch_store_bytes(int32_t W, int32_t H, in
     return (int64_t)n_layers * replicas * max_channels * (int64_t)W * H * (int64_t)sizeof(float);
 }
 
-extern "C" int die_nca_wide_sense_batch_store(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* store,
-                                              int64_t store_bytes, float* masked, const die_nca_dropout* drop, void* stream) {
-    const char* who = "die_nca_wide_sense_batch_store";
-    int rc = die_nca_store_check(m, b, nca, store, DIE_NCA_WIDE, who);
+// Everything the three entry points below share once their own leading argument checks have passed: the stack's and the store's
+// rules, the mask's, the overlap of the planes layer 0 reads (`memory` / `signals` of them, 0 with null planes: none) with what
+// the launches write, and the launches.
+static int wide_sense_batch_store(const char* who, const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* store,
+                                  int64_t store_bytes, float* masked, const die_nca_dropout* drop, const float* mem_planes, int memory,
+                                  const float* signal_planes, int signals, void* stream) {
+    int rc = die_nca_store_check(m, b, nca, store, DIE_NCA_WIDE, who, memory, signals);
     if (rc != DIE_OK) return rc;
     const int64_t need = die_nca_wide_sense_batch_store_bytes(m->W, m->H, b->replicas, nca->n_layers, die_nca_max_channels(nca));
     DIE_REQUIRE(store_bytes >= need, "%s: store too small (%lld < %lld)", who, (long long)store_bytes, (long long)need);
@@ -390,9 +393,25 @@ extern "C" int die_nca_wide_sense_batch_store(const die_medium* m, const die_bat
         rc = die_dropout_words(drop, &dw, who);
         if (rc != DIE_OK) return rc;
     }
+    // the memory and the signal planes are read by layer 0 while the store (and the masked planes) are written
+    const int64_t cells = (int64_t)m->W * m->H, masked_bytes = (int64_t)b->replicas * die_nca_max_channels(nca) * cells * 4;
+    auto planes_bytes = [&](int n) { return (((int64_t)n * b->replicas - 1) * b->plane_stride + cells) * 4; };
+    auto overlaps = [&](const void* p, int64_t bytes) {
+        return die_ranges_overlap(p, bytes, store, need) || (drop && die_ranges_overlap(p, bytes, masked, masked_bytes));
+    };
+    if (memory > 0)
+        DIE_REQUIRE(!overlaps(mem_planes, planes_bytes(memory)), "%s: the memory planes overlap the store or the masked planes", who);
+    if (signals > 0)
+        DIE_REQUIRE(!overlaps(signal_planes, planes_bytes(signals)), "%s: the signal planes overlap the store or the masked planes", who);
     const float* sense;
     int64_t rep;
-    return wide_sense_batch(m, b, nca, store, false, drop ? masked : nullptr, &sense, &rep, drop ? &dw : nullptr, stream);
+    return wide_sense_batch(m, b, nca, store, false, drop ? masked : nullptr, &sense, &rep, drop ? &dw : nullptr, stream, nullptr,
+                            mem_planes, memory, signal_planes, signals);
+}
+
+extern "C" int die_nca_wide_sense_batch_store(const die_medium* m, const die_batch* b, const die_nca_batch* nca, float* store,
+                                              int64_t store_bytes, float* masked, const die_nca_dropout* drop, void* stream) {
+    return wide_sense_batch_store("die_nca_wide_sense_batch_store", m, b, nca, store, store_bytes, masked, drop, nullptr, 0, nullptr, 0, stream);
 }
 
 // ---- the same for a population whose agents carry memory (the forward of die_nca_wide_backward_batch_memory) --------------
@@ -408,26 +427,7 @@ extern "C" int die_nca_wide_sense_batch_store_memory(const die_medium* m, const 
     DIE_REQUIRE(m && b && nca && store && mem_planes, "%s: null argument", who);
     DIE_REQUIRE(memory_channels >= 1 && memory_channels <= DIE_MEMORY_MAX_CHANNELS, "%s: %d memory channels outside 1..%d", who,
                 memory_channels, DIE_MEMORY_MAX_CHANNELS);
-    int rc = die_nca_store_check(m, b, nca, store, DIE_NCA_WIDE, who, memory_channels);
-    if (rc != DIE_OK) return rc;
-    const int64_t need = die_nca_wide_sense_batch_store_bytes(m->W, m->H, b->replicas, nca->n_layers, die_nca_max_channels(nca));
-    DIE_REQUIRE(store_bytes >= need, "%s: store too small (%lld < %lld)", who, (long long)store_bytes, (long long)need);
-    DropWords dw;
-    if (drop) {
-        DIE_REQUIRE(masked && masked != store, "%s: a dropout mask needs planes of its own for the masked values", who);
-        rc = die_dropout_words(drop, &dw, who);
-        if (rc != DIE_OK) return rc;
-    }
-    // the memory planes are read by layer 0 while the store (and the masked planes) are written
-    const int64_t cells = (int64_t)m->W * m->H;
-    const int64_t mem_bytes = (((int64_t)memory_channels * b->replicas - 1) * b->plane_stride + cells) * 4;
-    auto overlaps = [&](const void* q, int64_t bytes) { return die_ranges_overlap(mem_planes, mem_bytes, q, bytes); };
-    DIE_REQUIRE(!overlaps(store, need) && !(drop && overlaps(masked, (int64_t)b->replicas * die_nca_max_channels(nca) * cells * 4)),
-                "%s: the memory planes overlap the store or the masked planes", who);
-    const float* sense;
-    int64_t rep;
-    return wide_sense_batch(m, b, nca, store, false, drop ? masked : nullptr, &sense, &rep, drop ? &dw : nullptr, stream, nullptr,
-                            mem_planes, memory_channels);
+    return wide_sense_batch_store(who, m, b, nca, store, store_bytes, masked, drop, mem_planes, memory_channels, nullptr, 0, stream);
 }
 
 // ---- the same for a population whose agents also write a signal field (the forward of die_nca_wide_backward_batch_signal) --------
@@ -444,26 +444,6 @@ extern "C" int die_nca_wide_sense_batch_store_signal(const die_medium* m, const 
                 DIE_MEMORY_MAX_CHANNELS);
     DIE_REQUIRE(signal_channels >= 1 && signal_channels <= DIE_SIGNAL_MAX_CHANNELS, "%s: %d signal channels outside 1..%d", who,
                 signal_channels, DIE_SIGNAL_MAX_CHANNELS);
-    int rc = die_nca_store_check(m, b, nca, store, DIE_NCA_WIDE, who, memory_channels, signal_channels);
-    if (rc != DIE_OK) return rc;
-    const int64_t need = die_nca_wide_sense_batch_store_bytes(m->W, m->H, b->replicas, nca->n_layers, die_nca_max_channels(nca));
-    DIE_REQUIRE(store_bytes >= need, "%s: store too small (%lld < %lld)", who, (long long)store_bytes, (long long)need);
-    DropWords dw;
-    if (drop) {
-        DIE_REQUIRE(masked && masked != store, "%s: a dropout mask needs planes of its own for the masked values", who);
-        rc = die_dropout_words(drop, &dw, who);
-        if (rc != DIE_OK) return rc;
-    }
-    // the memory and the signal planes are read by layer 0 while the store (and the masked planes) are written
-    const int64_t cells = (int64_t)m->W * m->H, masked_bytes = (int64_t)b->replicas * die_nca_max_channels(nca) * cells * 4;
-    auto planes_bytes = [&](int n) { return (((int64_t)n * b->replicas - 1) * b->plane_stride + cells) * 4; };
-    auto overlaps = [&](const void* p, int64_t bytes) {
-        return die_ranges_overlap(p, bytes, store, need) || (drop && die_ranges_overlap(p, bytes, masked, masked_bytes));
-    };
-    DIE_REQUIRE(!overlaps(mem_planes, planes_bytes(memory_channels)), "%s: the memory planes overlap the store or the masked planes", who);
-    DIE_REQUIRE(!overlaps(signal_planes, planes_bytes(signal_channels)), "%s: the signal planes overlap the store or the masked planes", who);
-    const float* sense;
-    int64_t rep;
-    return wide_sense_batch(m, b, nca, store, false, drop ? masked : nullptr, &sense, &rep, drop ? &dw : nullptr, stream, nullptr,
-                            mem_planes, memory_channels, signal_planes, signal_channels);
+    return wide_sense_batch_store(who, m, b, nca, store, store_bytes, masked, drop, mem_planes, memory_channels, signal_planes,
+                                  signal_channels, stream);
 }

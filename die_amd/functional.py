@@ -159,6 +159,17 @@ class MemoryRecord:
         self.cell, self.win, self.W, self.H, self.N, self._standing, self._epoch = cell, win, int(W), int(H), int(N), standing, int(epoch)
 
 
+def _bare_medium(W, H, epoch):
+    return _lib.Medium(W, H, _lib.DIE_F32, epoch, None, None, None, None, 0, 0, 0, 0, 0, 0, 0, 0, None)     # (W, H, gW are read)
+
+
+def _check_standing(standing, shape: tuple, device) -> None:
+    """A `standing` argument of the four record functions: the planes as die_stock_plane(_batch) leaves them."""
+    if not isinstance(standing, th.Tensor) or standing.dtype != th.int64 or tuple(standing.shape) != shape or \
+            standing.device != device or not standing.is_contiguous():
+        raise ValueError(f'standing: a contiguous {shape} int64 tensor on {device}')
+
+
 def memory_record(obs, standing: Optional[th.Tensor] = None) -> MemoryRecord:
     """The record of `obs` = (agents, medium) as they stand now: one die_memory_cells launch.  `standing`: the (W, H) int64
     standing plane built for these agents at `medium.epoch` (die_stock_plane; NeuralAutomataAgent builds one per forward), or
@@ -172,9 +183,8 @@ def memory_record(obs, standing: Optional[th.Tensor] = None) -> MemoryRecord:
     if standing is None:
         standing = th.zeros((W, H), dtype=th.int64, device=dev)
         _lib.check(_lib.lib.die_stock_plane(C.byref(m), C.byref(a), medium.epoch, _ptr(standing), sp), 'die_stock_plane')
-    elif not isinstance(standing, th.Tensor) or standing.dtype != th.int64 or tuple(standing.shape) != (W, H) or \
-            standing.device != dev or not standing.is_contiguous():
-        raise ValueError(f'standing: a contiguous ({W}, {H}) int64 tensor on {dev}')
+    else:
+        _check_standing(standing, (W, H), dev)
     cell = th.full((N,), -1, dtype=th.int32, device=dev)
     win = th.full((N,), -1, dtype=th.int32, device=dev)
     _lib.check(_lib.lib.die_memory_cells(C.byref(m), C.byref(a), _ptr(standing), medium.epoch, _ptr(cell), _ptr(win), sp), 'die_memory_cells')
@@ -209,7 +219,7 @@ class _MemoryPlanes(th.autograd.Function):
     def forward(ctx, memory, record):
         W, H, N, M = record.W, record.H, record.N, memory.shape[0]
         planes = th.empty((M, W, H), dtype=th.float32, device=memory.device)
-        m = _lib.Medium(W, H, _lib.DIE_F32, record._epoch, None, None, None, None, 0, 0, 0, 0, 0, 0, 0, 0, None)     # (W, H, gW are read)
+        m = _bare_medium(W, H, record._epoch)
         _lib.check(_lib.lib.die_memory_planes(C.byref(m), _ptr(record._standing), record._epoch, M, _ptr(memory), N, N, _ptr(planes), W * H,
                                               stream_ptr(memory.device)), 'die_memory_planes')
         ctx.record = record
@@ -273,10 +283,6 @@ class SignalRecord:
         self.occupied, self.W, self.H, self._standing, self._epoch = occupied, int(W), int(H), standing, int(epoch)
 
 
-def _bare_medium(W, H, epoch):
-    return _lib.Medium(W, H, _lib.DIE_F32, epoch, None, None, None, None, 0, 0, 0, 0, 0, 0, 0, 0, None)     # (W, H, gW are read)
-
-
 def signal_record(obs, standing: Optional[th.Tensor] = None) -> SignalRecord:
     """The record of `obs` = (agents, medium) as they stand now: one die_signal_cells launch.  `standing`: the (W, H) int64
     standing plane built for these agents at `medium.epoch` (die_stock_plane; NeuralAutomataAgent builds one per forward), or
@@ -289,9 +295,8 @@ def signal_record(obs, standing: Optional[th.Tensor] = None) -> SignalRecord:
         standing = th.zeros((W, H), dtype=th.int64, device=dev)
         a = agents.c_struct()
         _lib.check(_lib.lib.die_stock_plane(C.byref(m), C.byref(a), medium.epoch, _ptr(standing), sp), 'die_stock_plane')
-    elif not isinstance(standing, th.Tensor) or standing.dtype != th.int64 or tuple(standing.shape) != (W, H) or \
-            standing.device != dev or not standing.is_contiguous():
-        raise ValueError(f'standing: a contiguous ({W}, {H}) int64 tensor on {dev}')
+    else:
+        _check_standing(standing, (W, H), dev)
     occupied = th.empty((W, H), dtype=th.uint8, device=dev)                   # (every byte is written by the call)
     _lib.check(_lib.lib.die_signal_cells(C.byref(m), _ptr(standing), medium.epoch, _ptr(occupied), sp), 'die_signal_cells')
     return SignalRecord(occupied, W, H, standing, medium.epoch)
@@ -379,15 +384,16 @@ class BatchedMemoryRecord:
         self.n, self._batch, self._standing, self._epoch = tuple(n), batch, standing, int(epoch)
 
 
-def _memory_population(population, what: str):
+def _record_population(population, what: str, kind: str, alone: str):
+    """The population of a batched record, checked: it has channels of `kind` ('memory' / 'signal') and small worlds; its env."""
     from .batch import BatchedNeuralAutomataAgent
     if not isinstance(population, BatchedNeuralAutomataAgent):
         raise TypeError('population: a BatchedNeuralAutomataAgent')
-    if not population._memory_channels:
-        raise ValueError(f'{what}: a population without memory channels (memory_channels=0) has no record')
+    if not getattr(population, f'_{kind}_channels'):
+        raise ValueError(f'{what}: a population without {kind} channels ({kind}_channels=0) has no record')
     if population.env.per_replica:
         raise NotImplementedError(f'{what}: large worlds (per_replica) are not batched — every replica is a stand-alone agent: use '
-                                  'replica_agent(r).recurrent_action / functional.memory_record')
+                                  f'replica_agent(r).{alone}')
     return population.env
 
 
@@ -397,13 +403,12 @@ def memory_record_batch(population, standing: Optional[th.Tensor] = None) -> Bat
     `env.step(population)` finds those as it left them, and two calls at one epoch are safe — then one die_memory_cells_batch
     launch.  `standing`: such planes already built for these worlds at this epoch (a `signal_record_batch`'s), taken as they
     are.  Small worlds; a population with memory channels."""
-    env = _memory_population(population, 'memory_record_batch')
+    env = _record_population(population, 'memory_record_batch', 'memory', 'recurrent_action / functional.memory_record')
     dev, R, W, H, Nmax = env.device, env.R, env.W, env.H, env.Nmax
     if standing is None:
         standing = _standing_planes_batch(population)
-    elif not isinstance(standing, th.Tensor) or standing.dtype != th.int64 or tuple(standing.shape) != (R, W, H) or \
-            standing.device != dev or not standing.is_contiguous():
-        raise ValueError(f'standing: a contiguous ({R}, {W}, {H}) int64 tensor on {dev}')
+    else:
+        _check_standing(standing, (R, W, H), dev)
     m, a, _, b = env._structs()
     sp = stream_ptr(dev)
     cell = th.empty((R, Nmax), dtype=th.int32, device=dev)           # (every word is written: the padding slots -1)
@@ -450,7 +455,7 @@ class _BatchedMemoryPlanes(th.autograd.Function):
         R, W, H, M = record.R, record.W, record.H, memory.shape[1]
         # plane j of replica r at (j * R + r) * W * H: a batched layer launch reads plane j of every replica one plane apart
         planes = th.empty((M, R, W, H), dtype=th.float32, device=memory.device)
-        m = _lib.Medium(W, H, _lib.DIE_F32, record._epoch, None, None, None, None, 0, 0, 0, 0, 0, 0, 0, 0, None)     # (W, H, gW are read)
+        m = _bare_medium(W, H, record._epoch)
         _lib.check(_lib.lib.die_memory_planes_batch(C.byref(m), C.byref(record._batch), _ptr(record._standing), record._epoch, M, _ptr(memory),
                                                     record.Nmax, _ptr(planes), stream_ptr(memory.device)), 'die_memory_planes_batch')
         ctx.record, ctx.M = record, M
@@ -537,21 +542,12 @@ def signal_record_batch(population, standing: Optional[th.Tensor] = None) -> Sig
     replicas.  `standing`: the contiguous (R, W, H) int64 standing planes built for these worlds at the env's epoch
     (die_stock_plane_batch), or None to build them here, in the buffer the population owns (`memory_record_batch`'s: one launch
     more).  Small worlds; a population with signal channels."""
-    from .batch import BatchedNeuralAutomataAgent
-    if not isinstance(population, BatchedNeuralAutomataAgent):
-        raise TypeError('population: a BatchedNeuralAutomataAgent')
-    if not population._signal_channels:
-        raise ValueError('signal_record_batch: a population without signal channels (signal_channels=0) has no record')
-    env = population.env
-    if env.per_replica:
-        raise NotImplementedError('signal_record_batch: large worlds (per_replica) are not batched — every replica is a stand-alone '
-                                  'agent: use replica_agent(r).signalling_action / functional.signal_record')
+    env = _record_population(population, 'signal_record_batch', 'signal', 'signalling_action / functional.signal_record')
     dev, R, W, H = env.device, env.R, env.W, env.H
     if standing is None:
         standing = _standing_planes_batch(population)
-    elif not isinstance(standing, th.Tensor) or standing.dtype != th.int64 or tuple(standing.shape) != (R, W, H) or \
-            standing.device != dev or not standing.is_contiguous():
-        raise ValueError(f'standing: a contiguous ({R}, {W}, {H}) int64 tensor on {dev}')
+    else:
+        _check_standing(standing, (R, W, H), dev)
     m, _, _, b = env._structs()
     stride = (W * H + 15) // 16 * 16                                          # every replica's bytes on a 16-byte boundary
     store = th.empty((R, stride), dtype=th.uint8, device=dev)                  # (every byte of every plane is written by the call)

@@ -26,7 +26,14 @@ RECORDED = STEPS + (
     'die_nca_backward_batch_inputs', 'die_nca_wide_backward_batch_workspace_bytes', 'die_nca_wide_backward_batch',
     'die_gather_scale_batch', 'die_gather_scale_backward_batch', 'die_deposit_cells_batch', 'die_env_step_backward_batch',
     'die_stock_plane', 'die_memory_planes', 'die_conv2d', 'die_conv2d_dropout', 'die_conv2d_wide', 'die_gather_scale', 'die_gather_memory',
-    'die_conv2d_backward', 'die_gather_scale_backward')
+    'die_conv2d_backward', 'die_gather_scale_backward',
+    # the stateful paths: memory and signal channels with gradients, stand-alone and batched
+    'die_memory_cells', 'die_memory_cells_batch', 'die_signal_cells', 'die_signal_cells_batch', 'die_signal_step', 'die_signal_step_batch',
+    'die_signal_step_backward', 'die_signal_step_backward_batch', 'die_memory_planes_backward', 'die_memory_planes_backward_batch',
+    'die_gather_memory_backward', 'die_gather_memory_backward_batch', 'die_nca_wide_sense_batch_store_memory',
+    'die_nca_wide_sense_batch_store_signal', 'die_nca_wide_backward_batch_memory', 'die_nca_wide_backward_batch_signal',
+    'die_nca_wide_backward_batch_memory_workspace_bytes', 'die_nca_wide_backward_batch_signal_workspace_bytes',
+    'die_conv2d_wide_backward', 'die_conv2d_wide_backward_workspace_bytes')
 # argument positions (include/die_hip.h): the batched steps' action, mask and the two Dynamics tables; the memory step's M and with_stock
 ACT, DROP, ROWS, ROWS_HOST, MEM_M, MEM_STOCK = 3, 9, 10, 11, 13, 16
 
@@ -268,6 +275,62 @@ def test_the_calls_of_a_stand_alone_differentiable_sense(calls, kind):
     assert ag.dropout_step == (1 if masked else 0)
 
 
+# ---------------------------------------------------------------------------------------------------- the stateful calls
+STATEFUL = {                                                # the call, K, M
+    'recurrent': ('recurrent_action', 0, 2),
+    'signalling': ('signalling_action', 2, 0),
+    'signalling_memory': ('signalling_action', 2, 2),
+}
+
+
+@pytest.mark.parametrize('dropout', [False, True], ids=['plain', 'dropout'])
+@pytest.mark.parametrize('node', ['none', 'stepped'])
+@pytest.mark.parametrize('kind', list(STATEFUL))
+@pytest.mark.parametrize('who', ['alone', 'population'])
+def test_the_calls_of_two_chained_stateful_calls(calls, who, kind, node, dropout):
+    """Two calls, the second given the first's `memory_next` / `signals_next`, then `backward()` on the sum of everything returned:
+    the calls of each forward, of the `differentiable_step` between them ('stepped': the env carries a chem node that needs a
+    gradient) and of the backward, as literals (STATEFUL_CALLS, below).  The docstrings' counts are the cross-check: a two-layer
+    population's `recurrent_action` makes 4 calls forward (L + 5 launches: the build and the record, the expand, the stack's L,
+    the two read-outs), its stack's adjoint is given `grad_in` wherever a memory with a graph or a chem node asks for it, and the
+    K·R planes of a population's field take ONE die_signal_step_backward_batch per link."""
+    name, K, M = STATEFUL[kind]
+    kw = dict(kernel_sizes=(3, 3), memory_channels=M, p_agent_dropout=0.5 if dropout else 0.0, **(dict(signal_channels=K) if K else {}))
+    seed = 3 if dropout else None
+    torch.manual_seed(5)
+    if who == 'alone':
+        env = die.Env((W, H), _dynamics(), seed=3, max_agents='alive')
+        ag = die.NeuralAutomataAgent(scale=0.01, deposit=2.0, boundary='circular', dropout_seed=seed, **kw).to(env.device)
+        call = lambda state: getattr(ag, name)(env._get_current_obs, *state)
+    else:
+        env = BatchedEnv((W, H), _dynamics(), replicas=R, seed=3)
+        pop = BatchedNeuralAutomataAgent(env, die.NeuralAutomataAgent(scale=0.01, deposit=2.0, boundary='circular', **kw), dropout_seed=seed)
+        assert (pop._dropout() is not None) == dropout
+        p = pop.parameters.detach().clone().requires_grad_()
+        call = lambda state: getattr(pop, name)(*state, p)
+    if node == 'stepped':
+        assert not env.differentiable_chem().requires_grad
+    state = (None,) * (2 if K else 1)                            # (memory,) / (signals, memory)
+    log, total = [], 0
+    for link in range(2):
+        del calls[:]
+        out = call(state)
+        log.append(list(calls))
+        total = total + sum(t.sum() for t in out if t is not None)
+        state = out[1:]
+        if node == 'stepped' and link == 0:
+            del calls[:]
+            env.differentiable_step(out[0])
+            log.append(list(calls))
+    del calls[:]
+    total.backward()
+    torch.cuda.synchronize()
+    log.append(list(calls))
+    print('    %r: %r,' % ('%s-%s-%s-%s' % (who, kind, node, 'dropout' if dropout else 'plain'), log))
+    assert log == STATEFUL_CALLS['%s-%s-%s-%s' % (who, kind, node, 'dropout' if dropout else 'plain')]
+    assert (ag if who == 'alone' else pop).dropout_step == (2 if dropout else 0)
+
+
 # ---------------------------------------------------------------------------------------------------- refusals
 MEMORY = ('{what}: no gradients through memory channels (memory_channels=2): the read-out into the memory and the expand onto the '
           'field have no adjoint')
@@ -308,3 +371,287 @@ def test_which_refusal_of_a_differentiable_call_wins(calls, wide, stock, memory)
         _refused(lambda: pop.forward_device(), (MEMORY if memory else STOCK).format(what='forward_device'))
     assert calls == [] and (ag.dropout_step, pop.dropout_step) == (0, 0)
     assert ag.memory is None and (pop.memory is None or not pop.memory.any())
+
+
+# ---------------------------------------------------------------------------------------------------- the recorded stateful calls
+# per case: the first call's forward, ['stepped': the differentiable_step between,] the second call's forward, the backward
+STATEFUL_CALLS = {
+    'alone-recurrent-none-plain': [
+        [('die_stock_plane', ()), ('die_memory_cells', ()), ('die_memory_planes', ()), ('die_conv2d_wide', (12,)), ('die_conv2d_wide', (12,)),
+         ('die_gather_scale', ()), ('die_memory_planes_backward', ())],
+        [('die_stock_plane', ()), ('die_memory_cells', ()), ('die_memory_planes', ()), ('die_conv2d_wide', (12,)), ('die_conv2d_wide', (12,)),
+         ('die_gather_scale', ()), ('die_memory_planes_backward', ())],
+        [('die_gather_memory_backward', ()), ('die_gather_scale_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', (14,)), ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (8, 14)),
+         ('die_memory_planes_backward', ()), ('die_gather_memory_backward', ()), ('die_gather_scale_backward', ()),
+         ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (14,)), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', (8, 14, 16))],
+    ],
+    'alone-recurrent-none-dropout': [
+        [('die_stock_plane', ()), ('die_memory_cells', ()), ('die_memory_planes', ()), ('die_conv2d_wide', (12,)), ('die_conv2d_wide', ()),
+         ('die_conv2d_wide', (12,)), ('die_gather_scale', ()), ('die_memory_planes_backward', ())],
+        [('die_stock_plane', ()), ('die_memory_cells', ()), ('die_memory_planes', ()), ('die_conv2d_wide', (12,)), ('die_conv2d_wide', ()),
+         ('die_conv2d_wide', (12,)), ('die_gather_scale', ()), ('die_memory_planes_backward', ())],
+        [('die_gather_memory_backward', ()), ('die_gather_scale_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (8, 14)),
+         ('die_memory_planes_backward', ()), ('die_gather_memory_backward', ()), ('die_gather_scale_backward', ()),
+         ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', (8, 14, 16))],
+    ],
+    'alone-recurrent-stepped-plain': [
+        [('die_stock_plane', ()), ('die_memory_cells', ()), ('die_memory_planes', ()), ('die_conv2d_wide', (12,)), ('die_conv2d_wide', (12,)),
+         ('die_gather_scale', ()), ('die_memory_planes_backward', ())],
+        [],
+        [('die_stock_plane', ()), ('die_memory_cells', ()), ('die_memory_planes', ()), ('die_conv2d_wide', (12,)), ('die_conv2d_wide', (12,)),
+         ('die_gather_scale', ()), ('die_memory_planes_backward', ())],
+        [('die_gather_memory_backward', ()), ('die_gather_scale_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', (14,)), ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (8, 14)),
+         ('die_memory_planes_backward', ()), ('die_gather_memory_backward', ()), ('die_gather_scale_backward', ()),
+         ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (14,)), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', (8, 14, 16))],
+    ],
+    'alone-recurrent-stepped-dropout': [
+        [('die_stock_plane', ()), ('die_memory_cells', ()), ('die_memory_planes', ()), ('die_conv2d_wide', (12,)), ('die_conv2d_wide', ()),
+         ('die_conv2d_wide', (12,)), ('die_gather_scale', ()), ('die_memory_planes_backward', ())],
+        [],
+        [('die_stock_plane', ()), ('die_memory_cells', ()), ('die_memory_planes', ()), ('die_conv2d_wide', (12,)), ('die_conv2d_wide', ()),
+         ('die_conv2d_wide', (12,)), ('die_gather_scale', ()), ('die_memory_planes_backward', ())],
+        [('die_gather_memory_backward', ()), ('die_gather_scale_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (8, 14)),
+         ('die_memory_planes_backward', ()), ('die_gather_memory_backward', ()), ('die_gather_scale_backward', ()),
+         ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', (8, 14, 16))],
+    ],
+    'alone-signalling-none-plain': [
+        [('die_stock_plane', ()), ('die_signal_cells', ()), ('die_conv2d_wide', (12,)), ('die_conv2d_wide', (12,)), ('die_gather_scale', ()),
+         ('die_signal_step', ())],
+        [('die_stock_plane', ()), ('die_signal_cells', ()), ('die_conv2d_wide', (12,)), ('die_conv2d_wide', (12,)), ('die_gather_scale', ()),
+         ('die_signal_step', ())],
+        [('die_signal_step_backward', ()), ('die_gather_scale_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', (14,)), ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (8, 14)),
+         ('die_signal_step_backward', (6,)), ('die_gather_scale_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', (14,)), ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (8, 14, 16))],
+    ],
+    'alone-signalling-none-dropout': [
+        [('die_stock_plane', ()), ('die_signal_cells', ()), ('die_conv2d_wide', (12,)), ('die_conv2d_wide', ()), ('die_conv2d_wide', (12,)),
+         ('die_gather_scale', ()), ('die_signal_step', ())],
+        [('die_stock_plane', ()), ('die_signal_cells', ()), ('die_conv2d_wide', (12,)), ('die_conv2d_wide', ()), ('die_conv2d_wide', (12,)),
+         ('die_gather_scale', ()), ('die_signal_step', ())],
+        [('die_signal_step_backward', ()), ('die_gather_scale_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (8, 14)),
+         ('die_signal_step_backward', (6,)), ('die_gather_scale_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (8, 14, 16))],
+    ],
+    'alone-signalling-stepped-plain': [
+        [('die_stock_plane', ()), ('die_signal_cells', ()), ('die_conv2d_wide', (12,)), ('die_conv2d_wide', (12,)), ('die_gather_scale', ()),
+         ('die_signal_step', ())],
+        [],
+        [('die_stock_plane', ()), ('die_signal_cells', ()), ('die_conv2d_wide', (12,)), ('die_conv2d_wide', (12,)), ('die_gather_scale', ()),
+         ('die_signal_step', ())],
+        [('die_signal_step_backward', ()), ('die_gather_scale_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', (14,)), ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (8, 14)),
+         ('die_signal_step_backward', (6,)), ('die_gather_scale_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', (14,)), ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (8, 14, 16))],
+    ],
+    'alone-signalling-stepped-dropout': [
+        [('die_stock_plane', ()), ('die_signal_cells', ()), ('die_conv2d_wide', (12,)), ('die_conv2d_wide', ()), ('die_conv2d_wide', (12,)),
+         ('die_gather_scale', ()), ('die_signal_step', ())],
+        [],
+        [('die_stock_plane', ()), ('die_signal_cells', ()), ('die_conv2d_wide', (12,)), ('die_conv2d_wide', ()), ('die_conv2d_wide', (12,)),
+         ('die_gather_scale', ()), ('die_signal_step', ())],
+        [('die_signal_step_backward', ()), ('die_gather_scale_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (8, 14)),
+         ('die_signal_step_backward', (6,)), ('die_gather_scale_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (8, 14, 16))],
+    ],
+    'alone-signalling_memory-none-plain': [
+        [('die_stock_plane', ()), ('die_signal_cells', ()), ('die_memory_cells', ()), ('die_memory_planes', ()), ('die_conv2d_wide', (12,)),
+         ('die_conv2d_wide', (12,)), ('die_gather_scale', ()), ('die_signal_step', ()), ('die_memory_planes_backward', ())],
+        [('die_stock_plane', ()), ('die_signal_cells', ()), ('die_memory_cells', ()), ('die_memory_planes', ()), ('die_conv2d_wide', (12,)),
+         ('die_conv2d_wide', (12,)), ('die_gather_scale', ()), ('die_signal_step', ()), ('die_memory_planes_backward', ())],
+        [('die_gather_memory_backward', ()), ('die_signal_step_backward', ()), ('die_gather_scale_backward', ()),
+         ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (14,)), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', (8, 14)), ('die_memory_planes_backward', ()), ('die_gather_memory_backward', ()),
+         ('die_signal_step_backward', (6,)), ('die_gather_scale_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', (14,)), ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (8, 14, 16))],
+    ],
+    'alone-signalling_memory-none-dropout': [
+        [('die_stock_plane', ()), ('die_signal_cells', ()), ('die_memory_cells', ()), ('die_memory_planes', ()), ('die_conv2d_wide', (12,)),
+         ('die_conv2d_wide', ()), ('die_conv2d_wide', (12,)), ('die_gather_scale', ()), ('die_signal_step', ()),
+         ('die_memory_planes_backward', ())],
+        [('die_stock_plane', ()), ('die_signal_cells', ()), ('die_memory_cells', ()), ('die_memory_planes', ()), ('die_conv2d_wide', (12,)),
+         ('die_conv2d_wide', ()), ('die_conv2d_wide', (12,)), ('die_gather_scale', ()), ('die_signal_step', ()),
+         ('die_memory_planes_backward', ())],
+        [('die_gather_memory_backward', ()), ('die_signal_step_backward', ()), ('die_gather_scale_backward', ()),
+         ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', (8, 14)), ('die_memory_planes_backward', ()), ('die_gather_memory_backward', ()),
+         ('die_signal_step_backward', (6,)), ('die_gather_scale_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (8, 14, 16))],
+    ],
+    'alone-signalling_memory-stepped-plain': [
+        [('die_stock_plane', ()), ('die_signal_cells', ()), ('die_memory_cells', ()), ('die_memory_planes', ()), ('die_conv2d_wide', (12,)),
+         ('die_conv2d_wide', (12,)), ('die_gather_scale', ()), ('die_signal_step', ()), ('die_memory_planes_backward', ())],
+        [],
+        [('die_stock_plane', ()), ('die_signal_cells', ()), ('die_memory_cells', ()), ('die_memory_planes', ()), ('die_conv2d_wide', (12,)),
+         ('die_conv2d_wide', (12,)), ('die_gather_scale', ()), ('die_signal_step', ()), ('die_memory_planes_backward', ())],
+        [('die_gather_memory_backward', ()), ('die_signal_step_backward', ()), ('die_gather_scale_backward', ()),
+         ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (14,)), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', (8, 14)), ('die_memory_planes_backward', ()), ('die_gather_memory_backward', ()),
+         ('die_signal_step_backward', (6,)), ('die_gather_scale_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', (14,)), ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (8, 14, 16))],
+    ],
+    'alone-signalling_memory-stepped-dropout': [
+        [('die_stock_plane', ()), ('die_signal_cells', ()), ('die_memory_cells', ()), ('die_memory_planes', ()), ('die_conv2d_wide', (12,)),
+         ('die_conv2d_wide', ()), ('die_conv2d_wide', (12,)), ('die_gather_scale', ()), ('die_signal_step', ()),
+         ('die_memory_planes_backward', ())],
+        [],
+        [('die_stock_plane', ()), ('die_signal_cells', ()), ('die_memory_cells', ()), ('die_memory_planes', ()), ('die_conv2d_wide', (12,)),
+         ('die_conv2d_wide', ()), ('die_conv2d_wide', (12,)), ('die_gather_scale', ()), ('die_signal_step', ()),
+         ('die_memory_planes_backward', ())],
+        [('die_gather_memory_backward', ()), ('die_signal_step_backward', ()), ('die_gather_scale_backward', ()),
+         ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', (8, 14)), ('die_memory_planes_backward', ()), ('die_gather_memory_backward', ()),
+         ('die_signal_step_backward', (6,)), ('die_gather_scale_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()),
+         ('die_conv2d_wide_backward', ()), ('die_conv2d_wide_backward_workspace_bytes', ()), ('die_conv2d_wide_backward', (8, 14, 16))],
+    ],
+    'population-recurrent-none-plain': [
+        [('die_stock_plane_batch', ()), ('die_memory_cells_batch', ()), ('die_memory_planes_batch', ()),
+         ('die_nca_wide_sense_batch_store_memory', (5, 6)), ('die_gather_scale_batch', ()), ('die_memory_planes_backward_batch', ())],
+        [('die_stock_plane_batch', ()), ('die_memory_cells_batch', ()), ('die_memory_planes_batch', ()),
+         ('die_nca_wide_sense_batch_store_memory', (5, 6)), ('die_gather_scale_batch', ()), ('die_memory_planes_backward_batch', ())],
+        [('die_gather_scale_backward_batch', ()), ('die_gather_memory_backward_batch', ()),
+         ('die_nca_wide_backward_batch_memory_workspace_bytes', ()), ('die_nca_wide_backward_batch_memory', (8,)),
+         ('die_memory_planes_backward_batch', ()), ('die_gather_scale_backward_batch', ()), ('die_gather_memory_backward_batch', ()),
+         ('die_nca_wide_backward_batch_memory_workspace_bytes', ()), ('die_nca_wide_backward_batch_memory', (8, 11))],
+    ],
+    'population-recurrent-none-dropout': [
+        [('die_stock_plane_batch', ()), ('die_memory_cells_batch', ()), ('die_memory_planes_batch', ()),
+         ('die_nca_wide_sense_batch_store_memory', ()), ('die_gather_scale_batch', ()), ('die_memory_planes_backward_batch', ())],
+        [('die_stock_plane_batch', ()), ('die_memory_cells_batch', ()), ('die_memory_planes_batch', ()),
+         ('die_nca_wide_sense_batch_store_memory', ()), ('die_gather_scale_batch', ()), ('die_memory_planes_backward_batch', ())],
+        [('die_gather_scale_backward_batch', ()), ('die_gather_memory_backward_batch', ()),
+         ('die_nca_wide_backward_batch_memory_workspace_bytes', ()), ('die_nca_wide_backward_batch_memory', ()),
+         ('die_memory_planes_backward_batch', ()), ('die_gather_scale_backward_batch', ()), ('die_gather_memory_backward_batch', ()),
+         ('die_nca_wide_backward_batch_memory_workspace_bytes', ()), ('die_nca_wide_backward_batch_memory', (11,))],
+    ],
+    'population-recurrent-stepped-plain': [
+        [('die_stock_plane_batch', ()), ('die_memory_cells_batch', ()), ('die_memory_planes_batch', ()),
+         ('die_nca_wide_sense_batch_store_memory', (5, 6)), ('die_gather_scale_batch', ()), ('die_memory_planes_backward_batch', ())],
+        [('die_env_step_batch', ()), ('die_deposit_cells_batch', ())],
+        [('die_stock_plane_batch', ()), ('die_memory_cells_batch', ()), ('die_memory_planes_batch', ()),
+         ('die_nca_wide_sense_batch_store_memory', (5, 6)), ('die_gather_scale_batch', ()), ('die_memory_planes_backward_batch', ())],
+        [('die_gather_scale_backward_batch', ()), ('die_gather_memory_backward_batch', ()),
+         ('die_nca_wide_backward_batch_memory_workspace_bytes', ()), ('die_nca_wide_backward_batch_memory', (8,)),
+         ('die_memory_planes_backward_batch', ()), ('die_env_step_backward_batch', (6, 7)), ('die_gather_scale_backward_batch', ()),
+         ('die_gather_memory_backward_batch', ()), ('die_nca_wide_backward_batch_memory_workspace_bytes', ()),
+         ('die_nca_wide_backward_batch_memory', (8, 11))],
+    ],
+    'population-recurrent-stepped-dropout': [
+        [('die_stock_plane_batch', ()), ('die_memory_cells_batch', ()), ('die_memory_planes_batch', ()),
+         ('die_nca_wide_sense_batch_store_memory', ()), ('die_gather_scale_batch', ()), ('die_memory_planes_backward_batch', ())],
+        [('die_env_step_batch', ()), ('die_deposit_cells_batch', ())],
+        [('die_stock_plane_batch', ()), ('die_memory_cells_batch', ()), ('die_memory_planes_batch', ()),
+         ('die_nca_wide_sense_batch_store_memory', ()), ('die_gather_scale_batch', ()), ('die_memory_planes_backward_batch', ())],
+        [('die_gather_scale_backward_batch', ()), ('die_gather_memory_backward_batch', ()),
+         ('die_nca_wide_backward_batch_memory_workspace_bytes', ()), ('die_nca_wide_backward_batch_memory', ()),
+         ('die_memory_planes_backward_batch', ()), ('die_env_step_backward_batch', (6, 7)), ('die_gather_scale_backward_batch', ()),
+         ('die_gather_memory_backward_batch', ()), ('die_nca_wide_backward_batch_memory_workspace_bytes', ()),
+         ('die_nca_wide_backward_batch_memory', (11,))],
+    ],
+    'population-signalling-none-plain': [
+        [('die_stock_plane_batch', ()), ('die_signal_cells_batch', ()), ('die_nca_wide_sense_batch_store_signal', (5, 6, 7)),
+         ('die_gather_scale_batch', ()), ('die_signal_step_batch', ())],
+        [('die_stock_plane_batch', ()), ('die_signal_cells_batch', ()), ('die_nca_wide_sense_batch_store_signal', (5, 6, 7)),
+         ('die_gather_scale_batch', ()), ('die_signal_step_batch', ())],
+        [('die_signal_step_backward_batch', ()), ('die_gather_scale_backward_batch', ()),
+         ('die_nca_wide_backward_batch_signal_workspace_bytes', ()), ('die_nca_wide_backward_batch_signal', (8, 13)),
+         ('die_signal_step_backward_batch', (7,)), ('die_gather_scale_backward_batch', ()),
+         ('die_nca_wide_backward_batch_signal_workspace_bytes', ()), ('die_nca_wide_backward_batch_signal', (8, 11, 13))],
+    ],
+    'population-signalling-none-dropout': [
+        [('die_stock_plane_batch', ()), ('die_signal_cells_batch', ()), ('die_nca_wide_sense_batch_store_signal', (7,)),
+         ('die_gather_scale_batch', ()), ('die_signal_step_batch', ())],
+        [('die_stock_plane_batch', ()), ('die_signal_cells_batch', ()), ('die_nca_wide_sense_batch_store_signal', (7,)),
+         ('die_gather_scale_batch', ()), ('die_signal_step_batch', ())],
+        [('die_signal_step_backward_batch', ()), ('die_gather_scale_backward_batch', ()),
+         ('die_nca_wide_backward_batch_signal_workspace_bytes', ()), ('die_nca_wide_backward_batch_signal', (13,)),
+         ('die_signal_step_backward_batch', (7,)), ('die_gather_scale_backward_batch', ()),
+         ('die_nca_wide_backward_batch_signal_workspace_bytes', ()), ('die_nca_wide_backward_batch_signal', (11, 13))],
+    ],
+    'population-signalling-stepped-plain': [
+        [('die_stock_plane_batch', ()), ('die_signal_cells_batch', ()), ('die_nca_wide_sense_batch_store_signal', (5, 6, 7)),
+         ('die_gather_scale_batch', ()), ('die_signal_step_batch', ())],
+        [('die_env_step_batch', ()), ('die_deposit_cells_batch', ())],
+        [('die_stock_plane_batch', ()), ('die_signal_cells_batch', ()), ('die_nca_wide_sense_batch_store_signal', (5, 6, 7)),
+         ('die_gather_scale_batch', ()), ('die_signal_step_batch', ())],
+        [('die_signal_step_backward_batch', ()), ('die_gather_scale_backward_batch', ()),
+         ('die_nca_wide_backward_batch_signal_workspace_bytes', ()), ('die_nca_wide_backward_batch_signal', (8, 13)),
+         ('die_env_step_backward_batch', (6, 7)), ('die_signal_step_backward_batch', (7,)), ('die_gather_scale_backward_batch', ()),
+         ('die_nca_wide_backward_batch_signal_workspace_bytes', ()), ('die_nca_wide_backward_batch_signal', (8, 11, 13))],
+    ],
+    'population-signalling-stepped-dropout': [
+        [('die_stock_plane_batch', ()), ('die_signal_cells_batch', ()), ('die_nca_wide_sense_batch_store_signal', (7,)),
+         ('die_gather_scale_batch', ()), ('die_signal_step_batch', ())],
+        [('die_env_step_batch', ()), ('die_deposit_cells_batch', ())],
+        [('die_stock_plane_batch', ()), ('die_signal_cells_batch', ()), ('die_nca_wide_sense_batch_store_signal', (7,)),
+         ('die_gather_scale_batch', ()), ('die_signal_step_batch', ())],
+        [('die_signal_step_backward_batch', ()), ('die_gather_scale_backward_batch', ()),
+         ('die_nca_wide_backward_batch_signal_workspace_bytes', ()), ('die_nca_wide_backward_batch_signal', (13,)),
+         ('die_env_step_backward_batch', (6, 7)), ('die_signal_step_backward_batch', (7,)), ('die_gather_scale_backward_batch', ()),
+         ('die_nca_wide_backward_batch_signal_workspace_bytes', ()), ('die_nca_wide_backward_batch_signal', (11, 13))],
+    ],
+    'population-signalling_memory-none-plain': [
+        [('die_stock_plane_batch', ()), ('die_signal_cells_batch', ()), ('die_memory_cells_batch', ()), ('die_memory_planes_batch', ()),
+         ('die_nca_wide_sense_batch_store_signal', (5, 6)), ('die_gather_scale_batch', ()), ('die_signal_step_batch', ()),
+         ('die_memory_planes_backward_batch', ())],
+        [('die_stock_plane_batch', ()), ('die_signal_cells_batch', ()), ('die_memory_cells_batch', ()), ('die_memory_planes_batch', ()),
+         ('die_nca_wide_sense_batch_store_signal', (5, 6)), ('die_gather_scale_batch', ()), ('die_signal_step_batch', ()),
+         ('die_memory_planes_backward_batch', ())],
+        [('die_gather_memory_backward_batch', ()), ('die_signal_step_backward_batch', ()), ('die_gather_scale_backward_batch', ()),
+         ('die_nca_wide_backward_batch_signal_workspace_bytes', ()), ('die_nca_wide_backward_batch_signal', (8,)),
+         ('die_memory_planes_backward_batch', ()), ('die_gather_memory_backward_batch', ()), ('die_signal_step_backward_batch', (7,)),
+         ('die_gather_scale_backward_batch', ()), ('die_nca_wide_backward_batch_signal_workspace_bytes', ()),
+         ('die_nca_wide_backward_batch_signal', (8, 11))],
+    ],
+    'population-signalling_memory-none-dropout': [
+        [('die_stock_plane_batch', ()), ('die_signal_cells_batch', ()), ('die_memory_cells_batch', ()), ('die_memory_planes_batch', ()),
+         ('die_nca_wide_sense_batch_store_signal', ()), ('die_gather_scale_batch', ()), ('die_signal_step_batch', ()),
+         ('die_memory_planes_backward_batch', ())],
+        [('die_stock_plane_batch', ()), ('die_signal_cells_batch', ()), ('die_memory_cells_batch', ()), ('die_memory_planes_batch', ()),
+         ('die_nca_wide_sense_batch_store_signal', ()), ('die_gather_scale_batch', ()), ('die_signal_step_batch', ()),
+         ('die_memory_planes_backward_batch', ())],
+        [('die_gather_memory_backward_batch', ()), ('die_signal_step_backward_batch', ()), ('die_gather_scale_backward_batch', ()),
+         ('die_nca_wide_backward_batch_signal_workspace_bytes', ()), ('die_nca_wide_backward_batch_signal', ()),
+         ('die_memory_planes_backward_batch', ()), ('die_gather_memory_backward_batch', ()), ('die_signal_step_backward_batch', (7,)),
+         ('die_gather_scale_backward_batch', ()), ('die_nca_wide_backward_batch_signal_workspace_bytes', ()),
+         ('die_nca_wide_backward_batch_signal', (11,))],
+    ],
+    'population-signalling_memory-stepped-plain': [
+        [('die_stock_plane_batch', ()), ('die_signal_cells_batch', ()), ('die_memory_cells_batch', ()), ('die_memory_planes_batch', ()),
+         ('die_nca_wide_sense_batch_store_signal', (5, 6)), ('die_gather_scale_batch', ()), ('die_signal_step_batch', ()),
+         ('die_memory_planes_backward_batch', ())],
+        [('die_env_step_batch', ()), ('die_deposit_cells_batch', ())],
+        [('die_stock_plane_batch', ()), ('die_signal_cells_batch', ()), ('die_memory_cells_batch', ()), ('die_memory_planes_batch', ()),
+         ('die_nca_wide_sense_batch_store_signal', (5, 6)), ('die_gather_scale_batch', ()), ('die_signal_step_batch', ()),
+         ('die_memory_planes_backward_batch', ())],
+        [('die_gather_memory_backward_batch', ()), ('die_signal_step_backward_batch', ()), ('die_gather_scale_backward_batch', ()),
+         ('die_nca_wide_backward_batch_signal_workspace_bytes', ()), ('die_nca_wide_backward_batch_signal', (8,)),
+         ('die_memory_planes_backward_batch', ()), ('die_env_step_backward_batch', (6, 7)), ('die_gather_memory_backward_batch', ()),
+         ('die_signal_step_backward_batch', (7,)), ('die_gather_scale_backward_batch', ()),
+         ('die_nca_wide_backward_batch_signal_workspace_bytes', ()), ('die_nca_wide_backward_batch_signal', (8, 11))],
+    ],
+    'population-signalling_memory-stepped-dropout': [
+        [('die_stock_plane_batch', ()), ('die_signal_cells_batch', ()), ('die_memory_cells_batch', ()), ('die_memory_planes_batch', ()),
+         ('die_nca_wide_sense_batch_store_signal', ()), ('die_gather_scale_batch', ()), ('die_signal_step_batch', ()),
+         ('die_memory_planes_backward_batch', ())],
+        [('die_env_step_batch', ()), ('die_deposit_cells_batch', ())],
+        [('die_stock_plane_batch', ()), ('die_signal_cells_batch', ()), ('die_memory_cells_batch', ()), ('die_memory_planes_batch', ()),
+         ('die_nca_wide_sense_batch_store_signal', ()), ('die_gather_scale_batch', ()), ('die_signal_step_batch', ()),
+         ('die_memory_planes_backward_batch', ())],
+        [('die_gather_memory_backward_batch', ()), ('die_signal_step_backward_batch', ()), ('die_gather_scale_backward_batch', ()),
+         ('die_nca_wide_backward_batch_signal_workspace_bytes', ()), ('die_nca_wide_backward_batch_signal', ()),
+         ('die_memory_planes_backward_batch', ()), ('die_env_step_backward_batch', (6, 7)), ('die_gather_memory_backward_batch', ()),
+         ('die_signal_step_backward_batch', (7,)), ('die_gather_scale_backward_batch', ()),
+         ('die_nca_wide_backward_batch_signal_workspace_bytes', ()), ('die_nca_wide_backward_batch_signal', (11,))],
+    ],
+}
