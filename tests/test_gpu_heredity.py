@@ -444,13 +444,17 @@ def _layer_arrays(ag):
     return [k.weight.detach().cpu().double().numpy() for k in ag.model.conv_layers()]
 
 
-def _window(mode, a, loss='all', detach=False, T=4):
+def _window(mode, a, loss='all', detach=False, T=4, before=None, dyn=None, slots=400):
     """T links of recurrent_action, a plain env.step, inherit_memory(record, memory_next) on 24 x 24 (`detach`: the inherited
     memory is handed on detached), the loss backpropagated: the device's tensors and gradients, and what the float64 loop needs
-    to repeat them — the device's own records."""
-    W, H, N, M = 24, 24, 400, 2                                      # (more free slots than the first pass fills: later passes breed too)
-    env = die.Env((W, H), _born_dyn(init_agent_ratio=0.2), seed=3, max_agents=N, sort_every=0, device=DEV)
+    to repeat them — the device's own records.  `before`: a callable of (env, agent) run on the fresh world first
+    (tests/test_gpu_epoch_wrap.py: real steps up to the epoch wrap, under a Dynamics `dyn` and with `slots` that keep the colony breeding
+    that long)."""
+    W, H, N, M = 24, 24, slots, 2                                    # (more free slots than the first pass fills: later passes breed too)
+    env = die.Env((W, H), _born_dyn(**(dyn or dict(init_agent_ratio=0.2))), seed=3, max_agents=N, sort_every=0, device=DEV)
     ag = _agent(mode, a)
+    if before is not None:
+        before(env, ag)
     rs = np.random.RandomState(4)
     us, vs = rs.standard_normal((T, 3, N)), rs.standard_normal((T, M, N))
     mem0 = rs.standard_normal((M, N)).astype(np.float32)
@@ -551,11 +555,16 @@ def _cands(n, seed, mode, a, M=2):
     return out
 
 
-@pytest.mark.parametrize('mode,a', [('blank', 0.0), ('copy', 0.1)])
-def test_batched_bptt_across_births_matches_the_float64_loop(mode, a):
-    W, H, R, N, M, T = 24, 24, 3, 400, 2, 4
-    benv = BatchedEnv((W, H), _born_dyn(init_agent_ratio=0.2), replicas=R, seed=11, max_agents=N, device=DEV)
+def _batched_window(mode, a, T=4, before=None, dyn=None, slots=400):
+    """T links of the batched recurrent_action, step_action, inherit_memory(record, memory_next) on three 24 x 24 worlds against the
+    float64 loop fed the device's own records: (births per replica and link, errors per array, forward distance).  `before`: a
+    callable of (benv, pop) run on the fresh worlds first (tests/test_gpu_epoch_wrap.py: real steps up to the epoch wrap, under a
+    Dynamics `dyn` and with `slots` that keep the colonies breeding that long)."""
+    W, H, R, N, M = 24, 24, 3, slots, 2
+    benv = BatchedEnv((W, H), _born_dyn(**(dyn or dict(init_agent_ratio=0.2))), replicas=R, seed=11, max_agents=N, device=DEV)
     pop = BatchedNeuralAutomataAgent.from_agents(benv, _cands(R, 27, mode, a))
+    if before is not None:
+        before(benv, pop)
     Nmax = benv.Nmax
     rs = np.random.RandomState(4)
     us, vs = rs.standard_normal((T, 3, R, Nmax)), rs.standard_normal((T, R, M, Nmax))
@@ -600,6 +609,12 @@ def test_batched_bptt_across_births_matches_the_float64_loop(mode, a):
         ref.backward()
         errs += [MG.rel_err(g, w.grad.numpy()) for g, w in zip(split(got[r]), ws)] + [MG.rel_err(gm[r, :, :n], m0.grad.numpy())]
         fwd = max(fwd, MG.rel_err(pop.memory[r, :, :n].cpu().numpy(), out['memories'][-1].detach().numpy()))
+    return births, errs, fwd
+
+
+@pytest.mark.parametrize('mode,a', [('blank', 0.0), ('copy', 0.1)])
+def test_batched_bptt_across_births_matches_the_float64_loop(mode, a):
+    births, errs, fwd = _batched_window(mode, a)
     print(f'batched bptt across births 24x24 R=3 T=4 {mode} a={a}: births {births}; device worst {max(errs):.3e} of max|grad_f64| per array '
           f'(ceiling {CEILING:.0e}); forward apart by {fwd:.2e}')
     assert fwd <= 1e-5

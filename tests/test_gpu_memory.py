@@ -275,11 +275,11 @@ def _run_alone(env, ag, steps):
     return np.array(rew), np.array(alive)
 
 
-def _candidates(n, seed, M=2, **kw):
+def _candidates(n, seed, M=2, scale=0.01, **kw):
     torch.manual_seed(seed)
     out = []
     for _ in range(n):
-        ag = die.NeuralAutomataAgent(scale=0.01, deposit=2.0, memory_channels=M, **kw)
+        ag = die.NeuralAutomataAgent(scale=scale, deposit=2.0, memory_channels=M, **kw)
         ag.model.init_weights()
         out.append(ag)
     return out

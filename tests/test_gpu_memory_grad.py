@@ -198,10 +198,10 @@ def test_gather_memory_backward_against_the_model(kind, Mc):
 
 
 # ---------------------------------------------------------------------------------------------------- the agents and worlds
-def _agent(seed=0, p=0.0, dropout_seed=None, with_agent_channel=True, **kw):
+def _agent(seed=0, p=0.0, dropout_seed=None, with_agent_channel=True, scale=F.COEFS[0], **kw):
     torch.manual_seed(seed)
     kw.setdefault('memory_channels', 2)
-    ag = die.NeuralAutomataAgent(kernel_sizes=(3, 3), hidden_channels=8, hidden_activation='tanh', scale=F.COEFS[0], deposit=F.COEFS[2],
+    ag = die.NeuralAutomataAgent(kernel_sizes=(3, 3), hidden_channels=8, hidden_activation='tanh', scale=scale, deposit=F.COEFS[2],
                                  p_agent_dropout=p, dropout_seed=dropout_seed, with_agent_channel=with_agent_channel, **kw)
     with torch.no_grad():
         for q in ag.model.parameters():
@@ -280,15 +280,18 @@ def _errors(got, ref):
 @pytest.mark.parametrize('with_agents', [True, False], ids=['agents channel', 'no agents channel'])
 @pytest.mark.parametrize('seeded', [False, True], ids=['no mask', 'seeded mask'])
 @pytest.mark.parametrize('W,H', [(13, 10), (24, 68)])
-def test_recurrent_action_is_forward_bit_for_bit(W, H, seeded, with_agents):
-    """13 x 10: H % 4 != 0, the expand's scalar path; 24 x 68: H % 4 == 0, past the wide layer's 16 x 64 tile in both axes."""
+def test_recurrent_action_is_forward_bit_for_bit(W, H, seeded, with_agents, links=3, before=None):
+    """13 x 10: H % 4 != 0, the expand's scalar path; 24 x 68: H % 4 == 0, past the wide layer's 16 x 64 tile in both axes.
+    (`links`, `before` — a callable of the two fresh worlds: tests/test_gpu_epoch_wrap.py runs the same checks across the epoch wrap.)"""
     kw = dict(p=0.25, dropout_seed=5) if seeded else {}
     plain_env, diff_env = _env(W, H), _env(W, H)
     plain = _agent(with_agent_channel=with_agents, **kw)
     diff = _twin(plain, with_agent_channel=with_agents, **kw)
     _same_state(_state(plain_env), _state(diff_env))
+    if before is not None:
+        before(plain_env, diff_env)
     memory = None
-    for t in range(3):
+    for t in range(links):
         obs_p, obs_d = plain_env._get_current_obs, diff_env._get_current_obs
         act = plain.forward(obs_p)
         action, memory = diff.recurrent_action(obs_d, memory)
@@ -307,11 +310,14 @@ def test_recurrent_action_is_forward_bit_for_bit(W, H, seeded, with_agents):
 
 
 # ---------------------------------------------------------------------------------------------------- 5. – 7. BPTT
-def _bptt(seeded, loss_on_memory=True, detach=False, leaf=False):
-    """Three rounds on 13 x 10 chained through memory_next, the world stepped by the detached actions between them."""
-    W, H, T = 13, 10, 3
+def _bptt(seeded, loss_on_memory=True, detach=False, leaf=False, T=3, shape=(13, 10), before=None):
+    """Three rounds on 13 x 10 chained through memory_next, the world stepped by the detached actions between them.  `before`: a
+    callable of (env, agent) run on the fresh world first (tests/test_gpu_epoch_wrap.py: real steps up to the epoch wrap)."""
+    W, H = shape
     p, seed = (0.25, 5) if seeded else (0.0, None)
     env, ag = _env(W, H), _agent(p=p, dropout_seed=seed)
+    if before is not None:
+        before(env, ag)
     N = env.agents.N
     rs = np.random.RandomState(4)
     u, v = rs.standard_normal((3, N)), rs.standard_normal((2, N))

@@ -266,15 +266,18 @@ def test_the_two_functional_ops_alone():
 
 # ---------------------------------------------------------------------------------------------------- 2. the values
 @pytest.mark.parametrize('case', list(CASES))
-def test_recurrent_action_is_the_step_and_the_stand_alone_call_bit_for_bit(case):
+def test_recurrent_action_is_the_step_and_the_stand_alone_call_bit_for_bit(case, links=3, before=None):
+    """(`links`, `before` — a callable of the two fresh batches: tests/test_gpu_epoch_wrap.py runs the same checks across the epoch wrap.)"""
     (benv_s, pop_s), (benv_d, pop_d) = _make(case), _make(case)
+    if before is not None:
+        before(benv_s, benv_d)
     R, M, Nmax = benv_s.R, pop_s._memory_channels, benv_s.Nmax
     _same_world(_world_bits(benv_s), _world_bits(benv_d))
     steps = benv_s.H % 4 == 0                                        # (the batched step takes H % 4 == 0: a 13 x 10 world stands still)
     buf = torch.zeros((3, R, Nmax), dtype=torch.float32, device=DEV)
     pop_d.parameters.requires_grad_()                                # (a graph hangs on what asks for a gradient: here the weights)
     memory = None
-    for t in range(3):
+    for t in range(links):
         mem_in = pop_d.memory.clone()
         alone = [_alone(benv_d, pop_d, r) for r in range(R)]
         action, memory = pop_d.recurrent_action(memory)
@@ -363,10 +366,13 @@ def _layer_grads(pop, row):
     return [np.asarray(row[off:off + cout * cin * k * k]).reshape(cout, cin, k, k) for k, cin, cout, off in pop._layers]
 
 
-def _unrolled(case, T=3, detach=False, leaf=True):
+def _unrolled(case, T=3, detach=False, leaf=True, before=None):
     """T rounds chained through memory_next, the worlds stepped by the detached actions between them, a loss term at every round:
-    the device's gradients and everything the float64 loop needs to repeat them."""
+    the device's gradients and everything the float64 loop needs to repeat them.  `before`: a callable of (benv, pop) run on the
+    fresh worlds first (tests/test_gpu_epoch_wrap.py: real steps up to the epoch wrap)."""
     benv, pop = _make(case)
+    if before is not None:
+        before(benv, pop)
     p = CASES[case][8]
     R, M, Nmax, E = benv.R, pop._memory_channels, benv.Nmax, pop.episodes
     rs = np.random.RandomState(4)

@@ -270,11 +270,11 @@ def test_a_hand_set_policy_follows_the_signal_and_does_not_without_it():
 
 
 # ---------------------------------------------------------------------------------------------------- 6. populations
-def _candidates(n, seed, K=2, M=0, **kw):
+def _candidates(n, seed, K=2, M=0, scale=0.01, **kw):
     torch.manual_seed(seed)
     out = []
     for _ in range(n):
-        ag = die.NeuralAutomataAgent(scale=0.01, deposit=2.0, signal_channels=K, memory_channels=M, signal_sigma=0.8, signal_decay=0.05, **kw)
+        ag = die.NeuralAutomataAgent(scale=scale, deposit=2.0, signal_channels=K, memory_channels=M, signal_sigma=0.8, signal_decay=0.05, **kw)
         ag.model.init_weights()
         out.append(ag)
     return out

@@ -252,16 +252,19 @@ def _model(ag, frames, occs, sig0, loss_of, records=None, mem0=None, world=None,
 @pytest.mark.parametrize('seeded', [False, True], ids=['no mask', 'seeded mask'])
 @pytest.mark.parametrize('M', [0, 2], ids=['no memory', 'memory'])
 @pytest.mark.parametrize('W,H', [(13, 10), (24, 68)])
-def test_signalling_action_is_forward_bit_for_bit(W, H, M, seeded):
-    """13 x 10: H % 4 != 0, the tile kernel; 24 x 68: the row kernel, past the wide layer's 16 x 64 tile in both axes."""
+def test_signalling_action_is_forward_bit_for_bit(W, H, M, seeded, links=3, before=None):
+    """13 x 10: H % 4 != 0, the tile kernel; 24 x 68: the row kernel, past the wide layer's 16 x 64 tile in both axes.
+    (`links`, `before` — a callable of the two fresh worlds: tests/test_gpu_epoch_wrap.py runs the same checks across the epoch wrap.)"""
     K = 2
     kw = dict(p=0.25, dropout_seed=5) if seeded else {}
     plain_env, diff_env = _env(W, H), _env(W, H)
     plain = _agent(K, M, **kw)
     diff = _twin(plain, K=K, M=M, **kw)
     _same_state(_state(plain_env), _state(diff_env))
+    if before is not None:
+        before(plain_env, diff_env)
     signals = memory = None
-    for t in range(3):
+    for t in range(links):
         obs_p, obs_d = plain_env._get_current_obs, diff_env._get_current_obs
         act = plain.forward(obs_p)
         action, signals, memory = diff.signalling_action(obs_d, signals, memory)
@@ -286,21 +289,28 @@ def test_signalling_action_is_forward_bit_for_bit(W, H, M, seeded):
 
 
 # ---------------------------------------------------------------------------------------------------- 5., 6. BPTT
-def _bptt(loss_on_signals=True, detach=False):
-    """Three rounds on 13 x 10 chained through signals_next from a leaf, the world stepped by the detached actions between them."""
-    W, H, T, K = 13, 10, 3, 2
-    env, ag = _crowded_env(W, H, 60, seed=21), _agent(K)
+def _bptt(loss_on_signals=True, detach=False, T=3, M=0, shape=(13, 10), before=None):
+    """Three rounds on 13 x 10 chained through signals_next from a leaf, the world stepped by the detached actions between them.
+    `M`: memory channels besides, chained from blank memory through memory_next.  `before`: a callable of (env, agent) run on the
+    fresh world first (tests/test_gpu_epoch_wrap.py: real steps up to the epoch wrap)."""
+    (W, H), K = shape, 2
+    env, ag = _crowded_env(W, H, 60 * W * H // 130, seed=21), _agent(K, M)
+    if before is not None:
+        before(env, ag)
     N = env.agents.N
     rs = np.random.RandomState(4)
     u, v = rs.standard_normal((3, N)), rs.standard_normal((K, W, H))
     sig0 = (rs.uniform(-1, 1, (K, W, H)) * (rs.rand(K, W, H) < 0.6)).astype(np.float32)
     leaf = torch.from_numpy(sig0).to(DEV).requires_grad_(True)
-    signals, frames, occs, alive = leaf, [], [], []
+    signals, frames, occs, alive, records = leaf, [], [], [], []
+    memory = torch.zeros((M, N), dtype=torch.float32, device=DEV) if M else None
     for t in range(T):
         frames.append(_frame(env, ag))
         occs.append(_occupancy(env))
+        if M:
+            records.append(_host_record(env))
         alive.append(int((env.agents.to_numpy()[2] > 0).sum()))
-        action, signals, _ = ag.signalling_action(env._get_current_obs, signals.detach() if detach and t > 0 else signals)
+        action, signals, memory = ag.signalling_action(env._get_current_obs, signals.detach() if detach and t > 0 else signals, memory)
         if t < T - 1:
             _step_with(env, action)
     assert all(n < N for n in alive)                                              # dead slots in every round …
@@ -312,7 +322,8 @@ def _bptt(loss_on_signals=True, detach=False):
     def loss_of(out, as_t):
         return (as_t(u) * out['actions'][-1]).sum() + ((as_t(v) * out['signals'][-1]).sum() if loss_on_signals else 0.)
 
-    ref_w, ref_s, out = _model(ag, frames, occs, sig0, loss_of, detach_at=range(1, T) if detach else ())
+    kw = dict(records=records, mem0=np.zeros((M, N))) if M else {}
+    ref_w, ref_s, out = _model(ag, frames, occs, sig0, loss_of, detach_at=range(1, T) if detach else (), **kw)
     return ag, _device_grads(ag), ref_w, leaf, ref_s, (action, signals, out)
 
 
@@ -343,10 +354,15 @@ def test_the_gradient_goes_through_the_field():
 
 
 # ---------------------------------------------------------------------------------------------------- 7. memory and the world
-def test_gradients_through_the_field_the_memory_and_the_world():
-    W, H, T, sigma, K, M = 16, 12, 2, 0.8, 2, 2
+def _through_the_world(T=2, before=None):
+    """T links of signalling_action + differentiable_step on 16 x 12 from a blank field and blank memory, a loss on the last chem
+    plane and the last field: (forward distance from the float64 loop, per-layer errors, the device's gradients, the loop's).
+    `before`: a callable of (env, agent) run on the fresh world first (tests/test_gpu_epoch_wrap.py)."""
+    W, H, sigma, K, M = 16, 12, 0.8, 2, 2
     env = _env(W, H, diffuse_sigma=sigma, rate_decay_chem=F.DECAY, diffuse_mode='wrap')
     ag = _agent(K, M)
+    if before is not None:
+        before(env, ag)
     N = env.agents.N
     rs = np.random.RandomState(6)
     cvec, svec = rs.standard_normal((W, H)), rs.standard_normal((K, W, H))
@@ -371,7 +387,12 @@ def test_gradients_through_the_field_the_memory_and_the_world():
     kw = dict(records=records, mem0=np.zeros((M, N)), world=dict(cells=cells, sigma=sigma, decay=F.DECAY), chem0=chem0)
     ref, _, out = _model(ag, frames, occs, np.zeros((K, W, H)), loss_of, **kw)
     fwd = max(MG.rel_err(chem_T, out['chem'].detach().numpy()), MG.rel_err(sig_T, out['signals'][-1].detach().numpy()))
-    err = _errors(got, ref)
+    return fwd, _errors(got, ref), got, ref
+
+
+def test_gradients_through_the_field_the_memory_and_the_world():
+    K = 2
+    fwd, err, got, ref = _through_the_world()
     print(f'field, memory and world 16x12 T=2: device', ' '.join(f'{e:.3e}' for e in err), f'(ceiling {CEILING:.0e}); forward apart by {fwd:.2e}')
     assert fwd <= 1e-4 and all(e <= CEILING for e in err), (fwd, err)
     assert np.abs(ref[-1][3:3 + K]).max() > 0 and MG.rel_err(got[-1][3:3 + K], ref[-1][3:3 + K]) <= CEILING

@@ -333,13 +333,16 @@ VALUES = {
 
 
 @pytest.mark.parametrize('case', list(VALUES))
-def test_signalling_action_is_the_step_and_the_stand_alone_call_bit_for_bit(case):
+def test_signalling_action_is_the_step_and_the_stand_alone_call_bit_for_bit(case, links=3, before=None):
     """24 x 68: past the wide layer's 16 x 64 tile in both axes, the row kernel.  13 x 10: H % 4 != 0, the tile kernel; no batched
-    step takes such a world, so it stands still and is compared with the stand-alone call only."""
+    step takes such a world, so it stands still and is compared with the stand-alone call only.  (`links`, `before` — a callable of
+    the two fresh batches: tests/test_gpu_epoch_wrap.py runs the same checks across the epoch wrap.)"""
     (W, H), R, E, M, seeded = VALUES[case]
     K = 2
     kw = dict(R=R, E=E, K=K, M=M, p=0.25 if seeded else 0.0, pop_kw=dict(dropout_seed=40, dropout_seed_stride=1) if seeded else {})
     (benv_s, pop_s), (benv_d, pop_d) = _make(W, H, **kw), _make(W, H, **kw)
+    if before is not None:
+        before(benv_s, benv_d)
     Nmax = benv_s.Nmax
     _same_world(_world_bits(benv_s), _world_bits(benv_d))
     assert len(set(benv_d.n)) > 1                                                 # differing n[r]: padding slots
@@ -347,7 +350,7 @@ def test_signalling_action_is_the_step_and_the_stand_alone_call_bit_for_bit(case
     buf = torch.zeros((3, R, Nmax), dtype=torch.float32, device=DEV)
     pop_d.parameters.requires_grad_()                                              # (a graph hangs on what asks for a gradient: here the weights)
     signals = memory = None
-    for t in range(3):
+    for t in range(links):
         sig_in = pop_d.signals.clone()
         mem_in = pop_d.memory.clone() if M else None
         alone = [_alone(benv_d, pop_d, r) for r in range(R)]
@@ -435,12 +438,15 @@ def _occupancies(benv, pop):
     return occ
 
 
-def _bptt(W, H, R=3, E=1, T=3, loss_on_signals=True, detach=False):
+def _bptt(W, H, R=3, E=1, T=3, loss_on_signals=True, detach=False, before=None):
     """T rounds chained through signals_next from a leaf on crowded worlds (60 slots on 13 x 10, 90 on 16 x 12); the worlds are
-    stepped by the detached actions where a batched step takes them (H % 4 == 0)."""
+    stepped by the detached actions where a batched step takes them (H % 4 == 0).  `before`: a callable of (benv, pop) run on the
+    crowded worlds first (tests/test_gpu_epoch_wrap.py: real steps up to the epoch wrap)."""
     K, N = 2, 60 if (W, H) == (13, 10) else 90
     benv, pop = _make(W, H, R=R, E=E, K=K, slots=N, dyn=dict(init_agent_ratio=0.1))
     _crowd(benv, seed=21)
+    if before is not None:
+        before(benv, pop)
     rs = np.random.RandomState(4)
     u, v = rs.standard_normal((3, R, N)), rs.standard_normal((R, K, W, H))
     sig0 = (rs.uniform(-1, 1, (R, K, W, H)) * (rs.rand(R, K, W, H) < 0.6)).astype(np.float32)
@@ -509,9 +515,15 @@ def test_the_gradient_goes_through_the_field():
 
 
 # ---------------------------------------------------------------------------------------------------- 7. memory and the worlds
-def test_gradients_through_the_field_the_memory_and_the_worlds():
-    W, H, T, sigma, K, M, R = 16, 12, 2, 0.8, 2, 2, 3
+def _through_the_worlds(T=2, before=None):
+    """T links of signalling_action + differentiable_step on three 16 x 12 worlds from blank fields and blank memory, a loss on the
+    last chem planes and the last fields, against the float64 loop: (forward distance, errors per replica and layer; the emission
+    and memory rows of every replica's last layer are held to the ceiling here).  `before`: a callable of (benv, pop) run on the
+    fresh worlds first (tests/test_gpu_epoch_wrap.py)."""
+    W, H, sigma, K, M, R = 16, 12, 0.8, 2, 2, 3
     benv, pop = _make(W, H, R=R, K=K, M=M, seed=5, dyn=dict(init_agent_ratio=0.3, diffuse_sigma=sigma, rate_decay_chem=F.DECAY, diffuse_mode='wrap'))
+    if before is not None:
+        before(benv, pop)
     pop.parameters.requires_grad_()
     rs = np.random.RandomState(6)
     cvec, svec = rs.standard_normal((R, W, H)), rs.standard_normal((R, K, W, H))
@@ -553,6 +565,11 @@ def test_gradients_through_the_field_the_memory_and_the_worlds():
         # the emission rows and the memory rows of the last layer reach this loss through the field, the memory and the world
         assert np.abs(ref[-1][3:3 + K]).max() > 0 and MG.rel_err(got[r][-1][3:3 + K], ref[-1][3:3 + K]) <= CEILING, r
         assert np.abs(ref[-1][3 + K:]).max() > 0 and MG.rel_err(got[r][-1][3 + K:], ref[-1][3 + K:]) <= CEILING, r
+    return fwd, errs
+
+
+def test_gradients_through_the_field_the_memory_and_the_worlds():
+    fwd, errs = _through_the_worlds()
     print('field, memory and worlds 16x12 T=2 R=3: device', ' '.join(f'{e:.3e}' for e in errs), f'(ceiling {CEILING:.0e}); forward apart by {fwd:.2e}')
     assert fwd <= 1e-4 and max(errs) <= CEILING, (fwd, errs)                        # (the chem plane's forward bound: tests/test_gpu_signal_grad.py test 7)
 

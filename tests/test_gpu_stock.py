@@ -431,11 +431,11 @@ def _assert_replica_is(benv, pop, r, env, ag, rew, alive, want_rew, want_alive):
     assert np.array_equal(pop.render(r), ag.render()[0]), r
 
 
-def _candidates(n, seed, **kw):
+def _candidates(n, seed, scale=0.01, **kw):
     torch.manual_seed(seed)
     out = []
     for _ in range(n):
-        ag = die.NeuralAutomataAgent(scale=0.01, deposit=2.0, with_stock_channel=True, **kw)
+        ag = die.NeuralAutomataAgent(scale=scale, deposit=2.0, with_stock_channel=True, **kw)
         ag.model.init_weights()
         out.append(ag)
     return out
