@@ -536,10 +536,27 @@ class NeuralAutomataAgent(TorchAgent):
                                           f"(sense() and forward() take all of {sorted(_lib.PAD_MODES)})")
 
     def _field_planes(self, medium) -> Dict[str, Any]:
-        """The observation channels the medium itself holds, as first-layer source planes: channel -> (tensor, DIE_PLANE_* kind)."""
+        """The observation channels the medium itself holds, as first-layer source planes: channel -> (tensor, DIE_PLANE_* kind).
+        Under `Dynamics(apply_sense_mask=True)` (`medium.sense_mask` set) the food and chem planes are masked copies, the cells
+        outside the mask zeroed (core/env.py:292-298: every agent gets `medium.where(sense_mask, 0)`) — two copies on the cold path.
+        The agents channel needs none: an occupied cell is inside the mask by its own weight (w0² ≈ 0.04 against the 0.0005 the
+        rounding keeps)."""
         medium._ensure_owner()
         fkind = _lib.DIE_PLANE_F32 if medium.dtype == th.float32 else _lib.DIE_PLANE_F16
-        return {'agents': (medium.owner, _lib.DIE_PLANE_AGENTS), 'env_food': (medium.food, fkind), 'chem1': (medium.chem, fkind)}
+        food, chem = medium.food, medium.chem
+        mask = getattr(medium, 'sense_mask', None)
+        if mask is not None:
+            seen = mask != 0
+            zero = th.zeros((), dtype=medium.dtype, device=medium.device)
+            food, chem = th.where(seen, food, zero), th.where(seen, chem, zero)
+        return {'agents': (medium.owner, _lib.DIE_PLANE_AGENTS), 'env_food': (food, fkind), 'chem1': (chem, fkind)}
+
+    @staticmethod
+    def _check_sense_mask(what: str, medium):
+        """The differentiable calls read the medium unmasked: under a sense mask they are refused before any launch, as
+        `Env._check_differentiable` refuses the step."""
+        if getattr(medium, 'sense_mask', None) is not None:
+            raise NotImplementedError(f'{what}: apply_sense_mask is not differentiable here')
 
     def _dropout(self) -> Optional[_lib.NcaDropout]:
         """die_nca_dropout of the coming call — the counter-based mask of `dropout_seed` at `dropout_step`, applied inside the last
@@ -625,7 +642,12 @@ class NeuralAutomataAgent(TorchAgent):
         layer (planes 3.. are what `forward` reads out into `memory`).  With `signal_channels=K` the stack reads `signals` (allocated
         here as zeros at the first call) and the tensor holds 3 + K + M planes: 3 .. 3 + K - 1 the emissions, then the memory's.
         The field itself is left as it is — only `forward` advances it — and the agents, where given, get their standing plane
-        built for it."""
+        built for it.
+
+        Under `Dynamics(apply_sense_mask=True)` the food and chem planes are read through `medium.sense_mask` (cells outside it
+        count as 0, as in the reference's observation).  The stock, memory and signal planes are not part of the medium and stay
+        as they are.  The differentiable entries (`differentiable_sense`, `differentiable_action`, `recurrent_action`,
+        `signalling_action`) raise NotImplementedError under a mask, before any launch."""
         self._check_wide()
         self._check_stock(medium=medium)
         self._check_memory(medium=medium)
@@ -759,6 +781,7 @@ class NeuralAutomataAgent(TorchAgent):
         self._check_differentiable('differentiable_sense')
         layers = self._model.conv_layers()
         self._check_boundary()
+        self._check_sense_mask('differentiable_sense', medium)   # (after the refusals that do not look at the medium)
         medium.sensed()
         dev = medium.device
         weights = [k.weight.to(device=dev, dtype=th.float32).contiguous() for k in layers]
@@ -783,6 +806,8 @@ class NeuralAutomataAgent(TorchAgent):
         `differentiable_sense`, and so does an agent with the stock channel."""
         self._check_differentiable('differentiable_action')
         agents, medium = obs
+        self._check_boundary()
+        self._check_sense_mask('differentiable_action', medium)
         sense = self.differentiable_sense(medium)
         self._sense_output = sense.detach()
         return _DifferentiableReadOut.apply(sense, agents, medium, self.action_coefs)
@@ -868,7 +893,7 @@ class NeuralAutomataAgent(TorchAgent):
     def _check_stateful(self, what: str, obs, signals, memory) -> None:
         """Every refusal `recurrent_action` and `signalling_action` share, in their one order, before any launch (`what`: the
         caller's name, the prefix of the texts).  On a decomposed medium the signal channels speak where the agent has them, else
-        the memory channels; a field bound to another shape speaks last."""
+        the memory channels; a field bound to another shape speaks last but one, a sense mask (NotImplementedError) last."""
         K, M = self.signal_channels, self.memory_channels
         self._check_stock(what)
         self._check_boundary(f'{what}: ')
@@ -889,6 +914,7 @@ class NeuralAutomataAgent(TorchAgent):
             if getattr(agents, 'global_slots', False):
                 raise NotImplementedError(f'memory_channels={M} on a decomposed world (die_amd/dist.py): its slots carry world ids')
         self._check_signals(medium=medium)                       # a field bound to another shape: ValueError until reset_signals()
+        self._check_sense_mask(what, medium)                     # a sense mask speaks after everything else
 
     def _stateful_action(self, what: str, obs, signals, memory):
         """The one body of `recurrent_action` (K = 0: no field, `signals_next` None) and `signalling_action`: the refusals, the
